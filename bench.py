@@ -11,6 +11,11 @@ Contract: python bench.py --gpus N --steps K --warmup W   prints ONE JSON line o
   * under torchrun (WORLD_SIZE / RANK / LOCAL_RANK in the environment) this process is one rank;
   * run plainly with --gpus N > 1 it is the LAUNCHER: it starts N rank processes of itself (before it
     has made any GPU call -- it never touches the GPU) and exits with their status.
+  * a plain run sets up, warms up, times the K steps and prints the headline line; everything measured or checked
+    beside it (re-measurements in other modes, the handle API, the CPU baseline, the parity check against the
+    oracle) runs only with --full.
+  * --dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32, rows in
+    global frame order, a fixed sample of element positions where an output is larger than 16 MiB).
 --config {1,2,3,4} selects the BASELINE.json configuration of that index (default: the per-GPU shard of
 configs[3], the one the metric is quoted on).
 """
@@ -23,6 +28,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -46,6 +52,21 @@ BASELINE_CONFIGS = {
     4: {"quote": "batch=512 7680\u00d74320 frames, 10000-coeff mark, + attack_resize 12.5% re-extract, 8\u00d7MI355X",
         "batch": 64, "width": 7680, "height": 4320, "k": 10000, "flow": "attack"},
 }
+
+
+DUMP_BYTES_PER_OUTPUT = 16 << 20     # --dump-outputs: at most four arrays of at most 16 MiB each (< 64 MiB in all)
+DUMP_SAMPLE_SEED = 20251015
+
+
+def dump_sample_positions(name: str, per_frame: int, total_frames: int):
+    """Element positions of one frame that --dump-outputs keeps of output `name` (None: all of them).  A fixed, seeded
+    sample, the same in every frame and independent of the number of ranks, sized so that total_frames rows fit in
+    DUMP_BYTES_PER_OUTPUT as float32."""
+    m = max(1, DUMP_BYTES_PER_OUTPUT // (4 * max(total_frames, 1)))
+    if m >= per_frame:
+        return None
+    rng = np.random.default_rng([DUMP_SAMPLE_SEED, zlib.crc32(name.encode())])
+    return np.sort(rng.choice(per_frame, size=m, replace=False))
 
 
 def free_port() -> int:
@@ -314,7 +335,7 @@ def family_rooflines(prec_name, stage, steps, W, H, chunk_eff, frames_per_step):
 
 
 def run_attack_resize(args, lib, L, ctx, check, dist, dev, rank, world, rgb, rgb_out, marks, marks_host,
-                      extracted, sims, B, total_frames, W, H, K, workload_tag, rank_report, dump):
+                      extracted, sims, B, total_frames, W, H, K, workload_tag, rank_report, dump, dump_outputs):
     """SURVEY 8(f) rank 1 / configs[4]: Writer::mark -> into_rgb8 -> resize to 1/8 (CatmullRom) and back
     -> Reader::extract + similarity, all on 8-bit device-resident frames (tests/attack_resize.rs)."""
     cfg = L.Config(L.ORDER_ENERGY, L.OPTION2, 0.1, L.PRECISION_F64 if args.precision == "f64" else L.PRECISION_F32)
@@ -339,6 +360,7 @@ def run_attack_resize(args, lib, L, ctx, check, dist, dev, rank, world, rgb, rgb
                                          extracted.data_ptr(), marks.data_ptr(), sims.data_ptr()), "ssw_batch_extract_rgb8")
 
     own, elapsed, stage, prune = timed_region(args, ctx, dist, step)
+    dump_outputs({"marked_rgb8": marked8, "attacked_rgb8": back8, "extracted": extracted, "similarity": sims})
     sims_host = sims.cpu().numpy()
     ext_host = extracted.cpu().numpy()
     ranks = rank_report(own)
@@ -346,7 +368,7 @@ def run_attack_resize(args, lib, L, ctx, check, dist, dev, rank, world, rgb, rgb
     chunk_eff = ctx.pass_frames(B, W, H)
     # the same step with one pass at a time on one stream: what each kernel does alone (verdict r4 #8)
     serial = None
-    if not args.no_serial_leg:
+    if args.full and not args.no_serial_leg:
         keep = args.steps
         args.steps = max(1, min(args.steps, 3))
         ctx.set_overlap(False)
@@ -389,7 +411,7 @@ def run_attack_resize(args, lib, L, ctx, check, dist, dev, rank, world, rgb, rgb
         }
         if serial is not None:
             result["serialized"] = serial
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # tests/attack_resize.rs:17-66 on frame 0 with the oracle: timed in the reference's own arithmetic class
         # (f32 FFT DCT + full stable sort), then untimed with the exact (f64) backend as the parity checker
         from oracle import oracle as O
@@ -670,7 +692,16 @@ def main():
     ap.add_argument("--no-full-transform-leg", action="store_true",
                     help="skip the re-measurement with the pruned derived transform off (the reference's 4 full transforms)")
     ap.add_argument("--dump", default=None, help="rank 0 writes the gathered per-frame sims / extracted marks here (.npz)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the timed path computed in its last step as DIR/<name>.npy (float32, < 64 MiB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the serialized, timers-off, full-transform and graph-replay "
+                         "re-measurements, --alt, the handle API, the CPU baselines and the parity check against the oracle")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (args.alt or args.cpu_all_cores) and not args.full:
+        ap.error("--alt and --cpu-all-cores are legs of --full")
 
     preset = BASELINE_CONFIGS[args.config or 3]
     for name in ("batch", "width", "height", "k"):
@@ -752,24 +783,44 @@ def main():
             raise SystemExit(f"rank {rank}: expected ranks {list(range(args.gpus))}, saw {seen}")
         return rep
 
+    def gather_frames(rows):
+        """Per-frame rows [B, ...] of every rank in global frame order, on rank 0 (None on the others)."""
+        if dist is None:
+            return rows
+        # strong scaling: shards may differ by one frame -> pad, gather, trim
+        counts = [int(c[0]) for c in dist.gather(np.array([B], dtype=np.int64))]
+        pad = np.full((max(counts),) + rows.shape[1:], np.nan, np.float32)
+        pad[:B] = rows
+        parts = [a[:c] for a, c in zip(dist.gather(pad), counts)]
+        return np.concatenate(parts) if rank == 0 else None
+
     def dump(sims_host, ext_host):
         if not args.dump:
             return
-        if dist is None:
-            all_s, all_e = [sims_host], [ext_host]
-        else:                                        # strong scaling: shards may differ by one frame -> pad, gather, trim
-            counts = [int(c[0]) for c in dist.gather(np.array([B], dtype=np.int64))]
-            top = max(counts)
-            pad_s = np.full((top,), np.nan, np.float32); pad_s[:B] = sims_host
-            pad_e = np.full((top, K), np.nan, np.float32); pad_e[:B] = ext_host
-            all_s = [a[:c] for a, c in zip(dist.gather(pad_s), counts)]
-            all_e = [a[:c] for a, c in zip(dist.gather(pad_e), counts)]
+        all_s, all_e = gather_frames(sims_host), gather_frames(ext_host)
         if rank == 0:
-            np.savez(args.dump, sims=np.concatenate(all_s), extracted=np.concatenate(all_e))
+            np.savez(args.dump, sims=all_s, extracted=all_e)
+
+    def dump_outputs(outputs):
+        """--dump-outputs: name -> the rank's device tensor [B, ...] as the timed steps left it, float32 on the host, rows of
+        every rank gathered; an output too large for DUMP_BYTES_PER_OUTPUT keeps the dump_sample_positions of each frame."""
+        if not args.dump_outputs:
+            return
+        for name, t in outputs.items():
+            rows = t.reshape(B, -1)
+            pos = dump_sample_positions(name, rows.shape[1], total_frames)
+            if pos is not None:
+                rows = rows[:, torch.from_numpy(pos).to(rows.device)]
+            host = gather_frames(rows.float().cpu().numpy())
+            if rank == 0:
+                if pos is None:
+                    host = host.reshape((total_frames,) + tuple(t.shape[1:]))
+                os.makedirs(args.dump_outputs, exist_ok=True)
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), host)
 
     if args.attack_resize:
         run_attack_resize(args, lib, L, ctx, check, dist, dev, rank, world, rgb, rgb_out, marks, marks_host,
-                          extracted, sims, B, total_frames, W, H, K, workload_tag, rank_report, dump)
+                          extracted, sims, B, total_frames, W, H, K, workload_tag, rank_report, dump, dump_outputs)
         if dist is not None:
             dist.barrier()                   # rank 0 runs the CPU baseline / parity legs before it gets here
             dist.close()
@@ -840,13 +891,15 @@ def main():
         return kernels, (roofline, roofline_hbm), {k: round(v["ms"] / steps, 3) for k, v in stage.items()}
 
     own, elapsed, stage, prune, sims_host, ext_host = measure(args.precision)
+    # the embed-only flow's timed steps compute the marked frames alone (measure()'s extraction after them is a check)
+    dump_outputs({"marked_rgb": rgb_out} if embed_only else {"marked_rgb": rgb_out, "extracted": extracted, "similarity": sims})
     kernels, (roofline, roofline_hbm), stage_ms = kernel_report(args.precision, stage, steps)
     ranks = rank_report(own)
     dump(sims_host, ext_host)
 
     # the same workload with one chunk at a time on one stream: per-kernel timings without co-running kernels
     serial = None
-    if not args.no_serial_leg:
+    if args.full and not args.no_serial_leg:
         keep = args.steps
         args.steps = max(1, min(args.steps, 5))
         s_own, s_elapsed, s_stage, _, s_sims, s_ext = measure(args.precision, overlap=False)
@@ -859,7 +912,7 @@ def main():
         args.steps = keep
 
     timers_off = None
-    if not args.no_timers_off_leg and not args.no_stage_timers:
+    if args.full and not args.no_timers_off_leg and not args.no_stage_timers:
         keep = (args.steps, args.no_stage_timers)
         args.steps, args.no_stage_timers = max(1, min(args.steps, 5)), True
         _, o_elapsed, _, _, _, _ = measure(args.precision)
@@ -871,7 +924,7 @@ def main():
     # the reference's literal unit of work: Reader::derived transforms the whole frame, 4 full
     # 2-D transforms per embed + extract -- the same step with the pruned derived transform switched off
     full = None
-    if not args.no_full_transform_leg and not embed_only:
+    if args.full and not args.no_full_transform_leg and not embed_only:
         keep = args.steps
         args.steps = max(1, min(args.steps, 5))
         ctx.set_prune(False)
@@ -894,7 +947,7 @@ def main():
     # points only enqueue, include/ssw.h stream contract) and replayed: what a caller with a fixed frame buffer gets once the
     # ~25 launches of a single-frame embed cost one graph launch.  Reported beside the eager headline, never instead of it.
     graph = None
-    if embed_only and B <= 2 and not args.no_timers_off_leg:
+    if args.full and embed_only and B <= 2 and not args.no_timers_off_leg:
         try:
             cfg_g = L.Config(L.ORDER_ENERGY, L.OPTION2, 0.1, L.PRECISION_F64 if args.precision == "f64" else L.PRECISION_F32)
             gs = torch.cuda.Stream()
@@ -987,12 +1040,12 @@ def main():
             result["alt_precision"] = alt
 
     # ---- the drop-in handle API, one host image per call (PCIe-inclusive; rank 0) -------------------
-    if rank == 0 and not args.no_handle_leg:
+    if rank == 0 and args.full and not args.no_handle_leg:
         result["handle_api"] = handle_api_leg(wm, L, lib, ctx, check, rgb[0], W, H, K, args.precision)
 
     # ---- CPU baseline: the oracle (faithful mode) on a bounded sample, on rank 0 (at N > 1 after the timed
     # region and its closing barrier: the other ranks wait in the final barrier below) -----------------
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         if alt is not None or serial is not None or timers_off is not None or full is not None:   # the headline precision's outputs again
             measure_cfg = L.Config(L.ORDER_ENERGY, L.OPTION2, 0.1,

@@ -456,9 +456,9 @@ def test_bench_strong_scaling_splits_a_fixed_batch(tmp_path):
 
 
 def test_bench_line_carries_every_leg():
-    """The default line's extra legs on a small shape: handle API (PCIe-inclusive, bit-identical to the batch entry
+    """The --full line's extra legs on a small shape: handle API (PCIe-inclusive, bit-identical to the batch entry
     points), the reference's four full transforms (prune off, bit-identical to the headline), CPU baseline and parity."""
-    j = _bench(["--gpus", "1", "--batch", "4", "--steps", "1", "--warmup", "1", "--width", "512", "--height", "288", "--k", "100",
+    j = _bench(["--full", "--gpus", "1", "--batch", "4", "--steps", "1", "--warmup", "1", "--width", "512", "--height", "288", "--k", "100",
                 "--no-alt", "--no-serial-leg", "--no-timers-off-leg"])
     h = j["handle_api"]
     assert h["bit_identical_to_batch_rgb8"] is True
@@ -487,11 +487,19 @@ def test_bench_line_carries_every_leg():
     assert 0 < j["roofline"]["best_launch"]["frac"] <= 1.0
 
 
-def test_bench_attack_line_checks_itself_against_the_oracle():
+def test_bench_attack_line_checks_itself_against_the_oracle(tmp_path):
     """`--config 4` flow (embed -> into_rgb8 -> CatmullRom 1/8 down + up -> extract, tests/attack_resize.rs:17-66) on a
-    small shape: the line carries a CPU baseline of the same flow and a parity block against the oracle."""
-    j = _bench(["--config", "4", "--gpus", "1", "--batch", "3", "--steps", "1", "--warmup", "1", "--width", "1024", "--height", "576",
-                "--k", "400"])
+    small shape: the line carries a CPU baseline of the same flow and a parity block against the oracle; --dump-outputs
+    writes the flow's four outputs."""
+    outs = tmp_path / "outs"
+    j = _bench(["--full", "--config", "4", "--gpus", "1", "--batch", "3", "--steps", "1", "--warmup", "1", "--width", "1024", "--height", "576",
+                "--k", "400", "--dump-outputs", str(outs)])
+    got = {p.name: np.load(p) for p in outs.iterdir()}
+    assert set(got) == {"marked_rgb8.npy", "attacked_rgb8.npy", "extracted.npy", "similarity.npy"}
+    m8, a8 = got["marked_rgb8.npy"], got["attacked_rgb8.npy"]        # 3 x 1.8 M values each: a sample of every frame
+    assert m8.shape == a8.shape and m8.shape[0] == 3 and m8.size * 4 <= 16 << 20 and got["extracted.npy"].shape == (3, 400)
+    assert np.array_equal(m8, np.round(m8)) and 0 <= m8.min() and m8.max() <= 255
+    assert got["similarity.npy"][0] == j["parity"]["sim_gpu"]
     assert j["cpu_baseline"]["kind"] == "port" and j["cpu_baseline"]["value"] > 0
     p = j["parity"]
     assert p["resize_down_bit_exact"] is True and p["resize_up_bit_exact"] is True
@@ -500,6 +508,30 @@ def test_bench_attack_line_checks_itself_against_the_oracle():
     assert j["roofline"]["best_launch"]["flop_per_launch"] > 0 and j["roofline"]["executed_flop_per_step"] > 0
     assert j["roofline_hbm"]["bound"] == "hbm" and 0 < j["roofline_hbm"]["frac"] <= 1.0
     assert j["config"]["chunk_frames"] == 3
+
+
+def test_bench_plain_line_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run prints the headline line alone (every other leg is --full's), and --dump-outputs writes what its timed
+    steps computed: the marked frames equal the batch entry point on the same frames and marks, the extracted marks and
+    similarities equal --dump's, and a second run with the same arguments writes the same arrays."""
+    import bench
+    w, h, k, n = 512, 288, 100, 3
+    args = ["--gpus", "1", "--batch", str(n), "--steps", "2", "--warmup", "1", "--width", str(w), "--height", str(h), "--k", str(k)]
+    first, second, npz = tmp_path / "first", tmp_path / "second", str(tmp_path / "d.npz")
+    j = _bench(args + ["--dump-outputs", str(first), "--dump", npz])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert not set(j) & {"serialized", "timers_off", "full_transform", "graph_replay", "alt_precision", "handle_api",
+                         "cpu_baseline", "cpu_baseline_select", "cpu_baseline_parallel", "parity"}
+    got = {p.name: np.load(p) for p in first.iterdir()}
+    assert set(got) == {"marked_rgb.npy", "extracted.npy", "similarity.npy"}
+    assert all(a.dtype == np.float32 for a in got.values()) and sum(p.stat().st_size for p in first.iterdir()) <= 64 << 20
+    d = np.load(npz)
+    assert np.array_equal(got["extracted.npy"], d["extracted"]) and np.array_equal(got["similarity.npy"], d["sims"])
+    marks = bench.marks_for_frames(1, 0, n, k).numpy()
+    assert np.array_equal(got["marked_rgb.npy"], G.batch_embed(G.synth(1, 0, n, w, h), marks)["rgb"])
+    _bench(args + ["--dump-outputs", str(second)])
+    for name, a in got.items():
+        assert np.array_equal(np.load(second / name), a), name
 
 
 def test_bench_under_torchrun_two_ranks(tmp_path):
@@ -559,7 +591,7 @@ def test_bench_eight_ranks_dry_run_on_one_gpu(tmp_path):
     eight, one = str(tmp_path / "eight.npz"), str(tmp_path / "one.npz")
     small = ["--steps", "1", "--warmup", "1", "--width", "512", "--height", "256", "--k", "100", "--no-alt", "--no-serial-leg",
              "--no-timers-off-leg"]
-    j8 = _bench(["--gpus", "8", "--batch", "2", "--dump", eight] + small, {"SSW_BENCH_SHARE_DEVICE": "1", "SSW_BENCH_DIST_BACKEND": "gloo"})
+    j8 = _bench(["--full", "--gpus", "8", "--batch", "2", "--dump", eight] + small, {"SSW_BENCH_SHARE_DEVICE": "1", "SSW_BENCH_DIST_BACKEND": "gloo"})
     assert j8["n_gpus"] == 8 and j8["ranks"]["ranks_seen"] == list(range(8)) and len(j8["ranks"]["mpix_per_s_per_rank"]) == 8
     assert j8["scaling"] == "weak" and j8["config"]["total_frames"] == 16 and j8["config"]["frames_per_gpu"] == 2
     assert j8["cpu_baseline"]["value"] > 0 and j8["parity"]["frames"][0]["sim_delta_vs_cpu_exact"] < 1e-4

@@ -110,3 +110,16 @@ def test_two_rank_gloo_run_equals_single_process(tmp_path):
     assert got[-1] == float(world)                            # MAX-reduce saw every rank
     single = np.array([_frame_result(7, f, w, h, k) for f in range(total)])
     assert np.array_equal(got[:-1], single)
+
+
+def test_dump_output_samples_are_fixed_and_within_budget():
+    """`bench.py --dump-outputs` keeps at most 16 MiB of float32 per output: small outputs whole, larger ones a seeded sample
+    of element positions per frame -- the same in every run and whatever the number of ranks, distinct between outputs."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_sample_positions("extracted", 1000, 256) is None
+    n = 3840 * 2160 * 3
+    p = bench.dump_sample_positions("marked_rgb", n, 256)
+    assert p.size * 256 * 4 <= bench.DUMP_BYTES_PER_OUTPUT and np.all(np.diff(p) > 0) and p[0] >= 0 and p[-1] < n
+    assert np.array_equal(p, bench.dump_sample_positions("marked_rgb", n, 256))
+    assert not np.array_equal(p, bench.dump_sample_positions("attacked_rgb8", n, 256))

@@ -15,7 +15,7 @@ echo "$COMMIT" > "$OUT/commit.txt"
 
 run_bench() {   # name, args...
     local name=$1; shift
-    python3 "$R/bench.py" "$@" > "$OUT/${TAG}_bench_${name}.json" 2> "$OUT/${TAG}_bench_${name}.err" || echo "bench $name failed" >&2
+    python3 "$R/bench.py" --full "$@" > "$OUT/${TAG}_bench_${name}.json" 2> "$OUT/${TAG}_bench_${name}.err" || echo "bench $name failed" >&2
     tail -c 300 "$OUT/${TAG}_bench_${name}.json"; echo
 }
 stats() {       # name, args...: rocprofv3 kernel trace + stats of the same command (short)
