@@ -105,7 +105,7 @@ int ssw_build_all_strategies(void);
      ROWS_DEEP / COLS_DEEP       one pre-pass per pass writes the operands of all launches (split odd halves)
      ROWS_LEVEL2 / COLS_LEVEL2   every launch of the pass sums len/16 terms (eight launches per pass)
      CLASS_MAJOR  the plane (or operand lines) between the passes in class-major order inside tiles of 128 columns
-     FUSED_COLS   r5: no f32 plane between the passes -- the row launches' epilogue writes the column operands */
+     FUSED_COLS   r5: no f32 plane between the passes -- the row launches' epilogue writes the column operands (forward only) */
 enum { SSW_PLAN_PAIR_F64 = 1, SSW_PLAN_ROWS_DEEP = 2, SSW_PLAN_COLS_DEEP = 4, SSW_PLAN_ROWS_LEVEL2 = 8, SSW_PLAN_COLS_LEVEL2 = 16,
        SSW_PLAN_CLASS_MAJOR = 32, SSW_PLAN_FUSED_COLS = 64 };
 int ssw_ctx_transform_plan(ssw_ctx* ctx, size_t n_frames, size_t w, size_t h, int dct_type, uint32_t* flags);
@@ -228,21 +228,17 @@ int ssw_ctx_set_odd_split(ssw_ctx* ctx, int enable);
      bn32 (-1)             32-pair tiles for small single-class launches: -1 automatic, 0 / 1 forced
      band_split (1)        single-image handles: row pass of the top half beside the upload of the bottom half
      fuse_cols (1)         forward transform: the row GEMMs' epilogue writes the column operands (no f32 plane between the passes)
-     fuse_inv_cols (0)     inverse transform: the same (bit-identical, 8 B/px less traffic, measured no faster: off)
      upload_bands (3)      single-image handles: bands of rows a host frame is uploaded and row-transformed in (2 .. 4)
      speculate_k (1)       Reader::base queues its selection for the mark length of the context's last extraction
      prep_light (1)        level-2 RGB row pre-pass in the < 64-VGPR form that fits beside GEMM blocks (0: the register-resident kernel)
      lane_stagger (1)      two lanes: an RGB pre-pass waits for the other lane's row launches and runs beside its column launches
      derived_fused (1)     the derived frame's pruned row pass in one kernel (0: pre-pass + gathered launches)
-     inv_prep_light (0)    inverse row pre-pass at level 2 with whole rows through LDS (bit-identical, measured no faster: off)
-     gemm_group_m (4), gemm_group_m_rows (4)   tile rows per group of the GEMM launches' block -> tile map (column / row passes)
      tile48 (1)            48-pair GEMM tiles for classes whose 64-pair tiling ends in a tile of <= 16 pairs (135 = 48 + 48 + 39)
-     merge_batch (0)       a batch pass's independent GEMM launches as one launch, class after class (r6 A/B: +1.7 % one lane, +0 two)
-     gemm_stagger (0)      r6 A/B: the second resident block of every CU starts this many 3.4-us sleeps late (measured: no effect)
    An entry never set reads its SSW_<NAME> environment variable at first use (the r4 behaviour), else the default.
    ssw_tuning_set takes effect for the calls that follow; workspaces and cached plans of existing contexts were sized
    under the old values, so change a value before creating the context that should see it (tests use a fresh context).
-   ssw_tuning_reset(NULL) returns every entry to environment / default.  Unknown name: SSW_ERR_BAD_ARG. */
+   ssw_tuning_reset(NULL) returns every entry to environment / default.  Unknown name: SSW_ERR_BAD_ARG.
+   Switches removed after measuring no gain are unknown names, and their SSW_* variables are ignored. */
 int ssw_tuning_set(const char* name, long long value);
 int ssw_tuning_get(const char* name, long long* value);
 int ssw_tuning_reset(const char* name);

@@ -41,27 +41,12 @@
 #include <cstdlib>
 #include <type_traits>
 
-#ifndef SSW_GEMM_DMA
-#define SSW_GEMM_DMA 1
-#endif
-// (the host pass never generates code for a kernel body, but it does check it: the LDS-DMA builtins and the s_waitcnt statements
-// made it drop the kernels' launch stubs without a word -- the host sees the register-staged body)
-#ifndef SSW_RGB_NB
-#define SSW_RGB_NB 2           // output rows whose I / Q quads the RGB epilogue keeps in flight together (4: a spill in the loop at 256 VGPRs)
-#endif
-#ifndef SSW_GEMM_NS
-#define SSW_GEMM_NS 2          // stages of the ring.  2: 48 KB of LDS per block, like the register-staged kernel, one k-step ahead; 3: 72 KB, two ahead -- measured equal (r6: rows 56.2-56.9 vs 56.4-56.5 ms, columns 43.5-43.7 vs 43.5-43.9 per 256 4K frames), so the smaller one
-#endif
-#if SSW_GEMM_DMA && defined(__HIP_DEVICE_COMPILE__)
-#define SSW_GEMM_DMA_DEV 1
-#else
-#define SSW_GEMM_DMA_DEV 0
-#endif
 
 namespace ssw {
 
 constexpr int PT = 256;
 constexpr int PBK = 8;
+constexpr int RGB_NB = 2;      // output rows whose I / Q quads the RGB epilogue keeps in flight together (4: a spill in the loop at 256 VGPRs)
 
 #ifdef SSW_TILE_TRACE
 // diagnostic build only (tools/tile_trace.py): the trace globals are defined by dct_pair_f64.hip before this header
@@ -98,39 +83,26 @@ struct PairClassArgs {
 struct PairMulti {
     PairClassArgs c[8];
     unsigned n_classes, L, tiles_m, tiles_n_total;
-    // r6: a batch pass's classes in ONE launch, class after class (cls_major): class c owns the blocks [cbase[c], cbase[c + 1]) --
-    // whole multiples of 8, so that a block's XCD is the one its class-local number says; the surplus blocks return at once --
-    // and walks its tiles like a launch of its own.  The next class's blocks start where the previous one's last blocks retire:
-    // no drained chip between the eight launches of a pass.  (Single frames keep their classes' tile columns side by side.)
-    unsigned cls_major = 0, cbase[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned group_m = 4;              // tile rows per group of the block -> tile map (tile_of_block; tuning: gemm_group_m)
-    unsigned stagger = 0;              // r6 A/B (tuning: gemm_stagger): blocks 256 .. 511 sleep this many x 8128 cycles before their tile
     PairOut po;                        // the fields the classes share; c1 .. bn32 are overwritten per class
 };
 
 template <bool COLS, int EPI, bool SAMEX, int SUB = 0, int BM = 128>
 __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml, Epilogue ep) {
+// (the host pass never generates code for a kernel body, but it does check it: the LDS-DMA builtins and the s_waitcnt statements
+// made it drop the kernels' launch stubs without a word -- it sees an empty body)
+#if defined(__HIP_DEVICE_COMPILE__)
     constexpr int NX = SAMEX ? 1 : 2;
     constexpr int BN = 64, XQ = BM / 64;                                   // XQ: X lines per staging thread
-    // operand tiles [buffer][product][rows * 8]; a column pass reuses the region to transpose its results (epilogue)
-#if SSW_GEMM_DMA_DEV
-    // r6: the tiles arrive by LDS-DMA (buffer_load ... lds) in a ring of NS stages [X1 | X2 | Y1 | Y2], two k-steps ahead of the MFMAs
-    constexpr int NS = SSW_GEMM_NS;
+    // r6: the operand tiles arrive by LDS-DMA (buffer_load ... lds) in a ring of two stages [X1 | X2 | Y1 | Y2], one k-step ahead
+    // of the MFMAs; a column pass reuses the region to transpose its results (epilogue)
     constexpr int STG = NX * BM * PBK + 2 * BN * PBK;                      // doubles per stage
-    constexpr int SXD = NS * STG, SYD = 0;
-#else
-    constexpr int SXD = 2 * NX * BM * PBK, SYD = 2 * 2 * BN * PBK;
-#endif
+    constexpr int SXD = 2 * STG;
     constexpr int TRD = COLS ? 4 * 32 * (BM / 2 + 16) / 2 : 0;              // 4 waves x 32 result rows x pitch floats
 #ifdef SSW_TILE_TRACE
-    __shared__ __attribute__((aligned(16))) double lds[(SXD + SYD > TRD ? SXD + SYD : TRD) + 16];
-    unsigned* kst_lds = reinterpret_cast<unsigned*>(lds + (SXD + SYD > TRD ? SXD + SYD : TRD));
+    __shared__ __attribute__((aligned(16))) double lds[(SXD > TRD ? SXD : TRD) + 16];
+    unsigned* kst_lds = reinterpret_cast<unsigned*>(lds + (SXD > TRD ? SXD : TRD));
 #else
-    __shared__ __attribute__((aligned(16))) double lds[SXD + SYD > TRD ? SXD + SYD : TRD];
-#endif
-#if !SSW_GEMM_DMA_DEV
-    double (*sX)[NX][BM * PBK] = reinterpret_cast<double (*)[NX][BM * PBK]>(lds);
-    double (*sY)[2][BN * PBK] = reinterpret_cast<double (*)[2][BN * PBK]>(lds + SXD);
+    __shared__ __attribute__((aligned(16))) double lds[SXD > TRD ? SXD : TRD];
 #endif
 
 #ifdef SSW_TILE_TRACE
@@ -139,22 +111,10 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
     unsigned kslot = 0xFFFFFFFFu;
     if (threadIdx.x == 0 && g_tile_trace) kslot = atomicAdd(&g_tile_trace_n, 1u);
 #endif
-    // the two blocks of a CU that start a launch together keep meeting in their epilogues (their phase difference is
-    // preserved from tile to tile); a launch-time offset for the second residents lets one block's epilogue and prologue run
-    // under the other's main loop
-    if (ml.stagger && blockIdx.x >= 256u && blockIdx.x < 512u)
-        for (unsigned i = 0; i < ml.stagger; ++i) __builtin_amdgcn_s_sleep(127);
     SSW_TT(0);
     unsigned tm, tn, cls = 0;
-    if (ml.cls_major) {
-        while (cls + 1 < ml.n_classes && blockIdx.x >= ml.cbase[cls + 1]) ++cls;                        // block-uniform
-        const unsigned lid = blockIdx.x - ml.cbase[cls], nb = ml.tiles_m * ml.c[cls].tiles_n;
-        if (lid >= nb) return;
-        tile_of_block(lid, nb, ml.tiles_m, ml.c[cls].tiles_n, tm, tn, ml.group_m);
-    } else {
-        tile_of_block(blockIdx.x, gridDim.x, ml.tiles_m, ml.tiles_n_total, tm, tn, ml.group_m);
-        while (cls + 1 < ml.n_classes && tn >= ml.c[cls].tiles_n) { tn -= ml.c[cls].tiles_n; ++cls; }  // block-uniform
-    }
+    tile_of_block(blockIdx.x, gridDim.x, ml.tiles_m, ml.tiles_n_total, tm, tn);
+    while (cls + 1 < ml.n_classes && tn >= ml.c[cls].tiles_n) { tn -= ml.c[cls].tiles_n; ++cls; }      // block-uniform
     const PairClassArgs& ca = ml.c[cls];
     const double* __restrict__ X1g = ca.x1;
     const double* __restrict__ X2g = ca.x2;
@@ -169,7 +129,6 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
     const unsigned lane = tid & 63, wave = tid >> 6;
     const unsigned li = lane & 15, lq = lane >> 4;
 
-#if SSW_GEMM_DMA_DEV
     // LDS tile rows hold 8 consecutive k (64 bytes) as four 16-byte chunks; chunk c of row r sits at position c ^ ((r >> 2) & 3):
     // a wave's DMA instruction fills 16 consecutive rows (1 KB, lane l -> row l / 4, position l % 4: the LDS side of an LDS-DMA
     // is lane-linear, the swizzle is applied to the lane's SOURCE address), and the fragment reads (ds_read_b64: 16 rows x one
@@ -182,7 +141,7 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
         // (column pass behind a fused row pass: the tile's lines are in class-major order, row j of the tile is line
         // fwd_cm128_pos(j) -- a permutation inside the same contiguous 8 KB of a k-step, whole 128-line tiles only)
         const unsigned j = drow + 64 * q;
-        unsigned r = m0 + ((COLS && BM == 128 && po.xperm) ? (po.xperm == 2 ? inverse_class_pos(j, 128, 128, true) : fwd_cm128_pos(j)) : j);
+        unsigned r = m0 + ((COLS && BM == 128 && po.xperm) ? fwd_cm128_pos(j) : j);
         r = r < L ? r : L - 1;
         xoff[q] = (r - m0) * 64u + 16u * (dch ^ ((j >> 2) & 3u));
     }
@@ -216,72 +175,11 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
         __builtin_amdgcn_raw_ptr_buffer_load_lds(y1r, (lds_ptr_t)(b + NX * BM * PBK), 16, yoff, yadv, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(y2r, (lds_ptr_t)(b + NX * BM * PBK + BN * PBK), 16, yoff, yadv, 0, 0);
     };
-#else
-    // LDS tile rows hold 8 consecutive k (64 bytes); double k of row r sits at position
-    // k ^ ((r >> 1) & 7): conflict-free for the ds_read_b64 / ds_read2_b64 fragment reads (16 lanes
-    // cover a 128-byte bank window exactly) and for the staging ds_write_b64.
-    // staging: line = tid / 4 (+ 64 q), k-pair = tid % 4
-    const unsigned srow = tid >> 2, sc = tid & 3;
-    const unsigned ssw = (srow >> 1) & 7;
-    unsigned xoff[XQ];
-#pragma unroll
-    for (int q = 0; q < XQ; ++q) {
-        // (column pass behind a fused row pass: the tile's lines are in class-major order, row j of the tile is line
-        // fwd_cm128_pos(j) -- a permutation inside the same contiguous 8 KB of a k-step, whole 128-line tiles only)
-        const unsigned j = srow + 64 * q;
-        unsigned r = m0 + ((COLS && BM == 128 && po.xperm) ? (po.xperm == 2 ? inverse_class_pos(j, 128, 128, true) : fwd_cm128_pos(j)) : j);
-        r = r < L ? r : L - 1;
-        xoff[q] = ((r - m0) * 8 + 2 * sc) * 8u;
-    }
-    unsigned yr = p0 + srow;
-    yr = yr < NP ? yr : NP - 1;
-    const unsigned yoff = ((yr - p0) * 8 + 2 * sc) * 8u;
-    // block-uniform buffer resources (scalar registers) at the tile's first line of k-block 0; a k-step
-    // advances a scalar byte offset by one k-block (< 4 GB: checked by the launcher)
-#ifdef SSW_ABL_X0          // timing-only ablation: every block stages the lines of tile 0 (L2-resident): what the operands' memory latency costs
-    const size_t m0x = 0;
-#else
-    const size_t m0x = m0;
-#endif
-    const __amdgpu_buffer_rsrc_t x1r = __builtin_amdgcn_make_buffer_rsrc((void*)(X1g + m0x * 8), 0, 0xFFFFFFFFu, 0x00020000);
-    const __amdgpu_buffer_rsrc_t x2r = __builtin_amdgcn_make_buffer_rsrc((void*)(X2g + m0x * 8), 0, 0xFFFFFFFFu, 0x00020000);
-    const __amdgpu_buffer_rsrc_t y1r = __builtin_amdgcn_make_buffer_rsrc((void*)(Y1g + (size_t)p0 * 8), 0, 0xFFFFFFFFu, 0x00020000);
-    const __amdgpu_buffer_rsrc_t y2r = __builtin_amdgcn_make_buffer_rsrc((void*)(Y2g + (size_t)p0 * 8), 0, 0xFFFFFFFFu, 0x00020000);
-    const unsigned xstep = L * 64u, ystep = yrows * 64u;
-
-    u32x4 rx1[XQ], rx2[XQ], ry1, ry2;
-    auto gload = [&](unsigned t) {
-        const unsigned xadv = t * xstep, yadv = t * ystep;
-#pragma unroll
-        for (int q = 0; q < XQ; ++q) {
-            rx1[q] = __builtin_amdgcn_raw_buffer_load_b128(x1r, xoff[q], xadv, 0);
-            if (!SAMEX) rx2[q] = __builtin_amdgcn_raw_buffer_load_b128(x2r, xoff[q], xadv, 0);
-        }
-        ry1 = __builtin_amdgcn_raw_buffer_load_b128(y1r, yoff, yadv, 0);
-        ry2 = __builtin_amdgcn_raw_buffer_load_b128(y2r, yoff, yadv, 0);
-    };
-    const unsigned st0 = srow * PBK + ((2 * sc) ^ ssw), st1 = srow * PBK + ((2 * sc + 1) ^ ssw);
-    auto put = [&](double* tile, const u32x4& v) {
-        *reinterpret_cast<u32x2*>(tile + st0) = (u32x2){v[0], v[1]};
-        *reinterpret_cast<u32x2*>(tile + st1) = (u32x2){v[2], v[3]};
-    };
-    auto lstore = [&](auto bufc) {
-        constexpr int buf = decltype(bufc)::value;
-#pragma unroll
-        for (int q = 0; q < XQ; ++q) {
-            put(&sX[buf][0][64 * q * PBK], rx1[q]);
-            if (!SAMEX) put(&sX[buf][NX - 1][64 * q * PBK], rx2[q]);
-        }
-        put(&sY[buf][0][0], ry1);
-        put(&sY[buf][1][0], ry2);
-    };
-#endif
     // The wave grid is 2 x 2 (each wave BM/2 lines x 32 pairs: NI = BM/32 line tiles) unless the tile holds at
     // most 32 valid pairs -- the last tile column of e.g. 540 pairs -- where it is 4 x 1 (each wave
     // BM/4 lines x 32 pairs: NI = BM/64) and the tile takes half the MFMAs instead of computing padding.
-    auto run = [&](auto nic, auto njc, auto oddc) {
+    auto run = [&](auto nic, auto njc) {
     constexpr int NI = decltype(nic)::value;
-    constexpr bool ODD = decltype(oddc)::value;              // odd number of k-steps (K = 135 -> 136 at 4K columns, 120 at 1080p rows)
     constexpr int NJ = decltype(njc)::value;                 // pair tiles of 16 per wave: 2; 1 / 3 (4 x 1 grid) when the tile holds <= 16 / 33 .. 48 valid pairs
     constexpr int NJA = NJ < 2 ? 2 : NJ;
     constexpr bool FULL = NI == BM / 32;
@@ -292,7 +190,6 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
 #pragma unroll
         for (int j = 0; j < NJA; ++j) { acc1[i][j] = (f64x4){0, 0, 0, 0}; acc2[i][j] = (f64x4){0, 0, 0, 0}; }
 
-#if SSW_GEMM_DMA_DEV
     // fragment of half-step s: lane group lq supplies k = 4 s + lq, i.e. half lq & 1 of chunk 2 s + lq / 2 (position: chunk ^ swizzle
     // of the row; wm, wn and the 16-row tile offsets are multiples of 16, so the swizzle depends on li alone)
     const unsigned fsw = (li >> 2) & 3;
@@ -334,7 +231,6 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
     };
     using B0 = std::integral_constant<int, 0>;
     using B1 = std::integral_constant<int, 1>;
-    (void)ODD;
     // One LDS read behind each of the first MFMAs of a half-step, then (second half) one DMA instruction behind each of the next
     auto interleave = [&](auto dmac) {
         constexpr int NDMA = decltype(dmac)::value;
@@ -353,191 +249,42 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
         __builtin_amdgcn_sched_group_barrier(0x008, NMF - NRD - NDMA > 0 ? NMF - NRD - NDMA : 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     };
-    // The ring.  Stage t % 3 holds k-step t; the barrier in the middle of step t is passed when every wave's DMA of stage t + 1 has
-    // landed (each wave waits for its own: vmcnt counts them in order, the stage behind stays in flight) and when every wave has
-    // its last fragments of stage t in registers (lgkmcnt(0)): stage t is refilled with k-step t + 3 right behind the barrier, two
-    // k-steps before its first read.  A raw s_barrier: __syncthreads() would wait for vmcnt(0) and drain the ring.
+    // The ring.  Stage t % 2 holds k-step t; the barrier in the middle of step t is passed when every wave's DMA of stage t + 1 has
+    // landed (each wave waits for its own: vmcnt(0), nothing else is in flight then) and when every wave has its last fragments
+    // of stage t in registers (lgkmcnt(0)): stage t is refilled with k-step t + 2 right behind the barrier, one k-step before its
+    // first read, while the MFMAs of stage t + 1 run.
     const unsigned nk = Kp / PBK;          // >= 2
     Frag fa, fb;
-    static_assert(NS == 2 || NS == 3, "ring of two or three stages");
     issue(0, 0);
     issue(1, STG);
-    if (NS == 3 && nk > 2) {
-        issue(2, 2 * STG);
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * LPT) : "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(LPT) : "memory");
-    }
+    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(LPT) : "memory");
     asm volatile("s_barrier" ::: "memory");
     SSW_TT(1);
     fread(0u, B0{}, fa);
     unsigned cur = 0, nxt = STG, t = 0;
-    // one k-step: second half-step of stage `cur`, the barrier, first half-step of stage `nxt`.  ISSUE: k-step t + NS exists and is
-    // requested into stage `cur`; VM: DMA instructions of this wave that may stay in flight at the barrier (the stages behind nxt)
-    auto step = [&](auto issuec, auto vmc) {
+    // one k-step: second half-step of stage `cur`, the barrier, first half-step of stage `nxt`.  ISSUE: k-step t + 2 exists and is
+    // requested into stage `cur`
+    auto step = [&](auto issuec) {
         constexpr bool ISSUE = decltype(issuec)::value != 0;
-        constexpr int VM = decltype(vmc)::value;
         fread(cur, B1{}, fb);
         fmma(fa);
         interleave(B0{});
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(VM) : "memory");
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         SSW_KT(t);
         fread(nxt, B0{}, fa);
-        if (ISSUE) issue(t + NS, cur);         // (behind the reads in program order: LDS accesses keep theirs, so the DMA instructions can then go one per MFMA)
+        if (ISSUE) issue(t + 2, cur);          // (behind the reads in program order: LDS accesses keep theirs, so the DMA instructions can then go one per MFMA)
         fmma(fb);
         interleave(std::integral_constant<int, ISSUE ? LPT : 0>{});
         cur = nxt;
-        nxt = nxt + STG == NS * STG ? 0u : nxt + STG;
+        nxt = nxt + STG == 2 * STG ? 0u : nxt + STG;
         ++t;
     };
-    while (t + NS < nk) step(B1{}, std::integral_constant<int, (NS - 2) * LPT>{});
-    if (NS == 3 && t + 2 < nk) step(B0{}, std::integral_constant<int, LPT>{});          // k-step nk - 3: stage nk - 1 stays in flight
-    if (t + 1 < nk) step(B0{}, B0{});                                         // k-step nk - 2: the last stage must have landed
+    while (t + 2 < nk) step(B1{});
+    if (t + 1 < nk) step(B0{});                // k-step nk - 2: the last stage must have landed
     fread(cur, B1{}, fb);
     fmma(fa);
     interleave(B0{});
     fmma(fb);
-#else
-    // fragment of half-step s: lane group lq supplies k = 4 s + lq
-    const unsigned fsw = (li >> 1) & 7;
-    unsigned rdx[2], rdy[2];
-#pragma unroll
-    for (int sh = 0; sh < 2; ++sh) {
-        rdx[sh] = (wm + li) * PBK + ((4 * sh + lq) ^ fsw);
-        rdy[sh] = (wn + li) * PBK + ((4 * sh + lq) ^ fsw);
-    }
-    struct Frag { double x1[NI], x2[NI], y1[NJA], y2[NJA]; };
-    auto fread = [&](auto bufc, auto shc, Frag& f) {
-        constexpr int cur = decltype(bufc)::value;
-        constexpr int sh = decltype(shc)::value;
-#pragma unroll
-        for (int jn = 0; jn < NJ; ++jn) {
-            f.y1[jn] = sY[cur][0][rdy[sh] + 16 * jn * PBK];
-            f.y2[jn] = sY[cur][1][rdy[sh] + 16 * jn * PBK];
-        }
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            f.x1[i] = sX[cur][0][rdx[sh] + 16 * i * PBK];
-            if (!SAMEX) f.x2[i] = sX[cur][NX - 1][rdx[sh] + 16 * i * PBK];
-        }
-    };
-    auto fmma = [&](const Frag& f) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int jn = 0; jn < NJ; ++jn) {
-                const double xb = SAMEX ? f.x1[i] : f.x2[i];
-                if (!COLS) {      // D[row = line][col = pair]
-                    acc1[i][jn] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.x1[i], f.y1[jn], acc1[i][jn], 0, 0, 0);
-                    acc2[i][jn] = __builtin_amdgcn_mfma_f64_16x16x4f64(xb, f.y2[jn], acc2[i][jn], 0, 0, 0);
-                } else {          // D[row = pair][col = line]: image columns along the lanes
-                    acc1[i][jn] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.y1[jn], f.x1[i], acc1[i][jn], 0, 0, 0);
-                    acc2[i][jn] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.y2[jn], xb, acc2[i][jn], 0, 0, 0);
-                }
-            }
-    };
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
-
-    // Software pipeline, shifted by half a k-step: the fragments of a half-step are read from LDS
-    // while the MFMAs of the previous half-step run; the tile of step t+1 is written (and the
-    // barrier taken) in the middle of step t, its global loads having been issued a step earlier.
-    const unsigned nk = Kp / PBK;          // >= 2 (Kp: a multiple of 8, at least 16); ODD: nk is odd, >= 3
-    Frag fa, fb;
-    // k-steps 0 and 1 are requested together (one memory latency at the start of a tile, not two): step 1
-    // waits in registers that the fragments will use later
-    gload(1);
-    u32x4 nx1[XQ], nx2[XQ];
-#pragma unroll
-    for (int q = 0; q < XQ; ++q) { nx1[q] = rx1[q]; if (!SAMEX) nx2[q] = rx2[q]; }
-    const u32x4 ny1 = ry1, ny2 = ry2;
-    gload(0);
-    lstore(B0{});
-    __syncthreads();
-    SSW_TT(1);
-#pragma unroll
-    for (int q = 0; q < XQ; ++q) { rx1[q] = nx1[q]; if (!SAMEX) rx2[q] = nx2[q]; }
-    ry1 = ny1; ry2 = ny2;
-    fread(B0{}, B0{}, fa);
-    // full step t on buffer CUR: needs t + 2 < nk
-    // one LDS read behind each of the first MFMAs of a half-step (a burst of reads would stall the
-    // wave at the LDS queue with its MFMAs behind it), then the staging writes two per MFMA
-    auto interleave = [&](auto storec) {
-        constexpr bool STORE = decltype(storec)::value != 0;
-        constexpr int NMF = 2 * NJ * NI;                        // MFMAs per half-step
-        constexpr int NRD = (2 * NJ + NI * NX + 1) / 2;         // ds_read2_b64 per half-step (fragments pair up)
-#pragma unroll
-        for (int i = 0; i < NRD; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        if (STORE) {
-            constexpr int NLD = XQ * NX + 2;                    // staged 16-byte loads per thread (2 LDS writes each)
-#pragma unroll
-            for (int i = 0; i < NLD; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, NMF - NRD - NLD > 0 ? NMF - NRD - NLD : 0, 0);
-            __builtin_amdgcn_sched_group_barrier(0x020, NLD, 0);
-        } else {
-            __builtin_amdgcn_sched_group_barrier(0x008, NMF - NRD, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto step = [&](auto curc, auto nxtc, unsigned t) {
-        fread(curc, B1{}, fb);
-        fmma(fa);
-        lstore(nxtc);                          // loaded a whole step ago
-        gload(t + 2);
-        interleave(B1{});
-        __syncthreads();
-        SSW_KT(t);
-        fread(nxtc, B0{}, fa);
-        fmma(fb);
-        interleave(B0{});
-    };
-    unsigned t = 0;
-    if constexpr (!ODD) {
-        for (; t + 2 < nk; t += 2) {
-            step(B0{}, B1{}, t);
-            step(B1{}, B0{}, t + 1);
-        }
-        // steps nk - 2 (buffer 0) and nk - 1 (buffer 1)
-        fread(B0{}, B1{}, fb);
-        fmma(fa);
-        interleave(B0{});
-        lstore(B1{});
-        __syncthreads();
-        fread(B1{}, B0{}, fa);
-        fmma(fb);
-        interleave(B0{});
-        fread(B1{}, B1{}, fb);
-        fmma(fa);
-        interleave(B0{});
-        fmma(fb);
-    } else {
-        // the same pipeline for an odd count: pairs of steps while the second one's request (step t + 3) exists, one more
-        // step on buffer 0, then the last two steps on buffers 1 and 0
-        for (; t + 3 < nk; t += 2) {
-            step(B0{}, B1{}, t);
-            step(B1{}, B0{}, t + 1);
-        }
-        step(B0{}, B1{}, t);                   // t = nk - 3: requests step nk - 1
-        fread(B1{}, B1{}, fb);
-        fmma(fa);
-        interleave(B0{});
-        lstore(B0{});
-        __syncthreads();
-        fread(B0{}, B0{}, fa);
-        fmma(fb);
-        interleave(B0{});
-        fread(B0{}, B1{}, fb);
-        fmma(fa);
-        interleave(B0{});
-        fmma(fb);
-    }
-#endif
     SSW_TT(2);
 #ifdef SSW_ABL_NOEPI       // timing-only ablation: no epilogue (one store keeps the accumulators alive)
     if (acc1[0][0][0] + acc2[NI - 1][NJ - 1][3] == 1.2345e300) po.out[0] = 1.f;
@@ -777,141 +524,6 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
                     const f64x2 v = *reinterpret_cast<const f64x2*>(slab + a * NLT * 8 + st_lds[j]);
                     // (non-temporal stores here: measured, no change in time or in FETCH_SIZE)
                     *reinterpret_cast<f64x2*>(po.cop + (size_t)(4 * rnd + a) * pstride + st_off[j]) = v;
-                }
-            }
-        }
-        trace_end();
-        return;
-    }
-    // r5: the last launches of an inverse row pass, fused with the inverse column pre-pass (EPI_INV_O_COLOP).  As above with
-    // four output positions per pair: sweep 0 takes the positions n1 / n2 ("+": E + a), sweep 1 their mirrors ("-": E - a);
-    // per sweep a wave has 32 NJ items.  The inverse column fold is block diagonal (planes 0 .. 7 from lines 0 .. 7 of a unit,
-    // planes 8 .. 15 from lines 8 .. 15): a lane holds eight planes of two units at a time and stores 16 bytes per plane.
-    // LDS: [unit of the pair][item][16 lines] floats, the four quads of an item XOR-swizzled by (item / 4) & 3 -- conflict-
-    // free for the ds_write_b32 of a lane group (16 items x one line) and the ds_read_b128 of 16 items alike.
-    if constexpr (!COLS && EPI == EPI_INV_O_COLOP) {
-        constexpr int NIT = 32 * NJ, NC = (NIT + 63) / 64;
-        static_assert(4 * 2 * NIT * 16 * 4 <= (int)sizeof(lds), "transpose area");
-        static_assert(BM == 128 && NI % 2 == 0, "a tile is one k-block of eight units");
-        __syncthreads();
-        float* tw = reinterpret_cast<float*>(lds) + wave * (2 * NIT * 16);
-        auto lds_order = [&]() {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        };
-        const unsigned Hc = po.H, HU = Hc / 16;
-        const unsigned tpf = po.cop_hup / 8;
-        const unsigned z = tm / tpf, g = tm - z * tpf;
-        const unsigned u0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(wm / 16));
-        const unsigned swm = __builtin_amdgcn_readfirstlane(wm);
-        const bool plain = ep.first == 1.0f && ep.base == 1.0f;
-        constexpr unsigned OOB = 0x80000000u;
-        const unsigned rows_valid = L - m0 < (unsigned)BM ? L - m0 : (unsigned)BM;
-        const unsigned eregion = rows_valid * (n / 2) * 8u;                  // this tile's lines of the E plane (n/2 doubles each)
-        const __amdgpu_buffer_rsrc_t trr = __builtin_amdgcn_make_buffer_rsrc((void*)(po.tmp + (size_t)m0 * (n / 2)), 0, eregion, 0x00020000);
-        // E of this lane's positions (read as doubles, like EPI_INV_O): lane offsets once per tile, rows through the scalar offset.
-        // Each sweep reads its units' E values again (the second time from L2) rather than keeping 128 more results in registers.
-        unsigned vt[NJ][2];
-        float fp[NJ][2];
-#pragma unroll
-        for (int jn = 0; jn < NJ; ++jn) {
-            const unsigned pair = p0 + wn + 16 * jn + li;
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                const unsigned nn = h2 ? po.c2 + po.cs * p2(pair) : po.c1 + po.cs * pair;
-                const bool ok = pair < NP && nn < n / 2;
-                vt[jn][h2] = ok ? (lq * (n / 2) + opos(nn, n / 2)) * 8u : OOB;
-                fp[jn][h2] = nn == 0 ? ep.first : ep.base;
-            }
-        }
-        const size_t pstride = (size_t)po.cop_lines * po.cop_k16;
-        // LDS position of line v of item f: quad (v / 4) ^ ((f / 4) & 3)
-        auto lpos = [&](unsigned f, unsigned v) { return f * 16u + 4u * ((v >> 2) ^ ((f >> 2) & 3u)) + (v & 3u); };
-#pragma unroll
-        for (int sweep = 0; sweep < 2; ++sweep) {
-            bool it_ok[NC];
-            size_t it_line[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const unsigned f = lane + 64 * c;
-                const unsigned pair = p0 + wn + 16 * (f >> 5) + (f & 15u);
-                const unsigned nn = ((f >> 4) & 1u) ? po.c2 + po.cs * p2(pair) : po.c1 + po.cs * pair;
-                it_ok[c] = f < (unsigned)NIT && pair < NP && nn < n / 2;
-                const unsigned pos = it_ok[c] ? (sweep ? n - 1 - nn : nn) : 0u;
-                it_line[c] = ((size_t)g * po.cop_lines + (size_t)z * po.W + oposf(pos, n)) * 8u + u0;
-            }
-#pragma unroll
-            for (int ip = 0; ip < NI; ip += 2) {
-                __builtin_amdgcn_sched_barrier(0);
-                lds_order();
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int i = ip + u;
-                    double e[4][NJ][2];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const unsigned soff = (swm + 16 * i + 4 * r) * (n / 2) * 8u;
-#pragma unroll
-                        for (int jn = 0; jn < NJ; ++jn)
-#pragma unroll
-                            for (int h2 = 0; h2 < 2; ++h2) {
-                                const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(trr, vt[jn][h2], soff, 0);
-                                e[r][jn][h2] = __hiloint2double((int)raw[1], (int)raw[0]);
-                            }
-                    }
-#pragma unroll
-                    for (int jn = 0; jn < NJ; ++jn)
-#pragma unroll
-                        for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const double a = h2 ? acc2[i][jn][r] : acc1[i][jn][r];
-                                float v = sweep ? (float)(e[r][jn][h2] - a) : (float)(e[r][jn][h2] + a);
-                                if (!plain) v *= sweep ? ep.base : fp[jn][h2];
-                                tw[u * (NIT * 16) + lpos(32 * jn + 16 * h2 + li, lq + 4 * r)] = v;
-                            }
-                }
-                lds_order();
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned Hq = Hc / 4, H8 = Hc / 8;
-#pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    double o[NC][2][8];
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        // the tables of one unit, only what this half needs, live for this unit only (two units' full sets as
-                        // vector registers next to the tile's 128 results spill)
-                        const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)(8 * g + u0 + ip + u));
-                        const bool unit_ok = e < HU;
-                        const unsigned ec = unit_ok ? e : 0u;
-                        ColL2Tab tab;
-                        tab.c3 = po.crot3[ec]; tab.s3 = po.crot3[HU + ec];
-                        if (half == 0) { tab.ra = rot_load(po.crot1, ec, Hq); tab.rb = rot_load(po.crot1, H8 - 1 - ec, Hq); tab.rc = Rot4{0, 0, 0, 0}; }
-                        else { tab.rc = rot_load(po.crot2, ec, H8); tab.ra = tab.rb = Rot4{0, 0, 0, 0}; }
-#pragma unroll
-                        for (int c = 0; c < NC; ++c) {
-                            const unsigned f = (lane + 64 * c) < (unsigned)NIT ? lane + 64 * c : 0u;
-                            float x[8];
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) {
-                                const f32x4 t4 = *reinterpret_cast<const f32x4*>(tw + u * (NIT * 16) + lpos(f, 8 * half + 4 * q));
-                                x[4 * q] = t4[0]; x[4 * q + 1] = t4[1]; x[4 * q + 2] = t4[2]; x[4 * q + 3] = t4[3];
-                            }
-                            if (half == 0) inv_col_l2_unit_lo(x, tab, o[c][u]); else inv_col_l2_unit_hi(x, tab, o[c][u]);
-                            if (!unit_ok) {
-#pragma unroll
-                                for (int a = 0; a < 8; ++a) o[c][u][a] = 0.0;
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        if (!it_ok[c]) continue;
-                        double* dst0 = po.cop + it_line[c] + ip + (size_t)(8 * half) * pstride;
-#pragma unroll
-                        for (int a = 0; a < 8; ++a) *reinterpret_cast<f64x2*>(dst0 + (size_t)a * pstride) = (f64x2){o[c][0][a], o[c][1][a]};
-                    }
                 }
             }
         }
@@ -1315,14 +927,14 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
                         // r6: the tile's lines lie in one frame (block-uniform: W % BM == 0 for every frame size of the 4K / 8K / 1080p
                         // paths): I, Q and the pixels through buffer resources of that frame, a lane outside the tile or the class
                         // at an offset behind the range -- no branch around a load or a store, so the compiler counts its waits and
-                        // the I / Q quads of four output rows are in flight together (with the branches every quad was its own
+                        // the I / Q quads of RGB_NB output rows are in flight together (with the branches every quad was its own
                         // load -> wait -> store chain: `vmcnt(1)`, `vmcnt(0)` per quad in the ISA, the previous quad's stores included)
                         if (rgb_fast) {
                             // (one copy of the round per pixel format: a format branch inside it would leave the number of stores
                             // between two waits open, and the compiler would wait for the previous quad's stores as well)
                             auto rgb_round = [&](auto u8c) {
                             constexpr bool U8 = decltype(u8c)::value;
-                            constexpr int NB = NRI < SSW_RGB_NB ? NRI : SSW_RGB_NB;
+                            constexpr int NB = NRI < RGB_NB ? NRI : RGB_NB;
 #pragma unroll
                             for (int tb = 0; tb < NRI; tb += NB) {
                                 unsigned off[NB];
@@ -1451,21 +1063,13 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
     using J1 = std::integral_constant<int, 1>;
     using J2 = std::integral_constant<int, 2>;
     using J3 = std::integral_constant<int, 3>;
-    using EVEN = std::integral_constant<bool, false>;
-    using ODDK = std::integral_constant<bool, true>;
     // (tiles of 48 pairs -- po.bn32 == 2 -- always run three pair tiles on the 4 x 1 grid, whatever their valid pair count)
     const bool j3 = BM == 128 && (po.bn32 == 2 || (!COLS && NP - p0 <= 48));
-    if (!SSW_GEMM_DMA_DEV && ((Kp / PBK) & 1u)) {             // (the DMA ring's loop takes any step count)
-        if (NP - p0 <= 16 && po.bn32 != 2) run(std::integral_constant<int, BM / 64>{}, J1{}, ODDK{});
-        else if (po.bn32 != 2 && (NP - p0 <= 32 || po.bn32)) run(std::integral_constant<int, BM / 64>{}, J2{}, ODDK{});
-        else if (j3)                       run(std::integral_constant<int, BM / 64>{}, J3{}, ODDK{});
-        else                               run(std::integral_constant<int, BM / 32>{}, J2{}, ODDK{});
-    } else {
-        if (NP - p0 <= 16 && po.bn32 != 2) run(std::integral_constant<int, BM / 64>{}, J1{}, EVEN{});
-        else if (po.bn32 != 2 && (NP - p0 <= 32 || po.bn32)) run(std::integral_constant<int, BM / 64>{}, J2{}, EVEN{});
-        else if (j3)                       run(std::integral_constant<int, BM / 64>{}, J3{}, EVEN{});
-        else                               run(std::integral_constant<int, BM / 32>{}, J2{}, EVEN{});
-    }
+    if (NP - p0 <= 16 && po.bn32 != 2) run(std::integral_constant<int, BM / 64>{}, J1{});
+    else if (po.bn32 != 2 && (NP - p0 <= 32 || po.bn32)) run(std::integral_constant<int, BM / 64>{}, J2{});
+    else if (j3)                       run(std::integral_constant<int, BM / 64>{}, J3{});
+    else                               run(std::integral_constant<int, BM / 32>{}, J2{});
+#endif
 }
 
 // what selects the template instance of a class: all classes of a launch must agree

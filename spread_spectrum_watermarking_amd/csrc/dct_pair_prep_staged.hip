@@ -738,8 +738,7 @@ __global__ __launch_bounds__(256) void prep16_inv_rows_staged_kernel(const float
 __global__ __launch_bounds__(256) void prep16_inv_rows_l2_kernel(const float* __restrict__ X, double* __restrict__ base,
                                                                  const double* __restrict__ rot1, const double* __restrict__ rot2,
                                                                  const double* __restrict__ rot3,
-                                                                 unsigned rows, unsigned W, unsigned K16, unsigned tblocks,
-                                                                 unsigned unit_h, unsigned unit_hup) {
+                                                                 unsigned rows, unsigned W, unsigned K16, unsigned tblocks) {
     __shared__ __attribute__((aligned(16))) double lds[RNS * RSL];
     __shared__ double* s_plane[RNS];
     __shared__ unsigned s_piece[RNS], s_mask[RNS];
@@ -761,18 +760,8 @@ __global__ __launch_bounds__(256) void prep16_inv_rows_l2_kernel(const float* __
     auto plane = [&](unsigned a) { return base + (size_t)a * rows * K16; };
     const unsigned g[4] = {R, Nh - 16 - R, Nh + R, W - 16 - R};
     f32x4 c[4][4];
-    // r5, fused inverse transform (unit_h = H != 0): the operand lines of a frame are ordered (unit of the column fold, line
-    // of the unit; 16 * unit_hup lines per frame, dct_pair_colops.hpp inv_col_unit_row) -- a line reads the coefficient row it
-    // holds (512-byte runs per region either way); the lines of the padding units hold zeros.  `rows` counts operand lines.
-    size_t src_row = row_base + lr;
-    bool src_ok = ok;
-    if (unit_h) {
-        const unsigned line = (unsigned)(row_base + lr), lpf = 16 * unit_hup, z = line / lpf, rem = line - z * lpf;
-        src_ok = ok && (rem >> 4) < unit_h / 16;
-        src_row = (size_t)z * unit_h + (src_ok ? inv_col_unit_row(rem >> 4, rem & 15u, unit_h) : 0u);
-    }
-    if (src_ok) {
-        const float* xr = X + src_row * W;
+    if (ok) {
+        const float* xr = X + (row_base + lr) * W;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -1012,12 +1001,12 @@ int launch_prep16_inv_cols_l2(hipStream_t st, const float* in, size_t n_frames, 
 }
 
 int launch_prep16_inv_rows_l2(hipStream_t st, const float* in, size_t rows, size_t w, double* base,
-                               const double* rot1, const double* rot2, const double* rot3, unsigned K16, unsigned unit_h, unsigned unit_hup) {
+                               const double* rot1, const double* rot2, const double* rot3, unsigned K16) {
     if (w % 128 != 0 || !rot3) return SSW_ERR_BAD_ARG;
     const unsigned NT = (unsigned)(w / 64), tblocks = (NT / 2 + 3) / 4;
     const unsigned long long nblk = (unsigned long long)((rows + RL - 1) / RL) * tblocks;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    prep16_inv_rows_l2_kernel<<<(unsigned)nblk, 256, 0, st>>>(in, base, rot1, rot2, rot3, (unsigned)rows, (unsigned)w, K16, tblocks, unit_h, unit_hup);
+    prep16_inv_rows_l2_kernel<<<(unsigned)nblk, 256, 0, st>>>(in, base, rot1, rot2, rot3, (unsigned)rows, (unsigned)w, K16, tblocks);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }

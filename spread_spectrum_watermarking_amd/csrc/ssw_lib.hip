@@ -226,8 +226,7 @@ int ssw_ctx_transform_plan(ssw_ctx* ctx, size_t n_frames, size_t w, size_t h, in
         if (l2r) f |= SSW_PLAN_ROWS_LEVEL2;
         if (l2c) f |= SSW_PLAN_COLS_LEVEL2;
         if (cm) f |= SSW_PLAN_CLASS_MAJOR;
-        if (l2r && l2c && cm && (inverse ? ssw::dct_pair_can_fuse_inv_cols(n_frames, w, h) : ssw::dct_pair_can_fuse_cols(n_frames, w, h)))
-            f |= SSW_PLAN_FUSED_COLS;
+        if (!inverse && l2r && l2c && cm && ssw::dct_pair_can_fuse_cols(n_frames, w, h)) f |= SSW_PLAN_FUSED_COLS;
     }
     *flags = f;
     return SSW_OK;

@@ -33,17 +33,11 @@ Entry g_tune[TUNE_COUNT] = {
     {"bn32", "SSW_BN32", -1},                          // 32-pair tiles for small single-class launches: -1 automatic, 0 / 1 forced
     {"band_split", "SSW_BAND_SPLIT", 1},               // single-image handles: row pass of the top half beside the upload of the bottom half
     {"fuse_cols", "SSW_FUSE_COLS", 1},                 // forward: column operands straight from the row GEMMs' epilogue (r5)
-    {"fuse_inv_cols", "SSW_FUSE_INV_COLS", 0},         // inverse: the same (r5; bit-identical, measured no faster: off by default)
     {"upload_bands", "SSW_UPLOAD_BANDS", 3},           // single-image handles: bands of rows a host frame is uploaded and row-transformed in (2 .. 4)
     {"speculate_k", "SSW_SPECULATE_K", 1},             // Reader::base queues the selection for the context's last extraction length
     {"prep_light", "SSW_PREP_LIGHT", 1},               // level-2 row pre-pass in the < 64-VGPR form that runs beside the GEMMs (0: pair_prep16_rows_kernel)
     {"lane_stagger", "SSW_LANE_STAGGER", 1},           // two lanes: RGB pre-passes beside the other lane's column launches, not its row launches (r5: +0.7 %)
     {"derived_fused", "SSW_DERIVED_FUSED", 1},         // the derived frame's pruned row pass in one kernel (marks of up to 1024 entries; 0: pre-pass + launches)
-    {"inv_prep_light", "SSW_INV_PREP_LIGHT", 0},       // inverse row pre-pass at level 2: whole rows through LDS, one lane per unit (r5 A/B)
-    {"gemm_stagger", "SSW_GEMM_STAGGER", 0},           // r6 A/B: the GEMM blocks 256 .. 511 of a launch (the CUs' second residents) start this many ~3.4-us sleeps late
-    {"gemm_group_m", "SSW_GEMM_GROUP_M", 4},           // column passes: tile rows per group of the GEMMs' block -> tile map (1: a line tile's tile columns are consecutive blocks)
-    {"gemm_group_m_rows", "SSW_GEMM_GROUP_M_ROWS", 4}, // row passes: the same (r6: 1 cuts a fused row launch's PMC FETCH_SIZE from 1.95 to 1.29 GB and costs 2.8 % of the row stage)
-    {"merge_batch", "SSW_MERGE_BATCH", 0},             // r6 A/B: a batch pass's independent launches as one, class after class (PairMulti::cls_major)
     {"tile48", "SSW_TILE48", 1},                       // r6: 48-pair tiles for classes whose 64-pair tiling ends in a tile of <= 16 pairs (135 = 48 + 48 + 39)
 };
 

@@ -80,8 +80,7 @@ def test_light_row_prepass_is_bit_identical_to_the_register_resident_one():
     """r5: the level-2 row pre-pass in the form that fits beside the GEMMs (csrc/dct_pair_prep_light.hip: runs of pixels
     through LDS, one lane per unit, < 64 VGPRs) against pair_prep16_rows_kernel (prep_light = 0) -- whole batch pipelines from
     f32 / 8-bit / 16-bit frames (I and Q written for the writer), natural and unit line order, partial tiles of units, plain
-    planes; and the inverse row pre-pass in the same style (inv_prep_light, off by default) against prep16_inv_rows_l2_kernel:
-    tools/prep_light_check.py."""
+    planes: tools/prep_light_check.py."""
     import prep_light_check
     lines = []
     bad = prep_light_check.run(lines.append, batch=[(2160, 3840, 8, 1000), (2160, 3840, 3, 500), (1080, 1920, 5, 500), (272, 512, 40, 100),
@@ -98,16 +97,16 @@ def test_fused_derived_pass_is_bit_identical_to_prepass_and_launches():
     Reader::extract reads the derived plane only at the base's first k indices, /root/reference/src/algorithm.rs:556-561."""
     import prep_light_check
     lines = []
-    bad = prep_light_check.run(lines.append, batch=[], planes=[], inverse=[])
+    bad = prep_light_check.run(lines.append, batch=[], planes=[])
     assert bad == 0, "\n".join(l for l in lines if "FAIL" in l)
     assert sum("one kernel ==" in l for l in lines) == 3 * len(prep_light_check.DERIVED)
 
 
 def test_gemm_ring_reproduces_the_register_staged_kernels_planes_bit_for_bit():
-    """r6: the GEMM's operand tiles arrive by LDS-DMA in a ring (csrc/dct_pair_f64_kernel.hpp, SSW_GEMM_DMA) instead of through
-    registers + ds_write -- same products, same k order per accumulator, so every plane is the r5 kernel's bit for bit.
-    tests/golden/gemm_digests.json holds the digests of the register-staged build (-DSSW_GEMM_DMA=0) on ssw_synth_frames
-    inputs: plane transforms (forward, orthonormal, inverse: src/dct2d.rs:83-219) of eight shapes covering every strategy --
+    """r6: the GEMM's operand tiles arrive by LDS-DMA in a ring (csrc/dct_pair_f64_kernel.hpp) instead of through registers +
+    ds_write as in r5 -- same products, same k order per accumulator, so every plane is the r5 kernel's bit for bit.
+    tests/golden/gemm_digests.json holds the digests that the r5 register-staged kernel produced (a recorded fact: that kernel
+    is no longer built) on ssw_synth_frames inputs: plane transforms (forward, orthonormal, inverse: src/dct2d.rs:83-219) of eight shapes covering every strategy --
     4K / 8K batches and single frames, 1080p, 720p, the 444-row dense path -- and three batch embed + extract pipelines
     (marked frames, extracted marks, similarities); tools/lib_ab_check.py computes them for the loaded library in a child process."""
     import lib_ab_check
@@ -119,14 +118,12 @@ def test_gemm_ring_reproduces_the_register_staged_kernels_planes_bit_for_bit():
     assert not diff, f"planes differ from the register-staged kernel's: {diff}"
 
 
-def test_gemm_tile_order_and_stagger_knobs_choose_between_equal_results():
-    """ssw_tuning_set names of r6 (gemm_group_m, gemm_group_m_rows: tile rows per group of the block -> tile map; gemm_stagger:
-    a launch-time offset for the CUs' second resident blocks; merge_batch: a batch pass's launches as one, class after class; tile48: 135 pairs as 48 + 48 + 39 or 64 + 64 + 7)
-    are A/B switches of the schedule: the digests stay the same."""
+def test_gemm_tile48_knob_chooses_between_equal_results():
+    """ssw_tuning_set name of r6 (tile48: 135 pairs as 48 + 48 + 39 or 64 + 64 + 7) is an A/B switch of the schedule: the
+    digests stay the same."""
     import lib_ab_check
     base = lib_ab_check.digests()
-    for env in ({"SSW_GEMM_GROUP_M_ROWS": "1", "SSW_GEMM_GROUP_M": "16"}, {"SSW_GEMM_STAGGER": "2", "SSW_GEMM_GROUP_M_ROWS": "16"},
-                {"SSW_MERGE_BATCH": "1", "SSW_TILE48": "0"}):
+    for env in ({"SSW_TILE48": "0"},):
         assert lib_ab_check.digests(env=env) == base, env
 
 
@@ -144,15 +141,13 @@ def test_transform_plan_reports_the_default_path():
     assert c.transform_plan(1, 3840, 2160)["fused_cols"] and c.transform_plan(2, 3840, 2160)["fused_cols"]
     assert not c.transform_plan(3, 3840, 2160)["fused_cols"] and not c.transform_plan(5, 3840, 2160)["fused_cols"]
     assert c.transform_plan(7, 3840, 2160)["fused_cols"]
-    assert not c.transform_plan(128, 3840, 2160, L.DCT3)["fused_cols"]                  # the inverse's fusion is opt-in
+    assert not c.transform_plan(128, 3840, 2160, L.DCT3)["fused_cols"]                  # the inverse is never fused
     p = c.transform_plan(256, 1920, 1080)
     assert p["pair_f64"] and p["rows_level2"] and p["class_major"] and not p["cols_deep"] and not p["fused_cols"], p
     assert not c.transform_plan(1, 640, 444)["pair_f64"]
     with tuning(fuse_cols=0):
         q = c.transform_plan(128, 3840, 2160)
         assert not q["fused_cols"] and q["cols_level2"] and q["rows_level2"]
-    with tuning(fuse_inv_cols=1):
-        assert c.transform_plan(128, 3840, 2160, L.DCT3)["fused_cols"]
 
 
 def test_diagnostic_build_runs_the_strategy_matrix():

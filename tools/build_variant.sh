@@ -4,7 +4,7 @@
 # Run `make -C csrc` first.  Timing-only ablations compute wrong values by design.
 #   tools/build_variant.sh trace -DSSW_TILE_TRACE -DSSW_TILE_TRACE_FWD_ONLY     per-tile / per-k-step stamps of the forward instances (tools/tile_trace.py)
 #   tools/build_variant.sh x0 -DSSW_ABL_X0                                      every block stages tile 0's lines (L2-resident operands)
-#   ALL=1 tools/build_variant.sh regs -DSSW_GEMM_DMA=0                          forward AND inverse units (five compiles in parallel)
+#   ALL=1 tools/build_variant.sh noepi -DSSW_ABL_NOEPI                          forward AND inverse units (five compiles in parallel)
 # usage: [ALL=1] tools/build_variant.sh NAME [-D flags]
 set -e
 NAME=$1; shift

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """r5: the FUSED forward transform (csrc/dct_pair_f64_kernel.hpp EPI_FWD_COLOP: the row GEMMs' epilogue applies the column
 pre-pass's arithmetic to its accumulators and writes the column operands; no f32 plane between the passes,
-src/dct2d.rs:152-168 stays the rounding point) and its mirror image for the inverse transform (EPI_INV_O_COLOP) against the unfused path (tuning fuse_cols = 0: row
-launches -> f32 plane -> prep16_cols_l2_kernel / prep16_inv_cols_l2_kernel): planes of ssw_dct2d bit for bit, forward,
-orthonormal and inverse, on shapes that cover every
+src/dct2d.rs:152-168 stays the rounding point) against the unfused path (tuning fuse_cols = 0: row launches -> f32 plane
+-> prep16_cols_l2_kernel): planes of ssw_dct2d bit for bit, forward and orthonormal, on shapes that cover every
 tail mode of the row launches (16 / 32 / 48 / 64 pairs in the last tile column) and frames whose units do not fill their
-last k-block; the first and the last frame also against the oracle's correctly rounded transform; then whole batch pipelines
+last k-block; the inverse transform (never fused: row launches -> f32 plane -> prep16_inv_cols_l2_kernel either way) on the
+same shapes; the first and the last frame also against the oracle's correctly rounded transform; then whole batch pipelines
 (embed + extract) fused against unfused.  Small shapes take the level-2 kernels through lowered thresholds (ssw_tuning_set).
 tests/test_fuzz_gpu.py calls run() in-process.
 usage: python tools/fuse_check.py"""
@@ -37,7 +37,7 @@ def run(out=print, shapes=SHAPES, batch=BATCH):
         for name, kind in (("fwd", L.DCT2), ("ortho", L.DCT2_ORTHOGONAL), ("inv", L.DCT3)):
             preps = []
             for fuse in (1, 0):
-                with tuning(fuse_cols=fuse, fuse_inv_cols=fuse, **LOW), G.fresh_ctx() as c:
+                with tuning(fuse_cols=fuse, **LOW), G.fresh_ctx() as c:
                     if fuse:
                         planned = c.transform_plan(n, w, h, kind)["fused_cols"]
                     c.enable_timing(True)
@@ -50,8 +50,8 @@ def run(out=print, shapes=SHAPES, batch=BATCH):
                 else:
                     b = r
             # the fused transform has ONE pre-pass stage (rows), the unfused one two (rows, columns): the path under test ran
-            # every forward case of the list must take the fused path; the inverse of one or two 4K frames stays unfused (its
-            # dependent launches run one class each, on 64-line tiles) -- ssw_ctx_transform_plan says which, the stage count confirms
+            # every forward case of the list must take the fused path, no inverse one -- ssw_ctx_transform_plan says which, the
+            # stage count confirms
             same = bool(np.array_equal(a, b)) and preps == ([1, 2] if planned else [2, 2]) and (planned or kind == L.DCT3)
             worst = 1.0
             for f in (0, n - 1):
@@ -66,7 +66,7 @@ def run(out=print, shapes=SHAPES, batch=BATCH):
         marks = np.random.default_rng(k).standard_normal((n, k)).astype(np.float32)
         res = []
         for fuse in (1, 0):
-            with tuning(fuse_cols=fuse, fuse_inv_cols=fuse, **LOW), G.fresh_ctx():
+            with tuning(fuse_cols=fuse, **LOW), G.fresh_ctx():
                 cfg = G.default_config(L.PRECISION_F64)
                 r = G.batch_embed(rgb, marks, cfg, want_coef=True, want_idx=True)
                 ext, sims = G.batch_extract(rgb, r["rgb"], k, marks, cfg)

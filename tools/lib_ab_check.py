@@ -3,7 +3,8 @@
 runs in a child process (SSW_LIB_PATH), transforms the same synthetic frames -- ssw_dct2d forward, orthonormal and inverse on
 shapes of every strategy, one batch embed + extract -- and prints a digest per case; the parent compares the digests.
 usage: python tools/lib_ab_check.py LIB_A LIB_B
-       python tools/lib_ab_check.py --golden LIB OUT.json     (writes the digests of one build: tests/golden/gemm_digests.json)"""
+       python tools/lib_ab_check.py --golden LIB OUT.json     (writes the digests of one build, in the format of
+                                                              tests/golden/gemm_digests.json: the r5 kernel's digests, kept as recorded)"""
 import hashlib
 import os
 import subprocess
@@ -66,8 +67,10 @@ def main():
         import json
         d = digests(sys.argv[2])
         with open(sys.argv[3], "w") as f:
-            json.dump({"_how": "python tools/lib_ab_check.py --golden <library built with -DSSW_GEMM_DMA=0: the register-staged r5 GEMM kernel> "
-                               "tests/golden/gemm_digests.json -- sha256[:16] of the f32 outputs on ssw_synth_frames(seed 7) inputs",
+            # (the committed tests/golden/gemm_digests.json was written from the r5 register-staged GEMM kernel, which is no longer
+            # built: it records that kernel's planes, do not regenerate it)
+            json.dump({"_how": "python tools/lib_ab_check.py --golden <library> OUT.json "
+                               "-- sha256[:16] of the f32 outputs on ssw_synth_frames(seed 7) inputs",
                        "digests": d}, f, indent=1)
         print(f"{len(d)} digests -> {sys.argv[3]}")
         return 0
