@@ -100,7 +100,8 @@ const char* ssw_version(void);
 int ssw_build_all_strategies(void);
 /* Which strategy of the 2-D transform (src/dct2d.rs:83-219) a batch of n_frames frames of w x h takes in the canonical (f64)
    precision under the context's current settings, as flags -- introspection for bench.py, DESIGN.md and the tests; every
-   strategy computes the same values:
+   strategy computes the same values.  The flags are read off the plan that builds the passes (csrc/dct_plan.hpp, for the
+   first group of frames on aligned planes), so they describe what runs at every folding level and split setting:
      PAIR_F64     operand-ready f64 GEMMs (otherwise the dense kernels)
      ROWS_DEEP / COLS_DEEP       one pre-pass per pass writes the operands of all launches (split odd halves)
      ROWS_LEVEL2 / COLS_LEVEL2   every launch of the pass sums len/16 terms (eight launches per pass)

@@ -342,12 +342,6 @@ __global__ __launch_bounds__(FT, SUB == 1 ? 3 : 2) void dct_cols_folded_f32_kern
 // ---------------------------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------------------------
-bool dct_rows_can_fold(size_t w, const float* in, const float* out) {
-    return w >= 16 && (w % 8 == 0) && aligned16(in) && aligned16(out);
-}
-bool dct_cols_can_fold(size_t w, size_t h, const float* in, const float* out) {
-    return h >= 16 && (h % 8 == 0) && (w % 4 == 0) && aligned16(in) && aligned16(out);
-}
 
 // Tile variant: the 128-wide variant is faster once the grid fills the chip (measured 114 vs 106
 // TFLOP/s at 4K x 16 frames); small launches (a single small frame) take the 64-wide one so that

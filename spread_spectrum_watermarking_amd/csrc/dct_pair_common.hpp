@@ -107,7 +107,7 @@ struct PairOutT {
 // stores runs (t/8 = 16 entries = the 16 pairs of one MFMA tile), and a block of the column pre-pass now reads ONE
 // contiguous 512-byte run per row for 128 consecutive operand lines (the one-tile order gave it ten runs of 64 / 32
 // bytes, or -- read by memory column -- stores scattered over lines 8 or 16 apart: 2.8 TB/s).
-// r4b (`level2`: row passes of 1280 columns or more, dct_pair_efold): every launch of the pass works on sums of n/16
+// r4b (`level2`: row passes of 1280 columns or more, PairLayout::rows_l2): every launch of the pass works on sums of n/16
 // terms and owns two residues mod 16 -- sixteen classes of t/16 entries each, in this order:
 //   class      R1A  R1B  R2A  R2B   E2P  E2M  O2P  O2M   EEP  EEM  EOP  EOM   O5  O11  O3  O13
 //   u mod 16   0    8    4    12    2    14   10   6     1    15   9    7     5   11   3   13
@@ -163,7 +163,7 @@ __host__ __device__ inline unsigned class_tile(unsigned n) { return n % 128 == 0
 // inside tiles of t positions (t % 4 == 0, t divides len; t = len: one tile -- the order of the E planes, which only
 // GEMM epilogues exchange):
 //   [ m = 0 mod 4 | m = 3 mod 4 | m = 1 mod 4 | m = 2 mod 4 ], each t/4 long, m / 4 ascending.
-// r4c (`l2`: inverse row passes at level 2, dct_pair_efold_inv): the four launches of the odd part produce the positions
+// r4c (`l2`: inverse row passes at level 2, PairLayout::rows_l2): the four launches of the odd part produce the positions
 // 8i, 8i-1 | 8i+4, 8i+3 | 8i+2, 8i-3 | 8i+1, 8i-2 and their mirrors -- residues {0, 7}, {4, 3}, {2, 5}, {1, 6} mod 8 (t % 8 == 0):
 //   [ 0 | 7 | 4 | 3 | 2 | 5 | 1 | 6  mod 8 ], each t/8 long, m / 8 ascending
 // (the launches of the half-length odd part, residues {0, 3} and {1, 2} mod 4, write runs of two of these classes).

@@ -282,9 +282,10 @@ __global__ __launch_bounds__(256, 2) void prep16_derived_fused_kernel(const void
 
 }  // namespace
 
-// classes: those of build_pruned_derived's level-2 plan (x2 != nullptr: split).  false: take the launches.
-bool dct_pair_derived_fused_ok(size_t w, unsigned n_classes, const DerivedFusedClass* cls) {
-    if (tuning(TUNE_DERIVED_FUSED) == 0 || w % 64 != 0 || !dct_pair_efold(w) || n_classes > 9) return false;
+// classes: those of build_pruned_derived's level-2 plan (x2 != nullptr: split), whose plan took this kernel
+// (plan_derived_fused).  false: they do not fit its registers -- take the launches.
+bool dct_pair_derived_fused_fits(unsigned n_classes, const DerivedFusedClass* cls) {
+    if (n_classes > 9) return false;
     unsigned load[4] = {0, 0, 0, 0}, cnt[4] = {0, 0, 0, 0};
     for (unsigned c = 0; c < n_classes; ++c) {
         if (cls[c].cap == 0) continue;

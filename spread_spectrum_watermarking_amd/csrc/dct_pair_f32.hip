@@ -312,7 +312,7 @@ __global__ __launch_bounds__(QT, 2) void pair_gemm_f32_kernel(
     else               run(std::integral_constant<int, 2>{});
 }
 
-// kind: 0 one folding level; 1 / 2 the even / odd half of two levels (see launch_dct_pair_gemm_f64)
+// kind: 0 one folding level; 1 / 2 the even / odd half of two levels (see launch_dct_pair_gemm_multi_f64)
 int launch_dct_pair_gemm_f32(hipStream_t st, bool is_row, bool inverse, int kind, int sub, const float* x1, const float* x2,
                              const float* y1, const float* y2, float* out, float* tmp, size_t n_frames, size_t w,
                              size_t h, Epilogue ep, const RgbSink* sink) {

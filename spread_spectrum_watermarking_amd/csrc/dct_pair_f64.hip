@@ -84,7 +84,7 @@ namespace ssw {
 namespace {
 
 // the per-class part of a launch: pair count, sum length, basis lines and the output map of (kind, sub)
-int pair_class_args(const PairClassDesc& d, bool is_row, bool inverse, size_t len, bool class_major, bool with_sink, bool has_tmp_out,
+int pair_class_args(const PairClassDesc& d, bool is_row, bool inverse, size_t len, const PairLayout& lay, bool with_sink, bool has_tmp_out,
                     PairClassArgs& ca, PairInstance& inst) {
     const int kind = d.kind, sub = d.sub;
     // inverse: sub = 1 serves the deep inverse (the half-length transform E): kind 1 -> its even half T2, kinds 3 / 4 -> E
@@ -141,7 +141,7 @@ int pair_class_args(const PairClassDesc& d, bool is_row, bool inverse, size_t le
             ca.c1 = kind == 3 ? 0u : 2u; ca.c2 = kind == 3 ? 0u - 1u : 1u; ca.cs = 4;             // positions of the odd part
         }
     }
-    if (class_major) {
+    if (lay.class_major) {
         // forward row pass of a deep transform: every class writes its frequencies side by side (ForwardClassLayout,
         // dct_pair_common.hpp) instead of 4-byte pieces 16 / 32 bytes apart -- the column pre-pass puts the columns back;
         // inverse: the split classes write (and read E) at one pair of residues mod 4 (po.cm, inverse_class_pos), the
@@ -150,9 +150,9 @@ int pair_class_args(const PairClassDesc& d, bool is_row, bool inverse, size_t le
         if (!inverse) {
             // po.ft = the tile: entry e of a class -> column base + (e >> gsh) * ft + (e & (2^gsh - 1)); class E's second
             // output of pair p is entry p - 1 of its "-" class (frequency 8 p - 1)
-            // level 2 (dct_pair_efold(len), like the pre-pass): sixteen classes, every launch a sum of len/16 terms
-            const bool l2 = dct_pair_efold(len);
-            const ForwardClassLayout fl{(unsigned)len, dct_pair_class_tile(len), l2};
+            // level 2 (lay.rows_l2, like the pre-pass): sixteen classes, every launch a sum of len/16 terms
+            const bool l2 = lay.rows_l2;
+            const ForwardClassLayout fl{(unsigned)len, lay.tile, l2};
             typedef ForwardClassLayout F;
             int k1 = -1;
             if (l2) k1 = (kind == 1 && sub == 2) ? F::R1A : (kind == 3 && sub == 1) ? F::F_E2P : (kind == 4 && sub == 1) ? F::F_O2P
@@ -196,39 +196,21 @@ int pair_class_args(const PairClassDesc& d, bool is_row, bool inverse, size_t le
 //           sine) rows 2i | 2i+1 of the quarter-length bases; outputs acc1 +/- acc2          pairs = len/8, K = len/8
 //           (class E's first and last pair share slot 0: its y2 is the launch variant of the sine basis, row 0 = row len/8)
 //   sub: the class belongs to the transform of length len >> sub that a deeper folding level applies to the even part.
-// r5: a forward transform of n frames whose row launches write the column operands themselves (EPI_FWD_COLOP).  Rows first,
-// both passes at level 2, 128-frequency class tiles, the column planes exactly as wide as the padded units, and both passes
-// on 128-line tiles (a tile of the row pass IS one k-block of the column operands; small batches keep the unfused path).
-// (the launcher's own test, launch_dct_pair_gemm_multi_f64: a pass of at most merge_max_lines lines runs its eight classes as
-// ONE launch, whose tile columns add up)
-static bool launch_is_small(size_t lines, size_t pairs) {
-    const unsigned long long classes = lines <= (size_t)tuning(TUNE_MERGE_MAX_LINES) ? 8 : 1;
-    return (unsigned long long)((lines + 127) / 128) * ((pairs + 63) / 64) * classes < 448;
-}
-bool dct_pair_can_fuse_cols(size_t n_frames, size_t w, size_t h) {
-    if (tuning(TUNE_FUSE_COLS) == 0 || n_frames == 0 || w < h || w % 128 != 0 || h % 16 != 0) return false;
-    if (dct_pair_class_tile(w) != 128 || !dct_pair_efold(w) || !dct_pair_efold_cols(h, w, true)) return false;
-    // ... and the column pass must reach its deep branch by itself (build_pass_impl: two && split && deep): with the public
-    // thresholds lowered (ssw_tuning_set: deep_min_cols, efold_cols_min) below 128 rows it would not, and would read an f32
-    // plane the fused row pass never wrote
-    if (!dct_pair_can_split(h, false) || !dct_pair_can_fold2_cols(h)) return false;
-    const size_t hup = dct_pair_fused_units(h);
-    if (pair_kpad<double>(h / 8) != hup) return false;
-    if (n_frames * 16 * hup > 0xFFFFFFFFull || n_frames * w > 0xFFFFFFFFull) return false;      // 32-bit line indices in both passes
-    return !launch_is_small(n_frames * 16 * hup, w / 16) && !launch_is_small(n_frames * w, h / 16);
-}
+// r5: a forward transform of n frames whose row launches write the column operands themselves (EPI_FWD_COLOP); whether a
+// transform takes it is the planner's decision (dct_plan.hip, PassStrategy::FusedRows / FusedCols).
 
 int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, int n_classes, const PairClassDesc* desc, float* out,
                                    double* tmp, size_t n_frames, size_t w, size_t h, Epilogue ep, const RgbSink* sink, double* tmp_out,
-                                   bool class_major, const FuseCols* fuse) {
+                                   const PairLayout& lay, const FuseCols* fuse) {
     if (n_frames == 0 || n_classes == 0) return SSW_OK;
     if (n_classes < 0 || n_classes > 8 || !desc) return SSW_ERR_BAD_ARG;
     if (w > 0xFFFFFFull || h > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
     // fused forward transform: the row launches (fuse->cop set) run over the unit-ordered, padded lines and write the
     // column operands; the column launches (fuse set, cop null) read their tiles in the row launches' class-major order
     const bool fuse_rows = fuse && fuse->mode == FUSE_ROWS_COP, fuse_cols = fuse && fuse->mode == FUSE_COLS;
-    if (fuse && (!(fuse_rows || fuse_cols) || fuse_rows != is_row || inverse || !dct_pair_can_fuse_cols(n_frames, w, h))) return SSW_ERR_BAD_ARG;
-    if (fuse_rows && (!class_major || sink || !fuse->cop || !fuse->rot1 || !fuse->rot2 || !fuse->rot3)) return SSW_ERR_BAD_ARG;
+    if (fuse && (!(fuse_rows || fuse_cols) || fuse_rows != is_row || inverse || w % 128 != 0 || h % 16 != 0 ||
+                 pair_kpad<double>(h / 8) != dct_pair_fused_units(h))) return SSW_ERR_BAD_ARG;
+    if (fuse_rows && (!lay.class_major || sink || !fuse->cop || !fuse->rot1 || !fuse->rot2 || !fuse->rot3)) return SSW_ERR_BAD_ARG;
     const size_t lines = fuse_rows ? n_frames * 16 * dct_pair_fused_units(h) : is_row ? n_frames * h : n_frames * w;
     const size_t len = is_row ? w : h;
     if (lines > 0xFFFFFFFFull) return SSW_ERR_BAD_DIMS;
@@ -239,7 +221,7 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     unsigned tiles_n = 0, leff0 = 0;
     for (int c = 0; c < n_classes; ++c) {
         PairInstance ic{0, false, 0};
-        SSW_TRY(pair_class_args(desc[c], is_row, inverse, len, class_major, with_sink, tmp_out != nullptr, ml.c[c], ic));
+        SSW_TRY(pair_class_args(desc[c], is_row, inverse, len, lay, with_sink, tmp_out != nullptr, ml.c[c], ic));
         if (c == 0) { inst = ic; leff0 = (unsigned)(len >> desc[c].sub); }
         else if (!(ic == inst) && !(ic.epi == inst.epi && ic.samex == inst.samex && n_classes > 1)) return SSW_ERR_BAD_ARG;
         if (inverse && (unsigned)(len >> desc[c].sub) != leff0) return SSW_ERR_BAD_ARG;      // po.n is shared
@@ -270,12 +252,12 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     ml.n_classes = (unsigned)n_classes; ml.L = L; ml.tiles_m = tiles_m; ml.tiles_n_total = tiles_n;
     PairOut po{out, tmp, (unsigned)w, (unsigned)h, (unsigned)(inverse ? leff0 : len), 0, 1, 2};
     po.tmp_out = tmp_out;
-    if (class_major && inverse && desc[0].kind >= 3 && desc[0].kind <= 8) { po.cm = dct_pair_efold_inv(len) ? 2u : 1u; po.cmt = dct_pair_class_tile(len); }
+    if (lay.class_major && inverse && desc[0].kind >= 3 && desc[0].kind <= 8) { po.cm = lay.rows_l2 ? 2u : 1u; po.cmt = lay.tile; }
     // level 2: T2 (written by kind 9, read by the half-length launches, kinds 3 / 4 sub 1) keeps the mod-4 class order, so
     // that those launches read runs instead of two doubles of every four
-    if (class_major && inverse && desc[0].kind == 9) po.cm = 1;
-    if (class_major && inverse && is_row && dct_pair_efold_inv(len) && (desc[0].kind == 3 || desc[0].kind == 4) && desc[0].sub == 1) po.tcm = 1;
-    if (class_major && !inverse) po.ft = dct_pair_class_tile(len);
+    if (lay.class_major && inverse && desc[0].kind == 9) po.cm = 1;
+    if (lay.class_major && inverse && is_row && lay.rows_l2 && (desc[0].kind == 3 || desc[0].kind == 4) && desc[0].sub == 1) po.tcm = 1;
+    if (lay.class_major && !inverse) po.ft = lay.tile;
     if (fuse_rows) {
         if (inst.samex || inst.epi != EPI_FWD || po.ft != 128) return SSW_ERR_BAD_ARG;
         po.cop = fuse->cop; po.cop_k16 = (unsigned)pair_kpad<double>(h / 8); po.cop_lines = (unsigned)(n_frames * w);
@@ -317,14 +299,6 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
 #undef SSW_LAUNCH_PAIR_BM
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
-}
-
-// One class per launch (the batch paths).
-int launch_dct_pair_gemm_f64(hipStream_t st, bool is_row, bool inverse, int kind, int sub, const double* x1, const double* x2,
-                             const double* y1, const double* y2, float* out, double* tmp, size_t n_frames, size_t w,
-                             size_t h, Epilogue ep, const RgbSink* sink, double* tmp_out, bool class_major) {
-    const PairClassDesc d{kind, sub, x1, x2, y1, y2};
-    return launch_dct_pair_gemm_multi_f64(st, is_row, inverse, 1, &d, out, tmp, n_frames, w, h, ep, sink, tmp_out, class_major);
 }
 
 // Forward row pass restricted to a gathered set of frequencies (pruned derived transform, prune.hip): one

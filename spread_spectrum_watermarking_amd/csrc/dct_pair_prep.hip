@@ -86,37 +86,6 @@ __global__ void make_rot_table_kernel(size_t n, double* out) {
     }
 }
 
-// first-level split through pair_rotate_kernel: any axis whose quarter length folds (rows and columns alike)
-// tile width of the class-major plane orders of a line of length len (dct_pair_common.hpp); SSW_CLASS_TILE=0: one tile
-// (the r3 order)
-// Forward row passes of 1280 columns or more run at LEVEL 2 (r4b / r4c; ssw_pipeline.hip build_pass): every operand folds or
-// rotates once more and all eight launches sum len/16 terms (240 at 4K: 79 % of peak against 84 % for len/8, at 2/3 of the
-// multiply-adds).  Measured a gain from 1280 x 720 up (smaller: not measured) -- once the plane between the passes is
-// class-major; in the natural order every launch writes 4-byte pieces 64 bytes apart (1080p before r4c: such launches took
-// 1.0 ms for 16 GFLOP).  SSW_EFOLD_MIN: A/B switch (minimum length).
-bool dct_pair_efold(size_t len) {
-    const size_t mn = (size_t)tuning(TUNE_EFOLD_MIN);
-    return dct_pair_can_deep_rows(len) && len >= mn;
-}
-// Inverse row passes of 1280 columns or more run at level 2 as well (r4c): the odd part's classes and the
-// quarter-length even part fold / rotate once more (dct_pair_prep_staged.hip, prep16_inv_rows_l2_kernel).
-// SSW_EFOLD_INV_MIN: A/B switch (minimum length).
-bool dct_pair_efold_inv(size_t len) {
-    const size_t mn = (size_t)tuning(TUNE_EFOLD_INV_MIN);
-    return dct_pair_can_deep_inv_rows(len) && dct_pair_prep_staged_rows_ok() && len >= mn;      // (len % 128 == 0: can_deep_inv_rows)
-}
-// Column passes of 720 rows or more (a multiple of 16) run at level 2 in both directions (r4c; the staged pre-passes only):
-// launches of K = H/16 = 135 at 4K run at 50 TFLOP/s against 64 for K = 270, but do half the multiply-adds (measured a gain
-// from 1280 x 720 up).  SSW_EFOLD_COLS_MIN: A/B switch.
-bool dct_pair_efold_cols(size_t h, size_t w, bool class_major) {
-    const size_t mn = (size_t)tuning(TUNE_EFOLD_COLS_MIN);
-    return dct_pair_can_deep_cols(h) && dct_pair_prep_staged_cols_ok(w, class_major) && h >= mn;
-}
-unsigned dct_pair_class_tile(size_t len) {
-    const bool one_tile = tuning(TUNE_CLASS_TILE) == 0;
-    return one_tile ? (unsigned)len : class_tile((unsigned)len);
-}
-bool dct_pair_can_split(size_t len, bool is_row) { (void)is_row; return len % 8 == 0 && len >= 128; }
 size_t dct_pair_split_kpad(size_t len) { return pair_kpad<double>(len / 4); }
 // doubles in the four split planes of a pass over n frames (the larger of the row and the column pass)
 size_t dct_pair_split_elems(size_t n_frames, size_t w, size_t h) {
@@ -1144,17 +1113,6 @@ size_t dct_pair_operand_elems(bool f64, size_t n_frames, size_t w, size_t h) {
     return a > b ? a : b;
 }
 
-bool dct_pair_can_run(bool f64, size_t n_frames, size_t w, size_t h, const float* in, const float* out) {
-    // an operand plane must stay below 4 GB (32-bit scalar offsets walk its k-blocks)
-    if (!f64 && !build_all_strategies()) return false;          // the f32 twin (dct_pair_f32.hip) is part of the diagnostic build only
-    return dct_rows_can_fold(w, in, out) && dct_cols_can_fold(w, h, in, out) && w % 8 == 0 && h % 8 == 0 &&
-           dct_pair_operand_elems(f64, n_frames, w, h) * (f64 ? 8 : 4) <= 0xFFFFFFFFull;
-}
-// second level along an axis of length len: quarter length a multiple of 4 (row passes read quads of a
-// line; the transposing column pre-pass only needs an even quarter), at least one k-step pair
-bool dct_pair_can_fold2(size_t len) { return len % 16 == 0 && len >= 64; }
-bool dct_pair_can_fold2_cols(size_t len) { return len % 8 == 0 && len >= 64; }
-
 template <typename T>
 static int prep_impl(hipStream_t st, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w, size_t h,
                      T* o1, T* o2) {
@@ -1238,9 +1196,6 @@ static int prep4_rgb_impl(hipStream_t st, int u8, const void* rgb, size_t n_fram
 
 // rows-first forward transform with two folding levels on the row axis: the first pre-pass straight
 // from the interleaved RGB frames (u8 or f32); ip / qp (both or neither) receive the I and Q planes.
-bool dct_pair_can_prep_from_rgb(size_t w, size_t h, const void* rgb, int u8) {
-    return w >= h && dct_pair_can_fold2(w) && (reinterpret_cast<uintptr_t>(rgb) & pix_align_mask(u8)) == 0;
-}
 int launch_dct_pair_prep4_rows_rgb(hipStream_t st, bool f64, int u8, const void* rgb, size_t n_frames, size_t w, size_t h,
                                    void* q1, void* q2, void* p, float* ip, float* qp) {
     return f64 ? prep4_rgb_impl<double>(st, u8, rgb, n_frames, w, h, (double*)q1, (double*)q2, (double*)p, ip, qp)
@@ -1270,7 +1225,6 @@ static int prep8_impl(hipStream_t st, int src_kind, const void* src, size_t n_fr
 }
 
 // third folding level along an axis of length len (forward row passes only)
-bool dct_pair_can_fold3(size_t len) { return len % 32 == 0 && len >= 128; }
 // src_kind: 0 = f32 plane, 1 = interleaved RGB f32, 2 = interleaved RGB u8 (ip / qp: I, Q planes out or null)
 int launch_dct_pair_prep8_rows(hipStream_t st, bool f64, int src_kind, const void* src, size_t n_frames, size_t w, size_t h,
                                void* r1, void* r2, void* m, void* p, float* ip, float* qp) {
@@ -1300,37 +1254,30 @@ int launch_dct_pair_prep8_cols(hipStream_t st, bool f64, const float* in, size_t
 
 // deep forward row pre-pass: src_kind 0 = f32 plane, 1 / 2 = interleaved RGB f32 / u8 (ip / qp: I, Q planes out or null);
 // base: 6 planes of lines * K8 doubles (AS BD AD BS R1 R2) followed by 4 planes of lines * K16 (AS2 BD2 AD2 BS2)
-bool dct_pair_can_deep_rows(size_t len) { const size_t mn = (size_t)tuning(TUNE_DEEP_MIN_ROWS); return len % 64 == 0 && len >= mn; }
 // 6 planes K8 wide + 4 K16 wide, or (forward row passes at level 2) 16 planes K16 wide
 size_t dct_pair_deep_elems(size_t lines, size_t len) {
     const size_t k8 = dct_pair_split_kpad(len), k16 = dct_pair_split_kpad(len / 2);
     return lines * (6 * k8 + 4 * k16 > 16 * k16 ? 6 * k8 + 4 * k16 : 16 * k16);
 }
 int launch_dct_pair_prep16_rows(hipStream_t st, int src_kind, const void* src, size_t n_frames, size_t w, size_t h, double* base,
-                                const double* rot1, const double* rot2, const double* rot3, float* ip, float* qp, bool unit_order) {
+                                const double* rot1, const double* rot2, const double* rot3, float* ip, float* qp, bool l2, bool unit_order) {
     if (n_frames == 0) return SSW_OK;
-    if (w > 0xFFFFFFull || h > 0xFFFFFFull || !dct_pair_can_deep_rows(w)) return SSW_ERR_BAD_DIMS;
+    if (w > 0xFFFFFFull || h > 0xFFFFFFull || w % 64 != 0) return SSW_ERR_BAD_DIMS;
     const unsigned K8 = (unsigned)dct_pair_split_kpad(w), K16 = (unsigned)dct_pair_split_kpad(w / 2);
     const unsigned tiles_e = (K16 + 31) / 32;
-    if (unit_order && (h % 16 != 0 || !dct_pair_efold(w))) return SSW_ERR_BAD_ARG;
+    if (unit_order && (h % 16 != 0 || !l2)) return SSW_ERR_BAD_ARG;
     const unsigned unit_hup = unit_order ? (unsigned)dct_pair_fused_units(h) : 0u;
     const size_t rows = unit_order ? n_frames * 16 * unit_hup : n_frames * h;       // operand lines
     const unsigned long long nblk = (unsigned long long)((rows + 31) / 32) * tiles_e;
     if (rows > 0xFFFFFFFFull || nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    DeepPlanes dp;
-    double* p = base;
-    const size_t p8 = rows * K8, p16 = rows * K16;
-    const unsigned efold = dct_pair_efold(w) ? 1u : 0u;
+    DeepPlanes dp = planes_of(base, rows, K8, K16);
+    const unsigned efold = l2 ? 1u : 0u;
     if (efold) {     // level 2: sixteen planes K16 wide, in this order (build_pass and the pruned pass index them by number)
-        void** const l2[16] = {&dp.asp, &dp.asm_, &dp.bdp, &dp.bdm, &dp.oap, &dp.obp, &dp.oam, &dp.obm,
+        void** const pl[16] = {&dp.asp, &dp.asm_, &dp.bdp, &dp.bdm, &dp.oap, &dp.obp, &dp.oam, &dp.obm,
                                &dp.r1p, &dp.r1m, &dp.r2a, &dp.r2b, &dp.as2, &dp.bd2, &dp.ad2, &dp.bs2};
-        for (int j = 0; j < 16; ++j) *l2[j] = p + (size_t)j * p16;
+        for (int j = 0; j < 16; ++j) *pl[j] = base + (size_t)j * rows * K16;
         dp.as = dp.bd = dp.ad = dp.bs = dp.r1 = dp.r2 = nullptr;
         if (!rot3) return SSW_ERR_BAD_ARG;
-    } else {
-        dp.as = p; dp.bd = p + p8; dp.ad = p + 2 * p8; dp.bs = p + 3 * p8; dp.r1 = p + 4 * p8; dp.r2 = p + 5 * p8;
-        p += 6 * p8;
-        dp.as2 = p; dp.bd2 = p + p16; dp.ad2 = p + 2 * p16; dp.bs2 = p + 3 * p16;
     }
     if (efold && dct_pair_prep_light_ok(w, rows))          // r5: the form that runs beside the GEMMs of the other lane (dct_pair_prep_light.hip)
         return launch_dct_pair_prep16_rows_light(st, src_kind, src, dp, rot1, rot2, rot3, ip, qp, rows, w, K16, unit_order ? (unsigned)h : 0u, unit_hup);
@@ -1346,98 +1293,74 @@ int launch_dct_pair_prep16_rows(hipStream_t st, int src_kind, const void* src, s
     return SSW_OK;
 }
 
-// deep forward column pre-pass (H % 16 == 0): same plane order as the row version, lines = n_frames * w
-bool dct_pair_can_deep_cols(size_t len) { const size_t mn = (size_t)tuning(TUNE_DEEP_MIN_COLS); return len % 16 == 0 && len >= mn; }
+// deep forward column pre-pass (H % 16 == 0): same plane order as the row version, lines = n_frames * w;
 // semi-deep: H % 8 == 0 but not % 16 (1080 rows): D split, SS folded a third time, SD left whole
-bool dct_pair_can_semi_deep_cols(size_t len) { const size_t mn = (size_t)tuning(TUNE_DEEP_MIN_COLS); return len % 8 == 0 && len % 16 != 0 && len >= mn; }
 size_t dct_pair_semi_deep_elems(size_t lines, size_t len) { return lines * (6 * dct_pair_split_kpad(len) + pair_kpad<double>(len / 2)); }
 int launch_dct_pair_prep16_cols(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                                const double* rot1, const double* rot2, bool class_major, const double* rot3) {
+                                const double* rot1, const double* rot2, const double* rot3, PrepFamily prep, const PairLayout& lay) {
     if (n_frames == 0) return SSW_OK;
-    const bool semi = dct_pair_can_semi_deep_cols(h);
-    if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull || !(dct_pair_can_deep_cols(h) || semi) || w % 4 != 0) return SSW_ERR_BAD_DIMS;
-    if (semi && class_major && !dct_pair_prep_staged_cols_ok(w, true)) return SSW_ERR_BAD_ARG;      // the r3 semi-deep kernels read the natural order only
+    const bool semi = h % 16 != 0, class_major = lay.class_major;
+    if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull || h % 8 != 0 || w % 4 != 0) return SSW_ERR_BAD_DIMS;
+    if (semi && class_major && prep == PrepFamily::R3) return SSW_ERR_BAD_ARG;      // the r3 semi-deep kernels read the natural order only
     const unsigned K8 = (unsigned)dct_pair_split_kpad(h);
     const unsigned K16 = semi ? (unsigned)pair_kpad<double>(h / 2) : (unsigned)dct_pair_split_kpad(h / 2);      // semi: width of the SD plane
-    if (dct_pair_efold_cols(h, w, class_major))
-        return launch_prep16_cols_l2(st, in, n_frames, w, h, base, rot1, rot2, rot3, class_major, class_major && dct_pair_efold(w), K16);
-    if (dct_pair_prep_staged_cols_ok(w, class_major))
-        return launch_prep16_cols_staged(st, in, n_frames, w, h, base, rot1, rot2, class_major, semi, K8, K16, dct_pair_efold(w));
+    if (prep == PrepFamily::L2)
+        return launch_prep16_cols_l2(st, in, n_frames, w, h, base, rot1, rot2, rot3, class_major, class_major && lay.rows_l2, K16);
+    if (prep == PrepFamily::Staged)
+        return launch_prep16_cols_staged(st, in, n_frames, w, h, base, rot1, rot2, class_major, semi, K8, K16, lay.rows_l2);
     const unsigned units = semi ? (unsigned)(((h / 8 + 1) / 2 + 3) & ~(size_t)3) : K16;
-    const unsigned ctile = dct_pair_class_tile(w);
+    const unsigned ctile = lay.tile;
     const unsigned cm = !class_major ? 0u : 1u;      // (the r3 per-class-run mode, 2, knew the ten-class order; lines of such lengths take the staged kernels now)
     const unsigned tiles_e = (units + 31) / 32, tiles_c = cm == 2 ? (unsigned)(w / 256) : (unsigned)((w + 31) / 32);
     const unsigned long long nblk = (unsigned long long)tiles_e * tiles_c * n_frames;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const size_t lines = n_frames * w;
-    DeepPlanes dp;
-    double* p = base;
-    const size_t p8 = lines * K8, p16 = lines * K16;
-    dp.as = p; dp.bd = p + p8; dp.ad = p + 2 * p8; dp.bs = p + 3 * p8; dp.r1 = p + 4 * p8; dp.r2 = p + 5 * p8;
-    p += 6 * p8;
-    dp.as2 = p; dp.bd2 = p + p16; dp.ad2 = p + 2 * p16; dp.bs2 = p + 3 * p16;      // semi: as2 = the SD plane, the others unused
+    const DeepPlanes dp = planes_of(base, n_frames * w, K8, K16);          // semi: as2 = the SD plane, the others unused
     if (semi) pair_prep16_cols_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, tiles_e, tiles_c, 0u, ctile, 0u);
-    else      pair_prep16_cols_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, tiles_e, tiles_c, cm, ctile, dct_pair_efold(w) ? 1u : 0u);
+    else      pair_prep16_cols_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, tiles_e, tiles_c, cm, ctile, lay.rows_l2 ? 1u : 0u);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
 
 // deep inverse pre-passes: same plane order (AS BD AD BS R1 R2 | AS2 BD2 AD2 BS2) with R1 = c[8q], R2 = c[8q+4]
-bool dct_pair_can_deep_inv_rows(size_t len) { const size_t mn = (size_t)tuning(TUNE_DEEP_MIN_ROWS); return len % 128 == 0 && len >= mn && len <= 128 * 256; }
-static DeepPlanes deep_planes(double* base, size_t lines, size_t len) {
-    const size_t p8 = lines * dct_pair_split_kpad(len), p16 = lines * dct_pair_split_kpad(len / 2);
-    DeepPlanes dp;
-    double* p = base;
-    dp.as = p; dp.bd = p + p8; dp.ad = p + 2 * p8; dp.bs = p + 3 * p8; dp.r1 = p + 4 * p8; dp.r2 = p + 5 * p8;
-    p += 6 * p8;
-    dp.as2 = p; dp.bd2 = p + p16; dp.ad2 = p + 2 * p16; dp.bs2 = p + 3 * p16;
-    return dp;
-}
 int launch_dct_pair_prep16_inv_rows(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                                    const double* rot1, const double* rot2, const double* rot3) {
+                                    const double* rot1, const double* rot2, const double* rot3, PrepFamily prep) {
     if (n_frames == 0) return SSW_OK;
-    if (!dct_pair_can_deep_inv_rows(w) || h > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
+    if (w % 128 != 0 || w > 128 * 256 || h > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
     const size_t rows = n_frames * h;
     if (rows > 0xFFFFFFFFull) return SSW_ERR_BAD_DIMS;
-    if (dct_pair_efold_inv(w))
+    if (prep == PrepFamily::L2)
         return launch_prep16_inv_rows_l2(st, in, rows, w, base, rot1, rot2, rot3, (unsigned)dct_pair_split_kpad(w / 2));
-    if (dct_pair_prep_staged_rows_ok())
+    if (prep == PrepFamily::Staged)
         return launch_prep16_inv_rows_staged(st, in, rows, w, base, rot1, rot2, (unsigned)dct_pair_split_kpad(w), (unsigned)dct_pair_split_kpad(w / 2));
     unsigned tp = 1;
     while (tp < w / 128) tp <<= 1;                                  // threads per line, <= 256
     const unsigned lpb = 256 / tp;
     const unsigned long long nblk = (rows + lpb - 1) / lpb;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    pair_prep16_inv_rows_kernel<double><<<(unsigned)nblk, 256, 0, st>>>(in, deep_planes(base, rows, w), rot1, rot2, (unsigned)rows, (unsigned)w,
+    pair_prep16_inv_rows_kernel<double><<<(unsigned)nblk, 256, 0, st>>>(in, planes_of(base, rows, dct_pair_split_kpad(w), dct_pair_split_kpad(w / 2)), rot1, rot2, (unsigned)rows, (unsigned)w,
                                                                        (unsigned)dct_pair_split_kpad(w), (unsigned)dct_pair_split_kpad(w / 2), tp);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
 int launch_dct_pair_prep16_inv_cols(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                                    const double* rot1, const double* rot2, bool class_major, const double* rot3) {
+                                    const double* rot1, const double* rot2, const double* rot3, PrepFamily prep, const PairLayout& lay) {
     if (n_frames == 0) return SSW_OK;
-    const bool semi = dct_pair_can_semi_deep_cols(h);
-    if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull || !(dct_pair_can_deep_cols(h) || semi)) return SSW_ERR_BAD_DIMS;
-    if (semi && class_major && !dct_pair_prep_staged_cols_ok(w, true)) return SSW_ERR_BAD_ARG;      // the r3 semi-deep kernels read the natural order only
+    const bool semi = h % 16 != 0, class_major = lay.class_major;
+    if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull || h % 8 != 0) return SSW_ERR_BAD_DIMS;
+    if (semi && class_major && prep == PrepFamily::R3) return SSW_ERR_BAD_ARG;      // the r3 semi-deep kernels read the natural order only
     const unsigned K8 = (unsigned)dct_pair_split_kpad(h);
     const unsigned K16 = semi ? (unsigned)pair_kpad<double>(h / 2) : (unsigned)dct_pair_split_kpad(h / 2);      // semi: width of the c[4q+2] plane
-    if (dct_pair_efold_cols(h, w, class_major))
-        return launch_prep16_inv_cols_l2(st, in, n_frames, w, h, base, rot1, rot2, rot3, class_major, class_major && dct_pair_efold_inv(w), K16);
-    if (dct_pair_prep_staged_cols_ok(w, class_major))
-        return launch_prep16_inv_cols_staged(st, in, n_frames, w, h, base, rot1, rot2, class_major, semi, K8, K16, class_major && dct_pair_efold_inv(w));
+    if (prep == PrepFamily::L2)
+        return launch_prep16_inv_cols_l2(st, in, n_frames, w, h, base, rot1, rot2, rot3, class_major, class_major && lay.rows_l2, K16);
+    if (prep == PrepFamily::Staged)
+        return launch_prep16_inv_cols_staged(st, in, n_frames, w, h, base, rot1, rot2, class_major, semi, K8, K16, class_major && lay.rows_l2);
     // groups of 8 units: K16 / 8 covers the padding of the n/16-wide planes; semi: the units (and the R planes' padding up to K8)
     const unsigned groups = semi ? (unsigned)((K8 / 2 + 7) / 8) : K16 / 8, tiles_c = (unsigned)((w + 31) / 32);
     const unsigned long long nblk = (unsigned long long)groups * tiles_c * n_frames;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const size_t lines = n_frames * w;
-    DeepPlanes dp;
-    double* p = base;
-    const size_t p8 = lines * K8, p16 = lines * K16;
-    dp.as = p; dp.bd = p + p8; dp.ad = p + 2 * p8; dp.bs = p + 3 * p8; dp.r1 = p + 4 * p8; dp.r2 = p + 5 * p8;
-    p += 6 * p8;
-    dp.as2 = p; dp.bd2 = p + p16; dp.ad2 = p + 2 * p16; dp.bs2 = p + 3 * p16;      // semi: as2 = the c[4q+2] plane, the others unused
+    const DeepPlanes dp = planes_of(base, n_frames * w, K8, K16);          // semi: as2 = the c[4q+2] plane, the others unused
     if (semi) pair_prep16_inv_cols_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, groups, tiles_c, 0u, (unsigned)w);
-    else      pair_prep16_inv_cols_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, groups, tiles_c, class_major ? (dct_pair_efold_inv(w) ? 2u : 1u) : 0u, dct_pair_class_tile(w));
+    else      pair_prep16_inv_cols_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, groups, tiles_c, class_major ? (lay.rows_l2 ? 2u : 1u) : 0u, lay.tile);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }

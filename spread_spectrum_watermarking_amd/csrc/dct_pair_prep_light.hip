@@ -136,7 +136,7 @@ __global__ __launch_bounds__(16 * LINES, 8) void pair_prep16_rows_light_kernel(
 }  // namespace
 
 bool dct_pair_prep_light_ok(size_t w, size_t lines) {
-    return tuning(TUNE_PREP_LIGHT) != 0 && w % 64 == 0 && dct_pair_efold(w) && lines * dct_pair_split_kpad(w / 2) * sizeof(double) <= 0xFFFFFFFFull;
+    return tuning(TUNE_PREP_LIGHT) != 0 && w % 64 == 0 && lines * dct_pair_split_kpad(w / 2) * sizeof(double) <= 0xFFFFFFFFull;
 }
 
 int launch_dct_pair_prep16_rows_light(hipStream_t st, int src_kind, const void* src, const DeepPlanes& dp, const double* rot1,

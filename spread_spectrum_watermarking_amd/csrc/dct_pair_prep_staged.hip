@@ -20,7 +20,7 @@ namespace ssw {
 
 namespace {
 
-constexpr unsigned CT = 128;                  // operand lines of a column-pass block = the class-major tile
+constexpr unsigned CT = PREP_STAGED_TILE;     // operand lines of a column-pass block = the class-major tile
 constexpr unsigned SLABD = CT * 8;            // doubles of one LDS slab: CT lines x one 64-byte k-block piece
 
 // Slab addressing: double j of line l sits at l * 8 + (j ^ sw(l)).  sw() spreads the lines that the 16 lanes of a
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256) void prep16_cols_staged_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------
-// Forward column pass at LEVEL 2 (r4c; H % 16 == 0, dct_pair_efold_cols): the thread of unit e holds the 16 rows of unit e
+// Forward column pass at LEVEL 2 (r4c; H % 16 == 0, PrepFamily::L2): the thread of unit e holds the 16 rows of unit e
 // AND of its mirror unit H/8 - 1 - e, so the extra fold / rotation of pair_prep16_rows_kernel's level 2 happens in
 // registers and the mirrored round B disappears.  Sixteen planes K16 wide, numbered like the row pass's:
 //   round A (exact)     0 .. 3 AS+ AS- BD+ BD-,  8 9 R1+ R1-
@@ -475,7 +475,7 @@ __global__ __launch_bounds__(256) void prep16_inv_cols_staged_kernel(const float
 }
 
 // ---------------------------------------------------------------------------------------------
-// Inverse column pass at LEVEL 2 (r4c; dct_pair_efold_cols): unit k < H/16 with its mirror unit H/8 - 1 - k in one thread.
+// Inverse column pass at LEVEL 2 (r4c; PrepFamily::L2): unit k < H/16 with its mirror unit H/8 - 1 - k in one thread.
 //   task < tasks0 (k-blocks of H/16 units): rows 2k+1, H/2-1-2k, H/2+2k+1, H-1-2k of unit k and of unit H/8-1-k -> planes
 //       0 .. 7; rows 16k, 16k+8 -> planes 8, 9; rows 8k+4, H-4-8k (R2 at k and at its mirror) -> planes 10, 11
 //   then tasks1 k-blocks of AS2 BD2 AD2 BS2 (planes 12 .. 15) as at level 1.  Four rounds of three slabs.
@@ -722,7 +722,7 @@ __global__ __launch_bounds__(256) void prep16_inv_rows_staged_kernel(const float
 }
 
 // ---------------------------------------------------------------------------------------------
-// Inverse row pass at LEVEL 2 (r4c; n % 128 == 0, dct_pair_efold_inv): the operands of launches that all sum n/16 terms
+// Inverse row pass at LEVEL 2 (r4c; n % 128 == 0, PrepFamily::L2): the operands of launches that all sum n/16 terms
 // (build_pass, "deep inverse").  Sixteen planes K16 wide, numbered like the forward level-2 pass:
 //   0 .. 3   AS+ AS- BD+ BD-      class E of the odd part c[2k+1] folded once more (exact)
 //   4 .. 7   (a, b) of AD plus / minus (a, b) of the reversed BS: class O rotated once more
@@ -918,27 +918,7 @@ __global__ __launch_bounds__(256) void prep16_inv_rows_l2_kernel(const float* __
     }
 }
 
-bool staged_enabled() {
-    return tuning(TUNE_PREP_STAGED) != 0;
-}
-
-DeepPlanes planes_of(double* base, size_t lines, unsigned K8, unsigned K16) {
-    DeepPlanes dp;
-    double* p = base;
-    const size_t p8 = lines * K8, p16 = lines * K16;
-    dp.as = p; dp.bd = p + p8; dp.ad = p + 2 * p8; dp.bs = p + 3 * p8; dp.r1 = p + 4 * p8; dp.r2 = p + 5 * p8;
-    p += 6 * p8;
-    dp.as2 = p; dp.bd2 = p + p16; dp.ad2 = p + 2 * p16; dp.bs2 = p + 3 * p16;
-    return dp;
-}
-
 }  // namespace
-
-// The staged kernels take: natural column order (any W % 4 == 0), or class-major tiles of exactly CT columns.
-bool dct_pair_prep_staged_cols_ok(size_t w, bool class_major) {
-    return staged_enabled() && w % 4 == 0 && w >= 4 && (!class_major || dct_pair_class_tile(w) == CT);
-}
-bool dct_pair_prep_staged_rows_ok() { return staged_enabled(); }
 
 int launch_prep16_cols_staged(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
                               const double* rot1, const double* rot2, bool class_major, bool semi, unsigned K8, unsigned K16, bool efold) {

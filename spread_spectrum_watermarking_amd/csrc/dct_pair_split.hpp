@@ -42,7 +42,7 @@ struct DeepPlanes {        // device pointers of one pass's operand planes
     void *as, *bd, *ad, *bs;         // K8 wide
     void *r1, *r2;                   // K8 wide
     void *as2, *bd2, *ad2, *bs2;     // K16 wide
-    // forward ROW passes at level 2 (r4b, dct_pair_efold): twelve planes K16 wide replace the six K8 wide ones --
+    // forward ROW passes at level 2 (r4b, PassStrategy::DeepL2): twelve planes K16 wide replace the six K8 wide ones --
     //   asp asm_ bdp bdm   class E folded once more: AS +/- its mirror, BD +/- its mirror (exact)
     //   oap obp oam obm    class O (a DCT-IV of AD and a DST-IV of BS, length n/8) rotated once more: (a, b) of AD plus /
     //                      minus (a, b) of the reversed BS
@@ -52,9 +52,18 @@ struct DeepPlanes {        // device pointers of one pass's operand planes
     void *oap = nullptr, *obp = nullptr, *oam = nullptr, *obm = nullptr;
     void *r1p = nullptr, *r1m = nullptr, *r2a = nullptr, *r2b = nullptr;
 };
+// the planes in their order from `base`: AS BD AD BS R1 R2 (lines * K8 each), then AS2 BD2 AD2 BS2 (lines * K16 each)
+inline DeepPlanes planes_of(double* base, size_t lines, size_t K8, size_t K16) {
+    DeepPlanes dp;
+    const size_t p8 = lines * K8, p16 = lines * K16;
+    double* q = base + 6 * p8;
+    dp.as = base; dp.bd = base + p8; dp.ad = base + 2 * p8; dp.bs = base + 3 * p8; dp.r1 = base + 4 * p8; dp.r2 = base + 5 * p8;
+    dp.as2 = q; dp.bd2 = q + p16; dp.ad2 = q + 2 * p16; dp.bs2 = q + 3 * p16;
+    return dp;
+}
 
 // dct_pair_prep_light.hip: the level-2 row pre-pass in the form that fits beside the GEMMs
-bool dct_pair_prep_light_ok(size_t w, size_t lines);
+bool dct_pair_prep_light_ok(size_t w, size_t lines);          // of a row pass at level 2
 int launch_dct_pair_prep16_rows_light(hipStream_t st, int src_kind, const void* src, const DeepPlanes& dp, const double* rot1,
                                       const double* rot2, const double* rot3, float* ip, float* qp, size_t rows, size_t w, unsigned K16,
                                       unsigned unit_h, unsigned unit_hup);
@@ -65,7 +74,7 @@ struct DerivedFusedClass {
     unsigned cap, off;         // gathered rows = compact columns off .. off + cap - 1
     bool split;
 };
-bool dct_pair_derived_fused_ok(size_t w, unsigned n_classes, const DerivedFusedClass* cls);
+bool dct_pair_derived_fused_fits(unsigned n_classes, const DerivedFusedClass* cls);
 int launch_dct_pair_derived_fused(hipStream_t st, int src_kind, const void* rgb, size_t lines, size_t w, const double* rot1,
                                   const double* rot2, const double* rot3, unsigned n_classes, const DerivedFusedClass* cls,
                                   float* out, unsigned cap_total);

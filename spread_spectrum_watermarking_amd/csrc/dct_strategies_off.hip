@@ -8,13 +8,6 @@
 
 namespace ssw {
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-// the shape / alignment conditions of the folded transforms (the operand-ready path asks for them too)
-bool dct_rows_can_fold(size_t w, const float* in, const float* out) { return w >= 16 && (w % 8 == 0) && aligned16(in) && aligned16(out); }
-bool dct_cols_can_fold(size_t w, size_t h, const float* in, const float* out) {
-    return h >= 16 && (h % 8 == 0) && (w % 4 == 0) && aligned16(in) && aligned16(out);
-}
-
 size_t half_basis_kpad(size_t n) { return ((n / 2 + 15) / 16) * 16; }        // sizes an allocation only (get_basis kinds 1 / 2 are never requested)
 int launch_make_half_basis_f32(hipStream_t, size_t, bool, int, float*) { return SSW_ERR_UNSUPPORTED; }
 int launch_make_half_basis_f64(hipStream_t, size_t, bool, int, double*) { return SSW_ERR_UNSUPPORTED; }

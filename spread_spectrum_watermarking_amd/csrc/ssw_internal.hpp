@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ssw.h"
+#include "dct_plan.hpp"
 
 namespace ssw {
 
@@ -68,8 +69,6 @@ int launch_make_half_basis_f32(hipStream_t st, size_t n, bool inverse, int parit
 // false in the default build: in-kernel folding (dct_folded*.hip) and the f32 operand-ready twin (dct_pair_f32.hip) are not
 // compiled in (dct_strategies_off.hip); `make ALL_STRATEGIES=1` builds the diagnostic library with every strategy
 bool build_all_strategies();
-bool dct_rows_can_fold(size_t w, const float* in, const float* out);
-bool dct_cols_can_fold(size_t w, size_t h, const float* in, const float* out);
 int launch_dct_rows_folded_f32(hipStream_t st, bool inverse, const float* in, float* out, size_t rows,
                                size_t w, const float* b_even, const float* b_odd, Epilogue ep);
 int launch_dct_cols_folded_f32(hipStream_t st, bool inverse, const float* in, float* out, size_t n_frames,
@@ -87,9 +86,6 @@ int launch_dct_cols_folded_f64(hipStream_t st, bool inverse, const float* in, fl
 // precision (f64 flag), the half bases are cached in the same layout.
 size_t dct_pair_kpad(bool f64, size_t n);                               // row stride of operands / bases of a length-n axis
 size_t dct_pair_operand_elems(bool f64, size_t n_frames, size_t w, size_t h);   // elements per operand plane
-bool dct_pair_can_run(bool f64, size_t n_frames, size_t w, size_t h, const float* in, const float* out);
-bool dct_pair_can_fold2(size_t len);
-bool dct_pair_can_fold2_cols(size_t len);   // column passes: H % 8 == 0 suffices (1080 rows)
 int launch_make_half_basis_blocked(hipStream_t st, bool f64, size_t n, bool inverse, int parity, void* out);
 // one level: (S, D) forward / (E, O) inverse
 int launch_dct_pair_prep(hipStream_t st, bool f64, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w,
@@ -105,12 +101,10 @@ enum { SSW_PIX_F32 = 0, SSW_PIX_U8 = 1, SSW_PIX_U16 = 2 };
 inline size_t pix_bytes(int fmt) { return fmt == SSW_PIX_U8 ? 1 : fmt == SSW_PIX_U16 ? 2 : 4; }          // per sample
 inline unsigned pix_align_mask(int fmt) { return fmt == SSW_PIX_U8 ? 3u : fmt == SSW_PIX_U16 ? 7u : 15u; }   // of a 4-pixel load
 inline int pix_src_kind(int fmt) { return fmt + 1; }                     // SRC of the row pre-passes: 1 f32, 2 u8, 3 u16
-bool dct_pair_can_prep_from_rgb(size_t w, size_t h, const void* rgb, int u8);
 int launch_dct_pair_prep4_rows_rgb(hipStream_t st, bool f64, int u8, const void* rgb, size_t n_frames, size_t w, size_t h,
                                    void* q1, void* q2, void* p, float* ip, float* qp);
 // three levels on a forward row pass: (SSS, SS-) [kpad(w/4) wide], S- [kpad(w/2)], x- [kpad(w)] from an f32
 // plane (src_kind 0) or interleaved RGB f32 / u8 (1 / 2; ip / qp: I, Q planes out or null)
-bool dct_pair_can_fold3(size_t len);
 int launch_dct_pair_prep8_rows(hipStream_t st, bool f64, int src_kind, const void* src, size_t n_frames, size_t w, size_t h,
                                void* r1, void* r2, void* m, void* p, float* ip, float* qp);
 // Writer::result fused into the last inverse pass (EPI_INV_O_RGB): the frames' I / Q planes and the RGB output
@@ -122,22 +116,18 @@ struct RgbSink {
 };
 int launch_dct_pair_prep8_cols(hipStream_t st, bool f64, const float* in, size_t n_frames, size_t w, size_t h,
                                void* r1, void* r2, void* m, void* p);
-// kind 0: one folding level; 1 / 2: the even / odd half of two levels; sub: see dct_pair_f64.hip;
-// sink (inverse column pass, kind 2 only): colour conversion in the epilogue instead of storing Y
-int launch_dct_pair_gemm_f64(hipStream_t st, bool is_row, bool inverse, int kind, int sub, const double* x1, const double* x2,
-                             const double* y1, const double* y2, float* out, double* tmp, size_t n_frames, size_t w,
-                             size_t h, Epilogue ep, const RgbSink* sink = nullptr, double* tmp_out = nullptr, bool class_major = false);
 // r5, fused forward transform: how a launch takes part.
 //   FUSE_ROWS_COP    row launch over the unit-ordered, padded lines whose epilogue writes the sixteen column-operand planes
 //                    `cop`; needs the rotation tables of H, H/2, H/4
 //   FUSE_COLS        column launch behind such a row pass: its 128-line tiles are in the row launches' class-major order
 enum { FUSE_ROWS_COP = 1, FUSE_COLS = 2 };
 struct FuseCols { int mode = 0; double* cop = nullptr; const double *rot1 = nullptr, *rot2 = nullptr, *rot3 = nullptr; };
-// several classes (same lines, same template instance) in one launch: single frames, whose launches are too small alone
+// one or several classes (same lines, same template instance) in one launch: kind 0 one folding level, 1 / 2 the even / odd
+// half of two levels, sub: see dct_pair_f64.hip; sink (last inverse column pass): colour conversion in the epilogue
 struct PairClassDesc { int kind, sub; const double *x1, *x2, *y1, *y2; };
 int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, int n_classes, const PairClassDesc* desc, float* out,
                                    double* tmp, size_t n_frames, size_t w, size_t h, Epilogue ep, const RgbSink* sink = nullptr,
-                                   double* tmp_out = nullptr, bool class_major = false, const FuseCols* fuse = nullptr);
+                                   double* tmp_out = nullptr, const PairLayout& layout = PairLayout(), const FuseCols* fuse = nullptr);
 int launch_dct_pair_gemm_f32(hipStream_t st, bool is_row, bool inverse, int kind, int sub, const float* x1, const float* x2,
                              const float* y1, const float* y2, float* out, float* tmp, size_t n_frames, size_t w,
                              size_t h, Epilogue ep, const RgbSink* sink = nullptr);
@@ -156,23 +146,16 @@ int launch_dct_pair_gemm_rows_subset_merged_f64(hipStream_t st, const PairSubset
                                                 unsigned out_stride, size_t lines);
 // split odd half (f64 only; dct_pair_prep.hip "Split odd half"): quarter-length cosine / sine bases (which: 0 cosE, 1 sinE,
 // 2 cosO, 3 sinO), the rotation table of an axis, and the pass that turns an odd operand plane into AS | BD | AD | BS
-bool dct_pair_can_split(size_t len, bool is_row);
 size_t dct_pair_split_kpad(size_t len);
 // tuning.hip: the process-wide table of strategy thresholds / A-B switches (ssw_tuning_set, include/ssw.h)
 enum { TUNE_EFOLD_MIN, TUNE_EFOLD_INV_MIN, TUNE_EFOLD_COLS_MIN, TUNE_CLASS_TILE, TUNE_DEEP_MIN_ROWS, TUNE_DEEP_MIN_COLS, TUNE_PREP_STAGED,
        TUNE_MERGE_MAX_LINES, TUNE_BN32, TUNE_BAND_SPLIT, TUNE_FUSE_COLS, TUNE_UPLOAD_BANDS, TUNE_SPECULATE_K, TUNE_PREP_LIGHT, TUNE_LANE_STAGGER, TUNE_DERIVED_FUSED, TUNE_TILE48, TUNE_COUNT };
 long long tuning(int which);
-unsigned dct_pair_class_tile(size_t len);               // tile width of the class-major plane orders (dct_pair_common.hpp)
-bool dct_pair_efold(size_t len);                        // forward row passes of this length run at level 2 (r4b)
-bool dct_pair_efold_inv(size_t len);                    // inverse row passes of this length run at level 2 (r4c)
-bool dct_pair_efold_cols(size_t h, size_t w, bool class_major);      // column passes (both directions) of h rows run at level 2 (r4c)
 int launch_prep16_cols_l2(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
                           const double* rot1, const double* rot2, const double* rot3, bool class_major, bool in_l2, unsigned K16);
 int launch_prep16_inv_cols_l2(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
                               const double* rot1, const double* rot2, const double* rot3, bool class_major, bool in_l2, unsigned K16);
-// LDS-staged forms of the deep pre-passes (dct_pair_prep_staged.hip; SSW_PREP_STAGED=0 keeps the r3 kernels)
-bool dct_pair_prep_staged_cols_ok(size_t w, bool class_major);
-bool dct_pair_prep_staged_rows_ok();
+// LDS-staged forms of the deep pre-passes (dct_pair_prep_staged.hip; PrepFamily::R3 keeps the r3 kernels)
 int launch_prep16_cols_staged(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
                               const double* rot1, const double* rot2, bool class_major, bool semi, unsigned K8, unsigned K16, bool efold);
 int launch_prep16_inv_cols_staged(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
@@ -188,25 +171,20 @@ int launch_make_rot_table(hipStream_t st, size_t n, double* out);
 int launch_dct_pair_rotate(hipStream_t st, const double* p, const double* rot, double* sp, size_t lines, size_t len);
 // deep forward row pre-pass (len % 64 == 0): D and SD split, SS folded a third time, in one sweep over the source
 // (f32 plane or interleaved RGB); base: AS BD AD BS R1 R2 (lines * split_kpad(len) each), AS2 BD2 AD2 BS2 (lines * split_kpad(len/2))
-bool dct_pair_can_deep_rows(size_t len);
-bool dct_pair_can_deep_cols(size_t len);                 // H % 16 == 0
-bool dct_pair_can_deep_inv_rows(size_t len);             // W % 128 == 0
-bool dct_pair_can_semi_deep_cols(size_t len);            // H % 8 == 0, not % 16: launch_dct_pair_prep16_cols leaves SD whole
 size_t dct_pair_semi_deep_elems(size_t lines, size_t len);
-// deep inverse pre-passes (coefficient plane -> the same ten planes; R1 = c[8q], R2 = c[8q+4])
+// deep inverse pre-passes (coefficient plane -> the same ten planes; R1 = c[8q], R2 = c[8q+4]); `prep` / `lay`: of the plan
 int launch_dct_pair_prep16_inv_rows(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                                    const double* rot1, const double* rot2, const double* rot3 = nullptr);
+                                    const double* rot1, const double* rot2, const double* rot3, PrepFamily prep);
 int launch_dct_pair_prep16_inv_cols(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                                    const double* rot1, const double* rot2, bool class_major = false, const double* rot3 = nullptr);
+                                    const double* rot1, const double* rot2, const double* rot3, PrepFamily prep, const PairLayout& lay);
 int launch_dct_pair_prep16_cols(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                                const double* rot1, const double* rot2, bool class_major = false, const double* rot3 = nullptr);
+                                const double* rot1, const double* rot2, const double* rot3, PrepFamily prep, const PairLayout& lay);
 size_t dct_pair_deep_elems(size_t lines, size_t len);
+// l2: the row pass runs at level 2 (sixteen planes K16 wide); unit_order: the fused transform's line order (needs l2)
 int launch_dct_pair_prep16_rows(hipStream_t st, int src_kind, const void* src, size_t n_frames, size_t w, size_t h, double* base,
-                                const double* rot1, const double* rot2, const double* rot3, float* ip, float* qp, bool unit_order = false);
-// r5, fused forward transform: units per frame of the row pass's line order (H/16 rounded up to whole k-blocks of 8) and
-// whether a transform of n frames takes it (dct_pair_f64.hip)
+                                const double* rot1, const double* rot2, const double* rot3, float* ip, float* qp, bool l2, bool unit_order = false);
+// r5, fused forward transform: units per frame of the row pass's line order (H/16 rounded up to whole k-blocks of 8)
 inline size_t dct_pair_fused_units(size_t h) { return ((h / 16 + 7) / 8) * 8; }
-bool dct_pair_can_fuse_cols(size_t n_frames, size_t w, size_t h);
 
 int launch_dct_pair_gemm_rows_subset_f32(hipStream_t st, const float* x, const float* y, unsigned cap, unsigned Kp, float* out,
                                          unsigned out_stride, unsigned off, size_t lines);
@@ -412,3 +390,4 @@ struct ssw_ctx {
     hipStream_t tail_stream = nullptr;
     bool tail_fresh = false;
 };
+namespace ssw { inline PlanSettings plan_settings(const ssw_ctx* ctx) { return PlanSettings{ctx->fold, ctx->fold_level, ctx->split}; } }

@@ -274,11 +274,16 @@ size_t effective_chunk(const ssw_ctx* ctx, size_t w, size_t h, size_t n_frames) 
 // ---- the 2-D transform as a chain ---------------------------------------------------------------------
 namespace {
 
+bool aligned_planes(const float* a, const float* b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0; }
+PairClassDesc D(int kind, int sub, const void* x1, const void* x2, const void* y1, const void* y2) {
+    return {kind, sub, (const double*)x1, (const double*)x2, (const double*)y1, (const double*)y2};
+}
+// one launch of the operand-ready GEMM in the pass's precision (the paths the f32 twin of the diagnostic build shares)
 int pair_gemm(hipStream_t st, bool f64, bool is_row, bool inverse, int kind, int sub, const void* x1, const void* x2,
               const void* y1, const void* y2, float* dst, void* tmpE, size_t n, size_t w, size_t h, Epilogue ep,
-              const RgbSink* sink = nullptr, void* tmp_out = nullptr, bool class_major = false) {
-    return f64 ? launch_dct_pair_gemm_f64(st, is_row, inverse, kind, sub, (const double*)x1, (const double*)x2, (const double*)y1,
-                                          (const double*)y2, dst, (double*)tmpE, n, w, h, ep, sink, (double*)tmp_out, class_major)
+              const RgbSink* sink = nullptr) {
+    const PairClassDesc d = D(kind, sub, x1, x2, y1, y2);
+    return f64 ? launch_dct_pair_gemm_multi_f64(st, is_row, inverse, 1, &d, dst, (double*)tmpE, n, w, h, ep, sink)
                : launch_dct_pair_gemm_f32(st, is_row, inverse, kind, sub, (const float*)x1, (const float*)x2, (const float*)y1,
                                           (const float*)y2, dst, (float*)tmpE, n, w, h, ep, sink);
 }
@@ -293,575 +298,477 @@ double pair_gemm_flop(bool is_row, int kind, int sub, size_t n, size_t w, size_t
     return 4.0 * lines * np * k;
 }
 
-// doubles of the lane's sixth operand buffer: the split planes of either pass, or the deep row pre-pass's ten planes
-size_t split_scratch_elems(size_t n, size_t w, size_t h) {
-    size_t e = dct_pair_split_elems(n, w, h);
-    if (dct_pair_can_deep_rows(w) || dct_pair_can_deep_inv_rows(w)) e = std::max(e, dct_pair_deep_elems(n * h, w));
-    if (dct_pair_can_deep_cols(h)) e = std::max(e, dct_pair_deep_elems(n * w, h));
-    if (dct_pair_can_fuse_cols(n, w, h))
-        e = std::max(e, dct_pair_deep_elems(n * 16 * dct_pair_fused_units(h), w));                                      // unit-ordered, padded lines
-    if (dct_pair_can_semi_deep_cols(h)) e = std::max(e, dct_pair_semi_deep_elems(n * w, h));
-    return e;
+// What the builders of a pass share: the pass, its plan and what both its stages account.  Held by value in the stages.
+struct PassBuild {
+    ssw_ctx* ctx; Xform x; PassPlan p;
+    bool first_pass, is_row, inverse, f64, from_rgb;
+    size_t n, w, h, len, lines;
+    const float* src; float* dst; Epilogue ep;
+    int st_pass, st_main, st_prep;
+    double px, esz, prep_bytes, out_bpp;
+    // algorithmic bytes of the pass's GEMM launches (ssw_ctx_get_traffic): the operand planes in (one element per pixel), the
+    // f32 result out -- or, in the last pass of Writer::result, I and Q in and the RGB frame out -- plus `xch` bytes per
+    // pixel that the dependent launches of an inverse pass write and read back as doubles (A1: 1 + 1, T2: 2 + 2, E: 4 + 4)
+    double gemm_bytes(double xch) const { return px * (esz + xch + out_bpp); }
+    double flop(int kind, int sub) const { return pair_gemm_flop(is_row, kind, sub, n, w, h); }
+    // the row launches write the plane between the passes class-major; the column launches read operands of their own
+    PairLayout gemm_layout() const { return is_row ? p.layout : PairLayout(); }
+    int gemm(hipStream_t st, int nc, const PairClassDesc* d, void* tmp = nullptr, void* tmp_out = nullptr, const RgbSink* sink = nullptr,
+             const PairLayout& lay = PairLayout()) const {
+        return launch_dct_pair_gemm_multi_f64(st, is_row, inverse, nc, d, dst, (double*)tmp, n, w, h, ep, sink, (double*)tmp_out, lay);
+    }
+    int rgb_kind() const { return from_rgb ? pix_src_kind(x.rgb_u8) : 0; }
+    const void* prep_src() const { return from_rgb ? x.rgb : (const void*)src; }
+    float* prep_i() const { return from_rgb ? x.iq_i : nullptr; }
+    float* prep_q() const { return from_rgb ? x.iq_q : nullptr; }
+};
+
+// The classes of one stage: one launch over all of them when the pass merges them, else class by class -- with the main-stage
+// timer around the last one when the pass has one (st_main >= 0).
+template <class Launch>
+int launch_classes(ssw_ctx* ctx, hipStream_t st, bool merge, int nc, const PairClassDesc* d, Launch launch, int st_main = -1,
+                   double f_main = 0.0) {
+    if (merge) return launch(nc, d);
+    for (int c = 0; c + 1 < nc; ++c) SSW_TRY(launch(1, &d[c]));
+    if (st_main < 0) return launch(1, &d[nc - 1]);
+    StageTimer tm(ctx, st_main, st, f_main);
+    return launch(1, &d[nc - 1]);
 }
 
-// Passes of at most this many lines run the classes of a stage as ONE launch (a single frame's launches are too small alone).
-// SSW_MERGE_MAX_LINES: A/B switch.
-static size_t merge_max_lines() {
-    return (size_t)tuning(TUNE_MERGE_MAX_LINES);
+// Writer::result: the last pass of an inverse transform (a column pass) converts to RGB in its epilogue
+RgbSink rgb_sink(const PassBuild& b, bool* fused_rgb) {
+    RgbSink sink;
+    if (b.inverse && !b.first_pass && !b.is_row && b.x.rgb_out && b.x.iq_i && b.x.iq_q) {
+        sink.iq_i = b.x.iq_i; sink.iq_q = b.x.iq_q; sink.rgb = b.x.rgb_out; sink.u8 = b.x.rgb_out_u8;
+        if (fused_rgb) *fused_rgb = true;
+    }
+    return sink;
 }
 
-// Can the column pre-pass of an `fh`-row plane read the class-major order a deep row pass leaves (dct_pair_common.hpp)?  The
-// deep kernels all can; of the semi-deep ones (fh % 16 == 8: 1080 rows) only the LDS-staged forms.
-static bool cols_read_class_major(size_t fh, size_t w) {
-    // (dct_pair_can_split: the column pass reaches its deep / semi-deep branch only through the split -- fh >= 128 whatever the thresholds say)
-    return dct_pair_can_fold2_cols(fh) && dct_pair_can_split(fh, false) &&
-           (dct_pair_can_deep_cols(fh) || (dct_pair_can_semi_deep_cols(fh) && dct_pair_prep_staged_cols_ok(w, true)));
+// the operands and bases every pair strategy uses: the k-blocked half bases of the whole length and, with the split, its
+// quarter-length cosine / sine bases, the rotation table and the lane's sixth operand buffer (planes K8 / K16 wide)
+struct PairBases {
+    size_t bytes = 0, p8 = 0, p16 = 0;
+    const void *b0 = nullptr, *b1 = nullptr, *sb[4] = {}, *rot = nullptr;
+    double* sp = nullptr;
+    PairClassDesc e() const { return D(3, 0, sp, sp + p8, sb[0], sb[1]); }                // the split odd half: AS x cosE, BD x sinE
+    PairClassDesc o() const { return D(4, 0, sp + 2 * p8, sp + 3 * p8, sb[2], sb[3]); }   // AD x cosO, BS x sinO
+    PairClassDesc r1(const void* e0, const void* e1) const { return D(1, 1, sp + 4 * p8, sp + 5 * p8, e0, e1); }   // c[8q] | c[8q+4]
+};
+int pair_bases(const PassBuild& b, ssw_ctx::Lane& ws, PairBases& pb) {
+    ssw_ctx* ctx = b.ctx;
+    pb.bytes = dct_pair_operand_elems(b.f64, b.n, b.w, b.h) * (size_t)b.esz;
+    SSW_TRY(get_basis(ctx, b.len, b.inverse, b.f64, 3, &pb.b0));        // k-blocked half bases
+    SSW_TRY(get_basis(ctx, b.len, b.inverse, b.f64, 4, &pb.b1));
+    if (!b.p.split) return SSW_OK;
+    for (int i = 0; i < 4; ++i) SSW_TRY(get_basis(ctx, b.len, b.inverse, true, i == 1 ? 10 : 5 + i, &pb.sb[i]));      // 10: sinE for launches
+    SSW_TRY(get_basis(ctx, b.len, false, true, 9, &pb.rot));
+    SSW_TRY(grow(ws.operand[5], split_scratch_elems(b.n, b.w, b.h) * sizeof(double)));
+    pb.sp = (double*)ws.operand[5].p;
+    pb.p8 = b.lines * dct_pair_split_kpad(b.len);
+    pb.p16 = b.lines * dct_pair_split_kpad(b.len / 2);
+    return SSW_OK;
 }
 
-// One pass of the separable transform (src -> dst along rows or columns) appended to `ch`.
-int build_pass_impl(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, bool first_pass, bool is_row, const float* src, float* dst,
-                    Epilogue ep, Chain& ch, bool* fused_rgb);
+// the odd half of the full-length transform from the operand plane `odd`: one launch, or rotate + two
+int odd_rotate(const PassBuild& b, const PairBases& pb, hipStream_t st, const void* odd) {
+    return b.p.split ? launch_dct_pair_rotate(st, (const double*)odd, (const double*)pb.rot, pb.sp, b.lines, b.len) : SSW_OK;
+}
+int odd_gemm(const PassBuild& b, const PairBases& pb, hipStream_t st, const void* odd, void* tmpE, const RgbSink* sink) {
+    if (!b.p.split)
+        return pair_gemm(st, b.f64, b.is_row, b.inverse, 2, 0, odd, odd, pb.b1, (const char*)pb.b1 + (b.len / 4) * 64, b.dst, tmpE, b.n, b.w, b.h, b.ep, sink);
+    const PairClassDesc e = pb.e(), o = pb.o();
+    SSW_TRY(b.gemm(st, 1, &e, tmpE, nullptr, sink));
+    return b.gemm(st, 1, &o, tmpE, nullptr, sink);
+}
+double odd_flop(const PassBuild& b) { return b.p.split ? b.flop(3, 0) + b.flop(4, 0) : b.flop(2, 0); }
+
+// ---- one builder per strategy (dct_plan.hpp) ----
+int build_dense(const PassBuild& b, Chain& ch) {
+    ssw_ctx* ctx = b.ctx;
+    const bool fold = b.p.strategy == PassStrategy::Folded;
+    const void *b0 = nullptr, *b1 = nullptr;
+    SSW_TRY(get_basis(ctx, b.len, b.inverse, b.f64, fold ? 1 : 0, &b0));
+    if (fold) SSW_TRY(get_basis(ctx, b.len, b.inverse, b.f64, 2, &b1));
+    const double dense = 2.0 * (double)b.lines * (double)b.len * (double)b.len;
+    const double flop = fold ? 0.5 * dense : dense;
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_pass, st, flop);
+        t.traffic(b.px * 8.0);
+        if (b.is_row) {
+            if (fold && b.f64) return launch_dct_rows_folded_f64(st, b.inverse, b.src, b.dst, b.lines, b.w, (const double*)b0, (const double*)b1, b.ep);
+            if (fold) return launch_dct_rows_folded_f32(st, b.inverse, b.src, b.dst, b.lines, b.w, (const float*)b0, (const float*)b1, b.ep);
+            return launch_dct_rows(st, b.x.precision, b.src, b.dst, b.lines, b.w, b0, b.ep);
+        }
+        if (fold && b.f64) return launch_dct_cols_folded_f64(st, b.inverse, b.src, b.dst, b.n, b.w, b.h, (const double*)b0, (const double*)b1, b.ep);
+        if (fold) return launch_dct_cols_folded_f32(st, b.inverse, b.src, b.dst, b.n, b.w, b.h, (const float*)b0, (const float*)b1, b.ep);
+        return launch_dct_cols(st, b.x.precision, b.src, b.dst, b.n, b.w, b.h, b0, b.ep);
+    }});
+    return SSW_OK;
+}
+
+int build_pair_l1(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
+    ssw_ctx* ctx = b.ctx;
+    PairBases pb;
+    SSW_TRY(pair_bases(b, ws, pb));
+    for (int i = 0; i < 2; ++i) SSW_TRY(grow(ws.operand[i], pb.bytes));
+    void *x1 = ws.operand[0].p, *x2 = ws.operand[1].p;
+    ch.push_back({true, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, SSW_STAGE_DCT_PREP, st, b.prep_bytes);
+        return launch_dct_pair_prep(st, b.f64, b.is_row, b.inverse, b.src, b.n, b.w, b.h, x1, x2);
+    }});
+    const double f_main = b.flop(0, 0);
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_pass, st, f_main);
+        t.traffic(b.gemm_bytes(0.0));
+        StageTimer tm(ctx, b.st_main, st, f_main);
+        return pair_gemm(st, b.f64, b.is_row, b.inverse, 0, 0, x1, x2, pb.b0, pb.b1, b.dst, nullptr, b.n, b.w, b.h, b.ep);
+    }});
+    return SSW_OK;
+}
+
+int build_pair_two(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused_rgb) {
+    ssw_ctx* ctx = b.ctx;
+    PairBases pb;
+    SSW_TRY(pair_bases(b, ws, pb));
+    for (int i = 1; i < (b.inverse ? 5 : 4); ++i) SSW_TRY(grow(ws.operand[i], pb.bytes));
+    void* x2 = ws.operand[1].p;       // D | O
+    void* xx1 = ws.operand[2].p;      // SS | EE
+    void* xx2 = ws.operand[3].p;      // SD | EO
+    void* tmpE = ws.operand[4].p;     // inverse: the even half E, unrounded
+    const void *q0 = nullptr, *q1 = nullptr;
+    SSW_TRY(get_basis(ctx, b.len / 2, b.inverse, b.f64, 3, &q0));
+    SSW_TRY(get_basis(ctx, b.len / 2, b.inverse, b.f64, 4, &q1));
+    ch.push_back({true, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
+        if (b.from_rgb) SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, b.f64, b.x.rgb_u8, b.x.rgb, b.n, b.w, b.h, xx1, xx2, x2, b.x.iq_i, b.x.iq_q));
+        else SSW_TRY(launch_dct_pair_prep4(st, b.f64, b.is_row, b.inverse, b.src, b.n, b.w, b.h, xx1, xx2, x2));
+        return odd_rotate(b, pb, st, x2);
+    }});
+    const double f_main = odd_flop(b), f_all = f_main + b.flop(1, 0);
+    const RgbSink sink = rgb_sink(b, fused_rgb);
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_pass, st, f_all);
+        t.traffic(b.gemm_bytes(b.inverse ? b.esz : 0.0));          // inverse: the even half E out and in
+        // even half: a half-length transform of S (forward) / of the even coefficients (inverse), folded again
+        SSW_TRY(pair_gemm(st, b.f64, b.is_row, b.inverse, 1, 0, xx1, xx2, q0, q1, b.dst, tmpE, b.n, b.w, b.h, b.ep));
+        // odd half: full half-length sum, the odd basis split into two row blocks (second block:
+        // len/4 lines further inside every k-block of the same plane = 64 bytes per line)
+        StageTimer tm(ctx, b.st_main, st, f_main);
+        return odd_gemm(b, pb, st, x2, tmpE, sink.rgb ? &sink : nullptr);
+    }});
+    return SSW_OK;
+}
+
+// forward pass, three levels: x- (odd frequencies), S- (2 mod 4), (SSS, SS-) (0 and 4 mod 8); on a column pass (8K: 4320
+// rows) the pre-pass transposes like the two-level one
+int build_pair_three(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
+    ssw_ctx* ctx = b.ctx;
+    PairBases pb;
+    SSW_TRY(pair_bases(b, ws, pb));
+    for (int i = 0; i < 4; ++i) SSW_TRY(grow(ws.operand[i], pb.bytes));
+    void *d1 = ws.operand[1].p, *d2 = ws.operand[0].p, *r1 = ws.operand[2].p, *r2 = ws.operand[3].p;
+    const void *h1 = nullptr, *e0 = nullptr, *e1 = nullptr;
+    SSW_TRY(get_basis(ctx, b.len / 2, false, b.f64, 4, &h1));          // odd half basis of len/2
+    SSW_TRY(get_basis(ctx, b.len / 4, false, b.f64, 3, &e0));          // half bases of len/4
+    SSW_TRY(get_basis(ctx, b.len / 4, false, b.f64, 4, &e1));
+    ch.push_back({true, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
+        if (!b.is_row) SSW_TRY(launch_dct_pair_prep8_cols(st, b.f64, b.src, b.n, b.w, b.h, r1, r2, d2, d1));
+        else SSW_TRY(launch_dct_pair_prep8_rows(st, b.f64, b.rgb_kind(), b.prep_src(), b.n, b.w, b.h, r1, r2, d2, d1, b.prep_i(), b.prep_q()));
+        return odd_rotate(b, pb, st, d1);
+    }});
+    const double f_main = odd_flop(b), f_all = f_main + b.flop(1, 1) + b.flop(2, 1);
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_pass, st, f_all);
+        t.traffic(b.gemm_bytes(0.0));
+        SSW_TRY(pair_gemm(st, b.f64, b.is_row, b.inverse, 1, 1, r1, r2, e0, e1, b.dst, nullptr, b.n, b.w, b.h, b.ep));
+        SSW_TRY(pair_gemm(st, b.f64, b.is_row, b.inverse, 2, 1, d2, d2, h1, (const char*)h1 + (b.len / 8) * 64, b.dst, nullptr, b.n, b.w, b.h, b.ep));
+        StageTimer tm(ctx, b.st_main, st, f_main);
+        return odd_gemm(b, pb, st, d1, nullptr, nullptr);
+    }});
+    return SSW_OK;
+}
+
+// The deep strategies: one pre-pass writes the operands of all launches (D and SD split, SS folded a third time); forward
+// passes of 64-divisible (rows) / 16-divisible (columns) length, inverse ones of 128- / 16-divisible length.  Their bases:
+struct DeepBases {
+    const void *e0 = nullptr, *e1 = nullptr;                    // half bases of len/4 (level 1: R1, R2)
+    const void* t[4] = {};                                      // cosine / sine bases of len/2 (classes E', O')
+    const void *rot2 = nullptr, *rot3 = nullptr;                // rotation tables of len/2, len/4 (level 2)
+    const void *h0 = nullptr, *h1 = nullptr;                    // half bases of len/8 (level 2: R1)
+    // the half-length split (level 1): AS2 BD2 | AD2 BS2 from the planes q, q + p16 ...
+    PairClassDesc e2(const double* q, size_t p16) const { return D(3, 1, q, q + p16, t[0], t[1]); }
+    PairClassDesc o2(const double* q, size_t p16) const { return D(4, 1, q + 2 * p16, q + 3 * p16, t[2], t[3]); }
+};
+int deep_bases(const PassBuild& b, bool l2, DeepBases& db) {
+    ssw_ctx* ctx = b.ctx;
+    const size_t len = b.len;
+    SSW_TRY(get_basis(ctx, len / 4, b.inverse, true, 3, &db.e0));
+    SSW_TRY(get_basis(ctx, len / 4, b.inverse, true, 4, &db.e1));
+    for (int i = 0; i < 4; ++i) SSW_TRY(get_basis(ctx, len / 2, b.inverse, true, i == 1 ? 10 : 5 + i, &db.t[i]));
+    SSW_TRY(get_basis(ctx, len / 2, false, true, 9, &db.rot2));
+    return l2 ? get_basis(ctx, len / 4, false, true, 9, &db.rot3) : SSW_OK;
+}
+int deep_l2_halves(const PassBuild& b, DeepBases& db) {
+    SSW_TRY(get_basis(b.ctx, b.len / 8, b.inverse, true, 3, &db.h0));
+    return get_basis(b.ctx, b.len / 8, b.inverse, true, 4, &db.h1);
+}
+
+// Level 2, both directions: the eight classes of a pass and the sixteen K16-wide planes of its pre-pass they read, by number
+// (launch_dct_pair_prep16_rows, prep16_inv_rows_l2_kernel), with the basis pair of each: 0 = (cosine, sine) of class E' of
+// len/2, 1 = of class O', 2 = the half bases of len/8.  Every launch sums len/16 terms:
+//   class E (DCT-II of AS, DST-II of BD) folds exactly        -> kinds 5 / 6   16i +/- 1,  16i + 9 | 16i + 7
+//   class O (DCT-IV of AD, DST-IV of BS) rotates              -> kinds 7 / 8   16i +/- 5,  16i +/- 3
+//   R2 (DCT-IV) rotates, R1 (DCT-II) folds exactly            -> kind 9, kind 1 sub 2      16i +/- 4,  16i | 16i + 8
+// The forward launches run in this order; the inverse as c[16 s] | c[16 s + 8] -> A1 (class 0), R2 + A1 -> T2 (1),
+// AS2 BD2 | AD2 BS2 + T2 -> E (2, 3), then the odd part + E -> x (4, 5, 7, 6).
+struct L2Class { int kind, x1, x2, basis; };
+constexpr L2Class kL2Classes[8] = {
+    {1, 8, 9, 2},       // R1+ R1-
+    {9, 10, 11, 0},     // R2 rotated
+    {3, 12, 13, 0},     // AS2 BD2
+    {4, 14, 15, 1},     // AD2 BS2
+    {5, 0, 3, 0},       // AS+ BD-
+    {6, 1, 2, 1},       // AS- BD+
+    {8, 6, 7, 0},       // O rotated, "-"
+    {7, 4, 5, 0}};      // O rotated, "+"
+PairClassDesc l2_class(int c, bool inverse, const double* planes, size_t plane, const DeepBases& db) {
+    const L2Class& k = kL2Classes[c];
+    const void* const y[3][2] = {{db.t[0], db.t[1]}, {db.t[2], db.t[3]}, {db.h0, db.h1}};
+    const int sub = (k.kind == 1 || (inverse && k.kind == 9)) ? 2 : (k.kind == 3 || k.kind == 4) ? 1 : 0;
+    return D(k.kind, sub, planes + (size_t)k.x1 * plane, planes + (size_t)k.x2 * plane, y[k.basis][0], y[k.basis][1]);
+}
+
+// forward, level 1: five launches, sums of len/8 terms (the half-length split and R1 / R2 at len/16)
+int build_deep(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
+    ssw_ctx* ctx = b.ctx;
+    PairBases pb;
+    DeepBases db;
+    SSW_TRY(pair_bases(b, ws, pb));
+    SSW_TRY(deep_bases(b, false, db));
+    double* sp = pb.sp;
+    ch.push_back({true, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
+        if (!b.is_row) return launch_dct_pair_prep16_cols(st, b.src, b.n, b.w, b.h, sp, (const double*)pb.rot, (const double*)db.rot2, nullptr, b.p.prep, b.p.layout);
+        return launch_dct_pair_prep16_rows(st, b.rgb_kind(), b.prep_src(), b.n, b.w, b.h, sp, (const double*)pb.rot, (const double*)db.rot2, nullptr,
+                                           b.prep_i(), b.prep_q(), false);
+    }});
+    const double f_main = b.flop(4, 0), f_all = f_main + b.flop(3, 0) + b.flop(1, 1) + b.flop(3, 1) + b.flop(4, 1);
+    const double* q = sp + 6 * pb.p8;
+    const PairClassDesc r1 = pb.r1(db.e0, db.e1), e2 = db.e2(q, pb.p16), o2 = db.o2(q, pb.p16);
+    // a single frame's launches are too small alone (class E of a 4K frame: 272 blocks for 512 slots): one launch over all classes
+    const PairClassDesc merged[5] = {r1, e2, o2, pb.o(), pb.e()}, single[5] = {r1, e2, o2, pb.e(), pb.o()};
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_pass, st, f_all);
+        t.traffic(b.gemm_bytes(0.0));
+        auto launch = [&](int nc, const PairClassDesc* d) { return b.gemm(st, nc, d, nullptr, nullptr, nullptr, b.gemm_layout()); };
+        if (!b.p.merge) return launch_classes(ctx, st, false, 5, single, launch, b.st_main, f_main);
+        StageTimer tm(ctx, b.st_main, st, f_all);
+        return launch(5, merged);
+    }});
+    return SSW_OK;
+}
+
+// LEVEL 2 (r4b / r4c): every operand of the full-length split and of SS folds or rotates once more in the pre-pass
+// (dct_pair_split.hpp, DeepPlanes): eight launches of len/16 terms over len/16 pairs, 2/3 of the level-1 multiply-adds.  The
+// "main" timer brackets ONE launch: kind 7 (level 1: class O of the full-length split).  r5, FUSED: the row pre-pass orders
+// its lines (frame, unit of the column fold, line of the unit), the row launches' epilogue (EPI_FWD_COLOP) rounds to f32 --
+// the store between the passes, src/dct2d.rs:152-168 -- applies the column pre-pass's arithmetic and writes the sixteen
+// column-operand planes; the column pass is its eight launches only (4 + 4 + 8 B/px of plane and pre-pass become 8).
+int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
+    ssw_ctx* ctx = b.ctx;
+    const bool fused = b.p.strategy == PassStrategy::FusedRows || b.p.strategy == PassStrategy::FusedCols;
+    PairBases pb;
+    DeepBases db;
+    SSW_TRY(pair_bases(b, ws, pb));
+    SSW_TRY(deep_bases(b, true, db));
+    SSW_TRY(deep_l2_halves(b, db));
+    const size_t n = b.n, w = b.w, h = b.h;
+    double* planes = pb.sp;                                       // the sixteen operand planes of the launches, K16 wide
+    size_t plane = pb.p16;
+    FuseCols fc;
+    double pad = 1.0;                                             // the padding units' share of the flop
+    double bytes = b.gemm_bytes(0.0);
+    float* out = b.dst;
+    if (fused) {
+        const size_t cplane = n * w * dct_pair_split_kpad(h / 2);          // column operands: n w lines, K16(h) wide
+        SSW_TRY(grow(ws.operand[0], 16 * cplane * sizeof(double)));
+        double* cop = (double*)ws.operand[0].p;
+        fc = FuseCols{FUSE_COLS};
+        if (!b.is_row) { planes = cop; plane = cplane; }
+        else {
+            const void *crot1 = nullptr, *crot2 = nullptr, *crot3 = nullptr;
+            SSW_TRY(get_basis(ctx, h, false, true, 9, &crot1));
+            SSW_TRY(get_basis(ctx, h / 2, false, true, 9, &crot2));
+            SSW_TRY(get_basis(ctx, h / 4, false, true, 9, &crot3));
+            const size_t lpad = n * 16 * dct_pair_fused_units(h);           // unit-ordered, padded lines
+            plane = lpad * dct_pair_split_kpad(b.len / 2);
+            pad = (double)lpad / (double)(n * h);
+            fc = FuseCols{FUSE_ROWS_COP, cop, (const double*)crot1, (const double*)crot2, (const double*)crot3};
+            bytes = b.px * (b.esz + 8.0);                       // row operands in, column operands out
+            out = nullptr;
+        }
+    }
+    double* sp = pb.sp;
+    if (!fused || b.is_row)
+        ch.push_back({true, [=](hipStream_t st) -> int {
+            StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
+            if (!b.is_row) return launch_dct_pair_prep16_cols(st, b.src, n, w, h, sp, (const double*)pb.rot, (const double*)db.rot2, (const double*)db.rot3,
+                                                              b.p.prep, b.p.layout);
+            return launch_dct_pair_prep16_rows(st, b.rgb_kind(), b.prep_src(), n, w, h, sp, (const double*)pb.rot, (const double*)db.rot2,
+                                               (const double*)db.rot3, b.prep_i(), b.prep_q(), true, fused);
+        }});
+    const double f_main = b.flop(7, 0), f_all = 8.0 * f_main;
+    std::array<PairClassDesc, 8> d;
+    for (int c = 0; c < 8; ++c) d[c] = l2_class(c, false, planes, plane, db);
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_pass, st, f_all * pad, b.p.merge ? b.st_main : -1);      // (merged: a single frame's eight classes in one launch)
+        t.traffic(bytes);
+        auto launch = [&](int nc, const PairClassDesc* dd) {
+            return launch_dct_pair_gemm_multi_f64(st, b.is_row, false, nc, dd, out, nullptr, n, w, h, b.ep, nullptr, nullptr, b.gemm_layout(),
+                                                  fused ? &fc : nullptr);
+        };
+        return launch_classes(ctx, st, b.p.merge, 8, d.data(), launch, b.st_main, f_main * pad);
+    }});
+    return SSW_OK;
+}
+
+// Columns of 8- but not 16-divisible length (1080 rows): D split and SS folded a third time in one pre-pass, SD stays one
+// launch (H/16 is not whole); behind a deep row pass the plane arrives class-major (r4c: the staged pre-pass reads it like the
+// deep one).  Inverse: c[8q] / c[8q+4] -> T2, the whole c[4q+2] part + T2 -> E, the split odd part + E -> output.
+int build_semi_deep(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused_rgb) {
+    ssw_ctx* ctx = b.ctx;
+    const bool inv = b.inverse;
+    PairBases pb;
+    SSW_TRY(pair_bases(b, ws, pb));
+    const void *e0 = nullptr, *e1 = nullptr, *h1 = nullptr;
+    SSW_TRY(get_basis(ctx, b.len / 4, inv, true, 3, &e0));
+    SSW_TRY(get_basis(ctx, b.len / 4, inv, true, 4, &e1));
+    SSW_TRY(get_basis(ctx, b.len / 2, inv, true, 4, &h1));
+    if (inv) for (int i : {1, 4}) SSW_TRY(grow(ws.operand[i], pb.bytes));
+    void* T2 = inv ? ws.operand[1].p : nullptr;
+    void* TE = inv ? ws.operand[4].p : nullptr;
+    double* sp = pb.sp;
+    const double* rot = (const double*)pb.rot;
+    ch.push_back({true, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
+        if (inv) return launch_dct_pair_prep16_inv_cols(st, b.src, b.n, b.w, b.h, sp, rot, rot, nullptr, b.p.prep, b.p.layout);
+        return launch_dct_pair_prep16_cols(st, b.src, b.n, b.w, b.h, sp, rot, rot, nullptr, b.p.prep, b.p.layout);
+    }});
+    const RgbSink sink = rgb_sink(b, fused_rgb);
+    const double* m = sp + 6 * pb.p8;
+    const PairClassDesc r1 = pb.r1(e0, e1), sd = D(2, 1, m, m, h1, (const char*)h1 + (b.len / 8) * 64), eo[2] = {pb.e(), pb.o()};
+    const double f_main = b.flop(3, 0), f_all = f_main + b.flop(4, 0) + b.flop(1, 1) + b.flop(2, 1);
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_pass, st, f_all);
+        t.traffic(b.gemm_bytes(inv ? 12.0 : 0.0));
+        if (inv) {
+            SSW_TRY(b.gemm(st, 1, &r1, T2));
+            SSW_TRY(b.gemm(st, 1, &sd, T2, TE));
+            return launch_classes(ctx, st, b.p.merge, 2, eo, [&](int nc, const PairClassDesc* d) { return b.gemm(st, nc, d, TE, nullptr, sink.rgb ? &sink : nullptr); });
+        }
+        if (b.p.merge) {      // the SD launch shares its image operand between its two products: another template instance
+            SSW_TRY(b.gemm(st, 1, &sd));
+            const PairClassDesc d[3] = {r1, eo[1], eo[0]};
+            StageTimer tm(ctx, b.st_main, st, f_all - b.flop(2, 1));
+            return b.gemm(st, 3, d);
+        }
+        SSW_TRY(b.gemm(st, 1, &r1));
+        SSW_TRY(b.gemm(st, 1, &sd));
+        SSW_TRY(b.gemm(st, 1, &eo[1]));
+        StageTimer tm(ctx, b.st_main, st, f_main);
+        return b.gemm(st, 1, &eo[0]);
+    }});
+    return SSW_OK;
+}
+
+// The inverse the deep way: c[8q] / c[8q+4] -> T2, the split c[4q+2] part + T2 -> T (the even half E), then the split odd
+// part + T -> the output; one pre-pass for all launches.  LEVEL 2 (r4c), the transpose of the forward pass's: T2 = its
+// even half A1 (kind 1 sub 2) +/- its odd half (R2 rotated, kind 9); E = T2 +/- the half-length odd part (kinds 3 / 4 sub 1);
+// x = E +/- the odd part (kinds 5 - 8): 8/14 of the level-1 multiply-adds.  The row launches write (and exchange E) class-major.
+int build_deep_inv(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused_rgb) {
+    ssw_ctx* ctx = b.ctx;
+    const bool l2 = b.p.strategy == PassStrategy::DeepInvL2;
+    const size_t len = b.len, lines = b.lines;
+    PairBases pb;
+    DeepBases db;
+    SSW_TRY(pair_bases(b, ws, pb));
+    SSW_TRY(deep_bases(b, false, db));
+    SSW_TRY(grow(ws.operand[1], std::max<size_t>(pb.bytes, lines * (len / 4) * sizeof(double))));
+    SSW_TRY(grow(ws.operand[4], std::max<size_t>(pb.bytes, lines * (len / 2) * sizeof(double))));
+    void* A1 = nullptr;               // the eighth-length even part, unrounded: len/8 doubles per line
+    if (l2) {
+        SSW_TRY(get_basis(ctx, len / 4, false, true, 9, &db.rot3));
+        SSW_TRY(deep_l2_halves(b, db));
+        SSW_TRY(grow(ws.operand[2], std::max<size_t>(pb.bytes, lines * (len / 8) * sizeof(double))));      // (>= what any other pass asks of it)
+        A1 = ws.operand[2].p;
+    }
+    void* T2 = ws.operand[1].p;       // quarter-length even half, unrounded
+    void* TE = ws.operand[4].p;       // the even half E, unrounded
+    double* sp = pb.sp;
+    const RgbSink sink = rgb_sink(b, fused_rgb);
+    ch.push_back({true, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
+        if (!b.is_row) return launch_dct_pair_prep16_inv_cols(st, b.src, b.n, b.w, b.h, sp, (const double*)pb.rot, (const double*)db.rot2, (const double*)db.rot3,
+                                                              b.p.prep, b.p.layout);
+        return launch_dct_pair_prep16_inv_rows(st, b.src, b.n, b.w, b.h, sp, (const double*)pb.rot, (const double*)db.rot2, (const double*)db.rot3, b.p.prep);
+    }});
+    // the stages: (level 2: A1, then) T2, E from T2, the output from E
+    auto L = [&](int c) { return l2_class(c, true, sp, pb.p16, db); };
+    const double* q = sp + 6 * pb.p8;
+    const PairClassDesc da = l2 ? L(0) : PairClassDesc{}, dt = l2 ? L(1) : pb.r1(db.e0, db.e1);
+    const PairClassDesc d1[2] = {l2 ? L(2) : db.e2(q, pb.p16), l2 ? L(3) : db.o2(q, pb.p16)};
+    const PairClassDesc d0[4] = {l2 ? L(4) : pb.e(), l2 ? L(5) : pb.o(), l2 ? L(7) : PairClassDesc{}, l2 ? L(6) : PairClassDesc{}};
+    const double f_all = l2 ? 8.0 * b.flop(7, 0) : b.flop(3, 0) + b.flop(4, 0) + b.flop(1, 1) + b.flop(3, 1) + b.flop(4, 1);
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_pass, st, f_all);
+        t.traffic(b.gemm_bytes(l2 ? 14.0 : 12.0));
+        const PairLayout lay = b.gemm_layout();
+        if (l2) SSW_TRY(b.gemm(st, 1, &da, A1));
+        SSW_TRY(l2 ? b.gemm(st, 1, &dt, A1, T2, nullptr, lay) : b.gemm(st, 1, &dt, T2));
+        // (single frames: the classes of each dependent stage in one launch)
+        SSW_TRY(launch_classes(ctx, st, b.p.merge, 2, d1, [&](int nc, const PairClassDesc* d) { return b.gemm(st, nc, d, T2, TE, nullptr, lay); }));
+        return launch_classes(ctx, st, b.p.merge, l2 ? 4 : 2, d0,
+                              [&](int nc, const PairClassDesc* d) { return b.gemm(st, nc, d, TE, nullptr, sink.rgb ? &sink : nullptr, lay); });
+    }});
+    return SSW_OK;
+}
+
+// One pass of the separable transform (src -> dst along rows or columns) appended to `ch`: the builder of the strategy
+// its plan names.
 int build_pass(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, bool first_pass, bool is_row, const float* src, float* dst,
                Epilogue ep, Chain& ch, bool* fused_rgb = nullptr) {
+    const PlanInput in{x.type, x.precision, x.n, x.w, x.h, x.full_h, x.natural_order, aligned_planes(src, dst), plan_settings(ctx)};
+    PassBuild b{ctx, x, plan_pass(in, first_pass, is_row), first_pass, is_row, x.type == SSW_DCT3, x.precision == SSW_PRECISION_F64,
+                x.rgb && first_pass, x.n, x.w, x.h, is_row ? x.w : x.h, is_row ? x.n * x.h : x.n * x.w, src, dst, ep};
+    if (b.from_rgb && !(is_row && b.p.levels >= 2)) return SSW_ERR_BAD_ARG;      // can_fuse_rgb() checks the same conditions
+    b.st_pass = is_row ? SSW_STAGE_DCT_ROW : SSW_STAGE_DCT_COL;
+    b.st_main = is_row ? SSW_STAGE_DCT_ROW_MAIN : SSW_STAGE_DCT_COL_MAIN;
+    b.st_prep = b.from_rgb ? SSW_STAGE_RGB_TO_YIQ : SSW_STAGE_DCT_PREP;
+    b.px = (double)b.n * (double)b.w * (double)b.h;
+    b.esz = b.f64 ? 8.0 : 4.0;
+    // algorithmic bytes of the pre-pass: the f32 plane (or the RGB frame) in, the operand planes (one element per pixel in the
+    // GEMM's precision, whatever the number of folding levels) and I / Q out
+    b.prep_bytes = b.from_rgb ? b.px * (3.0 * (double)pix_bytes(x.rgb_u8) + (x.iq_i ? 8.0 : 0.0) + b.esz) : b.px * (4.0 + b.esz);
+    const bool sink_pass = b.inverse && !first_pass && !is_row && x.rgb_out && x.iq_i && x.iq_q;
+    b.out_bpp = sink_pass ? 8.0 + 3.0 * (double)pix_bytes(x.rgb_out_u8) : 4.0;
     const size_t first = ch.size();
-    SSW_TRY(build_pass_impl(ctx, ws, x, first_pass, is_row, src, dst, ep, ch, fused_rgb));
+    typedef PassStrategy S;
+    const S s = b.p.strategy;
+    SSW_TRY(s == S::Dense || s == S::Folded ? build_dense(b, ch)
+            : s == S::PairL1                ? build_pair_l1(b, ws, ch)
+            : s == S::PairTwo               ? build_pair_two(b, ws, ch, fused_rgb)
+            : s == S::PairThree             ? build_pair_three(b, ws, ch)
+            : s == S::Deep                  ? build_deep(b, ws, ch)
+            : s == S::SemiDeep || s == S::SemiDeepInv ? build_semi_deep(b, ws, ch, fused_rgb)
+            : s == S::DeepInv || s == S::DeepInvL2    ? build_deep_inv(b, ws, ch, fused_rgb)
+                                                      : build_deep_l2(b, ws, ch));        // DeepL2, FusedRows, FusedCols
     for (size_t i = first; i < ch.size(); ++i) {                  // hints for the two-lane scheduler (run_pipeline_impl)
         if (!ch[i].hbm && is_row) ch[i].tag = 1;
         if (ch[i].hbm && is_row && first_pass && x.type != SSW_DCT3 && x.rgb) ch[i].tag = 2;
     }
     return SSW_OK;
-}
-int build_pass_impl(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, bool first_pass, bool is_row, const float* src, float* dst,
-                    Epilogue ep, Chain& ch, bool* fused_rgb) {
-    const bool inverse = (x.type == SSW_DCT3);
-    const bool f64 = (x.precision == SSW_PRECISION_F64);
-    const int precision = x.precision;
-    const size_t n = x.n, w = x.w, h = x.h;
-    const size_t len = is_row ? w : h;
-    const double px = (double)n * (double)w * (double)h;
-    const double esz = f64 ? 8.0 : 4.0;
-    const bool can_fold = ctx->fold && (is_row ? dct_rows_can_fold(w, src, dst) : dct_cols_can_fold(w, h, src, dst));
-    const bool operand = can_fold && ctx->fold_level >= 3 && dct_pair_can_run(f64, n, w, h, src, dst);
-    // (default build: the in-kernel folding of dct_folded*.hip is not compiled in -- what the pair path does not take runs dense)
-    const bool fold = can_fold && (operand || build_all_strategies());
-    const bool from_rgb = x.rgb && first_pass;
-    if (from_rgb && !(operand && is_row && ctx->fold_level >= 4 && dct_pair_can_fold2(len)))
-        return SSW_ERR_BAD_ARG;                                    // can_fuse_rgb() checks the same conditions
-    const int st_pass = is_row ? SSW_STAGE_DCT_ROW : SSW_STAGE_DCT_COL;
-    const int st_main = is_row ? SSW_STAGE_DCT_ROW_MAIN : SSW_STAGE_DCT_COL_MAIN;
-    const void* rgb = x.rgb;
-    const int rgb_u8 = x.rgb_u8;
-    float *iq_i = x.iq_i, *iq_q = x.iq_q;
-    // algorithmic bytes of the pre-pass: the f32 plane (or the RGB frame) in, the operand planes (one
-    // element per pixel in the GEMM's precision, whatever the number of folding levels) and I / Q out
-    const double prep_bytes = from_rgb ? px * (3.0 * (double)pix_bytes(rgb_u8) + (iq_i ? 8.0 : 0.0) + esz) : px * (4.0 + esz);
-    const int st_prep = from_rgb ? SSW_STAGE_RGB_TO_YIQ : SSW_STAGE_DCT_PREP;
-    // algorithmic bytes of the pass's GEMM launches (ssw_ctx_get_traffic): the operand planes in (one element per pixel), the
-    // f32 result out -- or, in the last pass of Writer::result, I and Q in and the RGB frame out -- plus `xch` bytes per
-    // pixel that the dependent launches of an inverse pass write and read back as doubles (A1: 1 + 1, T2: 2 + 2, E: 4 + 4)
-    const bool sink_pass = inverse && !first_pass && !is_row && x.rgb_out && x.iq_i && x.iq_q;
-    const double out_bpp = sink_pass ? 8.0 + 3.0 * (double)pix_bytes(x.rgb_out_u8) : 4.0;
-    auto gemm_bytes = [=](double xch) { return px * (esz + xch + out_bpp); };
-    if (operand) {
-        const size_t bytes = dct_pair_operand_elems(f64, n, w, h) * (size_t)esz;
-        const bool two = ctx->fold_level >= 4 && (is_row ? dct_pair_can_fold2(len) : dct_pair_can_fold2_cols(len));
-        const void *b0 = nullptr, *b1 = nullptr;
-        SSW_TRY(get_basis(ctx, len, inverse, f64, 3, &b0));        // k-blocked half bases
-        SSW_TRY(get_basis(ctx, len, inverse, f64, 4, &b1));
-        // a third level pays once the sums are long enough (4K: +1.6 %, 1080p: -3 %); level 6 forces it
-        const bool three = two && !inverse && dct_pair_can_fold3(len) &&
-                           (ctx->fold_level >= 6 || (ctx->fold_level == 5 && len >= 3072));
-        // the odd half as a rotated pair of quarter-length cosine / sine transforms (f64): a quarter of its multiply-adds
-        const bool split = two && f64 && ctx->split && dct_pair_can_split(len, is_row);
-        const void *sb[4] = {nullptr, nullptr, nullptr, nullptr}, *rot = nullptr;
-        double* sp = nullptr;
-        const size_t lines = is_row ? n * h : n * w;
-        const size_t sp_plane = lines * (split ? dct_pair_split_kpad(len) : 0);
-        if (split) {
-            for (int b = 0; b < 4; ++b) SSW_TRY(get_basis(ctx, len, inverse, true, b == 1 ? 10 : 5 + b, &sb[b]));      // 10: sinE for launches
-            SSW_TRY(get_basis(ctx, len, false, true, 9, &rot));
-            SSW_TRY(grow(ws.operand[5], split_scratch_elems(n, w, h) * sizeof(double)));
-            sp = (double*)ws.operand[5].p;
-        }
-        // forward passes of 64-divisible (rows) / 16-divisible (columns) length: one pre-pass writes the operands of five
-        // launches (D and SD split, SS folded a third time)
-        const bool deep = split && !inverse && (is_row ? dct_pair_can_deep_rows(len) : dct_pair_can_deep_cols(len) && w % 4 == 0);
-        if (deep) {
-            const void *e0 = nullptr, *e1 = nullptr, *sb2[4], *rot2 = nullptr, *rot3 = nullptr, *h0 = nullptr, *h1 = nullptr;
-            SSW_TRY(get_basis(ctx, len / 4, false, true, 3, &e0));
-            SSW_TRY(get_basis(ctx, len / 4, false, true, 4, &e1));
-            for (int b = 0; b < 4; ++b) SSW_TRY(get_basis(ctx, len / 2, false, true, b == 1 ? 10 : 5 + b, &sb2[b]));
-            SSW_TRY(get_basis(ctx, len / 2, false, true, 9, &rot2));
-            // Row passes of 1280 columns or more run at LEVEL 2 (r4b, dct_pair_efold): every operand of the full-length split
-            // and of SS folds or rotates once more in the pre-pass (dct_pair_split.hpp, DeepPlanes), so that all eight
-            // launches are sums of len/16 terms over len/16 pairs -- 2/3 of the level-1 pass's multiply-adds:
-            //   class E (DCT-II of AS, DST-II of BD) folds exactly        -> kinds 5 / 6   16i +/- 1,  16i + 9 | 16i + 7
-            //   class O (DCT-IV of AD, DST-IV of BS) rotates              -> kinds 7 / 8   16i +/- 5,  16i +/- 3
-            //   R2 (DCT-IV) rotates, R1 (DCT-II) folds exactly            -> kind 9, kind 1 sub 2      16i +/- 4,  16i | 16i + 8
-            // Shorter rows stay at level 1.  The "main" timer brackets ONE launch: kind 7 (level 1: class O of the full-length split).
-            // Column passes of 720 rows or more do the same (r4c, dct_pair_efold_cols; the pre-pass holds a unit and its
-            // mirror in one thread): K = H/16 = 135 at 4K -- such launches reach 50 TFLOP/s against 64 for K = 270, at half
-            // the multiply-adds.
-            const size_t fh0 = x.full_h ? x.full_h : h;
-            const bool cm0 = !x.natural_order && w >= fh0 && w % 4 == 0 && dct_pair_can_deep_rows(w) && cols_read_class_major(fh0, w) &&
-                             (is_row ? first_pass : !first_pass);
-            const bool l2 = is_row ? dct_pair_efold(len) : dct_pair_efold_cols(len, w, cm0);
-            if (l2) {
-                SSW_TRY(get_basis(ctx, len / 4, false, true, 9, &rot3));
-                SSW_TRY(get_basis(ctx, len / 8, false, true, 3, &h0));
-                SSW_TRY(get_basis(ctx, len / 8, false, true, 4, &h1));
-            }
-            const void *sb0 = sb[0], *sb1 = sb[1], *sb2_ = sb[2], *sb3 = sb[3];
-            const void *t0 = sb2[0], *t1 = sb2[1], *t2 = sb2[2], *t3 = sb2[3];
-            // rows first and both passes deep: the row launches write class-major, the column pre-pass reads it back
-            const size_t fh = x.full_h ? x.full_h : h;
-            const bool cm = cm0;
-            (void)fh;
-            // r5: FUSED forward transform (dct_pair_can_fuse_cols: rows first, both passes at level 2, batches on 128-line
-            // tiles).  The row pre-pass orders its lines (frame, unit of the column fold, line of the unit), the row launches'
-            // epilogue (EPI_FWD_COLOP) rounds to f32 -- the store between the passes, src/dct2d.rs:152-168 -- applies the column
-            // pre-pass's arithmetic to its accumulators and writes the sixteen column-operand planes; the column pass is its
-            // eight launches only.  The f32 plane between the passes and the column pre-pass are gone: 4 + 4 + 8 B/px become 8.
-            const bool fuse = l2 && cm && !x.full_h && dct_pair_can_fuse_cols(n, w, h);
-            if (fuse) {
-                const size_t k16h = dct_pair_split_kpad(h / 2), cplane = n * w * k16h;             // column operands: n w lines, K16(h) wide
-                SSW_TRY(grow(ws.operand[0], 16 * cplane * sizeof(double)));
-                double* cop = (double*)ws.operand[0].p;
-                auto CP = [=](int j) { return (const double*)(cop + (size_t)j * cplane); };
-                const double f_main = pair_gemm_flop(is_row, 7, 0, n, w, h), f_all = 8.0 * f_main;
-                if (is_row) {
-                    const void *crot1 = nullptr, *crot2 = nullptr, *crot3 = nullptr;
-                    SSW_TRY(get_basis(ctx, h, false, true, 9, &crot1));
-                    SSW_TRY(get_basis(ctx, h / 2, false, true, 9, &crot2));
-                    SSW_TRY(get_basis(ctx, h / 4, false, true, 9, &crot3));
-                    const size_t lpad = n * 16 * dct_pair_fused_units(h), p16r = lpad * dct_pair_split_kpad(len / 2);
-                    auto P = [=](int j) { return (const double*)(sp + (size_t)j * p16r); };
-                    const double pad = (double)lpad / (double)(n * h);                              // the padding units' share of the flop
-                    ch.push_back({true, [=](hipStream_t st) -> int {
-                        StageTimer t(ctx, st_prep, st, prep_bytes);
-                        return launch_dct_pair_prep16_rows(st, from_rgb ? pix_src_kind(rgb_u8) : 0, from_rgb ? rgb : (const void*)src, n, w, h, sp,
-                                                           (const double*)rot, (const double*)rot2, (const double*)rot3,
-                                                           from_rgb ? iq_i : nullptr, from_rgb ? iq_q : nullptr, true);
-                    }});
-                    const PairClassDesc d[8] = {{1, 2, P(8), P(9), (const double*)h0, (const double*)h1},
-                                                {9, 0, P(10), P(11), (const double*)t0, (const double*)t1},
-                                                {3, 1, P(12), P(13), (const double*)t0, (const double*)t1},
-                                                {4, 1, P(14), P(15), (const double*)t2, (const double*)t3},
-                                                {5, 0, P(0), P(3), (const double*)t0, (const double*)t1},
-                                                {6, 0, P(1), P(2), (const double*)t2, (const double*)t3},
-                                                {8, 0, P(6), P(7), (const double*)t0, (const double*)t1},
-                                                {7, 0, P(4), P(5), (const double*)t0, (const double*)t1}};
-                    const FuseCols fc{FUSE_ROWS_COP, cop, (const double*)crot1, (const double*)crot2, (const double*)crot3};
-                    const bool merge_r = lpad <= merge_max_lines();       // a single frame: the eight classes in one launch
-                    ch.push_back({false, [=](hipStream_t st) -> int {
-                        StageTimer t(ctx, st_pass, st, f_all * pad, merge_r ? st_main : -1);
-                        t.traffic(px * (esz + 8.0));                     // row operands in, column operands out
-                        if (merge_r) {
-                            return launch_dct_pair_gemm_multi_f64(st, true, false, 8, d, nullptr, nullptr, n, w, h, ep, nullptr, nullptr, true, &fc);
-                        }
-                        for (int c = 0; c < 7; ++c)
-                            SSW_TRY(launch_dct_pair_gemm_multi_f64(st, true, false, 1, &d[c], nullptr, nullptr, n, w, h, ep, nullptr, nullptr, true, &fc));
-                        StageTimer tm(ctx, st_main, st, f_main * pad);
-                        return launch_dct_pair_gemm_multi_f64(st, true, false, 1, &d[7], nullptr, nullptr, n, w, h, ep, nullptr, nullptr, true, &fc);
-                    }});
-                    return SSW_OK;
-                }
-                const PairClassDesc d[8] = {{1, 2, CP(8), CP(9), (const double*)h0, (const double*)h1},
-                                            {9, 0, CP(10), CP(11), (const double*)t0, (const double*)t1},
-                                            {3, 1, CP(12), CP(13), (const double*)t0, (const double*)t1},
-                                            {4, 1, CP(14), CP(15), (const double*)t2, (const double*)t3},
-                                            {5, 0, CP(0), CP(3), (const double*)t0, (const double*)t1},
-                                            {6, 0, CP(1), CP(2), (const double*)t2, (const double*)t3},
-                                            {8, 0, CP(6), CP(7), (const double*)t0, (const double*)t1},
-                                            {7, 0, CP(4), CP(5), (const double*)t0, (const double*)t1}};
-                const FuseCols fc{FUSE_COLS};
-                const bool merge_c = lines <= merge_max_lines();
-                ch.push_back({false, [=](hipStream_t st) -> int {
-                    StageTimer t(ctx, st_pass, st, f_all, merge_c ? st_main : -1);
-                    t.traffic(gemm_bytes(0.0));
-                    if (merge_c) {
-                        return launch_dct_pair_gemm_multi_f64(st, false, false, 8, d, dst, nullptr, n, w, h, ep, nullptr, nullptr, false, &fc);
-                    }
-                    for (int c = 0; c < 7; ++c)
-                        SSW_TRY(launch_dct_pair_gemm_multi_f64(st, false, false, 1, &d[c], dst, nullptr, n, w, h, ep, nullptr, nullptr, false, &fc));
-                    StageTimer tm(ctx, st_main, st, f_main);
-                    return launch_dct_pair_gemm_multi_f64(st, false, false, 1, &d[7], dst, nullptr, n, w, h, ep, nullptr, nullptr, false, &fc);
-                }});
-                return SSW_OK;
-            }
-            const size_t p8 = lines * dct_pair_split_kpad(len), p16 = lines * dct_pair_split_kpad(len / 2);
-            double* q = sp + 6 * p8;
-            ch.push_back({true, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_prep, st, prep_bytes);
-                if (!is_row) return launch_dct_pair_prep16_cols(st, src, n, w, h, sp, (const double*)rot, (const double*)rot2, cm, (const double*)rot3);
-                return launch_dct_pair_prep16_rows(st, from_rgb ? pix_src_kind(rgb_u8) : 0, from_rgb ? rgb : (const void*)src, n, w, h, sp,
-                                                   (const double*)rot, (const double*)rot2, (const double*)rot3,
-                                                   from_rgb ? iq_i : nullptr, from_rgb ? iq_q : nullptr);
-            }});
-            // a single frame's launches are too small alone (class E of a 4K frame: 272 blocks for 512 slots): one launch
-            // over all classes instead
-            const bool merge = lines <= merge_max_lines();             // (merging the batch launches as well: measured, no difference)
-            if (l2) {
-                // the sixteen planes of launch_dct_pair_prep16_rows, K16 wide each, by number
-                auto P = [=](int j) { return (const double*)(sp + (size_t)j * p16); };
-                const double f_main = pair_gemm_flop(is_row, 7, 0, n, w, h), f_all = 8.0 * f_main;
-                const PairClassDesc d[8] = {{1, 2, P(8), P(9), (const double*)h0, (const double*)h1},          // R1+ R1-
-                                            {9, 0, P(10), P(11), (const double*)t0, (const double*)t1},        // R2 rotated
-                                            {3, 1, P(12), P(13), (const double*)t0, (const double*)t1},        // AS2 BD2
-                                            {4, 1, P(14), P(15), (const double*)t2, (const double*)t3},        // AD2 BS2
-                                            {5, 0, P(0), P(3), (const double*)t0, (const double*)t1},          // AS+ BD-
-                                            {6, 0, P(1), P(2), (const double*)t2, (const double*)t3},          // AS- BD+
-                                            {8, 0, P(6), P(7), (const double*)t0, (const double*)t1},          // O rotated, "-"
-                                            {7, 0, P(4), P(5), (const double*)t0, (const double*)t1}};         // O rotated, "+"
-                ch.push_back({false, [=](hipStream_t st) -> int {
-                    StageTimer t(ctx, st_pass, st, f_all, merge ? st_main : -1);
-                    t.traffic(gemm_bytes(0.0));
-                    const bool rcm = cm && is_row;
-                    if (merge) {
-                        return launch_dct_pair_gemm_multi_f64(st, is_row, false, 8, d, dst, nullptr, n, w, h, ep, nullptr, nullptr, rcm);
-                    }
-                    for (int c = 0; c < 7; ++c)
-                        SSW_TRY(pair_gemm(st, true, is_row, false, d[c].kind, d[c].sub, d[c].x1, d[c].x2, d[c].y1, d[c].y2, dst, nullptr, n, w, h, ep,
-                                          nullptr, nullptr, rcm));
-                    StageTimer tm(ctx, st_main, st, f_main);
-                    return pair_gemm(st, true, is_row, false, 7, 0, d[7].x1, d[7].x2, d[7].y1, d[7].y2, dst, nullptr, n, w, h, ep, nullptr, nullptr, rcm);
-                }});
-                return SSW_OK;
-            }
-            const double f_main = pair_gemm_flop(is_row, 4, 0, n, w, h);
-            const double f_all = f_main + pair_gemm_flop(is_row, 3, 0, n, w, h) + pair_gemm_flop(is_row, 1, 1, n, w, h) +
-                                 pair_gemm_flop(is_row, 3, 1, n, w, h) + pair_gemm_flop(is_row, 4, 1, n, w, h);
-            ch.push_back({false, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_pass, st, f_all);
-                t.traffic(gemm_bytes(0.0));
-                const bool rcm = cm && is_row;
-                if (merge) {
-                    const PairClassDesc d[5] = {{1, 1, sp + 4 * p8, sp + 5 * p8, (const double*)e0, (const double*)e1},
-                                                {3, 1, q, q + p16, (const double*)t0, (const double*)t1},
-                                                {4, 1, q + 2 * p16, q + 3 * p16, (const double*)t2, (const double*)t3},
-                                                {4, 0, sp + 2 * p8, sp + 3 * p8, (const double*)sb2_, (const double*)sb3},
-                                                {3, 0, sp, sp + p8, (const double*)sb0, (const double*)sb1}};
-                    StageTimer tm(ctx, st_main, st, f_all);
-                    return launch_dct_pair_gemm_multi_f64(st, is_row, false, 5, d, dst, nullptr, n, w, h, ep, nullptr, nullptr, rcm);
-                }
-                SSW_TRY(pair_gemm(st, true, is_row, false, 1, 1, sp + 4 * p8, sp + 5 * p8, e0, e1, dst, nullptr, n, w, h, ep, nullptr, nullptr, rcm));
-                SSW_TRY(pair_gemm(st, true, is_row, false, 3, 1, q, q + p16, t0, t1, dst, nullptr, n, w, h, ep, nullptr, nullptr, rcm));
-                SSW_TRY(pair_gemm(st, true, is_row, false, 4, 1, q + 2 * p16, q + 3 * p16, t2, t3, dst, nullptr, n, w, h, ep, nullptr, nullptr, rcm));
-                SSW_TRY(pair_gemm(st, true, is_row, false, 3, 0, sp, sp + p8, sb0, sb1, dst, nullptr, n, w, h, ep, nullptr, nullptr, rcm));
-                StageTimer tm(ctx, st_main, st, f_main);
-                return pair_gemm(st, true, is_row, false, 4, 0, sp + 2 * p8, sp + 3 * p8, sb2_, sb3, dst, nullptr, n, w, h, ep, nullptr, nullptr, rcm);
-            }});
-            return SSW_OK;
-        }
-        // the odd half of the full-length transform from the operand plane `odd`: one launch, or rotate + two
-        auto odd_rotate = [=](hipStream_t st, const void* odd) -> int {
-            return split ? launch_dct_pair_rotate(st, (const double*)odd, (const double*)rot, sp, lines, len) : SSW_OK;
-        };
-        auto odd_gemm = [=](hipStream_t st, const void* odd, const void* basis, void* tmpE, const RgbSink* sink) -> int {
-            if (!split) return pair_gemm(st, f64, is_row, inverse, 2, 0, odd, odd, basis, (const char*)basis + (len / 4) * 64, dst, tmpE, n, w, h, ep, sink);
-            SSW_TRY(pair_gemm(st, true, is_row, inverse, 3, 0, sp, sp + sp_plane, sb[0], sb[1], dst, tmpE, n, w, h, ep, sink));
-            return pair_gemm(st, true, is_row, inverse, 4, 0, sp + 2 * sp_plane, sp + 3 * sp_plane, sb[2], sb[3], dst, tmpE, n, w, h, ep, sink);
-        };
-        const double f_odd = split ? pair_gemm_flop(is_row, 3, 0, n, w, h) + pair_gemm_flop(is_row, 4, 0, n, w, h)
-                                   : pair_gemm_flop(is_row, 2, 0, n, w, h);
-        // forward column passes of 8- but not 16-divisible length (1080 rows): D split and SS folded a third time in one
-        // pre-pass, SD stays one launch (H/16 is not whole)
-        const bool semi = split && !inverse && !is_row && dct_pair_can_semi_deep_cols(len) && w % 4 == 0;
-        if (semi) {
-            const void *e0 = nullptr, *e1 = nullptr, *h1 = nullptr;
-            SSW_TRY(get_basis(ctx, len / 4, false, true, 3, &e0));
-            SSW_TRY(get_basis(ctx, len / 4, false, true, 4, &e1));
-            SSW_TRY(get_basis(ctx, len / 2, false, true, 4, &h1));
-            const size_t p8 = lines * dct_pair_split_kpad(len);
-            double* m = sp + 6 * p8;
-            const void *sb0 = sb[0], *sb1 = sb[1], *sb2_ = sb[2], *sb3 = sb[3];
-            // behind a deep row pass the plane arrives class-major (r4c: the staged pre-pass reads it like the deep one)
-            const size_t fh = x.full_h ? x.full_h : h;
-            const bool cm = !x.natural_order && w >= fh && dct_pair_can_deep_rows(w) && cols_read_class_major(fh, w) && !first_pass;
-            ch.push_back({true, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_prep, st, prep_bytes);
-                return launch_dct_pair_prep16_cols(st, src, n, w, h, sp, (const double*)rot, (const double*)rot, cm);
-            }});
-            const double f_main = pair_gemm_flop(is_row, 3, 0, n, w, h);
-            const double f_all = f_main + pair_gemm_flop(is_row, 4, 0, n, w, h) + pair_gemm_flop(is_row, 1, 1, n, w, h) + pair_gemm_flop(is_row, 2, 1, n, w, h);
-            const bool merge = lines <= merge_max_lines();
-            ch.push_back({false, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_pass, st, f_all);
-                t.traffic(gemm_bytes(0.0));
-                if (merge) {      // the SD launch shares its image operand between its two products: another template instance
-                    SSW_TRY(pair_gemm(st, true, is_row, false, 2, 1, m, m, h1, (const char*)h1 + (len / 8) * 64, dst, nullptr, n, w, h, ep));
-                    const PairClassDesc d[3] = {{1, 1, sp + 4 * p8, sp + 5 * p8, (const double*)e0, (const double*)e1},
-                                                {4, 0, sp + 2 * p8, sp + 3 * p8, (const double*)sb2_, (const double*)sb3},
-                                                {3, 0, sp, sp + p8, (const double*)sb0, (const double*)sb1}};
-                    StageTimer tm(ctx, st_main, st, f_all - pair_gemm_flop(is_row, 2, 1, n, w, h));
-                    return launch_dct_pair_gemm_multi_f64(st, is_row, false, 3, d, dst, nullptr, n, w, h, ep);
-                }
-                SSW_TRY(pair_gemm(st, true, is_row, false, 1, 1, sp + 4 * p8, sp + 5 * p8, e0, e1, dst, nullptr, n, w, h, ep));
-                SSW_TRY(pair_gemm(st, true, is_row, false, 2, 1, m, m, h1, (const char*)h1 + (len / 8) * 64, dst, nullptr, n, w, h, ep));
-                SSW_TRY(pair_gemm(st, true, is_row, false, 4, 0, sp + 2 * p8, sp + 3 * p8, sb2_, sb3, dst, nullptr, n, w, h, ep));
-                StageTimer tm(ctx, st_main, st, f_main);
-                return pair_gemm(st, true, is_row, false, 3, 0, sp, sp + p8, sb0, sb1, dst, nullptr, n, w, h, ep);
-            }});
-            return SSW_OK;
-        }
-        // ... and the inverse column pass of such a length: c[8q] / c[8q+4] -> T2, the whole c[4q+2] part + T2 -> E, split odd
-        // part + E -> output
-        const bool semi_inv = split && inverse && !is_row && dct_pair_can_semi_deep_cols(len) && w % 4 == 0;
-        if (semi_inv) {
-            const void *e0 = nullptr, *e1 = nullptr, *h1 = nullptr;
-            SSW_TRY(get_basis(ctx, len / 4, true, true, 3, &e0));
-            SSW_TRY(get_basis(ctx, len / 4, true, true, 4, &e1));
-            SSW_TRY(get_basis(ctx, len / 2, true, true, 4, &h1));
-            SSW_TRY(grow(ws.operand[1], bytes));
-            SSW_TRY(grow(ws.operand[4], bytes));
-            void* T2 = ws.operand[1].p;
-            void* TE = ws.operand[4].p;
-            const size_t p8 = lines * dct_pair_split_kpad(len);
-            double* m = sp + 6 * p8;
-            const void *sb0 = sb[0], *sb1 = sb[1], *sb2_ = sb[2], *sb3 = sb[3];
-            const bool cm = !x.natural_order && w >= h && dct_pair_can_deep_inv_rows(w) && cols_read_class_major(h, w) && !first_pass;
-            ch.push_back({true, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_prep, st, prep_bytes);
-                return launch_dct_pair_prep16_inv_cols(st, src, n, w, h, sp, (const double*)rot, (const double*)rot, cm);
-            }});
-            RgbSink sink;
-            if (!first_pass && x.rgb_out && x.iq_i && x.iq_q) {
-                sink.iq_i = x.iq_i; sink.iq_q = x.iq_q; sink.rgb = x.rgb_out; sink.u8 = x.rgb_out_u8;
-                if (fused_rgb) *fused_rgb = true;
-            }
-            const bool with_sink = sink.rgb != nullptr;
-            const double f_all = pair_gemm_flop(is_row, 3, 0, n, w, h) + pair_gemm_flop(is_row, 4, 0, n, w, h) + pair_gemm_flop(is_row, 1, 1, n, w, h) +
-                                 pair_gemm_flop(is_row, 2, 1, n, w, h);
-            ch.push_back({false, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_pass, st, f_all);
-                t.traffic(gemm_bytes(12.0));
-                SSW_TRY(pair_gemm(st, true, is_row, true, 1, 1, sp + 4 * p8, sp + 5 * p8, e0, e1, dst, T2, n, w, h, ep));
-                SSW_TRY(pair_gemm(st, true, is_row, true, 2, 1, m, m, h1, (const char*)h1 + (len / 8) * 64, dst, T2, n, w, h, ep, nullptr, TE));
-                if (lines <= merge_max_lines()) {
-                    const PairClassDesc d0[2] = {{3, 0, sp, sp + p8, (const double*)sb0, (const double*)sb1},
-                                                 {4, 0, sp + 2 * p8, sp + 3 * p8, (const double*)sb2_, (const double*)sb3}};
-                    return launch_dct_pair_gemm_multi_f64(st, is_row, true, 2, d0, dst, (double*)TE, n, w, h, ep, with_sink ? &sink : nullptr);
-                }
-                SSW_TRY(pair_gemm(st, true, is_row, true, 3, 0, sp, sp + p8, sb0, sb1, dst, TE, n, w, h, ep, with_sink ? &sink : nullptr));
-                return pair_gemm(st, true, is_row, true, 4, 0, sp + 2 * p8, sp + 3 * p8, sb2_, sb3, dst, TE, n, w, h, ep, with_sink ? &sink : nullptr);
-            }});
-            return SSW_OK;
-        }
-        // the inverse the same way: c[8q] / c[8q+4] -> T2, the split c[4q+2] part + T2 -> T (the even half E), then the
-        // split odd part + T -> the output; one pre-pass for all five launches
-        const bool deep_inv = split && inverse && (is_row ? dct_pair_can_deep_inv_rows(len) : dct_pair_can_deep_cols(len) && w % 4 == 0);
-        if (deep_inv) {
-            const void *e0 = nullptr, *e1 = nullptr, *sb2[4], *rot2 = nullptr, *rot3 = nullptr, *h0 = nullptr, *h1 = nullptr;
-            SSW_TRY(get_basis(ctx, len / 4, true, true, 3, &e0));
-            SSW_TRY(get_basis(ctx, len / 4, true, true, 4, &e1));
-            for (int b = 0; b < 4; ++b) SSW_TRY(get_basis(ctx, len / 2, true, true, b == 1 ? 10 : 5 + b, &sb2[b]));
-            SSW_TRY(get_basis(ctx, len / 2, false, true, 9, &rot2));
-            SSW_TRY(grow(ws.operand[1], std::max<size_t>(bytes, lines * (len / 4) * sizeof(double))));
-            SSW_TRY(grow(ws.operand[4], std::max<size_t>(bytes, lines * (len / 2) * sizeof(double))));
-            // Row passes of 1280 columns or more (a multiple of 256) run at LEVEL 2 (r4c, dct_pair_efold_inv), the transpose of
-            // the forward pass's: every launch sums len/16 coefficients --
-            //   the quarter-length even part T2 = (its even half A1: kind 1 sub 2, folded) +/- (its odd half: R2 rotated, kind 9)
-            //   the half-length odd part (kinds 3 / 4 sub 1) as at level 1:  E = T2 +/- .
-            //   the odd part: class E folded (kinds 5 / 6), class O rotated (kinds 7 / 8):  x = E +/- .
-            // 8/14 of the level-1 pass's multiply-adds.
-            // Column passes of 720 rows or more likewise (dct_pair_efold_cols).
-            const bool cm0 = !x.natural_order && w >= h && w % 4 == 0 && dct_pair_can_deep_inv_rows(w) && cols_read_class_major(h, w) &&
-                             (is_row ? first_pass : !first_pass);
-            const bool il2 = is_row ? dct_pair_efold_inv(len) : dct_pair_efold_cols(len, w, cm0);
-            void* A1 = nullptr;
-            if (il2) {
-                SSW_TRY(get_basis(ctx, len / 4, false, true, 9, &rot3));
-                SSW_TRY(get_basis(ctx, len / 8, true, true, 3, &h0));
-                SSW_TRY(get_basis(ctx, len / 8, true, true, 4, &h1));
-                SSW_TRY(grow(ws.operand[2], std::max<size_t>(bytes, lines * (len / 8) * sizeof(double))));      // (>= what any other pass asks of it)
-                A1 = ws.operand[2].p;             // the eighth-length even part, unrounded: len/8 doubles per line
-            }
-            void* T2 = ws.operand[1].p;       // quarter-length even half, unrounded
-            void* TE = ws.operand[4].p;       // the even half E, unrounded
-            const size_t p8 = lines * dct_pair_split_kpad(len), p16 = lines * dct_pair_split_kpad(len / 2);
-            double* q = sp + 6 * p8;
-            const void *sb0 = sb[0], *sb1 = sb[1], *sb2_ = sb[2], *sb3 = sb[3];
-            const void *t0 = sb2[0], *t1 = sb2[1], *t2 = sb2[2], *t3 = sb2[3];
-            // rows first and both passes deep: the row pass's split launches write (and exchange E) class-major
-            const bool cm = cm0;
-            const bool rcm = cm && is_row;
-            RgbSink sink;
-            if (!first_pass && !is_row && x.rgb_out && x.iq_i && x.iq_q) {
-                sink.iq_i = x.iq_i; sink.iq_q = x.iq_q; sink.rgb = x.rgb_out; sink.u8 = x.rgb_out_u8;
-                if (fused_rgb) *fused_rgb = true;
-            }
-            const bool with_sink = sink.rgb != nullptr;
-            ch.push_back({true, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_prep, st, prep_bytes);
-                if (!is_row) return launch_dct_pair_prep16_inv_cols(st, src, n, w, h, sp, (const double*)rot, (const double*)rot2, cm, (const double*)rot3);
-                return launch_dct_pair_prep16_inv_rows(st, src, n, w, h, sp, (const double*)rot, (const double*)rot2, (const double*)rot3);
-            }});
-            if (il2) {
-                auto P = [=](int j) { return (const double*)(sp + (size_t)j * p16); };      // the planes of prep16_inv_rows_l2_kernel
-                const double f_all = 8.0 * pair_gemm_flop(is_row, 7, 0, n, w, h);
-                const PairClassDesc da = {1, 2, P(8), P(9), (const double*)h0, (const double*)h1};             // c[16 s] | c[16 s + 8] -> A1
-                const PairClassDesc db = {9, 2, P(10), P(11), (const double*)t0, (const double*)t1};           // R2 rotated + A1 -> T2
-                const PairClassDesc d1[2] = {{3, 1, P(12), P(13), (const double*)t0, (const double*)t1},       // AS2 BD2 + T2 -> E
-                                             {4, 1, P(14), P(15), (const double*)t2, (const double*)t3}};      // AD2 BS2
-                const PairClassDesc d0[4] = {{5, 0, P(0), P(3), (const double*)t0, (const double*)t1},         // AS+ BD-  + E -> x
-                                             {6, 0, P(1), P(2), (const double*)t2, (const double*)t3},         // AS- BD+
-                                             {7, 0, P(4), P(5), (const double*)t0, (const double*)t1},         // O rotated, "+"
-                                             {8, 0, P(6), P(7), (const double*)t0, (const double*)t1}};        // O rotated, "-"
-                ch.push_back({false, [=](hipStream_t st) -> int {
-                    StageTimer t(ctx, st_pass, st, f_all);
-                    t.traffic(gemm_bytes(14.0));
-                    SSW_TRY(launch_dct_pair_gemm_multi_f64(st, is_row, true, 1, &da, dst, (double*)A1, n, w, h, ep));
-                    SSW_TRY(launch_dct_pair_gemm_multi_f64(st, is_row, true, 1, &db, dst, (double*)A1, n, w, h, ep, nullptr, (double*)T2, rcm));
-                    if (lines <= merge_max_lines()) {          // single frames: the classes of each dependent stage in one launch
-                        SSW_TRY(launch_dct_pair_gemm_multi_f64(st, is_row, true, 2, d1, dst, (double*)T2, n, w, h, ep, nullptr, (double*)TE, rcm));
-                        return launch_dct_pair_gemm_multi_f64(st, is_row, true, 4, d0, dst, (double*)TE, n, w, h, ep, with_sink ? &sink : nullptr, nullptr, rcm);
-                    }
-                    for (int c = 0; c < 2; ++c)
-                        SSW_TRY(launch_dct_pair_gemm_multi_f64(st, is_row, true, 1, &d1[c], dst, (double*)T2, n, w, h, ep, nullptr, (double*)TE, rcm));
-                    for (int c = 0; c < 4; ++c)
-                        SSW_TRY(launch_dct_pair_gemm_multi_f64(st, is_row, true, 1, &d0[c], dst, (double*)TE, n, w, h, ep, with_sink ? &sink : nullptr, nullptr, rcm));
-                    return SSW_OK;
-                }});
-                return SSW_OK;
-            }
-            const double f_all = pair_gemm_flop(is_row, 3, 0, n, w, h) + pair_gemm_flop(is_row, 4, 0, n, w, h) + pair_gemm_flop(is_row, 1, 1, n, w, h) +
-                                 pair_gemm_flop(is_row, 3, 1, n, w, h) + pair_gemm_flop(is_row, 4, 1, n, w, h);
-            ch.push_back({false, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_pass, st, f_all);
-                t.traffic(gemm_bytes(12.0));
-                SSW_TRY(pair_gemm(st, true, is_row, true, 1, 1, sp + 4 * p8, sp + 5 * p8, e0, e1, dst, T2, n, w, h, ep));
-                if (lines <= merge_max_lines()) {          // single frames: the two classes of each dependent stage in one launch
-                    const PairClassDesc d1[2] = {{3, 1, q, q + p16, (const double*)t0, (const double*)t1},
-                                                 {4, 1, q + 2 * p16, q + 3 * p16, (const double*)t2, (const double*)t3}};
-                    SSW_TRY(launch_dct_pair_gemm_multi_f64(st, is_row, true, 2, d1, dst, (double*)T2, n, w, h, ep, nullptr, (double*)TE, rcm));
-                    const PairClassDesc d0[2] = {{3, 0, sp, sp + p8, (const double*)sb0, (const double*)sb1},
-                                                 {4, 0, sp + 2 * p8, sp + 3 * p8, (const double*)sb2_, (const double*)sb3}};
-                    return launch_dct_pair_gemm_multi_f64(st, is_row, true, 2, d0, dst, (double*)TE, n, w, h, ep, with_sink ? &sink : nullptr, nullptr, rcm);
-                }
-                SSW_TRY(pair_gemm(st, true, is_row, true, 3, 1, q, q + p16, t0, t1, dst, T2, n, w, h, ep, nullptr, TE, rcm));
-                SSW_TRY(pair_gemm(st, true, is_row, true, 4, 1, q + 2 * p16, q + 3 * p16, t2, t3, dst, T2, n, w, h, ep, nullptr, TE, rcm));
-                SSW_TRY(pair_gemm(st, true, is_row, true, 3, 0, sp, sp + p8, sb0, sb1, dst, TE, n, w, h, ep, with_sink ? &sink : nullptr, nullptr, rcm));
-                return pair_gemm(st, true, is_row, true, 4, 0, sp + 2 * p8, sp + 3 * p8, sb2_, sb3, dst, TE, n, w, h, ep, with_sink ? &sink : nullptr, nullptr, rcm);
-            }});
-            return SSW_OK;
-        }
-        if (three) {
-            // forward pass, three levels: x- (odd frequencies), S- (2 mod 4), (SSS, SS-) (0 and 4 mod 8); on a column
-            // pass (8K: 4320 rows) the pre-pass transposes like the two-level one
-            for (int b = 0; b < 4; ++b) SSW_TRY(grow(ws.operand[b], bytes));
-            void* d1 = ws.operand[1].p;
-            void* d2 = ws.operand[0].p;
-            void* r1 = ws.operand[2].p;
-            void* r2 = ws.operand[3].p;
-            const void *h1 = nullptr, *e0 = nullptr, *e1 = nullptr;
-            SSW_TRY(get_basis(ctx, len / 2, false, f64, 4, &h1));          // odd half basis of len/2
-            SSW_TRY(get_basis(ctx, len / 4, false, f64, 3, &e0));          // half bases of len/4
-            SSW_TRY(get_basis(ctx, len / 4, false, f64, 4, &e1));
-            ch.push_back({true, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_prep, st, prep_bytes);
-                if (!is_row) SSW_TRY(launch_dct_pair_prep8_cols(st, f64, src, n, w, h, r1, r2, d2, d1));
-                else SSW_TRY(launch_dct_pair_prep8_rows(st, f64, from_rgb ? pix_src_kind(rgb_u8) : 0, from_rgb ? rgb : (const void*)src, n, w, h,
-                                                        r1, r2, d2, d1, from_rgb ? iq_i : nullptr, from_rgb ? iq_q : nullptr));
-                return odd_rotate(st, d1);
-            }});
-            const double f_main = f_odd;
-            const double f_all = f_main + pair_gemm_flop(is_row, 1, 1, n, w, h) + pair_gemm_flop(is_row, 2, 1, n, w, h);
-            ch.push_back({false, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_pass, st, f_all);
-                t.traffic(gemm_bytes(0.0));
-                SSW_TRY(pair_gemm(st, f64, is_row, inverse, 1, 1, r1, r2, e0, e1, dst, nullptr, n, w, h, ep));
-                SSW_TRY(pair_gemm(st, f64, is_row, inverse, 2, 1, d2, d2, h1, (const char*)h1 + (len / 8) * 64, dst, nullptr, n, w, h, ep));
-                StageTimer tm(ctx, st_main, st, f_main);
-                return odd_gemm(st, d1, b1, nullptr, nullptr);
-            }});
-        } else if (!two) {
-            for (int b = 0; b < 2; ++b) SSW_TRY(grow(ws.operand[b], bytes));
-            void* x1 = ws.operand[0].p;
-            void* x2 = ws.operand[1].p;
-            ch.push_back({true, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, SSW_STAGE_DCT_PREP, st, prep_bytes);
-                return launch_dct_pair_prep(st, f64, is_row, inverse, src, n, w, h, x1, x2);
-            }});
-            const double f_main = pair_gemm_flop(is_row, 0, 0, n, w, h);
-            ch.push_back({false, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_pass, st, f_main);
-                t.traffic(gemm_bytes(0.0));
-                StageTimer tm(ctx, st_main, st, f_main);
-                return pair_gemm(st, f64, is_row, inverse, 0, 0, x1, x2, b0, b1, dst, nullptr, n, w, h, ep);
-            }});
-        } else {
-            for (int b = 1; b < (inverse ? 5 : 4); ++b) SSW_TRY(grow(ws.operand[b], bytes));
-            void* x2 = ws.operand[1].p;       // D | O
-            void* xx1 = ws.operand[2].p;      // SS | EE
-            void* xx2 = ws.operand[3].p;      // SD | EO
-            void* tmpE = ws.operand[4].p;     // inverse: the even half E, unrounded
-            const void *q0 = nullptr, *q1 = nullptr;
-            SSW_TRY(get_basis(ctx, len / 2, inverse, f64, 3, &q0));
-            SSW_TRY(get_basis(ctx, len / 2, inverse, f64, 4, &q1));
-            ch.push_back({true, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_prep, st, prep_bytes);
-                if (from_rgb) SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, f64, rgb_u8, rgb, n, w, h, xx1, xx2, x2, iq_i, iq_q));
-                else SSW_TRY(launch_dct_pair_prep4(st, f64, is_row, inverse, src, n, w, h, xx1, xx2, x2));
-                return odd_rotate(st, x2);
-            }});
-            const double f_main = f_odd;
-            const double f_all = f_main + pair_gemm_flop(is_row, 1, 0, n, w, h);
-            // Writer::result: the last pass of an inverse transform (a column pass) converts to RGB in its epilogue
-            RgbSink sink;
-            if (inverse && !first_pass && !is_row && x.rgb_out && x.iq_i && x.iq_q) {
-                sink.iq_i = x.iq_i; sink.iq_q = x.iq_q; sink.rgb = x.rgb_out; sink.u8 = x.rgb_out_u8;
-                if (fused_rgb) *fused_rgb = true;
-            }
-            const bool with_sink = sink.rgb != nullptr;
-            ch.push_back({false, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, st_pass, st, f_all);
-                t.traffic(gemm_bytes(inverse ? esz : 0.0));          // inverse: the even half E out and in
-                // even half: a half-length transform of S (forward) / of the even coefficients (inverse), folded again
-                SSW_TRY(pair_gemm(st, f64, is_row, inverse, 1, 0, xx1, xx2, q0, q1, dst, tmpE, n, w, h, ep));
-                // odd half: full half-length sum, the odd basis split into two row blocks (second block:
-                // len/4 lines further inside every k-block of the same plane = 64 bytes per line)
-                StageTimer tm(ctx, st_main, st, f_main);
-                return odd_gemm(st, x2, b1, tmpE, with_sink ? &sink : nullptr);
-            }});
-        }
-        return SSW_OK;
-    }
-    const void *b0 = nullptr, *b1 = nullptr;
-    if (fold) {
-        SSW_TRY(get_basis(ctx, len, inverse, f64, 1, &b0));
-        SSW_TRY(get_basis(ctx, len, inverse, f64, 2, &b1));
-    } else {
-        SSW_TRY(get_basis(ctx, len, inverse, f64, 0, &b0));
-    }
-    const double dense = is_row ? 2.0 * n * h * (double)w * w : 2.0 * n * w * (double)h * h;
-    const double flop = fold ? 0.5 * dense : dense;
-    if (is_row) {
-        ch.push_back({false, [=](hipStream_t st) -> int {
-            StageTimer t(ctx, SSW_STAGE_DCT_ROW, st, flop);
-            t.traffic(px * 8.0);
-            if (fold && f64) return launch_dct_rows_folded_f64(st, inverse, src, dst, n * h, w, (const double*)b0, (const double*)b1, ep);
-            if (fold) return launch_dct_rows_folded_f32(st, inverse, src, dst, n * h, w, (const float*)b0, (const float*)b1, ep);
-            return launch_dct_rows(st, precision, src, dst, n * h, w, b0, ep);
-        }});
-    } else {
-        ch.push_back({false, [=](hipStream_t st) -> int {
-            StageTimer t(ctx, SSW_STAGE_DCT_COL, st, flop);
-            t.traffic(px * 8.0);
-            if (fold && f64) return launch_dct_cols_folded_f64(st, inverse, src, dst, n, w, h, (const double*)b0, (const double*)b1, ep);
-            if (fold) return launch_dct_cols_folded_f32(st, inverse, src, dst, n, w, h, (const float*)b0, (const float*)b1, ep);
-            return launch_dct_cols(st, precision, src, dst, n, w, h, b0, ep);
-        }});
-    }
-    return SSW_OK;
-}
-
-// The operand-ready GEMMs walk an operand plane with 32-bit scalar offsets: a call's planes must stay below
-// 4 GB, so more frames than that are transformed in groups (frames are independent).
-size_t operand_frame_limit(const ssw_ctx* ctx, bool f64, size_t w, size_t h) {
-    if (!(ctx->fold && ctx->fold_level >= 3)) return ~(size_t)0;
-    const size_t per_frame = dct_pair_operand_elems(f64, 1, w, h) * (f64 ? sizeof(double) : sizeof(float));
-    const size_t m = per_frame ? 0xFFFFFFFFull / per_frame : ~(size_t)0;
-    return m >= 1 ? m : ~(size_t)0;
 }
 
 }  // namespace
@@ -870,7 +777,7 @@ int build_transform(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, Chain& ch, 
     const bool f64 = (x.precision == SSW_PRECISION_F64);
     const size_t n = x.n, w = x.w, h = x.h;
     if (n == 0) return SSW_OK;
-    const size_t max_frames = operand_frame_limit(ctx, f64, w, h);
+    const size_t max_frames = plan_frame_limit(plan_settings(ctx), f64, w, h);
     if (n > max_frames) {
         for (size_t f0 = 0; f0 < n; f0 += max_frames) {
             Xform s = x;
@@ -903,8 +810,16 @@ int build_transform(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, Chain& ch, 
     return SSW_OK;
 }
 
+namespace {
+// the row pass of a forward transform of n frames between the planes a and b
+PassPlan forward_rows_plan(const ssw_ctx* ctx, bool f64, size_t n, size_t w, size_t h, const float* a, const float* b) {
+    return plan_pass({SSW_DCT2, f64 ? SSW_PRECISION_F64 : SSW_PRECISION_F32, n, w, h, 0, false, aligned_planes(a, b), plan_settings(ctx)}, true, true);
+}
+}  // namespace
+
+// the row pass takes two folding levels or more (its pre-pass can read RGB) and the frames suit that pre-pass
 bool can_fuse_rgb(const ssw_ctx* ctx, bool f64, size_t w, size_t h, const float* y, const float* tmp, const void* rgb, int u8) {
-    return ctx->fold && ctx->fold_level >= 4 && dct_pair_can_run(f64, 1, w, h, y, tmp) && dct_pair_can_prep_from_rgb(w, h, rgb, u8);
+    return forward_rows_plan(ctx, f64, 1, w, h, y, tmp).levels >= 2 && dct_pair_can_prep_from_rgb(w, h, rgb, u8);
 }
 
 // Writer::new / Reader::base / Reader::derived: rgb -> Y (+ I, Q) -> forward 2-D DCT of Y into `y`.
@@ -1111,10 +1026,8 @@ int run_pipeline(ssw_ctx* ctx, size_t n_chunks, const std::function<int(size_t, 
 struct PruneSetup {
     bool on = false;
     PrunePlan plan;
-    int levels = 0;                 // folding levels of the forward row pass: 2 or 3
-    bool split = false;             // odd frequencies through the split odd half (two classes instead of one)
-    bool deep = false;              // deep row pre-pass: frequencies 2 mod 4 split as well, 0 / 4 mod 8 from the third level
-};
+    PassPlan rows;                  // of the full transform's row pass: levels 2 or 3; the split odd half (two classes instead
+};                                  // of one); deep: frequencies 2 mod 4 split as well, 0 / 4 mod 8 from the third level
 
 // capacity of the compact plane in frequency columns: the index lists of natural spectra use ~3 sqrt(k)
 // distinct columns (measured: 80..110 for k = 1000 at full HD and 4K); 8 sqrt(k), split over the classes
@@ -1131,25 +1044,24 @@ PruneSetup make_prune_setup(const ssw_ctx* ctx, bool f64, size_t n, size_t w, si
     PruneSetup ps;
     if (!ctx->prune || k == 0) return ps;
     if (!can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, u8)) return ps;       // rows first, >= two folding levels on the rows
-    if (!dct_pair_can_run(f64, n, w, h, y, tmp)) return ps;               // the chunk's planes within the 4 GB walk
+    const bool aligned = aligned_planes(y, tmp);
+    if (!dct_pair_can_run(f64, n, w, h, aligned)) return ps;              // the chunk's planes within the 4 GB walk
     const size_t cap = prune_capacity(k);
     if (cap * 4 > w) return ps;                                           // not worth it: full transform
-    if (!dct_pair_can_run(f64, n, cap, h, y, tmp)) return ps;
-    const bool three = dct_pair_can_fold3(w) && (ctx->fold_level >= 6 || (ctx->fold_level == 5 && w >= 3072));
-    ps.levels = three ? 3 : 2;
+    if (!dct_pair_can_run(f64, n, cap, h, aligned)) return ps;
+    ps.rows = forward_rows_plan(ctx, f64, n, w, h, y, tmp);
+    const bool deep = plan_is_deep(ps.rows);
     ps.plan.W = (unsigned)w;
     ps.plan.cap_total = (unsigned)cap;
     const unsigned c = (unsigned)cap;
-    ps.split = f64 && ctx->split && dct_pair_can_split(w, true);
     unsigned nc = 0, off = 0;
     auto add = [&](unsigned mod, unsigned rem, unsigned cc, unsigned rem2 = PRUNE_NO_REM, unsigned radd = 0) {
         ps.plan.c[nc] = {mod, rem, cc, off, rem2, radd};
         off += cc;
         ++nc;
     };
-    ps.deep = ps.split && dct_pair_can_deep_rows(w);
-    if (ps.deep && dct_pair_efold(w)) {
-        // level 2 (build_pass): nine classes of sums of w/16 terms; v = 16i +/- r -> row i (= (v + r) / 16) of the bases of
+    if (plan_is_level2(ps.rows)) {
+        // level 2 (build_deep_l2): nine classes of sums of w/16 terms; v = 16i +/- r -> row i (= (v + r) / 16) of the bases of
         // E even, v = 16i + 9 | 16i + 7 -> row i of E odd; the same two for the half-length split; R1 folded: 16i, 16i + 8
         add(16, 1, c / 8, 15, 1);         // AS+ BD-
         add(16, 9, c / 8, 7, 0);          // AS- BD+
@@ -1164,18 +1076,18 @@ PruneSetup make_prune_setup(const ssw_ctx* ctx, bool f64, size_t n, size_t w, si
         ps.on = true;
         return ps;
     }
-    if (ps.split) {                       // odd v = 8i +/- 1 -> class E row i (= (v + 1) / 8), v = 8i + 5 | 8i + 3 -> class O row i
+    if (ps.rows.split) {                  // odd v = 8i +/- 1 -> class E row i (= (v + 1) / 8), v = 8i + 5 | 8i + 3 -> class O row i
         add(8, 1, c / 4, 7, 1);
         add(8, 5, c / 4, 3, 0);
     } else {
         add(2, 1, c / 2);
     }
-    if (ps.deep) {                        // v = 2 (8i +/- 1) -> class E' row i (= (v + 2) / 16), v = 2 (8i + 5) | 2 (8i + 3) -> class O' row i
+    if (deep) {                           // v = 2 (8i +/- 1) -> class E' row i (= (v + 2) / 16), v = 2 (8i + 5) | 2 (8i + 3) -> class O' row i
         add(16, 2, c / 8, 14, 2);
         add(16, 10, c / 8, 6, 0);
         add(8, 0, c / 8);
         add(8, 4, c / 8);
-    } else if (three) {
+    } else if (ps.rows.levels == 3) {
         add(4, 2, c / 4);
         add(8, 0, c / 8);
         add(8, 4, c / 8);
@@ -1197,7 +1109,9 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
     const PrunePlan plan = ps.plan;
     const size_t cap = plan.cap_total;
     const size_t bytes = dct_pair_operand_elems(f64, n, w, h) * esz;
-    if (!ps.deep) for (int b = 0; b < 4; ++b) SSW_TRY(grow(ws.operand[b], bytes));      // the deep pre-pass writes into operand[5] only
+    const int levels = ps.rows.levels;
+    const bool deep = plan_is_deep(ps.rows), level2 = plan_is_level2(ps.rows);
+    if (!deep) for (int b = 0; b < 4; ++b) SSW_TRY(grow(ws.operand[b], bytes));      // the deep pre-pass writes into operand[5] only
     for (int b = 0; b < 2; ++b) SSW_TRY(grow(ws.compact[b], n * h * cap * sizeof(float)));
     SSW_TRY(grow(ws.prune_u32, (2 * w + cap + 64) * sizeof(uint32_t)));
     uint32_t* flag = (uint32_t*)ws.prune_u32.p;
@@ -1207,12 +1121,11 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
     struct ClassSrc { const void* x; const void* basis; size_t src_rows, kp, ktrue; const void* x2 = nullptr; const void* basis2 = nullptr; };
     ClassSrc cs[9];
     int pn1[9] = {0}, pn2[9] = {0};          // level 2: the classes' operand planes by number (the fused kernel's A-fragments)
-    bool level2 = false;
     unsigned ci = 0;
     const size_t lines = n * h;
     const void *rot = nullptr, *rot2 = nullptr, *rot3 = nullptr;
     double* sp = nullptr;
-    if (ps.deep && dct_pair_efold(w)) {          // level 2: the plan of make_prune_setup, planes by number like build_pass
+    if (level2) {             // level 2: the classes of make_prune_setup, planes by number (kL2Classes)
         const void *sb2[4], *h0 = nullptr, *h1 = nullptr;
         for (int b = 0; b < 4; ++b) SSW_TRY(get_basis(ctx, w / 2, false, true, 5 + b, &sb2[b]));
         SSW_TRY(get_basis(ctx, w, false, true, 9, &rot));
@@ -1225,19 +1138,19 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
         const size_t kp16 = dct_pair_split_kpad(w / 2), p16 = lines * kp16;
         const size_t re = dct_pair_split_basis_rows(w / 2, 0), ro = dct_pair_split_basis_rows(w / 2, 2);
         auto P = [=](int j) { return (const void*)(sp + (size_t)j * p16); };
-        cs[ci++] = {P(0), sb2[0], re, kp16, w / 16, P(3), sb2[1]};
-        cs[ci++] = {P(1), sb2[2], ro, kp16, w / 16, P(2), sb2[3]};
-        cs[ci++] = {P(4), sb2[0], re, kp16, w / 16, P(5), sb2[1]};
-        cs[ci++] = {P(6), sb2[0], re, kp16, w / 16, P(7), sb2[1]};
-        cs[ci++] = {P(12), sb2[0], re, kp16, w / 16, P(13), sb2[1]};
-        cs[ci++] = {P(14), sb2[2], ro, kp16, w / 16, P(15), sb2[3]};
-        cs[ci++] = {P(10), sb2[0], re, kp16, w / 16, P(11), sb2[1]};
-        cs[ci++] = {P(8), h0, w / 16, kp16, w / 16};
-        cs[ci++] = {P(9), h1, w / 16, kp16, w / 16};
-        static const int planes_l2[9][2] = {{0, 3}, {1, 2}, {4, 5}, {6, 7}, {12, 13}, {14, 15}, {10, 11}, {8, -1}, {9, -1}};
-        for (int c = 0; c < 9; ++c) { pn1[c] = planes_l2[c][0]; pn2[c] = planes_l2[c][1]; }
-        level2 = true;
-    } else if (ps.split) {
+        // the pair classes in the plan's order (16i +/- 1, 16i + 9 | 7, +/- 5, +/- 3, +/- 2, 10 | 6, +/- 4), then R1's two planes
+        for (int k : {4, 5, 7, 6, 2, 3, 1}) {
+            const L2Class& lc = kL2Classes[k];
+            pn1[ci] = lc.x1; pn2[ci] = lc.x2;
+            cs[ci++] = {P(lc.x1), sb2[2 * lc.basis], lc.basis ? ro : re, kp16, w / 16, P(lc.x2), sb2[2 * lc.basis + 1]};
+        }
+        const L2Class& r1 = kL2Classes[0];
+        for (int j = 0; j < 2; ++j) {
+            const int x = j ? r1.x2 : r1.x1;
+            pn1[ci] = x; pn2[ci] = -1;
+            cs[ci++] = {P(x), j ? h1 : h0, w / 16, kp16, w / 16};
+        }
+    } else if (ps.rows.split) {
         const void* sb[4];
         for (int b = 0; b < 4; ++b) SSW_TRY(get_basis(ctx, w, false, true, 5 + b, &sb[b]));
         SSW_TRY(get_basis(ctx, w, false, true, 9, &rot));
@@ -1247,10 +1160,10 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
         const void *sb2[4] = {nullptr, nullptr, nullptr, nullptr}, *e0 = nullptr, *e1 = nullptr;
         const size_t kp16 = dct_pair_split_kpad(w / 2), p16 = lines * kp16;
         double* q = sp + 6 * plane;
-        if (ps.deep) for (int b = 0; b < 4; ++b) SSW_TRY(get_basis(ctx, w / 2, false, true, 5 + b, &sb2[b]));
+        if (deep) for (int b = 0; b < 4; ++b) SSW_TRY(get_basis(ctx, w / 2, false, true, 5 + b, &sb2[b]));
         cs[ci++] = {sp, sb[0], dct_pair_split_basis_rows(w, 0), kp8, w / 8, sp + plane, sb[1]};              // AS x cosE, BD x sinE
         cs[ci++] = {sp + 2 * plane, sb[2], dct_pair_split_basis_rows(w, 2), kp8, w / 8, sp + 3 * plane, sb[3]};  // AD x cosO, BS x sinO
-        if (ps.deep) {
+        if (deep) {
             SSW_TRY(get_basis(ctx, w / 2, false, true, 9, &rot2));
             SSW_TRY(get_basis(ctx, w / 4, false, true, 3, &e0));
             SSW_TRY(get_basis(ctx, w / 4, false, true, 4, &e1));
@@ -1264,8 +1177,8 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
         SSW_TRY(get_basis(ctx, w, false, f64, 4, &b1));
         cs[ci++] = {ws.operand[1].p, b1, w / 2, dct_pair_kpad(f64, w), w / 2};       // x- | D : odd
     }
-    if (ps.deep) {
-    } else if (ps.levels == 3) {
+    if (deep) {
+    } else if (levels == 3) {
         const void *h1 = nullptr, *e0 = nullptr, *e1 = nullptr;
         SSW_TRY(get_basis(ctx, w / 2, false, f64, 4, &h1));
         SSW_TRY(get_basis(ctx, w / 4, false, f64, 3, &e0));
@@ -1291,8 +1204,6 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
     char* gathered = (char*)ws.gathered.p;
     float* t_compact = (float*)ws.compact[0].p;
     void *o0 = ws.operand[0].p, *o1 = ws.operand[1].p, *o2 = ws.operand[2].p, *o3 = ws.operand[3].p;
-    const int levels = ps.levels;
-    const bool deep = ps.deep;
     const double px = (double)n * (double)w * (double)h;
     const double prep_bytes = px * (3.0 * (double)pix_bytes(u8) + (double)esz);
     double flop = 0.0;
@@ -1314,7 +1225,7 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
             fc[c] = {(const double*)(gathered + goff[c]), cs[c].x2 ? (const double*)(gathered + goff2[c]) : nullptr, (unsigned)pn1[c],
                      (unsigned)(pn2[c] < 0 ? 0 : pn2[c]), plan.c[c].cap, plan.c[c].off, cs[c].x2 != nullptr};
         // (a single frame is 135 blocks of 16 lines for 256 CUs: the merged launches below are 35 us faster there)
-        if (lines > (size_t)tuning(TUNE_MERGE_MAX_LINES) && dct_pair_derived_fused_ok(w, plan.n_classes, fc)) {
+        if (plan_derived_fused(ps.rows, lines) && dct_pair_derived_fused_fits(plan.n_classes, fc)) {
             const unsigned ncl = plan.n_classes;
             std::array<DerivedFusedClass, 9> fca;
             for (unsigned c = 0; c < 9; ++c) fca[c] = fc[c < ncl ? c : 0];
@@ -1342,7 +1253,7 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
         untimed_work(ctx);
         StageTimer t(ctx, SSW_STAGE_RGB_TO_YIQ, st, prep_bytes);
         if (deep) return launch_dct_pair_prep16_rows(st, pix_src_kind(u8), rgb, n, w, h, sp, (const double*)rot, (const double*)rot2,
-                                                     (const double*)rot3, nullptr, nullptr);
+                                                     (const double*)rot3, nullptr, nullptr, level2);
         if (levels == 3) SSW_TRY(launch_dct_pair_prep8_rows(st, f64, pix_src_kind(u8), rgb, n, w, h, o2, o3, o0, o1, nullptr, nullptr));
         else SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, f64, u8, rgb, n, w, h, o2, o3, o1, nullptr, nullptr));
         return sp ? launch_dct_pair_rotate(st, (const double*)o1, (const double*)rot, sp, lines, w) : SSW_OK;
@@ -1353,7 +1264,7 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
         untimed_work(ctx);
         StageTimer t(ctx, SSW_STAGE_DCT_ROW, st, flop);
         t.traffic(px * (double)esz + (double)lines * (double)cap * 4.0);      // every operand plane once in, the compact plane out
-        if (f64 && lines <= (size_t)tuning(TUNE_MERGE_MAX_LINES)) {          // a single frame: the classes side by side in one launch per kind
+        if (f64 && plan_merge(lines)) {          // a single frame: the classes side by side in one launch per kind
             PairSubsetClass sc[9];
             for (unsigned c = 0; c < plan.n_classes; ++c)
                 sc[c] = {(const double*)cs[c].x, (const double*)cs[c].x2, (const double*)(gathered + goff[c]),

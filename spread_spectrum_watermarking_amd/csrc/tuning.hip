@@ -22,9 +22,9 @@ struct Entry {
 };
 
 Entry g_tune[TUNE_COUNT] = {
-    {"efold_min", "SSW_EFOLD_MIN", 1280},              // shortest forward row pass at level 2 (dct_pair_efold)
-    {"efold_inv_min", "SSW_EFOLD_INV_MIN", 1280},      // shortest inverse row pass at level 2 (dct_pair_efold_inv)
-    {"efold_cols_min", "SSW_EFOLD_COLS_MIN", 720},     // shortest column pass at level 2 (dct_pair_efold_cols)
+    {"efold_min", "SSW_EFOLD_MIN", 1280},              // shortest forward row pass at level 2 (dct_plan.hip)
+    {"efold_inv_min", "SSW_EFOLD_INV_MIN", 1280},      // shortest inverse row pass at level 2 (dct_plan.hip)
+    {"efold_cols_min", "SSW_EFOLD_COLS_MIN", 720},     // shortest column pass at level 2 (dct_plan.hip)
     {"class_tile", "SSW_CLASS_TILE", 1},               // class-major order inside tiles of 128 columns (0: one tile per line)
     {"deep_min_rows", "SSW_DEEP_MIN_ROWS", 256},       // shortest row pass that takes the deep pre-passes
     {"deep_min_cols", "SSW_DEEP_MIN_COLS", 256},       // ... column pass

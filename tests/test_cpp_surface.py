@@ -32,6 +32,16 @@ def test_class_major_layout_maps_on_the_host(tmp_path):
     assert out.strip() == "ok"
 
 
+def test_transform_planner_on_the_host(tmp_path):
+    """csrc/dct_plan.hpp: the strategy of every pass for the shapes DESIGN 4.0 names, the folding levels, the odd split off and
+    lowered thresholds (ssw_tuning_set), and the SSW_PLAN_* flags as a function of the plan -- no GPU, no context."""
+    exe = os.path.join(str(tmp_path), "dct_plan_test")
+    subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "--offload-arch=gfx950", os.path.join(ROOT, "tests", "cpp", "dct_plan_test.cpp"),
+                    "-o", exe, "-L", LIBDIR, "-lssw_hip", f"-Wl,-rpath,{LIBDIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    assert out.strip() == "ok", out
+
+
 def test_cpp_wrappers_compile_and_link(tmp_path):
     exe = build(tmp_path)
     assert os.path.exists(exe)

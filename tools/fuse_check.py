@@ -19,7 +19,7 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-# (h, w, frames): frames chosen so that both passes run on 128-line tiles (dct_pair_can_fuse_cols)
+# (h, w, frames): frames chosen so that both passes run on 128-line tiles (csrc/dct_plan.hip: PassStrategy::FusedRows / FusedCols)
 SHAPES = [(256, 256, 224), (272, 512, 150), (720, 1280, 46), (1088, 2048, 25), (2160, 3840, 8), (4320, 7680, 2),
           (2160, 3840, 1), (4320, 7680, 1), (2160, 3840, 2)]           # single frames: the eight classes of a pass in ONE launch
 BATCH = [(720, 1280, 48, 300), (2160, 3840, 8, 1000)]           # (h, w, frames, k)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The level-2 row passes (forward: dct_pair_efold, inverse: dct_pair_efold_inv -- by default rows of 1280 columns or more)
-and column passes (dct_pair_efold_cols: 720 rows or more) on SMALL shapes the oracle finishes in seconds: the thresholds
+"""The level-2 row passes (PassStrategy::DeepL2 / DeepInvL2 of csrc/dct_plan.hip -- by default rows of 1280 columns or more)
+and column passes (DeepL2 / DeepInvL2 columns: 720 rows or more) on SMALL shapes the oracle finishes in seconds: the thresholds
 are lowered through ssw_tuning_set (efold_min = efold_inv_min = 256, efold_cols_min = 64) so that every row of a multiple of
 64 (forward) / 256 (inverse) columns and every column of a multiple of 16 rows takes them; tests/test_fuzz_gpu.py calls
 run() in-process.  Transforms against the oracle's correctly rounded one, and two batch pipelines (pruned + two lanes

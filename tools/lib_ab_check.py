@@ -2,7 +2,9 @@
 """Bit-for-bit A/B of two builds of the library (e.g. lib/libssw_hip.so against a variant of tools/build_variant.sh): every build
 runs in a child process (SSW_LIB_PATH), transforms the same synthetic frames -- ssw_dct2d forward, orthonormal and inverse on
 shapes of every strategy, one batch embed + extract -- and prints a digest per case; the parent compares the digests.
-usage: python tools/lib_ab_check.py LIB_A LIB_B
+usage: python tools/lib_ab_check.py [--stages] LIB_A LIB_B
+       --stages: also the stage accounts of every case (ssw_ctx_get_timing launch counts, ssw_ctx_get_work, ssw_ctx_get_traffic),
+                 and the cases again at folding levels 0, 3, 4, 6 and with the odd split off on the 4K, 1080p and 512 x 272 shapes
        python tools/lib_ab_check.py --golden LIB OUT.json     (writes the digests of one build, in the format of
                                                               tests/golden/gemm_digests.json: the r5 kernel's digests, kept as recorded)"""
 import hashlib
@@ -12,6 +14,11 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(2160, 3840, 8), (2160, 3840, 1), (1080, 1920, 12), (720, 1280, 20), (4320, 7680, 2), (272, 512, 40), (444, 640, 3), (2160, 3840, 3)]
+BATCH = ((2160, 3840, 8), (1080, 1920, 12), (272, 512, 40))
+# --stages: non-default strategy settings, each on these shapes (the first tag is the default, covered by SHAPES)
+SETTINGS = (("fold0", "set_dct_folding", 0), ("fold3", "set_dct_folding", 3), ("fold4", "set_dct_folding", 4),
+            ("fold6", "set_dct_folding", 6), ("nosplit", "set_odd_split", False))
+SETTING_SHAPES = ((2160, 3840, 8), (1080, 1920, 12), (272, 512, 40))
 
 
 def child():
@@ -23,19 +30,43 @@ def child():
     from spread_spectrum_watermarking_amd.api import check
     ctx = wm.Context(0)
     lib = ctx._lib
-    for (h, w, n) in SHAPES:
+    stages = os.environ.get("SSW_AB_STAGES") == "1"
+    if stages:
+        ctx.enable_timing(True)
+        ctx.reset_timing()
+
+    def accounts(case):
+        # launches, work and traffic of every stage the case used (one token: the parent compares it like a digest)
+        if not stages:
+            return
+        t = ctx.timing()
+        acc = ",".join(f"{s}:{v['launches']}:{v['work']!r}:{v['bytes']!r}" for s, v in t.items() if v["launches"] or v["work"] or v["bytes"])
+        print(f"DIGEST stages {case} {acc}", flush=True)
+        ctx.reset_timing()
+
+    cases = [(h, w, n, "") for (h, w, n) in SHAPES]
+    if stages:
+        cases += [(h, w, n, tag) for tag, _, _ in SETTINGS for (h, w, n) in SETTING_SHAPES]
+    for (h, w, n, tag) in cases:
+        for t, fn, val in SETTINGS:
+            if t == tag:
+                getattr(ctx, fn)(val)
+        pre = f"{tag} " if tag else ""
         rgb = ctx.alloc(n * h * w * 12)
         check(lib.ssw_synth_frames(ctx.handle, 7, 0, n, w, h, rgb.ptr), "synth")
         y = ctx.alloc(n * h * w * 4)
         check(lib.ssw_rgb_to_yiq(ctx.handle, rgb.ptr, n, w, h, y.ptr, None, None), "yiq")
         y0 = y.to_host(np.float32, (n, h, w))
+        if stages:
+            ctx.reset_timing()
         for kind, name in ((L.DCT2, "fwd"), (L.DCT2_ORTHOGONAL, "ortho"), (L.DCT3, "inv")):
             t = ctx.to_device(y0)
             check(lib.ssw_dct2d(ctx.handle, kind, L.PRECISION_F64, n, w, h, t.ptr), "dct")
             out = t.to_host(np.float32, (n, h, w))
-            print(f"DIGEST dct {h}x{w}x{n} {name} {hashlib.sha256(out.tobytes()).hexdigest()[:16]}", flush=True)
+            print(f"DIGEST {pre}dct {h}x{w}x{n} {name} {hashlib.sha256(out.tobytes()).hexdigest()[:16]}", flush=True)
+            accounts(f"{pre}dct {h}x{w}x{n} {name}")
             t.free()
-        if (h, w, n) in ((2160, 3840, 8), (1080, 1920, 12), (272, 512, 40)):
+        if (h, w, n) in BATCH:
             k = 500
             marks = np.random.default_rng(3).standard_normal((n, k)).astype(np.float32)
             dm = ctx.to_device(marks)
@@ -44,10 +75,14 @@ def child():
             check(lib.ssw_batch_embed(ctx.handle, C.byref(cfg), rgb.ptr, n, w, h, dm.ptr, k, out.ptr, None, None), "embed")
             check(lib.ssw_batch_extract(ctx.handle, C.byref(cfg), rgb.ptr, out.ptr, n, w, h, k, ext.ptr, dm.ptr, sims.ptr), "extract")
             for nm, b, shp in (("marked", out, (n, h, w, 3)), ("ext", ext, (n, k)), ("sims", sims, (n,))):
-                print(f"DIGEST batch {h}x{w}x{n} {nm} {hashlib.sha256(b.to_host(np.float32, shp).tobytes()).hexdigest()[:16]}", flush=True)
+                print(f"DIGEST {pre}batch {h}x{w}x{n} {nm} {hashlib.sha256(b.to_host(np.float32, shp).tobytes()).hexdigest()[:16]}", flush=True)
+            accounts(f"{pre}batch {h}x{w}x{n}")
             for b in (dm, out, ext, sims):
                 b.free()
         rgb.free(); y.free()
+        if tag:
+            ctx.set_dct_folding(True)
+            ctx.set_odd_split(True)
     ctx.close()
 
 
@@ -74,9 +109,11 @@ def main():
                        "digests": d}, f, indent=1)
         print(f"{len(d)} digests -> {sys.argv[3]}")
         return 0
-    libs = sys.argv[1:3]
+    args = [a for a in sys.argv[1:] if a != "--stages"]
+    env = {"SSW_AB_STAGES": "1"} if "--stages" in sys.argv else None
+    libs = args[:2]
     try:
-        res = [digests(lib) for lib in libs]
+        res = [digests(lib, env) for lib in libs]
     except RuntimeError as e:
         print(e)
         return 2

@@ -48,7 +48,7 @@ lines_p = chunk * 16 * (-(-(H // 16) // 8) * 8) if H % 16 == 0 else lines_r     
 esz = 8
 K8 = lambda n: -(-(n // 8) // 16) * 16        # padded sum length of the n/8-wide operand planes
 K16 = lambda n: -(-(n // 16) // 16) * 16      # ... of the n/16-wide ones
-# level 2 (csrc/dct_pair_prep.hip dct_pair_efold / dct_pair_efold_cols): rows of 1280 columns or more, columns of 720 rows or more
+# level 2 (csrc/dct_plan.hip, PassStrategy::DeepL2 / DeepInvL2): rows of 1280 columns or more, columns of 720 rows or more
 # (a multiple of 16): every launch sums n/16 terms over n/16 pairs; below, the full-length classes sum n/8 terms over n/8 pairs
 l2r, l2c = W >= 1280 and W % 64 == 0, H >= 720 and H % 16 == 0
 PR, KR = (W // 16, K16(W)) if l2r else (W // 8, K8(W))
