@@ -69,9 +69,9 @@ typedef enum ssw_dct_type {
 /* Arithmetic of the DCT basis GEMMs (no counterpart in the reference, which
    delegates to rustdct's f32 FFT kernels). */
 typedef enum ssw_precision {
-    SSW_PRECISION_F32 = 0,        /* v_mfma_f32_32x32x2_f32: f32 fma chains.  NOT a parity path: extracted
-                                     marks within 1e-5 in the median, ~1e-3 worst case; since r3 (split
-                                     odd halves in f64) it is also the slower precision at 4K */
+    SSW_PRECISION_F32 = 0,        /* v_mfma_f32_32x32x2_f32: f32 fma chains of the dense GEMMs (no folding).
+                                     NOT a parity path: extracted marks within 1e-4 in the median, 5e-3
+                                     worst case; the slower precision wherever f64 folds */
     SSW_PRECISION_F64 = 1         /* DEFAULT.  v_mfma_f64_16x16x4_f64, f64 basis, result rounded
                                      once to f32: the correctly rounded ("canonical") transform,
                                      bit-identical extraction against the CPU restatement   */
@@ -93,10 +93,7 @@ typedef struct ssw_reader ssw_reader;
 
 /* ---- library / context ---------------------------------------------------- */
 const char* ssw_version(void);
-/* 1 when the loaded library is the diagnostic build (`make ALL_STRATEGIES=1`: lib/libssw_hip_all.so) that also carries the
-   superseded strategies of the transform (src/dct2d.rs:83-219) -- levels 1 / 2 of ssw_ctx_set_dct_folding (in-kernel folding)
-   and the f32 twin of the operand-ready GEMMs; 0 for the default library, where those requests run the dense kernels
-   (same results to their precision's bars, slower). */
+/* Always 0; the library has one build.  (Kept for callers of the former diagnostic build, which returned 1.) */
 int ssw_build_all_strategies(void);
 /* Which strategy of the 2-D transform (src/dct2d.rs:83-219) a batch of n_frames frames of w x h takes in the canonical (f64)
    precision under the context's current settings, as flags -- introspection for bench.py, DESIGN.md and the tests; every
@@ -184,25 +181,22 @@ int ssw_ctx_get_prune_stats(ssw_ctx* ctx, uint64_t* stats);
    the device. */
 int ssw_ctx_get_select_stats(ssw_ctx* ctx, uint64_t* stats);
 
-/* Even/odd folding of the basis GEMMs (fewer multiply-adds for the same transform; exact in f64,
-   one extra rounding per input pair in f32) where the frame shape allows (W % 8 == 0 / H % 8 == 0).
-   Strategy levels:
+/* Even/odd folding of the basis GEMMs (fewer multiply-adds for the same transform, exact in f64) where the frame shape
+   allows (W % 8 == 0 / H % 8 == 0).  Folding runs in SSW_PRECISION_F64 only.  Strategy levels:
      0  dense GEMMs
-     1  one folding level inside the GEMM kernel (1/2 of the dense MACs)
-     2  same as 1 (the in-kernel second level of round 1 was superseded by level 4 and removed)
+     1  dense GEMMs (the in-kernel folding of round 1 was superseded by level 3 and removed)
+     2  same as 1
      3  "operand-ready" GEMMs -- HBM-bound pre-passes write the folded operands once per pass as
-        k-blocked planes in the GEMM's precision and the MFMA loop issues no VALU instruction
-        (csrc/dct_pair_f64.hip, dct_pair_f32.hip, dct_pair_prep.hip); one level
+        k-blocked f64 planes and the MFMA loop issues no VALU instruction
+        (csrc/dct_pair_f64.hip, dct_pair_prep.hip); one level
      4  level 3 with the even half folded once more on row passes with W % 16 == 0 and column
         passes with H % 8 == 0 (3/8 of the dense MACs on that axis)
      5  default.  Level 4 plus a third folding level on forward row passes of at least 3072 columns
         (a multiple of 32): 11/32 of the dense MACs there
      6  level 5 without the size threshold (shorter rows lose more to the extra small launches than
         they save; for tests)
-   In f64 all levels produce the same f64-accurate result rounded once to f32; in f32 each folding
-   level adds one rounding per operand sum (tests/test_gpu_parity.py holds both to their bars).
-   The default library carries levels 0 and 3 .. 6 in f64; levels 1 / 2 and every folded level in SSW_PRECISION_F32 are
-   part of the diagnostic build only (ssw_build_all_strategies) and run dense otherwise. */
+   All levels produce the same f64-accurate result rounded once to f32 (tests/test_gpu_parity.py).  Levels 1 / 2, and
+   every level in SSW_PRECISION_F32, run the dense GEMMs. */
 #define SSW_DCT_FOLDING_DEFAULT 5
 int ssw_ctx_set_dct_folding(ssw_ctx* ctx, int level);
 /* f64 precision, folding level 4 and up: the odd half of a folded transform (a DCT-IV of half the length, the one part

@@ -147,7 +147,7 @@ def load() -> C.CDLL:
 
 
 def all_strategies() -> bool:
-    """True when the loaded library is the diagnostic build with every transform strategy (make ALL_STRATEGIES=1)."""
+    """Always False: the library has one build (ssw_build_all_strategies, include/ssw.h)."""
     return bool(load().ssw_build_all_strategies())
 
 

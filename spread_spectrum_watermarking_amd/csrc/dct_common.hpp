@@ -1,4 +1,4 @@
-// Device helpers shared by the dense (dct.hip) and even/odd-folded (dct_folded.hip) basis GEMMs.
+// Device helpers shared by the dense basis GEMMs (dct.hip) and the operand-ready path (dct_pair_common.hpp).
 #pragma once
 #include "ssw_internal.hpp"
 

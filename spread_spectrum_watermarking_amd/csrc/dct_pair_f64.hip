@@ -3,8 +3,8 @@
 // Measured on MI355X (tools/mfma_peak.hip): v_mfma_f64_16x16x4_f64 sustains 77.6 TFLOP/s when the
 // wave issues nothing else, but every VALU instruction issued next to it takes MFMA pipe time --
 // ~6 cycles for a 32-bit op, ~11.5 cycles for v_cvt_f64_f32 / v_add_f64 -- even from another wave
-// of the same SIMD.  The in-kernel folding of dct_folded_f64.hip spends one f64 VALU op per MFMA
-// (widen + add/subtract after the LDS read) and tops out at 81 % of peak for that reason.
+// of the same SIMD.  Folding inside the GEMM kernel (r1, retired; HISTORY) spent one f64 VALU op per
+// MFMA (widen + add/subtract after the LDS read) and topped out at 81 % of peak for that reason.
 //
 // Here the GEMM main loop contains no VALU instruction at all: global_load -> ds_write ->
 // ds_read -> MFMA, with scalar address arithmetic.  Its operands are produced once per pass by
@@ -17,7 +17,7 @@
 // are cached in the same layout.  For the column pass the pre-pass also transposes, so that one
 // "NT" kernel serves all four passes:
 //   acc1[x][y] = sum_k X1[x][k] Y1[y][k],   acc2[x][y] = sum_k X2[x][k] Y2[y][k]
-// with X = image operand (lines), Y = half basis (pairs).  Epilogues as in dct_folded_f64.hip:
+// with X = image operand (lines), Y = half basis (pairs).  Epilogues:
 // forward interleaves (even, odd) frequencies; inverse forms acc1 +/- acc2 for the mirrored
 // positions; results are rounded once to f32 (then the reference's f32 scale factor, if any).
 //
@@ -106,7 +106,7 @@ int pair_class_args(const PairClassDesc& d, bool is_row, bool inverse, size_t le
     if (split && leff % 8 != 0) return SSW_ERR_BAD_ARG;
     ca.x1 = d.x1; ca.x2 = d.x2; ca.y1 = d.y1; ca.y2 = d.y2;
     ca.NP = (unsigned)(kind == 0 ? leff / 2 : split ? leff / 8 : leff / 4);      // class E: n/8 + 1 pairs in n/8 slots (fold0)
-    ca.Kp = (unsigned)(split ? pair_kpad<double>(leff / 4) : kind == 1 ? pair_kpad<double>(leff / 2) : pair_kpad<double>(leff));
+    ca.Kp = (unsigned)(split ? pair_kpad(leff / 4) : kind == 1 ? pair_kpad(leff / 2) : pair_kpad(leff));
     ca.yrows = kind == 2 ? 2 * ca.NP : eshape ? ca.NP + 1 : ca.NP;      // lines of the basis plane(s): class E's keep row n/8
 #ifdef SSW_ABL_NP128        // timing-only ablation: the 135-pair column classes without their 7-pair tail tile
     if (!is_row && ca.NP == 135) ca.NP = 128;
@@ -209,7 +209,7 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     // column operands; the column launches (fuse set, cop null) read their tiles in the row launches' class-major order
     const bool fuse_rows = fuse && fuse->mode == FUSE_ROWS_COP, fuse_cols = fuse && fuse->mode == FUSE_COLS;
     if (fuse && (!(fuse_rows || fuse_cols) || fuse_rows != is_row || inverse || w % 128 != 0 || h % 16 != 0 ||
-                 pair_kpad<double>(h / 8) != dct_pair_fused_units(h))) return SSW_ERR_BAD_ARG;
+                 pair_kpad(h / 8) != dct_pair_fused_units(h))) return SSW_ERR_BAD_ARG;
     if (fuse_rows && (!lay.class_major || sink || !fuse->cop || !fuse->rot1 || !fuse->rot2 || !fuse->rot3)) return SSW_ERR_BAD_ARG;
     const size_t lines = fuse_rows ? n_frames * 16 * dct_pair_fused_units(h) : is_row ? n_frames * h : n_frames * w;
     const size_t len = is_row ? w : h;
@@ -260,7 +260,7 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     if (lay.class_major && !inverse) po.ft = lay.tile;
     if (fuse_rows) {
         if (inst.samex || inst.epi != EPI_FWD || po.ft != 128) return SSW_ERR_BAD_ARG;
-        po.cop = fuse->cop; po.cop_k16 = (unsigned)pair_kpad<double>(h / 8); po.cop_lines = (unsigned)(n_frames * w);
+        po.cop = fuse->cop; po.cop_k16 = (unsigned)pair_kpad(h / 8); po.cop_lines = (unsigned)(n_frames * w);
         po.cop_hup = (unsigned)dct_pair_fused_units(h);
         po.crot1 = fuse->rot1; po.crot2 = fuse->rot2; po.crot3 = fuse->rot3;
         inst.epi = EPI_FWD_COLOP;

@@ -6,8 +6,8 @@
 // Measured on MI355X (tools/mfma_peak.hip): v_mfma_f64_16x16x4_f64 sustains 77.6 TFLOP/s when the
 // wave issues nothing else, but every VALU instruction issued next to it takes MFMA pipe time --
 // ~6 cycles for a 32-bit op, ~11.5 cycles for v_cvt_f64_f32 / v_add_f64 -- even from another wave
-// of the same SIMD.  The in-kernel folding of dct_folded_f64.hip spends one f64 VALU op per MFMA
-// (widen + add/subtract after the LDS read) and tops out at 81 % of peak for that reason.
+// of the same SIMD.  Folding inside the GEMM kernel (r1, retired; HISTORY) spent one f64 VALU op per
+// MFMA (widen + add/subtract after the LDS read) and topped out at 81 % of peak for that reason.
 //
 // Here the GEMM main loop contains no VALU instruction at all: global_load -> ds_write ->
 // ds_read -> MFMA, with scalar address arithmetic.  Its operands are produced once per pass by
@@ -20,7 +20,7 @@
 // are cached in the same layout.  For the column pass the pre-pass also transposes, so that one
 // "NT" kernel serves all four passes:
 //   acc1[x][y] = sum_k X1[x][k] Y1[y][k],   acc2[x][y] = sum_k X2[x][k] Y2[y][k]
-// with X = image operand (lines), Y = half basis (pairs).  Epilogues as in dct_folded_f64.hip:
+// with X = image operand (lines), Y = half basis (pairs).  Epilogues:
 // forward interleaves (even, odd) frequencies; inverse forms acc1 +/- acc2 for the mirrored
 // positions; results are rounded once to f32 (then the reference's f32 scale factor, if any).
 //

@@ -1,7 +1,7 @@
-// HBM-bound pre-passes of the operand-ready GEMMs (dct_pair_f64.hip / dct_pair_f32.hip): they write
-// the image operand of a pass once, already folded (forward) or split (inverse), in the precision the
-// MFMA consumes (T = double: every sum exact; T = float: one rounding per sum) and in the k-blocked
-// layout (dct_pair_common.hpp).  Also the half bases in that layout.
+// HBM-bound pre-passes of the operand-ready GEMMs (dct_pair_f64.hip): they write
+// the image operand of a pass once, already folded (forward) or split (inverse), in f64 (every sum exact) and in the
+// k-blocked layout (dct_pair_common.hpp).  Also the half bases in that layout.  The kernels are templates of the element
+// type T; only T = double is instantiated.
 #include "dct_pair_split.hpp"
 #include "dct_pair_colops.hpp"
 #include "dct_pair_yiq_load.hpp"
@@ -11,7 +11,8 @@
 namespace ssw {
 
 // ---------------------------------------------------------------------------------------------
-// Half bases in the k-blocked layout: [Kp / 8][n / 2][8], same values as make_half_basis_f64_kernel.
+// Half bases in the k-blocked layout: [Kp / 8][n / 2][8]; row o of parity p holds basis frequency 2 o + p (forward) or the
+// inverse's entries of frequencies 2 s + p, zero beyond n / 2.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void make_half_basis_blocked_kernel(size_t n, bool inverse, int parity, size_t kpad, T* out) {
@@ -31,13 +32,12 @@ __global__ void make_half_basis_blocked_kernel(size_t n, bool inverse, int parit
     }
 }
 
-size_t dct_pair_kpad(bool f64, size_t n) { return f64 ? pair_kpad<double>(n) : pair_kpad<float>(n); }
+size_t dct_pair_kpad(size_t n) { return pair_kpad(n); }
 
-int launch_make_half_basis_blocked(hipStream_t st, bool f64, size_t n, bool inverse, int parity, void* out) {
-    const size_t kp = dct_pair_kpad(f64, n), total = (n / 2) * kp;
+int launch_make_half_basis_blocked(hipStream_t st, size_t n, bool inverse, int parity, double* out) {
+    const size_t kp = pair_kpad(n), total = (n / 2) * kp;
     const unsigned blocks = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    if (f64) make_half_basis_blocked_kernel<double><<<blocks ? blocks : 1, 256, 0, st>>>(n, inverse, parity, kp, (double*)out);
-    else     make_half_basis_blocked_kernel<float><<<blocks ? blocks : 1, 256, 0, st>>>(n, inverse, parity, kp, (float*)out);
+    make_half_basis_blocked_kernel<double><<<blocks ? blocks : 1, 256, 0, st>>>(n, inverse, parity, kp, out);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
@@ -86,7 +86,7 @@ __global__ void make_rot_table_kernel(size_t n, double* out) {
     }
 }
 
-size_t dct_pair_split_kpad(size_t len) { return pair_kpad<double>(len / 4); }
+size_t dct_pair_split_kpad(size_t len) { return pair_kpad(len / 4); }
 // doubles in the four split planes of a pass over n frames (the larger of the row and the column pass)
 size_t dct_pair_split_elems(size_t n_frames, size_t w, size_t h) {
     const size_t a = n_frames * h * dct_pair_split_kpad(w), b = n_frames * w * dct_pair_split_kpad(h);
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void pair_prep_cols_kernel(const float* __rest
 //   forward, q < n/4:  S[q] = x[q] + x[n-1-q],  S' = x[n/2-1-q] + x[n/2+q];  SS = S + S',  SD = S - S'
 //                      D[q] = x[q] - x[n-1-q],  D[n/2-1-q] = x[n/2-1-q] - x[n/2+q]
 //   inverse, q < n/4:  EE[q] = c[4q],  EO[q] = c[4q+2],  O[2q] = c[4q+1],  O[2q+1] = c[4q+3]
-// Q1, Q2: kq = half_basis_kpad(n/2) wide; P: kp = half_basis_kpad(n) wide; k-blocked, zero padded.
+// Q1, Q2: kq = pair_kpad(n/2) wide; P: kp = pair_kpad(n) wide; k-blocked, zero padded.
 // ---------------------------------------------------------------------------------------------
 template <typename T, bool INVERSE>
 __global__ __launch_bounds__(256) void pair_prep4_rows_kernel(const float* __restrict__ X, T* __restrict__ Q1,
@@ -1108,83 +1108,70 @@ __global__ __launch_bounds__(256) void pair_prep16_inv_cols_kernel(const float* 
 // ---------------------------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------------------------
-size_t dct_pair_operand_elems(bool f64, size_t n_frames, size_t w, size_t h) {
-    const size_t a = n_frames * h * dct_pair_kpad(f64, w), b = n_frames * w * dct_pair_kpad(f64, h);
+size_t dct_pair_operand_elems(size_t n_frames, size_t w, size_t h) {
+    const size_t a = n_frames * h * pair_kpad(w), b = n_frames * w * pair_kpad(h);
     return a > b ? a : b;
 }
 
-template <typename T>
-static int prep_impl(hipStream_t st, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w, size_t h,
-                     T* o1, T* o2) {
+int launch_dct_pair_prep(hipStream_t st, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w, size_t h,
+                         double* o1, double* o2) {
     if (n_frames == 0) return SSW_OK;
     if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
     if (is_row) {
-        const unsigned Kp = (unsigned)pair_kpad<T>(w), tiles_k = (Kp + 31) / 32;
+        const unsigned Kp = (unsigned)pair_kpad(w), tiles_k = (Kp + 31) / 32;
         const size_t rows = n_frames * h;
         const unsigned long long nblk = (unsigned long long)((rows + 31) / 32) * tiles_k;
         if (rows > 0xFFFFFFFFull || nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-        if (inverse) pair_prep_rows_kernel<T, true><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)rows, (unsigned)w, Kp, tiles_k);
-        else         pair_prep_rows_kernel<T, false><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)rows, (unsigned)w, Kp, tiles_k);
+        if (inverse) pair_prep_rows_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)rows, (unsigned)w, Kp, tiles_k);
+        else         pair_prep_rows_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)rows, (unsigned)w, Kp, tiles_k);
     } else {
-        const unsigned Kp = (unsigned)pair_kpad<T>(h);
+        const unsigned Kp = (unsigned)pair_kpad(h);
         const unsigned tiles_k = (Kp + 31) / 32, tiles_c = (unsigned)((w + 63) / 64);
         const unsigned long long nblk = (unsigned long long)tiles_k * tiles_c * n_frames;
         if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-        if (inverse) pair_prep_cols_kernel<T, true><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)w, (unsigned)h, Kp, (unsigned)n_frames, tiles_k, tiles_c);
-        else         pair_prep_cols_kernel<T, false><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)w, (unsigned)h, Kp, (unsigned)n_frames, tiles_k, tiles_c);
+        if (inverse) pair_prep_cols_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)w, (unsigned)h, Kp, (unsigned)n_frames, tiles_k, tiles_c);
+        else         pair_prep_cols_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)w, (unsigned)h, Kp, (unsigned)n_frames, tiles_k, tiles_c);
     }
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
 
-template <typename T>
-static int prep4_impl(hipStream_t st, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w, size_t h,
-                      T* q1, T* q2, T* p) {
+int launch_dct_pair_prep4(hipStream_t st, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w, size_t h,
+                          double* q1, double* q2, double* p) {
     if (n_frames == 0) return SSW_OK;
     if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
     const size_t len = is_row ? w : h;
-    const unsigned Kp = (unsigned)pair_kpad<T>(len), Kq = (unsigned)pair_kpad<T>(len / 2);
+    const unsigned Kp = (unsigned)pair_kpad(len), Kq = (unsigned)pair_kpad(len / 2);
     const unsigned tiles_q = (Kq + 31) / 32;
     if (is_row) {
         const size_t rows = n_frames * h;
         const unsigned long long nblk = (unsigned long long)((rows + 31) / 32) * tiles_q;
         if (rows > 0xFFFFFFFFull || nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-        if (inverse) pair_prep4_rows_kernel<T, true><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)rows, (unsigned)w, Kq, Kp, tiles_q);
-        else         pair_prep4_rows_kernel<T, false><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)rows, (unsigned)w, Kq, Kp, tiles_q);
+        if (inverse) pair_prep4_rows_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)rows, (unsigned)w, Kq, Kp, tiles_q);
+        else         pair_prep4_rows_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)rows, (unsigned)w, Kq, Kp, tiles_q);
     } else {
         const unsigned tiles_c = (unsigned)((w + 31) / 32);
         const unsigned long long nblk = (unsigned long long)tiles_q * tiles_c * n_frames;
         if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-        if (inverse) pair_prep4_cols_kernel<T, true><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)w, (unsigned)h, Kq, Kp, (unsigned)n_frames, tiles_q, tiles_c);
-        else         pair_prep4_cols_kernel<T, false><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)w, (unsigned)h, Kq, Kp, (unsigned)n_frames, tiles_q, tiles_c);
+        if (inverse) pair_prep4_cols_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)w, (unsigned)h, Kq, Kp, (unsigned)n_frames, tiles_q, tiles_c);
+        else         pair_prep4_cols_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)w, (unsigned)h, Kq, Kp, (unsigned)n_frames, tiles_q, tiles_c);
     }
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
 
-int launch_dct_pair_prep(hipStream_t st, bool f64, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w,
-                         size_t h, void* o1, void* o2) {
-    return f64 ? prep_impl<double>(st, is_row, inverse, in, n_frames, w, h, (double*)o1, (double*)o2)
-               : prep_impl<float>(st, is_row, inverse, in, n_frames, w, h, (float*)o1, (float*)o2);
-}
-
-int launch_dct_pair_prep4(hipStream_t st, bool f64, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w,
-                          size_t h, void* q1, void* q2, void* p) {
-    return f64 ? prep4_impl<double>(st, is_row, inverse, in, n_frames, w, h, (double*)q1, (double*)q2, (double*)p)
-               : prep4_impl<float>(st, is_row, inverse, in, n_frames, w, h, (float*)q1, (float*)q2, (float*)p);
-}
-
-template <typename T>
-static int prep4_rgb_impl(hipStream_t st, int u8, const void* rgb, size_t n_frames, size_t w, size_t h,
-                          T* q1, T* q2, T* p, float* ip, float* qp) {
+// rows-first forward transform with two folding levels on the row axis: the first pre-pass straight
+// from the interleaved RGB frames (u8 or f32); ip / qp (both or neither) receive the I and Q planes.
+int launch_dct_pair_prep4_rows_rgb(hipStream_t st, int u8, const void* rgb, size_t n_frames, size_t w, size_t h,
+                                   double* q1, double* q2, double* p, float* ip, float* qp) {
     if (n_frames == 0) return SSW_OK;
     if (w > 0xFFFFFFull || h > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const unsigned Kp = (unsigned)pair_kpad<T>(w), Kq = (unsigned)pair_kpad<T>(w / 2), tiles_q = (Kq + 31) / 32;
+    const unsigned Kp = (unsigned)pair_kpad(w), Kq = (unsigned)pair_kpad(w / 2), tiles_q = (Kq + 31) / 32;
     const size_t rows = n_frames * h;
     const unsigned long long nblk = (unsigned long long)((rows + 31) / 32) * tiles_q;
     if (rows > 0xFFFFFFFFull || nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
     const bool iq = ip && qp;
-#define SSW_PREP_RGB(U8V, IQV) pair_prep4_rows_rgb_kernel<T, U8V, IQV><<<(unsigned)nblk, 256, 0, st>>>( \
+#define SSW_PREP_RGB(U8V, IQV) pair_prep4_rows_rgb_kernel<double, U8V, IQV><<<(unsigned)nblk, 256, 0, st>>>( \
         rgb, q1, q2, p, ip, qp, (unsigned)rows, (unsigned)w, Kq, Kp, tiles_q)
     if (u8 == SSW_PIX_U8)       { if (iq) SSW_PREP_RGB(SSW_PIX_U8, true); else SSW_PREP_RGB(SSW_PIX_U8, false); }
     else if (u8 == SSW_PIX_U16) { if (iq) SSW_PREP_RGB(SSW_PIX_U16, true); else SSW_PREP_RGB(SSW_PIX_U16, false); }
@@ -1194,26 +1181,19 @@ static int prep4_rgb_impl(hipStream_t st, int u8, const void* rgb, size_t n_fram
     return SSW_OK;
 }
 
-// rows-first forward transform with two folding levels on the row axis: the first pre-pass straight
-// from the interleaved RGB frames (u8 or f32); ip / qp (both or neither) receive the I and Q planes.
-int launch_dct_pair_prep4_rows_rgb(hipStream_t st, bool f64, int u8, const void* rgb, size_t n_frames, size_t w, size_t h,
-                                   void* q1, void* q2, void* p, float* ip, float* qp) {
-    return f64 ? prep4_rgb_impl<double>(st, u8, rgb, n_frames, w, h, (double*)q1, (double*)q2, (double*)p, ip, qp)
-               : prep4_rgb_impl<float>(st, u8, rgb, n_frames, w, h, (float*)q1, (float*)q2, (float*)p, ip, qp);
-}
-
-template <typename T>
-static int prep8_impl(hipStream_t st, int src_kind, const void* src, size_t n_frames, size_t w, size_t h,
-                      T* r1, T* r2, T* m, T* p, float* ip, float* qp) {
+// third folding level along an axis of length len (forward row passes only)
+// src_kind: 0 = f32 plane, 1 = interleaved RGB f32, 2 = interleaved RGB u8 (ip / qp: I, Q planes out or null)
+int launch_dct_pair_prep8_rows(hipStream_t st, int src_kind, const void* src, size_t n_frames, size_t w, size_t h,
+                               double* r1, double* r2, double* m, double* p, float* ip, float* qp) {
     if (n_frames == 0) return SSW_OK;
     if (w > 0xFFFFFFull || h > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const unsigned Kp = (unsigned)pair_kpad<T>(w), Kq = (unsigned)pair_kpad<T>(w / 2), K8 = (unsigned)pair_kpad<T>(w / 4);
+    const unsigned Kp = (unsigned)pair_kpad(w), Kq = (unsigned)pair_kpad(w / 2), K8 = (unsigned)pair_kpad(w / 4);
     const unsigned tiles_e = (K8 + 31) / 32;
     const size_t rows = n_frames * h;
     const unsigned long long nblk = (unsigned long long)((rows + 31) / 32) * tiles_e;
     if (rows > 0xFFFFFFFFull || nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
     const bool iq = ip && qp;
-#define SSW_PREP8(SRCV, IQV) pair_prep8_rows_kernel<T, SRCV, IQV><<<(unsigned)nblk, 256, 0, st>>>( \
+#define SSW_PREP8(SRCV, IQV) pair_prep8_rows_kernel<double, SRCV, IQV><<<(unsigned)nblk, 256, 0, st>>>( \
         src, r1, r2, m, p, ip, qp, (unsigned)rows, (unsigned)w, K8, Kq, Kp, tiles_e)
     if (src_kind == 0) SSW_PREP8(0, false);
     else if (src_kind == 1) { if (iq) SSW_PREP8(1, true); else SSW_PREP8(1, false); }
@@ -1224,32 +1204,18 @@ static int prep8_impl(hipStream_t st, int src_kind, const void* src, size_t n_fr
     return SSW_OK;
 }
 
-// third folding level along an axis of length len (forward row passes only)
-// src_kind: 0 = f32 plane, 1 = interleaved RGB f32, 2 = interleaved RGB u8 (ip / qp: I, Q planes out or null)
-int launch_dct_pair_prep8_rows(hipStream_t st, bool f64, int src_kind, const void* src, size_t n_frames, size_t w, size_t h,
-                               void* r1, void* r2, void* m, void* p, float* ip, float* qp) {
-    return f64 ? prep8_impl<double>(st, src_kind, src, n_frames, w, h, (double*)r1, (double*)r2, (double*)m, (double*)p, ip, qp)
-               : prep8_impl<float>(st, src_kind, src, n_frames, w, h, (float*)r1, (float*)r2, (float*)m, (float*)p, ip, qp);
-}
-
-template <typename T>
-static int prep8_cols_impl(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, T* r1, T* r2, T* m, T* p) {
+// three levels on a forward column pass (H % 32 == 0): (SSS, SS-) [kpad(h/4) wide], S- [kpad(h/2)], x- [kpad(h)]
+int launch_dct_pair_prep8_cols(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h,
+                               double* r1, double* r2, double* m, double* p) {
     if (n_frames == 0) return SSW_OK;
     if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const unsigned Kp = (unsigned)pair_kpad<T>(h), Kq = (unsigned)pair_kpad<T>(h / 2), K8 = (unsigned)pair_kpad<T>(h / 4);
+    const unsigned Kp = (unsigned)pair_kpad(h), Kq = (unsigned)pair_kpad(h / 2), K8 = (unsigned)pair_kpad(h / 4);
     const unsigned tiles_e = (K8 + 31) / 32, tiles_c = (unsigned)((w + 31) / 32);
     const unsigned long long nblk = (unsigned long long)tiles_e * tiles_c * n_frames;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    pair_prep8_cols_kernel<T><<<(unsigned)nblk, 256, 0, st>>>(in, r1, r2, m, p, (unsigned)w, (unsigned)h, K8, Kq, Kp, (unsigned)n_frames, tiles_e, tiles_c);
+    pair_prep8_cols_kernel<double><<<(unsigned)nblk, 256, 0, st>>>(in, r1, r2, m, p, (unsigned)w, (unsigned)h, K8, Kq, Kp, (unsigned)n_frames, tiles_e, tiles_c);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
-}
-
-// three levels on a forward column pass (H % 32 == 0): (SSS, SS-) [kpad(h/4) wide], S- [kpad(h/2)], x- [kpad(h)]
-int launch_dct_pair_prep8_cols(hipStream_t st, bool f64, const float* in, size_t n_frames, size_t w, size_t h,
-                               void* r1, void* r2, void* m, void* p) {
-    return f64 ? prep8_cols_impl<double>(st, in, n_frames, w, h, (double*)r1, (double*)r2, (double*)m, (double*)p)
-               : prep8_cols_impl<float>(st, in, n_frames, w, h, (float*)r1, (float*)r2, (float*)m, (float*)p);
 }
 
 // deep forward row pre-pass: src_kind 0 = f32 plane, 1 / 2 = interleaved RGB f32 / u8 (ip / qp: I, Q planes out or null);
@@ -1295,7 +1261,7 @@ int launch_dct_pair_prep16_rows(hipStream_t st, int src_kind, const void* src, s
 
 // deep forward column pre-pass (H % 16 == 0): same plane order as the row version, lines = n_frames * w;
 // semi-deep: H % 8 == 0 but not % 16 (1080 rows): D split, SS folded a third time, SD left whole
-size_t dct_pair_semi_deep_elems(size_t lines, size_t len) { return lines * (6 * dct_pair_split_kpad(len) + pair_kpad<double>(len / 2)); }
+size_t dct_pair_semi_deep_elems(size_t lines, size_t len) { return lines * (6 * dct_pair_split_kpad(len) + pair_kpad(len / 2)); }
 int launch_dct_pair_prep16_cols(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
                                 const double* rot1, const double* rot2, const double* rot3, PrepFamily prep, const PairLayout& lay) {
     if (n_frames == 0) return SSW_OK;
@@ -1303,7 +1269,7 @@ int launch_dct_pair_prep16_cols(hipStream_t st, const float* in, size_t n_frames
     if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull || h % 8 != 0 || w % 4 != 0) return SSW_ERR_BAD_DIMS;
     if (semi && class_major && prep == PrepFamily::R3) return SSW_ERR_BAD_ARG;      // the r3 semi-deep kernels read the natural order only
     const unsigned K8 = (unsigned)dct_pair_split_kpad(h);
-    const unsigned K16 = semi ? (unsigned)pair_kpad<double>(h / 2) : (unsigned)dct_pair_split_kpad(h / 2);      // semi: width of the SD plane
+    const unsigned K16 = semi ? (unsigned)pair_kpad(h / 2) : (unsigned)dct_pair_split_kpad(h / 2);      // semi: width of the SD plane
     if (prep == PrepFamily::L2)
         return launch_prep16_cols_l2(st, in, n_frames, w, h, base, rot1, rot2, rot3, class_major, class_major && lay.rows_l2, K16);
     if (prep == PrepFamily::Staged)
@@ -1349,7 +1315,7 @@ int launch_dct_pair_prep16_inv_cols(hipStream_t st, const float* in, size_t n_fr
     if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull || h % 8 != 0) return SSW_ERR_BAD_DIMS;
     if (semi && class_major && prep == PrepFamily::R3) return SSW_ERR_BAD_ARG;      // the r3 semi-deep kernels read the natural order only
     const unsigned K8 = (unsigned)dct_pair_split_kpad(h);
-    const unsigned K16 = semi ? (unsigned)pair_kpad<double>(h / 2) : (unsigned)dct_pair_split_kpad(h / 2);      // semi: width of the c[4q+2] plane
+    const unsigned K16 = semi ? (unsigned)pair_kpad(h / 2) : (unsigned)dct_pair_split_kpad(h / 2);      // semi: width of the c[4q+2] plane
     if (prep == PrepFamily::L2)
         return launch_prep16_inv_cols_l2(st, in, n_frames, w, h, base, rot1, rot2, rot3, class_major, class_major && lay.rows_l2, K16);
     if (prep == PrepFamily::Staged)

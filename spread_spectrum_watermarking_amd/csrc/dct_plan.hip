@@ -63,7 +63,7 @@ bool can_fuse_cols(const PlanTuning& t, size_t n_frames, size_t w, size_t h) {
     if (!t.fuse_cols || n_frames == 0 || w < h || w % 128 != 0 || h % 16 != 0 || class_tile_of(t, w) != 128) return false;
     if (!efold(t, w) || !efold_cols(t, h, w, true) || !can_split(h) || !can_fold2_cols(h)) return false;
     const size_t hup = dct_pair_fused_units(h);
-    if (pair_kpad<double>(h / 8) != hup) return false;
+    if (pair_kpad(h / 8) != hup) return false;
     if (n_frames * 16 * hup > 0xFFFFFFFFull || n_frames * w > 0xFFFFFFFFull) return false;      // 32-bit line indices in both passes
     return !launch_is_small(t, n_frames * 16 * hup, w / 16) && !launch_is_small(t, n_frames * w, h / 16);
 }
@@ -77,17 +77,13 @@ PassPlan plan_pass_t(const PlanTuning& t, const PlanInput& in, bool first_pass, 
     p.layout.rows_l2 = inverse ? efold_inv(t, w) : efold(t, w);
     p.layout.tile = class_tile_of(t, w);
     const bool can_fold = s.fold && (is_row ? rows_can_fold(w, in.aligned) : cols_can_fold(w, h, in.aligned));
-    if (!(can_fold && s.fold_level >= 3 && dct_pair_can_run(f64, n, w, h, in.aligned))) {
-        // (default build: the in-kernel folding of dct_folded*.hip is not compiled in -- what the pair path does not take runs dense)
-        p.strategy = can_fold && build_all_strategies() ? PassStrategy::Folded : PassStrategy::Dense;
-        return p;
-    }
+    if (!(can_fold && s.fold_level >= 3 && f64 && dct_pair_can_run(n, w, h, in.aligned))) return p;        // Dense
     const bool two = s.fold_level >= 4 && (is_row ? can_fold2(len) : can_fold2_cols(len));
     // a third level pays once the sums are long enough (4K: +1.6 %, 1080p: -3 %); level 6 forces it
     const bool three = two && !inverse && can_fold3(len) && (s.fold_level >= 6 || (s.fold_level == 5 && len >= 3072));
     p.levels = three ? 3 : two ? 2 : 1;
-    // the odd half as a rotated pair of quarter-length cosine / sine transforms (f64): a quarter of its multiply-adds
-    p.split = two && f64 && s.split && can_split(len);
+    // the odd half as a rotated pair of quarter-length cosine / sine transforms: a quarter of its multiply-adds
+    p.split = two && s.split && can_split(len);
     // rows first, both passes deep: the row pass writes the plane between the passes class-major, the column pre-pass reads it
     const size_t fh = in.full_h ? in.full_h : h;
     const bool cm = !in.natural_order && w >= fh && w % 4 == 0 && (inverse ? deep_inv_rows(t, w) : deep_rows(t, w)) &&
@@ -152,11 +148,10 @@ bool plan_derived_fused(const PassPlan& rows, size_t lines) {
     return t.derived_fused && plan_is_level2(rows) && lines > t.merge_max_lines;
 }
 
-bool dct_pair_can_run(bool f64, size_t n_frames, size_t w, size_t h, bool aligned) {
-    if (!f64 && !build_all_strategies()) return false;          // the f32 twin (dct_pair_f32.hip) is part of the diagnostic build only
+bool dct_pair_can_run(size_t n_frames, size_t w, size_t h, bool aligned) {
     // an operand plane must stay below 4 GB (32-bit scalar offsets walk its k-blocks)
     return rows_can_fold(w, aligned) && cols_can_fold(w, h, aligned) && w % 8 == 0 && h % 8 == 0 &&
-           dct_pair_operand_elems(f64, n_frames, w, h) * (f64 ? 8 : 4) <= 0xFFFFFFFFull;
+           dct_pair_operand_elems(n_frames, w, h) * sizeof(double) <= 0xFFFFFFFFull;
 }
 
 bool dct_pair_can_prep_from_rgb(size_t w, size_t h, const void* rgb, int u8) {
@@ -164,7 +159,11 @@ bool dct_pair_can_prep_from_rgb(size_t w, size_t h, const void* rgb, int u8) {
 }
 
 size_t plan_frame_limit(const PlanSettings& s, bool f64, size_t w, size_t h) {
-    const size_t per_frame = dct_pair_operand_elems(f64, 1, w, h) * (f64 ? sizeof(double) : sizeof(float));
+    // Dense f32 group size: SSW_PRECISION_F32 has no operand planes (it runs dense), but its frames keep the groups the planes of
+    // a retired f32 pair path set (k-steps of 16 floats, an even number of them), so that its dense launches stay as they were.
+    auto f32_kpad = [](size_t len) { return (len / 2 + 31) / 32 * 32; };
+    const size_t per_frame = f64 ? dct_pair_operand_elems(1, w, h) * sizeof(double)
+                                 : std::max(h * f32_kpad(w), w * f32_kpad(h)) * sizeof(float);
     const size_t m = per_frame && s.fold && s.fold_level >= 3 ? 0xFFFFFFFFull / per_frame : 0;
     return m >= 1 ? m : ~(size_t)0;
 }

@@ -8,10 +8,11 @@
 
 namespace ssw {
 
-// Dense / Folded (in-kernel, diagnostic build) GEMMs; the operand-ready pair path at one, two or three folding levels; deep
-// pre-passes (one pre-pass for all launches, level 1 or level 2 = every launch sums len/16 terms); FusedRows / FusedCols (r5:
-// the row epilogue writes the column operands); SemiDeep(Inv) (columns of 8- but not 16-divisible length); DeepInv(L2).
-enum class PassStrategy { Dense, Folded, PairL1, PairTwo, PairThree, Deep, DeepL2, FusedRows, FusedCols, SemiDeep, SemiDeepInv,
+// Dense GEMMs (dct.hip: every shape the pair path does not take, and SSW_PRECISION_F32); the f64 operand-ready pair path at
+// one, two or three folding levels; deep pre-passes (one pre-pass for all launches, level 1 or level 2 = every launch sums
+// len/16 terms); FusedRows / FusedCols (r5: the row epilogue writes the column operands); SemiDeep(Inv) (columns of 8- but
+// not 16-divisible length); DeepInv(L2).
+enum class PassStrategy { Dense, PairL1, PairTwo, PairThree, Deep, DeepL2, FusedRows, FusedCols, SemiDeep, SemiDeepInv,
                           DeepInv, DeepInvL2 };
 enum class PrepFamily { None, R3, Staged, L2 };      // kernels of a deep / semi-deep column or deep inverse row pre-pass
 constexpr unsigned PREP_STAGED_TILE = 128;           // the LDS-staged pre-passes read class-major tiles of this many columns
@@ -50,10 +51,10 @@ bool plan_is_level2(const PassPlan& p);                      // DeepL2, FusedRow
 bool plan_is_deep(const PassPlan& p);                        // those, Deep and DeepInv
 bool plan_merge(size_t lines);                               // the merge rule (merge_max_lines)
 bool plan_derived_fused(const PassPlan& rows, size_t lines); // the pruned derived pass in one kernel (derived_fused)
-// the pair path fits the shape: folding shapes, aligned planes, operand planes below 4 GB
-bool dct_pair_can_run(bool f64, size_t n_frames, size_t w, size_t h, bool aligned);
+// the (f64) pair path fits the shape: folding shapes, aligned planes, operand planes below 4 GB
+bool dct_pair_can_run(size_t n_frames, size_t w, size_t h, bool aligned);
 bool dct_pair_can_prep_from_rgb(size_t w, size_t h, const void* rgb, int u8);       // a rows-first RGB pre-pass reads these frames
-size_t plan_frame_limit(const PlanSettings& s, bool f64, size_t w, size_t h);      // frames per group (32-bit operand offsets)
+size_t plan_frame_limit(const PlanSettings& s, bool f64, size_t w, size_t h);      // frames per group (f64: 32-bit operand offsets)
 // doubles of a lane's sixth operand buffer: what the passes of both directions of this shape use (they share the lane)
 size_t split_scratch_elems(size_t n, size_t w, size_t h);
 

@@ -62,37 +62,18 @@ int launch_dct_rows(hipStream_t st, int precision, const float* in, float* out, 
 int launch_dct_cols(hipStream_t st, int precision, const float* in, float* out, size_t n_frames,
                     size_t w, size_t h, const void* basis, Epilogue ep);
 
-// dct_folded.hip: even/odd-folded f32 GEMMs (half the multiply-adds); see the file header.
+// dct_pair_prep.hip / dct_pair_f64.hip: "operand-ready" folded GEMMs in f64 (no VALU work in the MFMA loop): pre-passes
+// write the folded operands once per pass as k-blocked f64 planes, the half bases are cached in the same layout.
 // Half bases: (N/2)x(N/2), layout [out][sum], parity 0 = even frequencies, 1 = odd.
-size_t half_basis_kpad(size_t n);   // row stride of a half basis: N/2 rounded up to the k-step, zero padded
-int launch_make_half_basis_f32(hipStream_t st, size_t n, bool inverse, int parity, float* out);
-// false in the default build: in-kernel folding (dct_folded*.hip) and the f32 operand-ready twin (dct_pair_f32.hip) are not
-// compiled in (dct_strategies_off.hip); `make ALL_STRATEGIES=1` builds the diagnostic library with every strategy
-bool build_all_strategies();
-int launch_dct_rows_folded_f32(hipStream_t st, bool inverse, const float* in, float* out, size_t rows,
-                               size_t w, const float* b_even, const float* b_odd, Epilogue ep);
-int launch_dct_cols_folded_f32(hipStream_t st, bool inverse, const float* in, float* out, size_t n_frames,
-                               size_t w, size_t h, const float* b_even, const float* b_odd, Epilogue ep);
-
-// dct_folded_f64.hip: the same folding in f64 (canonical precision), f64 half bases.
-int launch_make_half_basis_f64(hipStream_t st, size_t n, bool inverse, int parity, double* out);
-int launch_dct_rows_folded_f64(hipStream_t st, bool inverse, const float* in, float* out, size_t rows,
-                               size_t w, const double* b_even, const double* b_odd, Epilogue ep);
-int launch_dct_cols_folded_f64(hipStream_t st, bool inverse, const float* in, float* out, size_t n_frames,
-                               size_t w, size_t h, const double* b_even, const double* b_odd, Epilogue ep);
-
-// dct_pair_prep.hip / dct_pair_f64.hip / dct_pair_f32.hip: "operand-ready" folded GEMMs (no VALU work in
-// the MFMA loop): pre-passes write the folded operands once per pass as k-blocked planes in the GEMM's
-// precision (f64 flag), the half bases are cached in the same layout.
-size_t dct_pair_kpad(bool f64, size_t n);                               // row stride of operands / bases of a length-n axis
-size_t dct_pair_operand_elems(bool f64, size_t n_frames, size_t w, size_t h);   // elements per operand plane
-int launch_make_half_basis_blocked(hipStream_t st, bool f64, size_t n, bool inverse, int parity, void* out);
+size_t dct_pair_kpad(size_t n);                                         // row stride of operands / bases of a length-n axis
+size_t dct_pair_operand_elems(size_t n_frames, size_t w, size_t h);     // elements per operand plane
+int launch_make_half_basis_blocked(hipStream_t st, size_t n, bool inverse, int parity, double* out);
 // one level: (S, D) forward / (E, O) inverse
-int launch_dct_pair_prep(hipStream_t st, bool f64, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w,
-                         size_t h, void* o1, void* o2);
+int launch_dct_pair_prep(hipStream_t st, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w, size_t h,
+                         double* o1, double* o2);
 // two levels: (SS, SD | EE, EO) [kpad(len/2) wide] and (D | O) [kpad(len) wide] in one sweep
-int launch_dct_pair_prep4(hipStream_t st, bool f64, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w,
-                          size_t h, void* q1, void* q2, void* p);
+int launch_dct_pair_prep4(hipStream_t st, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w, size_t h,
+                          double* q1, double* q2, double* p);
 // first pass of a rows-first forward transform straight from interleaved RGB (u8 or f32), two levels;
 // ip / qp: I and Q planes out (both or neither)
 // Sample format of an interleaved RGB frame at the boundary (`u8` parameters below): what `into_rgb32f()` accepts
@@ -101,12 +82,12 @@ enum { SSW_PIX_F32 = 0, SSW_PIX_U8 = 1, SSW_PIX_U16 = 2 };
 inline size_t pix_bytes(int fmt) { return fmt == SSW_PIX_U8 ? 1 : fmt == SSW_PIX_U16 ? 2 : 4; }          // per sample
 inline unsigned pix_align_mask(int fmt) { return fmt == SSW_PIX_U8 ? 3u : fmt == SSW_PIX_U16 ? 7u : 15u; }   // of a 4-pixel load
 inline int pix_src_kind(int fmt) { return fmt + 1; }                     // SRC of the row pre-passes: 1 f32, 2 u8, 3 u16
-int launch_dct_pair_prep4_rows_rgb(hipStream_t st, bool f64, int u8, const void* rgb, size_t n_frames, size_t w, size_t h,
-                                   void* q1, void* q2, void* p, float* ip, float* qp);
+int launch_dct_pair_prep4_rows_rgb(hipStream_t st, int u8, const void* rgb, size_t n_frames, size_t w, size_t h,
+                                   double* q1, double* q2, double* p, float* ip, float* qp);
 // three levels on a forward row pass: (SSS, SS-) [kpad(w/4) wide], S- [kpad(w/2)], x- [kpad(w)] from an f32
 // plane (src_kind 0) or interleaved RGB f32 / u8 (1 / 2; ip / qp: I, Q planes out or null)
-int launch_dct_pair_prep8_rows(hipStream_t st, bool f64, int src_kind, const void* src, size_t n_frames, size_t w, size_t h,
-                               void* r1, void* r2, void* m, void* p, float* ip, float* qp);
+int launch_dct_pair_prep8_rows(hipStream_t st, int src_kind, const void* src, size_t n_frames, size_t w, size_t h,
+                               double* r1, double* r2, double* m, double* p, float* ip, float* qp);
 // Writer::result fused into the last inverse pass (EPI_INV_O_RGB): the frames' I / Q planes and the RGB output
 struct RgbSink {
     const float* iq_i = nullptr;
@@ -114,8 +95,8 @@ struct RgbSink {
     void* rgb = nullptr;          // [n][h][w][3] f32, or u8 when `u8`
     bool u8 = false;
 };
-int launch_dct_pair_prep8_cols(hipStream_t st, bool f64, const float* in, size_t n_frames, size_t w, size_t h,
-                               void* r1, void* r2, void* m, void* p);
+int launch_dct_pair_prep8_cols(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h,
+                               double* r1, double* r2, double* m, double* p);
 // r5, fused forward transform: how a launch takes part.
 //   FUSE_ROWS_COP    row launch over the unit-ordered, padded lines whose epilogue writes the sixteen column-operand planes
 //                    `cop`; needs the rotation tables of H, H/2, H/4
@@ -128,9 +109,6 @@ struct PairClassDesc { int kind, sub; const double *x1, *x2, *y1, *y2; };
 int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, int n_classes, const PairClassDesc* desc, float* out,
                                    double* tmp, size_t n_frames, size_t w, size_t h, Epilogue ep, const RgbSink* sink = nullptr,
                                    double* tmp_out = nullptr, const PairLayout& layout = PairLayout(), const FuseCols* fuse = nullptr);
-int launch_dct_pair_gemm_f32(hipStream_t st, bool is_row, bool inverse, int kind, int sub, const float* x1, const float* x2,
-                             const float* y1, const float* y2, float* out, float* tmp, size_t n_frames, size_t w,
-                             size_t h, Epilogue ep, const RgbSink* sink = nullptr);
 
 int launch_dct_pair_gemm_rows_subset_f64(hipStream_t st, const double* x, const double* y, unsigned cap, unsigned Kp, float* out,
                                          unsigned out_stride, unsigned off, size_t lines);
@@ -185,9 +163,6 @@ int launch_dct_pair_prep16_rows(hipStream_t st, int src_kind, const void* src, s
                                 const double* rot1, const double* rot2, const double* rot3, float* ip, float* qp, bool l2, bool unit_order = false);
 // r5, fused forward transform: units per frame of the row pass's line order (H/16 rounded up to whole k-blocks of 8)
 inline size_t dct_pair_fused_units(size_t h) { return ((h / 16 + 7) / 8) * 8; }
-
-int launch_dct_pair_gemm_rows_subset_f32(hipStream_t st, const float* x, const float* y, unsigned cap, unsigned Kp, float* out,
-                                         unsigned out_stride, unsigned off, size_t lines);
 
 // prune.hip: the derived frame's transform restricted to the frequency columns a chunk's index lists use
 // v is in the class when v % mod == rem, or == rem2 (classes of the split odd half: there the output is the cosine
@@ -292,12 +267,12 @@ struct ssw_ctx {
     hipStream_t own_stream = nullptr;   // private non-blocking stream created with the context
     size_t chunk_frames = 0;      // frames per internal pass; 0 = automatic (~2^28 pixels)
 
-    // basis cache: (N, inverse, f64, kind) -> device pointer; kind 0 = dense N x N,
-    // 1 / 2 = even / odd half basis (N/2 x N/2) of the folded kernels; 3 / 4 = the same, k-blocked (operand-ready GEMMs)
+    // basis cache: (N, inverse, f64, kind) -> device pointer; kind 0 = dense N x N (f32 or f64), 3 / 4 = even / odd half basis
+    // (N/2 x N/2, k-blocked: operand-ready GEMMs), 5.. = split odd half and rotation tables (get_basis); kinds >= 3 are f64
     std::map<std::tuple<size_t, bool, bool, int>, void*> basis;
     bool fold = true;             // use the even/odd-folded GEMMs where the shape allows
-    int fold_level = SSW_DCT_FOLDING_DEFAULT;           // 1 / 2: one folding level inside the GEMM kernel (dct_folded*.hip)
-                                  // 3: operand-ready GEMMs (dct_pair_*.hip); 4: two levels; 5: + a third on long forward row passes; 6: on all
+    int fold_level = SSW_DCT_FOLDING_DEFAULT;           // 1 / 2: dense; 3: operand-ready GEMMs (dct_pair_*.hip, f64 only);
+                                  // 4: two levels; 5: + a third on long forward row passes; 6: on all
 
     // growable scratch
     struct Buf {

@@ -206,7 +206,7 @@ int forward_from_host(ssw_ctx* ctx, const void* host_rgb, int u8, size_t w, size
 extern "C" {
 
 const char* ssw_version(void) { return "ssw-hip 0.1.0 (gfx950)"; }
-int ssw_build_all_strategies(void) { return ssw::build_all_strategies() ? 1 : 0; }
+int ssw_build_all_strategies(void) { return 0; }       // the library has one build (include/ssw.h)
 
 int ssw_ctx_transform_plan(ssw_ctx* ctx, size_t n_frames, size_t w, size_t h, int dct_type, uint32_t* flags) {
     if (!ctx || !flags || w == 0 || h == 0) return SSW_ERR_BAD_ARG;

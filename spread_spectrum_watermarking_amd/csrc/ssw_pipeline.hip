@@ -189,20 +189,19 @@ int get_basis(ssw_ctx* ctx, size_t n, bool inverse, bool f64, int kind, const vo
     auto it = ctx->basis.find(key);
     if (it != ctx->basis.end()) { *out = it->second; return SSW_OK; }
     void* p = nullptr;
-    // kinds 5..8: split odd half bases (cosE, sinE, cosO, sinO), 9: the rotation table, 10: sinE for the launches (row 0 =
-    // row n/8: class E's first and last pair share a slot) -- f64 only
+    // kind 0: the dense basis (f32 or f64).  f64 only: 3 / 4 the even / odd half basis, k-blocked; 5..8 the split odd half
+    // bases (cosE, sinE, cosO, sinO), 9 the rotation table, 10 sinE for the launches (row 0 = row n/8: class E's first and
+    // last pair share a slot)
+    if (kind != 0 && (kind < 3 || !f64)) return SSW_ERR_BAD_ARG;
     const int split_which = kind == 10 ? 4 : kind - 5;
     const size_t elems = kind == 0 ? n * dense_basis_kpad(n)
                        : kind == 9 ? n / 2
                        : kind >= 5 ? dct_pair_split_basis_rows(n, split_which) * dct_pair_split_kpad(n)
-                       : kind >= 3 ? (n / 2) * dct_pair_kpad(f64, n) : (n / 2) * half_basis_kpad(n);
-    if (kind >= 5 && !f64) return SSW_ERR_BAD_ARG;
+                                   : (n / 2) * dct_pair_kpad(n);
     SSW_ALLOC(&p, std::max<size_t>(elems, 1) * (f64 ? sizeof(double) : sizeof(float)));
     int rc = kind == 9 ? launch_make_rot_table(ctx->stream, n, (double*)p)
              : kind >= 5 ? launch_make_split_basis_blocked(ctx->stream, n, inverse, split_which, (double*)p)
-             : kind >= 3 ? launch_make_half_basis_blocked(ctx->stream, f64, n, inverse, kind - 3, p)
-             : kind != 0 ? (f64 ? launch_make_half_basis_f64(ctx->stream, n, inverse, kind - 1, (double*)p)
-                              : launch_make_half_basis_f32(ctx->stream, n, inverse, kind - 1, (float*)p))
+             : kind >= 3 ? launch_make_half_basis_blocked(ctx->stream, n, inverse, kind - 3, (double*)p)
              : f64     ? launch_make_basis_f64(ctx->stream, n, inverse, (double*)p)
                        : launch_make_basis_f32(ctx->stream, n, inverse, (float*)p);
     untimed_work(ctx);
@@ -250,7 +249,7 @@ size_t effective_chunk(const ssw_ctx* ctx, size_t w, size_t h, size_t n_frames) 
     if (c == 0) {
         const size_t px = std::max<size_t>(w * h, 1);
         c = std::max<size_t>(1, ((size_t)1 << 30) / px);
-        const size_t per_frame = dct_pair_operand_elems(true, 1, w, h) * sizeof(double);
+        const size_t per_frame = dct_pair_operand_elems(1, w, h) * sizeof(double);
         if (per_frame) c = std::max<size_t>(1, std::min(c, (size_t)0xFFFFFFFFull / per_frame));
         if (c >= 16) c &= ~(size_t)7;              // whole groups of 8 frames (4K: 129 -> 128: the GEMM line tiles stay whole)
         c = std::min(c, std::max<size_t>(n_frames, 1));
@@ -278,16 +277,6 @@ bool aligned_planes(const float* a, const float* b) { return ((reinterpret_cast<
 PairClassDesc D(int kind, int sub, const void* x1, const void* x2, const void* y1, const void* y2) {
     return {kind, sub, (const double*)x1, (const double*)x2, (const double*)y1, (const double*)y2};
 }
-// one launch of the operand-ready GEMM in the pass's precision (the paths the f32 twin of the diagnostic build shares)
-int pair_gemm(hipStream_t st, bool f64, bool is_row, bool inverse, int kind, int sub, const void* x1, const void* x2,
-              const void* y1, const void* y2, float* dst, void* tmpE, size_t n, size_t w, size_t h, Epilogue ep,
-              const RgbSink* sink = nullptr) {
-    const PairClassDesc d = D(kind, sub, x1, x2, y1, y2);
-    return f64 ? launch_dct_pair_gemm_multi_f64(st, is_row, inverse, 1, &d, dst, (double*)tmpE, n, w, h, ep, sink)
-               : launch_dct_pair_gemm_f32(st, is_row, inverse, kind, sub, (const float*)x1, (const float*)x2, (const float*)y1,
-                                          (const float*)y2, dst, (float*)tmpE, n, w, h, ep, sink);
-}
-
 // executed flop of one launch of the operand-ready GEMM (two products of lines x pairs x K multiply-adds)
 double pair_gemm_flop(bool is_row, int kind, int sub, size_t n, size_t w, size_t h) {
     const double lines = (double)(is_row ? n * h : n * w);
@@ -301,21 +290,21 @@ double pair_gemm_flop(bool is_row, int kind, int sub, size_t n, size_t w, size_t
 // What the builders of a pass share: the pass, its plan and what both its stages account.  Held by value in the stages.
 struct PassBuild {
     ssw_ctx* ctx; Xform x; PassPlan p;
-    bool first_pass, is_row, inverse, f64, from_rgb;
+    bool first_pass, is_row, inverse, from_rgb;
     size_t n, w, h, len, lines;
     const float* src; float* dst; Epilogue ep;
     int st_pass, st_main, st_prep;
-    double px, esz, prep_bytes, out_bpp;
-    // algorithmic bytes of the pass's GEMM launches (ssw_ctx_get_traffic): the operand planes in (one element per pixel), the
+    double px, prep_bytes, out_bpp;
+    // algorithmic bytes of the pass's GEMM launches (ssw_ctx_get_traffic): the operand planes in (one double per pixel), the
     // f32 result out -- or, in the last pass of Writer::result, I and Q in and the RGB frame out -- plus `xch` bytes per
     // pixel that the dependent launches of an inverse pass write and read back as doubles (A1: 1 + 1, T2: 2 + 2, E: 4 + 4)
-    double gemm_bytes(double xch) const { return px * (esz + xch + out_bpp); }
+    double gemm_bytes(double xch) const { return px * (8.0 + xch + out_bpp); }
     double flop(int kind, int sub) const { return pair_gemm_flop(is_row, kind, sub, n, w, h); }
     // the row launches write the plane between the passes class-major; the column launches read operands of their own
     PairLayout gemm_layout() const { return is_row ? p.layout : PairLayout(); }
-    int gemm(hipStream_t st, int nc, const PairClassDesc* d, void* tmp = nullptr, void* tmp_out = nullptr, const RgbSink* sink = nullptr,
+    int gemm(hipStream_t st, int nc, const PairClassDesc* d, double* tmp = nullptr, double* tmp_out = nullptr, const RgbSink* sink = nullptr,
              const PairLayout& lay = PairLayout()) const {
-        return launch_dct_pair_gemm_multi_f64(st, is_row, inverse, nc, d, dst, (double*)tmp, n, w, h, ep, sink, (double*)tmp_out, lay);
+        return launch_dct_pair_gemm_multi_f64(st, is_row, inverse, nc, d, dst, tmp, n, w, h, ep, sink, tmp_out, lay);
     }
     int rgb_kind() const { return from_rgb ? pix_src_kind(x.rgb_u8) : 0; }
     const void* prep_src() const { return from_rgb ? x.rgb : (const void*)src; }
@@ -357,9 +346,9 @@ struct PairBases {
 };
 int pair_bases(const PassBuild& b, ssw_ctx::Lane& ws, PairBases& pb) {
     ssw_ctx* ctx = b.ctx;
-    pb.bytes = dct_pair_operand_elems(b.f64, b.n, b.w, b.h) * (size_t)b.esz;
-    SSW_TRY(get_basis(ctx, b.len, b.inverse, b.f64, 3, &pb.b0));        // k-blocked half bases
-    SSW_TRY(get_basis(ctx, b.len, b.inverse, b.f64, 4, &pb.b1));
+    pb.bytes = dct_pair_operand_elems(b.n, b.w, b.h) * sizeof(double);
+    SSW_TRY(get_basis(ctx, b.len, b.inverse, true, 3, &pb.b0));        // k-blocked half bases
+    SSW_TRY(get_basis(ctx, b.len, b.inverse, true, 4, &pb.b1));
     if (!b.p.split) return SSW_OK;
     for (int i = 0; i < 4; ++i) SSW_TRY(get_basis(ctx, b.len, b.inverse, true, i == 1 ? 10 : 5 + i, &pb.sb[i]));      // 10: sinE for launches
     SSW_TRY(get_basis(ctx, b.len, false, true, 9, &pb.rot));
@@ -371,12 +360,14 @@ int pair_bases(const PassBuild& b, ssw_ctx::Lane& ws, PairBases& pb) {
 }
 
 // the odd half of the full-length transform from the operand plane `odd`: one launch, or rotate + two
-int odd_rotate(const PassBuild& b, const PairBases& pb, hipStream_t st, const void* odd) {
-    return b.p.split ? launch_dct_pair_rotate(st, (const double*)odd, (const double*)pb.rot, pb.sp, b.lines, b.len) : SSW_OK;
+int odd_rotate(const PassBuild& b, const PairBases& pb, hipStream_t st, const double* odd) {
+    return b.p.split ? launch_dct_pair_rotate(st, odd, (const double*)pb.rot, pb.sp, b.lines, b.len) : SSW_OK;
 }
-int odd_gemm(const PassBuild& b, const PairBases& pb, hipStream_t st, const void* odd, void* tmpE, const RgbSink* sink) {
-    if (!b.p.split)
-        return pair_gemm(st, b.f64, b.is_row, b.inverse, 2, 0, odd, odd, pb.b1, (const char*)pb.b1 + (b.len / 4) * 64, b.dst, tmpE, b.n, b.w, b.h, b.ep, sink);
+int odd_gemm(const PassBuild& b, const PairBases& pb, hipStream_t st, const double* odd, double* tmpE, const RgbSink* sink) {
+    if (!b.p.split) {
+        const PairClassDesc d = D(2, 0, odd, odd, pb.b1, (const char*)pb.b1 + (b.len / 4) * 64);
+        return b.gemm(st, 1, &d, tmpE, nullptr, sink);
+    }
     const PairClassDesc e = pb.e(), o = pb.o();
     SSW_TRY(b.gemm(st, 1, &e, tmpE, nullptr, sink));
     return b.gemm(st, 1, &o, tmpE, nullptr, sink);
@@ -386,22 +377,13 @@ double odd_flop(const PassBuild& b) { return b.p.split ? b.flop(3, 0) + b.flop(4
 // ---- one builder per strategy (dct_plan.hpp) ----
 int build_dense(const PassBuild& b, Chain& ch) {
     ssw_ctx* ctx = b.ctx;
-    const bool fold = b.p.strategy == PassStrategy::Folded;
-    const void *b0 = nullptr, *b1 = nullptr;
-    SSW_TRY(get_basis(ctx, b.len, b.inverse, b.f64, fold ? 1 : 0, &b0));
-    if (fold) SSW_TRY(get_basis(ctx, b.len, b.inverse, b.f64, 2, &b1));
-    const double dense = 2.0 * (double)b.lines * (double)b.len * (double)b.len;
-    const double flop = fold ? 0.5 * dense : dense;
+    const void* b0 = nullptr;
+    SSW_TRY(get_basis(ctx, b.len, b.inverse, b.x.precision == SSW_PRECISION_F64, 0, &b0));
+    const double flop = 2.0 * (double)b.lines * (double)b.len * (double)b.len;
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, flop);
         t.traffic(b.px * 8.0);
-        if (b.is_row) {
-            if (fold && b.f64) return launch_dct_rows_folded_f64(st, b.inverse, b.src, b.dst, b.lines, b.w, (const double*)b0, (const double*)b1, b.ep);
-            if (fold) return launch_dct_rows_folded_f32(st, b.inverse, b.src, b.dst, b.lines, b.w, (const float*)b0, (const float*)b1, b.ep);
-            return launch_dct_rows(st, b.x.precision, b.src, b.dst, b.lines, b.w, b0, b.ep);
-        }
-        if (fold && b.f64) return launch_dct_cols_folded_f64(st, b.inverse, b.src, b.dst, b.n, b.w, b.h, (const double*)b0, (const double*)b1, b.ep);
-        if (fold) return launch_dct_cols_folded_f32(st, b.inverse, b.src, b.dst, b.n, b.w, b.h, (const float*)b0, (const float*)b1, b.ep);
+        if (b.is_row) return launch_dct_rows(st, b.x.precision, b.src, b.dst, b.lines, b.w, b0, b.ep);
         return launch_dct_cols(st, b.x.precision, b.src, b.dst, b.n, b.w, b.h, b0, b.ep);
     }});
     return SSW_OK;
@@ -412,17 +394,18 @@ int build_pair_l1(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     PairBases pb;
     SSW_TRY(pair_bases(b, ws, pb));
     for (int i = 0; i < 2; ++i) SSW_TRY(grow(ws.operand[i], pb.bytes));
-    void *x1 = ws.operand[0].p, *x2 = ws.operand[1].p;
+    double *x1 = (double*)ws.operand[0].p, *x2 = (double*)ws.operand[1].p;
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, SSW_STAGE_DCT_PREP, st, b.prep_bytes);
-        return launch_dct_pair_prep(st, b.f64, b.is_row, b.inverse, b.src, b.n, b.w, b.h, x1, x2);
+        return launch_dct_pair_prep(st, b.is_row, b.inverse, b.src, b.n, b.w, b.h, x1, x2);
     }});
     const double f_main = b.flop(0, 0);
+    const PairClassDesc d = D(0, 0, x1, x2, pb.b0, pb.b1);
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, f_main);
         t.traffic(b.gemm_bytes(0.0));
         StageTimer tm(ctx, b.st_main, st, f_main);
-        return pair_gemm(st, b.f64, b.is_row, b.inverse, 0, 0, x1, x2, pb.b0, pb.b1, b.dst, nullptr, b.n, b.w, b.h, b.ep);
+        return b.gemm(st, 1, &d);
     }});
     return SSW_OK;
 }
@@ -432,26 +415,27 @@ int build_pair_two(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused
     PairBases pb;
     SSW_TRY(pair_bases(b, ws, pb));
     for (int i = 1; i < (b.inverse ? 5 : 4); ++i) SSW_TRY(grow(ws.operand[i], pb.bytes));
-    void* x2 = ws.operand[1].p;       // D | O
-    void* xx1 = ws.operand[2].p;      // SS | EE
-    void* xx2 = ws.operand[3].p;      // SD | EO
-    void* tmpE = ws.operand[4].p;     // inverse: the even half E, unrounded
+    double* x2 = (double*)ws.operand[1].p;       // D | O
+    double* xx1 = (double*)ws.operand[2].p;      // SS | EE
+    double* xx2 = (double*)ws.operand[3].p;      // SD | EO
+    double* tmpE = (double*)ws.operand[4].p;     // inverse: the even half E, unrounded
     const void *q0 = nullptr, *q1 = nullptr;
-    SSW_TRY(get_basis(ctx, b.len / 2, b.inverse, b.f64, 3, &q0));
-    SSW_TRY(get_basis(ctx, b.len / 2, b.inverse, b.f64, 4, &q1));
+    SSW_TRY(get_basis(ctx, b.len / 2, b.inverse, true, 3, &q0));
+    SSW_TRY(get_basis(ctx, b.len / 2, b.inverse, true, 4, &q1));
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
-        if (b.from_rgb) SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, b.f64, b.x.rgb_u8, b.x.rgb, b.n, b.w, b.h, xx1, xx2, x2, b.x.iq_i, b.x.iq_q));
-        else SSW_TRY(launch_dct_pair_prep4(st, b.f64, b.is_row, b.inverse, b.src, b.n, b.w, b.h, xx1, xx2, x2));
+        if (b.from_rgb) SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, b.x.rgb_u8, b.x.rgb, b.n, b.w, b.h, xx1, xx2, x2, b.x.iq_i, b.x.iq_q));
+        else SSW_TRY(launch_dct_pair_prep4(st, b.is_row, b.inverse, b.src, b.n, b.w, b.h, xx1, xx2, x2));
         return odd_rotate(b, pb, st, x2);
     }});
     const double f_main = odd_flop(b), f_all = f_main + b.flop(1, 0);
     const RgbSink sink = rgb_sink(b, fused_rgb);
+    const PairClassDesc even = D(1, 0, xx1, xx2, q0, q1);
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, f_all);
-        t.traffic(b.gemm_bytes(b.inverse ? b.esz : 0.0));          // inverse: the even half E out and in
+        t.traffic(b.gemm_bytes(b.inverse ? 8.0 : 0.0));          // inverse: the even half E out and in
         // even half: a half-length transform of S (forward) / of the even coefficients (inverse), folded again
-        SSW_TRY(pair_gemm(st, b.f64, b.is_row, b.inverse, 1, 0, xx1, xx2, q0, q1, b.dst, tmpE, b.n, b.w, b.h, b.ep));
+        SSW_TRY(b.gemm(st, 1, &even, tmpE));
         // odd half: full half-length sum, the odd basis split into two row blocks (second block:
         // len/4 lines further inside every k-block of the same plane = 64 bytes per line)
         StageTimer tm(ctx, b.st_main, st, f_main);
@@ -467,23 +451,24 @@ int build_pair_three(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     PairBases pb;
     SSW_TRY(pair_bases(b, ws, pb));
     for (int i = 0; i < 4; ++i) SSW_TRY(grow(ws.operand[i], pb.bytes));
-    void *d1 = ws.operand[1].p, *d2 = ws.operand[0].p, *r1 = ws.operand[2].p, *r2 = ws.operand[3].p;
+    double *d1 = (double*)ws.operand[1].p, *d2 = (double*)ws.operand[0].p, *r1 = (double*)ws.operand[2].p, *r2 = (double*)ws.operand[3].p;
     const void *h1 = nullptr, *e0 = nullptr, *e1 = nullptr;
-    SSW_TRY(get_basis(ctx, b.len / 2, false, b.f64, 4, &h1));          // odd half basis of len/2
-    SSW_TRY(get_basis(ctx, b.len / 4, false, b.f64, 3, &e0));          // half bases of len/4
-    SSW_TRY(get_basis(ctx, b.len / 4, false, b.f64, 4, &e1));
+    SSW_TRY(get_basis(ctx, b.len / 2, false, true, 4, &h1));          // odd half basis of len/2
+    SSW_TRY(get_basis(ctx, b.len / 4, false, true, 3, &e0));          // half bases of len/4
+    SSW_TRY(get_basis(ctx, b.len / 4, false, true, 4, &e1));
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
-        if (!b.is_row) SSW_TRY(launch_dct_pair_prep8_cols(st, b.f64, b.src, b.n, b.w, b.h, r1, r2, d2, d1));
-        else SSW_TRY(launch_dct_pair_prep8_rows(st, b.f64, b.rgb_kind(), b.prep_src(), b.n, b.w, b.h, r1, r2, d2, d1, b.prep_i(), b.prep_q()));
+        if (!b.is_row) SSW_TRY(launch_dct_pair_prep8_cols(st, b.src, b.n, b.w, b.h, r1, r2, d2, d1));
+        else SSW_TRY(launch_dct_pair_prep8_rows(st, b.rgb_kind(), b.prep_src(), b.n, b.w, b.h, r1, r2, d2, d1, b.prep_i(), b.prep_q()));
         return odd_rotate(b, pb, st, d1);
     }});
     const double f_main = odd_flop(b), f_all = f_main + b.flop(1, 1) + b.flop(2, 1);
+    const PairClassDesc r = D(1, 1, r1, r2, e0, e1), m = D(2, 1, d2, d2, h1, (const char*)h1 + (b.len / 8) * 64);
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, f_all);
         t.traffic(b.gemm_bytes(0.0));
-        SSW_TRY(pair_gemm(st, b.f64, b.is_row, b.inverse, 1, 1, r1, r2, e0, e1, b.dst, nullptr, b.n, b.w, b.h, b.ep));
-        SSW_TRY(pair_gemm(st, b.f64, b.is_row, b.inverse, 2, 1, d2, d2, h1, (const char*)h1 + (b.len / 8) * 64, b.dst, nullptr, b.n, b.w, b.h, b.ep));
+        SSW_TRY(b.gemm(st, 1, &r));
+        SSW_TRY(b.gemm(st, 1, &m));
         StageTimer tm(ctx, b.st_main, st, f_main);
         return odd_gemm(b, pb, st, d1, nullptr, nullptr);
     }});
@@ -606,7 +591,7 @@ int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
             plane = lpad * dct_pair_split_kpad(b.len / 2);
             pad = (double)lpad / (double)(n * h);
             fc = FuseCols{FUSE_ROWS_COP, cop, (const double*)crot1, (const double*)crot2, (const double*)crot3};
-            bytes = b.px * (b.esz + 8.0);                       // row operands in, column operands out
+            bytes = b.px * 16.0;                                // row operands in, column operands out
             out = nullptr;
         }
     }
@@ -647,8 +632,8 @@ int build_semi_deep(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fuse
     SSW_TRY(get_basis(ctx, b.len / 4, inv, true, 4, &e1));
     SSW_TRY(get_basis(ctx, b.len / 2, inv, true, 4, &h1));
     if (inv) for (int i : {1, 4}) SSW_TRY(grow(ws.operand[i], pb.bytes));
-    void* T2 = inv ? ws.operand[1].p : nullptr;
-    void* TE = inv ? ws.operand[4].p : nullptr;
+    double* T2 = inv ? (double*)ws.operand[1].p : nullptr;
+    double* TE = inv ? (double*)ws.operand[4].p : nullptr;
     double* sp = pb.sp;
     const double* rot = (const double*)pb.rot;
     ch.push_back({true, [=](hipStream_t st) -> int {
@@ -697,15 +682,15 @@ int build_deep_inv(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused
     SSW_TRY(deep_bases(b, false, db));
     SSW_TRY(grow(ws.operand[1], std::max<size_t>(pb.bytes, lines * (len / 4) * sizeof(double))));
     SSW_TRY(grow(ws.operand[4], std::max<size_t>(pb.bytes, lines * (len / 2) * sizeof(double))));
-    void* A1 = nullptr;               // the eighth-length even part, unrounded: len/8 doubles per line
+    double* A1 = nullptr;             // the eighth-length even part, unrounded: len/8 doubles per line
     if (l2) {
         SSW_TRY(get_basis(ctx, len / 4, false, true, 9, &db.rot3));
         SSW_TRY(deep_l2_halves(b, db));
         SSW_TRY(grow(ws.operand[2], std::max<size_t>(pb.bytes, lines * (len / 8) * sizeof(double))));      // (>= what any other pass asks of it)
-        A1 = ws.operand[2].p;
+        A1 = (double*)ws.operand[2].p;
     }
-    void* T2 = ws.operand[1].p;       // quarter-length even half, unrounded
-    void* TE = ws.operand[4].p;       // the even half E, unrounded
+    double* T2 = (double*)ws.operand[1].p;       // quarter-length even half, unrounded
+    double* TE = (double*)ws.operand[4].p;       // the even half E, unrounded
     double* sp = pb.sp;
     const RgbSink sink = rgb_sink(b, fused_rgb);
     ch.push_back({true, [=](hipStream_t st) -> int {
@@ -740,23 +725,22 @@ int build_deep_inv(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused
 int build_pass(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, bool first_pass, bool is_row, const float* src, float* dst,
                Epilogue ep, Chain& ch, bool* fused_rgb = nullptr) {
     const PlanInput in{x.type, x.precision, x.n, x.w, x.h, x.full_h, x.natural_order, aligned_planes(src, dst), plan_settings(ctx)};
-    PassBuild b{ctx, x, plan_pass(in, first_pass, is_row), first_pass, is_row, x.type == SSW_DCT3, x.precision == SSW_PRECISION_F64,
-                x.rgb && first_pass, x.n, x.w, x.h, is_row ? x.w : x.h, is_row ? x.n * x.h : x.n * x.w, src, dst, ep};
+    PassBuild b{ctx, x, plan_pass(in, first_pass, is_row), first_pass, is_row, x.type == SSW_DCT3, x.rgb && first_pass, x.n, x.w, x.h,
+                is_row ? x.w : x.h, is_row ? x.n * x.h : x.n * x.w, src, dst, ep};
     if (b.from_rgb && !(is_row && b.p.levels >= 2)) return SSW_ERR_BAD_ARG;      // can_fuse_rgb() checks the same conditions
     b.st_pass = is_row ? SSW_STAGE_DCT_ROW : SSW_STAGE_DCT_COL;
     b.st_main = is_row ? SSW_STAGE_DCT_ROW_MAIN : SSW_STAGE_DCT_COL_MAIN;
     b.st_prep = b.from_rgb ? SSW_STAGE_RGB_TO_YIQ : SSW_STAGE_DCT_PREP;
     b.px = (double)b.n * (double)b.w * (double)b.h;
-    b.esz = b.f64 ? 8.0 : 4.0;
-    // algorithmic bytes of the pre-pass: the f32 plane (or the RGB frame) in, the operand planes (one element per pixel in the
-    // GEMM's precision, whatever the number of folding levels) and I / Q out
-    b.prep_bytes = b.from_rgb ? b.px * (3.0 * (double)pix_bytes(x.rgb_u8) + (x.iq_i ? 8.0 : 0.0) + b.esz) : b.px * (4.0 + b.esz);
+    // algorithmic bytes of the pre-pass: the f32 plane (or the RGB frame) in, the operand planes (one double per pixel, whatever
+    // the number of folding levels) and I / Q out
+    b.prep_bytes = b.from_rgb ? b.px * (3.0 * (double)pix_bytes(x.rgb_u8) + (x.iq_i ? 8.0 : 0.0) + 8.0) : b.px * (4.0 + 8.0);
     const bool sink_pass = b.inverse && !first_pass && !is_row && x.rgb_out && x.iq_i && x.iq_q;
     b.out_bpp = sink_pass ? 8.0 + 3.0 * (double)pix_bytes(x.rgb_out_u8) : 4.0;
     const size_t first = ch.size();
     typedef PassStrategy S;
     const S s = b.p.strategy;
-    SSW_TRY(s == S::Dense || s == S::Folded ? build_dense(b, ch)
+    SSW_TRY(s == S::Dense                   ? build_dense(b, ch)
             : s == S::PairL1                ? build_pair_l1(b, ws, ch)
             : s == S::PairTwo               ? build_pair_two(b, ws, ch, fused_rgb)
             : s == S::PairThree             ? build_pair_three(b, ws, ch)
@@ -1042,13 +1026,13 @@ size_t prune_capacity(size_t k) {
 PruneSetup make_prune_setup(const ssw_ctx* ctx, bool f64, size_t n, size_t w, size_t h, size_t k, const float* y, const float* tmp,
                             const void* rgb, int u8) {
     PruneSetup ps;
-    if (!ctx->prune || k == 0) return ps;
+    if (!ctx->prune || k == 0 || !f64) return ps;                          // (the pair path runs in f64 only)
     if (!can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, u8)) return ps;       // rows first, >= two folding levels on the rows
     const bool aligned = aligned_planes(y, tmp);
-    if (!dct_pair_can_run(f64, n, w, h, aligned)) return ps;              // the chunk's planes within the 4 GB walk
+    if (!dct_pair_can_run(n, w, h, aligned)) return ps;                   // the chunk's planes within the 4 GB walk
     const size_t cap = prune_capacity(k);
     if (cap * 4 > w) return ps;                                           // not worth it: full transform
-    if (!dct_pair_can_run(f64, n, cap, h, aligned)) return ps;
+    if (!dct_pair_can_run(n, cap, h, aligned)) return ps;
     ps.rows = forward_rows_plan(ctx, f64, n, w, h, y, tmp);
     const bool deep = plan_is_deep(ps.rows);
     ps.plan.W = (unsigned)w;
@@ -1101,14 +1085,12 @@ PruneSetup make_prune_setup(const ssw_ctx* ctx, bool f64, size_t n, size_t w, si
 }
 
 // derived rgb frames -> compact coefficient plane ws.compact[1] [n][h][cap_total] holding, for every
-// frequency column the chunk's index lists use, the column the full transform would produce
-int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, int u8, size_t n, size_t w,
-                         size_t h, size_t k, const uint32_t* idx, const PruneSetup& ps, uint32_t* info, Chain& ch) {
-    const bool f64 = precision == SSW_PRECISION_F64;
-    const size_t esz = f64 ? 8 : 4;
+// frequency column the chunk's index lists use, the column the full (f64: make_prune_setup) transform would produce
+int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u8, size_t n, size_t w, size_t h, size_t k,
+                         const uint32_t* idx, const PruneSetup& ps, uint32_t* info, Chain& ch) {
     const PrunePlan plan = ps.plan;
     const size_t cap = plan.cap_total;
-    const size_t bytes = dct_pair_operand_elems(f64, n, w, h) * esz;
+    const size_t bytes = dct_pair_operand_elems(n, w, h) * sizeof(double);
     const int levels = ps.rows.levels;
     const bool deep = plan_is_deep(ps.rows), level2 = plan_is_level2(ps.rows);
     if (!deep) for (int b = 0; b < 4; ++b) SSW_TRY(grow(ws.operand[b], bytes));      // the deep pre-pass writes into operand[5] only
@@ -1174,52 +1156,52 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
         }
     } else {
         const void* b1 = nullptr;
-        SSW_TRY(get_basis(ctx, w, false, f64, 4, &b1));
-        cs[ci++] = {ws.operand[1].p, b1, w / 2, dct_pair_kpad(f64, w), w / 2};       // x- | D : odd
+        SSW_TRY(get_basis(ctx, w, false, true, 4, &b1));
+        cs[ci++] = {ws.operand[1].p, b1, w / 2, dct_pair_kpad(w), w / 2};       // x- | D : odd
     }
     if (deep) {
     } else if (levels == 3) {
         const void *h1 = nullptr, *e0 = nullptr, *e1 = nullptr;
-        SSW_TRY(get_basis(ctx, w / 2, false, f64, 4, &h1));
-        SSW_TRY(get_basis(ctx, w / 4, false, f64, 3, &e0));
-        SSW_TRY(get_basis(ctx, w / 4, false, f64, 4, &e1));
-        cs[ci++] = {ws.operand[0].p, h1, w / 4, dct_pair_kpad(f64, w / 2), w / 4};      // S-  : 2 mod 4
-        cs[ci++] = {ws.operand[2].p, e0, w / 8, dct_pair_kpad(f64, w / 4), w / 8};      // SSS : 0 mod 8
-        cs[ci++] = {ws.operand[3].p, e1, w / 8, dct_pair_kpad(f64, w / 4), w / 8};      // SS- : 4 mod 8
+        SSW_TRY(get_basis(ctx, w / 2, false, true, 4, &h1));
+        SSW_TRY(get_basis(ctx, w / 4, false, true, 3, &e0));
+        SSW_TRY(get_basis(ctx, w / 4, false, true, 4, &e1));
+        cs[ci++] = {ws.operand[0].p, h1, w / 4, dct_pair_kpad(w / 2), w / 4};      // S-  : 2 mod 4
+        cs[ci++] = {ws.operand[2].p, e0, w / 8, dct_pair_kpad(w / 4), w / 8};      // SSS : 0 mod 8
+        cs[ci++] = {ws.operand[3].p, e1, w / 8, dct_pair_kpad(w / 4), w / 8};      // SS- : 4 mod 8
     } else {
         const void *q0 = nullptr, *q1 = nullptr;
-        SSW_TRY(get_basis(ctx, w / 2, false, f64, 3, &q0));
-        SSW_TRY(get_basis(ctx, w / 2, false, f64, 4, &q1));
-        cs[ci++] = {ws.operand[2].p, q0, w / 4, dct_pair_kpad(f64, w / 2), w / 4};      // SS : 0 mod 4
-        cs[ci++] = {ws.operand[3].p, q1, w / 4, dct_pair_kpad(f64, w / 2), w / 4};      // SD : 2 mod 4
+        SSW_TRY(get_basis(ctx, w / 2, false, true, 3, &q0));
+        SSW_TRY(get_basis(ctx, w / 2, false, true, 4, &q1));
+        cs[ci++] = {ws.operand[2].p, q0, w / 4, dct_pair_kpad(w / 2), w / 4};      // SS : 0 mod 4
+        cs[ci++] = {ws.operand[3].p, q1, w / 4, dct_pair_kpad(w / 2), w / 4};      // SD : 2 mod 4
     }
     if (ci != plan.n_classes) return SSW_ERR_BAD_ARG;
     size_t goff[9], goff2[9], gtotal = 0;
     for (unsigned c = 0; c < plan.n_classes; ++c) {
         const size_t cap16 = (plan.c[c].cap + 15) / 16 * 16;               // (whole tiles of 16 rows: the fused pass's fragment order)
-        goff[c] = gtotal; gtotal += cs[c].kp * cap16 * esz;
-        goff2[c] = gtotal; if (cs[c].x2) gtotal += cs[c].kp * cap16 * esz;
+        goff[c] = gtotal; gtotal += cs[c].kp * cap16 * sizeof(double);
+        goff2[c] = gtotal; if (cs[c].x2) gtotal += cs[c].kp * cap16 * sizeof(double);
     }
     SSW_TRY(grow(ws.gathered, gtotal));
     char* gathered = (char*)ws.gathered.p;
     float* t_compact = (float*)ws.compact[0].p;
-    void *o0 = ws.operand[0].p, *o1 = ws.operand[1].p, *o2 = ws.operand[2].p, *o3 = ws.operand[3].p;
+    double *o0 = (double*)ws.operand[0].p, *o1 = (double*)ws.operand[1].p, *o2 = (double*)ws.operand[2].p, *o3 = (double*)ws.operand[3].p;
     const double px = (double)n * (double)w * (double)h;
-    const double prep_bytes = px * (3.0 * (double)pix_bytes(u8) + (double)esz);
+    const double prep_bytes = px * (3.0 * (double)pix_bytes(u8) + 8.0);
     double flop = 0.0;
     for (unsigned c = 0; c < plan.n_classes; ++c) flop += (cs[c].x2 ? 4.0 : 2.0) * (double)lines * plan.c[c].cap * (double)cs[c].ktrue;
     auto gather_jobs = [=](bool frag) {
         PruneGatherJobs jobs;
         jobs.n = 0;
         for (unsigned c = 0; c < plan.n_classes; ++c) {
-            const unsigned kblocks = (unsigned)(cs[c].kp / (64 / esz));
+            const unsigned kblocks = (unsigned)(cs[c].kp / KBlock<double>::KB);
             jobs.j[jobs.n++] = {rows + plan.c[c].off, (const char*)cs[c].basis, gathered + goff[c], plan.c[c].cap, (unsigned)cs[c].src_rows, kblocks, 0u, false, frag};
             if (cs[c].x2) jobs.j[jobs.n++] = {rows + plan.c[c].off, (const char*)cs[c].basis2, gathered + goff2[c], plan.c[c].cap, (unsigned)cs[c].src_rows, kblocks, 0u, true, frag};
         }
         return jobs;
     };
     // r5: marks of up to 1024 entries at level 2 -- the whole row pass in one kernel (dct_pair_derived.hip): no operand planes
-    if (level2 && f64) {
+    if (level2) {
         DerivedFusedClass fc[9];
         for (unsigned c = 0; c < plan.n_classes; ++c)
             fc[c] = {(const double*)(gathered + goff[c]), cs[c].x2 ? (const double*)(gathered + goff2[c]) : nullptr, (unsigned)pn1[c],
@@ -1242,7 +1224,7 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
                 return launch_dct_pair_derived_fused(st, pix_src_kind(u8), rgb, lines, w, (const double*)rot, (const double*)rot2, (const double*)rot3,
                                                      ncl, fca.data(), t_compact, (unsigned)cap);
             }});
-            Xform xc{SSW_DCT2, precision, n, cap, h, (float*)ws.compact[1].p, t_compact};
+            Xform xc{SSW_DCT2, SSW_PRECISION_F64, n, cap, h, (float*)ws.compact[1].p, t_compact};
             xc.natural_order = true;
             return build_pass(ctx, ws, xc, false, false, t_compact, (float*)ws.compact[1].p, Epilogue{1.f, 1.f}, ch);
         }
@@ -1254,17 +1236,17 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
         StageTimer t(ctx, SSW_STAGE_RGB_TO_YIQ, st, prep_bytes);
         if (deep) return launch_dct_pair_prep16_rows(st, pix_src_kind(u8), rgb, n, w, h, sp, (const double*)rot, (const double*)rot2,
                                                      (const double*)rot3, nullptr, nullptr, level2);
-        if (levels == 3) SSW_TRY(launch_dct_pair_prep8_rows(st, f64, pix_src_kind(u8), rgb, n, w, h, o2, o3, o0, o1, nullptr, nullptr));
-        else SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, f64, u8, rgb, n, w, h, o2, o3, o1, nullptr, nullptr));
-        return sp ? launch_dct_pair_rotate(st, (const double*)o1, (const double*)rot, sp, lines, w) : SSW_OK;
+        if (levels == 3) SSW_TRY(launch_dct_pair_prep8_rows(st, pix_src_kind(u8), rgb, n, w, h, o2, o3, o0, o1, nullptr, nullptr));
+        else SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, u8, rgb, n, w, h, o2, o3, o1, nullptr, nullptr));
+        return sp ? launch_dct_pair_rotate(st, o1, (const double*)rot, sp, lines, w) : SSW_OK;
     }});
     ch.back().tag = 2;
     ch.push_back({false, [=](hipStream_t st) -> int {
         SSW_TRY(launch_prune_gather_bases(st, gather_jobs(false)));
         untimed_work(ctx);
         StageTimer t(ctx, SSW_STAGE_DCT_ROW, st, flop);
-        t.traffic(px * (double)esz + (double)lines * (double)cap * 4.0);      // every operand plane once in, the compact plane out
-        if (f64 && plan_merge(lines)) {          // a single frame: the classes side by side in one launch per kind
+        t.traffic(px * 8.0 + (double)lines * (double)cap * 4.0);      // every operand plane once in, the compact plane out
+        if (plan_merge(lines)) {          // a single frame: the classes side by side in one launch per kind
             PairSubsetClass sc[9];
             for (unsigned c = 0; c < plan.n_classes; ++c)
                 sc[c] = {(const double*)cs[c].x, (const double*)cs[c].x2, (const double*)(gathered + goff[c]),
@@ -1275,15 +1257,13 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const v
             if (cs[c].x2) SSW_TRY(launch_dct_pair_gemm_rows_subset_split_f64(st, (const double*)cs[c].x, (const double*)cs[c].x2, (const double*)(gathered + goff[c]),
                                                                              (const double*)(gathered + goff2[c]), plan.c[c].cap, (unsigned)cs[c].kp, t_compact,
                                                                              (unsigned)cap, plan.c[c].off, lines));
-            else if (f64) SSW_TRY(launch_dct_pair_gemm_rows_subset_f64(st, (const double*)cs[c].x, (const double*)(gathered + goff[c]), plan.c[c].cap,
-                                                                       (unsigned)cs[c].kp, t_compact, (unsigned)cap, plan.c[c].off, lines));
-            else     SSW_TRY(launch_dct_pair_gemm_rows_subset_f32(st, (const float*)cs[c].x, (const float*)(gathered + goff[c]), plan.c[c].cap,
-                                                                  (unsigned)cs[c].kp, t_compact, (unsigned)cap, plan.c[c].off, lines));
+            else SSW_TRY(launch_dct_pair_gemm_rows_subset_f64(st, (const double*)cs[c].x, (const double*)(gathered + goff[c]), plan.c[c].cap,
+                                                              (unsigned)cs[c].kp, t_compact, (unsigned)cap, plan.c[c].off, lines));
         }
         return SSW_OK;
     }});
     // column pass on the compact plane: the second pass of the same transform, `cap` columns wide
-    Xform xc{SSW_DCT2, precision, n, cap, h, (float*)ws.compact[1].p, t_compact};
+    Xform xc{SSW_DCT2, SSW_PRECISION_F64, n, cap, h, (float*)ws.compact[1].p, t_compact};
     xc.natural_order = true;                 // the compact plane's columns are the gathered frequencies, in the plan's order
     return build_pass(ctx, ws, xc, false, false, t_compact, (float*)ws.compact[1].p, Epilogue{1.f, 1.f}, ch);
 }
@@ -1410,7 +1390,7 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
             ch.push_back({true, [=](hipStream_t st) -> int { return topk(ctx, st, *sel, yb, n, w, h, c.ordering, k, idx); }});   // :493
         if (!pruned) return full_derived(ws, f0, n, yb, tmp, idx, ch);
         const char* drgb = static_cast<const char*>(dev_derived_rgb) + f0 * plane * px_bytes;
-        SSW_TRY(build_pruned_derived(ctx, ws, c.precision, drgb, u8, n, w, h, k, idx, ps, overflow + ci * SSW_PRUNE_INFO, ch));
+        SSW_TRY(build_pruned_derived(ctx, ws, drgb, u8, n, w, h, k, idx, ps, overflow + ci * SSW_PRUNE_INFO, ch));
         const float* compact = (const float*)ws.compact[1].p;
         const uint32_t* pos = (const uint32_t*)ws.prune_u32.p + w;
         const size_t cap = ps.plan.cap_total;
@@ -1469,7 +1449,7 @@ int extract_single_pruned(ssw_ctx* ctx, int precision, const void* derived_rgb, 
     SSW_TRY(grow(ctx->overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));
     uint32_t* info = (uint32_t*)ctx->overflow.p;
     Chain ch;
-    SSW_TRY(build_pruned_derived(ctx, ws, precision, derived_rgb, u8, 1, w, h, k, idx, ps, info, ch));
+    SSW_TRY(build_pruned_derived(ctx, ws, derived_rgb, u8, 1, w, h, k, idx, ps, info, ch));
     SSW_TRY(run_serial(ch, ctx->stream));
     {
         StageTimer t(ctx, SSW_STAGE_EXTRACT, ctx->stream);

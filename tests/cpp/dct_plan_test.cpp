@@ -83,6 +83,29 @@ int main() {
         const TransformPlan p = plan(3, 640, 444);
         CHECK(p.rows().strategy == S::Dense && p.cols().strategy == S::Dense && plan_flags(p) == 0, "640x444");
     }
+    // SSW_PRECISION_F32 takes the dense kernels at every folding level (the pair path is f64 only)
+    for (int l : {1, 3, 5, 6}) {
+        PlanInput in;
+        in.type = SSW_DCT2; in.precision = SSW_PRECISION_F32; in.n = 8; in.w = 3840; in.h = 2160; in.s = level(l);
+        const TransformPlan p = plan_transform(in);
+        CHECK(p.rows().strategy == S::Dense && p.cols().strategy == S::Dense && plan_flags(p) == 0, "f32 dense");
+    }
+    // folding levels 1 / 2 run dense too
+    for (int l : {1, 2}) CHECK(plan(8, 3840, 2160, SSW_DCT2, level(l)).rows().strategy == S::Dense, "levels 1 / 2 dense");
+    // frames per group of build_transform, both precisions: f64 keeps a pass's operand planes below 4 GB; f32 (dense) keeps the
+    // group size it has always had (values recorded before the f32 pair path was removed)
+    {
+        struct Limit { size_t w, h, f64, f32; };
+        const Limit limits[] = {{3840, 2160, 129, 257}, {7680, 4320, 32, 64}, {1920, 1080, 514, 1028}, {1280, 720, 1165, 2184},
+                                {512, 272, 7710, 13107}, {256, 144, 29127, 43690}, {3840, 96, 2912, 4369}, {1024, 96, 10922, 16383},
+                                {640, 444, 3744, 7489}};
+        for (const Limit& l : limits) {
+            CHECK(plan_frame_limit(PlanSettings(), true, l.w, l.h) == l.f64, "frame limit f64");
+            CHECK(plan_frame_limit(PlanSettings(), false, l.w, l.h) == l.f32, "frame limit f32");
+        }
+        CHECK(plan_frame_limit(level(0), true, 3840, 2160) == ~(size_t)0 && plan_frame_limit(level(0), false, 3840, 2160) == ~(size_t)0,
+              "level 0: no frame limit");
+    }
     // unaligned planes take the dense kernels as well
     {
         PlanInput in;

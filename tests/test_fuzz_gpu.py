@@ -1,6 +1,6 @@
 """A bounded, fixed-seed leg of the builder's fuzzers (tools/fuzz_dct.py, tools/fuzz_batch.py) inside `pytest -m gpu`, so
 that the driver's GPU test run covers every strategy branch of the transform (deep / semi-deep / first-level split /
-exact-operand folding / in-kernel folding / dense; rows or columns first; class-major tiles or natural planes; staged or
+exact-operand folding / dense; rows or columns first; class-major tiles or natural planes; staged or
 r3 pre-passes by shape) and of the batch pipelines (pruned + two lanes against full + one lane) -- not only the
 hand-picked shapes of test_gpu_parity.py.  Reference: src/dct2d.rs:83-219 (the transform the oracle restates),
 src/algorithm.rs:295-316, :355-379, :529-593 (the batch flows).  Everything goes through the C ABI; the oracle checks."""
@@ -148,24 +148,6 @@ def test_transform_plan_reports_the_default_path():
     with tuning(fuse_cols=0):
         q = c.transform_plan(128, 3840, 2160)
         assert not q["fused_cols"] and q["cols_level2"] and q["rows_level2"]
-
-
-def test_diagnostic_build_runs_the_strategy_matrix():
-    """`make ALL_STRATEGIES=1` (lib/libssw_hip_all.so: the default library plus the r1 in-kernel folding and the f32 operand-
-    ready twin).  The tests that need those strategies skip themselves under the default library; here they run in a
-    child process that loads the diagnostic build through SSW_LIB_PATH -- the F32 parametrisations, folded against dense,
-    every folding level in f32, pruned / fused paths of the f32 twin."""
-    import subprocess
-    lib = os.path.join(ROOT, "spread_spectrum_watermarking_amd", "lib", "libssw_hip_all.so")
-    if not os.path.exists(lib):
-        pytest.skip("diagnostic library not built (make -C spread_spectrum_watermarking_amd/csrc ALL_STRATEGIES=1)")
-    env = dict(os.environ, SSW_LIB_PATH=lib)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), os.path.join(ROOT, "tests", "test_pipeline_gpu.py"),
-                        "-m", "gpu", "-q", "-x", "-k", "f32 or folded or strategy or pruned or fused_colour or batch_path"],
-                       env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
-    tail = r.stdout[-1500:] + r.stderr[-1500:]
-    assert r.returncode == 0, tail
-    assert " passed" in r.stdout and "skipped" not in r.stdout.splitlines()[-1], tail
 
 
 def test_tuning_table_round_trip():

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 import gpu_util as G
-from conftest import ALL_STRATEGIES, f32_to_u8, needs_all_strategies, u8_to_f32
+from conftest import f32_to_u8, u8_to_f32
 from oracle import oracle as O
 from spread_spectrum_watermarking_amd import _lib as L
 import spread_spectrum_watermarking_amd as wm
@@ -26,9 +26,9 @@ import spread_spectrum_watermarking_amd as wm
 pytestmark = pytest.mark.gpu
 
 F32, F64 = L.PRECISION_F32, L.PRECISION_F64
-# precisions of the default test run: f64 (the parity path); f32 joins when the diagnostic build with its operand-ready twin is loaded
-# (in the default library SSW_PRECISION_F32 runs the dense kernels: covered by the known-answer and single_simple tests below)
-PRECISIONS = [F32, F64] if ALL_STRATEGIES else [F64]
+# precisions of the folded paths: f64 only (SSW_PRECISION_F32 runs the dense kernels: covered by the known-answer and
+# single_simple tests below)
+PRECISIONS = [F64]
 
 
 def _ext_within_1e5(ext, ref):
@@ -145,14 +145,10 @@ def test_dct_folded_equals_dense(shape, dct_type, precision):
     finally:
         G.ctx().set_dct_folding(True)
     ref = np.stack([O.dct2d(p, dct_type) for p in x])
-    if precision == F32:
-        assert not np.array_equal(folded, dense)                  # really two different code paths
-        tol = (4e-6 if dct_type == L.DCT3 else 1e-6) * np.abs(ref).max()
-        assert np.abs(folded - ref).max() <= tol and np.abs(dense - ref).max() <= tol
-    else:                                                         # both are the correctly rounded transform
-        assert np.mean(folded == ref) >= 0.999 and np.mean(dense == ref) >= 0.999
-        assert np.mean(folded == dense) >= 0.999
-        assert np.abs(folded.astype(np.float64) - ref).max() <= 2e-7 * max(ac_max(ref), 1.0)
+    # both are the correctly rounded transform
+    assert np.mean(folded == ref) >= 0.999 and np.mean(dense == ref) >= 0.999
+    assert np.mean(folded == dense) >= 0.999
+    assert np.abs(folded.astype(np.float64) - ref).max() <= 2e-7 * max(ac_max(ref), 1.0)
 
 
 @pytest.mark.parametrize("shape", [(16, 16), (24, 40), (40, 128), (72, 136), (136, 72), (200, 328), (264, 8),
@@ -164,7 +160,7 @@ def test_dct_operand_ready_path_matches(shape, dct_type, level):
     """Pre-folded f64 operand planes + VALU-free GEMM loop (folding level 3; level 4 folds the even
     half once more wherever the axis length is a multiple of 16; level 6 a third time on forward row
     passes whose length is a multiple of 32 -- the default, 5, does that from 3072 columns): same exact operands and f64
-    products as the in-kernel folding, only the summation order differs, so the rounded result
+    products as the default path, only the summation order differs, so the rounded result
     must agree with it and with the oracle."""
     rng = np.random.default_rng(shape[0] * 5 + shape[1])
     x = rng.random((3,) + shape).astype(np.float32)
@@ -210,28 +206,6 @@ def test_odd_split_matches_exact_operands(shape, dct_type):
         assert np.abs(back - x).max() <= 4e-7
 
 
-@pytest.mark.parametrize("shape", [(24, 40), (72, 136), (136, 72), (80, 208), (144, 1040), (1080, 1920), (128, 256), (288, 136)])
-@pytest.mark.parametrize("dct_type", [L.DCT2, L.DCT2_ORTHOGONAL, L.DCT3])
-@pytest.mark.parametrize("level", [1, 3, 4, 6])
-@needs_all_strategies
-def test_dct_f32_every_strategy_within_tolerance(shape, dct_type, level):
-    """f32 precision: in-kernel folding (1) and the operand-ready GEMMs with one (3) / two (4) folding
-    levels round differently (each folding level adds one rounding per operand sum) but all stay
-    inside the f32 bars of test_dct_f32_mfma_within_tolerance."""
-    rng = np.random.default_rng(shape[0] * 11 + shape[1])
-    x = rng.random((2,) + shape).astype(np.float32)
-    if dct_type == L.DCT3:
-        x = np.stack([O.dct2d(p, O.DCT2) for p in x])
-    G.ctx().set_dct_folding(level)
-    try:
-        got = G.dct2d(x, dct_type, F32)
-    finally:
-        G.ctx().set_dct_folding(True)
-    ref = np.stack([O.dct2d(p, dct_type, O.BACKEND_F64) for p in x])
-    scale = max(float(np.abs(ref).max()), 1e-30)
-    assert np.abs(got.astype(np.float64) - ref).max() <= (4e-6 if dct_type == L.DCT3 else 1e-6) * scale
-
-
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_dct_batched_equals_single(precision):
     rng = np.random.default_rng(2)
@@ -258,7 +232,7 @@ def test_dct_linearity_and_roundtrip_1080p(precision):
     assert np.abs(cs - lin).max() <= 1e-6 * np.abs(lin).max()      # `s` itself is rounded to f32
     assert abs(float(ca[0, 0]) - 4.0 * float(a.astype(np.float64).sum())) <= 1e-6 * abs(float(ca[0, 0]))   # DC = 4 sum
     back = G.dct2d(ca, L.DCT3, precision)
-    assert np.abs(back - a).max() <= (2e-7 if precision == F64 else 3e-6)
+    assert np.abs(back - a).max() <= 2e-7
 
 
 # ---- ordering ----------------------------------------------------------------------------------
@@ -638,11 +612,10 @@ def test_batch_path_equals_handles_and_oracle(precision):
         assert np.array_equal(ext[f], e1)
         assert sims[f] == np.float32(wm.Tester(e1).similarity(marks[f]).similarity)
         assert sims[f] > 0.9 * np.linalg.norm(marks[f])
-        if precision == F64:
-            o_res = O.embed_frame(rgb[f], marks[f])
-            assert np.abs(res["rgb"][f] - o_res).max() <= 2e-7
-            o_ext, o_sim = O.extract_frame(rgb[f], o_res, marks[f])
-            assert abs(sims[f] - o_sim) < 1e-4 * abs(o_sim) + 1e-4
+        o_res = O.embed_frame(rgb[f], marks[f])
+        assert np.abs(res["rgb"][f] - o_res).max() <= 2e-7
+        o_ext, o_sim = O.extract_frame(rgb[f], o_res, marks[f])
+        assert abs(sims[f] - o_sim) < 1e-4 * abs(o_sim) + 1e-4
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
@@ -710,8 +683,8 @@ def test_full_hd_pipeline_parity_with_oracle():
 
 def test_4k_size_independent_properties():
     """BASELINE configs[1]/[3] frame size (3840x2160), default strategy: properties that need no CPU
-    reference -- inverse(forward(x)) == x to f32 round-off, the operand-ready two-level GEMMs agree with
-    the in-kernel one-level ones, embed -> extract recovers the mark, linearity of the transform."""
+    reference -- inverse(forward(x)) == x to f32 round-off, the operand-ready GEMMs agree with the dense
+    ones (folding level 1), embed -> extract recovers the mark, linearity of the transform."""
     w, h, k = 3840, 2160, 1000
     rgb = G.synth(9, 5, 2, w, h)
     y = np.ascontiguousarray(rgb[..., 0] * np.float32(0.3) + rgb[..., 1] * np.float32(0.59))

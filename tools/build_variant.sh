@@ -18,7 +18,7 @@ for u in $UNITS; do
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wall -Wno-unused-function "$@" -c "$C/$u.hip" -o "$D/$u.o" &
 done
 wait
-EXCL="-e dct_folded -e dct_pair_f32.o"
+EXCL=""
 for u in $UNITS; do EXCL="$EXCL -e /$u.o"; done
 OBJS=$(ls "$C"/*.o | grep -v $EXCL)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$R/spread_spectrum_watermarking_amd/lib/libssw_$NAME.so" $OBJS "$D"/*.o

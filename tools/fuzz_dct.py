@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Random frame shapes (multiples of 8 and a few that are not) through ssw_dct2d in f64 against the CPU oracle's
 correctly rounded transform: exercises every strategy of the planner (csrc/dct_plan.hpp: Deep / DeepL2 / SemiDeep /
-SemiDeepInv / DeepInv / DeepInvL2, PairL1 / PairTwo / PairThree with or without the split odd half, Folded, Dense; rows
+SemiDeepInv / DeepInv / DeepInvL2, PairL1 / PairTwo / PairThree with or without the split odd half, Dense; rows
 first and columns first; class-major or natural planes).
 tests/test_fuzz_gpu.py runs a fixed-seed leg of it in `pytest -m gpu`.
 usage: python tools/fuzz_dct.py [N_SHAPES SEED]"""

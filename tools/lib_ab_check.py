@@ -4,7 +4,8 @@ runs in a child process (SSW_LIB_PATH), transforms the same synthetic frames -- 
 shapes of every strategy, one batch embed + extract -- and prints a digest per case; the parent compares the digests.
 usage: python tools/lib_ab_check.py [--stages] LIB_A LIB_B
        --stages: also the stage accounts of every case (ssw_ctx_get_timing launch counts, ssw_ctx_get_work, ssw_ctx_get_traffic),
-                 and the cases again at folding levels 0, 3, 4, 6 and with the odd split off on the 4K, 1080p and 512 x 272 shapes
+                 the cases again at folding levels 0, 1, 3, 4, 6 and with the odd split off on the 4K, 1080p and 512 x 272 shapes,
+                 and every case in SSW_PRECISION_F32 (the dense f32 kernels)
        python tools/lib_ab_check.py --golden LIB OUT.json     (writes the digests of one build, in the format of
                                                               tests/golden/gemm_digests.json: the r5 kernel's digests, kept as recorded)"""
 import hashlib
@@ -16,8 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(2160, 3840, 8), (2160, 3840, 1), (1080, 1920, 12), (720, 1280, 20), (4320, 7680, 2), (272, 512, 40), (444, 640, 3), (2160, 3840, 3)]
 BATCH = ((2160, 3840, 8), (1080, 1920, 12), (272, 512, 40))
 # --stages: non-default strategy settings, each on these shapes (the first tag is the default, covered by SHAPES)
-SETTINGS = (("fold0", "set_dct_folding", 0), ("fold3", "set_dct_folding", 3), ("fold4", "set_dct_folding", 4),
-            ("fold6", "set_dct_folding", 6), ("nosplit", "set_odd_split", False))
+SETTINGS = (("fold0", "set_dct_folding", 0), ("fold1", "set_dct_folding", 1), ("fold3", "set_dct_folding", 3),
+            ("fold4", "set_dct_folding", 4), ("fold6", "set_dct_folding", 6), ("nosplit", "set_odd_split", False))
 SETTING_SHAPES = ((2160, 3840, 8), (1080, 1920, 12), (272, 512, 40))
 
 
@@ -47,7 +48,9 @@ def child():
     cases = [(h, w, n, "") for (h, w, n) in SHAPES]
     if stages:
         cases += [(h, w, n, tag) for tag, _, _ in SETTINGS for (h, w, n) in SETTING_SHAPES]
+        cases += [(h, w, n, "f32") for (h, w, n) in SHAPES]
     for (h, w, n, tag) in cases:
+        prec = L.PRECISION_F32 if tag == "f32" else L.PRECISION_F64
         for t, fn, val in SETTINGS:
             if t == tag:
                 getattr(ctx, fn)(val)
@@ -61,7 +64,7 @@ def child():
             ctx.reset_timing()
         for kind, name in ((L.DCT2, "fwd"), (L.DCT2_ORTHOGONAL, "ortho"), (L.DCT3, "inv")):
             t = ctx.to_device(y0)
-            check(lib.ssw_dct2d(ctx.handle, kind, L.PRECISION_F64, n, w, h, t.ptr), "dct")
+            check(lib.ssw_dct2d(ctx.handle, kind, prec, n, w, h, t.ptr), "dct")
             out = t.to_host(np.float32, (n, h, w))
             print(f"DIGEST {pre}dct {h}x{w}x{n} {name} {hashlib.sha256(out.tobytes()).hexdigest()[:16]}", flush=True)
             accounts(f"{pre}dct {h}x{w}x{n} {name}")
@@ -71,7 +74,7 @@ def child():
             marks = np.random.default_rng(3).standard_normal((n, k)).astype(np.float32)
             dm = ctx.to_device(marks)
             out, ext, sims = ctx.alloc(n * h * w * 12), ctx.alloc(n * k * 4), ctx.alloc(n * 4)
-            cfg = L.Config(L.ORDER_ENERGY, L.OPTION2, 0.1, L.PRECISION_F64)
+            cfg = L.Config(L.ORDER_ENERGY, L.OPTION2, 0.1, prec)
             check(lib.ssw_batch_embed(ctx.handle, C.byref(cfg), rgb.ptr, n, w, h, dm.ptr, k, out.ptr, None, None), "embed")
             check(lib.ssw_batch_extract(ctx.handle, C.byref(cfg), rgb.ptr, out.ptr, n, w, h, k, ext.ptr, dm.ptr, sims.ptr), "extract")
             for nm, b, shp in (("marked", out, (n, h, w, 3)), ("ext", ext, (n, k)), ("sims", sims, (n,))):
