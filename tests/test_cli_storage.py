@@ -76,3 +76,26 @@ def test_watermark_then_test_commands(tmp_path):
     assert lines[4] == '  Description: "the \\"cat\\""' and lines[5] == f'  File: "{js}"'
     assert float(lines[2].split(": ")[1]) > 25.0
     assert lines[7] == "  Matches: false" and abs(float(lines[8].split(": ")[1])) < 4.0
+
+
+@pytest.mark.gpu
+def test_watermark_then_test_with_stored_non_default_options(tmp_path):
+    """`watermark --ordering legacy --method option3 --alpha 0.2 --length 500`: the JSON stores the three options and
+    `test` extracts with them (main.rs:383-407), not with the defaults."""
+    from spread_spectrum_watermarking_amd.api import Reader, Tester
+    src = str(tmp_path / "cat.jpg")
+    shutil.copy(os.path.join(GOLDEN, "porcelain_cat_grey_background.jpg"), src)
+    assert cli.main(["watermark", src, "--ordering", "legacy", "--method", "option3", "--alpha", "0.2", "--length", "500"]) == 0
+    png, js = cli.out_paths(src)
+    st = Version1Storage.load(js)
+    assert st.config == Configuration(0.2, "Option3", "Legacy") and len(st.watermarks[0].values) == 500
+    doc = json.loads(open(js).read())["Version1"]["config"]
+    assert doc == {"insert_extract": {"alpha": 0.2, "method": "Option3"}, "ordering": "Legacy"}
+    buf = io.StringIO()
+    assert cli.cmd_test(cli.build_parser().parse_args(["test", src, png, js]), out=buf) == 0
+    lines = buf.getvalue().splitlines()
+    assert lines[0] == "-" and lines[1] == "  Matches: true"
+    orig, marked = cli._open_image(src), cli._open_image(png)
+    ext = Reader.base(orig, st.config.to_read_config()).extract(Reader.derived(marked), 500)
+    sim = Tester(ext).similarity(st.watermarks[0].values).similarity
+    assert lines[2] == f"  Similarity: {cli._rust_f32(sim)}"

@@ -38,6 +38,22 @@ def test_random_shapes_through_the_batch_pipelines(case):
     assert fuzz_batch.passes(r), r
 
 
+CONFIG_CASES = fuzz_batch.config_cases(8, 20261018)       # four portrait cases; every ordering, method and alpha
+
+
+@pytest.mark.parametrize("case", CONFIG_CASES, ids=[f"{c[0]}x{c[1]}x{c[2]}k{c[3]}-o{c[6][0]}m{c[6][1]}a{c[6][2]:g}"
+                                                    f"{'-portrait' if c[7] else ''}" for c in CONFIG_CASES])
+def test_random_shapes_and_configurations_through_the_batch_pipelines(case):
+    """The same under a drawn ordering, insertion method, alpha in {0.05, 0.1, 0.3} and orientation (portrait frames:
+    columns first, no RGB pre-pass, no pruned derived transform); frame 0 against the oracle in that configuration."""
+    r = fuzz_batch.check(*case)
+    assert r["plan"]["pair_f64"], r["plan"]
+    if case[7]:
+        assert r["pruned_chunks"] == 0, r
+    assert r["same"], "pruned + two lanes differs from full transforms + one lane"
+    assert fuzz_batch.passes(r), r
+
+
 @pytest.mark.parametrize("case", fuzz_batch.shapes(8, 77), ids=lambda c: f"{c[0]}x{c[1]}x{c[2]}k{c[3]}")
 def test_random_shapes_through_the_level2_batch_pipelines(case):
     """The same on the kernels the 4K / 8K batches run -- level-2 passes, the fused forward transform where the shape allows,
