@@ -384,6 +384,33 @@ int ssw_batch_extract_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* d
                            const uint8_t* dev_derived_rgb, size_t n_frames, size_t w, size_t h, size_t k,
                            float* dev_extracted, const float* dev_marks, float* dev_sims);
 
+/* ---- fingerprinting: many individually marked copies of one image (device-resident) ---- */
+/* For each of n_copies marks: Writer::new(image, cfg).mark(&[&mark_i]) (algorithm.rs:295-316, :355-379),
+   i.e. the loop of examples/main.rs:266-278 once per recipient.  dev_rgb: ONE frame [h][w][3];
+   dev_marks [n_copies][k]; dev_rgb_out [n_copies][h][w][3]; dev_indices_out optional [min(k, w*h-1)].
+   The forward transform, the selection and the inverse of the unmarked plane are computed once; each copy is then a
+   rank-R f64 update of the second inverse pass (R = distinct first-pass lines among the k indices) fused with the colour
+   conversion (csrc/fingerprint.hip).  Same numerical contract as ssw_batch_embed: within its f64 parity bars of every
+   single-mark Writer::mark, not bit-identical to it.  A copy does not depend on the other marks of the call or on its
+   position among them.  Marks longer than w*h-1 are cut like ssw_batch_embed (the stride of dev_marks stays k);
+   n_copies == 0 returns what ssw_batch_embed returns for no frames; SSW_PRECISION_F32 and the Custom variants:
+   SSW_ERR_UNSUPPORTED.  Stream contract of ssw_batch_embed (enqueues only; graph-capturable); copies go in groups, so
+   the workspace stays bounded (about 2 GiB) for any n_copies.  Timed as SSW_STAGE_EMBED / SSW_STAGE_YIQ_TO_RGB. */
+int ssw_fingerprint_embed(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_rgb, size_t w, size_t h,
+                          const float* dev_marks, size_t n_copies, size_t k, float* dev_rgb_out,
+                          uint32_t* dev_indices_out);
+/* The same on 8-bit frames (algorithm.rs:295-316, :355-379 with into_rgb32f() / into_rgb8() of the caller,
+   examples/main.rs:271-278): u8 in, copies quantised like into_rgb8(). */
+int ssw_fingerprint_embed_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* dev_rgb, size_t w, size_t h,
+                               const float* dev_marks, size_t n_copies, size_t k, uint8_t* dev_rgb_out,
+                               uint32_t* dev_indices_out);
+/* Handle form: copies of what embed(&[&mark_i]) + result() (algorithm.rs:348-352, :361-379) would give on n clones of
+   this writer, as it stands now (its current coefficients, the ordering Writer::new fixed, :314).  Does NOT consume or
+   modify the writer.  host_marks [n_copies][k]; host_out [n_copies][h][w][3] f32 / u8 (into_rgb8).  A consumed writer:
+   SSW_ERR_CONSUMED. */
+int ssw_writer_mark_copies(ssw_writer* wr, const float* host_marks, size_t n_copies, size_t k, float* host_out);
+int ssw_writer_mark_copies_rgb8(ssw_writer* wr, const float* host_marks, size_t n_copies, size_t k, uint8_t* host_out);
+
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,
    and `into_rgb16()` from Rgb32F: round(clamp(v,0,1) * 65535) (`image 0.24.3`, like the 8-bit forms). */

@@ -15,6 +15,7 @@
 // Header-only; link against libssw_hip.so.
 #pragma once
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -221,8 +222,33 @@ public:
         check(ssw_writer_result_rgb8(wr_, out.data.data()), "Writer::mark");
         return out;
     }
+    // Fingerprinting: for every mark what embed(&[&mark_i]) + result() would give on a clone of this writer as it stands
+    // (:348-379, examples/main.rs:266-278 once per recipient).  Does not consume or change the writer; all marks one length.
+    std::vector<ImageRgb32F> mark_copies(const std::vector<const MarkBuf*>& marks) {
+        return copies<ImageRgb32F>(marks, ssw_writer_mark_copies);
+    }
+    std::vector<ImageRgb8> mark_copies_rgb8(const std::vector<const MarkBuf*>& marks) {
+        return copies<ImageRgb8>(marks, ssw_writer_mark_copies_rgb8);
+    }
 
 private:
+    template <class Img, class Fn>
+    std::vector<Img> copies(const std::vector<const MarkBuf*>& marks, Fn fn) {
+        const size_t n = marks.size(), k = n ? marks[0]->data().size() : 0;
+        std::vector<float> m(n * k);
+        for (size_t i = 0; i < n; ++i) {
+            if (marks[i]->data().size() != k) throw Error(SSW_ERR_LENGTH_MISMATCH, "Writer::mark_copies");
+            std::copy(marks[i]->data().begin(), marks[i]->data().end(), m.begin() + i * k);
+        }
+        std::vector<typename decltype(Img::data)::value_type> all(n * w_ * h_ * 3);
+        check(fn(wr_, m.data(), n, k, all.data()), "Writer::mark_copies");
+        std::vector<Img> out;
+        for (size_t i = 0; i < n; ++i) {
+            out.emplace_back(w_, h_);
+            std::copy(all.begin() + i * w_ * h_ * 3, all.begin() + (i + 1) * w_ * h_ * 3, out.back().data.begin());
+        }
+        return out;
+    }
     size_t w_, h_;
     ssw_writer* wr_ = nullptr;
 };

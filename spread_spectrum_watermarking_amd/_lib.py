@@ -109,6 +109,10 @@ SIGNATURES = {
     "ssw_writer_mark": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _sz, _vp]),
     "ssw_writer_result_rgb8": (C.c_int, [_vp, _vp]),
     "ssw_writer_mark_rgb8": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _sz, _vp]),
+    "ssw_fingerprint_embed": (C.c_int, [_vp, _cfgp, _f32p, _sz, _sz, _f32p, _sz, _sz, _f32p, _u32p]),
+    "ssw_fingerprint_embed_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, _f32p, _sz, _sz, _vp, _u32p]),
+    "ssw_writer_mark_copies": (C.c_int, [_vp, _f32p, _sz, _sz, _vp]),
+    "ssw_writer_mark_copies_rgb8": (C.c_int, [_vp, _f32p, _sz, _sz, _vp]),
     "ssw_writer_destroy": (C.c_int, [_vp]),
     "ssw_reader_create": (C.c_int, [_vp, _vp, _sz, _sz, C.c_int, _cfgp, C.POINTER(_vp)]),
     "ssw_reader_create_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.c_int, _cfgp, C.POINTER(_vp)]),

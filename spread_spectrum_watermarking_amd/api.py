@@ -422,6 +422,31 @@ class Writer:
         check(self._lib.ssw_writer_mark_rgb8(self._h, ptrs, lens, len(arrs), out.ctypes.data), "Writer::mark")
         return out
 
+    def _copies(self, marks, out, dtype, fn, what):
+        arrs = [_mark_data(m) for m in marks]
+        if len({a.size for a in arrs}) > 1:
+            raise ValueError("mark_copies: every mark must have the same length")
+        n, k = len(arrs), (arrs[0].size if arrs else 0)
+        m = np.ascontiguousarray(np.stack(arrs) if arrs else np.zeros((0, 0)), dtype=np.float32)
+        shape = (n, self.height, self.width, 3)
+        if out is None:
+            out = np.empty(shape, dtype)
+        elif out.dtype != dtype or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a contiguous {np.dtype(dtype).name} array [N, H, W, 3]")
+        check(fn(self._h, m.ctypes.data, n, k, out.ctypes.data), what)
+        return out
+
+    def mark_copies(self, marks, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Fingerprinting: for every mark m_i what `embed([m_i])` + `result()` would give on a clone of this writer as it
+        stands (algorithm.rs:348-379; the loop of examples/main.rs:266-278 once per recipient) -> f32 [N, H, W, 3].  The
+        shared transform runs once and each copy is a low-rank update on the GPU; the writer is neither consumed nor
+        changed.  All marks must have one length (ValueError otherwise)."""
+        return self._copies(marks, out, np.float32, self._lib.ssw_writer_mark_copies, "Writer::mark_copies")
+
+    def mark_copies_rgb8(self, marks, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """mark_copies quantised like `into_rgb8()` on the device: u8 [N, H, W, 3]."""
+        return self._copies(marks, out, np.uint8, self._lib.ssw_writer_mark_copies_rgb8, "Writer::mark_copies")
+
     def __del__(self):
         try:
             if getattr(self, "_h", None) and self._ctx.handle:

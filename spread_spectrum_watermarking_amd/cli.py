@@ -5,6 +5,10 @@
         -> <stem>_wm.png and <stem>_wm.json next to <file>            (main.rs:240-319)
     python -m spread_spectrum_watermarking_amd.cli test [--similarity-exceed 6.0] <base> <watermarked> <json|wm>...
         -> one YAML-ish record per stored watermark                     (main.rs:346-434)
+    python -m spread_spectrum_watermarking_amd.cli fingerprint <file> --copies N [--length 1000] [--ordering energy]
+            [--alpha 0.1] [--method option2] [-d DESCRIPTION]
+        -> <stem>_fp<i>.png (i zero-padded) and one <stem>_fp.json holding the N marks, described "<desc> #i";
+           `test <file> <stem>_fp<i>.png <stem>_fp.json` then names the copy that leaked
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -50,6 +54,14 @@ def build_parser() -> argparse.ArgumentParser:
     w.add_argument("--method", choices=sorted(_METHOD_ARGS), default="option2", help="Method to insert and extract with.")
     w.add_argument("-d", "--description", default=None, help="Description to associate with the watermark.")
     w.add_argument("-p", dest="print_similarity", action="store_true", help="Show embedded watermark similarity.")
+    f = sub.add_parser("fingerprint", help="Make individually watermarked copies of a file, one mark per recipient.")
+    f.add_argument("file", help="The file to make copies of.")
+    f.add_argument("--copies", type=int, required=True, help="Number of copies (one watermark each).")
+    f.add_argument("--length", type=int, default=1000, help="Watermark length.")
+    f.add_argument("--ordering", choices=sorted(_ORDERING_ARGS), default="energy", help="The ordering to be used.")
+    f.add_argument("--alpha", type=float, default=0.1, help="Strength, alpha in the equations.")
+    f.add_argument("--method", choices=sorted(_METHOD_ARGS), default="option2", help="Method to insert and extract with.")
+    f.add_argument("-d", "--description", default=None, help="Description; copy i is described \"<description> #i\".")
     t = sub.add_parser("test", help="Test if any of the watermarks are present in the watermarked file.")
     t.add_argument("--similarity-exceed", type=float, default=6.0,
                    help="If the similarity exceeds this value it is considered to be matching.")
@@ -89,6 +101,36 @@ def cmd_watermark(args, out=sys.stdout) -> int:
     return 0
 
 
+def fingerprint_paths(image_path: str, copies: int) -> Tuple[List[str], str]:
+    """/tmp/foo.jpg, 12 -> [/tmp/foo_fp00.png .. /tmp/foo_fp11.png], /tmp/foo_fp.json."""
+    stem = os.path.splitext(image_path)[0] + "_fp"
+    digits = len(str(max(copies - 1, 0)))
+    return [f"{stem}{i:0{digits}d}.png" for i in range(copies)], stem + ".json"
+
+
+def cmd_fingerprint(args, out=sys.stdout) -> int:
+    if args.copies < 1:
+        raise SystemExit("--copies must be at least 1")
+    images_out, json_out = fingerprint_paths(args.file, args.copies)
+    for path in images_out + [json_out]:                     # like `watermark` (main.rs:253-265): never overwrite
+        if os.path.exists(path):
+            raise SystemExit(f"{path} file already exists")
+    orig = _open_image(args.file)
+    cfg = Configuration(alpha=args.alpha, method=_METHOD_ARGS[args.method], ordering=_ORDERING_ARGS[args.ordering])
+    marks = [MarkBuf.generate_normal(args.length) for _ in range(args.copies)]
+    # main.rs:266-278 once per recipient, as one call: Writer::new(orig) once, then every copy from the shared transform
+    copies8 = Writer(orig, cfg.to_write_config()).mark_copies_rgb8(marks)
+    from PIL import Image
+    for path, img in zip(images_out, copies8):
+        Image.fromarray(img).save(path)
+    desc = args.description or ""
+    storage = Version1Storage(cfg, [DescribedWatermark(m.data(), f"{desc} #{i}" if desc else f"#{i}") for i, m in enumerate(marks)])
+    with open(json_out, "w") as f:
+        f.write(storage.to_json())
+    print(f"{args.copies} copies: {images_out[0]} .. {images_out[-1]}, marks in {json_out}", file=out)
+    return 0
+
+
 def cmd_test(args, out=sys.stdout) -> int:
     base = _open_image(args.base)
     watermarked = _open_image(args.watermarked)
@@ -117,6 +159,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         return cmd_watermark(args)
     if args.command == "test":
         return cmd_test(args)
+    if args.command == "fingerprint":
+        return cmd_fingerprint(args)
     return 0
 
 

@@ -342,10 +342,15 @@ __device__ inline void load_k4_f64(const double* __restrict__ row, unsigned k, u
     }
 }
 
+// f32 store: the epilogue's rounding and factor (every pass of the transforms); f64 store: the unrounded sum, epilogue
+// ignored (the base plane of the fingerprint update, fingerprint.hip)
+__device__ inline void store_f64_acc(float* out, double acc, const Epilogue& ep, unsigned idx) { *out = apply_epilogue(ep, (float)acc, idx); }
+__device__ inline void store_f64_acc(double* out, double acc, const Epilogue&, unsigned) { *out = acc; }
+
 // Row pass, f64:  OUT[m][n] = sum_k A[m][k] (f32 image) * B[n][k] (f64 basis)
-template <bool ALIGNED>
+template <bool ALIGNED, typename OutT = float>
 __global__ __launch_bounds__(THREADS, 2) void dct_rows_f64_kernel(
-    const float* __restrict__ A, const double* __restrict__ B, float* __restrict__ OUT,
+    const float* __restrict__ A, const double* __restrict__ B, OutT* __restrict__ OUT,
     unsigned M, unsigned N, unsigned K, unsigned Kb, unsigned tiles_m, unsigned tiles_n, Epilogue ep) {
     __shared__ __attribute__((aligned(16))) float ldsA[2][BM * LDK32];
     __shared__ __attribute__((aligned(16))) double ldsB[2][BN * LDK64];
@@ -433,15 +438,15 @@ __global__ __launch_bounds__(THREADS, 2) void dct_rows_f64_kernel(
             for (int r = 0; r < 4; ++r) {
                 const unsigned row = m0 + wm + 16 * i + lq + 4 * r;
                 if (row < M && col < N)
-                    OUT[(size_t)row * N + col] = apply_epilogue(ep, (float)acc[i][jn][r], col);
+                    store_f64_acc(&OUT[(size_t)row * N + col], acc[i][jn][r], ep, col);
             }
         }
 }
 
 // Column pass, f64:  OUT[z][m][n] = sum_k A[m][k] (f64 basis) * B[z][k][n] (f32 image)
-template <bool ALIGNED>
+template <bool ALIGNED, typename OutT = float>
 __global__ __launch_bounds__(THREADS, 2) void dct_cols_f64_kernel(
-    const double* __restrict__ A, const float* __restrict__ Bz, float* __restrict__ OUTz,
+    const double* __restrict__ A, const float* __restrict__ Bz, OutT* __restrict__ OUTz,
     unsigned M, unsigned N, unsigned K, unsigned Kb, unsigned tiles_m, unsigned tiles_n,
     unsigned tiles_per_frame, Epilogue ep) {
     __shared__ __attribute__((aligned(16))) double ldsA[2][BM * LDK64];
@@ -452,7 +457,7 @@ __global__ __launch_bounds__(THREADS, 2) void dct_cols_f64_kernel(
     tile_of_block(blockIdx.x % tiles_per_frame, tiles_per_frame, tiles_m, tiles_n, tm, tn);
     const unsigned m0 = tm * BM, n0 = tn * BN;
     const float* __restrict__ B = Bz + (size_t)z * K * N;
-    float* __restrict__ OUT = OUTz + (size_t)z * M * N;
+    OutT* __restrict__ OUT = OUTz + (size_t)z * M * N;
 
     const unsigned tid = threadIdx.x;
     const unsigned lane = tid & 63, wave = tid >> 6;
@@ -533,7 +538,7 @@ __global__ __launch_bounds__(THREADS, 2) void dct_cols_f64_kernel(
             for (int r = 0; r < 4; ++r) {
                 const unsigned row = m0 + wm + 16 * i + lq + 4 * r;
                 if (row < M && col < N)
-                    OUT[(size_t)row * N + col] = apply_epilogue(ep, (float)acc[i][jn][r], row);
+                    store_f64_acc(&OUT[(size_t)row * N + col], acc[i][jn][r], ep, row);
             }
         }
 }
@@ -601,6 +606,39 @@ int launch_dct_cols(hipStream_t st, int precision, const float* in, float* out, 
         if (al) dct_cols_f32_kernel<true><<<(unsigned)nblk, THREADS, 0, st>>>(b, in, out, M, N, K, Kb, tiles_m, tiles_n, tiles_per_frame, ep);
         else    dct_cols_f32_kernel<false><<<(unsigned)nblk, THREADS, 0, st>>>(b, in, out, M, N, K, Kb, tiles_m, tiles_n, tiles_per_frame, ep);
     }
+    SSW_HIP_CHECK(hipGetLastError());
+    return SSW_OK;
+}
+
+// The f64 passes with an f64 store of the unrounded sums (no epilogue): out [rows][w] / [n_frames][h][w] doubles.
+int launch_dct_rows_f64out(hipStream_t st, const float* in, double* out, size_t rows, size_t w, const double* basis) {
+    if (rows == 0 || w == 0) return SSW_OK;
+    if (rows > 0xFFFFFFFFull || w > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
+    const unsigned M = (unsigned)rows, N = (unsigned)w, K = (unsigned)w, Kb = (unsigned)dense_basis_kpad(w);
+    const unsigned tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+    const unsigned long long nblk = (unsigned long long)tiles_m * tiles_n;
+    if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
+    const Epilogue ep{1.f, 1.f};
+    if ((K % 4 == 0) && aligned16(in) && aligned16(basis))
+        dct_rows_f64_kernel<true, double><<<(unsigned)nblk, THREADS, 0, st>>>(in, basis, out, M, N, K, Kb, tiles_m, tiles_n, ep);
+    else
+        dct_rows_f64_kernel<false, double><<<(unsigned)nblk, THREADS, 0, st>>>(in, basis, out, M, N, K, Kb, tiles_m, tiles_n, ep);
+    SSW_HIP_CHECK(hipGetLastError());
+    return SSW_OK;
+}
+int launch_dct_cols_f64out(hipStream_t st, const float* in, double* out, size_t n_frames, size_t w, size_t h, const double* basis) {
+    if (n_frames == 0 || w == 0 || h == 0) return SSW_OK;
+    if (w > 0xFFFFFFull || h > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
+    const unsigned M = (unsigned)h, N = (unsigned)w, K = (unsigned)h, Kb = (unsigned)dense_basis_kpad(h);
+    const unsigned tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+    const unsigned tiles_per_frame = tiles_m * tiles_n;
+    const unsigned long long nblk = (unsigned long long)tiles_per_frame * n_frames;
+    if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
+    const Epilogue ep{1.f, 1.f};
+    if ((K % 4 == 0) && (N % 4 == 0) && aligned16(in) && aligned16(basis))
+        dct_cols_f64_kernel<true, double><<<(unsigned)nblk, THREADS, 0, st>>>(basis, in, out, M, N, K, Kb, tiles_m, tiles_n, tiles_per_frame, ep);
+    else
+        dct_cols_f64_kernel<false, double><<<(unsigned)nblk, THREADS, 0, st>>>(basis, in, out, M, N, K, Kb, tiles_m, tiles_n, tiles_per_frame, ep);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }

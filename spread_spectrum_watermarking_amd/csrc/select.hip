@@ -27,6 +27,7 @@
 //   ties, constant planes) is handled in the same finish kernel by running the exact select over
 //   the whole plane instead of the candidate list -- slow but exact, and never taken by images.
 #include "ssw_internal.hpp"
+#include "embed_fn.hpp"
 
 #include <atomic>
 
@@ -582,11 +583,7 @@ int launch_topk(hipStream_t st, const float* coef, size_t n_frames, size_t w, si
 // Embed: Writer::embed_watermark (src/algorithm.rs:382-410) with insert functions :414-432.
 // One thread per rank i; indices are unique so there are no write conflicts.
 // ---------------------------------------------------------------------------------------------
-__device__ inline float insert_fn(int method, float alpha, float original, float mark) {
-    if (method == SSW_OPTION1) return original + alpha * mark;              // :414-416
-    if (method == SSW_OPTION2) return original * (1.0f + alpha * mark);     // :420-424
-    return original * expf(alpha * mark);                                   // :428-432
-}
+// insert_fn: embed_fn.hpp (shared with the fingerprint kernels, fingerprint.hip)
 __device__ inline float extract_fn(int method, float alpha, float base, float derived) {
     if (method == SSW_OPTION1) return (derived - base) / alpha;             // :566-572
     if (method == SSW_OPTION2) return (derived - base) / (base * alpha);    // :576-583

@@ -150,6 +150,12 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
                        size_t n_frames, size_t w, size_t h, size_t k, float* dev_extracted, const float* dev_marks,
                        float* dev_sims);
 
+// fingerprint.hip: n_copies copies of one image, each Writer::result of `coef` with its own single mark embedded at `idx`
+// (marks [n_copies][mark_stride]); enqueued on the context's stream; t32: an f32 plane of scratch
+int fingerprint_copies(ssw_ctx* ctx, const ssw_config& c, const float* coef, const uint32_t* idx, size_t k_eff, const float* iq_i,
+                       const float* iq_q, size_t w, size_t h, const float* marks, size_t mark_stride, size_t n_copies, void* out,
+                       bool u8_out, float* t32);
+
 // Reader::extract with a derived frame that is still RGB on the device (single-image handles): pruned transform +
 // extraction enqueued on the context's stream; see ssw_pipeline.hip
 int extract_single_pruned(ssw_ctx* ctx, int precision, const void* derived_rgb, int u8, size_t w, size_t h, const float* base_y,

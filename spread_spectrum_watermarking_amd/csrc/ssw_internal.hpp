@@ -61,6 +61,9 @@ int launch_dct_rows(hipStream_t st, int precision, const float* in, float* out, 
 // Column pass: out[f][u][c] = sum_r basis[u][r] * in[f][r][c].
 int launch_dct_cols(hipStream_t st, int precision, const float* in, float* out, size_t n_frames,
                     size_t w, size_t h, const void* basis, Epilogue ep);
+// The f64 passes with the unrounded sums stored as f64 (no epilogue): the base plane of the fingerprint update
+int launch_dct_rows_f64out(hipStream_t st, const float* in, double* out, size_t rows, size_t w, const double* basis);
+int launch_dct_cols_f64out(hipStream_t st, const float* in, double* out, size_t n_frames, size_t w, size_t h, const double* basis);
 
 // dct_pair_prep.hip / dct_pair_f64.hip: "operand-ready" folded GEMMs in f64 (no VALU work in the MFMA loop): pre-passes
 // write the folded operands once per pass as k-blocked f64 planes, the half bases are cached in the same layout.
@@ -346,6 +349,7 @@ struct ssw_ctx {
     Buf small;                    // misc (mark offsets, sims, ...)
     Buf sort_scratch;             // full-order sort (lazy, Reader::indices beyond the top-k limit)
     Buf resize_tmp;               // f32 intermediate of the resize's vertical pass
+    Buf fingerprint[6];           // fingerprint.hip: line plan (u32) | T64 + gathered basis | Yr64 | mark deltas | dT of a group | handle output
     std::map<std::pair<size_t, size_t>, ssw::DeviceTaps> taps;   // (in_len, out_len) -> filter taps
 
     // timing

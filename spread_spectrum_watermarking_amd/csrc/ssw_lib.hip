@@ -331,6 +331,7 @@ int ssw_ctx_destroy(ssw_ctx* ctx) {
     release(ctx->small);
     release(ctx->sort_scratch);
     release(ctx->resize_tmp);
+    for (auto& b : ctx->fingerprint) release(b);
     for (auto& kv : ctx->taps) { (void)hipFree(kv.second.left); (void)hipFree(kv.second.count); (void)hipFree(kv.second.weights); }
     for (auto& e : ctx->sync_events) (void)hipEventDestroy(e);
     for (auto& p : ctx->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -920,6 +921,51 @@ int ssw_writer_mark_rgb8(ssw_writer* wr, const float* const* marks, const size_t
     if (!out_rgb_hwc) return SSW_ERR_BAD_ARG;
     SSW_TRY(writer_embed_impl(wr, marks, lens, n_marks, false));
     return writer_result_impl(wr, out_rgb_hwc, true);
+}
+
+// Writer::mark_copies: what embed(&[&mark_i]) + result() would give on n clones of the writer as it stands (the current plane,
+// the ordering of the original one), without touching it.  Groups of copies go through a device buffer and are downloaded.
+static int writer_mark_copies_impl(ssw_writer* wr, const float* host_marks, size_t n_copies, size_t k, void* host_out, bool u8_out) {
+    if (!wr || !host_marks || !host_out) return SSW_ERR_BAD_ARG;
+    if (wr->consumed) return SSW_ERR_CONSUMED;
+    if (wr->cfg.precision != SSW_PRECISION_F64) return SSW_ERR_UNSUPPORTED;
+    if (n_copies == 0) return SSW_OK;
+    ssw_ctx* ctx = wr->ctx;
+    CtxGuard g(ctx);
+    const size_t plane = wr->w * wr->h;
+    const size_t k_eff = std::min(k, plane - 1);                      // zip() truncation, :396
+    if (wr->staging_in_flight) {                                      // embed()'s host staging is reused below
+        SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        wr->staging_in_flight = false;
+    }
+    if (k_eff > wr->idx_k) {                                          // :314, from the original coefficients
+        pool_put(ctx, wr->idx, wr->idx_k * sizeof(uint32_t));
+        wr->idx = nullptr; wr->idx_k = 0;
+        SSW_TRY(pool_get(ctx, k_eff * sizeof(uint32_t), (void**)&wr->idx));
+        SSW_TRY(topk0(ctx, wr->y0 ? wr->y0 : wr->y, 1, wr->w, wr->h, wr->cfg.ordering, k_eff, wr->idx));
+        wr->idx_k = k_eff;
+    }
+    const size_t mark_bytes = n_copies * std::max<size_t>(k, 1) * sizeof(float);
+    SSW_TRY(grow(ctx->small, mark_bytes));
+    if (k) SSW_TRY(upload(ctx, ctx->small.p, host_marks, n_copies * k * sizeof(float), ctx->stream));
+    const size_t out_bytes = plane * 3 * (u8_out ? 1 : sizeof(float));
+    const size_t group = std::max<size_t>(1, std::min<size_t>(n_copies, ((size_t)1 << 30) / out_bytes));
+    SSW_TRY(grow(ctx->fingerprint[5], group * out_bytes));
+    SSW_TRY(grow(ctx->lane[0].plane[3], plane * sizeof(float)));
+    for (size_t n0 = 0; n0 < n_copies; n0 += group) {
+        const size_t gn = std::min(group, n_copies - n0);
+        SSW_TRY(fingerprint_copies(ctx, wr->cfg, wr->y, wr->idx, k_eff, wr->i, wr->q, wr->w, wr->h, (const float*)ctx->small.p + n0 * k,
+                                   k, gn, ctx->fingerprint[5].p, u8_out, (float*)ctx->lane[0].plane[3].p));
+        SSW_TRY(download(ctx, static_cast<char*>(host_out) + n0 * out_bytes, ctx->fingerprint[5].p, gn * out_bytes, ctx->stream));
+    }
+    return SSW_OK;
+}
+
+int ssw_writer_mark_copies(ssw_writer* wr, const float* host_marks, size_t n_copies, size_t k, float* host_out) {
+    return writer_mark_copies_impl(wr, host_marks, n_copies, k, host_out, false);
+}
+int ssw_writer_mark_copies_rgb8(ssw_writer* wr, const float* host_marks, size_t n_copies, size_t k, uint8_t* host_out) {
+    return writer_mark_copies_impl(wr, host_marks, n_copies, k, host_out, true);
 }
 
 int ssw_writer_destroy(ssw_writer* wr) {
