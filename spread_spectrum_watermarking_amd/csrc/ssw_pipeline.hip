@@ -945,7 +945,17 @@ int run_pipeline_impl(ssw_ctx* ctx, size_t n_chunks, bool two, const std::functi
         while (next < n_chunks) {
             chain[l].clear();
             at[l] = 0;
+            const size_t bases = ctx->basis.size();
             SSW_TRY(build(next++, ctx->lane[l], chain[l]));
+            if (two && ctx->basis.size() != bases) {
+                // get_basis made a missing table on the context's stream while the chain was built: the stages that run on
+                // the second stream (an RGB pre-pass reads the rotation tables) must not start before it is written
+                hipEvent_t ev = nullptr;
+                SSW_TRY(next_sync_event(ctx, &ev));
+                SSW_HIP_CHECK(hipEventRecord(ev, G));
+                SSW_HIP_CHECK(hipStreamWaitEvent(H, ev, 0));
+                untimed_work(ctx);
+            }
             if (!chain[l].empty()) { active[l] = true; break; }
         }
         return SSW_OK;

@@ -313,3 +313,82 @@ def similarity_matrix(extracted, marks_db):
     for x in (de, dm, out):
         x.free()
     return r
+
+
+def plan_flags(n_frames, w, h, dct_type=L.DCT2):
+    """ssw_ctx_transform_plan as the raw SSW_PLAN_* bits (include/ssw.h)."""
+    f = C.c_uint32()
+    check(lib().ssw_ctx_transform_plan(ctx().handle, n_frames, w, h, dct_type, C.byref(f)), "ssw_ctx_transform_plan")
+    return int(f.value)
+
+
+def fingerprint(rgb, marks, cfg=None, want_idx=False):
+    """ssw_fingerprint_embed(_rgb8) on one frame [h, w, 3] (f32 or u8) and marks [n, k] -> copies [n, h, w, 3]."""
+    u8 = rgb.dtype == np.uint8
+    a = np.ascontiguousarray(rgb)
+    m = np.ascontiguousarray(marks, dtype=np.float32)
+    n, k = m.shape
+    h, w = a.shape[:2]
+    c = cfg or default_config()
+    d, dm = ctx().to_device(a), ctx().to_device(m) if m.size else ctx().alloc(16)
+    out = ctx().alloc(max(n * a.nbytes, 16))
+    idx = ctx().alloc(max(min(k, w * h - 1), 1) * 4) if want_idx else None
+    fn = lib().ssw_fingerprint_embed_rgb8 if u8 else lib().ssw_fingerprint_embed
+    check(fn(ctx().handle, C.byref(c), d.ptr, w, h, dm.ptr, n, k, out.ptr, idx.ptr if idx else None), "ssw_fingerprint_embed")
+    r = out.to_host(np.uint8 if u8 else np.float32, (n, h, w, 3))
+    res = (r, idx.to_host(np.uint32, (min(k, w * h - 1),))) if want_idx else r
+    for b in (d, dm, out, idx):
+        if b:
+            b.free()
+    return res
+
+
+# ---- the project's bars -------------------------------------------------------------------------------------------------
+def f32_stats(got, ref):
+    """(max |got - ref|, fraction bit-identical) of two f32 arrays."""
+    return float(np.abs(got.astype(np.float64) - ref.astype(np.float64)).max()), float(np.mean(got == ref))
+
+
+def assert_f32_bars(got, ref, identical=0.9999, what=""):
+    """Marked f32 frames: max |d| <= 2e-7 and at least `identical` of the values bit-identical."""
+    d = np.abs(got.astype(np.float64) - ref.astype(np.float64))
+    assert d.max() <= 2e-7, (what, d.max())
+    assert np.mean(got == ref) >= identical, (what, np.mean(got == ref))
+
+
+def assert_u8_bars(got, ref, what=""):
+    """8-bit frames: within 1 LSB and >= 99.99 % equal."""
+    d = np.abs(got.astype(np.int32) - ref.astype(np.int32))
+    assert d.max() <= 1, (what, d.max())
+    assert np.mean(d == 0) >= 0.9999, (what, np.mean(d == 0))
+
+
+def ext_within_1e5(ext, ref):
+    """north_star's bar on extracted marks, per element: |ext_i - ref_i| <= 1e-5 * max(1, |ref_i|) (relative f32 where the
+    element is above 1 in magnitude, absolute 1e-5 below -- marks are N(0, 1) samples, so most elements are below 1)."""
+    ext, ref = np.asarray(ext, np.float64), np.asarray(ref, np.float64)
+    return bool(np.all(np.abs(ext - ref) <= 1e-5 * np.maximum(1.0, np.abs(ref))))
+
+
+# ---- the oracle's frame flows, step by step ------------------------------------------------------------------------------
+# oracle.embed_frame / extract_frame redo the forward transform on every call; at 100 M pixels and more a test shares each
+# frame's forward plane and index list instead.  tests/test_oracle_golden.py pins these against the one-call flows.
+def oracle_forward(rgb):
+    """Writer::new / Reader::base|derived (algorithm.rs:308-313, :476-480): (DCT-II of Y, I, Q)."""
+    from oracle import oracle as O
+    y, i, q = O.rgb_to_yiq(rgb)
+    return O.dct2d(y), i, q
+
+
+def oracle_marked(coef, i, q, idx, mark, method=L.OPTION2, alpha=0.1):
+    """Writer::embed_watermark + Writer::result (algorithm.rs:356-377) on a forward plane and its index list."""
+    from oracle import oracle as O
+    y = O.dct2d(O.embed(coef, idx, [mark], method, alpha), O.DCT3)
+    return O.yiq_to_rgb(y, i, q)
+
+
+def oracle_extracted(base_coef, derived_coef, idx, mark, method=L.OPTION2, alpha=0.1):
+    """Reader::extract_watermark + Tester::similarity (algorithm.rs:529-561, :696-714): (extracted, similarity)."""
+    from oracle import oracle as O
+    ext = O.extract(base_coef, derived_coef, idx, len(mark), method, alpha)
+    return ext, O.similarity(ext, mark)

@@ -14,7 +14,7 @@ import spread_spectrum_watermarking_amd as wm
 from conftest import GOLDEN, ROOT
 from oracle import oracle as O
 from spread_spectrum_watermarking_amd import _lib as L
-from spread_spectrum_watermarking_amd.api import check
+from gpu_util import assert_f32_bars, assert_u8_bars, fingerprint
 
 pytestmark = pytest.mark.gpu
 
@@ -24,40 +24,6 @@ OPTION3_MARKED_IDENTICAL = 0.82          # tests/test_config_matrix_gpu.py: devi
 # marked frames against the oracle at 4K: the bar ssw_batch_embed's own 4K parity test holds (tests/test_gpu_parity.py, > 0.999;
 # measured 0.99985 for copy 0 here); against ssw_batch_embed the full 0.9999
 ORACLE_4K_IDENTICAL = 0.999
-
-
-def fingerprint(rgb, marks, cfg=None, want_idx=False):
-    """ssw_fingerprint_embed(_rgb8) on one frame [h, w, 3] (f32 or u8) and marks [n, k] -> copies [n, h, w, 3]."""
-    u8 = rgb.dtype == np.uint8
-    a = np.ascontiguousarray(rgb)
-    m = np.ascontiguousarray(marks, dtype=np.float32)
-    n, k = m.shape
-    h, w = a.shape[:2]
-    c = cfg or G.default_config()
-    ctx = G.ctx()
-    d, dm = ctx.to_device(a), ctx.to_device(m) if m.size else ctx.alloc(16)
-    out = ctx.alloc(max(n * a.nbytes, 16))
-    idx = ctx.alloc(max(min(k, w * h - 1), 1) * 4) if want_idx else None
-    fn = G.lib().ssw_fingerprint_embed_rgb8 if u8 else G.lib().ssw_fingerprint_embed
-    check(fn(ctx.handle, C.byref(c), d.ptr, w, h, dm.ptr, n, k, out.ptr, idx.ptr if idx else None), "ssw_fingerprint_embed")
-    r = out.to_host(np.uint8 if u8 else np.float32, (n, h, w, 3))
-    res = (r, idx.to_host(np.uint32, (min(k, w * h - 1),))) if want_idx else r
-    for b in (d, dm, out, idx):
-        if b:
-            b.free()
-    return res
-
-
-def assert_f32_bars(got, ref, identical=0.9999, what=""):
-    d = np.abs(got.astype(np.float64) - ref.astype(np.float64))
-    assert d.max() <= 2e-7, (what, d.max())
-    assert np.mean(got == ref) >= identical, (what, np.mean(got == ref))
-
-
-def assert_u8_bars(got, ref, what=""):
-    d = np.abs(got.astype(np.int32) - ref.astype(np.int32))
-    assert d.max() <= 1, (what, d.max())
-    assert np.mean(d == 0) >= 0.9999, (what, np.mean(d == 0))
 
 
 def marks_for(n, k, seed):

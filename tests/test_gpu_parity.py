@@ -31,12 +31,7 @@ F32, F64 = L.PRECISION_F32, L.PRECISION_F64
 PRECISIONS = [F64]
 
 
-def _ext_within_1e5(ext, ref):
-    """north_star's bar on extracted marks, per element: |ext_i - ref_i| <= 1e-5 * max(1, |ref_i|) (relative f32 where the
-    element is above 1 in magnitude, absolute 1e-5 below -- marks are N(0, 1) samples, so most elements are below 1)."""
-    ext, ref = np.asarray(ext, np.float64), np.asarray(ref, np.float64)
-    return bool(np.all(np.abs(ext - ref) <= 1e-5 * np.maximum(1.0, np.abs(ref))))
-
+_ext_within_1e5 = G.ext_within_1e5
 
 
 def ac_max(plane):

@@ -230,3 +230,21 @@ def test_seed1_mark_is_the_one_in_the_reference_png(marks, cat_images):
     assert abs(O.similarity(ext, marks["seed_2"])) < 3.0
     assert abs(O.similarity(ext, marks["seed_baaaaaad"])) < 3.0
     assert 30.0 < np.linalg.norm(ext) < 34.0        # sqrt(X*.X*) of an N(0,1) mark of length 1000
+
+
+@pytest.mark.parametrize("w, h", [(320, 176), (144, 264)], ids=["landscape", "portrait"])
+@pytest.mark.parametrize("conf", [(O.ORDER_ENERGY, O.OPTION2, 0.1), (O.ORDER_LEGACY, O.OPTION3, 0.3)], ids=["default", "legacy-o3"])
+def test_step_by_step_flows_equal_the_one_call_flows(w, h, conf):
+    """tests/gpu_util.py composes embed_frame / extract_frame from their steps so that the huge-frame tests
+    (tests/test_limits_gpu.py) run each forward transform and index list once: the composition is the same flow, bit for bit."""
+    import gpu_util as G
+    ordering, method, alpha = conf
+    rgb = O.synth_frame(9, w, w, h)
+    mark = np.random.default_rng(w).standard_normal(300).astype(np.float32)
+    coef, i, q = G.oracle_forward(rgb)
+    idx = O.indices(coef, ordering, k=mark.size)
+    marked = G.oracle_marked(coef, i, q, idx, mark, method, alpha)
+    assert np.array_equal(marked, O.embed_frame(rgb, mark, ordering=ordering, method=method, alpha=alpha))
+    ext, sim = G.oracle_extracted(coef, G.oracle_forward(marked)[0], idx, mark, method, alpha)
+    ref_ext, ref_sim = O.extract_frame(rgb, marked, mark, ordering=ordering, method=method, alpha=alpha)
+    assert np.array_equal(ext, ref_ext) and sim == ref_sim
