@@ -1,6 +1,7 @@
 // Shared by the operand-ready GEMMs (dct_pair_f64.hip) and their pre-passes (dct_pair_prep.hip).
 #pragma once
 #include "dct_common.hpp"
+#include "dct_pair_class.hpp"
 
 namespace ssw {
 
@@ -20,29 +21,7 @@ __host__ __device__ inline size_t blk_index(size_t line, unsigned k, size_t rows
     return ((size_t)(k / KB) * rows + line) * KB + (k % KB);
 }
 
-// Epilogues.  n = transform length, idx = output index along the transformed axis:
-//   EPI_FWD    out[c1 + cs pair] = acc1, out[c2 + cs pair] = acc2          (forward, any folding level)
-//   EPI_FWD_ADJ  the same with c1 = 0, c2 = 1, cs = 2 on a row pass: one 8-byte store
-//   EPI_INV    out[pair] = acc1 + acc2, out[n-1-pair] = acc1 - acc2        (inverse, one level)
-//   EPI_INV_E  T[pair] = acc1 + acc2, T[n/2-1-pair] = acc1 - acc2, unrounded (inverse level 2: the even half E)
-//   EPI_INV_O  with n1 = pair, n2 = pair + n/4:  out[n1] = T[n1] + acc1, out[n-1-n1] = T[n1] - acc1,
-//              out[n2] = T[n2] + acc2, out[n-1-n2] = T[n2] - acc2          (inverse level 2: odd part + combine)
-//   EPI_INV_O_RGB  EPI_INV_O on the last pass of Writer::result (a column pass): instead of storing the Y sample it
-//              converts (Y, I, Q) of that pixel to RGB like From<&YIQ32FImage> for Rgb32FImage (src/yiq.rs:187-197:
-//              (y + m1 i) + m2 q per channel, clamped to [0, 1]) and stores the interleaved pixel -- f32, or
-//              8-bit like into_rgb8() (round(clamp * 255)).  The colour conversion's HBM traffic (I, Q in, RGB out)
-//              then runs in the shadow of the other resident block's MFMAs and the Y plane is never written.
-//   EPI_INV_OT EPI_INV_O one level down (deep inverse): the odd part of the half-length transform E combined with ITS even
-//              half T2 (`tmp`, length n/2 per line) into E itself, unrounded: T[n1] = T2[n1] + acc, T[n-1-n1] = T2[n1] - acc
-//              (`tmp_out`, length n per line; n = the half-length transform's length)
-//   EPI_FWD_COLOP (r5; forward ROW pass of a rows-first transform whose two passes run at level 2, f64): EPI_FWD's values --
-//              rounded to f32 like the store between the passes (src/dct2d.rs:152-168), then the f32 per-index factor --
-//              are not stored: the operand lines are ordered (frame, unit of the column fold, line of the unit), a 16-line
-//              MFMA tile holds the sixteen rows of one unit, and the epilogue applies the column pre-pass's arithmetic
-//              (dct_pair_colops.hpp: col_l2_unit) to them and stores the sixteen k-blocked COLUMN operand planes directly.
-//              No f32 plane between the passes, no column pre-pass: 16 B/px of HBM traffic less per forward transform.
-enum { EPI_FWD = 0, EPI_FWD_ADJ = 1, EPI_INV = 2, EPI_INV_E = 3, EPI_INV_O = 4, EPI_INV_O_RGB = 5, EPI_INV_OT = 6, EPI_FWD_COLOP = 7 };
-
+// (the epilogues EPI_*: dct_pair_class.hpp)
 template <typename T>
 struct PairOutT {
     float* out;          // f32 plane(s)
@@ -274,8 +253,7 @@ __device__ inline void pair_store_rgb_quad(const PairOutT<T>& po, size_t px, con
 }
 
 // row stride (in doubles) of the operand planes / half bases of a length-n axis: n/2 rounded up to whole k-steps of 8, at
-// least two of them; the GEMM has a compile-time variant of its tile body for odd counts (135 -> 136 instead of 144 at 4K
-// columns)
+// least two of them (the GEMM's ring takes any number of k-steps >= 2: 135 -> 136 at 4K columns)
 inline size_t pair_kpad(size_t n) {
     const size_t m = KBlock<double>::KB, k = ((n / 2 + m - 1) / m) * m;
     return k < 2 * m ? 2 * m : k;

@@ -3,12 +3,6 @@
 // 4.5 minutes to compile), or all of them in dct_pair_f64.hip in the -DSSW_TILE_TRACE diagnostic build (SSW_INV_PART -1).
 namespace ssw {
 
-#define SSW_LAUNCH_PAIR_BM(COLS, EPI, SAMEX, SUBV, BMV) \
-        pair_gemm_f64_kernel<COLS, EPI, SAMEX, SUBV, BMV><<<(unsigned)nblk, PT, 0, st>>>(ml, ep)
-#define SSW_LAUNCH_PAIR_SUB(COLS, EPI, SAMEX, SUBV) do { if (small) SSW_LAUNCH_PAIR_BM(COLS, EPI, SAMEX, SUBV, 64); else SSW_LAUNCH_PAIR_BM(COLS, EPI, SAMEX, SUBV, 128); } while (0)
-#define SSW_LAUNCH_PAIR(COLS, EPI, SAMEX) do { if (inst.subname == 0) SSW_LAUNCH_PAIR_SUB(COLS, EPI, SAMEX, 0); else SSW_LAUNCH_PAIR_SUB(COLS, EPI, SAMEX, 1); } while (0)
-#define SSW_LAUNCH_ROWCOL(EPI, SAMEX) do { if (is_row) SSW_LAUNCH_PAIR(false, EPI, SAMEX); else SSW_LAUNCH_PAIR(true, EPI, SAMEX); } while (0)
-
 int launch_pair_gemm_inverse_part1(hipStream_t st, const PairMulti& ml, Epilogue ep, const PairInstance& inst, bool is_row, bool small,
                                    unsigned long long nblk);
 int launch_pair_gemm_inverse_part2(hipStream_t st, const PairMulti& ml, Epilogue ep, const PairInstance& inst, bool is_row, bool small,
@@ -63,10 +57,5 @@ int launch_pair_gemm_inverse_part3(hipStream_t st, const PairMulti& ml, Epilogue
     return SSW_OK;
 }
 #endif
-
-#undef SSW_LAUNCH_ROWCOL
-#undef SSW_LAUNCH_PAIR
-#undef SSW_LAUNCH_PAIR_SUB
-#undef SSW_LAUNCH_PAIR_BM
 
 }  // namespace ssw

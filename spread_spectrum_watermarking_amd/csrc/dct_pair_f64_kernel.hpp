@@ -6,12 +6,11 @@
 // Measured on MI355X (tools/mfma_peak.hip): v_mfma_f64_16x16x4_f64 sustains 77.6 TFLOP/s when the
 // wave issues nothing else, but every VALU instruction issued next to it takes MFMA pipe time --
 // ~6 cycles for a 32-bit op, ~11.5 cycles for v_cvt_f64_f32 / v_add_f64 -- even from another wave
-// of the same SIMD.  Folding inside the GEMM kernel (r1, retired; HISTORY) spent one f64 VALU op per
-// MFMA (widen + add/subtract after the LDS read) and topped out at 81 % of peak for that reason.
+// of the same SIMD: one f64 VALU op per MFMA costs 16 % of the pipe.
 //
-// Here the GEMM main loop contains no VALU instruction at all: global_load -> ds_write ->
-// ds_read -> MFMA, with scalar address arithmetic.  Its operands are produced once per pass by
-// HBM-bound pre-passes (dct_pair_prep.hip) in exactly the form the MFMA consumes:
+// Here the GEMM main loop is DMA -> ds_read -> MFMA with scalar k-offsets: no VALU instruction except four address adds
+// per k-step.  Its operands are produced once per pass by HBM-bound pre-passes (dct_pair_prep.hip) in exactly the form the
+// MFMA consumes:
 //   forward:  S[s] = (double)x[s] + (double)x[N-1-s],  D[s] = (double)x[s] - (double)x[N-1-s]
 //   inverse:  E[s] = (double)c[2s],                    O[s] = (double)c[2s+1]
 // stored k-blocked: [Kp / 8][lines][8] doubles (zero padded to Kp), i.e. the 64-byte piece of every
@@ -24,15 +23,20 @@
 // forward interleaves (even, odd) frequencies; inverse forms acc1 +/- acc2 for the mirrored
 // positions; results are rounded once to f32 (then the reference's f32 scale factor, if any).
 //
-// r3: the odd halves are split once more (dct_pair_prep.hip, "Split odd half"): their launches feed this kernel two
+// The odd halves are split once more (dct_pair_prep.hip, "Split odd half"): their launches feed this kernel two
 // DIFFERENT image operands (the rotated and folded AS | BD or AD | BS) against quarter-length cosine / sine bases and
 // the epilogues emit acc1 +/- acc2 (po.pm); a deep inverse adds EPI_INV_OT (the half-length even half E from its own
 // even half T2 and odd part).  Row passes store through buffer instructions with per-tile lane offsets (epilogue notes
-// below); deep transforms keep the plane between their passes class-major (dct_pair_common.hpp).
+// below); deep transforms keep the plane between their passes class-major (dct_pair_common.hpp).  What a launch class
+// is -- pairs, sum length, output map, template instance -- is one row of the table in dct_pair_class.hpp.
 //
 // Block: 256 threads = 4 waves as 2 x 2; block tile 128 lines x 64 pairs x 2 products; k-step 8;
-// per wave 16 MFMA 16x16 tiles = 128 accumulator registers; LDS 48 KB double-buffered (XOR-swizzled
-// 64-byte rows, conflict-free ds_read_b64 / ds_read2_b64), one barrier per k-step, 2 blocks per CU.
+// per wave 16 MFMA 16x16 tiles = 128 accumulator registers; 2 blocks per CU.  The operand tiles arrive by LDS-DMA
+// (buffer_load ... lds, 16 bytes per lane) in a ring of two 24-KB stages [X1 | X2 | Y1 | Y2] = 48 KB of LDS, one k-step
+// ahead of the MFMAs; the swizzle sits on the lanes' source addresses (chunk c of tile row r lands at c ^ ((r >> 2) & 3):
+// conflict-free ds_read_b64 fragment reads).  In the middle of k-step t a wave waits for its own DMA of stage t + 1 and its
+// last fragment reads of stage t, passes one raw s_barrier, and re-requests stage t for k-step t + 2; any number of
+// k-steps >= 2.
 // Lane l: li = l & 15 (line / pair inside a 16x16 tile), lq = l >> 4: in half-step s lane group lq
 // supplies k = 4 s + lq (the same assignment on both operands).
 #include "dct_pair_common.hpp"
@@ -69,17 +73,11 @@ typedef PairOutT<double> PairOut;
 // SUB only names the instance (launches that serve a deeper folding level show up separately in profiles).
 // BM: lines per block tile.  128 is the tile of every large launch; 64 serves launches whose 128-line grid
 // would leave the chip half empty (a single 4K frame: 17 x 15 = 255 tiles for 512 block slots).
-// One launch serves up to five "classes" -- GEMMs of the same kind (template instance) over the same lines with their own
+// One launch serves up to eight "classes" (dct_pair_class.hpp) -- GEMMs of the same template instance over the same lines with their own
 // operands, bases, pair counts, sum lengths and output maps: the tile columns of the classes lie side by side in the
 // launch's tile grid.  Batch launches carry one class; the five launches of a deep forward pass (two or three of an
 // inverse pass) of a single frame are merged into one, because each alone fills half of the chip's block slots for one
 // round (a 4K frame's class E: 34 x 8 = 272 blocks of 64 lines for 512 slots).
-struct PairClassArgs {
-    const double *x1, *x2, *y1, *y2;
-    unsigned NP, Kp, yrows, tiles_n;
-    unsigned c1, c2, cs, pm, np1, p2lo, bn32, fold0;
-    unsigned gsh, e2off;               // forward class-major output map (PairOutT::ft)
-};
 struct PairMulti {
     PairClassArgs c[8];
     unsigned n_classes, L, tiles_m, tiles_n_total;
@@ -1072,11 +1070,14 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
 #endif
 }
 
-// what selects the template instance of a class: all classes of a launch must agree
-struct PairInstance {
-    int epi; bool samex; int subname;
-    bool operator==(const PairInstance& o) const { return epi == o.epi && samex == o.samex && subname == o.subname; }
-};
+// Launch one of the template instances; in scope: st, ml, ep, nblk, and (below SSW_LAUNCH_PAIR_BM) `small` = 64-line tiles,
+// (below SSW_LAUNCH_PAIR_SUB) inst.subname, (SSW_LAUNCH_ROWCOL) is_row.
+#define SSW_LAUNCH_PAIR_BM(COLS, EPI, SAMEX, SUBV, BMV) \
+        pair_gemm_f64_kernel<COLS, EPI, SAMEX, SUBV, BMV><<<(unsigned)nblk, PT, 0, st>>>(ml, ep)
+#define SSW_LAUNCH_PAIR_SUB(COLS, EPI, SAMEX, SUBV) do { if (small) SSW_LAUNCH_PAIR_BM(COLS, EPI, SAMEX, SUBV, 64); else SSW_LAUNCH_PAIR_BM(COLS, EPI, SAMEX, SUBV, 128); } while (0)
+#define SSW_LAUNCH_PAIR(COLS, EPI, SAMEX) do { if (inst.subname == 0) SSW_LAUNCH_PAIR_SUB(COLS, EPI, SAMEX, 0); else SSW_LAUNCH_PAIR_SUB(COLS, EPI, SAMEX, 1); } while (0)
+#define SSW_LAUNCH_ROWCOL(EPI, SAMEX) do { if (is_row) SSW_LAUNCH_PAIR(false, EPI, SAMEX); else SSW_LAUNCH_PAIR(true, EPI, SAMEX); } while (0)
+
 // the inverse instances (dct_pair_f64_inv.hip)
 int launch_pair_gemm_inverse_instances(hipStream_t st, const PairMulti& ml, Epilogue ep, const PairInstance& inst, bool is_row, bool small,
                                        unsigned long long nblk);

@@ -342,10 +342,10 @@ int fingerprint_copies(ssw_ctx* ctx, const ssw_config& c, const float* coef, con
     double* dt = (double*)ctx->fingerprint[4].p;
 
     const void *inv_w, *inv_h, *fwd_a, *fwd_b;
-    SSW_TRY(get_basis(ctx, w, true, true, 0, &inv_w));
-    SSW_TRY(get_basis(ctx, h, true, true, 0, &inv_h));
-    SSW_TRY(get_basis(ctx, la, false, true, 0, &fwd_a));
-    SSW_TRY(get_basis(ctx, lb, false, true, 0, &fwd_b));
+    SSW_TRY(get_basis(ctx, w, true, true, BasisKind::Dense, &inv_w));
+    SSW_TRY(get_basis(ctx, h, true, true, BasisKind::Dense, &inv_h));
+    SSW_TRY(get_basis(ctx, la, false, true, BasisKind::Dense, &fwd_a));
+    SSW_TRY(get_basis(ctx, lb, false, true, BasisKind::Dense, &fwd_b));
     const size_t kp_a = dense_basis_kpad(la), kp_b = dense_basis_kpad(lb);
     const unsigned W = (unsigned)w;
     {

@@ -82,8 +82,8 @@ int flush_timers(ssw_ctx* ctx);
 // billed for it (a lane's hop to the other stream is a hipStreamWaitEvent: shared, it counted the dependency stall as stage time).
 inline void untimed_work(ssw_ctx* ctx) { if (ctx) ctx->tail_fresh = false; }
 
-// kind 0 = dense N x N, 1 / 2 = even / odd half basis, 3 / 4 = the same, k-blocked (operand-ready GEMMs)
-int get_basis(ssw_ctx* ctx, size_t n, bool inverse, bool f64, int kind, const void** out);
+// the cached basis `kind` of a length-n axis (made on first use); every kind but Dense is f64
+int get_basis(ssw_ctx* ctx, size_t n, bool inverse, bool f64, BasisKind kind, const void** out);
 
 bool valid_method(int m);
 bool valid_ordering(int o);

@@ -14,6 +14,7 @@
 
 #include "../../include/ssw.h"
 #include "dct_plan.hpp"
+#include "dct_pair_class.hpp"
 
 namespace ssw {
 
@@ -106,9 +107,9 @@ int launch_dct_pair_prep8_cols(hipStream_t st, const float* in, size_t n_frames,
 //   FUSE_COLS        column launch behind such a row pass: its 128-line tiles are in the row launches' class-major order
 enum { FUSE_ROWS_COP = 1, FUSE_COLS = 2 };
 struct FuseCols { int mode = 0; double* cop = nullptr; const double *rot1 = nullptr, *rot2 = nullptr, *rot3 = nullptr; };
-// one or several classes (same lines, same template instance) in one launch: kind 0 one folding level, 1 / 2 the even / odd
-// half of two levels, sub: see dct_pair_f64.hip; sink (last inverse column pass): colour conversion in the epilogue
-struct PairClassDesc { int kind, sub; const double *x1, *x2, *y1, *y2; };
+// one or several classes (same lines, same template instance) in one launch: the class (dct_pair_class.hpp) with its operand
+// and basis planes; sink (last inverse column pass): colour conversion in the epilogue
+struct PairClassDesc { PairClass cls; const double *x1, *x2, *y1, *y2; };
 int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, int n_classes, const PairClassDesc* desc, float* out,
                                    double* tmp, size_t n_frames, size_t w, size_t h, Epilogue ep, const RgbSink* sink = nullptr,
                                    double* tmp_out = nullptr, const PairLayout& layout = PairLayout(), const FuseCols* fuse = nullptr);
@@ -270,9 +271,8 @@ struct ssw_ctx {
     hipStream_t own_stream = nullptr;   // private non-blocking stream created with the context
     size_t chunk_frames = 0;      // frames per internal pass; 0 = automatic (~2^28 pixels)
 
-    // basis cache: (N, inverse, f64, kind) -> device pointer; kind 0 = dense N x N (f32 or f64), 3 / 4 = even / odd half basis
-    // (N/2 x N/2, k-blocked: operand-ready GEMMs), 5.. = split odd half and rotation tables (get_basis); kinds >= 3 are f64
-    std::map<std::tuple<size_t, bool, bool, int>, void*> basis;
+    // basis cache: (N, inverse, f64, kind) -> device pointer (get_basis; every kind but Dense is f64)
+    std::map<std::tuple<size_t, bool, bool, ssw::BasisKind>, void*> basis;
     bool fold = true;             // use the even/odd-folded GEMMs where the shape allows
     int fold_level = SSW_DCT_FOLDING_DEFAULT;           // 1 / 2: dense; 3: operand-ready GEMMs (dct_pair_*.hip, f64 only);
                                   // 4: two levels; 5: + a third on long forward row passes; 6: on all

@@ -184,26 +184,26 @@ int flush_timers(ssw_ctx* ctx) {
 }
 
 // Bases are generated on the context's stream, the stream every GEMM launch uses.
-int get_basis(ssw_ctx* ctx, size_t n, bool inverse, bool f64, int kind, const void** out) {
+int get_basis(ssw_ctx* ctx, size_t n, bool inverse, bool f64, BasisKind kind, const void** out) {
+    typedef BasisKind B;
     auto key = std::make_tuple(n, inverse, f64, kind);
     auto it = ctx->basis.find(key);
     if (it != ctx->basis.end()) { *out = it->second; return SSW_OK; }
     void* p = nullptr;
-    // kind 0: the dense basis (f32 or f64).  f64 only: 3 / 4 the even / odd half basis, k-blocked; 5..8 the split odd half
-    // bases (cosE, sinE, cosO, sinO), 9 the rotation table, 10 sinE for the launches (row 0 = row n/8: class E's first and
-    // last pair share a slot)
-    if (kind != 0 && (kind < 3 || !f64)) return SSW_ERR_BAD_ARG;
-    const int split_which = kind == 10 ? 4 : kind - 5;
-    const size_t elems = kind == 0 ? n * dense_basis_kpad(n)
-                       : kind == 9 ? n / 2
-                       : kind >= 5 ? dct_pair_split_basis_rows(n, split_which) * dct_pair_split_kpad(n)
-                                   : (n / 2) * dct_pair_kpad(n);
+    if (kind != B::Dense && !f64) return SSW_ERR_BAD_ARG;
+    const bool half = kind == B::HalfEven || kind == B::HalfOdd, rot = kind == B::Rot;
+    // the split bases as dct_pair_prep.hip numbers them: cosE, sinE, cosO, sinO, and sinE for the launches
+    const int split_which = kind == B::SinELaunch ? 4 : (int)kind - (int)B::CosE;
+    const size_t elems = kind == B::Dense ? n * dense_basis_kpad(n)
+                       : rot  ? n / 2
+                       : half ? (n / 2) * dct_pair_kpad(n)
+                              : dct_pair_split_basis_rows(n, split_which) * dct_pair_split_kpad(n);
     SSW_ALLOC(&p, std::max<size_t>(elems, 1) * (f64 ? sizeof(double) : sizeof(float)));
-    int rc = kind == 9 ? launch_make_rot_table(ctx->stream, n, (double*)p)
-             : kind >= 5 ? launch_make_split_basis_blocked(ctx->stream, n, inverse, split_which, (double*)p)
-             : kind >= 3 ? launch_make_half_basis_blocked(ctx->stream, n, inverse, kind - 3, (double*)p)
-             : f64     ? launch_make_basis_f64(ctx->stream, n, inverse, (double*)p)
-                       : launch_make_basis_f32(ctx->stream, n, inverse, (float*)p);
+    int rc = rot  ? launch_make_rot_table(ctx->stream, n, (double*)p)
+             : half ? launch_make_half_basis_blocked(ctx->stream, n, inverse, kind == B::HalfOdd ? 1 : 0, (double*)p)
+             : kind != B::Dense ? launch_make_split_basis_blocked(ctx->stream, n, inverse, split_which, (double*)p)
+             : f64  ? launch_make_basis_f64(ctx->stream, n, inverse, (double*)p)
+                    : launch_make_basis_f32(ctx->stream, n, inverse, (float*)p);
     untimed_work(ctx);
     if (rc != SSW_OK) { (void)hipFree(p); return rc; }
     ctx->basis[key] = p;
@@ -274,19 +274,6 @@ size_t effective_chunk(const ssw_ctx* ctx, size_t w, size_t h, size_t n_frames) 
 namespace {
 
 bool aligned_planes(const float* a, const float* b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0; }
-PairClassDesc D(int kind, int sub, const void* x1, const void* x2, const void* y1, const void* y2) {
-    return {kind, sub, (const double*)x1, (const double*)x2, (const double*)y1, (const double*)y2};
-}
-// executed flop of one launch of the operand-ready GEMM (two products of lines x pairs x K multiply-adds)
-double pair_gemm_flop(bool is_row, int kind, int sub, size_t n, size_t w, size_t h) {
-    const double lines = (double)(is_row ? n * h : n * w);
-    const size_t leff = (is_row ? w : h) >> sub;
-    if (kind == 3 || kind == 4) return 4.0 * lines * (double)(leff / 8) * (double)(leff / 8);      // class E: n/8 + 1 pairs in n/8 slots
-    if (kind >= 5) return 4.0 * lines * (double)(leff / 16) * (double)(leff / 16);                  // level 2: sums of len/16 terms, len/16 pairs
-    const double np = (double)(kind == 0 ? leff / 2 : leff / 4), k = (double)(kind == 1 ? leff / 4 : leff / 2);
-    return 4.0 * lines * np * k;
-}
-
 // What the builders of a pass share: the pass, its plan and what both its stages account.  Held by value in the stages.
 struct PassBuild {
     ssw_ctx* ctx; Xform x; PassPlan p;
@@ -299,7 +286,7 @@ struct PassBuild {
     // f32 result out -- or, in the last pass of Writer::result, I and Q in and the RGB frame out -- plus `xch` bytes per
     // pixel that the dependent launches of an inverse pass write and read back as doubles (A1: 1 + 1, T2: 2 + 2, E: 4 + 4)
     double gemm_bytes(double xch) const { return px * (8.0 + xch + out_bpp); }
-    double flop(int kind, int sub) const { return pair_gemm_flop(is_row, kind, sub, n, w, h); }
+    double flop(PairClass c) const { return pair_class_flop(c, lines, len); }      // executed flop of one launch of class c
     // the row launches write the plane between the passes class-major; the column launches read operands of their own
     PairLayout gemm_layout() const { return is_row ? p.layout : PairLayout(); }
     int gemm(hipStream_t st, int nc, const PairClassDesc* d, double* tmp = nullptr, double* tmp_out = nullptr, const RgbSink* sink = nullptr,
@@ -334,51 +321,83 @@ RgbSink rgb_sink(const PassBuild& b, bool* fused_rgb) {
     return sink;
 }
 
-// the operands and bases every pair strategy uses: the k-blocked half bases of the whole length and, with the split, its
-// quarter-length cosine / sine bases, the rotation table and the lane's sixth operand buffer (planes K8 / K16 wide)
-struct PairBases {
-    size_t bytes = 0, p8 = 0, p16 = 0;
-    const void *b0 = nullptr, *b1 = nullptr, *sb[4] = {}, *rot = nullptr;
-    double* sp = nullptr;
-    PairClassDesc e() const { return D(3, 0, sp, sp + p8, sb[0], sb[1]); }                // the split odd half: AS x cosE, BD x sinE
-    PairClassDesc o() const { return D(4, 0, sp + 2 * p8, sp + 3 * p8, sb[2], sb[3]); }   // AD x cosO, BS x sinO
-    PairClassDesc r1(const void* e0, const void* e1) const { return D(1, 1, sp + 4 * p8, sp + 5 * p8, e0, e1); }   // c[8q] | c[8q+4]
-};
-int pair_bases(const PassBuild& b, ssw_ctx::Lane& ws, PairBases& pb) {
-    ssw_ctx* ctx = b.ctx;
-    pb.bytes = dct_pair_operand_elems(b.n, b.w, b.h) * sizeof(double);
-    SSW_TRY(get_basis(ctx, b.len, b.inverse, true, 3, &pb.b0));        // k-blocked half bases
-    SSW_TRY(get_basis(ctx, b.len, b.inverse, true, 4, &pb.b1));
-    if (!b.p.split) return SSW_OK;
-    for (int i = 0; i < 4; ++i) SSW_TRY(get_basis(ctx, b.len, b.inverse, true, i == 1 ? 10 : 5 + i, &pb.sb[i]));      // 10: sinE for launches
-    SSW_TRY(get_basis(ctx, b.len, false, true, 9, &pb.rot));
-    SSW_TRY(grow(ws.operand[5], split_scratch_elems(b.n, b.w, b.h) * sizeof(double)));
-    pb.sp = (double*)ws.operand[5].p;
-    pb.p8 = b.lines * dct_pair_split_kpad(b.len);
-    pb.p16 = b.lines * dct_pair_split_kpad(b.len / 2);
+// The launch descriptor of class `c` over a length-`len` axis: the operand planes are the caller's, the cached bases the
+// class table's (a shared operand's second product reads the second row block of the same basis plane: `pairs` lines further
+// inside every k-block = 64 bytes per line).
+int class_desc(ssw_ctx* ctx, size_t len, bool inverse, PairClass c, const double* x1, const double* x2, PairClassDesc& d) {
+    const PairClassRow& r = pair_class_row(c);
+    const void *y1 = nullptr, *y2 = nullptr;
+    SSW_TRY(get_basis(ctx, len / r.ydiv, inverse, true, r.y1, &y1));
+    if (r.samex) y2 = (const char*)y1 + (len / r.ldiv / r.np_div) * 64;
+    else SSW_TRY(get_basis(ctx, len / r.ydiv, inverse, true, r.y2, &y2));
+    d = {c, x1, x2, (const double*)y1, (const double*)y2};
     return SSW_OK;
 }
 
-// the odd half of the full-length transform from the operand plane `odd`: one launch, or rotate + two
-int odd_rotate(const PassBuild& b, const PairBases& pb, hipStream_t st, const double* odd) {
-    return b.p.split ? launch_dct_pair_rotate(st, odd, (const double*)pb.rot, pb.sp, b.lines, b.len) : SSW_OK;
-}
-int odd_gemm(const PassBuild& b, const PairBases& pb, hipStream_t st, const double* odd, double* tmpE, const RgbSink* sink) {
-    if (!b.p.split) {
-        const PairClassDesc d = D(2, 0, odd, odd, pb.b1, (const char*)pb.b1 + (b.len / 4) * 64);
-        return b.gemm(st, 1, &d, tmpE, nullptr, sink);
+// The split scratch of a pass (the lane's sixth operand buffer) as the deep pre-passes write it, planes by number (DESIGN
+// §3): level 1 -- AS BD AD BS R1 R2, K8 wide, then AS2 BD2 AD2 BS2, K16 wide; level 2 -- sixteen planes K16 wide, in `l2`
+// (the fused column pass reads them from the row launches' buffer).  `rot`: the rotation table of the axis.
+struct PairPlanes {
+    size_t bytes = 0, p8 = 0, p16 = 0;
+    const void* rot = nullptr;
+    double *sp = nullptr, *l2 = nullptr;
+    size_t l2_plane = 0;
+    const double* plane(bool level2, int j) const {
+        return level2 ? l2 + (size_t)j * l2_plane : j < 6 ? sp + (size_t)j * p8 : sp + 6 * p8 + (size_t)(j - 6) * p16;
     }
-    const PairClassDesc e = pb.e(), o = pb.o();
-    SSW_TRY(b.gemm(st, 1, &e, tmpE, nullptr, sink));
-    return b.gemm(st, 1, &o, tmpE, nullptr, sink);
+};
+int pair_planes(const PassBuild& b, ssw_ctx::Lane& ws, PairPlanes& pp) {
+    pp.bytes = dct_pair_operand_elems(b.n, b.w, b.h) * sizeof(double);
+    if (!b.p.split) return SSW_OK;
+    SSW_TRY(get_basis(b.ctx, b.len, false, true, BasisKind::Rot, &pp.rot));
+    SSW_TRY(grow(ws.operand[5], split_scratch_elems(b.n, b.w, b.h) * sizeof(double)));
+    pp.sp = pp.l2 = (double*)ws.operand[5].p;
+    pp.p8 = b.lines * dct_pair_split_kpad(b.len);
+    pp.p16 = pp.l2_plane = b.lines * dct_pair_split_kpad(b.len / 2);
+    return SSW_OK;
 }
-double odd_flop(const PassBuild& b) { return b.p.split ? b.flop(3, 0) + b.flop(4, 0) : b.flop(2, 0); }
+// class `c` of the pass on the planes the table names for it
+int class_desc(const PassBuild& b, PairClass c, const double* x1, const double* x2, PairClassDesc& d) {
+    return class_desc(b.ctx, b.len, b.inverse, c, x1, x2, d);
+}
+int deep_desc(const PassBuild& b, const PairPlanes& pp, bool level2, PairClass c, PairClassDesc& d) {
+    const signed char* x = level2 ? pair_class_row(c).l2x : pair_class_row(c).l1x;
+    if (x[0] < 0 || !pp.sp) return SSW_ERR_BAD_ARG;
+    return class_desc(b, c, pp.plane(level2, x[0]), pp.plane(level2, x[1]), d);
+}
+int deep_descs(const PassBuild& b, const PairPlanes& pp, bool level2, std::initializer_list<PairClass> cls, PairClassDesc* d) {
+    for (PairClass c : cls) SSW_TRY(deep_desc(b, pp, level2, c, *d++));
+    return SSW_OK;
+}
+// the rotation tables of the half- and (level 2) quarter-length transforms
+int deep_rot(const PassBuild& b, bool level2, const void** rot2, const void** rot3) {
+    SSW_TRY(get_basis(b.ctx, b.len / 2, false, true, BasisKind::Rot, rot2));
+    return level2 ? get_basis(b.ctx, b.len / 4, false, true, BasisKind::Rot, rot3) : SSW_OK;
+}
+
+// the odd half of the full-length transform from the operand plane `odd`: one launch, or rotate + two
+struct OddHalfLaunch { PairClassDesc d[2]; int n = 0; double flop = 0.0; };
+int odd_half(const PassBuild& b, const PairPlanes& pp, const double* odd, OddHalfLaunch& o) {
+    if (!b.p.split) {
+        o.n = 1; o.flop = b.flop(PairClass::OddHalf);
+        return class_desc(b, PairClass::OddHalf, odd, odd, o.d[0]);
+    }
+    o.n = 2; o.flop = b.flop(PairClass::E) + b.flop(PairClass::O);
+    return deep_descs(b, pp, false, {PairClass::E, PairClass::O}, o.d);
+}
+int odd_rotate(const PassBuild& b, const PairPlanes& pp, hipStream_t st, const double* odd) {
+    return b.p.split ? launch_dct_pair_rotate(st, odd, (const double*)pp.rot, pp.sp, b.lines, b.len) : SSW_OK;
+}
+int odd_gemm(const PassBuild& b, const OddHalfLaunch& o, hipStream_t st, double* tmpE, const RgbSink* sink) {
+    for (int c = 0; c < o.n; ++c) SSW_TRY(b.gemm(st, 1, &o.d[c], tmpE, nullptr, sink));
+    return SSW_OK;
+}
 
 // ---- one builder per strategy (dct_plan.hpp) ----
 int build_dense(const PassBuild& b, Chain& ch) {
     ssw_ctx* ctx = b.ctx;
     const void* b0 = nullptr;
-    SSW_TRY(get_basis(ctx, b.len, b.inverse, b.x.precision == SSW_PRECISION_F64, 0, &b0));
+    SSW_TRY(get_basis(ctx, b.len, b.inverse, b.x.precision == SSW_PRECISION_F64, BasisKind::Dense, &b0));
     const double flop = 2.0 * (double)b.lines * (double)b.len * (double)b.len;
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, flop);
@@ -391,16 +410,17 @@ int build_dense(const PassBuild& b, Chain& ch) {
 
 int build_pair_l1(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     ssw_ctx* ctx = b.ctx;
-    PairBases pb;
-    SSW_TRY(pair_bases(b, ws, pb));
-    for (int i = 0; i < 2; ++i) SSW_TRY(grow(ws.operand[i], pb.bytes));
+    PairPlanes pp;
+    SSW_TRY(pair_planes(b, ws, pp));
+    for (int i = 0; i < 2; ++i) SSW_TRY(grow(ws.operand[i], pp.bytes));
     double *x1 = (double*)ws.operand[0].p, *x2 = (double*)ws.operand[1].p;
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, SSW_STAGE_DCT_PREP, st, b.prep_bytes);
         return launch_dct_pair_prep(st, b.is_row, b.inverse, b.src, b.n, b.w, b.h, x1, x2);
     }});
-    const double f_main = b.flop(0, 0);
-    const PairClassDesc d = D(0, 0, x1, x2, pb.b0, pb.b1);
+    const double f_main = b.flop(PairClass::OneLevel);
+    PairClassDesc d;
+    SSW_TRY(class_desc(b, PairClass::OneLevel, x1, x2, d));
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, f_main);
         t.traffic(b.gemm_bytes(0.0));
@@ -412,34 +432,32 @@ int build_pair_l1(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
 
 int build_pair_two(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused_rgb) {
     ssw_ctx* ctx = b.ctx;
-    PairBases pb;
-    SSW_TRY(pair_bases(b, ws, pb));
-    for (int i = 1; i < (b.inverse ? 5 : 4); ++i) SSW_TRY(grow(ws.operand[i], pb.bytes));
+    PairPlanes pp;
+    SSW_TRY(pair_planes(b, ws, pp));
+    for (int i = 1; i < (b.inverse ? 5 : 4); ++i) SSW_TRY(grow(ws.operand[i], pp.bytes));
     double* x2 = (double*)ws.operand[1].p;       // D | O
     double* xx1 = (double*)ws.operand[2].p;      // SS | EE
     double* xx2 = (double*)ws.operand[3].p;      // SD | EO
     double* tmpE = (double*)ws.operand[4].p;     // inverse: the even half E, unrounded
-    const void *q0 = nullptr, *q1 = nullptr;
-    SSW_TRY(get_basis(ctx, b.len / 2, b.inverse, true, 3, &q0));
-    SSW_TRY(get_basis(ctx, b.len / 2, b.inverse, true, 4, &q1));
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
         if (b.from_rgb) SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, b.x.rgb_u8, b.x.rgb, b.n, b.w, b.h, xx1, xx2, x2, b.x.iq_i, b.x.iq_q));
         else SSW_TRY(launch_dct_pair_prep4(st, b.is_row, b.inverse, b.src, b.n, b.w, b.h, xx1, xx2, x2));
-        return odd_rotate(b, pb, st, x2);
+        return odd_rotate(b, pp, st, x2);
     }});
-    const double f_main = odd_flop(b), f_all = f_main + b.flop(1, 0);
+    OddHalfLaunch odd;
+    PairClassDesc even;
+    SSW_TRY(odd_half(b, pp, x2, odd));
+    SSW_TRY(class_desc(b, PairClass::EvenHalf, xx1, xx2, even));
+    const double f_main = odd.flop, f_all = f_main + b.flop(PairClass::EvenHalf);
     const RgbSink sink = rgb_sink(b, fused_rgb);
-    const PairClassDesc even = D(1, 0, xx1, xx2, q0, q1);
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, f_all);
         t.traffic(b.gemm_bytes(b.inverse ? 8.0 : 0.0));          // inverse: the even half E out and in
         // even half: a half-length transform of S (forward) / of the even coefficients (inverse), folded again
         SSW_TRY(b.gemm(st, 1, &even, tmpE));
-        // odd half: full half-length sum, the odd basis split into two row blocks (second block:
-        // len/4 lines further inside every k-block of the same plane = 64 bytes per line)
         StageTimer tm(ctx, b.st_main, st, f_main);
-        return odd_gemm(b, pb, st, x2, tmpE, sink.rgb ? &sink : nullptr);
+        return odd_gemm(b, odd, st, tmpE, sink.rgb ? &sink : nullptr);
     }});
     return SSW_OK;
 }
@@ -448,130 +466,81 @@ int build_pair_two(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused
 // rows) the pre-pass transposes like the two-level one
 int build_pair_three(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     ssw_ctx* ctx = b.ctx;
-    PairBases pb;
-    SSW_TRY(pair_bases(b, ws, pb));
-    for (int i = 0; i < 4; ++i) SSW_TRY(grow(ws.operand[i], pb.bytes));
+    PairPlanes pp;
+    SSW_TRY(pair_planes(b, ws, pp));
+    for (int i = 0; i < 4; ++i) SSW_TRY(grow(ws.operand[i], pp.bytes));
     double *d1 = (double*)ws.operand[1].p, *d2 = (double*)ws.operand[0].p, *r1 = (double*)ws.operand[2].p, *r2 = (double*)ws.operand[3].p;
-    const void *h1 = nullptr, *e0 = nullptr, *e1 = nullptr;
-    SSW_TRY(get_basis(ctx, b.len / 2, false, true, 4, &h1));          // odd half basis of len/2
-    SSW_TRY(get_basis(ctx, b.len / 4, false, true, 3, &e0));          // half bases of len/4
-    SSW_TRY(get_basis(ctx, b.len / 4, false, true, 4, &e1));
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
         if (!b.is_row) SSW_TRY(launch_dct_pair_prep8_cols(st, b.src, b.n, b.w, b.h, r1, r2, d2, d1));
         else SSW_TRY(launch_dct_pair_prep8_rows(st, b.rgb_kind(), b.prep_src(), b.n, b.w, b.h, r1, r2, d2, d1, b.prep_i(), b.prep_q()));
-        return odd_rotate(b, pb, st, d1);
+        return odd_rotate(b, pp, st, d1);
     }});
-    const double f_main = odd_flop(b), f_all = f_main + b.flop(1, 1) + b.flop(2, 1);
-    const PairClassDesc r = D(1, 1, r1, r2, e0, e1), m = D(2, 1, d2, d2, h1, (const char*)h1 + (b.len / 8) * 64);
+    OddHalfLaunch odd;
+    PairClassDesc r, m;
+    SSW_TRY(odd_half(b, pp, d1, odd));
+    SSW_TRY(class_desc(b, PairClass::R1R2, r1, r2, r));
+    SSW_TRY(class_desc(b, PairClass::OddHalf2, d2, d2, m));
+    const double f_main = odd.flop, f_all = f_main + b.flop(PairClass::R1R2) + b.flop(PairClass::OddHalf2);
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, f_all);
         t.traffic(b.gemm_bytes(0.0));
         SSW_TRY(b.gemm(st, 1, &r));
         SSW_TRY(b.gemm(st, 1, &m));
         StageTimer tm(ctx, b.st_main, st, f_main);
-        return odd_gemm(b, pb, st, d1, nullptr, nullptr);
+        return odd_gemm(b, odd, st, nullptr, nullptr);
     }});
     return SSW_OK;
 }
 
 // The deep strategies: one pre-pass writes the operands of all launches (D and SD split, SS folded a third time); forward
-// passes of 64-divisible (rows) / 16-divisible (columns) length, inverse ones of 128- / 16-divisible length.  Their bases:
-struct DeepBases {
-    const void *e0 = nullptr, *e1 = nullptr;                    // half bases of len/4 (level 1: R1, R2)
-    const void* t[4] = {};                                      // cosine / sine bases of len/2 (classes E', O')
-    const void *rot2 = nullptr, *rot3 = nullptr;                // rotation tables of len/2, len/4 (level 2)
-    const void *h0 = nullptr, *h1 = nullptr;                    // half bases of len/8 (level 2: R1)
-    // the half-length split (level 1): AS2 BD2 | AD2 BS2 from the planes q, q + p16 ...
-    PairClassDesc e2(const double* q, size_t p16) const { return D(3, 1, q, q + p16, t[0], t[1]); }
-    PairClassDesc o2(const double* q, size_t p16) const { return D(4, 1, q + 2 * p16, q + 3 * p16, t[2], t[3]); }
-};
-int deep_bases(const PassBuild& b, bool l2, DeepBases& db) {
-    ssw_ctx* ctx = b.ctx;
-    const size_t len = b.len;
-    SSW_TRY(get_basis(ctx, len / 4, b.inverse, true, 3, &db.e0));
-    SSW_TRY(get_basis(ctx, len / 4, b.inverse, true, 4, &db.e1));
-    for (int i = 0; i < 4; ++i) SSW_TRY(get_basis(ctx, len / 2, b.inverse, true, i == 1 ? 10 : 5 + i, &db.t[i]));
-    SSW_TRY(get_basis(ctx, len / 2, false, true, 9, &db.rot2));
-    return l2 ? get_basis(ctx, len / 4, false, true, 9, &db.rot3) : SSW_OK;
-}
-int deep_l2_halves(const PassBuild& b, DeepBases& db) {
-    SSW_TRY(get_basis(b.ctx, b.len / 8, b.inverse, true, 3, &db.h0));
-    return get_basis(b.ctx, b.len / 8, b.inverse, true, 4, &db.h1);
-}
-
-// Level 2, both directions: the eight classes of a pass and the sixteen K16-wide planes of its pre-pass they read, by number
-// (launch_dct_pair_prep16_rows, prep16_inv_rows_l2_kernel), with the basis pair of each: 0 = (cosine, sine) of class E' of
-// len/2, 1 = of class O', 2 = the half bases of len/8.  Every launch sums len/16 terms:
-//   class E (DCT-II of AS, DST-II of BD) folds exactly        -> kinds 5 / 6   16i +/- 1,  16i + 9 | 16i + 7
-//   class O (DCT-IV of AD, DST-IV of BS) rotates              -> kinds 7 / 8   16i +/- 5,  16i +/- 3
-//   R2 (DCT-IV) rotates, R1 (DCT-II) folds exactly            -> kind 9, kind 1 sub 2      16i +/- 4,  16i | 16i + 8
-// The forward launches run in this order; the inverse as c[16 s] | c[16 s + 8] -> A1 (class 0), R2 + A1 -> T2 (1),
-// AS2 BD2 | AD2 BS2 + T2 -> E (2, 3), then the odd part + E -> x (4, 5, 7, 6).
-struct L2Class { int kind, x1, x2, basis; };
-constexpr L2Class kL2Classes[8] = {
-    {1, 8, 9, 2},       // R1+ R1-
-    {9, 10, 11, 0},     // R2 rotated
-    {3, 12, 13, 0},     // AS2 BD2
-    {4, 14, 15, 1},     // AD2 BS2
-    {5, 0, 3, 0},       // AS+ BD-
-    {6, 1, 2, 1},       // AS- BD+
-    {8, 6, 7, 0},       // O rotated, "-"
-    {7, 4, 5, 0}};      // O rotated, "+"
-PairClassDesc l2_class(int c, bool inverse, const double* planes, size_t plane, const DeepBases& db) {
-    const L2Class& k = kL2Classes[c];
-    const void* const y[3][2] = {{db.t[0], db.t[1]}, {db.t[2], db.t[3]}, {db.h0, db.h1}};
-    const int sub = (k.kind == 1 || (inverse && k.kind == 9)) ? 2 : (k.kind == 3 || k.kind == 4) ? 1 : 0;
-    return D(k.kind, sub, planes + (size_t)k.x1 * plane, planes + (size_t)k.x2 * plane, y[k.basis][0], y[k.basis][1]);
-}
+// passes of 64-divisible (rows) / 16-divisible (columns) length, inverse ones of 128- / 16-divisible length.
 
 // forward, level 1: five launches, sums of len/8 terms (the half-length split and R1 / R2 at len/16)
 int build_deep(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
+    typedef PairClass C;
     ssw_ctx* ctx = b.ctx;
-    PairBases pb;
-    DeepBases db;
-    SSW_TRY(pair_bases(b, ws, pb));
-    SSW_TRY(deep_bases(b, false, db));
-    double* sp = pb.sp;
+    PairPlanes pp;
+    const void *rot2 = nullptr, *rot3 = nullptr;
+    SSW_TRY(pair_planes(b, ws, pp));
+    SSW_TRY(deep_rot(b, false, &rot2, &rot3));
+    double* sp = pp.sp;
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
-        if (!b.is_row) return launch_dct_pair_prep16_cols(st, b.src, b.n, b.w, b.h, sp, (const double*)pb.rot, (const double*)db.rot2, nullptr, b.p.prep, b.p.layout);
-        return launch_dct_pair_prep16_rows(st, b.rgb_kind(), b.prep_src(), b.n, b.w, b.h, sp, (const double*)pb.rot, (const double*)db.rot2, nullptr,
+        if (!b.is_row) return launch_dct_pair_prep16_cols(st, b.src, b.n, b.w, b.h, sp, (const double*)pp.rot, (const double*)rot2, nullptr, b.p.prep, b.p.layout);
+        return launch_dct_pair_prep16_rows(st, b.rgb_kind(), b.prep_src(), b.n, b.w, b.h, sp, (const double*)pp.rot, (const double*)rot2, nullptr,
                                            b.prep_i(), b.prep_q(), false);
     }});
-    const double f_main = b.flop(4, 0), f_all = f_main + b.flop(3, 0) + b.flop(1, 1) + b.flop(3, 1) + b.flop(4, 1);
-    const double* q = sp + 6 * pb.p8;
-    const PairClassDesc r1 = pb.r1(db.e0, db.e1), e2 = db.e2(q, pb.p16), o2 = db.o2(q, pb.p16);
+    const double f_main = b.flop(C::O), f_all = f_main + b.flop(C::E) + b.flop(C::R1R2) + b.flop(C::E2) + b.flop(C::O2);
     // a single frame's launches are too small alone (class E of a 4K frame: 272 blocks for 512 slots): one launch over all classes
-    const PairClassDesc merged[5] = {r1, e2, o2, pb.o(), pb.e()}, single[5] = {r1, e2, o2, pb.e(), pb.o()};
+    std::array<PairClassDesc, 5> merged, single;
+    SSW_TRY(deep_descs(b, pp, false, {C::R1R2, C::E2, C::O2, C::O, C::E}, merged.data()));
+    SSW_TRY(deep_descs(b, pp, false, {C::R1R2, C::E2, C::O2, C::E, C::O}, single.data()));
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, f_all);
         t.traffic(b.gemm_bytes(0.0));
         auto launch = [&](int nc, const PairClassDesc* d) { return b.gemm(st, nc, d, nullptr, nullptr, nullptr, b.gemm_layout()); };
-        if (!b.p.merge) return launch_classes(ctx, st, false, 5, single, launch, b.st_main, f_main);
+        if (!b.p.merge) return launch_classes(ctx, st, false, 5, single.data(), launch, b.st_main, f_main);
         StageTimer tm(ctx, b.st_main, st, f_all);
-        return launch(5, merged);
+        return launch(5, merged.data());
     }});
     return SSW_OK;
 }
 
-// LEVEL 2 (r4b / r4c): every operand of the full-length split and of SS folds or rotates once more in the pre-pass
-// (dct_pair_split.hpp, DeepPlanes): eight launches of len/16 terms over len/16 pairs, 2/3 of the level-1 multiply-adds.  The
-// "main" timer brackets ONE launch: kind 7 (level 1: class O of the full-length split).  r5, FUSED: the row pre-pass orders
+// LEVEL 2: every operand of the full-length split and of SS folds or rotates once more in the pre-pass (dct_pair_split.hpp,
+// DeepPlanes): the eight launches of kLevel2Classes, len/16 terms over len/16 pairs each, 2/3 of the level-1 multiply-adds.  The
+// "main" timer brackets ONE launch: O rotated "+" (level 1: class O of the full-length split).  FUSED: the row pre-pass orders
 // its lines (frame, unit of the column fold, line of the unit), the row launches' epilogue (EPI_FWD_COLOP) rounds to f32 --
 // the store between the passes, src/dct2d.rs:152-168 -- applies the column pre-pass's arithmetic and writes the sixteen
 // column-operand planes; the column pass is its eight launches only (4 + 4 + 8 B/px of plane and pre-pass become 8).
 int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     ssw_ctx* ctx = b.ctx;
     const bool fused = b.p.strategy == PassStrategy::FusedRows || b.p.strategy == PassStrategy::FusedCols;
-    PairBases pb;
-    DeepBases db;
-    SSW_TRY(pair_bases(b, ws, pb));
-    SSW_TRY(deep_bases(b, true, db));
-    SSW_TRY(deep_l2_halves(b, db));
+    PairPlanes pp;
+    const void *rot2 = nullptr, *rot3 = nullptr;
+    SSW_TRY(pair_planes(b, ws, pp));
+    SSW_TRY(deep_rot(b, true, &rot2, &rot3));
     const size_t n = b.n, w = b.w, h = b.h;
-    double* planes = pb.sp;                                       // the sixteen operand planes of the launches, K16 wide
-    size_t plane = pb.p16;
     FuseCols fc;
     double pad = 1.0;                                             // the padding units' share of the flop
     double bytes = b.gemm_bytes(0.0);
@@ -581,32 +550,32 @@ int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
         SSW_TRY(grow(ws.operand[0], 16 * cplane * sizeof(double)));
         double* cop = (double*)ws.operand[0].p;
         fc = FuseCols{FUSE_COLS};
-        if (!b.is_row) { planes = cop; plane = cplane; }
+        if (!b.is_row) { pp.l2 = cop; pp.l2_plane = cplane; }
         else {
             const void *crot1 = nullptr, *crot2 = nullptr, *crot3 = nullptr;
-            SSW_TRY(get_basis(ctx, h, false, true, 9, &crot1));
-            SSW_TRY(get_basis(ctx, h / 2, false, true, 9, &crot2));
-            SSW_TRY(get_basis(ctx, h / 4, false, true, 9, &crot3));
+            SSW_TRY(get_basis(ctx, h, false, true, BasisKind::Rot, &crot1));
+            SSW_TRY(get_basis(ctx, h / 2, false, true, BasisKind::Rot, &crot2));
+            SSW_TRY(get_basis(ctx, h / 4, false, true, BasisKind::Rot, &crot3));
             const size_t lpad = n * 16 * dct_pair_fused_units(h);           // unit-ordered, padded lines
-            plane = lpad * dct_pair_split_kpad(b.len / 2);
+            pp.l2_plane = lpad * dct_pair_split_kpad(b.len / 2);
             pad = (double)lpad / (double)(n * h);
             fc = FuseCols{FUSE_ROWS_COP, cop, (const double*)crot1, (const double*)crot2, (const double*)crot3};
             bytes = b.px * 16.0;                                // row operands in, column operands out
             out = nullptr;
         }
     }
-    double* sp = pb.sp;
+    double* sp = pp.sp;
     if (!fused || b.is_row)
         ch.push_back({true, [=](hipStream_t st) -> int {
             StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
-            if (!b.is_row) return launch_dct_pair_prep16_cols(st, b.src, n, w, h, sp, (const double*)pb.rot, (const double*)db.rot2, (const double*)db.rot3,
+            if (!b.is_row) return launch_dct_pair_prep16_cols(st, b.src, n, w, h, sp, (const double*)pp.rot, (const double*)rot2, (const double*)rot3,
                                                               b.p.prep, b.p.layout);
-            return launch_dct_pair_prep16_rows(st, b.rgb_kind(), b.prep_src(), n, w, h, sp, (const double*)pb.rot, (const double*)db.rot2,
-                                               (const double*)db.rot3, b.prep_i(), b.prep_q(), true, fused);
+            return launch_dct_pair_prep16_rows(st, b.rgb_kind(), b.prep_src(), n, w, h, sp, (const double*)pp.rot, (const double*)rot2,
+                                               (const double*)rot3, b.prep_i(), b.prep_q(), true, fused);
         }});
-    const double f_main = b.flop(7, 0), f_all = 8.0 * f_main;
+    const double f_main = b.flop(PairClass::O5), f_all = 8.0 * f_main;      // (every class: the same pairs and sum length)
     std::array<PairClassDesc, 8> d;
-    for (int c = 0; c < 8; ++c) d[c] = l2_class(c, false, planes, plane, db);
+    for (int c = 0; c < 8; ++c) SSW_TRY(deep_desc(b, pp, true, kLevel2Classes[c], d[c]));
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, f_all * pad, b.p.merge ? b.st_main : -1);      // (merged: a single frame's eight classes in one launch)
         t.traffic(bytes);
@@ -620,31 +589,31 @@ int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
 }
 
 // Columns of 8- but not 16-divisible length (1080 rows): D split and SS folded a third time in one pre-pass, SD stays one
-// launch (H/16 is not whole); behind a deep row pass the plane arrives class-major (r4c: the staged pre-pass reads it like the
+// launch (H/16 is not whole); behind a deep row pass the plane arrives class-major (the staged pre-pass reads it like the
 // deep one).  Inverse: c[8q] / c[8q+4] -> T2, the whole c[4q+2] part + T2 -> E, the split odd part + E -> output.
 int build_semi_deep(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused_rgb) {
+    typedef PairClass C;
     ssw_ctx* ctx = b.ctx;
     const bool inv = b.inverse;
-    PairBases pb;
-    SSW_TRY(pair_bases(b, ws, pb));
-    const void *e0 = nullptr, *e1 = nullptr, *h1 = nullptr;
-    SSW_TRY(get_basis(ctx, b.len / 4, inv, true, 3, &e0));
-    SSW_TRY(get_basis(ctx, b.len / 4, inv, true, 4, &e1));
-    SSW_TRY(get_basis(ctx, b.len / 2, inv, true, 4, &h1));
-    if (inv) for (int i : {1, 4}) SSW_TRY(grow(ws.operand[i], pb.bytes));
+    PairPlanes pp;
+    SSW_TRY(pair_planes(b, ws, pp));
+    if (inv) for (int i : {1, 4}) SSW_TRY(grow(ws.operand[i], pp.bytes));
     double* T2 = inv ? (double*)ws.operand[1].p : nullptr;
     double* TE = inv ? (double*)ws.operand[4].p : nullptr;
-    double* sp = pb.sp;
-    const double* rot = (const double*)pb.rot;
+    double* sp = pp.sp;
+    const double* rot = (const double*)pp.rot;
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
         if (inv) return launch_dct_pair_prep16_inv_cols(st, b.src, b.n, b.w, b.h, sp, rot, rot, nullptr, b.p.prep, b.p.layout);
         return launch_dct_pair_prep16_cols(st, b.src, b.n, b.w, b.h, sp, rot, rot, nullptr, b.p.prep, b.p.layout);
     }});
     const RgbSink sink = rgb_sink(b, fused_rgb);
-    const double* m = sp + 6 * pb.p8;
-    const PairClassDesc r1 = pb.r1(e0, e1), sd = D(2, 1, m, m, h1, (const char*)h1 + (b.len / 8) * 64), eo[2] = {pb.e(), pb.o()};
-    const double f_main = b.flop(3, 0), f_all = f_main + b.flop(4, 0) + b.flop(1, 1) + b.flop(2, 1);
+    PairClassDesc r1, sd, eo[2];
+    SSW_TRY(deep_desc(b, pp, false, C::R1R2, r1));
+    SSW_TRY(deep_desc(b, pp, false, C::OddHalf2, sd));
+    SSW_TRY(deep_descs(b, pp, false, {C::E, C::O}, eo));
+    const double f_sd = b.flop(C::OddHalf2);
+    const double f_main = b.flop(C::E), f_all = f_main + b.flop(C::O) + b.flop(C::R1R2) + f_sd;
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, f_all);
         t.traffic(b.gemm_bytes(inv ? 12.0 : 0.0));
@@ -656,7 +625,7 @@ int build_semi_deep(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fuse
         if (b.p.merge) {      // the SD launch shares its image operand between its two products: another template instance
             SSW_TRY(b.gemm(st, 1, &sd));
             const PairClassDesc d[3] = {r1, eo[1], eo[0]};
-            StageTimer tm(ctx, b.st_main, st, f_all - b.flop(2, 1));
+            StageTimer tm(ctx, b.st_main, st, f_all - f_sd);
             return b.gemm(st, 3, d);
         }
         SSW_TRY(b.gemm(st, 1, &r1));
@@ -669,43 +638,45 @@ int build_semi_deep(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fuse
 }
 
 // The inverse the deep way: c[8q] / c[8q+4] -> T2, the split c[4q+2] part + T2 -> T (the even half E), then the split odd
-// part + T -> the output; one pre-pass for all launches.  LEVEL 2 (r4c), the transpose of the forward pass's: T2 = its
-// even half A1 (kind 1 sub 2) +/- its odd half (R2 rotated, kind 9); E = T2 +/- the half-length odd part (kinds 3 / 4 sub 1);
-// x = E +/- the odd part (kinds 5 - 8): 8/14 of the level-1 multiply-adds.  The row launches write (and exchange E) class-major.
+// part + T -> the output; one pre-pass for all launches.  LEVEL 2, the transpose of the forward pass's: T2 = its even half A1
+// (R1+ R1-) +/- its odd half (R2 rotated); E = T2 +/- the half-length odd part (AS2 BD2 | AD2 BS2); x = E +/- the odd part
+// (AS+ BD- | AS- BD+ | O rotated "+" | "-"): 8/14 of the level-1 multiply-adds.  The row launches write (and exchange E) class-major.
 int build_deep_inv(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused_rgb) {
+    typedef PairClass C;
     ssw_ctx* ctx = b.ctx;
     const bool l2 = b.p.strategy == PassStrategy::DeepInvL2;
     const size_t len = b.len, lines = b.lines;
-    PairBases pb;
-    DeepBases db;
-    SSW_TRY(pair_bases(b, ws, pb));
-    SSW_TRY(deep_bases(b, false, db));
-    SSW_TRY(grow(ws.operand[1], std::max<size_t>(pb.bytes, lines * (len / 4) * sizeof(double))));
-    SSW_TRY(grow(ws.operand[4], std::max<size_t>(pb.bytes, lines * (len / 2) * sizeof(double))));
+    PairPlanes pp;
+    const void *rot2 = nullptr, *rot3 = nullptr;
+    SSW_TRY(pair_planes(b, ws, pp));
+    SSW_TRY(deep_rot(b, l2, &rot2, &rot3));
+    SSW_TRY(grow(ws.operand[1], std::max<size_t>(pp.bytes, lines * (len / 4) * sizeof(double))));
+    SSW_TRY(grow(ws.operand[4], std::max<size_t>(pp.bytes, lines * (len / 2) * sizeof(double))));
     double* A1 = nullptr;             // the eighth-length even part, unrounded: len/8 doubles per line
     if (l2) {
-        SSW_TRY(get_basis(ctx, len / 4, false, true, 9, &db.rot3));
-        SSW_TRY(deep_l2_halves(b, db));
-        SSW_TRY(grow(ws.operand[2], std::max<size_t>(pb.bytes, lines * (len / 8) * sizeof(double))));      // (>= what any other pass asks of it)
+        SSW_TRY(grow(ws.operand[2], std::max<size_t>(pp.bytes, lines * (len / 8) * sizeof(double))));      // (>= what any other pass asks of it)
         A1 = (double*)ws.operand[2].p;
     }
     double* T2 = (double*)ws.operand[1].p;       // quarter-length even half, unrounded
     double* TE = (double*)ws.operand[4].p;       // the even half E, unrounded
-    double* sp = pb.sp;
+    double* sp = pp.sp;
     const RgbSink sink = rgb_sink(b, fused_rgb);
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
-        if (!b.is_row) return launch_dct_pair_prep16_inv_cols(st, b.src, b.n, b.w, b.h, sp, (const double*)pb.rot, (const double*)db.rot2, (const double*)db.rot3,
+        if (!b.is_row) return launch_dct_pair_prep16_inv_cols(st, b.src, b.n, b.w, b.h, sp, (const double*)pp.rot, (const double*)rot2, (const double*)rot3,
                                                               b.p.prep, b.p.layout);
-        return launch_dct_pair_prep16_inv_rows(st, b.src, b.n, b.w, b.h, sp, (const double*)pb.rot, (const double*)db.rot2, (const double*)db.rot3, b.p.prep);
+        return launch_dct_pair_prep16_inv_rows(st, b.src, b.n, b.w, b.h, sp, (const double*)pp.rot, (const double*)rot2, (const double*)rot3, b.p.prep);
     }});
     // the stages: (level 2: A1, then) T2, E from T2, the output from E
-    auto L = [&](int c) { return l2_class(c, true, sp, pb.p16, db); };
-    const double* q = sp + 6 * pb.p8;
-    const PairClassDesc da = l2 ? L(0) : PairClassDesc{}, dt = l2 ? L(1) : pb.r1(db.e0, db.e1);
-    const PairClassDesc d1[2] = {l2 ? L(2) : db.e2(q, pb.p16), l2 ? L(3) : db.o2(q, pb.p16)};
-    const PairClassDesc d0[4] = {l2 ? L(4) : pb.e(), l2 ? L(5) : pb.o(), l2 ? L(7) : PairClassDesc{}, l2 ? L(6) : PairClassDesc{}};
-    const double f_all = l2 ? 8.0 * b.flop(7, 0) : b.flop(3, 0) + b.flop(4, 0) + b.flop(1, 1) + b.flop(3, 1) + b.flop(4, 1);
+    PairClassDesc da{}, dt, d1[2], d0[4];
+    if (l2) SSW_TRY(deep_desc(b, pp, true, C::R1A, da));
+    SSW_TRY(deep_desc(b, pp, l2, l2 ? C::R2A : C::R1R2, dt));
+    SSW_TRY(deep_descs(b, pp, l2, {C::E2, C::O2}, d1));
+    if (l2) SSW_TRY(deep_descs(b, pp, true, {C::EE, C::EO, C::O5, C::O3}, d0));
+    else SSW_TRY(deep_descs(b, pp, false, {C::E, C::O}, d0));
+    const double f_all = l2 ? 8.0 * b.flop(C::O5) : b.flop(C::E) + b.flop(C::O) + b.flop(C::R1R2) + b.flop(C::E2) + b.flop(C::O2);
+    const std::array<PairClassDesc, 2> s1{d1[0], d1[1]};
+    const std::array<PairClassDesc, 4> s0{d0[0], d0[1], d0[2], d0[3]};
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_pass, st, f_all);
         t.traffic(b.gemm_bytes(l2 ? 14.0 : 12.0));
@@ -713,8 +684,8 @@ int build_deep_inv(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused
         if (l2) SSW_TRY(b.gemm(st, 1, &da, A1));
         SSW_TRY(l2 ? b.gemm(st, 1, &dt, A1, T2, nullptr, lay) : b.gemm(st, 1, &dt, T2));
         // (single frames: the classes of each dependent stage in one launch)
-        SSW_TRY(launch_classes(ctx, st, b.p.merge, 2, d1, [&](int nc, const PairClassDesc* d) { return b.gemm(st, nc, d, T2, TE, nullptr, lay); }));
-        return launch_classes(ctx, st, b.p.merge, l2 ? 4 : 2, d0,
+        SSW_TRY(launch_classes(ctx, st, b.p.merge, 2, s1.data(), [&](int nc, const PairClassDesc* d) { return b.gemm(st, nc, d, T2, TE, nullptr, lay); }));
+        return launch_classes(ctx, st, b.p.merge, l2 ? 4 : 2, s0.data(),
                               [&](int nc, const PairClassDesc* d) { return b.gemm(st, nc, d, TE, nullptr, sink.rgb ? &sink : nullptr, lay); });
     }});
     return SSW_OK;
@@ -1044,52 +1015,11 @@ PruneSetup make_prune_setup(const ssw_ctx* ctx, bool f64, size_t n, size_t w, si
     if (cap * 4 > w) return ps;                                           // not worth it: full transform
     if (!dct_pair_can_run(n, cap, h, aligned)) return ps;
     ps.rows = forward_rows_plan(ctx, f64, n, w, h, y, tmp);
-    const bool deep = plan_is_deep(ps.rows);
     ps.plan.W = (unsigned)w;
     ps.plan.cap_total = (unsigned)cap;
-    const unsigned c = (unsigned)cap;
-    unsigned nc = 0, off = 0;
-    auto add = [&](unsigned mod, unsigned rem, unsigned cc, unsigned rem2 = PRUNE_NO_REM, unsigned radd = 0) {
-        ps.plan.c[nc] = {mod, rem, cc, off, rem2, radd};
-        off += cc;
-        ++nc;
-    };
-    if (plan_is_level2(ps.rows)) {
-        // level 2 (build_deep_l2): nine classes of sums of w/16 terms; v = 16i +/- r -> row i (= (v + r) / 16) of the bases of
-        // E even, v = 16i + 9 | 16i + 7 -> row i of E odd; the same two for the half-length split; R1 folded: 16i, 16i + 8
-        add(16, 1, c / 8, 15, 1);         // AS+ BD-
-        add(16, 9, c / 8, 7, 0);          // AS- BD+
-        add(16, 5, c / 8, 11, 5);         // O rotated "+"
-        add(16, 3, c / 8, 13, 3);         // O rotated "-"
-        add(16, 2, c / 8, 14, 2);         // AS2 BD2
-        add(16, 10, c / 8, 6, 0);         // AD2 BS2
-        add(16, 4, c / 8, 12, 4);         // R2 rotated
-        add(16, 0, c / 16);               // R1+
-        add(16, 8, c / 16);               // R1-
-        ps.plan.n_classes = nc;
-        ps.on = true;
-        return ps;
-    }
-    if (ps.rows.split) {                  // odd v = 8i +/- 1 -> class E row i (= (v + 1) / 8), v = 8i + 5 | 8i + 3 -> class O row i
-        add(8, 1, c / 4, 7, 1);
-        add(8, 5, c / 4, 3, 0);
-    } else {
-        add(2, 1, c / 2);
-    }
-    if (deep) {                           // v = 2 (8i +/- 1) -> class E' row i (= (v + 2) / 16), v = 2 (8i + 5) | 2 (8i + 3) -> class O' row i
-        add(16, 2, c / 8, 14, 2);
-        add(16, 10, c / 8, 6, 0);
-        add(8, 0, c / 8);
-        add(8, 4, c / 8);
-    } else if (ps.rows.levels == 3) {
-        add(4, 2, c / 4);
-        add(8, 0, c / 8);
-        add(8, 4, c / 8);
-    } else {
-        add(4, 0, c / 4);
-        add(4, 2, c / 4);
-    }
-    ps.plan.n_classes = nc;
+    PairClass cls[8];
+    const int n_cls = prune_class_list(ps.rows, cls);             // what build_pruned_derived launches
+    prune_plan_classes(cls, n_cls, (unsigned)cap, ps.plan);
     ps.on = true;
     return ps;
 }
@@ -1109,7 +1039,8 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u
     uint32_t* flag = (uint32_t*)ws.prune_u32.p;
     uint32_t* pos = flag + w;
     uint32_t* rows = pos + w;
-    // class -> image operand plane(s), cached basis plane(s), padded / true sum length
+    // class of the plan -> image operand plane(s), cached basis plane(s), padded / true sum length: the launch classes of
+    // make_prune_setup by the class table -- a split class is one class of the plan (cosine and sine rows), a folded one two
     struct ClassSrc { const void* x; const void* basis; size_t src_rows, kp, ktrue; const void* x2 = nullptr; const void* basis2 = nullptr; };
     ClassSrc cs[9];
     int pn1[9] = {0}, pn2[9] = {0};          // level 2: the classes' operand planes by number (the fused kernel's A-fragments)
@@ -1117,73 +1048,43 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u
     const size_t lines = n * h;
     const void *rot = nullptr, *rot2 = nullptr, *rot3 = nullptr;
     double* sp = nullptr;
-    if (level2) {             // level 2: the classes of make_prune_setup, planes by number (kL2Classes)
-        const void *sb2[4], *h0 = nullptr, *h1 = nullptr;
-        for (int b = 0; b < 4; ++b) SSW_TRY(get_basis(ctx, w / 2, false, true, 5 + b, &sb2[b]));
-        SSW_TRY(get_basis(ctx, w, false, true, 9, &rot));
-        SSW_TRY(get_basis(ctx, w / 2, false, true, 9, &rot2));
-        SSW_TRY(get_basis(ctx, w / 4, false, true, 9, &rot3));
-        SSW_TRY(get_basis(ctx, w / 8, false, true, 3, &h0));
-        SSW_TRY(get_basis(ctx, w / 8, false, true, 4, &h1));
+    if (deep && !ps.rows.split) return SSW_ERR_BAD_ARG;
+    if (ps.rows.split) {
+        SSW_TRY(get_basis(ctx, w, false, true, BasisKind::Rot, &rot));
+        if (deep) SSW_TRY(get_basis(ctx, w / 2, false, true, BasisKind::Rot, &rot2));
+        if (level2) SSW_TRY(get_basis(ctx, w / 4, false, true, BasisKind::Rot, &rot3));
         SSW_TRY(grow(ws.operand[5], split_scratch_elems(n, w, h) * sizeof(double)));
         sp = (double*)ws.operand[5].p;
-        const size_t kp16 = dct_pair_split_kpad(w / 2), p16 = lines * kp16;
-        const size_t re = dct_pair_split_basis_rows(w / 2, 0), ro = dct_pair_split_basis_rows(w / 2, 2);
-        auto P = [=](int j) { return (const void*)(sp + (size_t)j * p16); };
-        // the pair classes in the plan's order (16i +/- 1, 16i + 9 | 7, +/- 5, +/- 3, +/- 2, 10 | 6, +/- 4), then R1's two planes
-        for (int k : {4, 5, 7, 6, 2, 3, 1}) {
-            const L2Class& lc = kL2Classes[k];
-            pn1[ci] = lc.x1; pn2[ci] = lc.x2;
-            cs[ci++] = {P(lc.x1), sb2[2 * lc.basis], lc.basis ? ro : re, kp16, w / 16, P(lc.x2), sb2[2 * lc.basis + 1]};
-        }
-        const L2Class& r1 = kL2Classes[0];
-        for (int j = 0; j < 2; ++j) {
-            const int x = j ? r1.x2 : r1.x1;
-            pn1[ci] = x; pn2[ci] = -1;
-            cs[ci++] = {P(x), j ? h1 : h0, w / 16, kp16, w / 16};
-        }
-    } else if (ps.rows.split) {
-        const void* sb[4];
-        for (int b = 0; b < 4; ++b) SSW_TRY(get_basis(ctx, w, false, true, 5 + b, &sb[b]));
-        SSW_TRY(get_basis(ctx, w, false, true, 9, &rot));
-        const size_t kp8 = dct_pair_split_kpad(w), plane = lines * kp8;
-        SSW_TRY(grow(ws.operand[5], split_scratch_elems(n, w, h) * sizeof(double)));
-        sp = (double*)ws.operand[5].p;
-        const void *sb2[4] = {nullptr, nullptr, nullptr, nullptr}, *e0 = nullptr, *e1 = nullptr;
-        const size_t kp16 = dct_pair_split_kpad(w / 2), p16 = lines * kp16;
-        double* q = sp + 6 * plane;
-        if (deep) for (int b = 0; b < 4; ++b) SSW_TRY(get_basis(ctx, w / 2, false, true, 5 + b, &sb2[b]));
-        cs[ci++] = {sp, sb[0], dct_pair_split_basis_rows(w, 0), kp8, w / 8, sp + plane, sb[1]};              // AS x cosE, BD x sinE
-        cs[ci++] = {sp + 2 * plane, sb[2], dct_pair_split_basis_rows(w, 2), kp8, w / 8, sp + 3 * plane, sb[3]};  // AD x cosO, BS x sinO
-        if (deep) {
-            SSW_TRY(get_basis(ctx, w / 2, false, true, 9, &rot2));
-            SSW_TRY(get_basis(ctx, w / 4, false, true, 3, &e0));
-            SSW_TRY(get_basis(ctx, w / 4, false, true, 4, &e1));
-            cs[ci++] = {q, sb2[0], dct_pair_split_basis_rows(w / 2, 0), kp16, w / 16, q + p16, sb2[1]};              // AS2 x cosE', BD2 x sinE'
-            cs[ci++] = {q + 2 * p16, sb2[2], dct_pair_split_basis_rows(w / 2, 2), kp16, w / 16, q + 3 * p16, sb2[3]}; // AD2 x cosO', BS2 x sinO'
-            cs[ci++] = {sp + 4 * plane, e0, w / 8, kp8, w / 8};                                                      // R1 (SSS): 0 mod 8
-            cs[ci++] = {sp + 5 * plane, e1, w / 8, kp8, w / 8};                                                      // R2 (SS-): 4 mod 8
-        }
-    } else {
-        const void* b1 = nullptr;
-        SSW_TRY(get_basis(ctx, w, false, true, 4, &b1));
-        cs[ci++] = {ws.operand[1].p, b1, w / 2, dct_pair_kpad(w), w / 2};       // x- | D : odd
     }
-    if (deep) {
-    } else if (levels == 3) {
-        const void *h1 = nullptr, *e0 = nullptr, *e1 = nullptr;
-        SSW_TRY(get_basis(ctx, w / 2, false, true, 4, &h1));
-        SSW_TRY(get_basis(ctx, w / 4, false, true, 3, &e0));
-        SSW_TRY(get_basis(ctx, w / 4, false, true, 4, &e1));
-        cs[ci++] = {ws.operand[0].p, h1, w / 4, dct_pair_kpad(w / 2), w / 4};      // S-  : 2 mod 4
-        cs[ci++] = {ws.operand[2].p, e0, w / 8, dct_pair_kpad(w / 4), w / 8};      // SSS : 0 mod 8
-        cs[ci++] = {ws.operand[3].p, e1, w / 8, dct_pair_kpad(w / 4), w / 8};      // SS- : 4 mod 8
-    } else {
-        const void *q0 = nullptr, *q1 = nullptr;
-        SSW_TRY(get_basis(ctx, w / 2, false, true, 3, &q0));
-        SSW_TRY(get_basis(ctx, w / 2, false, true, 4, &q1));
-        cs[ci++] = {ws.operand[2].p, q0, w / 4, dct_pair_kpad(w / 2), w / 4};      // SS : 0 mod 4
-        cs[ci++] = {ws.operand[3].p, q1, w / 4, dct_pair_kpad(w / 2), w / 4};      // SD : 2 mod 4
+    PairPlanes pp;
+    pp.sp = pp.l2 = sp;
+    pp.p8 = lines * dct_pair_split_kpad(w);
+    pp.p16 = pp.l2_plane = lines * dct_pair_split_kpad(w / 2);
+    PairClass cls[8];
+    const int n_cls = prune_class_list(ps.rows, cls);
+    for (int i = 0; i < n_cls; ++i) {
+        const PairClassRow& r = pair_class_row(cls[i]);
+        PairClassArgs ca;
+        PairInstance inst;
+        SSW_TRY(pair_class_args(cls[i], true, false, w, PairLayout(), false, false, false, ca, inst));
+        // operand planes: the deep pre-passes' by number; else the lane's buffers as the two- / three-level pre-passes fill them
+        // (x- | D in [1], S- in [0], SS SD | SSS SS- in [2] [3]) and the rotated odd half in the split scratch
+        const signed char* pn = level2 ? r.l2x : r.l1x;
+        const void *x1, *x2;
+        if (deep || r.split) { x1 = pp.plane(level2, pn[0]); x2 = pp.plane(level2, pn[1]); }
+        else if (r.samex) x1 = x2 = ws.operand[cls[i] == PairClass::OddHalf ? 1 : 0].p;
+        else { x1 = ws.operand[2].p; x2 = ws.operand[3].p; }
+        // the bases as cached (the gather reads sinE itself, not its launch variant)
+        const void *y1 = nullptr, *y2 = nullptr;
+        SSW_TRY(get_basis(ctx, w / r.ydiv, false, true, r.y1, &y1));
+        SSW_TRY(get_basis(ctx, w / r.ydiv, false, true, r.y2 == BasisKind::SinELaunch ? BasisKind::SinE : r.y2, &y2));
+        const size_t ktrue = w / r.ldiv / r.k_div;
+        pn1[ci] = pn[0]; pn2[ci] = r.split ? pn[1] : -1;
+        if (r.split) cs[ci++] = {x1, y1, ca.yrows, ca.Kp, ktrue, x2, y2};
+        else {
+            cs[ci++] = {x1, y1, ca.yrows, ca.Kp, ktrue};
+            if (!r.samex) { pn1[ci] = pn[1]; pn2[ci] = -1; cs[ci++] = {x2, y2, ca.yrows, ca.Kp, ktrue}; }
+        }
     }
     if (ci != plan.n_classes) return SSW_ERR_BAD_ARG;
     size_t goff[9], goff2[9], gtotal = 0;

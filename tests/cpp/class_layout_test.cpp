@@ -24,7 +24,7 @@ int main() {
             if (u >= n || seen[u]++) return fail("forward natural() not a bijection", n, p);
             if (u / t != p / t) return fail("forward natural() leaves its tile", n, p);
         }
-        // the launches' output maps (dct_pair_f64.hip, pair_class_args / fpos1 / fpos2): entry = pair index [- 1 for the
+        // the launches' output maps (dct_pair_class.hip, pair_class_args; the kernel's fpos1 / fpos2): entry = pair index [- 1 for the
         // "-" outputs of launches of class E's shape], column = base + (entry / group) * tile + entry % group
         if (!level2) {
             for (unsigned i = 0; i < n / 8; ++i) {

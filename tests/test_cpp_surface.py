@@ -42,6 +42,18 @@ def test_transform_planner_on_the_host(tmp_path):
     assert out.strip() == "ok", out
 
 
+def test_pair_class_table_on_the_host(tmp_path):
+    """csrc/dct_pair_class.hpp: the launch-class table answers what the per-class launch code answered before the table existed
+    (tests/golden/pair_class_parent.txt: all 33600 tuples of class, pass, direction, layout, length, the rejected ones included,
+    and the class rows of the pruned plans), and agrees with ForwardClassLayout, with a partition of the frequencies per pass
+    and with the flop the level-2 builders assume -- no GPU, no context."""
+    exe = os.path.join(str(tmp_path), "pair_class_test")
+    subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "--offload-arch=gfx950", os.path.join(ROOT, "tests", "cpp", "pair_class_test.cpp"),
+                    "-o", exe, "-L", LIBDIR, "-lssw_hip", f"-Wl,-rpath,{LIBDIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    out = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "pair_class_parent.txt")], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout
+
+
 def test_cpp_wrappers_compile_and_link(tmp_path):
     exe = build(tmp_path)
     assert os.path.exists(exe)
