@@ -411,6 +411,57 @@ int ssw_fingerprint_embed_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_
 int ssw_writer_mark_copies(ssw_writer* wr, const float* host_marks, size_t n_copies, size_t k, float* host_out);
 int ssw_writer_mark_copies_rgb8(ssw_writer* wr, const float* host_marks, size_t n_copies, size_t k, uint8_t* host_out);
 
+/* ---- tracing: ONE original against many suspect frames and many stored marks (device-resident) ---- */
+/* The read side of fingerprinting.  Per suspect s exactly (algorithm.rs:462-562, :696-714; the `test` loop of
+   examples/main.rs:369-415):
+       base  = Reader::base(original, cfg)
+       ext_s = base.extract(Reader::derived(suspect_s), k)
+       sims[s][j] = Tester::new(ext_s).similarity(mark_j)
+   dev_base_rgb: ONE frame [h][w][3]; dev_suspect_rgb [n_suspects][h][w][3]; dev_marks [n_marks][k] or NULL.
+   The base frame is transformed and ranked once per call; the suspects go through the pruned derived transform of
+   ssw_batch_extract in chunks on two lanes, with one prune plan for the whole call (one index list, so the column set
+   stays at its single-frame size).  Outputs:
+     dev_extracted [n_suspects][k]   bit-identical to ssw_batch_extract(_rgb8) with the base frame replicated n_suspects
+                                     times (the same kernels produce the values)
+     dev_sims [n_suspects][n_marks]  (may be NULL) bit-identical to ssw_similarity_matrix(dev_extracted, dev_marks): the f32
+                                     MFMA GEMM, equal to the reference's sums to 1e-4 relative
+     dev_best [n_suspects]           (may be NULL) index of the largest non-NaN entry of row s, the lowest index on ties;
+                                     0xFFFFFFFF when the row has none, when n_marks == 0 and when k == 0
+     dev_best_sim [n_suspects]       (may be NULL) the winner rescored in the reference's sequential f32 order: equal bit for
+                                     bit to ssw_similarity_batch(ext_s, mark_best), i.e. Tester::similarity itself (:702-713);
+                                     NaN where there is no winner
+     dev_n_exceed [n_suspects]       (may be NULL) entries of row s with sim > threshold; NaN never exceeds
+                                     (Similarity::exceeds_sigma, :677).  Two colluders show as 2.
+   NaN is a real case: a suspect identical to the original extracts all zeros and every similarity is 0 / sqrt(0).
+   Status codes follow ssw_batch_extract: k >= w*h SSW_ERR_K_TOO_LARGE (:553-555); n_suspects == 0 SSW_OK; dev_marks ==
+   NULL requires n_marks == 0 and every similarity output NULL (extraction only), anything else SSW_ERR_BAD_ARG; Custom
+   variants SSW_ERR_UNSUPPORTED; SSW_PRECISION_F32 takes the dense path.  Stream contract of ssw_batch_extract: enqueues
+   only, except for one look at the prune overflow flag; under stream capture or with ssw_ctx_set_prune(ctx, 0) the
+   suspects take the full transform (bit-identical outputs, no host wait).  When the column set does not fit the compact
+   plane every chunk is redone in full.  ssw_ctx_get_prune_stats: a call counts its chunks, and its column set once. */
+int ssw_fingerprint_trace(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_base_rgb, const float* dev_suspect_rgb,
+                          size_t n_suspects, size_t w, size_t h, size_t k, const float* dev_marks, size_t n_marks,
+                          float threshold, float* dev_extracted, float* dev_sims, uint32_t* dev_best, float* dev_best_sim,
+                          uint32_t* dev_n_exceed);
+/* The same on 8-bit frames (algorithm.rs:462-562, :696-714 with into_rgb32f() of the caller, examples/main.rs:383-415). */
+int ssw_fingerprint_trace_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* dev_base_rgb, const uint8_t* dev_suspect_rgb,
+                               size_t n_suspects, size_t w, size_t h, size_t k, const float* dev_marks, size_t n_marks,
+                               float threshold, float* dev_extracted, float* dev_sims, uint32_t* dev_best,
+                               float* dev_best_sim, uint32_t* dev_n_exceed);
+/* Host form (algorithm.rs:462-562, :696-714; examples/main.rs:369-415 as one call): 8-bit host images, one pointer per
+   suspect; marks and every output are host buffers (outputs may be NULL as above; host_extracted may be NULL too).  The base
+   is uploaded and transformed once; the suspects stream through the ring of ssw_batch_extract_host_rgb8 (upload of group
+   g + 1 under the kernels of group g).  Returns when every buffer is the caller's again.  Bit-identical to the device form. */
+int ssw_fingerprint_trace_host_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* host_base,
+                                    const uint8_t* const* host_suspects, size_t n_suspects, size_t w, size_t h, size_t k,
+                                    const float* host_marks, size_t n_marks, float threshold, float* host_extracted,
+                                    float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed);
+/* Handle form of the host call (algorithm.rs:529-539, :696-714): `base` is a base reader (else SSW_ERR_NOT_BASE); its
+   transformed plane and its index list are reused, nothing of the original crosses PCIe again.  The reader stays usable. */
+int ssw_reader_trace_host_rgb8(ssw_reader* base, const uint8_t* const* host_suspects, size_t n_suspects, size_t k,
+                               const float* host_marks, size_t n_marks, float threshold, float* host_extracted,
+                               float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed);
+
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,
    and `into_rgb16()` from Rgb32F: round(clamp(v,0,1) * 65535) (`image 0.24.3`, like the 8-bit forms). */

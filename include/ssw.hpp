@@ -16,6 +16,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -255,6 +256,16 @@ private:
 
 class ReaderDerived;
 
+// What Reader::trace returns, per suspect s: extracted[s] (k values), sims[s] (one per mark; the GEMM matrix, 1e-4 relative),
+// best[s] (index of the strongest mark, TraceResult::none without one), best_sim[s] (Tester::similarity of that mark, exact;
+// NaN without one), n_exceed[s] (marks above the threshold: two and more = colluders).
+struct TraceResult {
+    static constexpr uint32_t none = 0xFFFFFFFFu;
+    std::vector<std::vector<float>> extracted, sims;
+    std::vector<uint32_t> best, n_exceed;
+    std::vector<float> best_sim;
+};
+
 class Reader {                                         // algorithm.rs:441-594
 public:
     static Reader base(Context& ctx, const ImageRgb32F& image, const ReadConfig& config = ReadConfig()) {   // :462-464
@@ -279,6 +290,32 @@ public:
         return out;
     }
     void extract(const ReaderDerived& derived, std::vector<float>& extracted) const;   // :529-539
+    // Whose copy is each suspect?  extract() against every suspect and Tester::similarity against every stored mark
+    // (:529-539, :696-714; the `test` loop of examples/main.rs:369-415) as one call on this base reader's plane and index
+    // list (a derived reader: SSW_ERR_NOT_BASE).  All marks one length; suspects of the reader's size.
+    TraceResult trace(const std::vector<const ImageRgb8*>& suspects, const std::vector<const MarkBuf*>& marks, float threshold = 6.0f) const {
+        const size_t n = suspects.size(), nm = marks.size(), k = nm ? marks[0]->data().size() : 0;
+        std::vector<const uint8_t*> sp(n);
+        for (size_t i = 0; i < n; ++i) {
+            if (suspects[i]->width != w_ || suspects[i]->height != h_ || suspects[i]->data.size() != w_ * h_ * 3) throw Error(SSW_ERR_BAD_DIMS, "Reader::trace");
+            sp[i] = suspects[i]->data.data();
+        }
+        std::vector<float> m(nm * k), ext(n * k), sims(n * nm);
+        for (size_t j = 0; j < nm; ++j) {
+            if (marks[j]->data().size() != k) throw Error(SSW_ERR_LENGTH_MISMATCH, "Reader::trace");
+            std::copy(marks[j]->data().begin(), marks[j]->data().end(), m.begin() + j * k);
+        }
+        TraceResult r;
+        r.best.assign(n, TraceResult::none); r.n_exceed.assign(n, 0u); r.best_sim.assign(n, std::nanf(""));
+        check(ssw_reader_trace_host_rgb8(rd_, sp.data(), n, k, nm ? m.data() : nullptr, nm, threshold, ext.data(), nm ? sims.data() : nullptr,
+                                         nm ? r.best.data() : nullptr, nm ? r.best_sim.data() : nullptr, nm ? r.n_exceed.data() : nullptr),
+              "Reader::trace");
+        for (size_t i = 0; i < n; ++i) {
+            r.extracted.emplace_back(ext.begin() + i * k, ext.begin() + (i + 1) * k);
+            r.sims.emplace_back(sims.begin() + i * nm, sims.begin() + (i + 1) * nm);
+        }
+        return r;
+    }
 
 private:
     friend class ReaderDerived;

@@ -28,6 +28,7 @@ PRECISION_F32, PRECISION_F64 = 0, 1
 STAGES = ["rgb_to_yiq", "dct_row", "dct_col", "select", "embed", "extract", "similarity", "yiq_to_rgb",
           "resize", "convert", "dct_prep", "dct_row_main", "dct_col_main"]
 DCT_FOLDING_DEFAULT = 5
+TRACE_NONE = 0xFFFFFFFF      # ssw_fingerprint_trace: dev_best of a suspect that carries no mark
 PLAN_FLAGS = {"pair_f64": 1, "rows_deep": 2, "cols_deep": 4, "rows_level2": 8, "cols_level2": 16, "class_major": 32, "fused_cols": 64}
 TRANSFER_STATS = ["h2d_bytes", "d2h_bytes", "h2d_seconds", "d2h_seconds", "staged_bytes", "direct_bytes"]
 
@@ -111,6 +112,11 @@ SIGNATURES = {
     "ssw_writer_mark_rgb8": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _sz, _vp]),
     "ssw_fingerprint_embed": (C.c_int, [_vp, _cfgp, _f32p, _sz, _sz, _f32p, _sz, _sz, _f32p, _u32p]),
     "ssw_fingerprint_embed_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, _f32p, _sz, _sz, _vp, _u32p]),
+    "ssw_fingerprint_trace": (C.c_int, [_vp, _cfgp, _f32p, _f32p, _sz, _sz, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p, _f32p, _u32p]),
+    "ssw_fingerprint_trace_rgb8": (C.c_int, [_vp, _cfgp, _vp, _vp, _sz, _sz, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p, _f32p, _u32p]),
+    "ssw_fingerprint_trace_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p,
+                                                  _f32p, _u32p]),
+    "ssw_reader_trace_host_rgb8": (C.c_int, [_vp, C.POINTER(_vp), _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p, _f32p, _u32p]),
     "ssw_writer_mark_copies": (C.c_int, [_vp, _f32p, _sz, _sz, _vp]),
     "ssw_writer_mark_copies_rgb8": (C.c_int, [_vp, _f32p, _sz, _sz, _vp]),
     "ssw_writer_destroy": (C.c_int, [_vp]),

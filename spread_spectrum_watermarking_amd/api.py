@@ -505,6 +505,21 @@ class Reader:
         check(self._lib.ssw_reader_extract(self._h, d._h, out.ctypes.data, out.size), "Reader::extract")
         return out
 
+    def trace(self, suspects, marks, threshold: float = 6.0, k: Optional[int] = None) -> "TraceResult":
+        """Whose copy is each suspect?  Per 8-bit suspect image s: `self.extract(Reader.derived(s), k)`, then
+        `Tester(ext).similarity(m)` for every stored mark m (algorithm.rs:529-539, :696-714; the `test` loop of
+        examples/main.rs:369-415) as ONE call: this reader's transformed plane and index list are reused, the suspects
+        stream to the GPU.  All marks must have one length (ValueError otherwise); `k` is only needed without marks."""
+        if not self.is_base:
+            raise SswError(L.SSW_ERR_NOT_BASE, "Reader::trace")
+        arrs, ptrs, w, h = _frame_ptrs(suspects)
+        if (w, h) != (self.width, self.height):
+            raise SswError(L.SSW_ERR_LENGTH_MISMATCH, "Reader::trace")
+        m, k = _trace_marks(marks, k)
+        res = TraceResult.empty(len(arrs), m.shape[0], k)
+        check(self._lib.ssw_reader_trace_host_rgb8(self._h, ptrs, len(arrs), k, *res._args(m, threshold)), "Reader::trace")
+        return res
+
     def __del__(self):
         try:
             if getattr(self, "_h", None) and self._ctx.handle:
@@ -589,6 +604,68 @@ def extract_many(base_images, derived_images, k: int, marks=None, config: Option
                                                m.ctypes.data if m is not None else None, sims.ctypes.data if sims is not None else None),
           "ssw_batch_extract_host_rgb8")
     return ext, sims
+
+
+# ---- tracing: one original, many suspects, many stored marks (include/ssw.h: ssw_fingerprint_trace) -----------------
+def _trace_marks(marks, k):
+    arrs = [np.ascontiguousarray(_mark_data(x), dtype=np.float32) for x in (marks if marks is not None else [])]
+    if len({a.size for a in arrs}) > 1:
+        raise ValueError("trace: every mark must have the same length")
+    if arrs and k is not None and int(k) != arrs[0].size:
+        raise ValueError("trace: k differs from the marks' length")
+    if not arrs and k is None:
+        raise ValueError("trace: k is needed without marks")
+    k = arrs[0].size if arrs else int(k)
+    return (np.ascontiguousarray(np.stack(arrs)) if arrs else np.zeros((0, k), np.float32)), k
+
+
+@dataclass
+class TraceResult:
+    """extracted [S][k]; sims [S][M] (the GEMM matrix, 1e-4 relative); best [S] (index of the mark a suspect carries most
+    strongly, TraceResult.NONE without one -- e.g. the unmarked original, whose similarities are all NaN); best_sim [S]
+    (Tester::similarity of that mark, exact); n_exceed [S] (marks above the threshold: 2 and more = colluders)."""
+    extracted: np.ndarray
+    sims: np.ndarray
+    best: np.ndarray
+    best_sim: np.ndarray
+    n_exceed: np.ndarray
+    threshold: float = 6.0
+    NONE = L.TRACE_NONE
+
+    @staticmethod
+    def empty(n, n_marks, k) -> "TraceResult":
+        return TraceResult(np.empty((n, k), np.float32), np.empty((n, n_marks), np.float32), np.full(n, L.TRACE_NONE, np.uint32),
+                           np.full(n, np.nan, np.float32), np.zeros(n, np.uint32))
+
+    def _args(self, m, threshold):
+        """(marks, n_marks, threshold, extracted, sims, best, best_sim, n_exceed) of the C entry points."""
+        self.threshold = float(threshold)
+        if m.shape[0] == 0:
+            return (None, 0, C.c_float(threshold), self.extracted.ctypes.data, None, None, None, None)
+        return (m.ctypes.data, m.shape[0], C.c_float(threshold), self.extracted.ctypes.data, self.sims.ctypes.data,
+                self.best.ctypes.data, self.best_sim.ctypes.data, self.n_exceed.ctypes.data)
+
+    def matches(self, s: int) -> list:
+        """Indices of the marks suspect s exceeds the threshold with (NaN never exceeds, algorithm.rs:677)."""
+        return [int(j) for j in np.nonzero(self.sims[s] > np.float32(self.threshold))[0]]
+
+
+def trace_many(base, suspects, marks, k: Optional[int] = None, threshold: float = 6.0, config: Optional[ReadConfig] = None,
+               ctx: Optional[Context] = None) -> TraceResult:
+    """`Reader::base(base, config)` once, then per suspect `extract` + `Tester::similarity` against every mark
+    (examples/main.rs:369-415) as ONE streaming call over 8-bit host images: ssw_fingerprint_trace_host_rgb8."""
+    ctx = ctx or default_context()
+    config = config or ReadConfig.default()
+    b = np.ascontiguousarray(np.asarray(base)[:, :, :3])
+    if b.dtype != np.uint8:
+        raise ValueError("base must be an 8-bit [H, W, 3] image")
+    arrs, ptrs, w, h = _frame_ptrs(suspects, b.shape[1], b.shape[0])
+    m, k = _trace_marks(marks, k)
+    res = TraceResult.empty(len(arrs), m.shape[0], k)
+    cfg = config._c()
+    check(ctx._lib.ssw_fingerprint_trace_host_rgb8(ctx.handle, C.byref(cfg), b.ctypes.data, ptrs, len(arrs), w, h, k,
+                                                   *res._args(m, threshold)), "ssw_fingerprint_trace_host_rgb8")
+    return res
 
 
 # ---- Tester (algorithm.rs:668-715) -------------------------------------------------------------

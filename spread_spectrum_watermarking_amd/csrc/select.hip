@@ -688,13 +688,8 @@ int launch_extract_pruned(hipStream_t st, const float* base, const float* compac
 // Similarity: Tester::similarity (src/algorithm.rs:702-713).  The reference accumulates both
 // sums sequentially in f32; rounding depends on that order, so it is kept: the products are
 // formed in parallel (each is a single rounding either way), one lane does the two running sums.
-__global__ __launch_bounds__(256) void similarity_kernel(const float* __restrict__ extracted,
-                                                         const float* __restrict__ marks, size_t k,
-                                                         float* __restrict__ sims) {
-    __shared__ float pn[1024], pd[1024];
-    const size_t f = blockIdx.x;
-    const float* e = extracted + f * k;
-    const float* m = marks + f * k;
+// Block-wide (any block size; pn / pd: 1024 floats of LDS each); the result is valid in thread 0.
+__device__ inline float sequential_similarity(const float* __restrict__ e, const float* __restrict__ m, size_t k, float* pn, float* pd) {
     float nominator = 0.0f, denominator = 0.0f;
     for (size_t base = 0; base < k; base += 1024) {
         const size_t n = (k - base) < 1024 ? (k - base) : 1024;
@@ -712,7 +707,16 @@ __global__ __launch_bounds__(256) void similarity_kernel(const float* __restrict
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) sims[f] = nominator / sqrtf(denominator);
+    return nominator / sqrtf(denominator);
+}
+
+__global__ __launch_bounds__(256) void similarity_kernel(const float* __restrict__ extracted,
+                                                         const float* __restrict__ marks, size_t k,
+                                                         float* __restrict__ sims) {
+    __shared__ float pn[1024], pd[1024];
+    const size_t f = blockIdx.x;
+    const float sim = sequential_similarity(extracted + f * k, marks + f * k, k, pn, pd);
+    if (threadIdx.x == 0) sims[f] = sim;
 }
 
 int launch_similarity(hipStream_t st, const float* extracted, const float* marks, size_t n_pairs,
@@ -756,6 +760,127 @@ int launch_sim_scale(hipStream_t st, float* sims, const float* den, size_t n_ext
     const size_t total = n_ext * n_marks;
     if (!total) return SSW_OK;
     sim_scale_kernel<<<(unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096), 256, 0, st>>>(sims, den, n_ext, n_marks);
+    SSW_HIP_CHECK(hipGetLastError());
+    return SSW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tracing (ssw_fingerprint_trace): ONE base plane and ONE index list against the n frames of a chunk.
+// ---------------------------------------------------------------------------------------------
+// Reader::extract_watermark (src/algorithm.rs:556-561) for every frame of the chunk with the same operands, in the same
+// extract_fn, as extract_kernel / extract_pruned_kernel on a replicated base.  A thread owns one rank i: it loads idx[i],
+// base[idx[i]] and (pruned) pos[v] once and walks the block's slice of TRACE_SLICE frames.  The derived reads are
+// scattered 4-byte gathers (one per frame, n * H * cap floats apart), so TRACE_INFLIGHT of them are issued before the
+// first is used.  PRUNED: derived value of index j = (u, v) at compact[f][u][pos[v]]; else at derived[f][j].
+constexpr unsigned TRACE_SLICE = 16, TRACE_INFLIGHT = 8;
+template <bool PRUNED>
+__global__ __launch_bounds__(256) void extract_shared_kernel(const float* __restrict__ base, const float* __restrict__ derived,
+                                                             size_t plane_len, unsigned W, unsigned H, unsigned cap,
+                                                             const uint32_t* __restrict__ pos, const uint32_t* __restrict__ indices,
+                                                             size_t k, unsigned n_frames, int method, float alpha,
+                                                             float* __restrict__ out) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= k) return;
+    const uint32_t j = indices[i];
+    const float b = base[j];
+    size_t stride = plane_len, off = j;
+    bool have = true;
+    if (PRUNED) {
+        const uint32_t u = j / W, v = j - u * W;
+        const uint32_t p = pos[v];
+        // p == none only in a call whose column set overflowed; the caller redoes that call's chunks
+        have = p != 0xFFFFFFFFu;
+        stride = (size_t)H * cap;
+        off = (size_t)u * cap + (have ? p : 0u);
+    }
+    const unsigned f0 = blockIdx.y * TRACE_SLICE;
+    const unsigned f1 = f0 + TRACE_SLICE < n_frames ? f0 + TRACE_SLICE : n_frames;
+    for (unsigned f = f0; f < f1; f += TRACE_INFLIGHT) {
+        float d[TRACE_INFLIGHT];
+#pragma unroll
+        for (unsigned q = 0; q < TRACE_INFLIGHT; ++q) {
+            const unsigned fq = f + q < f1 ? f + q : f1 - 1;            // (clamped: the tail repeats the last frame's load)
+            d[q] = derived[fq * stride + off];
+        }
+#pragma unroll
+        for (unsigned q = 0; q < TRACE_INFLIGHT; ++q)
+            if (f + q < f1) out[(size_t)(f + q) * k + i] = extract_fn(method, alpha, b, have ? d[q] : 0.0f);
+    }
+}
+
+int launch_extract_shared(hipStream_t st, const float* base, const float* derived, size_t n_frames, size_t plane_len,
+                          const uint32_t* indices, size_t k, int method, float alpha, float* out) {
+    if (n_frames == 0 || k == 0) return SSW_OK;
+    const dim3 grid((unsigned)((k + 255) / 256), (unsigned)((n_frames + TRACE_SLICE - 1) / TRACE_SLICE));
+    extract_shared_kernel<false><<<grid, 256, 0, st>>>(base, derived, plane_len, 0u, 0u, 0u, nullptr, indices, k, (unsigned)n_frames,
+                                                       method, alpha, out);
+    SSW_HIP_CHECK(hipGetLastError());
+    return SSW_OK;
+}
+
+int launch_extract_shared_pruned(hipStream_t st, const float* base, const float* compact, size_t n_frames, size_t w, size_t h,
+                                 size_t cap, const uint32_t* pos, const uint32_t* indices, size_t k, int method, float alpha,
+                                 float* out) {
+    if (n_frames == 0 || k == 0) return SSW_OK;
+    const dim3 grid((unsigned)((k + 255) / 256), (unsigned)((n_frames + TRACE_SLICE - 1) / TRACE_SLICE));
+    extract_shared_kernel<true><<<grid, 256, 0, st>>>(base, compact, w * h, (unsigned)w, (unsigned)h, (unsigned)cap, pos, indices, k,
+                                                      (unsigned)n_frames, method, alpha, out);
+    SSW_HIP_CHECK(hipGetLastError());
+    return SSW_OK;
+}
+
+// Trace finish: one wave per suspect row s of the similarity matrix sims [n_rows][n_marks].
+//   best[s]     = index of the largest non-NaN entry, the lowest index on ties; TRACE_NONE when the row has none
+//   n_exceed[s] = entries with sim > threshold (NaN never exceeds: Similarity::exceeds_sigma, src/algorithm.rs:677)
+//   best_sim[s] = Tester::similarity(extracted[s], marks[best[s]]) in the reference's sequential f32 order
+//                 (sequential_similarity: what similarity_kernel computes); NaN without a winner
+// The lanes read the row 64 consecutive floats at a time; a lane keeps its first maximum (its columns ascend), the wave
+// reduction prefers the larger value, then the lower column.  Any output may be null.
+constexpr uint32_t TRACE_NONE = 0xFFFFFFFFu;
+__global__ __launch_bounds__(64) void trace_finish_kernel(const float* __restrict__ sims, size_t n_marks, float threshold,
+                                                          const float* __restrict__ extracted, const float* __restrict__ marks,
+                                                          size_t k, uint32_t* __restrict__ best, float* __restrict__ best_sim,
+                                                          uint32_t* __restrict__ n_exceed) {
+    __shared__ float pn[1024], pd[1024];
+    const size_t s = blockIdx.x;
+    const unsigned lane = threadIdx.x;
+    const float* row = sims + s * n_marks;
+    uint32_t bi = TRACE_NONE, count = 0;
+    float bv = 0.0f;
+    for (size_t c = lane; c < n_marks; c += 64) {
+        const float v = row[c];
+        count += v > threshold ? 1u : 0u;
+        const bool take = v == v && (bi == TRACE_NONE || v > bv);
+        bv = take ? v : bv;
+        bi = take ? (uint32_t)c : bi;
+    }
+    for (int m = 1; m < 64; m <<= 1) {
+        const float ov = __shfl_xor(bv, m);
+        const uint32_t oi = __shfl_xor(bi, m);
+        count += __shfl_xor(count, m);
+        const bool take = oi != TRACE_NONE && (bi == TRACE_NONE || ov > bv || (ov == bv && oi < bi));
+        bv = take ? ov : bv;
+        bi = take ? oi : bi;
+    }
+    bi = __builtin_amdgcn_readfirstlane(bi);                // every lane holds the same winner: make the branch below provably uniform
+    if (lane == 0) {
+        if (best) best[s] = bi;
+        if (n_exceed) n_exceed[s] = count;
+    }
+    if (!best_sim) return;
+    if (bi == TRACE_NONE) {
+        if (lane == 0) best_sim[s] = __builtin_nanf("");
+        return;
+    }
+    const float sim = sequential_similarity(extracted + s * k, marks + (size_t)bi * k, k, pn, pd);
+    if (lane == 0) best_sim[s] = sim;
+}
+
+int launch_trace_finish(hipStream_t st, const float* sims, size_t n_rows, size_t n_marks, float threshold, const float* extracted,
+                        const float* marks, size_t k, uint32_t* best, float* best_sim, uint32_t* n_exceed) {
+    if (n_rows == 0 || (!best && !best_sim && !n_exceed)) return SSW_OK;
+    if (n_marks > 0xFFFFFFFEull) return SSW_ERR_BAD_DIMS;
+    trace_finish_kernel<<<(unsigned)n_rows, 64, 0, st>>>(sims, n_marks, threshold, extracted, marks, k, best, best_sim, n_exceed);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }

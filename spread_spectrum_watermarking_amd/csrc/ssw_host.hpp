@@ -150,6 +150,23 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
                        size_t n_frames, size_t w, size_t h, size_t k, float* dev_extracted, const float* dev_marks,
                        float* dev_sims);
 
+// Tracing (ssw_fingerprint_trace; ssw_pipeline.hip).  trace_base: Reader::base of ONE frame + its first k indices into the
+// context's buffers (*y, *idx), enqueued on the context's stream.  trace_extract: base.extract(Reader::derived(suspect_s), k)
+// for n suspect frames against that plane and list -- chunks on two lanes, one prune plan for the call; looks at the
+// overflow flag once when it pruned.  trace_score (ssw_lib.hip): similarity matrix + finish; sims may be null.
+int trace_base(ssw_ctx* ctx, const ssw_config& c, const void* dev_base_rgb, int u8, size_t w, size_t h, size_t k, const float** y,
+               const uint32_t** idx);
+int trace_extract(ssw_ctx* ctx, const ssw_config& c, const float* base_y, const uint32_t* base_idx, const void* dev_suspect_rgb, int u8,
+                  size_t n_frames, size_t w, size_t h, size_t k, float* dev_extracted);
+int trace_check_args(const ssw_ctx* ctx, const ssw_config* cfg, size_t w, size_t h, size_t k, const void* marks, size_t n_marks,
+                     const void* sims, const void* best, const void* best_sim, const void* n_exceed);
+int trace_score(ssw_ctx* ctx, const float* dev_extracted, size_t n_suspects, const float* dev_marks, size_t n_marks, size_t k,
+                float threshold, float* dev_sims, uint32_t* dev_best, float* dev_best_sim, uint32_t* dev_n_exceed);
+// ssw_stream.hip: the host form -- suspects through the streaming ring, the base plane and list given (device)
+int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, const uint32_t* base_idx, const uint8_t* const* host_suspects,
+                      size_t n_suspects, size_t w, size_t h, size_t k, const float* host_marks, size_t n_marks, float threshold,
+                      float* host_extracted, float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed);
+
 // fingerprint.hip: n_copies copies of one image, each Writer::result of `coef` with its own single mark embedded at `idx`
 // (marks [n_copies][mark_stride]); enqueued on the context's stream; t32: an f32 plane of scratch
 int fingerprint_copies(ssw_ctx* ctx, const ssw_config& c, const float* coef, const uint32_t* idx, size_t k_eff, const float* iq_i,

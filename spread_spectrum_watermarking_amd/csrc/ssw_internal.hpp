@@ -255,6 +255,15 @@ int launch_extract(hipStream_t st, const float* base, const float* derived, size
                    float* out);
 int launch_similarity(hipStream_t st, const float* extracted, const float* marks, size_t n_pairs,
                       size_t k, float* sims);
+// tracing (ssw_fingerprint_trace): extract with ONE base plane [plane_len] and ONE index list [k] against n_frames derived
+// planes / compact planes; the finish of the similarity matrix (argmax, count above the threshold, exact rescoring)
+int launch_extract_shared(hipStream_t st, const float* base, const float* derived, size_t n_frames, size_t plane_len,
+                          const uint32_t* indices, size_t k, int method, float alpha, float* out);
+int launch_extract_shared_pruned(hipStream_t st, const float* base, const float* compact, size_t n_frames, size_t w, size_t h,
+                                 size_t cap, const uint32_t* pos, const uint32_t* indices, size_t k, int method, float alpha,
+                                 float* out);
+int launch_trace_finish(hipStream_t st, const float* sims, size_t n_rows, size_t n_marks, float threshold, const float* extracted,
+                        const float* marks, size_t k, uint32_t* best, float* best_sim, uint32_t* n_exceed);
 int launch_gemm_nt_f32(hipStream_t st, const float* A, size_t M, const float* B, size_t N, size_t K, float* out);
 int launch_sim_den(hipStream_t st, const float* extracted, size_t n_ext, size_t k, float* den);
 int launch_sim_scale(hipStream_t st, float* sims, const float* den, size_t n_ext, size_t n_marks);
@@ -349,6 +358,9 @@ struct ssw_ctx {
     Buf small;                    // misc (mark offsets, sims, ...)
     Buf sort_scratch;             // full-order sort (lazy, Reader::indices beyond the top-k limit)
     Buf resize_tmp;               // f32 intermediate of the resize's vertical pass
+    // ssw_fingerprint_trace: what every chunk on both lanes reads -- base plane | base index list | prune tables (flag, pos,
+    // rows) | gathered bases, launch order | gathered bases, fragment order | similarity matrix when the caller wants none
+    Buf trace[6];
     Buf fingerprint[6];           // fingerprint.hip: line plan (u32) | T64 + gathered basis | Yr64 | mark deltas | dT of a group | handle output
     std::map<std::pair<size_t, size_t>, ssw::DeviceTaps> taps;   // (in_len, out_len) -> filter taps
 

@@ -200,6 +200,63 @@ int forward_from_host(ssw_ctx* ctx, const void* host_rgb, int u8, size_t w, size
     SSW_TRY(run_serial(ch, ctx->stream));
     return stage_consumed(ctx, *fs);
 }
+// ssw_similarity_matrix as it is enqueued (also the matrix of ssw_fingerprint_trace: the same three launches, the same bits)
+int similarity_matrix_enqueue(ssw_ctx* ctx, const float* dev_extracted, size_t n_extracted, const float* dev_marks, size_t n_marks,
+                              size_t k, float* dev_sims) {
+    SSW_TRY(grow(ctx->small, n_extracted * sizeof(float)));
+    StageTimer t(ctx, SSW_STAGE_SIMILARITY, ctx->stream);
+    SSW_TRY(launch_sim_den(ctx->stream, dev_extracted, n_extracted, k, (float*)ctx->small.p));
+    SSW_TRY(launch_gemm_nt_f32(ctx->stream, dev_extracted, n_extracted, dev_marks, n_marks, k, dev_sims));
+    return launch_sim_scale(ctx->stream, dev_sims, (const float*)ctx->small.p, n_extracted, n_marks);
+}
+}  // namespace
+
+// ---- tracing: what the device, host and handle forms of ssw_fingerprint_trace share ---------------------------
+namespace ssw {
+namespace host {
+int trace_check_args(const ssw_ctx* ctx, const ssw_config* cfg, size_t w, size_t h, size_t k, const void* marks, size_t n_marks,
+                     const void* sims, const void* best, const void* best_sim, const void* n_exceed) {
+    if (!ctx) return SSW_ERR_BAD_ARG;
+    if (!marks && (n_marks || sims || best || best_sim || n_exceed)) return SSW_ERR_BAD_ARG;      // extraction only
+    SSW_TRY(check_config(cfg));
+    if (w == 0 || h == 0) return SSW_ERR_BAD_DIMS;
+    if (k >= w * h) return SSW_ERR_K_TOO_LARGE;                        // :553-555
+    return SSW_OK;
+}
+
+// sims[s][j] = Tester::new(ext_s).similarity(mark_j) (:696-714) as ssw_similarity_matrix computes it, then the finish kernel.
+// Without marks or without a mark entry (k == 0: every similarity is 0 / sqrt(0)) no row has a winner.
+int trace_score(ssw_ctx* ctx, const float* dev_extracted, size_t n_suspects, const float* dev_marks, size_t n_marks, size_t k,
+                float threshold, float* dev_sims, uint32_t* dev_best, float* dev_best_sim, uint32_t* dev_n_exceed) {
+    if (n_suspects == 0 || (!dev_sims && !dev_best && !dev_best_sim && !dev_n_exceed)) return SSW_OK;
+    float* sims = dev_sims;
+    if (!sims && n_marks) {
+        SSW_TRY(grow(ctx->trace[5], n_suspects * n_marks * sizeof(float)));
+        sims = (float*)ctx->trace[5].p;
+    }
+    if (n_marks && k) SSW_TRY(similarity_matrix_enqueue(ctx, dev_extracted, n_suspects, dev_marks, n_marks, k, sims));
+    else if (n_marks) { SSW_HIP_CHECK(hipMemsetAsync(sims, 0xFF, n_suspects * n_marks * sizeof(float), ctx->stream)); untimed_work(ctx); }   // NaN
+    StageTimer t(ctx, SSW_STAGE_SIMILARITY, ctx->stream);
+    return launch_trace_finish(ctx->stream, sims, n_suspects, k ? n_marks : 0, threshold, dev_extracted, dev_marks, k, dev_best, dev_best_sim,
+                               dev_n_exceed);
+}
+}  // namespace host
+}  // namespace ssw
+
+namespace {
+int fingerprint_trace_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base_rgb, const void* dev_suspect_rgb, int u8,
+                           size_t n_suspects, size_t w, size_t h, size_t k, const float* dev_marks, size_t n_marks, float threshold,
+                           float* dev_extracted, float* dev_sims, uint32_t* dev_best, float* dev_best_sim, uint32_t* dev_n_exceed) {
+    if (!ctx || !dev_base_rgb || !dev_suspect_rgb || !dev_extracted) return SSW_ERR_BAD_ARG;
+    SSW_TRY(trace_check_args(ctx, cfg, w, h, k, dev_marks, n_marks, dev_sims, dev_best, dev_best_sim, dev_n_exceed));
+    if (n_suspects == 0) return SSW_OK;
+    CtxGuard g(ctx);
+    const float* yb = nullptr;
+    const uint32_t* idx = nullptr;
+    SSW_TRY(trace_base(ctx, *cfg, dev_base_rgb, u8, w, h, k, &yb, &idx));
+    SSW_TRY(trace_extract(ctx, *cfg, yb, idx, dev_suspect_rgb, u8, n_suspects, w, h, k, dev_extracted));
+    return trace_score(ctx, dev_extracted, n_suspects, dev_marks, n_marks, k, threshold, dev_sims, dev_best, dev_best_sim, dev_n_exceed);
+}
 }  // namespace
 
 // ---- library / context ----------------------------------------------------------------------
@@ -332,6 +389,7 @@ int ssw_ctx_destroy(ssw_ctx* ctx) {
     release(ctx->sort_scratch);
     release(ctx->resize_tmp);
     for (auto& b : ctx->fingerprint) release(b);
+    for (auto& b : ctx->trace) release(b);
     for (auto& kv : ctx->taps) { (void)hipFree(kv.second.left); (void)hipFree(kv.second.count); (void)hipFree(kv.second.weights); }
     for (auto& e : ctx->sync_events) (void)hipEventDestroy(e);
     for (auto& p : ctx->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -627,11 +685,7 @@ int ssw_similarity_matrix(ssw_ctx* ctx, const float* dev_extracted, size_t n_ext
     if (!ctx || !dev_extracted || !dev_marks || !dev_sims) return SSW_ERR_BAD_ARG;
     if (n_extracted == 0 || n_marks == 0) return SSW_OK;
     CtxGuard g(ctx);
-    SSW_TRY(grow(ctx->small, n_extracted * sizeof(float)));
-    StageTimer t(ctx, SSW_STAGE_SIMILARITY, ctx->stream);
-    SSW_TRY(launch_sim_den(ctx->stream, dev_extracted, n_extracted, k, (float*)ctx->small.p));
-    SSW_TRY(launch_gemm_nt_f32(ctx->stream, dev_extracted, n_extracted, dev_marks, n_marks, k, dev_sims));
-    return launch_sim_scale(ctx->stream, dev_sims, (const float*)ctx->small.p, n_extracted, n_marks);
+    return similarity_matrix_enqueue(ctx, dev_extracted, n_extracted, dev_marks, n_marks, k, dev_sims);
 }
 
 // ---- whole path, batched (ssw_pipeline.hip) ------------------------------------------------
@@ -702,6 +756,42 @@ int ssw_batch_extract_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* d
                            float* dev_extracted, const float* dev_marks, float* dev_sims) {
     return batch_extract_impl(ctx, cfg, dev_base_rgb, dev_derived_rgb, SSW_PIX_U8, n_frames, w, h, k, dev_extracted,
                               dev_marks, dev_sims);
+}
+
+// ---- tracing: one base frame, many suspects, many stored marks (ssw_pipeline.hip: trace_base / trace_extract) ----
+int ssw_fingerprint_trace(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_base_rgb, const float* dev_suspect_rgb,
+                          size_t n_suspects, size_t w, size_t h, size_t k, const float* dev_marks, size_t n_marks,
+                          float threshold, float* dev_extracted, float* dev_sims, uint32_t* dev_best, float* dev_best_sim,
+                          uint32_t* dev_n_exceed) {
+    return fingerprint_trace_impl(ctx, cfg, dev_base_rgb, dev_suspect_rgb, SSW_PIX_F32, n_suspects, w, h, k, dev_marks, n_marks, threshold,
+                                  dev_extracted, dev_sims, dev_best, dev_best_sim, dev_n_exceed);
+}
+
+int ssw_fingerprint_trace_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* dev_base_rgb, const uint8_t* dev_suspect_rgb,
+                               size_t n_suspects, size_t w, size_t h, size_t k, const float* dev_marks, size_t n_marks,
+                               float threshold, float* dev_extracted, float* dev_sims, uint32_t* dev_best,
+                               float* dev_best_sim, uint32_t* dev_n_exceed) {
+    return fingerprint_trace_impl(ctx, cfg, dev_base_rgb, dev_suspect_rgb, SSW_PIX_U8, n_suspects, w, h, k, dev_marks, n_marks, threshold,
+                                  dev_extracted, dev_sims, dev_best, dev_best_sim, dev_n_exceed);
+}
+
+// Host form: the base through the handles' staging (one upload, one transform), the suspects through the streaming ring.
+int ssw_fingerprint_trace_host_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* host_base,
+                                    const uint8_t* const* host_suspects, size_t n_suspects, size_t w, size_t h, size_t k,
+                                    const float* host_marks, size_t n_marks, float threshold, float* host_extracted,
+                                    float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed) {
+    if (!ctx || !host_base || (n_suspects && !host_suspects)) return SSW_ERR_BAD_ARG;
+    SSW_TRY(trace_check_args(ctx, cfg, w, h, k, host_marks, n_marks, host_sims, host_best, host_best_sim, host_n_exceed));
+    if (n_suspects == 0) return SSW_OK;
+    CtxGuard g(ctx);
+    ssw_ctx::FrameStage* fs = nullptr;
+    SSW_TRY(stage_frame_in(ctx, host_base, w * h * 3, &fs));
+    const float* yb = nullptr;
+    const uint32_t* idx = nullptr;
+    SSW_TRY(trace_base(ctx, *cfg, fs->buf.p, SSW_PIX_U8, w, h, k, &yb, &idx));
+    SSW_TRY(stage_consumed(ctx, *fs));
+    return stream_trace_rgb8(ctx, *cfg, yb, idx, host_suspects, n_suspects, w, h, k, host_marks, n_marks, threshold, host_extracted,
+                             host_sims, host_best, host_best_sim, host_n_exceed);
 }
 
 // ---- 16-bit boundary (`into_rgb32f()` of an Rgb16 image, v / 65535, fused into the first operand
@@ -1141,6 +1231,23 @@ int ssw_reader_extract(ssw_reader* base, ssw_reader* derived, float* out, size_t
                                base->cfg.alpha, (float*)ctx->small.p));
     }
     return ssw_copy_to_host(ctx, out, ctx->small.p, k * sizeof(float));
+}
+
+// Reader::extract against many derived frames + Tester::similarity against many marks (:529-539, :696-714): the reader's
+// plane and its index list are the base of the trace
+int ssw_reader_trace_host_rgb8(ssw_reader* base, const uint8_t* const* host_suspects, size_t n_suspects, size_t k,
+                               const float* host_marks, size_t n_marks, float threshold, float* host_extracted,
+                               float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed) {
+    if (!base || (n_suspects && !host_suspects)) return SSW_ERR_BAD_ARG;
+    if (!base->is_base) return SSW_ERR_NOT_BASE;                                          // :530
+    ssw_ctx* ctx = base->ctx;
+    SSW_TRY(trace_check_args(ctx, &base->cfg, base->w, base->h, k, host_marks, n_marks, host_sims, host_best, host_best_sim, host_n_exceed));
+    if (n_suspects == 0) return SSW_OK;
+    CtxGuard g(ctx);
+    if (k) SSW_TRY(reader_ensure_indices(base, k));
+    ctx->expected_k = k ? k : ctx->expected_k;
+    return stream_trace_rgb8(ctx, base->cfg, base->y, base->idx, host_suspects, n_suspects, base->w, base->h, k, host_marks, n_marks,
+                             threshold, host_extracted, host_sims, host_best, host_best_sim, host_n_exceed);
 }
 
 int ssw_reader_destroy(ssw_reader* rd) {

@@ -1024,19 +1024,31 @@ PruneSetup make_prune_setup(const ssw_ctx* ctx, bool f64, size_t n, size_t w, si
     return ps;
 }
 
+// One prune plan for a whole call (ssw_fingerprint_trace: every chunk on both lanes reads ONE index list): the tables and the
+// gathered bases live in the context and are built once -- `build`: the chain gets that one stage (idx = the one list) and
+// nothing else; otherwise the chunk's chain starts at the pre-pass and reads them.
+struct PruneShared {
+    ssw_ctx::Buf *u32, *gathered, *gathered_frag;      // tables | bases in launch order | in the fused pass's fragment order
+    bool build;
+};
+
 // derived rgb frames -> compact coefficient plane ws.compact[1] [n][h][cap_total] holding, for every
 // frequency column the chunk's index lists use, the column the full (f64: make_prune_setup) transform would produce
 int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u8, size_t n, size_t w, size_t h, size_t k,
-                         const uint32_t* idx, const PruneSetup& ps, uint32_t* info, Chain& ch) {
+                         const uint32_t* idx, const PruneSetup& ps, uint32_t* info, Chain& ch, const PruneShared* sh = nullptr) {
     const PrunePlan plan = ps.plan;
     const size_t cap = plan.cap_total;
     const size_t bytes = dct_pair_operand_elems(n, w, h) * sizeof(double);
     const int levels = ps.rows.levels;
     const bool deep = plan_is_deep(ps.rows), level2 = plan_is_level2(ps.rows);
-    if (!deep) for (int b = 0; b < 4; ++b) SSW_TRY(grow(ws.operand[b], bytes));      // the deep pre-pass writes into operand[5] only
-    for (int b = 0; b < 2; ++b) SSW_TRY(grow(ws.compact[b], n * h * cap * sizeof(float)));
-    SSW_TRY(grow(ws.prune_u32, (2 * w + cap + 64) * sizeof(uint32_t)));
-    uint32_t* flag = (uint32_t*)ws.prune_u32.p;
+    const bool tables_only = sh && sh->build, per_chunk = !sh;
+    if (!tables_only) {
+        if (!deep) for (int b = 0; b < 4; ++b) SSW_TRY(grow(ws.operand[b], bytes));      // the deep pre-pass writes into operand[5] only
+        for (int b = 0; b < 2; ++b) SSW_TRY(grow(ws.compact[b], n * h * cap * sizeof(float)));
+    }
+    ssw_ctx::Buf& u32buf = sh ? *sh->u32 : ws.prune_u32;
+    SSW_TRY(grow(u32buf, (2 * w + cap + 64) * sizeof(uint32_t)));
+    uint32_t* flag = (uint32_t*)u32buf.p;
     uint32_t* pos = flag + w;
     uint32_t* rows = pos + w;
     // class of the plan -> image operand plane(s), cached basis plane(s), padded / true sum length: the launch classes of
@@ -1053,8 +1065,10 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u
         SSW_TRY(get_basis(ctx, w, false, true, BasisKind::Rot, &rot));
         if (deep) SSW_TRY(get_basis(ctx, w / 2, false, true, BasisKind::Rot, &rot2));
         if (level2) SSW_TRY(get_basis(ctx, w / 4, false, true, BasisKind::Rot, &rot3));
-        SSW_TRY(grow(ws.operand[5], split_scratch_elems(n, w, h) * sizeof(double)));
-        sp = (double*)ws.operand[5].p;
+        if (!tables_only) {
+            SSW_TRY(grow(ws.operand[5], split_scratch_elems(n, w, h) * sizeof(double)));
+            sp = (double*)ws.operand[5].p;
+        }
     }
     PairPlanes pp;
     pp.sp = pp.l2 = sp;
@@ -1093,8 +1107,12 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u
         goff[c] = gtotal; gtotal += cs[c].kp * cap16 * sizeof(double);
         goff2[c] = gtotal; if (cs[c].x2) gtotal += cs[c].kp * cap16 * sizeof(double);
     }
-    SSW_TRY(grow(ws.gathered, gtotal));
-    char* gathered = (char*)ws.gathered.p;
+    // (the two orders of the gathered bases share one buffer per chunk: a chunk takes one path; a call-wide plan keeps both,
+    // since the last, shorter chunk may take the other one)
+    SSW_TRY(grow(sh ? *sh->gathered : ws.gathered, gtotal));
+    if (sh && level2) SSW_TRY(grow(*sh->gathered_frag, gtotal));
+    char* gathered = (char*)(sh ? sh->gathered->p : ws.gathered.p);
+    char* gathered_frag = sh ? (char*)sh->gathered_frag->p : gathered;
     float* t_compact = (float*)ws.compact[0].p;
     double *o0 = (double*)ws.operand[0].p, *o1 = (double*)ws.operand[1].p, *o2 = (double*)ws.operand[2].p, *o3 = (double*)ws.operand[3].p;
     const double px = (double)n * (double)w * (double)h;
@@ -1106,27 +1124,38 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u
         jobs.n = 0;
         for (unsigned c = 0; c < plan.n_classes; ++c) {
             const unsigned kblocks = (unsigned)(cs[c].kp / KBlock<double>::KB);
-            jobs.j[jobs.n++] = {rows + plan.c[c].off, (const char*)cs[c].basis, gathered + goff[c], plan.c[c].cap, (unsigned)cs[c].src_rows, kblocks, 0u, false, frag};
-            if (cs[c].x2) jobs.j[jobs.n++] = {rows + plan.c[c].off, (const char*)cs[c].basis2, gathered + goff2[c], plan.c[c].cap, (unsigned)cs[c].src_rows, kblocks, 0u, true, frag};
+            char* dst = frag ? gathered_frag : gathered;
+            jobs.j[jobs.n++] = {rows + plan.c[c].off, (const char*)cs[c].basis, dst + goff[c], plan.c[c].cap, (unsigned)cs[c].src_rows, kblocks, 0u, false, frag};
+            if (cs[c].x2) jobs.j[jobs.n++] = {rows + plan.c[c].off, (const char*)cs[c].basis2, dst + goff2[c], plan.c[c].cap, (unsigned)cs[c].src_rows, kblocks, 0u, true, frag};
         }
         return jobs;
     };
+    if (tables_only) {
+        ch.push_back({true, [=](hipStream_t st) -> int {
+            untimed_work(ctx);
+            SSW_TRY(launch_prune_build(st, idx, 1, k, plan, flag, rows, pos, info));
+            SSW_TRY(launch_prune_gather_bases(st, gather_jobs(false)));
+            return level2 ? launch_prune_gather_bases(st, gather_jobs(true)) : SSW_OK;
+        }});
+        return SSW_OK;
+    }
     // r5: marks of up to 1024 entries at level 2 -- the whole row pass in one kernel (dct_pair_derived.hip): no operand planes
     if (level2) {
         DerivedFusedClass fc[9];
         for (unsigned c = 0; c < plan.n_classes; ++c)
-            fc[c] = {(const double*)(gathered + goff[c]), cs[c].x2 ? (const double*)(gathered + goff2[c]) : nullptr, (unsigned)pn1[c],
+            fc[c] = {(const double*)(gathered_frag + goff[c]), cs[c].x2 ? (const double*)(gathered_frag + goff2[c]) : nullptr, (unsigned)pn1[c],
                      (unsigned)(pn2[c] < 0 ? 0 : pn2[c]), plan.c[c].cap, plan.c[c].off, cs[c].x2 != nullptr};
         // (a single frame is 135 blocks of 16 lines for 256 CUs: the merged launches below are 35 us faster there)
         if (plan_derived_fused(ps.rows, lines) && dct_pair_derived_fused_fits(plan.n_classes, fc)) {
             const unsigned ncl = plan.n_classes;
             std::array<DerivedFusedClass, 9> fca;
             for (unsigned c = 0; c < 9; ++c) fca[c] = fc[c < ncl ? c : 0];
-            ch.push_back({true, [=](hipStream_t st) -> int {
-                untimed_work(ctx);
-                SSW_TRY(launch_prune_build(st, idx, n, k, plan, flag, rows, pos, info));
-                return launch_prune_gather_bases(st, gather_jobs(true));
-            }});
+            if (per_chunk)
+                ch.push_back({true, [=](hipStream_t st) -> int {
+                    untimed_work(ctx);
+                    SSW_TRY(launch_prune_build(st, idx, n, k, plan, flag, rows, pos, info));
+                    return launch_prune_gather_bases(st, gather_jobs(true));
+                }});
             const double in_bytes = px * 3.0 * (double)pix_bytes(u8);
             // (timed with the RGB pre-passes: an HBM-bound kernel -- frames in, compact plane out -- whose 0.1e12 flop ride along;
             // bench.py's GEMM family stays "every pair_gemm_f64_kernel launch")
@@ -1142,8 +1171,10 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u
     }
     // the set of columns, then Reader::derived's colour conversion + operand pre-pass (same kernels as the full path)
     ch.push_back({true, [=](hipStream_t st) -> int {
-        SSW_TRY(launch_prune_build(st, idx, n, k, plan, flag, rows, pos, info));
-        untimed_work(ctx);
+        if (per_chunk) {
+            SSW_TRY(launch_prune_build(st, idx, n, k, plan, flag, rows, pos, info));
+            untimed_work(ctx);
+        }
         StageTimer t(ctx, SSW_STAGE_RGB_TO_YIQ, st, prep_bytes);
         if (deep) return launch_dct_pair_prep16_rows(st, pix_src_kind(u8), rgb, n, w, h, sp, (const double*)rot, (const double*)rot2,
                                                      (const double*)rot3, nullptr, nullptr, level2);
@@ -1153,8 +1184,10 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u
     }});
     ch.back().tag = 2;
     ch.push_back({false, [=](hipStream_t st) -> int {
-        SSW_TRY(launch_prune_gather_bases(st, gather_jobs(false)));
-        untimed_work(ctx);
+        if (per_chunk) {
+            SSW_TRY(launch_prune_gather_bases(st, gather_jobs(false)));
+            untimed_work(ctx);
+        }
         StageTimer t(ctx, SSW_STAGE_DCT_ROW, st, flop);
         t.traffic(px * 8.0 + (double)lines * (double)cap * 4.0);      // every operand plane once in, the compact plane out
         if (plan_merge(lines)) {          // a single frame: the classes side by side in one launch per kind
@@ -1333,6 +1366,98 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         for (unsigned q = 0; q < ps.plan.n_classes; ++q) ctx->pruned_columns += info[ci * SSW_PRUNE_INFO + 1 + q];
         if (info[ci * SSW_PRUNE_INFO] == 0) continue;
         ctx->redone_chunks++;
+        Chain ch;
+        SSW_TRY(build_chunk(ci, ctx->lane[0], ch, false));
+        SSW_TRY(run_serial(ch, ctx->stream));
+    }
+    return SSW_OK;
+}
+
+// ---- one base frame against many suspect frames (ssw_fingerprint_trace) -----------------------------------------
+// Reader::base of the one original (:474-480, :493): plane and index list into buffers the CONTEXT owns -- every chunk on
+// both lanes reads them.  On the context's stream, with lane 0's workspace (the suspects' pipeline starts behind it).
+int trace_base(ssw_ctx* ctx, const ssw_config& c, const void* dev_base_rgb, int u8, size_t w, size_t h, size_t k, const float** y,
+               const uint32_t** idx) {
+    const size_t plane = w * h;
+    ssw_ctx::Lane& ws = ctx->lane[0];
+    SSW_TRY(grow(ctx->trace[0], plane * sizeof(float)));
+    SSW_TRY(grow(ctx->trace[1], std::max<size_t>(k, 1) * sizeof(uint32_t)));
+    SSW_TRY(grow(ws.plane[2], plane * sizeof(float)));
+    float* yb = (float*)ctx->trace[0].p;
+    uint32_t* ib = (uint32_t*)ctx->trace[1].p;
+    Chain ch;
+    SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_base_rgb, u8, 1, w, h, yb, nullptr, nullptr, (float*)ws.plane[2].p, ch));
+    SSW_TRY(run_serial(ch, ctx->stream));
+    if (k > 0) SSW_TRY(topk(ctx, ctx->stream, ws.sel, yb, 1, w, h, c.ordering, k, ib));
+    *y = yb;
+    *idx = ib;
+    return SSW_OK;
+}
+
+// base.extract(Reader::derived(suspect_s), k) for n_frames suspects (:529-561): the derived half of batch_extract_impl --
+// same chunks, same lanes, same kernels up to the compact plane -- with the prune tables and gathered bases made once for
+// the call (one list: the column set cannot grow with the batch, and there is one overflow flag) and the extraction that
+// reads every base value once per slice of frames.
+int trace_extract(ssw_ctx* ctx, const ssw_config& c, const float* yb, const uint32_t* idx, const void* dev_suspect_rgb, int u8,
+                  size_t n_frames, size_t w, size_t h, size_t k, float* dev_extracted) {
+    if (n_frames == 0) return SSW_OK;
+    const size_t plane = w * h;
+    const size_t chunk = effective_chunk(ctx, w, h, n_frames);
+    const size_t n_chunks = (n_frames + chunk - 1) / chunk;
+    const bool f64 = c.precision == SSW_PRECISION_F64;
+    const size_t px_bytes = 3 * pix_bytes(u8);
+    // (a captured stream cannot be waited for: full transform, as in batch_extract_impl)
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &capture) != hipSuccess) { (void)hipGetLastError(); capture = hipStreamCaptureStatusNone; }
+    const PruneSetup ps = capture != hipStreamCaptureStatusNone ? PruneSetup()
+                          : make_prune_setup(ctx, f64, std::min(chunk, n_frames), w, h, k, yb, yb, dev_suspect_rgb, u8);
+    uint32_t* info = nullptr;
+    const PruneShared shared{&ctx->trace[2], &ctx->trace[3], &ctx->trace[4], false};
+    if (ps.on) {
+        SSW_TRY(grow(ctx->overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));
+        info = (uint32_t*)ctx->overflow.p;
+        PruneShared make = shared;
+        make.build = true;
+        Chain ch;
+        SSW_TRY(build_pruned_derived(ctx, ctx->lane[0], dev_suspect_rgb, u8, 1, w, h, k, idx, ps, info, ch, &make));
+        SSW_TRY(run_serial(ch, ctx->stream));
+    }
+    auto build_chunk = [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch, bool pruned) -> int {
+        const size_t f0 = ci * chunk, n = std::min(chunk, n_frames - f0);
+        const char* srgb = static_cast<const char*>(dev_suspect_rgb) + f0 * plane * px_bytes;
+        float* ext = dev_extracted + f0 * k;
+        if (!pruned) {
+            for (int p : {1, 2}) SSW_TRY(grow(ws.plane[p], chunk * plane * sizeof(float)));
+            float* yd = (float*)ws.plane[1].p;
+            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, srgb, u8, n, w, h, yd, nullptr, nullptr, (float*)ws.plane[2].p, ch));   // Reader::derived
+            ch.push_back({true, [=](hipStream_t st) -> int {
+                StageTimer t(ctx, SSW_STAGE_EXTRACT, st);                           // :529-539
+                return launch_extract_shared(st, yb, yd, n, plane, idx, k, c.method, c.alpha, ext);
+            }});
+            return SSW_OK;
+        }
+        SSW_TRY(build_pruned_derived(ctx, ws, srgb, u8, n, w, h, k, idx, ps, info, ch, &shared));
+        const float* compact = (const float*)ws.compact[1].p;
+        const uint32_t* pos = (const uint32_t*)ctx->trace[2].p + w;
+        const size_t cap = ps.plan.cap_total;
+        ch.push_back({true, [=](hipStream_t st) -> int {
+            StageTimer t(ctx, SSW_STAGE_EXTRACT, st);                               // :529-539, derived values from the compact plane
+            return launch_extract_shared_pruned(st, yb, compact, n, w, h, cap, pos, idx, k, c.method, c.alpha, ext);
+        }});
+        return SSW_OK;
+    };
+    SSW_TRY(run_pipeline(ctx, n_chunks, [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch) { return build_chunk(ci, ws, ch, ps.on); }));
+    if (!ps.on) return SSW_OK;
+    // One flag for the call: a column set that did not fit the compact plane means every chunk is redone with the full
+    // transform.  The one place the call waits for the device.
+    uint32_t host_info[SSW_PRUNE_INFO];
+    SSW_HIP_CHECK(hipMemcpyAsync(host_info, info, sizeof(host_info), hipMemcpyDeviceToHost, ctx->stream));
+    SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ctx->pruned_chunks += n_chunks;
+    for (unsigned q = 0; q < ps.plan.n_classes; ++q) ctx->pruned_columns += host_info[1 + q];
+    if (host_info[0] == 0) return SSW_OK;
+    ctx->redone_chunks += n_chunks;
+    for (size_t ci = 0; ci < n_chunks; ++ci) {
         Chain ch;
         SSW_TRY(build_chunk(ci, ctx->lane[0], ch, false));
         SSW_TRY(run_serial(ch, ctx->stream));

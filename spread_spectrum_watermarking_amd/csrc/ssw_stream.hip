@@ -189,6 +189,66 @@ int stream_extract_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* cons
     return stream_drain(ctx, body());
 }
 
+// ssw_fingerprint_trace on host suspects: the base plane and list are on the device already (made once by the caller);
+// the suspects cross PCIe in the groups of stream_extract_rgb8 (upload of group g + 1 under the kernels of group g), the
+// marks once; the similarity matrix and its finish run over all suspects at the end, like the device form.
+int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, const uint32_t* base_idx, const uint8_t* const* host_suspects,
+                      size_t n_suspects, size_t w, size_t h, size_t k, const float* host_marks, size_t n_marks, float threshold,
+                      float* host_extracted, float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed) {
+    for (size_t f = 0; f < n_suspects; ++f) if (!host_suspects[f]) return SSW_ERR_BAD_ARG;
+    SSW_TRY(stream_setup(ctx));
+    ssw_ctx::HostStream& hs = ctx->hs;
+    struct Active { bool& a; explicit Active(bool& x) : a(x) { a = true; } ~Active() { a = false; } } active_guard(hs.active);
+    const size_t fb = w * h * 3, G = stream_group(w, h, n_suspects);
+    const std::vector<Group> groups = stream_groups(w, h, n_suspects, false);
+    const size_t n_groups = groups.size();
+    const bool score = host_sims || host_best || host_best_sim || host_n_exceed;
+    for (int s = 0; s < (int)std::min<size_t>(n_groups, NB); ++s) SSW_TRY(grow(hs.in[s], G * fb));
+    SSW_TRY(grow(hs.ext, std::max<size_t>(n_suspects * k * sizeof(float), 16)));
+    if (n_marks) SSW_TRY(grow(hs.marks, std::max<size_t>(n_marks * k * sizeof(float), 16)));
+    // results behind the extracted marks' buffer would move it: sims | best | best_sim | n_exceed in one block of their own
+    const size_t sims_bytes = (n_suspects * n_marks * sizeof(float) + 15) / 16 * 16, row_bytes = (n_suspects * 4 + 15) / 16 * 16;
+    if (score) SSW_TRY(grow(hs.sims, sims_bytes + 3 * row_bytes));
+    float* d_sims = score && n_marks ? (float*)hs.sims.p : nullptr;
+    uint32_t* d_best = score ? (uint32_t*)((char*)hs.sims.p + sims_bytes) : nullptr;
+    float* d_best_sim = score ? (float*)((char*)hs.sims.p + sims_bytes + row_bytes) : nullptr;
+    uint32_t* d_exceed = score ? (uint32_t*)((char*)hs.sims.p + sims_bytes + 2 * row_bytes) : nullptr;
+    auto body = [&]() -> int {
+        bool as = false;
+        if (n_marks && k) SSW_TRY(upload_nowait(ctx, hs.marks.p, host_marks, n_marks * k * sizeof(float), ctx->stream, &as));
+        auto h2d = [&](size_t g) -> int {
+            const int s = (int)(g % NB);
+            const size_t f0 = groups[g].f0, n = groups[g].n;
+            if (g >= (size_t)NB) SSW_HIP_CHECK(hipStreamWaitEvent(ctx->copy_stream, hs.k_done[s], 0));
+            for (size_t j = 0; j < n; ++j) SSW_TRY(upload_nowait(ctx, (char*)hs.in[s].p + j * fb, host_suspects[f0 + j], fb, ctx->copy_stream, &as));
+            SSW_HIP_CHECK(hipEventRecord(hs.up_done[s], ctx->copy_stream));
+            return SSW_OK;
+        };
+        for (size_t g = 0; g + 1 < (size_t)NB && g < n_groups; ++g) SSW_TRY(h2d(g));
+        for (size_t g = 0; g < n_groups; ++g) {
+            const int s = (int)(g % NB);
+            const size_t f0 = groups[g].f0, n = groups[g].n;
+            if (g + NB - 1 < n_groups) SSW_TRY(h2d(g + NB - 1));      // (before this group's look at its overflow flag: PCIe keeps running)
+            SSW_HIP_CHECK(hipStreamWaitEvent(ctx->stream, hs.up_done[s], 0));
+            untimed_work(ctx);
+            SSW_TRY(trace_extract(ctx, c, base_y, base_idx, hs.in[s].p, SSW_PIX_U8, n, w, h, k, (float*)hs.ext.p + f0 * k));
+            SSW_HIP_CHECK(hipEventRecord(hs.k_done[s], ctx->stream));
+            untimed_work(ctx);
+        }
+        if (score)
+            SSW_TRY(trace_score(ctx, (const float*)hs.ext.p, n_suspects, n_marks ? (const float*)hs.marks.p : nullptr, n_marks, k, threshold, d_sims,
+                                d_best, d_best_sim, d_exceed));
+        // (the context's stream: everything above is ordered on it)
+        if (k && host_extracted) SSW_TRY(download_nowait(ctx, host_extracted, hs.ext.p, n_suspects * k * sizeof(float), ctx->stream, &as));
+        if (host_sims && n_marks) SSW_TRY(download_nowait(ctx, host_sims, d_sims, n_suspects * n_marks * sizeof(float), ctx->stream, &as));
+        if (host_best) SSW_TRY(download_nowait(ctx, host_best, d_best, n_suspects * sizeof(uint32_t), ctx->stream, &as));
+        if (host_best_sim) SSW_TRY(download_nowait(ctx, host_best_sim, d_best_sim, n_suspects * sizeof(float), ctx->stream, &as));
+        if (host_n_exceed) SSW_TRY(download_nowait(ctx, host_n_exceed, d_exceed, n_suspects * sizeof(uint32_t), ctx->stream, &as));
+        return SSW_OK;
+    };
+    return stream_drain(ctx, body());
+}
+
 }  // namespace host
 }  // namespace ssw
 
