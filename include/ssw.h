@@ -462,6 +462,59 @@ int ssw_reader_trace_host_rgb8(ssw_reader* base, const uint8_t* const* host_susp
                                const float* host_marks, size_t n_marks, float threshold, float* host_extracted,
                                float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed);
 
+/* ---- tracing attacked copies: resized and cropped suspects are restored on the device ---- */
+/* A leaked copy is rarely pixel-aligned with the original.  The reference's two attack tests are the recipe: resize the
+   suspect back to the original's size with CatmullRom (tests/attack_resize.rs:31-36), and "complement the attacked image
+   with the original to fill in the blanks" with Pixel::blend (tests/attack_crop.rs:56-70); then extract as usual.
+   A placement says what a suspect is and where it lies in the original's frame. */
+typedef struct ssw_placement {
+    uint32_t w, h, channels;   /* the suspect as it is: [h][w][channels] u8, channels 3 (RGB) or 4 (RGBA) */
+    uint32_t x, y, pw, ph;     /* the rectangle of the original's frame it covers; pw = ph = 0: its own size w, h */
+} ssw_placement;
+/* restore(original O [h][w][3], suspect S, placement) for n suspects -> dev_out [n][h][w][3]
+   (tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70):
+     1. R = S when (pw, ph) == (S.w, S.h), else imageops::resize(S, pw, ph, CatmullRom): every channel, alpha included,
+        filtered on its own with the same taps, clamped and rounded exactly as ssw_resize_rgb8 does (the two share
+        csrc/resize_common.hpp);
+     2. out = O outside the rectangle (x, y, pw, ph); inside it out = R for 3 channels and rgb(blend(opaque O, R)) for 4,
+        blend = Rgba<u8>::blend of `image 0.24.3`: a == 0 gives O, a == 255 gives R, otherwise in f32, un-fused, in this order
+            bg = O / 255, fg = R / 255, fa = a / 255, ba = 1;  af = ba + fa - ba * fa;
+            out_c = ((fg_c * fa) + (bg_c * ba) * (1 - fa)) / af;  byte = 255 * out_c truncated toward zero.
+   Third-party arithmetic restated from the crate's published behaviour, like the resize: parity unpinned (the reference's
+   own test only exercises alpha 0 and 255); the formula above is the contract, and the result equals this recipe bit for bit.
+   dev_suspects / placements: HOST arrays of n device pointers / n placements.  No alignment is assumed of any pointer,
+   x, w * channels or the frame's w * 3.  A suspect with 3 channels, the frame's size and the whole-frame placement is
+   copied, not touched by any restore launch.  Enqueues on the context's stream like ssw_resize_rgb8 (no host
+   synchronisation, except the one that uploads a tap table the context has not cached yet); launch descriptors travel as
+   kernel arguments, 32 suspects per launch.  SSW_ERR_BAD_ARG: a rectangle that leaves the frame, channels not 3 or 4, any
+   zero size; n == 0: SSW_OK.  Timed as SSW_STAGE_RESIZE. */
+int ssw_restore_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, size_t h, const void* const* dev_suspects,
+                     const ssw_placement* placements, size_t n, uint8_t* dev_out);
+/* ssw_fingerprint_trace_host_rgb8 on suspects that are restored first (tests/attack_resize.rs:31-36,
+   tests/attack_crop.rs:56-70, then algorithm.rs:462-562, :696-714): host_suspects[s] is [placements[s].h][placements[s].w]
+   [placements[s].channels] u8.  Equals ssw_fingerprint_trace_host_rgb8 run on the frames ssw_restore_rgb8 produces, bit for
+   bit in all five outputs; results are in the order of host_suspects, whatever grouping happens inside.  A suspect with
+   3 channels, the frame's size and the whole-frame placement is not touched by any restore launch: a call made only of
+   such suspects gives today's trace, bit for bit.  Suspects of different sizes stream through the ring of
+   ssw_batch_extract_host_rgb8 as they are (upload of group g + 1 under the kernels of group g; the raw slots are sized
+   for the largest suspect of the call) and are restored into the group's frames on the device: the workspace stays
+   bounded for any n_suspects.  Status codes: placements as ssw_restore_rgb8 (SSW_ERR_BAD_ARG); n_suspects == 0 SSW_OK;
+   the rest as the trace forms (SSW_ERR_K_TOO_LARGE, SSW_ERR_UNSUPPORTED for Custom).  Restore launches are timed as
+   SSW_STAGE_RESIZE. */
+int ssw_fingerprint_trace_restored_host_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* host_base, size_t w, size_t h,
+                                             const uint8_t* const* host_suspects, const ssw_placement* placements,
+                                             size_t n_suspects, size_t k, const float* host_marks, size_t n_marks,
+                                             float threshold, float* host_extracted, float* host_sims, uint32_t* host_best,
+                                             float* host_best_sim, uint32_t* host_n_exceed);
+/* Handle form (algorithm.rs:529-539, :696-714 after tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70): `base` is a
+   base reader (else SSW_ERR_NOT_BASE); host_base_rgb are the original's pixels [h][w][3] u8 again -- a reader keeps the
+   plane and the list, not the image -- and may be NULL when no suspect needs them (every suspect 3 channels on the whole
+   frame).  Equals ssw_reader_trace_host_rgb8 on the frames ssw_restore_rgb8 produces, bit for bit in all five outputs. */
+int ssw_reader_trace_restored_host_rgb8(ssw_reader* base, const uint8_t* host_base_rgb, const uint8_t* const* host_suspects,
+                                        const ssw_placement* placements, size_t n_suspects, size_t k, const float* host_marks,
+                                        size_t n_marks, float threshold, float* host_extracted, float* host_sims,
+                                        uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed);
+
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,
    and `into_rgb16()` from Rgb32F: round(clamp(v,0,1) * 65535) (`image 0.24.3`, like the 8-bit forms). */

@@ -144,6 +144,14 @@ struct ImageRgb8 {
     ImageRgb8(size_t w, size_t h) : width(w), height(h), data(w * h * 3) {}
 };
 
+// An 8-bit RGBA image [h][w][4]: a suspect whose alpha says where it has pixels of its own (tests/attack_crop.rs:56-70).
+struct ImageRgba8 {
+    size_t width = 0, height = 0;
+    std::vector<uint8_t> data;
+    ImageRgba8() = default;
+    ImageRgba8(size_t w, size_t h) : width(w), height(h), data(w * h * 4) {}
+};
+
 // A 16-bit RGB image [h][w][3] (16-bit PNG / TIFF): `into_rgb32f()` = v / 65535 on the device, half the bytes cross PCIe.
 struct ImageRgb16 {
     size_t width = 0, height = 0;
@@ -266,6 +274,20 @@ struct TraceResult {
     std::vector<float> best_sim;
 };
 
+// Where a suspect lies in the original's frame (ssw_placement): the rectangle at (x, y) of size w x h; w = h = 0: the suspect's
+// own size.  Placement::whole_frame(original) is the placement of a scaled copy.
+struct Placement {
+    size_t x = 0, y = 0, w = 0, h = 0;
+    template <class Image> static Placement whole_frame(const Image& original) { return Placement{0, 0, original.width, original.height}; }
+};
+// A suspect of Reader::trace with placements: an RGB or RGBA image of any size, not owned
+struct Suspect {
+    const uint8_t* data;
+    size_t width, height, channels;
+    Suspect(const ImageRgb8& im) : data(im.data.data()), width(im.width), height(im.height), channels(3) { if (im.data.size() != width * height * 3) throw Error(SSW_ERR_BAD_DIMS, "Suspect"); }
+    Suspect(const ImageRgba8& im) : data(im.data.data()), width(im.width), height(im.height), channels(4) { if (im.data.size() != width * height * 4) throw Error(SSW_ERR_BAD_DIMS, "Suspect"); }
+};
+
 class Reader {                                         // algorithm.rs:441-594
 public:
     static Reader base(Context& ctx, const ImageRgb32F& image, const ReadConfig& config = ReadConfig()) {   // :462-464
@@ -309,6 +331,39 @@ public:
         r.best.assign(n, TraceResult::none); r.n_exceed.assign(n, 0u); r.best_sim.assign(n, std::nanf(""));
         check(ssw_reader_trace_host_rgb8(rd_, sp.data(), n, k, nm ? m.data() : nullptr, nm, threshold, ext.data(), nm ? sims.data() : nullptr,
                                          nm ? r.best.data() : nullptr, nm ? r.best_sim.data() : nullptr, nm ? r.n_exceed.data() : nullptr),
+              "Reader::trace");
+        for (size_t i = 0; i < n; ++i) {
+            r.extracted.emplace_back(ext.begin() + i * k, ext.begin() + (i + 1) * k);
+            r.sims.emplace_back(sims.begin() + i * nm, sims.begin() + (i + 1) * nm);
+        }
+        return r;
+    }
+    // The same for attacked copies: each suspect (RGB or RGBA, any size) is first restored on the device -- resized into the
+    // rectangle its placement names (tests/attack_resize.rs:31-36) and blended over the original (tests/attack_crop.rs:56-70);
+    // ssw_restore_rgb8 in ssw.h has the recipe.  `original`: the pixels this base reader was made from (it keeps the plane
+    // and the list, not the image).
+    TraceResult trace(const ImageRgb8& original, const std::vector<Suspect>& suspects, const std::vector<Placement>& placements,
+                      const std::vector<const MarkBuf*>& marks, float threshold = 6.0f) const {
+        const size_t n = suspects.size(), nm = marks.size(), k = nm ? marks[0]->data().size() : 0;
+        if (placements.size() != n || original.width != w_ || original.height != h_ || original.data.size() != w_ * h_ * 3)
+            throw Error(SSW_ERR_BAD_DIMS, "Reader::trace");
+        std::vector<const uint8_t*> sp(n);
+        std::vector<ssw_placement> pl(n);
+        for (size_t i = 0; i < n; ++i) {
+            sp[i] = suspects[i].data;
+            pl[i] = ssw_placement{(uint32_t)suspects[i].width, (uint32_t)suspects[i].height, (uint32_t)suspects[i].channels,
+                                  (uint32_t)placements[i].x, (uint32_t)placements[i].y, (uint32_t)placements[i].w, (uint32_t)placements[i].h};
+        }
+        std::vector<float> m(nm * k), ext(n * k), sims(n * nm);
+        for (size_t j = 0; j < nm; ++j) {
+            if (marks[j]->data().size() != k) throw Error(SSW_ERR_LENGTH_MISMATCH, "Reader::trace");
+            std::copy(marks[j]->data().begin(), marks[j]->data().end(), m.begin() + j * k);
+        }
+        TraceResult r;
+        r.best.assign(n, TraceResult::none); r.n_exceed.assign(n, 0u); r.best_sim.assign(n, std::nanf(""));
+        check(ssw_reader_trace_restored_host_rgb8(rd_, original.data.data(), sp.data(), pl.data(), n, k, nm ? m.data() : nullptr, nm, threshold,
+                                                  ext.data(), nm ? sims.data() : nullptr, nm ? r.best.data() : nullptr,
+                                                  nm ? r.best_sim.data() : nullptr, nm ? r.n_exceed.data() : nullptr),
               "Reader::trace");
         for (size_t i = 0; i < n; ++i) {
             r.extracted.emplace_back(ext.begin() + i * k, ext.begin() + (i + 1) * k);

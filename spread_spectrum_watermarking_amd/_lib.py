@@ -37,8 +37,15 @@ class Config(C.Structure):
     _fields_ = [("ordering", C.c_int32), ("method", C.c_int32), ("alpha", C.c_float), ("precision", C.c_int32)]
 
 
+class Placement(C.Structure):
+    """ssw_placement (include/ssw.h): the suspect as it is, and the rectangle of the original's frame it covers."""
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("channels", C.c_uint32),
+                ("x", C.c_uint32), ("y", C.c_uint32), ("pw", C.c_uint32), ("ph", C.c_uint32)]
+
+
 _vp, _f32p, _u32p, _u64p, _sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t
 _cfgp = C.POINTER(Config)
+_plp = C.POINTER(Placement)
 
 # name -> (restype, argtypes); this table is also what tests check against include/ssw.h
 SIGNATURES = {
@@ -117,6 +124,11 @@ SIGNATURES = {
     "ssw_fingerprint_trace_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p,
                                                   _f32p, _u32p]),
     "ssw_reader_trace_host_rgb8": (C.c_int, [_vp, C.POINTER(_vp), _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p, _f32p, _u32p]),
+    "ssw_restore_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _vp]),
+    "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
+                                                           _f32p, _f32p, _u32p, _f32p, _u32p]),
+    "ssw_reader_trace_restored_host_rgb8": (C.c_int, [_vp, _vp, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p,
+                                                      _f32p, _u32p]),
     "ssw_writer_mark_copies": (C.c_int, [_vp, _f32p, _sz, _sz, _vp]),
     "ssw_writer_mark_copies_rgb8": (C.c_int, [_vp, _f32p, _sz, _sz, _vp]),
     "ssw_writer_destroy": (C.c_int, [_vp]),

@@ -505,13 +505,26 @@ class Reader:
         check(self._lib.ssw_reader_extract(self._h, d._h, out.ctypes.data, out.size), "Reader::extract")
         return out
 
-    def trace(self, suspects, marks, threshold: float = 6.0, k: Optional[int] = None) -> "TraceResult":
+    def trace(self, suspects, marks, threshold: float = 6.0, k: Optional[int] = None, placements=None, base=None) -> "TraceResult":
         """Whose copy is each suspect?  Per 8-bit suspect image s: `self.extract(Reader.derived(s), k)`, then
         `Tester(ext).similarity(m)` for every stored mark m (algorithm.rs:529-539, :696-714; the `test` loop of
         examples/main.rs:369-415) as ONE call: this reader's transformed plane and index list are reused, the suspects
-        stream to the GPU.  All marks must have one length (ValueError otherwise); `k` is only needed without marks."""
+        stream to the GPU.  All marks must have one length (ValueError otherwise); `k` is only needed without marks.
+
+        placements: None (every suspect has the original's shape, as before), or one entry per suspect, a `Placement` or
+        None; suspects are then [h][w][3] or [h][w][4] arrays of any size and are restored on the device first (see
+        `restore` for the rule).  `base`: the original's 8-bit pixels again -- the reader keeps the plane and the list,
+        not the image -- needed as soon as a suspect has an alpha channel or covers less than the whole frame."""
         if not self.is_base:
             raise SswError(L.SSW_ERR_NOT_BASE, "Reader::trace")
+        if placements is not None:
+            arrs, ptrs, pl = _placed_suspects(suspects, placements, self.width, self.height)
+            m, k = _trace_marks(marks, k)
+            res = TraceResult.empty(len(arrs), m.shape[0], k)
+            b = None if base is None else _base_rgb8(base, self.width, self.height)
+            check(self._lib.ssw_reader_trace_restored_host_rgb8(self._h, b.ctypes.data if b is not None else None, ptrs, pl, len(arrs), k,
+                                                                *res._args(m, threshold)), "Reader::trace")
+            return res
         arrs, ptrs, w, h = _frame_ptrs(suspects)
         if (w, h) != (self.width, self.height):
             raise SswError(L.SSW_ERR_LENGTH_MISMATCH, "Reader::trace")
@@ -650,12 +663,104 @@ class TraceResult:
         return [int(j) for j in np.nonzero(self.sims[s] > np.float32(self.threshold))[0]]
 
 
+# ---- tracing attacked copies: resized and cropped suspects are restored on the device (include/ssw.h: ssw_restore_rgb8) ----
+@dataclass
+class Placement:
+    """Where a suspect lies in the original's frame: the rectangle at (x, y) of size w x h (None: see `restore`)."""
+    x: int = 0
+    y: int = 0
+    w: Optional[int] = None
+    h: Optional[int] = None
+
+
+def _resolve_placement(p: Optional[Placement], sw: int, sh: int, channels: int, W: int, H: int) -> L.Placement:
+    """The rule of `restore`: no rectangle size at (0, 0) on a suspect whose size differs from the original's = whole frame."""
+    p = p or Placement()
+    if (p.w is None) != (p.h is None):
+        raise ValueError("Placement: w and h go together")
+    if p.w is not None:
+        pw, ph = int(p.w), int(p.h)
+    elif (p.x, p.y) == (0, 0) and (sw, sh) != (W, H):
+        pw, ph = W, H
+    else:
+        pw, ph = sw, sh
+    if min(p.x, p.y) < 0 or pw <= 0 or ph <= 0:
+        raise ValueError("Placement: negative position or empty rectangle")
+    return L.Placement(sw, sh, channels, int(p.x), int(p.y), pw, ph)
+
+
+def _base_rgb8(base, w=None, h=None) -> np.ndarray:
+    b = np.ascontiguousarray(np.asarray(base)[:, :, :3])
+    if b.dtype != np.uint8 or b.ndim != 3 or b.shape[2] != 3:
+        raise ValueError("base must be an 8-bit [H, W, 3] image")
+    if w is not None and (b.shape[1], b.shape[0]) != (w, h):
+        raise ValueError("base: not the size of the reader's image")
+    return b
+
+
+def _placed_suspects(suspects, placements, W: int, H: int):
+    """Suspects of any size with 3 or 4 channels + one placement each -> (kept-alive arrays, void* array, ssw_placement array)."""
+    arrs = [np.ascontiguousarray(np.asarray(im)) for im in suspects]
+    if not arrs:
+        raise ValueError("no images")
+    placements = list(placements)
+    if len(placements) != len(arrs):
+        raise ValueError("placements: one entry (a Placement or None) per suspect")
+    for a in arrs:
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4) or 0 in a.shape:
+            raise ValueError("suspects must be 8-bit [h, w, 3] or [h, w, 4] arrays")
+    pl = (L.Placement * len(arrs))(*[_resolve_placement(p, a.shape[1], a.shape[0], a.shape[2], W, H) for a, p in zip(arrs, placements)])
+    return arrs, (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs]), pl
+
+
+def restore(base, suspects, placements=None, ctx: Optional[Context] = None) -> list:
+    """What tracing with `placements` does to each suspect before it extracts, as frames: the recipes of the reference's
+    attack tests -- resize back with CatmullRom (tests/attack_resize.rs:31-36), then "complement the attacked image with the
+    original" through Rgba::blend (tests/attack_crop.rs:56-70) -- on the device (ssw_restore_rgb8).  Returns one u8
+    [H, W, 3] frame per suspect.
+
+    base: the original, 8-bit [H, W, 3].  suspects: 8-bit [h, w, 3] or [h, w, 4] arrays of any size.  placements: None, or
+    one entry per suspect, each a `Placement(x, y, w, h)` -- the rectangle of the original's frame the suspect covers; it is
+    resized to w x h when its own size differs -- or None.  The rule for what is left out: a None entry, or a Placement
+    without w / h at (0, 0), means "whole frame" when the suspect's size differs from the original's (a scaled copy), and
+    "own size at (x, y)" otherwise (a cut-out, or an RGBA image of full size).  An alpha channel is filtered like a colour
+    channel and blended over the original: alpha 0 keeps the original's pixel."""
+    ctx = ctx or default_context()
+    b = _base_rgb8(base)
+    H, W = b.shape[:2]
+    suspects = list(suspects)
+    arrs, _, pl = _placed_suspects(suspects, placements if placements is not None else [None] * len(suspects), W, H)
+    n, fb = len(arrs), W * H * 3
+    dev_base, dev_out = ctx.to_device(b), ctx.alloc(n * fb)
+    dev = [ctx.to_device(a) for a in arrs]
+    ptrs = (C.c_void_p * n)(*[d.ptr.value for d in dev])
+    check(ctx._lib.ssw_restore_rgb8(ctx.handle, dev_base.ptr, W, H, ptrs, pl, n, dev_out.ptr), "ssw_restore_rgb8")
+    out = dev_out.to_host(np.uint8, (n, H, W, 3))
+    for d in dev + [dev_base, dev_out]:
+        d.free()
+    return [out[i] for i in range(n)]
+
+
 def trace_many(base, suspects, marks, k: Optional[int] = None, threshold: float = 6.0, config: Optional[ReadConfig] = None,
-               ctx: Optional[Context] = None) -> TraceResult:
+               ctx: Optional[Context] = None, placements=None) -> TraceResult:
     """`Reader::base(base, config)` once, then per suspect `extract` + `Tester::similarity` against every mark
-    (examples/main.rs:369-415) as ONE streaming call over 8-bit host images: ssw_fingerprint_trace_host_rgb8."""
+    (examples/main.rs:369-415) as ONE streaming call over 8-bit host images: ssw_fingerprint_trace_host_rgb8.
+
+    placements: None (every suspect has the original's shape, as before), or one entry per suspect, a `Placement` or None:
+    suspects of any size with 3 or 4 channels are restored on the device first (ssw_fingerprint_trace_restored_host_rgb8;
+    `restore` spells out the rule and returns the frames this call extracts from)."""
     ctx = ctx or default_context()
     config = config or ReadConfig.default()
+    if placements is not None:
+        b = _base_rgb8(base)
+        arrs, ptrs, pl = _placed_suspects(suspects, placements, b.shape[1], b.shape[0])
+        m, k = _trace_marks(marks, k)
+        res = TraceResult.empty(len(arrs), m.shape[0], k)
+        cfg = config._c()
+        check(ctx._lib.ssw_fingerprint_trace_restored_host_rgb8(ctx.handle, C.byref(cfg), b.ctypes.data, b.shape[1], b.shape[0], ptrs, pl,
+                                                                len(arrs), k, *res._args(m, threshold)),
+              "ssw_fingerprint_trace_restored_host_rgb8")
+        return res
     b = np.ascontiguousarray(np.asarray(base)[:, :, :3])
     if b.dtype != np.uint8:
         raise ValueError("base must be an 8-bit [H, W, 3] image")

@@ -10,9 +10,12 @@
         -> <stem>_fp<i>.png (i zero-padded) and one <stem>_fp.json holding the N marks, described "<desc> #i";
            `test <file> <stem>_fp<i>.png <stem>_fp.json` then names the copy that leaked
     python -m spread_spectrum_watermarking_amd.cli trace <base> --suspects A.png B.png ... --marks X_fp.json [Y.json ...]
-            [--similarity-exceed 6.0]
+            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] ...]
         -> one record per suspect: the stored mark it carries (or none) and every further mark above the threshold;
-           one GPU call per group of stored marks with equal (config, length), whatever the number of suspects
+           one GPU call per group of stored marks with equal (config, length), whatever the number of suspects.
+           Attacked copies are restored on the GPU first (tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70): a
+           suspect of another size is resized back to the base's, an alpha channel is blended over the base, and
+           --place puts a cut-out where it belongs (at X,Y, scaled to WxH when given); their records say "Restored:"
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -26,7 +29,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .api import MarkBuf, Reader, Tester, TraceResult, Writer
+from .api import MarkBuf, Placement, Reader, Tester, TraceResult, Writer
 from .storage import Configuration, DescribedWatermark, Version1Storage
 
 _ORDERING_ARGS = {"energy": "Energy", "energy-orthogonal": "EnergyOrthogonal", "legacy": "Legacy"}
@@ -47,9 +50,65 @@ def _open_image(path: str) -> np.ndarray:
         raise SystemExit(f"Could not load image at {path!r}") from e
 
 
+def _open_suspect(path: str) -> np.ndarray:
+    """A suspect keeps its alpha channel (RGBA); anything else is read like the base."""
+    from PIL import Image
+    try:
+        im = Image.open(path)
+        has_alpha = im.mode in ("RGBA", "LA", "PA") or (im.mode == "P" and "transparency" in im.info)
+        return np.asarray(im.convert("RGBA" if has_alpha else "RGB"))
+    except Exception as e:
+        raise SystemExit(f"Could not load image at {path!r}") from e
+
+
+def parse_place(text: str) -> Tuple[str, Placement]:
+    """FILE=X,Y[,WxH] -> (FILE, Placement); ValueError on anything else."""
+    name, sep, spec = text.rpartition("=")
+    parts = spec.split(",")
+    if not sep or not name or len(parts) not in (2, 3):
+        raise ValueError(f"--place {text!r}: expected FILE=X,Y[,WxH]")
+    try:
+        x, y = int(parts[0]), int(parts[1])
+        w = h = None
+        if len(parts) == 3:
+            ws, xs, hs = parts[2].partition("x")
+            if not xs:
+                raise ValueError
+            w, h = int(ws), int(hs)
+    except ValueError:
+        raise ValueError(f"--place {text!r}: expected FILE=X,Y[,WxH]") from None
+    if x < 0 or y < 0 or (w is not None and (w <= 0 or h <= 0)):
+        raise ValueError(f"--place {text!r}: negative position or empty size")
+    return name, Placement(x, y, w, h)
+
+
+def trace_placements(suspects: List[str], place: Optional[List[str]]) -> Dict[str, Placement]:
+    """The --place options by suspect; ValueError for a malformed one, a FILE not among --suspects, or one placed twice."""
+    out: Dict[str, Placement] = {}
+    for text in place or []:
+        name, p = parse_place(text)
+        if name not in suspects:
+            raise ValueError(f"--place {text!r}: {name!r} is not among --suspects")
+        if name in out:
+            raise ValueError(f"--place {text!r}: {name!r} is placed twice")
+        out[name] = p
+    return out
+
+
+class _TraceParser(argparse.ArgumentParser):
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if getattr(a, "command", None) == "trace":
+            try:
+                a.placements = trace_placements(a.suspects, a.place)
+            except ValueError as e:
+                self.error(str(e))
+        return a
+
+
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="spread_spectrum_watermarking_amd.cli")
-    sub = p.add_subparsers(dest="command")
+    p = _TraceParser(prog="spread_spectrum_watermarking_amd.cli")
+    sub = p.add_subparsers(dest="command", parser_class=argparse.ArgumentParser)
     w = sub.add_parser("watermark", help="Embed a watermark into a file.")
     w.add_argument("file", help="The file to to watermark.")
     w.add_argument("--length", type=int, default=1000, help="Watermark length.")
@@ -78,6 +137,8 @@ def build_parser() -> argparse.ArgumentParser:
     r.add_argument("base", help="The original file.")
     r.add_argument("--suspects", nargs="+", required=True, help="The files to trace.")
     r.add_argument("--marks", nargs="+", required=True, help="The watermark files to test from.")
+    r.add_argument("--place", action="append", metavar="FILE=X,Y[,WxH]",
+                   help="Where the cut-out FILE (one of --suspects) lies in the base, and the size it had there. Repeatable.")
     return p
 
 
@@ -174,16 +235,48 @@ def group_stored_marks(stored: List[Tuple[str, Version1Storage]]) -> Dict[Tuple[
 
 def cmd_trace(args, out=sys.stdout) -> int:
     base = _open_image(args.base)
-    suspects = [_open_image(p) for p in args.suspects]
+    suspects = [_open_suspect(p) for p in args.suspects]
+    H, W = base.shape[:2]
+    # what restoration does to each suspect (None: same-shape RGB, traced as it is): tests/attack_resize.rs:31-36 for another
+    # size, tests/attack_crop.rs:56-70 for an alpha channel or a placed cut-out
+    placements: List[Optional[Placement]] = []
+    restored: List[Optional[str]] = []
     for path, img in zip(args.suspects, suspects):
-        if img.shape != base.shape:                                       # algorithm.rs:550-552
-            raise SystemExit(f"{path}: Derived coefficient length not equal to base coefficient length.")
+        sh, sw, c = img.shape
+        p = getattr(args, "placements", {}).get(path)
+        if p is None and c == 3 and (sw, sh) == (W, H):
+            placements.append(None)
+            restored.append(None)
+            continue
+        if p is None:
+            p = Placement()
+            if c == 3 and sw <= W and sh <= H and (sw < W or sh < H):
+                print(f"{path}: smaller than the base and not placed: taken as a scaled copy of the whole frame "
+                      f"(--place {path}=X,Y for a cut-out)", file=sys.stderr)
+        whole = p.w is None and (p.x, p.y) == (0, 0) and (sw, sh) != (W, H)
+        pw, ph = (W, H) if whole else ((p.w, p.h) if p.w is not None else (sw, sh))
+        if p.x + pw > W or p.y + ph > H:
+            raise SystemExit(f"{path}: placed at {p.x},{p.y} with size {pw}x{ph}, it leaves the base ({W}x{H})")
+        what = []
+        if (pw, ph) != (sw, sh):
+            what.append(f"resize {sw}x{sh} -> {pw}x{ph}")
+        if (p.x, p.y, pw, ph) != (0, 0, W, H):
+            what.append(f"placed {pw}x{ph} at {p.x},{p.y}")
+        if c == 4:
+            what.append("alpha blended over the base")
+        placements.append(p)
+        restored.append(", ".join(what))
+    any_restored = any(r is not None for r in restored)
     stored = [(p, Version1Storage.load(p)) for p in args.marks]
     exceed = args.similarity_exceed
     # per suspect: (exact similarity or None, GEMM similarity, path, mark) of every stored mark, in file order per group
     rows: List[list] = [[] for _ in suspects]
     for (config, length), members in group_stored_marks(stored).items():   # main.rs:383-415, once per group for ALL suspects
-        res = Reader.base(base, config.to_read_config()).trace(suspects, [w.values for _, w in members], exceed, k=length)
+        reader = Reader.base(base, config.to_read_config())
+        if any_restored:
+            res = reader.trace(suspects, [w.values for _, w in members], exceed, k=length, placements=placements, base=base)
+        else:
+            res = reader.trace(suspects, [w.values for _, w in members], exceed, k=length)
         for s in range(len(suspects)):
             for j, (path, wmk) in enumerate(members):
                 best = int(res.best[s]) == j
@@ -193,6 +286,8 @@ def cmd_trace(args, out=sys.stdout) -> int:
         top = max(exact, key=lambda r: r[0]) if exact else None
         print("-", file=out)
         print(f"  Suspect: \"{spath}\"", file=out)
+        if restored[s] is not None:
+            print(f"  Restored: \"{restored[s]}\"", file=out)
         if top is None:
             print("  Matches: false", file=out)
             print(f"  MatchExceed: {_rust_f32(exceed)}", file=out)

@@ -15,11 +15,10 @@
 #include <cmath>
 #include <vector>
 
+#include "resize_common.hpp"
 #include "ssw_internal.hpp"
 
 namespace ssw {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ inline float clampf(float x, float lo, float hi) {
     if (x < lo) return lo;
@@ -263,56 +262,8 @@ __global__ __launch_bounds__(256) void resize_horizontal_kernel(const float* __r
 // summation order are those of the two-pass kernels: bit-identical results.
 // Needs 4-byte aligned rows (w * 3 % 4 == 0, nw * 3 % 4 == 0, OXB % 4 == 0).
 // ---------------------------------------------------------------------------------------------
-struct ResizeTile {
-    unsigned oyb, oxb;            // output tile (powers of two, oxb >= 4)
-    unsigned pitch;               // elements (bytes of s_in, floats of s_v) per LDS row, multiple of 4
-    unsigned in_rows;             // LDS rows of the input tile
-    unsigned tiles_x, tiles_y;
-    unsigned oxb_log2;
-};
-
-typedef float rz_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4r __attribute__((ext_vector_type(4)));
-
-// round(clamp(t, 0, 255)) with halves away from zero, as an integer -- exactly: scaling by 2^16 is exact, the
-// conversion truncates, and floor(c * 2^16) still tells whether the fraction reaches 1/2
-__device__ inline uint32_t resize_to_u8(float t) {
-    const float c = __builtin_amdgcn_fmed3f(t, 0.0f, 255.0f);     // = clamp for the finite sums this sees
-    return ((uint32_t)(c * 65536.0f) + 0x8000u) >> 16;
-}
-
-// vertical pass of one block: pieces of NW 32-bit words (4 NW bytes) per thread
-template <int NW>
-__device__ inline void resize_vertical_pieces(const unsigned char* s_in, float* s_v, const float* s_wv, const uint32_t* s_lv,
-                                              const uint32_t* s_cv, unsigned r0, unsigned noy, unsigned pieces, unsigned vmax,
-                                              unsigned pitch, unsigned tid) {
-    typedef unsigned int uvec __attribute__((ext_vector_type(NW)));
-    for (unsigned it = tid; it < noy * pieces; it += 256) {
-        const unsigned j = it / pieces, ck = it - j * pieces;
-        const unsigned n = s_cv[j];
-        const unsigned char* col = s_in + (s_lv[j] - r0) * pitch + 4 * NW * ck;
-        const float* wv = s_wv + j * vmax;
-        rz_f32x2 t[2 * NW];
-#pragma unroll
-        for (int u = 0; u < 2 * NW; ++u) t[u] = (rz_f32x2){0.0f, 0.0f};
-#pragma unroll 2
-        for (unsigned i = 0; i < n; ++i) {
-            const uvec v = *reinterpret_cast<const uvec*>(col + i * pitch);
-            const float wi = wv[i];
-            const rz_f32x2 ww = {wi, wi};
-#pragma unroll
-            for (int u = 0; u < NW; ++u) {
-                const rz_f32x2 a = {(float)(v[u] & 0xFF), (float)((v[u] >> 8) & 0xFF)};
-                const rz_f32x2 b = {(float)((v[u] >> 16) & 0xFF), (float)(v[u] >> 24)};
-                t[2 * u] += a * ww;
-                t[2 * u + 1] += b * ww;
-            }
-        }
-        f32x4* o = reinterpret_cast<f32x4*>(s_v + j * pitch + 4 * NW * ck);
-#pragma unroll
-        for (int u = 0; u < NW; ++u) o[u] = (f32x4){t[2 * u][0], t[2 * u][1], t[2 * u + 1][0], t[2 * u + 1][1]};
-    }
-}
+// ResizeTile, resize_to_u8, the vertical pass of a block and the per-pixel horizontal sum: resize_common.hpp (shared with
+// restore.hip, which must give the same bits)
 
 // HMODE (horizontal pass): 0 = one lane per (output pixel, channel) -- down-scaling along x, few outputs, long taps;
 // 1 = one thread per aligned quad of output pixels that share their taps' positions (left, count <= 5: integer
@@ -476,18 +427,12 @@ __global__ __launch_bounds__(256) void resize_fused_kernel(const uint8_t* __rest
             const unsigned n = s_ch[x];
             const float* src = s_v + j * tl.pitch + (s_lh[x] * 3 - a0);
             const float* wh = s_wh + x;
-            float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
-#pragma unroll 4
-            for (unsigned i = 0; i < n; ++i) {
-                const float wi = wh[i * tl.oxb];
-                t0 += src[3 * i + 0] * wi;
-                t1 += src[3 * i + 1] * wi;
-                t2 += src[3 * i + 2] * wi;
-            }
+            float t[3];
+            resize_horizontal_pixel<3>(src, wh, n, tl.oxb, t);
             unsigned char* o = s_out + j * out_pitch + x * 3;
-            o[0] = (unsigned char)resize_to_u8(t0);
-            o[1] = (unsigned char)resize_to_u8(t1);
-            o[2] = (unsigned char)resize_to_u8(t2);
+            o[0] = (unsigned char)resize_to_u8(t[0]);
+            o[1] = (unsigned char)resize_to_u8(t[1]);
+            o[2] = (unsigned char)resize_to_u8(t[2]);
         }
     }
     __syncthreads();
@@ -510,43 +455,11 @@ __global__ __launch_bounds__(256) void resize_fused_kernel(const uint8_t* __rest
     }
 }
 
-// tile shape: the cheapest one (input bytes loaded + vertical taps per output pixel) whose LDS footprint lets two
-// blocks share a CU; spans = reach (in input samples) of 1, 2, 4, ... 128 consecutive outputs (DeviceTaps::span)
-static bool pick_resize_tile(const DeviceTaps& vt, const DeviceTaps& ht, size_t w, size_t h, size_t nw, size_t nh, ResizeTile* out,
-                             size_t* lds_bytes) {
-    double best = 1e300;
-    bool found = false;
-    const double vtaps = (double)(vt.span[0] ? vt.span[0] : 1);
-    for (int ey = 0; ey < 8; ++ey)
-        for (int ex = 2; ex < 8; ++ex) {                                // OXB >= 4 (a multiple of 4)
-            const unsigned oyb = 1u << ey, oxb = 1u << ex;
-            if (oyb > 2 * nh || oxb > 2 * nw) continue;
-            const unsigned rows = vt.span[ey], px = ht.span[ex];
-            if (!rows || !px) continue;
-            const unsigned pitch = (px * 3 + 3 + 6 + 15) / 16 * 16;     // + up to 3 bytes of alignment slack + 2 pixels the quad path may read past the reach; 16-byte LDS accesses
-            const size_t out_tile = (size_t)oyb * oxb * 3;
-            const size_t in_tile = (size_t)rows * pitch;
-            const size_t lds = (size_t)oyb * pitch * 4 + ((size_t)oxb * ht.max_taps + (size_t)oyb * vt.max_taps) * 4 +
-                               (2 * (size_t)oyb + 2 * (size_t)oxb) * 4 + (in_tile > out_tile ? in_tile : out_tile) + 16;
-            if ((size_t)oxb * ht.max_taps > 1024 || (size_t)oyb * vt.max_taps > 1024) continue;   // tap tables: <= 4 values per thread
-            if (lds > 78 * 1024) continue;                               // two blocks per CU (160 KB of LDS)
-            const double cost = ((double)rows * pitch + (double)oyb * pitch * vtaps) / ((double)oyb * oxb);
-            if (cost < best) {
-                best = cost;
-                found = true;
-                *out = ResizeTile{oyb, oxb, pitch, rows, (unsigned)((nw + oxb - 1) / oxb), (unsigned)((nh + oyb - 1) / oyb), (unsigned)ex};
-                *lds_bytes = lds;
-            }
-        }
-    (void)w; (void)h;
-    return found;
-}
-
 static bool resize_can_fuse(const uint8_t* in, size_t n_frames, size_t w, size_t h, size_t nw, size_t nh, const DeviceTaps& vt,
                             const DeviceTaps& ht, const uint8_t* out, ResizeTile* tl, size_t* lds) {
     const bool rows_aligned = (w * 3) % 4 == 0 && (nw * 3) % 4 == 0 &&
                               ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 3) == 0;
-    return rows_aligned && n_frames <= 65535 && pick_resize_tile(vt, ht, w, h, nw, nh, tl, lds);
+    return rows_aligned && n_frames <= 65535 && pick_resize_tile(vt, ht, nw, nh, 3, tl, lds);
 }
 
 // f32 intermediate the two-pass fallback needs (0 when the fused kernel takes the call)

@@ -162,10 +162,27 @@ int trace_check_args(const ssw_ctx* ctx, const ssw_config* cfg, size_t w, size_t
                      const void* sims, const void* best, const void* best_sim, const void* n_exceed);
 int trace_score(ssw_ctx* ctx, const float* dev_extracted, size_t n_suspects, const float* dev_marks, size_t n_marks, size_t k,
                 float threshold, float* dev_sims, uint32_t* dev_best, float* dev_best_sim, uint32_t* dev_n_exceed);
-// ssw_stream.hip: the host form -- suspects through the streaming ring, the base plane and list given (device)
+// ssw_stream.hip: the host form -- suspects through the streaming ring, the base plane and list given (device).
+// `placements` (normalised, one per suspect; null: every suspect is a frame [h][w][3]): host_suspects[s] is the suspect as it
+// is and is restored on the device into its frame of the group, over `dev_base` (the original's pixels; may be null when no
+// placement reads them)
 int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, const uint32_t* base_idx, const uint8_t* const* host_suspects,
                       size_t n_suspects, size_t w, size_t h, size_t k, const float* host_marks, size_t n_marks, float threshold,
-                      float* host_extracted, float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed);
+                      float* host_extracted, float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed,
+                      const ssw_placement* placements = nullptr, const uint8_t* dev_base = nullptr);
+
+// Restoring attacked suspects before the trace (restore.hip; include/ssw.h: ssw_restore_rgb8).  restore_normalise: checks n
+// placements against the frame and fills in pw = ph = 0 (SSW_ERR_BAD_ARG).  restore_prepare: caches every tap table the
+// placements need -- the one step that may wait for the stream, so callers do it before their pipeline starts.
+// restore_enqueue: the restore launches of n jobs (none of them restore_untouched) on the context's stream, one stage timer.
+struct RestoreJob { const uint8_t* src; uint8_t* out; ssw_placement p; };      // device pointers; p normalised
+bool restore_untouched(const ssw_placement& p, size_t w, size_t h);            // 3 channels, the frame's size, whole frame
+bool restore_reads_base(const ssw_placement& p, size_t w, size_t h);           // the original's pixels are needed
+int restore_normalise(const ssw_placement* pl, size_t n, size_t w, size_t h, std::vector<ssw_placement>* out);
+int restore_prepare(ssw_ctx* ctx, const std::vector<ssw_placement>& pl);
+int restore_enqueue(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const RestoreJob* jobs, size_t n);
+// ssw_lib.hip: the cached CatmullRom tap table (in_len -> out_len) of the context
+int get_taps(ssw_ctx* ctx, size_t in_len, size_t out_len, DeviceTaps* out);
 
 // fingerprint.hip: n_copies copies of one image, each Writer::result of `coef` with its own single mark embedded at `idx`
 // (marks [n_copies][mark_stride]); enqueued on the context's stream; t32: an f32 plane of scratch

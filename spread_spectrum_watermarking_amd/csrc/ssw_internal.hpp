@@ -358,6 +358,7 @@ struct ssw_ctx {
     Buf small;                    // misc (mark offsets, sims, ...)
     Buf sort_scratch;             // full-order sort (lazy, Reader::indices beyond the top-k limit)
     Buf resize_tmp;               // f32 intermediate of the resize's vertical pass
+    Buf restore_base;             // the original's pixels while a restoring trace runs (ssw_*_trace_restored_host_rgb8)
     // ssw_fingerprint_trace: what every chunk on both lanes reads -- base plane | base index list | prune tables (flag, pos,
     // rows) | gathered bases, launch order | gathered bases, fragment order | similarity matrix when the caller wants none
     Buf trace[6];

@@ -388,6 +388,7 @@ int ssw_ctx_destroy(ssw_ctx* ctx) {
     release(ctx->small);
     release(ctx->sort_scratch);
     release(ctx->resize_tmp);
+    release(ctx->restore_base);
     for (auto& b : ctx->fingerprint) release(b);
     for (auto& b : ctx->trace) release(b);
     for (auto& kv : ctx->taps) { (void)hipFree(kv.second.left); (void)hipFree(kv.second.count); (void)hipFree(kv.second.weights); }
@@ -688,8 +689,11 @@ int ssw_similarity_matrix(ssw_ctx* ctx, const float* dev_extracted, size_t n_ext
     return similarity_matrix_enqueue(ctx, dev_extracted, n_extracted, dev_marks, n_marks, k, dev_sims);
 }
 
-// ---- whole path, batched (ssw_pipeline.hip) ------------------------------------------------
-namespace {
+}  // extern "C"
+
+// ---- the context's cached CatmullRom tap tables (ssw_resize_rgb8, restore.hip) ---------------
+namespace ssw {
+namespace host {
 
 int get_taps(ssw_ctx* ctx, size_t in_len, size_t out_len, DeviceTaps* out) {
     auto key = std::make_pair(in_len, out_len);
@@ -730,8 +734,12 @@ int get_taps(ssw_ctx* ctx, size_t in_len, size_t out_len, DeviceTaps* out) {
     return SSW_OK;
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace ssw
 
+extern "C" {
+
+// ---- whole path, batched (ssw_pipeline.hip) ------------------------------------------------
 int ssw_batch_embed(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_rgb, size_t n_frames,
                     size_t w, size_t h, const float* dev_marks, size_t k, float* dev_rgb_out,
                     float* dev_coef_out, uint32_t* dev_indices_out) {
@@ -792,6 +800,29 @@ int ssw_fingerprint_trace_host_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const u
     SSW_TRY(stage_consumed(ctx, *fs));
     return stream_trace_rgb8(ctx, *cfg, yb, idx, host_suspects, n_suspects, w, h, k, host_marks, n_marks, threshold, host_extracted,
                              host_sims, host_best, host_best_sim, host_n_exceed);
+}
+
+// Restoring host form (tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70, then the trace): the original stays on the
+// device for the whole call -- the restore launches composite over it -- and is transformed from there
+int ssw_fingerprint_trace_restored_host_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* host_base, size_t w, size_t h,
+                                             const uint8_t* const* host_suspects, const ssw_placement* placements,
+                                             size_t n_suspects, size_t k, const float* host_marks, size_t n_marks,
+                                             float threshold, float* host_extracted, float* host_sims, uint32_t* host_best,
+                                             float* host_best_sim, uint32_t* host_n_exceed) {
+    if (!ctx || !host_base || (n_suspects && (!host_suspects || !placements))) return SSW_ERR_BAD_ARG;
+    SSW_TRY(trace_check_args(ctx, cfg, w, h, k, host_marks, n_marks, host_sims, host_best, host_best_sim, host_n_exceed));
+    if (n_suspects == 0) return SSW_OK;
+    std::vector<ssw_placement> pl;
+    SSW_TRY(restore_normalise(placements, n_suspects, w, h, &pl));
+    CtxGuard g(ctx);
+    SSW_TRY(restore_prepare(ctx, pl));
+    SSW_TRY(grow(ctx->restore_base, w * h * 3));
+    SSW_TRY(upload(ctx, ctx->restore_base.p, host_base, w * h * 3, ctx->stream));
+    const float* yb = nullptr;
+    const uint32_t* idx = nullptr;
+    SSW_TRY(trace_base(ctx, *cfg, ctx->restore_base.p, SSW_PIX_U8, w, h, k, &yb, &idx));
+    return stream_trace_rgb8(ctx, *cfg, yb, idx, host_suspects, n_suspects, w, h, k, host_marks, n_marks, threshold, host_extracted,
+                             host_sims, host_best, host_best_sim, host_n_exceed, pl.data(), (const uint8_t*)ctx->restore_base.p);
 }
 
 // ---- 16-bit boundary (`into_rgb32f()` of an Rgb16 image, v / 65535, fused into the first operand
@@ -1248,6 +1279,35 @@ int ssw_reader_trace_host_rgb8(ssw_reader* base, const uint8_t* const* host_susp
     ctx->expected_k = k ? k : ctx->expected_k;
     return stream_trace_rgb8(ctx, base->cfg, base->y, base->idx, host_suspects, n_suspects, base->w, base->h, k, host_marks, n_marks,
                              threshold, host_extracted, host_sims, host_best, host_best_sim, host_n_exceed);
+}
+
+// The same on suspects that are restored first (tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70): the reader keeps
+// the plane and the list, not the image, so the original's pixels come again where a placement reads them
+int ssw_reader_trace_restored_host_rgb8(ssw_reader* base, const uint8_t* host_base_rgb, const uint8_t* const* host_suspects,
+                                        const ssw_placement* placements, size_t n_suspects, size_t k, const float* host_marks,
+                                        size_t n_marks, float threshold, float* host_extracted, float* host_sims,
+                                        uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed) {
+    if (!base || (n_suspects && (!host_suspects || !placements))) return SSW_ERR_BAD_ARG;
+    if (!base->is_base) return SSW_ERR_NOT_BASE;                                          // :530
+    ssw_ctx* ctx = base->ctx;
+    SSW_TRY(trace_check_args(ctx, &base->cfg, base->w, base->h, k, host_marks, n_marks, host_sims, host_best, host_best_sim, host_n_exceed));
+    if (n_suspects == 0) return SSW_OK;
+    std::vector<ssw_placement> pl;
+    SSW_TRY(restore_normalise(placements, n_suspects, base->w, base->h, &pl));
+    bool reads_base = false;
+    for (const ssw_placement& p : pl) reads_base = reads_base || restore_reads_base(p, base->w, base->h);
+    if (reads_base && !host_base_rgb) return SSW_ERR_BAD_ARG;
+    CtxGuard g(ctx);
+    SSW_TRY(restore_prepare(ctx, pl));
+    if (reads_base) {
+        SSW_TRY(grow(ctx->restore_base, base->w * base->h * 3));
+        SSW_TRY(upload(ctx, ctx->restore_base.p, host_base_rgb, base->w * base->h * 3, ctx->stream));
+    }
+    if (k) SSW_TRY(reader_ensure_indices(base, k));
+    ctx->expected_k = k ? k : ctx->expected_k;
+    return stream_trace_rgb8(ctx, base->cfg, base->y, base->idx, host_suspects, n_suspects, base->w, base->h, k, host_marks, n_marks,
+                             threshold, host_extracted, host_sims, host_best, host_best_sim, host_n_exceed, pl.data(),
+                             reads_base ? (const uint8_t*)ctx->restore_base.p : nullptr);
 }
 
 int ssw_reader_destroy(ssw_reader* rd) {

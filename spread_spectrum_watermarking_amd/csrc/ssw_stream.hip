@@ -194,7 +194,8 @@ int stream_extract_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* cons
 // marks once; the similarity matrix and its finish run over all suspects at the end, like the device form.
 int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, const uint32_t* base_idx, const uint8_t* const* host_suspects,
                       size_t n_suspects, size_t w, size_t h, size_t k, const float* host_marks, size_t n_marks, float threshold,
-                      float* host_extracted, float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed) {
+                      float* host_extracted, float* host_sims, uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed,
+                      const ssw_placement* pl, const uint8_t* dev_base) {
     for (size_t f = 0; f < n_suspects; ++f) if (!host_suspects[f]) return SSW_ERR_BAD_ARG;
     SSW_TRY(stream_setup(ctx));
     ssw_ctx::HostStream& hs = ctx->hs;
@@ -204,6 +205,13 @@ int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, co
     const size_t n_groups = groups.size();
     const bool score = host_sims || host_best || host_best_sim || host_n_exceed;
     for (int s = 0; s < (int)std::min<size_t>(n_groups, NB); ++s) SSW_TRY(grow(hs.in[s], G * fb));
+    // suspects that are restored first cross PCIe as they are, into raw slots beside the group's frames: one slot per frame of
+    // the group, each as large as the largest such suspect of the call (the ring stays G-sized whatever n_suspects is)
+    auto touched = [&](size_t f) { return pl && !restore_untouched(pl[f], w, h); };
+    auto raw_bytes = [&](size_t f) { return (size_t)pl[f].w * pl[f].h * pl[f].channels; };
+    size_t raw_slot = 0;
+    for (size_t f = 0; f < n_suspects; ++f) if (touched(f)) raw_slot = std::max(raw_slot, (raw_bytes(f) + 15) / 16 * 16);
+    if (raw_slot) for (int s = 0; s < (int)std::min<size_t>(n_groups, NB); ++s) SSW_TRY(grow(hs.in2[s], G * raw_slot));
     SSW_TRY(grow(hs.ext, std::max<size_t>(n_suspects * k * sizeof(float), 16)));
     if (n_marks) SSW_TRY(grow(hs.marks, std::max<size_t>(n_marks * k * sizeof(float), 16)));
     // results behind the extracted marks' buffer would move it: sims | best | best_sim | n_exceed in one block of their own
@@ -220,10 +228,14 @@ int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, co
             const int s = (int)(g % NB);
             const size_t f0 = groups[g].f0, n = groups[g].n;
             if (g >= (size_t)NB) SSW_HIP_CHECK(hipStreamWaitEvent(ctx->copy_stream, hs.k_done[s], 0));
-            for (size_t j = 0; j < n; ++j) SSW_TRY(upload_nowait(ctx, (char*)hs.in[s].p + j * fb, host_suspects[f0 + j], fb, ctx->copy_stream, &as));
+            for (size_t j = 0; j < n; ++j) {
+                if (touched(f0 + j)) SSW_TRY(upload_nowait(ctx, (char*)hs.in2[s].p + j * raw_slot, host_suspects[f0 + j], raw_bytes(f0 + j), ctx->copy_stream, &as));
+                else SSW_TRY(upload_nowait(ctx, (char*)hs.in[s].p + j * fb, host_suspects[f0 + j], fb, ctx->copy_stream, &as));
+            }
             SSW_HIP_CHECK(hipEventRecord(hs.up_done[s], ctx->copy_stream));
             return SSW_OK;
         };
+        std::vector<RestoreJob> jobs;
         for (size_t g = 0; g + 1 < (size_t)NB && g < n_groups; ++g) SSW_TRY(h2d(g));
         for (size_t g = 0; g < n_groups; ++g) {
             const int s = (int)(g % NB);
@@ -231,6 +243,10 @@ int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, co
             if (g + NB - 1 < n_groups) SSW_TRY(h2d(g + NB - 1));      // (before this group's look at its overflow flag: PCIe keeps running)
             SSW_HIP_CHECK(hipStreamWaitEvent(ctx->stream, hs.up_done[s], 0));
             untimed_work(ctx);
+            jobs.clear();                                             // raw slots -> the group's frames (none: no launch)
+            for (size_t j = 0; j < n; ++j)
+                if (touched(f0 + j)) jobs.push_back(RestoreJob{(const uint8_t*)hs.in2[s].p + j * raw_slot, (uint8_t*)hs.in[s].p + j * fb, pl[f0 + j]});
+            SSW_TRY(restore_enqueue(ctx, dev_base, w, h, jobs.data(), jobs.size()));
             SSW_TRY(trace_extract(ctx, c, base_y, base_idx, hs.in[s].p, SSW_PIX_U8, n, w, h, k, (float*)hs.ext.p + f0 * k));
             SSW_HIP_CHECK(hipEventRecord(hs.k_done[s], ctx->stream));
             untimed_work(ctx);
