@@ -254,7 +254,9 @@ typedef enum ssw_stage {
     SSW_STAGE_DCT_PREP = 10,      /* f64 operand pre-passes of folding levels 3 / 4 (HBM-bound) */
     SSW_STAGE_DCT_ROW_MAIN = 11,  /* the largest GEMM launch of a row pass alone (nested in DCT_ROW) */
     SSW_STAGE_DCT_COL_MAIN = 12,  /* the largest GEMM launch of a column pass alone (nested in DCT_COL) */
-    SSW_STAGE_COUNT = 13
+    SSW_STAGE_LOCATE = 13,        /* ssw_locate_rgb8: luma / box passes, coarse search, top-8, rescoring (bytes)  */
+    SSW_STAGE_LOCATE_COARSE = 14, /* the coarse SAD launches alone (nested in LOCATE); work = byte differences     */
+    SSW_STAGE_COUNT = 15
 } ssw_stage;
 int ssw_ctx_enable_timing(ssw_ctx* ctx, int enable);
 int ssw_ctx_reset_timing(ssw_ctx* ctx);
@@ -514,6 +516,38 @@ int ssw_reader_trace_restored_host_rgb8(ssw_reader* base, const uint8_t* host_ba
                                         const ssw_placement* placements, size_t n_suspects, size_t k, const float* host_marks,
                                         size_t n_marks, float threshold, float* host_extracted, float* host_sims,
                                         uint32_t* host_best, float* host_best_sim, uint32_t* host_n_exceed);
+
+/* ---- locating a cut-out: where in the original does a suspect lie? ---- */
+/* The placement of a cut-out is what ssw_restore_rgb8 needs and what the finder of a leaked copy does not know.  The
+   reference's crop test knows its rectangle (tests/attack_crop.rs:56-70); this is the search for it: a translation only --
+   no rotation, no unknown scale.  The size (pw, ph) the suspect had in the original's frame is its own (pw = ph = 0) or
+   given by the caller.  x, y of each placement are OUTPUTS; w, h, channels, pw, ph are inputs.
+   Definition, per suspect S [h][w][c] against the original O [H][W][3]; everything is an integer, no sum depends on its
+   order, and the result equals the numpy restatement in tests/test_locate_cpu.py exactly in x, y and SAD:
+     1. R = S when (pw, ph) == (w, h), else the CatmullRom resize of S to pw x ph with exactly the taps, clamping and
+        rounding of ssw_restore_rgb8 / ssw_resize_rgb8 (csrc/resize_common.hpp).  An alpha channel is ignored by the search:
+        a cut-out that is mostly transparent is not supported.
+     2. Luma L(p) = (77 R + 150 G + 29 B + 128) >> 8.
+     3. Candidate positions: 0 <= x <= W - pw, 0 <= y <= H - ph.
+     4. Coarse factor f = 4 when min(pw, ph) >= 64, else 1.  f = 1: B = L_O, S_f = L_R.  f = 4: B(x, y) =
+        (sum_{0<=i,j<4} L_O(x + i, y + j) + 8) >> 4, the box mean at EVERY pixel position (not decimated); S_f(i, j) is the
+        same box of L_R at (4 i, 4 j) for i < pw / 4, j < ph / 4 (integer division).
+     5. Coarse cost D(x, y) = sum_{i,j} |S_f(i, j) - B(x + f i, y + f j)| at every candidate position (u32: 255 pw ph / 16
+        fits).  For an exact cut-out D is 0 at the true position whatever its phase.
+     6. The 8 positions with the smallest (D, y, x) in lexicographic order (all of them when fewer exist).
+     7. For each of those SAD(x, y) = sum |L_R(i, j) - L_O(x + i, y + j)| over all pw ph pixels; the answer is the position
+        with the smallest (SAD, y, x), and host_sad[s] its SAD (64 bits: 255 W H exceeds 32 at 8K).
+   Known limit: a cut-out of a featureless region is ambiguous (many positions cost almost the same); the answer is still
+   the one this definition names.
+   dev_suspects / placements: HOST arrays of n device pointers / n placements; host_sad: HOST array of n.  No alignment is
+   assumed of any pointer.  The call synchronises: the answer is needed on the host.  Suspects run in groups of at most
+   256 MiB of workspace (one suspect's own need -- 4 bytes per candidate position, about 5 per pixel of R -- if that is more),
+   so the workspace is bounded for any n.  SSW_ERR_BAD_ARG: a rectangle larger than the frame, channels not 3 or 4, any zero
+   size; SSW_ERR_UNSUPPORTED: a resize that has no LDS tile (as ssw_restore_rgb8), 2^32 or more candidate positions;
+   n == 0: SSW_OK.  Timed as SSW_STAGE_LOCATE (the coarse search also as SSW_STAGE_LOCATE_COARSE; the resize of step 1 as
+   SSW_STAGE_RESIZE). */
+int ssw_locate_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, size_t h, const void* const* dev_suspects,
+                    ssw_placement* placements, size_t n, uint64_t* host_sad);
 
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,

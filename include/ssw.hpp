@@ -288,6 +288,44 @@ struct Suspect {
     Suspect(const ImageRgba8& im) : data(im.data.data()), width(im.width), height(im.height), channels(4) { if (im.data.size() != width * height * 4) throw Error(SSW_ERR_BAD_DIMS, "Suspect"); }
 };
 
+// Where a cut-out lies: the complete placement (ready for Reader::trace), the luma SAD there and the same per pixel
+struct Located {
+    Placement placement;
+    uint64_t sad = 0;
+    double mean_abs_diff = 0.0;
+};
+// ssw_locate_rgb8 on host images: finds each suspect in `original` by translation.  sizes[i]: the size suspect i had in the
+// original's frame ({0, 0}: its own; x, y of the entry are not read); an empty `sizes`: every suspect at its own size.
+inline std::vector<Located> locate(Context& ctx, const ImageRgb8& original, const std::vector<Suspect>& suspects,
+                                   const std::vector<Placement>& sizes = {}) {
+    const size_t n = suspects.size();
+    if ((!sizes.empty() && sizes.size() != n) || original.data.size() != original.width * original.height * 3) throw Error(SSW_ERR_BAD_DIMS, "locate");
+    std::vector<void*> dev(n + 1, nullptr);
+    struct Free {
+        ssw_ctx* c; std::vector<void*>& d;
+        ~Free() { for (void* p : d) if (p) ssw_dev_free(c, p); }
+    } guard{ctx.get(), dev};
+    auto put = [&](const void* src, size_t bytes, void** out) {
+        check(ssw_dev_alloc(ctx.get(), bytes, out), "locate");
+        check(ssw_copy_to_dev(ctx.get(), *out, src, bytes), "locate");
+    };
+    put(original.data.data(), original.data.size(), &dev[n]);
+    std::vector<ssw_placement> pl(n);
+    for (size_t i = 0; i < n; ++i) {
+        put(suspects[i].data, suspects[i].width * suspects[i].height * suspects[i].channels, &dev[i]);
+        const Placement s = sizes.empty() ? Placement() : sizes[i];
+        pl[i] = ssw_placement{(uint32_t)suspects[i].width, (uint32_t)suspects[i].height, (uint32_t)suspects[i].channels, 0u, 0u, (uint32_t)s.w, (uint32_t)s.h};
+    }
+    std::vector<uint64_t> sad(n);
+    check(ssw_locate_rgb8(ctx.get(), static_cast<const uint8_t*>(dev[n]), original.width, original.height, dev.data(), pl.data(), n, sad.data()), "locate");
+    std::vector<Located> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t pw = pl[i].pw ? pl[i].pw : pl[i].w, ph = pl[i].ph ? pl[i].ph : pl[i].h;
+        out[i] = Located{Placement{pl[i].x, pl[i].y, pw, ph}, sad[i], (double)sad[i] / ((double)pw * (double)ph)};
+    }
+    return out;
+}
+
 class Reader {                                         // algorithm.rs:441-594
 public:
     static Reader base(Context& ctx, const ImageRgb32F& image, const ReadConfig& config = ReadConfig()) {   // :462-464

@@ -26,7 +26,7 @@ OPTION1, OPTION2, OPTION3, METHOD_CUSTOM = 1, 2, 3, 4
 DCT2, DCT2_ORTHOGONAL, DCT3 = 0, 1, 2
 PRECISION_F32, PRECISION_F64 = 0, 1
 STAGES = ["rgb_to_yiq", "dct_row", "dct_col", "select", "embed", "extract", "similarity", "yiq_to_rgb",
-          "resize", "convert", "dct_prep", "dct_row_main", "dct_col_main"]
+          "resize", "convert", "dct_prep", "dct_row_main", "dct_col_main", "locate", "locate_coarse"]
 DCT_FOLDING_DEFAULT = 5
 TRACE_NONE = 0xFFFFFFFF      # ssw_fingerprint_trace: dev_best of a suspect that carries no mark
 PLAN_FLAGS = {"pair_f64": 1, "rows_deep": 2, "cols_deep": 4, "rows_level2": 8, "cols_level2": 16, "class_major": 32, "fused_cols": 64}
@@ -125,6 +125,7 @@ SIGNATURES = {
                                                   _f32p, _u32p]),
     "ssw_reader_trace_host_rgb8": (C.c_int, [_vp, C.POINTER(_vp), _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p, _f32p, _u32p]),
     "ssw_restore_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _vp]),
+    "ssw_locate_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, C.POINTER(C.c_uint64)]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
                                                            _f32p, _f32p, _u32p, _f32p, _u32p]),
     "ssw_reader_trace_restored_host_rgb8": (C.c_int, [_vp, _vp, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p,

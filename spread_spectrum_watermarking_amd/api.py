@@ -518,6 +518,8 @@ class Reader:
         if not self.is_base:
             raise SswError(L.SSW_ERR_NOT_BASE, "Reader::trace")
         if placements is not None:
+            if any(isinstance(p, Locate) for p in placements):           # cut-outs at an unknown position: one locate call
+                placements, _ = _resolve_locates(base, suspects, placements, self._ctx)
             arrs, ptrs, pl = _placed_suspects(suspects, placements, self.width, self.height)
             m, k = _trace_marks(marks, k)
             res = TraceResult.empty(len(arrs), m.shape[0], k)
@@ -713,6 +715,89 @@ def _placed_suspects(suspects, placements, W: int, H: int):
     return arrs, (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs]), pl
 
 
+# ---- locating cut-outs: the placement nobody told us (include/ssw.h: ssw_locate_rgb8) ---------------------------------------
+@dataclass
+class Locate:
+    """A placement entry that says "find me": the suspect is a cut-out of the original at an unknown position; w x h is the
+    size it had in the original's frame (None: its own size)."""
+    w: Optional[int] = None
+    h: Optional[int] = None
+
+
+@dataclass
+class Located:
+    """Where a suspect lies: `placement`, a complete Placement(x, y, w, h) ready for `restore` / `trace_many`; `sad`, the sum
+    of absolute luma differences there; `mean_abs_diff` = sad / (w * h) -- a few units for a true match of a marked copy."""
+    placement: Placement
+    sad: int
+    mean_abs_diff: float
+
+
+def _locate_sizes(arrs, sizes, W: int, H: int):
+    """One (w, h) pair, Locate or None per suspect -> ssw_placement array with x = y = 0 and the size each suspect had."""
+    sizes = list(sizes) if sizes is not None else [None] * len(arrs)
+    if len(sizes) != len(arrs):
+        raise ValueError("sizes: one entry (a Locate, a (w, h) pair or None) per suspect")
+    out = []
+    for a, z in zip(arrs, sizes):
+        w, h = (z.w, z.h) if isinstance(z, Locate) else (z if z is not None else (None, None))
+        if (w is None) != (h is None):
+            raise ValueError("Locate: w and h go together")
+        pw, ph = (int(w), int(h)) if w is not None else (a.shape[1], a.shape[0])
+        if pw <= 0 or ph <= 0 or pw > W or ph > H:
+            raise ValueError(f"Locate: a {pw}x{ph} rectangle does not fit the original ({W}x{H})")
+        out.append(L.Placement(a.shape[1], a.shape[0], a.shape[2], 0, 0, pw, ph))
+    return (L.Placement * len(out))(*out)
+
+
+def locate(base, suspects, sizes=None, ctx: Optional[Context] = None) -> list:
+    """Where in the original does each suspect lie?  A search over every translation on the device (ssw_locate_rgb8): integer
+    luma differences, a coarse pass over all positions, the 8 best rescored at full resolution -- exactly reproducible, see
+    include/ssw.h for the definition.  suspects: 8-bit [h, w, 3] or [h, w, 4] arrays (alpha is ignored: a mostly transparent
+    cut-out is not supported).  sizes: None, or per suspect a `Locate(w, h)` / (w, h) pair / None -- the size the cut-out
+    had in the original when it was scaled afterwards.  Returns one `Located` per suspect.  Rotation and unknown scale are
+    out of scope, and a cut-out of a featureless region (the cat's grey background) is ambiguous."""
+    ctx = ctx or default_context()
+    b = _base_rgb8(base)
+    H, W = b.shape[:2]
+    arrs = [np.ascontiguousarray(np.asarray(im)) for im in suspects]
+    if not arrs:
+        return []
+    for a in arrs:
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4) or 0 in a.shape:
+            raise ValueError("suspects must be 8-bit [h, w, 3] or [h, w, 4] arrays")
+    pl = _locate_sizes(arrs, sizes, W, H)
+    n = len(arrs)
+    dev_base = ctx.to_device(b)
+    dev = [ctx.to_device(a) for a in arrs]
+    ptrs = (C.c_void_p * n)(*[d.ptr.value for d in dev])
+    sad = (C.c_uint64 * n)()
+    try:
+        check(ctx._lib.ssw_locate_rgb8(ctx.handle, dev_base.ptr, W, H, ptrs, pl, n, sad), "ssw_locate_rgb8")
+    finally:
+        for d in dev + [dev_base]:
+            d.free()
+    return [Located(Placement(int(p.x), int(p.y), int(p.pw), int(p.ph)), int(s), int(s) / (int(p.pw) * int(p.ph))) for p, s in zip(pl, sad)]
+
+
+def _resolve_locates(base, suspects, placements, ctx=None, locate_fn=None):
+    """placements with `Locate` entries -> (placements with every Locate replaced by the Placement found, {index: Located}):
+    ONE locate call for all of them; the other entries pass through untouched."""
+    placements = list(placements)
+    suspects = list(suspects)
+    if len(placements) != len(suspects):
+        raise ValueError("placements: one entry (a Placement, a Locate or None) per suspect")
+    todo = [i for i, p in enumerate(placements) if isinstance(p, Locate)]
+    if not todo:
+        return placements, {}
+    if base is None:
+        raise ValueError("Locate entries need the original's pixels (base=)")
+    found = (locate_fn or locate)(base, [suspects[i] for i in todo], [placements[i] for i in todo], ctx)
+    for i, f in zip(todo, found):
+        placements[i] = f.placement
+    return placements, dict(zip(todo, found))
+
+
 def restore(base, suspects, placements=None, ctx: Optional[Context] = None) -> list:
     """What tracing with `placements` does to each suspect before it extracts, as frames: the recipes of the reference's
     attack tests -- resize back with CatmullRom (tests/attack_resize.rs:31-36), then "complement the attacked image with the
@@ -724,11 +809,14 @@ def restore(base, suspects, placements=None, ctx: Optional[Context] = None) -> l
     resized to w x h when its own size differs -- or None.  The rule for what is left out: a None entry, or a Placement
     without w / h at (0, 0), means "whole frame" when the suspect's size differs from the original's (a scaled copy), and
     "own size at (x, y)" otherwise (a cut-out, or an RGBA image of full size).  An alpha channel is filtered like a colour
-    channel and blended over the original: alpha 0 keeps the original's pixel."""
+    channel and blended over the original: alpha 0 keeps the original's pixel.  A `Locate(w, h)` entry is a cut-out whose
+    position is not known: all such entries are found with one `locate` call first and then treated as that Placement."""
     ctx = ctx or default_context()
     b = _base_rgb8(base)
     H, W = b.shape[:2]
     suspects = list(suspects)
+    if placements is not None and any(isinstance(p, Locate) for p in placements):
+        placements, _ = _resolve_locates(b, suspects, placements, ctx)
     arrs, _, pl = _placed_suspects(suspects, placements if placements is not None else [None] * len(suspects), W, H)
     n, fb = len(arrs), W * H * 3
     dev_base, dev_out = ctx.to_device(b), ctx.alloc(n * fb)
@@ -748,11 +836,14 @@ def trace_many(base, suspects, marks, k: Optional[int] = None, threshold: float 
 
     placements: None (every suspect has the original's shape, as before), or one entry per suspect, a `Placement` or None:
     suspects of any size with 3 or 4 channels are restored on the device first (ssw_fingerprint_trace_restored_host_rgb8;
-    `restore` spells out the rule and returns the frames this call extracts from)."""
+    `restore` spells out the rule and returns the frames this call extracts from).  `Locate(w, h)` entries -- cut-outs at an
+    unknown position -- are found with one `locate` call first."""
     ctx = ctx or default_context()
     config = config or ReadConfig.default()
     if placements is not None:
         b = _base_rgb8(base)
+        if any(isinstance(p, Locate) for p in placements):
+            placements, _ = _resolve_locates(b, suspects, placements, ctx)
         arrs, ptrs, pl = _placed_suspects(suspects, placements, b.shape[1], b.shape[0])
         m, k = _trace_marks(marks, k)
         res = TraceResult.empty(len(arrs), m.shape[0], k)

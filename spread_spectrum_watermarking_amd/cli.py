@@ -10,12 +10,14 @@
         -> <stem>_fp<i>.png (i zero-padded) and one <stem>_fp.json holding the N marks, described "<desc> #i";
            `test <file> <stem>_fp<i>.png <stem>_fp.json` then names the copy that leaked
     python -m spread_spectrum_watermarking_amd.cli trace <base> --suspects A.png B.png ... --marks X_fp.json [Y.json ...]
-            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] ...]
+            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] ...] [--locate FILE[=WxH] ...]
         -> one record per suspect: the stored mark it carries (or none) and every further mark above the threshold;
            one GPU call per group of stored marks with equal (config, length), whatever the number of suspects.
            Attacked copies are restored on the GPU first (tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70): a
            suspect of another size is resized back to the base's, an alpha channel is blended over the base, and
-           --place puts a cut-out where it belongs (at X,Y, scaled to WxH when given); their records say "Restored:"
+           --place puts a cut-out where it belongs (at X,Y, scaled to WxH when given); their records say "Restored:".
+           --locate finds where a cut-out belongs (the size WxH it had in the base when it was scaled afterwards) by a
+           search over every translation on the GPU; its record says "Located:" too
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -29,7 +31,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .api import MarkBuf, Placement, Reader, Tester, TraceResult, Writer
+from .api import Locate, MarkBuf, Placement, Reader, Tester, TraceResult, Writer, locate
 from .storage import Configuration, DescribedWatermark, Version1Storage
 
 _ORDERING_ARGS = {"energy": "Energy", "energy-orthogonal": "EnergyOrthogonal", "legacy": "Legacy"}
@@ -95,12 +97,43 @@ def trace_placements(suspects: List[str], place: Optional[List[str]]) -> Dict[st
     return out
 
 
+def parse_locate(text: str, suspects: List[str]) -> Tuple[str, Locate]:
+    """FILE[=WxH] -> (FILE, Locate); a text that is one of the suspects as it stands is a FILE without a size.  ValueError on
+    anything else."""
+    if text in suspects:
+        return text, Locate()
+    name, sep, spec = text.rpartition("=")
+    ws, xs, hs = spec.partition("x")
+    if not sep or not name or not xs or not (ws.isascii() and ws.isdigit() and hs.isascii() and hs.isdigit()):
+        raise ValueError(f"--locate {text!r}: expected FILE[=WxH]")
+    if int(ws) <= 0 or int(hs) <= 0:
+        raise ValueError(f"--locate {text!r}: empty size")
+    return name, Locate(int(ws), int(hs))
+
+
+def trace_locates(suspects: List[str], locates: Optional[List[str]], placed: Dict[str, Placement]) -> Dict[str, Locate]:
+    """The --locate options by suspect; ValueError for a malformed one, a FILE not among --suspects, one located twice, or one
+    that also has a --place."""
+    out: Dict[str, Locate] = {}
+    for text in locates or []:
+        name, z = parse_locate(text, suspects)
+        if name not in suspects:
+            raise ValueError(f"--locate {text!r}: {name!r} is not among --suspects")
+        if name in out:
+            raise ValueError(f"--locate {text!r}: {name!r} is located twice")
+        if name in placed:
+            raise ValueError(f"--locate {text!r}: {name!r} also has a --place")
+        out[name] = z
+    return out
+
+
 class _TraceParser(argparse.ArgumentParser):
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
         if getattr(a, "command", None) == "trace":
             try:
                 a.placements = trace_placements(a.suspects, a.place)
+                a.locates = trace_locates(a.suspects, a.locate, a.placements)
             except ValueError as e:
                 self.error(str(e))
         return a
@@ -139,6 +172,8 @@ def build_parser() -> argparse.ArgumentParser:
     r.add_argument("--marks", nargs="+", required=True, help="The watermark files to test from.")
     r.add_argument("--place", action="append", metavar="FILE=X,Y[,WxH]",
                    help="Where the cut-out FILE (one of --suspects) lies in the base, and the size it had there. Repeatable.")
+    r.add_argument("--locate", action="append", metavar="FILE[=WxH]",
+                   help="Find where the cut-out FILE (one of --suspects) lies in the base; WxH: the size it had there. Repeatable.")
     return p
 
 
@@ -241,9 +276,21 @@ def cmd_trace(args, out=sys.stdout) -> int:
     # size, tests/attack_crop.rs:56-70 for an alpha channel or a placed cut-out
     placements: List[Optional[Placement]] = []
     restored: List[Optional[str]] = []
+    # --locate: every cut-out at an unknown position is found with one call; from here on it is a placed suspect
+    placed: Dict[str, Placement] = dict(getattr(args, "placements", {}))
+    located: Dict[str, str] = {}
+    wanted = [(path, img, z) for path, img in zip(args.suspects, suspects) for z in [getattr(args, "locates", {}).get(path)] if z is not None]
+    for path, img, z in wanted:
+        zw, zh = (z.w, z.h) if z.w is not None else (img.shape[1], img.shape[0])
+        if zw > W or zh > H:
+            raise SystemExit(f"{path}: a {zw}x{zh} cut-out does not fit the base ({W}x{H})")
+    if wanted:
+        for (path, _, _), f in zip(wanted, locate(base, [img for _, img, _ in wanted], [z for _, _, z in wanted])):
+            placed[path] = f.placement
+            located[path] = f"{f.placement.x},{f.placement.y} (mean luma difference {f.mean_abs_diff:.2f})"
     for path, img in zip(args.suspects, suspects):
         sh, sw, c = img.shape
-        p = getattr(args, "placements", {}).get(path)
+        p = placed.get(path)
         if p is None and c == 3 and (sw, sh) == (W, H):
             placements.append(None)
             restored.append(None)
@@ -252,7 +299,7 @@ def cmd_trace(args, out=sys.stdout) -> int:
             p = Placement()
             if c == 3 and sw <= W and sh <= H and (sw < W or sh < H):
                 print(f"{path}: smaller than the base and not placed: taken as a scaled copy of the whole frame "
-                      f"(--place {path}=X,Y for a cut-out)", file=sys.stderr)
+                      f"(--place {path}=X,Y for a cut-out at a known position, --locate {path} to find it)", file=sys.stderr)
         whole = p.w is None and (p.x, p.y) == (0, 0) and (sw, sh) != (W, H)
         pw, ph = (W, H) if whole else ((p.w, p.h) if p.w is not None else (sw, sh))
         if p.x + pw > W or p.y + ph > H:
@@ -286,6 +333,8 @@ def cmd_trace(args, out=sys.stdout) -> int:
         top = max(exact, key=lambda r: r[0]) if exact else None
         print("-", file=out)
         print(f"  Suspect: \"{spath}\"", file=out)
+        if spath in located:
+            print(f"  Located: \"{located[spath]}\"", file=out)
         if restored[s] is not None:
             print(f"  Restored: \"{restored[s]}\"", file=out)
         if top is None:

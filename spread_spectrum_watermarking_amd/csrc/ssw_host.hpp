@@ -181,6 +181,10 @@ bool restore_reads_base(const ssw_placement& p, size_t w, size_t h);           /
 int restore_normalise(const ssw_placement* pl, size_t n, size_t w, size_t h, std::vector<ssw_placement>* out);
 int restore_prepare(ssw_ctx* ctx, const std::vector<ssw_placement>& pl);
 int restore_enqueue(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const RestoreJob* jobs, size_t n);
+// locate.hip (include/ssw.h: ssw_locate_rgb8): pl normalised with x = y = 0 and prepared; host_res [n][2]: SAD, (y << 32) | x.
+// Synchronises the context's stream.
+int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
+                const std::vector<ssw_placement>& pl, uint64_t* host_res);
 // ssw_lib.hip: the cached CatmullRom tap table (in_len -> out_len) of the context
 int get_taps(ssw_ctx* ctx, size_t in_len, size_t out_len, DeviceTaps* out);
 
