@@ -549,6 +549,48 @@ int ssw_reader_trace_restored_host_rgb8(ssw_reader* base, const uint8_t* host_ba
 int ssw_locate_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, size_t h, const void* const* dev_suspects,
                     ssw_placement* placements, size_t n, uint64_t* host_sad);
 
+/* ---- locating a cut-out whose scale is unknown: a scale ladder ---- */
+/* ssw_locate_rgb8 wants the size the cut-out had in the original; the finder of a part of the picture that was also scaled
+   for the web does not know it.  This is the search over scale as well: per suspect a range of widths wmin <= wmax the
+   cut-out may have had in the original.  pw, ph, x, y of each placement are OUTPUTS; w, h, channels are inputs.
+   Definition, per suspect S [sh][sw][c] against the original O [H][W][3]; everything is an integer, no sum depends on its
+   order, and the result equals the numpy restatement in tests/test_locate_scale_cpu.py exactly in pw, ph, x, y and SAD.
+   Lumas and the CatmullRom resize are those of steps 1 and 2 of ssw_locate_rgb8 above; the aspect ratio is kept:
+   ph(pw) = max(1, (2 sh pw + sw) / (2 sw)) (integer division).
+     Rungs.  pw_j = wmin + 8 j while <= wmax, plus wmax if it was not hit.  Rungs with pw_j > W or ph_j > H are dropped.
+       SSW_ERR_BAD_ARG if none is left, if wmin > wmax, or if min(wmin, ph(wmin)) < 32.
+     Ladder cost of rung j.  R_j = the resize of S to pw_j x ph_j.  T_j(i, k) = (sum of the 8 x 8 lumas of R_j at (8 i, 8 k)
+       + 32) >> 6 for i < pw_j / 8, k < ph_j / 8.  B8(x, y) = the same box mean of L_O, taken at every x, y that is a multiple
+       of 4 and where the box fits.  D_j(x, y) = sum_{i,k} |T_j(i, k) - B8(x + 8 i, y + 8 k)| at the candidate positions x, y
+       that are multiples of 4 with x <= W - pw_j, y <= H - ph_j.  The rung's entry is its smallest (D, y, x), with
+       n_j = (pw_j / 8)(ph_j / 8) samples.
+     Kept rungs.  The 8 rungs with the smallest D_j / n_j, compared by D_a n_b against D_b n_a in 64 bits; ties go to the
+       smaller j.
+     Refinement.  For every kept rung (pw_j, x_j, y_j) and every width pw in [pw_j - 7, pw_j + 7] that lies inside
+       [wmin, wmax] and fits the frame with ph(pw): steps 2-7 of ssw_locate_rgb8 on the resize of S to pw x ph(pw), restricted
+       to the candidate positions within +-8 of (x_j, y_j), clipped to the valid ones (a window that is empty after clipping
+       contributes nothing).  A width shared by two kept rungs is resized once.
+     Answer.  The (pw, ph, x, y, SAD) with the smallest SAD / (pw ph), compared by cross-multiplication in 64 bits
+       (255 * 2^26 * 2^26 fits); ties: smaller pw, then y, then x.  host_sad[s] is its SAD.
+   The rung step 8, the position stride 4, the box 8, the 8 kept rungs, +-7 and +-8 are fixed parts of the definition.
+   Known limits: the aspect ratio is assumed kept and there is no rotation; smooth regions are ambiguous, and a smaller rung
+   of a smooth patch can win on mean difference; min(pw, ph) >= 32 (enforced at wmin); an alpha channel is ignored.
+   What runs: per (suspect, rung) one fused resize tile whose epilogue stores only T_j (R_j never reaches memory), the
+   coarse kernel of ssw_locate_rgb8 on 2 x 2 phase planes of B8, and an atomic minimum of the key (D << 32) | position; every
+   tap table of the ladder goes up in one copy.  The 8 kept rungs and the final comparison are chosen on the HOST: the call
+   waits for the stream twice, after the ladder (8 bytes per rung come back) and for the answer, and the refinement's resizes
+   use the context's cached tap tables like ssw_restore_rgb8 (one more wait per table that is new to the context).
+   Workspace is grouped under the 256 MiB rule of ssw_locate_rgb8.  SSW_ERR_UNSUPPORTED: a rung's resize has no LDS tile
+   of whole boxes (a rung about ten times smaller than the suspect).  Other status codes as ssw_locate_rgb8; n == 0: SSW_OK.
+   Timed as SSW_STAGE_LOCATE, SSW_STAGE_LOCATE_COARSE (both coarse searches) and SSW_STAGE_RESIZE (rung tiles, refinement). */
+typedef struct ssw_scale_range { uint32_t wmin, wmax; } ssw_scale_range;
+int ssw_locate_scaled_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, size_t h, const void* const* dev_suspects,
+                           ssw_placement* placements, const ssw_scale_range* ranges, size_t n, uint64_t* host_sad);
+/* Diagnostic: T of ONE rung as the ladder's resize kernel stores it -- the (pw / 8) x (ph / 8) box means, row-major, of the
+   luma of the suspect [sh][sw][channels] resized to pw x ph -- into host_boxes.  pw, ph >= 8.  Synchronises. */
+int ssw_locate_rung_boxes(ssw_ctx* ctx, const void* dev_suspect, size_t sw, size_t sh, size_t channels, size_t pw, size_t ph,
+                          uint8_t* host_boxes);
+
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,
    and `into_rgb16()` from Rgb32F: round(clamp(v,0,1) * 65535) (`image 0.24.3`, like the 8-bit forms). */

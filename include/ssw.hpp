@@ -326,6 +326,41 @@ inline std::vector<Located> locate(Context& ctx, const ImageRgb8& original, cons
     return out;
 }
 
+// The widths a cut-out may have had in the original (ssw_scale_range): its scale is not known
+struct ScaleRange {
+    size_t wmin = 0, wmax = 0;
+};
+// ssw_locate_scaled_rgb8 on host images: finds each suspect in `original` by translation AND scale (aspect ratio kept, the
+// smaller side at least 32); Located::placement carries the size that was found.
+inline std::vector<Located> locate_scaled(Context& ctx, const ImageRgb8& original, const std::vector<Suspect>& suspects,
+                                          const std::vector<ScaleRange>& ranges) {
+    const size_t n = suspects.size();
+    if (ranges.size() != n || original.data.size() != original.width * original.height * 3) throw Error(SSW_ERR_BAD_DIMS, "locate_scaled");
+    std::vector<void*> dev(n + 1, nullptr);
+    struct Free {
+        ssw_ctx* c; std::vector<void*>& d;
+        ~Free() { for (void* p : d) if (p) ssw_dev_free(c, p); }
+    } guard{ctx.get(), dev};
+    auto put = [&](const void* src, size_t bytes, void** out) {
+        check(ssw_dev_alloc(ctx.get(), bytes, out), "locate_scaled");
+        check(ssw_copy_to_dev(ctx.get(), *out, src, bytes), "locate_scaled");
+    };
+    put(original.data.data(), original.data.size(), &dev[n]);
+    std::vector<ssw_placement> pl(n);
+    std::vector<ssw_scale_range> rg(n);
+    for (size_t i = 0; i < n; ++i) {
+        put(suspects[i].data, suspects[i].width * suspects[i].height * suspects[i].channels, &dev[i]);
+        pl[i] = ssw_placement{(uint32_t)suspects[i].width, (uint32_t)suspects[i].height, (uint32_t)suspects[i].channels, 0u, 0u, 0u, 0u};
+        rg[i] = ssw_scale_range{(uint32_t)ranges[i].wmin, (uint32_t)ranges[i].wmax};
+    }
+    std::vector<uint64_t> sad(n);
+    check(ssw_locate_scaled_rgb8(ctx.get(), static_cast<const uint8_t*>(dev[n]), original.width, original.height, dev.data(), pl.data(), rg.data(), n, sad.data()), "locate_scaled");
+    std::vector<Located> out(n);
+    for (size_t i = 0; i < n; ++i)
+        out[i] = Located{Placement{pl[i].x, pl[i].y, pl[i].pw, pl[i].ph}, sad[i], (double)sad[i] / ((double)pl[i].pw * (double)pl[i].ph)};
+    return out;
+}
+
 class Reader {                                         // algorithm.rs:441-594
 public:
     static Reader base(Context& ctx, const ImageRgb32F& image, const ReadConfig& config = ReadConfig()) {   // :462-464

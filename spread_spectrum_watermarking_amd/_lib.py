@@ -43,6 +43,11 @@ class Placement(C.Structure):
                 ("x", C.c_uint32), ("y", C.c_uint32), ("pw", C.c_uint32), ("ph", C.c_uint32)]
 
 
+class ScaleRange(C.Structure):
+    """ssw_scale_range (include/ssw.h): the widths a cut-out may have had in the original."""
+    _fields_ = [("wmin", C.c_uint32), ("wmax", C.c_uint32)]
+
+
 _vp, _f32p, _u32p, _u64p, _sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t
 _cfgp = C.POINTER(Config)
 _plp = C.POINTER(Placement)
@@ -126,6 +131,8 @@ SIGNATURES = {
     "ssw_reader_trace_host_rgb8": (C.c_int, [_vp, C.POINTER(_vp), _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p, _f32p, _u32p]),
     "ssw_restore_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _vp]),
     "ssw_locate_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, C.POINTER(C.c_uint64)]),
+    "ssw_locate_scaled_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, C.POINTER(ScaleRange), _sz, C.POINTER(C.c_uint64)]),
+    "ssw_locate_rung_boxes": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
                                                            _f32p, _f32p, _u32p, _f32p, _u32p]),
     "ssw_reader_trace_restored_host_rgb8": (C.c_int, [_vp, _vp, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p,

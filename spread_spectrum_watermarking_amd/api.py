@@ -18,8 +18,9 @@ GPU through libssw_hip.so; there is no CPU path in this package.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
-from typing import Callable, Optional, Sequence
+from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -719,18 +720,42 @@ def _placed_suspects(suspects, placements, W: int, H: int):
 @dataclass
 class Locate:
     """A placement entry that says "find me": the suspect is a cut-out of the original at an unknown position; w x h is the
-    size it had in the original's frame (None: its own size)."""
+    size it had in the original's frame (None: its own size).  When that size is not known either: `widths=(lo, hi)`, the
+    widths it may have had in the original, or `scale=(lo, hi)`, the same as factors of the suspect's own width (0.5: it was
+    enlarged to twice its size after it was cut out) -- found by the scale ladder of ssw_locate_scaled_rgb8."""
     w: Optional[int] = None
     h: Optional[int] = None
+    widths: Optional[Tuple[int, int]] = None
+    scale: Optional[Tuple[float, float]] = None
+
+    def width_range(self, suspect_width: int) -> Optional[Tuple[int, int]]:
+        """(wmin, wmax) of a ranged entry -- scale factors rounded outwards --, None for an entry of known size."""
+        if self.widths is None and self.scale is None:
+            return None
+        if (self.widths is not None and self.scale is not None) or self.w is not None or self.h is not None:
+            raise ValueError("Locate: one of (w, h), widths= and scale=")
+        lo, hi = self.widths if self.widths is not None else self.scale
+        if self.scale is not None:
+            if not (0 < lo <= hi):
+                raise ValueError("Locate: scale=(lo, hi) with 0 < lo <= hi")
+            lo, hi = max(1, math.floor(lo * suspect_width)), math.ceil(hi * suspect_width)
+        if int(lo) != lo or int(hi) != hi or not (0 < lo <= hi):
+            raise ValueError("Locate: widths=(lo, hi), integers with 0 < lo <= hi")
+        return int(lo), int(hi)
 
 
 @dataclass
 class Located:
     """Where a suspect lies: `placement`, a complete Placement(x, y, w, h) ready for `restore` / `trace_many`; `sad`, the sum
-    of absolute luma differences there; `mean_abs_diff` = sad / (w * h) -- a few units for a true match of a marked copy."""
+    of absolute luma differences there; `mean_abs_diff` = sad / (w * h) -- a few units for a true match of a marked copy.
+    `size` is the (w, h) the suspect had in the original: given by the caller, or found by the scale ladder."""
     placement: Placement
     sad: int
     mean_abs_diff: float
+
+    @property
+    def size(self) -> Tuple[int, int]:
+        return self.placement.w, self.placement.h
 
 
 def _locate_sizes(arrs, sizes, W: int, H: int):
@@ -755,8 +780,10 @@ def locate(base, suspects, sizes=None, ctx: Optional[Context] = None) -> list:
     luma differences, a coarse pass over all positions, the 8 best rescored at full resolution -- exactly reproducible, see
     include/ssw.h for the definition.  suspects: 8-bit [h, w, 3] or [h, w, 4] arrays (alpha is ignored: a mostly transparent
     cut-out is not supported).  sizes: None, or per suspect a `Locate(w, h)` / (w, h) pair / None -- the size the cut-out
-    had in the original when it was scaled afterwards.  Returns one `Located` per suspect.  Rotation and unknown scale are
-    out of scope, and a cut-out of a featureless region (the cat's grey background) is ambiguous."""
+    had in the original when it was scaled afterwards --, or a `Locate(widths=(lo, hi))` / `Locate(scale=(lo, hi))` when that
+    size is unknown: those entries go through the scale ladder (ssw_locate_scaled_rgb8; aspect ratio kept, the smaller side at
+    least 32) and `Located.size` says what was found.  Returns one `Located` per suspect.  Rotation is out of scope, and a
+    cut-out of a featureless region (the cat's grey background) is ambiguous."""
     ctx = ctx or default_context()
     b = _base_rgb8(base)
     H, W = b.shape[:2]
@@ -766,6 +793,12 @@ def locate(base, suspects, sizes=None, ctx: Optional[Context] = None) -> list:
     for a in arrs:
         if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4) or 0 in a.shape:
             raise ValueError("suspects must be 8-bit [h, w, 3] or [h, w, 4] arrays")
+    sizes = list(sizes) if sizes is not None else [None] * len(arrs)
+    if len(sizes) != len(arrs):
+        raise ValueError("sizes: one entry (a Locate, a (w, h) pair or None) per suspect")
+    ranges = [z.width_range(a.shape[1]) if isinstance(z, Locate) else None for a, z in zip(arrs, sizes)]
+    if any(r is not None for r in ranges):
+        return _locate_mixed(ctx, b, arrs, sizes, ranges)
     pl = _locate_sizes(arrs, sizes, W, H)
     n = len(arrs)
     dev_base = ctx.to_device(b)
@@ -778,6 +811,36 @@ def locate(base, suspects, sizes=None, ctx: Optional[Context] = None) -> list:
         for d in dev + [dev_base]:
             d.free()
     return [Located(Placement(int(p.x), int(p.y), int(p.pw), int(p.ph)), int(s), int(s) / (int(p.pw) * int(p.ph))) for p, s in zip(pl, sad)]
+
+
+def _locate_mixed(ctx, b, arrs, sizes, ranges) -> list:
+    """`locate` with ranged entries: one ssw_locate_scaled_rgb8 call for those, one ssw_locate_rgb8 call for the others."""
+    H, W = b.shape[:2]
+    ranged = [i for i, r in enumerate(ranges) if r is not None]
+    fixed = [i for i, r in enumerate(ranges) if r is None]
+    out = [None] * len(arrs)
+    dev_base = ctx.to_device(b)
+    dev = [ctx.to_device(a) for a in arrs]
+    try:
+        for idx, scaled in ((fixed, False), (ranged, True)):
+            if not idx:
+                continue
+            n = len(idx)
+            ptrs = (C.c_void_p * n)(*[dev[i].ptr.value for i in idx])
+            sad = (C.c_uint64 * n)()
+            if scaled:
+                pl = (L.Placement * n)(*[L.Placement(arrs[i].shape[1], arrs[i].shape[0], arrs[i].shape[2], 0, 0, 0, 0) for i in idx])
+                rg = (L.ScaleRange * n)(*[L.ScaleRange(*ranges[i]) for i in idx])
+                check(ctx._lib.ssw_locate_scaled_rgb8(ctx.handle, dev_base.ptr, W, H, ptrs, pl, rg, n, sad), "ssw_locate_scaled_rgb8")
+            else:
+                pl = _locate_sizes([arrs[i] for i in idx], [sizes[i] for i in idx], W, H)
+                check(ctx._lib.ssw_locate_rgb8(ctx.handle, dev_base.ptr, W, H, ptrs, pl, n, sad), "ssw_locate_rgb8")
+            for i, p, s in zip(idx, pl, sad):
+                out[i] = Located(Placement(int(p.x), int(p.y), int(p.pw), int(p.ph)), int(s), int(s) / (int(p.pw) * int(p.ph)))
+    finally:
+        for d in dev + [dev_base]:
+            d.free()
+    return out
 
 
 def _resolve_locates(base, suspects, placements, ctx=None, locate_fn=None):

@@ -10,14 +10,15 @@
         -> <stem>_fp<i>.png (i zero-padded) and one <stem>_fp.json holding the N marks, described "<desc> #i";
            `test <file> <stem>_fp<i>.png <stem>_fp.json` then names the copy that leaked
     python -m spread_spectrum_watermarking_amd.cli trace <base> --suspects A.png B.png ... --marks X_fp.json [Y.json ...]
-            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] ...] [--locate FILE[=WxH] ...]
+            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] ...] [--locate FILE[=WxH|=W0..W1] ...]
         -> one record per suspect: the stored mark it carries (or none) and every further mark above the threshold;
            one GPU call per group of stored marks with equal (config, length), whatever the number of suspects.
            Attacked copies are restored on the GPU first (tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70): a
            suspect of another size is resized back to the base's, an alpha channel is blended over the base, and
            --place puts a cut-out where it belongs (at X,Y, scaled to WxH when given); their records say "Restored:".
            --locate finds where a cut-out belongs (the size WxH it had in the base when it was scaled afterwards) by a
-           search over every translation on the GPU; its record says "Located:" too
+           search over every translation on the GPU; its record says "Located:" too.  FILE=W0..W1: the size is not known
+           either, only that the cut-out was between W0 and W1 wide in the base -- a search over scale as well
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -98,17 +99,30 @@ def trace_placements(suspects: List[str], place: Optional[List[str]]) -> Dict[st
 
 
 def parse_locate(text: str, suspects: List[str]) -> Tuple[str, Locate]:
-    """FILE[=WxH] -> (FILE, Locate); a text that is one of the suspects as it stands is a FILE without a size.  ValueError on
-    anything else."""
+    """FILE[=WxH] or FILE=W0..W1 -> (FILE, Locate); a text that is one of the suspects as it stands is a FILE without a size.
+    ValueError on anything else."""
     if text in suspects:
         return text, Locate()
     name, sep, spec = text.rpartition("=")
+    if ".." in spec:                                     # a range of widths: the scale is unknown
+        lo, _, hi = spec.partition("..")
+        if not sep or not name or not (lo.isascii() and lo.isdigit() and hi.isascii() and hi.isdigit()):
+            raise ValueError(f"--locate {text!r}: expected FILE=W0..W1")
+        if not 0 < int(lo) <= int(hi):
+            raise ValueError(f"--locate {text!r}: an empty range of widths")
+        return name, Locate(widths=(int(lo), int(hi)))
     ws, xs, hs = spec.partition("x")
     if not sep or not name or not xs or not (ws.isascii() and ws.isdigit() and hs.isascii() and hs.isdigit()):
         raise ValueError(f"--locate {text!r}: expected FILE[=WxH]")
     if int(ws) <= 0 or int(hs) <= 0:
         raise ValueError(f"--locate {text!r}: empty size")
     return name, Locate(int(ws), int(hs))
+
+
+def located_text(f, ranged: bool) -> str:
+    """The record's "Located:" value; an entry whose size was searched for says what was found."""
+    size = f" as {f.placement.w}x{f.placement.h}" if ranged else ""
+    return f"{f.placement.x},{f.placement.y}{size} (mean luma difference {f.mean_abs_diff:.2f})"
 
 
 def trace_locates(suspects: List[str], locates: Optional[List[str]], placed: Dict[str, Placement]) -> Dict[str, Locate]:
@@ -172,8 +186,9 @@ def build_parser() -> argparse.ArgumentParser:
     r.add_argument("--marks", nargs="+", required=True, help="The watermark files to test from.")
     r.add_argument("--place", action="append", metavar="FILE=X,Y[,WxH]",
                    help="Where the cut-out FILE (one of --suspects) lies in the base, and the size it had there. Repeatable.")
-    r.add_argument("--locate", action="append", metavar="FILE[=WxH]",
-                   help="Find where the cut-out FILE (one of --suspects) lies in the base; WxH: the size it had there. Repeatable.")
+    r.add_argument("--locate", action="append", metavar="FILE[=WxH|=W0..W1]",
+                   help="Find where the cut-out FILE (one of --suspects) lies in the base; WxH: the size it had there; "
+                        "W0..W1: the widths it may have had there (the scale is searched too). Repeatable.")
     return p
 
 
@@ -281,13 +296,15 @@ def cmd_trace(args, out=sys.stdout) -> int:
     located: Dict[str, str] = {}
     wanted = [(path, img, z) for path, img in zip(args.suspects, suspects) for z in [getattr(args, "locates", {}).get(path)] if z is not None]
     for path, img, z in wanted:
+        if z.widths is not None:
+            continue                                     # the ladder drops the widths that do not fit
         zw, zh = (z.w, z.h) if z.w is not None else (img.shape[1], img.shape[0])
         if zw > W or zh > H:
             raise SystemExit(f"{path}: a {zw}x{zh} cut-out does not fit the base ({W}x{H})")
     if wanted:
-        for (path, _, _), f in zip(wanted, locate(base, [img for _, img, _ in wanted], [z for _, _, z in wanted])):
+        for (path, _, z), f in zip(wanted, locate(base, [img for _, img, _ in wanted], [z for _, _, z in wanted])):
             placed[path] = f.placement
-            located[path] = f"{f.placement.x},{f.placement.y} (mean luma difference {f.mean_abs_diff:.2f})"
+            located[path] = located_text(f, z.widths is not None)
     for path, img in zip(args.suspects, suspects):
         sh, sw, c = img.shape
         p = placed.get(path)

@@ -18,9 +18,21 @@
 //   locate_fine_kernel          full-resolution SAD of one (suspect, candidate) per block group, u64
 //   locate_final_kernel         the candidate with the smallest (SAD, y, x)
 // Launch descriptors travel as kernel arguments, 32 suspects per launch, like restore.hip's.
+//
+// The scale ladder (ssw_locate_scaled_rgb8) for cut-outs whose size is not known either adds
+//   locate_box8_kernel          8 x 8 box means of the original at every fourth position, as 2 x 2 phase planes
+//   locate_rung_kernel          THE LADDER'S HOT PATH: one (suspect, rung) -- the fused CatmullRom tile of restore_resize_kernel
+//                               whose epilogue is clamp + round, luma and the 8 x 8 box sum; only the box means T_j are stored
+// and reuses locate_coarse_kernel (f = 2) and round 0 of locate_topk_kernel per rung; the 8 best rungs are refined by windowed
+// searches of the kernels above (a base offset in their descriptors).  The rungs are chosen on the host.
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
+#include <cstring>
+#include <map>
+
+#include "resize_common.hpp"
 #include "ssw_host.hpp"
 
 namespace ssw {
@@ -45,13 +57,14 @@ struct CoarseDev {
     uint32_t* D;                 // [ny][nx]
     uint32_t ppitch, prows, plane_stride;
     uint32_t tpitch, tw, th;
-    uint32_t nx, ny, f;
+    uint32_t nx, ny, f;          // f = 2: the scale ladder -- 2 x 2 phase planes of the 4-decimated 8 x 8 box plane
     uint32_t tiles_x, tiles_y, tile_begin;
+    uint32_t bxw, by;            // a windowed search: the plane word and row of candidate (0, 0); 0 for a search of the whole frame
 };
 struct CoarseBatch { CoarseDev it[LOC_BATCH]; };
-struct TopDev { const uint32_t* D; uint32_t n; };
+struct TopDev { const uint32_t* D; uint32_t n, nx, skipx, skipy; };     // skipx / skipy (with nx): candidates left of / above these are not part of the window
 struct TopBatch { TopDev it[LOC_BATCH]; };
-struct FineDev { const uint8_t* lr; uint32_t rpitch, pw, ph, nx; };
+struct FineDev { const uint8_t* lr; uint32_t rpitch, pw, ph, nx, bx, by; };   // bx, by: the frame position of candidate (0, 0)
 struct FineBatch { FineDev it[LOC_BATCH]; };
 
 __device__ inline uint32_t locate_luma(uint32_t r, uint32_t g, uint32_t b) { return (77u * r + 150u * g + 29u * b + 128u) >> 8; }
@@ -154,7 +167,7 @@ __global__ __launch_bounds__(256) void locate_coarse_kernel(CoarseBatch b, unsig
     const unsigned tile = blockIdx.x - d.tile_begin;
     const unsigned per_phase = d.tiles_x * d.tiles_y;
     const unsigned phase = tile / per_phase, tp = tile - phase * per_phase;
-    const unsigned px = d.f == 4 ? (phase & 3) : 0, py = d.f == 4 ? (phase >> 2) : 0;
+    const unsigned px = phase % d.f, py = phase / d.f;
     const unsigned nxp = d.nx > px ? (d.nx - px + d.f - 1) / d.f : 0;      // candidates of this phase
     const unsigned nyp = d.ny > py ? (d.ny - py + d.f - 1) / d.f : 0;
     const unsigned x0 = (tp % d.tiles_x) * LOC_TX, y0 = (tp / d.tiles_x) * LOC_TY;
@@ -172,7 +185,7 @@ __global__ __launch_bounds__(256) void locate_coarse_kernel(CoarseBatch b, unsig
             __syncthreads();
             for (unsigned it = tid; it < LOC_PROWS * LOC_PWORDS; it += 256) {
                 const unsigned r = it / LOC_PWORDS, c = it - r * LOC_PWORDS;
-                const unsigned row = y0 + j0 + r, wd = (x0 + i0) / 4 + c;
+                const unsigned row = d.by + y0 + j0 + r, wd = d.bxw + (x0 + i0) / 4 + c;
                 sP[r][c] = (row < d.prows && wd < pwords) ? plane[(size_t)row * pwords + wd] : 0u;
             }
             if (tid < LOC_JB * LOC_KW) {
@@ -222,6 +235,7 @@ __global__ __launch_bounds__(256) void locate_topk_kernel(TopBatch b, uint64_t* 
     uint64_t m = LOC_NONE;
     for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < d.n; i += gridDim.x * 256) {
         const uint64_t key = ((uint64_t)d.D[i] << 32) | i;
+        if ((d.skipx | d.skipy) && (i % d.nx < d.skipx || i / d.nx < d.skipy)) continue;
         if ((!round || key > prev) && key < m) m = key;
     }
     m = locate_block_min(m, s_red);
@@ -236,7 +250,7 @@ __global__ __launch_bounds__(256) void locate_fine_kernel(FineBatch b, const uin
     const FineDev& d = b.it[blockIdx.z];
     const uint64_t key = keys[(size_t)blockIdx.z * LOC_TOP + blockIdx.y];
     if (key == LOC_NONE) return;
-    const uint32_t idx = (uint32_t)key, y = idx / d.nx, x = idx - y * d.nx;
+    const uint32_t idx = (uint32_t)key, y = d.by + idx / d.nx, x = d.bx + idx % d.nx;
     const uint32_t* __restrict__ lo32 = reinterpret_cast<const uint32_t*>(lo);
     uint64_t total = 0;
     for (unsigned j = blockIdx.x; j < d.ph; j += gridDim.x) {
@@ -269,9 +283,142 @@ __global__ __launch_bounds__(64) void locate_final_kernel(FineBatch b, unsigned 
         const uint32_t idx = (uint32_t)key;
         if (sad < best || (sad == best && idx < best_idx)) { best = sad; best_idx = idx; }
     }
-    const uint32_t y = best_idx / b.it[s].nx, x = best_idx - y * b.it[s].nx;
+    const uint32_t y = b.it[s].by + best_idx / b.it[s].nx, x = b.it[s].bx + best_idx % b.it[s].nx;
     res[2 * s] = best;
     res[2 * s + 1] = ((uint64_t)y << 32) | x;
+}
+
+// ---- the scale ladder (ssw_locate_scaled_rgb8) --------------------------------------------------------------------------------
+// One (suspect, rung) of a launch: the suspect resized to pw x ph, of which only the 8 x 8 box means T [th][tw] are stored.
+// Tap tables are offsets (32-bit words) into the one buffer of the call.
+struct RungDev {
+    const uint8_t* src;          // the suspect [sh][sw][C]
+    uint8_t* T;                  // [th][tpitch]
+    uint32_t vleft, vcount, vweights, hleft, hcount, hweights;
+    uint32_t sw, vmax, hmax;
+    uint32_t ow, oh;             // 8 tw, 8 th: the output pixels that lie in a box
+    uint32_t tpitch;
+    uint32_t oyb, oxb, pitch, tiles_x, oxb_log2;      // ResizeTile; oyb, oxb multiples of 8: no box straddles two blocks
+    uint32_t tile_begin;
+};
+struct RungBatch { RungDev it[LOC_BATCH]; };
+
+// One thread = one byte of a phase plane: out[z][yq][xq] = (sum of the 8 x 8 lumas at (4 (2 xq + z % 2), 4 (2 yq + z / 2)) + 32) >> 6
+// where that box lies inside the plane, 0 elsewhere (the pitch's padding included).  grid: (opitch / 256, rows)
+__global__ __launch_bounds__(256) void locate_box8_kernel(const uint8_t* __restrict__ luma, unsigned lpitch, unsigned w, unsigned h,
+                                                          uint8_t* __restrict__ out, unsigned opitch, unsigned rows, unsigned plane_stride) {
+    const unsigned xq = blockIdx.x * 256 + threadIdx.x;
+    if (xq >= opitch) return;
+    for (unsigned z = 0; z < 4; ++z) {
+        for (unsigned yq = blockIdx.y; yq < rows; yq += gridDim.y) {
+            const unsigned x = 4 * (2 * xq + (z & 1)), y = 4 * (2 * yq + (z >> 1));
+            uint32_t v = 0;
+            if (x + 8 <= w && y + 8 <= h) {
+                uint32_t s = 32;
+#pragma unroll
+                for (unsigned j = 0; j < 8; ++j) {
+                    const uint32_t* __restrict__ r = reinterpret_cast<const uint32_t*>(luma + (size_t)(y + j) * lpitch + x);   // x, lpitch: multiples of 4
+                    s = __builtin_amdgcn_sad_u8(r[0], 0u, s);
+                    s = __builtin_amdgcn_sad_u8(r[1], 0u, s);
+                }
+                v = s >> 6;
+            }
+            out[(size_t)z * plane_stride + (size_t)yq * opitch + xq] = (uint8_t)v;
+        }
+    }
+}
+
+// THE HOT PATH of the ladder.  One block = one tile of oyb x oxb pixels of one rung: the fused CatmullRom tile of
+// restore_resize_kernel (tile -> LDS, vertical pass into an f32 strip, horizontal pass; every helper from resize_common.hpp),
+// with clamp + round, luma and the 8 x 8 box sum as its epilogue.  R_j never reaches HBM: only T_j is stored.  C = 4: alpha
+// is read past and ignored.  grid: (tiles of all rungs of the launch); dynamic LDS: the largest tile's.
+template <int C>
+__global__ __launch_bounds__(256) void locate_rung_kernel(RungBatch b, unsigned n, const uint32_t* __restrict__ taps) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned s = 0;
+    while (s + 1 < n && blockIdx.x >= b.it[s + 1].tile_begin) ++s;
+    const RungDev& d = b.it[s];
+    const ResizeTile tl{d.oyb, d.oxb, d.pitch, 0u, d.tiles_x, 0u, d.oxb_log2};
+    const unsigned vmax = d.vmax, hmax = d.hmax;
+    const uint32_t* __restrict__ vleft = taps + d.vleft;
+    const uint32_t* __restrict__ vcount = taps + d.vcount;
+    const float* __restrict__ vweights = reinterpret_cast<const float*>(taps + d.vweights);
+    const uint32_t* __restrict__ hleft = taps + d.hleft;
+    const uint32_t* __restrict__ hcount = taps + d.hcount;
+    const float* __restrict__ hweights = reinterpret_cast<const float*>(taps + d.hweights);
+    float* s_v = reinterpret_cast<float*>(smem);
+    float* s_wh = s_v + (size_t)tl.oyb * tl.pitch;
+    float* s_wv = s_wh + (size_t)tl.oxb * hmax;
+    uint32_t* s_lv = reinterpret_cast<uint32_t*>(s_wv + (size_t)tl.oyb * vmax);
+    uint32_t* s_cv = s_lv + tl.oyb;
+    uint32_t* s_lh = s_cv + tl.oyb;
+    uint32_t* s_ch = s_lh + tl.oxb;
+    unsigned char* s_in = smem + resize_lds_in_offset(tl, hmax, vmax);
+    unsigned char* s_lum = s_in;                       // reused after the vertical pass: [oyb][oxb] lumas
+
+    const unsigned tid = threadIdx.x;
+    const unsigned tile = blockIdx.x - d.tile_begin;
+    const unsigned tx = tile % tl.tiles_x, ty = tile / tl.tiles_x;
+    const unsigned oy0 = ty * tl.oyb, ox0 = tx * tl.oxb;
+    const unsigned noy = d.oh - oy0 < tl.oyb ? d.oh - oy0 : tl.oyb;      // multiples of 8
+    const unsigned nox = d.ow - ox0 < tl.oxb ? d.ow - ox0 : tl.oxb;
+
+    const unsigned r0 = vleft[oy0], r1 = vleft[oy0 + noy - 1] + vcount[oy0 + noy - 1];
+    const unsigned b0 = hleft[ox0] * C, b1 = (hleft[ox0 + nox - 1] + hcount[ox0 + nox - 1]) * C;
+    const unsigned a0 = b0 & ~3u;
+    const unsigned words = (b1 - a0 + 3) / 4;
+    const unsigned nrows = r1 - r0;
+    const unsigned row_bytes = d.sw * C;
+    {   // 1. tap tables and input tile -> LDS
+        for (unsigned i = tid; i < nox * hmax; i += 256) { const unsigned x = i / hmax, tp = i - x * hmax; s_wh[tp * tl.oxb + x] = hweights[(size_t)ox0 * hmax + i]; }   // tap-major
+        for (unsigned i = tid; i < noy * vmax; i += 256) s_wv[i] = vweights[(size_t)oy0 * vmax + i];
+        if (tid < noy) { s_lv[tid] = vleft[oy0 + tid]; s_cv[tid] = vcount[oy0 + tid]; }
+        if (tid < nox) { s_lh[tid] = hleft[ox0 + tid]; s_ch[tid] = hcount[ox0 + tid]; }
+        const uint8_t* __restrict__ src = d.src + (size_t)r0 * row_bytes + a0;
+        const unsigned avail = row_bytes - a0;                          // bytes from a0 to the end of the suspect's row
+        const bool rows_aligned = (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (row_bytes & 3) == 0;
+        for (unsigned it = tid; it < nrows * words; it += 256) {
+            const unsigned r = it / words, wd = it - r * words;
+            const uint8_t* p = src + (size_t)r * row_bytes + 4 * wd;
+            uint32_t v = 0;
+            if (rows_aligned && 4 * wd + 4 <= avail) v = *reinterpret_cast<const uint32_t*>(p);
+            else {                                                      // stay inside the row: never past the suspect's last byte
+#pragma unroll
+                for (unsigned e = 0; e < 4; ++e) if (4 * wd + e < avail) v |= (uint32_t)p[e] << (8 * e);
+            }
+            *reinterpret_cast<uint32_t*>(s_in + r * tl.pitch + 4 * wd) = v;
+        }
+    }
+    __syncthreads();
+    // 2. vertical pass: whole LDS rows, slack included (bytes the tile did not load give finite sums nobody reads)
+    {
+        const unsigned chunks16 = tl.pitch / 16;
+        if (noy * chunks16 >= 192) resize_vertical_pieces<4>(s_in, s_v, s_wv, s_lv, s_cv, r0, noy, chunks16, vmax, tl.pitch, tid);
+        else                       resize_vertical_pieces<2>(s_in, s_v, s_wv, s_lv, s_cv, r0, noy, tl.pitch / 8, vmax, tl.pitch, tid);
+    }
+    __syncthreads();
+    // 3. horizontal pass, clamp + round of the colour channels, luma
+    for (unsigned it = tid; it < (noy << tl.oxb_log2); it += 256) {
+        const unsigned j = it >> tl.oxb_log2, x = it & ((1u << tl.oxb_log2) - 1);
+        if (x >= nox) continue;
+        float t[C];
+        resize_horizontal_pixel<C>(s_v + j * tl.pitch + (s_lh[x] * C - a0), s_wh + x, s_ch[x], tl.oxb, t);
+        s_lum[j * tl.oxb + x] = (unsigned char)locate_luma(resize_to_u8(t[0]), resize_to_u8(t[1]), resize_to_u8(t[2]));
+    }
+    __syncthreads();
+    // 4. the boxes of the tile: one thread each, 16 words
+    const unsigned nbx = nox / 8, nby = noy / 8;
+    for (unsigned it = tid; it < nbx * nby; it += 256) {
+        const unsigned bk = it / nbx, bi = it - bk * nbx;
+        uint32_t sum = 32;
+#pragma unroll
+        for (unsigned j = 0; j < 8; ++j) {
+            const uint32_t* r = reinterpret_cast<const uint32_t*>(s_lum + (8 * bk + j) * tl.oxb + 8 * bi);
+            sum = __builtin_amdgcn_sad_u8(r[0], 0u, sum);
+            sum = __builtin_amdgcn_sad_u8(r[1], 0u, sum);
+        }
+        d.T[(size_t)(oy0 / 8 + bk) * d.tpitch + ox0 / 8 + bi] = (uint8_t)(sum >> 6);
+    }
 }
 
 namespace host {
@@ -288,6 +435,11 @@ struct Item {
     unsigned f, nx, ny;           // coarse factor, candidate positions
     unsigned rpitch, tw, th, tpitch;
     size_t off_rgb, off_strip, off_lr, off_sf, off_d, bytes;
+    // a windowed search (the refinement of the scale ladder): the frame position of candidate (0, 0) -- aligned down so that
+    // plane words and phases line up --, the candidates in front of the window, and whether R is the R of the item before
+    unsigned bx = 0, by = 0, skipx = 0, skipy = 0;
+    bool share = false;
+    size_t bytes_d = 0;
 };
 
 constexpr size_t GROUP_BYTES = 256u << 20;      // workspace of one group of suspects (one suspect may need more)
@@ -295,7 +447,7 @@ constexpr size_t GROUP_BYTES = 256u << 20;      // workspace of one group of sus
 }  // namespace
 
 int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
-                const std::vector<ssw_placement>& pl, uint64_t* host_res) {
+                const std::vector<ssw_placement>& pl, uint64_t* host_res, const std::vector<LocWindow>* win) {
     const size_t n = pl.size();
     hipStream_t st = ctx->stream;
     std::vector<Item> items(n);
@@ -308,6 +460,14 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
         any_f4 |= it.f == 4;
         it.nx = (unsigned)(w - it.p.pw + 1);
         it.ny = (unsigned)(h - it.p.ph + 1);
+        if (win) {
+            const LocWindow& wd = (*win)[i];
+            const unsigned ax = it.f == 4 ? 16u : 4u, ay = it.f == 4 ? 4u : 1u;
+            it.bx = wd.x0 / ax * ax; it.by = wd.y0 / ay * ay;
+            it.skipx = wd.x0 - it.bx; it.skipy = wd.y0 - it.by;
+            it.nx = wd.x1 - it.bx + 1; it.ny = wd.y1 - it.by + 1;
+            it.share = wd.share && i > 0;
+        }
         if ((uint64_t)it.nx * it.ny > 0xFFFFFFFFull) return SSW_ERR_UNSUPPORTED;      // a position is 32 bits of the key
         it.rpitch = (unsigned)up(it.p.pw, 4);
         it.tw = it.f == 4 ? it.p.pw / 4 : it.p.pw;
@@ -319,7 +479,8 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
         it.off_strip = o; o += rs && it.p.channels == 4 ? up((size_t)it.p.w * it.p.h * 3, 256) : 0;
         it.off_lr = o;    o += up((size_t)it.rpitch * it.p.ph, 256);
         it.off_sf = o;    o += it.f == 4 ? up((size_t)it.tpitch * it.th, 256) : 0;
-        it.off_d = o;     o += up((size_t)it.nx * it.ny * 4, 256);
+        it.bytes_d = up((size_t)it.nx * it.ny * 4, 256);
+        it.off_d = o;     o += it.bytes_d;
         it.bytes = o;
     }
     // the original: luma plane once per call, and its 16 phase planes when a suspect takes the coarse factor 4
@@ -353,15 +514,22 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
     // suspects in groups of bounded workspace, in the order of the call
     for (size_t g0 = 0; g0 < n;) {
         size_t g1 = g0, bytes = 0;
-        while (g1 < n && (g1 == g0 || bytes + items[g1].bytes <= GROUP_BYTES)) bytes += items[g1++].bytes;
+        auto need = [&](size_t i) { return items[i].share && i > g0 ? items[i].bytes_d : items[i].bytes; };   // a shared R lives in its group
+        while (g1 < n && (g1 == g0 || bytes + need(g1) <= GROUP_BYTES)) bytes += need(g1++);
         SSW_TRY(grow(ctx->locate[2], bytes + 16));
         uint8_t* ws = (uint8_t*)ctx->locate[2].p;
-        std::vector<size_t> base_off(g1 - g0);
-        for (size_t i = g0, o = 0; i < g1; ++i) { base_off[i - g0] = o; o += items[i].bytes; }
+        std::vector<size_t> base_off(g1 - g0), d_off(g1 - g0);
+        std::vector<char> shared(g1 - g0);
+        for (size_t i = g0, o = 0; i < g1; ++i) {
+            shared[i - g0] = items[i].share && i > g0;
+            base_off[i - g0] = shared[i - g0] ? base_off[i - 1 - g0] : o;
+            d_off[i - g0] = shared[i - g0] ? o : o + items[i].off_d;
+            o += need(i);
+        }
         // 1. R: the suspect resized to the size it had in the original (alpha dropped first); timed as SSW_STAGE_RESIZE
         for (size_t i = g0; i < g1; ++i) {
             const Item& it = items[i];
-            if (it.p.pw == it.p.w && it.p.ph == it.p.h) continue;
+            if ((it.p.pw == it.p.w && it.p.ph == it.p.h) || shared[i - g0]) continue;
             uint8_t* wsi = ws + base_off[i - g0];
             const uint8_t* src = (const uint8_t*)dev_suspects[i];
             if (it.p.channels == 4) {
@@ -388,17 +556,18 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
             CoarseBatch cb{};
             TopBatch tb{};
             FineBatch fb{};
-            unsigned nbox = 0, tiles = 0, max_words = 1, max_rows = 1, max_q = 1, max_qrows = 1, max_ph = 1;
+            unsigned nl = 0, nbox = 0, tiles = 0, max_words = 1, max_rows = 1, max_q = 1, max_qrows = 1, max_ph = 1;
             uint32_t max_n = 1;
             for (unsigned s = 0; s < m; ++s) {
                 const Item& it = items[b0 + s];
                 uint8_t* wsi = ws + base_off[b0 + s - g0];
                 const bool rs = it.p.pw != it.p.w || it.p.ph != it.p.h;
-                lb.it[s] = LumaDev{rs ? wsi + it.off_rgb : (const uint8_t*)dev_suspects[b0 + s], wsi + it.off_lr, it.p.pw, it.p.ph,
-                                   rs ? 3u : it.p.channels, it.rpitch};
+                const bool own = !shared[b0 + s - g0];
+                if (own) lb.it[nl++] = LumaDev{rs ? wsi + it.off_rgb : (const uint8_t*)dev_suspects[b0 + s], wsi + it.off_lr, it.p.pw, it.p.ph,
+                                               rs ? 3u : it.p.channels, it.rpitch};
                 max_words = std::max(max_words, it.rpitch / 4);
                 max_rows = std::max(max_rows, it.p.ph);
-                if (it.f == 4) {
+                if (it.f == 4 && own) {
                     bb.it[nbox++] = BoxDev{wsi + it.off_lr, wsi + it.off_sf, it.rpitch, it.p.pw, it.p.ph, it.tpitch, it.tw, it.th, 1u, 0u};
                     max_q = std::max(max_q, it.tpitch);
                     max_qrows = std::max(max_qrows, it.th);
@@ -406,7 +575,7 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
                 CoarseDev& c = cb.it[s];
                 c.plane = it.f == 4 ? phases : lo;
                 c.tmpl = wsi + (it.f == 4 ? it.off_sf : it.off_lr);
-                c.D = (uint32_t*)(wsi + it.off_d);
+                c.D = (uint32_t*)(ws + d_off[b0 + s - g0]);
                 c.ppitch = it.f == 4 ? qpitch : opitch;
                 c.prows = it.f == 4 ? hq : (uint32_t)h;
                 c.plane_stride = it.f == 4 ? (uint32_t)plane_stride : 0u;
@@ -415,14 +584,17 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
                 c.tiles_x = ((it.nx + it.f - 1) / it.f + LOC_TX - 1) / LOC_TX;
                 c.tiles_y = ((it.ny + it.f - 1) / it.f + LOC_TY - 1) / LOC_TY;
                 c.tile_begin = tiles;
+                c.bxw = it.bx / (4 * it.f); c.by = it.by / it.f;
                 tiles += c.tiles_x * c.tiles_y * it.f * it.f;
-                tb.it[s] = TopDev{c.D, it.nx * it.ny};
+                tb.it[s] = TopDev{c.D, it.nx * it.ny, it.nx, it.skipx, it.skipy};
                 max_n = std::max(max_n, it.nx * it.ny);
-                fb.it[s] = FineDev{wsi + it.off_lr, it.rpitch, it.p.pw, it.p.ph, it.nx};
+                fb.it[s] = FineDev{wsi + it.off_lr, it.rpitch, it.p.pw, it.p.ph, it.nx, it.bx, it.by};
                 max_ph = std::max(max_ph, it.p.ph);
             }
-            locate_luma_kernel<<<dim3((max_words + 255) / 256, grid_rows(max_rows), m), 256, 0, st>>>(lb);
-            SSW_HIP_CHECK(hipGetLastError());
+            if (nl) {
+                locate_luma_kernel<<<dim3((max_words + 255) / 256, grid_rows(max_rows), nl), 256, 0, st>>>(lb);
+                SSW_HIP_CHECK(hipGetLastError());
+            }
             if (nbox) {
                 locate_box_kernel<<<dim3((max_q + 255) / 256, grid_rows(max_qrows), nbox), 256, 0, st>>>(bb);
                 SSW_HIP_CHECK(hipGetLastError());
@@ -453,6 +625,306 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
     return SSW_OK;
 }
 
+// ---- the scale ladder: host side ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr unsigned LAD_STEP = 8, LAD_KEEP = 8, LAD_NEAR_W = 7, LAD_NEAR_XY = 8, LAD_MIN = 32;
+
+uint32_t ladder_height(uint64_t pw, uint64_t sw, uint64_t sh) { return (uint32_t)std::max<uint64_t>(1, (2 * sh * pw + sw) / (2 * sw)); }
+
+// every tap table of a call's ladder in one host buffer: one upload, one wait
+struct TapRef { uint32_t left, count, weights; DeviceTaps shape; };      // offsets in words; shape: max_taps and span only
+struct LadderTaps {
+    std::vector<uint32_t> words;
+    std::map<std::pair<size_t, size_t>, TapRef> refs;
+    const TapRef& get(size_t in_len, size_t out_len) {
+        const auto key = std::make_pair(in_len, out_len);
+        const auto it = refs.find(key);
+        if (it != refs.end()) return it->second;
+        ResizeTaps t;
+        build_resize_taps(in_len, out_len, t);
+        TapRef r;
+        r.left = (uint32_t)words.size();   words.insert(words.end(), t.left.begin(), t.left.end());
+        r.count = (uint32_t)words.size();  words.insert(words.end(), t.count.begin(), t.count.end());
+        r.weights = (uint32_t)words.size();
+        words.resize(words.size() + t.weights.size());
+        std::memcpy(words.data() + r.weights, t.weights.data(), t.weights.size() * sizeof(float));
+        r.shape.max_taps = t.max_taps;
+        resize_spans(t, out_len, r.shape.span);
+        return refs[key] = r;
+    }
+};
+
+struct Rung {
+    uint32_t sus, pw, ph, tw, th, nx, ny;      // nx, ny: candidate positions (multiples of 4)
+    RungDev dev;                               // src, T and tile_begin are filled in per launch
+    uint32_t tiles, channels;
+    size_t lds, bytes_t, bytes_d;
+};
+
+// the rung pw x ph of a suspect p (w, h, channels); SSW_ERR_UNSUPPORTED: no LDS tile holds whole boxes of this resize
+int make_rung(LadderTaps& taps, const ssw_placement& p, uint32_t sus, uint32_t pw, uint32_t ph, size_t W, size_t H, Rung* out) {
+    Rung r{};
+    r.sus = sus; r.pw = pw; r.ph = ph; r.tw = pw / 8; r.th = ph / 8; r.channels = p.channels;
+    r.nx = (uint32_t)((W - pw) / 4 + 1); r.ny = (uint32_t)((H - ph) / 4 + 1);
+    const TapRef vt = taps.get(p.h, ph), ht = taps.get(p.w, pw);
+    if (taps.words.size() > 0xFFFFFFFFull) return SSW_ERR_UNSUPPORTED;
+    ResizeTile tl;
+    if (!pick_resize_tile(vt.shape, ht.shape, 8 * r.tw, 8 * r.th, p.channels, &tl, &r.lds, 3, 3)) return SSW_ERR_UNSUPPORTED;
+    RungDev& d = r.dev;
+    d.vleft = vt.left; d.vcount = vt.count; d.vweights = vt.weights; d.vmax = vt.shape.max_taps;
+    d.hleft = ht.left; d.hcount = ht.count; d.hweights = ht.weights; d.hmax = ht.shape.max_taps;
+    d.sw = p.w; d.ow = 8 * r.tw; d.oh = 8 * r.th; d.tpitch = (uint32_t)up(r.tw, 4);
+    d.oyb = tl.oyb; d.oxb = tl.oxb; d.pitch = tl.pitch; d.oxb_log2 = tl.oxb_log2;
+    d.tiles_x = (d.ow + tl.oxb - 1) / tl.oxb;
+    r.tiles = d.tiles_x * ((d.oh + tl.oyb - 1) / tl.oyb);
+    r.bytes_t = up((size_t)d.tpitch * r.th, 256);
+    r.bytes_d = up((size_t)r.nx * r.ny * 4, 256);
+    *out = r;
+    return SSW_OK;
+}
+
+int set_rung_lds_attribute() {     // tiles above 64 KB of dynamic LDS need the per-device function attribute: once per device
+    static std::atomic<bool> attr_set[64];
+    int dev = 0;
+    SSW_HIP_CHECK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
+        SSW_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(locate_rung_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+        SSW_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(locate_rung_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+        if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
+    }
+    return SSW_OK;
+}
+
+int upload_taps(ssw_ctx* ctx, const LadderTaps& taps, const uint32_t** dev) {
+    SSW_TRY(grow(ctx->locate[5], taps.words.size() * sizeof(uint32_t)));
+    SSW_HIP_CHECK(hipMemcpyAsync(ctx->locate[5].p, taps.words.data(), taps.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    untimed_work(ctx);
+    *dev = (const uint32_t*)ctx->locate[5].p;
+    return SSW_OK;
+}
+
+// the rung launches of rungs [b0, b1) (at most LOC_BATCH): one per channel count that occurs; T of rung i at t_ptr[i - b0]
+int enqueue_rungs(ssw_ctx* ctx, const std::vector<Rung>& rungs, size_t b0, size_t b1, const void* const* dev_suspects, uint8_t* const* t_ptr,
+                  const uint32_t* dev_taps) {
+    double bytes = 0.0;
+    for (size_t i = b0; i < b1; ++i) bytes += (double)rungs[i].dev.sw * rungs[i].channels * rungs[i].dev.oh + (double)rungs[i].tw * rungs[i].th;
+    StageTimer t(ctx, SSW_STAGE_RESIZE, ctx->stream, bytes);
+    for (unsigned c = 3; c <= 4; ++c) {
+        RungBatch rb{};
+        unsigned m = 0, tiles = 0;
+        size_t lds = 0;
+        for (size_t i = b0; i < b1; ++i) {
+            if (rungs[i].channels != c) continue;
+            RungDev& d = rb.it[m++];
+            d = rungs[i].dev;
+            d.src = (const uint8_t*)dev_suspects[rungs[i].sus];
+            d.T = t_ptr[i - b0];
+            d.tile_begin = tiles;
+            tiles += rungs[i].tiles;
+            lds = std::max(lds, rungs[i].lds);
+        }
+        if (!m) continue;
+        if (c == 4) locate_rung_kernel<4><<<tiles, 256, lds, ctx->stream>>>(rb, m, dev_taps);
+        else        locate_rung_kernel<3><<<tiles, 256, lds, ctx->stream>>>(rb, m, dev_taps);
+        SSW_HIP_CHECK(hipGetLastError());
+    }
+    return SSW_OK;
+}
+
+}  // namespace
+
+// One suspect's answer of the scaled search
+struct ScaledAnswer { uint32_t pw, ph, x, y; uint64_t sad; };
+
+// pl: w, h, channels of each suspect (checked); ranges [n][2].  Waits for the stream twice: for the ladder's per-rung minima
+// (the 8 kept rungs decide which widths are resized next, and restore_enqueue's launches are shaped on the host), and for the answer.
+int locate_scaled_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
+                       const std::vector<ssw_placement>& pl, const uint32_t* ranges, ScaledAnswer* out) {
+    const size_t n = pl.size();
+    hipStream_t st = ctx->stream;
+    LadderTaps taps;
+    std::vector<Rung> rungs;
+    std::vector<size_t> first(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t wmin = ranges[2 * i], wmax = ranges[2 * i + 1];
+        if (wmin > wmax || std::min(wmin, ladder_height(wmin, pl[i].w, pl[i].h)) < LAD_MIN) return SSW_ERR_BAD_ARG;
+        for (uint64_t pw = wmin;; pw = std::min<uint64_t>(pw + LAD_STEP, wmax)) {
+            const uint32_t ph = ladder_height(pw, pl[i].w, pl[i].h);
+            if (pw > w || ph > h) break;                                // both grow with the rung: every later one leaves the frame too
+            Rung r;
+            SSW_TRY(make_rung(taps, pl[i], (uint32_t)i, (uint32_t)pw, ph, w, h, &r));
+            rungs.push_back(r);
+            if (pw == wmax) break;
+        }
+        first[i + 1] = rungs.size();
+        if (first[i + 1] == first[i]) return SSW_ERR_BAD_ARG;          // no rung fits the frame
+    }
+    const size_t nr = rungs.size();
+    // launches of at most LOC_BATCH rungs and GROUP_BYTES of workspace (T and D of each)
+    std::vector<size_t> cuts{0};
+    size_t ws_bytes = 0;
+    for (size_t b0 = 0; b0 < nr;) {
+        size_t b1 = b0, bytes = 0;
+        while (b1 < nr && b1 - b0 < LOC_BATCH && (b1 == b0 || bytes + rungs[b1].bytes_t + rungs[b1].bytes_d <= GROUP_BYTES)) {
+            bytes += rungs[b1].bytes_t + rungs[b1].bytes_d;
+            ++b1;
+        }
+        ws_bytes = std::max(ws_bytes, bytes);
+        cuts.push_back(b0 = b1);
+    }
+    const unsigned opitch = (unsigned)up(w, 4);
+    const unsigned nbx = (unsigned)((w - 8) / 4 + 1), nby = (unsigned)((h - 8) / 4 + 1);      // w, h >= 32: a rung fits
+    const unsigned qpitch = (unsigned)up((nbx + 1) / 2, 4), qrows = (nby + 1) / 2;
+    const size_t plane_stride = (size_t)qpitch * qrows;
+    if (4 * plane_stride > 0xFFFFFFFFull) return SSW_ERR_UNSUPPORTED;
+    SSW_TRY(grow(ctx->locate[0], (size_t)opitch * h + 16));
+    SSW_TRY(grow(ctx->locate[4], 4 * plane_stride + 16));
+    SSW_TRY(grow(ctx->locate[3], nr * LOC_TOP * sizeof(uint64_t)));
+    SSW_TRY(grow(ctx->locate[2], ws_bytes + 16));
+    uint8_t* lo = (uint8_t*)ctx->locate[0].p;
+    uint8_t* planes = (uint8_t*)ctx->locate[4].p;
+    uint64_t* keys = (uint64_t*)ctx->locate[3].p;
+    uint8_t* ws = (uint8_t*)ctx->locate[2].p;
+    const uint32_t* dev_taps = nullptr;
+    SSW_TRY(upload_taps(ctx, taps, &dev_taps));
+    SSW_TRY(set_rung_lds_attribute());
+    {
+        StageTimer t(ctx, SSW_STAGE_LOCATE, st, (double)w * h * 4.5);
+        SSW_HIP_CHECK(hipMemsetAsync(lo + (size_t)opitch * h, 0, 16, st));
+        LumaBatch lb{};
+        lb.it[0] = LumaDev{dev_base, lo, (uint32_t)w, (uint32_t)h, 3u, opitch};
+        locate_luma_kernel<<<dim3((opitch / 4 + 255) / 256, grid_rows(h), 1), 256, 0, st>>>(lb);
+        SSW_HIP_CHECK(hipGetLastError());
+        locate_box8_kernel<<<dim3((qpitch + 255) / 256, grid_rows(qrows)), 256, 0, st>>>(lo, opitch, (unsigned)w, (unsigned)h, planes, qpitch, qrows, (unsigned)plane_stride);
+        SSW_HIP_CHECK(hipGetLastError());
+        SSW_HIP_CHECK(hipMemsetAsync(keys, 0xFF, nr * LOC_TOP * sizeof(uint64_t), st));
+    }
+    for (size_t b = 0; b + 1 < cuts.size(); ++b) {
+        const size_t b0 = cuts[b], b1 = cuts[b + 1];
+        const unsigned m = (unsigned)(b1 - b0);
+        uint8_t* t_ptr[LOC_BATCH];
+        CoarseBatch cb{};
+        TopBatch tb{};
+        unsigned tiles = 0;
+        uint32_t max_n = 1;
+        double bd = 0.0, px_bytes = 0.0;
+        size_t o = 0;
+        for (unsigned s = 0; s < m; ++s) {
+            const Rung& r = rungs[b0 + s];
+            t_ptr[s] = ws + o;
+            CoarseDev& c = cb.it[s];
+            c.plane = planes; c.tmpl = t_ptr[s]; c.D = (uint32_t*)(ws + o + r.bytes_t);
+            c.ppitch = qpitch; c.prows = qrows; c.plane_stride = (uint32_t)plane_stride;
+            c.tpitch = r.dev.tpitch; c.tw = r.tw; c.th = r.th;
+            c.nx = r.nx; c.ny = r.ny; c.f = 2;
+            c.tiles_x = ((r.nx + 1) / 2 + LOC_TX - 1) / LOC_TX;
+            c.tiles_y = ((r.ny + 1) / 2 + LOC_TY - 1) / LOC_TY;
+            c.tile_begin = tiles;
+            tiles += c.tiles_x * c.tiles_y * 4;
+            tb.it[s] = TopDev{c.D, r.nx * r.ny, 0u, 0u, 0u};
+            max_n = std::max(max_n, r.nx * r.ny);
+            bd += (double)r.nx * r.ny * ((double)r.tw * r.th);
+            px_bytes += 8.0 * r.nx * r.ny + (double)r.tw * r.th;
+            o += r.bytes_t + r.bytes_d;
+        }
+        SSW_TRY(enqueue_rungs(ctx, rungs, b0, b1, dev_suspects, t_ptr, dev_taps));
+        StageTimer t(ctx, SSW_STAGE_LOCATE, st, px_bytes);
+        {
+            StageTimer tc(ctx, SSW_STAGE_LOCATE_COARSE, st);
+            if (ctx->timing) ctx->stage_work[SSW_STAGE_LOCATE_COARSE] += bd;          // byte differences, not bytes
+            locate_coarse_kernel<<<tiles, 256, 0, st>>>(cb, m);
+            SSW_HIP_CHECK(hipGetLastError());
+        }
+        // the rung's smallest (D, y, x): round 0 of the top-k, an atomic minimum of the 64-bit key
+        locate_topk_kernel<<<dim3((unsigned)std::min<size_t>(((size_t)max_n + 2047) / 2048, 512), m), 256, 0, st>>>(tb, keys + b0 * LOC_TOP, 0);
+        SSW_HIP_CHECK(hipGetLastError());
+    }
+    std::vector<uint64_t> hk(nr * LOC_TOP);
+    SSW_HIP_CHECK(hipMemcpyAsync(hk.data(), keys, hk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    untimed_work(ctx);
+    SSW_HIP_CHECK(hipStreamSynchronize(st));
+    // on the host: the 8 rungs with the smallest D / n, then the windowed searches around them
+    std::vector<ssw_placement> rp;
+    std::vector<LocWindow> win;
+    std::vector<const void*> rsus;
+    std::vector<size_t> owner;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t wmin = ranges[2 * i], wmax = ranges[2 * i + 1];
+        std::vector<size_t> order;
+        for (size_t j = first[i]; j < first[i + 1]; ++j) order.push_back(j);
+        auto D = [&](size_t j) { return hk[j * LOC_TOP] >> 32; };
+        auto N = [&](size_t j) { return (uint64_t)rungs[j].tw * rungs[j].th; };
+        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return D(a) * N(b) < D(b) * N(a); });
+        if (order.size() > LAD_KEEP) order.resize(LAD_KEEP);
+        struct Job { uint32_t pw, ph; LocWindow w; };
+        std::vector<Job> jobs;
+        for (size_t j : order) {
+            const Rung& r = rungs[j];
+            const uint32_t idx = (uint32_t)hk[j * LOC_TOP];
+            const int64_t xj = 4 * (int64_t)(idx % r.nx), yj = 4 * (int64_t)(idx / r.nx);
+            for (int64_t pw = std::max<int64_t>(wmin, (int64_t)r.pw - LAD_NEAR_W); pw <= std::min<int64_t>(wmax, (int64_t)r.pw + LAD_NEAR_W); ++pw) {
+                const uint32_t ph = ladder_height((uint64_t)pw, pl[i].w, pl[i].h);
+                if ((uint64_t)pw > w || ph > h) continue;
+                const int64_t x0 = std::max<int64_t>(0, xj - LAD_NEAR_XY), x1 = std::min<int64_t>((int64_t)w - pw, xj + LAD_NEAR_XY);
+                const int64_t y0 = std::max<int64_t>(0, yj - LAD_NEAR_XY), y1 = std::min<int64_t>((int64_t)h - ph, yj + LAD_NEAR_XY);
+                if (x0 > x1 || y0 > y1) continue;
+                const Job job{(uint32_t)pw, ph, LocWindow{(uint32_t)x0, (uint32_t)x1, (uint32_t)y0, (uint32_t)y1, false}};
+                bool seen = false;
+                for (const Job& q : jobs) seen |= q.pw == job.pw && q.w.x0 == job.w.x0 && q.w.x1 == job.w.x1 && q.w.y0 == job.w.y0 && q.w.y1 == job.w.y1;
+                if (!seen) jobs.push_back(job);
+            }
+        }
+        std::stable_sort(jobs.begin(), jobs.end(), [](const Job& a, const Job& b) { return a.pw < b.pw; });       // a width's searches side by side: one resize
+        for (size_t q = 0; q < jobs.size(); ++q) {
+            ssw_placement p = pl[i];
+            p.x = p.y = 0; p.pw = jobs[q].pw; p.ph = jobs[q].ph;
+            LocWindow lw = jobs[q].w;
+            lw.share = q > 0 && jobs[q - 1].pw == jobs[q].pw;
+            rp.push_back(p); win.push_back(lw); rsus.push_back(dev_suspects[i]); owner.push_back(i);
+        }
+    }
+    {   // the resize runs on the colour channels alone
+        std::vector<ssw_placement> rgb(rp);
+        for (ssw_placement& p : rgb) p.channels = 3;
+        SSW_TRY(restore_prepare(ctx, rgb));
+    }
+    std::vector<uint64_t> res(2 * rp.size());
+    SSW_TRY(locate_impl(ctx, dev_base, w, h, rsus.data(), rp, res.data(), &win));
+    std::vector<char> have(n, 0);
+    for (size_t q = 0; q < rp.size(); ++q) {
+        ScaledAnswer a{rp[q].pw, rp[q].ph, (uint32_t)res[2 * q + 1], (uint32_t)(res[2 * q + 1] >> 32), res[2 * q]};
+        ScaledAnswer& b = out[owner[q]];
+        bool better = !have[owner[q]];
+        if (!better) {                                                  // smallest SAD / (pw ph), then pw, y, x; 255 * 2^26 * 2^26 fits 64 bits
+            const uint64_t l = a.sad * ((uint64_t)b.pw * b.ph), r = b.sad * ((uint64_t)a.pw * a.ph);
+            better = l != r ? l < r : a.pw != b.pw ? a.pw < b.pw : a.y != b.y ? a.y < b.y : a.x < b.x;
+        }
+        if (better) { b = a; have[owner[q]] = 1; }
+    }
+    return SSW_OK;
+}
+
+// T_j of one rung alone (ssw_locate_rung_boxes): what locate_rung_kernel stores, compact on the host
+int rung_boxes_impl(ssw_ctx* ctx, const void* dev_suspect, const ssw_placement& p, uint8_t* host_t) {
+    LadderTaps taps;
+    std::vector<Rung> rungs(1);
+    SSW_TRY(make_rung(taps, p, 0u, p.pw, p.ph, p.pw, p.ph, &rungs[0]));
+    const Rung& r = rungs[0];
+    SSW_TRY(grow(ctx->locate[2], r.bytes_t + 16));
+    uint8_t* t_ptr[1] = {(uint8_t*)ctx->locate[2].p};
+    const uint32_t* dev_taps = nullptr;
+    SSW_TRY(upload_taps(ctx, taps, &dev_taps));
+    SSW_TRY(set_rung_lds_attribute());
+    SSW_TRY(enqueue_rungs(ctx, rungs, 0, 1, &dev_suspect, t_ptr, dev_taps));
+    std::vector<uint8_t> t((size_t)r.dev.tpitch * r.th);
+    SSW_HIP_CHECK(hipMemcpyAsync(t.data(), t_ptr[0], t.size(), hipMemcpyDeviceToHost, ctx->stream));
+    untimed_work(ctx);
+    SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (uint32_t k = 0; k < r.th; ++k) std::memcpy(host_t + (size_t)k * r.tw, t.data() + (size_t)k * r.dev.tpitch, r.tw);
+    return SSW_OK;
+}
+
 }  // namespace host
 }  // namespace ssw
 
@@ -480,4 +952,39 @@ extern "C" int ssw_locate_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t
         placements[i].y = (uint32_t)(res[2 * i + 1] >> 32);
     }
     return SSW_OK;
+}
+
+extern "C" int ssw_locate_scaled_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, size_t h, const void* const* dev_suspects,
+                                      ssw_placement* placements, const ssw_scale_range* ranges, size_t n, uint64_t* host_sad) {
+    using namespace ssw::host;
+    if (!ctx) return SSW_ERR_BAD_ARG;
+    if (n == 0) return SSW_OK;
+    if (!dev_base_rgb || !dev_suspects || !placements || !ranges || !host_sad) return SSW_ERR_BAD_ARG;
+    std::vector<ssw_placement> in(placements, placements + n), pl;
+    for (ssw_placement& p : in) p.x = p.y = p.pw = p.ph = 0;          // outputs: what the caller left there is not read
+    if (w == 0 || h == 0 || w > 0xFFFFFFFFull || h > 0xFFFFFFFFull) return SSW_ERR_BAD_ARG;
+    for (const ssw_placement& p : in)
+        if ((p.channels != 3 && p.channels != 4) || p.w == 0 || p.h == 0 || (uint64_t)p.w * p.channels > 0xFFFFFFFFull) return SSW_ERR_BAD_ARG;
+    for (size_t i = 0; i < n; ++i) if (!dev_suspects[i]) return SSW_ERR_BAD_ARG;
+    CtxGuard g(ctx);
+    std::vector<ScaledAnswer> ans(n);
+    std::vector<uint32_t> r(2 * n);
+    for (size_t i = 0; i < n; ++i) { r[2 * i] = ranges[i].wmin; r[2 * i + 1] = ranges[i].wmax; }
+    SSW_TRY(locate_scaled_impl(ctx, dev_base_rgb, w, h, dev_suspects, in, r.data(), ans.data()));
+    for (size_t i = 0; i < n; ++i) {
+        placements[i].pw = ans[i].pw; placements[i].ph = ans[i].ph;
+        placements[i].x = ans[i].x; placements[i].y = ans[i].y;
+        host_sad[i] = ans[i].sad;
+    }
+    return SSW_OK;
+}
+
+extern "C" int ssw_locate_rung_boxes(ssw_ctx* ctx, const void* dev_suspect, size_t sw, size_t sh, size_t channels, size_t pw, size_t ph,
+                                     uint8_t* host_boxes) {
+    using namespace ssw::host;
+    if (!ctx || !dev_suspect || !host_boxes) return SSW_ERR_BAD_ARG;
+    if ((channels != 3 && channels != 4) || sw == 0 || sh == 0 || pw < 8 || ph < 8 || sw * channels > 0xFFFFFFFFull || sh > 0xFFFFFFFFull ||
+        pw > 0xFFFFFFFFull || ph > 0xFFFFFFFFull) return SSW_ERR_BAD_ARG;
+    CtxGuard g(ctx);
+    return rung_boxes_impl(ctx, dev_suspect, ssw_placement{(uint32_t)sw, (uint32_t)sh, (uint32_t)channels, 0u, 0u, (uint32_t)pw, (uint32_t)ph}, host_boxes);
 }

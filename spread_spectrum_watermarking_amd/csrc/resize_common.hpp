@@ -86,16 +86,30 @@ __host__ __device__ inline unsigned resize_lds_in_offset(const ResizeTile& tl, u
     return ((tl.oyb * tl.pitch + tl.oxb * hmax + tl.oyb * vmax + 2 * tl.oyb + 2 * tl.oxb) * 4 + 15) & ~15u;
 }
 
+// reach in input samples of 1, 2, 4 .. 128 consecutive outputs, the maximum over all aligned groups (DeviceTaps::span)
+inline void resize_spans(const ResizeTaps& t, size_t out_len, uint32_t (&span)[8]) {
+    for (int e = 0; e < 8; ++e) {
+        const size_t g = (size_t)1 << e;
+        uint32_t m = 0;
+        for (size_t o = 0; o < out_len; o += g) {
+            const size_t last = (o + g < out_len ? o + g : out_len) - 1;
+            m = m > t.left[last] + t.count[last] - t.left[o] ? m : t.left[last] + t.count[last] - t.left[o];
+        }
+        span[e] = m;
+    }
+}
+
 // tile shape: the cheapest one (input bytes loaded + vertical taps per output pixel) whose LDS footprint lets two
 // blocks share a CU; spans = reach (in input samples) of 1, 2, 4, ... 128 consecutive outputs (DeviceTaps::span);
-// ch interleaved input channels, 3 output bytes per pixel
+// ch interleaved input channels, 3 output bytes per pixel.  ey_min / ex_min: the smallest tile (log2) the caller can use --
+// locate_rung_kernel wants whole 8 x 8 boxes in a tile
 inline bool pick_resize_tile(const DeviceTaps& vt, const DeviceTaps& ht, size_t nw, size_t nh, unsigned ch, ResizeTile* out,
-                             size_t* lds_bytes) {
+                             size_t* lds_bytes, int ey_min = 0, int ex_min = 2) {
     double best = 1e300;
     bool found = false;
     const double vtaps = (double)(vt.span[0] ? vt.span[0] : 1);
-    for (int ey = 0; ey < 8; ++ey)
-        for (int ex = 2; ex < 8; ++ex) {                                // OXB >= 4 (a multiple of 4)
+    for (int ey = ey_min; ey < 8; ++ey)
+        for (int ex = ex_min; ex < 8; ++ex) {                           // OXB >= 4 (a multiple of 4)
             const unsigned oyb = 1u << ey, oxb = 1u << ex;
             if (oyb > 2 * nh || oxb > 2 * nw) continue;
             const unsigned rows = vt.span[ey], px = ht.span[ex];

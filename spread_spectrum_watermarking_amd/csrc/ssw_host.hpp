@@ -183,8 +183,11 @@ int restore_prepare(ssw_ctx* ctx, const std::vector<ssw_placement>& pl);
 int restore_enqueue(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const RestoreJob* jobs, size_t n);
 // locate.hip (include/ssw.h: ssw_locate_rgb8): pl normalised with x = y = 0 and prepared; host_res [n][2]: SAD, (y << 32) | x.
 // Synchronises the context's stream.
+// win (the refinement of ssw_locate_scaled_rgb8; null: every position): per entry the candidate positions x0..x1, y0..y1
+// (inclusive, valid ones) it searches, and whether it is the same suspect at the same size as the entry before it
+struct LocWindow { uint32_t x0, x1, y0, y1; bool share; };
 int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
-                const std::vector<ssw_placement>& pl, uint64_t* host_res);
+                const std::vector<ssw_placement>& pl, uint64_t* host_res, const std::vector<LocWindow>* win = nullptr);
 // ssw_lib.hip: the cached CatmullRom tap table (in_len -> out_len) of the context
 int get_taps(ssw_ctx* ctx, size_t in_len, size_t out_len, DeviceTaps* out);
 

@@ -362,7 +362,8 @@ struct ssw_ctx {
     // ssw_fingerprint_trace: what every chunk on both lanes reads -- base plane | base index list | prune tables (flag, pos,
     // rows) | gathered bases, launch order | gathered bases, fragment order | similarity matrix when the caller wants none
     Buf trace[6];
-    Buf locate[4];                // locate.hip: the original's luma plane | its 16 phase planes | one group of suspects (R, luma, S_f, D) | keys, sums, results
+    Buf locate[6];                // locate.hip: the original's luma plane | its 16 phase planes | one group of suspects (R, luma, S_f, D) | keys, sums, results
+                                  // | (scale ladder) the original's 8 x 8 box planes | the ladder's tap tables
     Buf fingerprint[6];           // fingerprint.hip: line plan (u32) | T64 + gathered basis | Yr64 | mark deltas | dT of a group | handle output
     std::map<std::pair<size_t, size_t>, ssw::DeviceTaps> taps;   // (in_len, out_len) -> filter taps
 

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <new>
 
+#include "resize_common.hpp"
 #include "ssw_host.hpp"
 
 namespace ssw {
@@ -704,15 +705,7 @@ int get_taps(ssw_ctx* ctx, size_t in_len, size_t out_len, DeviceTaps* out) {
     build_resize_taps(in_len, out_len, host);
     DeviceTaps d;
     d.max_taps = host.max_taps;
-    for (int e = 0; e < 8; ++e) {                       // reach of 2^e consecutive outputs, maximum over all aligned groups
-        const size_t g = (size_t)1 << e;
-        uint32_t m = 0;
-        for (size_t o = 0; o < out_len; o += g) {
-            const size_t last = std::min(o + g, out_len) - 1;
-            m = std::max(m, host.left[last] + host.count[last] - host.left[o]);
-        }
-        d.span[e] = m;
-    }
+    resize_spans(host, out_len, d.span);
     d.quad_uniform = out_len % 4 == 0;
     for (size_t o = 0; o < out_len && d.quad_uniform; ++o)
         d.quad_uniform = host.count[o] <= 5 && host.left[o] == host.left[o & ~(size_t)3] && host.count[o] == host.count[o & ~(size_t)3];
