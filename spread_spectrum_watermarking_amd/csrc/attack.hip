@@ -262,49 +262,28 @@ __global__ __launch_bounds__(256) void resize_horizontal_kernel(const float* __r
 // summation order are those of the two-pass kernels: bit-identical results.
 // Needs 4-byte aligned rows (w * 3 % 4 == 0, nw * 3 % 4 == 0, OXB % 4 == 0).
 // ---------------------------------------------------------------------------------------------
-// ResizeTile, resize_to_u8, the vertical pass of a block and the per-pixel horizontal sum: resize_common.hpp (shared with
-// restore.hip, which must give the same bits)
+// ResizeTile, the LDS layout, the tile's reach, the vertical pass, the per-pixel horizontal sum and resize_to_u8:
+// resize_common.hpp (shared with restore.hip and locate.hip, which must give the same bits).  This kernel keeps its own
+// loader: rows here are 4-byte aligned, so it loads 16-byte pieces and keeps six of them in flight.
 
 // HMODE (horizontal pass): 0 = one lane per (output pixel, channel) -- down-scaling along x, few outputs, long taps;
 // 1 = one thread per aligned quad of output pixels that share their taps' positions (left, count <= 5: integer
 // up-scaling) -- the <= 15 strip values are loaded once and feed 12 output bytes; 2 = one thread per output pixel.
 template <int HMODE>
 __global__ __launch_bounds__(256) void resize_fused_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
-                                                           unsigned w, unsigned h, unsigned nw, unsigned nh,
-                                                           const uint32_t* __restrict__ vleft, const uint32_t* __restrict__ vcount,
-                                                           const float* __restrict__ vweights, unsigned vmax,
-                                                           const uint32_t* __restrict__ hleft, const uint32_t* __restrict__ hcount,
-                                                           const float* __restrict__ hweights, unsigned hmax, ResizeTile tl) {
+                                                           unsigned w, unsigned h, unsigned nw, unsigned nh, ResizeTapPtrs taps,
+                                                           ResizeTile tl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // layout: s_v f32 [oyb][pitch] | s_wh f32 [hmax][oxb] (tap-major) | s_wv f32 [oyb][vmax] | meta u32 [2 oyb + 2 oxb] |
-    //         s_in u8 [in_rows][pitch];  pitch is a multiple of 16: 16-byte LDS accesses throughout
-    float* s_v = reinterpret_cast<float*>(smem);
-    float* s_wh = s_v + (size_t)tl.oyb * tl.pitch;
-    float* s_wv = s_wh + (size_t)tl.oxb * hmax;
-    uint32_t* s_lv = reinterpret_cast<uint32_t*>(s_wv + (size_t)tl.oyb * vmax);
-    uint32_t* s_cv = s_lv + tl.oyb;
-    uint32_t* s_lh = s_cv + tl.oyb;
-    uint32_t* s_ch = s_lh + tl.oxb;
-    // (offset arithmetic on `smem` itself: a pointer rebuilt from an integer loses its LDS address space and every
-    //  access through it becomes a flat load)
-    const unsigned in_off = ((tl.oyb * tl.pitch + tl.oxb * hmax + tl.oyb * vmax + 2 * tl.oyb + 2 * tl.oxb) * 4 + 15) & ~15u;
-    unsigned char* s_in = smem + in_off;
-    unsigned char* s_out = s_in;                       // reused after the vertical pass: [oyb][oxb * 3]
+    const ResizeLds l = resize_lds_carve(smem, tl, taps.hmax, taps.vmax);
+    unsigned char* s_out = l.in;                       // reused after the vertical pass: [oyb][oxb * 3]
+    const unsigned vmax = taps.vmax, hmax = taps.hmax;
 
     const unsigned tid = threadIdx.x, lane = tid & 63;
     const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned tx = blockIdx.x % tl.tiles_x, ty = blockIdx.x / tl.tiles_x, f = blockIdx.y;
-    const unsigned oy0 = ty * tl.oyb, ox0 = tx * tl.oxb;
-    const unsigned noy = nh - oy0 < tl.oyb ? nh - oy0 : tl.oyb;
-    const unsigned nox = nw - ox0 < tl.oxb ? nw - ox0 : tl.oxb;
-
-    // The tile's reach: left / right bounds grow with the output index, so it is first left .. last right
-    // (block-uniform scalar loads; everything below is addressed from them).
-    const unsigned r0 = vleft[oy0], r1 = vleft[oy0 + noy - 1] + vcount[oy0 + noy - 1];
-    const unsigned b0 = hleft[ox0] * 3, b1 = (hleft[ox0 + nox - 1] + hcount[ox0 + nox - 1]) * 3;
-    const unsigned a0 = b0 & ~3u;                                   // rows are 4-byte aligned: aligned word loads
-    const unsigned words = (b1 - a0 + 3) / 4;
-    const unsigned nrows = r1 - r0;
+    const unsigned f = blockIdx.y;
+    const ResizeReach rc = resize_tile_reach<3>(taps, tl, blockIdx.x, nw, nh);
+    const unsigned oy0 = rc.oy0, ox0 = rc.ox0, noy = rc.noy, nox = rc.nox;
+    const unsigned r0 = rc.r0, nrows = rc.nrows, a0 = rc.a0, words = rc.words;
     {   // 1. tap tables and input tile -> LDS.  A block lives for a handful of memory latencies, so every global
         //    load that does not depend on another is issued before the first LDS write: the tables (<= 4 + 4 + 4
         //    values per thread) and the first six 16-byte pieces of the tile together, then the rest of the tile.
@@ -313,11 +292,11 @@ __global__ __launch_bounds__(256) void resize_fused_kernel(const uint8_t* __rest
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const unsigned i = tid + 256 * u;
-            hw[u] = i < nox * hmax ? hweights[(size_t)ox0 * hmax + i] : 0.0f;
-            vw[u] = i < noy * vmax ? vweights[(size_t)oy0 * vmax + i] : 0.0f;
+            hw[u] = i < nox * hmax ? taps.hweights[(size_t)ox0 * hmax + i] : 0.0f;
+            vw[u] = i < noy * vmax ? taps.vweights[(size_t)oy0 * vmax + i] : 0.0f;
         }
-        if (tid < noy) { meta[0] = vleft[oy0 + tid]; meta[1] = vcount[oy0 + tid]; }
-        if (tid < nox) { meta[2] = hleft[ox0 + tid]; meta[3] = hcount[ox0 + tid]; }
+        if (tid < noy) { meta[0] = taps.vleft[oy0 + tid]; meta[1] = taps.vcount[oy0 + tid]; }
+        if (tid < nox) { meta[2] = taps.hleft[ox0 + tid]; meta[3] = taps.hcount[ox0 + tid]; }
         const uint8_t* src = in + ((size_t)f * h + r0) * w * 3 + a0;
         const size_t row_bytes = (size_t)w * 3;
         const unsigned chunks = (words + 3) / 4;
@@ -347,27 +326,21 @@ __global__ __launch_bounds__(256) void resize_fused_kernel(const uint8_t* __rest
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const unsigned i = tid + 256 * u;
-                    if (i < nox * hmax) { const unsigned x = i / hmax, tp = i - x * hmax; s_wh[tp * tl.oxb + x] = hw[u]; }   // tap-major
-                    if (i < noy * vmax) s_wv[i] = vw[u];
+                    if (i < nox * hmax) { const unsigned x = i / hmax, tp = i - x * hmax; l.wh[tp * tl.oxb + x] = hw[u]; }   // tap-major
+                    if (i < noy * vmax) l.wv[i] = vw[u];
                 }
-                if (tid < noy) { s_lv[tid] = meta[0]; s_cv[tid] = meta[1]; }
-                if (tid < nox) { s_lh[tid] = meta[2]; s_ch[tid] = meta[3]; }
+                if (tid < noy) { l.lv[tid] = meta[0]; l.cv[tid] = meta[1]; }
+                if (tid < nox) { l.lh[tid] = meta[2]; l.ch[tid] = meta[3]; }
             }
 #pragma unroll
             for (int u = 0; u < NB; ++u)
-                if (dst[u] != 0xFFFFFFFFu) *reinterpret_cast<u32x4r*>(s_in + dst[u]) = v[u];
+                if (dst[u] != 0xFFFFFFFFu) *reinterpret_cast<u32x4r*>(l.in + dst[u]) = v[u];
         }
     }
     __syncthreads();
     // 2. vertical pass (vertical_sample of the crate): t = sum_i (float)in[left + i][e] * w[i], i ascending, mul and
-    //    add rounded separately.  One thread = 16 (or, when that leaves half the block idle, 8) consecutive bytes of
-    //    one output row: that many independent sums per LDS read.
-    {
-        // whole LDS rows, slack included: every strip element the horizontal pass may touch is then a finite sum
-        const unsigned chunks16 = tl.pitch / 16;
-        if (noy * chunks16 >= 192) resize_vertical_pieces<4>(s_in, s_v, s_wv, s_lv, s_cv, r0, noy, chunks16, vmax, tl.pitch, tid);
-        else                       resize_vertical_pieces<2>(s_in, s_v, s_wv, s_lv, s_cv, r0, noy, tl.pitch / 8, vmax, tl.pitch, tid);
-    }
+    //    add rounded separately
+    resize_vertical_pass(l, tl, rc, vmax, tid);
     __syncthreads();
     // 3. horizontal pass (horizontal_sample): t = sum_i strip[left + i][c] * w[i]; clamp, round; staged in LDS
     const unsigned out_pitch = tl.oxb * 3;
@@ -375,9 +348,9 @@ __global__ __launch_bounds__(256) void resize_fused_kernel(const uint8_t* __rest
         for (unsigned j = wave; j < noy; j += 4)
             for (unsigned e = lane; e < nox * 3; e += 64) {
                 const unsigned x = e / 3, c = e - 3 * x;
-                const unsigned n = s_ch[x];
-                const float* src = s_v + j * tl.pitch + (s_lh[x] * 3 - a0) + c;
-                const float* wh = s_wh + x;
+                const unsigned n = l.ch[x];
+                const float* src = l.v + j * tl.pitch + (l.lh[x] * 3 - a0) + c;
+                const float* wh = l.wh + x;
                 float t = 0.0f;
 #pragma unroll 4
                 for (unsigned i = 0; i < n; ++i) t += src[3 * i] * wh[i * tl.oxb];
@@ -389,7 +362,7 @@ __global__ __launch_bounds__(256) void resize_fused_kernel(const uint8_t* __rest
             const unsigned j = it >> nq_log2, q = it & ((1u << nq_log2) - 1);
             if (q >= nq) continue;
             const unsigned x0 = 4 * q;
-            const float* src = s_v + j * tl.pitch + (s_lh[x0] * 3 - a0);
+            const float* src = l.v + j * tl.pitch + (l.lh[x0] * 3 - a0);
             // Five taps are read whatever n is: the tap tables are zero-padded beyond n (hmax >= 5 rows exist), and the
             // strip beyond the reach holds finite values (sums of bytes times weights), so 0 * value adds nothing.
             float p[5][3];
@@ -399,7 +372,7 @@ __global__ __launch_bounds__(256) void resize_fused_kernel(const uint8_t* __rest
                 for (int c = 0; c < 3; ++c) p[i][c] = src[3 * i + c];
             f32x4 wq[5];                                           // tap i of the quad's four outputs: one 16-byte read
 #pragma unroll
-            for (int i = 0; i < 5; ++i) wq[i] = *reinterpret_cast<const f32x4*>(s_wh + i * tl.oxb + x0);
+            for (int i = 0; i < 5; ++i) wq[i] = *reinterpret_cast<const f32x4*>(l.wh + i * tl.oxb + x0);
             uint32_t by[12];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -424,9 +397,9 @@ __global__ __launch_bounds__(256) void resize_fused_kernel(const uint8_t* __rest
         for (unsigned it = tid; it < (noy << nx_log2); it += 256) {
             const unsigned j = it >> nx_log2, x = it & ((1u << nx_log2) - 1);
             if (x >= nox) continue;
-            const unsigned n = s_ch[x];
-            const float* src = s_v + j * tl.pitch + (s_lh[x] * 3 - a0);
-            const float* wh = s_wh + x;
+            const unsigned n = l.ch[x];
+            const float* src = l.v + j * tl.pitch + (l.lh[x] * 3 - a0);
+            const float* wh = l.wh + x;
             float t[3];
             resize_horizontal_pixel<3>(src, wh, n, tl.oxb, t);
             unsigned char* o = s_out + j * out_pitch + x * 3;
@@ -478,23 +451,14 @@ int launch_resize_rgb8(hipStream_t st, const uint8_t* in, size_t n_frames, size_
     size_t lds = 0;
     if (resize_can_fuse(in, n_frames, w, h, nw, nh, vt, ht, out, &tl, &lds)) {
         const dim3 grid(tl.tiles_x * tl.tiles_y, (unsigned)n_frames);
-        {   // tiles above 64 KB of dynamic LDS need the per-device function attribute: set it once per device
-            static std::atomic<bool> attr_set[64];           // two host threads, two contexts: no plain bools
-            int dev = 0;
-            SSW_HIP_CHECK(hipGetDevice(&dev));
-            if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-                SSW_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_fused_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-                SSW_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_fused_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-                SSW_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_fused_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-                if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-            }
-        }
-#define SSW_RESIZE_FUSED(MODE) resize_fused_kernel<MODE><<<grid, 256, lds, st>>>(in, out, (unsigned)w, (unsigned)h, (unsigned)nw, (unsigned)nh, \
-        vt.left, vt.count, vt.weights, vt.max_taps, ht.left, ht.count, ht.weights, ht.max_taps, tl)
-        if (nw < w) SSW_RESIZE_FUSED(0);
-        else if (ht.quad_uniform) SSW_RESIZE_FUSED(1);
-        else SSW_RESIZE_FUSED(2);
-#undef SSW_RESIZE_FUSED
+        static std::atomic<bool> lds_raised[64];
+        SSW_TRY(resize_raise_lds_limit({reinterpret_cast<const void*>(resize_fused_kernel<0>), reinterpret_cast<const void*>(resize_fused_kernel<1>),
+                                        reinterpret_cast<const void*>(resize_fused_kernel<2>)}, lds_raised));
+        const ResizeTapPtrs taps = resize_tap_ptrs(vt, ht);
+        const unsigned uw = (unsigned)w, uh = (unsigned)h, unw = (unsigned)nw, unh = (unsigned)nh;
+        if (nw < w)               resize_fused_kernel<0><<<grid, 256, lds, st>>>(in, out, uw, uh, unw, unh, taps, tl);
+        else if (ht.quad_uniform) resize_fused_kernel<1><<<grid, 256, lds, st>>>(in, out, uw, uh, unw, unh, taps, tl);
+        else                      resize_fused_kernel<2><<<grid, 256, lds, st>>>(in, out, uw, uh, unw, unh, taps, tl);
         SSW_HIP_CHECK(hipGetLastError());
         return SSW_OK;
     }

@@ -21,8 +21,9 @@
 //
 // The scale ladder (ssw_locate_scaled_rgb8) for cut-outs whose size is not known either adds
 //   locate_box8_kernel          8 x 8 box means of the original at every fourth position, as 2 x 2 phase planes
-//   locate_rung_kernel          THE LADDER'S HOT PATH: one (suspect, rung) -- the fused CatmullRom tile of restore_resize_kernel
-//                               whose epilogue is clamp + round, luma and the 8 x 8 box sum; only the box means T_j are stored
+//   locate_rung_kernel          THE LADDER'S HOT PATH: one (suspect, rung) -- the fused CatmullRom tile of resize_common.hpp
+//                               (resize_tile_front) whose epilogue is the horizontal pass, clamp + round, luma and the 8 x 8 box
+//                               sum; only the box means T_j are stored
 // and reuses locate_coarse_kernel (f = 2) and round 0 of locate_topk_kernel per rung; the 8 best rungs are refined by windowed
 // searches of the kernels above (a base offset in their descriptors).  The rungs are chosen on the host.
 #include <algorithm>
@@ -290,15 +291,14 @@ __global__ __launch_bounds__(64) void locate_final_kernel(FineBatch b, unsigned 
 
 // ---- the scale ladder (ssw_locate_scaled_rgb8) --------------------------------------------------------------------------------
 // One (suspect, rung) of a launch: the suspect resized to pw x ph, of which only the 8 x 8 box means T [th][tw] are stored.
-// Tap tables are offsets (32-bit words) into the one buffer of the call.
 struct RungDev {
     const uint8_t* src;          // the suspect [sh][sw][C]
     uint8_t* T;                  // [th][tpitch]
-    uint32_t vleft, vcount, vweights, hleft, hcount, hweights;
-    uint32_t sw, vmax, hmax;
+    ResizeTapPtrs taps;          // tables in the one buffer of the call
+    ResizeTile tl;               // oyb, oxb multiples of 8: no box straddles two blocks
+    uint32_t sw;
     uint32_t ow, oh;             // 8 tw, 8 th: the output pixels that lie in a box
     uint32_t tpitch;
-    uint32_t oyb, oxb, pitch, tiles_x, oxb_log2;      // ResizeTile; oyb, oxb multiples of 8: no box straddles two blocks
     uint32_t tile_begin;
 };
 struct RungBatch { RungDev it[LOC_BATCH]; };
@@ -329,80 +329,29 @@ __global__ __launch_bounds__(256) void locate_box8_kernel(const uint8_t* __restr
 }
 
 // THE HOT PATH of the ladder.  One block = one tile of oyb x oxb pixels of one rung: the fused CatmullRom tile of
-// restore_resize_kernel (tile -> LDS, vertical pass into an f32 strip, horizontal pass; every helper from resize_common.hpp),
-// with clamp + round, luma and the 8 x 8 box sum as its epilogue.  R_j never reaches HBM: only T_j is stored.  C = 4: alpha
-// is read past and ignored.  grid: (tiles of all rungs of the launch); dynamic LDS: the largest tile's.
+// resize_common.hpp (tile -> LDS, vertical pass into an f32 strip), then the horizontal pass with clamp + round, luma and the
+// 8 x 8 box sum as its epilogue.  R_j never reaches HBM: only T_j is stored.  C = 4: alpha is read past and ignored.
+// grid: (tiles of all rungs of the launch); dynamic LDS: the largest tile's.
 template <int C>
-__global__ __launch_bounds__(256) void locate_rung_kernel(RungBatch b, unsigned n, const uint32_t* __restrict__ taps) {
+__global__ __launch_bounds__(256) void locate_rung_kernel(RungBatch b, unsigned n) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned s = 0;
     while (s + 1 < n && blockIdx.x >= b.it[s + 1].tile_begin) ++s;
     const RungDev& d = b.it[s];
-    const ResizeTile tl{d.oyb, d.oxb, d.pitch, 0u, d.tiles_x, 0u, d.oxb_log2};
-    const unsigned vmax = d.vmax, hmax = d.hmax;
-    const uint32_t* __restrict__ vleft = taps + d.vleft;
-    const uint32_t* __restrict__ vcount = taps + d.vcount;
-    const float* __restrict__ vweights = reinterpret_cast<const float*>(taps + d.vweights);
-    const uint32_t* __restrict__ hleft = taps + d.hleft;
-    const uint32_t* __restrict__ hcount = taps + d.hcount;
-    const float* __restrict__ hweights = reinterpret_cast<const float*>(taps + d.hweights);
-    float* s_v = reinterpret_cast<float*>(smem);
-    float* s_wh = s_v + (size_t)tl.oyb * tl.pitch;
-    float* s_wv = s_wh + (size_t)tl.oxb * hmax;
-    uint32_t* s_lv = reinterpret_cast<uint32_t*>(s_wv + (size_t)tl.oyb * vmax);
-    uint32_t* s_cv = s_lv + tl.oyb;
-    uint32_t* s_lh = s_cv + tl.oyb;
-    uint32_t* s_ch = s_lh + tl.oxb;
-    unsigned char* s_in = smem + resize_lds_in_offset(tl, hmax, vmax);
-    unsigned char* s_lum = s_in;                       // reused after the vertical pass: [oyb][oxb] lumas
+    const ResizeTile& tl = d.tl;
+    const ResizeLds l = resize_lds_carve(smem, tl, d.taps.hmax, d.taps.vmax);
+    unsigned char* s_lum = l.in;                       // reused after the vertical pass: [oyb][oxb] lumas
 
     const unsigned tid = threadIdx.x;
-    const unsigned tile = blockIdx.x - d.tile_begin;
-    const unsigned tx = tile % tl.tiles_x, ty = tile / tl.tiles_x;
-    const unsigned oy0 = ty * tl.oyb, ox0 = tx * tl.oxb;
-    const unsigned noy = d.oh - oy0 < tl.oyb ? d.oh - oy0 : tl.oyb;      // multiples of 8
-    const unsigned nox = d.ow - ox0 < tl.oxb ? d.ow - ox0 : tl.oxb;
-
-    const unsigned r0 = vleft[oy0], r1 = vleft[oy0 + noy - 1] + vcount[oy0 + noy - 1];
-    const unsigned b0 = hleft[ox0] * C, b1 = (hleft[ox0 + nox - 1] + hcount[ox0 + nox - 1]) * C;
-    const unsigned a0 = b0 & ~3u;
-    const unsigned words = (b1 - a0 + 3) / 4;
-    const unsigned nrows = r1 - r0;
-    const unsigned row_bytes = d.sw * C;
-    {   // 1. tap tables and input tile -> LDS
-        for (unsigned i = tid; i < nox * hmax; i += 256) { const unsigned x = i / hmax, tp = i - x * hmax; s_wh[tp * tl.oxb + x] = hweights[(size_t)ox0 * hmax + i]; }   // tap-major
-        for (unsigned i = tid; i < noy * vmax; i += 256) s_wv[i] = vweights[(size_t)oy0 * vmax + i];
-        if (tid < noy) { s_lv[tid] = vleft[oy0 + tid]; s_cv[tid] = vcount[oy0 + tid]; }
-        if (tid < nox) { s_lh[tid] = hleft[ox0 + tid]; s_ch[tid] = hcount[ox0 + tid]; }
-        const uint8_t* __restrict__ src = d.src + (size_t)r0 * row_bytes + a0;
-        const unsigned avail = row_bytes - a0;                          // bytes from a0 to the end of the suspect's row
-        const bool rows_aligned = (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (row_bytes & 3) == 0;
-        for (unsigned it = tid; it < nrows * words; it += 256) {
-            const unsigned r = it / words, wd = it - r * words;
-            const uint8_t* p = src + (size_t)r * row_bytes + 4 * wd;
-            uint32_t v = 0;
-            if (rows_aligned && 4 * wd + 4 <= avail) v = *reinterpret_cast<const uint32_t*>(p);
-            else {                                                      // stay inside the row: never past the suspect's last byte
-#pragma unroll
-                for (unsigned e = 0; e < 4; ++e) if (4 * wd + e < avail) v |= (uint32_t)p[e] << (8 * e);
-            }
-            *reinterpret_cast<uint32_t*>(s_in + r * tl.pitch + 4 * wd) = v;
-        }
-    }
-    __syncthreads();
-    // 2. vertical pass: whole LDS rows, slack included (bytes the tile did not load give finite sums nobody reads)
-    {
-        const unsigned chunks16 = tl.pitch / 16;
-        if (noy * chunks16 >= 192) resize_vertical_pieces<4>(s_in, s_v, s_wv, s_lv, s_cv, r0, noy, chunks16, vmax, tl.pitch, tid);
-        else                       resize_vertical_pieces<2>(s_in, s_v, s_wv, s_lv, s_cv, r0, noy, tl.pitch / 8, vmax, tl.pitch, tid);
-    }
-    __syncthreads();
+    // 1. tap tables and input tile -> LDS, 2. vertical pass; noy, nox: multiples of 8
+    const ResizeReach rc = resize_tile_front<C>(l, d.taps, tl, blockIdx.x - d.tile_begin, d.ow, d.oh, d.src, d.sw);
+    const unsigned oy0 = rc.oy0, ox0 = rc.ox0, noy = rc.noy, nox = rc.nox, a0 = rc.a0;
     // 3. horizontal pass, clamp + round of the colour channels, luma
     for (unsigned it = tid; it < (noy << tl.oxb_log2); it += 256) {
         const unsigned j = it >> tl.oxb_log2, x = it & ((1u << tl.oxb_log2) - 1);
         if (x >= nox) continue;
         float t[C];
-        resize_horizontal_pixel<C>(s_v + j * tl.pitch + (s_lh[x] * C - a0), s_wh + x, s_ch[x], tl.oxb, t);
+        resize_horizontal_pixel<C>(l.v + j * tl.pitch + (l.lh[x] * C - a0), l.wh + x, l.ch[x], tl.oxb, t);
         s_lum[j * tl.oxb + x] = (unsigned char)locate_luma(resize_to_u8(t[0]), resize_to_u8(t[1]), resize_to_u8(t[2]));
     }
     __syncthreads();
@@ -427,6 +376,7 @@ namespace {
 
 size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 unsigned grid_rows(size_t rows) { return (unsigned)std::min<size_t>(std::max<size_t>(rows, 1), 65535); }
+bool resized(const ssw_placement& p) { return p.pw != p.w || p.ph != p.h; }
 
 // what one suspect needs of the group's workspace, as offsets into it
 struct Item {
@@ -444,20 +394,45 @@ struct Item {
 
 constexpr size_t GROUP_BYTES = 256u << 20;      // workspace of one group of suspects (one suspect may need more)
 
-}  // namespace
+// the original's luma plane, once per call: opitch % 4 == 0, 16 zero bytes of slack behind its last row (locate_fine_kernel)
+int original_luma(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, uint8_t** lo, unsigned* opitch) {
+    *opitch = (unsigned)up(w, 4);
+    SSW_TRY(grow(ctx->locate[0], (size_t)*opitch * h + 16));
+    *lo = (uint8_t*)ctx->locate[0].p;
+    SSW_HIP_CHECK(hipMemsetAsync(*lo + (size_t)*opitch * h, 0, 16, ctx->stream));
+    LumaBatch lb{};
+    lb.it[0] = LumaDev{dev_base, *lo, (uint32_t)w, (uint32_t)h, 3u, *opitch};
+    locate_luma_kernel<<<dim3((*opitch / 4 + 255) / 256, grid_rows(h), 1), 256, 0, ctx->stream>>>(lb);
+    SSW_HIP_CHECK(hipGetLastError());
+    return SSW_OK;
+}
 
-int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
-                const std::vector<ssw_placement>& pl, uint64_t* host_res, const std::vector<LocWindow>* win) {
-    const size_t n = pl.size();
-    hipStream_t st = ctx->stream;
-    std::vector<Item> items(n);
-    bool any_f4 = false;
-    for (size_t i = 0; i < n; ++i) {
-        Item& it = items[i];
+// One search of the coarse kernel: the template tmpl [th][tpitch] over a plane (f = 4: the original's 16 phase planes against
+// S_f; f = 2: its 2 x 2 box planes against a rung's T_j; f = 1: L_O against L_R, plane_stride 0), nx x ny candidates into D.
+// bx, by: the frame position of candidate (0, 0).  *tiles: the blocks of the launch so far, advanced by this search's.
+CoarseDev coarse_desc(const uint8_t* plane, uint32_t ppitch, uint32_t prows, size_t plane_stride, const uint8_t* tmpl, uint32_t tpitch,
+                      uint32_t tw, uint32_t th, uint32_t* D, uint32_t nx, uint32_t ny, uint32_t f, uint32_t bx, uint32_t by, unsigned* tiles) {
+    const uint32_t tiles_x = ((nx + f - 1) / f + LOC_TX - 1) / LOC_TX, tiles_y = ((ny + f - 1) / f + LOC_TY - 1) / LOC_TY;
+    const CoarseDev c{plane, tmpl, D, ppitch, prows, (uint32_t)plane_stride, tpitch, tw, th, nx, ny, f, tiles_x, tiles_y, *tiles, bx / (4 * f), by / f};
+    *tiles += tiles_x * tiles_y * f * f;
+    return c;
+}
+unsigned topk_blocks(uint32_t max_n) { return (unsigned)std::min<size_t>(((size_t)max_n + 2047) / 2048, 512); }
+
+// the resize runs on the colour channels alone
+int restore_prepare_rgb(ssw_ctx* ctx, std::vector<ssw_placement> pl) {
+    for (ssw_placement& p : pl) p.channels = 3;
+    return restore_prepare(ctx, pl);
+}
+
+// placements (and the windows of a refinement) -> what each search needs; SSW_ERR_UNSUPPORTED: a position is 32 bits of the key
+int plan_items(const std::vector<ssw_placement>& pl, const std::vector<LocWindow>* win, size_t w, size_t h, std::vector<Item>* items) {
+    items->resize(pl.size());
+    for (size_t i = 0; i < pl.size(); ++i) {
+        Item& it = (*items)[i];
         it.index = i;
         it.p = pl[i];
         it.f = std::min(it.p.pw, it.p.ph) >= 64 ? 4u : 1u;
-        any_f4 |= it.f == 4;
         it.nx = (unsigned)(w - it.p.pw + 1);
         it.ny = (unsigned)(h - it.p.ph + 1);
         if (win) {
@@ -468,12 +443,12 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
             it.nx = wd.x1 - it.bx + 1; it.ny = wd.y1 - it.by + 1;
             it.share = wd.share && i > 0;
         }
-        if ((uint64_t)it.nx * it.ny > 0xFFFFFFFFull) return SSW_ERR_UNSUPPORTED;      // a position is 32 bits of the key
+        if ((uint64_t)it.nx * it.ny > 0xFFFFFFFFull) return SSW_ERR_UNSUPPORTED;
         it.rpitch = (unsigned)up(it.p.pw, 4);
         it.tw = it.f == 4 ? it.p.pw / 4 : it.p.pw;
         it.th = it.f == 4 ? it.p.ph / 4 : it.p.ph;
         it.tpitch = it.f == 4 ? (unsigned)up(it.tw, 4) : it.rpitch;
-        const bool rs = it.p.pw != it.p.w || it.p.ph != it.p.h;
+        const bool rs = resized(it.p);
         size_t o = 0;
         it.off_rgb = o;   o += rs ? up((size_t)it.p.pw * it.p.ph * 3, 256) : 0;
         it.off_strip = o; o += rs && it.p.channels == 4 ? up((size_t)it.p.w * it.p.h * 3, 256) : 0;
@@ -483,25 +458,113 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
         it.off_d = o;     o += it.bytes_d;
         it.bytes = o;
     }
+    return SSW_OK;
+}
+
+// One group: the suspects [g0, g1) in the order of the call, as many as GROUP_BYTES of workspace hold (at least one).  Suspect i
+// has its R, luma and S_f at base_off[i - g0] and its D at d_off[i - g0]; a shared R is the one of the item before and lives in
+// its group.
+struct Group { size_t g0, g1, bytes; std::vector<size_t> base_off, d_off; std::vector<char> shared; };
+Group layout_group(const std::vector<Item>& items, size_t g0) {
+    Group g{g0, g0, 0, {}, {}, {}};
+    auto need = [&](size_t i) { return items[i].share && i > g0 ? items[i].bytes_d : items[i].bytes; };
+    while (g.g1 < items.size() && (g.g1 == g0 || g.bytes + need(g.g1) <= GROUP_BYTES)) g.bytes += need(g.g1++);
+    for (size_t i = g0, o = 0; i < g.g1; o += need(i++)) {
+        const bool sh = items[i].share && i > g0;
+        const size_t base = sh ? g.base_off.back() : o;
+        g.shared.push_back(sh);
+        g.base_off.push_back(base);
+        g.d_off.push_back(sh ? o : o + items[i].off_d);
+    }
+    return g;
+}
+
+// the original's planes of a call
+struct Original { const uint8_t* lo; unsigned opitch, h; const uint8_t* phases; unsigned qpitch, hq; size_t plane_stride; };
+
+// The searches of the suspects [b0, b0 + m) of a group, m <= LOC_BATCH, whose R (where resized) is in the workspace ws: luma,
+// S_f, coarse search, the 8 best of it, their full-resolution SADs and the answer into res
+int enqueue_batch(ssw_ctx* ctx, const std::vector<Item>& items, const Group& g, size_t b0, unsigned m, const void* const* dev_suspects,
+                  uint8_t* ws, const Original& og, uint64_t* keys, uint64_t* sums, uint64_t* res) {
+    hipStream_t st = ctx->stream;
+    LumaBatch lb{};
+    BoxBatch bb{};
+    CoarseBatch cb{};
+    TopBatch tb{};
+    FineBatch fb{};
+    unsigned nl = 0, nbox = 0, tiles = 0, max_words = 1, max_rows = 1, max_q = 1, max_qrows = 1, max_ph = 1;
+    uint32_t max_n = 1;
+    double bd = 0.0;
+    for (unsigned s = 0; s < m; ++s) {
+        const Item& it = items[b0 + s];
+        uint8_t* wsi = ws + g.base_off[b0 + s - g.g0];
+        const bool rs = resized(it.p), own = !g.shared[b0 + s - g.g0], f4 = it.f == 4;
+        if (own) lb.it[nl++] = LumaDev{rs ? wsi + it.off_rgb : (const uint8_t*)dev_suspects[b0 + s], wsi + it.off_lr, it.p.pw, it.p.ph,
+                                       rs ? 3u : it.p.channels, it.rpitch};
+        max_words = std::max(max_words, it.rpitch / 4);
+        max_rows = std::max(max_rows, it.p.ph);
+        if (f4 && own) {
+            bb.it[nbox++] = BoxDev{wsi + it.off_lr, wsi + it.off_sf, it.rpitch, it.p.pw, it.p.ph, it.tpitch, it.tw, it.th, 1u, 0u};
+            max_q = std::max(max_q, it.tpitch);
+            max_qrows = std::max(max_qrows, it.th);
+        }
+        cb.it[s] = coarse_desc(f4 ? og.phases : og.lo, f4 ? og.qpitch : og.opitch, f4 ? og.hq : og.h, f4 ? og.plane_stride : 0,
+                               wsi + (f4 ? it.off_sf : it.off_lr), it.tpitch, it.tw, it.th, (uint32_t*)(ws + g.d_off[b0 + s - g.g0]), it.nx, it.ny,
+                               it.f, it.bx, it.by, &tiles);
+        tb.it[s] = TopDev{cb.it[s].D, it.nx * it.ny, it.nx, it.skipx, it.skipy};
+        max_n = std::max(max_n, it.nx * it.ny);
+        fb.it[s] = FineDev{wsi + it.off_lr, it.rpitch, it.p.pw, it.p.ph, it.nx, it.bx, it.by};
+        max_ph = std::max(max_ph, it.p.ph);
+        bd += (double)it.nx * it.ny * ((double)it.tw * it.th);
+    }
+    if (nl) {
+        locate_luma_kernel<<<dim3((max_words + 255) / 256, grid_rows(max_rows), nl), 256, 0, st>>>(lb);
+        SSW_HIP_CHECK(hipGetLastError());
+    }
+    if (nbox) {
+        locate_box_kernel<<<dim3((max_q + 255) / 256, grid_rows(max_qrows), nbox), 256, 0, st>>>(bb);
+        SSW_HIP_CHECK(hipGetLastError());
+    }
+    {
+        StageTimer tc(ctx, SSW_STAGE_LOCATE_COARSE, st);
+        if (ctx->timing) ctx->stage_work[SSW_STAGE_LOCATE_COARSE] += bd;      // byte differences, not bytes
+        locate_coarse_kernel<<<tiles, 256, 0, st>>>(cb, m);
+        SSW_HIP_CHECK(hipGetLastError());
+    }
+    for (unsigned r = 0; r < LOC_TOP; ++r) {
+        locate_topk_kernel<<<dim3(topk_blocks(max_n), m), 256, 0, st>>>(tb, keys + b0 * LOC_TOP, r);
+        SSW_HIP_CHECK(hipGetLastError());
+    }
+    locate_fine_kernel<<<dim3(std::min(max_ph, 64u), LOC_TOP, m), 256, 0, st>>>(fb, og.lo, og.opitch, keys + b0 * LOC_TOP, sums + b0 * LOC_TOP);
+    SSW_HIP_CHECK(hipGetLastError());
+    locate_final_kernel<<<1, 64, 0, st>>>(fb, m, keys + b0 * LOC_TOP, sums + b0 * LOC_TOP, res + 2 * b0);
+    SSW_HIP_CHECK(hipGetLastError());
+    return SSW_OK;
+}
+
+}  // namespace
+
+int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
+                const std::vector<ssw_placement>& pl, uint64_t* host_res, const std::vector<LocWindow>* win) {
+    const size_t n = pl.size();
+    hipStream_t st = ctx->stream;
+    std::vector<Item> items;
+    SSW_TRY(plan_items(pl, win, w, h, &items));
+    const bool any_f4 = std::any_of(items.begin(), items.end(), [](const Item& it) { return it.f == 4; });
     // the original: luma plane once per call, and its 16 phase planes when a suspect takes the coarse factor 4
-    const unsigned opitch = (unsigned)up(w, 4);
     const unsigned wq = (unsigned)(w / 4), hq = (unsigned)(h / 4), qpitch = (unsigned)up(std::max(wq, 1u), 4);
     const size_t plane_stride = (size_t)qpitch * hq;
-    SSW_TRY(grow(ctx->locate[0], (size_t)opitch * h + 16));
     if (any_f4) SSW_TRY(grow(ctx->locate[1], 16 * plane_stride + 16));
     SSW_TRY(grow(ctx->locate[3], n * (2 * LOC_TOP + 2) * sizeof(uint64_t)));
-    uint8_t* lo = (uint8_t*)ctx->locate[0].p;
     uint8_t* phases = (uint8_t*)ctx->locate[1].p;
     uint64_t* keys = (uint64_t*)ctx->locate[3].p;
     uint64_t* sums = keys + n * LOC_TOP;
     uint64_t* res = sums + n * LOC_TOP;
+    uint8_t* lo = nullptr;
+    unsigned opitch = 0;
     {
         StageTimer t(ctx, SSW_STAGE_LOCATE, st, (double)w * h * (4.0 + (any_f4 ? 2.0 : 0.0)));
-        SSW_HIP_CHECK(hipMemsetAsync(lo + (size_t)opitch * h, 0, 16, st));
-        LumaBatch lb{};
-        lb.it[0] = LumaDev{dev_base, lo, (uint32_t)w, (uint32_t)h, 3u, opitch};
-        locate_luma_kernel<<<dim3((opitch / 4 + 255) / 256, grid_rows(h), 1), 256, 0, st>>>(lb);
-        SSW_HIP_CHECK(hipGetLastError());
+        SSW_TRY(original_luma(ctx, dev_base, w, h, &lo, &opitch));
         if (any_f4) {
             BoxBatch bb{};
             bb.it[0] = BoxDev{lo, phases, opitch, (uint32_t)w, (uint32_t)h, qpitch, wq, hq, 16u, (uint32_t)plane_stride};
@@ -511,26 +574,16 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
         SSW_HIP_CHECK(hipMemsetAsync(keys, 0xFF, n * LOC_TOP * sizeof(uint64_t), st));
         SSW_HIP_CHECK(hipMemsetAsync(sums, 0, n * LOC_TOP * sizeof(uint64_t), st));
     }
-    // suspects in groups of bounded workspace, in the order of the call
+    const Original og{lo, opitch, (unsigned)h, phases, qpitch, hq, plane_stride};
     for (size_t g0 = 0; g0 < n;) {
-        size_t g1 = g0, bytes = 0;
-        auto need = [&](size_t i) { return items[i].share && i > g0 ? items[i].bytes_d : items[i].bytes; };   // a shared R lives in its group
-        while (g1 < n && (g1 == g0 || bytes + need(g1) <= GROUP_BYTES)) bytes += need(g1++);
-        SSW_TRY(grow(ctx->locate[2], bytes + 16));
+        const Group g = layout_group(items, g0);
+        SSW_TRY(grow(ctx->locate[2], g.bytes + 16));
         uint8_t* ws = (uint8_t*)ctx->locate[2].p;
-        std::vector<size_t> base_off(g1 - g0), d_off(g1 - g0);
-        std::vector<char> shared(g1 - g0);
-        for (size_t i = g0, o = 0; i < g1; ++i) {
-            shared[i - g0] = items[i].share && i > g0;
-            base_off[i - g0] = shared[i - g0] ? base_off[i - 1 - g0] : o;
-            d_off[i - g0] = shared[i - g0] ? o : o + items[i].off_d;
-            o += need(i);
-        }
-        // 1. R: the suspect resized to the size it had in the original (alpha dropped first); timed as SSW_STAGE_RESIZE
-        for (size_t i = g0; i < g1; ++i) {
+        // R: the suspect resized to the size it had in the original (alpha dropped first); timed as SSW_STAGE_RESIZE
+        for (size_t i = g0; i < g.g1; ++i) {
             const Item& it = items[i];
-            if ((it.p.pw == it.p.w && it.p.ph == it.p.h) || shared[i - g0]) continue;
-            uint8_t* wsi = ws + base_off[i - g0];
+            if (!resized(it.p) || g.shared[i - g0]) continue;
+            uint8_t* wsi = ws + g.base_off[i - g0];
             const uint8_t* src = (const uint8_t*)dev_suspects[i];
             if (it.p.channels == 4) {
                 const size_t npix = (size_t)it.p.w * it.p.h;
@@ -543,81 +596,15 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
             SSW_TRY(restore_enqueue(ctx, nullptr, it.p.pw, it.p.ph, &job, 1));
         }
         double px_bytes = 0.0;
-        for (size_t i = g0; i < g1; ++i) {
+        for (size_t i = g0; i < g.g1; ++i) {
             const Item& it = items[i];
             const double a = (double)it.p.pw * it.p.ph;
-            px_bytes += a * (it.p.pw == it.p.w && it.p.ph == it.p.h ? it.p.channels : 3) + a + 8.0 * it.nx * it.ny;
+            px_bytes += a * (resized(it.p) ? 3 : it.p.channels) + a + 8.0 * it.nx * it.ny;
         }
         StageTimer t(ctx, SSW_STAGE_LOCATE, st, px_bytes);
-        for (size_t b0 = g0; b0 < g1; b0 += LOC_BATCH) {
-            const unsigned m = (unsigned)std::min<size_t>(LOC_BATCH, g1 - b0);
-            LumaBatch lb{};
-            BoxBatch bb{};
-            CoarseBatch cb{};
-            TopBatch tb{};
-            FineBatch fb{};
-            unsigned nl = 0, nbox = 0, tiles = 0, max_words = 1, max_rows = 1, max_q = 1, max_qrows = 1, max_ph = 1;
-            uint32_t max_n = 1;
-            for (unsigned s = 0; s < m; ++s) {
-                const Item& it = items[b0 + s];
-                uint8_t* wsi = ws + base_off[b0 + s - g0];
-                const bool rs = it.p.pw != it.p.w || it.p.ph != it.p.h;
-                const bool own = !shared[b0 + s - g0];
-                if (own) lb.it[nl++] = LumaDev{rs ? wsi + it.off_rgb : (const uint8_t*)dev_suspects[b0 + s], wsi + it.off_lr, it.p.pw, it.p.ph,
-                                               rs ? 3u : it.p.channels, it.rpitch};
-                max_words = std::max(max_words, it.rpitch / 4);
-                max_rows = std::max(max_rows, it.p.ph);
-                if (it.f == 4 && own) {
-                    bb.it[nbox++] = BoxDev{wsi + it.off_lr, wsi + it.off_sf, it.rpitch, it.p.pw, it.p.ph, it.tpitch, it.tw, it.th, 1u, 0u};
-                    max_q = std::max(max_q, it.tpitch);
-                    max_qrows = std::max(max_qrows, it.th);
-                }
-                CoarseDev& c = cb.it[s];
-                c.plane = it.f == 4 ? phases : lo;
-                c.tmpl = wsi + (it.f == 4 ? it.off_sf : it.off_lr);
-                c.D = (uint32_t*)(ws + d_off[b0 + s - g0]);
-                c.ppitch = it.f == 4 ? qpitch : opitch;
-                c.prows = it.f == 4 ? hq : (uint32_t)h;
-                c.plane_stride = it.f == 4 ? (uint32_t)plane_stride : 0u;
-                c.tpitch = it.tpitch; c.tw = it.tw; c.th = it.th;
-                c.nx = it.nx; c.ny = it.ny; c.f = it.f;
-                c.tiles_x = ((it.nx + it.f - 1) / it.f + LOC_TX - 1) / LOC_TX;
-                c.tiles_y = ((it.ny + it.f - 1) / it.f + LOC_TY - 1) / LOC_TY;
-                c.tile_begin = tiles;
-                c.bxw = it.bx / (4 * it.f); c.by = it.by / it.f;
-                tiles += c.tiles_x * c.tiles_y * it.f * it.f;
-                tb.it[s] = TopDev{c.D, it.nx * it.ny, it.nx, it.skipx, it.skipy};
-                max_n = std::max(max_n, it.nx * it.ny);
-                fb.it[s] = FineDev{wsi + it.off_lr, it.rpitch, it.p.pw, it.p.ph, it.nx, it.bx, it.by};
-                max_ph = std::max(max_ph, it.p.ph);
-            }
-            if (nl) {
-                locate_luma_kernel<<<dim3((max_words + 255) / 256, grid_rows(max_rows), nl), 256, 0, st>>>(lb);
-                SSW_HIP_CHECK(hipGetLastError());
-            }
-            if (nbox) {
-                locate_box_kernel<<<dim3((max_q + 255) / 256, grid_rows(max_qrows), nbox), 256, 0, st>>>(bb);
-                SSW_HIP_CHECK(hipGetLastError());
-            }
-            {
-                double bd = 0.0;
-                for (unsigned s = 0; s < m; ++s) bd += (double)items[b0 + s].nx * items[b0 + s].ny * ((double)items[b0 + s].tw * items[b0 + s].th);
-                StageTimer tc(ctx, SSW_STAGE_LOCATE_COARSE, st);
-                if (ctx->timing) ctx->stage_work[SSW_STAGE_LOCATE_COARSE] += bd;      // byte differences, not bytes
-                locate_coarse_kernel<<<tiles, 256, 0, st>>>(cb, m);
-                SSW_HIP_CHECK(hipGetLastError());
-            }
-            const unsigned tblocks = (unsigned)std::min<size_t>(((size_t)max_n + 2047) / 2048, 512);
-            for (unsigned r = 0; r < LOC_TOP; ++r) {
-                locate_topk_kernel<<<dim3(tblocks, m), 256, 0, st>>>(tb, keys + b0 * LOC_TOP, r);
-                SSW_HIP_CHECK(hipGetLastError());
-            }
-            locate_fine_kernel<<<dim3(std::min(max_ph, 64u), LOC_TOP, m), 256, 0, st>>>(fb, lo, opitch, keys + b0 * LOC_TOP, sums + b0 * LOC_TOP);
-            SSW_HIP_CHECK(hipGetLastError());
-            locate_final_kernel<<<1, 64, 0, st>>>(fb, m, keys + b0 * LOC_TOP, sums + b0 * LOC_TOP, res + 2 * b0);
-            SSW_HIP_CHECK(hipGetLastError());
-        }
-        g0 = g1;
+        for (size_t b0 = g0; b0 < g.g1; b0 += LOC_BATCH)
+            SSW_TRY(enqueue_batch(ctx, items, g, b0, (unsigned)std::min<size_t>(LOC_BATCH, g.g1 - b0), dev_suspects, ws, og, keys, sums, res));
+        g0 = g.g1;
     }
     SSW_HIP_CHECK(hipMemcpyAsync(host_res, res, n * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     untimed_work(ctx);
@@ -633,7 +620,6 @@ constexpr unsigned LAD_STEP = 8, LAD_KEEP = 8, LAD_NEAR_W = 7, LAD_NEAR_XY = 8, 
 uint32_t ladder_height(uint64_t pw, uint64_t sw, uint64_t sh) { return (uint32_t)std::max<uint64_t>(1, (2 * sh * pw + sw) / (2 * sw)); }
 
 // every tap table of a call's ladder in one host buffer: one upload, one wait
-struct TapRef { uint32_t left, count, weights; DeviceTaps shape; };      // offsets in words; shape: max_taps and span only
 struct LadderTaps {
     std::vector<uint32_t> words;
     std::map<std::pair<size_t, size_t>, TapRef> refs;
@@ -657,7 +643,8 @@ struct LadderTaps {
 
 struct Rung {
     uint32_t sus, pw, ph, tw, th, nx, ny;      // nx, ny: candidate positions (multiples of 4)
-    RungDev dev;                               // src, T and tile_begin are filled in per launch
+    RungDev dev;                               // src, T, taps and tile_begin are filled in per launch
+    TapRef vt, ht;
     uint32_t tiles, channels;
     size_t lds, bytes_t, bytes_d;
 };
@@ -667,32 +654,15 @@ int make_rung(LadderTaps& taps, const ssw_placement& p, uint32_t sus, uint32_t p
     Rung r{};
     r.sus = sus; r.pw = pw; r.ph = ph; r.tw = pw / 8; r.th = ph / 8; r.channels = p.channels;
     r.nx = (uint32_t)((W - pw) / 4 + 1); r.ny = (uint32_t)((H - ph) / 4 + 1);
-    const TapRef vt = taps.get(p.h, ph), ht = taps.get(p.w, pw);
+    r.vt = taps.get(p.h, ph); r.ht = taps.get(p.w, pw);
     if (taps.words.size() > 0xFFFFFFFFull) return SSW_ERR_UNSUPPORTED;
-    ResizeTile tl;
-    if (!pick_resize_tile(vt.shape, ht.shape, 8 * r.tw, 8 * r.th, p.channels, &tl, &r.lds, 3, 3)) return SSW_ERR_UNSUPPORTED;
     RungDev& d = r.dev;
-    d.vleft = vt.left; d.vcount = vt.count; d.vweights = vt.weights; d.vmax = vt.shape.max_taps;
-    d.hleft = ht.left; d.hcount = ht.count; d.hweights = ht.weights; d.hmax = ht.shape.max_taps;
+    if (!pick_resize_tile(r.vt.shape, r.ht.shape, 8 * r.tw, 8 * r.th, p.channels, &d.tl, &r.lds, 3, 3)) return SSW_ERR_UNSUPPORTED;
     d.sw = p.w; d.ow = 8 * r.tw; d.oh = 8 * r.th; d.tpitch = (uint32_t)up(r.tw, 4);
-    d.oyb = tl.oyb; d.oxb = tl.oxb; d.pitch = tl.pitch; d.oxb_log2 = tl.oxb_log2;
-    d.tiles_x = (d.ow + tl.oxb - 1) / tl.oxb;
-    r.tiles = d.tiles_x * ((d.oh + tl.oyb - 1) / tl.oyb);
+    r.tiles = d.tl.tiles_x * d.tl.tiles_y;
     r.bytes_t = up((size_t)d.tpitch * r.th, 256);
     r.bytes_d = up((size_t)r.nx * r.ny * 4, 256);
     *out = r;
-    return SSW_OK;
-}
-
-int set_rung_lds_attribute() {     // tiles above 64 KB of dynamic LDS need the per-device function attribute: once per device
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    SSW_HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        SSW_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(locate_rung_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        SSW_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(locate_rung_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-    }
     return SSW_OK;
 }
 
@@ -707,6 +677,8 @@ int upload_taps(ssw_ctx* ctx, const LadderTaps& taps, const uint32_t** dev) {
 // the rung launches of rungs [b0, b1) (at most LOC_BATCH): one per channel count that occurs; T of rung i at t_ptr[i - b0]
 int enqueue_rungs(ssw_ctx* ctx, const std::vector<Rung>& rungs, size_t b0, size_t b1, const void* const* dev_suspects, uint8_t* const* t_ptr,
                   const uint32_t* dev_taps) {
+    static std::atomic<bool> lds_raised[64];
+    SSW_TRY(resize_raise_lds_limit({reinterpret_cast<const void*>(locate_rung_kernel<3>), reinterpret_cast<const void*>(locate_rung_kernel<4>)}, lds_raised));
     double bytes = 0.0;
     for (size_t i = b0; i < b1; ++i) bytes += (double)rungs[i].dev.sw * rungs[i].channels * rungs[i].dev.oh + (double)rungs[i].tw * rungs[i].th;
     StageTimer t(ctx, SSW_STAGE_RESIZE, ctx->stream, bytes);
@@ -720,13 +692,14 @@ int enqueue_rungs(ssw_ctx* ctx, const std::vector<Rung>& rungs, size_t b0, size_
             d = rungs[i].dev;
             d.src = (const uint8_t*)dev_suspects[rungs[i].sus];
             d.T = t_ptr[i - b0];
+            d.taps = resize_tap_ptrs(dev_taps, rungs[i].vt, rungs[i].ht);
             d.tile_begin = tiles;
             tiles += rungs[i].tiles;
             lds = std::max(lds, rungs[i].lds);
         }
         if (!m) continue;
-        if (c == 4) locate_rung_kernel<4><<<tiles, 256, lds, ctx->stream>>>(rb, m, dev_taps);
-        else        locate_rung_kernel<3><<<tiles, 256, lds, ctx->stream>>>(rb, m, dev_taps);
+        if (c == 4) locate_rung_kernel<4><<<tiles, 256, lds, ctx->stream>>>(rb, m);
+        else        locate_rung_kernel<3><<<tiles, 256, lds, ctx->stream>>>(rb, m);
         SSW_HIP_CHECK(hipGetLastError());
     }
     return SSW_OK;
@@ -773,29 +746,23 @@ int locate_scaled_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h
         ws_bytes = std::max(ws_bytes, bytes);
         cuts.push_back(b0 = b1);
     }
-    const unsigned opitch = (unsigned)up(w, 4);
     const unsigned nbx = (unsigned)((w - 8) / 4 + 1), nby = (unsigned)((h - 8) / 4 + 1);      // w, h >= 32: a rung fits
     const unsigned qpitch = (unsigned)up((nbx + 1) / 2, 4), qrows = (nby + 1) / 2;
     const size_t plane_stride = (size_t)qpitch * qrows;
     if (4 * plane_stride > 0xFFFFFFFFull) return SSW_ERR_UNSUPPORTED;
-    SSW_TRY(grow(ctx->locate[0], (size_t)opitch * h + 16));
     SSW_TRY(grow(ctx->locate[4], 4 * plane_stride + 16));
     SSW_TRY(grow(ctx->locate[3], nr * LOC_TOP * sizeof(uint64_t)));
     SSW_TRY(grow(ctx->locate[2], ws_bytes + 16));
-    uint8_t* lo = (uint8_t*)ctx->locate[0].p;
     uint8_t* planes = (uint8_t*)ctx->locate[4].p;
     uint64_t* keys = (uint64_t*)ctx->locate[3].p;
     uint8_t* ws = (uint8_t*)ctx->locate[2].p;
     const uint32_t* dev_taps = nullptr;
     SSW_TRY(upload_taps(ctx, taps, &dev_taps));
-    SSW_TRY(set_rung_lds_attribute());
     {
         StageTimer t(ctx, SSW_STAGE_LOCATE, st, (double)w * h * 4.5);
-        SSW_HIP_CHECK(hipMemsetAsync(lo + (size_t)opitch * h, 0, 16, st));
-        LumaBatch lb{};
-        lb.it[0] = LumaDev{dev_base, lo, (uint32_t)w, (uint32_t)h, 3u, opitch};
-        locate_luma_kernel<<<dim3((opitch / 4 + 255) / 256, grid_rows(h), 1), 256, 0, st>>>(lb);
-        SSW_HIP_CHECK(hipGetLastError());
+        uint8_t* lo = nullptr;
+        unsigned opitch = 0;
+        SSW_TRY(original_luma(ctx, dev_base, w, h, &lo, &opitch));
         locate_box8_kernel<<<dim3((qpitch + 255) / 256, grid_rows(qrows)), 256, 0, st>>>(lo, opitch, (unsigned)w, (unsigned)h, planes, qpitch, qrows, (unsigned)plane_stride);
         SSW_HIP_CHECK(hipGetLastError());
         SSW_HIP_CHECK(hipMemsetAsync(keys, 0xFF, nr * LOC_TOP * sizeof(uint64_t), st));
@@ -813,16 +780,9 @@ int locate_scaled_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h
         for (unsigned s = 0; s < m; ++s) {
             const Rung& r = rungs[b0 + s];
             t_ptr[s] = ws + o;
-            CoarseDev& c = cb.it[s];
-            c.plane = planes; c.tmpl = t_ptr[s]; c.D = (uint32_t*)(ws + o + r.bytes_t);
-            c.ppitch = qpitch; c.prows = qrows; c.plane_stride = (uint32_t)plane_stride;
-            c.tpitch = r.dev.tpitch; c.tw = r.tw; c.th = r.th;
-            c.nx = r.nx; c.ny = r.ny; c.f = 2;
-            c.tiles_x = ((r.nx + 1) / 2 + LOC_TX - 1) / LOC_TX;
-            c.tiles_y = ((r.ny + 1) / 2 + LOC_TY - 1) / LOC_TY;
-            c.tile_begin = tiles;
-            tiles += c.tiles_x * c.tiles_y * 4;
-            tb.it[s] = TopDev{c.D, r.nx * r.ny, 0u, 0u, 0u};
+            cb.it[s] = coarse_desc(planes, qpitch, qrows, plane_stride, t_ptr[s], r.dev.tpitch, r.tw, r.th, (uint32_t*)(ws + o + r.bytes_t), r.nx, r.ny,
+                                   2u, 0u, 0u, &tiles);
+            tb.it[s] = TopDev{cb.it[s].D, r.nx * r.ny, 0u, 0u, 0u};
             max_n = std::max(max_n, r.nx * r.ny);
             bd += (double)r.nx * r.ny * ((double)r.tw * r.th);
             px_bytes += 8.0 * r.nx * r.ny + (double)r.tw * r.th;
@@ -837,7 +797,7 @@ int locate_scaled_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h
             SSW_HIP_CHECK(hipGetLastError());
         }
         // the rung's smallest (D, y, x): round 0 of the top-k, an atomic minimum of the 64-bit key
-        locate_topk_kernel<<<dim3((unsigned)std::min<size_t>(((size_t)max_n + 2047) / 2048, 512), m), 256, 0, st>>>(tb, keys + b0 * LOC_TOP, 0);
+        locate_topk_kernel<<<dim3(topk_blocks(max_n), m), 256, 0, st>>>(tb, keys + b0 * LOC_TOP, 0);
         SSW_HIP_CHECK(hipGetLastError());
     }
     std::vector<uint64_t> hk(nr * LOC_TOP);
@@ -884,11 +844,7 @@ int locate_scaled_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h
             rp.push_back(p); win.push_back(lw); rsus.push_back(dev_suspects[i]); owner.push_back(i);
         }
     }
-    {   // the resize runs on the colour channels alone
-        std::vector<ssw_placement> rgb(rp);
-        for (ssw_placement& p : rgb) p.channels = 3;
-        SSW_TRY(restore_prepare(ctx, rgb));
-    }
+    SSW_TRY(restore_prepare_rgb(ctx, rp));
     std::vector<uint64_t> res(2 * rp.size());
     SSW_TRY(locate_impl(ctx, dev_base, w, h, rsus.data(), rp, res.data(), &win));
     std::vector<char> have(n, 0);
@@ -915,7 +871,6 @@ int rung_boxes_impl(ssw_ctx* ctx, const void* dev_suspect, const ssw_placement& 
     uint8_t* t_ptr[1] = {(uint8_t*)ctx->locate[2].p};
     const uint32_t* dev_taps = nullptr;
     SSW_TRY(upload_taps(ctx, taps, &dev_taps));
-    SSW_TRY(set_rung_lds_attribute());
     SSW_TRY(enqueue_rungs(ctx, rungs, 0, 1, &dev_suspect, t_ptr, dev_taps));
     std::vector<uint8_t> t((size_t)r.dev.tpitch * r.th);
     SSW_HIP_CHECK(hipMemcpyAsync(t.data(), t_ptr[0], t.size(), hipMemcpyDeviceToHost, ctx->stream));
@@ -939,11 +894,7 @@ extern "C" int ssw_locate_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t
     SSW_TRY(restore_normalise(in.data(), n, w, h, &pl));
     for (size_t i = 0; i < n; ++i) if (!dev_suspects[i]) return SSW_ERR_BAD_ARG;
     CtxGuard g(ctx);
-    {   // the resize runs on the colour channels alone
-        std::vector<ssw_placement> rgb(pl);
-        for (ssw_placement& p : rgb) p.channels = 3;
-        SSW_TRY(restore_prepare(ctx, rgb));
-    }
+    SSW_TRY(restore_prepare_rgb(ctx, pl));
     std::vector<uint64_t> res(2 * n);
     SSW_TRY(locate_impl(ctx, dev_base_rgb, w, h, dev_suspects, pl, res.data()));
     for (size_t i = 0; i < n; ++i) {

@@ -10,10 +10,11 @@
 // Two kernels, both bound by HBM bytes:
 //   restore_place_kernel    no resize: whole frames [n][H][W][3] in one streaming launch -- O outside the rectangle, S (3 or
 //                           4 B/px) blended inside.  For a resized suspect it writes only the outside of the rectangle.
-//   restore_resize_kernel   the fused CatmullRom pass of attack.hip (tile -> LDS, vertical pass into an f32 strip that never
-//                           leaves the CU, horizontal pass) with 3 or 4 input channels, the blend against O as its epilogue
-//                           and an output that lands in a rectangle of a larger frame.  Tap arithmetic, accumulation and
-//                           rounding come from resize_common.hpp, which attack.hip uses too.
+//   restore_resize_kernel   the fused CatmullRom tile of resize_common.hpp (resize_tile_front: tile -> LDS, vertical pass into
+//                           an f32 strip that never leaves the CU) with 3 or 4 input channels; its own part is the horizontal
+//                           pass with the blend against O as its epilogue and an output that lands in a rectangle of a larger
+//                           frame.  LDS layout, reach, loader, accumulation and rounding come from that header, which
+//                           attack.hip and locate.hip use too.
 // Neither kernel assumes any alignment: 32-bit accesses are taken where an address IS 4-byte aligned, bytes elsewhere.
 #include <algorithm>
 #include <atomic>
@@ -121,75 +122,27 @@ __global__ __launch_bounds__(256) void restore_place_kernel(const uint8_t* __res
 }
 
 // One block = one tile of OYB x OXB pixels of the rectangle of one suspect; every suspect of a launch has the same size,
-// channel count and rectangle size (one pair of tap tables).  grid: (tiles, suspects).  LDS layout of resize_fused_kernel.
+// channel count and rectangle size (one pair of tap tables).  grid: (tiles, suspects).
 template <int C>
 __global__ __launch_bounds__(256) void restore_resize_kernel(const uint8_t* __restrict__ base, unsigned W, RestoreBatch b, unsigned sw,
-                                                             unsigned pw, unsigned ph, const uint32_t* __restrict__ vleft,
-                                                             const uint32_t* __restrict__ vcount, const float* __restrict__ vweights,
-                                                             unsigned vmax, const uint32_t* __restrict__ hleft,
-                                                             const uint32_t* __restrict__ hcount, const float* __restrict__ hweights,
-                                                             unsigned hmax, ResizeTile tl) {
+                                                             unsigned pw, unsigned ph, ResizeTapPtrs taps, ResizeTile tl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* s_v = reinterpret_cast<float*>(smem);
-    float* s_wh = s_v + (size_t)tl.oyb * tl.pitch;
-    float* s_wv = s_wh + (size_t)tl.oxb * hmax;
-    uint32_t* s_lv = reinterpret_cast<uint32_t*>(s_wv + (size_t)tl.oyb * vmax);
-    uint32_t* s_cv = s_lv + tl.oyb;
-    uint32_t* s_lh = s_cv + tl.oyb;
-    uint32_t* s_ch = s_lh + tl.oxb;
-    unsigned char* s_in = smem + resize_lds_in_offset(tl, hmax, vmax);
-    unsigned char* s_out = s_in;                       // reused after the vertical pass: [oyb][oxb * 3]
+    const ResizeLds l = resize_lds_carve(smem, tl, taps.hmax, taps.vmax);
+    unsigned char* s_out = l.in;                       // reused after the vertical pass: [oyb][oxb * 3]
 
     const RestoreDev& d = b.it[blockIdx.y];
     const unsigned tid = threadIdx.x, lane = tid & 63;
     const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned tx = blockIdx.x % tl.tiles_x, ty = blockIdx.x / tl.tiles_x;
-    const unsigned oy0 = ty * tl.oyb, ox0 = tx * tl.oxb;
-    const unsigned noy = ph - oy0 < tl.oyb ? ph - oy0 : tl.oyb;
-    const unsigned nox = pw - ox0 < tl.oxb ? pw - ox0 : tl.oxb;
-
-    // the tile's reach in the suspect: rows [r0, r1), bytes [a0, b1) of each (left / right bounds grow with the output index)
-    const unsigned r0 = vleft[oy0], r1 = vleft[oy0 + noy - 1] + vcount[oy0 + noy - 1];
-    const unsigned b0 = hleft[ox0] * C, b1 = (hleft[ox0 + nox - 1] + hcount[ox0 + nox - 1]) * C;
-    const unsigned a0 = b0 & ~3u;
-    const unsigned words = (b1 - a0 + 3) / 4;
-    const unsigned nrows = r1 - r0;
-    const unsigned row_bytes = sw * C;
-    {   // 1. tap tables and input tile -> LDS
-        for (unsigned i = tid; i < nox * hmax; i += 256) { const unsigned x = i / hmax, tp = i - x * hmax; s_wh[tp * tl.oxb + x] = hweights[(size_t)ox0 * hmax + i]; }   // tap-major
-        for (unsigned i = tid; i < noy * vmax; i += 256) s_wv[i] = vweights[(size_t)oy0 * vmax + i];
-        if (tid < noy) { s_lv[tid] = vleft[oy0 + tid]; s_cv[tid] = vcount[oy0 + tid]; }
-        if (tid < nox) { s_lh[tid] = hleft[ox0 + tid]; s_ch[tid] = hcount[ox0 + tid]; }
-        const uint8_t* __restrict__ src = d.src + (size_t)r0 * row_bytes + a0;
-        const unsigned avail = row_bytes - a0;                          // bytes from a0 to the end of the suspect's row
-        const bool rows_aligned = aligned4(src) && (row_bytes & 3) == 0;
-        for (unsigned it = tid; it < nrows * words; it += 256) {
-            const unsigned r = it / words, wd = it - r * words;
-            const uint8_t* p = src + (size_t)r * row_bytes + 4 * wd;
-            uint32_t v = 0;
-            if (rows_aligned && 4 * wd + 4 <= avail) v = *reinterpret_cast<const uint32_t*>(p);
-            else {                                                      // stay inside the row: never past the suspect's last byte
-#pragma unroll
-                for (unsigned e = 0; e < 4; ++e) if (4 * wd + e < avail) v |= (uint32_t)p[e] << (8 * e);
-            }
-            *reinterpret_cast<uint32_t*>(s_in + r * tl.pitch + 4 * wd) = v;
-        }
-    }
-    __syncthreads();
-    // 2. vertical pass: whole LDS rows, slack included (bytes the tile did not load give finite sums nobody reads)
-    {
-        const unsigned chunks16 = tl.pitch / 16;
-        if (noy * chunks16 >= 192) resize_vertical_pieces<4>(s_in, s_v, s_wv, s_lv, s_cv, r0, noy, chunks16, vmax, tl.pitch, tid);
-        else                       resize_vertical_pieces<2>(s_in, s_v, s_wv, s_lv, s_cv, r0, noy, tl.pitch / 8, vmax, tl.pitch, tid);
-    }
-    __syncthreads();
+    // 1. tap tables and input tile -> LDS, 2. vertical pass
+    const ResizeReach rc = resize_tile_front<C>(l, taps, tl, blockIdx.x, pw, ph, d.src, sw);
+    const unsigned oy0 = rc.oy0, ox0 = rc.ox0, noy = rc.noy, nox = rc.nox, a0 = rc.a0;
     // 3. horizontal pass, clamp + round of every channel, then the blend against the original; staged in LDS
     const unsigned out_pitch = tl.oxb * 3;
     for (unsigned it = tid; it < (noy << tl.oxb_log2); it += 256) {
         const unsigned j = it >> tl.oxb_log2, x = it & ((1u << tl.oxb_log2) - 1);
         if (x >= nox) continue;
         float t[C];
-        resize_horizontal_pixel<C>(s_v + j * tl.pitch + (s_lh[x] * C - a0), s_wh + x, s_ch[x], tl.oxb, t);
+        resize_horizontal_pixel<C>(l.v + j * tl.pitch + (l.lh[x] * C - a0), l.wh + x, l.ch[x], tl.oxb, t);
         uint32_t r[4] = {resize_to_u8(t[0]), resize_to_u8(t[1]), resize_to_u8(t[2]), 255u};
         uint32_t o[3] = {r[0], r[1], r[2]};
         if (C == 4) {
@@ -231,18 +184,6 @@ bool restore_tile(const DeviceTaps& vt, const DeviceTaps& ht, const ssw_placemen
     tl->tiles_x = (p.pw + tl->oxb - 1) / tl->oxb;
     tl->tiles_y = (p.ph + tl->oyb - 1) / tl->oyb;
     return true;
-}
-
-int set_lds_attribute() {      // tiles above 64 KB of dynamic LDS need the per-device function attribute: once per device
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    SSW_HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        SSW_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(restore_resize_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        SSW_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(restore_resize_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-    }
-    return SSW_OK;
 }
 
 }  // namespace
@@ -306,7 +247,9 @@ int restore_enqueue(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, c
         restore_place_kernel<<<dim3((unsigned)((quads + 255) / 256), rows, (unsigned)m), 256, 0, ctx->stream>>>(dev_base, (unsigned)w, (unsigned)h, b);
         SSW_HIP_CHECK(hipGetLastError());
     }
-    if (!classes.empty()) SSW_TRY(set_lds_attribute());
+    static std::atomic<bool> lds_raised[64];
+    if (!classes.empty())
+        SSW_TRY(resize_raise_lds_limit({reinterpret_cast<const void*>(restore_resize_kernel<3>), reinterpret_cast<const void*>(restore_resize_kernel<4>)}, lds_raised));
     for (auto& kv : classes) {
         const std::vector<RestoreDev>& v = kv.second;
         const ssw_placement p{std::get<0>(kv.first), std::get<1>(kv.first), std::get<4>(kv.first), 0, 0, std::get<2>(kv.first), std::get<3>(kv.first)};
@@ -316,17 +259,14 @@ int restore_enqueue(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, c
         ResizeTile tl;
         size_t lds = 0;
         if (!restore_tile(vt, ht, p, &tl, &lds)) return SSW_ERR_UNSUPPORTED;
+        const ResizeTapPtrs taps = resize_tap_ptrs(vt, ht);
         for (size_t i0 = 0; i0 < v.size(); i0 += RESTORE_BATCH) {
             const size_t m = std::min<size_t>(RESTORE_BATCH, v.size() - i0);
             RestoreBatch b{};
             std::copy(v.begin() + i0, v.begin() + i0 + m, b.it);
             const dim3 grid(tl.tiles_x * tl.tiles_y, (unsigned)m);
-            if (p.channels == 4)
-                restore_resize_kernel<4><<<grid, 256, lds, ctx->stream>>>(dev_base, (unsigned)w, b, p.w, p.pw, p.ph, vt.left, vt.count, vt.weights,
-                                                                          vt.max_taps, ht.left, ht.count, ht.weights, ht.max_taps, tl);
-            else
-                restore_resize_kernel<3><<<grid, 256, lds, ctx->stream>>>(dev_base, (unsigned)w, b, p.w, p.pw, p.ph, vt.left, vt.count, vt.weights,
-                                                                          vt.max_taps, ht.left, ht.count, ht.weights, ht.max_taps, tl);
+            if (p.channels == 4) restore_resize_kernel<4><<<grid, 256, lds, ctx->stream>>>(dev_base, (unsigned)w, b, p.w, p.pw, p.ph, taps, tl);
+            else                 restore_resize_kernel<3><<<grid, 256, lds, ctx->stream>>>(dev_base, (unsigned)w, b, p.w, p.pw, p.ph, taps, tl);
             SSW_HIP_CHECK(hipGetLastError());
         }
     }

@@ -901,6 +901,25 @@ def test_8k_pipeline_and_resize_attack_parity_with_oracle():
     assert abs(float(sims_d[0]) - o_sim) < 0.05 and sims_d[0] > 6.0
 
 
+# The fused resize tile at the edges of its shared front end (csrc/resize_common.hpp): what pick_resize_tile chooses for each
+# shape, printed from a scratch build, is in the comment -- together a last tile partial in both axes, the 4-word and the 2-word
+# vertical pieces, dynamic LDS above 64 KB and each of the three horizontal passes.
+RESIZE_TILE_CASES = [
+    (508, 500, 60, 68),      # down-scaling: tile 8 x 16, 4 x 9 tiles, last 4 x 12; full rows of tiles 4-word, the last row 2-word
+    (300, 300, 100, 100),    # tile 16 x 64, 79616 B of LDS (> 64 KB), last 4 x 36: 2-word
+    (100, 60, 200, 120),     # integer up-scaling (quads share their taps): tile 32 x 128, last 24 x 72
+    (128, 64, 380, 252),     # up-scaling: tile 64 x 128, 72448 B of LDS (> 64 KB), 3 x 4 tiles, last 60 x 124
+]
+
+
+@pytest.mark.parametrize("w,h,nw,nh", RESIZE_TILE_CASES)
+def test_resize_tile_edges_equal_the_oracle(w, h, nw, nh):
+    frames = np.random.default_rng(w + nw).integers(0, 256, (2, h, w, 3), dtype=np.uint8)
+    got = G.resize_rgb8(frames, nw, nh)
+    for f in range(2):
+        assert np.array_equal(got[f], O.resize_rgb8(frames[f], nw, nh)), f
+
+
 def test_automatic_pass_size():
     """~2^30 pixels per internal pass, capped where the f64 operand planes of a pass would pass 4 GB, in whole groups of 8."""
     ctx = G.ctx()

@@ -73,6 +73,34 @@ def test_rung_boxes_equal_the_box_means_of_the_restored_frame(pw, ph, channels):
     assert want.shape == got.shape and np.array_equal(got, want), np.abs(got.astype(int) - want).max()
 
 
+# The rung kernel on the shared front end of the fused tile (csrc/resize_common.hpp) at its edges; what pick_resize_tile chooses
+# for each shape, printed from a scratch build, is in the comment.  (suspect w, h, channels, rung w, h, bytes the suspect's
+# pointer is offset by)
+RUNG_TILE_CASES = [
+    (505, 487, 3, 64, 56, 1),    # rows of 1515 B behind an odd pointer: tile 8 x 16, 4-word vertical pieces
+    (505, 487, 4, 64, 56, 0),    # tile 8 x 8, 2-word vertical pieces
+    (211, 173, 3, 417, 341, 0),  # rows of 633 B: tile 32 x 128 over the 416 x 336 pixels that lie in a box, last tile 16 x 32
+    (211, 173, 4, 300, 250, 1),  # tile 32 x 128 of 69248 B of LDS (> 64 KB), last tile 24 x 40
+]
+
+
+@pytest.mark.parametrize("sw,sh,c,pw,ph,off", RUNG_TILE_CASES)
+def test_rung_boxes_at_the_tile_edges(sw, sh, c, pw, ph, off):
+    """As above: T_j against the box means of the restored frame, bit for bit."""
+    lib, ctx = G.lib(), G.ctx()
+    s = np.random.default_rng(sw + c).integers(0, 256, (sh, sw, c), dtype=np.uint8)
+    opaque = s.copy()
+    opaque[..., 3:] = 255                                               # the rung kernel ignores alpha, the restore blends it
+    frame = wm.restore(np.zeros((ph, pw, 3), np.uint8), [opaque], [Placement(0, 0, pw, ph)], ctx=ctx)[0]
+    want = box8(luma(frame))[::8, ::8][:ph // 8, :pw // 8]
+    ds = ctx.to_device(np.concatenate([np.zeros(off, np.uint8), s.reshape(-1)]))
+    got = np.zeros((ph // 8, pw // 8), np.uint8)
+    rc = lib.ssw_locate_rung_boxes(ctx.handle, C.c_void_p(ds.ptr.value + off), sw, sh, c, pw, ph, got.ctypes.data)
+    ds.free()
+    assert rc == L.SSW_OK
+    assert want.shape == got.shape and np.array_equal(got, want), np.abs(got.astype(int) - want).max()
+
+
 def test_three_half_scale_cut_outs_name_their_copies():
     base, _ = cat()
     k = 1000

@@ -157,6 +157,36 @@ def test_restore_on_a_frame_whose_rows_are_not_multiples_of_four():
         assert np.array_equal(g, restore_ref(base, s, p)), i
 
 
+# The fused tile's shared front end (csrc/resize_common.hpp) at its edges; what pick_resize_tile chooses for each shape, printed
+# from a scratch build, is in the comment.  Every last tile is partial in both axes.  (suspect w, h, channels, rectangle w, h,
+# bytes the suspect's pointer is offset by)
+RESTORE_TILE_CASES = [
+    (505, 487, 3, 61, 59, 0),    # rows of 1515 B (% 4 = 3): tile 8 x 16, full rows of tiles 4-word vertical pieces, the last (3 x 13) 2-word
+    (505, 487, 4, 61, 59, 1),    # aligned rows behind a pointer that is not: the byte loads; tile 4 x 16, 2-word
+    (53, 37, 3, 75, 49, 1),      # rows of 159 B: one tile 64 x 128 of 76544 B of LDS (> 64 KB), 49 x 75 of it used
+    (211, 173, 4, 417, 341, 0),  # up-scaling with alpha: tile 32 x 128, 4 x 11 tiles, last 21 x 33
+]
+
+
+@pytest.mark.parametrize("sw,sh,c,pw,ph,off", RESTORE_TILE_CASES)
+def test_restore_tile_edges_equal_the_recipe(sw, sh, c, pw, ph, off):
+    lib, ctx = G.lib(), G.ctx()
+    base = np.ascontiguousarray(cat_u8()[:ph + 7, :pw + 5])              # the rectangle at an odd position of a frame with odd rows
+    s = other_image((sh, sw, c), sw + c)
+    p = Placement(3, 5, pw, ph)
+    H, W = base.shape[:2]
+    db, dout = ctx.to_device(base), ctx.to_device(np.zeros_like(base))
+    ds = ctx.to_device(np.concatenate([np.zeros(off, np.uint8), s.reshape(-1)]))
+    ptrs = (C.c_void_p * 1)(ds.ptr.value + off)
+    pl = (L.Placement * 1)(L.Placement(sw, sh, c, p.x, p.y, pw, ph))
+    rc = lib.ssw_restore_rgb8(ctx.handle, db.ptr, W, H, ptrs, pl, 1, dout.ptr)
+    got = dout.to_host(np.uint8, base.shape)
+    for b in (db, ds, dout):
+        b.free()
+    assert rc == L.SSW_OK
+    assert np.array_equal(got, restore_ref(base, s, p))
+
+
 # ---- the trace forms ---------------------------------------------------------------------------------------------------------
 def same(a, b, what=""):
     for name in FIELDS:
