@@ -82,6 +82,8 @@ SIGNATURES = {
     "ssw_tuning_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong)]),
     "ssw_tuning_reset": (C.c_int, [C.c_char_p]),
     "ssw_ctx_get_prune_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "ssw_ctx_get_base_prune_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "ssw_debug_base_prune_bound": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]),
     "ssw_ctx_get_select_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "ssw_dev_mem_info": (C.c_int, [_vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "ssw_dev_alloc": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),

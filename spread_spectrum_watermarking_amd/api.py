@@ -118,7 +118,10 @@ class Context:
     def prune_stats(self) -> dict:
         st = (C.c_uint64 * 3)()
         check(self._lib.ssw_ctx_get_prune_stats(self.handle, st), "ssw_ctx_get_prune_stats")
-        return {"pruned_chunks": int(st[0]), "redone_chunks": int(st[1]), "columns_needed": int(st[2])}
+        bp = (C.c_uint64 * 3)()
+        check(self._lib.ssw_ctx_get_base_prune_stats(self.handle, bp), "ssw_ctx_get_base_prune_stats")
+        return {"pruned_chunks": int(st[0]), "redone_chunks": int(st[1]), "columns_needed": int(st[2]),
+                "base_tiles": int(bp[0]), "base_tiles_computed": int(bp[1]), "base_frames_extended": int(bp[2])}
 
     def select_stats(self) -> dict:
         st = (C.c_uint64 * 2)()

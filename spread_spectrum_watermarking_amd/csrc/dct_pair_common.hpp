@@ -71,6 +71,8 @@ struct PairOutT {
     // launches' frequencies (fwd_cm128_pos); tile row j is staged from line m0 + fwd_cm128_pos(j), i.e. the tile's columns
     // come out natural and the epilogue is unchanged
     unsigned xperm = 0;
+    // EPI_FWD_COLOP, energy instances (SUB >= 10): [frames][W] sums of squares of the f32 row-pass values per column-operand line
+    float* col_energy = nullptr;
 };
 
 // Column order of the intermediate plane between the two passes of a deep forward transform (row pass first): the

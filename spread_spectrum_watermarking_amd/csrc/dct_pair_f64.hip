@@ -117,6 +117,13 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
         inst.epi = EPI_FWD_COLOP;
     }
     if (fuse_cols) po.xperm = 1;
+    const bool energy = fuse_rows && fuse->energy != nullptr;
+    po.col_energy = energy ? fuse->energy : nullptr;
+    ml.need = nullptr; ml.need_mode = 0; ml.need_tpf = 1;
+    if (fuse_cols && fuse->tile_mode) {
+        if (inst.epi != EPI_FWD || inst.samex || small || (fuse->tile_mode == 2 && !fuse->need)) return SSW_ERR_BAD_ARG;
+        ml.need = fuse->need; ml.need_mode = (unsigned)fuse->tile_mode; ml.need_tpf = (unsigned)(w / 128);
+    }
     auto al = [](const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
     po.wide = (!is_row && w % 4 == 0 && al(out, 16) && (n_frames * w) % 4 == 0 && (!tmp || al(tmp, 16)) && (!tmp_out || al(tmp_out, 16))) ? 1u : 0u;
     if (with_sink && !(al(sink->iq_i, 16) && al(sink->iq_q, 16) && al(sink->rgb, sink->u8 ? 4 : 16))) po.wide = 0;
@@ -127,12 +134,15 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     ml.po = po;
     switch (inst.epi) {
     case EPI_FWD_COLOP:
-        if (inst.subname == 4) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 4, 128);
+        // (the energy instances are named SUB + 10: the writer's row launches stay the kernels they were)
+        if (energy) { if (inst.subname == 4) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 14, 128); else SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 13, 128); }
+        else if (inst.subname == 4) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 4, 128);
         else SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 3, 128);
         break;
     case EPI_FWD_ADJ: SSW_LAUNCH_PAIR(false, EPI_FWD_ADJ, false); break;
     case EPI_FWD:
-        if (inst.subname == 4) SSW_LAUNCH_PAIR_SUB(false, EPI_FWD, false, 4);
+        if (ml.need_mode) SSW_LAUNCH_PAIR_BM(true, EPI_FWD, false, 13, 128);      // (the two phases of a pruned base reader: eight classes, one launch)
+        else if (inst.subname == 4) SSW_LAUNCH_PAIR_SUB(false, EPI_FWD, false, 4);
         else if (inst.subname == 3) { if (is_row) SSW_LAUNCH_PAIR_SUB(false, EPI_FWD, false, 3); else SSW_LAUNCH_PAIR_SUB(true, EPI_FWD, false, 3); }
         else if (inst.samex) SSW_LAUNCH_ROWCOL(EPI_FWD, true);
         else SSW_LAUNCH_ROWCOL(EPI_FWD, false);

@@ -82,6 +82,9 @@ struct PairMulti {
     PairClassArgs c[8];
     unsigned n_classes, L, tiles_m, tiles_n_total;
     PairOut po;                        // the fields the classes share; c1 .. bn32 are overwritten per class
+    // forward column launches of a pruned base reader (FuseCols::tile_mode): line tile tm = frame * need_tpf + column tile
+    const unsigned* need = nullptr;
+    unsigned need_mode = 0, need_tpf = 1;
 };
 
 template <bool COLS, int EPI, bool SAMEX, int SUB = 0, int BM = 128>
@@ -113,6 +116,12 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
     unsigned tm, tn, cls = 0;
     tile_of_block(blockIdx.x, gridDim.x, ml.tiles_m, ml.tiles_n_total, tm, tn);
     while (cls + 1 < ml.n_classes && tn >= ml.c[cls].tiles_n) { tn -= ml.c[cls].tiles_n; ++cls; }      // block-uniform
+    if constexpr (COLS && EPI == EPI_FWD && BM == 128 && SUB >= 10) {
+        // pruned base reader (its own instance, SUB 13: every other column launch is the kernel it was): phase 1 computes column tile 0 of every frame, phase 2 the other tiles that are needed; a block
+        // of any other tile returns before it has issued a load (tm is block-uniform: the flag is a scalar load)
+        const unsigned t = tm % ml.need_tpf;
+        if (ml.need_mode == 1 ? t != 0 : (t == 0 || ml.need[tm] == 0)) return;
+    }
     const PairClassArgs& ca = ml.c[cls];
     const double* __restrict__ X1g = ca.x1;
     const double* __restrict__ X2g = ca.x2;
@@ -434,6 +443,17 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
             f1[jn] = fpos1(pair) == 0 ? ep.first : ep.base;
             f2[jn] = fpos2(pair) == 0 ? ep.first : ep.base;
         }
+        // energy instances: sum of squares of this lane's f32 values per output, i.e. per column-operand line (f32 VALU only);
+        // block totals of the tile's 64 pairs x 2 outputs in the 16 KB of LDS above the store slabs
+        constexpr bool ENERGY = SUB >= 10;
+        float en1[NJ], en2[NJ];
+        float* eb = reinterpret_cast<float*>(lds + 4 * 128 * 8);
+        if constexpr (ENERGY) {
+            static_assert(4 * 128 * 64 + 128 * 4 <= (int)sizeof(lds), "energy totals above the slabs");
+#pragma unroll
+            for (int jn = 0; jn < NJ; ++jn) { en1[jn] = 0.f; en2[jn] = 0.f; }
+            if (tid < 128) eb[tid] = 0.f;
+        }
         // phase A: this lane's items (item f = lane + 64 c of the wave: pair tile f / 32, output (f / 16) & 1, pair f & 15),
         // all sixteen planes of the wave's NI units
         double o[NC][NI][16];
@@ -446,6 +466,7 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
                 for (int r = 0; r < 4; ++r) {
                     float v1 = (float)acc1[i][jn][r], v2 = (float)acc2[i][jn][r];
                     if (!plain) { v1 *= f1[jn]; v2 *= f2[jn]; }
+                    if constexpr (ENERGY) { en1[jn] = __builtin_fmaf(v1, v1, en1[jn]); en2[jn] = __builtin_fmaf(v2, v2, en2[jn]); }
                     tw[lpos(32 * jn + li, lq + 4 * r)] = v1;
                     tw[lpos(32 * jn + 16 + li, lq + 4 * r)] = v2;
                 }
@@ -477,6 +498,20 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
         // 128-column tile).  A slab = one plane x the tile's 2 NPT lines x the k-block's eight units (64 bytes per line; the
         // four 16-byte chunks of a line XOR-swizzled by (T / 4) & 3); four planes per round, four rounds.  Store sweep: thread
         // = (line, chunk), four lanes complete a 64-byte piece, a wave writes 1 KB of sixteen consecutive lines.
+        if constexpr (ENERGY) {
+            __syncthreads();                  // the totals are zero
+#pragma unroll
+            for (int jn = 0; jn < NJ; ++jn) {
+                float a = en1[jn], b = en2[jn];
+                a += __shfl_xor(a, 16); a += __shfl_xor(a, 32);
+                b += __shfl_xor(b, 16); b += __shfl_xor(b, 32);
+                if (lq == 0) {
+                    const unsigned pl = wn + 16 * jn + li;              // pair inside the tile
+                    atomicAdd(eb + pl, a);
+                    atomicAdd(eb + 64 + pl, b);
+                }
+            }
+        }
         double* slab = lds;
         unsigned tl[NC];
 #pragma unroll
@@ -502,6 +537,16 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
 #pragma unroll
         for (int rnd = 0; rnd < 4; ++rnd) {
             __syncthreads();                  // the transpose areas (round 0) / the previous round's slabs have been read
+            if constexpr (ENERGY) {
+                // one add per (block, output): outputs that exist only (st_ok's conditions); the order of the adds is free --
+                // the sums decide what is computed, never a value
+                if (rnd == 0 && tid < 128) {
+                    const unsigned pl = tid & 63u, pair = p0 + pl;
+                    const bool second = tid >= 64;
+                    const bool ok = pl < (unsigned)NPT && pair < NP && (second ? (pair >= po.p2lo && second_out) : pair < po.np1);
+                    if (ok) unsafeAtomicAdd(po.col_energy + (size_t)z * po.W + (second ? fpos2(pair) : fpos1(pair)), eb[tid]);
+                }
+            }
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 if ((lane + 64 * c) >= (unsigned)NIT) continue;

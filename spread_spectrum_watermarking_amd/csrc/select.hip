@@ -514,6 +514,22 @@ __global__ __launch_bounds__(FINISH_THREADS) void select_finish_kernel(
     }
 }
 
+// src/algorithm.rs:245-250, :255-265 evaluated in f32 on the host (IEEE, same bits): s[first_row][first_column].  One function
+// for the selection and for the base-reader pruning, whose threshold is a bound only while both form the same keys.
+void select_ortho_scales(size_t w, size_t h, float s[2][2]) {
+    const float s_k0_w = sqrtf(1.0f / (4.0f * (float)w));
+    const float s_k0_h = sqrtf(1.0f / (4.0f * (float)h));
+    const float s_w = sqrtf(1.0f / (2.0f * (float)w));
+    const float s_h = sqrtf(1.0f / (2.0f * (float)h));
+    for (int fr = 0; fr < 2; ++fr)
+        for (int fc = 0; fc < 2; ++fc) {
+            volatile float sc = 1.0f;
+            sc = sc * (fr ? s_k0_w : s_w);
+            sc = sc * (fc ? s_k0_h : s_h);
+            s[fr][fc] = sc;
+        }
+}
+
 int launch_topk(hipStream_t st, const float* coef, size_t n_frames, size_t w, size_t h, int ordering,
                 size_t k, const SelectWorkspace& ws, uint32_t* indices) {
     const size_t plane_len = w * h;
@@ -527,19 +543,7 @@ int launch_topk(hipStream_t st, const float* coef, size_t n_frames, size_t w, si
     KeyParams kp;
     kp.ordering = ordering;
     kp.w = (unsigned)w;
-    {   // src/algorithm.rs:245-250, :255-265 evaluated in f32 on the host (IEEE, same bits)
-        const float s_k0_w = sqrtf(1.0f / (4.0f * (float)w));
-        const float s_k0_h = sqrtf(1.0f / (4.0f * (float)h));
-        const float s_w = sqrtf(1.0f / (2.0f * (float)w));
-        const float s_h = sqrtf(1.0f / (2.0f * (float)h));
-        for (int fr = 0; fr < 2; ++fr)
-            for (int fc = 0; fc < 2; ++fc) {
-                volatile float sc = 1.0f;
-                sc = sc * (fr ? s_k0_w : s_w);
-                sc = sc * (fc ? s_k0_h : s_h);
-                kp.s[fr][fc] = sc;
-            }
-    }
+    select_ortho_scales(w, h, kp.s);
     const unsigned stride_s = sample_stride_for(k);
     const size_t groups = (plane_len + stride_s * 4 - 1) / (stride_s * 4);
     size_t sb = (groups + 256 * 2 - 1) / (256 * 2);

@@ -124,12 +124,15 @@ struct Xform {
     // natural order (the compact plane of the pruned transform has its own)
     size_t full_h = 0;
     bool natural_order = false;
+    // fused forward transform of a base reader whose plane feeds only the selection of the first k keys and reads at those
+    // indices (batch extract): the column pass in two phases on the tiles that can hold one (base_prune.hip)
+    const BasePrune* base_prune = nullptr;
 };
 int build_transform(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, Chain& ch, bool* fused_rgb = nullptr);
 bool can_fuse_rgb(const ssw_ctx* ctx, bool f64, size_t w, size_t h, const float* y, const float* tmp, const void* rgb, int u8);
 // rgb -> Y (+ I, Q) -> forward transform of Y into `y` (Writer::new / Reader::new_impl), fused where possible
 int build_forward_from_rgb(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, int u8, size_t n, size_t w,
-                           size_t h, float* y, float* i, float* q, float* tmp, Chain& ch);
+                           size_t h, float* y, float* i, float* q, float* tmp, Chain& ch, const BasePrune* base_prune = nullptr);
 // the same transform as bands + 1 chains: the row pass of a band of image rows (h / bands of them), and the column pass of the whole frame
 bool can_split_forward_rows(const ssw_ctx* ctx, bool f64, size_t w, size_t h, size_t bands, const float* y, const float* tmp, const void* rgb, int u8);
 int build_forward_rows_band(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, int u8, size_t w, size_t rows,
@@ -149,6 +152,10 @@ int batch_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_rgb, i
 int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base_rgb, const void* dev_derived_rgb, int u8,
                        size_t n_frames, size_t w, size_t h, size_t k, float* dev_extracted, const float* dev_marks,
                        float* dev_sims);
+
+// ssw_debug_base_prune_bound: the row pass of n f32 base frames with the energy instances, then boundkey per natural column
+int base_prune_bound_impl(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_rgb, size_t n_frames, size_t w, size_t h, size_t k,
+                          float* dev_bound);
 
 // Tracing (ssw_fingerprint_trace; ssw_pipeline.hip).  trace_base: Reader::base of ONE frame + its first k indices into the
 // context's buffers (*y, *idx), enqueued on the context's stream.  trace_extract: base.extract(Reader::derived(suspect_s), k)

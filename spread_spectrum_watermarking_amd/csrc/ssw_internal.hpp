@@ -106,7 +106,15 @@ int launch_dct_pair_prep8_cols(hipStream_t st, const float* in, size_t n_frames,
 //                    `cop`; needs the rotation tables of H, H/2, H/4
 //   FUSE_COLS        column launch behind such a row pass: its 128-line tiles are in the row launches' class-major order
 enum { FUSE_ROWS_COP = 1, FUSE_COLS = 2 };
-struct FuseCols { int mode = 0; double* cop = nullptr; const double *rot1 = nullptr, *rot2 = nullptr, *rot3 = nullptr; };
+struct FuseCols {
+    int mode = 0; double* cop = nullptr; const double *rot1 = nullptr, *rot2 = nullptr, *rot3 = nullptr;
+    // base-reader pruning (base_prune.hip).  Row launch: `energy` [n][W] receives the sum of squares of every column-operand
+    // line's f32 row-pass values (atomic adds; zeroed by the caller).  Column launch: `tile_mode` 1 runs the blocks of
+    // column tile 0 of every frame only, 2 the blocks of the tiles t > 0 whose need[frame * (W / 128) + t] is set.
+    float* energy = nullptr;
+    const unsigned* need = nullptr;
+    int tile_mode = 0;
+};
 // one or several classes (same lines, same template instance) in one launch: the class (dct_pair_class.hpp) with its operand
 // and basis planes; sink (last inverse column pass): colour conversion in the epilogue
 struct PairClassDesc { PairClass cls; const double *x1, *x2, *y1, *y2; };
@@ -131,7 +139,7 @@ int launch_dct_pair_gemm_rows_subset_merged_f64(hipStream_t st, const PairSubset
 size_t dct_pair_split_kpad(size_t len);
 // tuning.hip: the process-wide table of strategy thresholds / A-B switches (ssw_tuning_set, include/ssw.h)
 enum { TUNE_EFOLD_MIN, TUNE_EFOLD_INV_MIN, TUNE_EFOLD_COLS_MIN, TUNE_CLASS_TILE, TUNE_DEEP_MIN_ROWS, TUNE_DEEP_MIN_COLS, TUNE_PREP_STAGED,
-       TUNE_MERGE_MAX_LINES, TUNE_BN32, TUNE_BAND_SPLIT, TUNE_FUSE_COLS, TUNE_UPLOAD_BANDS, TUNE_SPECULATE_K, TUNE_PREP_LIGHT, TUNE_LANE_STAGGER, TUNE_DERIVED_FUSED, TUNE_TILE48, TUNE_COUNT };
+       TUNE_MERGE_MAX_LINES, TUNE_BN32, TUNE_BAND_SPLIT, TUNE_FUSE_COLS, TUNE_UPLOAD_BANDS, TUNE_SPECULATE_K, TUNE_PREP_LIGHT, TUNE_LANE_STAGGER, TUNE_DERIVED_FUSED, TUNE_TILE48, TUNE_BASE_PRUNE, TUNE_COUNT };
 long long tuning(int which);
 int launch_prep16_cols_l2(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
                           const double* rot1, const double* rot2, const double* rot3, bool class_major, bool in_l2, unsigned K16);
@@ -202,6 +210,32 @@ int launch_extract_pruned(hipStream_t st, const float* base, const float* compac
                           size_t cap, const uint32_t* pos, const uint32_t* indices, size_t k, int method, float alpha,
                           float* out);
 
+// base_prune.hip: the base reader's column pass only where a column can hold one of the first k keys.
+// One lane's buffers: energy [n][W] f32 | need [n][W / 128] u32; `stats` (the context's): tiles total, tiles computed,
+// frames whose second phase computed a tile.
+constexpr unsigned SSW_BASE_PRUNE_TILE = 128;
+struct BasePrune {
+    float* energy = nullptr;
+    unsigned* need = nullptr;
+    unsigned long long* stats = nullptr;
+    size_t k = 0;
+    int ordering = 0;
+    // what the second phase is billed per tile (set by the pass builder): flop and algorithmic bytes of the column launches
+    // of one computed tile, bytes of one zero-filled tile; the decide kernel adds them up in `work` [3] (doubles), so that
+    // shapes that differ from call to call are each billed at their own rate
+    double* work = nullptr;
+    double tile_flop = 0.0, tile_bytes = 0.0, zero_bytes = 0.0;
+};
+// G of boundkey(v) = G * E[v]: every key of column v is <= it (rounded up; 0: the ordering has no bound)
+float base_prune_gain(size_t w, size_t h, int ordering);
+// per frame: T = a lower bound of the k-th key among the coefficients of tile 0 (index 0 excluded), then
+// need[frame][t] = any line v of tile t with !(G * E[v] < T); frames with fewer than k keys in tile 0 need every tile
+int launch_base_prune_decide(hipStream_t st, const float* coef, const BasePrune& bp, size_t n_frames, size_t w, size_t h);
+// zero coefficients in the tiles t > 0 that are not needed (they rank behind k computed keys whatever their value)
+int launch_base_prune_zero(hipStream_t st, float* coef, const unsigned* need, size_t n_frames, size_t w, size_t h);
+// diagnostic: boundkey of every frequency column in natural order, out [n][W]
+int launch_base_prune_bound(hipStream_t st, const float* energy, size_t n_frames, size_t w, size_t h, int ordering, float* out);
+
 // select.hip
 struct SelectWorkspace {
     uint32_t* hist = nullptr;       // [n_frames][2048] sample histogram
@@ -212,6 +246,7 @@ struct SelectWorkspace {
 };
 size_t select_cand_capacity(size_t k);   // candidate slots per frame needed for mark length k
 size_t select_max_k();
+void select_ortho_scales(size_t w, size_t h, float s[2][2]);      // EnergyOrthogonal / Legacy key scales [first_row][first_column]
 int launch_topk(hipStream_t st, const float* coef, size_t n_frames, size_t w, size_t h, int ordering,
                 size_t k, const SelectWorkspace& ws, uint32_t* indices);
 // attack.hip: 8-bit boundary + CatmullRom resize (third-party `image` crate semantics)
@@ -302,6 +337,7 @@ struct ssw_ctx {
         Buf compact[2];           // pruned derived transform: row-pass result, column-pass result [chunk][H][cap]
         Buf gathered;             // gathered half bases of the chunk's frequency classes
         Buf prune_u32;            // flag [W] | pos [W] | rows [cap] | info [8]
+        Buf base_prune;           // base-reader pruning: energy [chunk][W] f32 | need [chunk][W / 128] u32
         hipStream_t cur = nullptr;   // stream the lane's chain currently runs on
         hipEvent_t done = nullptr;   // recorded right after the lane's latest stage (borrowed from sync_events)
     };
@@ -316,6 +352,10 @@ struct ssw_ctx {
     Buf overflow;                         // [chunks] u32 flags of the pruned path (+ class counts)
     uint64_t pruned_chunks = 0, redone_chunks = 0;
     uint64_t pruned_columns = 0;          // sum over pruned chunks of the compact plane width (cap_total)
+    // base-reader pruning: device counters (u64: tiles total, tiles computed, frames extended, spare; then doubles: flop and
+    // bytes of the second phase's column launches, bytes of the zero-fill) and what flush_timers has already billed of the doubles
+    Buf base_prune_stats;
+    double base_prune_billed[3] = {0.0, 0.0, 0.0};
     // single-image handles (ssw_lib.hip): frames cross PCIe on `copy_stream` into / out of two alternating
     // device staging buffers, so the upload of the next frame runs beside the kernels of the previous one
     hipStream_t copy_stream = nullptr;

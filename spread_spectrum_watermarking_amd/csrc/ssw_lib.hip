@@ -382,10 +382,12 @@ int ssw_ctx_destroy(ssw_ctx* ctx) {
         release(ln.idx);
         release(ln.gathered);
         release(ln.prune_u32);
+        release(ln.base_prune);
         release_select(ln.sel);
     }
     if (ctx->select_fallbacks) (void)hipFree(ctx->select_fallbacks);
     release(ctx->overflow);
+    release(ctx->base_prune_stats);
     release(ctx->small);
     release(ctx->sort_scratch);
     release(ctx->resize_tmp);
@@ -475,6 +477,8 @@ int ssw_ctx_reset_timing(ssw_ctx* ctx) {
     SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) SSW_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
     SSW_HIP_CHECK(hipMemset(ctx->select_fallbacks, 0, sizeof(uint32_t)));
+    if (ctx->base_prune_stats.p) SSW_HIP_CHECK(hipMemset(ctx->base_prune_stats.p, 0, 8 * sizeof(unsigned long long)));
+    for (double& b : ctx->base_prune_billed) b = 0.0;
     return SSW_OK;
 }
 
@@ -529,6 +533,27 @@ int ssw_ctx_get_prune_stats(ssw_ctx* ctx, uint64_t* stats) {
     stats[1] = ctx->redone_chunks;
     stats[2] = ctx->pruned_columns;
     return SSW_OK;
+}
+
+int ssw_ctx_get_base_prune_stats(ssw_ctx* ctx, uint64_t* stats) {
+    if (!ctx || !stats) return SSW_ERR_BAD_ARG;
+    CtxGuard g(ctx);
+    stats[0] = stats[1] = stats[2] = 0;
+    if (!ctx->base_prune_stats.p) return SSW_OK;
+    SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (ctx->aux_stream) SSW_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
+    unsigned long long v[4] = {0, 0, 0, 0};
+    SSW_HIP_CHECK(hipMemcpy(v, ctx->base_prune_stats.p, sizeof(v), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) stats[i] = v[i];
+    return SSW_OK;
+}
+
+int ssw_debug_base_prune_bound(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_rgb, size_t n_frames, size_t w, size_t h,
+                               size_t k, float* dev_bound) {
+    if (!ctx || !dev_rgb || !dev_bound) return SSW_ERR_BAD_ARG;
+    SSW_TRY(check_config(cfg));
+    CtxGuard g(ctx);
+    return base_prune_bound_impl(ctx, cfg, dev_rgb, n_frames, w, h, k, dev_bound);
 }
 
 int ssw_ctx_get_select_stats(ssw_ctx* ctx, uint64_t* stats) {

@@ -180,6 +180,21 @@ int flush_timers(ssw_ctx* ctx) {
     used.erase(std::unique(used.begin(), used.end()), used.end());
     for (hipEvent_t e : used) ctx->free_events.push_back(e);
     ctx->tail_event = nullptr; ctx->tail_fresh = false;
+    // base-reader pruning: the second phase's share of the column launches is known to the device only -- its tiles are
+    // billed here, from the decide kernels' counter (computed tiles beyond every frame's tile 0, which the host billed)
+    // (each frame at its own shape's rate: the kernels add flop and bytes up as doubles; what was enqueued while the timers
+    // were off is passed over, like every other stage's work)
+    if (ctx->base_prune_stats.p) {
+        double wk[3] = {0.0, 0.0, 0.0};
+        SSW_HIP_CHECK(hipMemcpy(wk, (const char*)ctx->base_prune_stats.p + 4 * sizeof(unsigned long long), sizeof(wk), hipMemcpyDeviceToHost));
+        if (ctx->timing) {
+            ctx->stage_work[SSW_STAGE_DCT_COL] += wk[0] - ctx->base_prune_billed[0];
+            ctx->stage_bytes[SSW_STAGE_DCT_COL] += wk[1] - ctx->base_prune_billed[1];
+            ctx->stage_work[SSW_STAGE_SELECT] += wk[2] - ctx->base_prune_billed[2];       // (an HBM-bound stage: its bytes are its work)
+            ctx->stage_bytes[SSW_STAGE_SELECT] += wk[2] - ctx->base_prune_billed[2];
+        }
+        for (int i = 0; i < 3; ++i) ctx->base_prune_billed[i] = wk[i];
+    }
     return SSW_OK;
 }
 
@@ -542,6 +557,9 @@ int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     SSW_TRY(deep_rot(b, true, &rot2, &rot3));
     const size_t n = b.n, w = b.w, h = b.h;
     FuseCols fc;
+    // base reader of a batch extract: the row launches add up the column energies, the column pass runs in two phases
+    const bool bprune = fused && b.x.base_prune != nullptr;
+    BasePrune bp = bprune ? *b.x.base_prune : BasePrune();
     double pad = 1.0;                                             // the padding units' share of the flop
     double bytes = b.gemm_bytes(0.0);
     float* out = b.dst;
@@ -560,6 +578,7 @@ int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
             pp.l2_plane = lpad * dct_pair_split_kpad(b.len / 2);
             pad = (double)lpad / (double)(n * h);
             fc = FuseCols{FUSE_ROWS_COP, cop, (const double*)crot1, (const double*)crot2, (const double*)crot3};
+            if (bprune) fc.energy = bp.energy;
             bytes = b.px * 16.0;                                // row operands in, column operands out
             out = nullptr;
         }
@@ -576,7 +595,40 @@ int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     const double f_main = b.flop(PairClass::O5), f_all = 8.0 * f_main;      // (every class: the same pairs and sum length)
     std::array<PairClassDesc, 8> d;
     for (int c = 0; c < 8; ++c) SSW_TRY(deep_desc(b, pp, true, kLevel2Classes[c], d[c]));
+    if (bprune && !b.is_row) {
+        // phase 1: tile 0 of every frame (one launch over the eight classes: 3 blocks per frame and class); decide; phase 2:
+        // the tiles that can hold one of the first k keys, the others zero-filled (base_prune.hip).  The host bills phase 1;
+        // phase 2's tiles are billed from the device counter when the timers are resolved (flush_timers).
+        const double tiles = (double)(w / SSW_BASE_PRUNE_TILE);
+        bp.tile_flop = f_all / ((double)n * tiles);
+        bp.tile_bytes = bytes / ((double)n * tiles);
+        bp.zero_bytes = (double)h * SSW_BASE_PRUNE_TILE * 4.0;
+        auto phase = [=](hipStream_t st, int mode) {
+            FuseCols f2 = fc;
+            f2.tile_mode = mode; f2.need = bp.need;
+            return launch_dct_pair_gemm_multi_f64(st, false, false, 8, d.data(), out, nullptr, n, w, h, b.ep, nullptr, nullptr, b.gemm_layout(), &f2);
+        };
+        ch.push_back({false, [=](hipStream_t st) -> int {
+            StageTimer t(ctx, b.st_pass, st, f_all / tiles);
+            t.traffic(bytes / tiles);
+            return phase(st, 1);
+        }});
+        ch.push_back({true, [=](hipStream_t st) -> int {
+            StageTimer t(ctx, SSW_STAGE_SELECT, st, (double)n * ((double)h * SSW_BASE_PRUNE_TILE + (double)w) * 4.0);
+            SSW_TRY(launch_base_prune_decide(st, out, bp, n, w, h));
+            return launch_base_prune_zero(st, out, bp.need, n, w, h);
+        }});
+        ch.push_back({false, [=](hipStream_t st) -> int {
+            StageTimer t(ctx, b.st_pass, st, 0.0);
+            return phase(st, 2);
+        }});
+        return SSW_OK;
+    }
     ch.push_back({false, [=](hipStream_t st) -> int {
+        if (bprune) {           // (row pass) the energies start at zero
+            SSW_HIP_CHECK(hipMemsetAsync(bp.energy, 0, n * w * sizeof(float), st));
+            untimed_work(ctx);
+        }
         StageTimer t(ctx, b.st_pass, st, f_all * pad, b.p.merge ? b.st_main : -1);      // (merged: a single frame's eight classes in one launch)
         t.traffic(bytes);
         auto launch = [&](int nc, const PairClassDesc* dd) {
@@ -781,9 +833,10 @@ bool can_fuse_rgb(const ssw_ctx* ctx, bool f64, size_t w, size_t h, const float*
 // Where the default GEMM strategy applies (rows first, two folding levels on the row axis) the colour
 // conversion is fused into the first operand pre-pass and the f32 Y plane is never materialised.
 int build_forward_from_rgb(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, int u8, size_t n, size_t w,
-                           size_t h, float* y, float* i, float* q, float* tmp, Chain& ch) {
+                           size_t h, float* y, float* i, float* q, float* tmp, Chain& ch, const BasePrune* base_prune) {
     const bool f64 = precision == SSW_PRECISION_F64;
     Xform x{SSW_DCT2, precision, n, w, h, y, tmp};
+    x.base_prune = base_prune;
     if (can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, u8)) {
         x.rgb = rgb; x.rgb_u8 = u8; x.iq_i = i; x.iq_q = q;
         return build_transform(ctx, ws, x, ch);
@@ -1296,6 +1349,23 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
                                            (const float*)ctx->lane[0].plane[2].p, dev_derived_rgb, u8);
     if (ps.on) SSW_TRY(grow(ctx->overflow, n_chunks * SSW_PRUNE_INFO * sizeof(uint32_t)));
     uint32_t* overflow = (uint32_t*)ctx->overflow.p;
+    // Base-reader pruning (base_prune.hip): where the planner takes the fused forward transform for the chunks of this call
+    // and the ordering has a key bound.  ssw_ctx_set_prune(0) and the tuning entry base_prune = 0 give the full transform.
+    const size_t bp_tiles = w / SSW_BASE_PRUNE_TILE;
+    bool base_prune = ctx->prune && tuning(TUNE_BASE_PRUNE) != 0 && f64 && k > 0 && k <= select_max_k() && w % SSW_BASE_PRUNE_TILE == 0 && bp_tiles >= 2 &&
+                      base_prune_gain(w, h, c.ordering) > 0.0f && w >= h &&
+                      can_fuse_rgb(ctx, f64, w, h, (const float*)ctx->lane[0].plane[0].p, (const float*)ctx->lane[0].plane[2].p, dev_base_rgb, u8);
+    for (size_t f0 = 0; base_prune && f0 < n_frames; f0 += chunk) {      // (the last chunk may be shorter: another plan)
+        const size_t n = std::min(chunk, n_frames - f0);
+        const PlanInput in{SSW_DCT2, c.precision, n, w, h, 0, false, true, plan_settings(ctx)};
+        base_prune = n <= plan_frame_limit(plan_settings(ctx), f64, w, h) && plan_pass(in, true, true).strategy == PassStrategy::FusedRows &&
+                     plan_pass(in, false, false).strategy == PassStrategy::FusedCols;
+    }
+    if (base_prune && !ctx->base_prune_stats.p) {
+        SSW_TRY(grow(ctx->base_prune_stats, 8 * sizeof(unsigned long long)));
+        SSW_HIP_CHECK(hipMemsetAsync(ctx->base_prune_stats.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
+        untimed_work(ctx);
+    }
 
     // extract + similarity of one chunk from full coefficient planes (the un-pruned path and the redo)
     auto full_derived = [&](ssw_ctx::Lane& ws, size_t f0, size_t n, float* yb, float* tmp, uint32_t* idx, Chain& ch) -> int {
@@ -1328,8 +1398,18 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         uint32_t* idx = (uint32_t*)ws.idx.p;
         const char* brgb = static_cast<const char*>(dev_base_rgb) + f0 * plane * px_bytes;
         SelectWorkspace* sel = &ws.sel;
+        BasePrune bp;
+        if (base_prune) {
+            const size_t e_bytes = chunk * w * sizeof(float);
+            SSW_TRY(grow(ws.base_prune, e_bytes + chunk * bp_tiles * sizeof(unsigned)));
+            bp.energy = (float*)ws.base_prune.p;
+            bp.need = (unsigned*)((char*)ws.base_prune.p + e_bytes);
+            bp.stats = (unsigned long long*)ctx->base_prune_stats.p;
+            bp.work = (double*)(bp.stats + 4);
+            bp.k = k; bp.ordering = c.ordering;
+        }
         // Reader::base (:474-480): only the Y plane is ever used by a reader
-        SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, brgb, u8, n, w, h, yb, nullptr, nullptr, tmp, ch));
+        SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, brgb, u8, n, w, h, yb, nullptr, nullptr, tmp, ch, base_prune ? &bp : nullptr));
         if (k > 0)
             ch.push_back({true, [=](hipStream_t st) -> int { return topk(ctx, st, *sel, yb, n, w, h, c.ordering, k, idx); }});   // :493
         if (!pruned) return full_derived(ws, f0, n, yb, tmp, idx, ch);
@@ -1371,6 +1451,37 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         SSW_TRY(run_serial(ch, ctx->stream));
     }
     return SSW_OK;
+}
+
+// ssw_debug_base_prune_bound: what the decide kernel compares, for tests -- the chunk's forward transform as the batch
+// path builds it (so the energies are the ones it would use), then G * E per natural column
+int base_prune_bound_impl(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_rgb, size_t n_frames, size_t w, size_t h, size_t k,
+                          float* dev_bound) {
+    const ssw_config c = *cfg;
+    const bool f64 = c.precision == SSW_PRECISION_F64;
+    if (w == 0 || h == 0) return SSW_ERR_BAD_DIMS;
+    if (n_frames == 0) return SSW_OK;
+    const size_t plane = w * h, tiles = w / SSW_BASE_PRUNE_TILE;
+    ssw_ctx::Lane& ws = ctx->lane[0];
+    for (int p : {0, 2}) SSW_TRY(grow(ws.plane[p], n_frames * plane * sizeof(float)));
+    const PlanInput in{SSW_DCT2, c.precision, n_frames, w, h, 0, false, true, plan_settings(ctx)};
+    if (!f64 || k == 0 || k >= plane || w % SSW_BASE_PRUNE_TILE != 0 || tiles < 2 || w < h || !(base_prune_gain(w, h, c.ordering) > 0.0f) ||
+        !can_fuse_rgb(ctx, f64, w, h, (const float*)ws.plane[0].p, (const float*)ws.plane[2].p, dev_rgb, SSW_PIX_F32) ||
+        n_frames > plan_frame_limit(plan_settings(ctx), f64, w, h) || plan_pass(in, true, true).strategy != PassStrategy::FusedRows ||
+        plan_pass(in, false, false).strategy != PassStrategy::FusedCols)
+        return SSW_ERR_UNSUPPORTED;
+    const size_t e_bytes = n_frames * w * sizeof(float);
+    SSW_TRY(grow(ws.base_prune, e_bytes + n_frames * tiles * sizeof(unsigned)));
+    BasePrune bp;
+    bp.energy = (float*)ws.base_prune.p;
+    bp.need = (unsigned*)((char*)ws.base_prune.p + e_bytes);
+    bp.k = k; bp.ordering = c.ordering;
+    Chain ch;
+    SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_rgb, SSW_PIX_F32, n_frames, w, h, (float*)ws.plane[0].p, nullptr, nullptr,
+                                   (float*)ws.plane[2].p, ch, &bp));
+    SSW_TRY(run_serial(ch, ctx->stream));
+    untimed_work(ctx);
+    return launch_base_prune_bound(ctx->stream, bp.energy, n_frames, w, h, c.ordering, dev_bound);
 }
 
 // ---- one base frame against many suspect frames (ssw_fingerprint_trace) -----------------------------------------

@@ -39,6 +39,7 @@ Entry g_tune[TUNE_COUNT] = {
     {"lane_stagger", "SSW_LANE_STAGGER", 1},           // two lanes: RGB pre-passes beside the other lane's column launches, not its row launches (r5: +0.7 %)
     {"derived_fused", "SSW_DERIVED_FUSED", 1},         // the derived frame's pruned row pass in one kernel (marks of up to 1024 entries; 0: pre-pass + launches)
     {"tile48", "SSW_TILE48", 1},                       // r6: 48-pair tiles for classes whose 64-pair tiling ends in a tile of <= 16 pairs (135 = 48 + 48 + 39)
+    {"base_prune", "SSW_BASE_PRUNE", 1},               // batch extract: the base frame's column pass only on the 128-column tiles that can hold a top-k key
 };
 
 // value and state change together under this lock (first read from the environment, set, reset); the fast path of a reader
