@@ -176,7 +176,7 @@ int ssw_ctx_get_prune_stats(ssw_ctx* ctx, uint64_t* stats);
 /* Base-reader pruning of ssw_batch_extract* (on with ssw_ctx_set_prune and the tuning entry "base_prune", both default
    on; f64, Energy / EnergyOrthogonal, shapes whose forward transform is the fused one): the base frame's column pass runs
    on the 128-column tiles that can hold one of the first k keys -- tile 0, then the tiles whose per-column energy bound
-   reaches the k-th key of tile 0 -- and the other tiles are zero-filled; outputs are bit-identical to the full transform.
+   reaches the k-th key of tile 0 -- and the selection reads those tiles only; outputs are bit-identical to the full transform.
    stats[0] column tiles of the base frames, [1] of those computed, [2] frames whose second phase computed a tile; counted
    on the device since the last ssw_ctx_reset_timing.  Synchronises. */
 int ssw_ctx_get_base_prune_stats(ssw_ctx* ctx, uint64_t* stats);
@@ -185,6 +185,12 @@ int ssw_ctx_get_base_prune_stats(ssw_ctx* ctx, uint64_t* stats);
    apply to the shape / configuration.  Enqueues on the context's stream. */
 int ssw_debug_base_prune_bound(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_rgb, size_t n_frames, size_t w, size_t h,
                                size_t k, float* dev_bound);
+/* Diagnostic: the top-k selection under a tile mask, as the pruned base reader runs it.  dev_need [n][w / 128] (u32; null: no
+   mask): a 128-column tile whose flag is 0 is never read and its elements count as +0.0f.  cand_cap: candidate slots per
+   frame (0: the default; fewer than k sends every frame through the exact whole-plane select).  dev_indices [n][k].
+   Enqueues on the context's stream. */
+int ssw_debug_select_masked(ssw_ctx* ctx, const float* dev_coef, size_t n_frames, size_t w, size_t h, int ordering, size_t k,
+                            const uint32_t* dev_need, size_t cand_cap, uint32_t* dev_indices);
 /* Top-k selection (the first k entries of the ordering of src/algorithm.rs:200-280): stats[0] frames selected, [1] of
    those whose sampled threshold left fewer than k or more than the candidate buffer's survivors, so that the finish ran
    the exact select over the whole plane (same result, one CU sorting the plane: a latency cliff; massive ties and

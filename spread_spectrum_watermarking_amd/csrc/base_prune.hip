@@ -13,8 +13,8 @@
 // file's kernel takes T = a lower bound of the k-th largest key among tile 0's coefficients and marks the tiles t > 0
 // that hold a column with !(boundkey < T); the second phase computes those.  A skipped coefficient has key <= boundkey <
 // T <= the k-th computed key, strictly: at least k computed keys rank ahead of it, ties included, so the first k
-// entries of the order do not depend on its value -- the skipped tiles are filled with zeros (key 0 < T) and the
-// selection runs on the plane as before.  NaN / Inf energies compare "needed"; a frame with fewer than k keys in tile 0,
+// entries of the order do not depend on its value -- the skipped tiles are left as they are (stale workspace) and the
+// selection takes the flags as a tile mask (select.hip): it reads computed tiles only.  NaN / Inf energies compare "needed"; a frame with fewer than k keys in tile 0,
 // or whose T is not positive, needs every tile.  Legacy ordering (signed keys) has no bound and takes the full path.
 #include <algorithm>
 #include <cmath>
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(BP_THREADS) void base_prune_decide_kernel(const flo
                                                                        unsigned W, unsigned H, BpKey kp, unsigned k,
                                                                        unsigned* __restrict__ need, unsigned long long* __restrict__ stats,
                                                                        double* __restrict__ work, double tile_flop, double tile_bytes,
-                                                                       double zero_bytes) {
+                                                                       double select_bytes) {
     __shared__ unsigned hist[BP_BINS];
     __shared__ unsigned part[BP_THREADS / 64];
     __shared__ float t_sh;
@@ -109,25 +109,15 @@ __global__ __launch_bounds__(BP_THREADS) void base_prune_decide_kernel(const flo
         unsigned computed = 0;
         for (unsigned t = 0; t < tiles; ++t) computed += nd[t];
         if (work) {                                            // (the host billed tile 0 of every frame)
-            if (computed > 1) { atomicAdd(&work[0], (computed - 1) * tile_flop); atomicAdd(&work[1], (computed - 1) * tile_bytes); }
-            if (computed < tiles) atomicAdd(&work[2], (tiles - computed) * zero_bytes);
+            if (computed > 1) {
+                atomicAdd(&work[0], (computed - 1) * tile_flop); atomicAdd(&work[1], (computed - 1) * tile_bytes);
+                atomicAdd(&work[2], (computed - 1) * select_bytes);
+            }
         }
         atomicAdd(&stats[0], (unsigned long long)tiles);
         atomicAdd(&stats[1], (unsigned long long)computed);
         if (any_sh) atomicAdd(&stats[2], 1ull);
     }
-}
-
-// grid (frames * tiles, row groups)
-__global__ __launch_bounds__(256) void base_prune_zero_kernel(float* __restrict__ coef, const unsigned* __restrict__ need, unsigned W,
-                                                              unsigned H, unsigned tiles) {
-    const unsigned ft = blockIdx.x;
-    if (need[ft] != 0u) return;
-    const unsigned f = ft / tiles, t = ft - f * tiles;
-    float* p = coef + (size_t)f * W * H + (size_t)t * SSW_BASE_PRUNE_TILE;
-    const unsigned qx = 4 * (threadIdx.x & 31u), ry = threadIdx.x >> 5;
-    for (unsigned y = blockIdx.y * 8 + ry; y < H; y += gridDim.y * 8)
-        *reinterpret_cast<f32x4*>(p + (size_t)y * W + qx) = (f32x4){0.f, 0.f, 0.f, 0.f};
 }
 
 __global__ __launch_bounds__(256) void base_prune_bound_kernel(const float* __restrict__ energy, unsigned W, size_t total, float gain,
@@ -174,18 +164,7 @@ int launch_base_prune_decide(hipStream_t st, const float* coef, const BasePrune&
     const BpKey kp = make_key(w, h, bp.ordering);
     if (!(kp.gain > 0.0f)) return SSW_ERR_BAD_ARG;
     base_prune_decide_kernel<<<(unsigned)n_frames, BP_THREADS, 0, st>>>(coef, bp.energy, (unsigned)w, (unsigned)h, kp, (unsigned)bp.k, bp.need,
-                                                                       bp.stats, bp.work, bp.tile_flop, bp.tile_bytes, bp.zero_bytes);
-    SSW_HIP_CHECK(hipGetLastError());
-    return SSW_OK;
-}
-
-int launch_base_prune_zero(hipStream_t st, float* coef, const unsigned* need, size_t n_frames, size_t w, size_t h) {
-    if (n_frames == 0) return SSW_OK;
-    const size_t tiles = w / SSW_BASE_PRUNE_TILE;
-    if (!coef || !need || w % SSW_BASE_PRUNE_TILE != 0 || n_frames * tiles > 0x7FFFFFFFull || (reinterpret_cast<uintptr_t>(coef) & 15) != 0)
-        return SSW_ERR_BAD_ARG;
-    const unsigned gy = (unsigned)std::min<size_t>((h + 7) / 8, 16);
-    base_prune_zero_kernel<<<dim3((unsigned)(n_frames * tiles), gy), 256, 0, st>>>(coef, need, (unsigned)w, (unsigned)h, (unsigned)tiles);
+                                                                       bp.stats, bp.work, bp.tile_flop, bp.tile_bytes, bp.select_bytes);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }

@@ -86,7 +86,9 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     if (small)                                                     // 48-pair tiles are three pair tiles of a 128-line block
         for (int c = 0; c < n_classes; ++c)
             if (ml.c[c].bn32 == 2) { tiles_n -= ml.c[c].tiles_n; ml.c[c].bn32 = 0; ml.c[c].tiles_n = (ml.c[c].NP + 63) / 64; tiles_n += ml.c[c].tiles_n; }
-    const unsigned tiles_m = (L + BM - 1) / BM;
+    // (phase 1 of a pruned base reader computes one 128-line tile per frame: its grid is that small, the kernel maps it)
+    const bool tile0_grid = fuse_cols && fuse->tile_mode == 1;
+    const unsigned tiles_m = tile0_grid ? (unsigned)n_frames : (L + BM - 1) / BM;
     // ... and 32-pair tiles when that spreads such a (single-class) launch more evenly over the 256 CUs (all its blocks are
     // resident at once, so a launch takes as long as the fullest CU): balance = blocks / (256 * ceil(blocks / 256)); the
     // smaller tiles reuse their basis fragments less, hence the 8 % handicap

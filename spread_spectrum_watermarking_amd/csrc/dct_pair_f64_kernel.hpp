@@ -117,10 +117,12 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
     tile_of_block(blockIdx.x, gridDim.x, ml.tiles_m, ml.tiles_n_total, tm, tn);
     while (cls + 1 < ml.n_classes && tn >= ml.c[cls].tiles_n) { tn -= ml.c[cls].tiles_n; ++cls; }      // block-uniform
     if constexpr (COLS && EPI == EPI_FWD && BM == 128 && SUB >= 10) {
-        // pruned base reader (its own instance, SUB 13: every other column launch is the kernel it was): phase 1 computes column tile 0 of every frame, phase 2 the other tiles that are needed; a block
-        // of any other tile returns before it has issued a load (tm is block-uniform: the flag is a scalar load)
-        const unsigned t = tm % ml.need_tpf;
-        if (ml.need_mode == 1 ? t != 0 : (t == 0 || ml.need[tm] == 0)) return;
+        // pruned base reader (its own instance, SUB 13: every other column launch is the kernel it was).  Phase 1 computes column
+        // tile 0 of every frame: its grid has one line tile per frame (ml.tiles_m = frames).  Phase 2 runs over every line tile
+        // and computes the other tiles that are needed; a block of any other tile returns before it has issued a load (tm is
+        // block-uniform: the flag is a scalar load)
+        if (ml.need_mode == 1) tm *= ml.need_tpf;
+        else if (tm % ml.need_tpf == 0 || ml.need[tm] == 0) return;
     }
     const PairClassArgs& ca = ml.c[cls];
     const double* __restrict__ X1g = ca.x1;

@@ -49,6 +49,8 @@ constexpr size_t MAX_K = 16384;                 // 128 KiB of LDS for the in-blo
 constexpr unsigned SAMPLE_STRIDE = 64, SAMPLE_STRIDE_MID = 128, SAMPLE_STRIDE_LONG = 256;
 static inline unsigned sample_stride_for(size_t k) { return k >= 8192 ? SAMPLE_STRIDE_LONG : k >= 4096 ? SAMPLE_STRIDE_MID : SAMPLE_STRIDE; }
 constexpr unsigned FINISH_THREADS = 1024;
+constexpr unsigned SELECT_MASK_TILE = 128;      // columns per flag of a tile mask (launch_topk's `need`)
+static_assert(SELECT_MASK_TILE == SSW_BASE_PRUNE_TILE, "the mask is the base reader's tile map");
 
 size_t select_max_k() { return MAX_K; }
 size_t select_cand_capacity(size_t k) { size_t c = 16 * k; return c < 65536 ? 65536 : c; }
@@ -148,8 +150,13 @@ __device__ inline void find_threshold_digit(const uint32_t* h, uint32_t m, uint3
     }
 }
 
+// MASKED (the base frame of a pruned batch extract, base_prune.hip): need[frame][W / 128] flags the 128-column tiles of the
+// plane that were computed; a quad of another tile is stale workspace and is not loaded.  The sample positions stay the same
+// function of (group, frame): what the histogram loses against a zero-filled plane sat in the bin of key +0.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void select_sample_kernel(const float* __restrict__ coef, size_t plane_len,
-                                                            KeyParams kp, uint32_t* __restrict__ hist, unsigned sample_stride) {
+                                                            KeyParams kp, uint32_t* __restrict__ hist, unsigned sample_stride,
+                                                            const unsigned* __restrict__ need, unsigned tiles) {
     __shared__ uint32_t lh[NBINS];
     const size_t f = blockIdx.y;
     for (int i = threadIdx.x; i < NBINS; i += blockDim.x) lh[i] = 0;
@@ -162,6 +169,7 @@ __global__ __launch_bounds__(256) void select_sample_kernel(const float* __restr
     for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < groups; g += stride) {
         const size_t j0 = g * GROUP + 4 * (mix32((uint32_t)g * 0x9E3779B1u + (uint32_t)f) & (GROUP / 4 - 1));
         if (j0 >= plane_len) continue;
+        if (MASKED && need[f * tiles + ((uint32_t)j0 % kp.w) / SELECT_MASK_TILE] == 0u) continue;      // (one division per group of 64 quads)
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         unsigned cnt = 0;
         if (vec) {
@@ -183,11 +191,15 @@ __global__ __launch_bounds__(256) void select_sample_kernel(const float* __restr
 // 3. the one full pass over the plane: append every coefficient whose top digit >= threshold.
 // ENERGY ordering (the default; keys c*c >= 0, so digit order = float order): the test is one multiply and
 // one float compare against the threshold digit's lower edge, two 16-byte loads in flight per thread.
-template <bool ENERGY>
+// MASKED: only the needed tiles are read.  A half wave owns one 512-byte row piece of a needed tile at a time (the block's
+// list of needed tiles in LDS, 256 tiles of the row per round): rows and tiles come from loop counters, the only divisions
+// are the few per thread that spread the eight half waves over rows when a frame needs fewer than eight tiles.
+template <bool ENERGY, bool MASKED>
 __global__ __launch_bounds__(256) void select_compact_kernel(const float* __restrict__ coef, size_t plane_len,
                                                              KeyParams kp, uint32_t* __restrict__ ctrl,
                                                              const uint32_t* __restrict__ hist, uint32_t m,
-                                                             uint64_t* __restrict__ cand, size_t cap) {
+                                                             uint64_t* __restrict__ cand, size_t cap,
+                                                             const unsigned* __restrict__ need, unsigned tiles) {
     const size_t f = blockIdx.y;
     // 2. the threshold digit, from the frame's sample histogram: every block works it out for itself (8 KB of
     // L2-resident counts, one wave scan) instead of waiting for a separate one-block-per-frame launch
@@ -215,7 +227,47 @@ __global__ __launch_bounds__(256) void select_compact_kernel(const float* __rest
             if ((kb >> (32 - DIGIT_BITS)) >= thr && j != 0) append(j, kb);
         }
     };
-    if ((plane_len % 4 == 0) && ((reinterpret_cast<uintptr_t>(c) & 15) == 0)) {
+    if constexpr (MASKED) {
+        __shared__ unsigned short list[256];
+        __shared__ unsigned wcnt[4];
+        const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, half = tid >> 5, ql = tid & 31u;
+        const unsigned W = kp.w, H = (unsigned)(plane_len / W);
+        const unsigned* __restrict__ nd = need + f * tiles;
+        for (unsigned t0 = 0; t0 < tiles; t0 += 256) {                     // (one round up to 32768 columns)
+            const bool on = t0 + tid < tiles && nd[t0 + tid] != 0u;
+            const unsigned long long b = __ballot(on);
+            if (lane == 0) wcnt[wave] = (unsigned)__popcll(b);
+            __syncthreads();
+            unsigned before = 0, nt = 0;
+            for (unsigned w2 = 0; w2 < 4; ++w2) { before += w2 < wave ? wcnt[w2] : 0u; nt += wcnt[w2]; }
+            if (on) list[before + (unsigned)__popcll(b & ((1ull << lane) - 1ull))] = (unsigned short)tid;
+            __syncthreads();
+            // fewer than eight needed tiles: the half waves take 8 / nt rows at once (those left over idle)
+            const unsigned R = nt > 0 && nt < 8 ? 8 / nt : 1;
+            const unsigned hr = nt > 0 && nt < 8 ? half / nt : 0, hj = nt > 0 && nt < 8 ? half - hr * nt : half;
+            const unsigned G = (H + R - 1) / R;                             // row groups of the frame
+            for (unsigned g = blockIdx.x; nt > 0 && hr < R && g < G; g += 2 * gridDim.x) {      // two rows in flight per thread
+                const unsigned y0 = g * R + hr, g1 = g + gridDim.x, y1 = g1 * R + hr;
+                const bool ok0 = y0 < H, ok1 = g1 < G && y1 < H;
+                for (unsigned j = hj; j < nt; j += 8) {
+                    const unsigned x = (t0 + list[j]) * SELECT_MASK_TILE + 4 * ql;
+                    const uint32_t i0 = ok0 ? y0 * W + x : 0u, i1 = ok1 ? y1 * W + x : 0u;
+                    f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = {0.f, 0.f, 0.f, 0.f};
+                    if (ok0) v0 = *reinterpret_cast<const f32x4*>(c + i0);
+                    if (ok1) v1 = *reinterpret_cast<const f32x4*>(c + i1);
+                    if (ok0) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) consider(i0 + e, v0[e]);
+                    }
+                    if (ok1) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) consider(i1 + e, v1[e]);
+                    }
+                }
+            }
+            __syncthreads();                                                // the list is rebuilt by the next round
+        }
+    } else if ((plane_len % 4 == 0) && ((reinterpret_cast<uintptr_t>(c) & 15) == 0)) {
         const size_t nquad = plane_len / 4;
         size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
         for (; q + stride < nquad; q += 2 * stride) {
@@ -244,7 +296,14 @@ struct CandSource {
 struct PlaneSource {                    // item i = coefficient i + 1 (DC skipped, :204)
     const float* c;
     KeyParams kp;
-    __device__ uint64_t operator()(size_t i) const { return composite_key(kp, (uint32_t)(i + 1), c[i + 1]); }
+    const unsigned* need;               // the frame's tile flags, or null: an element of a tile that was not computed counts as
+                                        // +0.0f and is not loaded (what the zero-filled plane gave it; it cannot rank among the
+                                        // first k: base_prune.hip)
+    __device__ uint64_t operator()(size_t i) const {
+        const uint32_t j = (uint32_t)(i + 1);
+        const bool have = !need || need[(j % kp.w) / SELECT_MASK_TILE] != 0u;
+        return composite_key(kp, j, have ? c[j] : 0.0f);
+    }
 };
 
 // Stable LSD radix sort, descending, of lbuf[0 .. rows * blockDim.x) in place: 8 passes of 8 bits.  (r4: the finish of
@@ -493,7 +552,7 @@ __device__ void block_select_sort(const Src& src, size_t n, size_t k, unsigned n
 __global__ __launch_bounds__(FINISH_THREADS) void select_finish_kernel(
     const float* __restrict__ coef, size_t plane_len, KeyParams kp, uint32_t* __restrict__ ctrl,
     uint32_t* __restrict__ hist, const uint64_t* __restrict__ cand, size_t cap, size_t k, unsigned n_pow2,
-    uint32_t* __restrict__ indices, uint32_t* __restrict__ fallbacks) {
+    uint32_t* __restrict__ indices, uint32_t* __restrict__ fallbacks, const unsigned* __restrict__ need, unsigned tiles) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     uint64_t* lbuf = reinterpret_cast<uint64_t*>(smem_raw);                      // max(n_pow2, blockDim.x) entries
     uint64_t* lstate = lbuf + (n_pow2 > blockDim.x ? n_pow2 : blockDim.x);       // 8 entries
@@ -509,7 +568,7 @@ __global__ __launch_bounds__(FINISH_THREADS) void select_finish_kernel(
         block_select_sort(src, n, k, n_pow2, lhist, lpart, lbuf, lstate, indices + f * k);
     } else {                                     // degenerate data: exact select over the whole plane
         if (threadIdx.x == 0 && fallbacks) atomicAdd(fallbacks, 1u);      // a latency cliff: visible in ssw_ctx_get_select_stats
-        PlaneSource src{coef + f * plane_len, kp};
+        PlaneSource src{coef + f * plane_len, kp, need ? need + f * tiles : nullptr};
         block_select_sort(src, plane_len - 1, k, n_pow2, lhist, lpart, lbuf, lstate, indices + f * k);
     }
 }
@@ -531,7 +590,7 @@ void select_ortho_scales(size_t w, size_t h, float s[2][2]) {
 }
 
 int launch_topk(hipStream_t st, const float* coef, size_t n_frames, size_t w, size_t h, int ordering,
-                size_t k, const SelectWorkspace& ws, uint32_t* indices) {
+                size_t k, const SelectWorkspace& ws, uint32_t* indices, const unsigned* need, unsigned need_tile, size_t cand_cap) {
     const size_t plane_len = w * h;
     if (n_frames == 0 || k == 0) return SSW_OK;
     if (plane_len > 0xFFFFFFFFull) return SSW_ERR_BAD_DIMS;
@@ -539,6 +598,11 @@ int launch_topk(hipStream_t st, const float* coef, size_t n_frames, size_t w, si
     if (k > MAX_K) return SSW_ERR_UNSUPPORTED;
     if (ws.frames < n_frames || ws.cap < select_cand_capacity(k)) return SSW_ERR_BAD_ARG;
     if (ordering < SSW_ORDER_ENERGY || ordering > SSW_ORDER_LEGACY) return SSW_ERR_UNSUPPORTED;
+    // a tile mask: whole 128-column tiles of 16-byte aligned rows
+    if (need && (need_tile != SELECT_MASK_TILE || w % SELECT_MASK_TILE != 0 || (reinterpret_cast<uintptr_t>(coef) & 15) != 0)) return SSW_ERR_BAD_ARG;
+    if (cand_cap > ws.cap) return SSW_ERR_BAD_ARG;
+    const size_t cap = cand_cap ? cand_cap : ws.cap;        // (a smaller candidate list: ssw_debug_select_masked)
+    const unsigned tiles = need ? (unsigned)(w / SELECT_MASK_TILE) : 0u;
 
     KeyParams kp;
     kp.ordering = ordering;
@@ -554,14 +618,19 @@ int launch_topk(hipStream_t st, const float* coef, size_t n_frames, size_t w, si
     // -4.6 sigma event, and then the exact whole-plane select still answers); at least 32 samples deep
     uint32_t m = (uint32_t)((3 * k + stride_s - 1) / stride_s);
     if (m < 32) m = 32;
-    select_sample_kernel<<<dim3((unsigned)sb, (unsigned)n_frames), 256, 0, st>>>(coef, plane_len, kp, ws.hist, stride_s);
+    if (need) select_sample_kernel<true><<<dim3((unsigned)sb, (unsigned)n_frames), 256, 0, st>>>(coef, plane_len, kp, ws.hist, stride_s, need, tiles);
+    else select_sample_kernel<false><<<dim3((unsigned)sb, (unsigned)n_frames), 256, 0, st>>>(coef, plane_len, kp, ws.hist, stride_s, nullptr, 0u);
     size_t bpf = (plane_len + 256 * 32 - 1) / (256 * 32);             // >= 32 elements per thread
     if (bpf < 1) bpf = 1;
     if (bpf > 2048) bpf = 2048;
-    if (ordering == SSW_ORDER_ENERGY)
-        select_compact_kernel<true><<<dim3((unsigned)bpf, (unsigned)n_frames), 256, 0, st>>>(coef, plane_len, kp, ws.ctrl, ws.hist, m, ws.cand, ws.cap);
+    const dim3 cgrid((unsigned)bpf, (unsigned)n_frames);
+    if (need) {
+        if (ordering == SSW_ORDER_ENERGY) select_compact_kernel<true, true><<<cgrid, 256, 0, st>>>(coef, plane_len, kp, ws.ctrl, ws.hist, m, ws.cand, cap, need, tiles);
+        else select_compact_kernel<false, true><<<cgrid, 256, 0, st>>>(coef, plane_len, kp, ws.ctrl, ws.hist, m, ws.cand, cap, need, tiles);
+    } else if (ordering == SSW_ORDER_ENERGY)
+        select_compact_kernel<true, false><<<cgrid, 256, 0, st>>>(coef, plane_len, kp, ws.ctrl, ws.hist, m, ws.cand, cap, nullptr, 0u);
     else
-        select_compact_kernel<false><<<dim3((unsigned)bpf, (unsigned)n_frames), 256, 0, st>>>(coef, plane_len, kp, ws.ctrl, ws.hist, m, ws.cand, ws.cap);
+        select_compact_kernel<false, false><<<cgrid, 256, 0, st>>>(coef, plane_len, kp, ws.ctrl, ws.hist, m, ws.cand, cap, nullptr, 0u);
     unsigned n_pow2 = 2;
     while (n_pow2 < k) n_pow2 <<= 1;
     const size_t smem = (size_t)(n_pow2 > FINISH_THREADS ? n_pow2 : FINISH_THREADS) * sizeof(uint64_t) + 8 * sizeof(uint64_t) +
@@ -578,7 +647,7 @@ int launch_topk(hipStream_t st, const float* coef, size_t n_frames, size_t w, si
         }
     }
     select_finish_kernel<<<(unsigned)n_frames, FINISH_THREADS, smem, st>>>(coef, plane_len, kp, ws.ctrl, ws.hist,
-                                                                            ws.cand, ws.cap, k, n_pow2, indices, ws.fallbacks);
+                                                                            ws.cand, cap, k, n_pow2, indices, ws.fallbacks, need, tiles);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }

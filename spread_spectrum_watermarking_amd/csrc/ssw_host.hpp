@@ -142,9 +142,10 @@ int run_serial(Chain& ch, hipStream_t st);
 // transform now, on the context's stream, with lane 0's workspace (handles, ssw_dct2d)
 int dct2d_planes(ssw_ctx* ctx, int type, int precision, size_t n, size_t w, size_t h, float* data, float* tmp);
 
-// first k entries of the reference's ordering for n planes (select.hip; full sort beyond its limit)
+// first k entries of the reference's ordering for n planes (select.hip; full sort beyond its limit).  need: the tile mask of
+// a pruned base reader (base_prune.hip), [n][w / SSW_BASE_PRUNE_TILE] -- tiles whose flag is 0 are not read
 int topk(ssw_ctx* ctx, hipStream_t st, SelectWorkspace& sel, const float* coef, size_t n, size_t w, size_t h, int ordering,
-         size_t k, uint32_t* idx);
+         size_t k, uint32_t* idx, const unsigned* need = nullptr);
 
 int batch_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_rgb, int u8_in, size_t n_frames, size_t w,
                      size_t h, const float* dev_marks, size_t k, void* dev_rgb_out, bool u8_out, float* dev_coef_out,

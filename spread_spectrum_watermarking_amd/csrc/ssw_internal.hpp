@@ -109,8 +109,8 @@ enum { FUSE_ROWS_COP = 1, FUSE_COLS = 2 };
 struct FuseCols {
     int mode = 0; double* cop = nullptr; const double *rot1 = nullptr, *rot2 = nullptr, *rot3 = nullptr;
     // base-reader pruning (base_prune.hip).  Row launch: `energy` [n][W] receives the sum of squares of every column-operand
-    // line's f32 row-pass values (atomic adds; zeroed by the caller).  Column launch: `tile_mode` 1 runs the blocks of
-    // column tile 0 of every frame only, 2 the blocks of the tiles t > 0 whose need[frame * (W / 128) + t] is set.
+    // line's f32 row-pass values (atomic adds; zeroed by the caller).  Column launch: `tile_mode` 1 is a grid over column
+    // tile 0 of every frame only, 2 runs the blocks of the tiles t > 0 whose need[frame * (W / 128) + t] is set.
     float* energy = nullptr;
     const unsigned* need = nullptr;
     int tile_mode = 0;
@@ -221,18 +221,19 @@ struct BasePrune {
     size_t k = 0;
     int ordering = 0;
     // what the second phase is billed per tile (set by the pass builder): flop and algorithmic bytes of the column launches
-    // of one computed tile, bytes of one zero-filled tile; the decide kernel adds them up in `work` [3] (doubles), so that
-    // shapes that differ from call to call are each billed at their own rate
+    // of one computed tile, bytes the masked selection reads of it; the decide kernel adds them up in `work` [3] (doubles), so
+    // that shapes that differ from call to call are each billed at their own rate
     double* work = nullptr;
-    double tile_flop = 0.0, tile_bytes = 0.0, zero_bytes = 0.0;
+    double tile_flop = 0.0, tile_bytes = 0.0, select_bytes = 0.0;
+    // set by the pass builder that enqueues the decide kernel: `need` will hold this chunk's flags, and the tiles it leaves
+    // unset are NOT written -- whoever reads the plane afterwards goes by the flags (launch_topk's mask)
+    bool* decided = nullptr;
 };
 // G of boundkey(v) = G * E[v]: every key of column v is <= it (rounded up; 0: the ordering has no bound)
 float base_prune_gain(size_t w, size_t h, int ordering);
 // per frame: T = a lower bound of the k-th key among the coefficients of tile 0 (index 0 excluded), then
 // need[frame][t] = any line v of tile t with !(G * E[v] < T); frames with fewer than k keys in tile 0 need every tile
 int launch_base_prune_decide(hipStream_t st, const float* coef, const BasePrune& bp, size_t n_frames, size_t w, size_t h);
-// zero coefficients in the tiles t > 0 that are not needed (they rank behind k computed keys whatever their value)
-int launch_base_prune_zero(hipStream_t st, float* coef, const unsigned* need, size_t n_frames, size_t w, size_t h);
 // diagnostic: boundkey of every frequency column in natural order, out [n][W]
 int launch_base_prune_bound(hipStream_t st, const float* energy, size_t n_frames, size_t w, size_t h, int ordering, float* out);
 
@@ -247,8 +248,11 @@ struct SelectWorkspace {
 size_t select_cand_capacity(size_t k);   // candidate slots per frame needed for mark length k
 size_t select_max_k();
 void select_ortho_scales(size_t w, size_t h, float s[2][2]);      // EnergyOrthogonal / Legacy key scales [first_row][first_column]
+// need (optional): per-frame tile mask need[frame][w / need_tile], need_tile = 128 columns -- a tile whose flag is 0 holds
+// stale workspace: it is not read and its elements count as +0.0f.  cand_cap (0: ws.cap): a smaller candidate list (tests).
 int launch_topk(hipStream_t st, const float* coef, size_t n_frames, size_t w, size_t h, int ordering,
-                size_t k, const SelectWorkspace& ws, uint32_t* indices);
+                size_t k, const SelectWorkspace& ws, uint32_t* indices, const unsigned* need = nullptr, unsigned need_tile = 0,
+                size_t cand_cap = 0);
 // attack.hip: 8-bit boundary + CatmullRom resize (third-party `image` crate semantics)
 struct ResizeTaps {                 // host side
     uint32_t max_taps = 0;

@@ -556,6 +556,23 @@ int ssw_debug_base_prune_bound(ssw_ctx* ctx, const ssw_config* cfg, const float*
     return base_prune_bound_impl(ctx, cfg, dev_rgb, n_frames, w, h, k, dev_bound);
 }
 
+int ssw_debug_select_masked(ssw_ctx* ctx, const float* dev_coef, size_t n_frames, size_t w, size_t h, int ordering, size_t k,
+                            const uint32_t* dev_need, size_t cand_cap, uint32_t* dev_indices) {
+    if (!ctx || !dev_coef || !dev_indices) return SSW_ERR_BAD_ARG;
+    if (!valid_ordering(ordering) || ordering == SSW_ORDER_CUSTOM) return SSW_ERR_BAD_ARG;
+    if (w == 0 || h == 0) return SSW_ERR_BAD_DIMS;
+    if (k == 0 || k > w * h - 1) return SSW_ERR_K_TOO_LARGE;
+    if (k > select_max_k()) return SSW_ERR_UNSUPPORTED;
+    CtxGuard g(ctx);
+    SelectWorkspace& sel = ctx->lane[0].sel;
+    SSW_TRY(grow_select(ctx->stream, sel, n_frames, k));
+    sel.fallbacks = ctx->select_fallbacks;
+    ctx->select_frames += n_frames;
+    untimed_work(ctx);
+    return launch_topk(ctx->stream, dev_coef, n_frames, w, h, ordering, k, sel, dev_indices, dev_need, dev_need ? SSW_BASE_PRUNE_TILE : 0u,
+                       cand_cap);
+}
+
 int ssw_ctx_get_select_stats(ssw_ctx* ctx, uint64_t* stats) {
     if (!ctx || !stats) return SSW_ERR_BAD_ARG;
     CtxGuard g(ctx);

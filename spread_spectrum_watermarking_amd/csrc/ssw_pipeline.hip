@@ -180,8 +180,9 @@ int flush_timers(ssw_ctx* ctx) {
     used.erase(std::unique(used.begin(), used.end()), used.end());
     for (hipEvent_t e : used) ctx->free_events.push_back(e);
     ctx->tail_event = nullptr; ctx->tail_fresh = false;
-    // base-reader pruning: the second phase's share of the column launches is known to the device only -- its tiles are
-    // billed here, from the decide kernels' counter (computed tiles beyond every frame's tile 0, which the host billed)
+    // base-reader pruning: the second phase's share of the column launches, and of the masked selection's reads, is known to
+    // the device only -- its tiles are billed here, from the decide kernels' counter (computed tiles beyond every frame's tile
+    // 0, which the host billed)
     // (each frame at its own shape's rate: the kernels add flop and bytes up as doubles; what was enqueued while the timers
     // were off is passed over, like every other stage's work)
     if (ctx->base_prune_stats.p) {
@@ -596,13 +597,15 @@ int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     std::array<PairClassDesc, 8> d;
     for (int c = 0; c < 8; ++c) SSW_TRY(deep_desc(b, pp, true, kLevel2Classes[c], d[c]));
     if (bprune && !b.is_row) {
-        // phase 1: tile 0 of every frame (one launch over the eight classes: 3 blocks per frame and class); decide; phase 2:
-        // the tiles that can hold one of the first k keys, the others zero-filled (base_prune.hip).  The host bills phase 1;
-        // phase 2's tiles are billed from the device counter when the timers are resolved (flush_timers).
+        // phase 1: tile 0 of every frame (one launch over the eight classes, a grid of 3 blocks per frame and class); decide;
+        // phase 2: the tiles that can hold one of the first k keys; the others are not written, and the selection that follows
+        // takes the flags as its tile mask (base_prune.hip).  The host bills phase 1; phase 2's tiles are billed from the
+        // device counter when the timers are resolved (flush_timers).
         const double tiles = (double)(w / SSW_BASE_PRUNE_TILE);
         bp.tile_flop = f_all / ((double)n * tiles);
         bp.tile_bytes = bytes / ((double)n * tiles);
-        bp.zero_bytes = (double)h * SSW_BASE_PRUNE_TILE * 4.0;
+        bp.select_bytes = (double)h * SSW_BASE_PRUNE_TILE * 4.0;
+        if (bp.decided) *bp.decided = true;
         auto phase = [=](hipStream_t st, int mode) {
             FuseCols f2 = fc;
             f2.tile_mode = mode; f2.need = bp.need;
@@ -615,8 +618,7 @@ int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
         }});
         ch.push_back({true, [=](hipStream_t st) -> int {
             StageTimer t(ctx, SSW_STAGE_SELECT, st, (double)n * ((double)h * SSW_BASE_PRUNE_TILE + (double)w) * 4.0);
-            SSW_TRY(launch_base_prune_decide(st, out, bp, n, w, h));
-            return launch_base_prune_zero(st, out, bp.need, n, w, h);
+            return launch_base_prune_decide(st, out, bp, n, w, h);
         }});
         ch.push_back({false, [=](hipStream_t st) -> int {
             StageTimer t(ctx, b.st_pass, st, 0.0);
@@ -886,8 +888,10 @@ int dct2d_planes(ssw_ctx* ctx, int type, int precision, size_t n, size_t w, size
 }
 
 int topk(ssw_ctx* ctx, hipStream_t st, SelectWorkspace& sel, const float* coef, size_t n, size_t w, size_t h, int ordering,
-         size_t k, uint32_t* idx) {
-    const double bytes = 4.0 * (double)n * (double)w * (double)h;
+         size_t k, uint32_t* idx, const unsigned* need) {
+    // (under a tile mask: tile 0 of every frame; the other needed tiles are billed from the device counter, flush_timers)
+    const double bytes = 4.0 * (double)n * (double)(need ? SSW_BASE_PRUNE_TILE : w) * (double)h;
+    if (need && k > select_max_k()) return SSW_ERR_BAD_ARG;
     if (k > select_max_k()) {
         // Beyond the in-LDS top-k limit (16384 entries; BASELINE marks are 1000 and 10000 long): the full order of
         // every plane (sort_full.hip: a batched radix sort over all frames of the call), first k entries kept.  Off
@@ -902,7 +906,7 @@ int topk(ssw_ctx* ctx, hipStream_t st, SelectWorkspace& sel, const float* coef, 
     sel.fallbacks = ctx->select_fallbacks;
     ctx->select_frames += n;
     StageTimer t(ctx, SSW_STAGE_SELECT, st, bytes);
-    return launch_topk(st, coef, n, w, h, ordering, k, sel, idx);
+    return launch_topk(st, coef, n, w, h, ordering, k, sel, idx, need, need ? SSW_BASE_PRUNE_TILE : 0u);
 }
 
 // ---- two-lane pipeline ----------------------------------------------------------------------------------
@@ -1399,7 +1403,9 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         const char* brgb = static_cast<const char*>(dev_base_rgb) + f0 * plane * px_bytes;
         SelectWorkspace* sel = &ws.sel;
         BasePrune bp;
+        bool decided = false;           // the transform below took the two-phase column pass: skipped tiles are stale
         if (base_prune) {
+            bp.decided = &decided;
             const size_t e_bytes = chunk * w * sizeof(float);
             SSW_TRY(grow(ws.base_prune, e_bytes + chunk * bp_tiles * sizeof(unsigned)));
             bp.energy = (float*)ws.base_prune.p;
@@ -1410,8 +1416,9 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         }
         // Reader::base (:474-480): only the Y plane is ever used by a reader
         SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, brgb, u8, n, w, h, yb, nullptr, nullptr, tmp, ch, base_prune ? &bp : nullptr));
+        const unsigned* mask = decided ? bp.need : nullptr;
         if (k > 0)
-            ch.push_back({true, [=](hipStream_t st) -> int { return topk(ctx, st, *sel, yb, n, w, h, c.ordering, k, idx); }});   // :493
+            ch.push_back({true, [=](hipStream_t st) -> int { return topk(ctx, st, *sel, yb, n, w, h, c.ordering, k, idx, mask); }});   // :493
         if (!pruned) return full_derived(ws, f0, n, yb, tmp, idx, ch);
         const char* drgb = static_cast<const char*>(dev_derived_rgb) + f0 * plane * px_bytes;
         SSW_TRY(build_pruned_derived(ctx, ws, drgb, u8, n, w, h, k, idx, ps, overflow + ci * SSW_PRUNE_INFO, ch));
