@@ -111,4 +111,39 @@ void prune_plan_classes(const PairClass* cls, int n, unsigned cap, PrunePlan& pl
     plan.n_classes = nc;
 }
 
+int prune_class_sources(const PairClass* cls, int n, const PassPlan& rows, size_t w, PruneClassSrc out[9]) {
+    const bool deep = plan_is_deep(rows), level2 = plan_is_level2(rows);
+    int nc = 0;
+    for (int i = 0; i < n; ++i) {
+        const PairClassRow& r = pair_class_row(cls[i]);
+        PairClassArgs ca;
+        PairInstance inst;
+        if (pair_class_args(cls[i], true, false, w, PairLayout(), false, false, false, ca, inst) != SSW_OK) return 0;
+        const signed char* pn = level2 ? r.l2x : r.l1x;
+        const bool numbered = deep || r.split;
+        const BasisKind y2 = r.y2 == BasisKind::SinELaunch ? BasisKind::SinE : r.y2;
+        const unsigned ktrue = (unsigned)(w / r.ldiv / r.k_div);
+        auto add = [&](int j, BasisKind y) {
+            const int buf = numbered ? -1 : r.samex ? (cls[i] == PairClass::OddHalf ? 1 : 0) : 2 + j;
+            PruneClassSrc& s = out[nc++] = PruneClassSrc();
+            s.p1 = pn[j]; s.p2 = (signed char)(r.split ? pn[1] : -1); s.lane_buf = (signed char)buf; s.split = r.split;
+            s.y1 = y; s.y2 = r.split ? y2 : y;
+            s.ydiv = r.ydiv; s.src_rows = ca.yrows; s.Kp = ca.Kp; s.ktrue = ktrue;
+        };
+        add(0, r.y1);
+        if (!r.split && !r.samex) add(1, y2);
+    }
+    return nc;
+}
+
+size_t prune_gathered_offsets(const PrunePlan& plan, PruneClassSrc* src) {
+    size_t total = 0;
+    for (unsigned c = 0; c < plan.n_classes; ++c) {
+        const size_t bytes = (size_t)src[c].Kp * ((plan.c[c].cap + 15) / 16 * 16) * sizeof(double);
+        src[c].goff = total; total += bytes;
+        src[c].goff2 = total; if (src[c].split) total += bytes;
+    }
+    return total;
+}
+
 }  // namespace ssw

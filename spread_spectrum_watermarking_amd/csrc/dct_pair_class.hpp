@@ -133,5 +133,21 @@ double pair_class_flop(PairClass c, size_t lines, size_t len);
 struct PrunePlan;
 int prune_class_list(const PassPlan& rows, PairClass out[8]);
 void prune_plan_classes(const PairClass* cls, int n, unsigned cap, PrunePlan& plan);
+// What the subset product of each class OF THE PLAN reads (prune_plan_classes' order: a split launch class is one class of the
+// plan -- cosine and sine rows --, a folded one two), over lines of length w.  Returns the number of plan classes; 0 where
+// the table does not serve a class at that length.
+struct PruneClassSrc {
+    signed char p1, p2;        // operand plane(s) by number at the plan's level (l1x / l2x); p2: the sine operand of a split class, else -1
+    signed char lane_buf;      // a class that is neither deep nor split reads the lane's operand[lane_buf] as the two- / three-level
+                               // pre-passes fill them (x- | D in [1], S- in [0], SS SD | SSS SS- in [2] [3]); -1: the numbered plane
+    bool split;
+    BasisKind y1, y2;          // the bases as cached (the gather reads sinE itself, not its launch variant); y2: split only
+    unsigned ydiv, src_rows, Kp, ktrue;      // bases of length w / ydiv with src_rows lines; padded / true sum length
+    size_t goff = 0, goff2 = 0;              // prune_gathered_offsets: where its gathered bases lie (goff2: a split class's sine basis)
+};
+int prune_class_sources(const PairClass* cls, int n, const PassPlan& rows, size_t w, PruneClassSrc out[9]);
+// sets the byte offsets of the classes' gathered bases in one buffer, [Kp][cap in whole tiles of 16 rows] doubles each (the
+// fused pass's fragment order needs whole tiles), and returns the buffer's size
+size_t prune_gathered_offsets(const PrunePlan& plan, PruneClassSrc* src);
 
 }  // namespace ssw

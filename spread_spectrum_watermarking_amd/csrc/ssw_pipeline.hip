@@ -1044,12 +1044,15 @@ int run_pipeline(ssw_ctx* ctx, size_t n_chunks, const std::function<int(size_t, 
     return rc;
 }
 
-// ---- pruned transform of the derived frames (prune.hip) ---------------------------------------------------
+// ---- pruned transform of the derived frames (prune.hip) ---------------------------------------
 struct PruneSetup {
     bool on = false;
     PrunePlan plan;
     PassPlan rows;                  // of the full transform's row pass: levels 2 or 3; the split odd half (two classes instead
-};                                  // of one); deep: frequencies 2 mod 4 split as well, 0 / 4 mod 8 from the third level
+                                    // of one); deep: frequencies 2 mod 4 split as well, 0 / 4 mod 8 from the third level
+    PruneClassSrc src[9];           // per class of `plan`: what its subset product reads (dct_pair_class.hpp)
+    size_t gathered_bytes = 0;      // of one order of the gathered bases; 0: the class table does not serve this length (the chain fails)
+};
 
 // capacity of the compact plane in frequency columns: the index lists of natural spectra use ~3 sqrt(k)
 // distinct columns (measured: 80..110 for k = 1000 at full HD and 4K); 8 sqrt(k), split over the classes
@@ -1075,198 +1078,290 @@ PruneSetup make_prune_setup(const ssw_ctx* ctx, bool f64, size_t n, size_t w, si
     ps.plan.W = (unsigned)w;
     ps.plan.cap_total = (unsigned)cap;
     PairClass cls[8];
-    const int n_cls = prune_class_list(ps.rows, cls);             // what build_pruned_derived launches
+    const int n_cls = prune_class_list(ps.rows, cls);             // the row pass's launch classes: one list feeds the plan and its sources
     prune_plan_classes(cls, n_cls, (unsigned)cap, ps.plan);
+    if (prune_class_sources(cls, n_cls, ps.rows, w, ps.src) != 0) ps.gathered_bytes = prune_gathered_offsets(ps.plan, ps.src);
     ps.on = true;
     return ps;
 }
 
-// One prune plan for a whole call (ssw_fingerprint_trace: every chunk on both lanes reads ONE index list): the tables and the
-// gathered bases live in the context and are built once -- `build`: the chain gets that one stage (idx = the one list) and
-// nothing else; otherwise the chunk's chain starts at the pre-pass and reads them.
-struct PruneShared {
-    ssw_ctx::Buf *u32, *gathered, *gathered_frag;      // tables | bases in launch order | in the fused pass's fragment order
-    bool build;
+// The pruned path ends with one look at the overflow flags on the host; a stream that is being captured into
+// a graph cannot be waited for, so such a call takes the full transform (enqueue-only, no host round trip).
+bool stream_capturing(ssw_ctx* ctx) {
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &capture) != hipSuccess) { (void)hipGetLastError(); capture = hipStreamCaptureStatusNone; }
+    return capture != hipStreamCaptureStatusNone;
+}
+
+// One class of the plan with its pointers; the launches' per-class arguments are each one conversion of it
+struct PrunedClass {
+    PruneClassSrc s;                               // planes by number (the fused kernel's A-fragments), sum lengths, gathered offsets
+    const double *x = nullptr, *x2 = nullptr;      // operand plane(s) (set per chunk; x2: the sine operand of a split class)
+    const void *basis = nullptr, *basis2 = nullptr;      // cached bases (basis2: split only)
+};
+// The prune tables: the column set of one or more index lists (launch_prune_build) and the rows of the cached bases gathered
+// for it.  Three owners: a chunk of batch extract (its lane's buffers), the single-image handle (lane 0's), and a whole
+// trace call (the context's: every chunk on both lanes reads ONE list, so they are made once before the pipeline starts).
+struct PruneTables {
+    PrunePlan plan;
+    PassPlan rows;                                 // the row pass the plan prunes
+    uint32_t *flag, *pos, *rows_of, *info;         // [W] | [W] | [cap_total] | the info block: overflow flag, columns per class
+    char *gathered, *gathered_frag;                // the bases in launch order | in the fused pass's fragment order
+    const double* rot[3];                          // rotation tables of the split row pass: of w, w / 2, w / 4
+    PrunedClass c[9];
+    const double* y(unsigned i, bool frag, bool second) const {
+        if (second && !c[i].s.split) return nullptr;
+        return (const double*)((frag ? gathered_frag : gathered) + (second ? c[i].s.goff2 : c[i].s.goff));
+    }
+    DerivedFusedClass fused(unsigned i) const {
+        return {y(i, true, false), y(i, true, true), (unsigned)c[i].s.p1, (unsigned)(c[i].s.p2 < 0 ? 0 : c[i].s.p2), plan.c[i].cap, plan.c[i].off, c[i].s.split};
+    }
+    PairSubsetClass subset(unsigned i) const { return {c[i].x, c[i].x2, y(i, false, false), y(i, false, true), plan.c[i].cap, c[i].s.Kp, plan.c[i].off}; }
+    PruneGatherJob gather(unsigned i, bool frag, bool second) const {
+        return {rows_of + plan.c[i].off, (const char*)(second ? c[i].basis2 : c[i].basis), (char*)y(i, frag, second), plan.c[i].cap, c[i].s.src_rows,
+                (unsigned)(c[i].s.Kp / KBlock<double>::KB), 0u, second, frag};
+    }
 };
 
-// derived rgb frames -> compact coefficient plane ws.compact[1] [n][h][cap_total] holding, for every
-// frequency column the chunk's index lists use, the column the full (f64: make_prune_setup) transform would produce
-int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u8, size_t n, size_t w, size_t h, size_t k,
-                         const uint32_t* idx, const PruneSetup& ps, uint32_t* info, Chain& ch, const PruneShared* sh = nullptr) {
-    const PrunePlan plan = ps.plan;
-    const size_t cap = plan.cap_total;
-    const size_t bytes = dct_pair_operand_elems(n, w, h) * sizeof(double);
-    const int levels = ps.rows.levels;
+// Lays the tables out in their owner's buffers -- `lane`, or the context (null) -- and resolves the plan's bases.  A lane's two
+// orders of the gathered bases share one buffer (a chunk takes one row route); a call's keep both: its last chunk may take the other.
+int lay_out_prune_tables(ssw_ctx* ctx, ssw_ctx::Lane* lane, const PruneSetup& ps, size_t w, uint32_t* info, PruneTables& t) {
     const bool deep = plan_is_deep(ps.rows), level2 = plan_is_level2(ps.rows);
-    const bool tables_only = sh && sh->build, per_chunk = !sh;
-    if (!tables_only) {
-        if (!deep) for (int b = 0; b < 4; ++b) SSW_TRY(grow(ws.operand[b], bytes));      // the deep pre-pass writes into operand[5] only
-        for (int b = 0; b < 2; ++b) SSW_TRY(grow(ws.compact[b], n * h * cap * sizeof(float)));
-    }
-    ssw_ctx::Buf& u32buf = sh ? *sh->u32 : ws.prune_u32;
-    SSW_TRY(grow(u32buf, (2 * w + cap + 64) * sizeof(uint32_t)));
-    uint32_t* flag = (uint32_t*)u32buf.p;
-    uint32_t* pos = flag + w;
-    uint32_t* rows = pos + w;
-    // class of the plan -> image operand plane(s), cached basis plane(s), padded / true sum length: the launch classes of
-    // make_prune_setup by the class table -- a split class is one class of the plan (cosine and sine rows), a folded one two
-    struct ClassSrc { const void* x; const void* basis; size_t src_rows, kp, ktrue; const void* x2 = nullptr; const void* basis2 = nullptr; };
-    ClassSrc cs[9];
-    int pn1[9] = {0}, pn2[9] = {0};          // level 2: the classes' operand planes by number (the fused kernel's A-fragments)
-    unsigned ci = 0;
-    const size_t lines = n * h;
-    const void *rot = nullptr, *rot2 = nullptr, *rot3 = nullptr;
-    double* sp = nullptr;
-    if (deep && !ps.rows.split) return SSW_ERR_BAD_ARG;
+    if ((deep && !ps.rows.split) || ps.gathered_bytes == 0) return SSW_ERR_BAD_ARG;
+    ssw_ctx::Buf& u32 = lane ? lane->prune_u32 : ctx->trace[2];
+    ssw_ctx::Buf& natural = lane ? lane->gathered : ctx->trace[3];
+    ssw_ctx::Buf& frag = lane ? lane->gathered : ctx->trace[4];
+    t.plan = ps.plan;
+    t.rows = ps.rows;
+    t.info = info;
+    SSW_TRY(grow(u32, (2 * w + ps.plan.cap_total + 64) * sizeof(uint32_t)));
+    t.flag = (uint32_t*)u32.p;
+    t.pos = t.flag + w;
+    t.rows_of = t.pos + w;
+    t.rot[0] = t.rot[1] = t.rot[2] = nullptr;
     if (ps.rows.split) {
-        SSW_TRY(get_basis(ctx, w, false, true, BasisKind::Rot, &rot));
-        if (deep) SSW_TRY(get_basis(ctx, w / 2, false, true, BasisKind::Rot, &rot2));
-        if (level2) SSW_TRY(get_basis(ctx, w / 4, false, true, BasisKind::Rot, &rot3));
-        if (!tables_only) {
-            SSW_TRY(grow(ws.operand[5], split_scratch_elems(n, w, h) * sizeof(double)));
-            sp = (double*)ws.operand[5].p;
-        }
+        SSW_TRY(get_basis(ctx, w, false, true, BasisKind::Rot, (const void**)&t.rot[0]));
+        if (deep) SSW_TRY(get_basis(ctx, w / 2, false, true, BasisKind::Rot, (const void**)&t.rot[1]));
+        if (level2) SSW_TRY(get_basis(ctx, w / 4, false, true, BasisKind::Rot, (const void**)&t.rot[2]));
     }
-    PairPlanes pp;
-    pp.sp = pp.l2 = sp;
-    pp.p8 = lines * dct_pair_split_kpad(w);
-    pp.p16 = pp.l2_plane = lines * dct_pair_split_kpad(w / 2);
-    PairClass cls[8];
-    const int n_cls = prune_class_list(ps.rows, cls);
-    for (int i = 0; i < n_cls; ++i) {
-        const PairClassRow& r = pair_class_row(cls[i]);
-        PairClassArgs ca;
-        PairInstance inst;
-        SSW_TRY(pair_class_args(cls[i], true, false, w, PairLayout(), false, false, false, ca, inst));
-        // operand planes: the deep pre-passes' by number; else the lane's buffers as the two- / three-level pre-passes fill them
-        // (x- | D in [1], S- in [0], SS SD | SSS SS- in [2] [3]) and the rotated odd half in the split scratch
-        const signed char* pn = level2 ? r.l2x : r.l1x;
-        const void *x1, *x2;
-        if (deep || r.split) { x1 = pp.plane(level2, pn[0]); x2 = pp.plane(level2, pn[1]); }
-        else if (r.samex) x1 = x2 = ws.operand[cls[i] == PairClass::OddHalf ? 1 : 0].p;
-        else { x1 = ws.operand[2].p; x2 = ws.operand[3].p; }
-        // the bases as cached (the gather reads sinE itself, not its launch variant)
-        const void *y1 = nullptr, *y2 = nullptr;
-        SSW_TRY(get_basis(ctx, w / r.ydiv, false, true, r.y1, &y1));
-        SSW_TRY(get_basis(ctx, w / r.ydiv, false, true, r.y2 == BasisKind::SinELaunch ? BasisKind::SinE : r.y2, &y2));
-        const size_t ktrue = w / r.ldiv / r.k_div;
-        pn1[ci] = pn[0]; pn2[ci] = r.split ? pn[1] : -1;
-        if (r.split) cs[ci++] = {x1, y1, ca.yrows, ca.Kp, ktrue, x2, y2};
-        else {
-            cs[ci++] = {x1, y1, ca.yrows, ca.Kp, ktrue};
-            if (!r.samex) { pn1[ci] = pn[1]; pn2[ci] = -1; cs[ci++] = {x2, y2, ca.yrows, ca.Kp, ktrue}; }
-        }
+    for (unsigned i = 0; i < ps.plan.n_classes; ++i) {
+        t.c[i] = PrunedClass();
+        t.c[i].s = ps.src[i];
+        SSW_TRY(get_basis(ctx, w / ps.src[i].ydiv, false, true, ps.src[i].y1, &t.c[i].basis));
+        if (ps.src[i].split) SSW_TRY(get_basis(ctx, w / ps.src[i].ydiv, false, true, ps.src[i].y2, &t.c[i].basis2));
     }
-    if (ci != plan.n_classes) return SSW_ERR_BAD_ARG;
-    size_t goff[9], goff2[9], gtotal = 0;
-    for (unsigned c = 0; c < plan.n_classes; ++c) {
-        const size_t cap16 = (plan.c[c].cap + 15) / 16 * 16;               // (whole tiles of 16 rows: the fused pass's fragment order)
-        goff[c] = gtotal; gtotal += cs[c].kp * cap16 * sizeof(double);
-        goff2[c] = gtotal; if (cs[c].x2) gtotal += cs[c].kp * cap16 * sizeof(double);
-    }
-    // (the two orders of the gathered bases share one buffer per chunk: a chunk takes one path; a call-wide plan keeps both,
-    // since the last, shorter chunk may take the other one)
-    SSW_TRY(grow(sh ? *sh->gathered : ws.gathered, gtotal));
-    if (sh && level2) SSW_TRY(grow(*sh->gathered_frag, gtotal));
-    char* gathered = (char*)(sh ? sh->gathered->p : ws.gathered.p);
-    char* gathered_frag = sh ? (char*)sh->gathered_frag->p : gathered;
-    float* t_compact = (float*)ws.compact[0].p;
-    double *o0 = (double*)ws.operand[0].p, *o1 = (double*)ws.operand[1].p, *o2 = (double*)ws.operand[2].p, *o3 = (double*)ws.operand[3].p;
-    const double px = (double)n * (double)w * (double)h;
-    const double prep_bytes = px * (3.0 * (double)pix_bytes(u8) + 8.0);
-    double flop = 0.0;
-    for (unsigned c = 0; c < plan.n_classes; ++c) flop += (cs[c].x2 ? 4.0 : 2.0) * (double)lines * plan.c[c].cap * (double)cs[c].ktrue;
-    auto gather_jobs = [=](bool frag) {
+    SSW_TRY(grow(natural, ps.gathered_bytes));
+    if (!lane && level2) SSW_TRY(grow(frag, ps.gathered_bytes));
+    t.gathered = (char*)natural.p;
+    t.gathered_frag = (char*)frag.p;
+    return SSW_OK;
+}
+
+// The one place the tables are made: the column set of `n_lists` index lists (idx null: this chain built it in an earlier
+// stage), then the bases' rows in launch order and / or in fragment order.
+int enqueue_prune_tables(hipStream_t st, const PruneTables& t, const uint32_t* idx, size_t n_lists, size_t k, bool want_natural, bool want_frag) {
+    if (idx) SSW_TRY(launch_prune_build(st, idx, n_lists, k, t.plan, t.flag, t.rows_of, t.pos, t.info));
+    for (bool frag : {false, true}) {
+        if (!(frag ? want_frag : want_natural)) continue;
         PruneGatherJobs jobs;
         jobs.n = 0;
-        for (unsigned c = 0; c < plan.n_classes; ++c) {
-            const unsigned kblocks = (unsigned)(cs[c].kp / KBlock<double>::KB);
-            char* dst = frag ? gathered_frag : gathered;
-            jobs.j[jobs.n++] = {rows + plan.c[c].off, (const char*)cs[c].basis, dst + goff[c], plan.c[c].cap, (unsigned)cs[c].src_rows, kblocks, 0u, false, frag};
-            if (cs[c].x2) jobs.j[jobs.n++] = {rows + plan.c[c].off, (const char*)cs[c].basis2, dst + goff2[c], plan.c[c].cap, (unsigned)cs[c].src_rows, kblocks, 0u, true, frag};
+        for (unsigned i = 0; i < t.plan.n_classes; ++i) {
+            jobs.j[jobs.n++] = t.gather(i, frag, false);
+            if (t.c[i].s.split) jobs.j[jobs.n++] = t.gather(i, frag, true);
         }
-        return jobs;
-    };
-    if (tables_only) {
+        SSW_TRY(launch_prune_gather_bases(st, jobs));
+    }
+    return SSW_OK;
+}
+
+// the tables of a whole call (one index list), in the context, enqueued on its stream before the pipeline starts
+int make_call_prune_tables(ssw_ctx* ctx, const PruneSetup& ps, size_t w, size_t k, const uint32_t* idx, uint32_t* info) {
+    PruneTables t;
+    SSW_TRY(lay_out_prune_tables(ctx, nullptr, ps, w, info, t));
+    untimed_work(ctx);
+    return enqueue_prune_tables(ctx->stream, t, idx, 1, k, true, plan_is_level2(ps.rows));
+}
+
+// what the route builders of one chunk share; held by value in the stages
+struct PrunedChunk {
+    ssw_ctx* ctx;
+    const void* rgb; int u8;
+    size_t n, w, h, k, lines;
+    const uint32_t* idx;
+    bool make_tables;               // this chain makes the tables it reads (else the call did: make_call_prune_tables)
+    double *sp, *o[4];              // the split scratch and the lane's operand buffers
+    float* t_compact;               // the row pass's output [lines][cap]
+    PruneTables t;
+    size_t cap() const { return t.plan.cap_total; }
+    double px() const { return (double)n * (double)w * (double)h; }
+};
+
+// r5: marks of up to 1024 entries at level 2 -- the whole row pass in one kernel (dct_pair_derived.hip): no operand planes.
+// A chain that makes its tables does so in one HBM stage in front of it.
+void pruned_rows_fused(const PrunedChunk& q, const std::array<DerivedFusedClass, 9>& fca, Chain& ch) {
+    ssw_ctx* ctx = q.ctx;
+    if (q.make_tables)
         ch.push_back({true, [=](hipStream_t st) -> int {
             untimed_work(ctx);
-            SSW_TRY(launch_prune_build(st, idx, 1, k, plan, flag, rows, pos, info));
-            SSW_TRY(launch_prune_gather_bases(st, gather_jobs(false)));
-            return level2 ? launch_prune_gather_bases(st, gather_jobs(true)) : SSW_OK;
+            return enqueue_prune_tables(st, q.t, q.idx, q.n, q.k, false, true);
         }});
-        return SSW_OK;
-    }
-    // r5: marks of up to 1024 entries at level 2 -- the whole row pass in one kernel (dct_pair_derived.hip): no operand planes
-    if (level2) {
-        DerivedFusedClass fc[9];
-        for (unsigned c = 0; c < plan.n_classes; ++c)
-            fc[c] = {(const double*)(gathered_frag + goff[c]), cs[c].x2 ? (const double*)(gathered_frag + goff2[c]) : nullptr, (unsigned)pn1[c],
-                     (unsigned)(pn2[c] < 0 ? 0 : pn2[c]), plan.c[c].cap, plan.c[c].off, cs[c].x2 != nullptr};
-        // (a single frame is 135 blocks of 16 lines for 256 CUs: the merged launches below are 35 us faster there)
-        if (plan_derived_fused(ps.rows, lines) && dct_pair_derived_fused_fits(plan.n_classes, fc)) {
-            const unsigned ncl = plan.n_classes;
-            std::array<DerivedFusedClass, 9> fca;
-            for (unsigned c = 0; c < 9; ++c) fca[c] = fc[c < ncl ? c : 0];
-            if (per_chunk)
-                ch.push_back({true, [=](hipStream_t st) -> int {
-                    untimed_work(ctx);
-                    SSW_TRY(launch_prune_build(st, idx, n, k, plan, flag, rows, pos, info));
-                    return launch_prune_gather_bases(st, gather_jobs(true));
-                }});
-            const double in_bytes = px * 3.0 * (double)pix_bytes(u8);
-            // (timed with the RGB pre-passes: an HBM-bound kernel -- frames in, compact plane out -- whose 0.1e12 flop ride along;
-            // bench.py's GEMM family stays "every pair_gemm_f64_kernel launch")
-            ch.push_back({false, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, SSW_STAGE_RGB_TO_YIQ, st, in_bytes + (double)lines * (double)cap * 4.0);
-                return launch_dct_pair_derived_fused(st, pix_src_kind(u8), rgb, lines, w, (const double*)rot, (const double*)rot2, (const double*)rot3,
-                                                     ncl, fca.data(), t_compact, (unsigned)cap);
-            }});
-            Xform xc{SSW_DCT2, SSW_PRECISION_F64, n, cap, h, (float*)ws.compact[1].p, t_compact};
-            xc.natural_order = true;
-            return build_pass(ctx, ws, xc, false, false, t_compact, (float*)ws.compact[1].p, Epilogue{1.f, 1.f}, ch);
-        }
-    }
-    // the set of columns, then Reader::derived's colour conversion + operand pre-pass (same kernels as the full path)
+    const double in_bytes = q.px() * 3.0 * (double)pix_bytes(q.u8);
+    // (timed with the RGB pre-passes: an HBM-bound kernel -- frames in, compact plane out -- whose 0.1e12 flop ride along;
+    // bench.py's GEMM family stays "every pair_gemm_f64_kernel launch")
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, SSW_STAGE_RGB_TO_YIQ, st, in_bytes + (double)q.lines * (double)q.cap() * 4.0);
+        return launch_dct_pair_derived_fused(st, pix_src_kind(q.u8), q.rgb, q.lines, q.w, q.t.rot[0], q.t.rot[1], q.t.rot[2], q.t.plan.n_classes, fca.data(),
+                                             q.t_compact, (unsigned)q.cap());
+    }});
+}
+
+// Reader::derived's colour conversion + operand pre-pass (same kernels as the full path), then the subset products.  A chain
+// that makes its tables builds the column set in front of the pre-pass and gathers in front of the products: two streams.
+void pruned_rows_gathered(const PrunedChunk& q, Chain& ch) {
+    ssw_ctx* ctx = q.ctx;
+    const bool deep = plan_is_deep(q.t.rows), level2 = plan_is_level2(q.t.rows);
+    const int levels = q.t.rows.levels;
+    const unsigned ncl = q.t.plan.n_classes;
+    const double prep_bytes = q.px() * (3.0 * (double)pix_bytes(q.u8) + 8.0);
+    double flop = 0.0;
+    for (unsigned c = 0; c < ncl; ++c) flop += (q.t.c[c].s.split ? 4.0 : 2.0) * (double)q.lines * q.t.plan.c[c].cap * (double)q.t.c[c].s.ktrue;
     ch.push_back({true, [=](hipStream_t st) -> int {
-        if (per_chunk) {
-            SSW_TRY(launch_prune_build(st, idx, n, k, plan, flag, rows, pos, info));
+        if (q.make_tables) {
+            SSW_TRY(enqueue_prune_tables(st, q.t, q.idx, q.n, q.k, false, false));
             untimed_work(ctx);
         }
         StageTimer t(ctx, SSW_STAGE_RGB_TO_YIQ, st, prep_bytes);
-        if (deep) return launch_dct_pair_prep16_rows(st, pix_src_kind(u8), rgb, n, w, h, sp, (const double*)rot, (const double*)rot2,
-                                                     (const double*)rot3, nullptr, nullptr, level2);
-        if (levels == 3) SSW_TRY(launch_dct_pair_prep8_rows(st, pix_src_kind(u8), rgb, n, w, h, o2, o3, o0, o1, nullptr, nullptr));
-        else SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, u8, rgb, n, w, h, o2, o3, o1, nullptr, nullptr));
-        return sp ? launch_dct_pair_rotate(st, o1, (const double*)rot, sp, lines, w) : SSW_OK;
+        if (deep) return launch_dct_pair_prep16_rows(st, pix_src_kind(q.u8), q.rgb, q.n, q.w, q.h, q.sp, q.t.rot[0], q.t.rot[1], q.t.rot[2], nullptr, nullptr, level2);
+        if (levels == 3) SSW_TRY(launch_dct_pair_prep8_rows(st, pix_src_kind(q.u8), q.rgb, q.n, q.w, q.h, q.o[2], q.o[3], q.o[0], q.o[1], nullptr, nullptr));
+        else SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, q.u8, q.rgb, q.n, q.w, q.h, q.o[2], q.o[3], q.o[1], nullptr, nullptr));
+        return q.sp ? launch_dct_pair_rotate(st, q.o[1], q.t.rot[0], q.sp, q.lines, q.w) : SSW_OK;
     }});
     ch.back().tag = 2;
     ch.push_back({false, [=](hipStream_t st) -> int {
-        if (per_chunk) {
-            SSW_TRY(launch_prune_gather_bases(st, gather_jobs(false)));
+        if (q.make_tables) {
+            SSW_TRY(enqueue_prune_tables(st, q.t, nullptr, 0, 0, true, false));
             untimed_work(ctx);
         }
         StageTimer t(ctx, SSW_STAGE_DCT_ROW, st, flop);
-        t.traffic(px * 8.0 + (double)lines * (double)cap * 4.0);      // every operand plane once in, the compact plane out
-        if (plan_merge(lines)) {          // a single frame: the classes side by side in one launch per kind
+        t.traffic(q.px() * 8.0 + (double)q.lines * (double)q.cap() * 4.0);      // every operand plane once in, the compact plane out
+        if (plan_merge(q.lines)) {          // a single frame: the classes side by side in one launch per kind
             PairSubsetClass sc[9];
-            for (unsigned c = 0; c < plan.n_classes; ++c)
-                sc[c] = {(const double*)cs[c].x, (const double*)cs[c].x2, (const double*)(gathered + goff[c]),
-                         cs[c].x2 ? (const double*)(gathered + goff2[c]) : nullptr, plan.c[c].cap, (unsigned)cs[c].kp, plan.c[c].off};
-            return launch_dct_pair_gemm_rows_subset_merged_f64(st, sc, plan.n_classes, t_compact, (unsigned)cap, lines);
+            for (unsigned c = 0; c < ncl; ++c) sc[c] = q.t.subset(c);
+            return launch_dct_pair_gemm_rows_subset_merged_f64(st, sc, ncl, q.t_compact, (unsigned)q.cap(), q.lines);
         }
-        for (unsigned c = 0; c < plan.n_classes; ++c) {
-            if (cs[c].x2) SSW_TRY(launch_dct_pair_gemm_rows_subset_split_f64(st, (const double*)cs[c].x, (const double*)cs[c].x2, (const double*)(gathered + goff[c]),
-                                                                             (const double*)(gathered + goff2[c]), plan.c[c].cap, (unsigned)cs[c].kp, t_compact,
-                                                                             (unsigned)cap, plan.c[c].off, lines));
-            else SSW_TRY(launch_dct_pair_gemm_rows_subset_f64(st, (const double*)cs[c].x, (const double*)(gathered + goff[c]), plan.c[c].cap,
-                                                              (unsigned)cs[c].kp, t_compact, (unsigned)cap, plan.c[c].off, lines));
+        for (unsigned c = 0; c < ncl; ++c) {
+            const PairSubsetClass s = q.t.subset(c);
+            if (s.x2) SSW_TRY(launch_dct_pair_gemm_rows_subset_split_f64(st, s.x1, s.x2, s.y1, s.y2, s.cap, s.Kp, q.t_compact, (unsigned)q.cap(), s.off, q.lines));
+            else SSW_TRY(launch_dct_pair_gemm_rows_subset_f64(st, s.x1, s.y1, s.cap, s.Kp, q.t_compact, (unsigned)q.cap(), s.off, q.lines));
         }
         return SSW_OK;
     }});
-    // column pass on the compact plane: the second pass of the same transform, `cap` columns wide
-    Xform xc{SSW_DCT2, SSW_PRECISION_F64, n, cap, h, (float*)ws.compact[1].p, t_compact};
+}
+
+// column pass on the compact plane: the second pass of the same transform, `cap` columns wide, into ws.compact[1]
+int pruned_cols(ssw_ctx* ctx, ssw_ctx::Lane& ws, size_t n, size_t cap, size_t h, Chain& ch) {
+    float *t_compact = (float*)ws.compact[0].p, *compact = (float*)ws.compact[1].p;
+    Xform xc{SSW_DCT2, SSW_PRECISION_F64, n, cap, h, compact, t_compact};
     xc.natural_order = true;                 // the compact plane's columns are the gathered frequencies, in the plan's order
-    return build_pass(ctx, ws, xc, false, false, t_compact, (float*)ws.compact[1].p, Epilogue{1.f, 1.f}, ch);
+    return build_pass(ctx, ws, xc, false, false, t_compact, compact, Epilogue{1.f, 1.f}, ch);
+}
+
+// derived rgb frames -> compact coefficient plane ws.compact[1] [n][h][cap_total] holding, for every frequency column the
+// index lists use, the column the full (f64: make_prune_setup) transform would produce.  `call_tables`: the chunk reads the
+// call's tables; else it owns them in `ws` and its chain makes them.  *pos: their position list, for the extraction.
+int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u8, size_t n, size_t w, size_t h, size_t k,
+                         const uint32_t* idx, const PruneSetup& ps, uint32_t* info, bool call_tables, Chain& ch, const uint32_t** pos) {
+    const size_t cap = ps.plan.cap_total, lines = n * h;
+    const bool deep = plan_is_deep(ps.rows), level2 = plan_is_level2(ps.rows);
+    if (!deep) for (int b = 0; b < 4; ++b) SSW_TRY(grow(ws.operand[b], dct_pair_operand_elems(n, w, h) * sizeof(double)));      // the deep pre-pass writes into operand[5] only
+    for (int b = 0; b < 2; ++b) SSW_TRY(grow(ws.compact[b], n * h * cap * sizeof(float)));
+    if (ps.rows.split) SSW_TRY(grow(ws.operand[5], split_scratch_elems(n, w, h) * sizeof(double)));
+    PrunedChunk q{ctx, rgb, u8, n, w, h, k, lines, idx, !call_tables, ps.rows.split ? (double*)ws.operand[5].p : nullptr,
+                  {(double*)ws.operand[0].p, (double*)ws.operand[1].p, (double*)ws.operand[2].p, (double*)ws.operand[3].p}, (float*)ws.compact[0].p};
+    SSW_TRY(lay_out_prune_tables(ctx, call_tables ? nullptr : &ws, ps, w, info, q.t));
+    *pos = q.t.pos;
+    // operand planes: by number in the split scratch, else the lane's buffers as the two- / three-level pre-passes fill them
+    PairPlanes pp;
+    pp.sp = pp.l2 = q.sp;
+    pp.p8 = lines * dct_pair_split_kpad(w);
+    pp.p16 = pp.l2_plane = lines * dct_pair_split_kpad(w / 2);
+    for (unsigned c = 0; c < ps.plan.n_classes; ++c) {
+        const PruneClassSrc& s = ps.src[c];
+        q.t.c[c].x = s.lane_buf >= 0 ? q.o[s.lane_buf] : pp.plane(level2, s.p1);
+        q.t.c[c].x2 = s.split ? pp.plane(level2, s.p2) : nullptr;
+    }
+    // (a single frame is 135 blocks of 16 lines for 256 CUs: the merged launches of the gathered route are 35 us faster there)
+    std::array<DerivedFusedClass, 9> fca{};
+    if (level2) for (unsigned c = 0; c < 9; ++c) fca[c] = q.t.fused(c < ps.plan.n_classes ? c : 0);
+    if (level2 && plan_derived_fused(ps.rows, lines) && dct_pair_derived_fused_fits(ps.plan.n_classes, fca.data())) pruned_rows_fused(q, fca, ch);
+    else pruned_rows_gathered(q, ch);
+    return pruned_cols(ctx, ws, n, cap, h, ch);
+}
+
+// Prune -> look once -> redo: build_chunk(chunk, lane, chain, pruned) through the pipeline; where it pruned, ONE wait for the
+// device to read the info blocks in ctx->overflow (one per chunk, or one for the call), the counters, and every chunk whose
+// block has the overflow flag set -- its columns did not fit the compact plane -- again on lane 0 with the full transform.
+typedef std::function<int(size_t, ssw_ctx::Lane&, Chain&, bool)> PrunedChunkBuilder;
+int run_pruned_pipeline(ssw_ctx* ctx, size_t n_chunks, const PruneSetup& ps, bool info_per_chunk, const PrunedChunkBuilder& build_chunk) {
+    SSW_TRY(run_pipeline(ctx, n_chunks, [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch) { return build_chunk(ci, ws, ch, ps.on); }));
+    if (!ps.on) return SSW_OK;
+    std::vector<uint32_t> info((info_per_chunk ? n_chunks : 1) * SSW_PRUNE_INFO);
+    SSW_HIP_CHECK(hipMemcpyAsync(info.data(), ctx->overflow.p, info.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (size_t ci = 0; ci < n_chunks; ++ci) {
+        const uint32_t* block = info.data() + (info_per_chunk ? ci : 0) * SSW_PRUNE_INFO;
+        ctx->pruned_chunks++;
+        if (info_per_chunk || ci == 0)
+            for (unsigned q = 0; q < ps.plan.n_classes; ++q) ctx->pruned_columns += block[1 + q];
+        if (block[0] == 0) continue;
+        ctx->redone_chunks++;
+        Chain ch;
+        SSW_TRY(build_chunk(ci, ctx->lane[0], ch, false));
+        SSW_TRY(run_serial(ch, ctx->stream));
+    }
+    return SSW_OK;
+}
+
+// ---- base-reader pruning (base_prune.hip): who takes it, and its workspace -----------------------------------
+// The terms of shape, alignment and plan: whole tiles and at least two, rows no shorter than columns, an ordering with a key
+// bound, RGB frames the fused pre-pass reads, and the fused forward transform for `n` frames per chunk.  The CALL-level terms
+// are not here: batch extract adds ctx->prune, the tuning entry base_prune and k <= select_max_k() (its masked selection) --
+// switches between two ways to the same values; the debug entry ssw_debug_base_prune_bound shows what the decide kernel
+// would compare for a shape, whether or not a call would currently take the path, so it applies none of them (its own k
+// checks are those of its arguments).
+bool base_prune_shape_ok(const ssw_ctx* ctx, const ssw_config& c, size_t n, size_t w, size_t h, const void* rgb, int u8, const float* y, const float* tmp) {
+    const bool f64 = c.precision == SSW_PRECISION_F64;
+    if (!f64 || w % SSW_BASE_PRUNE_TILE != 0 || w / SSW_BASE_PRUNE_TILE < 2 || w < h || !(base_prune_gain(w, h, c.ordering) > 0.0f)) return false;
+    if (!can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, u8)) return false;
+    const PlanInput in{SSW_DCT2, c.precision, n, w, h, 0, false, true, plan_settings(ctx)};
+    return n <= plan_frame_limit(plan_settings(ctx), f64, w, h) && plan_pass(in, true, true).strategy == PassStrategy::FusedRows &&
+           plan_pass(in, false, false).strategy == PassStrategy::FusedCols;
+}
+// energy [frames][W] f32 | need [frames][W / 128] u32 in the lane's buffer
+int base_prune_workspace(ssw_ctx::Lane& ws, size_t frames, size_t w, BasePrune& bp) {
+    const size_t e_bytes = frames * w * sizeof(float);
+    SSW_TRY(grow(ws.base_prune, e_bytes + frames * (w / SSW_BASE_PRUNE_TILE) * sizeof(unsigned)));
+    bp.energy = (float*)ws.base_prune.p;
+    bp.need = (unsigned*)((char*)ws.base_prune.p + e_bytes);
+    return SSW_OK;
+}
+
+// extract (+ similarity against `marks`) of one chunk of batch extract: the derived values from full coefficient planes
+// (pos null), or from the compact plane [n][h][cap] through the tables' position list
+void push_extract_stage(Chain& ch, ssw_ctx* ctx, const ssw_config& c, const float* yb, const float* derived, const uint32_t* pos, size_t cap,
+                        size_t n, size_t w, size_t h, const uint32_t* idx, size_t k, float* ext, const float* marks, float* sims) {
+    ch.push_back({true, [=](hipStream_t st) -> int {
+        if (k > 0) {
+            StageTimer t(ctx, SSW_STAGE_EXTRACT, st);                           // :529-539
+            if (pos) SSW_TRY(launch_extract_pruned(st, yb, derived, n, w, h, cap, pos, idx, k, c.method, c.alpha, ext));
+            else SSW_TRY(launch_extract(st, yb, derived, n, w * h, idx, k, c.method, c.alpha, ext));
+        }
+        if (marks) {
+            StageTimer t(ctx, SSW_STAGE_SIMILARITY, st);                        // :696-714
+            SSW_TRY(launch_similarity(st, ext, marks, n, k, sims));
+        }
+        return SSW_OK;
+    }});
 }
 
 }  // namespace
@@ -1344,55 +1439,21 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
     // (lane 1 only when the call will run two lanes: three chunks or more)
     for (int l = 0; l < (pipeline_uses_two_lanes(ctx, n_chunks) ? 2 : 1); ++l)
         for (int p : {0, 2}) SSW_TRY(grow(ctx->lane[l].plane[p], chunk * plane * sizeof(float)));
-    // The pruned path ends with one look at the overflow flags on the host; a stream that is being captured into
-    // a graph cannot be waited for, so such a call takes the full transform (enqueue-only, no host round trip).
-    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(ctx->stream, &capture) != hipSuccess) { (void)hipGetLastError(); capture = hipStreamCaptureStatusNone; }
-    const bool allow_prune = capture == hipStreamCaptureStatusNone;
-    const PruneSetup ps = !allow_prune ? PruneSetup() : make_prune_setup(ctx, f64, std::min(chunk, n_frames), w, h, k, (const float*)ctx->lane[0].plane[0].p,
-                                           (const float*)ctx->lane[0].plane[2].p, dev_derived_rgb, u8);
-    if (ps.on) SSW_TRY(grow(ctx->overflow, n_chunks * SSW_PRUNE_INFO * sizeof(uint32_t)));
+    const float *y0 = (const float*)ctx->lane[0].plane[0].p, *tmp0 = (const float*)ctx->lane[0].plane[2].p;
+    const PruneSetup ps = stream_capturing(ctx) ? PruneSetup() : make_prune_setup(ctx, f64, std::min(chunk, n_frames), w, h, k, y0, tmp0, dev_derived_rgb, u8);
+    if (ps.on) SSW_TRY(grow(ctx->overflow, n_chunks * SSW_PRUNE_INFO * sizeof(uint32_t)));      // a block per chunk: every frame has its own list
     uint32_t* overflow = (uint32_t*)ctx->overflow.p;
     // Base-reader pruning (base_prune.hip): where the planner takes the fused forward transform for the chunks of this call
     // and the ordering has a key bound.  ssw_ctx_set_prune(0) and the tuning entry base_prune = 0 give the full transform.
-    const size_t bp_tiles = w / SSW_BASE_PRUNE_TILE;
-    bool base_prune = ctx->prune && tuning(TUNE_BASE_PRUNE) != 0 && f64 && k > 0 && k <= select_max_k() && w % SSW_BASE_PRUNE_TILE == 0 && bp_tiles >= 2 &&
-                      base_prune_gain(w, h, c.ordering) > 0.0f && w >= h &&
-                      can_fuse_rgb(ctx, f64, w, h, (const float*)ctx->lane[0].plane[0].p, (const float*)ctx->lane[0].plane[2].p, dev_base_rgb, u8);
-    for (size_t f0 = 0; base_prune && f0 < n_frames; f0 += chunk) {      // (the last chunk may be shorter: another plan)
-        const size_t n = std::min(chunk, n_frames - f0);
-        const PlanInput in{SSW_DCT2, c.precision, n, w, h, 0, false, true, plan_settings(ctx)};
-        base_prune = n <= plan_frame_limit(plan_settings(ctx), f64, w, h) && plan_pass(in, true, true).strategy == PassStrategy::FusedRows &&
-                     plan_pass(in, false, false).strategy == PassStrategy::FusedCols;
-    }
+    bool base_prune = ctx->prune && tuning(TUNE_BASE_PRUNE) != 0 && k > 0 && k <= select_max_k();
+    for (size_t f0 = 0; base_prune && f0 < n_frames; f0 += chunk)        // (the last chunk may be shorter: another plan)
+        base_prune = base_prune_shape_ok(ctx, c, std::min(chunk, n_frames - f0), w, h, dev_base_rgb, u8, y0, tmp0);
     if (base_prune && !ctx->base_prune_stats.p) {
         SSW_TRY(grow(ctx->base_prune_stats, 8 * sizeof(unsigned long long)));
         SSW_HIP_CHECK(hipMemsetAsync(ctx->base_prune_stats.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
         untimed_work(ctx);
     }
 
-    // extract + similarity of one chunk from full coefficient planes (the un-pruned path and the redo)
-    auto full_derived = [&](ssw_ctx::Lane& ws, size_t f0, size_t n, float* yb, float* tmp, uint32_t* idx, Chain& ch) -> int {
-        SSW_TRY(grow(ws.plane[1], chunk * plane * sizeof(float)));
-        float* yd = (float*)ws.plane[1].p;
-        const char* drgb = static_cast<const char*>(dev_derived_rgb) + f0 * plane * px_bytes;
-        SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, drgb, u8, n, w, h, yd, nullptr, nullptr, tmp, ch));   // Reader::derived
-        float* ext = dev_extracted + f0 * k;
-        const float* marks = dev_marks ? dev_marks + f0 * k : nullptr;
-        float* sims = dev_sims ? dev_sims + f0 : nullptr;
-        ch.push_back({true, [=](hipStream_t st) -> int {
-            if (k > 0) {
-                StageTimer t(ctx, SSW_STAGE_EXTRACT, st);                           // :529-539
-                SSW_TRY(launch_extract(st, yb, yd, n, plane, idx, k, c.method, c.alpha, ext));
-            }
-            if (marks) {
-                StageTimer t(ctx, SSW_STAGE_SIMILARITY, st);                        // :696-714
-                SSW_TRY(launch_similarity(st, ext, marks, n, k, sims));
-            }
-            return SSW_OK;
-        }});
-        return SSW_OK;
-    };
     auto build_chunk = [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch, bool pruned) -> int {
         const size_t f0 = ci * chunk, n = std::min(chunk, n_frames - f0);
         for (int p : {0, 2}) SSW_TRY(grow(ws.plane[p], chunk * plane * sizeof(float)));
@@ -1401,15 +1462,13 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         float* tmp = (float*)ws.plane[2].p;
         uint32_t* idx = (uint32_t*)ws.idx.p;
         const char* brgb = static_cast<const char*>(dev_base_rgb) + f0 * plane * px_bytes;
+        const char* drgb = static_cast<const char*>(dev_derived_rgb) + f0 * plane * px_bytes;
         SelectWorkspace* sel = &ws.sel;
         BasePrune bp;
         bool decided = false;           // the transform below took the two-phase column pass: skipped tiles are stale
         if (base_prune) {
             bp.decided = &decided;
-            const size_t e_bytes = chunk * w * sizeof(float);
-            SSW_TRY(grow(ws.base_prune, e_bytes + chunk * bp_tiles * sizeof(unsigned)));
-            bp.energy = (float*)ws.base_prune.p;
-            bp.need = (unsigned*)((char*)ws.base_prune.p + e_bytes);
+            SSW_TRY(base_prune_workspace(ws, chunk, w, bp));
             bp.stats = (unsigned long long*)ctx->base_prune_stats.p;
             bp.work = (double*)(bp.stats + 4);
             bp.k = k; bp.ordering = c.ordering;
@@ -1419,45 +1478,22 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         const unsigned* mask = decided ? bp.need : nullptr;
         if (k > 0)
             ch.push_back({true, [=](hipStream_t st) -> int { return topk(ctx, st, *sel, yb, n, w, h, c.ordering, k, idx, mask); }});   // :493
-        if (!pruned) return full_derived(ws, f0, n, yb, tmp, idx, ch);
-        const char* drgb = static_cast<const char*>(dev_derived_rgb) + f0 * plane * px_bytes;
-        SSW_TRY(build_pruned_derived(ctx, ws, drgb, u8, n, w, h, k, idx, ps, overflow + ci * SSW_PRUNE_INFO, ch));
-        const float* compact = (const float*)ws.compact[1].p;
-        const uint32_t* pos = (const uint32_t*)ws.prune_u32.p + w;
-        const size_t cap = ps.plan.cap_total;
-        float* ext = dev_extracted + f0 * k;
-        const float* marks = dev_marks ? dev_marks + f0 * k : nullptr;
-        float* sims = dev_sims ? dev_sims + f0 : nullptr;
-        ch.push_back({true, [=](hipStream_t st) -> int {
-            {
-                StageTimer t(ctx, SSW_STAGE_EXTRACT, st);                           // :529-539, derived values from the compact plane
-                SSW_TRY(launch_extract_pruned(st, yb, compact, n, w, h, cap, pos, idx, k, c.method, c.alpha, ext));
-            }
-            if (marks) {
-                StageTimer t(ctx, SSW_STAGE_SIMILARITY, st);                        // :696-714
-                SSW_TRY(launch_similarity(st, ext, marks, n, k, sims));
-            }
-            return SSW_OK;
-        }});
+        // Reader::derived: the compact plane of the columns the lists read, or (the un-pruned path and the redo) the full plane
+        const float* derived = nullptr;
+        const uint32_t* pos = nullptr;
+        if (pruned) {
+            SSW_TRY(build_pruned_derived(ctx, ws, drgb, u8, n, w, h, k, idx, ps, overflow + ci * SSW_PRUNE_INFO, false, ch, &pos));
+            derived = (const float*)ws.compact[1].p;
+        } else {
+            SSW_TRY(grow(ws.plane[1], chunk * plane * sizeof(float)));
+            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, drgb, u8, n, w, h, (float*)ws.plane[1].p, nullptr, nullptr, tmp, ch));
+            derived = (const float*)ws.plane[1].p;
+        }
+        push_extract_stage(ch, ctx, c, yb, derived, pos, ps.plan.cap_total, n, w, h, idx, k, dev_extracted + f0 * k,
+                           dev_marks ? dev_marks + f0 * k : nullptr, dev_sims ? dev_sims + f0 : nullptr);
         return SSW_OK;
     };
-    SSW_TRY(run_pipeline(ctx, n_chunks, [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch) { return build_chunk(ci, ws, ch, ps.on); }));
-    if (!ps.on) return SSW_OK;
-    // Chunks whose column set did not fit the compact plane are redone with the full transform.  This is
-    // the one place a batch call waits for the device.
-    std::vector<uint32_t> info(n_chunks * SSW_PRUNE_INFO);
-    SSW_HIP_CHECK(hipMemcpyAsync(info.data(), overflow, info.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (size_t ci = 0; ci < n_chunks; ++ci) {
-        ctx->pruned_chunks++;
-        for (unsigned q = 0; q < ps.plan.n_classes; ++q) ctx->pruned_columns += info[ci * SSW_PRUNE_INFO + 1 + q];
-        if (info[ci * SSW_PRUNE_INFO] == 0) continue;
-        ctx->redone_chunks++;
-        Chain ch;
-        SSW_TRY(build_chunk(ci, ctx->lane[0], ch, false));
-        SSW_TRY(run_serial(ch, ctx->stream));
-    }
-    return SSW_OK;
+    return run_pruned_pipeline(ctx, n_chunks, ps, true, build_chunk);
 }
 
 // ssw_debug_base_prune_bound: what the decide kernel compares, for tests -- the chunk's forward transform as the batch
@@ -1465,23 +1501,15 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
 int base_prune_bound_impl(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_rgb, size_t n_frames, size_t w, size_t h, size_t k,
                           float* dev_bound) {
     const ssw_config c = *cfg;
-    const bool f64 = c.precision == SSW_PRECISION_F64;
     if (w == 0 || h == 0) return SSW_ERR_BAD_DIMS;
     if (n_frames == 0) return SSW_OK;
-    const size_t plane = w * h, tiles = w / SSW_BASE_PRUNE_TILE;
+    const size_t plane = w * h;
     ssw_ctx::Lane& ws = ctx->lane[0];
     for (int p : {0, 2}) SSW_TRY(grow(ws.plane[p], n_frames * plane * sizeof(float)));
-    const PlanInput in{SSW_DCT2, c.precision, n_frames, w, h, 0, false, true, plan_settings(ctx)};
-    if (!f64 || k == 0 || k >= plane || w % SSW_BASE_PRUNE_TILE != 0 || tiles < 2 || w < h || !(base_prune_gain(w, h, c.ordering) > 0.0f) ||
-        !can_fuse_rgb(ctx, f64, w, h, (const float*)ws.plane[0].p, (const float*)ws.plane[2].p, dev_rgb, SSW_PIX_F32) ||
-        n_frames > plan_frame_limit(plan_settings(ctx), f64, w, h) || plan_pass(in, true, true).strategy != PassStrategy::FusedRows ||
-        plan_pass(in, false, false).strategy != PassStrategy::FusedCols)
+    if (k == 0 || k >= plane || !base_prune_shape_ok(ctx, c, n_frames, w, h, dev_rgb, SSW_PIX_F32, (const float*)ws.plane[0].p, (const float*)ws.plane[2].p))
         return SSW_ERR_UNSUPPORTED;
-    const size_t e_bytes = n_frames * w * sizeof(float);
-    SSW_TRY(grow(ws.base_prune, e_bytes + n_frames * tiles * sizeof(unsigned)));
     BasePrune bp;
-    bp.energy = (float*)ws.base_prune.p;
-    bp.need = (unsigned*)((char*)ws.base_prune.p + e_bytes);
+    SSW_TRY(base_prune_workspace(ws, n_frames, w, bp));
     bp.k = k; bp.ordering = c.ordering;
     Chain ch;
     SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_rgb, SSW_PIX_F32, n_frames, w, h, (float*)ws.plane[0].p, nullptr, nullptr,
@@ -1514,73 +1542,40 @@ int trace_base(ssw_ctx* ctx, const ssw_config& c, const void* dev_base_rgb, int 
 
 // base.extract(Reader::derived(suspect_s), k) for n_frames suspects (:529-561): the derived half of batch_extract_impl --
 // same chunks, same lanes, same kernels up to the compact plane -- with the prune tables and gathered bases made once for
-// the call (one list: the column set cannot grow with the batch, and there is one overflow flag) and the extraction that
-// reads every base value once per slice of frames.
+// the call (one list: the column set cannot grow with the batch, and there is one info block, so an overflow redoes every
+// chunk) and the extraction that reads every base value once per slice of frames.
 int trace_extract(ssw_ctx* ctx, const ssw_config& c, const float* yb, const uint32_t* idx, const void* dev_suspect_rgb, int u8,
                   size_t n_frames, size_t w, size_t h, size_t k, float* dev_extracted) {
     if (n_frames == 0) return SSW_OK;
     const size_t plane = w * h;
     const size_t chunk = effective_chunk(ctx, w, h, n_frames);
     const size_t n_chunks = (n_frames + chunk - 1) / chunk;
-    const bool f64 = c.precision == SSW_PRECISION_F64;
     const size_t px_bytes = 3 * pix_bytes(u8);
-    // (a captured stream cannot be waited for: full transform, as in batch_extract_impl)
-    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(ctx->stream, &capture) != hipSuccess) { (void)hipGetLastError(); capture = hipStreamCaptureStatusNone; }
-    const PruneSetup ps = capture != hipStreamCaptureStatusNone ? PruneSetup()
-                          : make_prune_setup(ctx, f64, std::min(chunk, n_frames), w, h, k, yb, yb, dev_suspect_rgb, u8);
-    uint32_t* info = nullptr;
-    const PruneShared shared{&ctx->trace[2], &ctx->trace[3], &ctx->trace[4], false};
-    if (ps.on) {
-        SSW_TRY(grow(ctx->overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));
-        info = (uint32_t*)ctx->overflow.p;
-        PruneShared make = shared;
-        make.build = true;
-        Chain ch;
-        SSW_TRY(build_pruned_derived(ctx, ctx->lane[0], dev_suspect_rgb, u8, 1, w, h, k, idx, ps, info, ch, &make));
-        SSW_TRY(run_serial(ch, ctx->stream));
-    }
+    const PruneSetup ps = stream_capturing(ctx) ? PruneSetup()
+                          : make_prune_setup(ctx, c.precision == SSW_PRECISION_F64, std::min(chunk, n_frames), w, h, k, yb, yb, dev_suspect_rgb, u8);
+    if (ps.on) SSW_TRY(grow(ctx->overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));                 // one block: one list for the call
+    uint32_t* info = (uint32_t*)ctx->overflow.p;
+    if (ps.on) SSW_TRY(make_call_prune_tables(ctx, ps, w, k, idx, info));
     auto build_chunk = [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch, bool pruned) -> int {
         const size_t f0 = ci * chunk, n = std::min(chunk, n_frames - f0);
         const char* srgb = static_cast<const char*>(dev_suspect_rgb) + f0 * plane * px_bytes;
         float* ext = dev_extracted + f0 * k;
-        if (!pruned) {
+        const uint32_t* pos = nullptr;                 // Reader::derived: the compact plane through the tables' position list, or the full plane
+        if (pruned) SSW_TRY(build_pruned_derived(ctx, ws, srgb, u8, n, w, h, k, idx, ps, info, true, ch, &pos));
+        else {
             for (int p : {1, 2}) SSW_TRY(grow(ws.plane[p], chunk * plane * sizeof(float)));
-            float* yd = (float*)ws.plane[1].p;
-            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, srgb, u8, n, w, h, yd, nullptr, nullptr, (float*)ws.plane[2].p, ch));   // Reader::derived
-            ch.push_back({true, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, SSW_STAGE_EXTRACT, st);                           // :529-539
-                return launch_extract_shared(st, yb, yd, n, plane, idx, k, c.method, c.alpha, ext);
-            }});
-            return SSW_OK;
+            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, srgb, u8, n, w, h, (float*)ws.plane[1].p, nullptr, nullptr, (float*)ws.plane[2].p, ch));
         }
-        SSW_TRY(build_pruned_derived(ctx, ws, srgb, u8, n, w, h, k, idx, ps, info, ch, &shared));
-        const float* compact = (const float*)ws.compact[1].p;
-        const uint32_t* pos = (const uint32_t*)ctx->trace[2].p + w;
+        const float* derived = (const float*)(pruned ? ws.compact[1].p : ws.plane[1].p);
         const size_t cap = ps.plan.cap_total;
         ch.push_back({true, [=](hipStream_t st) -> int {
-            StageTimer t(ctx, SSW_STAGE_EXTRACT, st);                               // :529-539, derived values from the compact plane
-            return launch_extract_shared_pruned(st, yb, compact, n, w, h, cap, pos, idx, k, c.method, c.alpha, ext);
+            StageTimer t(ctx, SSW_STAGE_EXTRACT, st);                               // :529-539
+            if (pos) return launch_extract_shared_pruned(st, yb, derived, n, w, h, cap, pos, idx, k, c.method, c.alpha, ext);
+            return launch_extract_shared(st, yb, derived, n, plane, idx, k, c.method, c.alpha, ext);
         }});
         return SSW_OK;
     };
-    SSW_TRY(run_pipeline(ctx, n_chunks, [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch) { return build_chunk(ci, ws, ch, ps.on); }));
-    if (!ps.on) return SSW_OK;
-    // One flag for the call: a column set that did not fit the compact plane means every chunk is redone with the full
-    // transform.  The one place the call waits for the device.
-    uint32_t host_info[SSW_PRUNE_INFO];
-    SSW_HIP_CHECK(hipMemcpyAsync(host_info, info, sizeof(host_info), hipMemcpyDeviceToHost, ctx->stream));
-    SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    ctx->pruned_chunks += n_chunks;
-    for (unsigned q = 0; q < ps.plan.n_classes; ++q) ctx->pruned_columns += host_info[1 + q];
-    if (host_info[0] == 0) return SSW_OK;
-    ctx->redone_chunks += n_chunks;
-    for (size_t ci = 0; ci < n_chunks; ++ci) {
-        Chain ch;
-        SSW_TRY(build_chunk(ci, ctx->lane[0], ch, false));
-        SSW_TRY(run_serial(ch, ctx->stream));
-    }
-    return SSW_OK;
+    return run_pruned_pipeline(ctx, n_chunks, ps, false, build_chunk);
 }
 
 // ---- Reader::extract against ONE derived frame that has not been transformed yet (single-image handles) ------
@@ -1588,7 +1583,8 @@ int trace_extract(ssw_ctx* ctx, const ssw_config& c, const float* yb, const uint
 // read (:469-480); a derived handle therefore only uploads its frame, and the transform happens here, when the base
 // reader's index list is known: the pruned transform of the batch path with n = 1 (same kernels, bit-identical
 // values).  Enqueues on the context's stream: the k extracted values into dev_out, the overflow flag into
-// dev_info[0] (non-zero: the columns did not fit, the caller must transform fully).  *applicable = false (nothing
+// dev_info[0] (non-zero: the columns did not fit, the caller must transform fully) -- enqueue-only, unlike
+// run_pruned_pipeline: the caller reads the flag with the download of the result.  *applicable = false (nothing
 // enqueued) when the shape or the settings do not take the pruned path.
 int extract_single_pruned(ssw_ctx* ctx, int precision, const void* derived_rgb, int u8, size_t w, size_t h, const float* base_y,
                           const uint32_t* idx, size_t k, int method, float alpha, float* dev_out, uint32_t** dev_info,
@@ -1603,12 +1599,12 @@ int extract_single_pruned(ssw_ctx* ctx, int precision, const void* derived_rgb, 
     SSW_TRY(grow(ctx->overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));
     uint32_t* info = (uint32_t*)ctx->overflow.p;
     Chain ch;
-    SSW_TRY(build_pruned_derived(ctx, ws, derived_rgb, u8, 1, w, h, k, idx, ps, info, ch));
+    const uint32_t* pos = nullptr;
+    SSW_TRY(build_pruned_derived(ctx, ws, derived_rgb, u8, 1, w, h, k, idx, ps, info, false, ch, &pos));
     SSW_TRY(run_serial(ch, ctx->stream));
     {
         StageTimer t(ctx, SSW_STAGE_EXTRACT, ctx->stream);
-        SSW_TRY(launch_extract_pruned(ctx->stream, base_y, (const float*)ws.compact[1].p, 1, w, h, ps.plan.cap_total,
-                                      (const uint32_t*)ws.prune_u32.p + w, idx, k, method, alpha, dev_out));
+        SSW_TRY(launch_extract_pruned(ctx->stream, base_y, (const float*)ws.compact[1].p, 1, w, h, ps.plan.cap_total, pos, idx, k, method, alpha, dev_out));
     }
     *dev_info = info;
     *applicable = true;

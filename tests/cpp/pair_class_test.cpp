@@ -7,6 +7,10 @@
 //  (2) The table against its neighbours: every forward class's frequency map equals ForwardClassLayout's natural(pos(slot, i));
 //      the classes of a level-2 pass and of a deep level-1 pass partition the frequencies; the flop of the eight level-2 classes
 //      is eight times that of O rotated "+", as build_deep_l2 assumes.
+//  (3) The class sources of the pruned row pass: tests/golden/prune_class_src_parent.txt holds what build_pruned_derived's own
+//      loop resolved per class of the plan BEFORE prune_class_sources existed (row plans of 3840, 1920, 1024 at level 2, 512
+//      deep at level 1, 1040 split and not split); the function must answer the same, and prune_gathered_offsets must lay the
+//      gathered bases out back to back in whole tiles of 16 rows.
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -144,9 +148,59 @@ static void neighbours() {
     }
 }
 
+static int sources(const char* path) {
+    std::FILE* f = std::fopen(path, "r");
+    if (!f) { std::printf("FAIL cannot open %s\n", path); return 1; }
+    char line[256];
+    int plans = 0;
+    while (std::fgets(line, sizeof line, f)) {
+        if (line[0] == '#' || line[0] == '\n') continue;
+        unsigned w = 0, n = 0; int strategy = 0, levels = 0, split = 0;
+        if (std::sscanf(line, "S %u %d %d %d %u", &w, &strategy, &levels, &split, &n) != 5 || n > 9) { std::printf("FAIL bad line %s", line); return 1; }
+        PassPlan rows;
+        rows.strategy = (PassStrategy)strategy; rows.levels = levels; rows.split = split != 0;
+        C cls[8];
+        const int n_cls = prune_class_list(rows, cls);
+        PruneClassSrc src[9];
+        PrunePlan plan;
+        const unsigned cap = 128;
+        prune_plan_classes(cls, n_cls, cap, plan);
+        const int got = prune_class_sources(cls, n_cls, rows, w, src);
+        CHECK(got == (int)n && plan.n_classes == n, "width %u: %d sources, %u plan classes, recorded %u", w, got, plan.n_classes, n);
+        for (unsigned c = 0; c < n; ++c) {
+            int r[10] = {0};
+            if (!std::fgets(line, sizeof line, f) || std::sscanf(line, "%d %d %d %d %d %d %d %d %d %d", &r[0], &r[1], &r[2], &r[3], &r[4], &r[5], &r[6], &r[7], &r[8], &r[9]) != 10) {
+                std::printf("FAIL bad source row\n"); return 1;
+            }
+            if ((int)c >= got) continue;
+            const PruneClassSrc& s = src[c];
+            CHECK(s.p1 == r[0] && s.p2 == r[1] && (int)s.y1 == r[2] && (!s.split || (int)s.y2 == r[3]) && (s.split || r[3] == -1), "width %u class %u: planes %d %d bases %d %d, recorded %d %d %d %d",
+                  w, c, s.p1, s.p2, (int)s.y1, (int)s.y2, r[0], r[1], r[2], r[3]);
+            CHECK((int)s.ydiv == r[4] && (int)s.src_rows == r[5] && (int)s.Kp == r[6] && (int)s.ktrue == r[7] && (int)s.split == r[8] && s.lane_buf == r[9],
+                  "width %u class %u: (%u %u %u %u %d %d), recorded (%d %d %d %d %d %d)", w, c, s.ydiv, s.src_rows, s.Kp, s.ktrue, (int)s.split, s.lane_buf, r[4], r[5], r[6], r[7], r[8], r[9]);
+        }
+        // the gathered bases: [Kp][cap rounded up to 16] doubles per basis, a split class's two one after the other, no gaps
+        size_t at = 0;
+        const size_t total = prune_gathered_offsets(plan, src);
+        for (unsigned c = 0; c < plan.n_classes && (int)c < got; ++c) {
+            const size_t bytes = (size_t)src[c].Kp * ((plan.c[c].cap + 15) & ~15u) * 8;
+            CHECK(src[c].goff == at, "width %u class %u: gathered offset %zu, expected %zu", w, c, src[c].goff, at);
+            at += bytes;
+            CHECK(src[c].goff2 == at, "width %u class %u: second gathered offset %zu, expected %zu", w, c, src[c].goff2, at);
+            if (src[c].split) at += bytes;
+        }
+        CHECK(total == at, "width %u: gathered bytes %zu, expected %zu", w, total, at);
+        ++plans;
+    }
+    std::fclose(f);
+    CHECK(plans == 6, "the recording has %d source plans", plans);
+    return 0;
+}
+
 int main(int argc, char** argv) {
-    if (argc < 2) { std::printf("usage: pair_class_test <recording>\n"); return 2; }
+    if (argc < 3) { std::printf("usage: pair_class_test <recording> <class sources>\n"); return 2; }
     if (replay(argv[1])) return 1;
+    if (sources(argv[2])) return 1;
     neighbours();
     if (failures) { std::printf("%d failures\n", failures); return 1; }
     std::printf("ok\n");

@@ -258,6 +258,30 @@ def test_two_chunks_on_two_lanes(smooth_frames):
         ctx.set_chunk_frames(0)
 
 
+def test_mixed_redo_with_base_prune_equals_the_unchunked_call(smooth_frames):
+    """The two-chunk input of test_pruned_path_falls_back_when_the_columns_do_not_fit with base pruning on: the 32 index lists
+    of the white-noise chunk use far more than the compact plane's 64 columns (each list alone about 59 of 384), so that chunk
+    is redone with the full transform, base frames included; the smooth chunk (all keys below column 24) fits.  Beside the
+    byte equality with base_prune = 0 (run_pair): the counters of both prunings, and the same bits as one chunk of 64 frames."""
+    base = np.concatenate([noise(N, H, W, 12), smooth_frames])
+    ctx = G.ctx()
+    ctx.set_chunk_frames(N)
+    try:
+        on, st, derived, marks = run_pair(base, K)
+    finally:
+        ctx.set_chunk_frames(0)
+    assert st["pruned_chunks"] == 2 and st["redone_chunks"] == 1, st
+    assert st["base_tiles"] == (2 + 1) * N * 3 and st["base_tiles_computed"] == 2 * 3 * N + N, st      # the noise chunk twice
+    whole = G.batch_extract(base, derived, K, marks)
+    assert on[0].tobytes() == whole[0].tobytes() and on[1].tobytes() == whole[1].tobytes()
+    ctx.set_prune(False)
+    try:
+        full = G.batch_extract(base, derived, K, marks)
+    finally:
+        ctx.set_prune(True)
+    assert on[0].tobytes() == full[0].tobytes() and on[1].tobytes() == full[1].tobytes()
+
+
 def test_two_tiles_wide():
     base = with_cosine(smooth(48, H, 256, 15), 128 + 40)
     base[::2] = smooth(24, H, 256, 16)

@@ -46,11 +46,13 @@ def test_pair_class_table_on_the_host(tmp_path):
     """csrc/dct_pair_class.hpp: the launch-class table answers what the per-class launch code answered before the table existed
     (tests/golden/pair_class_parent.txt: all 33600 tuples of class, pass, direction, layout, length, the rejected ones included,
     and the class rows of the pruned plans), and agrees with ForwardClassLayout, with a partition of the frequencies per pass
-    and with the flop the level-2 builders assume -- no GPU, no context."""
+    and with the flop the level-2 builders assume; the class sources of the pruned row pass answer what the loop they replaced
+    resolved (tests/golden/prune_class_src_parent.txt) -- no GPU, no context."""
     exe = os.path.join(str(tmp_path), "pair_class_test")
     subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "--offload-arch=gfx950", os.path.join(ROOT, "tests", "cpp", "pair_class_test.cpp"),
                     "-o", exe, "-L", LIBDIR, "-lssw_hip", f"-Wl,-rpath,{LIBDIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    out = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "pair_class_parent.txt")], capture_output=True, text=True)
+    out = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "pair_class_parent.txt"),
+                          os.path.join(ROOT, "tests", "golden", "prune_class_src_parent.txt")], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout
 
 

@@ -242,6 +242,51 @@ def test_4k_twelve_suspects(u8):
         assert np.array_equal(res[name], res5[name]), name
 
 
+def test_columns_that_do_not_fit_redo_every_chunk():
+    """The trace's redo branch (the shape of test_pruned_path_falls_back_when_the_columns_do_not_fit): k = 200 gives a compact
+    plane of 128 columns, 128 * 4 <= 1040, so pruning is attempted; the first 200 indices of this white-noise original touch
+    184 distinct columns (counted on the CPU with the oracle: O.indices of its plane, index % 1040), so the one list of the call
+    overflows by construction, the one flag is set, and all three chunks are redone with the full transform."""
+    w, h, k = 1040, 144, 200
+    base = np.random.default_rng(51).random((h, w, 3)).astype(np.float32)
+    marks = marks_for(5, k, 43)
+    sus = G.fingerprint(base, marks)
+    ctx = G.ctx()
+    ctx.set_chunk_frames(2)                            # three chunks on two lanes
+    try:
+        ctx.reset_timing()
+        res = trace(base, sus, marks)
+        st = ctx.prune_stats()
+        ctx.set_prune(False)
+        try:
+            full = trace(base, sus, marks)
+        finally:
+            ctx.set_prune(True)
+    finally:
+        ctx.set_chunk_frames(0)
+    assert st["pruned_chunks"] == 3 and st["redone_chunks"] == 3, st
+    for name in res:
+        assert np.array_equal(res[name], full[name], equal_nan=True), name
+
+
+def test_last_chunk_takes_the_other_row_route():
+    """The tuning of test_level2_and_fused_derived_kernels_on_a_small_frame with six suspects in chunks of five: the first
+    chunk's 720 lines (> merge_max_lines = 256) take the fused derived kernel, the last chunk's 144 lines the merged subset
+    launch, so the call's tables must hold the gathered bases in both orders."""
+    w, h, k = 1024, 144, 200
+    marks = marks_for(6, k, 21)
+    base, sus = scenario(O.synth_frame(21, 0, w, h), marks, u8=False)
+    with wm.tuning(efold_min=256, efold_inv_min=256, efold_cols_min=64, merge_max_lines=256), G.fresh_ctx() as ctx:
+        whole = trace(base, sus, marks)
+        ctx.set_chunk_frames(5)
+        ctx.reset_timing()
+        res = trace(base, sus, marks)
+        st = ctx.prune_stats()
+    assert st["pruned_chunks"] == 2 and st["redone_chunks"] == 0, st
+    for name in whole:
+        assert np.array_equal(res[name], whole[name], equal_nan=True), name
+
+
 # 5. independence -------------------------------------------------------------------------------------------------------
 def test_rows_independent_of_company_and_position():
     w, h, k = 768, 256, 200

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Bit-for-bit A/B of two builds of the library (e.g. lib/libssw_hip.so against a variant of tools/build_variant.sh): every build
 runs in a child process (SSW_LIB_PATH), transforms the same synthetic frames -- ssw_dct2d forward, orthonormal and inverse on
-shapes of every strategy, one batch embed + extract -- and prints a digest per case; the parent compares the digests.
+shapes of every strategy, one batch embed + extract, one trace at two chunks, one handle extract against a derived frame that
+is still RGB (the three users of the pruned derived transform) -- and prints a digest per case; the parent compares the digests.
 usage: python tools/lib_ab_check.py [--stages] LIB_A LIB_B
        --stages: also the stage accounts of every case (ssw_ctx_get_timing launch counts, ssw_ctx_get_work, ssw_ctx_get_traffic),
                  the cases again at folding levels 0, 1, 3, 4, 6 and with the odd split off on the 4K, 1080p and 512 x 272 shapes,
@@ -86,6 +87,35 @@ def child():
         if tag:
             ctx.set_dct_folding(True)
             ctx.set_odd_split(True)
+    if os.environ.get("SSW_AB_PRUNE_USERS") == "1":      # the A/B only: tests/golden/gemm_digests.json predates these cases
+        # the other two users of the pruned derived transform: ssw_fingerprint_trace at two chunks (the call's tables, read by both
+        # chunks), and a handle Reader.extract against a derived frame that is still RGB (lane 0's tables, one frame)
+        h, w, n, k = 1080, 1920, 6, 500
+        cfg = L.Config(L.ORDER_ENERGY, L.OPTION2, 0.1, L.PRECISION_F64)
+        marks = np.random.default_rng(4).standard_normal((n, k)).astype(np.float32)
+        base, dm = ctx.alloc(h * w * 12), ctx.to_device(marks)
+        check(lib.ssw_synth_frames(ctx.handle, 7, 0, 1, w, h, base.ptr), "synth")
+        sus, ext, sims = ctx.alloc(n * h * w * 12), ctx.alloc(n * k * 4), ctx.alloc(n * n * 4)
+        best, best_sim, n_exceed = ctx.alloc(n * 4), ctx.alloc(n * 4), ctx.alloc(n * 4)
+        check(lib.ssw_fingerprint_embed(ctx.handle, C.byref(cfg), base.ptr, w, h, dm.ptr, n, k, sus.ptr, None), "fingerprint")
+        ctx.set_chunk_frames(3)
+        if stages:
+            ctx.reset_timing()
+        check(lib.ssw_fingerprint_trace(ctx.handle, C.byref(cfg), base.ptr, sus.ptr, n, w, h, k, dm.ptr, n, C.c_float(6.0), ext.ptr, sims.ptr,
+                                        best.ptr, best_sim.ptr, n_exceed.ptr), "trace")
+        ctx.set_chunk_frames(0)
+        for nm, b, dt, shp in (("ext", ext, np.float32, (n, k)), ("sims", sims, np.float32, (n, n)), ("best", best, np.uint32, (n,))):
+            print(f"DIGEST trace {h}x{w}x{n} {nm} {hashlib.sha256(b.to_host(dt, shp).tobytes()).hexdigest()[:16]}", flush=True)
+        accounts(f"trace {h}x{w}x{n}")
+        frame, copy = base.to_host(np.float32, (h, w, 3)), sus.to_host(np.float32, (n, h, w, 3))[0]
+        for b in (base, dm, sus, ext, sims, best, best_sim, n_exceed):
+            b.free()
+        reader = wm.Reader.base(frame, wm.ReadConfig(precision=wm.Precision.F64), ctx)
+        if stages:
+            ctx.reset_timing()
+        got = reader.extract(wm.Reader.derived(copy, ctx, wm.Precision.F64), k)
+        print(f"DIGEST handle {h}x{w} ext {hashlib.sha256(np.asarray(got, np.float32).tobytes()).hexdigest()[:16]}", flush=True)
+        accounts(f"handle {h}x{w}")
     ctx.close()
 
 
@@ -113,7 +143,9 @@ def main():
         print(f"{len(d)} digests -> {sys.argv[3]}")
         return 0
     args = [a for a in sys.argv[1:] if a != "--stages"]
-    env = {"SSW_AB_STAGES": "1"} if "--stages" in sys.argv else None
+    env = {"SSW_AB_PRUNE_USERS": "1"}
+    if "--stages" in sys.argv:
+        env["SSW_AB_STAGES"] = "1"
     libs = args[:2]
     try:
         res = [digests(lib, env) for lib in libs]
