@@ -609,6 +609,52 @@ int ssw_locate_scaled_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, 
 int ssw_locate_rung_boxes(ssw_ctx* ctx, const void* dev_suspect, size_t sw, size_t sh, size_t channels, size_t pw, size_t ph,
                           uint8_t* host_boxes);
 
+/* ---- identifying a suspect's original: an image catalogue searched on the device ---- */
+/* Every stage above starts from "here is the original"; the finder of a leaked picture who owns a few thousand originals does
+   not know which one it is.  These calls answer that, and so precede everything the reference's `test` command does with an
+   original it is handed (the loop of examples/main.rs:369-415, Reader::base, src/algorithm.rs:462-464); the reference itself has
+   no such step.  Everything is an integer, no sum depends on its order, and the results equal the numpy restatement in
+   tests/test_identify_cpu.py exactly.
+   Signature of a frame F [h][w][c] u8, c = 3 or 4, w, h >= 32:
+     An alpha channel is ignored.  Luma is the one ssw_locate_rgb8 uses: L(p) = (77 R + 150 G + 29 B + 128) >> 8.
+     The grid is 32 x 32.  Cell (i, j) covers x in [floor(i w / 32), floor((i + 1) w / 32)) and y in [floor(j h / 32),
+     floor((j + 1) h / 32)); it is never empty, since w, h >= 32.
+     sig[j][i] = (sum of L over the cell + n / 2) / n, n the cell's pixel count, integer division.  1024 bytes, row-major.
+   Distance D(a, b) = sum_{t < 1024} |a[t] - b[t]|; at most 261 120, which fits 32 bits.
+   Match of a query signature against a catalogue of nc signatures: the `top` entries (1 <= top <= 8) with the smallest
+     (D, index) in lexicographic order -- ties go to the lower index; when nc < top the remaining slots hold index 0xFFFFFFFF and
+     distance 0xFFFFFFFF.
+   What it finds (measured with this definition on a 640 x 444 photograph, tests/test_identify_cpu.py): a marked copy of an
+   original, as it is or resized anywhere between a tenth and one and a half times its size, re-encoded as JPEG or squeezed to
+   another aspect ratio, lies at 2 900 .. 4 800 from its original, and every unrelated entry (the same picture rolled by 40
+   columns included) at more than 15 000.
+   Known limits: (1) a cut-out is NOT separable from unrelated images (a 580 x 404 cut-out of that photograph scores about
+   13 000 against its own original, a zoomed crop about 15 000): cut-outs still need the original named, then ssw_locate_rgb8;
+   (2) mirrored or turned copies do not match; (3) near-duplicates shifted by a pixel or two are not told apart.
+   Timing: both calls are timed under SSW_STAGE_LOCATE (bytes); there is no stage of their own, because the number of stages
+   is part of what callers and tests of this header rely on. */
+typedef struct ssw_image_shape { uint32_t w, h, channels; } ssw_image_shape;
+/* Signatures of n frames of DIFFERENT sizes and channel counts -> dev_sigs [n][1024].  dev_frames / shapes: HOST arrays of n
+   device pointers / n shapes; frame i is [shapes[i].h][shapes[i].w][shapes[i].channels] u8.  No alignment is assumed of any
+   pointer or of w * channels.  Only enqueues on the context's stream (no host wait; launch descriptors travel as kernel
+   arguments, 32 frames per launch).  SSW_ERR_BAD_ARG: w or h < 32, channels not 3 or 4, a null pointer; SSW_ERR_UNSUPPORTED: a
+   frame whose cells hold more than 2^24 pixels each; n == 0: SSW_OK. */
+int ssw_signature_rgb8(ssw_ctx* ctx, const void* const* dev_frames, const ssw_image_shape* shapes, size_t n, uint8_t* dev_sigs);
+/* The same on host images, one pointer per frame -> host_sigs [n][1024]: the frames are uploaded in groups of at most 256 MiB
+   of workspace (one frame's own size if that is more), like the host forms of the trace, and the call returns when every
+   buffer is the caller's again.  Bit-identical to the device form. */
+int ssw_signature_host_rgb8(ssw_ctx* ctx, const uint8_t* const* host_frames, const ssw_image_shape* shapes, size_t n,
+                            uint8_t* host_sigs);
+/* Match nq query signatures dev_query [nq][1024] against nc catalogue signatures dev_catalogue [nc][1024]:
+     dev_index [nq][top], dev_dist [nq][top]   the answer defined above, best first
+     dev_all [nq][nc]                          (may be NULL) every distance
+   Only enqueues on the context's stream.  The catalogue is read once per 128 queries and goes through the kernel in chunks
+   of 32768 entries inside the call; indices are positions in dev_catalogue whatever the chunking.  No alignment is assumed.
+   SSW_ERR_BAD_ARG: top outside 1 .. 8, nc >= 2^32, a null pointer; nq == 0: SSW_OK; nc == 0: SSW_OK with every slot at
+   0xFFFFFFFF. */
+int ssw_signature_match(ssw_ctx* ctx, const uint8_t* dev_query, size_t nq, const uint8_t* dev_catalogue, size_t nc, size_t top,
+                        uint32_t* dev_index, uint32_t* dev_dist, uint32_t* dev_all);
+
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,
    and `into_rgb16()` from Rgb32F: round(clamp(v,0,1) * 65535) (`image 0.24.3`, like the 8-bit forms). */

@@ -16,6 +16,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -360,6 +361,82 @@ inline std::vector<Located> locate_scaled(Context& ctx, const ImageRgb8& origina
         out[i] = Located{Placement{pl[i].x, pl[i].y, pl[i].pw, pl[i].ph}, sad[i], (double)sad[i] / ((double)pl[i].pw * (double)pl[i].ph)};
     return out;
 }
+
+// ssw_signature_host_rgb8 on host images of any sizes: 1024 bytes per image, in the order of `images`.
+inline std::vector<std::array<uint8_t, 1024>> signature(Context& ctx, const std::vector<Suspect>& images) {
+    const size_t n = images.size();
+    std::vector<const uint8_t*> ptrs(n);
+    std::vector<ssw_image_shape> shapes(n);
+    for (size_t i = 0; i < n; ++i) {
+        ptrs[i] = images[i].data;
+        shapes[i] = ssw_image_shape{(uint32_t)images[i].width, (uint32_t)images[i].height, (uint32_t)images[i].channels};
+    }
+    std::vector<std::array<uint8_t, 1024>> out(n);
+    check(ssw_signature_host_rgb8(ctx.get(), ptrs.data(), shapes.data(), n, n ? out[0].data() : nullptr), "signature");
+    return out;
+}
+
+// The originals someone owns, as signatures: which of them is a suspect a copy of?  The stage in front of locate / Reader::trace
+// (ssw_signature_match; include/ssw.h states the definition and what it cannot find: cut-outs, mirrored and turned copies).
+// The signatures stay on the device between match calls and go up again only after an add.
+class Catalogue {
+public:
+    struct Match {
+        static constexpr uint32_t none = 0xFFFFFFFFu;
+        uint32_t index = none, distance = none;        // position among the entries added; both `none` beyond the catalogue's size
+    };
+    explicit Catalogue(Context& ctx) : ctx_(ctx) {}
+    ~Catalogue() { if (dev_) ssw_dev_free(ctx_.get(), dev_); }
+    Catalogue(const Catalogue&) = delete;
+    Catalogue& operator=(const Catalogue&) = delete;
+    size_t size() const { return names_.size(); }
+    const std::string& name(size_t i) const { return names_[i]; }
+    void add(const std::string& name, const Suspect& image) {
+        const auto sig = signature(ctx_, {image});
+        names_.push_back(name);
+        sigs_.insert(sigs_.end(), sig[0].begin(), sig[0].end());
+    }
+    // per suspect the `top` (1 .. 8) nearest entries, nearest first, ties to the lower index
+    std::vector<std::vector<Match>> match(const std::vector<Suspect>& suspects, size_t top = 1) {
+        const size_t nq = suspects.size();
+        std::vector<std::vector<Match>> out(nq, std::vector<Match>(top));
+        if (nq == 0) return out;
+        const auto q = signature(ctx_, suspects);
+        if (dev_n_ != size()) {
+            if (dev_) check(ssw_dev_free(ctx_.get(), dev_), "Catalogue::match");
+            dev_ = nullptr;
+            if (size()) {
+                check(ssw_dev_alloc(ctx_.get(), sigs_.size(), &dev_), "Catalogue::match");
+                check(ssw_copy_to_dev(ctx_.get(), dev_, sigs_.data(), sigs_.size()), "Catalogue::match");
+            }
+            dev_n_ = size();
+        }
+        void* dq = nullptr;
+        void* res = nullptr;
+        struct Free {
+            ssw_ctx* c; void*& a; void*& b;
+            ~Free() { if (a) ssw_dev_free(c, a); if (b) ssw_dev_free(c, b); }
+        } guard{ctx_.get(), dq, res};
+        check(ssw_dev_alloc(ctx_.get(), nq * 1024, &dq), "Catalogue::match");
+        check(ssw_copy_to_dev(ctx_.get(), dq, q[0].data(), nq * 1024), "Catalogue::match");
+        check(ssw_dev_alloc(ctx_.get(), 2 * nq * top * sizeof(uint32_t), &res), "Catalogue::match");
+        uint32_t* idx = static_cast<uint32_t*>(res);
+        check(ssw_signature_match(ctx_.get(), static_cast<const uint8_t*>(dq), nq, static_cast<const uint8_t*>(dev_), size(), top, idx,
+                                  idx + nq * top, nullptr), "Catalogue::match");
+        std::vector<uint32_t> host(2 * nq * top);
+        check(ssw_copy_to_host(ctx_.get(), host.data(), res, host.size() * sizeof(uint32_t)), "Catalogue::match");
+        for (size_t s = 0; s < nq; ++s)
+            for (size_t t = 0; t < top; ++t) out[s][t] = Match{host[s * top + t], host[(nq + s) * top + t]};
+        return out;
+    }
+
+private:
+    Context& ctx_;
+    std::vector<std::string> names_;
+    std::vector<uint8_t> sigs_;
+    void* dev_ = nullptr;
+    size_t dev_n_ = 0;
+};
 
 class Reader {                                         // algorithm.rs:441-594
 public:

@@ -48,6 +48,17 @@ class ScaleRange(C.Structure):
     _fields_ = [("wmin", C.c_uint32), ("wmax", C.c_uint32)]
 
 
+class ImageShape(C.Structure):
+    """ssw_image_shape (include/ssw.h): one frame of ssw_signature_rgb8, [h][w][channels] u8."""
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("channels", C.c_uint32)]
+
+
+# ssw_signature_rgb8 / ssw_signature_match (csrc/catalogue.hip): bytes of a signature, the sentinel of an empty slot, and the
+# kernel's constants -- catalogue entries of a tile, of one launch (chunk), queries of a tile
+SIGNATURE_BYTES = 1024
+MATCH_NONE = 0xFFFFFFFF
+MATCH_TILE, MATCH_CHUNK, MATCH_QUERY_TILE, MATCH_TOP_MAX = 128, 32768, 128, 8
+
 _vp, _f32p, _u32p, _u64p, _sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t
 _cfgp = C.POINTER(Config)
 _plp = C.POINTER(Placement)
@@ -136,6 +147,9 @@ SIGNATURES = {
     "ssw_locate_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, C.POINTER(C.c_uint64)]),
     "ssw_locate_scaled_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, C.POINTER(ScaleRange), _sz, C.POINTER(C.c_uint64)]),
     "ssw_locate_rung_boxes": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp]),
+    "ssw_signature_rgb8": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(ImageShape), _sz, _vp]),
+    "ssw_signature_host_rgb8": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(ImageShape), _sz, _vp]),
+    "ssw_signature_match": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _u32p, _u32p, _u32p]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
                                                            _f32p, _f32p, _u32p, _f32p, _u32p]),
     "ssw_reader_trace_restored_host_rgb8": (C.c_int, [_vp, _vp, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p,

@@ -20,7 +20,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass, field
-from typing import Callable, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -928,6 +928,175 @@ def trace_many(base, suspects, marks, k: Optional[int] = None, threshold: float 
     check(ctx._lib.ssw_fingerprint_trace_host_rgb8(ctx.handle, C.byref(cfg), b.ctypes.data, ptrs, len(arrs), w, h, k,
                                                    *res._args(m, threshold)), "ssw_fingerprint_trace_host_rgb8")
     return res
+
+
+# ---- identifying a suspect's original: an image catalogue (include/ssw.h: ssw_signature_rgb8, ssw_signature_match) -----------
+IDENTIFY_MAX_DISTANCE = 8192
+
+
+def _sig_frames(images):
+    arrs = [np.ascontiguousarray(np.asarray(im)) for im in images]
+    for a in arrs:
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4):
+            raise ValueError("images must be 8-bit [h, w, 3] or [h, w, 4] arrays")
+        if a.shape[0] < 32 or a.shape[1] < 32:
+            raise ValueError(f"a {a.shape[1]}x{a.shape[0]} image is too small for a signature (32x32 at least)")
+    return arrs
+
+
+def signature(images, ctx: Optional[Context] = None) -> np.ndarray:
+    """The signatures of 8-bit images of any sizes, [h, w, 3] or [h, w, 4] (alpha is ignored) -> uint8 [n][1024]: the rounded
+    mean luma of the cells of a 32 x 32 grid, integers only (include/ssw.h states the definition); one call,
+    ssw_signature_host_rgb8."""
+    arrs = _sig_frames(images)
+    out = np.empty((len(arrs), L.SIGNATURE_BYTES), np.uint8)
+    if not arrs:
+        return out
+    ctx = ctx or default_context()
+    ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    shapes = (L.ImageShape * len(arrs))(*[L.ImageShape(a.shape[1], a.shape[0], a.shape[2]) for a in arrs])
+    check(ctx._lib.ssw_signature_host_rgb8(ctx.handle, ptrs, shapes, len(arrs), out.ctypes.data), "ssw_signature_host_rgb8")
+    return out
+
+
+class Catalogue:
+    """The originals someone owns, as signatures: `add` them once, `save` the file, and `match` / `identify` name the original of
+    a suspect picture -- the stage in front of `locate`, `restore` and `trace_many`, which all start from "here is the
+    original".  The signatures stay on the device between `match` calls (uploaded again only after an `add`)."""
+
+    def __init__(self, ctx: Optional[Context] = None):
+        self._ctx = ctx
+        self.names: List[str] = []
+        self.marks_files: List[Optional[str]] = []
+        self._sigs = np.zeros((0, L.SIGNATURE_BYTES), np.uint8)
+        self._sizes = np.zeros((0, 2), np.uint32)
+        self._dev: Optional[DeviceBuffer] = None
+        self._dev_n = -1
+
+    def __len__(self):
+        return len(self.names)
+
+    @property
+    def signatures(self) -> np.ndarray:
+        return self._sigs
+
+    @property
+    def sizes(self) -> np.ndarray:
+        return self._sizes
+
+    def add_signatures(self, names, signatures, sizes, marks_files=None) -> None:
+        """Entries whose signatures are known already (a loaded file, another catalogue): no device work."""
+        sig = np.ascontiguousarray(signatures, np.uint8).reshape(-1, L.SIGNATURE_BYTES)
+        sizes = np.asarray(sizes, np.uint32).reshape(-1, 2)
+        names = [str(x) for x in names]
+        marks_files = list(marks_files) if marks_files is not None else [None] * len(names)
+        if not (len(names) == len(marks_files) == sig.shape[0] == sizes.shape[0]):
+            raise ValueError("Catalogue: names, signatures, sizes and marks_files differ in length")
+        self.names += names
+        self.marks_files += [str(m) if m else None for m in marks_files]
+        self._sigs = np.concatenate([self._sigs, sig])
+        self._sizes = np.concatenate([self._sizes, sizes])
+
+    def add(self, name: str, image, marks_file: Optional[str] = None) -> None:
+        self.add_many([name], [image], [marks_file])
+
+    def add_many(self, names, images, marks_files=None) -> None:
+        """`add` for several originals with one signature call."""
+        arrs = _sig_frames(images)
+        self.add_signatures(names, signature(arrs, self._context()), [(a.shape[1], a.shape[0]) for a in arrs], marks_files)
+
+    def _context(self) -> Context:
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
+
+    def _resident(self) -> Optional[DeviceBuffer]:
+        if self._dev_n != len(self):
+            if self._dev is not None:
+                self._dev.free()
+            self._dev = self._context().to_device(self._sigs) if len(self) else None
+            self._dev_n = len(self)
+        return self._dev
+
+    def match_signatures(self, signatures, top: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """(index [nq][top], distance [nq][top]) of the `top` nearest entries per query signature, nearest first, ties to the
+        lower index; slots beyond the catalogue's size hold 0xFFFFFFFF in both (ssw_signature_match)."""
+        if not 1 <= int(top) <= L.MATCH_TOP_MAX:
+            raise ValueError(f"top must be 1 .. {L.MATCH_TOP_MAX}")
+        q = np.ascontiguousarray(signatures, np.uint8).reshape(-1, L.SIGNATURE_BYTES)
+        nq, top = q.shape[0], int(top)
+        if nq == 0:
+            return np.zeros((0, top), np.uint32), np.zeros((0, top), np.uint32)
+        ctx = self._context()
+        cat = self._resident()
+        dq, dout = ctx.to_device(q), ctx.alloc(2 * nq * top * 4)
+        try:
+            check(ctx._lib.ssw_signature_match(ctx.handle, dq.ptr, nq, cat.ptr if cat is not None else None, len(self), top, dout.ptr,
+                                               C.c_void_p(dout.ptr.value + nq * top * 4), None), "ssw_signature_match")
+            both = dout.to_host(np.uint32, (2, nq, top))
+        finally:
+            dq.free()
+            dout.free()
+        return both[0], both[1]
+
+    def match(self, suspects, top: int = 1) -> list:
+        """Per suspect image the `top` nearest originals, nearest first: [[(name, distance, (w, h)), ...], ...] (fewer than
+        `top` entries when the catalogue is smaller).  One signature call and one match call for all suspects."""
+        idx, dist = self.match_signatures(signature(suspects, self._context()), top)
+        return [[(self.names[i], int(d), (int(self._sizes[i][0]), int(self._sizes[i][1]))) for i, d in zip(row_i, row_d) if i != L.MATCH_NONE]
+                for row_i, row_d in zip(idx, dist)]
+
+    def save(self, path: str) -> None:
+        from .storage import save_catalogue
+        save_catalogue(path, self.names, self._sigs, self._sizes, self.marks_files)
+
+    @staticmethod
+    def load(path: str, ctx: Optional[Context] = None) -> "Catalogue":
+        from .storage import load_catalogue
+        names, sig, sizes, marks = load_catalogue(path)
+        c = Catalogue(ctx)
+        c.add_signatures(names, sig, sizes, marks)
+        return c
+
+    def __del__(self):
+        try:
+            if self._dev is not None:
+                self._dev.free()
+        except Exception:
+            pass
+
+
+@dataclass
+class Identified:
+    """`identify`'s answer for one suspect.  name: the original it is a copy of, or None when even the nearest entry is further
+    than max_distance; nearest / distance / size / marks_file / index describe that nearest entry either way; candidates: the
+    `top` nearest as (name, distance, (w, h)), nearest first."""
+    name: Optional[str]
+    nearest: Optional[str]
+    distance: Optional[int]
+    size: Optional[Tuple[int, int]]
+    marks_file: Optional[str]
+    index: Optional[int]
+    candidates: list
+
+
+def identify(catalogue: Catalogue, suspects, top: int = 1, max_distance: int = IDENTIFY_MAX_DISTANCE) -> list:
+    """Which original is each suspect a copy of?  One `Identified` per suspect.  max_distance: the largest signature distance
+    that still counts as "the same picture".  The default 8192 is a mean of 8 per cell; it lies between the largest distance
+    measured for a genuine whole-frame copy (4715, a 640 x 444 photograph reduced to 64 x 44) and the smallest measured for an
+    unrelated entry (15 640, the same photograph rolled by 40 columns) -- exactly that, not a guarantee.  Cut-outs are NOT
+    identified (a cut-out is as far from its original as an unrelated picture), nor mirrored or turned copies."""
+    idx, dist = catalogue.match_signatures(signature(suspects, catalogue._context()), top)
+    out = []
+    for row_i, row_d in zip(idx, dist):
+        cands = [(catalogue.names[i], int(d), (int(catalogue.sizes[i][0]), int(catalogue.sizes[i][1]))) for i, d in zip(row_i, row_d)
+                 if i != L.MATCH_NONE]
+        if not cands:
+            out.append(Identified(None, None, None, None, None, None, []))
+            continue
+        i, (name, d, size) = int(row_i[0]), cands[0]
+        out.append(Identified(name if d <= max_distance else None, name, d, size, catalogue.marks_files[i], i, cands))
+    return out
 
 
 # ---- Tester (algorithm.rs:668-715) -------------------------------------------------------------

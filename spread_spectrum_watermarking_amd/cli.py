@@ -19,6 +19,15 @@
            --locate finds where a cut-out belongs (the size WxH it had in the base when it was scaled afterwards) by a
            search over every translation on the GPU; its record says "Located:" too.  FILE=W0..W1: the size is not known
            either, only that the cut-out was between W0 and W1 wide in the base -- a search over scale as well
+    python -m spread_spectrum_watermarking_amd.cli index FILES... -o catalogue.npz [--marks FILE_fp.json ...]
+        -> creates catalogue.npz or appends to it: one signature (1024 bytes) per original, with its size and the marks file
+           that goes with it (given in the order of FILES, else <stem>_fp.json beside the image where that exists)
+    python -m spread_spectrum_watermarking_amd.cli identify SUSPECTS... --catalogue catalogue.npz [--top N] [--max-distance D]
+        -> one record per suspect: the original it is a copy of, found among all signatures on the GPU, or none when even
+           the nearest is further than D (whole-frame copies only: cut-outs, mirrored and turned copies are not identified)
+    python -m spread_spectrum_watermarking_amd.cli trace --catalogue catalogue.npz --suspects A.png B.png ... [--marks ...]
+        -> `identify` for every suspect in one call, then the trace above once per original that was named, with the marks
+           file the catalogue holds for it; every record gains an "Original:" line
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -32,7 +41,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .api import Locate, MarkBuf, Placement, Reader, Tester, TraceResult, Writer, locate
+from .api import IDENTIFY_MAX_DISTANCE, Catalogue, Locate, MarkBuf, Placement, Reader, Tester, TraceResult, Writer, identify, locate
 from .storage import Configuration, DescribedWatermark, Version1Storage
 
 _ORDERING_ARGS = {"energy": "Energy", "energy-orthogonal": "EnergyOrthogonal", "legacy": "Legacy"}
@@ -145,6 +154,13 @@ class _TraceParser(argparse.ArgumentParser):
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
         if getattr(a, "command", None) == "trace":
+            # the original and the marks may come from a catalogue instead; without one they are required, in argparse's words
+            needed = ["--suspects"] if a.catalogue is not None else ["base", "--suspects", "--marks"]
+            missing = [n for n in needed if getattr(a, n.lstrip("-")) is None]
+            if missing:
+                self.trace_parser.error("the following arguments are required: " + ", ".join(missing))
+            if a.catalogue is not None and a.base is not None:
+                self.trace_parser.error("give the original or --catalogue, not both")
             try:
                 a.placements = trace_placements(a.suspects, a.place)
                 a.locates = trace_locates(a.suspects, a.locate, a.placements)
@@ -181,14 +197,30 @@ def build_parser() -> argparse.ArgumentParser:
     r = sub.add_parser("trace", help="Name, for each suspect file, the stored watermark it carries.")
     r.add_argument("--similarity-exceed", type=float, default=6.0,
                    help="If the similarity exceeds this value it is considered to be matching.")
-    r.add_argument("base", help="The original file.")
-    r.add_argument("--suspects", nargs="+", required=True, help="The files to trace.")
-    r.add_argument("--marks", nargs="+", required=True, help="The watermark files to test from.")
+    r.add_argument("base", nargs="?", default=None, help="The original file (not with --catalogue).")
+    r.add_argument("--suspects", nargs="+", help="The files to trace.")
+    r.add_argument("--marks", nargs="+", help="The watermark files to test from (with --catalogue: besides the catalogue's own).")
+    r.add_argument("--catalogue", default=None, metavar="CATALOGUE.npz",
+                   help="Name each suspect's original from this catalogue (see `index`) instead of giving it.")
+    r.add_argument("--max-distance", type=int, default=IDENTIFY_MAX_DISTANCE,
+                   help="With --catalogue: the largest signature distance that still names an original.")
+    p.trace_parser = r
     r.add_argument("--place", action="append", metavar="FILE=X,Y[,WxH]",
                    help="Where the cut-out FILE (one of --suspects) lies in the base, and the size it had there. Repeatable.")
     r.add_argument("--locate", action="append", metavar="FILE[=WxH|=W0..W1]",
                    help="Find where the cut-out FILE (one of --suspects) lies in the base; WxH: the size it had there; "
                         "W0..W1: the widths it may have had there (the scale is searched too). Repeatable.")
+    x = sub.add_parser("index", help="Add originals to an image catalogue (created when it does not exist).")
+    x.add_argument("files", nargs="+", help="The originals.")
+    x.add_argument("-o", "--output", required=True, metavar="CATALOGUE.npz", help="The catalogue file.")
+    x.add_argument("--marks", nargs="+", default=None, metavar="FILE_fp.json",
+                   help="The marks file of each original, in the order of the files (default: <stem>_fp.json beside it, if there).")
+    i = sub.add_parser("identify", help="Name, for each suspect file, the original in the catalogue it is a copy of.")
+    i.add_argument("suspects", nargs="+", help="The files to identify.")
+    i.add_argument("--catalogue", required=True, metavar="CATALOGUE.npz", help="The catalogue file (see `index`).")
+    i.add_argument("--top", type=int, default=1, help="Also list the runners-up, N entries in all (1 .. 8).")
+    i.add_argument("--max-distance", type=int, default=IDENTIFY_MAX_DISTANCE,
+                   help="The largest signature distance that still names an original.")
     return p
 
 
@@ -283,7 +315,95 @@ def group_stored_marks(stored: List[Tuple[str, Version1Storage]]) -> Dict[Tuple[
     return groups
 
 
+def default_marks_file(image_path: str) -> Optional[str]:
+    """<stem>_fp.json beside the image (what `fingerprint` writes), if it exists."""
+    path = os.path.splitext(image_path)[0] + "_fp.json"
+    return path if os.path.exists(path) else None
+
+
+def cmd_index(args, out=sys.stdout) -> int:
+    if args.marks is not None and len(args.marks) != len(args.files):
+        raise SystemExit(f"--marks: {len(args.marks)} files for {len(args.files)} originals (one each, in order)")
+    cat = Catalogue.load(args.output) if os.path.exists(args.output) else Catalogue()
+    marks = args.marks if args.marks is not None else [default_marks_file(f) for f in args.files]
+    cat.add_many(args.files, [_open_image(f) for f in args.files], marks)
+    cat.save(args.output)
+    print(f"{len(args.files)} added, {len(cat)} originals in {args.output}", file=out)
+    return 0
+
+
+def original_text(r) -> str:
+    """The value of a record's "Original:" line for one `Identified`."""
+    if r.nearest is None:
+        return "none (the catalogue is empty)"
+    name = r.nearest.replace('"', '\\"')
+    if r.name is None:
+        return f"none (nearest \"{name}\", distance {r.distance})"
+    return f"\"{name}\" {r.size[0]}x{r.size[1]} (distance {r.distance})"
+
+
+def cmd_identify(args, out=sys.stdout) -> int:
+    if not 1 <= args.top <= 8:
+        raise SystemExit("--top must be 1 .. 8")
+    cat = Catalogue.load(args.catalogue)
+    found = identify(cat, [_open_suspect(p) for p in args.suspects], args.top, args.max_distance)
+    for path, r in zip(args.suspects, found):
+        print("-", file=out)
+        print(f"  Suspect: \"{path}\"", file=out)
+        print(f"  Original: {original_text(r)}", file=out)
+        for name, d, (w, h) in r.candidates[1:]:
+            n = name.replace('"', '\\"')
+            print(f"  Next: \"{n}\" {w}x{h} (distance {d})", file=out)
+    return 0
+
+
+def _beside(path: str, catalogue_path: str) -> str:
+    """A file named in a catalogue: as it is named, else relative to the catalogue's directory."""
+    if os.path.exists(path) or os.path.isabs(path):
+        return path
+    return os.path.join(os.path.dirname(os.path.abspath(catalogue_path)), path)
+
+
+def cmd_trace_catalogue(args, out=sys.stdout) -> int:
+    """trace --catalogue: every suspect identified in one match call, then today's trace once per original that was named,
+    with its stored marks file; an unidentified suspect gets a record that says so and is not traced."""
+    import argparse as _ap
+    import io
+    cat = Catalogue.load(args.catalogue)
+    found = identify(cat, [_open_suspect(p) for p in args.suspects], 1, args.max_distance)
+    groups: Dict[int, List[int]] = {}
+    for s, r in enumerate(found):
+        if r.name is not None:
+            groups.setdefault(r.index, []).append(s)
+    records: Dict[int, List[str]] = {}
+    for index, members in groups.items():
+        r = found[members[0]]
+        marks = ([_beside(r.marks_file, args.catalogue)] if r.marks_file else []) + list(args.marks or [])
+        if not marks:
+            raise SystemExit(f"{r.name}: the catalogue holds no marks file for it and no --marks was given")
+        paths = [args.suspects[s] for s in members]
+        sub = _ap.Namespace(base=_beside(r.name, args.catalogue), suspects=paths, marks=marks, similarity_exceed=args.similarity_exceed,
+                            placements={k: v for k, v in getattr(args, "placements", {}).items() if k in paths},
+                            locates={k: v for k, v in getattr(args, "locates", {}).items() if k in paths})
+        buf = io.StringIO()
+        cmd_trace(sub, buf)
+        lines = buf.getvalue().splitlines()
+        starts = [i for i, ln in enumerate(lines) if ln == "-"] + [len(lines)]
+        for s, a, b in zip(members, starts[:-1], starts[1:]):
+            records[s] = lines[a:b]
+    for s, path in enumerate(args.suspects):
+        rec = records.get(s) or ["-", f"  Suspect: \"{path}\""]
+        for ln in rec[:2]:
+            print(ln, file=out)
+        print(f"  Original: {original_text(found[s])}", file=out)
+        for ln in rec[2:]:
+            print(ln, file=out)
+    return 0
+
+
 def cmd_trace(args, out=sys.stdout) -> int:
+    if getattr(args, "catalogue", None) is not None:
+        return cmd_trace_catalogue(args, out)
     base = _open_image(args.base)
     suspects = [_open_suspect(p) for p in args.suspects]
     H, W = base.shape[:2]
@@ -381,6 +501,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         return cmd_fingerprint(args)
     if args.command == "trace":
         return cmd_trace(args)
+    if args.command == "index":
+        return cmd_index(args)
+    if args.command == "identify":
+        return cmd_identify(args)
     return 0
 
 

@@ -101,3 +101,35 @@ class Version1Storage:                                              # main.rs:12
         with open(path) as f:
             text = f.read()
         return Version1Storage.from_legacy(text) if path.endswith(".wm") else Version1Storage.from_json(text)
+
+
+# ---- the image catalogue of `identify` (no counterpart in the reference: its `test` command is handed the original) ----
+CATALOGUE_VERSION = 1
+
+
+def save_catalogue(path: str, names, signatures, sizes, marks_files) -> None:
+    """One .npz: version, signatures [n][1024] u8, sizes [n][2] u32 (w, h), names, marks_files ("" where there is none)."""
+    sig = np.ascontiguousarray(signatures, np.uint8).reshape(-1, 1024)
+    n = sig.shape[0]
+    if not (len(names) == len(marks_files) == n) or np.asarray(sizes).reshape(-1, 2).shape[0] != n:
+        raise ValueError("catalogue: names, signatures, sizes and marks_files differ in length")
+    with open(path, "wb") as f:                    # a file object: numpy appends no ".npz" to the name
+        np.savez(f, version=np.uint32(CATALOGUE_VERSION), signatures=sig, sizes=np.asarray(sizes, np.uint32).reshape(-1, 2),
+                 names=np.array([str(x) for x in names], dtype=np.str_),
+                 marks_files=np.array([str(x) if x else "" for x in marks_files], dtype=np.str_))
+
+
+def load_catalogue(path: str):
+    """-> (names, signatures [n][1024] u8, sizes [n][2] u32, marks_files with None where there is none)."""
+    with np.load(path, allow_pickle=False) as z:
+        for key in ("version", "signatures", "sizes", "names", "marks_files"):
+            if key not in z.files:
+                raise ValueError(f"{path}: not an image catalogue (no {key!r})")
+        if int(z["version"]) != CATALOGUE_VERSION:
+            raise ValueError(f"{path}: catalogue version {int(z['version'])}, expected {CATALOGUE_VERSION}")
+        sig, sizes = np.ascontiguousarray(z["signatures"], np.uint8), np.asarray(z["sizes"], np.uint32)
+        names = [str(x) for x in z["names"]]
+        marks = [str(x) or None for x in z["marks_files"]]
+    if sig.ndim != 2 or sig.shape[1] != 1024 or sizes.shape != (sig.shape[0], 2) or not (len(names) == len(marks) == sig.shape[0]):
+        raise ValueError(f"{path}: inconsistent catalogue arrays")
+    return names, sig, sizes, marks
