@@ -27,6 +27,17 @@ __host__ __device__ inline void col_unit_of_row(unsigned y, unsigned H, unsigned
     e = r < HU ? r : H8 - 1 - r;
     v = mir ? 15 - m : m;
 }
+// Operand line of a forward ROW pre-pass -> the image row it holds.  Natural order (unit_h == 0): the same number.  r5, fused
+// forward transform (unit_h = H != 0, level 2 only): the lines of a frame are ordered (unit of the COLUMN fold, line of the unit)
+// -- 16 * unit_hup lines per frame, unit_hup = H/16 rounded up to whole k-blocks of 8 -- so that a 16-line MFMA tile of the row
+// GEMM holds the sixteen rows that meet in one unit of the column pre-pass.  `pad`: a line of the padding units (zeros, no row).
+__device__ inline unsigned fused_line_row(unsigned line, unsigned unit_h, unsigned unit_hup, bool& pad) {
+    pad = false;
+    if (!unit_h) return line;
+    const unsigned lpf = 16 * unit_hup, z = line / lpf, rem = line - z * lpf;
+    pad = (rem >> 4) >= unit_h / 16;
+    return z * unit_h + (pad ? 0u : col_unit_row(rem >> 4, rem & 15u, unit_h));
+}
 
 // the rotation tables of one unit: {cos e, sin e, cos m, sin m} of the unit and its rotation partner (rot: [0, Mh) cos psi,
 // [Mh, 2 Mh) sin psi of a half length Mh)

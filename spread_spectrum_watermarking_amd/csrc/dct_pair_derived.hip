@@ -51,7 +51,7 @@ struct DfJobs {
     unsigned n[4];
 };
 
-template <int SRC /*1 rgb f32, 2 rgb u8, 3 rgb u16*/>
+template <PixFmt FMT>
 __global__ __launch_bounds__(256, 2) void prep16_derived_fused_kernel(const void* __restrict__ SRCP, const double* __restrict__ rot1,
                                                               const double* __restrict__ rot2, const double* __restrict__ rot3,
                                                               DfJobs jobs, float* __restrict__ out, unsigned rows, unsigned W,
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void prep16_derived_fused_kernel(const void
         jp1[j] = jon[j] ? jb.p1 * 64u : 0u;
         jp2[j] = jon2[j] ? jb.p2 * 64u : 0u;
     }
-    constexpr unsigned PXB = SRC == 1 ? 12u : SRC == 3 ? 6u : 3u;                   // bytes per pixel of the frames
+    constexpr unsigned PXB = pix_stride(FMT);                                      // bytes per pixel of the frames
     const unsigned rows_here = rows - line0 < (unsigned)DF_LINES ? rows - line0 : (unsigned)DF_LINES;
     const __amdgpu_buffer_rsrc_t fr = __builtin_amdgcn_make_buffer_rsrc((void*)(static_cast<const char*>(SRCP) + (size_t)line0 * W * PXB), 0,
                                                                       rows_here * W * PXB, 0x00020000);
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256, 2) void prep16_derived_fused_kernel(const void
     // `park` converts them to Y and stores them in LDS.  Vector-memory loads complete in order, so a request may only follow the
     // LAST B-fragment load of the tile being computed (a prefetch issued earlier stands in front of every B-fragment: measured,
     // load time + compute time instead of their maximum): it is issued behind the last k-step's B-fragment loads, in front of the MFMAs of k-steps 2 and 3.
-    RawQuad<SRC - 1> raw[4];
+    RawQuad<FMT> raw[4];
     unsigned dst[4];
     double tv = 0.0;
     bool tv_ok = false;
@@ -130,18 +130,18 @@ __global__ __launch_bounds__(256, 2) void prep16_derived_fused_kernel(const void
             const bool ok = ll < rows_here && efirst < N16;
             dst[i] = ok ? ll * DF_PITCH + u * 16 + 4 * q : 0xFFFFFFFFu;
             const unsigned off = ok ? (ll * W + px) * PXB : 0x80000000u;           // behind the range: nothing is read
-            if (SRC == 1) {
-                auto& w = reinterpret_cast<RawQuad<SSW_PIX_F32>&>(raw[i]).w;
+            if (FMT == PixFmt::F32) {
+                auto& w = reinterpret_cast<RawQuad<PixFmt::F32>&>(raw[i]).w;
                 w[0] = __builtin_amdgcn_raw_buffer_load_b128(fr, off, 0, 0);
                 w[1] = __builtin_amdgcn_raw_buffer_load_b128(fr, off + 16u, 0, 0);
                 w[2] = __builtin_amdgcn_raw_buffer_load_b128(fr, off + 32u, 0, 0);
-            } else if (SRC == 3) {
-                auto& w = reinterpret_cast<RawQuad<SSW_PIX_U16>&>(raw[i]).w;
+            } else if (FMT == PixFmt::U16) {
+                auto& w = reinterpret_cast<RawQuad<PixFmt::U16>&>(raw[i]).w;
                 w[0] = __builtin_amdgcn_raw_buffer_load_b64(fr, off, 0, 0);
                 w[1] = __builtin_amdgcn_raw_buffer_load_b64(fr, off + 8u, 0, 0);
                 w[2] = __builtin_amdgcn_raw_buffer_load_b64(fr, off + 16u, 0, 0);
             } else {
-                auto& w = reinterpret_cast<RawQuad<SSW_PIX_U8>&>(raw[i]).w;
+                auto& w = reinterpret_cast<RawQuad<PixFmt::U8>&>(raw[i]).w;
                 w[0] = __builtin_amdgcn_raw_buffer_load_b32(fr, off, 0, 0);
                 w[1] = __builtin_amdgcn_raw_buffer_load_b32(fr, off + 4u, 0, 0);
                 w[2] = __builtin_amdgcn_raw_buffer_load_b32(fr, off + 8u, 0, 0);
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void prep16_derived_fused_kernel(const void
         for (int i = 0; i < 4; ++i) {
             if (dst[i] == 0xFFFFFFFFu) continue;
             f32x4 y, iv, qv;
-            yiq_of_raw4<SRC - 1, false>(raw[i], y, iv, qv);
+            yiq_of_raw4<FMT, false>(raw[i], y, iv, qv);
             *reinterpret_cast<f32x4*>(ys + dst[i]) = y;
         }
         if (tid < 14 * 16) tabs[tid] = tv_ok ? tv : 0.0;
@@ -300,11 +300,11 @@ bool dct_pair_derived_fused_fits(unsigned n_classes, const DerivedFusedClass* cl
     return true;
 }
 
-int launch_dct_pair_derived_fused(hipStream_t st, int src_kind, const void* rgb, size_t lines, size_t w, const double* rot1,
+int launch_dct_pair_derived_fused(hipStream_t st, const RowInput& in, size_t lines, size_t w, const double* rot1,
                                   const double* rot2, const double* rot3, unsigned n_classes, const DerivedFusedClass* cls,
                                   float* out, unsigned cap_total) {
     if (lines == 0) return SSW_OK;
-    if (lines > 0xFFFFFFFFull || src_kind < 1 || src_kind > 3) return SSW_ERR_BAD_ARG;
+    if (lines > 0xFFFFFFFFull || in.kind == RowSrc::Plane || in.i || in.q) return SSW_ERR_BAD_ARG;      // frames in, no I / Q out
     DfJobs jobs;
     unsigned load[4] = {0, 0, 0, 0};
     for (int w2 = 0; w2 < 4; ++w2) jobs.n[w2] = 0;
@@ -330,15 +330,16 @@ int launch_dct_pair_derived_fused(hipStream_t st, int src_kind, const void* rgb,
         int dev = 0;
         SSW_HIP_CHECK(hipGetDevice(&dev));
         if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-            for (const void* f : {reinterpret_cast<const void*>(prep16_derived_fused_kernel<1>), reinterpret_cast<const void*>(prep16_derived_fused_kernel<2>),
-                                  reinterpret_cast<const void*>(prep16_derived_fused_kernel<3>)})
+            for (const void* f : {reinterpret_cast<const void*>(prep16_derived_fused_kernel<PixFmt::F32>), reinterpret_cast<const void*>(prep16_derived_fused_kernel<PixFmt::U8>),
+                                  reinterpret_cast<const void*>(prep16_derived_fused_kernel<PixFmt::U16>)})
                 SSW_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
             if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
         }
     }
-    if (src_kind == 1) prep16_derived_fused_kernel<1><<<nblk, 256, smem, st>>>(rgb, rot1, rot2, rot3, jobs, out, (unsigned)lines, (unsigned)w, Kp, cap_total);
-    else if (src_kind == 2) prep16_derived_fused_kernel<2><<<nblk, 256, smem, st>>>(rgb, rot1, rot2, rot3, jobs, out, (unsigned)lines, (unsigned)w, Kp, cap_total);
-    else prep16_derived_fused_kernel<3><<<nblk, 256, smem, st>>>(rgb, rot1, rot2, rot3, jobs, out, (unsigned)lines, (unsigned)w, Kp, cap_total);
+    SSW_TRY(dispatch_row_src(in, [&](auto src, auto iq) {
+        if constexpr (decltype(src)::value != RowSrc::Plane && !decltype(iq)::value)
+            prep16_derived_fused_kernel<pix_fmt(decltype(src)::value)><<<nblk, 256, smem, st>>>(in.p, rot1, rot2, rot3, jobs, out, (unsigned)lines, (unsigned)w, Kp, cap_total);
+    }));
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }

@@ -1,7 +1,6 @@
 // HBM-bound pre-passes of the operand-ready GEMMs (dct_pair_f64.hip): they write
 // the image operand of a pass once, already folded (forward) or split (inverse), in f64 (every sum exact) and in the
-// k-blocked layout (dct_pair_common.hpp).  Also the half bases in that layout.  The kernels are templates of the element
-// type T; only T = double is instantiated.
+// k-blocked layout (dct_pair_common.hpp).  Also the half bases in that layout.
 #include "dct_pair_split.hpp"
 #include "dct_pair_colops.hpp"
 #include "dct_pair_yiq_load.hpp"
@@ -14,8 +13,7 @@ namespace ssw {
 // Half bases in the k-blocked layout: [Kp / 8][n / 2][8]; row o of parity p holds basis frequency 2 o + p (forward) or the
 // inverse's entries of frequencies 2 s + p, zero beyond n / 2.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void make_half_basis_blocked_kernel(size_t n, bool inverse, int parity, size_t kpad, T* out) {
+__global__ void make_half_basis_blocked_kernel(size_t n, bool inverse, int parity, size_t kpad, double* out) {
     const size_t nh = n / 2, total = nh * kpad;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t o = i / kpad, s = i % kpad;
@@ -28,7 +26,7 @@ __global__ void make_half_basis_blocked_kernel(size_t n, bool inverse, int parit
             const double c = cospi((double)a / (double)(2ull * n));
             v = !inverse ? 2.0 * c : (freq == 0 ? 0.25 : 0.5 * c);
         }
-        out[blk_index<T>(o, (unsigned)s, nh)] = (T)v;
+        out[blk_index<double>(o, (unsigned)s, nh)] = v;
     }
 }
 
@@ -37,7 +35,7 @@ size_t dct_pair_kpad(size_t n) { return pair_kpad(n); }
 int launch_make_half_basis_blocked(hipStream_t st, size_t n, bool inverse, int parity, double* out) {
     const size_t kp = pair_kpad(n), total = (n / 2) * kp;
     const unsigned blocks = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    make_half_basis_blocked_kernel<double><<<blocks ? blocks : 1, 256, 0, st>>>(n, inverse, parity, kp, out);
+    make_half_basis_blocked_kernel<<<blocks ? blocks : 1, 256, 0, st>>>(n, inverse, parity, kp, out);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
@@ -59,9 +57,8 @@ int launch_make_half_basis_blocked(hipStream_t st, size_t n, bool inverse, int p
 // Bases, k-blocked like the half bases: rows i of scale * cos / sin(2 pi j (2n+1) / N), j = 2i (E, N/8 + 1 rows) or
 // 2i + 1 (O, N/8 rows), n < N/8; scale 2 forward, 1/2 inverse as in make_half_basis_blocked_kernel.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
 __global__ void make_split_basis_blocked_kernel(size_t n, bool inverse, int which /*0 cosE, 1 sinE, 2 cosO, 3 sinO, 4 sinE with row 0 := row n/8*/, size_t kpad,
-                                                size_t rows, T* out) {
+                                                size_t rows, double* out) {
     const size_t ktrue = n / 8, total = rows * kpad;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t o = i / kpad, s = i % kpad;
@@ -73,7 +70,7 @@ __global__ void make_split_basis_blocked_kernel(size_t n, bool inverse, int whic
             const double c = ((which & 1) || which == 4) ? sinpi(arg) : cospi(arg);
             v = (inverse ? 0.5 : 2.0) * c;
         }
-        out[blk_index<T>(o, (unsigned)s, rows)] = (T)v;
+        out[blk_index<double>(o, (unsigned)s, rows)] = v;
     }
 }
 // rotation table of a length-n axis: [0 .. n/4) cos psi, [n/4 .. n/2) sin psi, psi = pi (2 m + 1) / (2 n)
@@ -97,7 +94,7 @@ size_t dct_pair_split_basis_rows(size_t len, int which) { return (which & 2) ? l
 int launch_make_split_basis_blocked(hipStream_t st, size_t n, bool inverse, int which, double* out) {
     const size_t kp = dct_pair_split_kpad(n), rows = dct_pair_split_basis_rows(n, which), total = rows * kp;
     const unsigned blocks = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    make_split_basis_blocked_kernel<double><<<blocks ? blocks : 1, 256, 0, st>>>(n, inverse, which, kp, rows, out);
+    make_split_basis_blocked_kernel<<<blocks ? blocks : 1, 256, 0, st>>>(n, inverse, which, kp, rows, out);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
@@ -194,15 +191,15 @@ int launch_dct_pair_rotate(hipStream_t st, const double* p, const double* rot, d
 // ---------------------------------------------------------------------------------------------
 // Row pass: line = image row, k along the row.  Block = 32 lines x 32 k; thread = 4 consecutive k of
 // one line: 128-byte read runs per line, 512-byte write runs per k-block.
-template <typename T, bool INVERSE>
-__global__ __launch_bounds__(256) void pair_prep_rows_kernel(const float* __restrict__ X, T* __restrict__ O1,
-                                                            T* __restrict__ O2, unsigned rows, unsigned W, unsigned Kp,
+template <bool INVERSE>
+__global__ __launch_bounds__(256) void pair_prep_rows_kernel(const float* __restrict__ X, double* __restrict__ O1,
+                                                            double* __restrict__ O2, unsigned rows, unsigned W, unsigned Kp,
                                                             unsigned tiles_k) {
     const unsigned Nh = W / 2;
     const unsigned s = (blockIdx.x % tiles_k) * 32 + (threadIdx.x & 7) * 4;
     const unsigned row = (blockIdx.x / tiles_k) * 32 + (threadIdx.x >> 3);
     if (row >= rows || s >= Kp) return;
-    vec4_t<T> a = {0, 0, 0, 0}, b = {0, 0, 0, 0};
+    f64x4 a = {0, 0, 0, 0}, b = {0, 0, 0, 0};
     if (s < Nh) {                                                 // Nh % 4 == 0
         const float* x = X + (size_t)row * W;
         if (!INVERSE) {
@@ -210,28 +207,28 @@ __global__ __launch_bounds__(256) void pair_prep_rows_kernel(const float* __rest
             const f32x4 v = *reinterpret_cast<const f32x4*>(x + (W - 4 - s));
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                a[e] = (T)u[e] + (T)v[3 - e];
-                b[e] = (T)u[e] - (T)v[3 - e];
+                a[e] = (double)u[e] + (double)v[3 - e];
+                b[e] = (double)u[e] - (double)v[3 - e];
             }
         } else {
             const f32x4 u = *reinterpret_cast<const f32x4*>(x + 2 * s);
             const f32x4 v = *reinterpret_cast<const f32x4*>(x + 2 * s + 4);
-            a = (vec4_t<T>){(T)u[0], (T)u[2], (T)v[0], (T)v[2]};
-            b = (vec4_t<T>){(T)u[1], (T)u[3], (T)v[1], (T)v[3]};
+            a = (f64x4){(double)u[0], (double)u[2], (double)v[0], (double)v[2]};
+            b = (f64x4){(double)u[1], (double)u[3], (double)v[1], (double)v[3]};
         }
     }
-    *reinterpret_cast<vec4_t<T>*>(O1 + blk_index<T>(row, s, rows)) = a;
-    *reinterpret_cast<vec4_t<T>*>(O2 + blk_index<T>(row, s, rows)) = b;
+    *reinterpret_cast<f64x4*>(O1 + blk_index<double>(row, s, rows)) = a;
+    *reinterpret_cast<f64x4*>(O2 + blk_index<double>(row, s, rows)) = b;
 }
 
 // Column pass: line = (frame, column), k along the image rows: fold / split + transpose through LDS.
 // Block tile: 32 k x 64 columns; written as 4 KB runs (64 lines x one 64-byte k-block piece).
-template <typename T, bool INVERSE>
-__global__ __launch_bounds__(256) void pair_prep_cols_kernel(const float* __restrict__ IN, T* __restrict__ O1,
-                                                            T* __restrict__ O2, unsigned W, unsigned H, unsigned Kp,
+template <bool INVERSE>
+__global__ __launch_bounds__(256) void pair_prep_cols_kernel(const float* __restrict__ IN, double* __restrict__ O1,
+                                                            double* __restrict__ O2, unsigned W, unsigned H, unsigned Kp,
                                                             unsigned n_frames, unsigned tiles_k, unsigned tiles_c) {
-    __shared__ T s1[64][33];
-    __shared__ T s2[64][33];
+    __shared__ double s1[64][33];
+    __shared__ double s2[64][33];
     const unsigned Hh = H / 2;
     const unsigned z = blockIdx.x / (tiles_k * tiles_c);
     const unsigned tt = blockIdx.x % (tiles_k * tiles_c);
@@ -253,8 +250,8 @@ __global__ __launch_bounds__(256) void pair_prep_cols_kernel(const float* __rest
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                s1[cq + e][kl] = INVERSE ? (T)u[e] : (T)u[e] + (T)v[e];
-                s2[cq + e][kl] = INVERSE ? (T)v[e] : (T)u[e] - (T)v[e];
+                s1[cq + e][kl] = INVERSE ? (double)u[e] : (double)u[e] + (double)v[e];
+                s2[cq + e][kl] = INVERSE ? (double)v[e] : (double)u[e] - (double)v[e];
             }
         }
     }
@@ -263,11 +260,11 @@ __global__ __launch_bounds__(256) void pair_prep_cols_kernel(const float* __rest
         const unsigned cl = tid & 63, kq = (tid >> 6) * 8;        // one 64-byte k-block piece of one column per thread
         const unsigned c = c0 + cl;
         if (c < W && k0 + kq < Kp) {                              // Kp % 8 == 0
-            const size_t at = blk_index<T>((size_t)z * W + c, k0 + kq, (size_t)n_frames * W);
+            const size_t at = blk_index<double>((size_t)z * W + c, k0 + kq, (size_t)n_frames * W);
 #pragma unroll
             for (int e = 0; e < 8; e += 2) {
-                *reinterpret_cast<vec2_t<T>*>(O1 + at + e) = (vec2_t<T>){s1[cl][kq + e], s1[cl][kq + e + 1]};
-                *reinterpret_cast<vec2_t<T>*>(O2 + at + e) = (vec2_t<T>){s2[cl][kq + e], s2[cl][kq + e + 1]};
+                *reinterpret_cast<f64x2*>(O1 + at + e) = (f64x2){s1[cl][kq + e], s1[cl][kq + e + 1]};
+                *reinterpret_cast<f64x2*>(O2 + at + e) = (f64x2){s2[cl][kq + e], s2[cl][kq + e + 1]};
             }
         }
     }
@@ -275,65 +272,70 @@ __global__ __launch_bounds__(256) void pair_prep_cols_kernel(const float* __rest
 
 // ---------------------------------------------------------------------------------------------
 // Two-level pre-passes: f32 plane -> (SS, SD, D) forward / (EE, EO, O) inverse in one sweep
-// (12 B/px of HBM traffic; a separate second-level pass over S would make it 20).
+// (12 B/px of HBM traffic; a separate second-level pass over S would make it 20).  The forward ROW pass reads any RowSrc:
+// straight from the RGB frame (rgb -> Y, yiq.rs:177-186, formed on the fly) the Y plane is never written and re-read as f32
+// (8 B/px less HBM traffic per transform); I and Q planes are written for the writer, not for readers.
 //   forward, q < n/4:  S[q] = x[q] + x[n-1-q],  S' = x[n/2-1-q] + x[n/2+q];  SS = S + S',  SD = S - S'
 //                      D[q] = x[q] - x[n-1-q],  D[n/2-1-q] = x[n/2-1-q] - x[n/2+q]
 //   inverse, q < n/4:  EE[q] = c[4q],  EO[q] = c[4q+2],  O[2q] = c[4q+1],  O[2q+1] = c[4q+3]
 // Q1, Q2: kq = pair_kpad(n/2) wide; P: kp = pair_kpad(n) wide; k-blocked, zero padded.
 // ---------------------------------------------------------------------------------------------
-template <typename T, bool INVERSE>
-__global__ __launch_bounds__(256) void pair_prep4_rows_kernel(const float* __restrict__ X, T* __restrict__ Q1,
-                                                             T* __restrict__ Q2, T* __restrict__ P,
+template <bool INVERSE, RowSrc SRC, bool WITH_IQ>
+__global__ __launch_bounds__(256) void pair_prep4_rows_kernel(const void* __restrict__ SRCP, double* __restrict__ Q1,
+                                                             double* __restrict__ Q2, double* __restrict__ P,
+                                                             float* __restrict__ IP, float* __restrict__ QP,
                                                              unsigned rows, unsigned W, unsigned Kq, unsigned Kp,
                                                              unsigned tiles_q) {
+    static_assert(!INVERSE || SRC == RowSrc::Plane, "an inverse pass reads a coefficient plane");
     const unsigned Nh = W / 2, Nq = W / 4;
     const unsigned q = (blockIdx.x % tiles_q) * 32 + (threadIdx.x & 7) * 4;
     const unsigned row = (blockIdx.x / tiles_q) * 32 + (threadIdx.x >> 3);
     if (row >= rows || q >= Kq) return;
-    vec4_t<T> a1 = {0, 0, 0, 0}, a2 = {0, 0, 0, 0};
+    f64x4 a1 = {0, 0, 0, 0}, a2 = {0, 0, 0, 0};
     if (q < Nq) {                                                 // Nq % 4 == 0
-        const float* x = X + (size_t)row * W;
         if (!INVERSE) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(x + q);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(x + (Nh - 4 - q));
-            const f32x4 c = *reinterpret_cast<const f32x4*>(x + (Nh + q));
-            const f32x4 d = *reinterpret_cast<const f32x4*>(x + (W - 4 - q));
-            vec4_t<T> dn, dm;
+            const unsigned pos[4] = {q, Nh - 4 - q, Nh + q, W - 4 - q};
+            f32x4 y[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) y[u] = load_row_y4<SRC, WITH_IQ>(SRCP, IP, QP, row, W, pos[u]);
+            const f32x4 a = y[0], b = y[1], c = y[2], d = y[3];
+            f64x4 dn, dm;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const T s1 = (T)a[e] + (T)d[3 - e], s2 = (T)b[3 - e] + (T)c[e];
+                const double s1 = (double)a[e] + (double)d[3 - e], s2 = (double)b[3 - e] + (double)c[e];
                 a1[e] = s1 + s2;
                 a2[e] = s1 - s2;
-                dn[e] = (T)a[e] - (T)d[3 - e];
-                dm[3 - e] = (T)b[3 - e] - (T)c[e];
+                dn[e] = (double)a[e] - (double)d[3 - e];
+                dm[3 - e] = (double)b[3 - e] - (double)c[e];
             }
-            *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(row, q, rows)) = dn;
-            *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(row, Nh - 4 - q, rows)) = dm;
+            *reinterpret_cast<f64x4*>(P + blk_index<double>(row, q, rows)) = dn;
+            *reinterpret_cast<f64x4*>(P + blk_index<double>(row, Nh - 4 - q, rows)) = dm;
         } else {
+            const float* x = static_cast<const float*>(SRCP) + (size_t)row * W;
             f32x4 c[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) c[e] = *reinterpret_cast<const f32x4*>(x + 4 * (q + e));
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { a1[e] = (T)c[e][0]; a2[e] = (T)c[e][2]; }
-            T* o = P + blk_index<T>(row, 2 * q, rows);           // 2 q is a multiple of 8: one whole k-block piece
-            *reinterpret_cast<vec4_t<T>*>(o) = (vec4_t<T>){(T)c[0][1], (T)c[0][3], (T)c[1][1], (T)c[1][3]};
-            *reinterpret_cast<vec4_t<T>*>(o + 4) = (vec4_t<T>){(T)c[2][1], (T)c[2][3], (T)c[3][1], (T)c[3][3]};
+            for (int e = 0; e < 4; ++e) { a1[e] = (double)c[e][0]; a2[e] = (double)c[e][2]; }
+            double* o = P + blk_index<double>(row, 2 * q, rows);           // 2 q is a multiple of 8: one whole k-block piece
+            *reinterpret_cast<f64x4*>(o) = (f64x4){(double)c[0][1], (double)c[0][3], (double)c[1][1], (double)c[1][3]};
+            *reinterpret_cast<f64x4*>(o + 4) = (f64x4){(double)c[2][1], (double)c[2][3], (double)c[3][1], (double)c[3][3]};
         }
     }
-    *reinterpret_cast<vec4_t<T>*>(Q1 + blk_index<T>(row, q, rows)) = a1;
-    *reinterpret_cast<vec4_t<T>*>(Q2 + blk_index<T>(row, q, rows)) = a2;
+    *reinterpret_cast<f64x4*>(Q1 + blk_index<double>(row, q, rows)) = a1;
+    *reinterpret_cast<f64x4*>(Q2 + blk_index<double>(row, q, rows)) = a2;
     if (q == 0)
-        for (unsigned z = Nh; z < Kp; z += 4) *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(row, z, rows)) = (vec4_t<T>){0, 0, 0, 0};
+        for (unsigned z = Nh; z < Kp; z += 4) *reinterpret_cast<f64x4*>(P + blk_index<double>(row, z, rows)) = (f64x4){0, 0, 0, 0};
 }
 
 // Column pass: lines = (frame, column); block tile 32 q x 32 columns, transposed through LDS and
 // written as 2 KB runs (32 lines x one 64-byte k-block piece).
-template <typename T, bool INVERSE>
-__global__ __launch_bounds__(256) void pair_prep4_cols_kernel(const float* __restrict__ IN, T* __restrict__ Q1,
-                                                             T* __restrict__ Q2, T* __restrict__ P,
+template <bool INVERSE>
+__global__ __launch_bounds__(256) void pair_prep4_cols_kernel(const float* __restrict__ IN, double* __restrict__ Q1,
+                                                             double* __restrict__ Q2, double* __restrict__ P,
                                                              unsigned W, unsigned H, unsigned Kq, unsigned Kp,
                                                              unsigned n_frames, unsigned tiles_q, unsigned tiles_c) {
-    __shared__ T sA[32][33], sB[32][33], sC[32][33], sD[32][33];
+    __shared__ double sA[32][33], sB[32][33], sC[32][33], sD[32][33];
     const unsigned Hh = H / 2, Hq = H / 4;
     const unsigned z = blockIdx.x / (tiles_q * tiles_c);
     const unsigned tt = blockIdx.x % (tiles_q * tiles_c);
@@ -356,16 +358,16 @@ __global__ __launch_bounds__(256) void pair_prep4_cols_kernel(const float* __res
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (!INVERSE) {
-                const T s1 = (T)a[e] + (T)d[e], s2 = (T)b[e] + (T)cc[e];
+                const double s1 = (double)a[e] + (double)d[e], s2 = (double)b[e] + (double)cc[e];
                 sA[cq + e][qr] = s1 + s2;
                 sB[cq + e][qr] = s1 - s2;
-                sC[cq + e][qr] = (T)a[e] - (T)d[e];        // D[q]
-                sD[cq + e][qr] = (T)b[e] - (T)cc[e];       // D[H/2-1-q]
+                sC[cq + e][qr] = (double)a[e] - (double)d[e];        // D[q]
+                sD[cq + e][qr] = (double)b[e] - (double)cc[e];       // D[H/2-1-q]
             } else {
-                sA[cq + e][qr] = (T)a[e];                        // EE[q]
-                sB[cq + e][qr] = (T)b[e];                        // EO[q]
-                sC[cq + e][qr] = (T)cc[e];                       // O[2q]
-                sD[cq + e][qr] = (T)d[e];                        // O[2q+1]
+                sA[cq + e][qr] = (double)a[e];                        // EE[q]
+                sB[cq + e][qr] = (double)b[e];                        // EO[q]
+                sC[cq + e][qr] = (double)cc[e];                       // O[2q]
+                sD[cq + e][qr] = (double)d[e];                        // O[2q+1]
             }
         }
     }
@@ -375,83 +377,33 @@ __global__ __launch_bounds__(256) void pair_prep4_cols_kernel(const float* __res
         const unsigned c = c0 + cl, q = q0 + kq;
         if (c < W && q < Kq) {
             const size_t line = (size_t)z * W + c, lines = (size_t)n_frames * W;
-            *reinterpret_cast<vec4_t<T>*>(Q1 + blk_index<T>(line, q, lines)) = (vec4_t<T>){sA[cl][kq], sA[cl][kq + 1], sA[cl][kq + 2], sA[cl][kq + 3]};
-            *reinterpret_cast<vec4_t<T>*>(Q2 + blk_index<T>(line, q, lines)) = (vec4_t<T>){sB[cl][kq], sB[cl][kq + 1], sB[cl][kq + 2], sB[cl][kq + 3]};
+            *reinterpret_cast<f64x4*>(Q1 + blk_index<double>(line, q, lines)) = (f64x4){sA[cl][kq], sA[cl][kq + 1], sA[cl][kq + 2], sA[cl][kq + 3]};
+            *reinterpret_cast<f64x4*>(Q2 + blk_index<double>(line, q, lines)) = (f64x4){sB[cl][kq], sB[cl][kq + 1], sB[cl][kq + 2], sB[cl][kq + 3]};
             if (q < Hq && q + 4 > Hq) {                             // H/4 not a multiple of 4: the last quad is partial
                 for (unsigned e = 0; q + e < Hq; ++e) {
                     if (!INVERSE) {
-                        P[blk_index<T>(line, q + e, lines)] = sC[cl][kq + e];
-                        P[blk_index<T>(line, Hh - 1 - (q + e), lines)] = sD[cl][kq + e];
+                        P[blk_index<double>(line, q + e, lines)] = sC[cl][kq + e];
+                        P[blk_index<double>(line, Hh - 1 - (q + e), lines)] = sD[cl][kq + e];
                     } else {
-                        P[blk_index<T>(line, 2 * (q + e), lines)] = sC[cl][kq + e];
-                        P[blk_index<T>(line, 2 * (q + e) + 1, lines)] = sD[cl][kq + e];
+                        P[blk_index<double>(line, 2 * (q + e), lines)] = sC[cl][kq + e];
+                        P[blk_index<double>(line, 2 * (q + e) + 1, lines)] = sD[cl][kq + e];
                     }
                 }
             } else if (q < Hq) {
                 if (!INVERSE) {
-                    *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(line, q, lines)) = (vec4_t<T>){sC[cl][kq], sC[cl][kq + 1], sC[cl][kq + 2], sC[cl][kq + 3]};
-                    *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(line, Hh - 4 - q, lines)) = (vec4_t<T>){sD[cl][kq + 3], sD[cl][kq + 2], sD[cl][kq + 1], sD[cl][kq]};
+                    *reinterpret_cast<f64x4*>(P + blk_index<double>(line, q, lines)) = (f64x4){sC[cl][kq], sC[cl][kq + 1], sC[cl][kq + 2], sC[cl][kq + 3]};
+                    *reinterpret_cast<f64x4*>(P + blk_index<double>(line, Hh - 4 - q, lines)) = (f64x4){sD[cl][kq + 3], sD[cl][kq + 2], sD[cl][kq + 1], sD[cl][kq]};
                 } else {
-                    T* o = P + blk_index<T>(line, 2 * q, lines);
-                    *reinterpret_cast<vec4_t<T>*>(o) = (vec4_t<T>){sC[cl][kq], sD[cl][kq], sC[cl][kq + 1], sD[cl][kq + 1]};
-                    *reinterpret_cast<vec4_t<T>*>(o + 4) = (vec4_t<T>){sC[cl][kq + 2], sD[cl][kq + 2], sC[cl][kq + 3], sD[cl][kq + 3]};
+                    double* o = P + blk_index<double>(line, 2 * q, lines);
+                    *reinterpret_cast<f64x4*>(o) = (f64x4){sC[cl][kq], sD[cl][kq], sC[cl][kq + 1], sD[cl][kq + 1]};
+                    *reinterpret_cast<f64x4*>(o + 4) = (f64x4){sC[cl][kq + 2], sD[cl][kq + 2], sC[cl][kq + 3], sD[cl][kq + 3]};
                 }
             }
             if (q == 0)
-                for (unsigned zz = Hh; zz < Kp; zz += 4) *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(line, zz, lines)) = (vec4_t<T>){0, 0, 0, 0};
+                for (unsigned zz = Hh; zz < Kp; zz += 4) *reinterpret_cast<f64x4*>(P + blk_index<double>(line, zz, lines)) = (f64x4){0, 0, 0, 0};
         }
     }
 }
-// ---------------------------------------------------------------------------------------------
-// First pass of a forward transform straight from the RGB frame: rgb -> Y (yiq.rs:177-186, the same
-// arithmetic as color.hip / attack.hip) fused with the two-level row pre-pass above, so the Y plane is
-// never written and re-read as f32 (8 B/px less HBM traffic per transform); I and Q planes are written
-// for the writer, not for readers.
-// ---------------------------------------------------------------------------------------------
-// (prep_dot3 / load_yiq4: dct_pair_yiq_load.hpp, shared with dct_pair_prep_light.hip)
-
-template <typename T, int FMT, bool WITH_IQ>
-__global__ __launch_bounds__(256) void pair_prep4_rows_rgb_kernel(const void* __restrict__ RGB, T* __restrict__ Q1,
-                                                                 T* __restrict__ Q2, T* __restrict__ P,
-                                                                 float* __restrict__ IP, float* __restrict__ QP,
-                                                                 unsigned rows, unsigned W, unsigned Kq, unsigned Kp,
-                                                                 unsigned tiles_q) {
-    const unsigned Nh = W / 2, Nq = W / 4;
-    const unsigned q = (blockIdx.x % tiles_q) * 32 + (threadIdx.x & 7) * 4;
-    const unsigned row = (blockIdx.x / tiles_q) * 32 + (threadIdx.x >> 3);
-    if (row >= rows || q >= Kq) return;
-    vec4_t<T> a1 = {0, 0, 0, 0}, a2 = {0, 0, 0, 0};
-    if (q < Nq) {                                                 // Nq % 4 == 0
-        const void* base = static_cast<const char*>(RGB) + (size_t)row * W * 3 * (FMT == SSW_PIX_U8 ? 1 : FMT == SSW_PIX_U16 ? 2 : 4);
-        const unsigned pos[4] = {q, Nh - 4 - q, Nh + q, W - 4 - q};
-        f32x4 y[4], iv, qv;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            load_yiq4<FMT, WITH_IQ>(base, pos[u], y[u], iv, qv);
-            if (WITH_IQ) {
-                *reinterpret_cast<f32x4*>(IP + (size_t)row * W + pos[u]) = iv;
-                *reinterpret_cast<f32x4*>(QP + (size_t)row * W + pos[u]) = qv;
-            }
-        }
-        const f32x4 a = y[0], b = y[1], c = y[2], d = y[3];
-        vec4_t<T> dn, dm;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const T s1 = (T)a[e] + (T)d[3 - e], s2 = (T)b[3 - e] + (T)c[e];
-            a1[e] = s1 + s2;
-            a2[e] = s1 - s2;
-            dn[e] = (T)a[e] - (T)d[3 - e];
-            dm[3 - e] = (T)b[3 - e] - (T)c[e];
-        }
-        *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(row, q, rows)) = dn;
-        *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(row, Nh - 4 - q, rows)) = dm;
-    }
-    *reinterpret_cast<vec4_t<T>*>(Q1 + blk_index<T>(row, q, rows)) = a1;
-    *reinterpret_cast<vec4_t<T>*>(Q2 + blk_index<T>(row, q, rows)) = a2;
-    if (q == 0)
-        for (unsigned z = Nh; z < Kp; z += 4) *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(row, z, rows)) = (vec4_t<T>){0, 0, 0, 0};
-}
-
 // ---------------------------------------------------------------------------------------------
 // Three folding levels on a forward row pass (n % 32 == 0): the even part of the even part folds once
 // more.  With S = fold(x) (length n/2), SS = fold(S) (n/4), SSS = fold(SS) (n/8):
@@ -459,11 +411,11 @@ __global__ __launch_bounds__(256) void pair_prep4_rows_rgb_kernel(const void* __
 //   M  = S - mirror            (-> frequencies 2 mod 4;    width kpad(n/2))
 //   P  = x - mirror            (-> odd frequencies;        width kpad(n))
 // One thread = one quad e < n/8 of one line: it reads the 8 quads of x that meet in it.  The source is
-// an f32 plane or the interleaved RGB frame (Y formed on the fly, I / Q written for the writer).
+// any RowSrc (ssw_internal.hpp; dct_pair_yiq_load.hpp: Y formed on the fly, I / Q written for the writer).
 // ---------------------------------------------------------------------------------------------
-template <typename T, int SRC /*0 plane, 1 rgb f32, 2 rgb u8*/, bool WITH_IQ>
-__global__ __launch_bounds__(256) void pair_prep8_rows_kernel(const void* __restrict__ SRCP, T* __restrict__ R1,
-                                                             T* __restrict__ R2, T* __restrict__ M, T* __restrict__ P,
+template <RowSrc SRC, bool WITH_IQ>
+__global__ __launch_bounds__(256) void pair_prep8_rows_kernel(const void* __restrict__ SRCP, double* __restrict__ R1,
+                                                             double* __restrict__ R2, double* __restrict__ M, double* __restrict__ P,
                                                              float* __restrict__ IP, float* __restrict__ QP,
                                                              unsigned rows, unsigned W, unsigned K8, unsigned Kq, unsigned Kp,
                                                              unsigned tiles_e) {
@@ -471,42 +423,26 @@ __global__ __launch_bounds__(256) void pair_prep8_rows_kernel(const void* __rest
     const unsigned e0 = (blockIdx.x % tiles_e) * 32 + (threadIdx.x & 7) * 4;
     const unsigned row = (blockIdx.x / tiles_e) * 32 + (threadIdx.x >> 3);
     if (row >= rows || e0 >= K8) return;
-    vec4_t<T> r1 = {0, 0, 0, 0}, r2 = {0, 0, 0, 0};
+    f64x4 r1 = {0, 0, 0, 0}, r2 = {0, 0, 0, 0};
     if (e0 < Ne) {                                                // Ne % 4 == 0
         // quads of x, ascending positions; quad u mirrors quad 7 - u
         const unsigned pos[8] = {e0, Nq - 4 - e0, Nq + e0, Nh - 4 - e0, Nh + e0, 3 * Nq - 4 - e0, 3 * Nq + e0, W - 4 - e0};
         f32x4 x[8];
-        if (SRC == 0) {
-            const float* xr = static_cast<const float*>(SRCP) + (size_t)row * W;
 #pragma unroll
-            for (int u = 0; u < 8; ++u) x[u] = *reinterpret_cast<const f32x4*>(xr + pos[u]);
-        } else {
-            const void* base = SRC == 3 ? static_cast<const void*>(static_cast<const uint16_t*>(SRCP) + (size_t)row * W * 3)
-                           : SRC == 2 ? static_cast<const void*>(static_cast<const uint8_t*>(SRCP) + (size_t)row * W * 3)
-                                        : static_cast<const void*>(static_cast<const float*>(SRCP) + (size_t)row * W * 3);
-            f32x4 iv, qv;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                load_yiq4<SRC - 1, WITH_IQ>(base, pos[u], x[u], iv, qv);
-                if (WITH_IQ) {
-                    *reinterpret_cast<f32x4*>(IP + (size_t)row * W + pos[u]) = iv;
-                    *reinterpret_cast<f32x4*>(QP + (size_t)row * W + pos[u]) = qv;
-                }
-            }
-        }
+        for (int u = 0; u < 8; ++u) x[u] = load_row_y4<SRC, WITH_IQ>(SRCP, IP, QP, row, W, pos[u]);
         // level 1: S and D1 at the positions of quads 0..3 (their mirrors are quads 7..4, reversed)
-        vec4_t<T> S[4], D1[4];
+        f64x4 S[4], D1[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                S[u][i] = (T)x[u][i] + (T)x[7 - u][3 - i];
-                D1[u][i] = (T)x[u][i] - (T)x[7 - u][3 - i];
+                S[u][i] = (double)x[u][i] + (double)x[7 - u][3 - i];
+                D1[u][i] = (double)x[u][i] - (double)x[7 - u][3 - i];
             }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(row, pos[u], rows)) = D1[u];
+        for (int u = 0; u < 4; ++u) *reinterpret_cast<f64x4*>(P + blk_index<double>(row, pos[u], rows)) = D1[u];
         // level 2 on S (length n/2): quad 0 mirrors quad 3, quad 1 mirrors quad 2
-        vec4_t<T> SS[2], D2[2];
+        f64x4 SS[2], D2[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -515,7 +451,7 @@ __global__ __launch_bounds__(256) void pair_prep8_rows_kernel(const void* __rest
                 D2[u][i] = S[u][i] - S[3 - u][3 - i];
             }
 #pragma unroll
-        for (int u = 0; u < 2; ++u) *reinterpret_cast<vec4_t<T>*>(M + blk_index<T>(row, pos[u], rows)) = D2[u];
+        for (int u = 0; u < 2; ++u) *reinterpret_cast<f64x4*>(M + blk_index<double>(row, pos[u], rows)) = D2[u];
         // level 3 on SS (length n/4): quad 0 mirrors quad 1
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -523,11 +459,11 @@ __global__ __launch_bounds__(256) void pair_prep8_rows_kernel(const void* __rest
             r2[i] = SS[0][i] - SS[1][3 - i];
         }
     }
-    *reinterpret_cast<vec4_t<T>*>(R1 + blk_index<T>(row, e0, rows)) = r1;
-    *reinterpret_cast<vec4_t<T>*>(R2 + blk_index<T>(row, e0, rows)) = r2;
+    *reinterpret_cast<f64x4*>(R1 + blk_index<double>(row, e0, rows)) = r1;
+    *reinterpret_cast<f64x4*>(R2 + blk_index<double>(row, e0, rows)) = r2;
     if (e0 == 0) {
-        for (unsigned z = Nh; z < Kp; z += 4) *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(row, z, rows)) = (vec4_t<T>){0, 0, 0, 0};
-        for (unsigned z = Nq; z < Kq; z += 4) *reinterpret_cast<vec4_t<T>*>(M + blk_index<T>(row, z, rows)) = (vec4_t<T>){0, 0, 0, 0};
+        for (unsigned z = Nh; z < Kp; z += 4) *reinterpret_cast<f64x4*>(P + blk_index<double>(row, z, rows)) = (f64x4){0, 0, 0, 0};
+        for (unsigned z = Nq; z < Kq; z += 4) *reinterpret_cast<f64x4*>(M + blk_index<double>(row, z, rows)) = (f64x4){0, 0, 0, 0};
     }
 }
 
@@ -542,7 +478,7 @@ __global__ __launch_bounds__(256) void pair_prep8_rows_kernel(const void* __rest
 // One thread = 4 consecutive e < n/16 of one line: the 16 quads of x that meet in them (quad u mirrors quad 15 - u).
 // Planes are k-blocked, K8 = kpad(n/4) (>= n/8) and K16 = kpad(n/8) (>= n/16) wide, zero padded.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int SRC /*0 plane, 1 rgb f32, 2 rgb u8*/, bool WITH_IQ>
+template <RowSrc SRC, bool WITH_IQ>
 __global__ __launch_bounds__(256) void pair_prep16_rows_kernel(const void* __restrict__ SRCP, DeepPlanes dp,
                                                               const double* __restrict__ rot1, const double* __restrict__ rot2,
                                                               const double* __restrict__ rot3,
@@ -551,85 +487,57 @@ __global__ __launch_bounds__(256) void pair_prep16_rows_kernel(const void* __res
                                                               unsigned unit_h, unsigned unit_hup) {
     const unsigned Nh = W / 2, Nq = W / 4, N8 = W / 8, N16 = W / 16;
     const unsigned e0 = (blockIdx.x % tiles_e) * 32 + (threadIdx.x & 7) * 4;
-    // operand line of this thread, and the image row it holds.  Natural order: the same number.  r5, fused forward
-    // transform (unit_h = H != 0, level 2 only): the lines of a frame are ordered (unit of the COLUMN fold, line of the unit)
-    // -- 16 * unit_hup lines per frame, unit_hup = H/16 rounded up to whole k-blocks of 8 -- so that a 16-line MFMA tile
-    // of the row GEMM holds the sixteen rows that meet in one unit of the column pre-pass (dct_pair_colops.hpp).  A block's
-    // 32 lines are then 32 rows of sixteen regions of the frame: the reads are 384-byte runs per row either way, the
-    // stores stay 2 KB runs.  `rows` counts operand lines (the planes' line stride).
+    // operand line of this thread, and the image row it holds (fused_line_row, dct_pair_colops.hpp: natural order, or the fused
+    // forward transform's unit order -- a block's 32 lines are then 32 rows of sixteen regions of the frame: the reads are 384-byte
+    // runs per row either way, the stores stay 2 KB runs).  `rows` counts operand lines (the planes' line stride).
     const unsigned line = (blockIdx.x / tiles_e) * 32 + (threadIdx.x >> 3);
     if (line >= rows || e0 >= K16) return;
-    unsigned row = line;
-    bool pad_line = false;
-    if (unit_h) {
-        const unsigned lpf = 16 * unit_hup, z = line / lpf, rem = line - z * lpf;
-        pad_line = (rem >> 4) >= unit_h / 16;
-        row = z * unit_h + (pad_line ? 0u : col_unit_row(rem >> 4, rem & 15u, unit_h));
-    }
-    T* AD = static_cast<T*>(dp.ad); T* BS = static_cast<T*>(dp.bs);
-    T* R1 = static_cast<T*>(dp.r1); T* R2 = static_cast<T*>(dp.r2);
-    T* AS2 = static_cast<T*>(dp.as2); T* BD2 = static_cast<T*>(dp.bd2); T* AD2 = static_cast<T*>(dp.ad2); T* BS2 = static_cast<T*>(dp.bs2);
-    auto put = [&](T* plane, unsigned k, const vec4_t<T>& v) { *reinterpret_cast<vec4_t<T>*>(plane + blk_index<T>(line, k, rows)) = v; };
-    const vec4_t<T> zero = {0, 0, 0, 0};
+    bool pad_line;
+    const unsigned row = fused_line_row(line, unit_h, unit_hup, pad_line);
+    double* AD = static_cast<double*>(dp.ad); double* BS = static_cast<double*>(dp.bs);
+    double* R1 = static_cast<double*>(dp.r1); double* R2 = static_cast<double*>(dp.r2);
+    double* AS2 = static_cast<double*>(dp.as2); double* BD2 = static_cast<double*>(dp.bd2); double* AD2 = static_cast<double*>(dp.ad2); double* BS2 = static_cast<double*>(dp.bs2);
+    auto put = [&](double* plane, unsigned k, const f64x4& v) { *reinterpret_cast<f64x4*>(plane + blk_index<double>(line, k, rows)) = v; };
+    const f64x4 zero = {0, 0, 0, 0};
     if (e0 >= N16 || pad_line) {                                  // padding of the n/16-wide planes; lines of the padding units
         put(AS2, e0, zero); put(BD2, e0, zero); put(AD2, e0, zero); put(BS2, e0, zero);
         if (efold) {
             void* const l2[12] = {dp.asp, dp.asm_, dp.bdp, dp.bdm, dp.oap, dp.obp, dp.oam, dp.obm, dp.r1p, dp.r1m, dp.r2a, dp.r2b};
 #pragma unroll
-            for (int a = 0; a < 12; ++a) put(static_cast<T*>(l2[a]), e0, zero);
+            for (int a = 0; a < 12; ++a) put(static_cast<double*>(l2[a]), e0, zero);
         }
         return;
     }
     // quads of x, ascending positions inside a quad
     const unsigned pos[8] = {e0, N8 - 4 - e0, N8 + e0, Nq - 4 - e0, Nq + e0, 3 * N8 - 4 - e0, 3 * N8 + e0, Nh - 4 - e0};
     f32x4 x[16];
-    if (SRC == 0) {
-        const float* xr = static_cast<const float*>(SRCP) + (size_t)row * W;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            x[u] = *reinterpret_cast<const f32x4*>(xr + pos[u]);
-            x[15 - u] = *reinterpret_cast<const f32x4*>(xr + (W - 4 - pos[u]));
-        }
-    } else {
-        const void* base = SRC == 3 ? static_cast<const void*>(static_cast<const uint16_t*>(SRCP) + (size_t)row * W * 3)
-                           : SRC == 2 ? static_cast<const void*>(static_cast<const uint8_t*>(SRCP) + (size_t)row * W * 3)
-                                    : static_cast<const void*>(static_cast<const float*>(SRCP) + (size_t)row * W * 3);
-        f32x4 iv, qv;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const unsigned p = u < 8 ? pos[u] : W - 4 - pos[15 - u];
-            load_yiq4<SRC - 1, WITH_IQ>(base, p, x[u], iv, qv);
-            if (WITH_IQ) {
-                *reinterpret_cast<f32x4*>(IP + (size_t)row * W + p) = iv;
-                *reinterpret_cast<f32x4*>(QP + (size_t)row * W + p) = qv;
-            }
-        }
-    }
+    for (int u = 0; u < 16; ++u) x[u] = load_row_y4<SRC, WITH_IQ>(SRCP, IP, QP, row, W, u < 8 ? pos[u] : W - 4 - pos[15 - u]);
     // level 1 at the positions of quads 0..7
-    vec4_t<T> S[8], D[8];
+    f64x4 S[8], D[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            S[u][i] = (T)x[u][i] + (T)x[15 - u][3 - i];
-            D[u][i] = (T)x[u][i] - (T)x[15 - u][3 - i];
+            S[u][i] = (double)x[u][i] + (double)x[15 - u][3 - i];
+            D[u][i] = (double)x[u][i] - (double)x[15 - u][3 - i];
         }
     // D (DCT-IV input of length n/2): the unit at e0 and its mirror unit at n/8 - 4 - e0.  AS and BD (class E: a DCT-II
     // and a DST-II of length n/8) fold once more with their mirrors -- element e0 + i meets element n/8 - 1 - (e0 + i), which
     // is element 3 - i of the mirror unit: exact additions -- into AS+ AS- BD+ BD- of length n/16 (launches E even / odd)
     {
-        vec4_t<T> as, bd, ad, bs, asm_, bdm_, adm_, bsm_;
-        split_unit<T>(D[0], D[3], D[4], D[7], rot1, e0, Nq, as, bd, ad, bs);
-        split_unit<T>(D[1], D[2], D[5], D[6], rot1, N8 - 4 - e0, Nq, asm_, bdm_, adm_, bsm_);
+        f64x4 as, bd, ad, bs, asm_, bdm_, adm_, bsm_;
+        split_unit(D[0], D[3], D[4], D[7], rot1, e0, Nq, as, bd, ad, bs);
+        split_unit(D[1], D[2], D[5], D[6], rot1, N8 - 4 - e0, Nq, asm_, bdm_, adm_, bsm_);
         if (efold) {
-            vec4_t<T> p, m, q, r;
+            f64x4 p, m, q, r;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 p[i] = as[i] + asm_[3 - i]; m[i] = as[i] - asm_[3 - i];
                 q[i] = bd[i] + bdm_[3 - i]; r[i] = bd[i] - bdm_[3 - i];
             }
-            put(static_cast<T*>(dp.asp), e0, p); put(static_cast<T*>(dp.asm_), e0, m);
-            put(static_cast<T*>(dp.bdp), e0, q); put(static_cast<T*>(dp.bdm), e0, r);
+            put(static_cast<double*>(dp.asp), e0, p); put(static_cast<double*>(dp.asm_), e0, m);
+            put(static_cast<double*>(dp.bdp), e0, q); put(static_cast<double*>(dp.bdm), e0, r);
             // Class O: X[8i+5] = T(i) + U(i), X[8i+3] = T(i) - U(i) with T the DCT-IV of AD and U the DST-IV of BS, length
             // L = n/8; U(i) = (-1)^i DCT-IV(reversed BS)(i).  One more rotation of the pairs (n, L-1-n), angle pi (2n+1) / (4L)
             // (the table of a length-n/4 axis), turns a DCT-IV of length L into a DCT-II of a and a DST-II of b, length L/2:
@@ -637,26 +545,26 @@ __global__ __launch_bounds__(256) void pair_prep16_rows_kernel(const void* __res
             // With (a, b) of AD plus / minus (a, b) of the reversed BS the two signs of (-1)^i sort themselves into two
             // launches of the class-E shape on the bases of E even: P -> 16j + 5, 16j - 5;  M -> 16j + 3, 16j - 3.
             const f64x4 c3 = *reinterpret_cast<const f64x4*>(rot3 + e0), s3 = *reinterpret_cast<const f64x4*>(rot3 + N16 + e0);
-            vec4_t<T> oap, obp, oam, obm;
+            f64x4 oap, obp, oam, obm;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const T cc = (T)c3[i], ss = (T)s3[i];
-                const T au = ad[i] * cc + adm_[3 - i] * ss, bu = adm_[3 - i] * cc - ad[i] * ss;
-                const T av = bsm_[3 - i] * cc + bs[i] * ss, bv = bs[i] * cc - bsm_[3 - i] * ss;
+                const double cc = c3[i], ss = s3[i];
+                const double au = ad[i] * cc + adm_[3 - i] * ss, bu = adm_[3 - i] * cc - ad[i] * ss;
+                const double av = bsm_[3 - i] * cc + bs[i] * ss, bv = bs[i] * cc - bsm_[3 - i] * ss;
                 oap[i] = au + av; obp[i] = bu + bv;
                 oam[i] = au - av; obm[i] = bu - bv;
             }
-            put(static_cast<T*>(dp.oap), e0, oap); put(static_cast<T*>(dp.obp), e0, obp);
-            put(static_cast<T*>(dp.oam), e0, oam); put(static_cast<T*>(dp.obm), e0, obm);
+            put(static_cast<double*>(dp.oap), e0, oap); put(static_cast<double*>(dp.obp), e0, obp);
+            put(static_cast<double*>(dp.oam), e0, oam); put(static_cast<double*>(dp.obm), e0, obm);
         } else {
-            put(static_cast<T*>(dp.as), e0, as); put(static_cast<T*>(dp.bd), e0, bd);
-            put(static_cast<T*>(dp.as), N8 - 4 - e0, asm_); put(static_cast<T*>(dp.bd), N8 - 4 - e0, bdm_);
+            put(static_cast<double*>(dp.as), e0, as); put(static_cast<double*>(dp.bd), e0, bd);
+            put(static_cast<double*>(dp.as), N8 - 4 - e0, asm_); put(static_cast<double*>(dp.bd), N8 - 4 - e0, bdm_);
             put(AD, e0, ad); put(BS, e0, bs);
             put(AD, N8 - 4 - e0, adm_); put(BS, N8 - 4 - e0, bsm_);
         }
     }
     // level 2 on S (length n/2): quad u mirrors quad 7 - u
-    vec4_t<T> SS[4], SD[4];
+    f64x4 SS[4], SD[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -666,12 +574,12 @@ __global__ __launch_bounds__(256) void pair_prep16_rows_kernel(const void* __res
         }
     // SD (DCT-IV input of length n/4): one unit at e0
     {
-        vec4_t<T> as, bd, ad, bs;
-        split_unit<T>(SD[0], SD[1], SD[2], SD[3], rot2, e0, N8, as, bd, ad, bs);
+        f64x4 as, bd, ad, bs;
+        split_unit(SD[0], SD[1], SD[2], SD[3], rot2, e0, N8, as, bd, ad, bs);
         put(AS2, e0, as); put(BD2, e0, bd); put(AD2, e0, ad); put(BS2, e0, bs);
     }
     // level 3 on SS (length n/4): quad 0 mirrors quad 3, quad 1 mirrors quad 2
-    vec4_t<T> r1q[2], r2q[2];
+    f64x4 r1q[2], r2q[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -682,17 +590,17 @@ __global__ __launch_bounds__(256) void pair_prep16_rows_kernel(const void* __res
     if (efold) {
         // R1 (a DCT-II input of length n/8) folds with its mirror (exact); R2 (a DCT-IV input) rotates like class O above
         const f64x4 c3 = *reinterpret_cast<const f64x4*>(rot3 + e0), s3 = *reinterpret_cast<const f64x4*>(rot3 + N16 + e0);
-        vec4_t<T> p, m, a, b;
+        f64x4 p, m, a, b;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             p[i] = r1q[0][i] + r1q[1][3 - i];
             m[i] = r1q[0][i] - r1q[1][3 - i];
-            const T cc = (T)c3[i], ss = (T)s3[i];
+            const double cc = c3[i], ss = s3[i];
             a[i] = r2q[0][i] * cc + r2q[1][3 - i] * ss;
             b[i] = r2q[1][3 - i] * cc - r2q[0][i] * ss;
         }
-        put(static_cast<T*>(dp.r1p), e0, p); put(static_cast<T*>(dp.r1m), e0, m);
-        put(static_cast<T*>(dp.r2a), e0, a); put(static_cast<T*>(dp.r2b), e0, b);
+        put(static_cast<double*>(dp.r1p), e0, p); put(static_cast<double*>(dp.r1m), e0, m);
+        put(static_cast<double*>(dp.r2a), e0, a); put(static_cast<double*>(dp.r2b), e0, b);
         return;
     }
 #pragma unroll
@@ -703,7 +611,7 @@ __global__ __launch_bounds__(256) void pair_prep16_rows_kernel(const void* __res
     if (e0 == 0)
         for (unsigned z = N8; z < K8; z += 4) {
             put(AD, z, zero); put(BS, z, zero); put(R1, z, zero); put(R2, z, zero);
-            put(static_cast<T*>(dp.as), z, zero); put(static_cast<T*>(dp.bd), z, zero);
+            put(static_cast<double*>(dp.as), z, zero); put(static_cast<double*>(dp.bd), z, zero);
         }
 }
 
@@ -717,12 +625,11 @@ __global__ __launch_bounds__(256) void pair_prep16_rows_kernel(const void* __res
 //   R1(e) = SS[0] + SS[1], R2(e) = SS[0] - SS[1]
 // R1, R2: K8 = kpad(H/4) wide; M: Kq = kpad(H/2); P: Kp = kpad(H); k-blocked, zero padded.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void pair_prep8_cols_kernel(const float* __restrict__ IN, T* __restrict__ R1,
-                                                             T* __restrict__ R2, T* __restrict__ M, T* __restrict__ P,
+__global__ __launch_bounds__(256) void pair_prep8_cols_kernel(const float* __restrict__ IN, double* __restrict__ R1,
+                                                             double* __restrict__ R2, double* __restrict__ M, double* __restrict__ P,
                                                              unsigned W, unsigned H, unsigned K8, unsigned Kq, unsigned Kp,
                                                              unsigned n_frames, unsigned tiles_e, unsigned tiles_c) {
-    __shared__ T s[4][32][33];            // first R1, R2, M(e), M(Hq-1-e); then the four positions of P (34 KB in f64)
+    __shared__ double s[4][32][33];            // first R1, R2, M(e), M(Hq-1-e); then the four positions of P (34 KB in f64)
     const unsigned Hh = H / 2, Hq = H / 4, He = H / 8;
     const unsigned z = blockIdx.x / (tiles_e * tiles_c);
     const unsigned tt = blockIdx.x % (tiles_e * tiles_c);
@@ -734,9 +641,9 @@ __global__ __launch_bounds__(256) void pair_prep8_cols_kernel(const float* __res
     const unsigned cw = c0 + cl, ew = e0 + kq;
     const bool wr = cw < W && ew < K8;
     const size_t line = (size_t)z * W + cw, lines = (size_t)n_frames * W;
-    auto fwd = [&](int a) { return (vec4_t<T>){s[a][cl][kq], s[a][cl][kq + 1], s[a][cl][kq + 2], s[a][cl][kq + 3]}; };
-    auto rev = [&](int a) { return (vec4_t<T>){s[a][cl][kq + 3], s[a][cl][kq + 2], s[a][cl][kq + 1], s[a][cl][kq]}; };
-    T d1[4][4];                                                     // P values of this thread's (e, 4 columns), kept for the second round
+    auto fwd = [&](int a) { return (f64x4){s[a][cl][kq], s[a][cl][kq + 1], s[a][cl][kq + 2], s[a][cl][kq + 3]}; };
+    auto rev = [&](int a) { return (f64x4){s[a][cl][kq + 3], s[a][cl][kq + 2], s[a][cl][kq + 1], s[a][cl][kq]}; };
+    double d1[4][4];                                                     // P values of this thread's (e, 4 columns), kept for the second round
     {
         const unsigned e = e0 + er;
         unsigned c = c0 + cq;
@@ -751,13 +658,13 @@ __global__ __launch_bounds__(256) void pair_prep8_cols_kernel(const float* __res
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            T S[4];
+            double S[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                S[u] = (T)x[u][i] + (T)x[7 - u][i];
-                d1[u][i] = (T)x[u][i] - (T)x[7 - u][i];
+                S[u] = (double)x[u][i] + (double)x[7 - u][i];
+                d1[u][i] = (double)x[u][i] - (double)x[7 - u][i];
             }
-            const T ss0 = S[0] + S[3], ss1 = S[1] + S[2];
+            const double ss0 = S[0] + S[3], ss1 = S[1] + S[2];
             s[0][cq + i][er] = ss0 + ss1;
             s[1][cq + i][er] = ss0 - ss1;
             s[2][cq + i][er] = S[0] - S[3];
@@ -766,14 +673,14 @@ __global__ __launch_bounds__(256) void pair_prep8_cols_kernel(const float* __res
     }
     __syncthreads();
     if (wr) {
-        *reinterpret_cast<vec4_t<T>*>(R1 + blk_index<T>(line, ew, lines)) = fwd(0);      // zero beyond He (x was zero)
-        *reinterpret_cast<vec4_t<T>*>(R2 + blk_index<T>(line, ew, lines)) = fwd(1);
+        *reinterpret_cast<f64x4*>(R1 + blk_index<double>(line, ew, lines)) = fwd(0);      // zero beyond He (x was zero)
+        *reinterpret_cast<f64x4*>(R2 + blk_index<double>(line, ew, lines)) = fwd(1);
         if (ew < He) {                                              // He % 4 == 0: whole quads
-            *reinterpret_cast<vec4_t<T>*>(M + blk_index<T>(line, ew, lines)) = fwd(2);
-            *reinterpret_cast<vec4_t<T>*>(M + blk_index<T>(line, Hq - 4 - ew, lines)) = rev(3);
+            *reinterpret_cast<f64x4*>(M + blk_index<double>(line, ew, lines)) = fwd(2);
+            *reinterpret_cast<f64x4*>(M + blk_index<double>(line, Hq - 4 - ew, lines)) = rev(3);
         }
         if (ew == 0)
-            for (unsigned zz = Hq; zz < Kq; zz += 4) *reinterpret_cast<vec4_t<T>*>(M + blk_index<T>(line, zz, lines)) = (vec4_t<T>){0, 0, 0, 0};
+            for (unsigned zz = Hq; zz < Kq; zz += 4) *reinterpret_cast<f64x4*>(M + blk_index<double>(line, zz, lines)) = (f64x4){0, 0, 0, 0};
     }
     __syncthreads();
 #pragma unroll
@@ -783,13 +690,13 @@ __global__ __launch_bounds__(256) void pair_prep8_cols_kernel(const float* __res
     __syncthreads();
     if (wr) {
         if (ew < He) {
-            *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(line, ew, lines)) = fwd(0);
-            *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(line, Hq - 4 - ew, lines)) = rev(1);
-            *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(line, Hq + ew, lines)) = fwd(2);
-            *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(line, Hh - 4 - ew, lines)) = rev(3);
+            *reinterpret_cast<f64x4*>(P + blk_index<double>(line, ew, lines)) = fwd(0);
+            *reinterpret_cast<f64x4*>(P + blk_index<double>(line, Hq - 4 - ew, lines)) = rev(1);
+            *reinterpret_cast<f64x4*>(P + blk_index<double>(line, Hq + ew, lines)) = fwd(2);
+            *reinterpret_cast<f64x4*>(P + blk_index<double>(line, Hh - 4 - ew, lines)) = rev(3);
         }
         if (ew == 0)
-            for (unsigned zz = Hh; zz < Kp; zz += 4) *reinterpret_cast<vec4_t<T>*>(P + blk_index<T>(line, zz, lines)) = (vec4_t<T>){0, 0, 0, 0};
+            for (unsigned zz = Hh; zz < Kp; zz += 4) *reinterpret_cast<f64x4*>(P + blk_index<double>(line, zz, lines)) = (f64x4){0, 0, 0, 0};
     }
 }
 
@@ -801,24 +708,23 @@ __global__ __launch_bounds__(256) void pair_prep8_cols_kernel(const float* __res
 //   2: AS2 BD2 AD2 BS2 at e        3: R1 R2 at e and at H/8 - 1 - e
 // ---------------------------------------------------------------------------------------------
 // v[0 .. nvalid) -> plane positions k0 .. (ascending); one 32-byte store when the run is a whole aligned quad
-template <typename T>
-__device__ inline void store_run(T* __restrict__ plane, size_t line, size_t lines, unsigned k0, const T (&v)[4], unsigned nvalid) {
+__device__ inline void store_run(double* __restrict__ plane, size_t line, size_t lines, unsigned k0, const double (&v)[4], unsigned nvalid) {
     if (nvalid == 4 && (k0 & 3u) == 0) {
-        *reinterpret_cast<vec4_t<T>*>(plane + blk_index<T>(line, k0, lines)) = (vec4_t<T>){v[0], v[1], v[2], v[3]};
+        *reinterpret_cast<f64x4*>(plane + blk_index<double>(line, k0, lines)) = (f64x4){v[0], v[1], v[2], v[3]};
     } else {
-        for (unsigned j = 0; j < nvalid; ++j) plane[blk_index<T>(line, k0 + j, lines)] = v[j];
+        for (unsigned j = 0; j < nvalid; ++j) plane[blk_index<double>(line, k0 + j, lines)] = v[j];
     }
 }
 
 // SPLIT_SD = false ("semi-deep", H % 8 == 0 but not % 16, e.g. 1080 rows): H/16 is not whole, so SD stays one DCT-IV input
 // plane (`dp.as2`, kpad(H/2) wide: the r2 launch of the frequencies 2 mod 4) and the units run to ceil(H/16) -- the
 // middle unit is its own mirror and stores its values twice.
-template <typename T, bool SPLIT_SD>
+template <bool SPLIT_SD>
 __global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __restrict__ IN, DeepPlanes dp,
                                                               const double* __restrict__ rot1, const double* __restrict__ rot2,
                                                               unsigned W, unsigned H, unsigned K8, unsigned K16,
                                                               unsigned n_frames, unsigned tiles_e, unsigned tiles_c, unsigned class_major, unsigned ctile, unsigned efold) {
-    __shared__ T s[4][32][33];
+    __shared__ double s[4][32][33];
     const unsigned Hh = H / 2, Hq = H / 4, H8 = H / 8, H16 = SPLIT_SD ? H / 16 : (H / 8 + 1) / 2;      // H16: units
     const unsigned z = blockIdx.x / (tiles_e * tiles_c);
     const unsigned tt = blockIdx.x % (tiles_e * tiles_c);
@@ -841,9 +747,9 @@ __global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __re
     // operand line -- and with it the output column of the column GEMMs -- is the natural one
     const unsigned cn = (class_major && col_ok) ? ForwardClassLayout{W, ctile, efold != 0}.natural(cw) : cw;
     const size_t line = (size_t)z * W + cn, lines = (size_t)n_frames * W;
-    T* planes8[6] = {static_cast<T*>(dp.as), static_cast<T*>(dp.bd), static_cast<T*>(dp.ad), static_cast<T*>(dp.bs),
-                     static_cast<T*>(dp.r1), static_cast<T*>(dp.r2)};
-    T* planes16[4] = {static_cast<T*>(dp.as2), static_cast<T*>(dp.bd2), static_cast<T*>(dp.ad2), static_cast<T*>(dp.bs2)};
+    double* planes8[6] = {static_cast<double*>(dp.as), static_cast<double*>(dp.bd), static_cast<double*>(dp.ad), static_cast<double*>(dp.bs),
+                     static_cast<double*>(dp.r1), static_cast<double*>(dp.r2)};
+    double* planes16[4] = {static_cast<double*>(dp.as2), static_cast<double*>(dp.bd2), static_cast<double*>(dp.ad2), static_cast<double*>(dp.bs2)};
     const unsigned e = e0 + er;
     const bool unit_ok = e < H16;
     const unsigned ec = unit_ok ? e : 0;                           // table indices stay in range
@@ -863,11 +769,11 @@ __global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __re
         }
     }
     const unsigned nvalid = !col_ok ? 0u : (ew >= H16 ? 0u : (H16 - ew < 4 ? H16 - ew : 4u));      // valid units of the store quad
-    auto gather = [&](int a, T (&v)[4], bool reverse) {
+    auto gather = [&](int a, double (&v)[4], bool reverse) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = s[a][cl][kq + j];
         if (reverse) {                                              // first nvalid entries, reversed
-            T w[4] = {0, 0, 0, 0};
+            double w[4] = {0, 0, 0, 0};
             for (unsigned j = 0; j < nvalid; ++j) w[j] = v[nvalid - 1 - j];
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = w[j];
@@ -878,23 +784,23 @@ __global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __re
         if (round) __syncthreads();
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            T D[8], S[8];
+            double D[8], S[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                S[u] = (T)x[u][i] + (T)x[15 - u][i];
-                D[u] = (T)x[u][i] - (T)x[15 - u][i];
+                S[u] = (double)x[u][i] + (double)x[15 - u][i];
+                D[u] = (double)x[u][i] - (double)x[15 - u][i];
             }
-            T o[4] = {0, 0, 0, 0};
+            double o[4] = {0, 0, 0, 0};
             if (round == 0) {
-                split_one<T>(D[0], D[3], D[4], D[7], rot1, ec, Hq, o[0], o[1], o[2], o[3]);
+                split_one(D[0], D[3], D[4], D[7], rot1, ec, Hq, o[0], o[1], o[2], o[3]);
             } else if (round == 1) {
-                split_one<T>(D[1], D[2], D[5], D[6], rot1, H8 - 1 - ec, Hq, o[0], o[1], o[2], o[3]);
+                split_one(D[1], D[2], D[5], D[6], rot1, H8 - 1 - ec, Hq, o[0], o[1], o[2], o[3]);
             } else {
-                T SS[4], SD[4];
+                double SS[4], SD[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) { SS[u] = S[u] + S[7 - u]; SD[u] = S[u] - S[7 - u]; }
                 if (round == 2) {
-                    if (SPLIT_SD) split_one<T>(SD[0], SD[1], SD[2], SD[3], rot2, ec, H8, o[0], o[1], o[2], o[3]);
+                    if (SPLIT_SD) split_one(SD[0], SD[1], SD[2], SD[3], rot2, ec, H8, o[0], o[1], o[2], o[3]);
                     else { o[0] = SD[0]; o[1] = SD[1]; o[2] = SD[2]; o[3] = SD[3]; }      // SD at e, H/8-1-e, H/8+e, H/4-1-e
                 } else {
                     o[0] = SS[0] + SS[3]; o[1] = SS[0] - SS[3];      // R1, R2 at e
@@ -902,38 +808,38 @@ __global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __re
                 }
             }
 #pragma unroll
-            for (int a = 0; a < 4; ++a) s[a][cq + i][er] = unit_ok ? o[a] : (T)0;
+            for (int a = 0; a < 4; ++a) s[a][cq + i][er] = unit_ok ? o[a] : 0.0;
         }
         __syncthreads();
         if (col_ok && ew < (SPLIT_SD ? K16 : ((H16 + 3) & ~3u))) {
-            T v[4];
+            double v[4];
             if (round == 0) {
 #pragma unroll
-                for (int a = 0; a < 4; ++a) { gather(a, v, false); store_run<T>(planes8[a], line, lines, ew, v, nvalid); }
+                for (int a = 0; a < 4; ++a) { gather(a, v, false); store_run(planes8[a], line, lines, ew, v, nvalid); }
             } else if (round == 1) {
 #pragma unroll
-                for (int a = 0; a < 4; ++a) { gather(a, v, true); if (nvalid) store_run<T>(planes8[a], line, lines, H8 - ew - nvalid, v, nvalid); }
+                for (int a = 0; a < 4; ++a) { gather(a, v, true); if (nvalid) store_run(planes8[a], line, lines, H8 - ew - nvalid, v, nvalid); }
             } else if (round == 2) {
                 if (SPLIT_SD) {
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) { gather(a, v, false); store_run<T>(planes16[a], line, lines, ew, v, 4u); }   // zeros beyond H/16
+                    for (int a = 0; a < 4; ++a) { gather(a, v, false); store_run(planes16[a], line, lines, ew, v, 4u); }   // zeros beyond H/16
                 } else {
-                    T* M = planes16[0];
-                    gather(0, v, false); store_run<T>(M, line, lines, ew, v, nvalid);
-                    gather(2, v, false); store_run<T>(M, line, lines, H8 + ew, v, nvalid);
-                    gather(1, v, true); if (nvalid) store_run<T>(M, line, lines, H8 - ew - nvalid, v, nvalid);
-                    gather(3, v, true); if (nvalid) store_run<T>(M, line, lines, Hq - ew - nvalid, v, nvalid);
-                    if (ew == 0) for (unsigned k = Hq; k < K16; ++k) M[blk_index<T>(line, k, lines)] = (T)0;      // K16: kpad(H/2) here
+                    double* M = planes16[0];
+                    gather(0, v, false); store_run(M, line, lines, ew, v, nvalid);
+                    gather(2, v, false); store_run(M, line, lines, H8 + ew, v, nvalid);
+                    gather(1, v, true); if (nvalid) store_run(M, line, lines, H8 - ew - nvalid, v, nvalid);
+                    gather(3, v, true); if (nvalid) store_run(M, line, lines, Hq - ew - nvalid, v, nvalid);
+                    if (ew == 0) for (unsigned k = Hq; k < K16; ++k) M[blk_index<double>(line, k, lines)] = 0.0;      // K16: kpad(H/2) here
                 }
             } else {
-                gather(0, v, false); store_run<T>(planes8[4], line, lines, ew, v, nvalid);
-                gather(1, v, false); store_run<T>(planes8[5], line, lines, ew, v, nvalid);
-                gather(2, v, true); if (nvalid) store_run<T>(planes8[4], line, lines, H8 - ew - nvalid, v, nvalid);
-                gather(3, v, true); if (nvalid) store_run<T>(planes8[5], line, lines, H8 - ew - nvalid, v, nvalid);
+                gather(0, v, false); store_run(planes8[4], line, lines, ew, v, nvalid);
+                gather(1, v, false); store_run(planes8[5], line, lines, ew, v, nvalid);
+                gather(2, v, true); if (nvalid) store_run(planes8[4], line, lines, H8 - ew - nvalid, v, nvalid);
+                gather(3, v, true); if (nvalid) store_run(planes8[5], line, lines, H8 - ew - nvalid, v, nvalid);
                 if (ew == 0)
                     for (unsigned k = H8; k < K8; ++k)
 #pragma unroll
-                        for (int a = 0; a < 6; ++a) planes8[a][blk_index<T>(line, k, lines)] = (T)0;
+                        for (int a = 0; a < 6; ++a) planes8[a][blk_index<double>(line, k, lines)] = 0.0;
             }
         }
     }
@@ -953,7 +859,6 @@ __global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __re
 // Row pass (n % 128 == 0): one thread = the eight 16-element regions of a line that close under those pairings,
 //   g = R, n/4-16-R, n/4+R, n/2-16-R, n/2+R, 3n/4-16-R, 3n/4+R, n-16-R   (R = 16 t): 128 coefficients in, 128 doubles out.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
 __global__ __launch_bounds__(256) void pair_prep16_inv_rows_kernel(const float* __restrict__ X, DeepPlanes dp,
                                                                   const double* __restrict__ rot1, const double* __restrict__ rot2,
                                                                   unsigned rows, unsigned W, unsigned K8, unsigned K16, unsigned tp_line /*threads per line, power of 2*/) {
@@ -962,10 +867,10 @@ __global__ __launch_bounds__(256) void pair_prep16_inv_rows_kernel(const float* 
     const unsigned R = 16 * t;
     const unsigned Nh = W / 2, Nq = W / 4, N8 = W / 8, N16 = W / 16;
     if (row >= rows || R >= N8) return;
-    T* P8[6] = {static_cast<T*>(dp.as), static_cast<T*>(dp.bd), static_cast<T*>(dp.ad), static_cast<T*>(dp.bs), static_cast<T*>(dp.r1), static_cast<T*>(dp.r2)};
-    T* P16[4] = {static_cast<T*>(dp.as2), static_cast<T*>(dp.bd2), static_cast<T*>(dp.ad2), static_cast<T*>(dp.bs2)};
-    auto put4 = [&](T* plane, unsigned k, const vec4_t<T>& v) { *reinterpret_cast<vec4_t<T>*>(plane + blk_index<T>(row, k, rows)) = v; };
-    auto put2 = [&](T* plane, unsigned k, T a, T b) { *reinterpret_cast<vec2_t<T>*>(plane + blk_index<T>(row, k, rows)) = (vec2_t<T>){a, b}; };
+    double* P8[6] = {static_cast<double*>(dp.as), static_cast<double*>(dp.bd), static_cast<double*>(dp.ad), static_cast<double*>(dp.bs), static_cast<double*>(dp.r1), static_cast<double*>(dp.r2)};
+    double* P16[4] = {static_cast<double*>(dp.as2), static_cast<double*>(dp.bd2), static_cast<double*>(dp.ad2), static_cast<double*>(dp.bs2)};
+    auto put4 = [&](double* plane, unsigned k, const f64x4& v) { *reinterpret_cast<f64x4*>(plane + blk_index<double>(row, k, rows)) = v; };
+    auto put2 = [&](double* plane, unsigned k, double a, double b) { *reinterpret_cast<f64x2*>(plane + blk_index<double>(row, k, rows)) = (f64x2){a, b}; };
     const unsigned g[8] = {R, Nq - 16 - R, Nq + R, Nh - 16 - R, Nh + R, 3 * Nq - 16 - R, 3 * Nq + R, W - 16 - R};
     const float* xr = X + (size_t)row * W;
     f32x4 c[8][4];
@@ -974,35 +879,35 @@ __global__ __launch_bounds__(256) void pair_prep16_inv_rows_kernel(const float* 
 #pragma unroll
         for (int q = 0; q < 4; ++q) c[j][q] = *reinterpret_cast<const f32x4*>(xr + g[j] + 4 * q);
     // odd coefficients of region j as two ascending quads of k: element u = 2 t + 1 -> quad t / 4
-    auto odd = [&](int j, int half) { return (vec4_t<T>){(T)c[j][2 * half][1], (T)c[j][2 * half][3], (T)c[j][2 * half + 1][1], (T)c[j][2 * half + 1][3]}; };
+    auto odd = [&](int j, int half) { return (f64x4){(double)c[j][2 * half][1], (double)c[j][2 * half][3], (double)c[j][2 * half + 1][1], (double)c[j][2 * half + 1][3]}; };
     // unit A: k = e0 .. e0+7 (e0 = R/2) from regions 0, 3, 4, 7; its mirror unit n/8-8-e0 .. from regions 1, 2, 5, 6
     const unsigned e0 = R / 2, m0u = N8 - 8 - e0;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-        vec4_t<T> as, bd, ad, bs;
-        split_unit<T>(odd(0, half), odd(3, 1 - half), odd(4, half), odd(7, 1 - half), rot1, e0 + 4 * half, Nq, as, bd, ad, bs);
+        f64x4 as, bd, ad, bs;
+        split_unit(odd(0, half), odd(3, 1 - half), odd(4, half), odd(7, 1 - half), rot1, e0 + 4 * half, Nq, as, bd, ad, bs);
         put4(P8[0], e0 + 4 * half, as); put4(P8[1], e0 + 4 * half, bd); put4(P8[2], e0 + 4 * half, ad); put4(P8[3], e0 + 4 * half, bs);
-        split_unit<T>(odd(1, half), odd(2, 1 - half), odd(5, half), odd(6, 1 - half), rot1, m0u + 4 * half, Nq, as, bd, ad, bs);
+        split_unit(odd(1, half), odd(2, 1 - half), odd(5, half), odd(6, 1 - half), rot1, m0u + 4 * half, Nq, as, bd, ad, bs);
         put4(P8[0], m0u + 4 * half, as); put4(P8[1], m0u + 4 * half, bd); put4(P8[2], m0u + 4 * half, ad); put4(P8[3], m0u + 4 * half, bs);
     }
     // c[4q+2]: element 2 of every quad of a region, q ascending
-    auto mid = [&](int j) { return (vec4_t<T>){(T)c[j][0][2], (T)c[j][1][2], (T)c[j][2][2], (T)c[j][3][2]}; };
+    auto mid = [&](int j) { return (f64x4){(double)c[j][0][2], (double)c[j][1][2], (double)c[j][2][2], (double)c[j][3][2]}; };
     {
         const unsigned f0 = R / 4, f1 = N16 - 4 - f0;
-        vec4_t<T> as, bd, ad, bs;
-        split_unit<T>(mid(0), mid(3), mid(4), mid(7), rot2, f0, N8, as, bd, ad, bs);
+        f64x4 as, bd, ad, bs;
+        split_unit(mid(0), mid(3), mid(4), mid(7), rot2, f0, N8, as, bd, ad, bs);
         put4(P16[0], f0, as); put4(P16[1], f0, bd); put4(P16[2], f0, ad); put4(P16[3], f0, bs);
-        split_unit<T>(mid(1), mid(2), mid(5), mid(6), rot2, f1, N8, as, bd, ad, bs);
+        split_unit(mid(1), mid(2), mid(5), mid(6), rot2, f1, N8, as, bd, ad, bs);
         put4(P16[0], f1, as); put4(P16[1], f1, bd); put4(P16[2], f1, ad); put4(P16[3], f1, bs);
     }
     // c[8q] and c[8q+4]: elements 0 of quads 0, 2 and of quads 1, 3
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        put2(P8[4], g[j] / 8, (T)c[j][0][0], (T)c[j][2][0]);
-        put2(P8[5], g[j] / 8, (T)c[j][1][0], (T)c[j][3][0]);
+        put2(P8[4], g[j] / 8, (double)c[j][0][0], (double)c[j][2][0]);
+        put2(P8[5], g[j] / 8, (double)c[j][1][0], (double)c[j][3][0]);
     }
     if (t == 0) {
-        const vec4_t<T> zero = {0, 0, 0, 0};
+        const f64x4 zero = {0, 0, 0, 0};
         for (unsigned z = N8; z < K8; z += 4)
 #pragma unroll
             for (int a = 0; a < 6; ++a) put4(P8[a], z, zero);
@@ -1018,12 +923,12 @@ __global__ __launch_bounds__(256) void pair_prep16_inv_rows_kernel(const float* 
 // is a whole 64-byte piece of one line where the positions allow it.
 // SPLIT_MID = false ("semi-deep", H % 8 == 0 but not % 16): c[4q+2] stays one DCT-IV input plane (`dp.as2`, kpad(H/2)
 // wide) and the units run to ceil(H/16); the middle unit is its own mirror and stores its values twice.
-template <typename T, bool SPLIT_MID>
+template <bool SPLIT_MID>
 __global__ __launch_bounds__(256) void pair_prep16_inv_cols_kernel(const float* __restrict__ IN, DeepPlanes dp,
                                                                   const double* __restrict__ rot1, const double* __restrict__ rot2,
                                                                   unsigned W, unsigned H, unsigned K8, unsigned K16,
                                                                   unsigned n_frames, unsigned groups, unsigned tiles_c, unsigned class_major, unsigned ctile) {
-    __shared__ T s[16][32][9];
+    __shared__ double s[16][32][9];
     const unsigned Hh = H / 2, Hq = H / 4, H8 = H / 8, H16 = SPLIT_MID ? H / 16 : (H / 8 + 1) / 2;      // H16: units
     const unsigned z = blockIdx.x / (groups * tiles_c);
     const unsigned tt = blockIdx.x % (groups * tiles_c);
@@ -1034,75 +939,75 @@ __global__ __launch_bounds__(256) void pair_prep16_inv_cols_kernel(const float* 
     // of a row are four 32-byte runs (one per residue class) and the stores below stay runs of consecutive operand lines
     const unsigned coln = c0 + cl < W ? c0 + cl : W - 1;
     const unsigned col = class_major ? inverse_class_pos(coln, W, ctile, class_major == 2) : coln;      // 2: the level-2 order
-    auto ld = [&](unsigned r) { return (T)Pz[(size_t)r * W + col]; };
-    T* P8[6] = {static_cast<T*>(dp.as), static_cast<T*>(dp.bd), static_cast<T*>(dp.ad), static_cast<T*>(dp.bs), static_cast<T*>(dp.r1), static_cast<T*>(dp.r2)};
-    T* P16[4] = {static_cast<T*>(dp.as2), static_cast<T*>(dp.bd2), static_cast<T*>(dp.ad2), static_cast<T*>(dp.bs2)};
+    auto ld = [&](unsigned r) { return (double)Pz[(size_t)r * W + col]; };
+    double* P8[6] = {static_cast<double*>(dp.as), static_cast<double*>(dp.bd), static_cast<double*>(dp.ad), static_cast<double*>(dp.bs), static_cast<double*>(dp.r1), static_cast<double*>(dp.r2)};
+    double* P16[4] = {static_cast<double*>(dp.as2), static_cast<double*>(dp.bd2), static_cast<double*>(dp.ad2), static_cast<double*>(dp.bs2)};
     const unsigned e = 8 * G + t;                                  // D-split pair index (< H/16) and level-2 unit (< H/16)
     const bool ok = e < H16;
     const unsigned ec = ok ? e : 0, em = H8 - 1 - ec;
-    T o[16];
+    double o[16];
     {   // odd coefficients: k -> row 2k+1; unit at e: k = e, H/4-1-e, H/4+e, H/2-1-e; mirror unit at em
-        const T d0 = ld(2 * ec + 1), d1 = ld(Hh - 1 - 2 * ec), d2 = ld(Hh + 2 * ec + 1), d3 = ld(H - 1 - 2 * ec);
-        split_one<T>(d0, d1, d2, d3, rot1, ec, Hq, o[0], o[1], o[2], o[3]);
-        const T m0v = ld(2 * em + 1), m1 = ld(Hh - 1 - 2 * em), m2 = ld(Hh + 2 * em + 1), m3 = ld(H - 1 - 2 * em);
-        split_one<T>(m0v, m1, m2, m3, rot1, em, Hq, o[4], o[5], o[6], o[7]);
+        const double d0 = ld(2 * ec + 1), d1 = ld(Hh - 1 - 2 * ec), d2 = ld(Hh + 2 * ec + 1), d3 = ld(H - 1 - 2 * ec);
+        split_one(d0, d1, d2, d3, rot1, ec, Hq, o[0], o[1], o[2], o[3]);
+        const double m0v = ld(2 * em + 1), m1 = ld(Hh - 1 - 2 * em), m2 = ld(Hh + 2 * em + 1), m3 = ld(H - 1 - 2 * em);
+        split_one(m0v, m1, m2, m3, rot1, em, Hq, o[4], o[5], o[6], o[7]);
         // c[4q+2]: q = e, H/8-1-e, H/8+e, H/4-1-e
-        const T q0 = ld(4 * ec + 2), q1 = ld(Hh - 2 - 4 * ec), q2 = ld(Hh + 4 * ec + 2), q3 = ld(H - 2 - 4 * ec);
-        if (SPLIT_MID) split_one<T>(q0, q1, q2, q3, rot2, ec, H8, o[8], o[9], o[10], o[11]);
+        const double q0 = ld(4 * ec + 2), q1 = ld(Hh - 2 - 4 * ec), q2 = ld(Hh + 4 * ec + 2), q3 = ld(H - 2 - 4 * ec);
+        if (SPLIT_MID) split_one(q0, q1, q2, q3, rot2, ec, H8, o[8], o[9], o[10], o[11]);
         else { o[8] = q0; o[9] = q1; o[10] = q2; o[11] = q3; }          // c[4q+2] itself at q = e, H/8-1-e, H/8+e, H/4-1-e
         // c[8q], c[8q+4] for q = 2e, 2e+1 (< H/8; with an odd H/8 the last unit has one)
         const bool q2ok = 2 * ec + 1 < H8;
-        o[12] = ld(16 * ec); o[13] = q2ok ? ld(16 * ec + 8) : (T)0; o[14] = ld(16 * ec + 4); o[15] = q2ok ? ld(16 * ec + 12) : (T)0;
+        o[12] = ld(16 * ec); o[13] = q2ok ? ld(16 * ec + 8) : 0.0; o[14] = ld(16 * ec + 4); o[15] = q2ok ? ld(16 * ec + 12) : 0.0;
     }
 #pragma unroll
-    for (int v = 0; v < 16; ++v) s[v][cl][t] = ok ? o[v] : (T)0;
+    for (int v = 0; v < 16; ++v) s[v][cl][t] = ok ? o[v] : 0.0;
     __syncthreads();
     if (c0 + cl >= W) return;
     const size_t line = (size_t)z * W + c0 + cl, lines = (size_t)n_frames * W;
     const unsigned nv = 8 * G >= H16 ? 0u : (H16 - 8 * G < 8 ? H16 - 8 * G : 8u);          // valid units of the group
     const unsigned h = t;                                          // store side: thread h of a column takes value type h
     {   // AS BD AD BS at e = 8G .. (h < 4) or at the mirror units H/8 - 1 - e, ascending from H/8 - 8G - nv (h >= 4)
-        T* plane = P8[h & 3];
+        double* plane = P8[h & 3];
         if (h < 4) {
             if (nv == 8) {
-                T* o8 = plane + blk_index<T>(line, 8 * G, lines);
-                *reinterpret_cast<vec4_t<T>*>(o8) = (vec4_t<T>){s[h][cl][0], s[h][cl][1], s[h][cl][2], s[h][cl][3]};
-                *reinterpret_cast<vec4_t<T>*>(o8 + 4) = (vec4_t<T>){s[h][cl][4], s[h][cl][5], s[h][cl][6], s[h][cl][7]};
+                double* o8 = plane + blk_index<double>(line, 8 * G, lines);
+                *reinterpret_cast<f64x4*>(o8) = (f64x4){s[h][cl][0], s[h][cl][1], s[h][cl][2], s[h][cl][3]};
+                *reinterpret_cast<f64x4*>(o8 + 4) = (f64x4){s[h][cl][4], s[h][cl][5], s[h][cl][6], s[h][cl][7]};
             } else {
-                for (unsigned j = 0; j < nv; ++j) plane[blk_index<T>(line, 8 * G + j, lines)] = s[h][cl][j];
+                for (unsigned j = 0; j < nv; ++j) plane[blk_index<double>(line, 8 * G + j, lines)] = s[h][cl][j];
             }
         } else {
             const unsigned k0 = H8 - 8 * G - nv;
             if (nv == 8 && (k0 & 7u) == 0) {
-                T* o8 = plane + blk_index<T>(line, k0, lines);
-                *reinterpret_cast<vec4_t<T>*>(o8) = (vec4_t<T>){s[h][cl][7], s[h][cl][6], s[h][cl][5], s[h][cl][4]};
-                *reinterpret_cast<vec4_t<T>*>(o8 + 4) = (vec4_t<T>){s[h][cl][3], s[h][cl][2], s[h][cl][1], s[h][cl][0]};
+                double* o8 = plane + blk_index<double>(line, k0, lines);
+                *reinterpret_cast<f64x4*>(o8) = (f64x4){s[h][cl][7], s[h][cl][6], s[h][cl][5], s[h][cl][4]};
+                *reinterpret_cast<f64x4*>(o8 + 4) = (f64x4){s[h][cl][3], s[h][cl][2], s[h][cl][1], s[h][cl][0]};
             } else {
-                for (unsigned j = 0; j < nv; ++j) plane[blk_index<T>(line, k0 + j, lines)] = s[h][cl][nv - 1 - j];
+                for (unsigned j = 0; j < nv; ++j) plane[blk_index<double>(line, k0 + j, lines)] = s[h][cl][nv - 1 - j];
             }
         }
     }
     if (SPLIT_MID) {   // AS2 .. BS2 at e' = 8G + 4 (h / 4) .. +3: zeros beyond H/16 (the planes are K16 wide)
-        T* plane = P16[h & 3];
+        double* plane = P16[h & 3];
         const unsigned k0 = 8 * G + 4 * (h >> 2), j0 = 4 * (h >> 2);
-        if (k0 < K16) *reinterpret_cast<vec4_t<T>*>(plane + blk_index<T>(line, k0, lines)) = (vec4_t<T>){s[8 + (h & 3)][cl][j0], s[8 + (h & 3)][cl][j0 + 1], s[8 + (h & 3)][cl][j0 + 2], s[8 + (h & 3)][cl][j0 + 3]};
+        if (k0 < K16) *reinterpret_cast<f64x4*>(plane + blk_index<double>(line, k0, lines)) = (f64x4){s[8 + (h & 3)][cl][j0], s[8 + (h & 3)][cl][j0 + 1], s[8 + (h & 3)][cl][j0 + 2], s[8 + (h & 3)][cl][j0 + 3]};
     } else if (h < 4) {   // the c[4q+2] plane: thread h takes the run of value type 8 + h (ascending for h = 0, 2; mirrored for 1, 3)
-        T* plane = P16[0];
+        double* plane = P16[0];
         const unsigned start = h == 0 ? 8 * G : h == 2 ? H8 + 8 * G : (h == 1 ? H8 : Hq) - 8 * G - nv;
-        for (unsigned j = 0; j < nv; ++j) plane[blk_index<T>(line, start + j, lines)] = s[8 + h][cl][(h & 1) ? nv - 1 - j : j];
-        if (G == 0 && h == 0) for (unsigned k = Hq; k < K16; ++k) plane[blk_index<T>(line, k, lines)] = (T)0;      // K16: kpad(H/2) here
+        for (unsigned j = 0; j < nv; ++j) plane[blk_index<double>(line, start + j, lines)] = s[8 + h][cl][(h & 1) ? nv - 1 - j : j];
+        if (G == 0 && h == 0) for (unsigned k = Hq; k < K16; ++k) plane[blk_index<double>(line, k, lines)] = 0.0;      // K16: kpad(H/2) here
     }
     {   // R1 = c[8q], R2 = c[8q+4] at q = 16G + 2h, +1 (units beyond H/16 wrote zeros: padding up to K8 where 16G < K8)
         const unsigned q0 = 16 * G + 2 * h;
         if (q0 < K8) {
-            *reinterpret_cast<vec2_t<T>*>(P8[4] + blk_index<T>(line, q0, lines)) = (vec2_t<T>){s[12][cl][h], s[13][cl][h]};
-            *reinterpret_cast<vec2_t<T>*>(P8[5] + blk_index<T>(line, q0, lines)) = (vec2_t<T>){s[14][cl][h], s[15][cl][h]};
+            *reinterpret_cast<f64x2*>(P8[4] + blk_index<double>(line, q0, lines)) = (f64x2){s[12][cl][h], s[13][cl][h]};
+            *reinterpret_cast<f64x2*>(P8[5] + blk_index<double>(line, q0, lines)) = (f64x2){s[14][cl][h], s[15][cl][h]};
         }
     }
     if (G == 0 && h == 0)                                           // AS .. BS beyond H/8
         for (unsigned k = H8; k < K8; ++k)
 #pragma unroll
-            for (int a = 0; a < 4; ++a) P8[a][blk_index<T>(line, k, lines)] = (T)0;
+            for (int a = 0; a < 4; ++a) P8[a][blk_index<double>(line, k, lines)] = 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1122,69 +1027,55 @@ int launch_dct_pair_prep(hipStream_t st, bool is_row, bool inverse, const float*
         const size_t rows = n_frames * h;
         const unsigned long long nblk = (unsigned long long)((rows + 31) / 32) * tiles_k;
         if (rows > 0xFFFFFFFFull || nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-        if (inverse) pair_prep_rows_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)rows, (unsigned)w, Kp, tiles_k);
-        else         pair_prep_rows_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)rows, (unsigned)w, Kp, tiles_k);
+        if (inverse) pair_prep_rows_kernel<true><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)rows, (unsigned)w, Kp, tiles_k);
+        else         pair_prep_rows_kernel<false><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)rows, (unsigned)w, Kp, tiles_k);
     } else {
         const unsigned Kp = (unsigned)pair_kpad(h);
         const unsigned tiles_k = (Kp + 31) / 32, tiles_c = (unsigned)((w + 63) / 64);
         const unsigned long long nblk = (unsigned long long)tiles_k * tiles_c * n_frames;
         if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-        if (inverse) pair_prep_cols_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)w, (unsigned)h, Kp, (unsigned)n_frames, tiles_k, tiles_c);
-        else         pair_prep_cols_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)w, (unsigned)h, Kp, (unsigned)n_frames, tiles_k, tiles_c);
+        if (inverse) pair_prep_cols_kernel<true><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)w, (unsigned)h, Kp, (unsigned)n_frames, tiles_k, tiles_c);
+        else         pair_prep_cols_kernel<false><<<(unsigned)nblk, 256, 0, st>>>(in, o1, o2, (unsigned)w, (unsigned)h, Kp, (unsigned)n_frames, tiles_k, tiles_c);
     }
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
 
-int launch_dct_pair_prep4(hipStream_t st, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w, size_t h,
+// rows-first forward transform: the row pre-pass reads the plane or the interleaved RGB frames themselves (in.i / in.q, both or
+// neither, receive the I and Q planes); column and inverse passes read a plane
+int launch_dct_pair_prep4(hipStream_t st, bool is_row, bool inverse, const RowInput& in, size_t n_frames, size_t w, size_t h,
                           double* q1, double* q2, double* p) {
     if (n_frames == 0) return SSW_OK;
-    if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
+    const bool plane = in.kind == RowSrc::Plane;
+    if (w > 0xFFFFFFull || h > 0xFFFFFFull || (plane && n_frames > 0xFFFFFFull)) return SSW_ERR_BAD_DIMS;
+    if (!plane && (!is_row || inverse)) return SSW_ERR_BAD_ARG;
     const size_t len = is_row ? w : h;
     const unsigned Kp = (unsigned)pair_kpad(len), Kq = (unsigned)pair_kpad(len / 2);
     const unsigned tiles_q = (Kq + 31) / 32;
+    const float* x = static_cast<const float*>(in.p);
     if (is_row) {
         const size_t rows = n_frames * h;
         const unsigned long long nblk = (unsigned long long)((rows + 31) / 32) * tiles_q;
         if (rows > 0xFFFFFFFFull || nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-        if (inverse) pair_prep4_rows_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)rows, (unsigned)w, Kq, Kp, tiles_q);
-        else         pair_prep4_rows_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)rows, (unsigned)w, Kq, Kp, tiles_q);
+        if (inverse) pair_prep4_rows_kernel<true, RowSrc::Plane, false><<<(unsigned)nblk, 256, 0, st>>>(x, q1, q2, p, nullptr, nullptr, (unsigned)rows, (unsigned)w, Kq, Kp, tiles_q);
+        else SSW_TRY(dispatch_row_src(in, [&](auto src, auto iq) {
+            pair_prep4_rows_kernel<false, decltype(src)::value, decltype(iq)::value><<<(unsigned)nblk, 256, 0, st>>>(
+                in.p, q1, q2, p, in.i, in.q, (unsigned)rows, (unsigned)w, Kq, Kp, tiles_q);
+        }));
     } else {
         const unsigned tiles_c = (unsigned)((w + 31) / 32);
         const unsigned long long nblk = (unsigned long long)tiles_q * tiles_c * n_frames;
         if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-        if (inverse) pair_prep4_cols_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)w, (unsigned)h, Kq, Kp, (unsigned)n_frames, tiles_q, tiles_c);
-        else         pair_prep4_cols_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, q1, q2, p, (unsigned)w, (unsigned)h, Kq, Kp, (unsigned)n_frames, tiles_q, tiles_c);
+        if (inverse) pair_prep4_cols_kernel<true><<<(unsigned)nblk, 256, 0, st>>>(x, q1, q2, p, (unsigned)w, (unsigned)h, Kq, Kp, (unsigned)n_frames, tiles_q, tiles_c);
+        else         pair_prep4_cols_kernel<false><<<(unsigned)nblk, 256, 0, st>>>(x, q1, q2, p, (unsigned)w, (unsigned)h, Kq, Kp, (unsigned)n_frames, tiles_q, tiles_c);
     }
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
 
-// rows-first forward transform with two folding levels on the row axis: the first pre-pass straight
-// from the interleaved RGB frames (u8 or f32); ip / qp (both or neither) receive the I and Q planes.
-int launch_dct_pair_prep4_rows_rgb(hipStream_t st, int u8, const void* rgb, size_t n_frames, size_t w, size_t h,
-                                   double* q1, double* q2, double* p, float* ip, float* qp) {
-    if (n_frames == 0) return SSW_OK;
-    if (w > 0xFFFFFFull || h > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const unsigned Kp = (unsigned)pair_kpad(w), Kq = (unsigned)pair_kpad(w / 2), tiles_q = (Kq + 31) / 32;
-    const size_t rows = n_frames * h;
-    const unsigned long long nblk = (unsigned long long)((rows + 31) / 32) * tiles_q;
-    if (rows > 0xFFFFFFFFull || nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const bool iq = ip && qp;
-#define SSW_PREP_RGB(U8V, IQV) pair_prep4_rows_rgb_kernel<double, U8V, IQV><<<(unsigned)nblk, 256, 0, st>>>( \
-        rgb, q1, q2, p, ip, qp, (unsigned)rows, (unsigned)w, Kq, Kp, tiles_q)
-    if (u8 == SSW_PIX_U8)       { if (iq) SSW_PREP_RGB(SSW_PIX_U8, true); else SSW_PREP_RGB(SSW_PIX_U8, false); }
-    else if (u8 == SSW_PIX_U16) { if (iq) SSW_PREP_RGB(SSW_PIX_U16, true); else SSW_PREP_RGB(SSW_PIX_U16, false); }
-    else                        { if (iq) SSW_PREP_RGB(SSW_PIX_F32, true); else SSW_PREP_RGB(SSW_PIX_F32, false); }
-#undef SSW_PREP_RGB
-    SSW_HIP_CHECK(hipGetLastError());
-    return SSW_OK;
-}
-
-// third folding level along an axis of length len (forward row passes only)
-// src_kind: 0 = f32 plane, 1 = interleaved RGB f32, 2 = interleaved RGB u8 (ip / qp: I, Q planes out or null)
-int launch_dct_pair_prep8_rows(hipStream_t st, int src_kind, const void* src, size_t n_frames, size_t w, size_t h,
-                               double* r1, double* r2, double* m, double* p, float* ip, float* qp) {
+// third folding level along the rows (forward row passes only)
+int launch_dct_pair_prep8_rows(hipStream_t st, const RowInput& in, size_t n_frames, size_t w, size_t h,
+                               double* r1, double* r2, double* m, double* p) {
     if (n_frames == 0) return SSW_OK;
     if (w > 0xFFFFFFull || h > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
     const unsigned Kp = (unsigned)pair_kpad(w), Kq = (unsigned)pair_kpad(w / 2), K8 = (unsigned)pair_kpad(w / 4);
@@ -1192,14 +1083,10 @@ int launch_dct_pair_prep8_rows(hipStream_t st, int src_kind, const void* src, si
     const size_t rows = n_frames * h;
     const unsigned long long nblk = (unsigned long long)((rows + 31) / 32) * tiles_e;
     if (rows > 0xFFFFFFFFull || nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const bool iq = ip && qp;
-#define SSW_PREP8(SRCV, IQV) pair_prep8_rows_kernel<double, SRCV, IQV><<<(unsigned)nblk, 256, 0, st>>>( \
-        src, r1, r2, m, p, ip, qp, (unsigned)rows, (unsigned)w, K8, Kq, Kp, tiles_e)
-    if (src_kind == 0) SSW_PREP8(0, false);
-    else if (src_kind == 1) { if (iq) SSW_PREP8(1, true); else SSW_PREP8(1, false); }
-    else if (src_kind == 2) { if (iq) SSW_PREP8(2, true); else SSW_PREP8(2, false); }
-    else                    { if (iq) SSW_PREP8(3, true); else SSW_PREP8(3, false); }
-#undef SSW_PREP8
+    SSW_TRY(dispatch_row_src(in, [&](auto src, auto iq) {
+        pair_prep8_rows_kernel<decltype(src)::value, decltype(iq)::value><<<(unsigned)nblk, 256, 0, st>>>(
+            in.p, r1, r2, m, p, in.i, in.q, (unsigned)rows, (unsigned)w, K8, Kq, Kp, tiles_e);
+    }));
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
@@ -1213,20 +1100,20 @@ int launch_dct_pair_prep8_cols(hipStream_t st, const float* in, size_t n_frames,
     const unsigned tiles_e = (K8 + 31) / 32, tiles_c = (unsigned)((w + 31) / 32);
     const unsigned long long nblk = (unsigned long long)tiles_e * tiles_c * n_frames;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    pair_prep8_cols_kernel<double><<<(unsigned)nblk, 256, 0, st>>>(in, r1, r2, m, p, (unsigned)w, (unsigned)h, K8, Kq, Kp, (unsigned)n_frames, tiles_e, tiles_c);
+    pair_prep8_cols_kernel<<<(unsigned)nblk, 256, 0, st>>>(in, r1, r2, m, p, (unsigned)w, (unsigned)h, K8, Kq, Kp, (unsigned)n_frames, tiles_e, tiles_c);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
 
-// deep forward row pre-pass: src_kind 0 = f32 plane, 1 / 2 = interleaved RGB f32 / u8 (ip / qp: I, Q planes out or null);
+// deep forward row pre-pass of any RowInput;
 // base: 6 planes of lines * K8 doubles (AS BD AD BS R1 R2) followed by 4 planes of lines * K16 (AS2 BD2 AD2 BS2)
 // 6 planes K8 wide + 4 K16 wide, or (forward row passes at level 2) 16 planes K16 wide
 size_t dct_pair_deep_elems(size_t lines, size_t len) {
     const size_t k8 = dct_pair_split_kpad(len), k16 = dct_pair_split_kpad(len / 2);
     return lines * (6 * k8 + 4 * k16 > 16 * k16 ? 6 * k8 + 4 * k16 : 16 * k16);
 }
-int launch_dct_pair_prep16_rows(hipStream_t st, int src_kind, const void* src, size_t n_frames, size_t w, size_t h, double* base,
-                                const double* rot1, const double* rot2, const double* rot3, float* ip, float* qp, bool l2, bool unit_order) {
+int launch_dct_pair_prep16_rows(hipStream_t st, const RowInput& in, size_t n_frames, size_t w, size_t h, double* base,
+                                const double* rot1, const double* rot2, const double* rot3, bool l2, bool unit_order) {
     if (n_frames == 0) return SSW_OK;
     if (w > 0xFFFFFFull || h > 0xFFFFFFull || w % 64 != 0) return SSW_ERR_BAD_DIMS;
     const unsigned K8 = (unsigned)dct_pair_split_kpad(w), K16 = (unsigned)dct_pair_split_kpad(w / 2);
@@ -1246,15 +1133,11 @@ int launch_dct_pair_prep16_rows(hipStream_t st, int src_kind, const void* src, s
         if (!rot3) return SSW_ERR_BAD_ARG;
     }
     if (efold && dct_pair_prep_light_ok(w, rows))          // r5: the form that runs beside the GEMMs of the other lane (dct_pair_prep_light.hip)
-        return launch_dct_pair_prep16_rows_light(st, src_kind, src, dp, rot1, rot2, rot3, ip, qp, rows, w, K16, unit_order ? (unsigned)h : 0u, unit_hup);
-    const bool iq = ip && qp;
-#define SSW_PREP16(SRCV, IQV) pair_prep16_rows_kernel<double, SRCV, IQV><<<(unsigned)nblk, 256, 0, st>>>( \
-        src, dp, rot1, rot2, rot3, ip, qp, (unsigned)rows, (unsigned)w, K8, K16, tiles_e, efold, unit_order ? (unsigned)h : 0u, unit_hup)
-    if (src_kind == 0) SSW_PREP16(0, false);
-    else if (src_kind == 1) { if (iq) SSW_PREP16(1, true); else SSW_PREP16(1, false); }
-    else if (src_kind == 2) { if (iq) SSW_PREP16(2, true); else SSW_PREP16(2, false); }
-    else                    { if (iq) SSW_PREP16(3, true); else SSW_PREP16(3, false); }
-#undef SSW_PREP16
+        return launch_dct_pair_prep16_rows_light(st, in, dp, rot1, rot2, rot3, rows, w, K16, unit_order ? (unsigned)h : 0u, unit_hup);
+    SSW_TRY(dispatch_row_src(in, [&](auto src, auto iq) {
+        pair_prep16_rows_kernel<decltype(src)::value, decltype(iq)::value><<<(unsigned)nblk, 256, 0, st>>>(
+            in.p, dp, rot1, rot2, rot3, in.i, in.q, (unsigned)rows, (unsigned)w, K8, K16, tiles_e, efold, unit_order ? (unsigned)h : 0u, unit_hup);
+    }));
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
@@ -1281,8 +1164,8 @@ int launch_dct_pair_prep16_cols(hipStream_t st, const float* in, size_t n_frames
     const unsigned long long nblk = (unsigned long long)tiles_e * tiles_c * n_frames;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
     const DeepPlanes dp = planes_of(base, n_frames * w, K8, K16);          // semi: as2 = the SD plane, the others unused
-    if (semi) pair_prep16_cols_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, tiles_e, tiles_c, 0u, ctile, 0u);
-    else      pair_prep16_cols_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, tiles_e, tiles_c, cm, ctile, lay.rows_l2 ? 1u : 0u);
+    if (semi) pair_prep16_cols_kernel<false><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, tiles_e, tiles_c, 0u, ctile, 0u);
+    else      pair_prep16_cols_kernel<true><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, tiles_e, tiles_c, cm, ctile, lay.rows_l2 ? 1u : 0u);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
@@ -1303,7 +1186,7 @@ int launch_dct_pair_prep16_inv_rows(hipStream_t st, const float* in, size_t n_fr
     const unsigned lpb = 256 / tp;
     const unsigned long long nblk = (rows + lpb - 1) / lpb;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    pair_prep16_inv_rows_kernel<double><<<(unsigned)nblk, 256, 0, st>>>(in, planes_of(base, rows, dct_pair_split_kpad(w), dct_pair_split_kpad(w / 2)), rot1, rot2, (unsigned)rows, (unsigned)w,
+    pair_prep16_inv_rows_kernel<<<(unsigned)nblk, 256, 0, st>>>(in, planes_of(base, rows, dct_pair_split_kpad(w), dct_pair_split_kpad(w / 2)), rot1, rot2, (unsigned)rows, (unsigned)w,
                                                                        (unsigned)dct_pair_split_kpad(w), (unsigned)dct_pair_split_kpad(w / 2), tp);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
@@ -1325,8 +1208,8 @@ int launch_dct_pair_prep16_inv_cols(hipStream_t st, const float* in, size_t n_fr
     const unsigned long long nblk = (unsigned long long)groups * tiles_c * n_frames;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
     const DeepPlanes dp = planes_of(base, n_frames * w, K8, K16);          // semi: as2 = the c[4q+2] plane, the others unused
-    if (semi) pair_prep16_inv_cols_kernel<double, false><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, groups, tiles_c, 0u, (unsigned)w);
-    else      pair_prep16_inv_cols_kernel<double, true><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, groups, tiles_c, class_major ? (lay.rows_l2 ? 2u : 1u) : 0u, lay.tile);
+    if (semi) pair_prep16_inv_cols_kernel<false><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, groups, tiles_c, 0u, (unsigned)w);
+    else      pair_prep16_inv_cols_kernel<true><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, groups, tiles_c, class_major ? (lay.rows_l2 ? 2u : 1u) : 0u, lay.tile);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }

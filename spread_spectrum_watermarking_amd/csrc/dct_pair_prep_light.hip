@@ -22,7 +22,7 @@ namespace {
 
 constexpr int LIGHT_PITCH = 16 * 32 + 8;         // floats per line in LDS: sixteen runs of 32 pixels (+ 8: lines on different banks)
 
-template <int SRC /*0 plane, 1 rgb f32, 2 rgb u8, 3 rgb u16*/, bool WITH_IQ, int LINES>
+template <RowSrc SRC, bool WITH_IQ, int LINES>
 __global__ __launch_bounds__(16 * LINES, 8) void pair_prep16_rows_light_kernel(
     const void* __restrict__ SRCP, DeepPlanes dp, const double* __restrict__ rot1, const double* __restrict__ rot2,
     const double* __restrict__ rot3, float* __restrict__ IP, float* __restrict__ QP, unsigned rows, unsigned W, unsigned K16,
@@ -33,23 +33,14 @@ __global__ __launch_bounds__(16 * LINES, 8) void pair_prep16_rows_light_kernel(
     const unsigned N8 = W / 8, N16 = W / 16;
     const unsigned e0 = (blockIdx.x % tiles_e) * 32, line0 = (blockIdx.x / tiles_e) * LINES;
     const unsigned tid = threadIdx.x;
-    // image row of an operand line (natural order: the same number; fused forward transform: lines ordered by unit of the
-    // column fold, see pair_prep16_rows_kernel); pad lines hold zeros
-    auto row_of = [&](unsigned line, bool& pad) -> unsigned {
-        pad = false;
-        if (!unit_h) return line;
-        const unsigned lpf = 16 * unit_hup, z = line / lpf, rem = line - z * lpf;
-        pad = (rem >> 4) >= unit_h / 16;
-        return z * unit_h + (pad ? 0u : col_unit_row(rem >> 4, rem & 15u, unit_h));
-    };
     // ---- phase 1: LINES x 16 runs x 8 quads of pixels -> Y in LDS
 #pragma unroll 2
     for (int i = 0; i < 8; ++i) {
         const unsigned t = tid + NT * i;
         const unsigned q = t & 7u, u = (t >> 3) & 15u, ll = t >> 7;
         const unsigned line = line0 + ll;
-        bool pad;
-        const unsigned row = row_of(line, pad);
+        bool pad;                                                   // image row of the operand line; pad lines hold zeros
+        const unsigned row = fused_line_row(line, unit_h, unit_hup, pad);
         // run u of unit e: pixel (u/2) N8 + e (u even) or (u/2 + 1) N8 - 1 - e (u odd) for u < 8, its mirror W - 1 - p for
         // 15 - u; over e0 .. e0 + 31 an ascending (u even) or descending (u odd) run of 32 pixels, quad q of it:
         const unsigned v = u < 8 ? u : 15 - u, hv = v >> 1;
@@ -60,19 +51,7 @@ __global__ __launch_bounds__(16 * LINES, 8) void pair_prep16_rows_light_kernel(
         // the quad's units: e0 + 4q .. (ascending) or e0 + 28 - 4q .. (descending); beyond N16 there is nothing to read
         const unsigned efirst = asc ? e0 + 4 * q : e0 + 28 - 4 * q;
         if (line >= rows || pad || efirst >= N16) continue;
-        f32x4 y, iv, qv;
-        if (SRC == 0) {
-            y = *reinterpret_cast<const f32x4*>(static_cast<const float*>(SRCP) + (size_t)row * W + px);
-        } else {
-            const void* base = SRC == 3 ? static_cast<const void*>(static_cast<const uint16_t*>(SRCP) + (size_t)row * W * 3)
-                             : SRC == 2 ? static_cast<const void*>(static_cast<const uint8_t*>(SRCP) + (size_t)row * W * 3)
-                                        : static_cast<const void*>(static_cast<const float*>(SRCP) + (size_t)row * W * 3);
-            load_yiq4<SRC - 1, WITH_IQ>(base, px, y, iv, qv);
-            if (WITH_IQ) {
-                *reinterpret_cast<f32x4*>(IP + (size_t)row * W + px) = iv;
-                *reinterpret_cast<f32x4*>(QP + (size_t)row * W + px) = qv;
-            }
-        }
+        const f32x4 y = load_row_y4<SRC, WITH_IQ>(SRCP, IP, QP, row, W, px);
         *reinterpret_cast<f32x4*>(ys + ll * LIGHT_PITCH + u * 32 + 4 * q) = y;
     }
     __syncthreads();
@@ -83,7 +62,7 @@ __global__ __launch_bounds__(16 * LINES, 8) void pair_prep16_rows_light_kernel(
     const unsigned line = line0 + ll;
     if (line >= rows) return;
     bool pad;
-    (void)row_of(line, pad);
+    (void)fused_line_row(line, unit_h, unit_hup, pad);
     const float* yl = ys + ll * LIGHT_PITCH;
 #pragma unroll 1
     for (int j = 0; j < 2; ++j) {
@@ -139,21 +118,16 @@ bool dct_pair_prep_light_ok(size_t w, size_t lines) {
     return tuning(TUNE_PREP_LIGHT) != 0 && w % 64 == 0 && lines * dct_pair_split_kpad(w / 2) * sizeof(double) <= 0xFFFFFFFFull;
 }
 
-int launch_dct_pair_prep16_rows_light(hipStream_t st, int src_kind, const void* src, const DeepPlanes& dp, const double* rot1,
-                                      const double* rot2, const double* rot3, float* ip, float* qp, size_t rows, size_t w, unsigned K16,
-                                      unsigned unit_h, unsigned unit_hup) {
+int launch_dct_pair_prep16_rows_light(hipStream_t st, const RowInput& in, const DeepPlanes& dp, const double* rot1, const double* rot2,
+                                      const double* rot3, size_t rows, size_t w, unsigned K16, unsigned unit_h, unsigned unit_hup) {
     constexpr int LINES = 8;                                        // operand lines per tile
     const unsigned tiles_e = (K16 + 31) / 32;
     const unsigned long long nblk = (unsigned long long)((rows + LINES - 1) / LINES) * tiles_e;
     if (rows > 0xFFFFFFFFull || nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const bool iq = ip && qp;
-#define SSW_LIGHT(SRCV, IQV) pair_prep16_rows_light_kernel<SRCV, IQV, LINES><<<(unsigned)nblk, 16 * LINES, LINES * LIGHT_PITCH * sizeof(float), st>>>( \
-        src, dp, rot1, rot2, rot3, ip, qp, (unsigned)rows, (unsigned)w, K16, tiles_e, unit_h, unit_hup)
-    if (src_kind == 0) SSW_LIGHT(0, false);
-    else if (src_kind == 1) { if (iq) SSW_LIGHT(1, true); else SSW_LIGHT(1, false); }
-    else if (src_kind == 2) { if (iq) SSW_LIGHT(2, true); else SSW_LIGHT(2, false); }
-    else                    { if (iq) SSW_LIGHT(3, true); else SSW_LIGHT(3, false); }
-#undef SSW_LIGHT
+    SSW_TRY(dispatch_row_src(in, [&](auto src, auto iq) {
+        pair_prep16_rows_light_kernel<decltype(src)::value, decltype(iq)::value, LINES><<<(unsigned)nblk, 16 * LINES, LINES * LIGHT_PITCH * sizeof(float), st>>>(
+            in.p, dp, rot1, rot2, rot3, in.i, in.q, (unsigned)rows, (unsigned)w, K16, tiles_e, unit_h, unit_hup);
+    }));
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }

@@ -644,7 +644,7 @@ __global__ __launch_bounds__(256) void prep16_inv_rows_staged_kernel(const float
         f64x4 as[2], bd[2], ad[2], bs[2];
 #pragma unroll
         for (int half = 0; half < 2; ++half)
-            split_unit<double>(odd(0, half), odd(1, 1 - half), odd(2, half), odd(3, 1 - half), rot1, R / 2 + 4 * half, Nq, as[half], bd[half], ad[half], bs[half]);
+            split_unit(odd(0, half), odd(1, 1 - half), odd(2, half), odd(3, 1 - half), rot1, R / 2 + 4 * half, Nq, as[half], bd[half], ad[half], bs[half]);
 #pragma unroll
         for (int rnd = 0; rnd < 2; ++rnd) {
             if (tid < 16) {
@@ -671,7 +671,7 @@ __global__ __launch_bounds__(256) void prep16_inv_rows_staged_kernel(const float
             s_mask[tid] = (v0 ? 0x3u : 0u) | (v1 ? 0xCu : 0u);
         }
         f64x4 as, bd, ad, bs;
-        split_unit<double>(mid(0), mid(1), mid(2), mid(3), rot2, R / 4, N8, as, bd, ad, bs);
+        split_unit(mid(0), mid(1), mid(2), mid(3), rot2, R / 4, N8, as, bd, ad, bs);
         const unsigned at = 4 * (t & 1u), sl = t >> 1;
         put4(sl, at, as); put4(4 + sl, at, bd); put4(8 + sl, at, ad); put4(12 + sl, at, bs);
         flush(16);
@@ -792,7 +792,7 @@ __global__ __launch_bounds__(256) void prep16_inv_rows_l2_kernel(const float* __
         f64x4 as[2], bd[2], ad[2], bs[2];
 #pragma unroll
         for (int half = 0; half < 2; ++half)
-            split_unit<double>(odd(0, half), odd(1, 1 - half), odd(2, half), odd(3, 1 - half), rot1, R / 2 + 4 * half, Nq, as[half], bd[half], ad[half], bs[half]);
+            split_unit(odd(0, half), odd(1, 1 - half), odd(2, half), odd(3, 1 - half), rot1, R / 2 + 4 * half, Nq, as[half], bd[half], ad[half], bs[half]);
 #pragma unroll
         for (int rnd = 0; rnd < 2; ++rnd) {
 #pragma unroll
@@ -843,7 +843,7 @@ __global__ __launch_bounds__(256) void prep16_inv_rows_l2_kernel(const float* __
             s_mask[tid] = 0xFu;
         }
         f64x4 as, bd, ad, bs;
-        split_unit<double>(mid(0), mid(1), mid(2), mid(3), rot2, R / 4, N8, as, bd, ad, bs);
+        split_unit(mid(0), mid(1), mid(2), mid(3), rot2, R / 4, N8, as, bd, ad, bs);
         const unsigned at = 4 * (t & 1u), sl = t >> 1;
         put4(sl, at, as); put4(4 + sl, at, bd); put4(8 + sl, at, ad); put4(12 + sl, at, bs);
         flush(16);

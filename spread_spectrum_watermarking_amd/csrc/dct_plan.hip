@@ -154,8 +154,8 @@ bool dct_pair_can_run(size_t n_frames, size_t w, size_t h, bool aligned) {
            dct_pair_operand_elems(n_frames, w, h) * sizeof(double) <= 0xFFFFFFFFull;
 }
 
-bool dct_pair_can_prep_from_rgb(size_t w, size_t h, const void* rgb, int u8) {
-    return w >= h && can_fold2(w) && (reinterpret_cast<uintptr_t>(rgb) & pix_align_mask(u8)) == 0;
+bool dct_pair_can_prep_from_rgb(size_t w, size_t h, const void* rgb, PixFmt fmt) {
+    return w >= h && can_fold2(w) && (reinterpret_cast<uintptr_t>(rgb) & pix_align_mask(fmt)) == 0;
 }
 
 size_t plan_frame_limit(const PlanSettings& s, bool f64, size_t w, size_t h) {

@@ -53,7 +53,6 @@ bool plan_merge(size_t lines);                               // the merge rule (
 bool plan_derived_fused(const PassPlan& rows, size_t lines); // the pruned derived pass in one kernel (derived_fused)
 // the (f64) pair path fits the shape: folding shapes, aligned planes, operand planes below 4 GB
 bool dct_pair_can_run(size_t n_frames, size_t w, size_t h, bool aligned);
-bool dct_pair_can_prep_from_rgb(size_t w, size_t h, const void* rgb, int u8);       // a rows-first RGB pre-pass reads these frames
 size_t plan_frame_limit(const PlanSettings& s, bool f64, size_t w, size_t h);      // frames per group (f64: 32-bit operand offsets)
 // doubles of a lane's sixth operand buffer: what the passes of both directions of this shape use (they share the lane)
 size_t split_scratch_elems(size_t n, size_t w, size_t h);

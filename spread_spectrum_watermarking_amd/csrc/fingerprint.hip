@@ -401,7 +401,7 @@ int fingerprint_copies(ssw_ctx* ctx, const ssw_config& c, const float* coef, con
 }
 
 // ssw_fingerprint_embed(_rgb8): Writer::new on the device frame (forward transform, selection), then the copies
-int fingerprint_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_rgb, int u8_in, size_t w, size_t h,
+int fingerprint_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_rgb, PixFmt fmt_in, size_t w, size_t h,
                            const float* dev_marks, size_t n_copies, size_t k, void* dev_rgb_out, bool u8_out, uint32_t* dev_indices_out) {
     if (!ctx || !dev_rgb || !dev_marks || !dev_rgb_out) return SSW_ERR_BAD_ARG;
     SSW_TRY(check_config(cfg));
@@ -420,7 +420,7 @@ int fingerprint_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_
     float* tmp = (float*)ws.plane[3].p;
     uint32_t* idx = dev_indices_out ? dev_indices_out : (uint32_t*)ws.idx.p;
     Chain ch;
-    SSW_TRY(build_forward_from_rgb(ctx, ws, cfg->precision, dev_rgb, u8_in, 1, w, h, y, pi, pq, tmp, ch));   // Writer::new :308-313
+    SSW_TRY(build_forward_from_rgb(ctx, ws, cfg->precision, dev_rgb, fmt_in, 1, w, h, y, pi, pq, tmp, ch));   // Writer::new :308-313
     SSW_TRY(run_serial(ch, ctx->stream));
     if (k_eff) SSW_TRY(topk(ctx, ctx->stream, ws.sel, y, 1, w, h, cfg->ordering, k_eff, idx));              // :314 (first k only)
     return fingerprint_copies(ctx, *cfg, y, idx, k_eff, pi, pq, w, h, dev_marks, k, n_copies, dev_rgb_out, u8_out, tmp);
@@ -431,11 +431,11 @@ int fingerprint_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_
 
 int ssw_fingerprint_embed(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_rgb, size_t w, size_t h, const float* dev_marks,
                           size_t n_copies, size_t k, float* dev_rgb_out, uint32_t* dev_indices_out) {
-    return ssw::host::fingerprint_embed_impl(ctx, cfg, dev_rgb, ssw::SSW_PIX_F32, w, h, dev_marks, n_copies, k, dev_rgb_out, false,
+    return ssw::host::fingerprint_embed_impl(ctx, cfg, dev_rgb, ssw::PixFmt::F32, w, h, dev_marks, n_copies, k, dev_rgb_out, false,
                                              dev_indices_out);
 }
 int ssw_fingerprint_embed_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* dev_rgb, size_t w, size_t h, const float* dev_marks,
                                size_t n_copies, size_t k, uint8_t* dev_rgb_out, uint32_t* dev_indices_out) {
-    return ssw::host::fingerprint_embed_impl(ctx, cfg, dev_rgb, ssw::SSW_PIX_U8, w, h, dev_marks, n_copies, k, dev_rgb_out, true,
+    return ssw::host::fingerprint_embed_impl(ctx, cfg, dev_rgb, ssw::PixFmt::U8, w, h, dev_marks, n_copies, k, dev_rgb_out, true,
                                              dev_indices_out);
 }

@@ -75,23 +75,28 @@ int launch_make_half_basis_blocked(hipStream_t st, size_t n, bool inverse, int p
 // one level: (S, D) forward / (E, O) inverse
 int launch_dct_pair_prep(hipStream_t st, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w, size_t h,
                          double* o1, double* o2);
-// two levels: (SS, SD | EE, EO) [kpad(len/2) wide] and (D | O) [kpad(len) wide] in one sweep
-int launch_dct_pair_prep4(hipStream_t st, bool is_row, bool inverse, const float* in, size_t n_frames, size_t w, size_t h,
+// Sample format of an interleaved RGB frame at the boundary: what `into_rgb32f()` accepts (src/algorithm.rs:308, :476):
+// f32 as it is, 8-bit v / 255, 16-bit v / 65535
+enum class PixFmt { F32, U8, U16 };
+constexpr size_t pix_bytes(PixFmt f) { return f == PixFmt::U8 ? 1 : f == PixFmt::U16 ? 2 : 4; }                 // per sample
+constexpr unsigned pix_align_mask(PixFmt f) { return f == PixFmt::U8 ? 3u : f == PixFmt::U16 ? 7u : 15u; }     // of a 4-pixel load
+bool dct_pair_can_prep_from_rgb(size_t w, size_t h, const void* rgb, PixFmt fmt);       // dct_plan.hip: a rows-first RGB pre-pass reads these frames
+// What a forward row pre-pass reads: an f32 plane, or the interleaved RGB frame itself (Y formed on the fly)
+enum class RowSrc { Plane, RgbF32, RgbU8, RgbU16 };
+constexpr RowSrc row_src(PixFmt f) { return f == PixFmt::U8 ? RowSrc::RgbU8 : f == PixFmt::U16 ? RowSrc::RgbU16 : RowSrc::RgbF32; }
+constexpr PixFmt pix_fmt(RowSrc s) { return s == RowSrc::RgbU8 ? PixFmt::U8 : s == RowSrc::RgbU16 ? PixFmt::U16 : PixFmt::F32; }   // of an RGB source
+// ... and what it writes besides its operand planes: the I and Q planes (both or neither; RGB sources only -- the writer's)
+struct RowInput {
+    RowSrc kind; const void* p; float *i, *q;
+    static RowInput plane(const float* y) { return {RowSrc::Plane, y, nullptr, nullptr}; }
+    static RowInput rgb(PixFmt f, const void* frames, float* i = nullptr, float* q = nullptr) { return {row_src(f), frames, i, q}; }
+};
+// two levels: (SS, SD | EE, EO) [kpad(len/2) wide] and (D | O) [kpad(len) wide] in one sweep; column and inverse passes read a plane
+int launch_dct_pair_prep4(hipStream_t st, bool is_row, bool inverse, const RowInput& in, size_t n_frames, size_t w, size_t h,
                           double* q1, double* q2, double* p);
-// first pass of a rows-first forward transform straight from interleaved RGB (u8 or f32), two levels;
-// ip / qp: I and Q planes out (both or neither)
-// Sample format of an interleaved RGB frame at the boundary (`u8` parameters below): what `into_rgb32f()` accepts
-// (src/algorithm.rs:308, :476): f32 as it is, 8-bit v / 255, 16-bit v / 65535
-enum { SSW_PIX_F32 = 0, SSW_PIX_U8 = 1, SSW_PIX_U16 = 2 };
-inline size_t pix_bytes(int fmt) { return fmt == SSW_PIX_U8 ? 1 : fmt == SSW_PIX_U16 ? 2 : 4; }          // per sample
-inline unsigned pix_align_mask(int fmt) { return fmt == SSW_PIX_U8 ? 3u : fmt == SSW_PIX_U16 ? 7u : 15u; }   // of a 4-pixel load
-inline int pix_src_kind(int fmt) { return fmt + 1; }                     // SRC of the row pre-passes: 1 f32, 2 u8, 3 u16
-int launch_dct_pair_prep4_rows_rgb(hipStream_t st, int u8, const void* rgb, size_t n_frames, size_t w, size_t h,
-                                   double* q1, double* q2, double* p, float* ip, float* qp);
-// three levels on a forward row pass: (SSS, SS-) [kpad(w/4) wide], S- [kpad(w/2)], x- [kpad(w)] from an f32
-// plane (src_kind 0) or interleaved RGB f32 / u8 (1 / 2; ip / qp: I, Q planes out or null)
-int launch_dct_pair_prep8_rows(hipStream_t st, int src_kind, const void* src, size_t n_frames, size_t w, size_t h,
-                               double* r1, double* r2, double* m, double* p, float* ip, float* qp);
+// three levels on a forward row pass: (SSS, SS-) [kpad(w/4) wide], S- [kpad(w/2)], x- [kpad(w)]
+int launch_dct_pair_prep8_rows(hipStream_t st, const RowInput& in, size_t n_frames, size_t w, size_t h,
+                               double* r1, double* r2, double* m, double* p);
 // Writer::result fused into the last inverse pass (EPI_INV_O_RGB): the frames' I / Q planes and the RGB output
 struct RgbSink {
     const float* iq_i = nullptr;
@@ -160,7 +165,7 @@ int launch_make_split_basis_blocked(hipStream_t st, size_t n, bool inverse, int 
 int launch_make_rot_table(hipStream_t st, size_t n, double* out);
 int launch_dct_pair_rotate(hipStream_t st, const double* p, const double* rot, double* sp, size_t lines, size_t len);
 // deep forward row pre-pass (len % 64 == 0): D and SD split, SS folded a third time, in one sweep over the source
-// (f32 plane or interleaved RGB); base: AS BD AD BS R1 R2 (lines * split_kpad(len) each), AS2 BD2 AD2 BS2 (lines * split_kpad(len/2))
+// (a RowInput); base: AS BD AD BS R1 R2 (lines * split_kpad(len) each), AS2 BD2 AD2 BS2 (lines * split_kpad(len/2))
 size_t dct_pair_semi_deep_elems(size_t lines, size_t len);
 // deep inverse pre-passes (coefficient plane -> the same ten planes; R1 = c[8q], R2 = c[8q+4]); `prep` / `lay`: of the plan
 int launch_dct_pair_prep16_inv_rows(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
@@ -171,8 +176,8 @@ int launch_dct_pair_prep16_cols(hipStream_t st, const float* in, size_t n_frames
                                 const double* rot1, const double* rot2, const double* rot3, PrepFamily prep, const PairLayout& lay);
 size_t dct_pair_deep_elems(size_t lines, size_t len);
 // l2: the row pass runs at level 2 (sixteen planes K16 wide); unit_order: the fused transform's line order (needs l2)
-int launch_dct_pair_prep16_rows(hipStream_t st, int src_kind, const void* src, size_t n_frames, size_t w, size_t h, double* base,
-                                const double* rot1, const double* rot2, const double* rot3, float* ip, float* qp, bool l2, bool unit_order = false);
+int launch_dct_pair_prep16_rows(hipStream_t st, const RowInput& in, size_t n_frames, size_t w, size_t h, double* base,
+                                const double* rot1, const double* rot2, const double* rot3, bool l2, bool unit_order = false);
 // r5, fused forward transform: units per frame of the row pass's line order (H/16 rounded up to whole k-blocks of 8)
 inline size_t dct_pair_fused_units(size_t h) { return ((h / 16 + 7) / 8) * 8; }
 

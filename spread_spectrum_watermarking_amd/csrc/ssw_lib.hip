@@ -49,7 +49,7 @@ struct ssw_reader {
     // frequency columns those need (the pruned transform of the batch path, bit-identical values); fully when
     // coefficients() is called or the pruned path does not apply.
     void* rgb = nullptr;
-    int rgb_u8 = 0;                 // SSW_PIX_* of `rgb`
+    PixFmt rgb_fmt = PixFmt::F32;   // sample format of `rgb`
     hipEvent_t rgb_uploaded = nullptr;
 };
 
@@ -144,10 +144,10 @@ int stage_consumed(ssw_ctx* ctx, ssw_ctx::FrameStage& fs) {
 
 // Writer::new / Reader::new_impl up to the coefficients (:308-313, :476-480): host frame (f32 or 8-bit) -> Y
 // (+ I, Q) -> forward transform, through the same fused chain as the batch entry points (n = 1).  Enqueues only.
-int forward_from_host(ssw_ctx* ctx, const void* host_rgb, int u8, size_t w, size_t h, int precision, float* y, float* i,
+int forward_from_host(ssw_ctx* ctx, const void* host_rgb, PixFmt fmt, size_t w, size_t h, int precision, float* y, float* i,
                       float* q) {
     const size_t plane = w * h;
-    const size_t bytes = plane * 3 * pix_bytes(u8);
+    const size_t bytes = plane * 3 * pix_bytes(fmt);
     SSW_TRY(grow(ctx->lane[0].plane[3], plane * sizeof(float)));
     float* tmp = (float*)ctx->lane[0].plane[3].p;
     {
@@ -161,9 +161,9 @@ int forward_from_host(ssw_ctx* ctx, const void* host_rgb, int u8, size_t w, size
         const bool no_split = tuning(TUNE_BAND_SPLIT) == 0;                     // A/B switch (tuning.hip)
         long long nb = tuning(TUNE_UPLOAD_BANDS);
         nb = nb < 2 ? 2 : nb > ssw_ctx::FrameStage::MAX_BANDS ? ssw_ctx::FrameStage::MAX_BANDS : nb;
-        while (nb > 2 && ((bytes / nb) % 16 != 0 || !can_split_forward_rows(ctx, precision == SSW_PRECISION_F64, w, h, (size_t)nb, y, tmp, fs.buf.p, u8))) --nb;
+        while (nb > 2 && ((bytes / nb) % 16 != 0 || !can_split_forward_rows(ctx, precision == SSW_PRECISION_F64, w, h, (size_t)nb, y, tmp, fs.buf.p, fmt))) --nb;
         if (!no_split && bytes >= ((size_t)8 << 20) &&
-            can_split_forward_rows(ctx, precision == SSW_PRECISION_F64, w, h, (size_t)nb, y, tmp, fs.buf.p, u8)) {
+            can_split_forward_rows(ctx, precision == SSW_PRECISION_F64, w, h, (size_t)nb, y, tmp, fs.buf.p, fmt)) {
             ++ctx->frame_stage_next;
             SSW_TRY(frame_stage_events(fs));
             if (fs.in_use) SSW_HIP_CHECK(hipStreamWaitEvent(ctx->copy_stream, fs.consumed, 0));
@@ -179,7 +179,7 @@ int forward_from_host(ssw_ctx* ctx, const void* host_rgb, int u8, size_t w, size
                 untimed_work(ctx);                  // the band's first stage starts its timer behind the wait for its upload
                 if (rc != SSW_OK) break;
                 Chain ch;
-                rc = build_forward_rows_band(ctx, ctx->lane[0], precision, (char*)fs.buf.p + band * hb, u8, w, rows, h, tmp + band * hp,
+                rc = build_forward_rows_band(ctx, ctx->lane[0], precision, (char*)fs.buf.p + band * hb, fmt, w, rows, h, tmp + band * hp,
                                              i ? i + band * hp : nullptr, q ? q + band * hp : nullptr, ch);
                 if (rc == SSW_OK) rc = run_serial(ch, ctx->stream);
             }
@@ -197,7 +197,7 @@ int forward_from_host(ssw_ctx* ctx, const void* host_rgb, int u8, size_t w, size
     ssw_ctx::FrameStage* fs = nullptr;
     SSW_TRY(stage_frame_in(ctx, host_rgb, bytes, &fs));
     Chain ch;
-    SSW_TRY(build_forward_from_rgb(ctx, ctx->lane[0], precision, fs->buf.p, u8, 1, w, h, y, i, q, tmp, ch));
+    SSW_TRY(build_forward_from_rgb(ctx, ctx->lane[0], precision, fs->buf.p, fmt, 1, w, h, y, i, q, tmp, ch));
     SSW_TRY(run_serial(ch, ctx->stream));
     return stage_consumed(ctx, *fs);
 }
@@ -245,7 +245,7 @@ int trace_score(ssw_ctx* ctx, const float* dev_extracted, size_t n_suspects, con
 }  // namespace ssw
 
 namespace {
-int fingerprint_trace_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base_rgb, const void* dev_suspect_rgb, int u8,
+int fingerprint_trace_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base_rgb, const void* dev_suspect_rgb, PixFmt fmt,
                            size_t n_suspects, size_t w, size_t h, size_t k, const float* dev_marks, size_t n_marks, float threshold,
                            float* dev_extracted, float* dev_sims, uint32_t* dev_best, float* dev_best_sim, uint32_t* dev_n_exceed) {
     if (!ctx || !dev_base_rgb || !dev_suspect_rgb || !dev_extracted) return SSW_ERR_BAD_ARG;
@@ -254,8 +254,8 @@ int fingerprint_trace_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_
     CtxGuard g(ctx);
     const float* yb = nullptr;
     const uint32_t* idx = nullptr;
-    SSW_TRY(trace_base(ctx, *cfg, dev_base_rgb, u8, w, h, k, &yb, &idx));
-    SSW_TRY(trace_extract(ctx, *cfg, yb, idx, dev_suspect_rgb, u8, n_suspects, w, h, k, dev_extracted));
+    SSW_TRY(trace_base(ctx, *cfg, dev_base_rgb, fmt, w, h, k, &yb, &idx));
+    SSW_TRY(trace_extract(ctx, *cfg, yb, idx, dev_suspect_rgb, fmt, n_suspects, w, h, k, dev_extracted));
     return trace_score(ctx, dev_extracted, n_suspects, dev_marks, n_marks, k, threshold, dev_sims, dev_best, dev_best_sim, dev_n_exceed);
 }
 }  // namespace
@@ -780,26 +780,26 @@ extern "C" {
 int ssw_batch_embed(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_rgb, size_t n_frames,
                     size_t w, size_t h, const float* dev_marks, size_t k, float* dev_rgb_out,
                     float* dev_coef_out, uint32_t* dev_indices_out) {
-    return batch_embed_impl(ctx, cfg, dev_rgb, false, n_frames, w, h, dev_marks, k, dev_rgb_out, false,
+    return batch_embed_impl(ctx, cfg, dev_rgb, PixFmt::F32, n_frames, w, h, dev_marks, k, dev_rgb_out, false,
                             dev_coef_out, dev_indices_out);
 }
 
 int ssw_batch_extract(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_base_rgb,
                       const float* dev_derived_rgb, size_t n_frames, size_t w, size_t h, size_t k,
                       float* dev_extracted, const float* dev_marks, float* dev_sims) {
-    return batch_extract_impl(ctx, cfg, dev_base_rgb, dev_derived_rgb, false, n_frames, w, h, k, dev_extracted,
+    return batch_extract_impl(ctx, cfg, dev_base_rgb, dev_derived_rgb, PixFmt::F32, n_frames, w, h, k, dev_extracted,
                               dev_marks, dev_sims);
 }
 
 int ssw_batch_embed_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* dev_rgb, size_t n_frames,
                          size_t w, size_t h, const float* dev_marks, size_t k, uint8_t* dev_rgb_out) {
-    return batch_embed_impl(ctx, cfg, dev_rgb, SSW_PIX_U8, n_frames, w, h, dev_marks, k, dev_rgb_out, true, nullptr, nullptr);
+    return batch_embed_impl(ctx, cfg, dev_rgb, PixFmt::U8, n_frames, w, h, dev_marks, k, dev_rgb_out, true, nullptr, nullptr);
 }
 
 int ssw_batch_extract_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* dev_base_rgb,
                            const uint8_t* dev_derived_rgb, size_t n_frames, size_t w, size_t h, size_t k,
                            float* dev_extracted, const float* dev_marks, float* dev_sims) {
-    return batch_extract_impl(ctx, cfg, dev_base_rgb, dev_derived_rgb, SSW_PIX_U8, n_frames, w, h, k, dev_extracted,
+    return batch_extract_impl(ctx, cfg, dev_base_rgb, dev_derived_rgb, PixFmt::U8, n_frames, w, h, k, dev_extracted,
                               dev_marks, dev_sims);
 }
 
@@ -808,7 +808,7 @@ int ssw_fingerprint_trace(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_
                           size_t n_suspects, size_t w, size_t h, size_t k, const float* dev_marks, size_t n_marks,
                           float threshold, float* dev_extracted, float* dev_sims, uint32_t* dev_best, float* dev_best_sim,
                           uint32_t* dev_n_exceed) {
-    return fingerprint_trace_impl(ctx, cfg, dev_base_rgb, dev_suspect_rgb, SSW_PIX_F32, n_suspects, w, h, k, dev_marks, n_marks, threshold,
+    return fingerprint_trace_impl(ctx, cfg, dev_base_rgb, dev_suspect_rgb, PixFmt::F32, n_suspects, w, h, k, dev_marks, n_marks, threshold,
                                   dev_extracted, dev_sims, dev_best, dev_best_sim, dev_n_exceed);
 }
 
@@ -816,7 +816,7 @@ int ssw_fingerprint_trace_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_
                                size_t n_suspects, size_t w, size_t h, size_t k, const float* dev_marks, size_t n_marks,
                                float threshold, float* dev_extracted, float* dev_sims, uint32_t* dev_best,
                                float* dev_best_sim, uint32_t* dev_n_exceed) {
-    return fingerprint_trace_impl(ctx, cfg, dev_base_rgb, dev_suspect_rgb, SSW_PIX_U8, n_suspects, w, h, k, dev_marks, n_marks, threshold,
+    return fingerprint_trace_impl(ctx, cfg, dev_base_rgb, dev_suspect_rgb, PixFmt::U8, n_suspects, w, h, k, dev_marks, n_marks, threshold,
                                   dev_extracted, dev_sims, dev_best, dev_best_sim, dev_n_exceed);
 }
 
@@ -833,7 +833,7 @@ int ssw_fingerprint_trace_host_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const u
     SSW_TRY(stage_frame_in(ctx, host_base, w * h * 3, &fs));
     const float* yb = nullptr;
     const uint32_t* idx = nullptr;
-    SSW_TRY(trace_base(ctx, *cfg, fs->buf.p, SSW_PIX_U8, w, h, k, &yb, &idx));
+    SSW_TRY(trace_base(ctx, *cfg, fs->buf.p, PixFmt::U8, w, h, k, &yb, &idx));
     SSW_TRY(stage_consumed(ctx, *fs));
     return stream_trace_rgb8(ctx, *cfg, yb, idx, host_suspects, n_suspects, w, h, k, host_marks, n_marks, threshold, host_extracted,
                              host_sims, host_best, host_best_sim, host_n_exceed);
@@ -857,7 +857,7 @@ int ssw_fingerprint_trace_restored_host_rgb8(ssw_ctx* ctx, const ssw_config* cfg
     SSW_TRY(upload(ctx, ctx->restore_base.p, host_base, w * h * 3, ctx->stream));
     const float* yb = nullptr;
     const uint32_t* idx = nullptr;
-    SSW_TRY(trace_base(ctx, *cfg, ctx->restore_base.p, SSW_PIX_U8, w, h, k, &yb, &idx));
+    SSW_TRY(trace_base(ctx, *cfg, ctx->restore_base.p, PixFmt::U8, w, h, k, &yb, &idx));
     return stream_trace_rgb8(ctx, *cfg, yb, idx, host_suspects, n_suspects, w, h, k, host_marks, n_marks, threshold, host_extracted,
                              host_sims, host_best, host_best_sim, host_n_exceed, pl.data(), (const uint8_t*)ctx->restore_base.p);
 }
@@ -866,13 +866,13 @@ int ssw_fingerprint_trace_restored_host_rgb8(ssw_ctx* ctx, const ssw_config* cfg
 // pre-pass like the 8-bit form; Writer::mark returns Rgb32F, src/algorithm.rs:355-379, so the marked frames leave as f32) ----
 int ssw_batch_embed_rgb16(ssw_ctx* ctx, const ssw_config* cfg, const uint16_t* dev_rgb, size_t n_frames,
                           size_t w, size_t h, const float* dev_marks, size_t k, float* dev_rgb_out) {
-    return batch_embed_impl(ctx, cfg, dev_rgb, SSW_PIX_U16, n_frames, w, h, dev_marks, k, dev_rgb_out, false, nullptr, nullptr);
+    return batch_embed_impl(ctx, cfg, dev_rgb, PixFmt::U16, n_frames, w, h, dev_marks, k, dev_rgb_out, false, nullptr, nullptr);
 }
 
 int ssw_batch_extract_rgb16(ssw_ctx* ctx, const ssw_config* cfg, const uint16_t* dev_base_rgb,
                             const uint16_t* dev_derived_rgb, size_t n_frames, size_t w, size_t h, size_t k,
                             float* dev_extracted, const float* dev_marks, float* dev_sims) {
-    return batch_extract_impl(ctx, cfg, dev_base_rgb, dev_derived_rgb, SSW_PIX_U16, n_frames, w, h, k, dev_extracted,
+    return batch_extract_impl(ctx, cfg, dev_base_rgb, dev_derived_rgb, PixFmt::U16, n_frames, w, h, k, dev_extracted,
                               dev_marks, dev_sims);
 }
 
@@ -930,7 +930,7 @@ int ssw_resize_rgb8(ssw_ctx* ctx, const uint8_t* dev_in, size_t n_frames, size_t
 }
 
 // ---- Writer ---------------------------------------------------------------------------------
-static int writer_create_impl(ssw_ctx* ctx, const void* rgb_hwc, int u8, size_t w, size_t h, const ssw_config* cfg,
+static int writer_create_impl(ssw_ctx* ctx, const void* rgb_hwc, PixFmt fmt, size_t w, size_t h, const ssw_config* cfg,
                               ssw_writer** out) {
     if (!ctx || !rgb_hwc || !out) return SSW_ERR_BAD_ARG;
     *out = nullptr;
@@ -945,7 +945,7 @@ static int writer_create_impl(ssw_ctx* ctx, const void* rgb_hwc, int u8, size_t 
     if (pool_get(ctx, plane * 4, (void**)&wr->y) != SSW_OK || pool_get(ctx, plane * 4, (void**)&wr->i) != SSW_OK ||
         pool_get(ctx, plane * 4, (void**)&wr->q) != SSW_OK)
         return fail(SSW_ERR_OUT_OF_MEMORY);
-    const int rc = forward_from_host(ctx, rgb_hwc, u8, w, h, cfg->precision, wr->y, wr->i, wr->q);   // :308-313
+    const int rc = forward_from_host(ctx, rgb_hwc, fmt, w, h, cfg->precision, wr->y, wr->i, wr->q);   // :308-313
     if (rc != SSW_OK) return fail(rc);
     *out = wr;
     return SSW_OK;
@@ -953,17 +953,17 @@ static int writer_create_impl(ssw_ctx* ctx, const void* rgb_hwc, int u8, size_t 
 
 int ssw_writer_create(ssw_ctx* ctx, const float* rgb_hwc, size_t w, size_t h,
                       const ssw_config* cfg, ssw_writer** out) {
-    return writer_create_impl(ctx, rgb_hwc, false, w, h, cfg, out);
+    return writer_create_impl(ctx, rgb_hwc, PixFmt::F32, w, h, cfg, out);
 }
 
 int ssw_writer_create_rgb8(ssw_ctx* ctx, const uint8_t* rgb_hwc, size_t w, size_t h,
                            const ssw_config* cfg, ssw_writer** out) {
-    return writer_create_impl(ctx, rgb_hwc, SSW_PIX_U8, w, h, cfg, out);
+    return writer_create_impl(ctx, rgb_hwc, PixFmt::U8, w, h, cfg, out);
 }
 
 int ssw_writer_create_rgb16(ssw_ctx* ctx, const uint16_t* rgb_hwc, size_t w, size_t h,
                             const ssw_config* cfg, ssw_writer** out) {
-    return writer_create_impl(ctx, rgb_hwc, SSW_PIX_U16, w, h, cfg, out);
+    return writer_create_impl(ctx, rgb_hwc, PixFmt::U16, w, h, cfg, out);
 }
 
 int ssw_writer_coefficients(ssw_writer* wr, float* out_plane) {
@@ -1143,7 +1143,7 @@ int ssw_writer_destroy(ssw_writer* wr) {
 
 // ---- Reader ---------------------------------------------------------------------------------
 static int reader_ensure_indices(ssw_reader* rd, size_t k);
-static int reader_create_impl(ssw_ctx* ctx, const void* rgb_hwc, int u8, size_t w, size_t h, int is_base,
+static int reader_create_impl(ssw_ctx* ctx, const void* rgb_hwc, PixFmt fmt, size_t w, size_t h, int is_base,
                               const ssw_config* cfg, ssw_reader** out) {
     if (!ctx || !rgb_hwc || !out) return SSW_ERR_BAD_ARG;
     *out = nullptr;
@@ -1161,8 +1161,8 @@ static int reader_create_impl(ssw_ctx* ctx, const void* rgb_hwc, int u8, size_t 
     auto fail = [&](int rc) { ssw_reader_destroy(rd); return rc; };
     if (!is_base && ctx->prune) {
         // upload only; transformed on first use (see ssw_reader)
-        const size_t bytes = plane * 3 * pix_bytes(u8);
-        rd->rgb_u8 = u8;
+        const size_t bytes = plane * 3 * pix_bytes(fmt);
+        rd->rgb_fmt = fmt;
         bool fenced = false;
         const int rt = rgb_spare_take(ctx, bytes, &rd->rgb, &rd->rgb_uploaded, &fenced);
         if (rt != SSW_OK) return fail(rt);
@@ -1179,7 +1179,7 @@ static int reader_create_impl(ssw_ctx* ctx, const void* rgb_hwc, int u8, size_t 
         return SSW_OK;
     }
     if (pool_get(ctx, plane * 4, (void**)&rd->y) != SSW_OK) return fail(SSW_ERR_OUT_OF_MEMORY);
-    const int rc = forward_from_host(ctx, rgb_hwc, u8, w, h, c.precision, rd->y, nullptr, nullptr);   // :476-480
+    const int rc = forward_from_host(ctx, rgb_hwc, fmt, w, h, c.precision, rd->y, nullptr, nullptr);   // :476-480
     if (rc != SSW_OK) return fail(rc);
     // The ordering is the reader's (:493) but its length is only known at extract(): queue it now for the length the
     // context's last extraction used, so that it runs while the derived frame is still crossing PCIe instead of after it
@@ -1202,14 +1202,14 @@ static int reader_ensure_coefficients(ssw_reader* rd) {
     auto run = [&]() -> int {
         SSW_TRY(grow(ctx->lane[0].plane[3], plane * sizeof(float)));
         Chain ch;
-        SSW_TRY(build_forward_from_rgb(ctx, ctx->lane[0], rd->cfg.precision, rd->rgb, rd->rgb_u8, 1, rd->w, rd->h, y,
+        SSW_TRY(build_forward_from_rgb(ctx, ctx->lane[0], rd->cfg.precision, rd->rgb, rd->rgb_fmt, 1, rd->w, rd->h, y,
                                        nullptr, nullptr, (float*)ctx->lane[0].plane[3].p, ch));
         return run_serial(ch, ctx->stream);
     };
     const int rc = run();
     if (rc != SSW_OK) { pool_put(ctx, y, plane * 4); return rc; }
     rd->y = y;
-    rgb_spare_give(ctx, rd->rgb, plane * 3 * pix_bytes(rd->rgb_u8), rd->rgb_uploaded);      // reuse is ordered behind this point of the stream
+    rgb_spare_give(ctx, rd->rgb, plane * 3 * pix_bytes(rd->rgb_fmt), rd->rgb_uploaded);      // reuse is ordered behind this point of the stream
     rd->rgb = nullptr;
     rd->rgb_uploaded = nullptr;
     return SSW_OK;
@@ -1217,17 +1217,17 @@ static int reader_ensure_coefficients(ssw_reader* rd) {
 
 int ssw_reader_create(ssw_ctx* ctx, const float* rgb_hwc, size_t w, size_t h, int is_base,
                       const ssw_config* cfg, ssw_reader** out) {
-    return reader_create_impl(ctx, rgb_hwc, false, w, h, is_base, cfg, out);
+    return reader_create_impl(ctx, rgb_hwc, PixFmt::F32, w, h, is_base, cfg, out);
 }
 
 int ssw_reader_create_rgb8(ssw_ctx* ctx, const uint8_t* rgb_hwc, size_t w, size_t h, int is_base,
                            const ssw_config* cfg, ssw_reader** out) {
-    return reader_create_impl(ctx, rgb_hwc, SSW_PIX_U8, w, h, is_base, cfg, out);
+    return reader_create_impl(ctx, rgb_hwc, PixFmt::U8, w, h, is_base, cfg, out);
 }
 
 int ssw_reader_create_rgb16(ssw_ctx* ctx, const uint16_t* rgb_hwc, size_t w, size_t h, int is_base,
                             const ssw_config* cfg, ssw_reader** out) {
-    return reader_create_impl(ctx, rgb_hwc, SSW_PIX_U16, w, h, is_base, cfg, out);
+    return reader_create_impl(ctx, rgb_hwc, PixFmt::U16, w, h, is_base, cfg, out);
 }
 
 int ssw_reader_coefficients(ssw_reader* rd, float* out_plane) {
@@ -1282,7 +1282,7 @@ int ssw_reader_extract(ssw_reader* base, ssw_reader* derived, float* out, size_t
         // the derived frame is still RGB: transform it only where the first k indices of the base reader read it
         bool pruned = false;
         uint32_t* info = nullptr;
-        SSW_TRY(extract_single_pruned(ctx, derived->cfg.precision, derived->rgb, derived->rgb_u8, base->w, base->h, base->y,
+        SSW_TRY(extract_single_pruned(ctx, derived->cfg.precision, derived->rgb, derived->rgb_fmt, base->w, base->h, base->y,
                                       base->idx, k, base->cfg.method, base->cfg.alpha, (float*)ctx->small.p, &info, &pruned));
         if (pruned) {
             uint32_t overflow = 1;
@@ -1353,7 +1353,7 @@ int ssw_reader_destroy(ssw_reader* rd) {
     CtxGuard g(ctx);
     pool_put(ctx, rd->y, rd->w * rd->h * 4);
     pool_put(ctx, rd->idx, rd->idx_k * sizeof(uint32_t));
-    rgb_spare_give(ctx, rd->rgb, rd->w * rd->h * 3 * pix_bytes(rd->rgb_u8), rd->rgb_uploaded);
+    rgb_spare_give(ctx, rd->rgb, rd->w * rd->h * 3 * pix_bytes(rd->rgb_fmt), rd->rgb_uploaded);
     delete rd;
     return SSW_OK;
 }

@@ -309,10 +309,8 @@ struct PassBuild {
              const PairLayout& lay = PairLayout()) const {
         return launch_dct_pair_gemm_multi_f64(st, is_row, inverse, nc, d, dst, tmp, n, w, h, ep, sink, tmp_out, lay);
     }
-    int rgb_kind() const { return from_rgb ? pix_src_kind(x.rgb_u8) : 0; }
-    const void* prep_src() const { return from_rgb ? x.rgb : (const void*)src; }
-    float* prep_i() const { return from_rgb ? x.iq_i : nullptr; }
-    float* prep_q() const { return from_rgb ? x.iq_q : nullptr; }
+    // what the pass's pre-pass reads: the frames themselves (first pass from RGB: Y on the fly, I / Q out) or the f32 plane
+    RowInput row_input() const { return from_rgb ? RowInput::rgb(x.rgb_fmt, x.rgb, x.iq_i, x.iq_q) : RowInput::plane(src); }
 };
 
 // The classes of one stage: one launch over all of them when the pass merges them, else class by class -- with the main-stage
@@ -457,8 +455,7 @@ int build_pair_two(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused
     double* tmpE = (double*)ws.operand[4].p;     // inverse: the even half E, unrounded
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
-        if (b.from_rgb) SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, b.x.rgb_u8, b.x.rgb, b.n, b.w, b.h, xx1, xx2, x2, b.x.iq_i, b.x.iq_q));
-        else SSW_TRY(launch_dct_pair_prep4(st, b.is_row, b.inverse, b.src, b.n, b.w, b.h, xx1, xx2, x2));
+        SSW_TRY(launch_dct_pair_prep4(st, b.is_row, b.inverse, b.row_input(), b.n, b.w, b.h, xx1, xx2, x2));
         return odd_rotate(b, pp, st, x2);
     }});
     OddHalfLaunch odd;
@@ -489,7 +486,7 @@ int build_pair_three(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
         if (!b.is_row) SSW_TRY(launch_dct_pair_prep8_cols(st, b.src, b.n, b.w, b.h, r1, r2, d2, d1));
-        else SSW_TRY(launch_dct_pair_prep8_rows(st, b.rgb_kind(), b.prep_src(), b.n, b.w, b.h, r1, r2, d2, d1, b.prep_i(), b.prep_q()));
+        else SSW_TRY(launch_dct_pair_prep8_rows(st, b.row_input(), b.n, b.w, b.h, r1, r2, d2, d1));
         return odd_rotate(b, pp, st, d1);
     }});
     OddHalfLaunch odd;
@@ -524,8 +521,7 @@ int build_deep(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
         if (!b.is_row) return launch_dct_pair_prep16_cols(st, b.src, b.n, b.w, b.h, sp, (const double*)pp.rot, (const double*)rot2, nullptr, b.p.prep, b.p.layout);
-        return launch_dct_pair_prep16_rows(st, b.rgb_kind(), b.prep_src(), b.n, b.w, b.h, sp, (const double*)pp.rot, (const double*)rot2, nullptr,
-                                           b.prep_i(), b.prep_q(), false);
+        return launch_dct_pair_prep16_rows(st, b.row_input(), b.n, b.w, b.h, sp, (const double*)pp.rot, (const double*)rot2, nullptr, false);
     }});
     const double f_main = b.flop(C::O), f_all = f_main + b.flop(C::E) + b.flop(C::R1R2) + b.flop(C::E2) + b.flop(C::O2);
     // a single frame's launches are too small alone (class E of a 4K frame: 272 blocks for 512 slots): one launch over all classes
@@ -590,8 +586,7 @@ int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
             StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
             if (!b.is_row) return launch_dct_pair_prep16_cols(st, b.src, n, w, h, sp, (const double*)pp.rot, (const double*)rot2, (const double*)rot3,
                                                               b.p.prep, b.p.layout);
-            return launch_dct_pair_prep16_rows(st, b.rgb_kind(), b.prep_src(), n, w, h, sp, (const double*)pp.rot, (const double*)rot2,
-                                               (const double*)rot3, b.prep_i(), b.prep_q(), true, fused);
+            return launch_dct_pair_prep16_rows(st, b.row_input(), n, w, h, sp, (const double*)pp.rot, (const double*)rot2, (const double*)rot3, true, fused);
         }});
     const double f_main = b.flop(PairClass::O5), f_all = 8.0 * f_main;      // (every class: the same pairs and sum length)
     std::array<PairClassDesc, 8> d;
@@ -759,9 +754,9 @@ int build_pass(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, bool first_pass,
     b.px = (double)b.n * (double)b.w * (double)b.h;
     // algorithmic bytes of the pre-pass: the f32 plane (or the RGB frame) in, the operand planes (one double per pixel, whatever
     // the number of folding levels) and I / Q out
-    b.prep_bytes = b.from_rgb ? b.px * (3.0 * (double)pix_bytes(x.rgb_u8) + (x.iq_i ? 8.0 : 0.0) + 8.0) : b.px * (4.0 + 8.0);
+    b.prep_bytes = b.from_rgb ? b.px * (3.0 * (double)pix_bytes(x.rgb_fmt) + (x.iq_i ? 8.0 : 0.0) + 8.0) : b.px * (4.0 + 8.0);
     const bool sink_pass = b.inverse && !first_pass && !is_row && x.rgb_out && x.iq_i && x.iq_q;
-    b.out_bpp = sink_pass ? 8.0 + 3.0 * (double)pix_bytes(x.rgb_out_u8) : 4.0;
+    b.out_bpp = sink_pass ? 8.0 + 3.0 * (x.rgb_out_u8 ? 1.0 : 4.0) : 4.0;
     const size_t first = ch.size();
     typedef PassStrategy S;
     const S s = b.p.strategy;
@@ -793,7 +788,7 @@ int build_transform(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, Chain& ch, 
             s.n = std::min(max_frames, n - f0);
             s.data = x.data + f0 * w * h;
             s.tmp = x.tmp + f0 * w * h;
-            if (x.rgb) s.rgb = static_cast<const char*>(x.rgb) + f0 * w * h * 3 * pix_bytes(x.rgb_u8);
+            if (x.rgb) s.rgb = static_cast<const char*>(x.rgb) + f0 * w * h * 3 * pix_bytes(x.rgb_fmt);
             if (x.iq_i) s.iq_i = x.iq_i + f0 * w * h;
             if (x.iq_q) s.iq_q = x.iq_q + f0 * w * h;
             if (x.rgb_out) s.rgb_out = static_cast<char*>(x.rgb_out) + f0 * w * h * 3 * (x.rgb_out_u8 ? 1 : sizeof(float));
@@ -827,28 +822,28 @@ PassPlan forward_rows_plan(const ssw_ctx* ctx, bool f64, size_t n, size_t w, siz
 }  // namespace
 
 // the row pass takes two folding levels or more (its pre-pass can read RGB) and the frames suit that pre-pass
-bool can_fuse_rgb(const ssw_ctx* ctx, bool f64, size_t w, size_t h, const float* y, const float* tmp, const void* rgb, int u8) {
-    return forward_rows_plan(ctx, f64, 1, w, h, y, tmp).levels >= 2 && dct_pair_can_prep_from_rgb(w, h, rgb, u8);
+bool can_fuse_rgb(const ssw_ctx* ctx, bool f64, size_t w, size_t h, const float* y, const float* tmp, const void* rgb, PixFmt fmt) {
+    return forward_rows_plan(ctx, f64, 1, w, h, y, tmp).levels >= 2 && dct_pair_can_prep_from_rgb(w, h, rgb, fmt);
 }
 
 // Writer::new / Reader::base / Reader::derived: rgb -> Y (+ I, Q) -> forward 2-D DCT of Y into `y`.
 // Where the default GEMM strategy applies (rows first, two folding levels on the row axis) the colour
 // conversion is fused into the first operand pre-pass and the f32 Y plane is never materialised.
-int build_forward_from_rgb(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, int u8, size_t n, size_t w,
+int build_forward_from_rgb(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, PixFmt fmt, size_t n, size_t w,
                            size_t h, float* y, float* i, float* q, float* tmp, Chain& ch, const BasePrune* base_prune) {
     const bool f64 = precision == SSW_PRECISION_F64;
     Xform x{SSW_DCT2, precision, n, w, h, y, tmp};
     x.base_prune = base_prune;
-    if (can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, u8)) {
-        x.rgb = rgb; x.rgb_u8 = u8; x.iq_i = i; x.iq_q = q;
+    if (can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, fmt)) {
+        x.rgb = rgb; x.rgb_fmt = fmt; x.iq_i = i; x.iq_q = q;
         return build_transform(ctx, ws, x, ch);
     }
     const size_t npix = n * w * h;
-    const double bytes = (double)npix * (3.0 * (double)pix_bytes(u8) + (i ? 12.0 : 4.0));
+    const double bytes = (double)npix * (3.0 * (double)pix_bytes(fmt) + (i ? 12.0 : 4.0));
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, SSW_STAGE_RGB_TO_YIQ, st, bytes);
-        if (u8 == SSW_PIX_U8) return launch_rgb8_to_yiq(st, static_cast<const uint8_t*>(rgb), npix, y, i, q);
-        if (u8 == SSW_PIX_U16) return launch_rgb16_to_yiq(st, static_cast<const uint16_t*>(rgb), npix, y, i, q);
+        if (fmt == PixFmt::U8) return launch_rgb8_to_yiq(st, static_cast<const uint8_t*>(rgb), npix, y, i, q);
+        if (fmt == PixFmt::U16) return launch_rgb16_to_yiq(st, static_cast<const uint16_t*>(rgb), npix, y, i, q);
         return launch_rgb_to_yiq(st, static_cast<const float*>(rgb), npix, y, i, q);
     }});
     return build_transform(ctx, ws, x, ch);
@@ -858,14 +853,14 @@ int build_forward_from_rgb(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const
 // of the top half of a frame runs while the bottom half is still crossing PCIe -- image rows are independent lines
 // of a row pass, so any band of rows gives the values the whole frame gives).  `rows` consecutive image rows starting
 // at `rgb` -> the same rows of the intermediate plane `tmp` (+ I, Q); then the column pass tmp -> y on the whole frame.
-bool can_split_forward_rows(const ssw_ctx* ctx, bool f64, size_t w, size_t h, size_t bands, const float* y, const float* tmp, const void* rgb, int u8) {
-    return bands >= 2 && w >= h && h % 16 == 0 && h % bands == 0 && can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, u8) &&
-           can_fuse_rgb(ctx, f64, w, h / bands, y, tmp, rgb, u8);
+bool can_split_forward_rows(const ssw_ctx* ctx, bool f64, size_t w, size_t h, size_t bands, const float* y, const float* tmp, const void* rgb, PixFmt fmt) {
+    return bands >= 2 && w >= h && h % 16 == 0 && h % bands == 0 && can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, fmt) &&
+           can_fuse_rgb(ctx, f64, w, h / bands, y, tmp, rgb, fmt);
 }
-int build_forward_rows_band(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, int u8, size_t w, size_t rows,
+int build_forward_rows_band(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, PixFmt fmt, size_t w, size_t rows,
                             size_t frame_h, float* tmp, float* i, float* q, Chain& ch) {
     Xform x{SSW_DCT2, precision, 1, w, rows, tmp /* never read or written by this pass */, tmp};
-    x.rgb = rgb; x.rgb_u8 = u8; x.iq_i = i; x.iq_q = q;
+    x.rgb = rgb; x.rgb_fmt = fmt; x.iq_i = i; x.iq_q = q;
     x.full_h = frame_h;
     return build_pass(ctx, ws, x, true, true, tmp, tmp, Epilogue{1.f, 1.f}, ch);
 }
@@ -1065,10 +1060,10 @@ size_t prune_capacity(size_t k) {
 }
 
 PruneSetup make_prune_setup(const ssw_ctx* ctx, bool f64, size_t n, size_t w, size_t h, size_t k, const float* y, const float* tmp,
-                            const void* rgb, int u8) {
+                            const void* rgb, PixFmt fmt) {
     PruneSetup ps;
     if (!ctx->prune || k == 0 || !f64) return ps;                          // (the pair path runs in f64 only)
-    if (!can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, u8)) return ps;       // rows first, >= two folding levels on the rows
+    if (!can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, fmt)) return ps;       // rows first, >= two folding levels on the rows
     const bool aligned = aligned_planes(y, tmp);
     if (!dct_pair_can_run(n, w, h, aligned)) return ps;                   // the chunk's planes within the 4 GB walk
     const size_t cap = prune_capacity(k);
@@ -1185,7 +1180,7 @@ int make_call_prune_tables(ssw_ctx* ctx, const PruneSetup& ps, size_t w, size_t 
 // what the route builders of one chunk share; held by value in the stages
 struct PrunedChunk {
     ssw_ctx* ctx;
-    const void* rgb; int u8;
+    RowInput in;                    // the derived frames: an RGB source, no I / Q out
     size_t n, w, h, k, lines;
     const uint32_t* idx;
     bool make_tables;               // this chain makes the tables it reads (else the call did: make_call_prune_tables)
@@ -1194,6 +1189,7 @@ struct PrunedChunk {
     PruneTables t;
     size_t cap() const { return t.plan.cap_total; }
     double px() const { return (double)n * (double)w * (double)h; }
+    double rgb_bytes() const { return px() * 3.0 * (double)pix_bytes(pix_fmt(in.kind)); }      // the frames, once in
 };
 
 // r5: marks of up to 1024 entries at level 2 -- the whole row pass in one kernel (dct_pair_derived.hip): no operand planes.
@@ -1205,12 +1201,12 @@ void pruned_rows_fused(const PrunedChunk& q, const std::array<DerivedFusedClass,
             untimed_work(ctx);
             return enqueue_prune_tables(st, q.t, q.idx, q.n, q.k, false, true);
         }});
-    const double in_bytes = q.px() * 3.0 * (double)pix_bytes(q.u8);
+    const double in_bytes = q.rgb_bytes();
     // (timed with the RGB pre-passes: an HBM-bound kernel -- frames in, compact plane out -- whose 0.1e12 flop ride along;
     // bench.py's GEMM family stays "every pair_gemm_f64_kernel launch")
     ch.push_back({false, [=](hipStream_t st) -> int {
         StageTimer t(ctx, SSW_STAGE_RGB_TO_YIQ, st, in_bytes + (double)q.lines * (double)q.cap() * 4.0);
-        return launch_dct_pair_derived_fused(st, pix_src_kind(q.u8), q.rgb, q.lines, q.w, q.t.rot[0], q.t.rot[1], q.t.rot[2], q.t.plan.n_classes, fca.data(),
+        return launch_dct_pair_derived_fused(st, q.in, q.lines, q.w, q.t.rot[0], q.t.rot[1], q.t.rot[2], q.t.plan.n_classes, fca.data(),
                                              q.t_compact, (unsigned)q.cap());
     }});
 }
@@ -1222,7 +1218,7 @@ void pruned_rows_gathered(const PrunedChunk& q, Chain& ch) {
     const bool deep = plan_is_deep(q.t.rows), level2 = plan_is_level2(q.t.rows);
     const int levels = q.t.rows.levels;
     const unsigned ncl = q.t.plan.n_classes;
-    const double prep_bytes = q.px() * (3.0 * (double)pix_bytes(q.u8) + 8.0);
+    const double prep_bytes = q.rgb_bytes() + q.px() * 8.0;
     double flop = 0.0;
     for (unsigned c = 0; c < ncl; ++c) flop += (q.t.c[c].s.split ? 4.0 : 2.0) * (double)q.lines * q.t.plan.c[c].cap * (double)q.t.c[c].s.ktrue;
     ch.push_back({true, [=](hipStream_t st) -> int {
@@ -1231,9 +1227,9 @@ void pruned_rows_gathered(const PrunedChunk& q, Chain& ch) {
             untimed_work(ctx);
         }
         StageTimer t(ctx, SSW_STAGE_RGB_TO_YIQ, st, prep_bytes);
-        if (deep) return launch_dct_pair_prep16_rows(st, pix_src_kind(q.u8), q.rgb, q.n, q.w, q.h, q.sp, q.t.rot[0], q.t.rot[1], q.t.rot[2], nullptr, nullptr, level2);
-        if (levels == 3) SSW_TRY(launch_dct_pair_prep8_rows(st, pix_src_kind(q.u8), q.rgb, q.n, q.w, q.h, q.o[2], q.o[3], q.o[0], q.o[1], nullptr, nullptr));
-        else SSW_TRY(launch_dct_pair_prep4_rows_rgb(st, q.u8, q.rgb, q.n, q.w, q.h, q.o[2], q.o[3], q.o[1], nullptr, nullptr));
+        if (deep) return launch_dct_pair_prep16_rows(st, q.in, q.n, q.w, q.h, q.sp, q.t.rot[0], q.t.rot[1], q.t.rot[2], level2);
+        if (levels == 3) SSW_TRY(launch_dct_pair_prep8_rows(st, q.in, q.n, q.w, q.h, q.o[2], q.o[3], q.o[0], q.o[1]));
+        else SSW_TRY(launch_dct_pair_prep4(st, true, false, q.in, q.n, q.w, q.h, q.o[2], q.o[3], q.o[1]));
         return q.sp ? launch_dct_pair_rotate(st, q.o[1], q.t.rot[0], q.sp, q.lines, q.w) : SSW_OK;
     }});
     ch.back().tag = 2;
@@ -1269,14 +1265,14 @@ int pruned_cols(ssw_ctx* ctx, ssw_ctx::Lane& ws, size_t n, size_t cap, size_t h,
 // derived rgb frames -> compact coefficient plane ws.compact[1] [n][h][cap_total] holding, for every frequency column the
 // index lists use, the column the full (f64: make_prune_setup) transform would produce.  `call_tables`: the chunk reads the
 // call's tables; else it owns them in `ws` and its chain makes them.  *pos: their position list, for the extraction.
-int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, int u8, size_t n, size_t w, size_t h, size_t k,
+int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, PixFmt fmt, size_t n, size_t w, size_t h, size_t k,
                          const uint32_t* idx, const PruneSetup& ps, uint32_t* info, bool call_tables, Chain& ch, const uint32_t** pos) {
     const size_t cap = ps.plan.cap_total, lines = n * h;
     const bool deep = plan_is_deep(ps.rows), level2 = plan_is_level2(ps.rows);
     if (!deep) for (int b = 0; b < 4; ++b) SSW_TRY(grow(ws.operand[b], dct_pair_operand_elems(n, w, h) * sizeof(double)));      // the deep pre-pass writes into operand[5] only
     for (int b = 0; b < 2; ++b) SSW_TRY(grow(ws.compact[b], n * h * cap * sizeof(float)));
     if (ps.rows.split) SSW_TRY(grow(ws.operand[5], split_scratch_elems(n, w, h) * sizeof(double)));
-    PrunedChunk q{ctx, rgb, u8, n, w, h, k, lines, idx, !call_tables, ps.rows.split ? (double*)ws.operand[5].p : nullptr,
+    PrunedChunk q{ctx, RowInput::rgb(fmt, rgb), n, w, h, k, lines, idx, !call_tables, ps.rows.split ? (double*)ws.operand[5].p : nullptr,
                   {(double*)ws.operand[0].p, (double*)ws.operand[1].p, (double*)ws.operand[2].p, (double*)ws.operand[3].p}, (float*)ws.compact[0].p};
     SSW_TRY(lay_out_prune_tables(ctx, call_tables ? nullptr : &ws, ps, w, info, q.t));
     *pos = q.t.pos;
@@ -1329,10 +1325,10 @@ int run_pruned_pipeline(ssw_ctx* ctx, size_t n_chunks, const PruneSetup& ps, boo
 // switches between two ways to the same values; the debug entry ssw_debug_base_prune_bound shows what the decide kernel
 // would compare for a shape, whether or not a call would currently take the path, so it applies none of them (its own k
 // checks are those of its arguments).
-bool base_prune_shape_ok(const ssw_ctx* ctx, const ssw_config& c, size_t n, size_t w, size_t h, const void* rgb, int u8, const float* y, const float* tmp) {
+bool base_prune_shape_ok(const ssw_ctx* ctx, const ssw_config& c, size_t n, size_t w, size_t h, const void* rgb, PixFmt fmt, const float* y, const float* tmp) {
     const bool f64 = c.precision == SSW_PRECISION_F64;
     if (!f64 || w % SSW_BASE_PRUNE_TILE != 0 || w / SSW_BASE_PRUNE_TILE < 2 || w < h || !(base_prune_gain(w, h, c.ordering) > 0.0f)) return false;
-    if (!can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, u8)) return false;
+    if (!can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, fmt)) return false;
     const PlanInput in{SSW_DCT2, c.precision, n, w, h, 0, false, true, plan_settings(ctx)};
     return n <= plan_frame_limit(plan_settings(ctx), f64, w, h) && plan_pass(in, true, true).strategy == PassStrategy::FusedRows &&
            plan_pass(in, false, false).strategy == PassStrategy::FusedCols;
@@ -1367,7 +1363,7 @@ void push_extract_stage(Chain& ch, ssw_ctx* ctx, const ssw_config& c, const floa
 }  // namespace
 
 // ---- Writer::new + Writer::mark, batched ------------------------------------------------------------------
-int batch_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_rgb, int u8_in, size_t n_frames, size_t w,
+int batch_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_rgb, PixFmt fmt_in, size_t n_frames, size_t w,
                      size_t h, const float* dev_marks, size_t k, void* dev_rgb_out, bool u8_out, float* dev_coef_out,
                      uint32_t* dev_indices_out) {
     if (!ctx || !dev_rgb || !dev_marks || !dev_rgb_out) return SSW_ERR_BAD_ARG;
@@ -1379,7 +1375,7 @@ int batch_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_rgb, i
     const size_t chunk = effective_chunk(ctx, w, h, n_frames);
     const size_t n_chunks = (n_frames + chunk - 1) / chunk;
     const ssw_config c = *cfg;
-    const size_t in_px = 3 * pix_bytes(u8_in), out_px = u8_out ? 3 : 3 * sizeof(float);
+    const size_t in_px = 3 * pix_bytes(fmt_in), out_px = u8_out ? 3 : 3 * sizeof(float);
     auto build = [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch) -> int {
         const size_t f0 = ci * chunk, n = std::min(chunk, n_frames - f0);
         for (int p = 0; p < 4; ++p) SSW_TRY(grow(ws.plane[p], chunk * plane * sizeof(float)));
@@ -1394,7 +1390,7 @@ int batch_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_rgb, i
         float* coef_out = dev_coef_out ? dev_coef_out + f0 * plane : nullptr;
         const float* marks = dev_marks + f0 * k;
         SelectWorkspace* sel = &ws.sel;
-        SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, rgb, u8_in, n, w, h, y, pi, pq, tmp, ch));   // Writer::new :308-313
+        SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, rgb, fmt_in, n, w, h, y, pi, pq, tmp, ch));   // Writer::new :308-313
         ch.push_back({true, [=](hipStream_t st) -> int {
             if (coef_out) { SSW_HIP_CHECK(hipMemcpyAsync(coef_out, y, n * plane * sizeof(float), hipMemcpyDeviceToDevice, st)); untimed_work(ctx); }
             if (k_eff == 0) return SSW_OK;
@@ -1419,7 +1415,7 @@ int batch_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_rgb, i
 }
 
 // ---- Reader::base + Reader::derived + extract (+ Tester::similarity), batched --------------------------------
-int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base_rgb, const void* dev_derived_rgb, int u8,
+int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base_rgb, const void* dev_derived_rgb, PixFmt fmt,
                        size_t n_frames, size_t w, size_t h, size_t k, float* dev_extracted, const float* dev_marks,
                        float* dev_sims) {
     if (!ctx || !dev_base_rgb || !dev_derived_rgb || !dev_extracted) return SSW_ERR_BAD_ARG;
@@ -1434,20 +1430,20 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
     const size_t n_chunks = (n_frames + chunk - 1) / chunk;
     const ssw_config c = *cfg;
     const bool f64 = c.precision == SSW_PRECISION_F64;
-    const size_t px_bytes = 3 * pix_bytes(u8);
+    const size_t px_bytes = 3 * pix_bytes(fmt);
     // planes of lane 0 decide the (alignment-dependent) strategy for all lanes: hipMalloc'd, always 256-byte aligned
     // (lane 1 only when the call will run two lanes: three chunks or more)
     for (int l = 0; l < (pipeline_uses_two_lanes(ctx, n_chunks) ? 2 : 1); ++l)
         for (int p : {0, 2}) SSW_TRY(grow(ctx->lane[l].plane[p], chunk * plane * sizeof(float)));
     const float *y0 = (const float*)ctx->lane[0].plane[0].p, *tmp0 = (const float*)ctx->lane[0].plane[2].p;
-    const PruneSetup ps = stream_capturing(ctx) ? PruneSetup() : make_prune_setup(ctx, f64, std::min(chunk, n_frames), w, h, k, y0, tmp0, dev_derived_rgb, u8);
+    const PruneSetup ps = stream_capturing(ctx) ? PruneSetup() : make_prune_setup(ctx, f64, std::min(chunk, n_frames), w, h, k, y0, tmp0, dev_derived_rgb, fmt);
     if (ps.on) SSW_TRY(grow(ctx->overflow, n_chunks * SSW_PRUNE_INFO * sizeof(uint32_t)));      // a block per chunk: every frame has its own list
     uint32_t* overflow = (uint32_t*)ctx->overflow.p;
     // Base-reader pruning (base_prune.hip): where the planner takes the fused forward transform for the chunks of this call
     // and the ordering has a key bound.  ssw_ctx_set_prune(0) and the tuning entry base_prune = 0 give the full transform.
     bool base_prune = ctx->prune && tuning(TUNE_BASE_PRUNE) != 0 && k > 0 && k <= select_max_k();
     for (size_t f0 = 0; base_prune && f0 < n_frames; f0 += chunk)        // (the last chunk may be shorter: another plan)
-        base_prune = base_prune_shape_ok(ctx, c, std::min(chunk, n_frames - f0), w, h, dev_base_rgb, u8, y0, tmp0);
+        base_prune = base_prune_shape_ok(ctx, c, std::min(chunk, n_frames - f0), w, h, dev_base_rgb, fmt, y0, tmp0);
     if (base_prune && !ctx->base_prune_stats.p) {
         SSW_TRY(grow(ctx->base_prune_stats, 8 * sizeof(unsigned long long)));
         SSW_HIP_CHECK(hipMemsetAsync(ctx->base_prune_stats.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
@@ -1474,7 +1470,7 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
             bp.k = k; bp.ordering = c.ordering;
         }
         // Reader::base (:474-480): only the Y plane is ever used by a reader
-        SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, brgb, u8, n, w, h, yb, nullptr, nullptr, tmp, ch, base_prune ? &bp : nullptr));
+        SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, brgb, fmt, n, w, h, yb, nullptr, nullptr, tmp, ch, base_prune ? &bp : nullptr));
         const unsigned* mask = decided ? bp.need : nullptr;
         if (k > 0)
             ch.push_back({true, [=](hipStream_t st) -> int { return topk(ctx, st, *sel, yb, n, w, h, c.ordering, k, idx, mask); }});   // :493
@@ -1482,11 +1478,11 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         const float* derived = nullptr;
         const uint32_t* pos = nullptr;
         if (pruned) {
-            SSW_TRY(build_pruned_derived(ctx, ws, drgb, u8, n, w, h, k, idx, ps, overflow + ci * SSW_PRUNE_INFO, false, ch, &pos));
+            SSW_TRY(build_pruned_derived(ctx, ws, drgb, fmt, n, w, h, k, idx, ps, overflow + ci * SSW_PRUNE_INFO, false, ch, &pos));
             derived = (const float*)ws.compact[1].p;
         } else {
             SSW_TRY(grow(ws.plane[1], chunk * plane * sizeof(float)));
-            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, drgb, u8, n, w, h, (float*)ws.plane[1].p, nullptr, nullptr, tmp, ch));
+            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, drgb, fmt, n, w, h, (float*)ws.plane[1].p, nullptr, nullptr, tmp, ch));
             derived = (const float*)ws.plane[1].p;
         }
         push_extract_stage(ch, ctx, c, yb, derived, pos, ps.plan.cap_total, n, w, h, idx, k, dev_extracted + f0 * k,
@@ -1506,13 +1502,13 @@ int base_prune_bound_impl(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_
     const size_t plane = w * h;
     ssw_ctx::Lane& ws = ctx->lane[0];
     for (int p : {0, 2}) SSW_TRY(grow(ws.plane[p], n_frames * plane * sizeof(float)));
-    if (k == 0 || k >= plane || !base_prune_shape_ok(ctx, c, n_frames, w, h, dev_rgb, SSW_PIX_F32, (const float*)ws.plane[0].p, (const float*)ws.plane[2].p))
+    if (k == 0 || k >= plane || !base_prune_shape_ok(ctx, c, n_frames, w, h, dev_rgb, PixFmt::F32, (const float*)ws.plane[0].p, (const float*)ws.plane[2].p))
         return SSW_ERR_UNSUPPORTED;
     BasePrune bp;
     SSW_TRY(base_prune_workspace(ws, n_frames, w, bp));
     bp.k = k; bp.ordering = c.ordering;
     Chain ch;
-    SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_rgb, SSW_PIX_F32, n_frames, w, h, (float*)ws.plane[0].p, nullptr, nullptr,
+    SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_rgb, PixFmt::F32, n_frames, w, h, (float*)ws.plane[0].p, nullptr, nullptr,
                                    (float*)ws.plane[2].p, ch, &bp));
     SSW_TRY(run_serial(ch, ctx->stream));
     untimed_work(ctx);
@@ -1522,7 +1518,7 @@ int base_prune_bound_impl(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_
 // ---- one base frame against many suspect frames (ssw_fingerprint_trace) -----------------------------------------
 // Reader::base of the one original (:474-480, :493): plane and index list into buffers the CONTEXT owns -- every chunk on
 // both lanes reads them.  On the context's stream, with lane 0's workspace (the suspects' pipeline starts behind it).
-int trace_base(ssw_ctx* ctx, const ssw_config& c, const void* dev_base_rgb, int u8, size_t w, size_t h, size_t k, const float** y,
+int trace_base(ssw_ctx* ctx, const ssw_config& c, const void* dev_base_rgb, PixFmt fmt, size_t w, size_t h, size_t k, const float** y,
                const uint32_t** idx) {
     const size_t plane = w * h;
     ssw_ctx::Lane& ws = ctx->lane[0];
@@ -1532,7 +1528,7 @@ int trace_base(ssw_ctx* ctx, const ssw_config& c, const void* dev_base_rgb, int 
     float* yb = (float*)ctx->trace[0].p;
     uint32_t* ib = (uint32_t*)ctx->trace[1].p;
     Chain ch;
-    SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_base_rgb, u8, 1, w, h, yb, nullptr, nullptr, (float*)ws.plane[2].p, ch));
+    SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_base_rgb, fmt, 1, w, h, yb, nullptr, nullptr, (float*)ws.plane[2].p, ch));
     SSW_TRY(run_serial(ch, ctx->stream));
     if (k > 0) SSW_TRY(topk(ctx, ctx->stream, ws.sel, yb, 1, w, h, c.ordering, k, ib));
     *y = yb;
@@ -1544,15 +1540,15 @@ int trace_base(ssw_ctx* ctx, const ssw_config& c, const void* dev_base_rgb, int 
 // same chunks, same lanes, same kernels up to the compact plane -- with the prune tables and gathered bases made once for
 // the call (one list: the column set cannot grow with the batch, and there is one info block, so an overflow redoes every
 // chunk) and the extraction that reads every base value once per slice of frames.
-int trace_extract(ssw_ctx* ctx, const ssw_config& c, const float* yb, const uint32_t* idx, const void* dev_suspect_rgb, int u8,
+int trace_extract(ssw_ctx* ctx, const ssw_config& c, const float* yb, const uint32_t* idx, const void* dev_suspect_rgb, PixFmt fmt,
                   size_t n_frames, size_t w, size_t h, size_t k, float* dev_extracted) {
     if (n_frames == 0) return SSW_OK;
     const size_t plane = w * h;
     const size_t chunk = effective_chunk(ctx, w, h, n_frames);
     const size_t n_chunks = (n_frames + chunk - 1) / chunk;
-    const size_t px_bytes = 3 * pix_bytes(u8);
+    const size_t px_bytes = 3 * pix_bytes(fmt);
     const PruneSetup ps = stream_capturing(ctx) ? PruneSetup()
-                          : make_prune_setup(ctx, c.precision == SSW_PRECISION_F64, std::min(chunk, n_frames), w, h, k, yb, yb, dev_suspect_rgb, u8);
+                          : make_prune_setup(ctx, c.precision == SSW_PRECISION_F64, std::min(chunk, n_frames), w, h, k, yb, yb, dev_suspect_rgb, fmt);
     if (ps.on) SSW_TRY(grow(ctx->overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));                 // one block: one list for the call
     uint32_t* info = (uint32_t*)ctx->overflow.p;
     if (ps.on) SSW_TRY(make_call_prune_tables(ctx, ps, w, k, idx, info));
@@ -1561,10 +1557,10 @@ int trace_extract(ssw_ctx* ctx, const ssw_config& c, const float* yb, const uint
         const char* srgb = static_cast<const char*>(dev_suspect_rgb) + f0 * plane * px_bytes;
         float* ext = dev_extracted + f0 * k;
         const uint32_t* pos = nullptr;                 // Reader::derived: the compact plane through the tables' position list, or the full plane
-        if (pruned) SSW_TRY(build_pruned_derived(ctx, ws, srgb, u8, n, w, h, k, idx, ps, info, true, ch, &pos));
+        if (pruned) SSW_TRY(build_pruned_derived(ctx, ws, srgb, fmt, n, w, h, k, idx, ps, info, true, ch, &pos));
         else {
             for (int p : {1, 2}) SSW_TRY(grow(ws.plane[p], chunk * plane * sizeof(float)));
-            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, srgb, u8, n, w, h, (float*)ws.plane[1].p, nullptr, nullptr, (float*)ws.plane[2].p, ch));
+            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, srgb, fmt, n, w, h, (float*)ws.plane[1].p, nullptr, nullptr, (float*)ws.plane[2].p, ch));
         }
         const float* derived = (const float*)(pruned ? ws.compact[1].p : ws.plane[1].p);
         const size_t cap = ps.plan.cap_total;
@@ -1586,7 +1582,7 @@ int trace_extract(ssw_ctx* ctx, const ssw_config& c, const float* yb, const uint
 // dev_info[0] (non-zero: the columns did not fit, the caller must transform fully) -- enqueue-only, unlike
 // run_pruned_pipeline: the caller reads the flag with the download of the result.  *applicable = false (nothing
 // enqueued) when the shape or the settings do not take the pruned path.
-int extract_single_pruned(ssw_ctx* ctx, int precision, const void* derived_rgb, int u8, size_t w, size_t h, const float* base_y,
+int extract_single_pruned(ssw_ctx* ctx, int precision, const void* derived_rgb, PixFmt fmt, size_t w, size_t h, const float* base_y,
                           const uint32_t* idx, size_t k, int method, float alpha, float* dev_out, uint32_t** dev_info,
                           bool* applicable) {
     *applicable = false;
@@ -1594,13 +1590,13 @@ int extract_single_pruned(ssw_ctx* ctx, int precision, const void* derived_rgb, 
     ssw_ctx::Lane& ws = ctx->lane[0];
     for (int p : {0, 2}) SSW_TRY(grow(ws.plane[p], plane * sizeof(float)));
     const PruneSetup ps = make_prune_setup(ctx, precision == SSW_PRECISION_F64, 1, w, h, k, (const float*)ws.plane[0].p,
-                                           (const float*)ws.plane[2].p, derived_rgb, u8);
+                                           (const float*)ws.plane[2].p, derived_rgb, fmt);
     if (!ps.on) return SSW_OK;
     SSW_TRY(grow(ctx->overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));
     uint32_t* info = (uint32_t*)ctx->overflow.p;
     Chain ch;
     const uint32_t* pos = nullptr;
-    SSW_TRY(build_pruned_derived(ctx, ws, derived_rgb, u8, 1, w, h, k, idx, ps, info, false, ch, &pos));
+    SSW_TRY(build_pruned_derived(ctx, ws, derived_rgb, fmt, 1, w, h, k, idx, ps, info, false, ch, &pos));
     SSW_TRY(run_serial(ch, ctx->stream));
     {
         StageTimer t(ctx, SSW_STAGE_EXTRACT, ctx->stream);

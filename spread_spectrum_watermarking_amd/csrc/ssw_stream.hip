@@ -119,7 +119,7 @@ int stream_embed_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* const*
             SSW_HIP_CHECK(hipStreamWaitEvent(ctx->stream, hs.up_done[s], 0));
             if (g >= (size_t)NB) SSW_HIP_CHECK(hipStreamWaitEvent(ctx->stream, hs.down_done[s], 0));   // download of group g - NB reads out[s]
             untimed_work(ctx);                 // the group's first stage timer starts behind these waits
-            SSW_TRY(batch_embed_impl(ctx, cfg, hs.in[s].p, SSW_PIX_U8, n, w, h, (const float*)hs.marks.p + f0 * k, k, hs.out[s].p, true, nullptr, nullptr));
+            SSW_TRY(batch_embed_impl(ctx, cfg, hs.in[s].p, PixFmt::U8, n, w, h, (const float*)hs.marks.p + f0 * k, k, hs.out[s].p, true, nullptr, nullptr));
             SSW_HIP_CHECK(hipEventRecord(hs.k_done[s], ctx->stream));
             untimed_work(ctx);
             if (g + NB - 1 < n_groups) SSW_TRY(h2d(g + NB - 1));      // staged (pageable) frames: the host copies while group g computes
@@ -176,7 +176,7 @@ int stream_extract_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* cons
             if (g + NB - 1 < n_groups) SSW_TRY(h2d(g + NB - 1));
             SSW_HIP_CHECK(hipStreamWaitEvent(ctx->stream, hs.up_done[s], 0));
             untimed_work(ctx);
-            SSW_TRY(batch_extract_impl(ctx, cfg, hs.in[s].p, hs.in2[s].p, SSW_PIX_U8, n, w, h, k, (float*)hs.ext.p + f0 * k,
+            SSW_TRY(batch_extract_impl(ctx, cfg, hs.in[s].p, hs.in2[s].p, PixFmt::U8, n, w, h, k, (float*)hs.ext.p + f0 * k,
                                        host_marks ? (const float*)hs.marks.p + f0 * k : nullptr, host_sims ? (float*)hs.sims.p + f0 : nullptr));
             SSW_HIP_CHECK(hipEventRecord(hs.k_done[s], ctx->stream));
             untimed_work(ctx);
@@ -247,7 +247,7 @@ int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, co
             for (size_t j = 0; j < n; ++j)
                 if (touched(f0 + j)) jobs.push_back(RestoreJob{(const uint8_t*)hs.in2[s].p + j * raw_slot, (uint8_t*)hs.in[s].p + j * fb, pl[f0 + j]});
             SSW_TRY(restore_enqueue(ctx, dev_base, w, h, jobs.data(), jobs.size()));
-            SSW_TRY(trace_extract(ctx, c, base_y, base_idx, hs.in[s].p, SSW_PIX_U8, n, w, h, k, (float*)hs.ext.p + f0 * k));
+            SSW_TRY(trace_extract(ctx, c, base_y, base_idx, hs.in[s].p, PixFmt::U8, n, w, h, k, (float*)hs.ext.p + f0 * k));
             SSW_HIP_CHECK(hipEventRecord(hs.k_done[s], ctx->stream));
             untimed_work(ctx);
         }

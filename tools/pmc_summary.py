@@ -3,12 +3,22 @@
 usage: pmc_summary.py <dir> [substring filter]"""
 import csv, glob, os, sys, collections
 d = sys.argv[1]; filt = sys.argv[2] if len(sys.argv) > 2 else ""
+def short_name(name):
+    """The instance without its parameter list: cut at the first "(" outside the template arguments (an enum argument is
+    printed as a cast, "<(ssw::RowSrc)1, false>")."""
+    name = name.replace("(anonymous namespace)::", "").replace("void ", "").replace("ssw::", "")
+    depth = 0
+    for i, ch in enumerate(name):
+        depth += (ch == "<") - (ch == ">")
+        if ch == "(" and depth == 0:
+            return name[:i]
+    return name
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
     for row in csv.DictReader(open(f)):
         name = row.get("Kernel_Name", "")
         if filt and filt not in name: continue
-        short = name.replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "").replace("ssw::", "")
+        short = short_name(name)
         acc[short][row["Counter_Name"]].append(float(row["Counter_Value"]))
 for k in sorted(acc):
     print(k, {c: round(sum(v) / len(v), 1) for c, v in sorted(acc[k].items())}, "n=%d" % len(next(iter(acc[k].values()))))

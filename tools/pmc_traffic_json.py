@@ -53,7 +53,8 @@ K16 = lambda n: -(-(n // 16) // 16) * 16      # ... of the n/16-wide ones
 l2r, l2c = W >= 1280 and W % 64 == 0, H >= 720 and H % 16 == 0
 PR, KR = (W // 16, K16(W)) if l2r else (W // 8, K8(W))
 PC, KC = (H // 16, K16(H)) if l2c else (H // 8, K8(H))
-names = {   # instance in the rocprofv3 output -> (label used by bench.py / DESIGN.md, algorithmic bytes per launch, note)
+names = {   # instance in the rocprofv3 output (tools/pmc_summary.py; enum arguments print as casts: (RowSrc)1 = RgbF32, (PixFmt)0 = F32,
+            # csrc/ssw_internal.hpp) -> (label used by bench.py / DESIGN.md, algorithmic bytes per launch, note)
     "pair_gemm_f64_kernel<false, 0, false, 4>": ("pair_gemm_f64_kernel<rows, split odd half, class O (level 2: rotated, '+' launch)>",
         2 * lines_r * KR * esz + 2 * (PR + 1) * KR * esz + lines_r * (2 * PR) * 4,
         "two operand planes (k-blocked f64) x cosine / sine rows -> two frequencies per pair (f32); level 2: W/16 + 1 pairs in W/16 slots"),
@@ -80,20 +81,20 @@ names = {   # instance in the rocprofv3 output -> (label used by bench.py / DESI
     "pair_gemm_f64_kernel<true, 5, false, 0>": ("pair_gemm_f64_kernel<cols, inverse split odd half + yiq->rgb>",
         2 * lines_c * KC * esz + 2 * PC * KC * esz + lines_c * (2 * PC) * esz + lines_c * (4 * PC) * (8 + 12),
         "last pass of Writer::result: split odd part + unrounded even half in, I and Q in, RGB f32 out (level 2: four launches, a quarter of the rows each)"),
-    "pair_prep16_rows_kernel<double, 1, false>": ("pair_prep16_rows_kernel<double, rgb>", lines_r * W * (12 + esz),
+    "pair_prep16_rows_kernel<(RowSrc)1, false>": ("pair_prep16_rows_kernel<rgb>", lines_r * W * (12 + esz),
         "reader: RGB f32 in, the ten f64 operand planes of the deep row pass out"),
-    "pair_prep16_rows_kernel<double, 1, true>": ("pair_prep16_rows_kernel<double, rgb, with I/Q>", lines_r * W * (12 + 8 + esz),
+    "pair_prep16_rows_kernel<(RowSrc)1, true>": ("pair_prep16_rows_kernel<rgb, with I/Q>", lines_r * W * (12 + 8 + esz),
         "writer: RGB f32 in, operand planes + I, Q planes out"),
-    "pair_prep16_rows_light_kernel<1, false, 8>": ("pair_prep16_rows_light_kernel<rgb>", lines_r * W * (12 + esz),
+    "pair_prep16_rows_light_kernel<(RowSrc)1, false, 8>": ("pair_prep16_rows_light_kernel<rgb>", lines_r * W * (12 + esz),
         "r5, reader: RGB f32 in, the sixteen f64 operand planes of the level-2 row pass out (the < 64-VGPR form, csrc/dct_pair_prep_light.hip)"),
-    "pair_prep16_rows_light_kernel<1, true, 8>": ("pair_prep16_rows_light_kernel<rgb, with I/Q>", lines_r * W * (12 + 8 + esz),
+    "pair_prep16_rows_light_kernel<(RowSrc)1, true, 8>": ("pair_prep16_rows_light_kernel<rgb, with I/Q>", lines_r * W * (12 + 8 + esz),
         "r5, writer: RGB f32 in, operand planes + I, Q planes out"),
-    "prep16_derived_fused_kernel<1>": ("prep16_derived_fused_kernel<rgb>", lines_r * W * 12 + lines_r * 256 * 4,
+    "prep16_derived_fused_kernel<(PixFmt)0>": ("prep16_derived_fused_kernel<rgb>", lines_r * W * 12 + lines_r * 256 * 4,
         "r5: the derived frame's pruned row pass in one kernel (csrc/dct_pair_derived.hip): RGB f32 in, the compact plane (256 columns for k = 1000) out"),
-    "pair_prep16_cols_kernel<double>": ("pair_prep16_cols_kernel<double>", lines_r * W * (4 + esz),
+    "pair_prep16_cols_kernel<true>": ("pair_prep16_cols_kernel", lines_r * W * (4 + esz),
         "r3 kernel (SSW_PREP_STAGED=0): f32 plane in, transposed deep f64 operand planes out (mean over launches incl. the narrow pruned ones)"),
-    "pair_prep16_inv_rows_kernel<double>": ("pair_prep16_inv_rows_kernel<double>", lines_r * W * (4 + esz), "r3 kernel: coefficient plane in, deep inverse operand planes out"),
-    "pair_prep16_inv_cols_kernel<double>": ("pair_prep16_inv_cols_kernel<double>", lines_r * W * (4 + esz), "r3 kernel: the same, transposed"),
+    "pair_prep16_inv_rows_kernel": ("pair_prep16_inv_rows_kernel", lines_r * W * (4 + esz), "r3 kernel: coefficient plane in, deep inverse operand planes out"),
+    "pair_prep16_inv_cols_kernel<true>": ("pair_prep16_inv_cols_kernel", lines_r * W * (4 + esz), "r3 kernel: the same, transposed"),
     # r4: the LDS-staged forms (csrc/dct_pair_prep_staged.hip); <1 | 2, true> = class-major tiles, deep
     "prep16_cols_staged_kernel<1, true>": ("prep16_cols_staged_kernel<class-major tile, deep>", lines_r * W * (4 + esz),
         "forward column pre-pass: f32 plane (class-major tiles of 128 columns) in, the ten transposed f64 operand planes out"),

@@ -20,7 +20,8 @@ ks = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"
 
 def short(name):
     name = name.replace("void ", "").replace("ssw::", "").replace("(anonymous namespace)::", "")
-    return name.split("(")[0][:48]
+    i = name.find(">(")                                    # (enum template arguments print as casts: "<(RowSrc)1, false>(...")
+    return (name[:i + 1] if i >= 0 else name.split("(")[0])[:48]
 
 
 def union(iv):
