@@ -451,7 +451,8 @@ int ssw_writer_mark_copies_rgb8(ssw_writer* wr, const float* host_marks, size_t 
                                      bit to ssw_similarity_batch(ext_s, mark_best), i.e. Tester::similarity itself (:702-713);
                                      NaN where there is no winner
      dev_n_exceed [n_suspects]       (may be NULL) entries of row s with sim > threshold; NaN never exceeds
-                                     (Similarity::exceeds_sigma, :677).  Two colluders show as 2.
+                                     (Similarity::exceeds_sigma, :677).  Two colluders show as 2 -- for an averaged forgery; see the
+                                     strength report (ssw_collude_rgb8 below).
    NaN is a real case: a suspect identical to the original extracts all zeros and every similarity is 0 / sqrt(0).
    Status codes follow ssw_batch_extract: k >= w*h SSW_ERR_K_TOO_LARGE (:553-555); n_suspects == 0 SSW_OK; dev_marks ==
    NULL requires n_marks == 0 and every similarity output NULL (extraction only), anything else SSW_ERR_BAD_ARG; Custom
@@ -654,6 +655,61 @@ int ssw_signature_host_rgb8(ssw_ctx* ctx, const uint8_t* const* host_frames, con
    0xFFFFFFFF. */
 int ssw_signature_match(ssw_ctx* ctx, const uint8_t* dev_query, size_t nq, const uint8_t* dev_catalogue, size_t nc, size_t top,
                         uint32_t* dev_index, uint32_t* dev_dist, uint32_t* dev_all);
+
+/* ---- strength of a mark: its visibility and its collusion resistance (device-resident) ---- */
+/* The two questions to answer before a copy ships: how far is a marked copy from its original, and how many recipients must
+   pool their copies before tracing fails?  The second is the standard evaluation of a fingerprinting scheme and the reason
+   the reference insists on N(0, 1) marks (src/algorithm.rs:604-606, Cox et al. IV-D) -- its own note on several marks in one
+   image (src/algorithm.rs:389-393: 100 marks of N = 1000 leave each an average similarity of 3.1) is the nearest it comes
+   to measuring it; the first is what the reference's README concedes for the default Option2(0.1) (a "cloudy" background).
+   The reference computes neither.  Everything is an integer, no value depends on the order of a sum, and the results equal the
+   numpy restatement in tests/test_collude_cpu.py exactly.  Both calls are timed under SSW_STAGE_CONVERT with their
+   algorithmic bytes as work; there is no stage of their own, because the number of stages is part of what callers and tests
+   of this header rely on.  Neither has a host-streaming form. */
+/* Distance of n copies dev_copies [n][h][w][3] from their original(s) dev_base [n_base][h][w][3], n_base == 1 (the one
+   original is compared against every copy) or n_base == n (frame i against copy i).  Per copy, with d = copy - base per byte
+   and the luma of ssw_locate_rgb8, L(p) = (77 R + 150 G + 29 B + 128) >> 8:
+     stats[0..2]  sum of d * d over the R, G and B bytes
+     stats[3]     sum of (L(copy) - L(base))^2 over the pixels
+     stats[4]     the number of bytes with d != 0
+     stats[5]     max |d|
+   dev_stats [n][6], 64 bits each (255^2 w h exceeds 32 bits from about 66 000 pixels).  PSNR is the caller's arithmetic:
+   10 log10(255^2 * 3 w h / (stats[0] + stats[1] + stats[2])), infinite at 0.  The call zeroes dev_stats itself and only
+   enqueues on the context's stream.  No alignment is assumed of any pointer or of w * 3.  With n_base == 1 a block reads its
+   piece of the original once and goes over the copies with it: (1 + n) * 3 bytes per pixel.  Work: (n_base + n) * 3 w h +
+   48 n bytes.  n == 0: SSW_OK; SSW_ERR_BAD_ARG: a null pointer, n_base not 1 or n; SSW_ERR_BAD_DIMS: w * h == 0 (and a side above
+   2^31 or a frame whose bytes do not fit size_t, in both calls). */
+int ssw_quality_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, size_t n_base, const uint8_t* dev_copies, size_t n, size_t w, size_t h,
+                     uint64_t* dev_stats);
+/* A forged copy out of several: coalition i makes dev_out[i] [h][w][3] from `count` of the frames dev_copies [n_copies][h][w][3].
+   The definition is per byte: v[j] are the values of the members at that byte in member order, s[0] <= ... <= s[c-1] the same
+   values sorted, c = count; integer division throughout:
+     SSW_COLLUDE_AVERAGE   (sum of v + c / 2) / c
+     SSW_COLLUDE_MEDIAN    (s[(c-1)/2] + s[c/2] + 1) >> 1    -- odd c: the middle value itself
+     SSW_COLLUDE_MIN       s[0]
+     SSW_COLLUDE_MAX       s[c-1]
+     SSW_COLLUDE_MINMAX    (s[0] + s[c-1] + 1) >> 1
+     SSW_COLLUDE_MOSAIC    v[((x >> 5) + (y >> 5)) % c] at pixel (x, y): cut-and-paste of 32 x 32 tiles; the tile size is a
+                           fixed part of the definition
+   1 <= count <= 16; a member may occur more than once (a weighted coalition); count == 1 copies the frame.  `coalitions` is a
+   HOST array; the descriptors travel as kernel arguments, 32 per launch as in ssw_restore_rgb8.  No host synchronisation, no
+   workspace: the call only enqueues on the context's stream.  No alignment is assumed of any pointer or of w * 3.  dev_out
+   must not overlap dev_copies.  Work: the sum over the coalitions of (c + 1) * 3 w h bytes.  n_coalitions == 0: SSW_OK;
+   SSW_ERR_BAD_ARG: a null pointer, a count outside 1 .. 16, member >= n_copies, an unknown method (nothing is enqueued then);
+   SSW_ERR_BAD_DIMS: an empty frame.
+   What to expect (the oracle on a 640 x 444 photograph, k = 1000, alpha = 0.1, 8 copies; tests/test_collude_cpu.py): two
+   colluders who average score 21.9 each and four 14.2, but three who take the median or the minimum already fall below 6. */
+typedef enum ssw_collude_method {
+    SSW_COLLUDE_AVERAGE = 0,
+    SSW_COLLUDE_MEDIAN = 1,
+    SSW_COLLUDE_MIN = 2,
+    SSW_COLLUDE_MAX = 3,
+    SSW_COLLUDE_MINMAX = 4,
+    SSW_COLLUDE_MOSAIC = 5
+} ssw_collude_method;
+typedef struct ssw_coalition { uint32_t method, count; uint32_t member[16]; } ssw_coalition;
+int ssw_collude_rgb8(ssw_ctx* ctx, const uint8_t* dev_copies, size_t n_copies, size_t w, size_t h, const ssw_coalition* coalitions,
+                     size_t n_coalitions, uint8_t* dev_out);
 
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,

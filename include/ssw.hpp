@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <memory>
 #include <random>
 #include <stdexcept>
@@ -267,7 +268,8 @@ class ReaderDerived;
 
 // What Reader::trace returns, per suspect s: extracted[s] (k values), sims[s] (one per mark; the GEMM matrix, 1e-4 relative),
 // best[s] (index of the strongest mark, TraceResult::none without one), best_sim[s] (Tester::similarity of that mark, exact;
-// NaN without one), n_exceed[s] (marks above the threshold: two and more = colluders).
+// NaN without one), n_exceed[s] (marks above the threshold: two and more = colluders -- for an averaged forgery; see the
+// strength report: wm::collude, wm::quality).
 struct TraceResult {
     static constexpr uint32_t none = 0xFFFFFFFFu;
     std::vector<std::vector<float>> extracted, sims;
@@ -373,6 +375,80 @@ inline std::vector<std::array<uint8_t, 1024>> signature(Context& ctx, const std:
     }
     std::vector<std::array<uint8_t, 1024>> out(n);
     check(ssw_signature_host_rgb8(ctx.get(), ptrs.data(), shapes.data(), n, n ? out[0].data() : nullptr), "signature");
+    return out;
+}
+
+// How far a copy is from its original (ssw_quality_rgb8): squared error per channel and of the luma, changed bytes, the largest
+// byte difference; PSNR is the caller's arithmetic on them.
+struct Quality {
+    uint64_t sse[3] = {0, 0, 0}, sse_luma = 0, changed = 0, max_abs = 0, pixels = 0;
+    double psnr() const {
+        const double e = (double)sse[0] + (double)sse[1] + (double)sse[2];
+        return e == 0.0 ? std::numeric_limits<double>::infinity() : 10.0 * std::log10(255.0 * 255.0 * 3.0 * (double)pixels / e);
+    }
+    double psnr_luma() const {
+        return sse_luma == 0 ? std::numeric_limits<double>::infinity() : 10.0 * std::log10(255.0 * 255.0 * (double)pixels / (double)sse_luma);
+    }
+    double changed_fraction() const { return pixels ? (double)changed / (3.0 * (double)pixels) : 0.0; }
+};
+// One forgery of wm::collude: a method and 1 .. 16 indices into the copies (repeats allowed)
+struct Coalition {
+    ssw_collude_method method = SSW_COLLUDE_AVERAGE;
+    std::vector<uint32_t> members;
+};
+namespace detail {
+// n host frames of one size, one after the other on the device; freed with the object
+struct DeviceFrames {
+    ssw_ctx* c;
+    uint8_t* p = nullptr;
+    DeviceFrames(ssw_ctx* ctx, size_t bytes, const char* where) : c(ctx) { check(ssw_dev_alloc(c, bytes ? bytes : 16, reinterpret_cast<void**>(&p)), where); }
+    ~DeviceFrames() { if (p) ssw_dev_free(c, p); }
+    DeviceFrames(const DeviceFrames&) = delete;
+    DeviceFrames& operator=(const DeviceFrames&) = delete;
+    void put(const std::vector<const ImageRgb8*>& images, size_t w, size_t h, const char* where) {
+        for (size_t i = 0; i < images.size(); ++i) {
+            if (images[i]->width != w || images[i]->height != h || images[i]->data.size() != w * h * 3) throw Error(SSW_ERR_BAD_DIMS, where);
+            check(ssw_copy_to_dev(c, p + i * w * h * 3, images[i]->data.data(), w * h * 3), where);
+        }
+    }
+};
+}  // namespace detail
+// ssw_quality_rgb8 on host images: every copy against the one original.
+inline std::vector<Quality> quality(Context& ctx, const ImageRgb8& original, const std::vector<const ImageRgb8*>& copies) {
+    const size_t n = copies.size(), w = original.width, h = original.height, fb = w * h * 3;
+    detail::DeviceFrames base(ctx.get(), fb, "quality"), dev(ctx.get(), n * fb, "quality"), st(ctx.get(), n * 6 * sizeof(uint64_t), "quality");
+    base.put({&original}, w, h, "quality");
+    dev.put(copies, w, h, "quality");
+    check(ssw_quality_rgb8(ctx.get(), base.p, 1, dev.p, n, w, h, reinterpret_cast<uint64_t*>(st.p)), "quality");
+    std::vector<uint64_t> raw(n * 6);
+    check(ssw_copy_to_host(ctx.get(), raw.data(), st.p, raw.size() * sizeof(uint64_t)), "quality");
+    std::vector<Quality> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t* r = &raw[i * 6];
+        out[i].sse[0] = r[0]; out[i].sse[1] = r[1]; out[i].sse[2] = r[2];
+        out[i].sse_luma = r[3]; out[i].changed = r[4]; out[i].max_abs = r[5]; out[i].pixels = w * h;
+    }
+    return out;
+}
+// ssw_collude_rgb8 on host images of one size: one forged frame per coalition, in order.
+inline std::vector<ImageRgb8> collude(Context& ctx, const std::vector<const ImageRgb8*>& copies, const std::vector<Coalition>& coalitions) {
+    if (copies.empty()) throw Error(SSW_ERR_BAD_ARG, "collude");
+    const size_t n = copies.size(), m = coalitions.size(), w = copies[0]->width, h = copies[0]->height, fb = w * h * 3;
+    std::vector<ssw_coalition> co(m);
+    for (size_t i = 0; i < m; ++i) {
+        if (coalitions[i].members.empty() || coalitions[i].members.size() > 16) throw Error(SSW_ERR_BAD_ARG, "collude");
+        co[i] = ssw_coalition{(uint32_t)coalitions[i].method, (uint32_t)coalitions[i].members.size(), {}};
+        std::copy(coalitions[i].members.begin(), coalitions[i].members.end(), co[i].member);
+    }
+    detail::DeviceFrames dev(ctx.get(), n * fb, "collude"), forged(ctx.get(), m * fb, "collude");
+    dev.put(copies, w, h, "collude");
+    check(ssw_collude_rgb8(ctx.get(), dev.p, n, w, h, co.data(), m, forged.p), "collude");
+    std::vector<ImageRgb8> out(m);
+    for (size_t i = 0; i < m; ++i) {
+        out[i].width = w; out[i].height = h;
+        out[i].data.resize(fb);
+        check(ssw_copy_to_host(ctx.get(), out[i].data.data(), forged.p + i * fb, fb), "collude");
+    }
     return out;
 }
 

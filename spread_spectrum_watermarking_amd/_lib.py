@@ -59,6 +59,18 @@ SIGNATURE_BYTES = 1024
 MATCH_NONE = 0xFFFFFFFF
 MATCH_TILE, MATCH_CHUNK, MATCH_QUERY_TILE, MATCH_TOP_MAX = 128, 32768, 128, 8
 
+
+class Coalition(C.Structure):
+    """ssw_coalition (include/ssw.h): one forgery of ssw_collude_rgb8 -- a method and `count` of the call's frames."""
+    _fields_ = [("method", C.c_uint32), ("count", C.c_uint32), ("member", C.c_uint32 * 16)]
+
+
+# ssw_collude_method, by the names the Python surface and the CLI accept; members of a coalition
+COLLUDE_AVERAGE, COLLUDE_MEDIAN, COLLUDE_MIN, COLLUDE_MAX, COLLUDE_MINMAX, COLLUDE_MOSAIC = range(6)
+COLLUDE_METHODS = {"average": 0, "median": 1, "min": 2, "max": 3, "minmax": 4, "mosaic": 5}
+COLLUDE_MAX_MEMBERS = 16
+QUALITY_STATS = 6            # ssw_quality_rgb8: u64 per copy -- SSE of R, G, B, SSE of the luma, changed bytes, max |d|
+
 _vp, _f32p, _u32p, _u64p, _sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t
 _cfgp = C.POINTER(Config)
 _plp = C.POINTER(Placement)
@@ -150,6 +162,8 @@ SIGNATURES = {
     "ssw_signature_rgb8": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(ImageShape), _sz, _vp]),
     "ssw_signature_host_rgb8": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(ImageShape), _sz, _vp]),
     "ssw_signature_match": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _u32p, _u32p, _u32p]),
+    "ssw_quality_rgb8": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64p]),
+    "ssw_collude_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(Coalition), _sz, _vp]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
                                                            _f32p, _f32p, _u32p, _f32p, _u32p]),
     "ssw_reader_trace_restored_host_rgb8": (C.c_int, [_vp, _vp, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p,

@@ -1099,6 +1099,200 @@ def identify(catalogue: Catalogue, suspects, top: int = 1, max_distance: int = I
     return out
 
 
+# ---- strength of a mark: visibility and collusion resistance (include/ssw.h: ssw_quality_rgb8, ssw_collude_rgb8) -------------
+UPLOAD_GROUP_BYTES = 256 << 20      # frames the host wrappers keep on the device at a time (one frame's own size if that is more)
+
+
+@dataclass
+class Quality:
+    """How far one copy is from its original (ssw_quality_rgb8): squared error per channel and of the luma, changed bytes and
+    the largest byte difference -- integers; the derived figures are the caller's arithmetic and are made here."""
+    sse: Tuple[int, int, int]
+    sse_luma: int
+    changed: int
+    max_abs: int
+    pixels: int
+
+    @property
+    def psnr(self) -> float:
+        """10 log10(255^2 * 3 W H / (SSE_R + SSE_G + SSE_B)) in dB; inf for identical frames."""
+        e = sum(self.sse)
+        return math.inf if e == 0 else 10.0 * math.log10(255.0 ** 2 * 3 * self.pixels / e)
+
+    @property
+    def psnr_luma(self) -> float:
+        return math.inf if self.sse_luma == 0 else 10.0 * math.log10(255.0 ** 2 * self.pixels / self.sse_luma)
+
+    @property
+    def changed_fraction(self) -> float:
+        return self.changed / (3.0 * self.pixels) if self.pixels else 0.0
+
+
+def _qualities(stats: np.ndarray, pixels: int) -> list:
+    return [Quality((int(r[0]), int(r[1]), int(r[2])), int(r[3]), int(r[4]), int(r[5]), pixels) for r in stats]
+
+
+def _frames_u8(images, what: str) -> list:
+    arrs = [np.asarray(im) for im in images]
+    for a in arrs:                                           # checked as they come: nothing is sliced away (an alpha channel is an error)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape != arrs[0].shape or a.size == 0:
+            raise ValueError(f"{what}: 8-bit [H, W, 3] images of one size")
+    return [np.ascontiguousarray(a) for a in arrs]
+
+
+def _upload_frames(ctx: Context, buf: "DeviceBuffer", arrs) -> None:
+    for i, a in enumerate(arrs):
+        check(ctx._lib.ssw_copy_to_dev(ctx.handle, C.c_void_p(buf.ptr.value + i * a.nbytes), a.ctypes.data, a.nbytes), "ssw_copy_to_dev")
+
+
+def quality(base, copies, ctx: Optional[Context] = None) -> list:
+    """One `Quality` per copy.  base: the original, 8-bit [H, W, 3] -- or one original per copy (a list, or [n, H, W, 3]);
+    copies: 8-bit images of that size.  One ssw_quality_rgb8 call per group of at most 256 MiB of frames."""
+    cp = _frames_u8(copies, "quality")
+    if not cp:
+        return []
+    b = np.asarray(base) if not isinstance(base, (list, tuple)) else None
+    bases = _frames_u8([base] if b is not None and b.ndim == 3 else base, "quality")
+    if len(bases) not in (1, len(cp)) or bases[0].shape != cp[0].shape:
+        raise ValueError("quality: one original of the copies' size, or one per copy")
+    ctx = ctx or default_context()
+    h, w = cp[0].shape[:2]
+    fb, n, shared = w * h * 3, len(cp), len(bases) == 1
+    per = max(1, UPLOAD_GROUP_BYTES // (fb if shared else 2 * fb))
+    dev_c, dev_s = ctx.alloc(min(per, n) * fb), ctx.alloc(min(per, n) * 8 * L.QUALITY_STATS)
+    dev_b = ctx.to_device(bases[0]) if shared else ctx.alloc(min(per, n) * fb)
+    out = []
+    for g0 in range(0, n, per):
+        g = cp[g0:g0 + per]
+        _upload_frames(ctx, dev_c, g)
+        if not shared:
+            _upload_frames(ctx, dev_b, bases[g0:g0 + per])
+        check(ctx._lib.ssw_quality_rgb8(ctx.handle, dev_b.ptr, 1 if shared else len(g), dev_c.ptr, len(g), w, h, dev_s.ptr), "ssw_quality_rgb8")
+        out += _qualities(dev_s.to_host(np.uint64, (len(g), L.QUALITY_STATS)), w * h)
+    for d in (dev_c, dev_s, dev_b):
+        d.free()
+    return out
+
+
+def _coalition(method, members, n_copies: int) -> L.Coalition:
+    m = L.COLLUDE_METHODS.get(method.lower()) if isinstance(method, str) else int(method)
+    if m is None or m not in L.COLLUDE_METHODS.values():
+        raise ValueError(f"collude: unknown method {method!r} (one of {', '.join(L.COLLUDE_METHODS)})")
+    members = [int(i) for i in members]
+    if not 1 <= len(members) <= L.COLLUDE_MAX_MEMBERS or any(not 0 <= i < n_copies for i in members):
+        raise ValueError(f"collude: 1 .. {L.COLLUDE_MAX_MEMBERS} members, each the index of a copy")
+    return L.Coalition(m, len(members), (C.c_uint32 * L.COLLUDE_MAX_MEMBERS)(*members))
+
+
+def collude(copies, coalitions, ctx: Optional[Context] = None) -> list:
+    """Forged copies out of several (ssw_collude_rgb8; include/ssw.h states the six definitions).  copies: 8-bit [H, W, 3]
+    images of one size; coalitions: (method, members) pairs -- method "average", "median", "min", "max", "minmax" or "mosaic"
+    (or the constant), members 1 .. 16 indices into `copies`, repeats allowed.  Returns one u8 [H, W, 3] frame per coalition,
+    in order.  The coalitions go in groups whose members and results are at most 256 MiB on the device."""
+    cp = _frames_u8(copies, "collude")
+    co = [_coalition(m, mem, len(cp)) for m, mem in coalitions]
+    if not co:
+        return []
+    ctx = ctx or default_context()
+    h, w = cp[0].shape[:2]
+    fb, out = w * h * 3, []
+    g0 = 0
+    while g0 < len(co):
+        used, g1 = [], g0
+        while g1 < len(co):
+            more = [i for i in dict.fromkeys(co[g1].member[:co[g1].count]) if i not in used]
+            if g1 > g0 and (len(used) + len(more) + g1 - g0 + 1) * fb > UPLOAD_GROUP_BYTES:
+                break
+            used += more
+            g1 += 1
+        where = {i: j for j, i in enumerate(used)}
+        local = (L.Coalition * (g1 - g0))(*[L.Coalition(c.method, c.count, (C.c_uint32 * L.COLLUDE_MAX_MEMBERS)(*[where[i] for i in c.member[:c.count]]))
+                                             for c in co[g0:g1]])
+        dev_c, dev_o = ctx.alloc(len(used) * fb), ctx.alloc((g1 - g0) * fb)
+        _upload_frames(ctx, dev_c, [cp[i] for i in used])
+        check(ctx._lib.ssw_collude_rgb8(ctx.handle, dev_c.ptr, len(used), w, h, local, g1 - g0, dev_o.ptr), "ssw_collude_rgb8")
+        out += list(dev_o.to_host(np.uint8, (g1 - g0, h, w, 3)))
+        dev_c.free(); dev_o.free()
+        g0 = g1
+    return out
+
+
+@dataclass
+class Collusion:
+    """What tracing made of one forgery: `size` colluders (the first `size` copies) pooled with `method`.  weakest_colluder: the
+    smallest similarity among them; strongest_innocent: the largest among the other recipients (NaN when there are none);
+    found / accused: colluders / innocents above the threshold."""
+    method: str
+    size: int
+    weakest_colluder: float
+    strongest_innocent: float
+    found: int
+    accused: int
+
+
+@dataclass
+class StrengthRow:
+    """`strength_report` for one alpha: the `Quality` of every copy and one `Collusion` per (method, size), methods outermost."""
+    alpha: float
+    quality: list
+    collusions: list
+
+    def collusion(self, method: str, size: int) -> Collusion:
+        return next(c for c in self.collusions if (c.method, c.size) == (method, size))
+
+
+def _collusion(method: str, size: int, sims: np.ndarray, threshold: float) -> Collusion:
+    inside, outside = sims[:size], sims[size:]
+    over = sims > np.float32(threshold)                      # NaN never exceeds (algorithm.rs:677)
+    return Collusion(method, size, float(inside.min()), float(outside.max()) if outside.size else math.nan,
+                     int(over[:size].sum()), int(over[size:].sum()))
+
+
+def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
+                    methods=("average", "median", "min", "max", "minmax", "mosaic"), threshold: float = 6.0,
+                    config: Optional[WriteConfig] = None, seed=None, ctx: Optional[Context] = None) -> list:
+    """The two questions to answer before a copy ships, per insertion strength: how visible is the mark, and how many
+    recipients must pool their copies before tracing fails?  For each alpha (`config` with its alpha replaced; the default
+    Option2 + Energy): `copies` marked copies of the 8-bit `image` (ssw_fingerprint_embed_rgb8), their distance from it
+    (ssw_quality_rgb8), one forgery per (method, size) from the first `size` copies (one ssw_collude_rgb8 call) and one
+    trace of all forgeries against all marks (ssw_fingerprint_trace_rgb8) -- device-resident: only the original and the
+    marks go up, only statistics and similarities come down.  Marks: numpy.random.default_rng(seed)
+    .standard_normal((copies, k)).astype(float32), the same for every alpha.  Returns one `StrengthRow` per alpha."""
+    img = _frames_u8([image], "strength_report")[0]
+    sizes, methods = [int(c) for c in sizes], [str(m).lower() for m in methods]
+    if any(c > copies for c in sizes):
+        raise ValueError("strength_report: a coalition cannot be larger than the number of copies")
+    if any(not 1 <= c <= L.COLLUDE_MAX_MEMBERS for c in sizes) or copies < 1:
+        raise ValueError(f"strength_report: coalitions of 1 .. {L.COLLUDE_MAX_MEMBERS} copies")
+    plan = [(m, c) for m in methods for c in sizes]
+    co = (L.Coalition * max(len(plan), 1))(*[_coalition(m, range(c), copies) for m, c in plan])
+    ctx = ctx or default_context()
+    config = config or WriteConfig.default()
+    marks = np.random.default_rng(seed).standard_normal((copies, k)).astype(np.float32)
+    h, w = img.shape[:2]
+    fb, nf = w * h * 3, len(plan)
+    dev_img, dev_marks = ctx.to_device(img), ctx.to_device(marks)
+    dev_copies, dev_stats = ctx.alloc(copies * fb), ctx.alloc(copies * 8 * L.QUALITY_STATS)
+    dev_forged, dev_ext, dev_sims = ctx.alloc(max(nf, 1) * fb), ctx.alloc(max(nf * k, 1) * 4), ctx.alloc(max(nf * copies, 1) * 4)
+    lib, rows = ctx._lib, []
+    for alpha in alphas:
+        cfg = L.Config(config.ordering.tag, config.insertion.tag, float(alpha), config.precision)
+        check(lib.ssw_fingerprint_embed_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, w, h, dev_marks.ptr, copies, k, dev_copies.ptr, None),
+              "ssw_fingerprint_embed_rgb8")
+        check(lib.ssw_quality_rgb8(ctx.handle, dev_img.ptr, 1, dev_copies.ptr, copies, w, h, dev_stats.ptr), "ssw_quality_rgb8")
+        sims = np.zeros((0, copies), np.float32)
+        if nf:
+            check(lib.ssw_collude_rgb8(ctx.handle, dev_copies.ptr, copies, w, h, co, nf, dev_forged.ptr), "ssw_collude_rgb8")
+            check(lib.ssw_fingerprint_trace_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, dev_forged.ptr, nf, w, h, k, dev_marks.ptr, copies,
+                                                 C.c_float(threshold), dev_ext.ptr, dev_sims.ptr, None, None, None), "ssw_fingerprint_trace_rgb8")
+            sims = dev_sims.to_host(np.float32, (nf, copies))
+        q = _qualities(dev_stats.to_host(np.uint64, (copies, L.QUALITY_STATS)), w * h)
+        rows.append(StrengthRow(float(alpha), q, [_collusion(m, c, sims[i], threshold) for i, (m, c) in enumerate(plan)]))
+    for d in (dev_img, dev_marks, dev_copies, dev_stats, dev_forged, dev_ext, dev_sims):
+        d.free()
+    return rows
+
+
 # ---- Tester (algorithm.rs:668-715) -------------------------------------------------------------
 @dataclass
 class Similarity:

@@ -28,6 +28,11 @@
     python -m spread_spectrum_watermarking_amd.cli trace --catalogue catalogue.npz --suspects A.png B.png ... [--marks ...]
         -> `identify` for every suspect in one call, then the trace above once per original that was named, with the marks
            file the catalogue holds for it; every record gains an "Original:" line
+    python -m spread_spectrum_watermarking_amd.cli strength <file> --alpha 0.02 0.05 0.1 [-n 1000] [--copies 8] [--collude 2 4]
+            [--method average median min max minmax mosaic] [--similarity-exceed 6.0] [--json]
+        -> before a copy ships: per alpha the PSNR range of the marked copies, and per collusion method and coalition size
+           how many of the colluders a trace of their forgery still finds, the weakest colluder's and the strongest innocent
+           recipient's similarity; everything stays on the GPU between the original going up and the numbers coming down
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -41,7 +46,9 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .api import IDENTIFY_MAX_DISTANCE, Catalogue, Locate, MarkBuf, Placement, Reader, Tester, TraceResult, Writer, identify, locate
+from ._lib import COLLUDE_METHODS
+from .api import (IDENTIFY_MAX_DISTANCE, Catalogue, Locate, MarkBuf, Placement, Reader, Tester, TraceResult, Writer, identify, locate,
+                  strength_report)
 from .storage import Configuration, DescribedWatermark, Version1Storage
 
 _ORDERING_ARGS = {"energy": "Energy", "energy-orthogonal": "EnergyOrthogonal", "legacy": "Legacy"}
@@ -221,6 +228,16 @@ def build_parser() -> argparse.ArgumentParser:
     i.add_argument("--top", type=int, default=1, help="Also list the runners-up, N entries in all (1 .. 8).")
     i.add_argument("--max-distance", type=int, default=IDENTIFY_MAX_DISTANCE,
                    help="The largest signature distance that still names an original.")
+    g = sub.add_parser("strength", help="Report a mark's visibility and its collusion resistance for one or more strengths.")
+    g.add_argument("file", help="The file copies would be made of.")
+    g.add_argument("--alpha", type=float, nargs="+", required=True, help="The strengths to report on.")
+    g.add_argument("-n", "--length", type=int, default=1000, help="Watermark length.")
+    g.add_argument("--copies", type=int, default=8, help="Number of recipients.")
+    g.add_argument("--collude", type=int, nargs="+", default=[2, 4], metavar="C", help="Coalition sizes (the first C recipients).")
+    g.add_argument("--method", nargs="+", choices=list(COLLUDE_METHODS), default=list(COLLUDE_METHODS), help="Collusion methods.")
+    g.add_argument("--similarity-exceed", type=float, default=6.0,
+                   help="If the similarity exceeds this value it is considered to be matching.")
+    g.add_argument("--json", action="store_true", help="Print the report as one JSON document.")
     return p
 
 
@@ -354,6 +371,39 @@ def cmd_identify(args, out=sys.stdout) -> int:
         for name, d, (w, h) in r.candidates[1:]:
             n = name.replace('"', '\\"')
             print(f"  Next: \"{n}\" {w}x{h} (distance {d})", file=out)
+    return 0
+
+
+def cmd_strength(args, out=None) -> int:
+    out = out or sys.stdout                                  # looked up at the call: a caller may have redirected it
+    orig = _open_image(args.file)
+    try:
+        rows = strength_report(orig, args.alpha, k=args.length, copies=args.copies, sizes=args.collude, methods=args.method,
+                               threshold=args.similarity_exceed)
+    except ValueError as e:
+        raise SystemExit(str(e)) from e
+    if args.json:
+        import json
+        num = lambda v: None if v != v else (v if abs(v) != float("inf") else str(v))      # JSON has no NaN / Infinity
+        doc = [{"alpha": r.alpha,
+                "copies": [{"psnr": num(q.psnr), "psnr_luma": num(q.psnr_luma), "sse": list(q.sse), "sse_luma": q.sse_luma,
+                            "changed": q.changed, "max_abs": q.max_abs, "pixels": q.pixels} for q in r.quality],
+                "collusions": [{"method": c.method, "size": c.size, "found": c.found, "accused": c.accused,
+                                "weakest_colluder": num(c.weakest_colluder), "strongest_innocent": num(c.strongest_innocent)}
+                               for c in r.collusions]} for r in rows]
+        print(json.dumps(doc), file=out)
+        return 0
+    for r in rows:
+        psnr = [q.psnr for q in r.quality]
+        print("-", file=out)
+        print(f"  Alpha: {_rust_f32(r.alpha)}", file=out)
+        print(f"  PSNR: {min(psnr):.2f} .. {max(psnr):.2f} dB over {len(psnr)} copies "
+              f"(largest byte difference {max(q.max_abs for q in r.quality)})", file=out)
+        for c in r.collusions:
+            innocent = "none" if c.strongest_innocent != c.strongest_innocent else f"{c.strongest_innocent:.2f}"
+            accused = f", {c.accused} innocent accused" if c.accused else ""
+            print(f"  {c.method} of {c.size}: found {c.found}/{c.size}, weakest colluder {c.weakest_colluder:.2f}, "
+                  f"strongest innocent {innocent}{accused}", file=out)
     return 0
 
 
@@ -505,6 +555,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         return cmd_index(args)
     if args.command == "identify":
         return cmd_identify(args)
+    if args.command == "strength":
+        return cmd_strength(args)
     return 0
 
 
