@@ -710,6 +710,41 @@ typedef enum ssw_collude_method {
 typedef struct ssw_coalition { uint32_t method, count; uint32_t member[16]; } ssw_coalition;
 int ssw_collude_rgb8(ssw_ctx* ctx, const uint8_t* dev_copies, size_t n_copies, size_t w, size_t h, const ssw_coalition* coalitions,
                      size_t n_coalitions, uint8_t* dev_out);
+/* The attack every leaked copy has been through -- somebody saved it as a JPEG: dev_out[j] [h][w][3] is frame jobs[j].frame of
+   dev_frames [n_frames][h][w][3] as it comes back from a baseline JPEG of quality jobs[j].quality (1 .. 100), exactly what
+   PIL's save(f, "JPEG", quality=q) followed by open gives (libjpeg-turbo's defaults).  Only the entropy coder, which loses nothing,
+   is left out, so there is no bitstream and no file size.  The definition is in integers from end to end, and the numpy
+   restatement in tests/test_jpeg_cpu.py (`jpeg_ref`, checked there against PIL byte for byte) is what the call equals:
+     colour   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16,
+              Cr = (32768 R - 27439 G - 5329 B + 8421375) >> 16  (8421375 = (128 << 16) + 32767)
+     padding  to whole MCUs of 16 x 16 pixels: the luma, and the chroma's right edge, repeat the frame's last pixel; the chroma's
+              bottom rows repeat the last DOWNSAMPLED row (of a frame of odd height: its last row is used twice first)
+     4:2:0    Cb, Cr: the sum of 2 x 2 samples plus a bias that alternates 1, 2 along a row, >> 2
+     tables   Annex K.1 (luma) and K.2 (chroma) times s percent, s = 5000 / q below quality 50 and 200 - 2 q from there on:
+              (entry * s + 50) / 100 in integers, limited to 1 .. 255 (baseline); computed on the host
+     blocks   per 8 x 8 block of samples - 128: jpeg_fdct_islow (rows, then columns; 13-bit constants), each coefficient divided
+              by 8 * entry, round half away from zero, multiplied by entry again, jpeg_idct_islow (columns, then rows), + 128,
+              limited to 0 .. 255
+     upsample "fancy" h2v2: vertically 3 a + the sample above (even rows) or below (odd rows), then horizontally
+              (3 c + left + 8) >> 4 for even and (3 c + right + 7) >> 4 for odd pixels, the frame's own first and last chroma
+              sample repeated at the edges
+     colour   R = Y + ((91881 Cr' + 32768) >> 16), G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16),
+              B = Y + ((116130 Cb' + 32768) >> 16) with Cb' = Cb - 128, Cr' = Cr - 128, limited to 0 .. 255
+   `jobs` is a HOST array; a frame may occur in many jobs and in any order.  The call only enqueues on the context's stream (no host
+   synchronisation); the jobs go in groups of at most 16 whose decoded planes (1.5 bytes per padded pixel and job, at most 64 MiB
+   or one job's) are the context's workspace, and their tables travel as kernel arguments.  No alignment is assumed of any
+   pointer or of w * 3.  dev_out must not overlap dev_frames.  Timed under SSW_STAGE_CONVERT; work: per job 2 * 3 w h bytes of
+   frames and 2 * (w h + 2 ceil(w / 2) ceil(h / 2)) bytes of planes.  n_jobs == 0: SSW_OK; SSW_ERR_BAD_ARG: a null pointer, a
+   quality outside 1 .. 100, frame >= n_frames, a side below 8 (libjpeg's own upsampler reads beyond the last chroma column of
+   frames 4 or fewer pixels wide; nothing is enqueued then); SSW_ERR_BAD_DIMS: an empty frame or a side above 65535, the most a
+   JPEG holds.
+   What to expect (the oracle on a 640 x 444 photograph, k = 1000; tests/test_jpeg_cpu.py): a copy marked at alpha 0.1 still
+   scores 30.9 after quality 50 and 19.0 after quality 10; one marked at alpha 0.02 scores 20.6 after quality 50 and 3.7 --
+   untraceable -- after quality 10.  Other subsampling modes, grey or CMYK frames, custom tables and the ifast / float DCTs are
+   not offered. */
+typedef struct ssw_jpeg_job { uint32_t frame; uint32_t quality; } ssw_jpeg_job;
+int ssw_jpeg_rgb8(ssw_ctx* ctx, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h, const ssw_jpeg_job* jobs,
+                  size_t n_jobs, uint8_t* dev_out);
 
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,

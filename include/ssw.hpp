@@ -452,6 +452,30 @@ inline std::vector<ImageRgb8> collude(Context& ctx, const std::vector<const Imag
     return out;
 }
 
+// One result of wm::jpeg: a frame (an index into the images) and a JPEG quality 1 .. 100
+struct JpegJob {
+    uint32_t frame = 0;
+    uint32_t quality = 75;
+};
+// ssw_jpeg_rgb8 on host images of one size: per job that frame as it comes back from a baseline JPEG of that quality -- what
+// libjpeg-turbo's defaults (4:2:0, islow DCT, fancy upsampling) give, byte for byte; include/ssw.h states the steps.
+inline std::vector<ImageRgb8> jpeg(Context& ctx, const std::vector<const ImageRgb8*>& frames, const std::vector<JpegJob>& jobs) {
+    if (frames.empty()) throw Error(SSW_ERR_BAD_ARG, "jpeg");
+    const size_t n = frames.size(), m = jobs.size(), w = frames[0]->width, h = frames[0]->height, fb = w * h * 3;
+    std::vector<ssw_jpeg_job> jb(m);
+    for (size_t i = 0; i < m; ++i) jb[i] = ssw_jpeg_job{jobs[i].frame, jobs[i].quality};
+    detail::DeviceFrames dev(ctx.get(), n * fb, "jpeg"), coded(ctx.get(), m * fb, "jpeg");
+    dev.put(frames, w, h, "jpeg");
+    check(ssw_jpeg_rgb8(ctx.get(), dev.p, n, w, h, jb.data(), m, coded.p), "jpeg");
+    std::vector<ImageRgb8> out(m);
+    for (size_t i = 0; i < m; ++i) {
+        out[i].width = w; out[i].height = h;
+        out[i].data.resize(fb);
+        check(ssw_copy_to_host(ctx.get(), out[i].data.data(), coded.p + i * fb, fb), "jpeg");
+    }
+    return out;
+}
+
 // The originals someone owns, as signatures: which of them is a suspect a copy of?  The stage in front of locate / Reader::trace
 // (ssw_signature_match; include/ssw.h states the definition and what it cannot find: cut-outs, mirrored and turned copies).
 // The signatures stay on the device between match calls and go up again only after an add.

@@ -69,6 +69,14 @@ class Coalition(C.Structure):
 COLLUDE_AVERAGE, COLLUDE_MEDIAN, COLLUDE_MIN, COLLUDE_MAX, COLLUDE_MINMAX, COLLUDE_MOSAIC = range(6)
 COLLUDE_METHODS = {"average": 0, "median": 1, "min": 2, "max": 3, "minmax": 4, "mosaic": 5}
 COLLUDE_MAX_MEMBERS = 16
+
+
+class JpegJob(C.Structure):
+    """ssw_jpeg_job (include/ssw.h): one result of ssw_jpeg_rgb8 -- a frame of the call and a quality 1 .. 100."""
+    _fields_ = [("frame", C.c_uint32), ("quality", C.c_uint32)]
+
+
+JPEG_MIN_SIDE = 8            # ssw_jpeg_rgb8 refuses smaller frames
 QUALITY_STATS = 6            # ssw_quality_rgb8: u64 per copy -- SSE of R, G, B, SSE of the luma, changed bytes, max |d|
 
 _vp, _f32p, _u32p, _u64p, _sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t
@@ -164,6 +172,7 @@ SIGNATURES = {
     "ssw_signature_match": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _u32p, _u32p, _u32p]),
     "ssw_quality_rgb8": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64p]),
     "ssw_collude_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(Coalition), _sz, _vp]),
+    "ssw_jpeg_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(JpegJob), _sz, _vp]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
                                                            _f32p, _f32p, _u32p, _f32p, _u32p]),
     "ssw_reader_trace_restored_host_rgb8": (C.c_int, [_vp, _vp, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p,

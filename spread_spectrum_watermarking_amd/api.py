@@ -1217,6 +1217,51 @@ def collude(copies, coalitions, ctx: Optional[Context] = None) -> list:
     return out
 
 
+def _jpeg_qualities(qualities, what: str) -> list:
+    qs = list(qualities)
+    if any(isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 1 <= q <= 100 for q in qs):
+        raise ValueError(f"{what}: JPEG qualities are integers 1 .. 100")
+    return [int(q) for q in qs]
+
+
+def _jpeg_frames(images, what: str) -> list:
+    frames = _frames_u8(images, what)
+    if frames and min(frames[0].shape[:2]) < L.JPEG_MIN_SIDE:
+        raise ValueError(f"{what}: a JPEG attack needs frames of at least {L.JPEG_MIN_SIDE} x {L.JPEG_MIN_SIDE} pixels")
+    return frames
+
+
+def jpeg(images, qualities, ctx: Optional[Context] = None) -> list:
+    """Every image as it comes back from a baseline JPEG of every quality (ssw_jpeg_rgb8; include/ssw.h states the steps): what
+    PIL's save(f, "JPEG", quality=q) and open give, byte for byte, without a bitstream.  images: 8-bit [H, W, 3] of one size, no
+    side below 8; qualities: integers 1 .. 100.  Returns [len(images)][len(qualities)] u8 [H, W, 3] frames.  The jobs go in
+    groups whose frames and results are at most 256 MiB on the device."""
+    frames, qs = _jpeg_frames(images, "jpeg"), _jpeg_qualities(qualities, "jpeg")
+    if not frames or not qs:
+        return [[] for _ in frames]
+    ctx = ctx or default_context()
+    h, w = frames[0].shape[:2]
+    fb, jobs, flat = w * h * 3, [(i, q) for i in range(len(frames)) for q in qs], []
+    g0 = 0
+    while g0 < len(jobs):
+        used, g1 = [], g0                                     # the jobs are in frame order: a group's frames are a run
+        while g1 < len(jobs):
+            new = not used or used[-1] != jobs[g1][0]
+            if g1 > g0 and (len(used) + new + g1 - g0 + 1) * fb > UPLOAD_GROUP_BYTES:
+                break
+            if new:
+                used.append(jobs[g1][0])
+            g1 += 1
+        local = (L.JpegJob * (g1 - g0))(*[L.JpegJob(i - used[0], q) for i, q in jobs[g0:g1]])
+        dev_f, dev_o = ctx.alloc(len(used) * fb), ctx.alloc((g1 - g0) * fb)
+        _upload_frames(ctx, dev_f, [frames[i] for i in used])
+        check(ctx._lib.ssw_jpeg_rgb8(ctx.handle, dev_f.ptr, len(used), w, h, local, g1 - g0, dev_o.ptr), "ssw_jpeg_rgb8")
+        flat += list(dev_o.to_host(np.uint8, (g1 - g0, h, w, 3)))
+        dev_f.free(); dev_o.free()
+        g0 = g1
+    return [flat[i * len(qs):(i + 1) * len(qs)] for i in range(len(frames))]
+
+
 @dataclass
 class Collusion:
     """What tracing made of one forgery: `size` colluders (the first `size` copies) pooled with `method`.  weakest_colluder: the
@@ -1231,11 +1276,28 @@ class Collusion:
 
 
 @dataclass
+class JpegResult:
+    """What tracing made of the marked copies after a JPEG of `quality`.  survived: copies whose own mark still exceeds the
+    threshold; weakest_own: the smallest similarity of a copy with its own mark; strongest_innocent: the largest with another
+    recipient's (NaN when there is one copy); accused: (copy, other mark) pairs above the threshold; psnr_min / psnr_max: the
+    compressed copies against the original, in dB."""
+    quality: int
+    survived: int
+    weakest_own: float
+    strongest_innocent: float
+    accused: int
+    psnr_min: float
+    psnr_max: float
+
+
+@dataclass
 class StrengthRow:
-    """`strength_report` for one alpha: the `Quality` of every copy and one `Collusion` per (method, size), methods outermost."""
+    """`strength_report` for one alpha: the `Quality` of every copy, one `Collusion` per (method, size), methods outermost, and
+    one `JpegResult` per JPEG quality asked for."""
     alpha: float
     quality: list
     collusions: list
+    jpeg: list = field(default_factory=list)
 
     def collusion(self, method: str, size: int) -> Collusion:
         return next(c for c in self.collusions if (c.method, c.size) == (method, size))
@@ -1248,17 +1310,30 @@ def _collusion(method: str, size: int, sims: np.ndarray, threshold: float) -> Co
                      int(over[:size].sum()), int(over[size:].sum()))
 
 
+def _jpeg_result(quality: int, sims: np.ndarray, qualities: list, threshold: float) -> JpegResult:
+    """sims [copies][copies]: row c is copy c after the JPEG against every mark"""
+    own, others = np.diagonal(sims), sims[~np.eye(len(sims), dtype=bool)]
+    over = sims > np.float32(threshold)                      # NaN never exceeds (algorithm.rs:677)
+    psnr = [q.psnr for q in qualities]
+    return JpegResult(quality, int(np.diagonal(over).sum()), float(own.min()), float(others.max()) if others.size else math.nan,
+                      int(over.sum() - np.diagonal(over).sum()), min(psnr), max(psnr))
+
+
 def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                     methods=("average", "median", "min", "max", "minmax", "mosaic"), threshold: float = 6.0,
-                    config: Optional[WriteConfig] = None, seed=None, ctx: Optional[Context] = None) -> list:
+                    config: Optional[WriteConfig] = None, seed=None, ctx: Optional[Context] = None, jpeg=()) -> list:
     """The two questions to answer before a copy ships, per insertion strength: how visible is the mark, and how many
     recipients must pool their copies before tracing fails?  For each alpha (`config` with its alpha replaced; the default
     Option2 + Energy): `copies` marked copies of the 8-bit `image` (ssw_fingerprint_embed_rgb8), their distance from it
     (ssw_quality_rgb8), one forgery per (method, size) from the first `size` copies (one ssw_collude_rgb8 call) and one
     trace of all forgeries against all marks (ssw_fingerprint_trace_rgb8) -- device-resident: only the original and the
     marks go up, only statistics and similarities come down.  Marks: numpy.random.default_rng(seed)
-    .standard_normal((copies, k)).astype(float32), the same for every alpha.  Returns one `StrengthRow` per alpha."""
-    img = _frames_u8([image], "strength_report")[0]
+    .standard_normal((copies, k)).astype(float32), the same for every alpha.  jpeg: JPEG qualities (1 .. 100); per alpha every
+    copy is compressed at every quality (one ssw_jpeg_rgb8 call), all results are traced against all marks (one more
+    ssw_fingerprint_trace_rgb8 call) and measured against the original (one more ssw_quality_rgb8 call): one `JpegResult` per
+    quality in `StrengthRow.jpeg`.  Returns one `StrengthRow` per alpha."""
+    jq = _jpeg_qualities(jpeg, "strength_report")
+    img = (_jpeg_frames if jq else _frames_u8)([image], "strength_report")[0]
     sizes, methods = [int(c) for c in sizes], [str(m).lower() for m in methods]
     if any(c > copies for c in sizes):
         raise ValueError("strength_report: a coalition cannot be larger than the number of copies")
@@ -1274,6 +1349,9 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     dev_img, dev_marks = ctx.to_device(img), ctx.to_device(marks)
     dev_copies, dev_stats = ctx.alloc(copies * fb), ctx.alloc(copies * 8 * L.QUALITY_STATS)
     dev_forged, dev_ext, dev_sims = ctx.alloc(max(nf, 1) * fb), ctx.alloc(max(nf * k, 1) * 4), ctx.alloc(max(nf * copies, 1) * 4)
+    nj = len(jq) * copies                                      # JPEG results of an alpha, quality-major
+    jobs = (L.JpegJob * max(nj, 1))(*[L.JpegJob(c, q) for q in jq for c in range(copies)])
+    dev_jpeg = [ctx.alloc(nj * fb), ctx.alloc(nj * k * 4), ctx.alloc(nj * copies * 4), ctx.alloc(nj * 8 * L.QUALITY_STATS)] if nj else []
     lib, rows = ctx._lib, []
     for alpha in alphas:
         cfg = L.Config(config.ordering.tag, config.insertion.tag, float(alpha), config.precision)
@@ -1288,7 +1366,16 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
             sims = dev_sims.to_host(np.float32, (nf, copies))
         q = _qualities(dev_stats.to_host(np.uint64, (copies, L.QUALITY_STATS)), w * h)
         rows.append(StrengthRow(float(alpha), q, [_collusion(m, c, sims[i], threshold) for i, (m, c) in enumerate(plan)]))
-    for d in (dev_img, dev_marks, dev_copies, dev_stats, dev_forged, dev_ext, dev_sims):
+        if nj:
+            dev_frames, dev_jext, dev_jsims, dev_jstats = dev_jpeg
+            check(lib.ssw_jpeg_rgb8(ctx.handle, dev_copies.ptr, copies, w, h, jobs, nj, dev_frames.ptr), "ssw_jpeg_rgb8")
+            check(lib.ssw_fingerprint_trace_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, dev_frames.ptr, nj, w, h, k, dev_marks.ptr, copies,
+                                                 C.c_float(threshold), dev_jext.ptr, dev_jsims.ptr, None, None, None), "ssw_fingerprint_trace_rgb8")
+            check(lib.ssw_quality_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, nj, w, h, dev_jstats.ptr), "ssw_quality_rgb8")
+            jsims = dev_jsims.to_host(np.float32, (len(jq), copies, copies))
+            jstats = _qualities(dev_jstats.to_host(np.uint64, (nj, L.QUALITY_STATS)), w * h)
+            rows[-1].jpeg = [_jpeg_result(qu, jsims[i], jstats[i * copies:(i + 1) * copies], threshold) for i, qu in enumerate(jq)]
+    for d in [dev_img, dev_marks, dev_copies, dev_stats, dev_forged, dev_ext, dev_sims] + dev_jpeg:
         d.free()
     return rows
 

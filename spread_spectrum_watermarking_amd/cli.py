@@ -29,10 +29,11 @@
         -> `identify` for every suspect in one call, then the trace above once per original that was named, with the marks
            file the catalogue holds for it; every record gains an "Original:" line
     python -m spread_spectrum_watermarking_amd.cli strength <file> --alpha 0.02 0.05 0.1 [-n 1000] [--copies 8] [--collude 2 4]
-            [--method average median min max minmax mosaic] [--similarity-exceed 6.0] [--json]
+            [--method average median min max minmax mosaic] [--jpeg 90 75 50] [--similarity-exceed 6.0] [--json]
         -> before a copy ships: per alpha the PSNR range of the marked copies, and per collusion method and coalition size
            how many of the colluders a trace of their forgery still finds, the weakest colluder's and the strongest innocent
-           recipient's similarity; everything stays on the GPU between the original going up and the numbers coming down
+           recipient's similarity; with --jpeg, per quality what a trace still finds in every copy after it was saved as a
+           JPEG; everything stays on the GPU between the original going up and the numbers coming down
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -237,6 +238,8 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--method", nargs="+", choices=list(COLLUDE_METHODS), default=list(COLLUDE_METHODS), help="Collusion methods.")
     g.add_argument("--similarity-exceed", type=float, default=6.0,
                    help="If the similarity exceeds this value it is considered to be matching.")
+    g.add_argument("--jpeg", type=int, nargs="+", default=[], metavar="Q",
+                   help="Also compress every copy as a JPEG of these qualities (1 .. 100) and trace what is left.")
     g.add_argument("--json", action="store_true", help="Print the report as one JSON document.")
     return p
 
@@ -379,7 +382,7 @@ def cmd_strength(args, out=None) -> int:
     orig = _open_image(args.file)
     try:
         rows = strength_report(orig, args.alpha, k=args.length, copies=args.copies, sizes=args.collude, methods=args.method,
-                               threshold=args.similarity_exceed)
+                               threshold=args.similarity_exceed, jpeg=args.jpeg)
     except ValueError as e:
         raise SystemExit(str(e)) from e
     if args.json:
@@ -390,7 +393,10 @@ def cmd_strength(args, out=None) -> int:
                             "changed": q.changed, "max_abs": q.max_abs, "pixels": q.pixels} for q in r.quality],
                 "collusions": [{"method": c.method, "size": c.size, "found": c.found, "accused": c.accused,
                                 "weakest_colluder": num(c.weakest_colluder), "strongest_innocent": num(c.strongest_innocent)}
-                               for c in r.collusions]} for r in rows]
+                               for c in r.collusions],
+                "jpeg": [{"quality": j.quality, "survived": j.survived, "accused": j.accused, "weakest_own": num(j.weakest_own),
+                          "strongest_innocent": num(j.strongest_innocent), "psnr_min": num(j.psnr_min), "psnr_max": num(j.psnr_max)}
+                         for j in r.jpeg]} for r in rows]
         print(json.dumps(doc), file=out)
         return 0
     for r in rows:
@@ -404,6 +410,11 @@ def cmd_strength(args, out=None) -> int:
             accused = f", {c.accused} innocent accused" if c.accused else ""
             print(f"  {c.method} of {c.size}: found {c.found}/{c.size}, weakest colluder {c.weakest_colluder:.2f}, "
                   f"strongest innocent {innocent}{accused}", file=out)
+        for j in r.jpeg:
+            innocent = "none" if j.strongest_innocent != j.strongest_innocent else f"{j.strongest_innocent:.1f}"
+            accused = f", {j.accused} innocent accused" if j.accused else ""
+            print(f"  jpeg {j.quality}: own mark found {j.survived}/{len(r.quality)}, weakest {j.weakest_own:.1f}, "
+                  f"strongest innocent {innocent}{accused}, {j.psnr_min:.1f} .. {j.psnr_max:.1f} dB", file=out)
     return 0
 
 
