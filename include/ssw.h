@@ -745,6 +745,46 @@ int ssw_collude_rgb8(ssw_ctx* ctx, const uint8_t* dev_copies, size_t n_copies, s
 typedef struct ssw_jpeg_job { uint32_t frame; uint32_t quality; } ssw_jpeg_job;
 int ssw_jpeg_rgb8(ssw_ctx* ctx, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h, const ssw_jpeg_job* jobs,
                   size_t n_jobs, uint8_t* dev_out);
+/* A perceptual score beside PSNR: the structural similarity (SSIM) of n copies dev_copies [n][h][w][3] and their original(s)
+   dev_base [n_base][h][w][3], n_base == 1 or n_base == n as in ssw_quality_rgb8.  Squared error is a poor measure of what a
+   viewer sees -- eight copies of one photograph marked at one alpha spread over 8 dB of PSNR.  Luma is the one of
+   ssw_locate_rgb8 / ssw_quality_rgb8, L(p) = (77 R + 150 G + 29 B + 128) >> 8; a is the luma of the original, b that of the copy.
+     cells     4 x 4 pixels at (4 i, 4 j), i < floor(w / 4), j < floor(h / 4); the up to three trailing columns and rows take no part
+     windows   8 x 8 pixels = 2 x 2 cells, at a stride of 4 pixels in both directions: nx = floor(w / 4) - 1 by
+               ny = floor(h / 4) - 1 of them; window (wx, wy) covers the pixels [4 wx, 4 wx + 8) x [4 wy, 4 wy + 8)
+   Per window, over its 64 pixels, all in 32-bit integers (the largest intermediate is 64 sum(a^2 + b^2) <= 532 684 800):
+     s1 = sum a   s2 = sum b   ss = sum (a^2 + b^2)   s12 = sum a b
+     vars  = 64 ss - s1^2 - s2^2          covar = 64 s12 - s1 s2
+     n1 = 2 s1 s2 + 416                   n2 = 2 covar + 235963
+     d1 = s1^2 + s2^2 + 416               d2 = vars + 235963
+        (416 = floor(0.01^2 255^2 64 + .5), 235963 = floor(0.03^2 255^2 64 63 + .5))
+     q = f64(n1 n2) / f64(d1 d2)          n1 n2 and d1 d2 exact in 64-bit integers (below 2^58), each converted
+                                          round-to-nearest-even, one IEEE division
+     t = (int32) floor(q 2^30 + 0.5)
+   f64(n1) f64(n2) in place of the conversion of the exact product is the same number: the factors are exact in f64 and the
+   product is rounded once.  In these integers 2 s1 s2 <= s1^2 + s2^2, vars - 2 covar = 64 sum (a - b)^2 - (s1 - s2)^2 >= 0 and
+   d1 d2 > 0 hold exactly, so -2^30 < t <= 2^30 = SSW_SSIM_ONE, and t = 2^30 for every window of two equal frames.
+   Per copy dev_stats [n][SSW_SSIM_STATS] receives two 64-bit values:
+     stats[0]  the sum of t over all windows, signed
+     stats[1]  the minimum over the windows of ((uint64)(t + 2^30) << 32 | index), index = wy nx + wx: the worst window; among
+               equal windows the first one wins (one 64-bit atomic minimum: deterministic)
+   and, when dev_map is not NULL, dev_map [n][ny][nx] receives t of every window.  The mean SSIM stats[0] / (2^30 nx ny) and the
+   worst window's value and pixel position (4 wx, 4 wy) are the caller's arithmetic, as PSNR is for ssw_quality_rgb8.  Everything
+   up to the division is an integer, the result is fixed-point and summed as integers: no value depends on the order of a sum,
+   and the call equals the numpy restatement in tests/test_ssim_cpu.py (`ssim_ref`) exactly.
+   The windows and constants are those of the widely used x264 / FFmpeg `ssim`; no bit equality with either is claimed (they
+   evaluate in f32).  The limits: luma only; 8 x 8 box windows, not the Gaussian 11 x 11 of Wang et al.; trailing pixels ignored;
+   no multi-scale variant; no host-streaming form.
+   The call initialises dev_stats itself (sum 0, minimum all ones) and only enqueues on the context's stream, with no
+   workspace.  No alignment is assumed of dev_base, dev_copies or of w * 3 (dev_stats and dev_map as their types require).  A
+   block of the kernel owns SSW_SSIM_TILE_W x SSW_SSIM_TILE_H pixels of windows and reads one more column and row of cells;
+   with n_base == 1 it reads them from the original once and goes over the copies: (1 + n) * 3 bytes per pixel, plus 8 % for the
+   shared cells.  Timed under SSW_STAGE_CONVERT; work: (n_base + n) * 3 w h + 16 n bytes, + 4 nx ny n with a map.  n == 0: SSW_OK;
+   SSW_ERR_BAD_ARG: a null dev_base, dev_copies or dev_stats, n_base not 1 or n, a side below SSW_SSIM_MIN_SIDE (nothing is
+   enqueued then); SSW_ERR_BAD_DIMS: an empty frame, a side above 2^31, nx ny >= 2^32. */
+enum { SSW_SSIM_MIN_SIDE = 8, SSW_SSIM_ONE = 1 << 30, SSW_SSIM_STATS = 2, SSW_SSIM_TILE_W = 252, SSW_SSIM_TILE_H = 60 };
+int ssw_ssim_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, size_t n_base, const uint8_t* dev_copies, size_t n, size_t w, size_t h,
+                  uint64_t* dev_stats, int32_t* dev_map);
 
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,

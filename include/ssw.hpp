@@ -430,6 +430,38 @@ inline std::vector<Quality> quality(Context& ctx, const ImageRgb8& original, con
     }
     return out;
 }
+// The structural similarity of a copy and its original (ssw_ssim_rgb8; include/ssw.h states the definition): the sum of the
+// windows' fixed-point values (SSW_SSIM_ONE = identical) and the worst window with the pixel of its upper left corner; the mean
+// is the caller's arithmetic on them.
+struct Ssim {
+    int64_t sum = 0;
+    int32_t worst = 0;
+    uint32_t worst_x = 0, worst_y = 0;
+    uint64_t windows = 0;
+    double mean() const { return windows ? (double)sum / ((double)SSW_SSIM_ONE * (double)windows) : 0.0; }
+    double worst_value() const { return (double)worst / (double)SSW_SSIM_ONE; }
+};
+// ssw_ssim_rgb8 on host images: every copy against the one original.  No side below SSW_SSIM_MIN_SIDE.
+inline std::vector<Ssim> ssim(Context& ctx, const ImageRgb8& original, const std::vector<const ImageRgb8*>& copies) {
+    const size_t n = copies.size(), w = original.width, h = original.height, fb = w * h * 3;
+    if (w < SSW_SSIM_MIN_SIDE || h < SSW_SSIM_MIN_SIDE) throw Error(SSW_ERR_BAD_ARG, "ssim");
+    const size_t nx = w / 4 - 1, ny = h / 4 - 1;
+    detail::DeviceFrames base(ctx.get(), fb, "ssim"), dev(ctx.get(), n * fb, "ssim"), st(ctx.get(), n * SSW_SSIM_STATS * sizeof(uint64_t), "ssim");
+    base.put({&original}, w, h, "ssim");
+    dev.put(copies, w, h, "ssim");
+    check(ssw_ssim_rgb8(ctx.get(), base.p, 1, dev.p, n, w, h, reinterpret_cast<uint64_t*>(st.p), nullptr), "ssim");
+    std::vector<uint64_t> raw(n * SSW_SSIM_STATS);
+    check(ssw_copy_to_host(ctx.get(), raw.data(), st.p, raw.size() * sizeof(uint64_t)), "ssim");
+    std::vector<Ssim> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t key = raw[i * SSW_SSIM_STATS + 1], index = key & 0xFFFFFFFFull;
+        out[i].sum = (int64_t)raw[i * SSW_SSIM_STATS];
+        out[i].worst = (int32_t)((int64_t)(key >> 32) - SSW_SSIM_ONE);
+        out[i].worst_x = (uint32_t)(index % nx * 4); out[i].worst_y = (uint32_t)(index / nx * 4);
+        out[i].windows = nx * ny;
+    }
+    return out;
+}
 // ssw_collude_rgb8 on host images of one size: one forged frame per coalition, in order.
 inline std::vector<ImageRgb8> collude(Context& ctx, const std::vector<const ImageRgb8*>& copies, const std::vector<Coalition>& coalitions) {
     if (copies.empty()) throw Error(SSW_ERR_BAD_ARG, "collude");

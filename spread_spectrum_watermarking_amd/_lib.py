@@ -78,6 +78,10 @@ class JpegJob(C.Structure):
 
 JPEG_MIN_SIDE = 8            # ssw_jpeg_rgb8 refuses smaller frames
 QUALITY_STATS = 6            # ssw_quality_rgb8: u64 per copy -- SSE of R, G, B, SSE of the luma, changed bytes, max |d|
+SSIM_MIN_SIDE = 8            # ssw_ssim_rgb8 refuses smaller frames
+SSIM_ONE = 1 << 30           # the fixed-point value of two identical windows
+SSIM_STATS = 2               # u64 per copy: the sum of the windows' values (signed), (worst value + SSIM_ONE) << 32 | its index
+SSIM_TILE_W, SSIM_TILE_H = 252, 60     # pixels of windows a block of ssim_kernel owns
 
 _vp, _f32p, _u32p, _u64p, _sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t
 _cfgp = C.POINTER(Config)
@@ -173,6 +177,7 @@ SIGNATURES = {
     "ssw_quality_rgb8": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64p]),
     "ssw_collude_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(Coalition), _sz, _vp]),
     "ssw_jpeg_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(JpegJob), _sz, _vp]),
+    "ssw_ssim_rgb8": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64p, _vp]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
                                                            _f32p, _f32p, _u32p, _f32p, _u32p]),
     "ssw_reader_trace_restored_host_rgb8": (C.c_int, [_vp, _vp, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float, _f32p, _f32p, _u32p,

@@ -1174,6 +1174,83 @@ def quality(base, copies, ctx: Optional[Context] = None) -> list:
     return out
 
 
+@dataclass
+class Ssim:
+    """The structural similarity of one copy and its original (ssw_ssim_rgb8; include/ssw.h states the definition): the sum of
+    the windows' fixed-point values (2^30 = identical), the worst window's value and index (wy * windows_x + wx; the first of
+    equal ones) -- integers; the derived figures are the caller's arithmetic and are made here.  map: int32
+    [windows_y, windows_x], the value of every window, when it was asked for."""
+    sum: int
+    worst: int
+    worst_index: int
+    windows_x: int
+    windows_y: int
+    map: Optional[np.ndarray] = None
+
+    @property
+    def mean(self) -> float:
+        return self.sum / (L.SSIM_ONE * self.windows_x * self.windows_y)
+
+    @property
+    def worst_value(self) -> float:
+        return self.worst / L.SSIM_ONE
+
+    @property
+    def worst_position(self) -> Tuple[int, int]:
+        """pixel (x, y) of the worst window's upper left corner; the window is 8 x 8"""
+        return 4 * (self.worst_index % self.windows_x), 4 * (self.worst_index // self.windows_x)
+
+
+def _ssim_windows(w: int, h: int) -> Tuple[int, int]:
+    return w // 4 - 1, h // 4 - 1
+
+
+def _ssims(stats: np.ndarray, nx: int, ny: int, maps=None) -> list:
+    """stats: u64 [n, 2] as ssw_ssim_rgb8 writes them"""
+    stats = np.ascontiguousarray(stats, np.uint64)
+    return [Ssim(int(s), (int(key) >> 32) - L.SSIM_ONE, int(key) & 0xFFFFFFFF, nx, ny, None if maps is None else maps[i])
+            for i, (s, key) in enumerate(zip(stats.view(np.int64)[:, 0], stats[:, 1]))]
+
+
+def _ssim_frames(images, what: str) -> list:
+    frames = _frames_u8(images, what)
+    if frames and min(frames[0].shape[:2]) < L.SSIM_MIN_SIDE:
+        raise ValueError(f"{what}: SSIM needs frames of at least {L.SSIM_MIN_SIDE} x {L.SSIM_MIN_SIDE} pixels")
+    return frames
+
+
+def ssim(base, copies, ctx: Optional[Context] = None, maps: bool = False) -> list:
+    """One `Ssim` per copy.  base: the original, 8-bit [H, W, 3] -- or one original per copy (a list, or [n, H, W, 3]);
+    copies: 8-bit images of that size, no side below 8.  maps: also the value of every window, as `Ssim.map`.  One
+    ssw_ssim_rgb8 call per group of at most 256 MiB of frames."""
+    cp = _ssim_frames(copies, "ssim")
+    if not cp:
+        return []
+    b = np.asarray(base) if not isinstance(base, (list, tuple)) else None
+    bases = _frames_u8([base] if b is not None and b.ndim == 3 else base, "ssim")
+    if len(bases) not in (1, len(cp)) or bases[0].shape != cp[0].shape:
+        raise ValueError("ssim: one original of the copies' size, or one per copy")
+    ctx = ctx or default_context()
+    h, w = cp[0].shape[:2]
+    (nx, ny), fb, n, shared = _ssim_windows(w, h), w * h * 3, len(cp), len(bases) == 1
+    per = max(1, UPLOAD_GROUP_BYTES // (fb if shared else 2 * fb))
+    dev_c, dev_s = ctx.alloc(min(per, n) * fb), ctx.alloc(min(per, n) * 8 * L.SSIM_STATS)
+    dev_b = ctx.to_device(bases[0]) if shared else ctx.alloc(min(per, n) * fb)
+    dev_m = ctx.alloc(min(per, n) * nx * ny * 4) if maps else None
+    out = []
+    for g0 in range(0, n, per):
+        g = cp[g0:g0 + per]
+        _upload_frames(ctx, dev_c, g)
+        if not shared:
+            _upload_frames(ctx, dev_b, bases[g0:g0 + per])
+        check(ctx._lib.ssw_ssim_rgb8(ctx.handle, dev_b.ptr, 1 if shared else len(g), dev_c.ptr, len(g), w, h, dev_s.ptr, dev_m.ptr if maps else None),
+              "ssw_ssim_rgb8")
+        out += _ssims(dev_s.to_host(np.uint64, (len(g), L.SSIM_STATS)), nx, ny, dev_m.to_host(np.int32, (len(g), ny, nx)) if maps else None)
+    for d in (dev_c, dev_s, dev_b) + ((dev_m,) if maps else ()):
+        d.free()
+    return out
+
+
 def _coalition(method, members, n_copies: int) -> L.Coalition:
     m = L.COLLUDE_METHODS.get(method.lower()) if isinstance(method, str) else int(method)
     if m is None or m not in L.COLLUDE_METHODS.values():
@@ -1280,7 +1357,7 @@ class JpegResult:
     """What tracing made of the marked copies after a JPEG of `quality`.  survived: copies whose own mark still exceeds the
     threshold; weakest_own: the smallest similarity of a copy with its own mark; strongest_innocent: the largest with another
     recipient's (NaN when there is one copy); accused: (copy, other mark) pairs above the threshold; psnr_min / psnr_max: the
-    compressed copies against the original, in dB."""
+    compressed copies against the original, in dB; ssim_min / ssim_max: their mean SSIM (NaN unless the report was asked for it)."""
     quality: int
     survived: int
     weakest_own: float
@@ -1288,16 +1365,19 @@ class JpegResult:
     accused: int
     psnr_min: float
     psnr_max: float
+    ssim_min: float = math.nan
+    ssim_max: float = math.nan
 
 
 @dataclass
 class StrengthRow:
     """`strength_report` for one alpha: the `Quality` of every copy, one `Collusion` per (method, size), methods outermost, and
-    one `JpegResult` per JPEG quality asked for."""
+    one `JpegResult` per JPEG quality asked for; ssim: the `Ssim` of every copy when the report was asked for it."""
     alpha: float
     quality: list
     collusions: list
     jpeg: list = field(default_factory=list)
+    ssim: list = field(default_factory=list)
 
     def collusion(self, method: str, size: int) -> Collusion:
         return next(c for c in self.collusions if (c.method, c.size) == (method, size))
@@ -1310,18 +1390,19 @@ def _collusion(method: str, size: int, sims: np.ndarray, threshold: float) -> Co
                      int(over[:size].sum()), int(over[size:].sum()))
 
 
-def _jpeg_result(quality: int, sims: np.ndarray, qualities: list, threshold: float) -> JpegResult:
+def _jpeg_result(quality: int, sims: np.ndarray, qualities: list, threshold: float, ssims=()) -> JpegResult:
     """sims [copies][copies]: row c is copy c after the JPEG against every mark"""
+    mean = [s.mean for s in ssims] or [math.nan]
     own, others = np.diagonal(sims), sims[~np.eye(len(sims), dtype=bool)]
     over = sims > np.float32(threshold)                      # NaN never exceeds (algorithm.rs:677)
     psnr = [q.psnr for q in qualities]
     return JpegResult(quality, int(np.diagonal(over).sum()), float(own.min()), float(others.max()) if others.size else math.nan,
-                      int(over.sum() - np.diagonal(over).sum()), min(psnr), max(psnr))
+                      int(over.sum() - np.diagonal(over).sum()), min(psnr), max(psnr), min(mean), max(mean))
 
 
 def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                     methods=("average", "median", "min", "max", "minmax", "mosaic"), threshold: float = 6.0,
-                    config: Optional[WriteConfig] = None, seed=None, ctx: Optional[Context] = None, jpeg=()) -> list:
+                    config: Optional[WriteConfig] = None, seed=None, ctx: Optional[Context] = None, jpeg=(), ssim: bool = False) -> list:
     """The two questions to answer before a copy ships, per insertion strength: how visible is the mark, and how many
     recipients must pool their copies before tracing fails?  For each alpha (`config` with its alpha replaced; the default
     Option2 + Energy): `copies` marked copies of the 8-bit `image` (ssw_fingerprint_embed_rgb8), their distance from it
@@ -1331,9 +1412,13 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     .standard_normal((copies, k)).astype(float32), the same for every alpha.  jpeg: JPEG qualities (1 .. 100); per alpha every
     copy is compressed at every quality (one ssw_jpeg_rgb8 call), all results are traced against all marks (one more
     ssw_fingerprint_trace_rgb8 call) and measured against the original (one more ssw_quality_rgb8 call): one `JpegResult` per
-    quality in `StrengthRow.jpeg`.  Returns one `StrengthRow` per alpha."""
+    quality in `StrengthRow.jpeg`.  ssim: also the structural similarity of every copy and its original (one ssw_ssim_rgb8 call per
+    alpha, `StrengthRow.ssim`; one more on the JPEG results, `JpegResult.ssim_min` / `ssim_max`); no side below 8 then.
+    Returns one `StrengthRow` per alpha."""
     jq = _jpeg_qualities(jpeg, "strength_report")
     img = (_jpeg_frames if jq else _frames_u8)([image], "strength_report")[0]
+    if ssim:
+        _ssim_frames([img], "strength_report")
     sizes, methods = [int(c) for c in sizes], [str(m).lower() for m in methods]
     if any(c > copies for c in sizes):
         raise ValueError("strength_report: a coalition cannot be larger than the number of copies")
@@ -1352,6 +1437,8 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     nj = len(jq) * copies                                      # JPEG results of an alpha, quality-major
     jobs = (L.JpegJob * max(nj, 1))(*[L.JpegJob(c, q) for q in jq for c in range(copies)])
     dev_jpeg = [ctx.alloc(nj * fb), ctx.alloc(nj * k * 4), ctx.alloc(nj * copies * 4), ctx.alloc(nj * 8 * L.QUALITY_STATS)] if nj else []
+    dev_ssim = [ctx.alloc(max(copies, nj) * 8 * L.SSIM_STATS)] if ssim else []
+    windows = _ssim_windows(w, h)
     lib, rows = ctx._lib, []
     for alpha in alphas:
         cfg = L.Config(config.ordering.tag, config.insertion.tag, float(alpha), config.precision)
@@ -1366,6 +1453,9 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
             sims = dev_sims.to_host(np.float32, (nf, copies))
         q = _qualities(dev_stats.to_host(np.uint64, (copies, L.QUALITY_STATS)), w * h)
         rows.append(StrengthRow(float(alpha), q, [_collusion(m, c, sims[i], threshold) for i, (m, c) in enumerate(plan)]))
+        if ssim:
+            check(lib.ssw_ssim_rgb8(ctx.handle, dev_img.ptr, 1, dev_copies.ptr, copies, w, h, dev_ssim[0].ptr, None), "ssw_ssim_rgb8")
+            rows[-1].ssim = _ssims(dev_ssim[0].to_host(np.uint64, (copies, L.SSIM_STATS)), *windows)
         if nj:
             dev_frames, dev_jext, dev_jsims, dev_jstats = dev_jpeg
             check(lib.ssw_jpeg_rgb8(ctx.handle, dev_copies.ptr, copies, w, h, jobs, nj, dev_frames.ptr), "ssw_jpeg_rgb8")
@@ -1374,8 +1464,13 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
             check(lib.ssw_quality_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, nj, w, h, dev_jstats.ptr), "ssw_quality_rgb8")
             jsims = dev_jsims.to_host(np.float32, (len(jq), copies, copies))
             jstats = _qualities(dev_jstats.to_host(np.uint64, (nj, L.QUALITY_STATS)), w * h)
-            rows[-1].jpeg = [_jpeg_result(qu, jsims[i], jstats[i * copies:(i + 1) * copies], threshold) for i, qu in enumerate(jq)]
-    for d in [dev_img, dev_marks, dev_copies, dev_stats, dev_forged, dev_ext, dev_sims] + dev_jpeg:
+            jssim = []
+            if ssim:
+                check(lib.ssw_ssim_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, nj, w, h, dev_ssim[0].ptr, None), "ssw_ssim_rgb8")
+                jssim = _ssims(dev_ssim[0].to_host(np.uint64, (nj, L.SSIM_STATS)), *windows)
+            rows[-1].jpeg = [_jpeg_result(qu, jsims[i], jstats[i * copies:(i + 1) * copies], threshold, jssim[i * copies:(i + 1) * copies])
+                             for i, qu in enumerate(jq)]
+    for d in [dev_img, dev_marks, dev_copies, dev_stats, dev_forged, dev_ext, dev_sims] + dev_jpeg + dev_ssim:
         d.free()
     return rows
 

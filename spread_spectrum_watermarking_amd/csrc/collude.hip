@@ -21,6 +21,7 @@
 //                    one member a pixel takes.
 #include <algorithm>
 
+#include "rgb_groups.hpp"
 #include "ssw_host.hpp"
 
 namespace ssw {
@@ -45,7 +46,6 @@ __device__ inline uint32_t pk_max(uint32_t a, uint32_t b) {
 
 // twelve bytes at p as six registers of two bytes each: e[k] = bytes 4k, 4k + 2; o[k] = bytes 4k + 1, 4k + 3
 struct Planes { uint32_t e[3], o[3]; };
-__device__ inline void load12(const uint8_t* __restrict__ p, uint32_t (&v)[3]) { __builtin_memcpy(v, p, 12); }
 __device__ inline Planes planes(const uint32_t (&v)[3]) {
     Planes r;
 #pragma unroll
@@ -60,17 +60,6 @@ __device__ inline void store12(uint8_t* __restrict__ p, const Planes& r) {
 }
 
 // ---- quality ---------------------------------------------------------------------------------------------------------------------
-__device__ inline uint32_t luma(uint32_t r, uint32_t g, uint32_t b) { return (77u * r + 150u * g + 29u * b + 128u) >> 8; }
-__device__ inline uint32_t dot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }
-// the lumas of the four pixels of a group: weights 77, 150, 29 on three consecutive bytes
-__device__ inline void luma4(const uint32_t (&v)[3], uint32_t (&l)[4]) {
-    const uint32_t p1 = (uint32_t)((((uint64_t)v[1] << 32) | v[0]) >> 24), p2 = (uint32_t)((((uint64_t)v[2] << 32) | v[1]) >> 16);
-    l[0] = dot4(v[0], 0x001D964Du, 128u) >> 8;
-    l[1] = dot4(p1, 0x001D964Du, 128u) >> 8;
-    l[2] = dot4(p2, 0x001D964Du, 128u) >> 8;
-    l[3] = dot4(v[2], 0x1D964D00u, 128u) >> 8;
-}
-
 struct QStat { uint32_t sse[3], luma, changed, max2; };      // max2: the maximum as two 16-bit lanes
 
 __device__ inline void quality_group(const Planes& b, const uint32_t (&bl)[4], const uint32_t (&cv)[3], QStat& s) {
