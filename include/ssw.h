@@ -785,6 +785,41 @@ int ssw_jpeg_rgb8(ssw_ctx* ctx, const uint8_t* dev_frames, size_t n_frames, size
 enum { SSW_SSIM_MIN_SIDE = 8, SSW_SSIM_ONE = 1 << 30, SSW_SSIM_STATS = 2, SSW_SSIM_TILE_W = 252, SSW_SSIM_TILE_H = 60 };
 int ssw_ssim_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, size_t n_base, const uint8_t* dev_copies, size_t n, size_t w, size_t h,
                   uint64_t* dev_stats, int32_t* dev_map);
+/* The attacks of a photo editor's filter menu: dev_out[j] [h][w][3] is frame jobs[j].frame of dev_frames [n_frames][h][w][3]
+   after a Gaussian blur, an unsharp mask or a 3 x 3 median -- exactly what Pillow's ImageFilter.GaussianBlur(radius),
+   UnsharpMask(radius, percent, threshold) and MedianFilter(3) give.  They are integer arithmetic on the bytes; the numpy
+   restatement in tests/test_filter_cpu.py (`filter_ref`, checked there against Pillow byte for byte) is what the call equals.
+   Every channel is filtered on its own.  clamp(i) = min(max(i, 0), n - 1) against the FRAME, applied anew in every pass.
+     SSW_FILTER_BLUR(radius)   radius is the Gaussian's sigma, a float.  In float arithmetic, every operation rounded to float
+              (the square root and the floor are taken in double and rounded), as Pillow's C does:
+                s2 = radius * radius / 3          L = sqrt(12.0 * s2 + 1.0)          l = floor((L - 1.0) / 2.0)
+                a = (2 l + 1) * (l * (l + 1) - 3 * s2)     a = a / (6 * (s2 - (l + 1) * (l + 1)))     rho = l + a
+              then r = (int) rho, ww = (uint32) (16777216.0f / (rho * 2 + 1)), fw = (2^24 - (2 r + 1) ww) / 2 in integers.
+              One box pass along a line of n samples:
+                out[x] = (ww * sum_{|d| <= r} in[clamp(x + d)] + fw * (in[clamp(x - r - 1)] + in[clamp(x + r + 1)]) + 2^23) >> 24
+              stored as a byte.  BLUR is three such passes along the rows, then three along the columns: six roundings to bytes.
+              The weights sum to at most 2^24, so every intermediate fits 32 bits unsigned (at most 255 * 2^24 + 2^23).
+              0 < radius <= 8.0 keeps r <= 7: a pass reaches 8 samples, three passes 24.  Radius 8.0: rho = 7.46875, r = 7,
+              ww = 1052688, fw = 493448; radius 1.0: r = 0, ww = 11184811, fw = 2796202.  (r, ww, fw) are made on the host and
+              travel as kernel arguments.
+     SSW_FILTER_UNSHARP(radius, percent, threshold)   b = BLUR(radius) of the frame, d = in - b per byte; where |d| > threshold
+              (strictly) out = min(max(in + d * percent / 100, 0), 255), the division truncating toward zero as in C; elsewhere
+              out = in.  1 <= percent <= 1000, 0 <= threshold <= 255; Pillow's defaults are (2, 150, 3).
+     SSW_FILTER_MEDIAN3   the fifth smallest of the 3 x 3 neighbourhood, indices clamped (the edge is repeated).
+   Fields a kind does not use must be 0.  `jobs` is a HOST array; a frame may occur in many jobs and in any order; dev_out holds
+   n_jobs frames in job order and must not overlap dev_frames.  The call only enqueues on the context's stream (no host
+   synchronisation); the jobs go in groups of at most 16, and the row-blurred planes of a group's BLUR / UNSHARP jobs (3 bytes per
+   pixel and job, at most 64 MiB or one job's) are the context's workspace.  No alignment is assumed of any pointer or of
+   w * 3, and no minimum side: clamping defines everything from 1 x 1 on.  Timed under SSW_STAGE_CONVERT; work: per job
+   2 * 3 w h bytes whatever the kind, one frame in and one out (a blur moves twice that, through the plane, and UNSHARP reads the
+   frame once more).  n_jobs == 0 is checked first: SSW_OK; SSW_ERR_BAD_ARG: a null pointer, frame >= n_frames, an unknown kind,
+   a radius outside (0, 8] or not finite, a percent outside 1 .. 1000, a threshold above 255, a non-zero unused field (nothing
+   is enqueued when any job is bad); SSW_ERR_BAD_DIMS: a side of 0 or above 65535.
+   Medians larger than 3 x 3, Pillow's kernel filters and BoxBlur, radii per axis, RGBA or grey frames are not offered. */
+typedef enum ssw_filter_kind { SSW_FILTER_BLUR = 0, SSW_FILTER_UNSHARP = 1, SSW_FILTER_MEDIAN3 = 2 } ssw_filter_kind;
+typedef struct ssw_filter_job { uint32_t frame; uint32_t kind; float radius; uint32_t percent; uint32_t threshold; } ssw_filter_job;
+int ssw_filter_rgb8(ssw_ctx* ctx, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h, const ssw_filter_job* jobs,
+                    size_t n_jobs, uint8_t* dev_out);
 
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,

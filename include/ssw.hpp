@@ -508,6 +508,37 @@ inline std::vector<ImageRgb8> jpeg(Context& ctx, const std::vector<const ImageRg
     return out;
 }
 
+// One result of wm::filter: a frame (an index into the images) and one of the three filters of ssw_filter_rgb8
+struct FilterJob {
+    uint32_t frame = 0;
+    uint32_t kind = SSW_FILTER_MEDIAN3;
+    float radius = 0.0f;                  // blur, unsharp: the Gaussian's sigma, 0 < radius <= 8
+    uint32_t percent = 0, threshold = 0;  // unsharp: 1 .. 1000 and 0 .. 255
+    static FilterJob blur(uint32_t frame, float radius) { return FilterJob{frame, SSW_FILTER_BLUR, radius, 0, 0}; }
+    static FilterJob unsharp(uint32_t frame, float radius = 2.0f, uint32_t percent = 150, uint32_t threshold = 3) {
+        return FilterJob{frame, SSW_FILTER_UNSHARP, radius, percent, threshold};
+    }
+    static FilterJob median(uint32_t frame) { return FilterJob{frame, SSW_FILTER_MEDIAN3, 0.0f, 0, 0}; }
+};
+// ssw_filter_rgb8 on host images of one size: per job that frame after a Gaussian blur, an unsharp mask or a 3 x 3 median -- what
+// Pillow's filters of those names give, byte for byte; include/ssw.h states the definitions.
+inline std::vector<ImageRgb8> filter(Context& ctx, const std::vector<const ImageRgb8*>& frames, const std::vector<FilterJob>& jobs) {
+    if (frames.empty()) throw Error(SSW_ERR_BAD_ARG, "filter");
+    const size_t n = frames.size(), m = jobs.size(), w = frames[0]->width, h = frames[0]->height, fb = w * h * 3;
+    std::vector<ssw_filter_job> jb(m);
+    for (size_t i = 0; i < m; ++i) jb[i] = ssw_filter_job{jobs[i].frame, jobs[i].kind, jobs[i].radius, jobs[i].percent, jobs[i].threshold};
+    detail::DeviceFrames dev(ctx.get(), n * fb, "filter"), filtered(ctx.get(), m * fb, "filter");
+    dev.put(frames, w, h, "filter");
+    check(ssw_filter_rgb8(ctx.get(), dev.p, n, w, h, jb.data(), m, filtered.p), "filter");
+    std::vector<ImageRgb8> out(m);
+    for (size_t i = 0; i < m; ++i) {
+        out[i].width = w; out[i].height = h;
+        out[i].data.resize(fb);
+        check(ssw_copy_to_host(ctx.get(), out[i].data.data(), filtered.p + i * fb, fb), "filter");
+    }
+    return out;
+}
+
 // The originals someone owns, as signatures: which of them is a suspect a copy of?  The stage in front of locate / Reader::trace
 // (ssw_signature_match; include/ssw.h states the definition and what it cannot find: cut-outs, mirrored and turned copies).
 // The signatures stay on the device between match calls and go up again only after an add.

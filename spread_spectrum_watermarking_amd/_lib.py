@@ -77,6 +77,16 @@ class JpegJob(C.Structure):
 
 
 JPEG_MIN_SIDE = 8            # ssw_jpeg_rgb8 refuses smaller frames
+
+
+class FilterJob(C.Structure):
+    """ssw_filter_job (include/ssw.h): one result of ssw_filter_rgb8 -- a frame of the call, a kind and its parameters; the
+    fields a kind does not use are 0."""
+    _fields_ = [("frame", C.c_uint32), ("kind", C.c_uint32), ("radius", C.c_float), ("percent", C.c_uint32), ("threshold", C.c_uint32)]
+
+
+FILTER_BLUR, FILTER_UNSHARP, FILTER_MEDIAN3 = range(3)
+FILTER_RADIUS_MAX = 8.0      # keeps the box radius of a blur pass at 7 or below
 QUALITY_STATS = 6            # ssw_quality_rgb8: u64 per copy -- SSE of R, G, B, SSE of the luma, changed bytes, max |d|
 SSIM_MIN_SIDE = 8            # ssw_ssim_rgb8 refuses smaller frames
 SSIM_ONE = 1 << 30           # the fixed-point value of two identical windows
@@ -177,6 +187,7 @@ SIGNATURES = {
     "ssw_quality_rgb8": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64p]),
     "ssw_collude_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(Coalition), _sz, _vp]),
     "ssw_jpeg_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(JpegJob), _sz, _vp]),
+    "ssw_filter_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(FilterJob), _sz, _vp]),
     "ssw_ssim_rgb8": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64p, _vp]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
                                                            _f32p, _f32p, _u32p, _f32p, _u32p]),

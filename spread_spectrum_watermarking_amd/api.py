@@ -1339,6 +1339,92 @@ def jpeg(images, qualities, ctx: Optional[Context] = None) -> list:
     return [flat[i * len(qs):(i + 1) * len(qs)] for i in range(len(frames))]
 
 
+@dataclass(frozen=True)
+class Filter:
+    """One attack of ssw_filter_rgb8 (include/ssw.h states the definitions; they are Pillow's): make it with `Filter.blur`,
+    `Filter.unsharp` or `Filter.median`.  `label` names it in reports: "blur 1.5", "unsharp 2,150,3", "median 3"."""
+    kind: int
+    radius: float = 0.0
+    percent: int = 0
+    threshold: int = 0
+
+    @staticmethod
+    def _radius(radius) -> float:
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+            raise ValueError("Filter: the radius is a number")
+        r = float(np.float32(radius)) if math.isfinite(radius) else math.nan
+        if not 0.0 < r <= L.FILTER_RADIUS_MAX:                   # NaN fails too
+            raise ValueError(f"Filter: a radius above 0 and at most {L.FILTER_RADIUS_MAX:g}")
+        return r
+
+    @classmethod
+    def blur(cls, radius) -> "Filter":
+        """ImageFilter.GaussianBlur(radius): radius is the Gaussian's sigma, 0 < radius <= 8"""
+        return cls(L.FILTER_BLUR, cls._radius(radius))
+
+    @classmethod
+    def unsharp(cls, radius=2, percent=150, threshold=3) -> "Filter":
+        """ImageFilter.UnsharpMask(radius, percent, threshold): percent 1 .. 1000, threshold 0 .. 255"""
+        for v, lo, hi, what in ((percent, 1, 1000, "percent"), (threshold, 0, 255, "threshold")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"Filter: an unsharp mask's {what} is an integer {lo} .. {hi}")
+        return cls(L.FILTER_UNSHARP, cls._radius(radius), int(percent), int(threshold))
+
+    @classmethod
+    def median(cls) -> "Filter":
+        """ImageFilter.MedianFilter(3)"""
+        return cls(L.FILTER_MEDIAN3)
+
+    @property
+    def label(self) -> str:
+        if self.kind == L.FILTER_BLUR:
+            return f"blur {self.radius:g}"
+        if self.kind == L.FILTER_UNSHARP:
+            return f"unsharp {self.radius:g},{self.percent},{self.threshold}"
+        return "median 3"
+
+    def job(self, frame: int) -> L.FilterJob:
+        return L.FilterJob(frame, self.kind, self.radius, self.percent, self.threshold)
+
+
+def _filters(filters, what: str) -> list:
+    fs = list(filters)
+    if any(not isinstance(f, Filter) for f in fs):
+        raise ValueError(f"{what}: filters are made with Filter.blur, Filter.unsharp or Filter.median")
+    return fs
+
+
+def filter(images, filters, ctx: Optional[Context] = None) -> list:
+    """Every image under every filter (ssw_filter_rgb8; include/ssw.h states the definitions): what Pillow's GaussianBlur,
+    UnsharpMask and MedianFilter(3) give, byte for byte.  images: 8-bit [H, W, 3] of one size, any size; filters: `Filter`
+    objects.  Returns [len(images)][len(filters)] u8 [H, W, 3] frames.  The jobs go in groups whose frames and results are at
+    most 256 MiB on the device."""
+    frames, fs = _frames_u8(images, "filter"), _filters(filters, "filter")
+    if not frames or not fs:
+        return [[] for _ in frames]
+    ctx = ctx or default_context()
+    h, w = frames[0].shape[:2]
+    fb, jobs, flat = w * h * 3, [(i, f) for i in range(len(frames)) for f in fs], []
+    g0 = 0
+    while g0 < len(jobs):
+        used, g1 = [], g0                                     # the jobs are in frame order: a group's frames are a run
+        while g1 < len(jobs):
+            new = not used or used[-1] != jobs[g1][0]
+            if g1 > g0 and (len(used) + new + g1 - g0 + 1) * fb > UPLOAD_GROUP_BYTES:
+                break
+            if new:
+                used.append(jobs[g1][0])
+            g1 += 1
+        local = (L.FilterJob * (g1 - g0))(*[f.job(i - used[0]) for i, f in jobs[g0:g1]])
+        dev_f, dev_o = ctx.alloc(len(used) * fb), ctx.alloc((g1 - g0) * fb)
+        _upload_frames(ctx, dev_f, [frames[i] for i in used])
+        check(ctx._lib.ssw_filter_rgb8(ctx.handle, dev_f.ptr, len(used), w, h, local, g1 - g0, dev_o.ptr), "ssw_filter_rgb8")
+        flat += list(dev_o.to_host(np.uint8, (g1 - g0, h, w, 3)))
+        dev_f.free(); dev_o.free()
+        g0 = g1
+    return [flat[i * len(fs):(i + 1) * len(fs)] for i in range(len(frames))]
+
+
 @dataclass
 class Collusion:
     """What tracing made of one forgery: `size` colluders (the first `size` copies) pooled with `method`.  weakest_colluder: the
@@ -1370,14 +1456,30 @@ class JpegResult:
 
 
 @dataclass
+class FilterResult:
+    """What tracing made of the marked copies after the filter `filter` (a `Filter.label`); the other fields as in `JpegResult`."""
+    filter: str
+    survived: int
+    weakest_own: float
+    strongest_innocent: float
+    accused: int
+    psnr_min: float
+    psnr_max: float
+    ssim_min: float = math.nan
+    ssim_max: float = math.nan
+
+
+@dataclass
 class StrengthRow:
     """`strength_report` for one alpha: the `Quality` of every copy, one `Collusion` per (method, size), methods outermost, and
-    one `JpegResult` per JPEG quality asked for; ssim: the `Ssim` of every copy when the report was asked for it."""
+    one `JpegResult` per JPEG quality asked for; ssim: the `Ssim` of every copy when the report was asked for it; filters: one
+    `FilterResult` per filter asked for."""
     alpha: float
     quality: list
     collusions: list
     jpeg: list = field(default_factory=list)
     ssim: list = field(default_factory=list)
+    filters: list = field(default_factory=list)
 
     def collusion(self, method: str, size: int) -> Collusion:
         return next(c for c in self.collusions if (c.method, c.size) == (method, size))
@@ -1400,9 +1502,15 @@ def _jpeg_result(quality: int, sims: np.ndarray, qualities: list, threshold: flo
                       int(over.sum() - np.diagonal(over).sum()), min(psnr), max(psnr), min(mean), max(mean))
 
 
+def _filter_result(label: str, sims: np.ndarray, qualities: list, threshold: float, ssims=()) -> FilterResult:
+    j = _jpeg_result(0, sims, qualities, threshold, ssims)
+    return FilterResult(label, j.survived, j.weakest_own, j.strongest_innocent, j.accused, j.psnr_min, j.psnr_max, j.ssim_min, j.ssim_max)
+
+
 def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                     methods=("average", "median", "min", "max", "minmax", "mosaic"), threshold: float = 6.0,
-                    config: Optional[WriteConfig] = None, seed=None, ctx: Optional[Context] = None, jpeg=(), ssim: bool = False) -> list:
+                    config: Optional[WriteConfig] = None, seed=None, ctx: Optional[Context] = None, jpeg=(), ssim: bool = False,
+                    filters=()) -> list:
     """The two questions to answer before a copy ships, per insertion strength: how visible is the mark, and how many
     recipients must pool their copies before tracing fails?  For each alpha (`config` with its alpha replaced; the default
     Option2 + Energy): `copies` marked copies of the 8-bit `image` (ssw_fingerprint_embed_rgb8), their distance from it
@@ -1414,8 +1522,11 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     ssw_fingerprint_trace_rgb8 call) and measured against the original (one more ssw_quality_rgb8 call): one `JpegResult` per
     quality in `StrengthRow.jpeg`.  ssim: also the structural similarity of every copy and its original (one ssw_ssim_rgb8 call per
     alpha, `StrengthRow.ssim`; one more on the JPEG results, `JpegResult.ssim_min` / `ssim_max`); no side below 8 then.
+    filters: `Filter` objects; per alpha every copy goes through every filter (one ssw_filter_rgb8 call, filter-major), all
+    results are traced against all marks and measured against the original (one more ssw_fingerprint_trace_rgb8 and
+    ssw_quality_rgb8 call, and one ssw_ssim_rgb8 with `ssim`): one `FilterResult` per filter in `StrengthRow.filters`.
     Returns one `StrengthRow` per alpha."""
-    jq = _jpeg_qualities(jpeg, "strength_report")
+    jq, fl = _jpeg_qualities(jpeg, "strength_report"), _filters(filters, "strength_report")
     img = (_jpeg_frames if jq else _frames_u8)([image], "strength_report")[0]
     if ssim:
         _ssim_frames([img], "strength_report")
@@ -1437,7 +1548,10 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     nj = len(jq) * copies                                      # JPEG results of an alpha, quality-major
     jobs = (L.JpegJob * max(nj, 1))(*[L.JpegJob(c, q) for q in jq for c in range(copies)])
     dev_jpeg = [ctx.alloc(nj * fb), ctx.alloc(nj * k * 4), ctx.alloc(nj * copies * 4), ctx.alloc(nj * 8 * L.QUALITY_STATS)] if nj else []
-    dev_ssim = [ctx.alloc(max(copies, nj) * 8 * L.SSIM_STATS)] if ssim else []
+    nfl = len(fl) * copies                                     # filtered copies of an alpha, filter-major
+    fjobs = (L.FilterJob * max(nfl, 1))(*[f.job(c) for f in fl for c in range(copies)])
+    dev_filter = [ctx.alloc(nfl * fb), ctx.alloc(nfl * k * 4), ctx.alloc(nfl * copies * 4), ctx.alloc(nfl * 8 * L.QUALITY_STATS)] if nfl else []
+    dev_ssim = [ctx.alloc(max(copies, nj, nfl) * 8 * L.SSIM_STATS)] if ssim else []
     windows = _ssim_windows(w, h)
     lib, rows = ctx._lib, []
     for alpha in alphas:
@@ -1470,7 +1584,21 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                 jssim = _ssims(dev_ssim[0].to_host(np.uint64, (nj, L.SSIM_STATS)), *windows)
             rows[-1].jpeg = [_jpeg_result(qu, jsims[i], jstats[i * copies:(i + 1) * copies], threshold, jssim[i * copies:(i + 1) * copies])
                              for i, qu in enumerate(jq)]
-    for d in [dev_img, dev_marks, dev_copies, dev_stats, dev_forged, dev_ext, dev_sims] + dev_jpeg + dev_ssim:
+        if nfl:
+            dev_frames, dev_fext, dev_fsims, dev_fstats = dev_filter
+            check(lib.ssw_filter_rgb8(ctx.handle, dev_copies.ptr, copies, w, h, fjobs, nfl, dev_frames.ptr), "ssw_filter_rgb8")
+            check(lib.ssw_fingerprint_trace_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, dev_frames.ptr, nfl, w, h, k, dev_marks.ptr, copies,
+                                                 C.c_float(threshold), dev_fext.ptr, dev_fsims.ptr, None, None, None), "ssw_fingerprint_trace_rgb8")
+            check(lib.ssw_quality_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, nfl, w, h, dev_fstats.ptr), "ssw_quality_rgb8")
+            fsims = dev_fsims.to_host(np.float32, (len(fl), copies, copies))
+            fstats = _qualities(dev_fstats.to_host(np.uint64, (nfl, L.QUALITY_STATS)), w * h)
+            fssim = []
+            if ssim:
+                check(lib.ssw_ssim_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, nfl, w, h, dev_ssim[0].ptr, None), "ssw_ssim_rgb8")
+                fssim = _ssims(dev_ssim[0].to_host(np.uint64, (nfl, L.SSIM_STATS)), *windows)
+            rows[-1].filters = [_filter_result(f.label, fsims[i], fstats[i * copies:(i + 1) * copies], threshold, fssim[i * copies:(i + 1) * copies])
+                                for i, f in enumerate(fl)]
+    for d in [dev_img, dev_marks, dev_copies, dev_stats, dev_forged, dev_ext, dev_sims] + dev_jpeg + dev_filter + dev_ssim:
         d.free()
     return rows
 

@@ -29,12 +29,14 @@
         -> `identify` for every suspect in one call, then the trace above once per original that was named, with the marks
            file the catalogue holds for it; every record gains an "Original:" line
     python -m spread_spectrum_watermarking_amd.cli strength <file> --alpha 0.02 0.05 0.1 [-n 1000] [--copies 8] [--collude 2 4]
-            [--method average median min max minmax mosaic] [--jpeg 90 75 50] [--ssim] [--similarity-exceed 6.0] [--json]
+            [--method average median min max minmax mosaic] [--jpeg 90 75 50] [--filter blur:1.5 median unsharp:2,150,3] [--ssim]
+            [--similarity-exceed 6.0] [--json]
         -> before a copy ships: per alpha the PSNR range of the marked copies (with --ssim also their mean SSIM and the worst
            8 x 8 window), and per collusion method and coalition size
            how many of the colluders a trace of their forgery still finds, the weakest colluder's and the strongest innocent
            recipient's similarity; with --jpeg, per quality what a trace still finds in every copy after it was saved as a
-           JPEG; everything stays on the GPU between the original going up and the numbers coming down
+           JPEG; with --filter the same after a Gaussian blur (blur:RADIUS), an unsharp mask (unsharp[:RADIUS[,PERCENT[,THRESHOLD]]])
+           or a 3 x 3 median (median), as Pillow's filters of those names do them; everything stays on the GPU between the original going up and the numbers coming down
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -49,12 +51,28 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from ._lib import COLLUDE_METHODS
-from .api import (IDENTIFY_MAX_DISTANCE, Catalogue, Locate, MarkBuf, Placement, Reader, Tester, TraceResult, Writer, identify, locate,
+from .api import (IDENTIFY_MAX_DISTANCE, Catalogue, Filter, Locate, MarkBuf, Placement, Reader, Tester, TraceResult, Writer, identify, locate,
                   strength_report)
 from .storage import Configuration, DescribedWatermark, Version1Storage
 
 _ORDERING_ARGS = {"energy": "Energy", "energy-orthogonal": "EnergyOrthogonal", "legacy": "Legacy"}
 _METHOD_ARGS = {"option1": "Option1", "option2": "Option2", "option3": "Option3"}
+
+
+def _filter_arg(text: str) -> Filter:
+    """blur:RADIUS | unsharp[:RADIUS[,PERCENT[,THRESHOLD]]] | median[:3]"""
+    name, _, rest = text.partition(":")
+    parts = rest.split(",") if rest else []
+    try:
+        if name == "blur" and len(parts) == 1:
+            return Filter.blur(float(parts[0]))
+        if name == "unsharp" and len(parts) <= 3:
+            return Filter.unsharp(*([float(parts[0])] if parts else []), *[int(v) for v in parts[1:]])
+        if name == "median" and parts in ([], ["3"]):
+            return Filter.median()
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"{text!r}: {e}") from e
+    raise argparse.ArgumentTypeError(f"{text!r}: blur:RADIUS, unsharp[:RADIUS[,PERCENT[,THRESHOLD]]] or median")
 
 
 def _rust_f32(x: float) -> str:
@@ -241,6 +259,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="If the similarity exceeds this value it is considered to be matching.")
     g.add_argument("--jpeg", type=int, nargs="+", default=[], metavar="Q",
                    help="Also compress every copy as a JPEG of these qualities (1 .. 100) and trace what is left.")
+    g.add_argument("--filter", type=_filter_arg, nargs="+", default=[], metavar="FILTER", dest="filters",
+                   help="Also put every copy through these filters and trace what is left: blur:RADIUS (0 < RADIUS <= 8), "
+                        "unsharp[:RADIUS[,PERCENT[,THRESHOLD]]] (default 2,150,3), median.")
     g.add_argument("--ssim", action="store_true", help="Also report the structural similarity (SSIM) of every copy and its worst window.")
     g.add_argument("--json", action="store_true", help="Print the report as one JSON document.")
     return p
@@ -384,7 +405,7 @@ def cmd_strength(args, out=None) -> int:
     orig = _open_image(args.file)
     try:
         rows = strength_report(orig, args.alpha, k=args.length, copies=args.copies, sizes=args.collude, methods=args.method,
-                               threshold=args.similarity_exceed, jpeg=args.jpeg, ssim=args.ssim)
+                               threshold=args.similarity_exceed, jpeg=args.jpeg, ssim=args.ssim, filters=args.filters)
     except ValueError as e:
         raise SystemExit(str(e)) from e
     if args.json:
@@ -398,7 +419,10 @@ def cmd_strength(args, out=None) -> int:
                                for c in r.collusions],
                 "jpeg": [{"quality": j.quality, "survived": j.survived, "accused": j.accused, "weakest_own": num(j.weakest_own),
                           "strongest_innocent": num(j.strongest_innocent), "psnr_min": num(j.psnr_min), "psnr_max": num(j.psnr_max)}
-                         for j in r.jpeg]} for r in rows]
+                         for j in r.jpeg],
+                "filters": [{"filter": f.filter, "survived": f.survived, "accused": f.accused, "weakest_own": num(f.weakest_own),
+                             "strongest_innocent": num(f.strongest_innocent), "psnr_min": num(f.psnr_min), "psnr_max": num(f.psnr_max)}
+                            for f in r.filters]} for r in rows]
         for d, r in zip(doc, rows):
             for c, s in zip(d["copies"], r.ssim):
                 c.update({"ssim": s.mean, "ssim_worst": s.worst_value, "ssim_worst_at": list(s.worst_position)})
@@ -426,6 +450,12 @@ def cmd_strength(args, out=None) -> int:
             ssim = f", ssim {j.ssim_min:.2f} .. {j.ssim_max:.2f}" if r.ssim else ""
             print(f"  jpeg {j.quality}: own mark found {j.survived}/{len(r.quality)}, weakest {j.weakest_own:.1f}, "
                   f"strongest innocent {innocent}{accused}, {j.psnr_min:.1f} .. {j.psnr_max:.1f} dB{ssim}", file=out)
+        for f in r.filters:
+            innocent = "none" if f.strongest_innocent != f.strongest_innocent else f"{f.strongest_innocent:.1f}"
+            accused = f", {f.accused} innocent accused" if f.accused else ""
+            ssim = f", ssim {f.ssim_min:.2f} .. {f.ssim_max:.2f}" if r.ssim else ""
+            print(f"  {f.filter}: own mark found {f.survived}/{len(r.quality)}, weakest {f.weakest_own:.1f}, "
+                  f"strongest innocent {innocent}{accused}, {f.psnr_min:.1f} .. {f.psnr_max:.1f} dB{ssim}", file=out)
     return 0
 
 

@@ -415,6 +415,7 @@ struct ssw_ctx {
                                   // | (scale ladder) the original's 8 x 8 box planes | the ladder's tap tables
     Buf catalogue[3];             // catalogue.hip: the blocks' top-8 lists of a match | host form: one group of frames | its signatures
     Buf jpeg;                     // jpeg.hip: the decoded Y, Cb and Cr planes of one group of jobs
+    Buf filter;                   // filter.hip: the row-blurred planes of one group of jobs
     Buf fingerprint[6];           // fingerprint.hip: line plan (u32) | T64 + gathered basis | Yr64 | mark deltas | dT of a group | handle output
     std::map<std::pair<size_t, size_t>, ssw::DeviceTaps> taps;   // (in_len, out_len) -> filter taps
 

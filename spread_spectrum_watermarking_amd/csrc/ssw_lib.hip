@@ -397,6 +397,7 @@ int ssw_ctx_destroy(ssw_ctx* ctx) {
     for (auto& b : ctx->locate) release(b);
     for (auto& b : ctx->catalogue) release(b);
     release(ctx->jpeg);
+    release(ctx->filter);
     for (auto& kv : ctx->taps) { (void)hipFree(kv.second.left); (void)hipFree(kv.second.count); (void)hipFree(kv.second.weights); }
     for (auto& e : ctx->sync_events) (void)hipEventDestroy(e);
     for (auto& p : ctx->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
