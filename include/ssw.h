@@ -180,6 +180,12 @@ int ssw_ctx_get_prune_stats(ssw_ctx* ctx, uint64_t* stats);
    stats[0] column tiles of the base frames, [1] of those computed, [2] frames whose second phase computed a tile; counted
    on the device since the last ssw_ctx_reset_timing.  Synchronises. */
 int ssw_ctx_get_base_prune_stats(ssw_ctx* ctx, uint64_t* stats);
+/* ... with the tuning entry "base_energy_lowp" (default on; rows of more than 1024 columns): the exact row launches compute
+   the first 64-pair tile column of every launch class only, a low-precision kernel bounds the energies of the other columns
+   from above, and the exact launches of those tile columns run after the decision, per frame, where a needed column tile
+   reads them.  *jobs: the (frame, class, tail tile column) jobs that ran, counted on the device since the last
+   ssw_ctx_reset_timing.  Synchronises. */
+int ssw_ctx_get_base_prune_tail_jobs(ssw_ctx* ctx, uint64_t* jobs);
 /* Diagnostic: the key bound of every frequency column of n f32 base frames, as the pruning of ssw_batch_extract forms it
    for mark length k (row pass only): dev_bound [n][w], natural column order.  SSW_ERR_UNSUPPORTED where that path does not
    apply to the shape / configuration.  Enqueues on the context's stream. */

@@ -128,6 +128,7 @@ SIGNATURES = {
     "ssw_tuning_reset": (C.c_int, [C.c_char_p]),
     "ssw_ctx_get_prune_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "ssw_ctx_get_base_prune_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "ssw_ctx_get_base_prune_tail_jobs": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "ssw_debug_base_prune_bound": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]),
     "ssw_debug_select_masked": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.c_int, _sz, _vp, _sz, _vp]),
     "ssw_ctx_get_select_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),

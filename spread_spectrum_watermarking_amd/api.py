@@ -120,8 +120,11 @@ class Context:
         check(self._lib.ssw_ctx_get_prune_stats(self.handle, st), "ssw_ctx_get_prune_stats")
         bp = (C.c_uint64 * 3)()
         check(self._lib.ssw_ctx_get_base_prune_stats(self.handle, bp), "ssw_ctx_get_base_prune_stats")
+        jobs = C.c_uint64(0)
+        check(self._lib.ssw_ctx_get_base_prune_tail_jobs(self.handle, C.byref(jobs)), "ssw_ctx_get_base_prune_tail_jobs")
         return {"pruned_chunks": int(st[0]), "redone_chunks": int(st[1]), "columns_needed": int(st[2]),
-                "base_tiles": int(bp[0]), "base_tiles_computed": int(bp[1]), "base_frames_extended": int(bp[2])}
+                "base_tiles": int(bp[0]), "base_tiles_computed": int(bp[1]), "base_frames_extended": int(bp[2]),
+                "base_tail_jobs": int(jobs.value)}
 
     def select_stats(self) -> dict:
         st = (C.c_uint64 * 2)()

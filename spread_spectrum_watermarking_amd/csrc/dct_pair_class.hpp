@@ -45,6 +45,7 @@ struct PairClassArgs {
     unsigned NP, Kp, yrows, tiles_n;
     unsigned c1, c2, cs, pm, np1, p2lo, bn32, fold0;
     unsigned gsh, e2off;               // forward class-major output map (PairOut::ft)
+    unsigned tn0 = 0;                  // first tile column of the launch (the gated tail launches of a pruned base reader: 1)
 };
 // ... and what selects the template instance of a class: all classes of a launch must agree
 struct PairInstance {

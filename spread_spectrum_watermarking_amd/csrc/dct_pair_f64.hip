@@ -82,6 +82,20 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     // 64-line tiles when 128-line ones would not fill the 512 block slots of the chip (2 per CU)
     const bool small = (unsigned long long)((L + 127) / 128) * tiles_n < 448;
     if (fuse && small) return SSW_ERR_BAD_ARG;
+    // pruned base reader, low-precision tail bound (base_energy.hip): the head launches run tile column 0 of every class,
+    // the gated tail launches the others (the planner sized the launch by all of them: `small` above)
+    const int row_part = fuse_rows ? fuse->row_part : 0;
+    if (row_part) {
+        if ((row_part == 2 && !fuse->need) || (row_part != 1 && row_part != 2)) return SSW_ERR_BAD_ARG;
+        tiles_n = 0;
+        for (int c = 0; c < n_classes; ++c) {
+            PairClassArgs& ca = ml.c[c];
+            if (ca.tiles_n < 2 || ca.gsh > 16 || ca.bn32 == 1) return SSW_ERR_BAD_ARG;
+            if (row_part == 1) ca.tiles_n = 1;
+            else { ca.tn0 = 1; ca.tiles_n -= 1; }
+            tiles_n += ca.tiles_n;
+        }
+    }
     const unsigned BM = small ? 64 : 128;
     if (small)                                                     // 48-pair tiles are three pair tiles of a 128-line block
         for (int c = 0; c < n_classes; ++c)
@@ -126,6 +140,11 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
         if (inst.epi != EPI_FWD || inst.samex || small || (fuse->tile_mode == 2 && !fuse->need)) return SSW_ERR_BAD_ARG;
         ml.need = fuse->need; ml.need_mode = (unsigned)fuse->tile_mode; ml.need_tpf = (unsigned)(w / 128);
     }
+    if (row_part == 2) {
+        if (energy || po.ft != 128) return SSW_ERR_BAD_ARG;
+        ml.need = fuse->need; ml.need_tpf = (unsigned)(w / 128);
+        ml.tail = fuse->tail; ml.tail_flop = fuse->tail_flop; ml.tail_bytes = fuse->tail_bytes;
+    }
     auto al = [](const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
     po.wide = (!is_row && w % 4 == 0 && al(out, 16) && (n_frames * w) % 4 == 0 && (!tmp || al(tmp, 16)) && (!tmp_out || al(tmp_out, 16))) ? 1u : 0u;
     if (with_sink && !(al(sink->iq_i, 16) && al(sink->iq_q, 16) && al(sink->rgb, sink->u8 ? 4 : 16))) po.wide = 0;
@@ -137,7 +156,8 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     switch (inst.epi) {
     case EPI_FWD_COLOP:
         // (the energy instances are named SUB + 10: the writer's row launches stay the kernels they were)
-        if (energy) { if (inst.subname == 4) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 14, 128); else SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 13, 128); }
+        if (row_part == 2) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 5, 128);      // (the gated tail launches: one instance)
+        else if (energy) { if (inst.subname == 4) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 14, 128); else SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 13, 128); }
         else if (inst.subname == 4) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 4, 128);
         else SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 3, 128);
         break;

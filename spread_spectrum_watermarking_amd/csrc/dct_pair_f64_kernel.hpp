@@ -85,6 +85,11 @@ struct PairMulti {
     // forward column launches of a pruned base reader (FuseCols::tile_mode): line tile tm = frame * need_tpf + column tile
     const unsigned* need = nullptr;
     unsigned need_mode = 0, need_tpf = 1;
+    // gated tail row launches of a pruned base reader (SUB 5, FuseCols::row_part 2): `need` as above with need_tpf = column
+    // tiles per frame; tail[0] counts the (frame, class, tile column) jobs that ran, tail[1] / tail[2] (doubles) their flop and
+    // bytes at tail_flop / tail_bytes per pair of a job
+    unsigned long long* tail = nullptr;
+    double tail_flop = 0.0, tail_bytes = 0.0;
 };
 
 template <bool COLS, int EPI, bool SAMEX, int SUB = 0, int BM = 128>
@@ -123,6 +128,28 @@ __global__ __launch_bounds__(PT, 2) void pair_gemm_f64_kernel(const PairMulti ml
         // block-uniform: the flag is a scalar load)
         if (ml.need_mode == 1) tm *= ml.need_tpf;
         else if (tm % ml.need_tpf == 0 || ml.need[tm] == 0) return;
+    }
+    if constexpr (!COLS && EPI == EPI_FWD_COLOP && SUB == 5) {
+        // tail row launches of a pruned base reader (their own instance, SUB 5): the class's tile columns from tn0 on.  A line
+        // tile lies inside one frame z (unit-ordered, padded lines); the tile column's pairs write the column-operand lines of
+        // the column tiles lo .. hi (entry e of a class -> tile e >> gsh; the second outputs of a class of E's shape lie one
+        // entry lower).  A block returns before it has issued a load unless the decide kernel flagged one of them: the flags
+        // are scalar loads, the branch is block-uniform.
+        const PairClassArgs& cg = ml.c[cls];
+        tn += cg.tn0;
+        const unsigned tw = cg.bn32 == 2 ? 48u : 64u;
+        const unsigned tpf = ml.po.cop_hup / 8, z = tm / tpf;
+        const unsigned pf = tn * tw, pl = pf + tw - 1u < cg.NP ? pf + tw - 1u : cg.NP - 1u;
+        const unsigned lo = (pf - cg.e2off) >> cg.gsh, hi = pl >> cg.gsh;
+        unsigned any = 0;
+        for (unsigned t = lo; t <= hi; ++t) any |= ml.need[(size_t)z * ml.need_tpf + t];
+        if (!any) return;
+        if (ml.tail && tm == z * tpf && threadIdx.x == 0) {
+            const double pairs = (double)(pl - pf + 1u);
+            atomicAdd(&ml.tail[0], 1ull);
+            atomicAdd(reinterpret_cast<double*>(ml.tail) + 1, pairs * ml.tail_flop);
+            atomicAdd(reinterpret_cast<double*>(ml.tail) + 2, pairs * ml.tail_bytes);
+        }
     }
     const PairClassArgs& ca = ml.c[cls];
     const double* __restrict__ X1g = ca.x1;

@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <string>
 #include <tuple>
@@ -119,6 +120,12 @@ struct FuseCols {
     float* energy = nullptr;
     const unsigned* need = nullptr;
     int tile_mode = 0;
+    // ... with the low-precision tail bound (base_energy.hip), row launches: `row_part` 1 runs tile column 0 of every class (the
+    // head: exact energies), 2 the other tile columns, each block gated on `need` (no energies); `tail`: [0] jobs that ran,
+    // [1] [2] their flop / bytes as doubles, tail_flop / tail_bytes per pair of a job
+    int row_part = 0;
+    unsigned long long* tail = nullptr;
+    double tail_flop = 0.0, tail_bytes = 0.0;
 };
 // one or several classes (same lines, same template instance) in one launch: the class (dct_pair_class.hpp) with its operand
 // and basis planes; sink (last inverse column pass): colour conversion in the epilogue
@@ -144,7 +151,7 @@ int launch_dct_pair_gemm_rows_subset_merged_f64(hipStream_t st, const PairSubset
 size_t dct_pair_split_kpad(size_t len);
 // tuning.hip: the process-wide table of strategy thresholds / A-B switches (ssw_tuning_set, include/ssw.h)
 enum { TUNE_EFOLD_MIN, TUNE_EFOLD_INV_MIN, TUNE_EFOLD_COLS_MIN, TUNE_CLASS_TILE, TUNE_DEEP_MIN_ROWS, TUNE_DEEP_MIN_COLS, TUNE_PREP_STAGED,
-       TUNE_MERGE_MAX_LINES, TUNE_BN32, TUNE_BAND_SPLIT, TUNE_FUSE_COLS, TUNE_UPLOAD_BANDS, TUNE_SPECULATE_K, TUNE_PREP_LIGHT, TUNE_LANE_STAGGER, TUNE_DERIVED_FUSED, TUNE_TILE48, TUNE_BASE_PRUNE, TUNE_COUNT };
+       TUNE_MERGE_MAX_LINES, TUNE_BN32, TUNE_BAND_SPLIT, TUNE_FUSE_COLS, TUNE_UPLOAD_BANDS, TUNE_SPECULATE_K, TUNE_PREP_LIGHT, TUNE_LANE_STAGGER, TUNE_DERIVED_FUSED, TUNE_TILE48, TUNE_BASE_PRUNE, TUNE_BASE_ENERGY_LOWP, TUNE_COUNT };
 long long tuning(int which);
 int launch_prep16_cols_l2(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
                           const double* rot1, const double* rot2, const double* rot3, bool class_major, bool in_l2, unsigned K16);
@@ -219,6 +226,9 @@ int launch_extract_pruned(hipStream_t st, const float* base, const float* compac
 // One lane's buffers: energy [n][W] f32 | need [n][W / 128] u32; `stats` (the context's): tiles total, tiles computed,
 // frames whose second phase computed a tile.
 constexpr unsigned SSW_BASE_PRUNE_TILE = 128;
+// the context's counters, 64-bit words: [0 .. 2] `stats` below, [4 .. 6] `work` (doubles); [8] tail jobs that ran (a frame's
+// tile column of one class of the gated row launches, base_energy.hip), [9] [10] their flop and bytes (doubles)
+constexpr unsigned SSW_BASE_PRUNE_STATS = 16;
 struct BasePrune {
     float* energy = nullptr;
     unsigned* need = nullptr;
@@ -233,6 +243,9 @@ struct BasePrune {
     // set by the pass builder that enqueues the decide kernel: `need` will hold this chunk's flags, and the tiles it leaves
     // unset are NOT written -- whoever reads the plane afterwards goes by the flags (launch_topk's mask)
     bool* decided = nullptr;
+    // low-precision tail bound (base_energy.hip): the row pass's builder leaves the gated tail launches here, the column
+    // pass's builder runs them between the decide kernel and phase 2 (the caller owns the function object)
+    std::function<int(hipStream_t)>* tail = nullptr;
 };
 // G of boundkey(v) = G * E[v]: every key of column v is <= it (rounded up; 0: the ordering has no bound)
 float base_prune_gain(size_t w, size_t h, int ordering);
@@ -241,6 +254,22 @@ float base_prune_gain(size_t w, size_t h, int ordering);
 int launch_base_prune_decide(hipStream_t st, const float* coef, const BasePrune& bp, size_t n_frames, size_t w, size_t h);
 // diagnostic: boundkey of every frequency column in natural order, out [n][W]
 int launch_base_prune_bound(hipStream_t st, const float* energy, size_t n_frames, size_t w, size_t h, int ordering, float* out);
+
+// base_energy.hip: the energies of the tail columns as a rigorous upper bound, from f16 hi + lo products.
+// One class of the row pass: its operand planes (k-blocked doubles, `lines` lines), its pre-split bases (base_energy_split),
+// pairs and padded sum length, the first tail pair, and the class-major output map of the row launches.
+struct BaseEnergyClass {
+    const double *x1 = nullptr, *x2 = nullptr;
+    const void* y16 = nullptr;
+    unsigned NP = 0, Kp = 0, pair0 = 0, pm = 0, c1 = 0, c2 = 0, gsh = 0, e2off = 0;
+};
+// bytes of a class's pre-split bases: hi | lo halves of both bases in fragment order, then the largest |entry| (one float)
+size_t base_energy_split_bytes(unsigned NP, unsigned Kp, unsigned pair0);
+int launch_base_energy_split(hipStream_t st, const double* y1, const double* y2, unsigned yrows, unsigned NP, unsigned Kp, unsigned pair0, void* out);
+// adds the bounds of pairs pair0 .. NP - 1 of every class into energy [frames][W]; lines_per_frame = 16 * units (padded), of
+// which the first `h` are image rows
+int launch_base_energy_bound(hipStream_t st, int n_classes, const BaseEnergyClass* cls, size_t n_frames, size_t w, size_t h, size_t lines_per_frame,
+                             float factor, float* energy);
 
 // select.hip
 struct SelectWorkspace {
@@ -326,6 +355,8 @@ struct ssw_ctx {
 
     // basis cache: (N, inverse, f64, kind) -> device pointer (get_basis; every kind but Dense is f64)
     std::map<std::tuple<size_t, bool, bool, ssw::BasisKind>, void*> basis;
+    // (row length, launch class, first tail pair) -> both bases of the class as f16 hi + lo fragments (get_split16, base_energy.hip)
+    std::map<std::tuple<size_t, int, unsigned>, void*> split16;
     bool fold = true;             // use the even/odd-folded GEMMs where the shape allows
     int fold_level = SSW_DCT_FOLDING_DEFAULT;           // 1 / 2: dense; 3: operand-ready GEMMs (dct_pair_*.hip, f64 only);
                                   // 4: two levels; 5: + a third on long forward row passes; 6: on all
@@ -364,7 +395,7 @@ struct ssw_ctx {
     // base-reader pruning: device counters (u64: tiles total, tiles computed, frames extended, spare; then doubles: flop and
     // bytes of the second phase's column launches, bytes of the zero-fill) and what flush_timers has already billed of the doubles
     Buf base_prune_stats;
-    double base_prune_billed[3] = {0.0, 0.0, 0.0};
+    double base_prune_billed[5] = {0.0, 0.0, 0.0, 0.0, 0.0};     // column flop, bytes, selection bytes | tail row flop, bytes
     // single-image handles (ssw_lib.hip): frames cross PCIe on `copy_stream` into / out of two alternating
     // device staging buffers, so the upload of the next frame runs beside the kernels of the previous one
     hipStream_t copy_stream = nullptr;

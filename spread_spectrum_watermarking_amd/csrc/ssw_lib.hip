@@ -375,6 +375,7 @@ int ssw_ctx_destroy(ssw_ctx* ctx) {
         if (fs.consumed) (void)hipEventDestroy(fs.consumed);
     }
     for (auto& kv : ctx->basis) (void)hipFree(kv.second);
+    for (auto& kv : ctx->split16) (void)hipFree(kv.second);
     for (auto& ln : ctx->lane) {
         for (auto& b : ln.plane) release(b);
         for (auto& b : ln.operand) release(b);
@@ -480,7 +481,7 @@ int ssw_ctx_reset_timing(ssw_ctx* ctx) {
     SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) SSW_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
     SSW_HIP_CHECK(hipMemset(ctx->select_fallbacks, 0, sizeof(uint32_t)));
-    if (ctx->base_prune_stats.p) SSW_HIP_CHECK(hipMemset(ctx->base_prune_stats.p, 0, 8 * sizeof(unsigned long long)));
+    if (ctx->base_prune_stats.p) SSW_HIP_CHECK(hipMemset(ctx->base_prune_stats.p, 0, SSW_BASE_PRUNE_STATS * sizeof(unsigned long long)));
     for (double& b : ctx->base_prune_billed) b = 0.0;
     return SSW_OK;
 }
@@ -548,6 +549,19 @@ int ssw_ctx_get_base_prune_stats(ssw_ctx* ctx, uint64_t* stats) {
     unsigned long long v[4] = {0, 0, 0, 0};
     SSW_HIP_CHECK(hipMemcpy(v, ctx->base_prune_stats.p, sizeof(v), hipMemcpyDeviceToHost));
     for (int i = 0; i < 3; ++i) stats[i] = v[i];
+    return SSW_OK;
+}
+
+int ssw_ctx_get_base_prune_tail_jobs(ssw_ctx* ctx, uint64_t* jobs) {
+    if (!ctx || !jobs) return SSW_ERR_BAD_ARG;
+    CtxGuard g(ctx);
+    *jobs = 0;
+    if (!ctx->base_prune_stats.p) return SSW_OK;
+    SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (ctx->aux_stream) SSW_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
+    unsigned long long v = 0;
+    SSW_HIP_CHECK(hipMemcpy(&v, (const char*)ctx->base_prune_stats.p + 8 * sizeof(unsigned long long), sizeof(v), hipMemcpyDeviceToHost));
+    *jobs = v;
     return SSW_OK;
 }
 

@@ -195,6 +195,14 @@ int flush_timers(ssw_ctx* ctx) {
             ctx->stage_bytes[SSW_STAGE_SELECT] += wk[2] - ctx->base_prune_billed[2];
         }
         for (int i = 0; i < 3; ++i) ctx->base_prune_billed[i] = wk[i];
+        // ... and the gated tail row launches' jobs (base_energy.hip), counted by the launches themselves
+        double tw[2] = {0.0, 0.0};
+        SSW_HIP_CHECK(hipMemcpy(tw, (const char*)ctx->base_prune_stats.p + 9 * sizeof(unsigned long long), sizeof(tw), hipMemcpyDeviceToHost));
+        if (ctx->timing) {
+            ctx->stage_work[SSW_STAGE_DCT_ROW] += tw[0] - ctx->base_prune_billed[3];
+            ctx->stage_bytes[SSW_STAGE_DCT_ROW] += tw[1] - ctx->base_prune_billed[4];
+        }
+        for (int i = 0; i < 2; ++i) ctx->base_prune_billed[3 + i] = tw[i];
     }
     return SSW_OK;
 }
@@ -223,6 +231,22 @@ int get_basis(ssw_ctx* ctx, size_t n, bool inverse, bool f64, BasisKind kind, co
     untimed_work(ctx);
     if (rc != SSW_OK) { (void)hipFree(p); return rc; }
     ctx->basis[key] = p;
+    *out = p;
+    return SSW_OK;
+}
+
+// Both bases of launch class `c` over a length-`len` axis as f16 hi + lo fragments for the pairs from pair0 on
+// (base_energy.hip), cached in a map of their own and freed with the bases they are made from
+int get_split16(ssw_ctx* ctx, size_t len, PairClass c, const double* y1, const double* y2, const PairClassArgs& ca, unsigned pair0, const void** out) {
+    auto key = std::make_tuple(len, (int)c, pair0);
+    auto it = ctx->split16.find(key);
+    if (it != ctx->split16.end()) { *out = it->second; return SSW_OK; }
+    void* p = nullptr;
+    SSW_ALLOC(&p, base_energy_split_bytes(ca.NP, ca.Kp, pair0));
+    const int rc = launch_base_energy_split(ctx->stream, y1, y2, ca.yrows, ca.NP, ca.Kp, pair0, p);
+    untimed_work(ctx);
+    if (rc != SSW_OK) { (void)hipFree(p); return rc; }
+    ctx->split16[key] = p;
     *out = p;
     return SSW_OK;
 }
@@ -615,11 +639,86 @@ int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
             StageTimer t(ctx, SSW_STAGE_SELECT, st, (double)n * ((double)h * SSW_BASE_PRUNE_TILE + (double)w) * 4.0);
             return launch_base_prune_decide(st, out, bp, n, w, h);
         }});
+        if (bp.tail && *bp.tail) {
+            // the exact row launches of the tile columns beyond the head, each block gated on the flags (base_energy.hip):
+            // the column operands of the needed tiles are complete before phase 2 reads them
+            const std::function<int(hipStream_t)> tail = *bp.tail;
+            ch.push_back({false, [=](hipStream_t st) -> int {
+                StageTimer t(ctx, SSW_STAGE_DCT_ROW, st, 0.0);
+                return tail(st);
+            }});
+        }
         ch.push_back({false, [=](hipStream_t st) -> int {
             StageTimer t(ctx, b.st_pass, st, 0.0);
             return phase(st, 2);
         }});
         return SSW_OK;
+    }
+    if (bprune && bp.tail) *bp.tail = nullptr;
+    if (bprune && b.is_row && bp.tail && tuning(TUNE_BASE_ENERGY_LOWP) != 0) {
+        // Low-precision tail bound (base_energy.hip): where every class has more than one tile column, the energy launches
+        // run tile column 0 only (the head), the bound kernel covers the other pairs, and the exact launches of those tile
+        // columns wait for the decide kernel in the column pass's chain.
+        std::array<BaseEnergyClass, 8> be;
+        bool ok = true;
+        unsigned pair0 = 0, np = 0;
+        double chunks = 1.0;
+        for (int c = 0; c < 8 && ok; ++c) {
+            PairClassArgs ca;
+            PairInstance inst;
+            SSW_TRY(pair_class_args(d[c].cls, true, false, b.len, b.gemm_layout(), false, false, tuning(TUNE_TILE48) != 0, ca, inst));
+            const unsigned p0 = ca.bn32 == 2 ? 48u : 64u;
+            // (sums of more than 256 terms stay exact: the accumulation term of the bound grows with the sum length times the
+            // line's norm, and at 8K -- 480 terms -- it passed the threshold on every tail tile of the 8K benchmark frames)
+            // (the bound kernel adds a term for both outputs of every tail pair: that is the exact epilogue's set of outputs only
+            // while every pair has both -- np1 = none, p2lo = 0 -- and a class is plain or split, pm 0 / 1)
+            ok = ca.tiles_n >= 2 && ca.Kp <= 256 && ca.gsh <= 16 && ca.bn32 != 1 && ca.np1 == 0xFFFFFFFFu && ca.p2lo == 0 && ca.pm <= 1 &&
+                 (c == 0 || (p0 == pair0 && ca.NP == np));
+            if (!ok) break;
+            pair0 = p0; np = ca.NP;
+            const void* y16 = nullptr;
+            SSW_TRY(get_split16(ctx, b.len, d[c].cls, d[c].y1, d[c].y2, ca, pair0, &y16));
+            be[c].x1 = d[c].x1; be[c].x2 = d[c].x2; be[c].y16 = y16;
+            be[c].NP = ca.NP; be[c].Kp = ca.Kp; be[c].pair0 = pair0; be[c].pm = ca.pm; be[c].c1 = ca.c1; be[c].c2 = ca.c2; be[c].gsh = ca.gsh; be[c].e2off = ca.e2off;
+            chunks = (double)(((ca.NP - pair0 + 15) / 16 + 10) / 11);
+        }
+        if (ok) {
+            const size_t lpf = 16 * dct_pair_fused_units(h);
+            const double head = (double)pair0 / (double)np;
+            const double bound_bytes = 8.0 * 2.0 * chunks * (double)(n * lpf) * (double)be[0].Kp * 8.0;
+            unsigned long long* tail_stats = bp.stats ? bp.stats + 8 : nullptr;
+            const double tail_flop = 4.0 * (double)lpf * (double)(b.len / 16), tail_bytes = 16.0 * (double)h;
+            ch.push_back({false, [=](hipStream_t st) -> int {
+                SSW_HIP_CHECK(hipMemsetAsync(bp.energy, 0, n * w * sizeof(float), st));
+                untimed_work(ctx);
+                {
+                    StageTimer tp(ctx, SSW_STAGE_DCT_PREP, st, bound_bytes);
+                    SSW_TRY(launch_base_energy_bound(st, 8, be.data(), n, w, h, lpf, b.ep.base, bp.energy));
+                }
+                FuseCols fh = fc;
+                fh.row_part = 1;
+                // (not billed to the main-launch stage: that figure stays the time and flop of one full launch, the writer's)
+                StageTimer t(ctx, b.st_pass, st, f_all * pad * head);
+                t.traffic(b.px * 8.0 * (1.0 + head));
+                auto launch = [&](int nc, const PairClassDesc* dd) {
+                    return launch_dct_pair_gemm_multi_f64(st, true, false, nc, dd, out, nullptr, n, w, h, b.ep, nullptr, nullptr, b.gemm_layout(), &fh);
+                };
+                return launch_classes(ctx, st, b.p.merge, 8, d.data(), launch);
+            }});
+            const PairLayout lay = b.gemm_layout();
+            const Epilogue ep = b.ep;
+            const bool merge = b.p.merge;
+            *bp.tail = [=](hipStream_t st) -> int {
+                FuseCols ft = fc;
+                ft.row_part = 2; ft.energy = nullptr; ft.need = bp.need;
+                ft.tail = tail_stats; ft.tail_flop = tail_flop; ft.tail_bytes = tail_bytes;
+                auto launch = [&](int nc, const PairClassDesc* dd) {
+                    return launch_dct_pair_gemm_multi_f64(st, true, false, nc, dd, out, nullptr, n, w, h, ep, nullptr, nullptr, lay, &ft);
+                };
+                return launch_classes(ctx, st, merge, 8, d.data(), launch);
+            };
+            return SSW_OK;
+        }
     }
     ch.push_back({false, [=](hipStream_t st) -> int {
         if (bprune) {           // (row pass) the energies start at zero
@@ -1445,8 +1544,8 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
     for (size_t f0 = 0; base_prune && f0 < n_frames; f0 += chunk)        // (the last chunk may be shorter: another plan)
         base_prune = base_prune_shape_ok(ctx, c, std::min(chunk, n_frames - f0), w, h, dev_base_rgb, fmt, y0, tmp0);
     if (base_prune && !ctx->base_prune_stats.p) {
-        SSW_TRY(grow(ctx->base_prune_stats, 8 * sizeof(unsigned long long)));
-        SSW_HIP_CHECK(hipMemsetAsync(ctx->base_prune_stats.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
+        SSW_TRY(grow(ctx->base_prune_stats, SSW_BASE_PRUNE_STATS * sizeof(unsigned long long)));
+        SSW_HIP_CHECK(hipMemsetAsync(ctx->base_prune_stats.p, 0, SSW_BASE_PRUNE_STATS * sizeof(unsigned long long), ctx->stream));
         untimed_work(ctx);
     }
 
@@ -1462,8 +1561,10 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         SelectWorkspace* sel = &ws.sel;
         BasePrune bp;
         bool decided = false;           // the transform below took the two-phase column pass: skipped tiles are stale
+        std::function<int(hipStream_t)> tail;      // (copied into the chain by the column pass's builder)
         if (base_prune) {
             bp.decided = &decided;
+            bp.tail = &tail;
             SSW_TRY(base_prune_workspace(ws, chunk, w, bp));
             bp.stats = (unsigned long long*)ctx->base_prune_stats.p;
             bp.work = (double*)(bp.stats + 4);
@@ -1505,8 +1606,10 @@ int base_prune_bound_impl(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_
     if (k == 0 || k >= plane || !base_prune_shape_ok(ctx, c, n_frames, w, h, dev_rgb, PixFmt::F32, (const float*)ws.plane[0].p, (const float*)ws.plane[2].p))
         return SSW_ERR_UNSUPPORTED;
     BasePrune bp;
+    std::function<int(hipStream_t)> tail;
     SSW_TRY(base_prune_workspace(ws, n_frames, w, bp));
     bp.k = k; bp.ordering = c.ordering;
+    bp.tail = &tail;
     Chain ch;
     SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_rgb, PixFmt::F32, n_frames, w, h, (float*)ws.plane[0].p, nullptr, nullptr,
                                    (float*)ws.plane[2].p, ch, &bp));

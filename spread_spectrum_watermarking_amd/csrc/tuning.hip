@@ -40,6 +40,7 @@ Entry g_tune[TUNE_COUNT] = {
     {"derived_fused", "SSW_DERIVED_FUSED", 1},         // the derived frame's pruned row pass in one kernel (marks of up to 1024 entries; 0: pre-pass + launches)
     {"tile48", "SSW_TILE48", 1},                       // r6: 48-pair tiles for classes whose 64-pair tiling ends in a tile of <= 16 pairs (135 = 48 + 48 + 39)
     {"base_prune", "SSW_BASE_PRUNE", 1},               // batch extract: the base frame's column pass only on the 128-column tiles that can hold a top-k key
+    {"base_energy_lowp", "SSW_BASE_ENERGY_LOWP", 1},   // ... its tail columns' energies as an f16 hi + lo upper bound, the exact row launches of those columns gated on the decision (0: eight full energy launches)
 };
 
 // value and state change together under this lock (first read from the environment, set, reset); the fast path of a reader
