@@ -25,6 +25,7 @@ import gpu_util as G
 from spread_spectrum_watermarking_amd import _lib as L
 from spread_spectrum_watermarking_amd.api import tuning
 from test_base_prune_gpu import FUSED, check_bound, check_oracle, marks_for, noise, routes, with_cosine
+from tail_layout import tail_layout
 from test_base_select_gpu import smooth
 
 pytestmark = pytest.mark.gpu
@@ -110,26 +111,33 @@ def tail_jobs(st, n, tiles_per_frame):
     return st["base_tail_jobs"] // passes
 
 
-def bounds_both_routes(base, lay, ordering=L.ORDER_ENERGY):
+def bounds_both_routes(base, lay, ordering=L.ORDER_ENERGY, head=None, coef=None):
     """check_bound under both routes (ssw_debug_base_prune_bound >= the largest key of each column); the head's columns carry
-    the exact energies.  With 64-pair tiles (W = 2048, and W = 1152 under tile48 = 0) they are compared bit for bit: two waves
-    add into a block's total and two blocks into a frame's, both commutative.  The 48-pair tiles of W = 1152 under the default
-    tiling add four waves' parts in the order they arrive (LDS atomics), on either route: there the head is compared within
-    what that reordering can move -- per route three additions of the four parts, the addition of the two blocks and the
-    product with G, each 2^-24 of a positive sum: 2 * 5 * 2^-24 relative.  Tail bounds lie above the exact energies up to the
-    reordering of the exact route's H = 256 terms (2 * 256 * 2^-24)."""
+    the exact energies.  `head`: the columns fed by head pairs only (default: those of this module's three layouts).  With
+    64-pair tiles (W = 2048, and W = 1152 under tile48 = 0) they are compared bit for bit: two waves add into a block's total
+    and two blocks into a frame's, both commutative.  The 48-pair tiles of W = 1152 under the default tiling add four waves'
+    parts in the order they arrive (LDS atomics), on either route: there the head is compared within what that reordering can
+    move -- per route three additions of the four parts, the addition of the two blocks and the product with G, each 2^-24 of
+    a positive sum: 2 * 5 * 2^-24 relative.  A frame of more than 256 (padded) lines has more than two 128-line blocks, whose
+    totals arrive in any order too: blocks - 1 additions per route instead of the one, with either tile width (H = 256: the
+    rules above, unchanged).  Tail bounds lie above the exact energies up to the reordering of the exact route's H = 256 terms
+    (2 * 256 * 2^-24).  `coef`: the reference plane check_bound compares with, instead of the library's own."""
     assert base.shape[2] == lay[0]
-    lowp = check_bound(base, K, ordering)
+    lowp = check_bound(base, K, ordering, coef)
     with tuning(base_energy_lowp=0):
-        exact = check_bound(base, K, ordering)
-    head = 128 * (FIRST_TAIL_TILE[lay] - 1)                # every column below is fed by head pairs only
-    if lay != W48:
+        exact = check_bound(base, K, ordering, coef)
+    if head is None:
+        head = 128 * (FIRST_TAIL_TILE[lay] - 1)            # every column below is fed by head pairs only
+    tw = tail_layout(*lay).tw
+    blocks = (base.shape[1] // 16 + 7) // 8                # 128-line blocks per frame: the units padded to whole blocks
+    additions = (3 if tw == 48 else 0) + (blocks - 1) + 1
+    if tw == 64 and blocks <= 2:
         assert lowp[:, :head].tobytes() == exact[:, :head].tobytes(), "head bounds differ from the exact route"
     else:
         a, b = lowp[:, :head], exact[:, :head]
         assert np.array_equal(np.isfinite(a), np.isfinite(b))
         ok = np.isfinite(a)
-        assert np.all(np.abs(a[ok] - b[ok]) <= np.float32(10 * 2.0 ** -24) * np.abs(b[ok])), "head bounds differ from the exact route"
+        assert np.all(np.abs(a[ok] - b[ok]) <= np.float32(2 * additions * 2.0 ** -24) * np.abs(b[ok])), "head bounds differ from the exact route"
     fin = np.isfinite(exact) & np.isfinite(lowp)
     assert np.all(lowp[fin] >= exact[fin] * np.float32(1 - 2.0 ** -15)), "a tail bound below the exact energy's"
     assert not np.any(np.isfinite(lowp) & ~np.isfinite(exact)), "a finite bound where the exact energy is not"

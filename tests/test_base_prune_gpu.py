@@ -97,8 +97,9 @@ def check_oracle(base, derived, marks, on, cfg_kw=None):
         assert abs(float(on[1][f]) - ref_sim) < 1e-4 * max(1.0, abs(ref_sim)), (f, on[1][f], ref_sim)
 
 
-def check_bound(base, k=K, ordering=L.ORDER_ENERGY):
-    """boundkey(v) >= the largest key of column v of the library's own full plane, on every frame."""
+def check_bound(base, k=K, ordering=L.ORDER_ENERGY, coef=None):
+    """boundkey(v) >= the largest key of column v of the library's own full plane (or of `coef`, a reference plane [n, h, w] of
+    the caller's), on every frame."""
     n, h, w, _ = base.shape
     ctx = G.ctx()
     d = ctx.to_device(np.ascontiguousarray(base))
@@ -107,8 +108,10 @@ def check_bound(base, k=K, ordering=L.ORDER_ENERGY):
     check(G.lib().ssw_debug_base_prune_bound(ctx.handle, C.byref(cfg), d.ptr, n, w, h, k, out.ptr), "ssw_debug_base_prune_bound")
     bound = out.to_host(np.float32, (n, w))
     d.free(); out.free()
-    yplane = G.rgb_to_yiq(base, with_iq=False)[0]
-    coef = G.dct2d(np.asarray(yplane, np.float32).reshape(n, h, w), L.DCT2, L.PRECISION_F64)
+    if coef is None:
+        yplane = G.rgb_to_yiq(base, with_iq=False)[0]
+        coef = G.dct2d(np.asarray(yplane, np.float32).reshape(n, h, w), L.DCT2, L.PRECISION_F64)
+    coef = np.asarray(coef, np.float32).reshape(n, h, w)
     with np.errstate(all="ignore"):
         if ordering == L.ORDER_ENERGY:
             key = (coef * coef).astype(np.float32)
