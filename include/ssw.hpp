@@ -412,18 +412,40 @@ struct DeviceFrames {
         }
     }
 };
+// ssw_quality_rgb8, ssw_ssim_rgb8: every copy against the one original through run(dev_base, dev_copies, n, dev_stats); the
+// S words a copy's statistics take come back one copy after the other.
+template <size_t S, class Run>
+std::vector<uint64_t> against_original(Context& ctx, const ImageRgb8& original, const std::vector<const ImageRgb8*>& copies, const char* where, Run run) {
+    const size_t n = copies.size(), w = original.width, h = original.height, fb = w * h * 3;
+    DeviceFrames base(ctx.get(), fb, where), dev(ctx.get(), n * fb, where), st(ctx.get(), n * S * sizeof(uint64_t), where);
+    base.put({&original}, w, h, where);
+    dev.put(copies, w, h, where);
+    check(run(base.p, dev.p, n, reinterpret_cast<uint64_t*>(st.p)), where);
+    std::vector<uint64_t> raw(n * S);
+    check(ssw_copy_to_host(ctx.get(), raw.data(), st.p, raw.size() * sizeof(uint64_t)), where);
+    return raw;
+}
+// ssw_collude_rgb8, ssw_jpeg_rgb8, ssw_filter_rgb8: the frames go up, call(ctx, dev_frames, n, w, h, jobs, m, dev_out) writes one
+// frame per job, and the m frames come down.
+template <class Job, class Call>
+std::vector<ImageRgb8> frames_through_jobs(Context& ctx, const std::vector<const ImageRgb8*>& frames, const std::vector<Job>& jobs, const char* where, Call call) {
+    if (frames.empty()) throw Error(SSW_ERR_BAD_ARG, where);
+    const size_t n = frames.size(), m = jobs.size(), w = frames[0]->width, h = frames[0]->height, fb = w * h * 3;
+    DeviceFrames dev(ctx.get(), n * fb, where), made(ctx.get(), m * fb, where);
+    dev.put(frames, w, h, where);
+    check(call(ctx.get(), dev.p, n, w, h, jobs.data(), m, made.p), where);
+    std::vector<ImageRgb8> out(m, ImageRgb8(w, h));
+    for (size_t i = 0; i < m; ++i) check(ssw_copy_to_host(ctx.get(), out[i].data.data(), made.p + i * fb, fb), where);
+    return out;
+}
 }  // namespace detail
 // ssw_quality_rgb8 on host images: every copy against the one original.
 inline std::vector<Quality> quality(Context& ctx, const ImageRgb8& original, const std::vector<const ImageRgb8*>& copies) {
-    const size_t n = copies.size(), w = original.width, h = original.height, fb = w * h * 3;
-    detail::DeviceFrames base(ctx.get(), fb, "quality"), dev(ctx.get(), n * fb, "quality"), st(ctx.get(), n * 6 * sizeof(uint64_t), "quality");
-    base.put({&original}, w, h, "quality");
-    dev.put(copies, w, h, "quality");
-    check(ssw_quality_rgb8(ctx.get(), base.p, 1, dev.p, n, w, h, reinterpret_cast<uint64_t*>(st.p)), "quality");
-    std::vector<uint64_t> raw(n * 6);
-    check(ssw_copy_to_host(ctx.get(), raw.data(), st.p, raw.size() * sizeof(uint64_t)), "quality");
-    std::vector<Quality> out(n);
-    for (size_t i = 0; i < n; ++i) {
+    const size_t w = original.width, h = original.height;
+    const auto run = [&](const uint8_t* base, const uint8_t* dev, size_t n, uint64_t* st) { return ssw_quality_rgb8(ctx.get(), base, 1, dev, n, w, h, st); };
+    const std::vector<uint64_t> raw = detail::against_original<6>(ctx, original, copies, "quality", run);
+    std::vector<Quality> out(copies.size());
+    for (size_t i = 0; i < out.size(); ++i) {
         const uint64_t* r = &raw[i * 6];
         out[i].sse[0] = r[0]; out[i].sse[1] = r[1]; out[i].sse[2] = r[2];
         out[i].sse_luma = r[3]; out[i].changed = r[4]; out[i].max_abs = r[5]; out[i].pixels = w * h;
@@ -443,17 +465,13 @@ struct Ssim {
 };
 // ssw_ssim_rgb8 on host images: every copy against the one original.  No side below SSW_SSIM_MIN_SIDE.
 inline std::vector<Ssim> ssim(Context& ctx, const ImageRgb8& original, const std::vector<const ImageRgb8*>& copies) {
-    const size_t n = copies.size(), w = original.width, h = original.height, fb = w * h * 3;
+    const size_t w = original.width, h = original.height;
     if (w < SSW_SSIM_MIN_SIDE || h < SSW_SSIM_MIN_SIDE) throw Error(SSW_ERR_BAD_ARG, "ssim");
     const size_t nx = w / 4 - 1, ny = h / 4 - 1;
-    detail::DeviceFrames base(ctx.get(), fb, "ssim"), dev(ctx.get(), n * fb, "ssim"), st(ctx.get(), n * SSW_SSIM_STATS * sizeof(uint64_t), "ssim");
-    base.put({&original}, w, h, "ssim");
-    dev.put(copies, w, h, "ssim");
-    check(ssw_ssim_rgb8(ctx.get(), base.p, 1, dev.p, n, w, h, reinterpret_cast<uint64_t*>(st.p), nullptr), "ssim");
-    std::vector<uint64_t> raw(n * SSW_SSIM_STATS);
-    check(ssw_copy_to_host(ctx.get(), raw.data(), st.p, raw.size() * sizeof(uint64_t)), "ssim");
-    std::vector<Ssim> out(n);
-    for (size_t i = 0; i < n; ++i) {
+    const auto run = [&](const uint8_t* base, const uint8_t* dev, size_t n, uint64_t* st) { return ssw_ssim_rgb8(ctx.get(), base, 1, dev, n, w, h, st, nullptr); };
+    const std::vector<uint64_t> raw = detail::against_original<SSW_SSIM_STATS>(ctx, original, copies, "ssim", run);
+    std::vector<Ssim> out(copies.size());
+    for (size_t i = 0; i < out.size(); ++i) {
         const uint64_t key = raw[i * SSW_SSIM_STATS + 1], index = key & 0xFFFFFFFFull;
         out[i].sum = (int64_t)raw[i * SSW_SSIM_STATS];
         out[i].worst = (int32_t)((int64_t)(key >> 32) - SSW_SSIM_ONE);
@@ -464,24 +482,13 @@ inline std::vector<Ssim> ssim(Context& ctx, const ImageRgb8& original, const std
 }
 // ssw_collude_rgb8 on host images of one size: one forged frame per coalition, in order.
 inline std::vector<ImageRgb8> collude(Context& ctx, const std::vector<const ImageRgb8*>& copies, const std::vector<Coalition>& coalitions) {
-    if (copies.empty()) throw Error(SSW_ERR_BAD_ARG, "collude");
-    const size_t n = copies.size(), m = coalitions.size(), w = copies[0]->width, h = copies[0]->height, fb = w * h * 3;
-    std::vector<ssw_coalition> co(m);
-    for (size_t i = 0; i < m; ++i) {
+    std::vector<ssw_coalition> co(coalitions.size());
+    for (size_t i = 0; i < co.size(); ++i) {
         if (coalitions[i].members.empty() || coalitions[i].members.size() > 16) throw Error(SSW_ERR_BAD_ARG, "collude");
         co[i] = ssw_coalition{(uint32_t)coalitions[i].method, (uint32_t)coalitions[i].members.size(), {}};
         std::copy(coalitions[i].members.begin(), coalitions[i].members.end(), co[i].member);
     }
-    detail::DeviceFrames dev(ctx.get(), n * fb, "collude"), forged(ctx.get(), m * fb, "collude");
-    dev.put(copies, w, h, "collude");
-    check(ssw_collude_rgb8(ctx.get(), dev.p, n, w, h, co.data(), m, forged.p), "collude");
-    std::vector<ImageRgb8> out(m);
-    for (size_t i = 0; i < m; ++i) {
-        out[i].width = w; out[i].height = h;
-        out[i].data.resize(fb);
-        check(ssw_copy_to_host(ctx.get(), out[i].data.data(), forged.p + i * fb, fb), "collude");
-    }
-    return out;
+    return detail::frames_through_jobs(ctx, copies, co, "collude", ssw_collude_rgb8);
 }
 
 // One result of wm::jpeg: a frame (an index into the images) and a JPEG quality 1 .. 100
@@ -492,20 +499,9 @@ struct JpegJob {
 // ssw_jpeg_rgb8 on host images of one size: per job that frame as it comes back from a baseline JPEG of that quality -- what
 // libjpeg-turbo's defaults (4:2:0, islow DCT, fancy upsampling) give, byte for byte; include/ssw.h states the steps.
 inline std::vector<ImageRgb8> jpeg(Context& ctx, const std::vector<const ImageRgb8*>& frames, const std::vector<JpegJob>& jobs) {
-    if (frames.empty()) throw Error(SSW_ERR_BAD_ARG, "jpeg");
-    const size_t n = frames.size(), m = jobs.size(), w = frames[0]->width, h = frames[0]->height, fb = w * h * 3;
-    std::vector<ssw_jpeg_job> jb(m);
-    for (size_t i = 0; i < m; ++i) jb[i] = ssw_jpeg_job{jobs[i].frame, jobs[i].quality};
-    detail::DeviceFrames dev(ctx.get(), n * fb, "jpeg"), coded(ctx.get(), m * fb, "jpeg");
-    dev.put(frames, w, h, "jpeg");
-    check(ssw_jpeg_rgb8(ctx.get(), dev.p, n, w, h, jb.data(), m, coded.p), "jpeg");
-    std::vector<ImageRgb8> out(m);
-    for (size_t i = 0; i < m; ++i) {
-        out[i].width = w; out[i].height = h;
-        out[i].data.resize(fb);
-        check(ssw_copy_to_host(ctx.get(), out[i].data.data(), coded.p + i * fb, fb), "jpeg");
-    }
-    return out;
+    std::vector<ssw_jpeg_job> jb(jobs.size());
+    for (size_t i = 0; i < jb.size(); ++i) jb[i] = ssw_jpeg_job{jobs[i].frame, jobs[i].quality};
+    return detail::frames_through_jobs(ctx, frames, jb, "jpeg", ssw_jpeg_rgb8);
 }
 
 // One result of wm::filter: a frame (an index into the images) and one of the three filters of ssw_filter_rgb8
@@ -523,20 +519,9 @@ struct FilterJob {
 // ssw_filter_rgb8 on host images of one size: per job that frame after a Gaussian blur, an unsharp mask or a 3 x 3 median -- what
 // Pillow's filters of those names give, byte for byte; include/ssw.h states the definitions.
 inline std::vector<ImageRgb8> filter(Context& ctx, const std::vector<const ImageRgb8*>& frames, const std::vector<FilterJob>& jobs) {
-    if (frames.empty()) throw Error(SSW_ERR_BAD_ARG, "filter");
-    const size_t n = frames.size(), m = jobs.size(), w = frames[0]->width, h = frames[0]->height, fb = w * h * 3;
-    std::vector<ssw_filter_job> jb(m);
-    for (size_t i = 0; i < m; ++i) jb[i] = ssw_filter_job{jobs[i].frame, jobs[i].kind, jobs[i].radius, jobs[i].percent, jobs[i].threshold};
-    detail::DeviceFrames dev(ctx.get(), n * fb, "filter"), filtered(ctx.get(), m * fb, "filter");
-    dev.put(frames, w, h, "filter");
-    check(ssw_filter_rgb8(ctx.get(), dev.p, n, w, h, jb.data(), m, filtered.p), "filter");
-    std::vector<ImageRgb8> out(m);
-    for (size_t i = 0; i < m; ++i) {
-        out[i].width = w; out[i].height = h;
-        out[i].data.resize(fb);
-        check(ssw_copy_to_host(ctx.get(), out[i].data.data(), filtered.p + i * fb, fb), "filter");
-    }
-    return out;
+    std::vector<ssw_filter_job> jb(jobs.size());
+    for (size_t i = 0; i < jb.size(); ++i) jb[i] = ssw_filter_job{jobs[i].frame, jobs[i].kind, jobs[i].radius, jobs[i].percent, jobs[i].threshold};
+    return detail::frames_through_jobs(ctx, frames, jb, "filter", ssw_filter_rgb8);
 }
 
 // The originals someone owns, as signatures: which of them is a suspect a copy of?  The stage in front of locate / Reader::trace

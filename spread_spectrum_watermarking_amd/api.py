@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -1143,9 +1144,61 @@ def _frames_u8(images, what: str) -> list:
     return [np.ascontiguousarray(a) for a in arrs]
 
 
-def _upload_frames(ctx: Context, buf: "DeviceBuffer", arrs) -> None:
+def _frames_of_side(images, what: str, user: str, side: int) -> list:
+    """`_frames_u8` for `user` ("SSIM", "a JPEG attack"), which refuses frames with a side below `side`"""
+    frames = _frames_u8(images, what)
+    if frames and min(frames[0].shape[:2]) < side:
+        raise ValueError(f"{what}: {user} needs frames of at least {side} x {side} pixels")
+    return frames
+
+
+def _upload_frames(ctx: Context, buf: "DeviceBuffer", arrs) -> "DeviceBuffer":
     for i, a in enumerate(arrs):
         check(ctx._lib.ssw_copy_to_dev(ctx.handle, C.c_void_p(buf.ptr.value + i * a.nbytes), a.ctypes.data, a.nbytes), "ssw_copy_to_dev")
+    return buf
+
+
+@contextmanager
+def _owned(ctx: Context):
+    """The device buffers of one host wrapper's call: yields `alloc`, the context's, and frees every buffer made through it on
+    every way out of the `with` block -- an error from the library leaves nothing to `__del__`."""
+    buffers = []
+
+    def alloc(nbytes: int) -> "DeviceBuffer":
+        buffers.append(ctx.alloc(nbytes))
+        return buffers[-1]
+    try:
+        yield alloc
+    finally:
+        for d in buffers:
+            d.free()
+
+
+def _copies_against_originals(base, cp, what: str, ctx: Optional[Context], outputs, call) -> list:
+    """The driver of `quality` and `ssim`.  base: one original, or one per copy of `cp` (checked here); the copies go up beside
+    their originals in groups of at most UPLOAD_GROUP_BYTES of frames.  Per group call(ctx, dev_base, n_base, dev_copies, n,
+    *dev_outputs) runs on device pointers, then every output comes down -- outputs: one (dtype, shape per copy) each.  Returns
+    per group the list of its downloaded arrays, [n, *shape] each."""
+    b = np.asarray(base) if not isinstance(base, (list, tuple)) else None
+    bases = _frames_u8([base] if b is not None and b.ndim == 3 else base, what)
+    if len(bases) not in (1, len(cp)) or bases[0].shape != cp[0].shape:
+        raise ValueError(f"{what}: one original of the copies' size, or one per copy")
+    ctx = ctx or default_context()
+    fb, n, shared = cp[0].nbytes, len(cp), len(bases) == 1
+    per = max(1, UPLOAD_GROUP_BYTES // (fb if shared else 2 * fb))
+    groups = []
+    with _owned(ctx) as alloc:
+        dev_c = alloc(min(per, n) * fb)
+        dev_o = [alloc(min(per, n) * int(np.prod(shape)) * np.dtype(dtype).itemsize) for dtype, shape in outputs]
+        dev_b = _upload_frames(ctx, alloc(fb), bases) if shared else alloc(min(per, n) * fb)
+        for g0 in range(0, n, per):
+            g = cp[g0:g0 + per]
+            _upload_frames(ctx, dev_c, g)
+            if not shared:
+                _upload_frames(ctx, dev_b, bases[g0:g0 + per])
+            call(ctx, dev_b.ptr, 1 if shared else len(g), dev_c.ptr, len(g), *[d.ptr for d in dev_o])
+            groups.append([d.to_host(dtype, (len(g),) + shape) for d, (dtype, shape) in zip(dev_o, outputs)])
+    return groups
 
 
 def quality(base, copies, ctx: Optional[Context] = None) -> list:
@@ -1154,27 +1207,12 @@ def quality(base, copies, ctx: Optional[Context] = None) -> list:
     cp = _frames_u8(copies, "quality")
     if not cp:
         return []
-    b = np.asarray(base) if not isinstance(base, (list, tuple)) else None
-    bases = _frames_u8([base] if b is not None and b.ndim == 3 else base, "quality")
-    if len(bases) not in (1, len(cp)) or bases[0].shape != cp[0].shape:
-        raise ValueError("quality: one original of the copies' size, or one per copy")
-    ctx = ctx or default_context()
     h, w = cp[0].shape[:2]
-    fb, n, shared = w * h * 3, len(cp), len(bases) == 1
-    per = max(1, UPLOAD_GROUP_BYTES // (fb if shared else 2 * fb))
-    dev_c, dev_s = ctx.alloc(min(per, n) * fb), ctx.alloc(min(per, n) * 8 * L.QUALITY_STATS)
-    dev_b = ctx.to_device(bases[0]) if shared else ctx.alloc(min(per, n) * fb)
-    out = []
-    for g0 in range(0, n, per):
-        g = cp[g0:g0 + per]
-        _upload_frames(ctx, dev_c, g)
-        if not shared:
-            _upload_frames(ctx, dev_b, bases[g0:g0 + per])
-        check(ctx._lib.ssw_quality_rgb8(ctx.handle, dev_b.ptr, 1 if shared else len(g), dev_c.ptr, len(g), w, h, dev_s.ptr), "ssw_quality_rgb8")
-        out += _qualities(dev_s.to_host(np.uint64, (len(g), L.QUALITY_STATS)), w * h)
-    for d in (dev_c, dev_s, dev_b):
-        d.free()
-    return out
+
+    def call(ctx, dev_b, n_base, dev_c, n, dev_stats):
+        check(ctx._lib.ssw_quality_rgb8(ctx.handle, dev_b, n_base, dev_c, n, w, h, dev_stats), "ssw_quality_rgb8")
+    groups = _copies_against_originals(base, cp, "quality", ctx, [(np.uint64, (L.QUALITY_STATS,))], call)
+    return [q for stats, in groups for q in _qualities(stats, w * h)]
 
 
 @dataclass
@@ -1215,43 +1253,21 @@ def _ssims(stats: np.ndarray, nx: int, ny: int, maps=None) -> list:
             for i, (s, key) in enumerate(zip(stats.view(np.int64)[:, 0], stats[:, 1]))]
 
 
-def _ssim_frames(images, what: str) -> list:
-    frames = _frames_u8(images, what)
-    if frames and min(frames[0].shape[:2]) < L.SSIM_MIN_SIDE:
-        raise ValueError(f"{what}: SSIM needs frames of at least {L.SSIM_MIN_SIDE} x {L.SSIM_MIN_SIDE} pixels")
-    return frames
-
-
 def ssim(base, copies, ctx: Optional[Context] = None, maps: bool = False) -> list:
     """One `Ssim` per copy.  base: the original, 8-bit [H, W, 3] -- or one original per copy (a list, or [n, H, W, 3]);
     copies: 8-bit images of that size, no side below 8.  maps: also the value of every window, as `Ssim.map`.  One
     ssw_ssim_rgb8 call per group of at most 256 MiB of frames."""
-    cp = _ssim_frames(copies, "ssim")
+    cp = _frames_of_side(copies, "ssim", "SSIM", L.SSIM_MIN_SIDE)
     if not cp:
         return []
-    b = np.asarray(base) if not isinstance(base, (list, tuple)) else None
-    bases = _frames_u8([base] if b is not None and b.ndim == 3 else base, "ssim")
-    if len(bases) not in (1, len(cp)) or bases[0].shape != cp[0].shape:
-        raise ValueError("ssim: one original of the copies' size, or one per copy")
-    ctx = ctx or default_context()
     h, w = cp[0].shape[:2]
-    (nx, ny), fb, n, shared = _ssim_windows(w, h), w * h * 3, len(cp), len(bases) == 1
-    per = max(1, UPLOAD_GROUP_BYTES // (fb if shared else 2 * fb))
-    dev_c, dev_s = ctx.alloc(min(per, n) * fb), ctx.alloc(min(per, n) * 8 * L.SSIM_STATS)
-    dev_b = ctx.to_device(bases[0]) if shared else ctx.alloc(min(per, n) * fb)
-    dev_m = ctx.alloc(min(per, n) * nx * ny * 4) if maps else None
-    out = []
-    for g0 in range(0, n, per):
-        g = cp[g0:g0 + per]
-        _upload_frames(ctx, dev_c, g)
-        if not shared:
-            _upload_frames(ctx, dev_b, bases[g0:g0 + per])
-        check(ctx._lib.ssw_ssim_rgb8(ctx.handle, dev_b.ptr, 1 if shared else len(g), dev_c.ptr, len(g), w, h, dev_s.ptr, dev_m.ptr if maps else None),
-              "ssw_ssim_rgb8")
-        out += _ssims(dev_s.to_host(np.uint64, (len(g), L.SSIM_STATS)), nx, ny, dev_m.to_host(np.int32, (len(g), ny, nx)) if maps else None)
-    for d in (dev_c, dev_s, dev_b) + ((dev_m,) if maps else ()):
-        d.free()
-    return out
+    nx, ny = _ssim_windows(w, h)
+    outputs = [(np.uint64, (L.SSIM_STATS,))] + ([(np.int32, (ny, nx))] if maps else [])       # the map: one more output per copy
+
+    def call(ctx, dev_b, n_base, dev_c, n, dev_stats, dev_map=None):
+        check(ctx._lib.ssw_ssim_rgb8(ctx.handle, dev_b, n_base, dev_c, n, w, h, dev_stats, dev_map), "ssw_ssim_rgb8")
+    groups = _copies_against_originals(base, cp, "ssim", ctx, outputs, call)
+    return [s for got in groups for s in _ssims(got[0], nx, ny, *got[1:])]
 
 
 def _coalition(method, members, n_copies: int) -> L.Coalition:
@@ -1264,6 +1280,42 @@ def _coalition(method, members, n_copies: int) -> L.Coalition:
     return L.Coalition(m, len(members), (C.c_uint32 * L.COLLUDE_MAX_MEMBERS)(*members))
 
 
+def _job_groups(job_frames, fb: int) -> list:
+    """How jobs that read frames of `fb` bytes and write one each share the device: job_frames[j] are the frames job j reads.
+    Returns the groups (used frames in first-use order, g0, g1) of consecutive jobs g0 .. g1 - 1.  A group always takes its
+    first job; a further job joins while (frames used + its new frames + jobs + 1) * fb <= UPLOAD_GROUP_BYTES."""
+    groups, g0 = [], 0
+    while g0 < len(job_frames):
+        used, g1 = {}, g0                                    # a dict as an ordered set
+        while g1 < len(job_frames):
+            more = [i for i in dict.fromkeys(job_frames[g1]) if i not in used]
+            if g1 > g0 and (len(used) + len(more) + g1 - g0 + 1) * fb > UPLOAD_GROUP_BYTES:
+                break
+            used.update(dict.fromkeys(more))
+            g1 += 1
+        groups.append((list(used), g0, g1))
+        g0 = g1
+    return groups
+
+
+def _run_jobs(ctx: Optional[Context], frames, job_frames, name: str, struct, local) -> list:
+    """The runner of `collude`, `jpeg` and `filter`: the library call `name` (frames in, an array of `struct` jobs, one frame out
+    per job) over the groups of `_job_groups`.  local(j, where): job j as a `struct` that names frame i as where[i], its place
+    among the frames its group sent up.  Returns one u8 [H, W, 3] frame per job, in order."""
+    ctx = ctx or default_context()
+    h, w = frames[0].shape[:2]
+    fb, out = w * h * 3, []
+    for used, g0, g1 in _job_groups(job_frames, fb):
+        where = {i: j for j, i in enumerate(used)}
+        jobs = (struct * (g1 - g0))(*[local(j, where) for j in range(g0, g1)])
+        with _owned(ctx) as alloc:
+            dev_f, dev_o = alloc(len(used) * fb), alloc((g1 - g0) * fb)
+            _upload_frames(ctx, dev_f, [frames[i] for i in used])
+            check(getattr(ctx._lib, name)(ctx.handle, dev_f.ptr, len(used), w, h, jobs, g1 - g0, dev_o.ptr), name)
+            out += list(dev_o.to_host(np.uint8, (g1 - g0, h, w, 3)))
+    return out
+
+
 def collude(copies, coalitions, ctx: Optional[Context] = None) -> list:
     """Forged copies out of several (ssw_collude_rgb8; include/ssw.h states the six definitions).  copies: 8-bit [H, W, 3]
     images of one size; coalitions: (method, members) pairs -- method "average", "median", "min", "max", "minmax" or "mosaic"
@@ -1273,28 +1325,23 @@ def collude(copies, coalitions, ctx: Optional[Context] = None) -> list:
     co = [_coalition(m, mem, len(cp)) for m, mem in coalitions]
     if not co:
         return []
-    ctx = ctx or default_context()
-    h, w = cp[0].shape[:2]
-    fb, out = w * h * 3, []
-    g0 = 0
-    while g0 < len(co):
-        used, g1 = [], g0
-        while g1 < len(co):
-            more = [i for i in dict.fromkeys(co[g1].member[:co[g1].count]) if i not in used]
-            if g1 > g0 and (len(used) + len(more) + g1 - g0 + 1) * fb > UPLOAD_GROUP_BYTES:
-                break
-            used += more
-            g1 += 1
-        where = {i: j for j, i in enumerate(used)}
-        local = (L.Coalition * (g1 - g0))(*[L.Coalition(c.method, c.count, (C.c_uint32 * L.COLLUDE_MAX_MEMBERS)(*[where[i] for i in c.member[:c.count]]))
-                                             for c in co[g0:g1]])
-        dev_c, dev_o = ctx.alloc(len(used) * fb), ctx.alloc((g1 - g0) * fb)
-        _upload_frames(ctx, dev_c, [cp[i] for i in used])
-        check(ctx._lib.ssw_collude_rgb8(ctx.handle, dev_c.ptr, len(used), w, h, local, g1 - g0, dev_o.ptr), "ssw_collude_rgb8")
-        out += list(dev_o.to_host(np.uint8, (g1 - g0, h, w, 3)))
-        dev_c.free(); dev_o.free()
-        g0 = g1
-    return out
+    members = [c.member[:c.count] for c in co]
+    return _run_jobs(ctx, cp, members, "ssw_collude_rgb8", L.Coalition, lambda j, where: L.Coalition(
+        co[j].method, co[j].count, (C.c_uint32 * L.COLLUDE_MAX_MEMBERS)(*[where[i] for i in members[j]])))
+
+
+# An attack on single frames: the library call, its job struct and how a job is made of (frame, parameter) -- what `jpeg`,
+# `filter` and the attack stage of `strength_report` need to know of it
+_JPEG_ATTACK = ("ssw_jpeg_rgb8", L.JpegJob, L.JpegJob)
+_FILTER_ATTACK = ("ssw_filter_rgb8", L.FilterJob, lambda frame, f: f.job(frame))
+
+
+def _attack_every(ctx: Optional[Context], frames, params, attack) -> list:
+    """Every frame under every parameter of `attack`, jobs in frame order: [len(frames)][len(params)] u8 [H, W, 3] frames."""
+    name, struct, job = attack
+    jobs = [(i, p) for i in range(len(frames)) for p in params]
+    flat = _run_jobs(ctx, frames, [(i,) for i, _ in jobs], name, struct, lambda j, where: job(where[jobs[j][0]], jobs[j][1]))
+    return [flat[i * len(params):(i + 1) * len(params)] for i in range(len(frames))]
 
 
 def _jpeg_qualities(qualities, what: str) -> list:
@@ -1304,42 +1351,15 @@ def _jpeg_qualities(qualities, what: str) -> list:
     return [int(q) for q in qs]
 
 
-def _jpeg_frames(images, what: str) -> list:
-    frames = _frames_u8(images, what)
-    if frames and min(frames[0].shape[:2]) < L.JPEG_MIN_SIDE:
-        raise ValueError(f"{what}: a JPEG attack needs frames of at least {L.JPEG_MIN_SIDE} x {L.JPEG_MIN_SIDE} pixels")
-    return frames
-
-
 def jpeg(images, qualities, ctx: Optional[Context] = None) -> list:
     """Every image as it comes back from a baseline JPEG of every quality (ssw_jpeg_rgb8; include/ssw.h states the steps): what
     PIL's save(f, "JPEG", quality=q) and open give, byte for byte, without a bitstream.  images: 8-bit [H, W, 3] of one size, no
     side below 8; qualities: integers 1 .. 100.  Returns [len(images)][len(qualities)] u8 [H, W, 3] frames.  The jobs go in
     groups whose frames and results are at most 256 MiB on the device."""
-    frames, qs = _jpeg_frames(images, "jpeg"), _jpeg_qualities(qualities, "jpeg")
+    frames, qs = _frames_of_side(images, "jpeg", "a JPEG attack", L.JPEG_MIN_SIDE), _jpeg_qualities(qualities, "jpeg")
     if not frames or not qs:
         return [[] for _ in frames]
-    ctx = ctx or default_context()
-    h, w = frames[0].shape[:2]
-    fb, jobs, flat = w * h * 3, [(i, q) for i in range(len(frames)) for q in qs], []
-    g0 = 0
-    while g0 < len(jobs):
-        used, g1 = [], g0                                     # the jobs are in frame order: a group's frames are a run
-        while g1 < len(jobs):
-            new = not used or used[-1] != jobs[g1][0]
-            if g1 > g0 and (len(used) + new + g1 - g0 + 1) * fb > UPLOAD_GROUP_BYTES:
-                break
-            if new:
-                used.append(jobs[g1][0])
-            g1 += 1
-        local = (L.JpegJob * (g1 - g0))(*[L.JpegJob(i - used[0], q) for i, q in jobs[g0:g1]])
-        dev_f, dev_o = ctx.alloc(len(used) * fb), ctx.alloc((g1 - g0) * fb)
-        _upload_frames(ctx, dev_f, [frames[i] for i in used])
-        check(ctx._lib.ssw_jpeg_rgb8(ctx.handle, dev_f.ptr, len(used), w, h, local, g1 - g0, dev_o.ptr), "ssw_jpeg_rgb8")
-        flat += list(dev_o.to_host(np.uint8, (g1 - g0, h, w, 3)))
-        dev_f.free(); dev_o.free()
-        g0 = g1
-    return [flat[i * len(qs):(i + 1) * len(qs)] for i in range(len(frames))]
+    return _attack_every(ctx, frames, qs, _JPEG_ATTACK)
 
 
 @dataclass(frozen=True)
@@ -1405,27 +1425,7 @@ def filter(images, filters, ctx: Optional[Context] = None) -> list:
     frames, fs = _frames_u8(images, "filter"), _filters(filters, "filter")
     if not frames or not fs:
         return [[] for _ in frames]
-    ctx = ctx or default_context()
-    h, w = frames[0].shape[:2]
-    fb, jobs, flat = w * h * 3, [(i, f) for i in range(len(frames)) for f in fs], []
-    g0 = 0
-    while g0 < len(jobs):
-        used, g1 = [], g0                                     # the jobs are in frame order: a group's frames are a run
-        while g1 < len(jobs):
-            new = not used or used[-1] != jobs[g1][0]
-            if g1 > g0 and (len(used) + new + g1 - g0 + 1) * fb > UPLOAD_GROUP_BYTES:
-                break
-            if new:
-                used.append(jobs[g1][0])
-            g1 += 1
-        local = (L.FilterJob * (g1 - g0))(*[f.job(i - used[0]) for i, f in jobs[g0:g1]])
-        dev_f, dev_o = ctx.alloc(len(used) * fb), ctx.alloc((g1 - g0) * fb)
-        _upload_frames(ctx, dev_f, [frames[i] for i in used])
-        check(ctx._lib.ssw_filter_rgb8(ctx.handle, dev_f.ptr, len(used), w, h, local, g1 - g0, dev_o.ptr), "ssw_filter_rgb8")
-        flat += list(dev_o.to_host(np.uint8, (g1 - g0, h, w, 3)))
-        dev_f.free(); dev_o.free()
-        g0 = g1
-    return [flat[i * len(fs):(i + 1) * len(fs)] for i in range(len(frames))]
+    return _attack_every(ctx, frames, fs, _FILTER_ATTACK)
 
 
 @dataclass
@@ -1495,19 +1495,23 @@ def _collusion(method: str, size: int, sims: np.ndarray, threshold: float) -> Co
                      int(over[:size].sum()), int(over[size:].sum()))
 
 
-def _jpeg_result(quality: int, sims: np.ndarray, qualities: list, threshold: float, ssims=()) -> JpegResult:
-    """sims [copies][copies]: row c is copy c after the JPEG against every mark"""
+def _attack_fold(sims: np.ndarray, qualities: list, threshold: float, ssims=()) -> tuple:
+    """What `JpegResult` and `FilterResult` share, in their order: (survived, weakest_own, strongest_innocent, accused, psnr_min,
+    psnr_max, ssim_min, ssim_max).  sims [copies][copies]: row c is copy c after the attack against every mark"""
     mean = [s.mean for s in ssims] or [math.nan]
     own, others = np.diagonal(sims), sims[~np.eye(len(sims), dtype=bool)]
     over = sims > np.float32(threshold)                      # NaN never exceeds (algorithm.rs:677)
     psnr = [q.psnr for q in qualities]
-    return JpegResult(quality, int(np.diagonal(over).sum()), float(own.min()), float(others.max()) if others.size else math.nan,
-                      int(over.sum() - np.diagonal(over).sum()), min(psnr), max(psnr), min(mean), max(mean))
+    return (int(np.diagonal(over).sum()), float(own.min()), float(others.max()) if others.size else math.nan,
+            int(over.sum() - np.diagonal(over).sum()), min(psnr), max(psnr), min(mean), max(mean))
+
+
+def _jpeg_result(quality: int, sims: np.ndarray, qualities: list, threshold: float, ssims=()) -> JpegResult:
+    return JpegResult(quality, *_attack_fold(sims, qualities, threshold, ssims))
 
 
 def _filter_result(label: str, sims: np.ndarray, qualities: list, threshold: float, ssims=()) -> FilterResult:
-    j = _jpeg_result(0, sims, qualities, threshold, ssims)
-    return FilterResult(label, j.survived, j.weakest_own, j.strongest_innocent, j.accused, j.psnr_min, j.psnr_max, j.ssim_min, j.ssim_max)
+    return FilterResult(label, *_attack_fold(sims, qualities, threshold, ssims))
 
 
 def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
@@ -1530,9 +1534,9 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     ssw_quality_rgb8 call, and one ssw_ssim_rgb8 with `ssim`): one `FilterResult` per filter in `StrengthRow.filters`.
     Returns one `StrengthRow` per alpha."""
     jq, fl = _jpeg_qualities(jpeg, "strength_report"), _filters(filters, "strength_report")
-    img = (_jpeg_frames if jq else _frames_u8)([image], "strength_report")[0]
+    img = _frames_of_side([image], "strength_report", "a JPEG attack", L.JPEG_MIN_SIDE if jq else 0)[0]
     if ssim:
-        _ssim_frames([img], "strength_report")
+        _frames_of_side([img], "strength_report", "SSIM", L.SSIM_MIN_SIDE)
     sizes, methods = [int(c) for c in sizes], [str(m).lower() for m in methods]
     if any(c > copies for c in sizes):
         raise ValueError("strength_report: a coalition cannot be larger than the number of copies")
@@ -1544,65 +1548,60 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     config = config or WriteConfig.default()
     marks = np.random.default_rng(seed).standard_normal((copies, k)).astype(np.float32)
     h, w = img.shape[:2]
-    fb, nf = w * h * 3, len(plan)
-    dev_img, dev_marks = ctx.to_device(img), ctx.to_device(marks)
-    dev_copies, dev_stats = ctx.alloc(copies * fb), ctx.alloc(copies * 8 * L.QUALITY_STATS)
-    dev_forged, dev_ext, dev_sims = ctx.alloc(max(nf, 1) * fb), ctx.alloc(max(nf * k, 1) * 4), ctx.alloc(max(nf * copies, 1) * 4)
-    nj = len(jq) * copies                                      # JPEG results of an alpha, quality-major
-    jobs = (L.JpegJob * max(nj, 1))(*[L.JpegJob(c, q) for q in jq for c in range(copies)])
-    dev_jpeg = [ctx.alloc(nj * fb), ctx.alloc(nj * k * 4), ctx.alloc(nj * copies * 4), ctx.alloc(nj * 8 * L.QUALITY_STATS)] if nj else []
-    nfl = len(fl) * copies                                     # filtered copies of an alpha, filter-major
-    fjobs = (L.FilterJob * max(nfl, 1))(*[f.job(c) for f in fl for c in range(copies)])
-    dev_filter = [ctx.alloc(nfl * fb), ctx.alloc(nfl * k * 4), ctx.alloc(nfl * copies * 4), ctx.alloc(nfl * 8 * L.QUALITY_STATS)] if nfl else []
-    dev_ssim = [ctx.alloc(max(copies, nj, nfl) * 8 * L.SSIM_STATS)] if ssim else []
-    windows = _ssim_windows(w, h)
+    fb, nf, windows = w * h * 3, len(plan), _ssim_windows(w, h)
     lib, rows = ctx._lib, []
-    for alpha in alphas:
-        cfg = L.Config(config.ordering.tag, config.insertion.tag, float(alpha), config.precision)
-        check(lib.ssw_fingerprint_embed_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, w, h, dev_marks.ptr, copies, k, dev_copies.ptr, None),
-              "ssw_fingerprint_embed_rgb8")
-        check(lib.ssw_quality_rgb8(ctx.handle, dev_img.ptr, 1, dev_copies.ptr, copies, w, h, dev_stats.ptr), "ssw_quality_rgb8")
-        sims = np.zeros((0, copies), np.float32)
-        if nf:
-            check(lib.ssw_collude_rgb8(ctx.handle, dev_copies.ptr, copies, w, h, co, nf, dev_forged.ptr), "ssw_collude_rgb8")
-            check(lib.ssw_fingerprint_trace_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, dev_forged.ptr, nf, w, h, k, dev_marks.ptr, copies,
-                                                 C.c_float(threshold), dev_ext.ptr, dev_sims.ptr, None, None, None), "ssw_fingerprint_trace_rgb8")
-            sims = dev_sims.to_host(np.float32, (nf, copies))
-        q = _qualities(dev_stats.to_host(np.uint64, (copies, L.QUALITY_STATS)), w * h)
-        rows.append(StrengthRow(float(alpha), q, [_collusion(m, c, sims[i], threshold) for i, (m, c) in enumerate(plan)]))
-        if ssim:
-            check(lib.ssw_ssim_rgb8(ctx.handle, dev_img.ptr, 1, dev_copies.ptr, copies, w, h, dev_ssim[0].ptr, None), "ssw_ssim_rgb8")
-            rows[-1].ssim = _ssims(dev_ssim[0].to_host(np.uint64, (copies, L.SSIM_STATS)), *windows)
-        if nj:
-            dev_frames, dev_jext, dev_jsims, dev_jstats = dev_jpeg
-            check(lib.ssw_jpeg_rgb8(ctx.handle, dev_copies.ptr, copies, w, h, jobs, nj, dev_frames.ptr), "ssw_jpeg_rgb8")
-            check(lib.ssw_fingerprint_trace_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, dev_frames.ptr, nj, w, h, k, dev_marks.ptr, copies,
-                                                 C.c_float(threshold), dev_jext.ptr, dev_jsims.ptr, None, None, None), "ssw_fingerprint_trace_rgb8")
-            check(lib.ssw_quality_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, nj, w, h, dev_jstats.ptr), "ssw_quality_rgb8")
-            jsims = dev_jsims.to_host(np.float32, (len(jq), copies, copies))
-            jstats = _qualities(dev_jstats.to_host(np.uint64, (nj, L.QUALITY_STATS)), w * h)
-            jssim = []
+    with _owned(ctx) as alloc:
+        def trace(cfg, dev_frames, n, dev_e, dev_s):
+            check(lib.ssw_fingerprint_trace_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, dev_frames.ptr, n, w, h, k, dev_marks.ptr, copies,
+                                                 C.c_float(threshold), dev_e.ptr, dev_s.ptr, None, None, None), "ssw_fingerprint_trace_rgb8")
+
+        def measure(dev_frames, n, dev_st):
+            check(lib.ssw_quality_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, n, w, h, dev_st.ptr), "ssw_quality_rgb8")
+
+        def ssims_of(dev_frames, n):
+            check(lib.ssw_ssim_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, n, w, h, dev_ssim.ptr, None), "ssw_ssim_rgb8")
+            return _ssims(dev_ssim.to_host(np.uint64, (n, L.SSIM_STATS)), *windows)
+
+        def stage(attack, params):       # every copy under every parameter, parameter-major: the call, its jobs, their number, the results' buffers
+            name, struct, job = attack
+            n = len(params) * copies
+            return (name, (struct * n)(*[job(c, p) for p in params for c in range(copies)]), n,
+                    [alloc(n * b) for b in (fb, k * 4, copies * 4, 8 * L.QUALITY_STATS)] if n else None)
+
+        def attacked(cfg, made, labels, result):       # attack, trace, quality, the downloads, SSIM: one `result` per label
+            name, jobs, n, (dev_frames, dev_e, dev_s, dev_st) = made
+            check(getattr(lib, name)(ctx.handle, dev_copies.ptr, copies, w, h, jobs, n, dev_frames.ptr), name)
+            trace(cfg, dev_frames, n, dev_e, dev_s)
+            measure(dev_frames, n, dev_st)
+            sims = dev_s.to_host(np.float32, (len(labels), copies, copies))
+            q = _qualities(dev_st.to_host(np.uint64, (n, L.QUALITY_STATS)), w * h)
+            s = ssims_of(dev_frames, n) if ssim else []
+            return [result(label, sims[i], q[i * copies:(i + 1) * copies], threshold, s[i * copies:(i + 1) * copies])
+                    for i, label in enumerate(labels)]
+
+        dev_img, dev_marks = _upload_frames(ctx, alloc(img.nbytes), [img]), _upload_frames(ctx, alloc(marks.nbytes), [marks])
+        dev_copies, dev_stats = alloc(copies * fb), alloc(copies * 8 * L.QUALITY_STATS)
+        dev_forged, dev_ext, dev_sims = alloc(max(nf, 1) * fb), alloc(max(nf * k, 1) * 4), alloc(max(nf * copies, 1) * 4)
+        jpeg_stage, filter_stage = stage(_JPEG_ATTACK, jq), stage(_FILTER_ATTACK, fl)
+        dev_ssim = alloc(max(copies, jpeg_stage[2], filter_stage[2]) * 8 * L.SSIM_STATS) if ssim else None
+        for alpha in alphas:
+            cfg = L.Config(config.ordering.tag, config.insertion.tag, float(alpha), config.precision)
+            check(lib.ssw_fingerprint_embed_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, w, h, dev_marks.ptr, copies, k, dev_copies.ptr, None),
+                  "ssw_fingerprint_embed_rgb8")
+            measure(dev_copies, copies, dev_stats)
+            sims = np.zeros((0, copies), np.float32)
+            if nf:
+                check(lib.ssw_collude_rgb8(ctx.handle, dev_copies.ptr, copies, w, h, co, nf, dev_forged.ptr), "ssw_collude_rgb8")
+                trace(cfg, dev_forged, nf, dev_ext, dev_sims)
+                sims = dev_sims.to_host(np.float32, (nf, copies))
+            q = _qualities(dev_stats.to_host(np.uint64, (copies, L.QUALITY_STATS)), w * h)
+            rows.append(StrengthRow(float(alpha), q, [_collusion(m, c, sims[i], threshold) for i, (m, c) in enumerate(plan)]))
             if ssim:
-                check(lib.ssw_ssim_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, nj, w, h, dev_ssim[0].ptr, None), "ssw_ssim_rgb8")
-                jssim = _ssims(dev_ssim[0].to_host(np.uint64, (nj, L.SSIM_STATS)), *windows)
-            rows[-1].jpeg = [_jpeg_result(qu, jsims[i], jstats[i * copies:(i + 1) * copies], threshold, jssim[i * copies:(i + 1) * copies])
-                             for i, qu in enumerate(jq)]
-        if nfl:
-            dev_frames, dev_fext, dev_fsims, dev_fstats = dev_filter
-            check(lib.ssw_filter_rgb8(ctx.handle, dev_copies.ptr, copies, w, h, fjobs, nfl, dev_frames.ptr), "ssw_filter_rgb8")
-            check(lib.ssw_fingerprint_trace_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, dev_frames.ptr, nfl, w, h, k, dev_marks.ptr, copies,
-                                                 C.c_float(threshold), dev_fext.ptr, dev_fsims.ptr, None, None, None), "ssw_fingerprint_trace_rgb8")
-            check(lib.ssw_quality_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, nfl, w, h, dev_fstats.ptr), "ssw_quality_rgb8")
-            fsims = dev_fsims.to_host(np.float32, (len(fl), copies, copies))
-            fstats = _qualities(dev_fstats.to_host(np.uint64, (nfl, L.QUALITY_STATS)), w * h)
-            fssim = []
-            if ssim:
-                check(lib.ssw_ssim_rgb8(ctx.handle, dev_img.ptr, 1, dev_frames.ptr, nfl, w, h, dev_ssim[0].ptr, None), "ssw_ssim_rgb8")
-                fssim = _ssims(dev_ssim[0].to_host(np.uint64, (nfl, L.SSIM_STATS)), *windows)
-            rows[-1].filters = [_filter_result(f.label, fsims[i], fstats[i * copies:(i + 1) * copies], threshold, fssim[i * copies:(i + 1) * copies])
-                                for i, f in enumerate(fl)]
-    for d in [dev_img, dev_marks, dev_copies, dev_stats, dev_forged, dev_ext, dev_sims] + dev_jpeg + dev_filter + dev_ssim:
-        d.free()
+                rows[-1].ssim = ssims_of(dev_copies, copies)
+            if jq:
+                rows[-1].jpeg = attacked(cfg, jpeg_stage, jq, _jpeg_result)
+            if fl:
+                rows[-1].filters = attacked(cfg, filter_stage, [f.label for f in fl], _filter_result)
     return rows
 
 

@@ -411,18 +411,17 @@ def cmd_strength(args, out=None) -> int:
     if args.json:
         import json
         num = lambda v: None if v != v else (v if abs(v) != float("inf") else str(v))      # JSON has no NaN / Infinity
+
+        def attack(key, a):                                  # a JpegResult or a FilterResult: `key` names its first field
+            return {key: getattr(a, key), "survived": a.survived, "accused": a.accused, "weakest_own": num(a.weakest_own),
+                    "strongest_innocent": num(a.strongest_innocent), "psnr_min": num(a.psnr_min), "psnr_max": num(a.psnr_max)}
         doc = [{"alpha": r.alpha,
                 "copies": [{"psnr": num(q.psnr), "psnr_luma": num(q.psnr_luma), "sse": list(q.sse), "sse_luma": q.sse_luma,
                             "changed": q.changed, "max_abs": q.max_abs, "pixels": q.pixels} for q in r.quality],
                 "collusions": [{"method": c.method, "size": c.size, "found": c.found, "accused": c.accused,
                                 "weakest_colluder": num(c.weakest_colluder), "strongest_innocent": num(c.strongest_innocent)}
                                for c in r.collusions],
-                "jpeg": [{"quality": j.quality, "survived": j.survived, "accused": j.accused, "weakest_own": num(j.weakest_own),
-                          "strongest_innocent": num(j.strongest_innocent), "psnr_min": num(j.psnr_min), "psnr_max": num(j.psnr_max)}
-                         for j in r.jpeg],
-                "filters": [{"filter": f.filter, "survived": f.survived, "accused": f.accused, "weakest_own": num(f.weakest_own),
-                             "strongest_innocent": num(f.strongest_innocent), "psnr_min": num(f.psnr_min), "psnr_max": num(f.psnr_max)}
-                            for f in r.filters]} for r in rows]
+                "jpeg": [attack("quality", j) for j in r.jpeg], "filters": [attack("filter", f) for f in r.filters]} for r in rows]
         for d, r in zip(doc, rows):
             for c, s in zip(d["copies"], r.ssim):
                 c.update({"ssim": s.mean, "ssim_worst": s.worst_value, "ssim_worst_at": list(s.worst_position)})
@@ -444,18 +443,12 @@ def cmd_strength(args, out=None) -> int:
             accused = f", {c.accused} innocent accused" if c.accused else ""
             print(f"  {c.method} of {c.size}: found {c.found}/{c.size}, weakest colluder {c.weakest_colluder:.2f}, "
                   f"strongest innocent {innocent}{accused}", file=out)
-        for j in r.jpeg:
-            innocent = "none" if j.strongest_innocent != j.strongest_innocent else f"{j.strongest_innocent:.1f}"
-            accused = f", {j.accused} innocent accused" if j.accused else ""
-            ssim = f", ssim {j.ssim_min:.2f} .. {j.ssim_max:.2f}" if r.ssim else ""
-            print(f"  jpeg {j.quality}: own mark found {j.survived}/{len(r.quality)}, weakest {j.weakest_own:.1f}, "
-                  f"strongest innocent {innocent}{accused}, {j.psnr_min:.1f} .. {j.psnr_max:.1f} dB{ssim}", file=out)
-        for f in r.filters:
-            innocent = "none" if f.strongest_innocent != f.strongest_innocent else f"{f.strongest_innocent:.1f}"
-            accused = f", {f.accused} innocent accused" if f.accused else ""
-            ssim = f", ssim {f.ssim_min:.2f} .. {f.ssim_max:.2f}" if r.ssim else ""
-            print(f"  {f.filter}: own mark found {f.survived}/{len(r.quality)}, weakest {f.weakest_own:.1f}, "
-                  f"strongest innocent {innocent}{accused}, {f.psnr_min:.1f} .. {f.psnr_max:.1f} dB{ssim}", file=out)
+        for label, a in [(f"jpeg {j.quality}", j) for j in r.jpeg] + [(f.filter, f) for f in r.filters]:
+            innocent = "none" if a.strongest_innocent != a.strongest_innocent else f"{a.strongest_innocent:.1f}"
+            accused = f", {a.accused} innocent accused" if a.accused else ""
+            ssim = f", ssim {a.ssim_min:.2f} .. {a.ssim_max:.2f}" if r.ssim else ""
+            print(f"  {label}: own mark found {a.survived}/{len(r.quality)}, weakest {a.weakest_own:.1f}, "
+                  f"strongest innocent {innocent}{accused}, {a.psnr_min:.1f} .. {a.psnr_max:.1f} dB{ssim}", file=out)
     return 0
 
 

@@ -91,3 +91,47 @@ def test_cpp_doc_test_flow_matches_oracle(tmp_path):
     assert np.mean(marked8 == o_marked8) >= 0.9999
     _, o_sim8 = O.extract_frame(O.u8_to_f32(img8), O.u8_to_f32(marked8), mark)
     assert abs(float(vals["similarity8"]) - o_sim8) < 1e-4 * max(1.0, abs(o_sim8))
+
+
+def build_strength_wrappers(tmpdir, *flags):
+    exe = os.path.join(str(tmpdir), "strength_wrappers_test")
+    return exe, subprocess.run(["g++", "-std=c++17", "-O1", *flags, "-I", os.path.join(ROOT, "include"),
+                                os.path.join(ROOT, "tests", "cpp", "strength_wrappers_test.cpp"), "-o", exe,
+                                "-L", LIBDIR, "-lssw_hip", f"-Wl,-rpath,{LIBDIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True, capture_output=True, text=True)
+
+
+def test_cpp_strength_wrappers_compile_without_warnings(tmp_path):
+    exe, done = build_strength_wrappers(tmp_path, "-Wall", "-Wextra")
+    assert os.path.exists(exe) and done.stderr == "", done.stderr
+
+
+@pytest.mark.gpu
+def test_cpp_strength_wrappers_answer_what_the_python_ones_do(tmp_path):
+    """wm::quality, ssim, collude, jpeg and filter of include/ssw.hpp, run: two 24 x 40 copies of an original, every byte and
+    every statistic against api.quality, ssim, collude, jpeg and filter on the same frames -- both routes end in the same
+    library calls, so nothing may differ."""
+    import spread_spectrum_watermarking_amd as wm
+    exe, _ = build_strength_wrappers(tmp_path)
+    h, w = 24, 40
+    rng = np.random.default_rng(11)
+    original = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    copies = [np.clip(original.astype(np.int16) + rng.integers(-6, 7, original.shape), 0, 255).astype(np.uint8) for _ in range(2)]
+    p = lambda n: os.path.join(str(tmp_path), n)
+    for name, frame in (("original.u8", original), ("copy0.u8", copies[0]), ("copy1.u8", copies[1])):
+        frame.tofile(p(name))
+    run = subprocess.run([exe, p("original.u8"), p("copy0.u8"), p("copy1.u8"), str(w), str(h), p("frames.u8")], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr
+    lines = [[int(v) for v in line.split()[1:]] for line in run.stdout.splitlines()]
+    assert [line.split()[0] for line in run.stdout.splitlines()] == ["quality"] * 2 + ["ssim"] * 2
+    ctx = wm.Context(0)
+    assert lines[:2] == [[*q.sse, q.sse_luma, q.changed, q.max_abs, q.pixels] for q in wm.quality(original, copies, ctx)]
+    assert lines[2:] == [[s.sum, s.worst, *s.worst_position, s.windows_x * s.windows_y] for s in wm.ssim(original, copies, ctx)]
+    filters = [wm.Filter.blur(1.5), wm.Filter.median(), wm.Filter.unsharp()]
+    expected = (wm.collude(copies, [("median", [0, 1]), ("mosaic", [1])], ctx) + [f for per in wm.jpeg(copies, (75, 10), ctx) for f in per]
+                + [f for per in wm.filter(copies, filters, ctx) for f in per])
+    got = np.fromfile(p("frames.u8"), np.uint8).reshape(-1, h, w, 3)
+    assert len(expected) == len(got) == 12
+    for i, e in enumerate(expected):
+        assert np.array_equal(got[i], e), i
+    assert not np.array_equal(got[0], got[1]) and not np.array_equal(got[2], got[3]) and not np.array_equal(got[6], got[7])
+    ctx.close()
