@@ -9,7 +9,7 @@
 // = 4 H (times the largest squared orthonormal scale for EnergyOrthogonal) rounded up by 2^-5, which covers the f32
 // rounding of the sum (<= (H + 32) 2^-24 relative: H < 2^17), of the coefficient (2^-24), of the key (2^-23) and of G E.
 //
-// The column pass runs in two phases (FuseCols::tile_mode): tile 0 (columns 0 .. 127) of every frame first; then this
+// The column pass runs in two phases (BasePart::Phase1Cols / Phase2Cols): tile 0 (columns 0 .. 127) of every frame first; then this
 // file's kernel takes T = a lower bound of the k-th largest key among tile 0's coefficients and marks the tiles t > 0
 // that hold a column with !(boundkey < T); the second phase computes those.  A skipped coefficient has key <= boundkey <
 // T <= the k-th computed key, strictly: at least k computed keys rank ahead of it, ties included, so the first k

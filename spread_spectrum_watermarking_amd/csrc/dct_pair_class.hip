@@ -76,6 +76,33 @@ double pair_class_flop(PairClass c, size_t lines, size_t len) {
     return 4.0 * (double)lines * (double)(leff / r.np_div) * (double)(leff / r.k_div);
 }
 
+// More than one tile column, of 64 or 48 pairs (not the 32-pair tiles of a small launch), in the class-major output map.
+// (sums of more than 256 terms stay exact: the accumulation term of the bound grows with the sum length times the line's norm,
+// and at 8K -- 480 terms -- it passed the threshold on every tail tile of the 8K benchmark frames)
+// (the bound kernel adds a term for both outputs of every tail pair: that is the exact epilogue's set of outputs only while
+// every pair has both -- np1 = none, p2lo = 0 -- and a class is plain or split, pm 0 / 1)
+bool base_tail_class_ok(const PairClassArgs& ca) {
+    return ca.tiles_n >= 2 && ca.Kp <= 256 && ca.gsh <= 16 && ca.bn32 != 1 && ca.np1 == 0xFFFFFFFFu && ca.p2lo == 0 && ca.pm <= 1;
+}
+
+int base_tail_plan(size_t len, const PairLayout& layout, bool tile48, BaseTailPlan& plan) {
+    plan = BaseTailPlan();
+    unsigned pair0 = 0, np = 0;
+    for (int c = 0; c < 8; ++c) {
+        PairClassArgs ca;
+        PairInstance inst;
+        SSW_TRY(pair_class_args(kLevel2Classes[c], true, false, len, layout, false, false, tile48, ca, inst));
+        const unsigned p0 = ca.bn32 == 2 ? 48u : 64u;              // the head: tile column 0
+        if (!base_tail_class_ok(ca) || (c > 0 && (p0 != pair0 || ca.NP != np))) { plan = BaseTailPlan(); return SSW_OK; }
+        pair0 = p0; np = ca.NP;
+        plan.cls[c] = {ca.Kp, ca.yrows, ca.pm, ca.c1, ca.c2, ca.gsh, ca.e2off};
+    }
+    plan.eligible = true;
+    plan.pair0 = pair0; plan.NP = np;
+    plan.chunks = ((np - pair0 + 15) / 16 + 10) / 11;
+    return SSW_OK;
+}
+
 int prune_class_list(const PassPlan& rows, PairClass out[8]) {
     typedef PairClass C;
     int n = 0;

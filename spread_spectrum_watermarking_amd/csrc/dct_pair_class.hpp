@@ -129,6 +129,19 @@ int pair_class_args(PairClass c, bool is_row, bool inverse, size_t len, const Pa
 // executed flop of one launch of class `c`: two products of lines x pairs x sum length multiply-adds
 double pair_class_flop(PairClass c, size_t lines, size_t len);
 
+// The low-precision tail bound of a pruned base reader's row pass (base_energy.hip): whether a class's launch can be cut into
+// tile column 0 (the head) and gated tail launches whose energies the bound kernel covers ...
+bool base_tail_class_ok(const PairClassArgs& ca);
+// ... and the same for the level-2 row pass over lines of length `len` (kLevel2Classes, in their order): eligible when every
+// class is and all agree on the first tail pair and the pair count; then the numbers the bound kernel takes per class
+// (BaseEnergyClass) and its chunks of 11 MFMA pair tiles.  Not eligible: every number is 0.  No device pointer in here.
+struct BaseTailPlan {
+    bool eligible = false;
+    unsigned pair0 = 0, NP = 0, chunks = 0;
+    struct Class { unsigned Kp = 0, yrows = 0, pm = 0, c1 = 0, c2 = 0, gsh = 0, e2off = 0; } cls[8];
+};
+int base_tail_plan(size_t len, const PairLayout& layout, bool tile48, BaseTailPlan& plan);
+
 // The pruned derived row pass (prune.hip): the classes a row plan launches, in the plan's order, and their rows of the
 // PrunePlan for `cap` gathered columns -- each class's forward frequency map as (mod, rem, rem2, radd).
 struct PrunePlan;

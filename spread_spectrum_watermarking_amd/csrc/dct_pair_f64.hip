@@ -57,6 +57,13 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     if (fuse && (!(fuse_rows || fuse_cols) || fuse_rows != is_row || inverse || w % 128 != 0 || h % 16 != 0 ||
                  pair_kpad(h / 8) != dct_pair_fused_units(h))) return SSW_ERR_BAD_ARG;
     if (fuse_rows && (!lay.class_major || sink || !fuse->cop || !fuse->rot1 || !fuse->rot2 || !fuse->rot3)) return SSW_ERR_BAD_ARG;
+    // pruned base reader: the part this launch is, on the pass it belongs to and with the pointers it reads
+    typedef BasePart P;
+    const P part = fuse ? fuse->part : P::None;
+    const bool energy = part == P::EnergyRows || part == P::HeadRows, gated = part == P::TailRows || part == P::Phase2Cols;
+    const bool col_part = part == P::Phase1Cols || part == P::Phase2Cols;
+    if (part != P::None && (col_part ? !fuse_cols : !fuse_rows)) return SSW_ERR_BAD_ARG;
+    if ((energy && !fuse->energy) || (gated && !fuse->need)) return SSW_ERR_BAD_ARG;
     const size_t lines = fuse_rows ? n_frames * 16 * dct_pair_fused_units(h) : is_row ? n_frames * h : n_frames * w;
     const size_t len = is_row ? w : h;
     if (lines > 0xFFFFFFFFull) return SSW_ERR_BAD_DIMS;
@@ -82,16 +89,14 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     // 64-line tiles when 128-line ones would not fill the 512 block slots of the chip (2 per CU)
     const bool small = (unsigned long long)((L + 127) / 128) * tiles_n < 448;
     if (fuse && small) return SSW_ERR_BAD_ARG;
-    // pruned base reader, low-precision tail bound (base_energy.hip): the head launches run tile column 0 of every class,
-    // the gated tail launches the others (the planner sized the launch by all of them: `small` above)
-    const int row_part = fuse_rows ? fuse->row_part : 0;
-    if (row_part) {
-        if ((row_part == 2 && !fuse->need) || (row_part != 1 && row_part != 2)) return SSW_ERR_BAD_ARG;
+    // low-precision tail bound (base_energy.hip): the head launches run tile column 0 of every class, the gated tail
+    // launches the others (the planner sized the launch by all of them: `small` above)
+    if (part == P::HeadRows || part == P::TailRows) {
         tiles_n = 0;
         for (int c = 0; c < n_classes; ++c) {
             PairClassArgs& ca = ml.c[c];
-            if (ca.tiles_n < 2 || ca.gsh > 16 || ca.bn32 == 1) return SSW_ERR_BAD_ARG;
-            if (row_part == 1) ca.tiles_n = 1;
+            if (!base_tail_class_ok(ca)) return SSW_ERR_BAD_ARG;
+            if (part == P::HeadRows) ca.tiles_n = 1;
             else { ca.tn0 = 1; ca.tiles_n -= 1; }
             tiles_n += ca.tiles_n;
         }
@@ -101,8 +106,7 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
         for (int c = 0; c < n_classes; ++c)
             if (ml.c[c].bn32 == 2) { tiles_n -= ml.c[c].tiles_n; ml.c[c].bn32 = 0; ml.c[c].tiles_n = (ml.c[c].NP + 63) / 64; tiles_n += ml.c[c].tiles_n; }
     // (phase 1 of a pruned base reader computes one 128-line tile per frame: its grid is that small, the kernel maps it)
-    const bool tile0_grid = fuse_cols && fuse->tile_mode == 1;
-    const unsigned tiles_m = tile0_grid ? (unsigned)n_frames : (L + BM - 1) / BM;
+    const unsigned tiles_m = part == P::Phase1Cols ? (unsigned)n_frames : (L + BM - 1) / BM;
     // ... and 32-pair tiles when that spreads such a (single-class) launch more evenly over the 256 CUs (all its blocks are
     // resident at once, so a launch takes as long as the fullest CU): balance = blocks / (256 * ceil(blocks / 256)); the
     // smaller tiles reuse their basis fragments less, hence the 8 % handicap
@@ -133,15 +137,14 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
         inst.epi = EPI_FWD_COLOP;
     }
     if (fuse_cols) po.xperm = 1;
-    const bool energy = fuse_rows && fuse->energy != nullptr;
     po.col_energy = energy ? fuse->energy : nullptr;
     ml.need = nullptr; ml.need_mode = 0; ml.need_tpf = 1;
-    if (fuse_cols && fuse->tile_mode) {
-        if (inst.epi != EPI_FWD || inst.samex || small || (fuse->tile_mode == 2 && !fuse->need)) return SSW_ERR_BAD_ARG;
-        ml.need = fuse->need; ml.need_mode = (unsigned)fuse->tile_mode; ml.need_tpf = (unsigned)(w / 128);
+    if (col_part) {                                      // need_mode: 1 = the grid over tile 0, 2 = the flagged tiles beyond it
+        if (inst.epi != EPI_FWD || inst.samex || small) return SSW_ERR_BAD_ARG;
+        ml.need = fuse->need; ml.need_mode = part == P::Phase1Cols ? 1u : 2u; ml.need_tpf = (unsigned)(w / 128);
     }
-    if (row_part == 2) {
-        if (energy || po.ft != 128) return SSW_ERR_BAD_ARG;
+    if (part == P::TailRows) {
+        if (po.ft != 128) return SSW_ERR_BAD_ARG;
         ml.need = fuse->need; ml.need_tpf = (unsigned)(w / 128);
         ml.tail = fuse->tail; ml.tail_flop = fuse->tail_flop; ml.tail_bytes = fuse->tail_bytes;
     }
@@ -156,7 +159,7 @@ int launch_dct_pair_gemm_multi_f64(hipStream_t st, bool is_row, bool inverse, in
     switch (inst.epi) {
     case EPI_FWD_COLOP:
         // (the energy instances are named SUB + 10: the writer's row launches stay the kernels they were)
-        if (row_part == 2) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 5, 128);      // (the gated tail launches: one instance)
+        if (part == P::TailRows) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 5, 128);      // (the gated tail launches: one instance)
         else if (energy) { if (inst.subname == 4) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 14, 128); else SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 13, 128); }
         else if (inst.subname == 4) SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 4, 128);
         else SSW_LAUNCH_PAIR_BM(false, EPI_FWD_COLOP, false, 3, 128);

@@ -82,10 +82,10 @@ struct PairMulti {
     PairClassArgs c[8];
     unsigned n_classes, L, tiles_m, tiles_n_total;
     PairOut po;                        // the fields the classes share; c1 .. bn32 are overwritten per class
-    // forward column launches of a pruned base reader (FuseCols::tile_mode): line tile tm = frame * need_tpf + column tile
+    // forward column launches of a pruned base reader (BasePart::Phase1Cols / Phase2Cols): line tile tm = frame * need_tpf + column tile
     const unsigned* need = nullptr;
     unsigned need_mode = 0, need_tpf = 1;
-    // gated tail row launches of a pruned base reader (SUB 5, FuseCols::row_part 2): `need` as above with need_tpf = column
+    // gated tail row launches of a pruned base reader (SUB 5, BasePart::TailRows): `need` as above with need_tpf = column
     // tiles per frame; tail[0] counts the (frame, class, tile column) jobs that ran, tail[1] / tail[2] (doubles) their flop and
     // bytes at tail_flop / tail_bytes per pair of a job
     unsigned long long* tail = nullptr;

@@ -124,15 +124,24 @@ struct Xform {
     // natural order (the compact plane of the pruned transform has its own)
     size_t full_h = 0;
     bool natural_order = false;
-    // fused forward transform of a base reader whose plane feeds only the selection of the first k keys and reads at those
-    // indices (batch extract): the column pass in two phases on the tiles that can hold one (base_prune.hip)
-    const BasePrune* base_prune = nullptr;
 };
 int build_transform(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, Chain& ch, bool* fused_rgb = nullptr);
 bool can_fuse_rgb(const ssw_ctx* ctx, bool f64, size_t w, size_t h, const float* y, const float* tmp, const void* rgb, PixFmt fmt);
 // rgb -> Y (+ I, Q) -> forward transform of Y into `y` (Writer::new / Reader::new_impl), fused where possible
 int build_forward_from_rgb(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, PixFmt fmt, size_t n, size_t w,
-                           size_t h, float* y, float* i, float* q, float* tmp, Chain& ch, const BasePrune* base_prune = nullptr);
+                           size_t h, float* y, float* i, float* q, float* tmp, Chain& ch);
+// Reader::base of a batch extract (base_prune.hip): the same transform of Y only, with the column pass in two phases on the
+// tiles that can hold one of the first k keys where the fused forward transform applies; *mask = `need` then, else null.
+// One lane's buffers: energy [n][W] f32 | need [n][W / 128] u32; `counters`: the context's block, or null (nothing counted).
+struct BaseReaderArgs {
+    float* energy = nullptr;
+    unsigned* need = nullptr;
+    BasePruneCounters* counters = nullptr;
+    size_t k = 0;
+    int ordering = 0;
+};
+int build_base_reader(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, PixFmt fmt, size_t n, size_t w, size_t h, float* y,
+                      float* tmp, const BaseReaderArgs& a, Chain& ch, const unsigned** mask);
 // the same transform as bands + 1 chains: the row pass of a band of image rows (h / bands of them), and the column pass of the whole frame
 bool can_split_forward_rows(const ssw_ctx* ctx, bool f64, size_t w, size_t h, size_t bands, const float* y, const float* tmp, const void* rgb, PixFmt fmt);
 int build_forward_rows_band(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, PixFmt fmt, size_t w, size_t rows,

@@ -6,7 +6,6 @@
 
 #include <cstddef>
 #include <cstdint>
-#include <functional>
 #include <map>
 #include <string>
 #include <tuple>
@@ -112,18 +111,20 @@ int launch_dct_pair_prep8_cols(hipStream_t st, const float* in, size_t n_frames,
 //                    `cop`; needs the rotation tables of H, H/2, H/4
 //   FUSE_COLS        column launch behind such a row pass: its 128-line tiles are in the row launches' class-major order
 enum { FUSE_ROWS_COP = 1, FUSE_COLS = 2 };
+// ... and which part of a pruned base reader (base_prune.hip, base_energy.hip) it is, with the pointers that part reads:
+//   EnergyRows   row launch over every tile column; `energy` [n][W] receives the sum of squares of every column-operand
+//                line's f32 row-pass values (atomic adds; zeroed by the caller)
+//   HeadRows     low-precision tail bound: tile column 0 of every class only (the head: exact energies into `energy`)
+//   TailRows     ... the other tile columns, each block gated on `need` (no energies); `tail`: [0] jobs that ran, [1] [2]
+//                their flop / bytes as doubles, tail_flop / tail_bytes per pair of a job
+//   Phase1Cols   column launch on a grid over column tile 0 of every frame only
+//   Phase2Cols   column launch that runs the blocks of the tiles t > 0 whose need[frame * (W / 128) + t] is set
+enum class BasePart { None, EnergyRows, HeadRows, TailRows, Phase1Cols, Phase2Cols };
 struct FuseCols {
     int mode = 0; double* cop = nullptr; const double *rot1 = nullptr, *rot2 = nullptr, *rot3 = nullptr;
-    // base-reader pruning (base_prune.hip).  Row launch: `energy` [n][W] receives the sum of squares of every column-operand
-    // line's f32 row-pass values (atomic adds; zeroed by the caller).  Column launch: `tile_mode` 1 is a grid over column
-    // tile 0 of every frame only, 2 runs the blocks of the tiles t > 0 whose need[frame * (W / 128) + t] is set.
+    BasePart part = BasePart::None;
     float* energy = nullptr;
     const unsigned* need = nullptr;
-    int tile_mode = 0;
-    // ... with the low-precision tail bound (base_energy.hip), row launches: `row_part` 1 runs tile column 0 of every class (the
-    // head: exact energies), 2 the other tile columns, each block gated on `need` (no energies); `tail`: [0] jobs that ran,
-    // [1] [2] their flop / bytes as doubles, tail_flop / tail_bytes per pair of a job
-    int row_part = 0;
     unsigned long long* tail = nullptr;
     double tail_flop = 0.0, tail_bytes = 0.0;
 };
@@ -223,12 +224,25 @@ int launch_extract_pruned(hipStream_t st, const float* base, const float* compac
                           float* out);
 
 // base_prune.hip: the base reader's column pass only where a column can hold one of the first k keys.
-// One lane's buffers: energy [n][W] f32 | need [n][W / 128] u32; `stats` (the context's): tiles total, tiles computed,
-// frames whose second phase computed a tile.
 constexpr unsigned SSW_BASE_PRUNE_TILE = 128;
-// the context's counters, 64-bit words: [0 .. 2] `stats` below, [4 .. 6] `work` (doubles); [8] tail jobs that ran (a frame's
-// tile column of one class of the gated row launches, base_energy.hip), [9] [10] their flop and bytes (doubles)
+// The context's counters: one device block of SSW_BASE_PRUNE_STATS 64-bit words.  The kernels get sub-blocks of it by pointer
+// and index them: the decide kernel `stats` (from `tiles`) and `work` (from `col_flop`), the gated tail row launches `tail`
+// (from `tail_jobs`, the doubles behind it as [1] [2]) -- hence the offsets below.
 constexpr unsigned SSW_BASE_PRUNE_STATS = 16;
+struct BasePruneCounters {
+    unsigned long long tiles, tiles_computed, frames_extended;      // frames_extended: frames whose second phase computed a tile
+    unsigned long long pad0;
+    double col_flop, col_bytes, select_bytes;      // second phase: the column launches' computed tiles, the masked selection's reads of them
+    unsigned long long pad1;
+    unsigned long long tail_jobs;                  // a frame's tile column of one class of the gated row launches (base_energy.hip)
+    double tail_flop, tail_bytes;
+    unsigned long long pad2[5];
+};
+static_assert(sizeof(BasePruneCounters) == SSW_BASE_PRUNE_STATS * sizeof(unsigned long long), "the context's block");
+static_assert(offsetof(BasePruneCounters, tiles) == 0 && offsetof(BasePruneCounters, col_flop) == 4 * 8 &&
+              offsetof(BasePruneCounters, tail_jobs) == 8 * 8 && offsetof(BasePruneCounters, tail_flop) == 9 * 8, "the kernels' sub-blocks");
+// What the decide kernel gets.  One lane's buffers: energy [n][W] f32 | need [n][W / 128] u32; `stats` / `work`: the context's
+// counters (BasePruneCounters::tiles / ::col_flop on), or null.
 struct BasePrune {
     float* energy = nullptr;
     unsigned* need = nullptr;
@@ -240,12 +254,6 @@ struct BasePrune {
     // that shapes that differ from call to call are each billed at their own rate
     double* work = nullptr;
     double tile_flop = 0.0, tile_bytes = 0.0, select_bytes = 0.0;
-    // set by the pass builder that enqueues the decide kernel: `need` will hold this chunk's flags, and the tiles it leaves
-    // unset are NOT written -- whoever reads the plane afterwards goes by the flags (launch_topk's mask)
-    bool* decided = nullptr;
-    // low-precision tail bound (base_energy.hip): the row pass's builder leaves the gated tail launches here, the column
-    // pass's builder runs them between the decide kernel and phase 2 (the caller owns the function object)
-    std::function<int(hipStream_t)>* tail = nullptr;
 };
 // G of boundkey(v) = G * E[v]: every key of column v is <= it (rounded up; 0: the ordering has no bound)
 float base_prune_gain(size_t w, size_t h, int ordering);

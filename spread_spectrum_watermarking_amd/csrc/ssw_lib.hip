@@ -481,7 +481,7 @@ int ssw_ctx_reset_timing(ssw_ctx* ctx) {
     SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) SSW_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
     SSW_HIP_CHECK(hipMemset(ctx->select_fallbacks, 0, sizeof(uint32_t)));
-    if (ctx->base_prune_stats.p) SSW_HIP_CHECK(hipMemset(ctx->base_prune_stats.p, 0, SSW_BASE_PRUNE_STATS * sizeof(unsigned long long)));
+    if (ctx->base_prune_stats.p) SSW_HIP_CHECK(hipMemset(ctx->base_prune_stats.p, 0, sizeof(BasePruneCounters)));
     for (double& b : ctx->base_prune_billed) b = 0.0;
     return SSW_OK;
 }
@@ -546,9 +546,9 @@ int ssw_ctx_get_base_prune_stats(ssw_ctx* ctx, uint64_t* stats) {
     if (!ctx->base_prune_stats.p) return SSW_OK;
     SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) SSW_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
-    unsigned long long v[4] = {0, 0, 0, 0};
-    SSW_HIP_CHECK(hipMemcpy(v, ctx->base_prune_stats.p, sizeof(v), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 3; ++i) stats[i] = v[i];
+    BasePruneCounters c;
+    SSW_HIP_CHECK(hipMemcpy(&c, ctx->base_prune_stats.p, sizeof(c), hipMemcpyDeviceToHost));
+    stats[0] = c.tiles; stats[1] = c.tiles_computed; stats[2] = c.frames_extended;
     return SSW_OK;
 }
 
@@ -559,9 +559,9 @@ int ssw_ctx_get_base_prune_tail_jobs(ssw_ctx* ctx, uint64_t* jobs) {
     if (!ctx->base_prune_stats.p) return SSW_OK;
     SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) SSW_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
-    unsigned long long v = 0;
-    SSW_HIP_CHECK(hipMemcpy(&v, (const char*)ctx->base_prune_stats.p + 8 * sizeof(unsigned long long), sizeof(v), hipMemcpyDeviceToHost));
-    *jobs = v;
+    BasePruneCounters c;
+    SSW_HIP_CHECK(hipMemcpy(&c, ctx->base_prune_stats.p, sizeof(c), hipMemcpyDeviceToHost));
+    *jobs = c.tail_jobs;
     return SSW_OK;
 }
 

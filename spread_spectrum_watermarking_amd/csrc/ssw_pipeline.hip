@@ -162,6 +162,7 @@ StageTimer::~StageTimer() {
     if (b) ctx->pending.push_back({stage, a, b, alias});
 }
 
+namespace { int base_prune_bill(ssw_ctx* ctx); }       // (beside the base reader's set-up, below)
 int flush_timers(ssw_ctx* ctx) {
     std::vector<hipEvent_t> used;
     for (auto& p : ctx->pending) {
@@ -180,30 +181,7 @@ int flush_timers(ssw_ctx* ctx) {
     used.erase(std::unique(used.begin(), used.end()), used.end());
     for (hipEvent_t e : used) ctx->free_events.push_back(e);
     ctx->tail_event = nullptr; ctx->tail_fresh = false;
-    // base-reader pruning: the second phase's share of the column launches, and of the masked selection's reads, is known to
-    // the device only -- its tiles are billed here, from the decide kernels' counter (computed tiles beyond every frame's tile
-    // 0, which the host billed)
-    // (each frame at its own shape's rate: the kernels add flop and bytes up as doubles; what was enqueued while the timers
-    // were off is passed over, like every other stage's work)
-    if (ctx->base_prune_stats.p) {
-        double wk[3] = {0.0, 0.0, 0.0};
-        SSW_HIP_CHECK(hipMemcpy(wk, (const char*)ctx->base_prune_stats.p + 4 * sizeof(unsigned long long), sizeof(wk), hipMemcpyDeviceToHost));
-        if (ctx->timing) {
-            ctx->stage_work[SSW_STAGE_DCT_COL] += wk[0] - ctx->base_prune_billed[0];
-            ctx->stage_bytes[SSW_STAGE_DCT_COL] += wk[1] - ctx->base_prune_billed[1];
-            ctx->stage_work[SSW_STAGE_SELECT] += wk[2] - ctx->base_prune_billed[2];       // (an HBM-bound stage: its bytes are its work)
-            ctx->stage_bytes[SSW_STAGE_SELECT] += wk[2] - ctx->base_prune_billed[2];
-        }
-        for (int i = 0; i < 3; ++i) ctx->base_prune_billed[i] = wk[i];
-        // ... and the gated tail row launches' jobs (base_energy.hip), counted by the launches themselves
-        double tw[2] = {0.0, 0.0};
-        SSW_HIP_CHECK(hipMemcpy(tw, (const char*)ctx->base_prune_stats.p + 9 * sizeof(unsigned long long), sizeof(tw), hipMemcpyDeviceToHost));
-        if (ctx->timing) {
-            ctx->stage_work[SSW_STAGE_DCT_ROW] += tw[0] - ctx->base_prune_billed[3];
-            ctx->stage_bytes[SSW_STAGE_DCT_ROW] += tw[1] - ctx->base_prune_billed[4];
-        }
-        for (int i = 0; i < 2; ++i) ctx->base_prune_billed[3 + i] = tw[i];
-    }
+    SSW_TRY(base_prune_bill(ctx));
     return SSW_OK;
 }
 
@@ -237,13 +215,14 @@ int get_basis(ssw_ctx* ctx, size_t n, bool inverse, bool f64, BasisKind kind, co
 
 // Both bases of launch class `c` over a length-`len` axis as f16 hi + lo fragments for the pairs from pair0 on
 // (base_energy.hip), cached in a map of their own and freed with the bases they are made from
-int get_split16(ssw_ctx* ctx, size_t len, PairClass c, const double* y1, const double* y2, const PairClassArgs& ca, unsigned pair0, const void** out) {
+int get_split16(ssw_ctx* ctx, size_t len, PairClass c, const double* y1, const double* y2, unsigned yrows, unsigned NP, unsigned Kp, unsigned pair0,
+                const void** out) {
     auto key = std::make_tuple(len, (int)c, pair0);
     auto it = ctx->split16.find(key);
     if (it != ctx->split16.end()) { *out = it->second; return SSW_OK; }
     void* p = nullptr;
-    SSW_ALLOC(&p, base_energy_split_bytes(ca.NP, ca.Kp, pair0));
-    const int rc = launch_base_energy_split(ctx->stream, y1, y2, ca.yrows, ca.NP, ca.Kp, pair0, p);
+    SSW_ALLOC(&p, base_energy_split_bytes(NP, Kp, pair0));
+    const int rc = launch_base_energy_split(ctx->stream, y1, y2, yrows, NP, Kp, pair0, p);
     untimed_work(ctx);
     if (rc != SSW_OK) { (void)hipFree(p); return rc; }
     ctx->split16[key] = p;
@@ -569,169 +548,185 @@ int build_deep(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
 // its lines (frame, unit of the column fold, line of the unit), the row launches' epilogue (EPI_FWD_COLOP) rounds to f32 --
 // the store between the passes, src/dct2d.rs:152-168 -- applies the column pre-pass's arithmetic and writes the sixteen
 // column-operand planes; the column pass is its eight launches only (4 + 4 + 8 B/px of plane and pre-pass become 8).
-int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
-    ssw_ctx* ctx = b.ctx;
-    const bool fused = b.p.strategy == PassStrategy::FusedRows || b.p.strategy == PassStrategy::FusedCols;
+//
+// What every level-2 route shares, set up once per pass: the operand planes and rotation tables, on a fused transform the
+// column-operand buffer and how a launch takes part (`fc`), the eight launch descriptors of kLevel2Classes, and the accounts
+// of the pass's GEMM stage.
+struct Level2Pass {
+    bool fused = false;
     PairPlanes pp;
     const void *rot2 = nullptr, *rot3 = nullptr;
-    SSW_TRY(pair_planes(b, ws, pp));
-    SSW_TRY(deep_rot(b, true, &rot2, &rot3));
-    const size_t n = b.n, w = b.w, h = b.h;
     FuseCols fc;
-    // base reader of a batch extract: the row launches add up the column energies, the column pass runs in two phases
-    const bool bprune = fused && b.x.base_prune != nullptr;
-    BasePrune bp = bprune ? *b.x.base_prune : BasePrune();
-    double pad = 1.0;                                             // the padding units' share of the flop
-    double bytes = b.gemm_bytes(0.0);
-    float* out = b.dst;
-    if (fused) {
+    double pad = 1.0;                              // the padding units' share of the flop
+    double f_main = 0.0, f_all = 0.0, bytes = 0.0;
+    float* out = nullptr;
+    std::array<PairClassDesc, 8> d;
+};
+int level2_pass(const PassBuild& b, ssw_ctx::Lane& ws, Level2Pass& l2) {
+    ssw_ctx* ctx = b.ctx;
+    const size_t n = b.n, w = b.w, h = b.h;
+    l2.fused = b.p.strategy == PassStrategy::FusedRows || b.p.strategy == PassStrategy::FusedCols;
+    SSW_TRY(pair_planes(b, ws, l2.pp));
+    SSW_TRY(deep_rot(b, true, &l2.rot2, &l2.rot3));
+    l2.bytes = b.gemm_bytes(0.0);
+    l2.out = b.dst;
+    if (l2.fused) {
         const size_t cplane = n * w * dct_pair_split_kpad(h / 2);          // column operands: n w lines, K16(h) wide
         SSW_TRY(grow(ws.operand[0], 16 * cplane * sizeof(double)));
         double* cop = (double*)ws.operand[0].p;
-        fc = FuseCols{FUSE_COLS};
-        if (!b.is_row) { pp.l2 = cop; pp.l2_plane = cplane; }
+        l2.fc = FuseCols{FUSE_COLS};
+        if (!b.is_row) { l2.pp.l2 = cop; l2.pp.l2_plane = cplane; }
         else {
             const void *crot1 = nullptr, *crot2 = nullptr, *crot3 = nullptr;
             SSW_TRY(get_basis(ctx, h, false, true, BasisKind::Rot, &crot1));
             SSW_TRY(get_basis(ctx, h / 2, false, true, BasisKind::Rot, &crot2));
             SSW_TRY(get_basis(ctx, h / 4, false, true, BasisKind::Rot, &crot3));
             const size_t lpad = n * 16 * dct_pair_fused_units(h);           // unit-ordered, padded lines
-            pp.l2_plane = lpad * dct_pair_split_kpad(b.len / 2);
-            pad = (double)lpad / (double)(n * h);
-            fc = FuseCols{FUSE_ROWS_COP, cop, (const double*)crot1, (const double*)crot2, (const double*)crot3};
-            if (bprune) fc.energy = bp.energy;
-            bytes = b.px * 16.0;                                // row operands in, column operands out
-            out = nullptr;
+            l2.pp.l2_plane = lpad * dct_pair_split_kpad(b.len / 2);
+            l2.pad = (double)lpad / (double)(n * h);
+            l2.fc = FuseCols{FUSE_ROWS_COP, cop, (const double*)crot1, (const double*)crot2, (const double*)crot3};
+            l2.bytes = b.px * 16.0;                             // row operands in, column operands out
+            l2.out = nullptr;
         }
     }
-    double* sp = pp.sp;
-    if (!fused || b.is_row)
-        ch.push_back({true, [=](hipStream_t st) -> int {
-            StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
-            if (!b.is_row) return launch_dct_pair_prep16_cols(st, b.src, n, w, h, sp, (const double*)pp.rot, (const double*)rot2, (const double*)rot3,
-                                                              b.p.prep, b.p.layout);
-            return launch_dct_pair_prep16_rows(st, b.row_input(), n, w, h, sp, (const double*)pp.rot, (const double*)rot2, (const double*)rot3, true, fused);
-        }});
-    const double f_main = b.flop(PairClass::O5), f_all = 8.0 * f_main;      // (every class: the same pairs and sum length)
-    std::array<PairClassDesc, 8> d;
-    for (int c = 0; c < 8; ++c) SSW_TRY(deep_desc(b, pp, true, kLevel2Classes[c], d[c]));
-    if (bprune && !b.is_row) {
-        // phase 1: tile 0 of every frame (one launch over the eight classes, a grid of 3 blocks per frame and class); decide;
-        // phase 2: the tiles that can hold one of the first k keys; the others are not written, and the selection that follows
-        // takes the flags as its tile mask (base_prune.hip).  The host bills phase 1; phase 2's tiles are billed from the
-        // device counter when the timers are resolved (flush_timers).
-        const double tiles = (double)(w / SSW_BASE_PRUNE_TILE);
-        bp.tile_flop = f_all / ((double)n * tiles);
-        bp.tile_bytes = bytes / ((double)n * tiles);
-        bp.select_bytes = (double)h * SSW_BASE_PRUNE_TILE * 4.0;
-        if (bp.decided) *bp.decided = true;
-        auto phase = [=](hipStream_t st, int mode) {
-            FuseCols f2 = fc;
-            f2.tile_mode = mode; f2.need = bp.need;
-            return launch_dct_pair_gemm_multi_f64(st, false, false, 8, d.data(), out, nullptr, n, w, h, b.ep, nullptr, nullptr, b.gemm_layout(), &f2);
-        };
+    l2.f_main = b.flop(PairClass::O5); l2.f_all = 8.0 * l2.f_main;         // (every class: the same pairs and sum length)
+    for (int c = 0; c < 8; ++c) SSW_TRY(deep_desc(b, l2.pp, true, kLevel2Classes[c], l2.d[c]));
+    return SSW_OK;
+}
+// the pass's pre-pass (a fused column pass has none: the row launches wrote its operands)
+void push_level2_prep(const PassBuild& b, const Level2Pass& l2, Chain& ch) {
+    if (l2.fused && !b.is_row) return;
+    ssw_ctx* ctx = b.ctx;
+    ch.push_back({true, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
+        const double *rot1 = (const double*)l2.pp.rot, *rot2 = (const double*)l2.rot2, *rot3 = (const double*)l2.rot3;
+        if (!b.is_row) return launch_dct_pair_prep16_cols(st, b.src, b.n, b.w, b.h, l2.pp.sp, rot1, rot2, rot3, b.p.prep, b.p.layout);
+        return launch_dct_pair_prep16_rows(st, b.row_input(), b.n, b.w, b.h, l2.pp.sp, rot1, rot2, rot3, true, l2.fused);
+    }});
+}
+// the pass's GEMM stage: the eight launches, as `fc` says (null: not a fused transform)
+int run_level2_gemm(const PassBuild& b, const Level2Pass& l2, const FuseCols* fc, hipStream_t st) {
+    StageTimer t(b.ctx, b.st_pass, st, l2.f_all * l2.pad, b.p.merge ? b.st_main : -1);      // (merged: a single frame's eight classes in one launch)
+    t.traffic(l2.bytes);
+    auto launch = [&](int nc, const PairClassDesc* dd) {
+        return launch_dct_pair_gemm_multi_f64(st, b.is_row, false, nc, dd, l2.out, nullptr, b.n, b.w, b.h, b.ep, nullptr, nullptr, b.gemm_layout(), fc);
+    };
+    return launch_classes(b.ctx, st, b.p.merge, 8, l2.d.data(), launch, b.st_main, l2.f_main * l2.pad);
+}
+int build_deep_l2(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
+    Level2Pass l2;
+    SSW_TRY(level2_pass(b, ws, l2));
+    push_level2_prep(b, l2, ch);
+    ch.push_back({false, [=](hipStream_t st) -> int { return run_level2_gemm(b, l2, l2.fused ? &l2.fc : nullptr, st); }});
+    return SSW_OK;
+}
+
+// ---- the base reader of a batch extract: the fused forward transform whose row launches add up the column
+// energies (base_energy.hip) and whose column pass runs only where a column can hold one of the first k keys (base_prune.hip);
+// build_base_reader puts the two passes together ----
+typedef std::function<int(hipStream_t)> TailLaunch;
+
+// Row pass: the pre-pass, then one stage that zeroes the energies and runs the eight exact energy launches -- or, with the
+// low-precision tail bound (base_energy.hip), where base_tail_plan finds every class with more than one tile column: the bound
+// kernel over the tail pairs and the energy launches on tile column 0 only (the head).  The exact launches of the other tile
+// columns are then `tail`, each block gated on the flags: they wait for the decide kernel in the column pass's chain.  No such
+// launches: `tail` is empty.
+int build_base_rows(const PassBuild& b, const Level2Pass& l2, const BaseReaderArgs& a, Chain& ch, TailLaunch& tail) {
+    ssw_ctx* ctx = b.ctx;
+    const size_t n = b.n, w = b.w, h = b.h;
+    tail = nullptr;
+    push_level2_prep(b, l2, ch);
+    FuseCols fe = l2.fc;
+    fe.energy = a.energy;
+    BaseTailPlan tp;
+    if (tuning(TUNE_BASE_ENERGY_LOWP) != 0) SSW_TRY(base_tail_plan(b.len, b.gemm_layout(), tuning(TUNE_TILE48) != 0, tp));
+    if (!tp.eligible) {
+        fe.part = BasePart::EnergyRows;
         ch.push_back({false, [=](hipStream_t st) -> int {
-            StageTimer t(ctx, b.st_pass, st, f_all / tiles);
-            t.traffic(bytes / tiles);
-            return phase(st, 1);
-        }});
-        ch.push_back({true, [=](hipStream_t st) -> int {
-            StageTimer t(ctx, SSW_STAGE_SELECT, st, (double)n * ((double)h * SSW_BASE_PRUNE_TILE + (double)w) * 4.0);
-            return launch_base_prune_decide(st, out, bp, n, w, h);
-        }});
-        if (bp.tail && *bp.tail) {
-            // the exact row launches of the tile columns beyond the head, each block gated on the flags (base_energy.hip):
-            // the column operands of the needed tiles are complete before phase 2 reads them
-            const std::function<int(hipStream_t)> tail = *bp.tail;
-            ch.push_back({false, [=](hipStream_t st) -> int {
-                StageTimer t(ctx, SSW_STAGE_DCT_ROW, st, 0.0);
-                return tail(st);
-            }});
-        }
-        ch.push_back({false, [=](hipStream_t st) -> int {
-            StageTimer t(ctx, b.st_pass, st, 0.0);
-            return phase(st, 2);
+            SSW_HIP_CHECK(hipMemsetAsync(a.energy, 0, n * w * sizeof(float), st));
+            untimed_work(ctx);
+            return run_level2_gemm(b, l2, &fe, st);
         }});
         return SSW_OK;
     }
-    if (bprune && bp.tail) *bp.tail = nullptr;
-    if (bprune && b.is_row && bp.tail && tuning(TUNE_BASE_ENERGY_LOWP) != 0) {
-        // Low-precision tail bound (base_energy.hip): where every class has more than one tile column, the energy launches
-        // run tile column 0 only (the head), the bound kernel covers the other pairs, and the exact launches of those tile
-        // columns wait for the decide kernel in the column pass's chain.
-        std::array<BaseEnergyClass, 8> be;
-        bool ok = true;
-        unsigned pair0 = 0, np = 0;
-        double chunks = 1.0;
-        for (int c = 0; c < 8 && ok; ++c) {
-            PairClassArgs ca;
-            PairInstance inst;
-            SSW_TRY(pair_class_args(d[c].cls, true, false, b.len, b.gemm_layout(), false, false, tuning(TUNE_TILE48) != 0, ca, inst));
-            const unsigned p0 = ca.bn32 == 2 ? 48u : 64u;
-            // (sums of more than 256 terms stay exact: the accumulation term of the bound grows with the sum length times the
-            // line's norm, and at 8K -- 480 terms -- it passed the threshold on every tail tile of the 8K benchmark frames)
-            // (the bound kernel adds a term for both outputs of every tail pair: that is the exact epilogue's set of outputs only
-            // while every pair has both -- np1 = none, p2lo = 0 -- and a class is plain or split, pm 0 / 1)
-            ok = ca.tiles_n >= 2 && ca.Kp <= 256 && ca.gsh <= 16 && ca.bn32 != 1 && ca.np1 == 0xFFFFFFFFu && ca.p2lo == 0 && ca.pm <= 1 &&
-                 (c == 0 || (p0 == pair0 && ca.NP == np));
-            if (!ok) break;
-            pair0 = p0; np = ca.NP;
-            const void* y16 = nullptr;
-            SSW_TRY(get_split16(ctx, b.len, d[c].cls, d[c].y1, d[c].y2, ca, pair0, &y16));
-            be[c].x1 = d[c].x1; be[c].x2 = d[c].x2; be[c].y16 = y16;
-            be[c].NP = ca.NP; be[c].Kp = ca.Kp; be[c].pair0 = pair0; be[c].pm = ca.pm; be[c].c1 = ca.c1; be[c].c2 = ca.c2; be[c].gsh = ca.gsh; be[c].e2off = ca.e2off;
-            chunks = (double)(((ca.NP - pair0 + 15) / 16 + 10) / 11);
-        }
-        if (ok) {
-            const size_t lpf = 16 * dct_pair_fused_units(h);
-            const double head = (double)pair0 / (double)np;
-            const double bound_bytes = 8.0 * 2.0 * chunks * (double)(n * lpf) * (double)be[0].Kp * 8.0;
-            unsigned long long* tail_stats = bp.stats ? bp.stats + 8 : nullptr;
-            const double tail_flop = 4.0 * (double)lpf * (double)(b.len / 16), tail_bytes = 16.0 * (double)h;
-            ch.push_back({false, [=](hipStream_t st) -> int {
-                SSW_HIP_CHECK(hipMemsetAsync(bp.energy, 0, n * w * sizeof(float), st));
-                untimed_work(ctx);
-                {
-                    StageTimer tp(ctx, SSW_STAGE_DCT_PREP, st, bound_bytes);
-                    SSW_TRY(launch_base_energy_bound(st, 8, be.data(), n, w, h, lpf, b.ep.base, bp.energy));
-                }
-                FuseCols fh = fc;
-                fh.row_part = 1;
-                // (not billed to the main-launch stage: that figure stays the time and flop of one full launch, the writer's)
-                StageTimer t(ctx, b.st_pass, st, f_all * pad * head);
-                t.traffic(b.px * 8.0 * (1.0 + head));
-                auto launch = [&](int nc, const PairClassDesc* dd) {
-                    return launch_dct_pair_gemm_multi_f64(st, true, false, nc, dd, out, nullptr, n, w, h, b.ep, nullptr, nullptr, b.gemm_layout(), &fh);
-                };
-                return launch_classes(ctx, st, b.p.merge, 8, d.data(), launch);
-            }});
-            const PairLayout lay = b.gemm_layout();
-            const Epilogue ep = b.ep;
-            const bool merge = b.p.merge;
-            *bp.tail = [=](hipStream_t st) -> int {
-                FuseCols ft = fc;
-                ft.row_part = 2; ft.energy = nullptr; ft.need = bp.need;
-                ft.tail = tail_stats; ft.tail_flop = tail_flop; ft.tail_bytes = tail_bytes;
-                auto launch = [&](int nc, const PairClassDesc* dd) {
-                    return launch_dct_pair_gemm_multi_f64(st, true, false, nc, dd, out, nullptr, n, w, h, ep, nullptr, nullptr, lay, &ft);
-                };
-                return launch_classes(ctx, st, merge, 8, d.data(), launch);
-            };
-            return SSW_OK;
-        }
+    std::array<BaseEnergyClass, 8> be;
+    for (int c = 0; c < 8; ++c) {
+        const BaseTailPlan::Class& k = tp.cls[c];
+        const PairClassDesc& d = l2.d[c];
+        const void* y16 = nullptr;
+        SSW_TRY(get_split16(ctx, b.len, d.cls, d.y1, d.y2, k.yrows, tp.NP, k.Kp, tp.pair0, &y16));
+        be[c].x1 = d.x1; be[c].x2 = d.x2; be[c].y16 = y16;
+        be[c].NP = tp.NP; be[c].Kp = k.Kp; be[c].pair0 = tp.pair0; be[c].pm = k.pm; be[c].c1 = k.c1; be[c].c2 = k.c2; be[c].gsh = k.gsh; be[c].e2off = k.e2off;
     }
+    const size_t lpf = 16 * dct_pair_fused_units(h);
+    const double head = (double)tp.pair0 / (double)tp.NP;
+    const double bound_bytes = 8.0 * 2.0 * (double)tp.chunks * (double)(n * lpf) * (double)be[0].Kp * 8.0;
+    fe.part = BasePart::HeadRows;
     ch.push_back({false, [=](hipStream_t st) -> int {
-        if (bprune) {           // (row pass) the energies start at zero
-            SSW_HIP_CHECK(hipMemsetAsync(bp.energy, 0, n * w * sizeof(float), st));
-            untimed_work(ctx);
+        SSW_HIP_CHECK(hipMemsetAsync(a.energy, 0, n * w * sizeof(float), st));
+        untimed_work(ctx);
+        {
+            StageTimer tb(ctx, SSW_STAGE_DCT_PREP, st, bound_bytes);
+            SSW_TRY(launch_base_energy_bound(st, 8, be.data(), n, w, h, lpf, b.ep.base, a.energy));
         }
-        StageTimer t(ctx, b.st_pass, st, f_all * pad, b.p.merge ? b.st_main : -1);      // (merged: a single frame's eight classes in one launch)
-        t.traffic(bytes);
+        // (not billed to the main-launch stage: that figure stays the time and flop of one full launch, the writer's)
+        StageTimer t(ctx, b.st_pass, st, l2.f_all * l2.pad * head);
+        t.traffic(b.px * 8.0 * (1.0 + head));
         auto launch = [&](int nc, const PairClassDesc* dd) {
-            return launch_dct_pair_gemm_multi_f64(st, b.is_row, false, nc, dd, out, nullptr, n, w, h, b.ep, nullptr, nullptr, b.gemm_layout(),
-                                                  fused ? &fc : nullptr);
+            return launch_dct_pair_gemm_multi_f64(st, true, false, nc, dd, l2.out, nullptr, n, w, h, b.ep, nullptr, nullptr, b.gemm_layout(), &fe);
         };
-        return launch_classes(ctx, st, b.p.merge, 8, d.data(), launch, b.st_main, f_main * pad);
+        return launch_classes(ctx, st, b.p.merge, 8, l2.d.data(), launch);
+    }});
+    FuseCols ft = l2.fc;
+    ft.part = BasePart::TailRows; ft.need = a.need;
+    ft.tail = a.counters ? &a.counters->tail_jobs : nullptr;       // the launches count their jobs, and bill them at these rates per pair
+    ft.tail_flop = 4.0 * (double)lpf * (double)(b.len / 16); ft.tail_bytes = 16.0 * (double)h;
+    tail = [=](hipStream_t st) -> int {
+        auto launch = [&](int nc, const PairClassDesc* dd) {
+            return launch_dct_pair_gemm_multi_f64(st, true, false, nc, dd, l2.out, nullptr, n, w, h, b.ep, nullptr, nullptr, b.gemm_layout(), &ft);
+        };
+        return launch_classes(ctx, st, b.p.merge, 8, l2.d.data(), launch);
+    };
+    return SSW_OK;
+}
+
+// Column pass.  Phase 1: tile 0 of every frame (one launch over the eight classes, a grid of 3 blocks per frame and class);
+// decide; the row pass's `tail`, if it left one: the column operands of the needed tiles are complete before phase 2 reads
+// them; phase 2: the tiles that can hold one of the first k keys.  The others are not written: whoever reads the plane
+// afterwards goes by the flags (launch_topk's mask).  The host bills phase 1; phase 2's tiles are billed from the device
+// counters when the timers are resolved (base_prune_bill).
+int build_base_cols(const PassBuild& b, const Level2Pass& l2, const BaseReaderArgs& a, const TailLaunch& tail, Chain& ch) {
+    ssw_ctx* ctx = b.ctx;
+    const size_t n = b.n, w = b.w, h = b.h;
+    const double tiles = (double)(w / SSW_BASE_PRUNE_TILE);
+    BasePrune bp;
+    bp.energy = a.energy; bp.need = a.need; bp.k = a.k; bp.ordering = a.ordering;
+    if (a.counters) { bp.stats = &a.counters->tiles; bp.work = &a.counters->col_flop; }
+    bp.tile_flop = l2.f_all / ((double)n * tiles);
+    bp.tile_bytes = l2.bytes / ((double)n * tiles);
+    bp.select_bytes = (double)h * SSW_BASE_PRUNE_TILE * 4.0;
+    auto phase = [=](hipStream_t st, BasePart part) {
+        FuseCols f2 = l2.fc;
+        f2.part = part; f2.need = a.need;
+        return launch_dct_pair_gemm_multi_f64(st, false, false, 8, l2.d.data(), l2.out, nullptr, n, w, h, b.ep, nullptr, nullptr, b.gemm_layout(), &f2);
+    };
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_pass, st, l2.f_all / tiles);
+        t.traffic(l2.bytes / tiles);
+        return phase(st, BasePart::Phase1Cols);
+    }});
+    ch.push_back({true, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, SSW_STAGE_SELECT, st, (double)n * ((double)h * SSW_BASE_PRUNE_TILE + (double)w) * 4.0);
+        return launch_base_prune_decide(st, l2.out, bp, n, w, h);
+    }});
+    if (tail)
+        ch.push_back({false, [=](hipStream_t st) -> int {
+            StageTimer t(ctx, SSW_STAGE_DCT_ROW, st, 0.0);
+            return tail(st);
+        }});
+    ch.push_back({false, [=](hipStream_t st) -> int {
+        StageTimer t(ctx, b.st_pass, st, 0.0);
+        return phase(st, BasePart::Phase2Cols);
     }});
     return SSW_OK;
 }
@@ -839,13 +834,12 @@ int build_deep_inv(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused
     return SSW_OK;
 }
 
-// One pass of the separable transform (src -> dst along rows or columns) appended to `ch`: the builder of the strategy
-// its plan names.
-int build_pass(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, bool first_pass, bool is_row, const float* src, float* dst,
-               Epilogue ep, Chain& ch, bool* fused_rgb = nullptr) {
+// One pass of the separable transform (src -> dst along rows or columns) as its builders see it: its plan and what its
+// stages account.
+int make_pass(ssw_ctx* ctx, const Xform& x, bool first_pass, bool is_row, const float* src, float* dst, Epilogue ep, PassBuild& b) {
     const PlanInput in{x.type, x.precision, x.n, x.w, x.h, x.full_h, x.natural_order, aligned_planes(src, dst), plan_settings(ctx)};
-    PassBuild b{ctx, x, plan_pass(in, first_pass, is_row), first_pass, is_row, x.type == SSW_DCT3, x.rgb && first_pass, x.n, x.w, x.h,
-                is_row ? x.w : x.h, is_row ? x.n * x.h : x.n * x.w, src, dst, ep};
+    b = PassBuild{ctx, x, plan_pass(in, first_pass, is_row), first_pass, is_row, x.type == SSW_DCT3, x.rgb && first_pass, x.n, x.w, x.h,
+                  is_row ? x.w : x.h, is_row ? x.n * x.h : x.n * x.w, src, dst, ep};
     if (b.from_rgb && !(is_row && b.p.levels >= 2)) return SSW_ERR_BAD_ARG;      // can_fuse_rgb() checks the same conditions
     b.st_pass = is_row ? SSW_STAGE_DCT_ROW : SSW_STAGE_DCT_COL;
     b.st_main = is_row ? SSW_STAGE_DCT_ROW_MAIN : SSW_STAGE_DCT_COL_MAIN;
@@ -856,6 +850,21 @@ int build_pass(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, bool first_pass,
     b.prep_bytes = b.from_rgb ? b.px * (3.0 * (double)pix_bytes(x.rgb_fmt) + (x.iq_i ? 8.0 : 0.0) + 8.0) : b.px * (4.0 + 8.0);
     const bool sink_pass = b.inverse && !first_pass && !is_row && x.rgb_out && x.iq_i && x.iq_q;
     b.out_bpp = sink_pass ? 8.0 + 3.0 * (x.rgb_out_u8 ? 1.0 : 4.0) : 4.0;
+    return SSW_OK;
+}
+// hints for the two-lane scheduler (run_pipeline_impl) on the stages the pass's builder appended, ch[first] on
+void tag_pass_stages(const PassBuild& b, Chain& ch, size_t first) {
+    for (size_t i = first; i < ch.size(); ++i) {
+        if (!ch[i].hbm && b.is_row) ch[i].tag = 1;
+        if (ch[i].hbm && b.is_row && b.first_pass && b.x.type != SSW_DCT3 && b.x.rgb) ch[i].tag = 2;
+    }
+}
+
+// The pass appended to `ch`: the builder of the strategy its plan names.
+int build_pass(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, bool first_pass, bool is_row, const float* src, float* dst,
+               Epilogue ep, Chain& ch, bool* fused_rgb = nullptr) {
+    PassBuild b;
+    SSW_TRY(make_pass(ctx, x, first_pass, is_row, src, dst, ep, b));
     const size_t first = ch.size();
     typedef PassStrategy S;
     const S s = b.p.strategy;
@@ -867,10 +876,7 @@ int build_pass(ssw_ctx* ctx, ssw_ctx::Lane& ws, const Xform& x, bool first_pass,
             : s == S::SemiDeep || s == S::SemiDeepInv ? build_semi_deep(b, ws, ch, fused_rgb)
             : s == S::DeepInv || s == S::DeepInvL2    ? build_deep_inv(b, ws, ch, fused_rgb)
                                                       : build_deep_l2(b, ws, ch));        // DeepL2, FusedRows, FusedCols
-    for (size_t i = first; i < ch.size(); ++i) {                  // hints for the two-lane scheduler (run_pipeline_impl)
-        if (!ch[i].hbm && is_row) ch[i].tag = 1;
-        if (ch[i].hbm && is_row && first_pass && x.type != SSW_DCT3 && x.rgb) ch[i].tag = 2;
-    }
+    tag_pass_stages(b, ch, first);
     return SSW_OK;
 }
 
@@ -929,10 +935,9 @@ bool can_fuse_rgb(const ssw_ctx* ctx, bool f64, size_t w, size_t h, const float*
 // Where the default GEMM strategy applies (rows first, two folding levels on the row axis) the colour
 // conversion is fused into the first operand pre-pass and the f32 Y plane is never materialised.
 int build_forward_from_rgb(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, PixFmt fmt, size_t n, size_t w,
-                           size_t h, float* y, float* i, float* q, float* tmp, Chain& ch, const BasePrune* base_prune) {
+                           size_t h, float* y, float* i, float* q, float* tmp, Chain& ch) {
     const bool f64 = precision == SSW_PRECISION_F64;
     Xform x{SSW_DCT2, precision, n, w, h, y, tmp};
-    x.base_prune = base_prune;
     if (can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, fmt)) {
         x.rgb = rgb; x.rgb_fmt = fmt; x.iq_i = i; x.iq_q = q;
         return build_transform(ctx, ws, x, ch);
@@ -946,6 +951,38 @@ int build_forward_from_rgb(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const
         return launch_rgb_to_yiq(st, static_cast<const float*>(rgb), npix, y, i, q);
     }});
     return build_transform(ctx, ws, x, ch);
+}
+
+// Reader::base of a batch extract, whose plane feeds only the selection of the first k keys and reads at those indices: where
+// the planner takes the fused forward transform for these frames, its row pass with the energies and its column pass in two
+// phases (build_base_rows, build_base_cols); *mask = the flags the column pass leaves -- the tiles whose flag is 0 are NOT
+// written, the selection reads by them.  Anywhere else the ordinary transform, and *mask = null.
+int build_base_reader(ssw_ctx* ctx, ssw_ctx::Lane& ws, int precision, const void* rgb, PixFmt fmt, size_t n, size_t w, size_t h, float* y,
+                      float* tmp, const BaseReaderArgs& a, Chain& ch, const unsigned** mask) {
+    const bool f64 = precision == SSW_PRECISION_F64;
+    *mask = nullptr;
+    if (n > 0 && w >= h && n <= plan_frame_limit(plan_settings(ctx), f64, w, h) && can_fuse_rgb(ctx, f64, w, h, y, tmp, rgb, fmt)) {
+        Xform x{SSW_DCT2, precision, n, w, h, y, tmp};
+        x.rgb = rgb; x.rgb_fmt = fmt;
+        PassBuild rows, cols;
+        SSW_TRY(make_pass(ctx, x, true, true, y, tmp, Epilogue{1.f, 1.f}, rows));
+        SSW_TRY(make_pass(ctx, x, false, false, tmp, y, Epilogue{1.f, 1.f}, cols));
+        if (rows.p.strategy == PassStrategy::FusedRows && cols.p.strategy == PassStrategy::FusedCols) {
+            Level2Pass lr, lc;
+            TailLaunch tail;
+            const size_t first = ch.size();
+            SSW_TRY(level2_pass(rows, ws, lr));
+            SSW_TRY(build_base_rows(rows, lr, a, ch, tail));
+            tag_pass_stages(rows, ch, first);
+            const size_t first_col = ch.size();
+            SSW_TRY(level2_pass(cols, ws, lc));
+            SSW_TRY(build_base_cols(cols, lc, a, tail, ch));
+            tag_pass_stages(cols, ch, first_col);
+            *mask = a.need;
+            return SSW_OK;
+        }
+    }
+    return build_forward_from_rgb(ctx, ws, precision, rgb, fmt, n, w, h, y, nullptr, nullptr, tmp, ch);
 }
 
 // The two passes of a rows-first forward transform from RGB as separate chains (single-image handles: the row pass
@@ -983,7 +1020,7 @@ int dct2d_planes(ssw_ctx* ctx, int type, int precision, size_t n, size_t w, size
 
 int topk(ssw_ctx* ctx, hipStream_t st, SelectWorkspace& sel, const float* coef, size_t n, size_t w, size_t h, int ordering,
          size_t k, uint32_t* idx, const unsigned* need) {
-    // (under a tile mask: tile 0 of every frame; the other needed tiles are billed from the device counter, flush_timers)
+    // (under a tile mask: tile 0 of every frame; the other needed tiles are billed from the device counters, base_prune_bill)
     const double bytes = 4.0 * (double)n * (double)(need ? SSW_BASE_PRUNE_TILE : w) * (double)h;
     if (need && k > select_max_k()) return SSW_ERR_BAD_ARG;
     if (k > select_max_k()) {
@@ -1433,11 +1470,33 @@ bool base_prune_shape_ok(const ssw_ctx* ctx, const ssw_config& c, size_t n, size
            plan_pass(in, false, false).strategy == PassStrategy::FusedCols;
 }
 // energy [frames][W] f32 | need [frames][W / 128] u32 in the lane's buffer
-int base_prune_workspace(ssw_ctx::Lane& ws, size_t frames, size_t w, BasePrune& bp) {
+int base_prune_workspace(ssw_ctx::Lane& ws, size_t frames, size_t w, BaseReaderArgs& a) {
     const size_t e_bytes = frames * w * sizeof(float);
     SSW_TRY(grow(ws.base_prune, e_bytes + frames * (w / SSW_BASE_PRUNE_TILE) * sizeof(unsigned)));
-    bp.energy = (float*)ws.base_prune.p;
-    bp.need = (unsigned*)((char*)ws.base_prune.p + e_bytes);
+    a.energy = (float*)ws.base_prune.p;
+    a.need = (unsigned*)((char*)ws.base_prune.p + e_bytes);
+    return SSW_OK;
+}
+// What only the device knows of a pruned base reader's work is billed when the timers are resolved (flush_timers), from the
+// context's counters: the second phase's share of the column launches and of the masked selection's reads (the computed tiles
+// beyond every frame's tile 0, which the host billed), and the jobs of the gated tail row launches (base_energy.hip), counted
+// by the launches themselves.  Each frame at its own shape's rate: the kernels add flop and bytes up as doubles; what was
+// enqueued while the timers were off is passed over, like every other stage's work.
+int base_prune_bill(ssw_ctx* ctx) {
+    if (!ctx->base_prune_stats.p) return SSW_OK;
+    BasePruneCounters c;
+    SSW_HIP_CHECK(hipMemcpy(&c, ctx->base_prune_stats.p, sizeof(c), hipMemcpyDeviceToHost));
+    const double now[5] = {c.col_flop, c.col_bytes, c.select_bytes, c.tail_flop, c.tail_bytes};
+    double* billed = ctx->base_prune_billed;
+    if (ctx->timing) {
+        ctx->stage_work[SSW_STAGE_DCT_COL] += now[0] - billed[0];
+        ctx->stage_bytes[SSW_STAGE_DCT_COL] += now[1] - billed[1];
+        ctx->stage_work[SSW_STAGE_SELECT] += now[2] - billed[2];       // (an HBM-bound stage: its bytes are its work)
+        ctx->stage_bytes[SSW_STAGE_SELECT] += now[2] - billed[2];
+        ctx->stage_work[SSW_STAGE_DCT_ROW] += now[3] - billed[3];
+        ctx->stage_bytes[SSW_STAGE_DCT_ROW] += now[4] - billed[4];
+    }
+    for (int i = 0; i < 5; ++i) billed[i] = now[i];
     return SSW_OK;
 }
 
@@ -1544,8 +1603,8 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
     for (size_t f0 = 0; base_prune && f0 < n_frames; f0 += chunk)        // (the last chunk may be shorter: another plan)
         base_prune = base_prune_shape_ok(ctx, c, std::min(chunk, n_frames - f0), w, h, dev_base_rgb, fmt, y0, tmp0);
     if (base_prune && !ctx->base_prune_stats.p) {
-        SSW_TRY(grow(ctx->base_prune_stats, SSW_BASE_PRUNE_STATS * sizeof(unsigned long long)));
-        SSW_HIP_CHECK(hipMemsetAsync(ctx->base_prune_stats.p, 0, SSW_BASE_PRUNE_STATS * sizeof(unsigned long long), ctx->stream));
+        SSW_TRY(grow(ctx->base_prune_stats, sizeof(BasePruneCounters)));
+        SSW_HIP_CHECK(hipMemsetAsync(ctx->base_prune_stats.p, 0, sizeof(BasePruneCounters), ctx->stream));
         untimed_work(ctx);
     }
 
@@ -1559,20 +1618,17 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         const char* brgb = static_cast<const char*>(dev_base_rgb) + f0 * plane * px_bytes;
         const char* drgb = static_cast<const char*>(dev_derived_rgb) + f0 * plane * px_bytes;
         SelectWorkspace* sel = &ws.sel;
-        BasePrune bp;
-        bool decided = false;           // the transform below took the two-phase column pass: skipped tiles are stale
-        std::function<int(hipStream_t)> tail;      // (copied into the chain by the column pass's builder)
-        if (base_prune) {
-            bp.decided = &decided;
-            bp.tail = &tail;
-            SSW_TRY(base_prune_workspace(ws, chunk, w, bp));
-            bp.stats = (unsigned long long*)ctx->base_prune_stats.p;
-            bp.work = (double*)(bp.stats + 4);
-            bp.k = k; bp.ordering = c.ordering;
-        }
         // Reader::base (:474-480): only the Y plane is ever used by a reader
-        SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, brgb, fmt, n, w, h, yb, nullptr, nullptr, tmp, ch, base_prune ? &bp : nullptr));
-        const unsigned* mask = decided ? bp.need : nullptr;
+        const unsigned* mask = nullptr;         // set: the transform took the two-phase column pass, skipped tiles are stale
+        if (base_prune) {
+            BaseReaderArgs a;
+            SSW_TRY(base_prune_workspace(ws, chunk, w, a));
+            a.counters = (BasePruneCounters*)ctx->base_prune_stats.p;
+            a.k = k; a.ordering = c.ordering;
+            SSW_TRY(build_base_reader(ctx, ws, c.precision, brgb, fmt, n, w, h, yb, tmp, a, ch, &mask));
+        } else {
+            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, brgb, fmt, n, w, h, yb, nullptr, nullptr, tmp, ch));
+        }
         if (k > 0)
             ch.push_back({true, [=](hipStream_t st) -> int { return topk(ctx, st, *sel, yb, n, w, h, c.ordering, k, idx, mask); }});   // :493
         // Reader::derived: the compact plane of the columns the lists read, or (the un-pruned path and the redo) the full plane
@@ -1605,17 +1661,15 @@ int base_prune_bound_impl(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_
     for (int p : {0, 2}) SSW_TRY(grow(ws.plane[p], n_frames * plane * sizeof(float)));
     if (k == 0 || k >= plane || !base_prune_shape_ok(ctx, c, n_frames, w, h, dev_rgb, PixFmt::F32, (const float*)ws.plane[0].p, (const float*)ws.plane[2].p))
         return SSW_ERR_UNSUPPORTED;
-    BasePrune bp;
-    std::function<int(hipStream_t)> tail;
-    SSW_TRY(base_prune_workspace(ws, n_frames, w, bp));
-    bp.k = k; bp.ordering = c.ordering;
-    bp.tail = &tail;
+    BaseReaderArgs a;
+    SSW_TRY(base_prune_workspace(ws, n_frames, w, a));
+    a.k = k; a.ordering = c.ordering;
     Chain ch;
-    SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_rgb, PixFmt::F32, n_frames, w, h, (float*)ws.plane[0].p, nullptr, nullptr,
-                                   (float*)ws.plane[2].p, ch, &bp));
+    const unsigned* mask = nullptr;
+    SSW_TRY(build_base_reader(ctx, ws, c.precision, dev_rgb, PixFmt::F32, n_frames, w, h, (float*)ws.plane[0].p, (float*)ws.plane[2].p, a, ch, &mask));
     SSW_TRY(run_serial(ch, ctx->stream));
     untimed_work(ctx);
-    return launch_base_prune_bound(ctx->stream, bp.energy, n_frames, w, h, c.ordering, dev_bound);
+    return launch_base_prune_bound(ctx->stream, a.energy, n_frames, w, h, c.ordering, dev_bound);
 }
 
 // ---- one base frame against many suspect frames (ssw_fingerprint_trace) -----------------------------------------

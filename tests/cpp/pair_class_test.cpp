@@ -6,7 +6,7 @@
 //      "no such row".
 //  (2) The table against its neighbours: every forward class's frequency map equals ForwardClassLayout's natural(pos(slot, i));
 //      the classes of a level-2 pass and of a deep level-1 pass partition the frequencies; the flop of the eight level-2 classes
-//      is eight times that of O rotated "+", as build_deep_l2 assumes.
+//      is eight times that of O rotated "+", as the set-up of build_deep_l2 assumes (level2_pass).
 //  (3) The class sources of the pruned row pass: tests/golden/prune_class_src_parent.txt holds what build_pruned_derived's own
 //      loop resolved per class of the plan BEFORE prune_class_sources existed (row plans of 3840, 1920, 1024 at level 2, 512
 //      deep at level 1, 1040 split and not split); the function must answer the same, and prune_gathered_offsets must lay the

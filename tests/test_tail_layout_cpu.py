@@ -1,7 +1,8 @@
 """tests/tail_layout.py against the code, on the host: tests/cpp/tail_layout_test.cpp prints what pair_class_args answers for the
 eight level-2 row classes of a width and the column tiles each tile column writes, in the gate's own arithmetic; the Python
 restatement must say the same for the three layouts of tests/test_base_energy_gpu.py and the four of
-tests/test_base_tail_layouts_gpu.py.  Then the table of those layouts as plain numbers -- what the GPU tests rely on."""
+tests/test_base_tail_layouts_gpu.py, and base_tail_plan -- what the row pass's builder goes by -- the same tile width, pairs
+and chunks; two more widths must come out not eligible (264 terms; one tile column).  Then the table of those layouts as plain numbers -- what the GPU tests rely on."""
 import os
 import subprocess
 
@@ -13,6 +14,7 @@ from conftest import ROOT
 
 LIBDIR = os.path.join(ROOT, "spread_spectrum_watermarking_amd", "lib")
 LAYOUTS = [(1152, 0), (1152, 1), (2048, 1), (2176, 1), (2176, 0), (3840, 1), (4096, 1)]
+INELIGIBLE = [(4224, 1), (1024, 1)]
 
 
 @pytest.fixture(scope="module")
@@ -20,13 +22,15 @@ def printed(tmp_path_factory):
     exe = os.path.join(str(tmp_path_factory.mktemp("tail_layout")), "tail_layout_test")
     subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "--offload-arch=gfx950", os.path.join(ROOT, "tests", "cpp", "tail_layout_test.cpp"),
                     "-o", exe, "-L", LIBDIR, "-lssw_hip", f"-Wl,-rpath,{LIBDIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    out = subprocess.run([exe] + [f"{w}:{t}" for w, t in LAYOUTS], capture_output=True, text=True)
+    out = subprocess.run([exe] + [f"{w}:{t}" for w, t in LAYOUTS + INELIGIBLE], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     per, cur = {}, None
     for line in out.stdout.splitlines():
         f = line.split()
         if f[0] == "L":
             cur = per[(int(f[1]), int(f[2]))] = {"split_bytes": int(f[3]), "classes": []}
+        elif f[0] == "P":
+            cur["plan"] = tuple(int(v) for v in f[1:])
         else:
             assert f[0] == "C" and int(f[1]) == len(cur["classes"]), line
             cur["classes"].append((tuple(int(v) for v in f[2:8]), [tuple(int(v) for v in r.split(":")) for r in f[8:]]))
@@ -37,11 +41,22 @@ def printed(tmp_path_factory):
 def test_restatement_equals_pair_class_args_and_the_gate(printed, lay):
     got, t = printed[lay], T.tail_layout(*lay)
     assert got["split_bytes"] == t.split_bytes                 # k-steps x (2 bases x hi / lo) x MFMA tiles x 1 KB + the maximum
+    assert got["plan"] == (1, t.tw, t.pairs, t.chunks)         # eligible, first tail pair = the tile width, pairs, chunks
     assert len(got["classes"]) == 8
     for c, ((np_, kp, tiles_n, bn32, gsh, e2off), ranges) in enumerate(got["classes"]):
         assert (np_, kp, tiles_n, bn32, gsh, e2off) == (t.pairs, t.kp, len(t.tile_cols), t.bn32, T.GSH, T.E_SHAPED[c]), (c, T.CLASSES[c])
         assert ranges[1:] == [T.feeds(t, c, tn) for tn in range(1, tiles_n)], (c, T.CLASSES[c])
         assert ranges[0] == (0, (t.tw - 1) >> T.GSH)
+
+
+@pytest.mark.parametrize("lay", INELIGIBLE, ids=lambda l: f"{l[0]}-tile48={l[1]}")
+def test_the_plan_refuses_long_sums_and_single_tile_columns(printed, lay):
+    got, t = printed[lay], T.tail_layout(*lay)
+    assert (t.kp, t.pairs, len(t.tile_cols)) == {4224: (264, 264, 5), 1024: (64, 64, 1)}[lay[0]]      # why: > 256 terms | no tail
+    assert got["plan"] == (0, 0, 0, 0) and got["split_bytes"] == 0
+    for c, ((np_, kp, tiles_n, bn32, gsh, e2off), ranges) in enumerate(got["classes"]):
+        assert (np_, kp, tiles_n, bn32, gsh, e2off) == (t.pairs, t.kp, len(t.tile_cols), t.bn32, T.GSH, T.E_SHAPED[c]), (c, T.CLASSES[c])
+        assert ranges == []
 
 
 def row(lay):
