@@ -241,8 +241,6 @@ int ssw_ctx_set_odd_split(ssw_ctx* ctx, int enable);
    threshold so that small shapes the oracle finishes in seconds take the kernels of the 4K path.  Names (default):
      efold_min (1280), efold_inv_min (1280), efold_cols_min (720)   shortest forward row / inverse row / column pass at level 2
      deep_min_rows (256), deep_min_cols (256)                       shortest pass that takes the deep pre-passes
-     class_tile (1)        class-major planes inside tiles of 128 columns (0: one tile per line)
-     prep_staged (1)       LDS-staged pre-passes (0: the r3 kernels)
      merge_max_lines (8192) passes of at most this many lines run a stage's launches as one
      bn32 (-1)             32-pair tiles for small single-class launches: -1 automatic, 0 / 1 forced
      band_split (1)        single-image handles: row pass of the top half beside the upload of the bottom half

@@ -701,8 +701,10 @@ __global__ __launch_bounds__(256) void pair_prep8_cols_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------------------------------------
-// The deep forward pre-pass of a COLUMN pass (H % 16 == 0): the same planes as pair_prep16_rows_kernel, lines =
-// (frame, column), transposed through LDS.  One block = 32 units e < H/16 x 32 columns; per (e, column) the 16 rows
+// The deep forward pre-pass of a COLUMN pass (H % 16 == 0) over ONE-TILE CLASS-MAJOR input: the row pass wrote the plane
+// class-major with the whole line as its one tile, because 128 does not divide W (ForwardClassLayout{W, W}; every other
+// plane takes the kernels of dct_pair_prep_staged.hip).  The same planes as pair_prep16_rows_kernel, lines = (frame,
+// column), transposed through LDS.  One block = 32 units e < H/16 x 32 memory columns; per (e, column) the 16 rows
 // that meet in e (row u mirrors row 15 - u).  Four LDS rounds of four planes each (34 KB):
 //   0: AS BD AD BS at e            1: the same planes at the mirror unit H/8 - 1 - e
 //   2: AS2 BD2 AD2 BS2 at e        3: R1 R2 at e and at H/8 - 1 - e
@@ -716,36 +718,25 @@ __device__ inline void store_run(double* __restrict__ plane, size_t line, size_t
     }
 }
 
-// SPLIT_SD = false ("semi-deep", H % 8 == 0 but not % 16, e.g. 1080 rows): H/16 is not whole, so SD stays one DCT-IV input
-// plane (`dp.as2`, kpad(H/2) wide: the r2 launch of the frequencies 2 mod 4) and the units run to ceil(H/16) -- the
-// middle unit is its own mirror and stores its values twice.
-template <bool SPLIT_SD>
-__global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __restrict__ IN, DeepPlanes dp,
-                                                              const double* __restrict__ rot1, const double* __restrict__ rot2,
-                                                              unsigned W, unsigned H, unsigned K8, unsigned K16,
-                                                              unsigned n_frames, unsigned tiles_e, unsigned tiles_c, unsigned class_major, unsigned ctile, unsigned efold) {
+// efold: the row pass ran at level 2 (the sixteen-class order of ForwardClassLayout)
+__global__ __launch_bounds__(256) void pair_prep16_cols_onetile_kernel(const float* __restrict__ IN, DeepPlanes dp,
+                                                                      const double* __restrict__ rot1, const double* __restrict__ rot2,
+                                                                      unsigned W, unsigned H, unsigned K8, unsigned K16,
+                                                                      unsigned n_frames, unsigned tiles_e, unsigned tiles_c, unsigned efold) {
     __shared__ double s[4][32][33];
-    const unsigned Hh = H / 2, Hq = H / 4, H8 = H / 8, H16 = SPLIT_SD ? H / 16 : (H / 8 + 1) / 2;      // H16: units
+    const unsigned Hh = H / 2, Hq = H / 4, H8 = H / 8, H16 = H / 16;      // H16: units
     const unsigned z = blockIdx.x / (tiles_e * tiles_c);
     const unsigned tt = blockIdx.x % (tiles_e * tiles_c);
-    const unsigned e0 = (tt % tiles_e) * 32, tile = tt / tiles_e;
+    const unsigned e0 = (tt % tiles_e) * 32, c0 = (tt / tiles_e) * 32;
     const float* __restrict__ Pz = IN + (size_t)z * H * W;
     const unsigned tid = threadIdx.x;
     const unsigned er = tid >> 3, cq = (tid & 7) * 4;              // load side: one e, 4 columns
     const unsigned cl = tid & 31, kq = (tid >> 5) * 4;             // store side: one column, 4 consecutive e
-    // class_major == 2 (W % 256 == 0, long lines): the block takes the ten runs of memory columns -- one per launch class,
-    // 32 or 16 wide -- that hold the natural columns [256 tile, 256 tile + 256): its stores then fill whole runs of
-    // operand lines (8K: both pre-passes of a forward transform 7.1 -> 6.5 ms per 32 frames; at 4K the plain mapping is faster)
-    const unsigned nsub = 1u;
-    for (unsigned sub = 0; sub < nsub; ++sub) {
-    if (sub) __syncthreads();
-    const unsigned wd = 32u;
-    const unsigned c0 = tile * 32;
-    const bool col_ok = cl < wd && c0 + cl < W;
+    const bool col_ok = c0 + cl < W;
     const unsigned cw = c0 + cl, ew = e0 + kq;
     // memory column cw of the intermediate plane holds frequency natural(cw) of the row pass (class-major order): the
     // operand line -- and with it the output column of the column GEMMs -- is the natural one
-    const unsigned cn = (class_major && col_ok) ? ForwardClassLayout{W, ctile, efold != 0}.natural(cw) : cw;
+    const unsigned cn = col_ok ? ForwardClassLayout{W, W, efold != 0}.natural(cw) : cw;
     const size_t line = (size_t)z * W + cn, lines = (size_t)n_frames * W;
     double* planes8[6] = {static_cast<double*>(dp.as), static_cast<double*>(dp.bd), static_cast<double*>(dp.ad), static_cast<double*>(dp.bs),
                      static_cast<double*>(dp.r1), static_cast<double*>(dp.r2)};
@@ -800,8 +791,7 @@ __global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __re
 #pragma unroll
                 for (int u = 0; u < 4; ++u) { SS[u] = S[u] + S[7 - u]; SD[u] = S[u] - S[7 - u]; }
                 if (round == 2) {
-                    if (SPLIT_SD) split_one(SD[0], SD[1], SD[2], SD[3], rot2, ec, H8, o[0], o[1], o[2], o[3]);
-                    else { o[0] = SD[0]; o[1] = SD[1]; o[2] = SD[2]; o[3] = SD[3]; }      // SD at e, H/8-1-e, H/8+e, H/4-1-e
+                    split_one(SD[0], SD[1], SD[2], SD[3], rot2, ec, H8, o[0], o[1], o[2], o[3]);
                 } else {
                     o[0] = SS[0] + SS[3]; o[1] = SS[0] - SS[3];      // R1, R2 at e
                     o[2] = SS[1] + SS[2]; o[3] = SS[1] - SS[2];      // R1, R2 at H/8 - 1 - e
@@ -811,7 +801,7 @@ __global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __re
             for (int a = 0; a < 4; ++a) s[a][cq + i][er] = unit_ok ? o[a] : 0.0;
         }
         __syncthreads();
-        if (col_ok && ew < (SPLIT_SD ? K16 : ((H16 + 3) & ~3u))) {
+        if (col_ok && ew < K16) {
             double v[4];
             if (round == 0) {
 #pragma unroll
@@ -820,17 +810,8 @@ __global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __re
 #pragma unroll
                 for (int a = 0; a < 4; ++a) { gather(a, v, true); if (nvalid) store_run(planes8[a], line, lines, H8 - ew - nvalid, v, nvalid); }
             } else if (round == 2) {
-                if (SPLIT_SD) {
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) { gather(a, v, false); store_run(planes16[a], line, lines, ew, v, 4u); }   // zeros beyond H/16
-                } else {
-                    double* M = planes16[0];
-                    gather(0, v, false); store_run(M, line, lines, ew, v, nvalid);
-                    gather(2, v, false); store_run(M, line, lines, H8 + ew, v, nvalid);
-                    gather(1, v, true); if (nvalid) store_run(M, line, lines, H8 - ew - nvalid, v, nvalid);
-                    gather(3, v, true); if (nvalid) store_run(M, line, lines, Hq - ew - nvalid, v, nvalid);
-                    if (ew == 0) for (unsigned k = Hq; k < K16; ++k) M[blk_index<double>(line, k, lines)] = 0.0;      // K16: kpad(H/2) here
-                }
+                for (int a = 0; a < 4; ++a) { gather(a, v, false); store_run(planes16[a], line, lines, ew, v, 4u); }   // zeros beyond H/16
             } else {
                 gather(0, v, false); store_run(planes8[4], line, lines, ew, v, nvalid);
                 gather(1, v, false); store_run(planes8[5], line, lines, ew, v, nvalid);
@@ -843,171 +824,6 @@ __global__ __launch_bounds__(256) void pair_prep16_cols_kernel(const float* __re
             }
         }
     }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Deep INVERSE pre-passes.  The inverse transform of coefficients c[0 .. n) combines, per axis,
-//   x[m]  = T[m] +/- o[m]      T = half-length inverse of the even coefficients, o = DCT-IV of the odd ones (n/2 each)
-//   T[m]  = T2[m] +/- o2[m]    T2 = quarter-length inverse of c[4q], o2 = DCT-IV of c[4q+2]                (n/4 each)
-//   T2[m] = EEE-part +/- EEO-part: c[8q] and c[8q+4] against the half bases of length n/4                   (n/8 each)
-// and both DCT-IVs are split like the forward ones: the operands are
-//   AS BD AD BS  (n/8 each)   from k -> c[2k+1]  (rotation partners k, n/2-1-k; fold partners n/4-1-k, n/4+k)
-//   AS2 .. BS2   (n/16 each)  from q -> c[4q+2]
-//   R1 = c[8q], R2 = c[8q+4]  (n/8 each)
-// in the DeepPlanes order of the forward pre-passes.
-// Row pass (n % 128 == 0): one thread = the eight 16-element regions of a line that close under those pairings,
-//   g = R, n/4-16-R, n/4+R, n/2-16-R, n/2+R, 3n/4-16-R, 3n/4+R, n-16-R   (R = 16 t): 128 coefficients in, 128 doubles out.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pair_prep16_inv_rows_kernel(const float* __restrict__ X, DeepPlanes dp,
-                                                                  const double* __restrict__ rot1, const double* __restrict__ rot2,
-                                                                  unsigned rows, unsigned W, unsigned K8, unsigned K16, unsigned tp_line /*threads per line, power of 2*/) {
-    const unsigned t = threadIdx.x & (tp_line - 1);
-    const unsigned row = blockIdx.x * (256 / tp_line) + threadIdx.x / tp_line;
-    const unsigned R = 16 * t;
-    const unsigned Nh = W / 2, Nq = W / 4, N8 = W / 8, N16 = W / 16;
-    if (row >= rows || R >= N8) return;
-    double* P8[6] = {static_cast<double*>(dp.as), static_cast<double*>(dp.bd), static_cast<double*>(dp.ad), static_cast<double*>(dp.bs), static_cast<double*>(dp.r1), static_cast<double*>(dp.r2)};
-    double* P16[4] = {static_cast<double*>(dp.as2), static_cast<double*>(dp.bd2), static_cast<double*>(dp.ad2), static_cast<double*>(dp.bs2)};
-    auto put4 = [&](double* plane, unsigned k, const f64x4& v) { *reinterpret_cast<f64x4*>(plane + blk_index<double>(row, k, rows)) = v; };
-    auto put2 = [&](double* plane, unsigned k, double a, double b) { *reinterpret_cast<f64x2*>(plane + blk_index<double>(row, k, rows)) = (f64x2){a, b}; };
-    const unsigned g[8] = {R, Nq - 16 - R, Nq + R, Nh - 16 - R, Nh + R, 3 * Nq - 16 - R, 3 * Nq + R, W - 16 - R};
-    const float* xr = X + (size_t)row * W;
-    f32x4 c[8][4];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) c[j][q] = *reinterpret_cast<const f32x4*>(xr + g[j] + 4 * q);
-    // odd coefficients of region j as two ascending quads of k: element u = 2 t + 1 -> quad t / 4
-    auto odd = [&](int j, int half) { return (f64x4){(double)c[j][2 * half][1], (double)c[j][2 * half][3], (double)c[j][2 * half + 1][1], (double)c[j][2 * half + 1][3]}; };
-    // unit A: k = e0 .. e0+7 (e0 = R/2) from regions 0, 3, 4, 7; its mirror unit n/8-8-e0 .. from regions 1, 2, 5, 6
-    const unsigned e0 = R / 2, m0u = N8 - 8 - e0;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        f64x4 as, bd, ad, bs;
-        split_unit(odd(0, half), odd(3, 1 - half), odd(4, half), odd(7, 1 - half), rot1, e0 + 4 * half, Nq, as, bd, ad, bs);
-        put4(P8[0], e0 + 4 * half, as); put4(P8[1], e0 + 4 * half, bd); put4(P8[2], e0 + 4 * half, ad); put4(P8[3], e0 + 4 * half, bs);
-        split_unit(odd(1, half), odd(2, 1 - half), odd(5, half), odd(6, 1 - half), rot1, m0u + 4 * half, Nq, as, bd, ad, bs);
-        put4(P8[0], m0u + 4 * half, as); put4(P8[1], m0u + 4 * half, bd); put4(P8[2], m0u + 4 * half, ad); put4(P8[3], m0u + 4 * half, bs);
-    }
-    // c[4q+2]: element 2 of every quad of a region, q ascending
-    auto mid = [&](int j) { return (f64x4){(double)c[j][0][2], (double)c[j][1][2], (double)c[j][2][2], (double)c[j][3][2]}; };
-    {
-        const unsigned f0 = R / 4, f1 = N16 - 4 - f0;
-        f64x4 as, bd, ad, bs;
-        split_unit(mid(0), mid(3), mid(4), mid(7), rot2, f0, N8, as, bd, ad, bs);
-        put4(P16[0], f0, as); put4(P16[1], f0, bd); put4(P16[2], f0, ad); put4(P16[3], f0, bs);
-        split_unit(mid(1), mid(2), mid(5), mid(6), rot2, f1, N8, as, bd, ad, bs);
-        put4(P16[0], f1, as); put4(P16[1], f1, bd); put4(P16[2], f1, ad); put4(P16[3], f1, bs);
-    }
-    // c[8q] and c[8q+4]: elements 0 of quads 0, 2 and of quads 1, 3
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        put2(P8[4], g[j] / 8, (double)c[j][0][0], (double)c[j][2][0]);
-        put2(P8[5], g[j] / 8, (double)c[j][1][0], (double)c[j][3][0]);
-    }
-    if (t == 0) {
-        const f64x4 zero = {0, 0, 0, 0};
-        for (unsigned z = N8; z < K8; z += 4)
-#pragma unroll
-            for (int a = 0; a < 6; ++a) put4(P8[a], z, zero);
-        for (unsigned z = N16; z < K16; z += 4)
-#pragma unroll
-            for (int a = 0; a < 4; ++a) put4(P16[a], z, zero);
-    }
-}
-
-// Column pass (H % 16 == 0): lines = (frame, column).  One block = 32 columns x one group G of 8 units: thread (column,
-// t) serves the D-split pair (e = 8G + t, H/8 - 1 - e), the level-2 unit e' = 8G + t and the level-3 pairs q = 16G + 2t,
-// +1 -- 16 coefficients in (coalesced across the columns), 16 doubles out, transposed through LDS so that every store
-// is a whole 64-byte piece of one line where the positions allow it.
-// SPLIT_MID = false ("semi-deep", H % 8 == 0 but not % 16): c[4q+2] stays one DCT-IV input plane (`dp.as2`, kpad(H/2)
-// wide) and the units run to ceil(H/16); the middle unit is its own mirror and stores its values twice.
-template <bool SPLIT_MID>
-__global__ __launch_bounds__(256) void pair_prep16_inv_cols_kernel(const float* __restrict__ IN, DeepPlanes dp,
-                                                                  const double* __restrict__ rot1, const double* __restrict__ rot2,
-                                                                  unsigned W, unsigned H, unsigned K8, unsigned K16,
-                                                                  unsigned n_frames, unsigned groups, unsigned tiles_c, unsigned class_major, unsigned ctile) {
-    __shared__ double s[16][32][9];
-    const unsigned Hh = H / 2, Hq = H / 4, H8 = H / 8, H16 = SPLIT_MID ? H / 16 : (H / 8 + 1) / 2;      // H16: units
-    const unsigned z = blockIdx.x / (groups * tiles_c);
-    const unsigned tt = blockIdx.x % (groups * tiles_c);
-    const unsigned G = tt % groups, c0 = (tt / groups) * 32;
-    const float* __restrict__ Pz = IN + (size_t)z * H * W;
-    const unsigned cl = threadIdx.x & 31, t = threadIdx.x >> 5;
-    // class-major input: lane cl takes NATURAL column c0 + cl, i.e. memory column inverse_class_pos(c0 + cl) -- the loads
-    // of a row are four 32-byte runs (one per residue class) and the stores below stay runs of consecutive operand lines
-    const unsigned coln = c0 + cl < W ? c0 + cl : W - 1;
-    const unsigned col = class_major ? inverse_class_pos(coln, W, ctile, class_major == 2) : coln;      // 2: the level-2 order
-    auto ld = [&](unsigned r) { return (double)Pz[(size_t)r * W + col]; };
-    double* P8[6] = {static_cast<double*>(dp.as), static_cast<double*>(dp.bd), static_cast<double*>(dp.ad), static_cast<double*>(dp.bs), static_cast<double*>(dp.r1), static_cast<double*>(dp.r2)};
-    double* P16[4] = {static_cast<double*>(dp.as2), static_cast<double*>(dp.bd2), static_cast<double*>(dp.ad2), static_cast<double*>(dp.bs2)};
-    const unsigned e = 8 * G + t;                                  // D-split pair index (< H/16) and level-2 unit (< H/16)
-    const bool ok = e < H16;
-    const unsigned ec = ok ? e : 0, em = H8 - 1 - ec;
-    double o[16];
-    {   // odd coefficients: k -> row 2k+1; unit at e: k = e, H/4-1-e, H/4+e, H/2-1-e; mirror unit at em
-        const double d0 = ld(2 * ec + 1), d1 = ld(Hh - 1 - 2 * ec), d2 = ld(Hh + 2 * ec + 1), d3 = ld(H - 1 - 2 * ec);
-        split_one(d0, d1, d2, d3, rot1, ec, Hq, o[0], o[1], o[2], o[3]);
-        const double m0v = ld(2 * em + 1), m1 = ld(Hh - 1 - 2 * em), m2 = ld(Hh + 2 * em + 1), m3 = ld(H - 1 - 2 * em);
-        split_one(m0v, m1, m2, m3, rot1, em, Hq, o[4], o[5], o[6], o[7]);
-        // c[4q+2]: q = e, H/8-1-e, H/8+e, H/4-1-e
-        const double q0 = ld(4 * ec + 2), q1 = ld(Hh - 2 - 4 * ec), q2 = ld(Hh + 4 * ec + 2), q3 = ld(H - 2 - 4 * ec);
-        if (SPLIT_MID) split_one(q0, q1, q2, q3, rot2, ec, H8, o[8], o[9], o[10], o[11]);
-        else { o[8] = q0; o[9] = q1; o[10] = q2; o[11] = q3; }          // c[4q+2] itself at q = e, H/8-1-e, H/8+e, H/4-1-e
-        // c[8q], c[8q+4] for q = 2e, 2e+1 (< H/8; with an odd H/8 the last unit has one)
-        const bool q2ok = 2 * ec + 1 < H8;
-        o[12] = ld(16 * ec); o[13] = q2ok ? ld(16 * ec + 8) : 0.0; o[14] = ld(16 * ec + 4); o[15] = q2ok ? ld(16 * ec + 12) : 0.0;
-    }
-#pragma unroll
-    for (int v = 0; v < 16; ++v) s[v][cl][t] = ok ? o[v] : 0.0;
-    __syncthreads();
-    if (c0 + cl >= W) return;
-    const size_t line = (size_t)z * W + c0 + cl, lines = (size_t)n_frames * W;
-    const unsigned nv = 8 * G >= H16 ? 0u : (H16 - 8 * G < 8 ? H16 - 8 * G : 8u);          // valid units of the group
-    const unsigned h = t;                                          // store side: thread h of a column takes value type h
-    {   // AS BD AD BS at e = 8G .. (h < 4) or at the mirror units H/8 - 1 - e, ascending from H/8 - 8G - nv (h >= 4)
-        double* plane = P8[h & 3];
-        if (h < 4) {
-            if (nv == 8) {
-                double* o8 = plane + blk_index<double>(line, 8 * G, lines);
-                *reinterpret_cast<f64x4*>(o8) = (f64x4){s[h][cl][0], s[h][cl][1], s[h][cl][2], s[h][cl][3]};
-                *reinterpret_cast<f64x4*>(o8 + 4) = (f64x4){s[h][cl][4], s[h][cl][5], s[h][cl][6], s[h][cl][7]};
-            } else {
-                for (unsigned j = 0; j < nv; ++j) plane[blk_index<double>(line, 8 * G + j, lines)] = s[h][cl][j];
-            }
-        } else {
-            const unsigned k0 = H8 - 8 * G - nv;
-            if (nv == 8 && (k0 & 7u) == 0) {
-                double* o8 = plane + blk_index<double>(line, k0, lines);
-                *reinterpret_cast<f64x4*>(o8) = (f64x4){s[h][cl][7], s[h][cl][6], s[h][cl][5], s[h][cl][4]};
-                *reinterpret_cast<f64x4*>(o8 + 4) = (f64x4){s[h][cl][3], s[h][cl][2], s[h][cl][1], s[h][cl][0]};
-            } else {
-                for (unsigned j = 0; j < nv; ++j) plane[blk_index<double>(line, k0 + j, lines)] = s[h][cl][nv - 1 - j];
-            }
-        }
-    }
-    if (SPLIT_MID) {   // AS2 .. BS2 at e' = 8G + 4 (h / 4) .. +3: zeros beyond H/16 (the planes are K16 wide)
-        double* plane = P16[h & 3];
-        const unsigned k0 = 8 * G + 4 * (h >> 2), j0 = 4 * (h >> 2);
-        if (k0 < K16) *reinterpret_cast<f64x4*>(plane + blk_index<double>(line, k0, lines)) = (f64x4){s[8 + (h & 3)][cl][j0], s[8 + (h & 3)][cl][j0 + 1], s[8 + (h & 3)][cl][j0 + 2], s[8 + (h & 3)][cl][j0 + 3]};
-    } else if (h < 4) {   // the c[4q+2] plane: thread h takes the run of value type 8 + h (ascending for h = 0, 2; mirrored for 1, 3)
-        double* plane = P16[0];
-        const unsigned start = h == 0 ? 8 * G : h == 2 ? H8 + 8 * G : (h == 1 ? H8 : Hq) - 8 * G - nv;
-        for (unsigned j = 0; j < nv; ++j) plane[blk_index<double>(line, start + j, lines)] = s[8 + h][cl][(h & 1) ? nv - 1 - j : j];
-        if (G == 0 && h == 0) for (unsigned k = Hq; k < K16; ++k) plane[blk_index<double>(line, k, lines)] = 0.0;      // K16: kpad(H/2) here
-    }
-    {   // R1 = c[8q], R2 = c[8q+4] at q = 16G + 2h, +1 (units beyond H/16 wrote zeros: padding up to K8 where 16G < K8)
-        const unsigned q0 = 16 * G + 2 * h;
-        if (q0 < K8) {
-            *reinterpret_cast<f64x2*>(P8[4] + blk_index<double>(line, q0, lines)) = (f64x2){s[12][cl][h], s[13][cl][h]};
-            *reinterpret_cast<f64x2*>(P8[5] + blk_index<double>(line, q0, lines)) = (f64x2){s[14][cl][h], s[15][cl][h]};
-        }
-    }
-    if (G == 0 && h == 0)                                           // AS .. BS beyond H/8
-        for (unsigned k = H8; k < K8; ++k)
-#pragma unroll
-            for (int a = 0; a < 4; ++a) P8[a][blk_index<double>(line, k, lines)] = 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1150,66 +966,19 @@ int launch_dct_pair_prep16_cols(hipStream_t st, const float* in, size_t n_frames
     if (n_frames == 0) return SSW_OK;
     const bool semi = h % 16 != 0, class_major = lay.class_major;
     if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull || h % 8 != 0 || w % 4 != 0) return SSW_ERR_BAD_DIMS;
-    if (semi && class_major && prep == PrepFamily::R3) return SSW_ERR_BAD_ARG;      // the r3 semi-deep kernels read the natural order only
     const unsigned K8 = (unsigned)dct_pair_split_kpad(h);
     const unsigned K16 = semi ? (unsigned)pair_kpad(h / 2) : (unsigned)dct_pair_split_kpad(h / 2);      // semi: width of the SD plane
     if (prep == PrepFamily::L2)
         return launch_prep16_cols_l2(st, in, n_frames, w, h, base, rot1, rot2, rot3, class_major, class_major && lay.rows_l2, K16);
     if (prep == PrepFamily::Staged)
         return launch_prep16_cols_staged(st, in, n_frames, w, h, base, rot1, rot2, class_major, semi, K8, K16, lay.rows_l2);
-    const unsigned units = semi ? (unsigned)(((h / 8 + 1) / 2 + 3) & ~(size_t)3) : K16;
-    const unsigned ctile = lay.tile;
-    const unsigned cm = !class_major ? 0u : 1u;      // (the r3 per-class-run mode, 2, knew the ten-class order; lines of such lengths take the staged kernels now)
-    const unsigned tiles_e = (units + 31) / 32, tiles_c = cm == 2 ? (unsigned)(w / 256) : (unsigned)((w + 31) / 32);
+    // PrepFamily::OneTile: deep columns of a class-major plane whose one tile is the whole line (dct_plan.hip: col_prep)
+    if (semi || !class_major || lay.tile != w) return SSW_ERR_BAD_ARG;
+    const unsigned tiles_e = (K16 + 31) / 32, tiles_c = (unsigned)((w + 31) / 32);
     const unsigned long long nblk = (unsigned long long)tiles_e * tiles_c * n_frames;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const DeepPlanes dp = planes_of(base, n_frames * w, K8, K16);          // semi: as2 = the SD plane, the others unused
-    if (semi) pair_prep16_cols_kernel<false><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, tiles_e, tiles_c, 0u, ctile, 0u);
-    else      pair_prep16_cols_kernel<true><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, tiles_e, tiles_c, cm, ctile, lay.rows_l2 ? 1u : 0u);
-    SSW_HIP_CHECK(hipGetLastError());
-    return SSW_OK;
-}
-
-// deep inverse pre-passes: same plane order (AS BD AD BS R1 R2 | AS2 BD2 AD2 BS2) with R1 = c[8q], R2 = c[8q+4]
-int launch_dct_pair_prep16_inv_rows(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                                    const double* rot1, const double* rot2, const double* rot3, PrepFamily prep) {
-    if (n_frames == 0) return SSW_OK;
-    if (w % 128 != 0 || w > 128 * 256 || h > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const size_t rows = n_frames * h;
-    if (rows > 0xFFFFFFFFull) return SSW_ERR_BAD_DIMS;
-    if (prep == PrepFamily::L2)
-        return launch_prep16_inv_rows_l2(st, in, rows, w, base, rot1, rot2, rot3, (unsigned)dct_pair_split_kpad(w / 2));
-    if (prep == PrepFamily::Staged)
-        return launch_prep16_inv_rows_staged(st, in, rows, w, base, rot1, rot2, (unsigned)dct_pair_split_kpad(w), (unsigned)dct_pair_split_kpad(w / 2));
-    unsigned tp = 1;
-    while (tp < w / 128) tp <<= 1;                                  // threads per line, <= 256
-    const unsigned lpb = 256 / tp;
-    const unsigned long long nblk = (rows + lpb - 1) / lpb;
-    if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    pair_prep16_inv_rows_kernel<<<(unsigned)nblk, 256, 0, st>>>(in, planes_of(base, rows, dct_pair_split_kpad(w), dct_pair_split_kpad(w / 2)), rot1, rot2, (unsigned)rows, (unsigned)w,
-                                                                       (unsigned)dct_pair_split_kpad(w), (unsigned)dct_pair_split_kpad(w / 2), tp);
-    SSW_HIP_CHECK(hipGetLastError());
-    return SSW_OK;
-}
-int launch_dct_pair_prep16_inv_cols(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                                    const double* rot1, const double* rot2, const double* rot3, PrepFamily prep, const PairLayout& lay) {
-    if (n_frames == 0) return SSW_OK;
-    const bool semi = h % 16 != 0, class_major = lay.class_major;
-    if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull || h % 8 != 0) return SSW_ERR_BAD_DIMS;
-    if (semi && class_major && prep == PrepFamily::R3) return SSW_ERR_BAD_ARG;      // the r3 semi-deep kernels read the natural order only
-    const unsigned K8 = (unsigned)dct_pair_split_kpad(h);
-    const unsigned K16 = semi ? (unsigned)pair_kpad(h / 2) : (unsigned)dct_pair_split_kpad(h / 2);      // semi: width of the c[4q+2] plane
-    if (prep == PrepFamily::L2)
-        return launch_prep16_inv_cols_l2(st, in, n_frames, w, h, base, rot1, rot2, rot3, class_major, class_major && lay.rows_l2, K16);
-    if (prep == PrepFamily::Staged)
-        return launch_prep16_inv_cols_staged(st, in, n_frames, w, h, base, rot1, rot2, class_major, semi, K8, K16, class_major && lay.rows_l2);
-    // groups of 8 units: K16 / 8 covers the padding of the n/16-wide planes; semi: the units (and the R planes' padding up to K8)
-    const unsigned groups = semi ? (unsigned)((K8 / 2 + 7) / 8) : K16 / 8, tiles_c = (unsigned)((w + 31) / 32);
-    const unsigned long long nblk = (unsigned long long)groups * tiles_c * n_frames;
-    if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
-    const DeepPlanes dp = planes_of(base, n_frames * w, K8, K16);          // semi: as2 = the c[4q+2] plane, the others unused
-    if (semi) pair_prep16_inv_cols_kernel<false><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, groups, tiles_c, 0u, (unsigned)w);
-    else      pair_prep16_inv_cols_kernel<true><<<(unsigned)nblk, 256, 0, st>>>(in, dp, rot1, rot2, (unsigned)w, (unsigned)h, K8, K16, (unsigned)n_frames, groups, tiles_c, class_major ? (lay.rows_l2 ? 2u : 1u) : 0u, lay.tile);
+    pair_prep16_cols_onetile_kernel<<<(unsigned)nblk, 256, 0, st>>>(in, planes_of(base, n_frames * w, K8, K16), rot1, rot2, (unsigned)w, (unsigned)h, K8, K16,
+                                                                      (unsigned)n_frames, tiles_e, tiles_c, lay.rows_l2 ? 1u : 0u);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }

@@ -1,13 +1,14 @@
 // Deep pre-passes, r4: the three HBM-bound pre-passes that r3 left at 31-43 % of HBM -- forward columns, inverse rows,
-// inverse columns (dct_pair_prep.hip: pair_prep16_cols_kernel, pair_prep16_inv_rows_kernel, pair_prep16_inv_cols_kernel)
-// -- with every result staged through LDS in the layout of the k-blocked operand planes, so that
+// inverse columns -- with every result staged through LDS in the layout of the k-blocked operand planes, so that
 //   * a global read is a run of >= 512 contiguous bytes per row (column passes: one class-major tile of 128 memory
 //     columns, dct_pair_common.hpp) or >= 512 bytes per line (row pass: 8 neighbouring 64-byte regions), and
 //   * a global store instruction writes 16 bytes per lane of ONE contiguous run: the 64-byte k-block pieces of 128
 //     (column passes) or 32 (row pass) consecutive operand lines = 8 KB / 2 KB.
 // (r3: 32-byte pieces of lines 8 or 16 apart, 8-byte stores for the mirrored halves at 4K, four 32-byte read runs per
 // row: PMC traffic 1.4-2.1 x the algorithmic bytes.)  Same operations in the same order per operand element as the r3
-// kernels -- the operand planes are bit-identical (tools/prep_check.py), so is every result downstream.
+// kernels, whose operand planes they reproduced bit for bit before those were retired (HISTORY.md).  Of that generation one
+// kernel remains: pair_prep16_cols_onetile_kernel (dct_pair_prep.hip), for forward columns behind a row pass whose length
+// 128 does not divide -- its class-major plane is one tile as wide as the line, not tiles of PREP_STAGED_TILE.
 //
 // Reference: src/dct2d.rs:172-206 is the column pass whose strided gather / scatter these kernels replace; the f32
 // store between the two passes (:152-168) stays where it was (the input of the column kernels IS that f32 plane).
@@ -98,7 +99,9 @@ __device__ inline unsigned xcd_contiguous_id(unsigned bid, unsigned nblk) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Forward column pass (H % 16 == 0; SPLIT_SD = false: "semi-deep", H % 8 == 0 only -- see pair_prep16_cols_kernel).
+// Forward column pass (H % 16 == 0; SPLIT_SD = false: "semi-deep", H % 8 == 0 but not % 16, e.g. 1080 rows: H/16 is not whole,
+// so SD stays one DCT-IV input plane (`dp.as2`, kpad(H/2) wide: the r2 launch of the frequencies 2 mod 4) and the units run to
+// ceil(H/16) -- the middle unit is its own mirror and stores its values twice).
 // Block = one class-major tile of CT memory columns x one group of 8 units e = 8 g + u; thread = (unit u, memory quad):
 // the 16 rows that meet in e (row v mirrors row 15 - v), 4 columns each.  Three LDS rounds of up to six slabs:
 //   A  AS BD AD BS R1 R2 at unit e                       -> k-block g, whole 64-byte pieces
@@ -370,6 +373,16 @@ __global__ __launch_bounds__(256) void prep16_cols_l2_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
+// Deep INVERSE pre-passes.  The inverse transform of coefficients c[0 .. n) combines, per axis,
+//   x[m]  = T[m] +/- o[m]      T = half-length inverse of the even coefficients, o = DCT-IV of the odd ones (n/2 each)
+//   T[m]  = T2[m] +/- o2[m]    T2 = quarter-length inverse of c[4q], o2 = DCT-IV of c[4q+2]                (n/4 each)
+//   T2[m] = EEE-part +/- EEO-part: c[8q] and c[8q+4] against the half bases of length n/4                   (n/8 each)
+// and both DCT-IVs are split like the forward ones: the operands are
+//   AS BD AD BS  (n/8 each)   from k -> c[2k+1]  (rotation partners k, n/2-1-k; fold partners n/4-1-k, n/4+k)
+//   AS2 .. BS2   (n/16 each)  from q -> c[4q+2]
+//   R1 = c[8q], R2 = c[8q+4]  (n/8 each)
+// in the DeepPlanes order of the forward pre-passes.
+//
 // Inverse column pass.  Every operand element of the inverse depends on its own four (or one) coefficient rows only:
 //   AS BD AD BS at unit k < H/8:    rows 2k+1, H/2-1-2k, H/2+2k+1, H-1-2k        (rotation table of H, half length H/4)
 //   R1[k] = row 8k, R2[k] = row 8k+4
@@ -567,8 +580,9 @@ __global__ __launch_bounds__(256) void prep16_inv_cols_l2_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------
-// Inverse row pass (n % 128 == 0).  The eight regions of a thread of pair_prep16_inv_rows_kernel are two independent
-// sets of four; here a thread = (line, tau), tau < n/64, takes the four 16-coefficient regions
+// Inverse row pass (n % 128 == 0).  The operands (c[2k+1] -> AS BD AD BS, c[4q+2] -> AS2 .. BS2, R1 = c[8q], R2 = c[8q+4])
+// close under their rotation and fold pairings in sets of four 16-coefficient regions of a line; a thread = (line, tau),
+// tau < n/64, takes the four regions
 //   g = 16 tau, n/2 - 16 - 16 tau, n/2 + 16 tau, n - 16 - 16 tau
 // that meet in the units k = 8 tau .. 8 tau + 7 of the odd part (c[2k+1]: AS BD AD BS, k-block tau), in the units
 // 4 tau .. 4 tau + 3 of the level-2 odd part (c[4q+2]: AS2 BD2 AD2 BS2, half a k-block) and hold two doubles of R1 = c[8q]
@@ -639,7 +653,7 @@ __global__ __launch_bounds__(256) void prep16_inv_rows_staged_kernel(const float
         rows_store(lds, nslabs, s_plane, s_piece, s_mask, rows, row_base, nl, tid);
         __syncthreads();
     };
-    // ---- rounds 1, 2: AS BD, then AD BS, at k-block tau (the same operations as the units A / mirror of the r3 kernel)
+    // ---- rounds 1, 2: AS BD, then AD BS, at k-block tau
     {
         f64x4 as[2], bd[2], ad[2], bs[2];
 #pragma unroll
@@ -937,8 +951,8 @@ int launch_prep16_cols_staged(hipStream_t st, const float* in, size_t n_frames, 
     return SSW_OK;
 }
 
-int launch_prep16_inv_cols_staged(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                                  const double* rot1, const double* rot2, bool class_major, bool semi, unsigned K8, unsigned K16, bool l2) {
+static int launch_prep16_inv_cols_staged(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
+                                         const double* rot1, const double* rot2, bool class_major, bool semi, unsigned K8, unsigned K16, bool l2) {
     const unsigned tasks0 = K8 / 8, tasks1 = semi ? (K16 / 8 + 2) / 3 : K16 / 8, tiles_c = (unsigned)((w + CT - 1) / CT);
     const unsigned long long nwork = (unsigned long long)(tasks0 + tasks1) * tiles_c * n_frames;
     if (nwork > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
@@ -966,8 +980,8 @@ int launch_prep16_cols_l2(hipStream_t st, const float* in, size_t n_frames, size
     return SSW_OK;
 }
 
-int launch_prep16_inv_cols_l2(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                              const double* rot1, const double* rot2, const double* rot3, bool class_major, bool in_l2, unsigned K16) {
+static int launch_prep16_inv_cols_l2(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
+                                     const double* rot1, const double* rot2, const double* rot3, bool class_major, bool in_l2, unsigned K16) {
     if (h % 16 != 0 || !rot3) return SSW_ERR_BAD_ARG;
     const unsigned tasks0 = K16 / 8, tasks1 = K16 / 8, tiles_c = (unsigned)((w + CT - 1) / CT);
     const unsigned long long nwork = (unsigned long long)(tasks0 + tasks1) * tiles_c * n_frames;
@@ -980,8 +994,8 @@ int launch_prep16_inv_cols_l2(hipStream_t st, const float* in, size_t n_frames, 
     return SSW_OK;
 }
 
-int launch_prep16_inv_rows_l2(hipStream_t st, const float* in, size_t rows, size_t w, double* base,
-                               const double* rot1, const double* rot2, const double* rot3, unsigned K16) {
+static int launch_prep16_inv_rows_l2(hipStream_t st, const float* in, size_t rows, size_t w, double* base,
+                                      const double* rot1, const double* rot2, const double* rot3, unsigned K16) {
     if (w % 128 != 0 || !rot3) return SSW_ERR_BAD_ARG;
     const unsigned NT = (unsigned)(w / 64), tblocks = (NT / 2 + 3) / 4;
     const unsigned long long nblk = (unsigned long long)((rows + RL - 1) / RL) * tblocks;
@@ -991,14 +1005,40 @@ int launch_prep16_inv_rows_l2(hipStream_t st, const float* in, size_t rows, size
     return SSW_OK;
 }
 
-int launch_prep16_inv_rows_staged(hipStream_t st, const float* in, size_t rows, size_t w, double* base,
-                                  const double* rot1, const double* rot2, unsigned K8, unsigned K16) {
+static int launch_prep16_inv_rows_staged(hipStream_t st, const float* in, size_t rows, size_t w, double* base,
+                                         const double* rot1, const double* rot2, unsigned K8, unsigned K16) {
     const unsigned NT = (unsigned)(w / 64), tblocks = (NT + 7) / 8;
     const unsigned long long nblk = (unsigned long long)((rows + RL - 1) / RL) * tblocks;
     if (nblk > 0x7FFFFFFFull) return SSW_ERR_BAD_DIMS;
     prep16_inv_rows_staged_kernel<<<(unsigned)nblk, 256, 0, st>>>(in, planes_of(base, rows, K8, K16), rot1, rot2, (unsigned)rows, (unsigned)w, K8, K16, tblocks);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
+}
+
+// deep inverse pre-passes: the plane order of the forward ones (AS BD AD BS R1 R2 | AS2 BD2 AD2 BS2) with R1 = c[8q], R2 = c[8q+4];
+// `prep` is PrepFamily::L2 or PrepFamily::Staged
+int launch_dct_pair_prep16_inv_rows(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
+                                    const double* rot1, const double* rot2, const double* rot3, PrepFamily prep) {
+    if (n_frames == 0) return SSW_OK;
+    if (w % 128 != 0 || w > 128 * 256 || h > 0xFFFFFFull) return SSW_ERR_BAD_DIMS;
+    const size_t rows = n_frames * h;
+    if (rows > 0xFFFFFFFFull) return SSW_ERR_BAD_DIMS;
+    const unsigned K8 = (unsigned)dct_pair_split_kpad(w), K16 = (unsigned)dct_pair_split_kpad(w / 2);
+    if (prep == PrepFamily::L2) return launch_prep16_inv_rows_l2(st, in, rows, w, base, rot1, rot2, rot3, K16);
+    if (prep != PrepFamily::Staged) return SSW_ERR_BAD_ARG;
+    return launch_prep16_inv_rows_staged(st, in, rows, w, base, rot1, rot2, K8, K16);
+}
+int launch_dct_pair_prep16_inv_cols(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
+                                    const double* rot1, const double* rot2, const double* rot3, PrepFamily prep, const PairLayout& lay) {
+    if (n_frames == 0) return SSW_OK;
+    const bool semi = h % 16 != 0, class_major = lay.class_major;
+    if (w > 0xFFFFFFull || h > 0xFFFFFFull || n_frames > 0xFFFFFFull || h % 8 != 0) return SSW_ERR_BAD_DIMS;
+    const unsigned K8 = (unsigned)dct_pair_split_kpad(h);
+    const unsigned K16 = semi ? (unsigned)pair_kpad(h / 2) : (unsigned)dct_pair_split_kpad(h / 2);      // semi: width of the c[4q+2] plane
+    if (prep == PrepFamily::L2)
+        return launch_prep16_inv_cols_l2(st, in, n_frames, w, h, base, rot1, rot2, rot3, class_major, class_major && lay.rows_l2, K16);
+    if (prep != PrepFamily::Staged) return SSW_ERR_BAD_ARG;
+    return launch_prep16_inv_cols_staged(st, in, n_frames, w, h, base, rot1, rot2, class_major, semi, K8, K16, class_major && lay.rows_l2);
 }
 
 }  // namespace ssw

@@ -10,12 +10,12 @@ namespace {
 
 struct PlanTuning {
     size_t efold_min, efold_inv_min, efold_cols_min, deep_min_rows, deep_min_cols, merge_max_lines;
-    bool prep_staged, class_tile, fuse_cols, derived_fused;
+    bool fuse_cols, derived_fused;
 };
 PlanTuning read_tuning() {
     auto z = [](int which) { return (size_t)tuning(which); };
     return {z(TUNE_EFOLD_MIN), z(TUNE_EFOLD_INV_MIN), z(TUNE_EFOLD_COLS_MIN), z(TUNE_DEEP_MIN_ROWS), z(TUNE_DEEP_MIN_COLS),
-            z(TUNE_MERGE_MAX_LINES), z(TUNE_PREP_STAGED) != 0, z(TUNE_CLASS_TILE) != 0, z(TUNE_FUSE_COLS) != 0, z(TUNE_DERIVED_FUSED) != 0};
+            z(TUNE_MERGE_MAX_LINES), z(TUNE_FUSE_COLS) != 0, z(TUNE_DERIVED_FUSED) != 0};
 }
 
 // the shape / alignment conditions of the folded transforms (the operand-ready path asks for them too)
@@ -32,24 +32,25 @@ bool deep_rows(const PlanTuning& t, size_t len) { return len % 64 == 0 && len >=
 bool deep_cols(const PlanTuning& t, size_t len) { return len % 16 == 0 && len >= t.deep_min_cols; }
 bool deep_inv_rows(const PlanTuning& t, size_t len) { return len % 128 == 0 && len >= t.deep_min_rows && len <= 128 * 256; }
 bool semi_deep_cols(const PlanTuning& t, size_t len) { return len % 8 == 0 && len % 16 != 0 && len >= t.deep_min_cols; }
-// The staged kernels (prep_staged = 0: the r3 ones) take the natural column order or class-major tiles of PREP_STAGED_TILE.
-unsigned class_tile_of(const PlanTuning& t, size_t len) { return t.class_tile ? class_tile((unsigned)len) : (unsigned)len; }
-bool staged_cols_ok(const PlanTuning& t, size_t w, bool class_major) {
-    return t.prep_staged && w % 4 == 0 && w >= 4 && (!class_major || class_tile_of(t, w) == PREP_STAGED_TILE);
+// The staged column kernels take the natural column order or class-major tiles of PREP_STAGED_TILE: not the class-major plane of
+// a row pass whose length 128 does not divide (one tile as wide as the line, class_tile(), dct_pair_common.hpp).
+bool staged_cols_ok(size_t w, bool class_major) {
+    return w % 4 == 0 && w >= 4 && (!class_major || class_tile((unsigned)w) == PREP_STAGED_TILE);
 }
 // LEVEL 2 (r4b / r4c): forward rows of efold_min = 1280 columns or more, inverse rows of efold_inv_min, columns of
-// efold_cols_min = 720 rows (staged pre-passes only).  Every launch sums len/16 terms: 240 at 4K rows, 79 % of peak against 84 %
-// for len/8 at 2/3 of the multiply-adds; K = 135 columns at 50 TFLOP/s against 64 for 270 at half of them.  Measured a gain
+// efold_cols_min = 720 rows (natural order or 128-column class tiles).  Every launch sums len/16 terms: 240 at 4K rows, 79 % of peak
+// against 84 % for len/8 at 2/3 of the multiply-adds; K = 135 columns at 50 TFLOP/s against 64 for 270 at half of them.  Measured a gain
 // from 1280 x 720 up, once the plane between the passes is class-major.
 bool efold(const PlanTuning& t, size_t len) { return deep_rows(t, len) && len >= t.efold_min; }
-bool efold_inv(const PlanTuning& t, size_t len) { return deep_inv_rows(t, len) && t.prep_staged && len >= t.efold_inv_min; }
+bool efold_inv(const PlanTuning& t, size_t len) { return deep_inv_rows(t, len) && len >= t.efold_inv_min; }
 bool efold_cols(const PlanTuning& t, size_t h, size_t w, bool class_major) {
-    return deep_cols(t, h) && staged_cols_ok(t, w, class_major) && h >= t.efold_cols_min;
+    return deep_cols(t, h) && staged_cols_ok(w, class_major) && h >= t.efold_cols_min;
 }
-// Can the column pre-pass of an `fh`-row plane read the class-major order of a deep row pass?  The deep kernels all can, of
-// the semi-deep ones the staged forms; and the column pass reaches those strategies only through the split (fh >= 128).
+// Can the column pre-pass of an `fh`-row plane read the class-major order of a deep row pass?  The deep kernels all can, the
+// semi-deep ones (staged only) when 128 divides the row length; and the column pass reaches those strategies only through the
+// split (fh >= 128).
 bool cols_read_class_major(const PlanTuning& t, size_t fh, size_t w) {
-    return can_fold2_cols(fh) && can_split(fh) && (deep_cols(t, fh) || (semi_deep_cols(t, fh) && staged_cols_ok(t, w, true)));
+    return can_fold2_cols(fh) && can_split(fh) && (deep_cols(t, fh) || (semi_deep_cols(t, fh) && staged_cols_ok(w, true)));
 }
 // the GEMM launcher's rule: 64-line tiles when 128-line ones (x 8 classes when merged) would not fill 448 block slots
 bool launch_is_small(const PlanTuning& t, size_t lines, size_t pairs) {
@@ -60,7 +61,7 @@ bool launch_is_small(const PlanTuning& t, size_t lines, size_t pairs) {
 // as the padded units, both passes on 128-line tiles (small batches keep the unfused path).  The column pass must take its
 // deep strategy by itself (can_split): else it would read an f32 plane the fused row pass never wrote.
 bool can_fuse_cols(const PlanTuning& t, size_t n_frames, size_t w, size_t h) {
-    if (!t.fuse_cols || n_frames == 0 || w < h || w % 128 != 0 || h % 16 != 0 || class_tile_of(t, w) != 128) return false;
+    if (!t.fuse_cols || n_frames == 0 || w < h || w % 128 != 0 || h % 16 != 0) return false;
     if (!efold(t, w) || !efold_cols(t, h, w, true) || !can_split(h) || !can_fold2_cols(h)) return false;
     const size_t hup = dct_pair_fused_units(h);
     if (pair_kpad(h / 8) != hup) return false;
@@ -75,7 +76,7 @@ PassPlan plan_pass_t(const PlanTuning& t, const PlanInput& in, bool first_pass, 
     const PlanSettings& s = in.s;
     p.merge = (is_row ? n * h : n * w) <= t.merge_max_lines;
     p.layout.rows_l2 = inverse ? efold_inv(t, w) : efold(t, w);
-    p.layout.tile = class_tile_of(t, w);
+    p.layout.tile = class_tile((unsigned)w);
     const bool can_fold = s.fold && (is_row ? rows_can_fold(w, in.aligned) : cols_can_fold(w, h, in.aligned));
     if (!(can_fold && s.fold_level >= 3 && f64 && dct_pair_can_run(n, w, h, in.aligned))) return p;        // Dense
     const bool two = s.fold_level >= 4 && (is_row ? can_fold2(len) : can_fold2_cols(len));
@@ -88,14 +89,16 @@ PassPlan plan_pass_t(const PlanTuning& t, const PlanInput& in, bool first_pass, 
     const size_t fh = in.full_h ? in.full_h : h;
     const bool cm = !in.natural_order && w >= fh && w % 4 == 0 && (inverse ? deep_inv_rows(t, w) : deep_rows(t, w)) &&
                     cols_read_class_major(t, fh, w) && is_row == first_pass;
-    auto col_prep = [&](bool l2) { return l2 ? PrepFamily::L2 : staged_cols_ok(t, w, cm) ? PrepFamily::Staged : PrepFamily::R3; };
+    // column pre-pass: level 2 and staged read the natural order or 128-column class tiles; a class-major plane whose row length
+    // 128 does not divide is one tile, which only the deep forward kernel of dct_pair_prep.hip reads (cols_read_class_major)
+    auto col_prep = [&](bool l2) { return l2 ? PrepFamily::L2 : staged_cols_ok(w, cm) ? PrepFamily::Staged : PrepFamily::OneTile; };
     const bool deep = p.split && (is_row ? (inverse ? deep_inv_rows(t, len) : deep_rows(t, len)) : deep_cols(t, len) && w % 4 == 0);
     if (deep) {
         p.layout.class_major = cm;
         const bool l2 = is_row ? (inverse ? efold_inv(t, len) : efold(t, len)) : efold_cols(t, len, w, cm);
         if (inverse) {
             p.strategy = l2 ? PassStrategy::DeepInvL2 : PassStrategy::DeepInv;
-            p.prep = !is_row ? col_prep(l2) : l2 ? PrepFamily::L2 : t.prep_staged ? PrepFamily::Staged : PrepFamily::R3;
+            p.prep = !is_row ? col_prep(l2) : l2 ? PrepFamily::L2 : PrepFamily::Staged;
         } else if (l2 && cm && !in.full_h && can_fuse_cols(t, n, w, h)) {
             p.strategy = is_row ? PassStrategy::FusedRows : PassStrategy::FusedCols;
             if (is_row) p.merge = n * 16 * dct_pair_fused_units(h) <= t.merge_max_lines;      // the unit-ordered, padded lines

@@ -14,7 +14,9 @@ namespace ssw {
 // not 16-divisible length); DeepInv(L2).
 enum class PassStrategy { Dense, PairL1, PairTwo, PairThree, Deep, DeepL2, FusedRows, FusedCols, SemiDeep, SemiDeepInv,
                           DeepInv, DeepInvL2 };
-enum class PrepFamily { None, R3, Staged, L2 };      // kernels of a deep / semi-deep column or deep inverse row pre-pass
+// Kernels of a deep / semi-deep column or deep inverse row pre-pass: at level 2, LDS-staged, or -- deep forward columns only --
+// the kernel that reads a class-major plane of ONE tile (the row pass's length is no multiple of PREP_STAGED_TILE).
+enum class PrepFamily { None, OneTile, Staged, L2 };
 constexpr unsigned PREP_STAGED_TILE = 128;           // the LDS-staged pre-passes read class-major tiles of this many columns
 
 // The plane between the passes as a launch sees it (dct_pair_common.hpp): class-major or natural; whether the transform's row

@@ -151,22 +151,15 @@ int launch_dct_pair_gemm_rows_subset_merged_f64(hipStream_t st, const PairSubset
 // 2 cosO, 3 sinO), the rotation table of an axis, and the pass that turns an odd operand plane into AS | BD | AD | BS
 size_t dct_pair_split_kpad(size_t len);
 // tuning.hip: the process-wide table of strategy thresholds / A-B switches (ssw_tuning_set, include/ssw.h)
-enum { TUNE_EFOLD_MIN, TUNE_EFOLD_INV_MIN, TUNE_EFOLD_COLS_MIN, TUNE_CLASS_TILE, TUNE_DEEP_MIN_ROWS, TUNE_DEEP_MIN_COLS, TUNE_PREP_STAGED,
+enum { TUNE_EFOLD_MIN, TUNE_EFOLD_INV_MIN, TUNE_EFOLD_COLS_MIN, TUNE_DEEP_MIN_ROWS, TUNE_DEEP_MIN_COLS,
        TUNE_MERGE_MAX_LINES, TUNE_BN32, TUNE_BAND_SPLIT, TUNE_FUSE_COLS, TUNE_UPLOAD_BANDS, TUNE_SPECULATE_K, TUNE_PREP_LIGHT, TUNE_LANE_STAGGER, TUNE_DERIVED_FUSED, TUNE_TILE48, TUNE_BASE_PRUNE, TUNE_BASE_ENERGY_LOWP, TUNE_COUNT };
 long long tuning(int which);
+// the level-2 and LDS-staged forms of the deep forward column pre-pass (dct_pair_prep_staged.hip), as
+// launch_dct_pair_prep16_cols calls them; PrepFamily::OneTile keeps the kernel of dct_pair_prep.hip
 int launch_prep16_cols_l2(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
                           const double* rot1, const double* rot2, const double* rot3, bool class_major, bool in_l2, unsigned K16);
-int launch_prep16_inv_cols_l2(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                              const double* rot1, const double* rot2, const double* rot3, bool class_major, bool in_l2, unsigned K16);
-// LDS-staged forms of the deep pre-passes (dct_pair_prep_staged.hip; PrepFamily::R3 keeps the r3 kernels)
 int launch_prep16_cols_staged(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
                               const double* rot1, const double* rot2, bool class_major, bool semi, unsigned K8, unsigned K16, bool efold);
-int launch_prep16_inv_cols_staged(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
-                                  const double* rot1, const double* rot2, bool class_major, bool semi, unsigned K8, unsigned K16, bool l2);
-int launch_prep16_inv_rows_l2(hipStream_t st, const float* in, size_t rows, size_t w, double* base,
-                              const double* rot1, const double* rot2, const double* rot3, unsigned K16);
-int launch_prep16_inv_rows_staged(hipStream_t st, const float* in, size_t rows, size_t w, double* base,
-                                  const double* rot1, const double* rot2, unsigned K8, unsigned K16);
 size_t dct_pair_split_elems(size_t n_frames, size_t w, size_t h);
 size_t dct_pair_split_basis_rows(size_t len, int which);
 int launch_make_split_basis_blocked(hipStream_t st, size_t n, bool inverse, int which, double* out);
@@ -175,7 +168,8 @@ int launch_dct_pair_rotate(hipStream_t st, const double* p, const double* rot, d
 // deep forward row pre-pass (len % 64 == 0): D and SD split, SS folded a third time, in one sweep over the source
 // (a RowInput); base: AS BD AD BS R1 R2 (lines * split_kpad(len) each), AS2 BD2 AD2 BS2 (lines * split_kpad(len/2))
 size_t dct_pair_semi_deep_elems(size_t lines, size_t len);
-// deep inverse pre-passes (coefficient plane -> the same ten planes; R1 = c[8q], R2 = c[8q+4]); `prep` / `lay`: of the plan
+// deep inverse pre-passes (dct_pair_prep_staged.hip: coefficient plane -> the same ten planes; R1 = c[8q], R2 = c[8q+4]);
+// `prep` / `lay`: of the plan
 int launch_dct_pair_prep16_inv_rows(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,
                                     const double* rot1, const double* rot2, const double* rot3, PrepFamily prep);
 int launch_dct_pair_prep16_inv_cols(hipStream_t st, const float* in, size_t n_frames, size_t w, size_t h, double* base,

@@ -25,10 +25,8 @@ Entry g_tune[TUNE_COUNT] = {
     {"efold_min", "SSW_EFOLD_MIN", 1280},              // shortest forward row pass at level 2 (dct_plan.hip)
     {"efold_inv_min", "SSW_EFOLD_INV_MIN", 1280},      // shortest inverse row pass at level 2 (dct_plan.hip)
     {"efold_cols_min", "SSW_EFOLD_COLS_MIN", 720},     // shortest column pass at level 2 (dct_plan.hip)
-    {"class_tile", "SSW_CLASS_TILE", 1},               // class-major order inside tiles of 128 columns (0: one tile per line)
     {"deep_min_rows", "SSW_DEEP_MIN_ROWS", 256},       // shortest row pass that takes the deep pre-passes
     {"deep_min_cols", "SSW_DEEP_MIN_COLS", 256},       // ... column pass
-    {"prep_staged", "SSW_PREP_STAGED", 1},             // the LDS-staged pre-passes (0: the r3 kernels)
     {"merge_max_lines", "SSW_MERGE_MAX_LINES", 8192},  // passes of at most this many lines run a stage's classes as one launch
     {"bn32", "SSW_BN32", -1},                          // 32-pair tiles for small single-class launches: -1 automatic, 0 / 1 forced
     {"band_split", "SSW_BAND_SPLIT", 1},               // single-image handles: row pass of the top half beside the upload of the bottom half

@@ -78,6 +78,23 @@ int main() {
         const TransformPlan q = plan(40, 512, 272, SSW_DCT3);
         CHECK(q.rows().strategy == S::DeepInv && q.cols().strategy == S::DeepInv && q.rows().prep == PrepFamily::Staged, "512x272 inverse");
     }
+    // rows whose length 128 does not divide: the class-major plane is one tile as wide as the line, which the one-tile deep
+    // forward column pre-pass reads (level 1: 320 x 256; behind a level-2 row pass: 1344 x 256).  The inverse has no
+    // deep row pass there (it needs a multiple of 128), so its plane stays natural and its columns take the staged kernels.
+    {
+        const TransformPlan p = plan(3, 320, 256);
+        CHECK(p.rows().strategy == S::Deep && p.rows().layout.class_major && p.rows().layout.tile == 320, "320x256 rows");
+        CHECK(p.cols().strategy == S::Deep && p.cols().prep == PrepFamily::OneTile && p.cols().layout.class_major, "320x256 columns");
+        CHECK(plan_flags(p) == (PAIR | RD | CD | CM), "320x256 flags");
+        const TransformPlan q = plan(3, 1344, 256);
+        CHECK(q.rows().strategy == S::DeepL2 && q.rows().layout.class_major && q.rows().layout.tile == 1344, "1344x256 rows");
+        CHECK(q.cols().strategy == S::Deep && q.cols().prep == PrepFamily::OneTile && !plan_is_level2(q.cols()), "1344x256 columns");
+        for (size_t w : {320, 1344}) {
+            const TransformPlan r = plan(3, w, 256, SSW_DCT3);
+            CHECK(!plan_is_deep(r.rows()) && !r.rows().layout.class_major && !r.cols().layout.class_major, "one-tile widths, inverse rows");
+            CHECK(r.cols().strategy == S::DeepInv && r.cols().prep == PrepFamily::Staged, "one-tile widths, inverse columns");
+        }
+    }
     // the reference's 640 x 444 cat: 444 rows do not fold -- the dense kernels
     {
         const TransformPlan p = plan(3, 640, 444);
@@ -131,7 +148,8 @@ int main() {
         CHECK(plan_flags(p) == PAIR, "odd split off flags");
         CHECK(plan(8, 3840, 2160, SSW_DCT3, s).rows().strategy == S::PairTwo, "odd split off, inverse");
     }
-    // thresholds through the tuning table
+    // thresholds through the tuning table; the retired switches back to the r3 pre-passes are unknown names
+    CHECK(ssw_tuning_set("prep_staged", 0) == SSW_ERR_BAD_ARG && ssw_tuning_set("class_tile", 0) == SSW_ERR_BAD_ARG, "retired switches");
     CHECK(ssw_tuning_set("fuse_cols", 0) == SSW_OK, "set fuse_cols");
     {
         const TransformPlan p = plan(128, 3840, 2160);

@@ -78,12 +78,13 @@ def test_tuning_table_needs_no_gpu():
     base = tuning.get("efold_cols_min")
     with tuning(efold_cols_min=64):
         assert tuning.get("efold_cols_min") == 64
-        with tuning(efold_cols_min=128, prep_staged=0):
-            assert tuning.get("efold_cols_min") == 128 and tuning.get("prep_staged") == 0
-        assert tuning.get("efold_cols_min") == 64 and tuning.get("prep_staged") == 1
+        with tuning(efold_cols_min=128, fuse_cols=0):
+            assert tuning.get("efold_cols_min") == 128 and tuning.get("fuse_cols") == 0
+        assert tuning.get("efold_cols_min") == 64 and tuning.get("fuse_cols") == 1
     assert tuning.get("efold_cols_min") == base
     assert lib.ssw_tuning_set(b"no_such_switch", 1) == L.SSW_ERR_BAD_ARG
-    for retired in (b"fuse_inv_cols", b"inv_prep_light", b"gemm_stagger", b"gemm_group_m", b"gemm_group_m_rows", b"merge_batch"):
+    for retired in (b"fuse_inv_cols", b"inv_prep_light", b"gemm_stagger", b"gemm_group_m", b"gemm_group_m_rows", b"merge_batch",
+                    b"prep_staged", b"class_tile"):
         assert lib.ssw_tuning_set(retired, 1) == L.SSW_ERR_BAD_ARG, retired
     assert lib.ssw_tuning_reset(None) == L.SSW_OK
     assert lib.ssw_build_all_strategies() == 0          # always 0: the library has one build

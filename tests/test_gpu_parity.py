@@ -174,7 +174,23 @@ def test_dct_operand_ready_path_matches(shape, dct_type, level):
 
 # (H, W): rows deep forward and inverse (W % 128), forward only (W % 64), first level only (W % 8); columns deep (H % 16,
 # >= 256) or first level only (H % 8, or short); plus shapes the split does not take at all
-@pytest.mark.parametrize("shape", [(256, 512), (272, 384), (264, 320), (136, 200), (512, 256), (304, 1024), (1080, 1920), (72, 136)])
+ODD_SPLIT_SHAPES = [(256, 512), (272, 384), (264, 320), (136, 200), (512, 256), (304, 1024), (1080, 1920), (72, 136)]
+# deep columns behind deep rows whose length 128 does not divide: the forward column pre-pass reads a class-major plane of ONE
+# tile (csrc/dct_pair_prep.hip: pair_prep16_cols_onetile_kernel).  16 whole units of rows; 17 units (a partial store quad and
+# the planes' padding up to their k-blocks); a row pass at level 2 (the sixteen-class order of the plane)
+ONE_TILE_SHAPES = [(256, 320), (272, 320), (256, 1344)]
+
+
+def test_one_tile_shapes_take_the_one_tile_column_prepass():
+    """What makes ONE_TILE_SHAPES cover that kernel: a class-major plane (deep rows) whose width 128 does not divide, read by
+    deep columns that are not at level 2 (those are the staged kernels' and need 128-column tiles)."""
+    for h, w in ONE_TILE_SHAPES:
+        p = G.ctx().transform_plan(3, w, h)
+        assert w % 128 != 0 and p["class_major"] and p["rows_deep"] and p["cols_deep"] and not p["cols_level2"], (h, w, p)
+    assert G.ctx().transform_plan(3, 1344, 256)["rows_level2"] and not G.ctx().transform_plan(3, 320, 256)["rows_level2"]
+
+
+@pytest.mark.parametrize("shape", ODD_SPLIT_SHAPES + ONE_TILE_SHAPES)
 @pytest.mark.parametrize("dct_type", [L.DCT2, L.DCT2_ORTHOGONAL, L.DCT3])
 def test_odd_split_matches_exact_operands(shape, dct_type):
     """ssw_ctx_set_odd_split: the odd halves as rotated quarter-length cosine + sine pairs (default; "deep" pre-passes

@@ -397,7 +397,7 @@ def test_a_context_that_saw_poison_answers_like_a_fresh_one(name, k, follow):
                 # the pads these follow-ups are there for lie along k: the row pre-pass leaves w/4 = 108 terms in rows of 112
                 # doubles; the staged column pre-pass runs, deep (272 rows: 34 units in rows of 40) or semi-deep (264 rows:
                 # the M plane's 66 terms in rows of 72, which only its zero fill writes)
-                assert tuning.get("prep_staged") == 1 and (w // 4) % 8 != 0 and M.kpad(w // 2) > w // 4
+                assert (w // 4) % 8 != 0 and M.kpad(w // 2) > w // 4
                 assert h >= tuning.get("deep_min_cols") and M.kpad(h // 4) > h // 8
                 if follow.startswith("semi"):
                     assert h % 16 == 8 and not plan["cols_deep"] and M.kpad(h // 2) > h // 4

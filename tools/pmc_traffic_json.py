@@ -91,10 +91,8 @@ names = {   # instance in the rocprofv3 output (tools/pmc_summary.py; enum argum
         "r5, writer: RGB f32 in, operand planes + I, Q planes out"),
     "prep16_derived_fused_kernel<(PixFmt)0>": ("prep16_derived_fused_kernel<rgb>", lines_r * W * 12 + lines_r * 256 * 4,
         "r5: the derived frame's pruned row pass in one kernel (csrc/dct_pair_derived.hip): RGB f32 in, the compact plane (256 columns for k = 1000) out"),
-    "pair_prep16_cols_kernel<true>": ("pair_prep16_cols_kernel", lines_r * W * (4 + esz),
-        "r3 kernel (SSW_PREP_STAGED=0): f32 plane in, transposed deep f64 operand planes out (mean over launches incl. the narrow pruned ones)"),
-    "pair_prep16_inv_rows_kernel": ("pair_prep16_inv_rows_kernel", lines_r * W * (4 + esz), "r3 kernel: coefficient plane in, deep inverse operand planes out"),
-    "pair_prep16_inv_cols_kernel<true>": ("pair_prep16_inv_cols_kernel", lines_r * W * (4 + esz), "r3 kernel: the same, transposed"),
+    "pair_prep16_cols_onetile_kernel": ("pair_prep16_cols_onetile_kernel", lines_r * W * (4 + esz),
+        "forward column pre-pass behind rows whose length 128 does not divide: f32 plane (class-major, one tile) in, the ten transposed f64 operand planes out"),
     # r4: the LDS-staged forms (csrc/dct_pair_prep_staged.hip); <1 | 2, true> = class-major tiles, deep
     "prep16_cols_staged_kernel<1, true>": ("prep16_cols_staged_kernel<class-major tile, deep>", lines_r * W * (4 + esz),
         "forward column pre-pass: f32 plane (class-major tiles of 128 columns) in, the ten transposed f64 operand planes out"),
