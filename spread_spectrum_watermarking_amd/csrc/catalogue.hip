@@ -329,8 +329,8 @@ int match_enqueue(ssw_ctx* ctx, const uint8_t* query, size_t nq, const uint8_t* 
                   uint32_t* all) {
     hipStream_t st = ctx->stream;
     SSW_TRY(match_raise_lds_limit());
-    SSW_TRY(grow(ctx->catalogue[0], MT_PART_BYTES));
-    uint64_t* part = (uint64_t*)ctx->catalogue[0].p;
+    SSW_TRY(grow(ctx->catalogue.top8, MT_PART_BYTES));
+    uint64_t* part = ctx->catalogue.top8.as<uint64_t>();
     for (size_t q0 = 0; q0 < nq; q0 += MT_Q) {
         const unsigned m = (unsigned)std::min<size_t>(MT_Q, nq - q0);
         // the catalogue once per query tile, the distances of the tile when the caller wants them
@@ -378,8 +378,8 @@ extern "C" int ssw_signature_host_rgb8(ssw_ctx* ctx, const uint8_t* const* host_
     CtxGuard g(ctx);
     hipStream_t st = ctx->stream;
     auto frame_bytes = [&](size_t i) { return (size_t)shapes[i].w * shapes[i].h * shapes[i].channels; };
-    SSW_TRY(grow(ctx->catalogue[2], n * ssw::SIG_BYTES));
-    uint8_t* sigs = (uint8_t*)ctx->catalogue[2].p;
+    SSW_TRY(grow(ctx->catalogue.sigs, n * ssw::SIG_BYTES));
+    uint8_t* sigs = ctx->catalogue.sigs.as<uint8_t>();
     // groups of at most SIG_GROUP_BYTES (one frame's own size if that is more): uploads and kernels are ordered on the
     // context's stream, so the next group's frames overwrite the workspace only behind the kernels that read it
     std::vector<const void*> ptrs;
@@ -388,8 +388,8 @@ extern "C" int ssw_signature_host_rgb8(ssw_ctx* ctx, const uint8_t* const* host_
         size_t g1 = g0, bytes = 0;
         offs.clear();
         while (g1 < n && (g1 == g0 || bytes + frame_bytes(g1) <= SIG_GROUP_BYTES)) { offs.push_back(bytes); bytes += up(frame_bytes(g1++), 256); }
-        SSW_TRY(grow(ctx->catalogue[1], bytes));
-        uint8_t* ws = (uint8_t*)ctx->catalogue[1].p;
+        SSW_TRY(grow(ctx->catalogue.frames, bytes));
+        uint8_t* ws = ctx->catalogue.frames.as<uint8_t>();
         ptrs.clear();
         for (size_t i = g0; i < g1; ++i) {
             SSW_TRY(upload(ctx, ws + offs[i - g0], host_frames[i], frame_bytes(i), st));

@@ -152,8 +152,9 @@ void prune_plan_classes(const PairClass* cls, int n, unsigned cap, PrunePlan& pl
 // the table does not serve a class at that length.
 struct PruneClassSrc {
     signed char p1, p2;        // operand plane(s) by number at the plan's level (l1x / l2x); p2: the sine operand of a split class, else -1
-    signed char lane_buf;      // a class that is neither deep nor split reads the lane's operand[lane_buf] as the two- / three-level
-                               // pre-passes fill them (x- | D in [1], S- in [0], SS SD | SSS SS- in [2] [3]); -1: the numbered plane
+    signed char lane_buf;      // a class that is neither deep nor split reads plane lane_buf of the pruned chunk's four (Lane::Pruned::o,
+                               // ssw_internal.hpp) as the two- / three-level pre-passes fill them: 0 S-, 1 x- | D, 2 3 SS SD | SSS SS-;
+                               // -1: the numbered plane
     bool split;
     BasisKind y1, y2;          // the bases as cached (the gather reads sinE itself, not its launch variant); y2: split only
     unsigned ydiv, src_rows, Kp, ktrue;      // bases of length w / ydiv with src_rows lines; padded / true sum length

@@ -56,7 +56,7 @@ bool plan_derived_fused(const PassPlan& rows, size_t lines); // the pruned deriv
 // the (f64) pair path fits the shape: folding shapes, aligned planes, operand planes below 4 GB
 bool dct_pair_can_run(size_t n_frames, size_t w, size_t h, bool aligned);
 size_t plan_frame_limit(const PlanSettings& s, bool f64, size_t w, size_t h);      // frames per group (f64: 32-bit operand offsets)
-// doubles of a lane's sixth operand buffer: what the passes of both directions of this shape use (they share the lane)
+// doubles of a lane's `deep` operand slot: what the passes of both directions of this shape use (they share the lane)
 size_t split_scratch_elems(size_t n, size_t w, size_t h);
 
 }  // namespace ssw

@@ -416,8 +416,8 @@ extern "C" int ssw_filter_rgb8(ssw_ctx* ctx, const uint8_t* dev_frames, size_t n
     const size_t group = std::min<size_t>({ssw::FL_BATCH, n_jobs, std::max<size_t>(1, ssw::FL_GROUP_BYTES / fb)});
     bool any_blur = false;
     for (size_t i = 0; i < n_jobs; ++i) any_blur |= jobs[i].kind != SSW_FILTER_MEDIAN3;
-    if (any_blur) SSW_TRY(grow(ctx->filter, group * fb));
-    uint8_t* planes = static_cast<uint8_t*>(ctx->filter.p);
+    if (any_blur) SSW_TRY(grow(ctx->shared.filter, group * fb));
+    uint8_t* planes = ctx->shared.filter.as<uint8_t>();
     const uint32_t W = (uint32_t)w, H = (uint32_t)h;
     // per job: the frame in and the frame out, whatever the kind
     StageTimer t(ctx, SSW_STAGE_CONVERT, st, (double)n_jobs * (double)(2 * fb));

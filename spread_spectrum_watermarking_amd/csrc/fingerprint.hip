@@ -323,23 +323,23 @@ int fingerprint_copies(ssw_ctx* ctx, const ssw_config& c, const float* coef, con
 
     // u32 plan: slot_of_line [lb] | line_of_slot [lb] | cnt [lb] | off [lb + 1] | cursor [lb] | list [k_eff] | info [4]
     const size_t u32_words = 5 * lb + 1 + k_eff + 4;
-    SSW_TRY(grow(ctx->fingerprint[0], u32_words * sizeof(uint32_t)));
-    SSW_TRY(grow(ctx->fingerprint[1], (s_pad * la + s_pad * lb) * sizeof(double)));
-    SSW_TRY(grow(ctx->fingerprint[2], plane * sizeof(double)));
-    SSW_TRY(grow(ctx->fingerprint[3], group * std::max<size_t>(k_eff, 1) * sizeof(double)));
-    SSW_TRY(grow(ctx->fingerprint[4], group * s_pad * la * sizeof(double)));
-    uint32_t* slot_of_line = (uint32_t*)ctx->fingerprint[0].p;
+    SSW_TRY(grow(ctx->fingerprint.line_plan, u32_words * sizeof(uint32_t)));
+    SSW_TRY(grow(ctx->fingerprint.t64, (s_pad * la + s_pad * lb) * sizeof(double)));
+    SSW_TRY(grow(ctx->fingerprint.yr64, plane * sizeof(double)));
+    SSW_TRY(grow(ctx->fingerprint.deltas, group * std::max<size_t>(k_eff, 1) * sizeof(double)));
+    SSW_TRY(grow(ctx->fingerprint.dt, group * s_pad * la * sizeof(double)));
+    uint32_t* slot_of_line = ctx->fingerprint.line_plan.as<uint32_t>();
     uint32_t* line_of_slot = slot_of_line + lb;
     uint32_t* cnt = line_of_slot + lb;
     uint32_t* off = cnt + lb;
     uint32_t* cursor = off + lb + 1;
     uint32_t* list = cursor + lb;
     uint32_t* info = list + k_eff;
-    double* t64 = (double*)ctx->fingerprint[1].p;
+    double* t64 = ctx->fingerprint.t64.as<double>();
     double* g = t64 + s_pad * la;
-    double* yr = (double*)ctx->fingerprint[2].p;
-    double* d = (double*)ctx->fingerprint[3].p;
-    double* dt = (double*)ctx->fingerprint[4].p;
+    double* yr = ctx->fingerprint.yr64.as<double>();
+    double* d = ctx->fingerprint.deltas.as<double>();
+    double* dt = ctx->fingerprint.dt.as<double>();
 
     const void *inv_w, *inv_h, *fwd_a, *fwd_b;
     SSW_TRY(get_basis(ctx, w, true, true, BasisKind::Dense, &inv_w));
@@ -412,13 +412,11 @@ int fingerprint_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_
     const size_t k_eff = std::min(k, plane - 1);                       // zip() truncation, :396
     CtxGuard gd(ctx);
     ssw_ctx::Lane& ws = ctx->lane[0];
-    for (int p = 0; p < 4; ++p) SSW_TRY(grow(ws.plane[p], plane * sizeof(float)));
+    ssw_ctx::Lane::WriterPlanes pl;
+    SSW_TRY(ws.writer_planes(plane * sizeof(float), pl));
     SSW_TRY(grow(ws.idx, std::max<size_t>(k_eff, 1) * sizeof(uint32_t)));
-    float* y = (float*)ws.plane[0].p;
-    float* pi = (float*)ws.plane[1].p;
-    float* pq = (float*)ws.plane[2].p;
-    float* tmp = (float*)ws.plane[3].p;
-    uint32_t* idx = dev_indices_out ? dev_indices_out : (uint32_t*)ws.idx.p;
+    float *y = pl.y, *pi = pl.i, *pq = pl.q, *tmp = pl.scratch;
+    uint32_t* idx = dev_indices_out ? dev_indices_out : ws.idx.as<uint32_t>();
     Chain ch;
     SSW_TRY(build_forward_from_rgb(ctx, ws, cfg->precision, dev_rgb, fmt_in, 1, w, h, y, pi, pq, tmp, ch));   // Writer::new :308-313
     SSW_TRY(run_serial(ch, ctx->stream));

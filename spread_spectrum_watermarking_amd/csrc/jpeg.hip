@@ -300,8 +300,8 @@ extern "C" int ssw_jpeg_rgb8(ssw_ctx* ctx, const uint8_t* dev_frames, size_t n_f
     const uint32_t strips = (mcus + ssw::JP_MCUS - 1) / ssw::JP_MCUS;
     const size_t per_job = (size_t)pitch * rows16 * 3 / 2;
     const size_t group = std::min<size_t>({ssw::JP_BATCH, n_jobs, std::max<size_t>(1, ssw::JP_GROUP_BYTES / per_job)});
-    SSW_TRY(grow(ctx->jpeg, group * per_job));
-    uint8_t* planes = static_cast<uint8_t*>(ctx->jpeg.p);
+    SSW_TRY(grow(ctx->shared.jpeg, group * per_job));
+    uint8_t* planes = ctx->shared.jpeg.as<uint8_t>();
     // per job: the frame in and out, and the decoded planes out and in again
     StageTimer t(ctx, SSW_STAGE_CONVERT, st, (double)n_jobs * (double)(2 * fb + 2 * (w * h + 2 * cw * ch)));
     for (size_t i0 = 0; i0 < n_jobs; i0 += group) {

@@ -397,8 +397,7 @@ constexpr size_t GROUP_BYTES = 256u << 20;      // workspace of one group of sus
 // the original's luma plane, once per call: opitch % 4 == 0, 16 zero bytes of slack behind its last row (locate_fine_kernel)
 int original_luma(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, uint8_t** lo, unsigned* opitch) {
     *opitch = (unsigned)up(w, 4);
-    SSW_TRY(grow(ctx->locate[0], (size_t)*opitch * h + 16));
-    *lo = (uint8_t*)ctx->locate[0].p;
+    SSW_TRY(grow_as(ctx->locate.luma, (size_t)*opitch * h + 16, *lo));
     SSW_HIP_CHECK(hipMemsetAsync(*lo + (size_t)*opitch * h, 0, 16, ctx->stream));
     LumaBatch lb{};
     lb.it[0] = LumaDev{dev_base, *lo, (uint32_t)w, (uint32_t)h, 3u, *opitch};
@@ -554,10 +553,10 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
     // the original: luma plane once per call, and its 16 phase planes when a suspect takes the coarse factor 4
     const unsigned wq = (unsigned)(w / 4), hq = (unsigned)(h / 4), qpitch = (unsigned)up(std::max(wq, 1u), 4);
     const size_t plane_stride = (size_t)qpitch * hq;
-    if (any_f4) SSW_TRY(grow(ctx->locate[1], 16 * plane_stride + 16));
-    SSW_TRY(grow(ctx->locate[3], n * (2 * LOC_TOP + 2) * sizeof(uint64_t)));
-    uint8_t* phases = (uint8_t*)ctx->locate[1].p;
-    uint64_t* keys = (uint64_t*)ctx->locate[3].p;
+    if (any_f4) SSW_TRY(grow(ctx->locate.phases, 16 * plane_stride + 16));
+    uint8_t* phases = ctx->locate.phases.as<uint8_t>();
+    uint64_t* keys = nullptr;
+    SSW_TRY(grow_as(ctx->locate.keys, n * (2 * LOC_TOP + 2) * sizeof(uint64_t), keys));
     uint64_t* sums = keys + n * LOC_TOP;
     uint64_t* res = sums + n * LOC_TOP;
     uint8_t* lo = nullptr;
@@ -577,8 +576,8 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
     const Original og{lo, opitch, (unsigned)h, phases, qpitch, hq, plane_stride};
     for (size_t g0 = 0; g0 < n;) {
         const Group g = layout_group(items, g0);
-        SSW_TRY(grow(ctx->locate[2], g.bytes + 16));
-        uint8_t* ws = (uint8_t*)ctx->locate[2].p;
+        uint8_t* ws = nullptr;
+        SSW_TRY(grow_as(ctx->locate.group, g.bytes + 16, ws));
         // R: the suspect resized to the size it had in the original (alpha dropped first); timed as SSW_STAGE_RESIZE
         for (size_t i = g0; i < g.g1; ++i) {
             const Item& it = items[i];
@@ -667,10 +666,10 @@ int make_rung(LadderTaps& taps, const ssw_placement& p, uint32_t sus, uint32_t p
 }
 
 int upload_taps(ssw_ctx* ctx, const LadderTaps& taps, const uint32_t** dev) {
-    SSW_TRY(grow(ctx->locate[5], taps.words.size() * sizeof(uint32_t)));
-    SSW_HIP_CHECK(hipMemcpyAsync(ctx->locate[5].p, taps.words.data(), taps.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    SSW_TRY(grow(ctx->locate.taps, taps.words.size() * sizeof(uint32_t)));
+    SSW_HIP_CHECK(hipMemcpyAsync(ctx->locate.taps.p, taps.words.data(), taps.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     untimed_work(ctx);
-    *dev = (const uint32_t*)ctx->locate[5].p;
+    *dev = ctx->locate.taps.as<const uint32_t>();
     return SSW_OK;
 }
 
@@ -750,12 +749,12 @@ int locate_scaled_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h
     const unsigned qpitch = (unsigned)up((nbx + 1) / 2, 4), qrows = (nby + 1) / 2;
     const size_t plane_stride = (size_t)qpitch * qrows;
     if (4 * plane_stride > 0xFFFFFFFFull) return SSW_ERR_UNSUPPORTED;
-    SSW_TRY(grow(ctx->locate[4], 4 * plane_stride + 16));
-    SSW_TRY(grow(ctx->locate[3], nr * LOC_TOP * sizeof(uint64_t)));
-    SSW_TRY(grow(ctx->locate[2], ws_bytes + 16));
-    uint8_t* planes = (uint8_t*)ctx->locate[4].p;
-    uint64_t* keys = (uint64_t*)ctx->locate[3].p;
-    uint8_t* ws = (uint8_t*)ctx->locate[2].p;
+    SSW_TRY(grow(ctx->locate.box_planes, 4 * plane_stride + 16));
+    SSW_TRY(grow(ctx->locate.keys, nr * LOC_TOP * sizeof(uint64_t)));
+    SSW_TRY(grow(ctx->locate.group, ws_bytes + 16));
+    uint8_t* planes = ctx->locate.box_planes.as<uint8_t>();
+    uint64_t* keys = ctx->locate.keys.as<uint64_t>();
+    uint8_t* ws = ctx->locate.group.as<uint8_t>();
     const uint32_t* dev_taps = nullptr;
     SSW_TRY(upload_taps(ctx, taps, &dev_taps));
     {
@@ -867,8 +866,8 @@ int rung_boxes_impl(ssw_ctx* ctx, const void* dev_suspect, const ssw_placement& 
     std::vector<Rung> rungs(1);
     SSW_TRY(make_rung(taps, p, 0u, p.pw, p.ph, p.pw, p.ph, &rungs[0]));
     const Rung& r = rungs[0];
-    SSW_TRY(grow(ctx->locate[2], r.bytes_t + 16));
-    uint8_t* t_ptr[1] = {(uint8_t*)ctx->locate[2].p};
+    SSW_TRY(grow(ctx->locate.group, r.bytes_t + 16));
+    uint8_t* t_ptr[1] = {ctx->locate.group.as<uint8_t>()};
     const uint32_t* dev_taps = nullptr;
     SSW_TRY(upload_taps(ctx, taps, &dev_taps));
     SSW_TRY(enqueue_rungs(ctx, rungs, 0, 1, &dev_suspect, t_ptr, dev_taps));

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <map>
@@ -348,6 +349,72 @@ int launch_widen_indices(hipStream_t st, const uint32_t* in, size_t n, uint64_t*
 
 namespace ssw { namespace host { struct Transfer; } }
 
+// ---- workspace ---------------------------------------------------------------
+// Every device buffer a context keeps between calls is a Buf, and every Buf is a member of a group declared from a list
+// (SSW_BUF_GROUP): for_each_buf (below the context) visits the groups, so teardown and the pass-size account cannot miss one.
+namespace ssw {
+struct Buf {       // growable scratch (grow / release: ssw_host.hpp)
+    void* p = nullptr;
+    size_t bytes = 0;
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+namespace host {
+int grow(Buf& b, size_t bytes);
+template <class T> int grow_as(Buf& b, size_t bytes, T*& out) { SSW_TRY(grow(b, bytes)); out = b.as<T>(); return SSW_OK; }      // grown, and typed
+}
+
+#define SSW_BUF_MEMBER(name) Buf name;
+#define SSW_BUF_VISIT(name) f(#name, g.name);
+#define SSW_BUF_COUNT(name) +1
+#define SSW_BUF_GROUP(Group, LIST)                                                                      \
+    struct Group {                                                                                      \
+        LIST(SSW_BUF_MEMBER)                                                                            \
+        static constexpr size_t count = 0 LIST(SSW_BUF_COUNT);                                          \
+        template <class G, class F> static void each(G& g, F&& f) { LIST(SSW_BUF_VISIT) }               \
+    };                                                                                                  \
+    static_assert(sizeof(Group) == Group::count * sizeof(Buf), #Group ": nothing but the Bufs of its list")
+
+// The lane's f32 planes [chunk][H][W], and who puts what into them (the sharing is deliberate: DESIGN §3):
+//   slot        batch embed, fingerprint   batch extract, trace, base-prune bound, pruned handle    handles, ssw_dct2d (lane 0)
+//   y           Y / coefficients           base coefficients (trace: none, the context's plane)      --
+//   i_derived   I                          derived coefficients of an un-pruned chunk                --
+//   q_scratch   Q                          the transforms' scratch plane                             --
+//   scratch     the transforms' scratch    --                                                        the transform's scratch
+#define SSW_LANE_PLANES(X) X(y) X(i_derived) X(q_scratch) X(scratch)
+SSW_BUF_GROUP(LanePlanes, SSW_LANE_PLANES);
+// The lane's f64 operand slots; one pass at a time uses them, as the views of Lane say (the table is above them).
+#define SSW_LANE_OPERANDS(X) X(s_cop) X(odd_t2) X(ss_a1) X(sd) X(even) X(deep)
+SSW_BUF_GROUP(LaneOperands, SSW_LANE_OPERANDS);
+// pruned derived transform: the row pass's result, the column pass's [chunk][H][cap]
+#define SSW_LANE_COMPACT(X) X(rows) X(cols)
+SSW_BUF_GROUP(LaneCompact, SSW_LANE_COMPACT);
+// The prune tables of one index-list set: u32 = flag [W] | pos [W] | rows [cap] (+ 64); the gathered half bases of the
+// frequency classes in launch order and in the fused pass's fragment order.  A lane has one set per chunk (its two orders
+// share `gathered`: a chunk takes one row route, `gathered_frag` stays empty), a trace call one for every chunk (ssw_ctx::trace).
+#define SSW_PRUNE_BUFS(X) X(u32) X(gathered) X(gathered_frag)
+SSW_BUF_GROUP(PruneBufs, SSW_PRUNE_BUFS);
+// ssw_fingerprint_trace, what every chunk on both lanes reads: the base plane, its index list, the call's prune tables
+// (TraceBufs::prune), the similarity matrix when the caller wants none
+#define SSW_TRACE_BUFS(X) X(base_plane) X(base_idx) X(sims)
+SSW_BUF_GROUP(TraceBufs, SSW_TRACE_BUFS);
+// locate.hip: the original's luma plane | its 16 phase planes | one group's workspace (suspects R, luma, S_f, D; the ladder's
+// boxes; the refinement's resized cut-outs) | keys, sums, results | (scale ladder) the original's 8 x 8 box planes | its tap tables
+#define SSW_LOCATE_BUFS(X) X(luma) X(phases) X(group) X(keys) X(box_planes) X(taps)
+SSW_BUF_GROUP(LocateBufs, SSW_LOCATE_BUFS);
+// catalogue.hip: the blocks' top-8 lists of a match | host form: one group of frames | its signatures
+#define SSW_CATALOGUE_BUFS(X) X(top8) X(frames) X(sigs)
+SSW_BUF_GROUP(CatalogueBufs, SSW_CATALOGUE_BUFS);
+// fingerprint.hip: line plan (u32) | T64 + gathered basis | Yr64 | mark deltas | dT of a group | handle output
+#define SSW_FINGERPRINT_BUFS(X) X(line_plan) X(t64) X(yr64) X(deltas) X(dt) X(out)
+SSW_BUF_GROUP(FingerprintBufs, SSW_FINGERPRINT_BUFS);
+// The context's single buffers: [chunks] u32 flags of the pruned path (+ class counts) | the base reader's device counters
+// (BasePruneCounters) | misc (mark offsets, sims, ...) | full-order sort (lazy, Reader::indices beyond the top-k limit) | f32
+// intermediate of the resize's vertical pass | the original's pixels while a restoring trace runs | jpeg.hip: the decoded Y,
+// Cb and Cr planes of one group of jobs | filter.hip: the row-blurred planes of one group of jobs
+#define SSW_SHARED_BUFS(X) X(overflow) X(base_prune_stats) X(small) X(sort_scratch) X(resize_tmp) X(restore_base) X(jpeg) X(filter)
+SSW_BUF_GROUP(SharedBufs, SSW_SHARED_BUFS);
+}  // namespace ssw
+
 // ---- context ----------------------------------------------------------------
 struct ssw_ctx {
     int device = 0;
@@ -363,26 +430,88 @@ struct ssw_ctx {
     int fold_level = SSW_DCT_FOLDING_DEFAULT;           // 1 / 2: dense; 3: operand-ready GEMMs (dct_pair_*.hip, f64 only);
                                   // 4: two levels; 5: + a third on long forward row passes; 6: on all
 
-    // growable scratch
-    struct Buf {
-        void* p = nullptr;
-        size_t bytes = 0;
-    };
+    using Buf = ssw::Buf;
     // A lane = the workspace of one chunk in flight.  The batch entry points keep two chunks in flight
     // (ssw_ctx_set_overlap): while one lane's basis GEMMs run on the context's stream, the other lane's
     // HBM-bound stages (operand pre-passes, selection, colour conversion) run on `aux_stream`.
     struct Lane {
-        Buf plane[4];             // y / i / q / t planes of the chunk
-        Buf operand[6];           // operand planes of the operand-ready GEMMs: S|E, D|O, SS|EE, SD|EO, T, split odd (AS|BD|AD|BS)
+        ssw::LanePlanes plane;
+        ssw::LaneOperands operand;
         Buf idx;                  // [chunk][k] u32
         ssw::SelectWorkspace sel;
-        Buf compact[2];           // pruned derived transform: row-pass result, column-pass result [chunk][H][cap]
-        Buf gathered;             // gathered half bases of the chunk's frequency classes
-        Buf prune_u32;            // flag [W] | pos [W] | rows [cap] | info [8]
+        ssw::LaneCompact compact;
+        ssw::PruneBufs prune;     // of the chunk's index lists
         Buf base_prune;           // base-reader pruning: energy [chunk][W] f32 | need [chunk][W / 128] u32
         hipStream_t cur = nullptr;   // stream the lane's chain currently runs on
         hipEvent_t done = nullptr;   // recorded right after the lane's latest stage (borrowed from sync_events)
+
+        template <class T> static int grown(Buf& b, size_t bytes, T*& out) { return ssw::host::grow_as(b, bytes, out); }
+        // ---- the f32 planes by entry point (the table above LanePlanes); `bytes`: one plane of the chunk
+        struct WriterPlanes { float *y, *i, *q, *scratch; };
+        int writer_planes(size_t bytes, WriterPlanes& v) {
+            SSW_TRY(grown(plane.y, bytes, v.y)); SSW_TRY(grown(plane.i_derived, bytes, v.i)); SSW_TRY(grown(plane.q_scratch, bytes, v.q));
+            return grown(plane.scratch, bytes, v.scratch);
+        }
+        struct ReaderPlanes { float *y, *scratch; };
+        int reader_planes(size_t bytes, ReaderPlanes& v) { SSW_TRY(grown(plane.y, bytes, v.y)); return grown(plane.q_scratch, bytes, v.scratch); }
+        int reader_scratch(size_t bytes, float** t) { return grown(plane.q_scratch, bytes, *t); }
+        int derived_plane(size_t bytes, float** d) { return grown(plane.i_derived, bytes, *d); }
+        int handle_scratch(size_t bytes, float** t) { return grown(plane.scratch, bytes, *t); }
+
+        // ---- the operand slots by strategy (dct_plan.hpp): each view grows the slots its pass uses and hands them back
+        // by role.  `bytes`: one operand plane of the pass (dct_pair_operand_elems doubles).  A lane runs one pass at a
+        // time, so the roles of a slot never overlap -- but a chain is BUILT before it runs, and a slot that a later pass
+        // of the same chain grows is captured by the earlier one: grow() retires the old allocation instead of freeing it
+        // (ssw_pipeline.hip; found in r5 as a write into freed memory).
+        //   slot     one level   two levels   three levels   fused forward               semi-deep / deep inverse        pruned derived
+        //   s_cop    S | E       --           S-             16 column-operand planes    --                              o[0]: S-
+        //   odd_t2   D | O       D | O        x-             --                          T2 (quarter-length even half)   o[1]: x- | D
+        //   ss_a1    --          SS | EE      SSS            --                          A1 (level 2: eighth-length)     o[2]: SS | SSS
+        //   sd       --          SD | EO      SS-            --                          --                              o[3]: SD | SS-
+        //   even     --          inverse: E   --             --                          E, unrounded                    --
+        //   deep     the split odd half (AS BD AD BS) of any split pass; the numbered planes of the deep pre-passes (PairPlanes)
+        struct OneLevel { double *s, *d; };
+        int one_level(size_t bytes, OneLevel& v) { SSW_TRY(grown(operand.s_cop, bytes, v.s)); return grown(operand.odd_t2, bytes, v.d); }
+        struct TwoLevel { double *odd, *ss, *sd, *even; };      // even: grown for an inverse pass only (unrounded E)
+        int two_level(size_t bytes, bool inverse, TwoLevel& v) {
+            SSW_TRY(grown(operand.odd_t2, bytes, v.odd)); SSW_TRY(grown(operand.ss_a1, bytes, v.ss)); SSW_TRY(grown(operand.sd, bytes, v.sd));
+            v.even = operand.even.as<double>();
+            return inverse ? grown(operand.even, bytes, v.even) : SSW_OK;
+        }
+        struct ThreeLevel { double *s_minus, *odd, *r1, *r2; };
+        int three_level(size_t bytes, ThreeLevel& v) {
+            SSW_TRY(grown(operand.s_cop, bytes, v.s_minus)); SSW_TRY(grown(operand.odd_t2, bytes, v.odd));
+            SSW_TRY(grown(operand.ss_a1, bytes, v.r1)); return grown(operand.sd, bytes, v.r2);
+        }
+        // the fused forward transform's sixteen column-operand planes, `bytes` in all (the row launches write, the column launches read)
+        int column_operands(size_t bytes, double** cop) { return grown(operand.s_cop, bytes, *cop); }
+        int split_scratch(size_t bytes, double** sp) { return grown(operand.deep, bytes, *sp); }
+        // What the dependent launches of an inverse pass exchange, unrounded, `lines` lines of len / 4, len / 2 and (a1: the
+        // level-2 deep inverse) len / 8 doubles -- each at least a whole operand plane: the A1 slot is the two-level passes'
+        // SS | EE, and a row pass that exchanges A1 is followed, in the same chain, by a column pass that asks for the
+        // larger of the two; sized for both at once, the slot does not move between them.
+        struct Exchange { double *t2, *even, *a1; };
+        int inverse_exchange(size_t bytes, size_t lines, size_t len, bool a1, Exchange& v) {
+            const size_t line = lines * sizeof(double);
+            SSW_TRY(grown(operand.odd_t2, std::max(bytes, line * (len / 4)), v.t2)); SSW_TRY(grown(operand.even, std::max(bytes, line * (len / 2)), v.even));
+            v.a1 = nullptr;
+            return a1 ? grown(operand.ss_a1, std::max(bytes, line * (len / 8)), v.a1) : SSW_OK;
+        }
+        // The pruned derived transform of a chunk: o[PruneClassSrc::lane_buf], the four planes the two- / three-level row
+        // pre-passes fill (operand_bytes 0, a deep row pass: none grown -- it writes the numbered planes of `sp` only), both
+        // compact planes and the split scratch (split_bytes 0: not split, null).
+        struct Pruned { double* o[4]; double* sp; float *rows, *cols; };
+        int pruned_derived(size_t operand_bytes, size_t compact_bytes, size_t split_bytes, Pruned& v) {
+            Buf* const slot[4] = {&operand.s_cop, &operand.odd_t2, &operand.ss_a1, &operand.sd};
+            for (int i = 0; i < 4; ++i) SSW_TRY(operand_bytes ? grown(*slot[i], operand_bytes, v.o[i]) : (v.o[i] = slot[i]->as<double>(), SSW_OK));
+            SSW_TRY(grown(compact.rows, compact_bytes, v.rows)); SSW_TRY(grown(compact.cols, compact_bytes, v.cols));
+            v.sp = nullptr;
+            return split_bytes ? split_scratch(split_bytes, &v.sp) : SSW_OK;
+        }
     };
+    // (for_each_buf lists a lane's groups and its two single Bufs: a Buf added here must be added there)
+    static_assert(sizeof(Lane) == sizeof(ssw::LanePlanes) + sizeof(ssw::LaneOperands) + sizeof(ssw::LaneCompact) + sizeof(ssw::PruneBufs) +
+                                  2 * sizeof(Buf) + sizeof(ssw::SelectWorkspace) + sizeof(hipStream_t) + sizeof(hipEvent_t), "the lane's Bufs");
     static constexpr int MAX_LANES = 2;
     Lane lane[MAX_LANES];
     hipStream_t aux_stream = nullptr;     // HBM-bound stages of the batch pipelines
@@ -391,12 +520,9 @@ struct ssw_ctx {
     bool split = true;                    // f64 GEMMs: odd halves as rotated quarter-length cosine + sine pairs
     std::vector<hipEvent_t> sync_events;  // cross-stream dependencies (ring)
     size_t sync_next = 0;
-    Buf overflow;                         // [chunks] u32 flags of the pruned path (+ class counts)
     uint64_t pruned_chunks = 0, redone_chunks = 0;
     uint64_t pruned_columns = 0;          // sum over pruned chunks of the compact plane width (cap_total)
-    // base-reader pruning: device counters (u64: tiles total, tiles computed, frames extended, spare; then doubles: flop and
-    // bytes of the second phase's column launches, bytes of the zero-fill) and what flush_timers has already billed of the doubles
-    Buf base_prune_stats;
+    // base-reader pruning: what flush_timers has already billed of the device counters' doubles (shared.base_prune_stats)
     double base_prune_billed[5] = {0.0, 0.0, 0.0, 0.0, 0.0};     // column flop, bytes, selection bytes | tail row flop, bytes
     // single-image handles (ssw_lib.hip): frames cross PCIe on `copy_stream` into / out of two alternating
     // device staging buffers, so the upload of the next frame runs beside the kernels of the previous one
@@ -437,19 +563,12 @@ struct ssw_ctx {
         bool active = false;              // a streaming call is running: the ring must stay (dev_malloc's give-back skips it)
     };
     HostStream hs;
-    Buf small;                    // misc (mark offsets, sims, ...)
-    Buf sort_scratch;             // full-order sort (lazy, Reader::indices beyond the top-k limit)
-    Buf resize_tmp;               // f32 intermediate of the resize's vertical pass
-    Buf restore_base;             // the original's pixels while a restoring trace runs (ssw_*_trace_restored_host_rgb8)
-    // ssw_fingerprint_trace: what every chunk on both lanes reads -- base plane | base index list | prune tables (flag, pos,
-    // rows) | gathered bases, launch order | gathered bases, fragment order | similarity matrix when the caller wants none
-    Buf trace[6];
-    Buf locate[6];                // locate.hip: the original's luma plane | its 16 phase planes | one group of suspects (R, luma, S_f, D) | keys, sums, results
-                                  // | (scale ladder) the original's 8 x 8 box planes | the ladder's tap tables
-    Buf catalogue[3];             // catalogue.hip: the blocks' top-8 lists of a match | host form: one group of frames | its signatures
-    Buf jpeg;                     // jpeg.hip: the decoded Y, Cb and Cr planes of one group of jobs
-    Buf filter;                   // filter.hip: the row-blurred planes of one group of jobs
-    Buf fingerprint[6];           // fingerprint.hip: line plan (u32) | T64 + gathered basis | Yr64 | mark deltas | dT of a group | handle output
+    // the per-feature buffers and the context's single ones (the groups above the context)
+    struct Trace : ssw::TraceBufs { ssw::PruneBufs prune; } trace;      // prune: the call's tables, what a lane's are to a chunk
+    ssw::LocateBufs locate;
+    ssw::CatalogueBufs catalogue;
+    ssw::FingerprintBufs fingerprint;
+    ssw::SharedBufs shared;
     std::map<std::pair<size_t, size_t>, ssw::DeviceTaps> taps;   // (in_len, out_len) -> filter taps
 
     // timing
@@ -469,4 +588,44 @@ struct ssw_ctx {
     hipStream_t tail_stream = nullptr;
     bool tail_fresh = false;
 };
+
+namespace ssw {
+// Every workspace Buf of a context, once: f(lane or ring slot (-1: neither), group, name, buf, counted).  `counted`: the buffer is
+// part of what lane_bytes_held adds to the device's free memory for the automatic pass size -- the lanes' planes, operand
+// slots, compact planes, index lists and prune tables (gathered bases included), the 44 B/px that a pass is budgeted at.
+// Deliberately NOT counted: the lanes' base_prune buffers and selection workspaces (O(chunk * (W + k)), no part of the
+// per-pixel budget) and everything the context owns outside the lanes -- counting them would change pass sizes under memory
+// pressure.  The selection workspaces are not Bufs (three arrays sized together, select.hip): sel(lane, workspace) gets them.
+template <class Ctx, class F, class S> void for_each_workspace(Ctx& c, F&& f, S&& sel) {
+    for (int l = 0; l < ssw_ctx::MAX_LANES; ++l) {
+        auto& ln = c.lane[l];
+        sel(l, ln.sel);
+        auto counted = [&](const char* group) { return [&f, l, group](const char* name, auto& b) { f(l, group, name, b, true); }; };
+        LanePlanes::each(ln.plane, counted("plane"));
+        LaneOperands::each(ln.operand, counted("operand"));
+        LaneCompact::each(ln.compact, counted("compact"));
+        PruneBufs::each(ln.prune, counted("prune"));
+        f(l, "lane", "idx", ln.idx, true);
+        f(l, "lane", "base_prune", ln.base_prune, false);
+    }
+    auto own = [&](const char* group) { return [&f, group](const char* name, auto& b) { f(-1, group, name, b, false); }; };
+    TraceBufs::each(c.trace, own("trace"));
+    PruneBufs::each(c.trace.prune, own("trace.prune"));
+    LocateBufs::each(c.locate, own("locate"));
+    CatalogueBufs::each(c.catalogue, own("catalogue"));
+    FingerprintBufs::each(c.fingerprint, own("fingerprint"));
+    SharedBufs::each(c.shared, own("shared"));
+    for (int s = 0; s < ssw_ctx::HostStream::NB; ++s) { f(s, "hs", "in", c.hs.in[s], false); f(s, "hs", "in2", c.hs.in2[s], false); f(s, "hs", "out", c.hs.out[s], false); }
+    f(-1, "hs", "marks", c.hs.marks, false); f(-1, "hs", "ext", c.hs.ext, false); f(-1, "hs", "sims", c.hs.sims, false);
+    int stage = 0;
+    for (auto& fs : c.frame_stage) f(stage++, "frame_stage", "buf", fs.buf, false);
+}
+template <class Ctx, class F> void for_each_buf(Ctx& c, F&& f) { for_each_workspace(c, f, [](int, const SelectWorkspace&) {}); }
+// what the lanes hold of the pass budget (effective_chunk, ssw_pipeline.hip)
+inline size_t lane_bytes_held(const ssw_ctx* ctx) {
+    size_t held = 0;
+    for_each_buf(*ctx, [&](int, const char*, const char*, const Buf& b, bool counted) { if (counted) held += b.bytes; });
+    return held;
+}
+}  // namespace ssw
 namespace ssw { inline PlanSettings plan_settings(const ssw_ctx* ctx) { return PlanSettings{ctx->fold, ctx->fold_level, ctx->split}; } }

@@ -148,8 +148,8 @@ int forward_from_host(ssw_ctx* ctx, const void* host_rgb, PixFmt fmt, size_t w, 
                       float* q) {
     const size_t plane = w * h;
     const size_t bytes = plane * 3 * pix_bytes(fmt);
-    SSW_TRY(grow(ctx->lane[0].plane[3], plane * sizeof(float)));
-    float* tmp = (float*)ctx->lane[0].plane[3].p;
+    float* tmp = nullptr;
+    SSW_TRY(ctx->lane[0].handle_scratch(plane * sizeof(float), &tmp));
     {
         // Bands of image rows (two to four, `upload_bands`): the row pass of a band runs while the next ones are still
         // crossing PCIe (image rows are independent lines of a row pass: same values), then the column pass of the whole
@@ -172,14 +172,14 @@ int forward_from_host(ssw_ctx* ctx, const void* host_rgb, PixFmt fmt, size_t w, 
             int rc = SSW_OK;
             for (int band = 0; band < (int)nb && rc == SSW_OK; ++band) {
                 bool async = false;
-                rc = upload_nowait(ctx, (char*)fs.buf.p + band * hb, (const char*)host_rgb + band * hb, hb, ctx->copy_stream, &async);
+                rc = upload_nowait(ctx, fs.buf.as<char>() + band * hb, (const char*)host_rgb + band * hb, hb, ctx->copy_stream, &async);
                 in_flight = in_flight || async;
                 if (rc == SSW_OK && hipEventRecord(fs.uploaded[band], ctx->copy_stream) != hipSuccess) rc = SSW_ERR_HIP;
                 if (rc == SSW_OK && hipStreamWaitEvent(ctx->stream, fs.uploaded[band], 0) != hipSuccess) rc = SSW_ERR_HIP;
                 untimed_work(ctx);                  // the band's first stage starts its timer behind the wait for its upload
                 if (rc != SSW_OK) break;
                 Chain ch;
-                rc = build_forward_rows_band(ctx, ctx->lane[0], precision, (char*)fs.buf.p + band * hb, fmt, w, rows, h, tmp + band * hp,
+                rc = build_forward_rows_band(ctx, ctx->lane[0], precision, fs.buf.as<char>() + band * hb, fmt, w, rows, h, tmp + band * hp,
                                              i ? i + band * hp : nullptr, q ? q + band * hp : nullptr, ch);
                 if (rc == SSW_OK) rc = run_serial(ch, ctx->stream);
             }
@@ -204,11 +204,11 @@ int forward_from_host(ssw_ctx* ctx, const void* host_rgb, PixFmt fmt, size_t w, 
 // ssw_similarity_matrix as it is enqueued (also the matrix of ssw_fingerprint_trace: the same three launches, the same bits)
 int similarity_matrix_enqueue(ssw_ctx* ctx, const float* dev_extracted, size_t n_extracted, const float* dev_marks, size_t n_marks,
                               size_t k, float* dev_sims) {
-    SSW_TRY(grow(ctx->small, n_extracted * sizeof(float)));
+    SSW_TRY(grow(ctx->shared.small, n_extracted * sizeof(float)));
     StageTimer t(ctx, SSW_STAGE_SIMILARITY, ctx->stream);
-    SSW_TRY(launch_sim_den(ctx->stream, dev_extracted, n_extracted, k, (float*)ctx->small.p));
+    SSW_TRY(launch_sim_den(ctx->stream, dev_extracted, n_extracted, k, ctx->shared.small.as<float>()));
     SSW_TRY(launch_gemm_nt_f32(ctx->stream, dev_extracted, n_extracted, dev_marks, n_marks, k, dev_sims));
-    return launch_sim_scale(ctx->stream, dev_sims, (const float*)ctx->small.p, n_extracted, n_marks);
+    return launch_sim_scale(ctx->stream, dev_sims, ctx->shared.small.as<const float>(), n_extracted, n_marks);
 }
 }  // namespace
 
@@ -232,8 +232,8 @@ int trace_score(ssw_ctx* ctx, const float* dev_extracted, size_t n_suspects, con
     if (n_suspects == 0 || (!dev_sims && !dev_best && !dev_best_sim && !dev_n_exceed)) return SSW_OK;
     float* sims = dev_sims;
     if (!sims && n_marks) {
-        SSW_TRY(grow(ctx->trace[5], n_suspects * n_marks * sizeof(float)));
-        sims = (float*)ctx->trace[5].p;
+        SSW_TRY(grow(ctx->trace.sims, n_suspects * n_marks * sizeof(float)));
+        sims = ctx->trace.sims.as<float>();
     }
     if (n_marks && k) SSW_TRY(similarity_matrix_enqueue(ctx, dev_extracted, n_suspects, dev_marks, n_marks, k, sims));
     else if (n_marks) { SSW_HIP_CHECK(hipMemsetAsync(sims, 0xFF, n_suspects * n_marks * sizeof(float), ctx->stream)); untimed_work(ctx); }   // NaN
@@ -315,32 +315,31 @@ int ssw_ctx_create(int device_id, ssw_ctx** out) {
     ssw_ctx* ctx = new (std::nothrow) ssw_ctx();
     if (!ctx) return SSW_ERR_OUT_OF_MEMORY;
     ctx->device = device_id;
-    hipError_t e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete ctx; set_last_error(hipGetErrorString(e)); return SSW_ERR_HIP; }
-    ctx->stream = ctx->own_stream;
-    // second stream of the batch pipelines (ssw_pipeline.hip): the HBM-bound stages of one chunk run here
+    // One exit for every failure: ssw_ctx_destroy releases whatever exists by then (null streams and a null counter included).
+    // aux_stream: second stream of the batch pipelines (ssw_pipeline.hip): the HBM-bound stages of one chunk run here
     // while the basis GEMMs of the other chunk in flight run on the context's stream.
     // (Measured: restricting this stream to 16 .. 128 CUs with a CU mask only slows the step down -- the
     // chunk's GEMMs wait for its pre-pass -- so it is a plain stream.  Measured again at level 2, where the pre-passes
     // are a third of a step, also with the complement mask on the GEMM stream: 64 CUs 8.8 / 9.8, 96 + complement 10.0,
     // 128 CUs 12.1 Gpix/s against 13.9.)
     // Stream priorities (either way round) change nothing either.
-    e = hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { (void)hipStreamDestroy(ctx->own_stream); delete ctx; set_last_error(hipGetErrorString(e)); return SSW_ERR_HIP; }
-    // frames of the single-image handles cross PCIe here, beside the kernels of the previous handle
-    e = hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        (void)hipStreamDestroy(ctx->aux_stream); (void)hipStreamDestroy(ctx->own_stream);
-        delete ctx; set_last_error(hipGetErrorString(e)); return SSW_ERR_HIP;
+    // copy_stream: frames of the single-image handles cross PCIe here, beside the kernels of the previous handle
+    for (hipStream_t* st : {&ctx->own_stream, &ctx->aux_stream, &ctx->copy_stream}) {
+        const hipError_t e = hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+        if (e == hipSuccess) continue;
+        set_last_error(hipGetErrorString(e));
+        (void)ssw_ctx_destroy(ctx);
+        return SSW_ERR_HIP;
     }
+    ctx->stream = ctx->own_stream;
     // the selection's fallback counter lives as long as the context (allocated here, not lazily inside a batch call:
     // a first call under stream capture must not allocate)
     if (hipMalloc((void**)&ctx->select_fallbacks, sizeof(uint32_t)) != hipSuccess ||
         hipMemset(ctx->select_fallbacks, 0, sizeof(uint32_t)) != hipSuccess) {
         (void)hipGetLastError();
-        if (ctx->select_fallbacks) (void)hipFree(ctx->select_fallbacks);
-        (void)hipStreamDestroy(ctx->copy_stream); (void)hipStreamDestroy(ctx->aux_stream); (void)hipStreamDestroy(ctx->own_stream);
-        delete ctx; set_last_error("hipMalloc: selection counter"); return SSW_ERR_OUT_OF_MEMORY;
+        (void)ssw_ctx_destroy(ctx);
+        set_last_error("hipMalloc: selection counter");
+        return SSW_ERR_OUT_OF_MEMORY;
     }
     const char* ov = std::getenv("SSW_OVERLAP");
     if (ov) ctx->overlap = std::atoi(ov) != 0;
@@ -352,61 +351,33 @@ int ssw_ctx_create(int device_id, ssw_ctx** out) {
     return SSW_OK;
 }
 
+// Also the failure path of ssw_ctx_create: every stream and the selection counter may still be null.
 int ssw_ctx_destroy(ssw_ctx* ctx) {
     if (!ctx) return SSW_OK;
     CtxGuard g(ctx);
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
-    if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-    if (ctx->down_stream) (void)hipStreamSynchronize(ctx->down_stream);
+    for (hipStream_t st : {ctx->stream, ctx->aux_stream, ctx->copy_stream, ctx->down_stream})
+        if (st) (void)hipStreamSynchronize(st);
     transfer_destroy(ctx);
-    for (int s = 0; s < ssw_ctx::HostStream::NB; ++s) {
-        release(ctx->hs.in[s]); release(ctx->hs.in2[s]); release(ctx->hs.out[s]);
+    for_each_workspace(*ctx, [](int, const char*, const char*, ssw_ctx::Buf& b, bool) { release(b); }, [](int, SelectWorkspace& s) { release_select(s); });
+    for (int s = 0; s < ssw_ctx::HostStream::NB; ++s)
         for (hipEvent_t e : {ctx->hs.up_done[s], ctx->hs.k_done[s], ctx->hs.down_done[s]}) if (e) (void)hipEventDestroy(e);
-    }
-    release(ctx->hs.marks); release(ctx->hs.ext); release(ctx->hs.sims);
     for (void* p : ctx->retired) (void)hipFree(p);
     ctx->retired.clear();
     (void)plane_pool_flush(ctx);
     for (auto& fs : ctx->frame_stage) {
-        release(fs.buf);
         for (hipEvent_t e : fs.uploaded)
             if (e) (void)hipEventDestroy(e);
         if (fs.consumed) (void)hipEventDestroy(fs.consumed);
     }
     for (auto& kv : ctx->basis) (void)hipFree(kv.second);
     for (auto& kv : ctx->split16) (void)hipFree(kv.second);
-    for (auto& ln : ctx->lane) {
-        for (auto& b : ln.plane) release(b);
-        for (auto& b : ln.operand) release(b);
-        for (auto& b : ln.compact) release(b);
-        release(ln.idx);
-        release(ln.gathered);
-        release(ln.prune_u32);
-        release(ln.base_prune);
-        release_select(ln.sel);
-    }
     if (ctx->select_fallbacks) (void)hipFree(ctx->select_fallbacks);
-    release(ctx->overflow);
-    release(ctx->base_prune_stats);
-    release(ctx->small);
-    release(ctx->sort_scratch);
-    release(ctx->resize_tmp);
-    release(ctx->restore_base);
-    for (auto& b : ctx->fingerprint) release(b);
-    for (auto& b : ctx->trace) release(b);
-    for (auto& b : ctx->locate) release(b);
-    for (auto& b : ctx->catalogue) release(b);
-    release(ctx->jpeg);
-    release(ctx->filter);
     for (auto& kv : ctx->taps) { (void)hipFree(kv.second.left); (void)hipFree(kv.second.count); (void)hipFree(kv.second.weights); }
     for (auto& e : ctx->sync_events) (void)hipEventDestroy(e);
     for (auto& p : ctx->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& e : ctx->free_events) (void)hipEventDestroy(e);
-    if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
-    if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-    if (ctx->down_stream) (void)hipStreamDestroy(ctx->down_stream);
-    (void)hipStreamDestroy(ctx->own_stream);
+    for (hipStream_t st : {ctx->aux_stream, ctx->copy_stream, ctx->down_stream, ctx->own_stream})
+        if (st) (void)hipStreamDestroy(st);
     delete ctx;
     return SSW_OK;
 }
@@ -481,7 +452,7 @@ int ssw_ctx_reset_timing(ssw_ctx* ctx) {
     SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) SSW_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
     SSW_HIP_CHECK(hipMemset(ctx->select_fallbacks, 0, sizeof(uint32_t)));
-    if (ctx->base_prune_stats.p) SSW_HIP_CHECK(hipMemset(ctx->base_prune_stats.p, 0, sizeof(BasePruneCounters)));
+    if (ctx->shared.base_prune_stats.p) SSW_HIP_CHECK(hipMemset(ctx->shared.base_prune_stats.p, 0, sizeof(BasePruneCounters)));
     for (double& b : ctx->base_prune_billed) b = 0.0;
     return SSW_OK;
 }
@@ -543,11 +514,11 @@ int ssw_ctx_get_base_prune_stats(ssw_ctx* ctx, uint64_t* stats) {
     if (!ctx || !stats) return SSW_ERR_BAD_ARG;
     CtxGuard g(ctx);
     stats[0] = stats[1] = stats[2] = 0;
-    if (!ctx->base_prune_stats.p) return SSW_OK;
+    if (!ctx->shared.base_prune_stats.p) return SSW_OK;
     SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) SSW_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
     BasePruneCounters c;
-    SSW_HIP_CHECK(hipMemcpy(&c, ctx->base_prune_stats.p, sizeof(c), hipMemcpyDeviceToHost));
+    SSW_HIP_CHECK(hipMemcpy(&c, ctx->shared.base_prune_stats.p, sizeof(c), hipMemcpyDeviceToHost));
     stats[0] = c.tiles; stats[1] = c.tiles_computed; stats[2] = c.frames_extended;
     return SSW_OK;
 }
@@ -556,11 +527,11 @@ int ssw_ctx_get_base_prune_tail_jobs(ssw_ctx* ctx, uint64_t* jobs) {
     if (!ctx || !jobs) return SSW_ERR_BAD_ARG;
     CtxGuard g(ctx);
     *jobs = 0;
-    if (!ctx->base_prune_stats.p) return SSW_OK;
+    if (!ctx->shared.base_prune_stats.p) return SSW_OK;
     SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) SSW_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
     BasePruneCounters c;
-    SSW_HIP_CHECK(hipMemcpy(&c, ctx->base_prune_stats.p, sizeof(c), hipMemcpyDeviceToHost));
+    SSW_HIP_CHECK(hipMemcpy(&c, ctx->shared.base_prune_stats.p, sizeof(c), hipMemcpyDeviceToHost));
     *jobs = c.tail_jobs;
     return SSW_OK;
 }
@@ -690,10 +661,11 @@ int ssw_dct2d(ssw_ctx* ctx, int dct_type, int precision, size_t n_frames, size_t
     if (w == 0 || h == 0) return SSW_ERR_BAD_DIMS;
     CtxGuard g(ctx);
     const size_t chunk = effective_chunk(ctx, w, h, n_frames);
-    SSW_TRY(grow(ctx->lane[0].plane[3], chunk * w * h * sizeof(float)));
+    float* tmp = nullptr;
+    SSW_TRY(ctx->lane[0].handle_scratch(chunk * w * h * sizeof(float), &tmp));
     for (size_t f0 = 0; f0 < n_frames; f0 += chunk) {
         const size_t n = std::min(chunk, n_frames - f0);
-        SSW_TRY(dct2d_planes(ctx, dct_type, precision, n, w, h, dev_planes + f0 * w * h, (float*)ctx->lane[0].plane[3].p));
+        SSW_TRY(dct2d_planes(ctx, dct_type, precision, n, w, h, dev_planes + f0 * w * h, tmp));
     }
     return SSW_OK;
 }
@@ -869,13 +841,13 @@ int ssw_fingerprint_trace_restored_host_rgb8(ssw_ctx* ctx, const ssw_config* cfg
     SSW_TRY(restore_normalise(placements, n_suspects, w, h, &pl));
     CtxGuard g(ctx);
     SSW_TRY(restore_prepare(ctx, pl));
-    SSW_TRY(grow(ctx->restore_base, w * h * 3));
-    SSW_TRY(upload(ctx, ctx->restore_base.p, host_base, w * h * 3, ctx->stream));
+    SSW_TRY(grow(ctx->shared.restore_base, w * h * 3));
+    SSW_TRY(upload(ctx, ctx->shared.restore_base.p, host_base, w * h * 3, ctx->stream));
     const float* yb = nullptr;
     const uint32_t* idx = nullptr;
-    SSW_TRY(trace_base(ctx, *cfg, ctx->restore_base.p, PixFmt::U8, w, h, k, &yb, &idx));
+    SSW_TRY(trace_base(ctx, *cfg, ctx->shared.restore_base.p, PixFmt::U8, w, h, k, &yb, &idx));
     return stream_trace_rgb8(ctx, *cfg, yb, idx, host_suspects, n_suspects, w, h, k, host_marks, n_marks, threshold, host_extracted,
-                             host_sims, host_best, host_best_sim, host_n_exceed, pl.data(), (const uint8_t*)ctx->restore_base.p);
+                             host_sims, host_best, host_best_sim, host_n_exceed, pl.data(), ctx->shared.restore_base.as<const uint8_t>());
 }
 
 // ---- 16-bit boundary (`into_rgb32f()` of an Rgb16 image, v / 65535, fused into the first operand
@@ -935,12 +907,12 @@ int ssw_resize_rgb8(ssw_ctx* ctx, const uint8_t* dev_in, size_t n_frames, size_t
     SSW_TRY(get_taps(ctx, w, nw, &ht));
     const size_t chunk = effective_chunk(ctx, w, h, n_frames);
     const size_t tmp_bytes = resize_tmp_bytes(dev_in, std::min(chunk, n_frames), w, h, nw, nh, vt, ht, dev_out);
-    if (tmp_bytes) SSW_TRY(grow(ctx->resize_tmp, tmp_bytes));       // two-pass fallback only (unaligned rows)
+    if (tmp_bytes) SSW_TRY(grow(ctx->shared.resize_tmp, tmp_bytes));       // two-pass fallback only (unaligned rows)
     for (size_t f0 = 0; f0 < n_frames; f0 += chunk) {
         const size_t n = std::min(chunk, n_frames - f0);
         StageTimer t(ctx, SSW_STAGE_RESIZE, ctx->stream, (double)n * 3.0 * ((double)w * h + (double)nw * nh));
         SSW_TRY(launch_resize_rgb8(ctx->stream, dev_in + f0 * w * h * 3, n, w, h, nw, nh, vt, ht,
-                                   (float*)ctx->resize_tmp.p, dev_out + f0 * nw * nh * 3));
+                                   ctx->shared.resize_tmp.as<float>(), dev_out + f0 * nw * nh * 3));
     }
     return SSW_OK;
 }
@@ -1019,8 +991,8 @@ static int writer_embed_impl(ssw_writer* wr, const float* const* marks, const si
         if (len) std::memcpy(wr->blob.data() + at, marks[m], len * sizeof(float));
         at += len;
     }
-    SSW_TRY(grow(ctx->small, bytes_marks + 2 * bytes_tab));
-    char* base = (char*)ctx->small.p;
+    SSW_TRY(grow(ctx->shared.small, bytes_marks + 2 * bytes_tab));
+    char* base = ctx->shared.small.as<char>();
     // the host vector belongs to the handle and stays until it is destroyed: no host synchronisation here
     SSW_HIP_CHECK(hipMemcpyAsync(base, wr->blob.data(), bytes_marks + 2 * bytes_tab, hipMemcpyHostToDevice, ctx->stream));
     wr->staging_in_flight = true;
@@ -1057,11 +1029,12 @@ static int writer_result_impl(ssw_writer* wr, void* out_rgb_hwc, bool u8_out) {
     CtxGuard g(ctx);
     const size_t plane = wr->w * wr->h;
     const size_t out_bytes = plane * 3 * (u8_out ? 1 : sizeof(float));
-    SSW_TRY(grow(ctx->lane[0].plane[3], plane * sizeof(float)));
+    float* tmp = nullptr;
+    SSW_TRY(ctx->lane[0].handle_scratch(plane * sizeof(float), &tmp));
     ssw_ctx::FrameStage& fs = ctx->frame_stage[ctx->frame_stage_next++ & 1];
     SSW_TRY(frame_stage_events(fs));
     SSW_TRY(grow(fs.buf, out_bytes));
-    Xform inv{SSW_DCT3, wr->cfg.precision, 1, wr->w, wr->h, wr->y, (float*)ctx->lane[0].plane[3].p};      // :368-374
+    Xform inv{SSW_DCT3, wr->cfg.precision, 1, wr->w, wr->h, wr->y, tmp};      // :368-374
     inv.iq_i = wr->i; inv.iq_q = wr->q; inv.rgb_out = fs.buf.p; inv.rgb_out_u8 = u8_out;                 // + :377
     bool fused_rgb = false;
     Chain ch;
@@ -1069,8 +1042,8 @@ static int writer_result_impl(ssw_writer* wr, void* out_rgb_hwc, bool u8_out) {
     SSW_TRY(run_serial(ch, ctx->stream));
     if (!fused_rgb) {
         StageTimer t(ctx, SSW_STAGE_YIQ_TO_RGB, ctx->stream);
-        if (u8_out) SSW_TRY(launch_yiq_to_rgb8(ctx->stream, wr->y, wr->i, wr->q, plane, (uint8_t*)fs.buf.p));
-        else        SSW_TRY(launch_yiq_to_rgb(ctx->stream, wr->y, wr->i, wr->q, plane, (float*)fs.buf.p));   // :377
+        if (u8_out) SSW_TRY(launch_yiq_to_rgb8(ctx->stream, wr->y, wr->i, wr->q, plane, fs.buf.as<uint8_t>()));
+        else        SSW_TRY(launch_yiq_to_rgb(ctx->stream, wr->y, wr->i, wr->q, plane, fs.buf.as<float>()));   // :377
     }
     const int rc = download(ctx, out_rgb_hwc, fs.buf.p, out_bytes, ctx->stream);
     SSW_TRY(stage_consumed(ctx, fs));
@@ -1120,17 +1093,18 @@ static int writer_mark_copies_impl(ssw_writer* wr, const float* host_marks, size
         wr->idx_k = k_eff;
     }
     const size_t mark_bytes = n_copies * std::max<size_t>(k, 1) * sizeof(float);
-    SSW_TRY(grow(ctx->small, mark_bytes));
-    if (k) SSW_TRY(upload(ctx, ctx->small.p, host_marks, n_copies * k * sizeof(float), ctx->stream));
+    SSW_TRY(grow(ctx->shared.small, mark_bytes));
+    if (k) SSW_TRY(upload(ctx, ctx->shared.small.p, host_marks, n_copies * k * sizeof(float), ctx->stream));
     const size_t out_bytes = plane * 3 * (u8_out ? 1 : sizeof(float));
     const size_t group = std::max<size_t>(1, std::min<size_t>(n_copies, ((size_t)1 << 30) / out_bytes));
-    SSW_TRY(grow(ctx->fingerprint[5], group * out_bytes));
-    SSW_TRY(grow(ctx->lane[0].plane[3], plane * sizeof(float)));
+    SSW_TRY(grow(ctx->fingerprint.out, group * out_bytes));
+    float* tmp = nullptr;
+    SSW_TRY(ctx->lane[0].handle_scratch(plane * sizeof(float), &tmp));
     for (size_t n0 = 0; n0 < n_copies; n0 += group) {
         const size_t gn = std::min(group, n_copies - n0);
-        SSW_TRY(fingerprint_copies(ctx, wr->cfg, wr->y, wr->idx, k_eff, wr->i, wr->q, wr->w, wr->h, (const float*)ctx->small.p + n0 * k,
-                                   k, gn, ctx->fingerprint[5].p, u8_out, (float*)ctx->lane[0].plane[3].p));
-        SSW_TRY(download(ctx, static_cast<char*>(host_out) + n0 * out_bytes, ctx->fingerprint[5].p, gn * out_bytes, ctx->stream));
+        SSW_TRY(fingerprint_copies(ctx, wr->cfg, wr->y, wr->idx, k_eff, wr->i, wr->q, wr->w, wr->h, ctx->shared.small.as<const float>() + n0 * k,
+                                   k, gn, ctx->fingerprint.out.p, u8_out, tmp));
+        SSW_TRY(download(ctx, static_cast<char*>(host_out) + n0 * out_bytes, ctx->fingerprint.out.p, gn * out_bytes, ctx->stream));
     }
     return SSW_OK;
 }
@@ -1216,10 +1190,11 @@ static int reader_ensure_coefficients(ssw_reader* rd) {
     float* y = nullptr;
     SSW_TRY(pool_get(ctx, plane * 4, (void**)&y));
     auto run = [&]() -> int {
-        SSW_TRY(grow(ctx->lane[0].plane[3], plane * sizeof(float)));
+        float* tmp = nullptr;
+        SSW_TRY(ctx->lane[0].handle_scratch(plane * sizeof(float), &tmp));
         Chain ch;
         SSW_TRY(build_forward_from_rgb(ctx, ctx->lane[0], rd->cfg.precision, rd->rgb, rd->rgb_fmt, 1, rd->w, rd->h, y,
-                                       nullptr, nullptr, (float*)ctx->lane[0].plane[3].p, ch));
+                                       nullptr, nullptr, tmp, ch));
         return run_serial(ch, ctx->stream);
     };
     const int rc = run();
@@ -1276,9 +1251,9 @@ int ssw_reader_indices(ssw_reader* rd, size_t k, uint64_t* out) {
     SSW_TRY(reader_ensure_indices(rd, k));
     ssw_ctx* ctx = rd->ctx;
     ctx->expected_k = k;
-    SSW_TRY(grow(ctx->small, k * sizeof(uint64_t)));
-    SSW_TRY(launch_widen_indices(ctx->stream, rd->idx, k, (uint64_t*)ctx->small.p));
-    return ssw_copy_to_host(ctx, out, ctx->small.p, k * sizeof(uint64_t));
+    SSW_TRY(grow(ctx->shared.small, k * sizeof(uint64_t)));
+    SSW_TRY(launch_widen_indices(ctx->stream, rd->idx, k, ctx->shared.small.as<uint64_t>()));
+    return ssw_copy_to_host(ctx, out, ctx->shared.small.p, k * sizeof(uint64_t));
 }
 
 int ssw_reader_extract(ssw_reader* base, ssw_reader* derived, float* out, size_t k) {
@@ -1293,17 +1268,17 @@ int ssw_reader_extract(ssw_reader* base, ssw_reader* derived, float* out, size_t
     CtxGuard g(ctx);
     SSW_TRY(reader_ensure_indices(base, k));
     ctx->expected_k = k;
-    SSW_TRY(grow(ctx->small, k * sizeof(float)));
+    SSW_TRY(grow(ctx->shared.small, k * sizeof(float)));
     if (!derived->y && derived->w == base->w && derived->h == base->h) {
         // the derived frame is still RGB: transform it only where the first k indices of the base reader read it
         bool pruned = false;
         uint32_t* info = nullptr;
         SSW_TRY(extract_single_pruned(ctx, derived->cfg.precision, derived->rgb, derived->rgb_fmt, base->w, base->h, base->y,
-                                      base->idx, k, base->cfg.method, base->cfg.alpha, (float*)ctx->small.p, &info, &pruned));
+                                      base->idx, k, base->cfg.method, base->cfg.alpha, ctx->shared.small.as<float>(), &info, &pruned));
         if (pruned) {
             uint32_t overflow = 1;
             SSW_HIP_CHECK(hipMemcpyAsync(&overflow, info, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            SSW_TRY(ssw_copy_to_host(ctx, out, ctx->small.p, k * sizeof(float)));      // waits for the stream
+            SSW_TRY(ssw_copy_to_host(ctx, out, ctx->shared.small.p, k * sizeof(float)));      // waits for the stream
             if (overflow == 0) return SSW_OK;
         }
     }
@@ -1312,9 +1287,9 @@ int ssw_reader_extract(ssw_reader* base, ssw_reader* derived, float* out, size_t
         StageTimer t(ctx, SSW_STAGE_EXTRACT, ctx->stream);
         // cached list may be longer than k: its first k entries are the first k of the order
         SSW_TRY(launch_extract(ctx->stream, base->y, derived->y, 1, plane, base->idx, k, base->cfg.method,
-                               base->cfg.alpha, (float*)ctx->small.p));
+                               base->cfg.alpha, ctx->shared.small.as<float>()));
     }
-    return ssw_copy_to_host(ctx, out, ctx->small.p, k * sizeof(float));
+    return ssw_copy_to_host(ctx, out, ctx->shared.small.p, k * sizeof(float));
 }
 
 // Reader::extract against many derived frames + Tester::similarity against many marks (:529-539, :696-714): the reader's
@@ -1353,14 +1328,14 @@ int ssw_reader_trace_restored_host_rgb8(ssw_reader* base, const uint8_t* host_ba
     CtxGuard g(ctx);
     SSW_TRY(restore_prepare(ctx, pl));
     if (reads_base) {
-        SSW_TRY(grow(ctx->restore_base, base->w * base->h * 3));
-        SSW_TRY(upload(ctx, ctx->restore_base.p, host_base_rgb, base->w * base->h * 3, ctx->stream));
+        SSW_TRY(grow(ctx->shared.restore_base, base->w * base->h * 3));
+        SSW_TRY(upload(ctx, ctx->shared.restore_base.p, host_base_rgb, base->w * base->h * 3, ctx->stream));
     }
     if (k) SSW_TRY(reader_ensure_indices(base, k));
     ctx->expected_k = k ? k : ctx->expected_k;
     return stream_trace_rgb8(ctx, base->cfg, base->y, base->idx, host_suspects, n_suspects, base->w, base->h, k, host_marks, n_marks,
                              threshold, host_extracted, host_sims, host_best, host_best_sim, host_n_exceed, pl.data(),
-                             reads_base ? (const uint8_t*)ctx->restore_base.p : nullptr);
+                             reads_base ? ctx->shared.restore_base.as<const uint8_t>() : nullptr);
 }
 
 int ssw_reader_destroy(ssw_reader* rd) {
@@ -1382,8 +1357,8 @@ int ssw_similarity(ssw_ctx* ctx, const float* extracted, size_t n_extracted, con
     CtxGuard g(ctx);
     const size_t k = n_extracted;
     const size_t bytes = (k * 4 + 15) / 16 * 16;
-    SSW_TRY(grow(ctx->small, 2 * bytes + 16));
-    char* base = (char*)ctx->small.p;
+    SSW_TRY(grow(ctx->shared.small, 2 * bytes + 16));
+    char* base = ctx->shared.small.as<char>();
     if (k) {
         SSW_HIP_CHECK(hipMemcpyAsync(base, extracted, k * 4, hipMemcpyHostToDevice, ctx->stream));
         SSW_HIP_CHECK(hipMemcpyAsync(base + bytes, mark, k * 4, hipMemcpyHostToDevice, ctx->stream));

@@ -82,10 +82,10 @@ int dev_malloc(void** p, size_t bytes) {
 
 int grow(ssw_ctx::Buf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return SSW_OK;
-    // A buffer that grows in the middle of a call may already be captured by stages built earlier in the same chain (a
-    // row pass that exchanges A1 through operand[2], then a column pass that asks for a larger operand[2]): the old
-    // allocation is retired, not freed -- those stages keep working on it, the later ones use the new one -- and the next
-    // entry into the library frees it (CtxGuard).  Without a context in scope: free now (hipFree waits for work in flight).
+    // A buffer that grows in the middle of a call may already be captured by stages built earlier in the same chain (the
+    // lane's slots have several roles: ssw_internal.hpp, Lane): the old allocation is retired, not freed -- those stages
+    // keep working on it, the later ones use the new one -- and the next entry into the library frees it (CtxGuard).
+    // Without a context in scope: free now (hipFree waits for work in flight).
     if (b.p) {
         if (tl_ctx) tl_ctx->retired.push_back(b.p);
         else SSW_HIP_CHECK(hipFree(b.p));
@@ -250,19 +250,6 @@ int check_config(const ssw_config* cfg) {
 // clamped to half of what the device can give right now (free memory + what the lanes already hold), so that
 // a smaller device or a co-tenant (torch's caching allocator) gets smaller passes instead of an
 // SSW_ERR_OUT_OF_MEMORY.
-namespace {
-size_t lane_bytes_held(const ssw_ctx* ctx) {
-    size_t held = 0;
-    for (const auto& ln : ctx->lane) {
-        for (const auto& b : ln.plane) held += b.bytes;
-        for (const auto& b : ln.operand) held += b.bytes;
-        for (const auto& b : ln.compact) held += b.bytes;
-        held += ln.idx.bytes + ln.gathered.bytes + ln.prune_u32.bytes;
-    }
-    return held;
-}
-}  // namespace
-
 size_t effective_chunk(const ssw_ctx* ctx, size_t w, size_t h, size_t n_frames) {
     size_t c = ctx->chunk_frames;
     if (c == 0) {
@@ -351,7 +338,7 @@ int class_desc(ssw_ctx* ctx, size_t len, bool inverse, PairClass c, const double
     return SSW_OK;
 }
 
-// The split scratch of a pass (the lane's sixth operand buffer) as the deep pre-passes write it, planes by number (DESIGN
+// The split scratch of a pass (the lane's `deep` operand slot) as the deep pre-passes write it, planes by number (DESIGN
 // §3): level 1 -- AS BD AD BS R1 R2, K8 wide, then AS2 BD2 AD2 BS2, K16 wide; level 2 -- sixteen planes K16 wide, in `l2`
 // (the fused column pass reads them from the row launches' buffer).  `rot`: the rotation table of the axis.
 struct PairPlanes {
@@ -367,8 +354,8 @@ int pair_planes(const PassBuild& b, ssw_ctx::Lane& ws, PairPlanes& pp) {
     pp.bytes = dct_pair_operand_elems(b.n, b.w, b.h) * sizeof(double);
     if (!b.p.split) return SSW_OK;
     SSW_TRY(get_basis(b.ctx, b.len, false, true, BasisKind::Rot, &pp.rot));
-    SSW_TRY(grow(ws.operand[5], split_scratch_elems(b.n, b.w, b.h) * sizeof(double)));
-    pp.sp = pp.l2 = (double*)ws.operand[5].p;
+    SSW_TRY(ws.split_scratch(split_scratch_elems(b.n, b.w, b.h) * sizeof(double), &pp.sp));
+    pp.l2 = pp.sp;
     pp.p8 = b.lines * dct_pair_split_kpad(b.len);
     pp.p16 = pp.l2_plane = b.lines * dct_pair_split_kpad(b.len / 2);
     return SSW_OK;
@@ -429,8 +416,9 @@ int build_pair_l1(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     ssw_ctx* ctx = b.ctx;
     PairPlanes pp;
     SSW_TRY(pair_planes(b, ws, pp));
-    for (int i = 0; i < 2; ++i) SSW_TRY(grow(ws.operand[i], pp.bytes));
-    double *x1 = (double*)ws.operand[0].p, *x2 = (double*)ws.operand[1].p;
+    ssw_ctx::Lane::OneLevel o;
+    SSW_TRY(ws.one_level(pp.bytes, o));
+    double *x1 = o.s, *x2 = o.d;
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, SSW_STAGE_DCT_PREP, st, b.prep_bytes);
         return launch_dct_pair_prep(st, b.is_row, b.inverse, b.src, b.n, b.w, b.h, x1, x2);
@@ -451,11 +439,10 @@ int build_pair_two(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused
     ssw_ctx* ctx = b.ctx;
     PairPlanes pp;
     SSW_TRY(pair_planes(b, ws, pp));
-    for (int i = 1; i < (b.inverse ? 5 : 4); ++i) SSW_TRY(grow(ws.operand[i], pp.bytes));
-    double* x2 = (double*)ws.operand[1].p;       // D | O
-    double* xx1 = (double*)ws.operand[2].p;      // SS | EE
-    double* xx2 = (double*)ws.operand[3].p;      // SD | EO
-    double* tmpE = (double*)ws.operand[4].p;     // inverse: the even half E, unrounded
+    ssw_ctx::Lane::TwoLevel o;
+    SSW_TRY(ws.two_level(pp.bytes, b.inverse, o));
+    double *x2 = o.odd, *xx1 = o.ss, *xx2 = o.sd;      // D | O, SS | EE, SD | EO
+    double* tmpE = o.even;                             // inverse: the even half E, unrounded
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
         SSW_TRY(launch_dct_pair_prep4(st, b.is_row, b.inverse, b.row_input(), b.n, b.w, b.h, xx1, xx2, x2));
@@ -484,8 +471,9 @@ int build_pair_three(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch) {
     ssw_ctx* ctx = b.ctx;
     PairPlanes pp;
     SSW_TRY(pair_planes(b, ws, pp));
-    for (int i = 0; i < 4; ++i) SSW_TRY(grow(ws.operand[i], pp.bytes));
-    double *d1 = (double*)ws.operand[1].p, *d2 = (double*)ws.operand[0].p, *r1 = (double*)ws.operand[2].p, *r2 = (double*)ws.operand[3].p;
+    ssw_ctx::Lane::ThreeLevel o;
+    SSW_TRY(ws.three_level(pp.bytes, o));
+    double *d1 = o.odd, *d2 = o.s_minus, *r1 = o.r1, *r2 = o.r2;
     ch.push_back({true, [=](hipStream_t st) -> int {
         StageTimer t(ctx, b.st_prep, st, b.prep_bytes);
         if (!b.is_row) SSW_TRY(launch_dct_pair_prep8_cols(st, b.src, b.n, b.w, b.h, r1, r2, d2, d1));
@@ -572,8 +560,8 @@ int level2_pass(const PassBuild& b, ssw_ctx::Lane& ws, Level2Pass& l2) {
     l2.out = b.dst;
     if (l2.fused) {
         const size_t cplane = n * w * dct_pair_split_kpad(h / 2);          // column operands: n w lines, K16(h) wide
-        SSW_TRY(grow(ws.operand[0], 16 * cplane * sizeof(double)));
-        double* cop = (double*)ws.operand[0].p;
+        double* cop = nullptr;
+        SSW_TRY(ws.column_operands(16 * cplane * sizeof(double), &cop));
         l2.fc = FuseCols{FUSE_COLS};
         if (!b.is_row) { l2.pp.l2 = cop; l2.pp.l2_plane = cplane; }
         else {
@@ -740,9 +728,9 @@ int build_semi_deep(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fuse
     const bool inv = b.inverse;
     PairPlanes pp;
     SSW_TRY(pair_planes(b, ws, pp));
-    if (inv) for (int i : {1, 4}) SSW_TRY(grow(ws.operand[i], pp.bytes));
-    double* T2 = inv ? (double*)ws.operand[1].p : nullptr;
-    double* TE = inv ? (double*)ws.operand[4].p : nullptr;
+    ssw_ctx::Lane::Exchange x{nullptr, nullptr, nullptr};
+    if (inv) SSW_TRY(ws.inverse_exchange(pp.bytes, 0, 0, false, x));      // (whole operand planes)
+    double *T2 = x.t2, *TE = x.even;
     double* sp = pp.sp;
     const double* rot = (const double*)pp.rot;
     ch.push_back({true, [=](hipStream_t st) -> int {
@@ -793,15 +781,10 @@ int build_deep_inv(const PassBuild& b, ssw_ctx::Lane& ws, Chain& ch, bool* fused
     const void *rot2 = nullptr, *rot3 = nullptr;
     SSW_TRY(pair_planes(b, ws, pp));
     SSW_TRY(deep_rot(b, l2, &rot2, &rot3));
-    SSW_TRY(grow(ws.operand[1], std::max<size_t>(pp.bytes, lines * (len / 4) * sizeof(double))));
-    SSW_TRY(grow(ws.operand[4], std::max<size_t>(pp.bytes, lines * (len / 2) * sizeof(double))));
-    double* A1 = nullptr;             // the eighth-length even part, unrounded: len/8 doubles per line
-    if (l2) {
-        SSW_TRY(grow(ws.operand[2], std::max<size_t>(pp.bytes, lines * (len / 8) * sizeof(double))));      // (>= what any other pass asks of it)
-        A1 = (double*)ws.operand[2].p;
-    }
-    double* T2 = (double*)ws.operand[1].p;       // quarter-length even half, unrounded
-    double* TE = (double*)ws.operand[4].p;       // the even half E, unrounded
+    ssw_ctx::Lane::Exchange x;
+    SSW_TRY(ws.inverse_exchange(pp.bytes, lines, len, l2, x));
+    // unrounded: the eighth-length even part (level 2: len/8 doubles per line), the quarter-length even half, the even half E
+    double *A1 = x.a1, *T2 = x.t2, *TE = x.even;
     double* sp = pp.sp;
     const RgbSink sink = rgb_sink(b, fused_rgb);
     ch.push_back({true, [=](hipStream_t st) -> int {
@@ -1029,9 +1012,9 @@ int topk(ssw_ctx* ctx, hipStream_t st, SelectWorkspace& sel, const float* coef, 
         // the hot path: only Reader::indices() with a large k and marks that long reach it.
         size_t sb = 0;
         SSW_TRY(full_sort_scratch_bytes(w * h, n, &sb));
-        SSW_TRY(grow(ctx->sort_scratch, sb));
+        SSW_TRY(grow(ctx->shared.sort_scratch, sb));
         StageTimer t(ctx, SSW_STAGE_SELECT, st, bytes);
-        return launch_full_sort(st, coef, n, w, h, ordering, ctx->sort_scratch.p, ctx->sort_scratch.bytes, idx, k);
+        return launch_full_sort(st, coef, n, w, h, ordering, ctx->shared.sort_scratch.p, ctx->shared.sort_scratch.bytes, idx, k);
     }
     SSW_TRY(grow_select(st, sel, n, k));
     sel.fallbacks = ctx->select_fallbacks;
@@ -1259,14 +1242,13 @@ struct PruneTables {
 int lay_out_prune_tables(ssw_ctx* ctx, ssw_ctx::Lane* lane, const PruneSetup& ps, size_t w, uint32_t* info, PruneTables& t) {
     const bool deep = plan_is_deep(ps.rows), level2 = plan_is_level2(ps.rows);
     if ((deep && !ps.rows.split) || ps.gathered_bytes == 0) return SSW_ERR_BAD_ARG;
-    ssw_ctx::Buf& u32 = lane ? lane->prune_u32 : ctx->trace[2];
-    ssw_ctx::Buf& natural = lane ? lane->gathered : ctx->trace[3];
-    ssw_ctx::Buf& frag = lane ? lane->gathered : ctx->trace[4];
+    PruneBufs& pb = lane ? lane->prune : ctx->trace.prune;
+    ssw_ctx::Buf &u32 = pb.u32, &natural = pb.gathered, &frag = lane ? pb.gathered : pb.gathered_frag;
     t.plan = ps.plan;
     t.rows = ps.rows;
     t.info = info;
     SSW_TRY(grow(u32, (2 * w + ps.plan.cap_total + 64) * sizeof(uint32_t)));
-    t.flag = (uint32_t*)u32.p;
+    t.flag = u32.as<uint32_t>();
     t.pos = t.flag + w;
     t.rows_of = t.pos + w;
     t.rot[0] = t.rot[1] = t.rot[2] = nullptr;
@@ -1283,8 +1265,8 @@ int lay_out_prune_tables(ssw_ctx* ctx, ssw_ctx::Lane* lane, const PruneSetup& ps
     }
     SSW_TRY(grow(natural, ps.gathered_bytes));
     if (!lane && level2) SSW_TRY(grow(frag, ps.gathered_bytes));
-    t.gathered = (char*)natural.p;
-    t.gathered_frag = (char*)frag.p;
+    t.gathered = natural.as<char>();
+    t.gathered_frag = frag.as<char>();
     return SSW_OK;
 }
 
@@ -1320,7 +1302,7 @@ struct PrunedChunk {
     size_t n, w, h, k, lines;
     const uint32_t* idx;
     bool make_tables;               // this chain makes the tables it reads (else the call did: make_call_prune_tables)
-    double *sp, *o[4];              // the split scratch and the lane's operand buffers
+    double *sp, *o[4];              // the split scratch and the lane's four planes of the folded pre-passes, o[PruneClassSrc::lane_buf]
     float* t_compact;               // the row pass's output [lines][cap]
     PruneTables t;
     size_t cap() const { return t.plan.cap_total; }
@@ -1390,26 +1372,25 @@ void pruned_rows_gathered(const PrunedChunk& q, Chain& ch) {
     }});
 }
 
-// column pass on the compact plane: the second pass of the same transform, `cap` columns wide, into ws.compact[1]
+// column pass on the compact plane: the second pass of the same transform, `cap` columns wide, into ws.compact.cols
 int pruned_cols(ssw_ctx* ctx, ssw_ctx::Lane& ws, size_t n, size_t cap, size_t h, Chain& ch) {
-    float *t_compact = (float*)ws.compact[0].p, *compact = (float*)ws.compact[1].p;
+    float *t_compact = ws.compact.rows.as<float>(), *compact = ws.compact.cols.as<float>();
     Xform xc{SSW_DCT2, SSW_PRECISION_F64, n, cap, h, compact, t_compact};
     xc.natural_order = true;                 // the compact plane's columns are the gathered frequencies, in the plan's order
     return build_pass(ctx, ws, xc, false, false, t_compact, compact, Epilogue{1.f, 1.f}, ch);
 }
 
-// derived rgb frames -> compact coefficient plane ws.compact[1] [n][h][cap_total] holding, for every frequency column the
+// derived rgb frames -> compact coefficient plane ws.compact.cols [n][h][cap_total] holding, for every frequency column the
 // index lists use, the column the full (f64: make_prune_setup) transform would produce.  `call_tables`: the chunk reads the
 // call's tables; else it owns them in `ws` and its chain makes them.  *pos: their position list, for the extraction.
 int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, PixFmt fmt, size_t n, size_t w, size_t h, size_t k,
                          const uint32_t* idx, const PruneSetup& ps, uint32_t* info, bool call_tables, Chain& ch, const uint32_t** pos) {
     const size_t cap = ps.plan.cap_total, lines = n * h;
     const bool deep = plan_is_deep(ps.rows), level2 = plan_is_level2(ps.rows);
-    if (!deep) for (int b = 0; b < 4; ++b) SSW_TRY(grow(ws.operand[b], dct_pair_operand_elems(n, w, h) * sizeof(double)));      // the deep pre-pass writes into operand[5] only
-    for (int b = 0; b < 2; ++b) SSW_TRY(grow(ws.compact[b], n * h * cap * sizeof(float)));
-    if (ps.rows.split) SSW_TRY(grow(ws.operand[5], split_scratch_elems(n, w, h) * sizeof(double)));
-    PrunedChunk q{ctx, RowInput::rgb(fmt, rgb), n, w, h, k, lines, idx, !call_tables, ps.rows.split ? (double*)ws.operand[5].p : nullptr,
-                  {(double*)ws.operand[0].p, (double*)ws.operand[1].p, (double*)ws.operand[2].p, (double*)ws.operand[3].p}, (float*)ws.compact[0].p};
+    ssw_ctx::Lane::Pruned v;
+    SSW_TRY(ws.pruned_derived(deep ? 0 : dct_pair_operand_elems(n, w, h) * sizeof(double), n * h * cap * sizeof(float),
+                              ps.rows.split ? split_scratch_elems(n, w, h) * sizeof(double) : 0, v));
+    PrunedChunk q{ctx, RowInput::rgb(fmt, rgb), n, w, h, k, lines, idx, !call_tables, v.sp, {v.o[0], v.o[1], v.o[2], v.o[3]}, v.rows};
     SSW_TRY(lay_out_prune_tables(ctx, call_tables ? nullptr : &ws, ps, w, info, q.t));
     *pos = q.t.pos;
     // operand planes: by number in the split scratch, else the lane's buffers as the two- / three-level pre-passes fill them
@@ -1431,14 +1412,14 @@ int build_pruned_derived(ssw_ctx* ctx, ssw_ctx::Lane& ws, const void* rgb, PixFm
 }
 
 // Prune -> look once -> redo: build_chunk(chunk, lane, chain, pruned) through the pipeline; where it pruned, ONE wait for the
-// device to read the info blocks in ctx->overflow (one per chunk, or one for the call), the counters, and every chunk whose
+// device to read the info blocks in ctx->shared.overflow (one per chunk, or one for the call), the counters, and every chunk whose
 // block has the overflow flag set -- its columns did not fit the compact plane -- again on lane 0 with the full transform.
 typedef std::function<int(size_t, ssw_ctx::Lane&, Chain&, bool)> PrunedChunkBuilder;
 int run_pruned_pipeline(ssw_ctx* ctx, size_t n_chunks, const PruneSetup& ps, bool info_per_chunk, const PrunedChunkBuilder& build_chunk) {
     SSW_TRY(run_pipeline(ctx, n_chunks, [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch) { return build_chunk(ci, ws, ch, ps.on); }));
     if (!ps.on) return SSW_OK;
     std::vector<uint32_t> info((info_per_chunk ? n_chunks : 1) * SSW_PRUNE_INFO);
-    SSW_HIP_CHECK(hipMemcpyAsync(info.data(), ctx->overflow.p, info.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SSW_HIP_CHECK(hipMemcpyAsync(info.data(), ctx->shared.overflow.p, info.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (size_t ci = 0; ci < n_chunks; ++ci) {
         const uint32_t* block = info.data() + (info_per_chunk ? ci : 0) * SSW_PRUNE_INFO;
@@ -1473,8 +1454,8 @@ bool base_prune_shape_ok(const ssw_ctx* ctx, const ssw_config& c, size_t n, size
 int base_prune_workspace(ssw_ctx::Lane& ws, size_t frames, size_t w, BaseReaderArgs& a) {
     const size_t e_bytes = frames * w * sizeof(float);
     SSW_TRY(grow(ws.base_prune, e_bytes + frames * (w / SSW_BASE_PRUNE_TILE) * sizeof(unsigned)));
-    a.energy = (float*)ws.base_prune.p;
-    a.need = (unsigned*)((char*)ws.base_prune.p + e_bytes);
+    a.energy = ws.base_prune.as<float>();
+    a.need = (unsigned*)(ws.base_prune.as<char>() + e_bytes);
     return SSW_OK;
 }
 // What only the device knows of a pruned base reader's work is billed when the timers are resolved (flush_timers), from the
@@ -1483,9 +1464,9 @@ int base_prune_workspace(ssw_ctx::Lane& ws, size_t frames, size_t w, BaseReaderA
 // by the launches themselves.  Each frame at its own shape's rate: the kernels add flop and bytes up as doubles; what was
 // enqueued while the timers were off is passed over, like every other stage's work.
 int base_prune_bill(ssw_ctx* ctx) {
-    if (!ctx->base_prune_stats.p) return SSW_OK;
+    if (!ctx->shared.base_prune_stats.p) return SSW_OK;
     BasePruneCounters c;
-    SSW_HIP_CHECK(hipMemcpy(&c, ctx->base_prune_stats.p, sizeof(c), hipMemcpyDeviceToHost));
+    SSW_HIP_CHECK(hipMemcpy(&c, ctx->shared.base_prune_stats.p, sizeof(c), hipMemcpyDeviceToHost));
     const double now[5] = {c.col_flop, c.col_bytes, c.select_bytes, c.tail_flop, c.tail_bytes};
     double* billed = ctx->base_prune_billed;
     if (ctx->timing) {
@@ -1536,15 +1517,13 @@ int batch_embed_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_rgb, P
     const size_t in_px = 3 * pix_bytes(fmt_in), out_px = u8_out ? 3 : 3 * sizeof(float);
     auto build = [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch) -> int {
         const size_t f0 = ci * chunk, n = std::min(chunk, n_frames - f0);
-        for (int p = 0; p < 4; ++p) SSW_TRY(grow(ws.plane[p], chunk * plane * sizeof(float)));
+        ssw_ctx::Lane::WriterPlanes pl;
+        SSW_TRY(ws.writer_planes(chunk * plane * sizeof(float), pl));
         SSW_TRY(grow(ws.idx, chunk * std::max<size_t>(k_eff, 1) * sizeof(uint32_t)));
-        float* y = (float*)ws.plane[0].p;
-        float* pi = (float*)ws.plane[1].p;
-        float* pq = (float*)ws.plane[2].p;
-        float* tmp = (float*)ws.plane[3].p;
+        float *y = pl.y, *pi = pl.i, *pq = pl.q, *tmp = pl.scratch;
         const char* rgb = static_cast<const char*>(dev_rgb) + f0 * plane * in_px;
         char* out = static_cast<char*>(dev_rgb_out) + f0 * plane * out_px;
-        uint32_t* idx = dev_indices_out ? dev_indices_out + f0 * k_eff : (uint32_t*)ws.idx.p;
+        uint32_t* idx = dev_indices_out ? dev_indices_out + f0 * k_eff : ws.idx.as<uint32_t>();
         float* coef_out = dev_coef_out ? dev_coef_out + f0 * plane : nullptr;
         const float* marks = dev_marks + f0 * k;
         SelectWorkspace* sel = &ws.sel;
@@ -1591,30 +1570,30 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
     const size_t px_bytes = 3 * pix_bytes(fmt);
     // planes of lane 0 decide the (alignment-dependent) strategy for all lanes: hipMalloc'd, always 256-byte aligned
     // (lane 1 only when the call will run two lanes: three chunks or more)
-    for (int l = 0; l < (pipeline_uses_two_lanes(ctx, n_chunks) ? 2 : 1); ++l)
-        for (int p : {0, 2}) SSW_TRY(grow(ctx->lane[l].plane[p], chunk * plane * sizeof(float)));
-    const float *y0 = (const float*)ctx->lane[0].plane[0].p, *tmp0 = (const float*)ctx->lane[0].plane[2].p;
+    ssw_ctx::Lane::ReaderPlanes of_lane[ssw_ctx::MAX_LANES];
+    for (int l = 0; l < (pipeline_uses_two_lanes(ctx, n_chunks) ? 2 : 1); ++l) SSW_TRY(ctx->lane[l].reader_planes(chunk * plane * sizeof(float), of_lane[l]));
+    const float *y0 = of_lane[0].y, *tmp0 = of_lane[0].scratch;
     const PruneSetup ps = stream_capturing(ctx) ? PruneSetup() : make_prune_setup(ctx, f64, std::min(chunk, n_frames), w, h, k, y0, tmp0, dev_derived_rgb, fmt);
-    if (ps.on) SSW_TRY(grow(ctx->overflow, n_chunks * SSW_PRUNE_INFO * sizeof(uint32_t)));      // a block per chunk: every frame has its own list
-    uint32_t* overflow = (uint32_t*)ctx->overflow.p;
+    if (ps.on) SSW_TRY(grow(ctx->shared.overflow, n_chunks * SSW_PRUNE_INFO * sizeof(uint32_t)));      // a block per chunk: every frame has its own list
+    uint32_t* overflow = ctx->shared.overflow.as<uint32_t>();
     // Base-reader pruning (base_prune.hip): where the planner takes the fused forward transform for the chunks of this call
     // and the ordering has a key bound.  ssw_ctx_set_prune(0) and the tuning entry base_prune = 0 give the full transform.
     bool base_prune = ctx->prune && tuning(TUNE_BASE_PRUNE) != 0 && k > 0 && k <= select_max_k();
     for (size_t f0 = 0; base_prune && f0 < n_frames; f0 += chunk)        // (the last chunk may be shorter: another plan)
         base_prune = base_prune_shape_ok(ctx, c, std::min(chunk, n_frames - f0), w, h, dev_base_rgb, fmt, y0, tmp0);
-    if (base_prune && !ctx->base_prune_stats.p) {
-        SSW_TRY(grow(ctx->base_prune_stats, sizeof(BasePruneCounters)));
-        SSW_HIP_CHECK(hipMemsetAsync(ctx->base_prune_stats.p, 0, sizeof(BasePruneCounters), ctx->stream));
+    if (base_prune && !ctx->shared.base_prune_stats.p) {
+        SSW_TRY(grow(ctx->shared.base_prune_stats, sizeof(BasePruneCounters)));
+        SSW_HIP_CHECK(hipMemsetAsync(ctx->shared.base_prune_stats.p, 0, sizeof(BasePruneCounters), ctx->stream));
         untimed_work(ctx);
     }
 
     auto build_chunk = [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch, bool pruned) -> int {
         const size_t f0 = ci * chunk, n = std::min(chunk, n_frames - f0);
-        for (int p : {0, 2}) SSW_TRY(grow(ws.plane[p], chunk * plane * sizeof(float)));
+        ssw_ctx::Lane::ReaderPlanes pl;
+        SSW_TRY(ws.reader_planes(chunk * plane * sizeof(float), pl));
         SSW_TRY(grow(ws.idx, chunk * std::max<size_t>(k, 1) * sizeof(uint32_t)));
-        float* yb = (float*)ws.plane[0].p;
-        float* tmp = (float*)ws.plane[2].p;
-        uint32_t* idx = (uint32_t*)ws.idx.p;
+        float *yb = pl.y, *tmp = pl.scratch;
+        uint32_t* idx = ws.idx.as<uint32_t>();
         const char* brgb = static_cast<const char*>(dev_base_rgb) + f0 * plane * px_bytes;
         const char* drgb = static_cast<const char*>(dev_derived_rgb) + f0 * plane * px_bytes;
         SelectWorkspace* sel = &ws.sel;
@@ -1623,7 +1602,7 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         if (base_prune) {
             BaseReaderArgs a;
             SSW_TRY(base_prune_workspace(ws, chunk, w, a));
-            a.counters = (BasePruneCounters*)ctx->base_prune_stats.p;
+            a.counters = ctx->shared.base_prune_stats.as<BasePruneCounters>();
             a.k = k; a.ordering = c.ordering;
             SSW_TRY(build_base_reader(ctx, ws, c.precision, brgb, fmt, n, w, h, yb, tmp, a, ch, &mask));
         } else {
@@ -1636,11 +1615,12 @@ int batch_extract_impl(ssw_ctx* ctx, const ssw_config* cfg, const void* dev_base
         const uint32_t* pos = nullptr;
         if (pruned) {
             SSW_TRY(build_pruned_derived(ctx, ws, drgb, fmt, n, w, h, k, idx, ps, overflow + ci * SSW_PRUNE_INFO, false, ch, &pos));
-            derived = (const float*)ws.compact[1].p;
+            derived = ws.compact.cols.as<float>();
         } else {
-            SSW_TRY(grow(ws.plane[1], chunk * plane * sizeof(float)));
-            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, drgb, fmt, n, w, h, (float*)ws.plane[1].p, nullptr, nullptr, tmp, ch));
-            derived = (const float*)ws.plane[1].p;
+            float* full = nullptr;
+            SSW_TRY(ws.derived_plane(chunk * plane * sizeof(float), &full));
+            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, drgb, fmt, n, w, h, full, nullptr, nullptr, tmp, ch));
+            derived = full;
         }
         push_extract_stage(ch, ctx, c, yb, derived, pos, ps.plan.cap_total, n, w, h, idx, k, dev_extracted + f0 * k,
                            dev_marks ? dev_marks + f0 * k : nullptr, dev_sims ? dev_sims + f0 : nullptr);
@@ -1658,15 +1638,16 @@ int base_prune_bound_impl(ssw_ctx* ctx, const ssw_config* cfg, const float* dev_
     if (n_frames == 0) return SSW_OK;
     const size_t plane = w * h;
     ssw_ctx::Lane& ws = ctx->lane[0];
-    for (int p : {0, 2}) SSW_TRY(grow(ws.plane[p], n_frames * plane * sizeof(float)));
-    if (k == 0 || k >= plane || !base_prune_shape_ok(ctx, c, n_frames, w, h, dev_rgb, PixFmt::F32, (const float*)ws.plane[0].p, (const float*)ws.plane[2].p))
+    ssw_ctx::Lane::ReaderPlanes pl;
+    SSW_TRY(ws.reader_planes(n_frames * plane * sizeof(float), pl));
+    if (k == 0 || k >= plane || !base_prune_shape_ok(ctx, c, n_frames, w, h, dev_rgb, PixFmt::F32, pl.y, pl.scratch))
         return SSW_ERR_UNSUPPORTED;
     BaseReaderArgs a;
     SSW_TRY(base_prune_workspace(ws, n_frames, w, a));
     a.k = k; a.ordering = c.ordering;
     Chain ch;
     const unsigned* mask = nullptr;
-    SSW_TRY(build_base_reader(ctx, ws, c.precision, dev_rgb, PixFmt::F32, n_frames, w, h, (float*)ws.plane[0].p, (float*)ws.plane[2].p, a, ch, &mask));
+    SSW_TRY(build_base_reader(ctx, ws, c.precision, dev_rgb, PixFmt::F32, n_frames, w, h, pl.y, pl.scratch, a, ch, &mask));
     SSW_TRY(run_serial(ch, ctx->stream));
     untimed_work(ctx);
     return launch_base_prune_bound(ctx->stream, a.energy, n_frames, w, h, c.ordering, dev_bound);
@@ -1679,13 +1660,14 @@ int trace_base(ssw_ctx* ctx, const ssw_config& c, const void* dev_base_rgb, PixF
                const uint32_t** idx) {
     const size_t plane = w * h;
     ssw_ctx::Lane& ws = ctx->lane[0];
-    SSW_TRY(grow(ctx->trace[0], plane * sizeof(float)));
-    SSW_TRY(grow(ctx->trace[1], std::max<size_t>(k, 1) * sizeof(uint32_t)));
-    SSW_TRY(grow(ws.plane[2], plane * sizeof(float)));
-    float* yb = (float*)ctx->trace[0].p;
-    uint32_t* ib = (uint32_t*)ctx->trace[1].p;
+    float* tmp = nullptr;
+    SSW_TRY(grow(ctx->trace.base_plane, plane * sizeof(float)));
+    SSW_TRY(grow(ctx->trace.base_idx, std::max<size_t>(k, 1) * sizeof(uint32_t)));
+    SSW_TRY(ws.reader_scratch(plane * sizeof(float), &tmp));
+    float* yb = ctx->trace.base_plane.as<float>();
+    uint32_t* ib = ctx->trace.base_idx.as<uint32_t>();
     Chain ch;
-    SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_base_rgb, fmt, 1, w, h, yb, nullptr, nullptr, (float*)ws.plane[2].p, ch));
+    SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, dev_base_rgb, fmt, 1, w, h, yb, nullptr, nullptr, tmp, ch));
     SSW_TRY(run_serial(ch, ctx->stream));
     if (k > 0) SSW_TRY(topk(ctx, ctx->stream, ws.sel, yb, 1, w, h, c.ordering, k, ib));
     *y = yb;
@@ -1706,20 +1688,22 @@ int trace_extract(ssw_ctx* ctx, const ssw_config& c, const float* yb, const uint
     const size_t px_bytes = 3 * pix_bytes(fmt);
     const PruneSetup ps = stream_capturing(ctx) ? PruneSetup()
                           : make_prune_setup(ctx, c.precision == SSW_PRECISION_F64, std::min(chunk, n_frames), w, h, k, yb, yb, dev_suspect_rgb, fmt);
-    if (ps.on) SSW_TRY(grow(ctx->overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));                 // one block: one list for the call
-    uint32_t* info = (uint32_t*)ctx->overflow.p;
+    if (ps.on) SSW_TRY(grow(ctx->shared.overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));                 // one block: one list for the call
+    uint32_t* info = ctx->shared.overflow.as<uint32_t>();
     if (ps.on) SSW_TRY(make_call_prune_tables(ctx, ps, w, k, idx, info));
     auto build_chunk = [&](size_t ci, ssw_ctx::Lane& ws, Chain& ch, bool pruned) -> int {
         const size_t f0 = ci * chunk, n = std::min(chunk, n_frames - f0);
         const char* srgb = static_cast<const char*>(dev_suspect_rgb) + f0 * plane * px_bytes;
         float* ext = dev_extracted + f0 * k;
         const uint32_t* pos = nullptr;                 // Reader::derived: the compact plane through the tables' position list, or the full plane
+        float *full = nullptr, *tmp = nullptr;
         if (pruned) SSW_TRY(build_pruned_derived(ctx, ws, srgb, fmt, n, w, h, k, idx, ps, info, true, ch, &pos));
         else {
-            for (int p : {1, 2}) SSW_TRY(grow(ws.plane[p], chunk * plane * sizeof(float)));
-            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, srgb, fmt, n, w, h, (float*)ws.plane[1].p, nullptr, nullptr, (float*)ws.plane[2].p, ch));
+            SSW_TRY(ws.derived_plane(chunk * plane * sizeof(float), &full));
+            SSW_TRY(ws.reader_scratch(chunk * plane * sizeof(float), &tmp));
+            SSW_TRY(build_forward_from_rgb(ctx, ws, c.precision, srgb, fmt, n, w, h, full, nullptr, nullptr, tmp, ch));
         }
-        const float* derived = (const float*)(pruned ? ws.compact[1].p : ws.plane[1].p);
+        const float* derived = pruned ? ws.compact.cols.as<float>() : full;
         const size_t cap = ps.plan.cap_total;
         ch.push_back({true, [=](hipStream_t st) -> int {
             StageTimer t(ctx, SSW_STAGE_EXTRACT, st);                               // :529-539
@@ -1745,19 +1729,19 @@ int extract_single_pruned(ssw_ctx* ctx, int precision, const void* derived_rgb, 
     *applicable = false;
     const size_t plane = w * h;
     ssw_ctx::Lane& ws = ctx->lane[0];
-    for (int p : {0, 2}) SSW_TRY(grow(ws.plane[p], plane * sizeof(float)));
-    const PruneSetup ps = make_prune_setup(ctx, precision == SSW_PRECISION_F64, 1, w, h, k, (const float*)ws.plane[0].p,
-                                           (const float*)ws.plane[2].p, derived_rgb, fmt);
+    ssw_ctx::Lane::ReaderPlanes pl;
+    SSW_TRY(ws.reader_planes(plane * sizeof(float), pl));
+    const PruneSetup ps = make_prune_setup(ctx, precision == SSW_PRECISION_F64, 1, w, h, k, pl.y, pl.scratch, derived_rgb, fmt);
     if (!ps.on) return SSW_OK;
-    SSW_TRY(grow(ctx->overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));
-    uint32_t* info = (uint32_t*)ctx->overflow.p;
+    SSW_TRY(grow(ctx->shared.overflow, SSW_PRUNE_INFO * sizeof(uint32_t)));
+    uint32_t* info = ctx->shared.overflow.as<uint32_t>();
     Chain ch;
     const uint32_t* pos = nullptr;
     SSW_TRY(build_pruned_derived(ctx, ws, derived_rgb, fmt, 1, w, h, k, idx, ps, info, false, ch, &pos));
     SSW_TRY(run_serial(ch, ctx->stream));
     {
         StageTimer t(ctx, SSW_STAGE_EXTRACT, ctx->stream);
-        SSW_TRY(launch_extract_pruned(ctx->stream, base_y, (const float*)ws.compact[1].p, 1, w, h, ps.plan.cap_total, pos, idx, k, method, alpha, dev_out));
+        SSW_TRY(launch_extract_pruned(ctx->stream, base_y, ws.compact.cols.as<float>(), 1, w, h, ps.plan.cap_total, pos, idx, k, method, alpha, dev_out));
     }
     *dev_info = info;
     *applicable = true;

@@ -100,7 +100,7 @@ int stream_embed_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* const*
             const int s = (int)(g % NB);
             const size_t f0 = groups[g].f0, n = groups[g].n;
             if (g >= (size_t)NB) SSW_HIP_CHECK(hipStreamWaitEvent(ctx->copy_stream, hs.k_done[s], 0));      // kernels of group g - NB read in[s]
-            for (size_t j = 0; j < n; ++j) SSW_TRY(upload_nowait(ctx, (char*)hs.in[s].p + j * fb, host_frames[f0 + j], fb, ctx->copy_stream, &as));
+            for (size_t j = 0; j < n; ++j) SSW_TRY(upload_nowait(ctx, hs.in[s].as<char>() + j * fb, host_frames[f0 + j], fb, ctx->copy_stream, &as));
             SSW_HIP_CHECK(hipEventRecord(hs.up_done[s], ctx->copy_stream));
             return SSW_OK;
         };
@@ -108,7 +108,7 @@ int stream_embed_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* const*
             const int s = (int)(g % NB);
             const size_t f0 = groups[g].f0, n = groups[g].n;
             SSW_HIP_CHECK(hipStreamWaitEvent(ctx->down_stream, hs.k_done[s], 0));
-            for (size_t j = 0; j < n; ++j) SSW_TRY(download_nowait(ctx, host_out[f0 + j], (const char*)hs.out[s].p + j * fb, fb, ctx->down_stream, &as));
+            for (size_t j = 0; j < n; ++j) SSW_TRY(download_nowait(ctx, host_out[f0 + j], hs.out[s].as<const char>() + j * fb, fb, ctx->down_stream, &as));
             SSW_HIP_CHECK(hipEventRecord(hs.down_done[s], ctx->down_stream));
             return SSW_OK;
         };
@@ -119,7 +119,7 @@ int stream_embed_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* const*
             SSW_HIP_CHECK(hipStreamWaitEvent(ctx->stream, hs.up_done[s], 0));
             if (g >= (size_t)NB) SSW_HIP_CHECK(hipStreamWaitEvent(ctx->stream, hs.down_done[s], 0));   // download of group g - NB reads out[s]
             untimed_work(ctx);                 // the group's first stage timer starts behind these waits
-            SSW_TRY(batch_embed_impl(ctx, cfg, hs.in[s].p, PixFmt::U8, n, w, h, (const float*)hs.marks.p + f0 * k, k, hs.out[s].p, true, nullptr, nullptr));
+            SSW_TRY(batch_embed_impl(ctx, cfg, hs.in[s].p, PixFmt::U8, n, w, h, hs.marks.as<const float>() + f0 * k, k, hs.out[s].p, true, nullptr, nullptr));
             SSW_HIP_CHECK(hipEventRecord(hs.k_done[s], ctx->stream));
             untimed_work(ctx);
             if (g + NB - 1 < n_groups) SSW_TRY(h2d(g + NB - 1));      // staged (pageable) frames: the host copies while group g computes
@@ -161,8 +161,8 @@ int stream_extract_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* cons
             const size_t f0 = groups[g].f0, n = groups[g].n;
             if (g >= (size_t)NB) SSW_HIP_CHECK(hipStreamWaitEvent(ctx->copy_stream, hs.k_done[s], 0));
             for (size_t j = 0; j < n; ++j) {
-                SSW_TRY(upload_nowait(ctx, (char*)hs.in[s].p + j * fb, host_base[f0 + j], fb, ctx->copy_stream, &as));
-                SSW_TRY(upload_nowait(ctx, (char*)hs.in2[s].p + j * fb, host_derived[f0 + j], fb, ctx->copy_stream, &as));
+                SSW_TRY(upload_nowait(ctx, hs.in[s].as<char>() + j * fb, host_base[f0 + j], fb, ctx->copy_stream, &as));
+                SSW_TRY(upload_nowait(ctx, hs.in2[s].as<char>() + j * fb, host_derived[f0 + j], fb, ctx->copy_stream, &as));
             }
             SSW_HIP_CHECK(hipEventRecord(hs.up_done[s], ctx->copy_stream));
             return SSW_OK;
@@ -176,8 +176,8 @@ int stream_extract_rgb8(ssw_ctx* ctx, const ssw_config* cfg, const uint8_t* cons
             if (g + NB - 1 < n_groups) SSW_TRY(h2d(g + NB - 1));
             SSW_HIP_CHECK(hipStreamWaitEvent(ctx->stream, hs.up_done[s], 0));
             untimed_work(ctx);
-            SSW_TRY(batch_extract_impl(ctx, cfg, hs.in[s].p, hs.in2[s].p, PixFmt::U8, n, w, h, k, (float*)hs.ext.p + f0 * k,
-                                       host_marks ? (const float*)hs.marks.p + f0 * k : nullptr, host_sims ? (float*)hs.sims.p + f0 : nullptr));
+            SSW_TRY(batch_extract_impl(ctx, cfg, hs.in[s].p, hs.in2[s].p, PixFmt::U8, n, w, h, k, hs.ext.as<float>() + f0 * k,
+                                       host_marks ? hs.marks.as<const float>() + f0 * k : nullptr, host_sims ? hs.sims.as<float>() + f0 : nullptr));
             SSW_HIP_CHECK(hipEventRecord(hs.k_done[s], ctx->stream));
             untimed_work(ctx);
         }
@@ -217,10 +217,10 @@ int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, co
     // results behind the extracted marks' buffer would move it: sims | best | best_sim | n_exceed in one block of their own
     const size_t sims_bytes = (n_suspects * n_marks * sizeof(float) + 15) / 16 * 16, row_bytes = (n_suspects * 4 + 15) / 16 * 16;
     if (score) SSW_TRY(grow(hs.sims, sims_bytes + 3 * row_bytes));
-    float* d_sims = score && n_marks ? (float*)hs.sims.p : nullptr;
-    uint32_t* d_best = score ? (uint32_t*)((char*)hs.sims.p + sims_bytes) : nullptr;
-    float* d_best_sim = score ? (float*)((char*)hs.sims.p + sims_bytes + row_bytes) : nullptr;
-    uint32_t* d_exceed = score ? (uint32_t*)((char*)hs.sims.p + sims_bytes + 2 * row_bytes) : nullptr;
+    float* d_sims = score && n_marks ? hs.sims.as<float>() : nullptr;
+    uint32_t* d_best = score ? (uint32_t*)(hs.sims.as<char>() + sims_bytes) : nullptr;
+    float* d_best_sim = score ? (float*)(hs.sims.as<char>() + sims_bytes + row_bytes) : nullptr;
+    uint32_t* d_exceed = score ? (uint32_t*)(hs.sims.as<char>() + sims_bytes + 2 * row_bytes) : nullptr;
     auto body = [&]() -> int {
         bool as = false;
         if (n_marks && k) SSW_TRY(upload_nowait(ctx, hs.marks.p, host_marks, n_marks * k * sizeof(float), ctx->stream, &as));
@@ -229,8 +229,8 @@ int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, co
             const size_t f0 = groups[g].f0, n = groups[g].n;
             if (g >= (size_t)NB) SSW_HIP_CHECK(hipStreamWaitEvent(ctx->copy_stream, hs.k_done[s], 0));
             for (size_t j = 0; j < n; ++j) {
-                if (touched(f0 + j)) SSW_TRY(upload_nowait(ctx, (char*)hs.in2[s].p + j * raw_slot, host_suspects[f0 + j], raw_bytes(f0 + j), ctx->copy_stream, &as));
-                else SSW_TRY(upload_nowait(ctx, (char*)hs.in[s].p + j * fb, host_suspects[f0 + j], fb, ctx->copy_stream, &as));
+                if (touched(f0 + j)) SSW_TRY(upload_nowait(ctx, hs.in2[s].as<char>() + j * raw_slot, host_suspects[f0 + j], raw_bytes(f0 + j), ctx->copy_stream, &as));
+                else SSW_TRY(upload_nowait(ctx, hs.in[s].as<char>() + j * fb, host_suspects[f0 + j], fb, ctx->copy_stream, &as));
             }
             SSW_HIP_CHECK(hipEventRecord(hs.up_done[s], ctx->copy_stream));
             return SSW_OK;
@@ -245,14 +245,14 @@ int stream_trace_rgb8(ssw_ctx* ctx, const ssw_config& c, const float* base_y, co
             untimed_work(ctx);
             jobs.clear();                                             // raw slots -> the group's frames (none: no launch)
             for (size_t j = 0; j < n; ++j)
-                if (touched(f0 + j)) jobs.push_back(RestoreJob{(const uint8_t*)hs.in2[s].p + j * raw_slot, (uint8_t*)hs.in[s].p + j * fb, pl[f0 + j]});
+                if (touched(f0 + j)) jobs.push_back(RestoreJob{hs.in2[s].as<const uint8_t>() + j * raw_slot, hs.in[s].as<uint8_t>() + j * fb, pl[f0 + j]});
             SSW_TRY(restore_enqueue(ctx, dev_base, w, h, jobs.data(), jobs.size()));
-            SSW_TRY(trace_extract(ctx, c, base_y, base_idx, hs.in[s].p, PixFmt::U8, n, w, h, k, (float*)hs.ext.p + f0 * k));
+            SSW_TRY(trace_extract(ctx, c, base_y, base_idx, hs.in[s].p, PixFmt::U8, n, w, h, k, hs.ext.as<float>() + f0 * k));
             SSW_HIP_CHECK(hipEventRecord(hs.k_done[s], ctx->stream));
             untimed_work(ctx);
         }
         if (score)
-            SSW_TRY(trace_score(ctx, (const float*)hs.ext.p, n_suspects, n_marks ? (const float*)hs.marks.p : nullptr, n_marks, k, threshold, d_sims,
+            SSW_TRY(trace_score(ctx, hs.ext.as<const float>(), n_suspects, n_marks ? hs.marks.as<const float>() : nullptr, n_marks, k, threshold, d_sims,
                                 d_best, d_best_sim, d_exceed));
         // (the context's stream: everything above is ordered on it)
         if (k && host_extracted) SSW_TRY(download_nowait(ctx, host_extracted, hs.ext.p, n_suspects * k * sizeof(float), ctx->stream, &as));

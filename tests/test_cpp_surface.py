@@ -42,6 +42,17 @@ def test_transform_planner_on_the_host(tmp_path):
     assert out.strip() == "ok", out
 
 
+def test_workspace_enumeration_on_the_host(tmp_path):
+    """csrc/ssw_internal.hpp: the one enumeration of a context's workspace buffers that teardown and the automatic pass size
+    run off -- every Buf once, under its own name, none left out, and exactly the lanes' planes, operand slots, compact planes,
+    index lists, gathered bases and prune tables counted towards the held total -- no GPU, no HIP call."""
+    exe = os.path.join(str(tmp_path), "workspace_test")
+    subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "--offload-arch=gfx950", os.path.join(ROOT, "tests", "cpp", "workspace_test.cpp"),
+                    "-o", exe, "-L", LIBDIR, "-lssw_hip", f"-Wl,-rpath,{LIBDIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout
+
+
 def test_pair_class_table_on_the_host(tmp_path):
     """csrc/dct_pair_class.hpp: the launch-class table answers what the per-class launch code answered before the table existed
     (tests/golden/pair_class_parent.txt: all 33600 tuples of class, pass, direction, layout, length, the rejected ones included,

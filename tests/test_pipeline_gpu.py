@@ -76,6 +76,89 @@ def test_context_create_destroy_releases_device_memory(tmp_path):
     assert leaked < 8 << 20, f"device memory leaked across context cycles: {r.stdout[-300:]}"
 
 
+# One cycle of the teardown test: every owner of workspace buffers once, at the smallest shapes the per-feature tests use.
+_TOUCH_EVERY_OWNER = r"""
+import ctypes as C, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import spread_spectrum_watermarking_amd as wm
+from spread_spectrum_watermarking_amd.api import check, Placement, Locate
+
+W, H, K, N = 320, 192, 64, 6
+rng = np.random.default_rng(3)
+yy, xx = np.mgrid[0:H, 0:W]
+frames = [np.clip(128 + (60 * np.sin(xx / (5.0 + f)) * np.cos(yy / (7.0 + f)))[..., None] + rng.integers(-40, 41, (H, W, 3)), 0, 255).astype(np.uint8)
+          for f in range(N)]
+marks = rng.standard_normal((N, K)).astype(np.float32)
+
+def resize(ctx, img, nw, nh):
+    d, out = ctx.to_device(img), ctx.alloc(nw * nh * 3)
+    check(ctx._lib.ssw_resize_rgb8(ctx.handle, d.ptr, 1, img.shape[1], img.shape[0], nw, nh, out.ptr), "ssw_resize_rgb8")
+    r = out.to_host(np.uint8, (nh, nw, 3))
+    d.free(); out.free()
+    return r
+
+def touch_every_owner(ctx):
+    ctx.set_chunk_frames(2)                      # three passes: both lanes, the pruned path
+    marked = wm.mark_many(frames, marks, ctx=ctx)                                            # batch embed, the streaming ring
+    ext, sims = wm.extract_many(frames, marked, K, marks, ctx=ctx)                           # batch extract
+    small = resize(ctx, marked[0], 240, 144)                                                 # one resize
+    crop = np.ascontiguousarray(marked[0][40:150, 50:260])
+    wm.trace_many(frames[0], [small, crop], marks, ctx=ctx, placements=[None, Placement(50, 40)])      # restore + trace
+    cut = resize(ctx, np.ascontiguousarray(frames[1][21:117, 37:197]), 240, 144)             # 160 x 96 of the original, enlarged
+    wm.locate(frames[1], [cut], [Locate(widths=(140, 180))], ctx=ctx)                        # the scale ladder
+    cat = wm.Catalogue(ctx)
+    cat.add_many([str(i) for i in range(N)], frames)
+    cat.match([small])
+    cat._dev.free()
+    writer = wm.Writer(frames[2], ctx=ctx)
+    copies = list(writer.mark_copies_rgb8(marks[:3]))                                        # fingerprinting
+    del writer
+    wm.collude(copies, [("median", [0, 1, 2]), ("mosaic", [1, 2])], ctx)
+    wm.jpeg(copies, (75, 10), ctx)
+    wm.filter(copies, [wm.Filter.blur(1.5), wm.Filter.median(), wm.Filter.unsharp()], ctx)
+    wm.ssim(frames[2], copies, ctx)
+    reader = wm.Reader.base(frames[3], ctx=ctx)
+    assert len(reader.indices(20000)) == 20000                                               # beyond the top-k limit: the sort scratch
+    del reader
+    ctx.synchronize()
+"""
+
+_TEARDOWN_SCRIPT = _TOUCH_EVERY_OWNER + r"""
+probe = wm.Context(0)
+
+def cycle():
+    ctx = wm.Context(0)
+    touch_every_owner(ctx)
+    ctx.close()
+
+cycle()                                          # first cycle: code objects, runtime pools
+free0, _ = probe.mem_info()
+for _ in range(3):
+    cycle()
+free1, _ = probe.mem_info()
+for _ in range(3):
+    cycle()
+free2, _ = probe.mem_info()
+print("leaked_bytes", min(free0 - free1, free1 - free2), "windows", free0 - free1, free1 - free2)
+"""
+
+
+def test_context_destroy_releases_every_features_workspace(tmp_path):
+    """ssw_ctx_destroy runs off the one enumeration of the context's workspace (csrc/ssw_internal.hpp: for_each_workspace), so
+    every feature's buffers go with it: a cycle creates a context, runs batch embed + extract (host form: the streaming ring),
+    a restoring trace, locate with the scale ladder, a catalogue match, fingerprint copies, collude, jpeg, filter, ssim, a full
+    index sort and a resize, and closes it.  Same scheme and bar as the test above: a fresh process, one warm-up cycle, two
+    windows of three cycles, the smaller one counts."""
+    script = tmp_path / "teardown_check.py"
+    script.write_text(_TEARDOWN_SCRIPT)
+    r = subprocess.run([sys.executable, str(script), ROOT], capture_output=True, text=True, timeout=600)
+    # no retry: a child that dies (rc != 0) is a failure, whatever came before it
+    assert r.returncode == 0 and "leaked_bytes" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+    leaked = int(r.stdout.split("leaked_bytes")[1].split()[0])
+    assert leaked < 8 << 20, f"device memory leaked across context cycles: {r.stdout[-300:]}"
+
+
 def test_alloc_failure_is_out_of_memory_and_recoverable():
     ctx = G.ctx()
     p = C.c_void_p()
