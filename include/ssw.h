@@ -824,6 +824,54 @@ typedef enum ssw_filter_kind { SSW_FILTER_BLUR = 0, SSW_FILTER_UNSHARP = 1, SSW_
 typedef struct ssw_filter_job { uint32_t frame; uint32_t kind; float radius; uint32_t percent; uint32_t threshold; } ssw_filter_job;
 int ssw_filter_rgb8(ssw_ctx* ctx, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h, const ssw_filter_job* jobs,
                     size_t n_jobs, uint8_t* dev_out);
+/* The scale attack: a copy scaled for the web.  ssw_resample_rgb8 makes of n_frames frames [h][w][3] the frames [nh][nw][3]
+   that PIL.Image.resize((nw, nh), filter) makes of them -- exactly: Pillow's 8-bit resample is integer arithmetic on the bytes,
+   and the numpy restatement in tests/test_resample_cpu.py (`resample_ref`, checked there against Pillow byte for byte) is what
+   the call equals.  Every channel is resampled on its own.  One axis with `in` samples and `out` samples, in double on the
+   host, each operation rounded on its own (no contraction; csrc/resample_tables.hpp):
+       scale = in / out        fs = max(scale, 1.0)        support = S * fs        ss = 1 / fs
+     and for output xx
+       center = (xx + 0.5) * scale
+       xmin = max((int) (center - support + 0.5), 0)              xmax = min((int) (center + support + 0.5), in) - xmin
+       k[x] = f((x + xmin - center + 0.5) * ss)   for x < xmax    ww = sum of k in ascending order;  k[x] /= ww  if ww != 0
+       tap[x] = (int) (k[x] * 2^22 - 0.5) if k[x] < 0, else (int) (k[x] * 2^22 + 0.5)          ((int) truncates toward zero)
+     with the filters f and their supports S
+       SSW_RESAMPLE_BOX       S = 0.5   1 for -0.5 < x <= 0.5, else 0
+       SSW_RESAMPLE_BILINEAR  S = 1     1 - |x| for |x| < 1, else 0
+       SSW_RESAMPLE_BICUBIC   S = 2     with a = -0.5 and x = |x|: ((a + 2) x - (a + 3)) x x + 1 for x < 1 (multiplied from the
+                                        left); (((x - 5) x + 8) x - 4) a for 1 <= x < 2; else 0
+       SSW_RESAMPLE_LANCZOS   S = 3     sinc(x) sinc(x / 3) for -3 <= x < 3, else 0; sinc(0) = 1, sinc(x) = sin(pi x) / (pi x)
+                                        with libm's sin
+     One pass along a line:   out[xx] = clip8((2^21 + sum_x in[xmin + x] * tap[x]) >> 22)
+     with 32-bit sums (they are exact: the restatement asserts that each fits an int32), an arithmetic shift and a clamp to
+     0 .. 255.  A frame is resampled along the rows first, into bytes, and then along the columns; a pass whose in == out is
+     skipped, not run as an identity, and nw == w && nh == h is a copy.  Any w, h, nw, nh from 1 to 65535.  Pillow's NEAREST
+     and HAMMING, `box`, `reducing_gap`, RGBA and 16-bit frames are not offered.
+   ssw_scale_attack_rgb8 has the job signature of ssw_filter_rgb8: dev_out[j] [h][w][3] is frame jobs[j].frame of dev_frames
+   [n_frames][h][w][3] resampled to jobs[j].nw x jobs[j].nh with jobs[j].filter as above, then brought back to w x h by the
+   resize ssw_restore_rgb8 applies to a three-channel suspect of another size that covers the whole frame (the CatmullRom of
+   csrc/resize_common.hpp, which ssw_resize_rgb8 shares): what a trace of the thumbnail sees.  nw == w && nh == h copies the
+   frame.  `jobs` is a HOST array; a frame may occur in many jobs and in any order; consecutive jobs of one (nw, nh, filter) run
+   as one batch.  The way back has the limits of ssw_restore_rgb8: SSW_ERR_UNSUPPORTED for a size that has no LDS tile (a
+   thumbnail far larger than the frame), and the first use of a pair of lengths in a context waits for the stream once while
+   its tap table goes up.
+   Both calls only enqueue on the context's stream; their own tables go up in one copy per batch on that stream.  The row pass
+   writes a byte plane [h][nw][3] per frame into the context's workspace, in groups of at most 32 frames and 64 MiB (or one
+   frame's); the thumbnails of a batch live beside it, at most 64 MiB (or one job's) at a time.  No alignment is assumed of any
+   pointer or of w * 3.  dev_out must not overlap the input.  Timed under SSW_STAGE_CONVERT; work per frame or job
+   3 w h + 2 * 3 nw h + 3 nw nh bytes, the plane's term dropped when either pass is skipped; the way back of a job is timed as
+   ssw_restore_rgb8 times it, under SSW_STAGE_RESIZE with 3 nw nh + 3 w h bytes.
+   n_frames == 0 (resample) or n_jobs == 0 is checked first: SSW_OK; SSW_ERR_BAD_ARG: a null pointer, frame >= n_frames, an
+   unknown filter, a dev_out that overlaps the input (nothing is enqueued when any job is bad); SSW_ERR_BAD_DIMS: a side of 0 or
+   above 65535. */
+typedef enum ssw_resample_filter {
+    SSW_RESAMPLE_BOX = 0, SSW_RESAMPLE_BILINEAR = 1, SSW_RESAMPLE_BICUBIC = 2, SSW_RESAMPLE_LANCZOS = 3
+} ssw_resample_filter;
+int ssw_resample_rgb8(ssw_ctx* ctx, const uint8_t* dev_in, size_t n_frames, size_t w, size_t h, size_t nw, size_t nh, int filter,
+                      uint8_t* dev_out);
+typedef struct ssw_scale_job { uint32_t frame; uint32_t nw; uint32_t nh; uint32_t filter; } ssw_scale_job;
+int ssw_scale_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h, const ssw_scale_job* jobs,
+                          size_t n_jobs, uint8_t* dev_out);
 
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,

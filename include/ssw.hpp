@@ -524,6 +524,40 @@ inline std::vector<ImageRgb8> filter(Context& ctx, const std::vector<const Image
     return detail::frames_through_jobs(ctx, frames, jb, "filter", ssw_filter_rgb8);
 }
 
+// The filters of Pillow's Image.resize that ssw_resample_rgb8 offers
+enum class ResampleFilter : uint32_t { Box = SSW_RESAMPLE_BOX, Bilinear = SSW_RESAMPLE_BILINEAR, Bicubic = SSW_RESAMPLE_BICUBIC, Lanczos = SSW_RESAMPLE_LANCZOS };
+// ssw_resample_rgb8 on host images of one size: every image as PIL.Image.resize((nw, nh), filter) makes it, byte for byte;
+// include/ssw.h states the definition.
+inline std::vector<ImageRgb8> resample(Context& ctx, const std::vector<const ImageRgb8*>& frames, size_t nw, size_t nh,
+                                       ResampleFilter filter = ResampleFilter::Bicubic) {
+    if (frames.empty()) throw Error(SSW_ERR_BAD_ARG, "resample");
+    const size_t n = frames.size(), w = frames[0]->width, h = frames[0]->height, ob = nw * nh * 3;
+    detail::DeviceFrames dev(ctx.get(), n * w * h * 3, "resample"), made(ctx.get(), n * ob, "resample");
+    dev.put(frames, w, h, "resample");
+    check(ssw_resample_rgb8(ctx.get(), dev.p, n, w, h, nw, nh, (int)filter, made.p), "resample");
+    std::vector<ImageRgb8> out(n, ImageRgb8(nw, nh));
+    for (size_t i = 0; i < n; ++i) check(ssw_copy_to_host(ctx.get(), out[i].data.data(), made.p + i * ob, ob), "resample");
+    return out;
+}
+// One result of wm::scale_attack: a frame (an index into the images), the thumbnail's size and the filter that makes it
+struct Scale {
+    uint32_t frame = 0;
+    uint32_t nw = 1, nh = 1;
+    ResampleFilter filter = ResampleFilter::Bicubic;
+    // the thumbnail of a w x h frame at `factor`: sides rounded half up, at least 1
+    static Scale by(uint32_t frame, size_t w, size_t h, double factor, ResampleFilter filter = ResampleFilter::Bicubic) {
+        const auto side = [&](size_t v) { const long s = (long)((double)v * factor + 0.5); return (uint32_t)(s < 1 ? 1 : s); };
+        return Scale{frame, side(w), side(h), filter};
+    }
+};
+// ssw_scale_attack_rgb8 on host images of one size: per job that frame scaled as Pillow's Image.resize does it and brought back
+// to its size as a trace brings back a suspect of another size; include/ssw.h states both steps.
+inline std::vector<ImageRgb8> scale_attack(Context& ctx, const std::vector<const ImageRgb8*>& frames, const std::vector<Scale>& jobs) {
+    std::vector<ssw_scale_job> jb(jobs.size());
+    for (size_t i = 0; i < jb.size(); ++i) jb[i] = ssw_scale_job{jobs[i].frame, jobs[i].nw, jobs[i].nh, (uint32_t)jobs[i].filter};
+    return detail::frames_through_jobs(ctx, frames, jb, "scale_attack", ssw_scale_attack_rgb8);
+}
+
 // The originals someone owns, as signatures: which of them is a suspect a copy of?  The stage in front of locate / Reader::trace
 // (ssw_signature_match; include/ssw.h states the definition and what it cannot find: cut-outs, mirrored and turned copies).
 // The signatures stay on the device between match calls and go up again only after an add.

@@ -86,6 +86,19 @@ class FilterJob(C.Structure):
 
 
 FILTER_BLUR, FILTER_UNSHARP, FILTER_MEDIAN3 = range(3)
+
+
+class ScaleJob(C.Structure):
+    """ssw_scale_job (include/ssw.h): one result of ssw_scale_attack_rgb8 -- a frame of the call, the thumbnail's size and the
+    ssw_resample_filter that makes it."""
+    _fields_ = [("frame", C.c_uint32), ("nw", C.c_uint32), ("nh", C.c_uint32), ("filter", C.c_uint32)]
+
+
+# ssw_resample_filter, by the names the Python surface and the CLI accept (Pillow's)
+RESAMPLE_BOX, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC, RESAMPLE_LANCZOS = range(4)
+RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2, "lanczos": 3}
+RESAMPLE_SIDE_MAX = 65535
+SCALE_FACTOR_MAX = 4.0       # api.Scale: the largest factor
 FILTER_RADIUS_MAX = 8.0      # keeps the box radius of a blur pass at 7 or below
 QUALITY_STATS = 6            # ssw_quality_rgb8: u64 per copy -- SSE of R, G, B, SSE of the luma, changed bytes, max |d|
 SSIM_MIN_SIDE = 8            # ssw_ssim_rgb8 refuses smaller frames
@@ -189,6 +202,8 @@ SIGNATURES = {
     "ssw_collude_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(Coalition), _sz, _vp]),
     "ssw_jpeg_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(JpegJob), _sz, _vp]),
     "ssw_filter_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(FilterJob), _sz, _vp]),
+    "ssw_resample_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp]),
+    "ssw_scale_attack_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(ScaleJob), _sz, _vp]),
     "ssw_ssim_rgb8": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64p, _vp]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
                                                            _f32p, _f32p, _u32p, _f32p, _u32p]),

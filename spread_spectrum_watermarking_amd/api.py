@@ -1428,6 +1428,113 @@ def filter(images, filters, ctx: Optional[Context] = None) -> list:
     return _attack_every(ctx, frames, fs, _FILTER_ATTACK)
 
 
+def _resample_filter(filter) -> int:
+    f = L.RESAMPLE_FILTERS.get(filter.lower()) if isinstance(filter, str) else None
+    if f is None:
+        raise ValueError(f"unknown resample filter {filter!r} (one of {', '.join(L.RESAMPLE_FILTERS)})")
+    return f
+
+
+def _side(v, what: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= L.RESAMPLE_SIDE_MAX:
+        raise ValueError(f"{what}: a side is an integer 1 .. {L.RESAMPLE_SIDE_MAX}")
+    return int(v)
+
+
+def resample(images, size, filter="bicubic", ctx: Optional[Context] = None) -> list:
+    """Every image as PIL.Image.resize(size, filter) makes it, byte for byte (ssw_resample_rgb8; include/ssw.h states the
+    definition).  images: 8-bit [H, W, 3] of one size; size: (nw, nh), sides 1 .. 65535; filter: "box", "bilinear", "bicubic" or
+    "lanczos".  Returns one u8 [nh, nw, 3] frame per image.  The frames go in groups whose inputs and results are at most
+    256 MiB on the device."""
+    frames, f = _frames_u8(images, "resample"), _resample_filter(filter)
+    nw, nh = (_side(v, "resample") for v in size)
+    if not frames:
+        return []
+    ctx = ctx or default_context()
+    h, w = frames[0].shape[:2]
+    fb, ob, n, out = w * h * 3, nw * nh * 3, len(frames), []
+    per = max(1, UPLOAD_GROUP_BYTES // (fb + ob))
+    with _owned(ctx) as alloc:
+        dev_i, dev_o = alloc(min(per, n) * fb), alloc(min(per, n) * ob)
+        for g0 in range(0, n, per):
+            g = frames[g0:g0 + per]
+            _upload_frames(ctx, dev_i, g)
+            check(ctx._lib.ssw_resample_rgb8(ctx.handle, dev_i.ptr, len(g), w, h, nw, nh, f, dev_o.ptr), "ssw_resample_rgb8")
+            out += list(dev_o.to_host(np.uint8, (len(g), nh, nw, 3)))
+    return out
+
+
+@dataclass(frozen=True)
+class Scale:
+    """One attack of ssw_scale_attack_rgb8: the copy as PIL.Image.resize makes its thumbnail, brought back to the original's
+    size as `trace` brings back a suspect of another size.  `Scale(factor, filter)`: the thumbnail has `size(w, h)`, sides
+    rounded half up, 0 < factor <= 4; `Scale.to(nw, nh, filter)`: a thumbnail of that size whatever the frame's.  filter: "box",
+    "bilinear", "bicubic" (the default) or "lanczos".  `label` names it in reports: "scale 0.5 bicubic", "scale 640x360 lanczos"."""
+    factor: float = 0.0
+    filter: str = "bicubic"
+    nw: int = 0
+    nh: int = 0
+
+    def __post_init__(self):
+        _resample_filter(self.filter)
+        object.__setattr__(self, "filter", self.filter.lower())
+        if self.nw or self.nh:
+            if self.factor:
+                raise ValueError("Scale: a factor or a size, not both")
+            object.__setattr__(self, "nw", _side(self.nw, "Scale"))
+            object.__setattr__(self, "nh", _side(self.nh, "Scale"))
+            return
+        f = self.factor
+        if isinstance(f, bool) or not isinstance(f, (int, float, np.integer, np.floating)):
+            raise ValueError("Scale: the factor is a number")
+        if not (math.isfinite(f) and 0.0 < f <= L.SCALE_FACTOR_MAX):
+            raise ValueError(f"Scale: a factor above 0 and at most {L.SCALE_FACTOR_MAX:g}")
+        object.__setattr__(self, "factor", float(f))
+
+    @classmethod
+    def to(cls, nw, nh, filter="bicubic") -> "Scale":
+        return cls(0.0, filter, _side(nw, "Scale"), _side(nh, "Scale"))
+
+    def size(self, w: int, h: int) -> Tuple[int, int]:
+        if self.nw:
+            return self.nw, self.nh
+        return max(1, int(w * self.factor + 0.5)), max(1, int(h * self.factor + 0.5))
+
+    @property
+    def label(self) -> str:
+        return f"scale {self.nw}x{self.nh} {self.filter}" if self.nw else f"scale {self.factor:g} {self.filter}"
+
+    def job(self, frame: int, w: int, h: int) -> L.ScaleJob:
+        nw, nh = self.size(w, h)
+        return L.ScaleJob(frame, nw, nh, L.RESAMPLE_FILTERS[self.filter])
+
+
+def _scales(scales, what: str) -> list:
+    sc = list(scales)
+    if any(not isinstance(s, Scale) for s in sc):
+        raise ValueError(f"{what}: scales are made with Scale(factor, filter) or Scale.to(nw, nh, filter)")
+    return sc
+
+
+def _scale_attack(w: int, h: int) -> tuple:
+    """The attack of `_attack_every` and of the report's stage for frames of w x h: a scale job needs the frame's size"""
+    return ("ssw_scale_attack_rgb8", L.ScaleJob, lambda frame, s: s.job(frame, w, h))
+
+
+def scale_attack(images, scales, ctx: Optional[Context] = None) -> list:
+    """Every image after every scale attack (ssw_scale_attack_rgb8): shrunk or enlarged as Pillow does it, then brought back to
+    its size as `trace` would.  images: 8-bit [H, W, 3] of one size; scales: `Scale` objects.  Returns
+    [len(images)][len(scales)] u8 [H, W, 3] frames.  The jobs go in groups whose frames and results are at most 256 MiB on the
+    device."""
+    frames, sc = _frames_u8(images, "scale_attack"), _scales(scales, "scale_attack")
+    if not frames or not sc:
+        return [[] for _ in frames]
+    h, w = frames[0].shape[:2]
+    if any(max(s.size(w, h)) > L.RESAMPLE_SIDE_MAX for s in sc):
+        raise ValueError(f"scale_attack: a thumbnail's side is at most {L.RESAMPLE_SIDE_MAX}")
+    return _attack_every(ctx, frames, sc, _scale_attack(w, h))
+
+
 @dataclass
 class Collusion:
     """What tracing made of one forgery: `size` colluders (the first `size` copies) pooled with `method`.  weakest_colluder: the
@@ -1473,16 +1580,33 @@ class FilterResult:
 
 
 @dataclass
+class ScaleResult:
+    """What tracing made of the marked copies after the scale attack `scale` (a `Scale.label`) with thumbnails of `size`
+    (nw, nh); the other fields as in `JpegResult`."""
+    scale: str
+    size: Tuple[int, int]
+    survived: int
+    weakest_own: float
+    strongest_innocent: float
+    accused: int
+    psnr_min: float
+    psnr_max: float
+    ssim_min: float = math.nan
+    ssim_max: float = math.nan
+
+
+@dataclass
 class StrengthRow:
     """`strength_report` for one alpha: the `Quality` of every copy, one `Collusion` per (method, size), methods outermost, and
     one `JpegResult` per JPEG quality asked for; ssim: the `Ssim` of every copy when the report was asked for it; filters: one
-    `FilterResult` per filter asked for."""
+    `FilterResult` per filter asked for; scales: one `ScaleResult` per scale asked for."""
     alpha: float
     quality: list
     collusions: list
     jpeg: list = field(default_factory=list)
     ssim: list = field(default_factory=list)
     filters: list = field(default_factory=list)
+    scales: list = field(default_factory=list)
 
     def collusion(self, method: str, size: int) -> Collusion:
         return next(c for c in self.collusions if (c.method, c.size) == (method, size))
@@ -1514,10 +1638,14 @@ def _filter_result(label: str, sims: np.ndarray, qualities: list, threshold: flo
     return FilterResult(label, *_attack_fold(sims, qualities, threshold, ssims))
 
 
+def _scale_result(label_size: tuple, sims: np.ndarray, qualities: list, threshold: float, ssims=()) -> ScaleResult:
+    return ScaleResult(*label_size, *_attack_fold(sims, qualities, threshold, ssims))
+
+
 def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                     methods=("average", "median", "min", "max", "minmax", "mosaic"), threshold: float = 6.0,
                     config: Optional[WriteConfig] = None, seed=None, ctx: Optional[Context] = None, jpeg=(), ssim: bool = False,
-                    filters=()) -> list:
+                    filters=(), scales=()) -> list:
     """The two questions to answer before a copy ships, per insertion strength: how visible is the mark, and how many
     recipients must pool their copies before tracing fails?  For each alpha (`config` with its alpha replaced; the default
     Option2 + Energy): `copies` marked copies of the 8-bit `image` (ssw_fingerprint_embed_rgb8), their distance from it
@@ -1532,8 +1660,10 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     filters: `Filter` objects; per alpha every copy goes through every filter (one ssw_filter_rgb8 call, filter-major), all
     results are traced against all marks and measured against the original (one more ssw_fingerprint_trace_rgb8 and
     ssw_quality_rgb8 call, and one ssw_ssim_rgb8 with `ssim`): one `FilterResult` per filter in `StrengthRow.filters`.
+    scales: `Scale` objects; the same after the filters with one ssw_scale_attack_rgb8 call, scale-major: one `ScaleResult` per
+    scale in `StrengthRow.scales` -- whether `trace` still names the recipient of a thumbnail that Pillow made.
     Returns one `StrengthRow` per alpha."""
-    jq, fl = _jpeg_qualities(jpeg, "strength_report"), _filters(filters, "strength_report")
+    jq, fl, sc = _jpeg_qualities(jpeg, "strength_report"), _filters(filters, "strength_report"), _scales(scales, "strength_report")
     img = _frames_of_side([image], "strength_report", "a JPEG attack", L.JPEG_MIN_SIDE if jq else 0)[0]
     if ssim:
         _frames_of_side([img], "strength_report", "SSIM", L.SSIM_MIN_SIDE)
@@ -1582,8 +1712,8 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
         dev_img, dev_marks = _upload_frames(ctx, alloc(img.nbytes), [img]), _upload_frames(ctx, alloc(marks.nbytes), [marks])
         dev_copies, dev_stats = alloc(copies * fb), alloc(copies * 8 * L.QUALITY_STATS)
         dev_forged, dev_ext, dev_sims = alloc(max(nf, 1) * fb), alloc(max(nf * k, 1) * 4), alloc(max(nf * copies, 1) * 4)
-        jpeg_stage, filter_stage = stage(_JPEG_ATTACK, jq), stage(_FILTER_ATTACK, fl)
-        dev_ssim = alloc(max(copies, jpeg_stage[2], filter_stage[2]) * 8 * L.SSIM_STATS) if ssim else None
+        jpeg_stage, filter_stage, scale_stage = stage(_JPEG_ATTACK, jq), stage(_FILTER_ATTACK, fl), stage(_scale_attack(w, h), sc)
+        dev_ssim = alloc(max(copies, jpeg_stage[2], filter_stage[2], scale_stage[2]) * 8 * L.SSIM_STATS) if ssim else None
         for alpha in alphas:
             cfg = L.Config(config.ordering.tag, config.insertion.tag, float(alpha), config.precision)
             check(lib.ssw_fingerprint_embed_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, w, h, dev_marks.ptr, copies, k, dev_copies.ptr, None),
@@ -1602,6 +1732,8 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                 rows[-1].jpeg = attacked(cfg, jpeg_stage, jq, _jpeg_result)
             if fl:
                 rows[-1].filters = attacked(cfg, filter_stage, [f.label for f in fl], _filter_result)
+            if sc:
+                rows[-1].scales = attacked(cfg, scale_stage, [(s.label, s.size(w, h)) for s in sc], _scale_result)
     return rows
 
 

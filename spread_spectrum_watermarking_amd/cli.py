@@ -29,14 +29,15 @@
         -> `identify` for every suspect in one call, then the trace above once per original that was named, with the marks
            file the catalogue holds for it; every record gains an "Original:" line
     python -m spread_spectrum_watermarking_amd.cli strength <file> --alpha 0.02 0.05 0.1 [-n 1000] [--copies 8] [--collude 2 4]
-            [--method average median min max minmax mosaic] [--jpeg 90 75 50] [--filter blur:1.5 median unsharp:2,150,3] [--ssim]
+            [--method average median min max minmax mosaic] [--jpeg 90 75 50] [--filter blur:1.5 median unsharp:2,150,3] [--scale 0.5 0.25:lanczos 640x360:bilinear] [--ssim]
             [--similarity-exceed 6.0] [--json]
         -> before a copy ships: per alpha the PSNR range of the marked copies (with --ssim also their mean SSIM and the worst
            8 x 8 window), and per collusion method and coalition size
            how many of the colluders a trace of their forgery still finds, the weakest colluder's and the strongest innocent
            recipient's similarity; with --jpeg, per quality what a trace still finds in every copy after it was saved as a
            JPEG; with --filter the same after a Gaussian blur (blur:RADIUS), an unsharp mask (unsharp[:RADIUS[,PERCENT[,THRESHOLD]]])
-           or a 3 x 3 median (median), as Pillow's filters of those names do them; everything stays on the GPU between the original going up and the numbers coming down
+           or a 3 x 3 median (median), as Pillow's filters of those names do them; with --scale the same after the copy was
+           scaled as Pillow's Image.resize does it (FACTOR[:FILTER] or WIDTHxHEIGHT[:FILTER]) and brought back to size; everything stays on the GPU between the original going up and the numbers coming down
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -51,7 +52,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from ._lib import COLLUDE_METHODS
-from .api import (IDENTIFY_MAX_DISTANCE, Catalogue, Filter, Locate, MarkBuf, Placement, Reader, Tester, TraceResult, Writer, identify, locate,
+from .api import (IDENTIFY_MAX_DISTANCE, Catalogue, Filter, Locate, MarkBuf, Placement, Reader, Scale, Tester, TraceResult, Writer, identify, locate,
                   strength_report)
 from .storage import Configuration, DescribedWatermark, Version1Storage
 
@@ -73,6 +74,20 @@ def _filter_arg(text: str) -> Filter:
     except ValueError as e:
         raise argparse.ArgumentTypeError(f"{text!r}: {e}") from e
     raise argparse.ArgumentTypeError(f"{text!r}: blur:RADIUS, unsharp[:RADIUS[,PERCENT[,THRESHOLD]]] or median")
+
+
+def _scale_arg(text: str) -> Scale:
+    """FACTOR[:FILTER] | WIDTHxHEIGHT[:FILTER]"""
+    what, colon, name = text.partition(":")
+    try:
+        if colon and not name:
+            raise ValueError("a filter's name after the colon")
+        if "x" in what:
+            nw, _, nh = what.partition("x")
+            return Scale.to(int(nw), int(nh), name or "bicubic")
+        return Scale(float(what), name or "bicubic")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"{text!r}: FACTOR[:FILTER] or WIDTHxHEIGHT[:FILTER] ({e})") from e
 
 
 def _rust_f32(x: float) -> str:
@@ -262,6 +277,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--filter", type=_filter_arg, nargs="+", default=[], metavar="FILTER", dest="filters",
                    help="Also put every copy through these filters and trace what is left: blur:RADIUS (0 < RADIUS <= 8), "
                         "unsharp[:RADIUS[,PERCENT[,THRESHOLD]]] (default 2,150,3), median.")
+    g.add_argument("--scale", type=_scale_arg, nargs="+", default=[], metavar="SCALE", dest="scales",
+                   help="Also scale every copy as Pillow's Image.resize does, bring it back to size and trace what is left: "
+                        "FACTOR[:FILTER] (0 < FACTOR <= 4) or WIDTHxHEIGHT[:FILTER]; FILTER box, bilinear, bicubic (default) or lanczos.")
     g.add_argument("--ssim", action="store_true", help="Also report the structural similarity (SSIM) of every copy and its worst window.")
     g.add_argument("--json", action="store_true", help="Print the report as one JSON document.")
     return p
@@ -403,9 +421,10 @@ def cmd_identify(args, out=sys.stdout) -> int:
 def cmd_strength(args, out=None) -> int:
     out = out or sys.stdout                                  # looked up at the call: a caller may have redirected it
     orig = _open_image(args.file)
+    scales = getattr(args, "scales", [])
     try:
         rows = strength_report(orig, args.alpha, k=args.length, copies=args.copies, sizes=args.collude, methods=args.method,
-                               threshold=args.similarity_exceed, jpeg=args.jpeg, ssim=args.ssim, filters=args.filters)
+                               threshold=args.similarity_exceed, jpeg=args.jpeg, ssim=args.ssim, filters=args.filters, scales=scales)
     except ValueError as e:
         raise SystemExit(str(e)) from e
     if args.json:
@@ -425,6 +444,8 @@ def cmd_strength(args, out=None) -> int:
         for d, r in zip(doc, rows):
             for c, s in zip(d["copies"], r.ssim):
                 c.update({"ssim": s.mean, "ssim_worst": s.worst_value, "ssim_worst_at": list(s.worst_position)})
+            if scales:                                       # the key is there when --scale was given
+                d["scales"] = [dict(attack("scale", a), size=list(a.size)) for a in r.scales]
         print(json.dumps(doc), file=out)
         return 0
     for r in rows:
@@ -443,7 +464,8 @@ def cmd_strength(args, out=None) -> int:
             accused = f", {c.accused} innocent accused" if c.accused else ""
             print(f"  {c.method} of {c.size}: found {c.found}/{c.size}, weakest colluder {c.weakest_colluder:.2f}, "
                   f"strongest innocent {innocent}{accused}", file=out)
-        for label, a in [(f"jpeg {j.quality}", j) for j in r.jpeg] + [(f.filter, f) for f in r.filters]:
+        for label, a in ([(f"jpeg {j.quality}", j) for j in r.jpeg] + [(f.filter, f) for f in r.filters] +
+                         [(f"{a.scale} ({a.size[0]}x{a.size[1]})", a) for a in r.scales]):
             innocent = "none" if a.strongest_innocent != a.strongest_innocent else f"{a.strongest_innocent:.1f}"
             accused = f", {a.accused} innocent accused" if a.accused else ""
             ssim = f", ssim {a.ssim_min:.2f} .. {a.ssim_max:.2f}" if r.ssim else ""
