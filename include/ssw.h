@@ -872,6 +872,80 @@ int ssw_resample_rgb8(ssw_ctx* ctx, const uint8_t* dev_in, size_t n_frames, size
 typedef struct ssw_scale_job { uint32_t frame; uint32_t nw; uint32_t nh; uint32_t filter; } ssw_scale_job;
 int ssw_scale_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h, const ssw_scale_job* jobs,
                           size_t n_jobs, uint8_t* dev_out);
+/* The rotation attack and its undoing: a copy that was straightened or tilted in a photo editor, and what a tracer who knows
+   the angle makes of it.  ssw_affine_rgb8 makes of n_frames frames in [h][w][3] the frames [oh][ow][3] that
+   PIL.Image.transform((ow, oh), AFFINE, m, resample, fillcolor=fill) makes of them -- exactly: Pillow evaluates the transform
+   in IEEE doubles, every operation rounded on its own (no contraction) and truncated to a byte, and the numpy restatement in
+   tests/test_rotate_cpu.py (`affine_ref`, checked there against Pillow byte for byte) is what the call equals.
+   The matrix, as PIL.Image.rotate(angle) makes it with expand=False and the default centre, in Python on the host
+   (csrc/affine_tables.hpp: rotation_matrix makes the same numbers):
+       a = -radians(angle % 360.0)
+       m = [round(cos a, 15), round(sin a, 15), 0, round(-sin a, 15), round(cos a, 15), 0]
+       cx, cy = w / 2.0, h / 2.0
+       m[2] = (m[0] * -cx + m[1] * -cy + 0.0) + cx
+       m[5] = (m[3] * -cx + m[4] * -cy + 0.0) + cy
+   The transform: for output pixel (X, Y), every operation a double operation rounded on its own, in this order.
+     1. Sample point.  xin = m0*(X+0.5) + m1*(Y+0.5) + m2 and yin = m3*(X+0.5) + m4*(Y+0.5) + m5, summed from the left.
+     2. Outside test.  If xin < 0 || xin >= w || yin < 0 || yin >= h, the pixel is `fill`.  This test comes before any
+        conversion to an integer.  (A sample point that is not a number -- the sums of a matrix with entries near the largest
+        double can be one -- is outside as well; Pillow converts it.)
+     3. Base position.  Otherwise xin -= 0.5; yin -= 0.5; x = floor(xin); y = floor(yin); dx = xin - x; dy = yin - y.
+        XC(i) = clamp(i, 0, w-1) and YC(j) = clamp(j, 0, h-1).
+     4. SSW_AFFINE_BILINEAR, per channel: L(a,b,d) = a + (b - a) * d.
+          v1 = L(in[YC(y)][XC(x)], in[YC(y)][XC(x+1)], dx)
+          v2 the same on row y+1 when 0 <= y+1 < h, otherwise v2 = v1
+          v = L(v1, v2, dy); the byte is (uint8) v, truncated, with no +0.5.
+     5. SSW_AFFINE_BICUBIC, per channel:
+          C(a,b,c,d,t): p1 = b; p2 = -a + c; p3 = 2*(a - b) + c - d; p4 = -a + b - c + d; p1 + t*(p2 + t*(p3 + t*p4))
+          r(j) = C(in[YC(j)][XC(x-1)], in[YC(j)][XC(x)], in[YC(j)][XC(x+1)], in[YC(j)][XC(x+2)], dx)
+          v1 = r(y-1); v2 = r(y) if 0 <= y < h, otherwise v1; v3 = r(y+1) if 0 <= y+1 < h, otherwise v2;
+          v4 = r(y+2) if 0 <= y+2 < h, otherwise v3; v = C(v1, v2, v3, v4, dy)
+          the byte is 0 if v <= 0, 255 if v >= 255, otherwise (uint8) v, truncated.
+   NEAREST, expand=True, another centre, `translate`, RGBA and 16-bit frames are not offered.  Pillow's own shortcuts for 0,
+   180 and (on a square frame) 90 and 270 degrees are transposes; the formula gives them the same bytes (tests/test_rotate_cpu.py).
+   The undoing is what a tracer who knows the angle would do.  F is the matrix of `angle` and B the matrix of `-angle`, both for
+   the frame's own (w, h).  A is the attacked frame: the transform by F with the job's filter and fill.  U is the transform of
+   A by B, always BICUBIC (the tracer does not know the attacker's filter).  O is the original.  The restored frame is U where
+   the mask holds and O elsewhere -- the reference's recipe for lost pixels, "complement the attacked image with the original"
+   (tests/attack_crop.rs).  The mask holds at (X, Y) when all three are true, (xin, yin) being B's sample point for (X, Y):
+     - (xin, yin) is inside;
+     - with x = floor(xin-0.5) and y = floor(yin-0.5) the footprint needs no clamping: x-1 >= 0, x+2 <= w-1, y-1 >= 0, y+2 <= h-1;
+     - the sample points that F gives the four corner pixels of that footprint, (x-1 | x+2, y-1 | y+2), are all inside.
+   Each term of the affine sum is monotone after rounding, so the corners bound every tap and no fill pixel of A is ever read
+   under the mask: the restored frame does not depend on the fill.  A job whose forward and back are both the identity
+   [1 0 0 0 1 0] (angle 0) is a copy of the frame, not a masked one.
+   ssw_rotate_attack_rgb8: dev_out[j] [h][w][3] is frame jobs[j].frame of dev_frames [n_frames][h][w][3] attacked with
+   jobs[j].forward, filter and fill, then undone with jobs[j].back over dev_base [h][w][3], the original.  ssw_unrotate_rgb8:
+   dev_out[i] is suspect jobs[i].frame of dev_suspects [n][h][w][3] undone with jobs[i].back over dev_base, the mask made with
+   jobs[i].forward; filter and fill are not read.  The undoing is one launch that writes no frame in between.  `jobs` is a HOST
+   array; a frame may occur in many jobs and in any order; consecutive jobs of one filter, fill and pair of matrices run as one
+   batch.  All three calls only enqueue on the context's stream.  The attacked frames of a batch live in the context's
+   workspace, at most 32 jobs and 64 MiB (or one job's) at a time.  No alignment is assumed of any pointer or of w * 3.  Outputs
+   must not overlap inputs.  Sides are 1 .. 65535.  The attack is timed under SSW_STAGE_CONVERT, the undoing under
+   SSW_STAGE_RESIZE; work 3 w h + 3 ow oh bytes per transform.
+   n_frames == 0, n_jobs == 0 or n == 0 is checked first: SSW_OK; SSW_ERR_BAD_ARG: a null pointer, an unknown filter,
+   frame >= n_frames (unrotate: >= n), a matrix entry that is not finite, an output that overlaps an input (nothing is enqueued
+   when any job is bad); SSW_ERR_BAD_DIMS: a side of 0 or above 65535.
+   ssw_affine_plan is host arithmetic (no context): how a transform by m of a w x h frame would be launched -- *lds_form 1 when
+   the box of source pixels of a tile of 32 x 8 output pixels (at most *box_w x *box_h; either may be null) is staged in LDS, 0
+   when the taps come from global memory (a strong shrink or shear). */
+typedef enum ssw_affine_filter { SSW_AFFINE_BILINEAR = 0, SSW_AFFINE_BICUBIC = 1 } ssw_affine_filter;
+int ssw_affine_rgb8(ssw_ctx* ctx, const uint8_t* dev_in, size_t n_frames, size_t w, size_t h, size_t ow, size_t oh, const double* m,
+                    int filter, const uint8_t* fill, uint8_t* dev_out);
+typedef struct ssw_rotate_job { uint32_t frame, filter; uint8_t fill[4]; double forward[6], back[6]; } ssw_rotate_job;
+int ssw_rotate_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h,
+                           const ssw_rotate_job* jobs, size_t n_jobs, uint8_t* dev_out);
+int ssw_unrotate_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const uint8_t* dev_suspects, size_t n, size_t w, size_t h,
+                      const ssw_rotate_job* jobs, uint8_t* dev_out);
+/* How much of a w x h frame an undoing takes from the rotated copy: host_kept[i] (a HOST array of n) is the number of pixels
+   under the mask of jobs[i] (forward and back are read; an identity job: all w h).  Counted on the device, one launch per job;
+   waits for the context's stream.  n == 0: SSW_OK; SSW_ERR_BAD_ARG: a null pointer, a matrix entry that is not finite;
+   SSW_ERR_BAD_DIMS: a side of 0 or above 65535. */
+int ssw_unrotate_kept(ssw_ctx* ctx, size_t w, size_t h, const ssw_rotate_job* jobs, size_t n, uint64_t* host_kept);
+int ssw_affine_plan(size_t w, size_t h, const double* m, int* lds_form, uint32_t* box_w, uint32_t* box_h);
+/* PIL.Image.rotate(angle)'s matrix for a w x h frame as stated above, number for number what Python makes (host arithmetic, no
+   context; tests/test_rotate_cpu.py compares 64 angles bit for bit).  SSW_ERR_BAD_ARG: m null or an angle that is not finite. */
+int ssw_rotation_matrix(double angle, size_t w, size_t h, double* m);
 
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,

@@ -558,6 +558,80 @@ inline std::vector<ImageRgb8> scale_attack(Context& ctx, const std::vector<const
     return detail::frames_through_jobs(ctx, frames, jb, "scale_attack", ssw_scale_attack_rgb8);
 }
 
+// The filters of Pillow's Image.rotate / Image.transform that ssw_affine_rgb8 offers
+enum class AffineFilter : uint32_t { Bilinear = SSW_AFFINE_BILINEAR, Bicubic = SSW_AFFINE_BICUBIC };
+using Matrix = std::array<double, 6>;
+// PIL.Image.rotate(angle)'s matrix for a w x h frame (ssw_rotation_matrix)
+inline Matrix rotation_matrix(double angle, size_t w, size_t h) {
+    Matrix m{};
+    check(ssw_rotation_matrix(angle, w, h, m.data()), "rotation_matrix");
+    return m;
+}
+// ssw_affine_rgb8 on host images of one size: every image as PIL.Image.transform((ow, oh), AFFINE, m, filter, fillcolor=fill)
+// makes it, byte for byte; include/ssw.h states the definition.
+inline std::vector<ImageRgb8> affine(Context& ctx, const std::vector<const ImageRgb8*>& frames, size_t ow, size_t oh, const Matrix& m,
+                                     AffineFilter filter = AffineFilter::Bicubic, const std::array<uint8_t, 3>& fill = {0, 0, 0}) {
+    if (frames.empty()) throw Error(SSW_ERR_BAD_ARG, "affine");
+    const size_t n = frames.size(), w = frames[0]->width, h = frames[0]->height, ob = ow * oh * 3;
+    detail::DeviceFrames dev(ctx.get(), n * w * h * 3, "affine"), made(ctx.get(), n * ob, "affine");
+    dev.put(frames, w, h, "affine");
+    check(ssw_affine_rgb8(ctx.get(), dev.p, n, w, h, ow, oh, m.data(), (int)filter, fill.data(), made.p), "affine");
+    std::vector<ImageRgb8> out(n, ImageRgb8(ow, oh));
+    for (size_t i = 0; i < n; ++i) check(ssw_copy_to_host(ctx.get(), out[i].data.data(), made.p + i * ob, ob), "affine");
+    return out;
+}
+// every image as PIL.Image.rotate(angle, filter, fillcolor=fill) makes it
+inline std::vector<ImageRgb8> rotate(Context& ctx, const std::vector<const ImageRgb8*>& frames, double angle, AffineFilter filter = AffineFilter::Bicubic,
+                                     const std::array<uint8_t, 3>& fill = {0, 0, 0}) {
+    if (frames.empty()) throw Error(SSW_ERR_BAD_ARG, "rotate");
+    return affine(ctx, frames, frames[0]->width, frames[0]->height, rotation_matrix(angle, frames[0]->width, frames[0]->height), filter, fill);
+}
+// One result of wm::rotate_attack / wm::unrotate: a frame (an index into the images), the angle it is (or was) turned by, and
+// the filter and fill of the attack
+struct Rotate {
+    uint32_t frame = 0;
+    double angle = 0.0;
+    AffineFilter filter = AffineFilter::Bicubic;
+    std::array<uint8_t, 3> fill{{0, 0, 0}};
+    ssw_rotate_job job(size_t w, size_t h) const {
+        ssw_rotate_job j{};
+        j.frame = frame; j.filter = (uint32_t)filter;
+        for (int c = 0; c < 3; ++c) j.fill[c] = fill[c];
+        const Matrix f = rotation_matrix(angle, w, h), b = rotation_matrix(-angle, w, h);
+        for (int i = 0; i < 6; ++i) { j.forward[i] = f[i]; j.back[i] = b[i]; }
+        return j;
+    }
+};
+// ssw_rotate_attack_rgb8 on host images of one size: per job that frame turned as Pillow's Image.rotate does it, then turned
+// back by the known angle and completed with `original` where the turns lost pixels; include/ssw.h states both steps.
+inline std::vector<ImageRgb8> rotate_attack(Context& ctx, const ImageRgb8& original, const std::vector<const ImageRgb8*>& frames,
+                                            const std::vector<Rotate>& jobs) {
+    const size_t w = original.width, h = original.height;
+    detail::DeviceFrames base(ctx.get(), w * h * 3, "rotate_attack");
+    base.put({&original}, w, h, "rotate_attack");
+    std::vector<ssw_rotate_job> jb(jobs.size());
+    for (size_t i = 0; i < jb.size(); ++i) jb[i] = jobs[i].job(w, h);
+    const auto call = [&](ssw_ctx* c, const uint8_t* dev, size_t n, size_t fw, size_t fh, const ssw_rotate_job* j, size_t m, uint8_t* out) {
+        return ssw_rotate_attack_rgb8(c, base.p, dev, n, fw, fh, j, m, out);
+    };
+    return detail::frames_through_jobs(ctx, frames, jb, "rotate_attack", call);
+}
+// ssw_unrotate_rgb8 on host images of the original's size: suspect i turned back by angles[i] and completed with `original`:
+// what tracing a copy that was turned by a known angle extracts from.
+inline std::vector<ImageRgb8> unrotate(Context& ctx, const ImageRgb8& original, const std::vector<const ImageRgb8*>& suspects,
+                                       const std::vector<double>& angles) {
+    if (angles.size() != suspects.size()) throw Error(SSW_ERR_BAD_ARG, "unrotate");
+    const size_t w = original.width, h = original.height;
+    detail::DeviceFrames base(ctx.get(), w * h * 3, "unrotate");
+    base.put({&original}, w, h, "unrotate");
+    std::vector<ssw_rotate_job> jb(angles.size());
+    for (size_t i = 0; i < jb.size(); ++i) jb[i] = Rotate{(uint32_t)i, angles[i]}.job(w, h);
+    const auto call = [&](ssw_ctx* c, const uint8_t* dev, size_t n, size_t fw, size_t fh, const ssw_rotate_job* j, size_t, uint8_t* out) {
+        return ssw_unrotate_rgb8(c, base.p, dev, n, fw, fh, j, out);
+    };
+    return detail::frames_through_jobs(ctx, suspects, jb, "unrotate", call);
+}
+
 // The originals someone owns, as signatures: which of them is a suspect a copy of?  The stage in front of locate / Reader::trace
 // (ssw_signature_match; include/ssw.h states the definition and what it cannot find: cut-outs, mirrored and turned copies).
 // The signatures stay on the device between match calls and go up again only after an add.

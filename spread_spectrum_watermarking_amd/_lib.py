@@ -99,6 +99,17 @@ RESAMPLE_BOX, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC, RESAMPLE_LANCZOS = range(4)
 RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2, "lanczos": 3}
 RESAMPLE_SIDE_MAX = 65535
 SCALE_FACTOR_MAX = 4.0       # api.Scale: the largest factor
+
+
+class RotateJob(C.Structure):
+    """ssw_rotate_job (include/ssw.h): one result of ssw_rotate_attack_rgb8 / ssw_unrotate_rgb8 -- a frame of the call, the
+    ssw_affine_filter and fill of the attack, the matrix of the angle and the matrix of its negative."""
+    _fields_ = [("frame", C.c_uint32), ("filter", C.c_uint32), ("fill", C.c_uint8 * 4), ("forward", C.c_double * 6), ("back", C.c_double * 6)]
+
+
+# ssw_affine_filter, by the names the Python surface and the CLI accept (Pillow's)
+AFFINE_BILINEAR, AFFINE_BICUBIC = range(2)
+AFFINE_FILTERS = {"bilinear": 0, "bicubic": 1}
 FILTER_RADIUS_MAX = 8.0      # keeps the box radius of a blur pass at 7 or below
 QUALITY_STATS = 6            # ssw_quality_rgb8: u64 per copy -- SSE of R, G, B, SSE of the luma, changed bytes, max |d|
 SSIM_MIN_SIDE = 8            # ssw_ssim_rgb8 refuses smaller frames
@@ -204,6 +215,12 @@ SIGNATURES = {
     "ssw_filter_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(FilterJob), _sz, _vp]),
     "ssw_resample_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp]),
     "ssw_scale_attack_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(ScaleJob), _sz, _vp]),
+    "ssw_affine_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_uint8), _vp]),
+    "ssw_rotate_attack_rgb8": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, C.POINTER(RotateJob), _sz, _vp]),
+    "ssw_unrotate_rgb8": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, C.POINTER(RotateJob), _vp]),
+    "ssw_unrotate_kept": (C.c_int, [_vp, _sz, _sz, C.POINTER(RotateJob), _sz, _u64p]),
+    "ssw_affine_plan": (C.c_int, [_sz, _sz, C.POINTER(C.c_double), C.POINTER(C.c_int), _u32p, _u32p]),
+    "ssw_rotation_matrix": (C.c_int, [C.c_double, _sz, _sz, C.POINTER(C.c_double)]),
     "ssw_ssim_rgb8": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64p, _vp]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
                                                            _f32p, _f32p, _u32p, _f32p, _u32p]),

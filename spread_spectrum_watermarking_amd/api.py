@@ -522,10 +522,12 @@ class Reader:
         placements: None (every suspect has the original's shape, as before), or one entry per suspect, a `Placement` or
         None; suspects are then [h][w][3] or [h][w][4] arrays of any size and are restored on the device first (see
         `restore` for the rule).  `base`: the original's 8-bit pixels again -- the reader keeps the plane and the list,
-        not the image -- needed as soon as a suspect has an alpha channel or covers less than the whole frame."""
+        not the image -- needed as soon as a suspect has an alpha channel, covers less than the whole frame or is `Rotated`."""
         if not self.is_base:
             raise SswError(L.SSW_ERR_NOT_BASE, "Reader::trace")
         if placements is not None:
+            if any(isinstance(p, Rotated) for p in placements):          # turned copies: one unrotate call
+                suspects, placements = _undo_rotated(base, suspects, placements, self._ctx)
             if any(isinstance(p, Locate) for p in placements):           # cut-outs at an unknown position: one locate call
                 placements, _ = _resolve_locates(base, suspects, placements, self._ctx)
             arrs, ptrs, pl = _placed_suspects(suspects, placements, self.width, self.height)
@@ -789,7 +791,7 @@ def locate(base, suspects, sizes=None, ctx: Optional[Context] = None) -> list:
     cut-out is not supported).  sizes: None, or per suspect a `Locate(w, h)` / (w, h) pair / None -- the size the cut-out
     had in the original when it was scaled afterwards --, or a `Locate(widths=(lo, hi))` / `Locate(scale=(lo, hi))` when that
     size is unknown: those entries go through the scale ladder (ssw_locate_scaled_rgb8; aspect ratio kept, the smaller side at
-    least 32) and `Located.size` says what was found.  Returns one `Located` per suspect.  Rotation is out of scope, and a
+    least 32) and `Located.size` says what was found.  Returns one `Located` per suspect.  A turned cut-out is not found, and a
     cut-out of a featureless region (the cat's grey background) is ambiguous."""
     ctx = ctx or default_context()
     b = _base_rgb8(base)
@@ -907,11 +909,14 @@ def trace_many(base, suspects, marks, k: Optional[int] = None, threshold: float 
     placements: None (every suspect has the original's shape, as before), or one entry per suspect, a `Placement` or None:
     suspects of any size with 3 or 4 channels are restored on the device first (ssw_fingerprint_trace_restored_host_rgb8;
     `restore` spells out the rule and returns the frames this call extracts from).  `Locate(w, h)` entries -- cut-outs at an
-    unknown position -- are found with one `locate` call first."""
+    unknown position -- are found with one `locate` call first.  `Rotated(angle)` entries -- copies of the original's size that
+    were turned by a known angle -- are turned back with one `unrotate` call first and traced as whole frames."""
     ctx = ctx or default_context()
     config = config or ReadConfig.default()
     if placements is not None:
         b = _base_rgb8(base)
+        if any(isinstance(p, Rotated) for p in placements):
+            suspects, placements = _undo_rotated(b, suspects, placements, ctx)
         if any(isinstance(p, Locate) for p in placements):
             placements, _ = _resolve_locates(b, suspects, placements, ctx)
         arrs, ptrs, pl = _placed_suspects(suspects, placements, b.shape[1], b.shape[0])
@@ -1298,10 +1303,11 @@ def _job_groups(job_frames, fb: int) -> list:
     return groups
 
 
-def _run_jobs(ctx: Optional[Context], frames, job_frames, name: str, struct, local) -> list:
+def _run_jobs(ctx: Optional[Context], frames, job_frames, name: str, struct, local, base=None) -> list:
     """The runner of `collude`, `jpeg` and `filter`: the library call `name` (frames in, an array of `struct` jobs, one frame out
     per job) over the groups of `_job_groups`.  local(j, where): job j as a `struct` that names frame i as where[i], its place
-    among the frames its group sent up.  Returns one u8 [H, W, 3] frame per job, in order."""
+    among the frames its group sent up.  base: the original, for a call that takes it in front of the frames (the rotation
+    attack).  Returns one u8 [H, W, 3] frame per job, in order."""
     ctx = ctx or default_context()
     h, w = frames[0].shape[:2]
     fb, out = w * h * 3, []
@@ -1311,7 +1317,8 @@ def _run_jobs(ctx: Optional[Context], frames, job_frames, name: str, struct, loc
         with _owned(ctx) as alloc:
             dev_f, dev_o = alloc(len(used) * fb), alloc((g1 - g0) * fb)
             _upload_frames(ctx, dev_f, [frames[i] for i in used])
-            check(getattr(ctx._lib, name)(ctx.handle, dev_f.ptr, len(used), w, h, jobs, g1 - g0, dev_o.ptr), name)
+            lead = () if base is None else (_upload_frames(ctx, alloc(fb), [base]).ptr,)
+            check(getattr(ctx._lib, name)(ctx.handle, *lead, dev_f.ptr, len(used), w, h, jobs, g1 - g0, dev_o.ptr), name)
             out += list(dev_o.to_host(np.uint8, (g1 - g0, h, w, 3)))
     return out
 
@@ -1331,16 +1338,17 @@ def collude(copies, coalitions, ctx: Optional[Context] = None) -> list:
 
 
 # An attack on single frames: the library call, its job struct and how a job is made of (frame, parameter) -- what `jpeg`,
-# `filter` and the attack stage of `strength_report` need to know of it
+# `filter` and the attack stage of `strength_report` need to know of it; a fourth entry, True: the call takes the original in
+# front of the frames
 _JPEG_ATTACK = ("ssw_jpeg_rgb8", L.JpegJob, L.JpegJob)
 _FILTER_ATTACK = ("ssw_filter_rgb8", L.FilterJob, lambda frame, f: f.job(frame))
 
 
-def _attack_every(ctx: Optional[Context], frames, params, attack) -> list:
+def _attack_every(ctx: Optional[Context], frames, params, attack, base=None) -> list:
     """Every frame under every parameter of `attack`, jobs in frame order: [len(frames)][len(params)] u8 [H, W, 3] frames."""
-    name, struct, job = attack
+    name, struct, job = attack[:3]
     jobs = [(i, p) for i in range(len(frames)) for p in params]
-    flat = _run_jobs(ctx, frames, [(i,) for i, _ in jobs], name, struct, lambda j, where: job(where[jobs[j][0]], jobs[j][1]))
+    flat = _run_jobs(ctx, frames, [(i,) for i, _ in jobs], name, struct, lambda j, where: job(where[jobs[j][0]], jobs[j][1]), base)
     return [flat[i * len(params):(i + 1) * len(params)] for i in range(len(frames))]
 
 
@@ -1535,6 +1543,217 @@ def scale_attack(images, scales, ctx: Optional[Context] = None) -> list:
     return _attack_every(ctx, frames, sc, _scale_attack(w, h))
 
 
+# ---- the rotation attack and its undoing (include/ssw.h: ssw_affine_rgb8, ssw_rotate_attack_rgb8, ssw_unrotate_rgb8) ---------
+def _affine_filter(filter) -> int:
+    f = L.AFFINE_FILTERS.get(filter.lower()) if isinstance(filter, str) else None
+    if f is None:
+        raise ValueError(f"unknown affine filter {filter!r} (one of {', '.join(L.AFFINE_FILTERS)})")
+    return f
+
+
+def _fill(fill, what: str) -> tuple:
+    f = tuple(fill)
+    if len(f) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255 for v in f):
+        raise ValueError(f"{what}: the fill is three integers 0 .. 255")
+    return tuple(int(v) for v in f)
+
+
+def _angle(angle, what: str) -> float:
+    if isinstance(angle, bool) or not isinstance(angle, (int, float, np.integer, np.floating)) or not math.isfinite(angle):
+        raise ValueError(f"{what}: the angle is a finite number of degrees")
+    return float(angle)
+
+
+def rotation_matrix(angle: float, w: int, h: int) -> list:
+    """The matrix PIL.Image.rotate(angle) hands to Image.transform for a w x h frame (expand=False, the default centre), number
+    for number (include/ssw.h states it; csrc/affine_tables.hpp makes the same in C++)."""
+    a = -math.radians(angle % 360.0)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    cx, cy = w / 2.0, h / 2.0
+    m[2] = (m[0] * -cx + m[1] * -cy + 0.0) + cx
+    m[5] = (m[3] * -cx + m[4] * -cy + 0.0) + cy
+    return m
+
+
+def affine(images, size, matrix, filter="bicubic", fill=(0, 0, 0), ctx: Optional[Context] = None) -> list:
+    """Every image as PIL.Image.transform(size, AFFINE, matrix, filter, fillcolor=fill) makes it, byte for byte (ssw_affine_rgb8;
+    include/ssw.h states the definition).  images: 8-bit [H, W, 3] of one size; size: (ow, oh), sides 1 .. 65535; matrix: six
+    finite numbers; filter: "bilinear" or "bicubic".  Returns one u8 [oh, ow, 3] frame per image.  The frames go in groups whose
+    inputs and results are at most 256 MiB on the device."""
+    frames, f, fl = _frames_u8(images, "affine"), _affine_filter(filter), _fill(fill, "affine")
+    ow, oh = (_side(v, "affine") for v in size)
+    m = [float(v) for v in matrix]
+    if len(m) != 6 or not all(math.isfinite(v) for v in m):
+        raise ValueError("affine: the matrix is six finite numbers")
+    if not frames:
+        return []
+    ctx = ctx or default_context()
+    h, w = frames[0].shape[:2]
+    fb, ob, n, out = w * h * 3, ow * oh * 3, len(frames), []
+    per = max(1, UPLOAD_GROUP_BYTES // (fb + ob))
+    cm, cf = (C.c_double * 6)(*m), (C.c_uint8 * 3)(*fl)
+    with _owned(ctx) as alloc:
+        dev_i, dev_o = alloc(min(per, n) * fb), alloc(min(per, n) * ob)
+        for g0 in range(0, n, per):
+            g = frames[g0:g0 + per]
+            _upload_frames(ctx, dev_i, g)
+            check(ctx._lib.ssw_affine_rgb8(ctx.handle, dev_i.ptr, len(g), w, h, ow, oh, cm, f, cf, dev_o.ptr), "ssw_affine_rgb8")
+            out += list(dev_o.to_host(np.uint8, (len(g), oh, ow, 3)))
+    return out
+
+
+def rotate(images, angle, filter="bicubic", fill=(0, 0, 0), ctx: Optional[Context] = None) -> list:
+    """Every image as PIL.Image.rotate(angle, filter, fillcolor=fill) makes it, byte for byte: `affine` with `rotation_matrix`."""
+    frames = _frames_u8(images, "rotate")
+    if not frames:
+        return []
+    h, w = frames[0].shape[:2]
+    return affine(frames, (w, h), rotation_matrix(_angle(angle, "rotate"), w, h), filter, fill, ctx)
+
+
+@dataclass(frozen=True)
+class Rotate:
+    """One attack of ssw_rotate_attack_rgb8: the copy as PIL.Image.rotate(angle, filter) makes it, turned back by the known
+    angle and completed with the original as `trace` does it for a `Rotated(angle)` suspect.  angle: degrees counter-clockwise,
+    as Pillow's; filter: "bilinear" or "bicubic" (the default).  `label` names it in reports: "rotate 0.5 bicubic"."""
+    angle: float
+    filter: str = "bicubic"
+
+    def __post_init__(self):
+        _affine_filter(self.filter)
+        object.__setattr__(self, "filter", self.filter.lower())
+        object.__setattr__(self, "angle", _angle(self.angle, "Rotate"))
+
+    @property
+    def label(self) -> str:
+        return f"rotate {self.angle:g} {self.filter}"
+
+    def job(self, frame: int, w: int, h: int, fill=(0, 0, 0)) -> L.RotateJob:
+        return L.RotateJob(frame, L.AFFINE_FILTERS[self.filter], (C.c_uint8 * 4)(*fill, 0), (C.c_double * 6)(*rotation_matrix(self.angle, w, h)),
+                           (C.c_double * 6)(*rotation_matrix(-self.angle, w, h)))
+
+    def kept(self, w: int, h: int) -> float:
+        """The share of a w x h frame's pixels that the undoing takes from the rotated copy (the mask of include/ssw.h); the
+        others are the original's.  Host arithmetic on the frame's geometry, a band of rows at a time."""
+        F, B = rotation_matrix(self.angle, w, h), rotation_matrix(-self.angle, w, h)
+        if F == [1.0, 0.0, 0.0, 0.0, 1.0, 0.0] and B == F:
+            return 1.0
+
+        def point(m, X, Y):
+            return m[0] * (X + 0.5) + m[1] * (Y + 0.5) + m[2], m[3] * (X + 0.5) + m[4] * (Y + 0.5) + m[5]
+
+        def inside(x, y):
+            return (x >= 0.0) & (x < w) & (y >= 0.0) & (y < h)
+
+        count, X = 0, np.arange(w, dtype=np.float64)[None, :]
+        for y0 in range(0, h, 256):
+            Y = np.arange(y0, min(y0 + 256, h), dtype=np.float64)[:, None]
+            xin, yin = point(B, X, Y)
+            x, y = np.floor(xin - 0.5), np.floor(yin - 0.5)
+            keep = inside(xin, yin) & (x - 1 >= 0) & (x + 2 <= w - 1) & (y - 1 >= 0) & (y + 2 <= h - 1)
+            for cx in (x - 1, x + 2):
+                for cy in (y - 1, y + 2):
+                    keep &= inside(*point(F, cx, cy))
+            count += int(keep.sum())
+        return count / (w * h)
+
+
+@dataclass(frozen=True)
+class Rotated:
+    """A placement entry that says "this suspect is the original's frame turned by `angle` degrees" (counter-clockwise, as
+    PIL.Image.rotate(angle) does it): it is turned back on the device (ssw_unrotate_rgb8) and traced as a whole frame.  The
+    suspect has the original's size and 3 channels.  Finding the angle is not built."""
+    angle: float
+
+    def __post_init__(self):
+        object.__setattr__(self, "angle", _angle(self.angle, "Rotated"))
+
+
+def _rotations(rotations, what: str) -> list:
+    ro = list(rotations)
+    if any(not isinstance(r, Rotate) for r in ro):
+        raise ValueError(f"{what}: rotations are made with Rotate(angle, filter)")
+    return ro
+
+
+def _kept_shares(ctx: Context, rotations, w: int, h: int) -> list:
+    """`Rotate.kept` of every rotation for a w x h frame, counted on the device (ssw_unrotate_kept): the same numbers"""
+    if not rotations:
+        return []
+    jobs, counts = (L.RotateJob * len(rotations))(*[r.job(0, w, h) for r in rotations]), np.zeros(len(rotations), np.uint64)
+    check(ctx._lib.ssw_unrotate_kept(ctx.handle, w, h, jobs, len(rotations), counts.ctypes.data), "ssw_unrotate_kept")
+    return [int(c) / (w * h) for c in counts]
+
+
+def _rotate_attack(w: int, h: int) -> tuple:
+    """The attack of `_attack_every` and of the report's stage for frames of w x h: a rotation's matrices need the frame's size"""
+    return ("ssw_rotate_attack_rgb8", L.RotateJob, lambda frame, r: r.job(frame, w, h), True)
+
+
+def rotate_attack(base, images, rotations, ctx: Optional[Context] = None) -> list:
+    """Every image after every rotation attack (ssw_rotate_attack_rgb8): turned as Pillow does it, then turned back and
+    completed with `base`, the original, as `trace` would.  base: 8-bit [H, W, 3]; images: 8-bit [H, W, 3] of that size;
+    rotations: `Rotate` objects.  Returns [len(images)][len(rotations)] u8 [H, W, 3] frames.  The jobs go in groups whose frames
+    and results are at most 256 MiB on the device."""
+    frames, ro = _frames_u8(images, "rotate_attack"), _rotations(rotations, "rotate_attack")
+    if not frames or not ro:
+        return [[] for _ in frames]
+    b = _frames_u8([base], "rotate_attack")[0]
+    if b.shape != frames[0].shape:
+        raise ValueError("rotate_attack: the original has the images' size")
+    h, w = b.shape[:2]
+    return _attack_every(ctx, frames, ro, _rotate_attack(w, h), b)
+
+
+def unrotate(base, suspects, angles, ctx: Optional[Context] = None) -> list:
+    """Every suspect turned back by its angle and completed with the original where the turn lost pixels (ssw_unrotate_rgb8;
+    include/ssw.h states the mask): what tracing a `Rotated(angle)` entry extracts from.  base: the original, 8-bit [H, W, 3];
+    suspects: 8-bit [H, W, 3] of that size; angles: one per suspect, the angle each was turned by.  Returns one u8 [H, W, 3]
+    frame per suspect."""
+    b = _frames_u8([base], "unrotate")[0]
+    frames = _frames_u8(suspects, "unrotate")
+    angles = [_angle(a, "unrotate") for a in angles]
+    if len(angles) != len(frames):
+        raise ValueError("unrotate: one angle per suspect")
+    if not frames:
+        return []
+    if frames[0].shape != b.shape:
+        raise ValueError("unrotate: a rotated suspect has the original's size and 3 channels")
+    ctx = ctx or default_context()
+    h, w = b.shape[:2]
+    fb, n, out = w * h * 3, len(frames), []
+    per = max(1, UPLOAD_GROUP_BYTES // (2 * fb))
+    with _owned(ctx) as alloc:
+        dev_b, dev_i, dev_o = _upload_frames(ctx, alloc(fb), [b]), alloc(min(per, n) * fb), alloc(min(per, n) * fb)
+        for g0 in range(0, n, per):
+            g = frames[g0:g0 + per]
+            _upload_frames(ctx, dev_i, g)
+            jobs = (L.RotateJob * len(g))(*[Rotate(a).job(i, w, h) for i, a in enumerate(angles[g0:g0 + per])])
+            check(ctx._lib.ssw_unrotate_rgb8(ctx.handle, dev_b.ptr, dev_i.ptr, len(g), w, h, jobs, dev_o.ptr), "ssw_unrotate_rgb8")
+            out += list(dev_o.to_host(np.uint8, (len(g), h, w, 3)))
+    return out
+
+
+def _undo_rotated(base, suspects, placements, ctx):
+    """placements with `Rotated` entries -> (suspects, placements) with every such suspect turned back (one `unrotate` call) and
+    its entry None: a whole frame of the original's size.  The other entries pass through untouched."""
+    placements, suspects = list(placements), list(suspects)
+    if len(placements) != len(suspects):
+        raise ValueError("placements: one entry (a Placement, a Locate, a Rotated or None) per suspect")
+    todo = [i for i, p in enumerate(placements) if isinstance(p, Rotated)]
+    if not todo:
+        return suspects, placements
+    if base is None:
+        raise ValueError("Rotated entries need the original's pixels (base=)")
+    b = _base_rgb8(base)
+    turned = [np.asarray(suspects[i]) for i in todo]
+    if any(a.dtype != np.uint8 or a.shape != b.shape for a in turned):
+        raise ValueError("Rotated: the suspect has the original's size and 3 channels")
+    for i, f in zip(todo, unrotate(b, turned, [placements[i].angle for i in todo], ctx)):
+        suspects[i], placements[i] = f, None
+    return suspects, placements
+
+
 @dataclass
 class Collusion:
     """What tracing made of one forgery: `size` colluders (the first `size` copies) pooled with `method`.  weakest_colluder: the
@@ -1596,10 +1815,28 @@ class ScaleResult:
 
 
 @dataclass
+class RotateResult:
+    """What tracing made of the marked copies after the rotation attack `rotation` (a `Rotate.label`), turned back by the known
+    angle; kept: the share of the frame's pixels the undoing took from the rotated copy (the rest is the original's); the other
+    fields as in `JpegResult`."""
+    rotation: str
+    kept: float
+    survived: int
+    weakest_own: float
+    strongest_innocent: float
+    accused: int
+    psnr_min: float
+    psnr_max: float
+    ssim_min: float = math.nan
+    ssim_max: float = math.nan
+
+
+@dataclass
 class StrengthRow:
     """`strength_report` for one alpha: the `Quality` of every copy, one `Collusion` per (method, size), methods outermost, and
     one `JpegResult` per JPEG quality asked for; ssim: the `Ssim` of every copy when the report was asked for it; filters: one
-    `FilterResult` per filter asked for; scales: one `ScaleResult` per scale asked for."""
+    `FilterResult` per filter asked for; scales: one `ScaleResult` per scale asked for; rotations: one `RotateResult` per rotation
+    asked for."""
     alpha: float
     quality: list
     collusions: list
@@ -1607,6 +1844,7 @@ class StrengthRow:
     ssim: list = field(default_factory=list)
     filters: list = field(default_factory=list)
     scales: list = field(default_factory=list)
+    rotations: list = field(default_factory=list)
 
     def collusion(self, method: str, size: int) -> Collusion:
         return next(c for c in self.collusions if (c.method, c.size) == (method, size))
@@ -1642,10 +1880,14 @@ def _scale_result(label_size: tuple, sims: np.ndarray, qualities: list, threshol
     return ScaleResult(*label_size, *_attack_fold(sims, qualities, threshold, ssims))
 
 
+def _rotate_result(label_kept: tuple, sims: np.ndarray, qualities: list, threshold: float, ssims=()) -> RotateResult:
+    return RotateResult(*label_kept, *_attack_fold(sims, qualities, threshold, ssims))
+
+
 def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                     methods=("average", "median", "min", "max", "minmax", "mosaic"), threshold: float = 6.0,
                     config: Optional[WriteConfig] = None, seed=None, ctx: Optional[Context] = None, jpeg=(), ssim: bool = False,
-                    filters=(), scales=()) -> list:
+                    filters=(), scales=(), rotations=()) -> list:
     """The two questions to answer before a copy ships, per insertion strength: how visible is the mark, and how many
     recipients must pool their copies before tracing fails?  For each alpha (`config` with its alpha replaced; the default
     Option2 + Energy): `copies` marked copies of the 8-bit `image` (ssw_fingerprint_embed_rgb8), their distance from it
@@ -1662,8 +1904,11 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     ssw_quality_rgb8 call, and one ssw_ssim_rgb8 with `ssim`): one `FilterResult` per filter in `StrengthRow.filters`.
     scales: `Scale` objects; the same after the filters with one ssw_scale_attack_rgb8 call, scale-major: one `ScaleResult` per
     scale in `StrengthRow.scales` -- whether `trace` still names the recipient of a thumbnail that Pillow made.
+    rotations: `Rotate` objects; the same after the scales with one ssw_rotate_attack_rgb8 call, rotation-major: one
+    `RotateResult` per rotation in `StrengthRow.rotations` -- what `trace` finds in a copy that Pillow turned when it is told the angle.
     Returns one `StrengthRow` per alpha."""
     jq, fl, sc = _jpeg_qualities(jpeg, "strength_report"), _filters(filters, "strength_report"), _scales(scales, "strength_report")
+    ro = _rotations(rotations, "strength_report")
     img = _frames_of_side([image], "strength_report", "a JPEG attack", L.JPEG_MIN_SIDE if jq else 0)[0]
     if ssim:
         _frames_of_side([img], "strength_report", "SSIM", L.SSIM_MIN_SIDE)
@@ -1693,14 +1938,15 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
             return _ssims(dev_ssim.to_host(np.uint64, (n, L.SSIM_STATS)), *windows)
 
         def stage(attack, params):       # every copy under every parameter, parameter-major: the call, its jobs, their number, the results' buffers
-            name, struct, job = attack
+            name, struct, job = attack[:3]
             n = len(params) * copies
-            return (name, (struct * n)(*[job(c, p) for p in params for c in range(copies)]), n,
+            return (name if len(attack) == 3 else (name, True), (struct * n)(*[job(c, p) for p in params for c in range(copies)]), n,
                     [alloc(n * b) for b in (fb, k * 4, copies * 4, 8 * L.QUALITY_STATS)] if n else None)
 
         def attacked(cfg, made, labels, result):       # attack, trace, quality, the downloads, SSIM: one `result` per label
             name, jobs, n, (dev_frames, dev_e, dev_s, dev_st) = made
-            check(getattr(lib, name)(ctx.handle, dev_copies.ptr, copies, w, h, jobs, n, dev_frames.ptr), name)
+            name, lead = (name, ()) if isinstance(name, str) else (name[0], (dev_img.ptr,))       # the original in front
+            check(getattr(lib, name)(ctx.handle, *lead, dev_copies.ptr, copies, w, h, jobs, n, dev_frames.ptr), name)
             trace(cfg, dev_frames, n, dev_e, dev_s)
             measure(dev_frames, n, dev_st)
             sims = dev_s.to_host(np.float32, (len(labels), copies, copies))
@@ -1713,7 +1959,9 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
         dev_copies, dev_stats = alloc(copies * fb), alloc(copies * 8 * L.QUALITY_STATS)
         dev_forged, dev_ext, dev_sims = alloc(max(nf, 1) * fb), alloc(max(nf * k, 1) * 4), alloc(max(nf * copies, 1) * 4)
         jpeg_stage, filter_stage, scale_stage = stage(_JPEG_ATTACK, jq), stage(_FILTER_ATTACK, fl), stage(_scale_attack(w, h), sc)
-        dev_ssim = alloc(max(copies, jpeg_stage[2], filter_stage[2], scale_stage[2]) * 8 * L.SSIM_STATS) if ssim else None
+        rotate_stage = stage(_rotate_attack(w, h), ro)
+        dev_ssim = alloc(max(copies, jpeg_stage[2], filter_stage[2], scale_stage[2], rotate_stage[2]) * 8 * L.SSIM_STATS) if ssim else None
+        kept = list(zip([r.label for r in ro], _kept_shares(ctx, ro, w, h)))
         for alpha in alphas:
             cfg = L.Config(config.ordering.tag, config.insertion.tag, float(alpha), config.precision)
             check(lib.ssw_fingerprint_embed_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, w, h, dev_marks.ptr, copies, k, dev_copies.ptr, None),
@@ -1734,6 +1982,8 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                 rows[-1].filters = attacked(cfg, filter_stage, [f.label for f in fl], _filter_result)
             if sc:
                 rows[-1].scales = attacked(cfg, scale_stage, [(s.label, s.size(w, h)) for s in sc], _scale_result)
+            if ro:
+                rows[-1].rotations = attacked(cfg, rotate_stage, kept, _rotate_result)
     return rows
 
 

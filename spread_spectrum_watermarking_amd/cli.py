@@ -10,12 +10,13 @@
         -> <stem>_fp<i>.png (i zero-padded) and one <stem>_fp.json holding the N marks, described "<desc> #i";
            `test <file> <stem>_fp<i>.png <stem>_fp.json` then names the copy that leaked
     python -m spread_spectrum_watermarking_amd.cli trace <base> --suspects A.png B.png ... --marks X_fp.json [Y.json ...]
-            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] ...] [--locate FILE[=WxH|=W0..W1] ...]
+            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] | FILE=rotate:DEGREES ...] [--locate FILE[=WxH|=W0..W1] ...]
         -> one record per suspect: the stored mark it carries (or none) and every further mark above the threshold;
            one GPU call per group of stored marks with equal (config, length), whatever the number of suspects.
            Attacked copies are restored on the GPU first (tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70): a
            suspect of another size is resized back to the base's, an alpha channel is blended over the base, and
            --place puts a cut-out where it belongs (at X,Y, scaled to WxH when given); their records say "Restored:".
+           --place FILE=rotate:DEGREES turns back a copy of the base's size that was turned by a known angle.
            --locate finds where a cut-out belongs (the size WxH it had in the base when it was scaled afterwards) by a
            search over every translation on the GPU; its record says "Located:" too.  FILE=W0..W1: the size is not known
            either, only that the cut-out was between W0 and W1 wide in the base -- a search over scale as well
@@ -29,7 +30,7 @@
         -> `identify` for every suspect in one call, then the trace above once per original that was named, with the marks
            file the catalogue holds for it; every record gains an "Original:" line
     python -m spread_spectrum_watermarking_amd.cli strength <file> --alpha 0.02 0.05 0.1 [-n 1000] [--copies 8] [--collude 2 4]
-            [--method average median min max minmax mosaic] [--jpeg 90 75 50] [--filter blur:1.5 median unsharp:2,150,3] [--scale 0.5 0.25:lanczos 640x360:bilinear] [--ssim]
+            [--method average median min max minmax mosaic] [--jpeg 90 75 50] [--filter blur:1.5 median unsharp:2,150,3] [--scale 0.5 0.25:lanczos 640x360:bilinear] [--rotate 0.5 2:bilinear -1] [--ssim]
             [--similarity-exceed 6.0] [--json]
         -> before a copy ships: per alpha the PSNR range of the marked copies (with --ssim also their mean SSIM and the worst
            8 x 8 window), and per collusion method and coalition size
@@ -37,7 +38,9 @@
            recipient's similarity; with --jpeg, per quality what a trace still finds in every copy after it was saved as a
            JPEG; with --filter the same after a Gaussian blur (blur:RADIUS), an unsharp mask (unsharp[:RADIUS[,PERCENT[,THRESHOLD]]])
            or a 3 x 3 median (median), as Pillow's filters of those names do them; with --scale the same after the copy was
-           scaled as Pillow's Image.resize does it (FACTOR[:FILTER] or WIDTHxHEIGHT[:FILTER]) and brought back to size; everything stays on the GPU between the original going up and the numbers coming down
+           scaled as Pillow's Image.resize does it (FACTOR[:FILTER] or WIDTHxHEIGHT[:FILTER]) and brought back to size; with --rotate
+           the same after the copy was turned as Pillow's Image.rotate does it (DEGREES[:FILTER]) and turned back by the known
+           angle, with the share of the frame that survives the two turns; everything stays on the GPU between the original going up and the numbers coming down
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -52,7 +55,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from ._lib import COLLUDE_METHODS
-from .api import (IDENTIFY_MAX_DISTANCE, Catalogue, Filter, Locate, MarkBuf, Placement, Reader, Scale, Tester, TraceResult, Writer, identify, locate,
+from .api import (IDENTIFY_MAX_DISTANCE, Catalogue, Filter, Locate, MarkBuf, Placement, Reader, Rotate, Rotated, Scale, Tester, TraceResult, Writer, identify, locate,
                   strength_report)
 from .storage import Configuration, DescribedWatermark, Version1Storage
 
@@ -90,6 +93,17 @@ def _scale_arg(text: str) -> Scale:
         raise argparse.ArgumentTypeError(f"{text!r}: FACTOR[:FILTER] or WIDTHxHEIGHT[:FILTER] ({e})") from e
 
 
+def _rotate_arg(text: str) -> Rotate:
+    """DEGREES[:FILTER]"""
+    what, colon, name = text.partition(":")
+    try:
+        if colon and not name:
+            raise ValueError("a filter's name after the colon")
+        return Rotate(float(what), name or "bicubic")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"{text!r}: DEGREES[:FILTER] ({e})") from e
+
+
 def _rust_f32(x: float) -> str:
     """`{}` of an f32 in Rust: shortest round-trip digits, no trailing `.0`."""
     s = np.format_float_positional(np.float32(x), unique=True, trim="-")
@@ -115,9 +129,14 @@ def _open_suspect(path: str) -> np.ndarray:
         raise SystemExit(f"Could not load image at {path!r}") from e
 
 
-def parse_place(text: str) -> Tuple[str, Placement]:
-    """FILE=X,Y[,WxH] -> (FILE, Placement); ValueError on anything else."""
+def parse_place(text: str):
+    """FILE=X,Y[,WxH] -> (FILE, Placement), FILE=rotate:DEGREES -> (FILE, Rotated); ValueError on anything else."""
     name, sep, spec = text.rpartition("=")
+    if sep and name and spec.startswith("rotate:"):
+        try:
+            return name, Rotated(float(spec[len("rotate:"):]))
+        except ValueError:
+            raise ValueError(f"--place {text!r}: expected FILE=rotate:DEGREES") from None
     parts = spec.split(",")
     if not sep or not name or len(parts) not in (2, 3):
         raise ValueError(f"--place {text!r}: expected FILE=X,Y[,WxH]")
@@ -280,6 +299,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--scale", type=_scale_arg, nargs="+", default=[], metavar="SCALE", dest="scales",
                    help="Also scale every copy as Pillow's Image.resize does, bring it back to size and trace what is left: "
                         "FACTOR[:FILTER] (0 < FACTOR <= 4) or WIDTHxHEIGHT[:FILTER]; FILTER box, bilinear, bicubic (default) or lanczos.")
+    g.add_argument("--rotate", type=_rotate_arg, nargs="+", default=[], metavar="ROTATION", dest="rotations",
+                   help="Also turn every copy as Pillow's Image.rotate does, turn it back by the known angle and trace what is left: "
+                        "DEGREES[:FILTER]; FILTER bilinear or bicubic (default).")
     g.add_argument("--ssim", action="store_true", help="Also report the structural similarity (SSIM) of every copy and its worst window.")
     g.add_argument("--json", action="store_true", help="Print the report as one JSON document.")
     return p
@@ -421,10 +443,11 @@ def cmd_identify(args, out=sys.stdout) -> int:
 def cmd_strength(args, out=None) -> int:
     out = out or sys.stdout                                  # looked up at the call: a caller may have redirected it
     orig = _open_image(args.file)
-    scales = getattr(args, "scales", [])
+    scales, rotations = getattr(args, "scales", []), getattr(args, "rotations", [])
     try:
         rows = strength_report(orig, args.alpha, k=args.length, copies=args.copies, sizes=args.collude, methods=args.method,
-                               threshold=args.similarity_exceed, jpeg=args.jpeg, ssim=args.ssim, filters=args.filters, scales=scales)
+                               threshold=args.similarity_exceed, jpeg=args.jpeg, ssim=args.ssim, filters=args.filters, scales=scales,
+                               rotations=rotations)
     except ValueError as e:
         raise SystemExit(str(e)) from e
     if args.json:
@@ -446,6 +469,8 @@ def cmd_strength(args, out=None) -> int:
                 c.update({"ssim": s.mean, "ssim_worst": s.worst_value, "ssim_worst_at": list(s.worst_position)})
             if scales:                                       # the key is there when --scale was given
                 d["scales"] = [dict(attack("scale", a), size=list(a.size)) for a in r.scales]
+            if rotations:                                    # ... when --rotate was given
+                d["rotations"] = [dict(attack("rotation", a), kept=a.kept) for a in r.rotations]
         print(json.dumps(doc), file=out)
         return 0
     for r in rows:
@@ -465,12 +490,13 @@ def cmd_strength(args, out=None) -> int:
             print(f"  {c.method} of {c.size}: found {c.found}/{c.size}, weakest colluder {c.weakest_colluder:.2f}, "
                   f"strongest innocent {innocent}{accused}", file=out)
         for label, a in ([(f"jpeg {j.quality}", j) for j in r.jpeg] + [(f.filter, f) for f in r.filters] +
-                         [(f"{a.scale} ({a.size[0]}x{a.size[1]})", a) for a in r.scales]):
+                         [(f"{a.scale} ({a.size[0]}x{a.size[1]})", a) for a in r.scales] + [(a.rotation, a) for a in r.rotations]):
             innocent = "none" if a.strongest_innocent != a.strongest_innocent else f"{a.strongest_innocent:.1f}"
             accused = f", {a.accused} innocent accused" if a.accused else ""
             ssim = f", ssim {a.ssim_min:.2f} .. {a.ssim_max:.2f}" if r.ssim else ""
+            kept = f", {100 * a.kept:.1f} % kept" if hasattr(a, "kept") else ""
             print(f"  {label}: own mark found {a.survived}/{len(r.quality)}, weakest {a.weakest_own:.1f}, "
-                  f"strongest innocent {innocent}{accused}, {a.psnr_min:.1f} .. {a.psnr_max:.1f} dB{ssim}", file=out)
+                  f"strongest innocent {innocent}{accused}, {a.psnr_min:.1f} .. {a.psnr_max:.1f} dB{ssim}{kept}", file=out)
     return 0
 
 
@@ -545,6 +571,12 @@ def cmd_trace(args, out=sys.stdout) -> int:
     for path, img in zip(args.suspects, suspects):
         sh, sw, c = img.shape
         p = placed.get(path)
+        if isinstance(p, Rotated):
+            if (sw, sh, c) != (W, H, 3):
+                raise SystemExit(f"{path}: a turned copy has the base's size ({W}x{H}) and no alpha channel")
+            placements.append(p)
+            restored.append(f"turned back by {p.angle:g} degrees, completed with the base")
+            continue
         if p is None and c == 3 and (sw, sh) == (W, H):
             placements.append(None)
             restored.append(None)
