@@ -702,6 +702,9 @@ public:
     static Reader base(Context& ctx, const ImageRgb8& image, const ReadConfig& config = ReadConfig()) {
         return Reader(ctx, image, true, config);
     }
+    static Reader base(Context& ctx, const ImageRgb16& image, const ReadConfig& config = ReadConfig()) {
+        return Reader(ctx, image, true, config);
+    }
     ~Reader() { ssw_reader_destroy(rd_); }
     Reader(Reader&& o) noexcept : w_(o.w_), h_(o.h_), rd_(o.rd_) { o.rd_ = nullptr; }
     Reader(const Reader&) = delete;
@@ -808,6 +811,8 @@ public:
         : r_(ctx, image, false, [&] { ReadConfig c; c.precision = precision; return c; }()) {}
     ReaderDerived(Context& ctx, const ImageRgb8& image, ssw_precision precision = SSW_PRECISION_F64)
         : r_(ctx, image, false, [&] { ReadConfig c; c.precision = precision; return c; }()) {}
+    ReaderDerived(Context& ctx, const ImageRgb16& image, ssw_precision precision = SSW_PRECISION_F64)
+        : r_(ctx, image, false, [&] { ReadConfig c; c.precision = precision; return c; }()) {}
     std::vector<float> coefficients() const { return r_.coefficients(); }
 
 private:
@@ -851,8 +856,8 @@ inline std::vector<ImageRgb8> mark_many(Context& ctx, const std::vector<const Im
     std::vector<ImageRgb8> out(images.size(), ImageRgb8(w, h));
     std::vector<uint8_t*> op(images.size());
     for (size_t i = 0; i < images.size(); ++i) {
-        if (images[i]->width != w || images[i]->height != h || images[i]->data.size() != w * h * 3 || marks[i]->data().size() != k)
-            throw Error(SSW_ERR_BAD_DIMS, "mark_many");
+        if (images[i]->width != w || images[i]->height != h || images[i]->data.size() != w * h * 3) throw Error(SSW_ERR_BAD_DIMS, "mark_many");
+        if (marks[i]->data().size() != k) throw Error(SSW_ERR_LENGTH_MISMATCH, "mark_many");
         in[i] = images[i]->data.data();
         std::copy(marks[i]->data().begin(), marks[i]->data().end(), m.begin() + i * k);
         op[i] = out[i].data.data();
