@@ -947,6 +947,45 @@ int ssw_affine_plan(size_t w, size_t h, const double* m, int* lds_form, uint32_t
    context; tests/test_rotate_cpu.py compares 64 angles bit for bit).  SSW_ERR_BAD_ARG: m null or an angle that is not finite. */
 int ssw_rotation_matrix(double angle, size_t w, size_t h, double* m);
 
+/* ---- finding the angle of a turned copy: an angle ladder (csrc/angle.hip) ------------------------------------------------
+   By which angle was each suspect turned?  A search over the angle of a rotation about the centre -- what PIL.Image.rotate
+   does without `expand` -- for suspects of the original's size.  Everything is an integer and no sum depends on its order:
+   the answer equals the numpy restatement of tests/test_angle_cpu.py exactly.  The reference has no counterpart.
+   Inputs.  The original O = dev_base and n suspects S = dev_suspects [n], all [h][w][3] u8.  A range amin <= amax in degrees,
+   counter-clockwise as PIL.Image.rotate, -45 <= amin, amax <= 45.
+   Angles.  Every angle is a / 32 degrees for an integer a (an exact double).  Of the matrix that ssw_rotation_matrix makes for
+   a / 32 the search uses C(a) = floor(m0 * 65536 + 0.5) and S(a) = floor(m1 * 65536 + 0.5), evaluated in doubles, and nothing
+   else: ssw_angle_table gives the two (host arithmetic, no context; SSW_ERR_BAD_ARG: a null pointer).
+   Planes.  L = (77 R + 150 G + 29 B + 128) >> 8, the luma of ssw_locate_rgb8.  f = 1: the planes Po (original) and Ps (suspect)
+   are L itself, wr = w, hr = h.  f = 4: the decimated 4 x 4 box means (sum + 8) >> 4 at (4 X, 4 Y), wr = w >> 2, hr = h >> 2
+   (trailing pixels are dropped).
+   Cost of angle a at factor f (64-bit integers; lg = log2 f, sh = 17 + lg).  For every pixel (X, Y) of Ps:
+       p  = 2 f X + f - w                          q  = 2 f Y + f - h          (half pixels of the frame from its centre)
+       Rx = (w - f) * 65536 + C p + S q            Ry = (h - f) * 65536 - S p + C q
+       X0 = Rx >> sh, fx = (Rx >> (sh - 8)) & 255; Y0, fy likewise of Ry                      (arithmetic shifts)
+       valid = 1 <= X0 <= wr - 3 and 1 <= Y0 <= hr - 3
+       v  = ((256-fx)(256-fy) Po[Y0][X0] + fx (256-fy) Po[Y0][X0+1] + (256-fx) fy Po[Y0+1][X0] + fx fy Po[Y0+1][X0+1] + 32768) >> 16
+   D = sum over the valid pixels of |Ps[Y][X] - v|, c = their number: the original's plane turned forward by the candidate
+   against the suspect as it is.  Mean costs are compared cross-multiplied in 64 bits: (D1, c1) < (D2, c2) when D1 c2 < D2 c1.
+   Ladder.  j0 = floor(4 amin), j1 = ceil(4 amax), clipped to -180 .. 180; one rung per j in j0 .. j1: the angle a = 8 j (a step
+   of 0.25 degrees) at f = 4.  Kept: the 4 rungs of smallest mean cost, ties to the smaller j (all, when there are fewer).
+   Refinement: every a within 7 of a kept rung's 8 j and inside 8 j0 .. 8 j1, each once, at f = 1.  Answer: the smallest mean
+   cost of the refinement, ties to the smaller a.
+   host_found[i] (a HOST array of n): n = the answer a of suspect i (its angle is n / 32 degrees), sad and count = its D and c,
+   n_rungs = j1 - j0 + 1.  host_rungs (a HOST array, may be null): [n][n_rungs][2] = D, c of every rung of every suspect.
+   The original's planes are made once per call; the suspects go in groups of at most 256 MiB of planes (one suspect's, if
+   they are larger).  The kept rungs are chosen on the device: the call waits for the context's stream once, at its end (the
+   answer is needed on the host).  Timed under SSW_STAGE_LOCATE; the ladder's launch -- the coarse pass -- also under
+   SSW_STAGE_LOCATE_COARSE (work: byte differences), as ssw_locate_rgb8 bills its own.
+   n == 0 is checked first: SSW_OK.  SSW_ERR_BAD_ARG: a null pointer, a range that is not finite, reversed or beyond +-45;
+   SSW_ERR_BAD_DIMS: a side below 32 (with this limit c > 0 at every angle of the range); SSW_ERR_UNSUPPORTED: w h > 2^27
+   (the cross-multiplied products stay below 2^63).  Not searched: a copy that was turned AND cropped or scaled, a rotation
+   about another centre.  The answer's resolution is 1/32 degree. */
+typedef struct ssw_angle_found { int32_t n; uint32_t n_rungs; uint64_t sad, count; } ssw_angle_found;
+int ssw_find_angle_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const uint8_t* dev_suspects, size_t n, size_t w, size_t h,
+                        double amin, double amax, ssw_angle_found* host_found, uint64_t* host_rungs);
+int ssw_angle_table(int32_t n, int32_t* c, int32_t* s);
+
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,
    and `into_rgb16()` from Rgb32F: round(clamp(v,0,1) * 65535) (`image 0.24.3`, like the 8-bit forms). */

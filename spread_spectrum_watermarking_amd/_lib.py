@@ -107,6 +107,15 @@ class RotateJob(C.Structure):
     _fields_ = [("frame", C.c_uint32), ("filter", C.c_uint32), ("fill", C.c_uint8 * 4), ("forward", C.c_double * 6), ("back", C.c_double * 6)]
 
 
+class AngleFound(C.Structure):
+    """ssw_angle_found (include/ssw.h): one answer of ssw_find_angle_rgb8 -- the angle is n / 32 degrees, sad and count its D and c."""
+    _fields_ = [("n", C.c_int32), ("n_rungs", C.c_uint32), ("sad", C.c_uint64), ("count", C.c_uint64)]
+
+
+ANGLE_PER_DEGREE = 32        # ssw_find_angle_rgb8: the answer's resolution
+ANGLE_MIN_SIDE = 32          # ... refuses smaller frames
+ANGLE_MAX_PIXELS = 1 << 27   # ... and larger ones
+
 # ssw_affine_filter, by the names the Python surface and the CLI accept (Pillow's)
 AFFINE_BILINEAR, AFFINE_BICUBIC = range(2)
 AFFINE_FILTERS = {"bilinear": 0, "bicubic": 1}
@@ -221,6 +230,8 @@ SIGNATURES = {
     "ssw_unrotate_kept": (C.c_int, [_vp, _sz, _sz, C.POINTER(RotateJob), _sz, _u64p]),
     "ssw_affine_plan": (C.c_int, [_sz, _sz, C.POINTER(C.c_double), C.POINTER(C.c_int), _u32p, _u32p]),
     "ssw_rotation_matrix": (C.c_int, [C.c_double, _sz, _sz, C.POINTER(C.c_double)]),
+    "ssw_find_angle_rgb8": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, C.c_double, C.c_double, C.POINTER(AngleFound), _u64p]),
+    "ssw_angle_table": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ssw_ssim_rgb8": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64p, _vp]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,
                                                            _f32p, _f32p, _u32p, _f32p, _u32p]),

@@ -526,13 +526,15 @@ class Reader:
         if not self.is_base:
             raise SswError(L.SSW_ERR_NOT_BASE, "Reader::trace")
         if placements is not None:
-            if any(isinstance(p, Rotated) for p in placements):          # turned copies: one unrotate call
-                suspects, placements = _undo_rotated(base, suspects, placements, self._ctx)
+            turned = {}
+            if any(isinstance(p, Rotated) for p in placements):          # turned copies: one angle search, one unrotate call
+                suspects, placements, turned = _undo_rotated(base, suspects, placements, self._ctx)
             if any(isinstance(p, Locate) for p in placements):           # cut-outs at an unknown position: one locate call
                 placements, _ = _resolve_locates(base, suspects, placements, self._ctx)
             arrs, ptrs, pl = _placed_suspects(suspects, placements, self.width, self.height)
             m, k = _trace_marks(marks, k)
             res = TraceResult.empty(len(arrs), m.shape[0], k)
+            res.turned = turned
             b = None if base is None else _base_rgb8(base, self.width, self.height)
             check(self._lib.ssw_reader_trace_restored_host_rgb8(self._h, b.ctypes.data if b is not None else None, ptrs, pl, len(arrs), k,
                                                                 *res._args(m, threshold)), "Reader::trace")
@@ -655,6 +657,7 @@ class TraceResult:
     best_sim: np.ndarray
     n_exceed: np.ndarray
     threshold: float = 6.0
+    turned: dict = field(default_factory=dict)      # {suspect: FoundAngle} of the `Rotated` entries whose angle was searched for
     NONE = L.TRACE_NONE
 
     @staticmethod
@@ -910,18 +913,22 @@ def trace_many(base, suspects, marks, k: Optional[int] = None, threshold: float 
     suspects of any size with 3 or 4 channels are restored on the device first (ssw_fingerprint_trace_restored_host_rgb8;
     `restore` spells out the rule and returns the frames this call extracts from).  `Locate(w, h)` entries -- cut-outs at an
     unknown position -- are found with one `locate` call first.  `Rotated(angle)` entries -- copies of the original's size that
-    were turned by a known angle -- are turned back with one `unrotate` call first and traced as whole frames."""
+    were turned by a known angle -- are turned back with one `unrotate` call first and traced as whole frames; `Rotated()`
+    entries, whose angle is not known, are searched for with one `find_angle` call before that (`TraceResult.turned` says what
+    was found)."""
     ctx = ctx or default_context()
     config = config or ReadConfig.default()
     if placements is not None:
         b = _base_rgb8(base)
+        turned = {}
         if any(isinstance(p, Rotated) for p in placements):
-            suspects, placements = _undo_rotated(b, suspects, placements, ctx)
+            suspects, placements, turned = _undo_rotated(b, suspects, placements, ctx)
         if any(isinstance(p, Locate) for p in placements):
             placements, _ = _resolve_locates(b, suspects, placements, ctx)
         arrs, ptrs, pl = _placed_suspects(suspects, placements, b.shape[1], b.shape[0])
         m, k = _trace_marks(marks, k)
         res = TraceResult.empty(len(arrs), m.shape[0], k)
+        res.turned = turned
         cfg = config._c()
         check(ctx._lib.ssw_fingerprint_trace_restored_host_rgb8(ctx.handle, C.byref(cfg), b.ctypes.data, b.shape[1], b.shape[0], ptrs, pl,
                                                                 len(arrs), k, *res._args(m, threshold)),
@@ -1658,15 +1665,81 @@ class Rotate:
         return count / (w * h)
 
 
+DEFAULT_ANGLE_SEARCH = (-10.0, 10.0)
+
+
+def _search(search, what: str) -> Tuple[float, float]:
+    """A range of angles (lo, hi) in degrees as ssw_find_angle_rgb8 takes it: finite, lo <= hi, within +-45."""
+    try:
+        lo, hi = search
+        lo, hi = _angle(lo, what), _angle(hi, what)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: search=(lo, hi), two finite numbers of degrees") from None
+    if not -45.0 <= lo <= hi <= 45.0:
+        raise ValueError(f"{what}: search=(lo, hi) with -45 <= lo <= hi <= 45")
+    return lo, hi
+
+
 @dataclass(frozen=True)
 class Rotated:
-    """A placement entry that says "this suspect is the original's frame turned by `angle` degrees" (counter-clockwise, as
-    PIL.Image.rotate(angle) does it): it is turned back on the device (ssw_unrotate_rgb8) and traced as a whole frame.  The
-    suspect has the original's size and 3 channels.  Finding the angle is not built."""
-    angle: float
+    """A placement entry that says "this suspect is the original's frame turned" (counter-clockwise, as PIL.Image.rotate does
+    it): it is turned back on the device (ssw_unrotate_rgb8) and traced as a whole frame.  The suspect has the original's size
+    and 3 channels.  `Rotated(angle)`: turned by `angle` degrees.  `Rotated()` or `Rotated(search=(lo, hi))`: the angle is not
+    known and is searched for in the range first, among all such entries of a call at once (`find_angle`)."""
+    angle: Optional[float] = None
+    search: Tuple[float, float] = DEFAULT_ANGLE_SEARCH
 
     def __post_init__(self):
-        object.__setattr__(self, "angle", _angle(self.angle, "Rotated"))
+        if self.angle is not None:
+            object.__setattr__(self, "angle", _angle(self.angle, "Rotated"))
+        object.__setattr__(self, "search", _search(self.search, "Rotated"))
+
+
+@dataclass
+class FoundAngle:
+    """By which angle a suspect was turned (ssw_find_angle_rgb8): `angle` = n / 32 degrees, counter-clockwise as
+    PIL.Image.rotate's; `sad` the sum of absolute luma differences between the original turned by it and the suspect over the
+    `count` pixels the turn keeps well inside the frame; `mean` = sad / count -- a few units for a true match of a marked copy."""
+    angle: float
+    n: int
+    sad: int
+    count: int
+    mean: float
+
+
+def find_angle(base, suspects, search=DEFAULT_ANGLE_SEARCH, ctx: Optional[Context] = None, rungs: bool = False):
+    """By which angle was each suspect turned?  A search over the angle of a rotation about the centre on the device
+    (ssw_find_angle_rgb8): integer luma differences between the original turned forward and the suspect, a ladder of angles 0.25
+    degrees apart on 4 x 4 box means, the 4 best rungs refined in steps of 1/32 degree at full resolution -- exactly reproducible,
+    see include/ssw.h for the definition.  base: the original, 8-bit [H, W, 3], both sides at least 32; suspects: 8-bit [H, W, 3]
+    of that size; search: (lo, hi) in degrees, within +-45.  Returns one `FoundAngle` per suspect; with rungs=True also the
+    ladder's sums, uint64 [n][rungs][2] = D, c.  A copy that was turned and cropped or scaled is not found."""
+    lo, hi = _search(search, "find_angle")
+    b = _frames_u8([base], "find_angle")[0]
+    frames = _frames_u8(suspects, "find_angle")
+    if frames and frames[0].shape != b.shape:
+        raise ValueError("find_angle: a turned suspect has the original's size and 3 channels")
+    h, w = b.shape[:2]
+    if min(w, h) < L.ANGLE_MIN_SIDE or w * h > L.ANGLE_MAX_PIXELS:
+        raise ValueError(f"find_angle: frames of at least {L.ANGLE_MIN_SIDE} x {L.ANGLE_MIN_SIDE} and at most 2^27 pixels")
+    n_rungs = min(180, math.ceil(4.0 * hi)) - max(-180, math.floor(4.0 * lo)) + 1
+    found, sums = [], np.zeros((len(frames), n_rungs, 2), np.uint64)
+    if not frames:
+        return (found, sums) if rungs else found
+    ctx = ctx or default_context()
+    fb, n = w * h * 3, len(frames)
+    per = max(1, UPLOAD_GROUP_BYTES // fb)
+    with _owned(ctx) as alloc:
+        dev_b, dev_s = _upload_frames(ctx, alloc(fb), [b]), alloc(min(per, n) * fb)
+        for g0 in range(0, n, per):
+            g = frames[g0:g0 + per]
+            _upload_frames(ctx, dev_s, g)
+            got = (L.AngleFound * len(g))()
+            part = np.zeros((len(g), n_rungs, 2), np.uint64)
+            check(ctx._lib.ssw_find_angle_rgb8(ctx.handle, dev_b.ptr, dev_s.ptr, len(g), w, h, lo, hi, got, part.ctypes.data), "ssw_find_angle_rgb8")
+            sums[g0:g0 + len(g)] = part
+            found += [FoundAngle(int(f.n) / L.ANGLE_PER_DEGREE, int(f.n), int(f.sad), int(f.count), int(f.sad) / max(1, int(f.count))) for f in got]
+    return (found, sums) if rungs else found
 
 
 def _rotations(rotations, what: str) -> list:
@@ -1734,24 +1807,30 @@ def unrotate(base, suspects, angles, ctx: Optional[Context] = None) -> list:
     return out
 
 
-def _undo_rotated(base, suspects, placements, ctx):
-    """placements with `Rotated` entries -> (suspects, placements) with every such suspect turned back (one `unrotate` call) and
-    its entry None: a whole frame of the original's size.  The other entries pass through untouched."""
+def _undo_rotated(base, suspects, placements, ctx, find_fn=None, unrotate_fn=None):
+    """placements with `Rotated` entries -> (suspects, placements, {index: FoundAngle}) with every such suspect turned back (one
+    `unrotate` call) and its entry None: a whole frame of the original's size.  The entries without an angle are searched for
+    first, all of one range with one `find_angle` call.  The other entries pass through untouched."""
     placements, suspects = list(placements), list(suspects)
     if len(placements) != len(suspects):
         raise ValueError("placements: one entry (a Placement, a Locate, a Rotated or None) per suspect")
     todo = [i for i, p in enumerate(placements) if isinstance(p, Rotated)]
     if not todo:
-        return suspects, placements
+        return suspects, placements, {}
     if base is None:
         raise ValueError("Rotated entries need the original's pixels (base=)")
     b = _base_rgb8(base)
-    turned = [np.asarray(suspects[i]) for i in todo]
-    if any(a.dtype != np.uint8 or a.shape != b.shape for a in turned):
+    turned = {i: np.asarray(suspects[i]) for i in todo}
+    if any(a.dtype != np.uint8 or a.shape != b.shape for a in turned.values()):
         raise ValueError("Rotated: the suspect has the original's size and 3 channels")
-    for i, f in zip(todo, unrotate(b, turned, [placements[i].angle for i in todo], ctx)):
+    angles, found = {i: placements[i].angle for i in todo}, {}
+    for search in sorted({placements[i].search for i in todo if placements[i].angle is None}):
+        idx = [i for i in todo if placements[i].angle is None and placements[i].search == search]
+        for i, f in zip(idx, (find_fn or find_angle)(b, [turned[i] for i in idx], search, ctx)):
+            angles[i], found[i] = f.angle, f
+    for i, f in zip(todo, (unrotate_fn or unrotate)(b, [turned[i] for i in todo], [angles[i] for i in todo], ctx)):
         suspects[i], placements[i] = f, None
-    return suspects, placements
+    return suspects, placements, found
 
 
 @dataclass

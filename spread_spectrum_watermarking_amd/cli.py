@@ -10,13 +10,15 @@
         -> <stem>_fp<i>.png (i zero-padded) and one <stem>_fp.json holding the N marks, described "<desc> #i";
            `test <file> <stem>_fp<i>.png <stem>_fp.json` then names the copy that leaked
     python -m spread_spectrum_watermarking_amd.cli trace <base> --suspects A.png B.png ... --marks X_fp.json [Y.json ...]
-            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] | FILE=rotate:DEGREES ...] [--locate FILE[=WxH|=W0..W1] ...]
+            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] | FILE=rotate:DEGREES | FILE=rotate:? | FILE=rotate:LO..HI ...] [--locate FILE[=WxH|=W0..W1] ...]
         -> one record per suspect: the stored mark it carries (or none) and every further mark above the threshold;
            one GPU call per group of stored marks with equal (config, length), whatever the number of suspects.
            Attacked copies are restored on the GPU first (tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70): a
            suspect of another size is resized back to the base's, an alpha channel is blended over the base, and
            --place puts a cut-out where it belongs (at X,Y, scaled to WxH when given); their records say "Restored:".
-           --place FILE=rotate:DEGREES turns back a copy of the base's size that was turned by a known angle.
+           --place FILE=rotate:DEGREES turns back a copy of the base's size that was turned by a known angle; FILE=rotate:?
+           searches for the angle first (-10 .. 10 degrees; FILE=rotate:LO..HI: that range, within +-45), all such suspects in
+           one search on the GPU, and the record says "Turned:".
            --locate finds where a cut-out belongs (the size WxH it had in the base when it was scaled afterwards) by a
            search over every translation on the GPU; its record says "Located:" too.  FILE=W0..W1: the size is not known
            either, only that the cut-out was between W0 and W1 wide in the base -- a search over scale as well
@@ -130,13 +132,20 @@ def _open_suspect(path: str) -> np.ndarray:
 
 
 def parse_place(text: str):
-    """FILE=X,Y[,WxH] -> (FILE, Placement), FILE=rotate:DEGREES -> (FILE, Rotated); ValueError on anything else."""
+    """FILE=X,Y[,WxH] -> (FILE, Placement); FILE=rotate:DEGREES, FILE=rotate:? or FILE=rotate:LO..HI -> (FILE, Rotated);
+    ValueError on anything else."""
     name, sep, spec = text.rpartition("=")
     if sep and name and spec.startswith("rotate:"):
+        what = spec[len("rotate:"):]
         try:
-            return name, Rotated(float(spec[len("rotate:"):]))
+            if what == "?":
+                return name, Rotated()
+            if ".." in what:
+                lo, _, hi = what.partition("..")
+                return name, Rotated(search=(float(lo), float(hi)))
+            return name, Rotated(float(what))
         except ValueError:
-            raise ValueError(f"--place {text!r}: expected FILE=rotate:DEGREES") from None
+            raise ValueError(f"--place {text!r}: expected FILE=rotate:DEGREES, FILE=rotate:? or FILE=rotate:LO..HI (within -45 .. 45)") from None
     parts = spec.split(",")
     if not sep or not name or len(parts) not in (2, 3):
         raise ValueError(f"--place {text!r}: expected FILE=X,Y[,WxH]")
@@ -153,6 +162,12 @@ def parse_place(text: str):
     if x < 0 or y < 0 or (w is not None and (w <= 0 or h <= 0)):
         raise ValueError(f"--place {text!r}: negative position or empty size")
     return name, Placement(x, y, w, h)
+
+
+def turned_text(f) -> str:
+    """The record's "Turned:" value of a suspect whose angle was searched for (f: a FoundAngle)."""
+    degrees = f"{f.angle:.5f}".rstrip("0").rstrip(".")          # n / 32: five decimals are all there are
+    return f"{degrees} (mean luma difference {f.mean:.2f})"
 
 
 def trace_placements(suspects: List[str], place: Optional[List[str]]) -> Dict[str, Placement]:
@@ -267,7 +282,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="With --catalogue: the largest signature distance that still names an original.")
     p.trace_parser = r
     r.add_argument("--place", action="append", metavar="FILE=X,Y[,WxH]",
-                   help="Where the cut-out FILE (one of --suspects) lies in the base, and the size it had there. Repeatable.")
+                   help="Where the cut-out FILE (one of --suspects) lies in the base, and the size it had there; "
+                        "FILE=rotate:DEGREES: a copy turned by a known angle; FILE=rotate:? or FILE=rotate:LO..HI: the angle is "
+                        "searched for. Repeatable.")
     r.add_argument("--locate", action="append", metavar="FILE[=WxH|=W0..W1]",
                    help="Find where the cut-out FILE (one of --suspects) lies in the base; WxH: the size it had there; "
                         "W0..W1: the widths it may have had there (the scale is searched too). Repeatable.")
@@ -575,7 +592,8 @@ def cmd_trace(args, out=sys.stdout) -> int:
             if (sw, sh, c) != (W, H, 3):
                 raise SystemExit(f"{path}: a turned copy has the base's size ({W}x{H}) and no alpha channel")
             placements.append(p)
-            restored.append(f"turned back by {p.angle:g} degrees, completed with the base")
+            restored.append(f"turned back by {p.angle:g} degrees, completed with the base" if p.angle is not None
+                            else "turned back by the angle found, completed with the base")
             continue
         if p is None and c == 3 and (sw, sh) == (W, H):
             placements.append(None)
@@ -604,10 +622,14 @@ def cmd_trace(args, out=sys.stdout) -> int:
     exceed = args.similarity_exceed
     # per suspect: (exact similarity or None, GEMM similarity, path, mark) of every stored mark, in file order per group
     rows: List[list] = [[] for _ in suspects]
+    turned: Dict[int, str] = {}
     for (config, length), members in group_stored_marks(stored).items():   # main.rs:383-415, once per group for ALL suspects
         reader = Reader.base(base, config.to_read_config())
         if any_restored:
             res = reader.trace(suspects, [w.values for _, w in members], exceed, k=length, placements=placements, base=base)
+            for s, f in res.turned.items():          # found once, with the first group; every later group is told the angle
+                turned[s] = turned_text(f)
+                placements[s] = Rotated(f.angle)
         else:
             res = reader.trace(suspects, [w.values for _, w in members], exceed, k=length)
         for s in range(len(suspects)):
@@ -621,6 +643,8 @@ def cmd_trace(args, out=sys.stdout) -> int:
         print(f"  Suspect: \"{spath}\"", file=out)
         if spath in located:
             print(f"  Located: \"{located[spath]}\"", file=out)
+        if s in turned:
+            print(f"  Turned: \"{turned[s]}\"", file=out)
         if restored[s] is not None:
             print(f"  Restored: \"{restored[s]}\"", file=out)
         if top is None:

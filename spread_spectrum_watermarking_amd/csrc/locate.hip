@@ -543,6 +543,33 @@ int enqueue_batch(ssw_ctx* ctx, const std::vector<Item>& items, const Group& g, 
 
 }  // namespace
 
+// The planes of n frames [h][w][3] of one size for a search of another file (angle.hip), enqueued on the context's stream: the
+// luma planes, rows of `pitch` bytes (pitch % 4 == 0, bytes past w are 0) ...
+int locate_luma_planes(ssw_ctx* ctx, const uint8_t* rgb, size_t n, size_t w, size_t h, uint8_t* out, size_t out_stride, unsigned pitch) {
+    for (size_t i0 = 0; i0 < n; i0 += LOC_BATCH) {
+        const unsigned m = (unsigned)std::min<size_t>(LOC_BATCH, n - i0);
+        LumaBatch lb{};
+        for (unsigned s = 0; s < m; ++s) lb.it[s] = LumaDev{rgb + (i0 + s) * w * h * 3, out + (i0 + s) * out_stride, (uint32_t)w, (uint32_t)h, 3u, pitch};
+        locate_luma_kernel<<<dim3((pitch / 4 + 255) / 256, grid_rows(h), m), 256, 0, ctx->stream>>>(lb);
+        SSW_HIP_CHECK(hipGetLastError());
+    }
+    return SSW_OK;
+}
+// ... and of such luma planes the decimated 4 x 4 box means S_f, [h / 4] rows of `opitch` bytes, w / 4 of them means, the others 0
+int locate_box4_planes(ssw_ctx* ctx, const uint8_t* luma, size_t luma_stride, unsigned lpitch, size_t n, size_t w, size_t h, uint8_t* out,
+                       size_t out_stride, unsigned opitch) {
+    for (size_t i0 = 0; i0 < n; i0 += LOC_BATCH) {
+        const unsigned m = (unsigned)std::min<size_t>(LOC_BATCH, n - i0);
+        BoxBatch bb{};
+        for (unsigned s = 0; s < m; ++s)
+            bb.it[s] = BoxDev{luma + (i0 + s) * luma_stride, out + (i0 + s) * out_stride, lpitch, (uint32_t)w, (uint32_t)h, opitch, (uint32_t)(w / 4),
+                              (uint32_t)(h / 4), 1u, 0u};
+        locate_box_kernel<<<dim3((opitch + 255) / 256, grid_rows(h / 4), m), 256, 0, ctx->stream>>>(bb);
+        SSW_HIP_CHECK(hipGetLastError());
+    }
+    return SSW_OK;
+}
+
 int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
                 const std::vector<ssw_placement>& pl, uint64_t* host_res, const std::vector<LocWindow>* win) {
     const size_t n = pl.size();

@@ -205,6 +205,11 @@ int restore_enqueue(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, c
 struct LocWindow { uint32_t x0, x1, y0, y1; bool share; };
 int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
                 const std::vector<ssw_placement>& pl, uint64_t* host_res, const std::vector<LocWindow>* win = nullptr);
+// locate.hip's plane kernels for the angle search (angle.hip), enqueued on the context's stream: the luma planes of n frames
+// [h][w][3] (rows of `pitch` bytes, pitch % 4 == 0), and of such planes the decimated 4 x 4 box means (h / 4 rows of `opitch` bytes)
+int locate_luma_planes(ssw_ctx* ctx, const uint8_t* rgb, size_t n, size_t w, size_t h, uint8_t* out, size_t out_stride, unsigned pitch);
+int locate_box4_planes(ssw_ctx* ctx, const uint8_t* luma, size_t luma_stride, unsigned lpitch, size_t n, size_t w, size_t h, uint8_t* out,
+                       size_t out_stride, unsigned opitch);
 // ssw_lib.hip: the cached CatmullRom tap table (in_len -> out_len) of the context
 int get_taps(ssw_ctx* ctx, size_t in_len, size_t out_len, DeviceTaps* out);
 

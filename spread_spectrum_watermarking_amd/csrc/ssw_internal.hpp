@@ -399,7 +399,9 @@ SSW_BUF_GROUP(PruneBufs, SSW_PRUNE_BUFS);
 SSW_BUF_GROUP(TraceBufs, SSW_TRACE_BUFS);
 // locate.hip: the original's luma plane | its 16 phase planes | one group's workspace (suspects R, luma, S_f, D; the ladder's
 // boxes; the refinement's resized cut-outs) | keys, sums, results | (scale ladder) the original's 8 x 8 box planes | its tap tables
-#define SSW_LOCATE_BUFS(X) X(luma) X(phases) X(group) X(keys) X(box_planes) X(taps)
+// angle.hip shares luma, phases (the original's one decimated plane) and group (the suspects' planes) and adds: C, S of every
+// angle of a call's range | answers, rung and refinement sums, the refinement's slot lists
+#define SSW_LOCATE_BUFS(X) X(luma) X(phases) X(group) X(keys) X(box_planes) X(taps) X(angle_tab) X(angle_sums)
 SSW_BUF_GROUP(LocateBufs, SSW_LOCATE_BUFS);
 // catalogue.hip: the blocks' top-8 lists of a match | host form: one group of frames | its signatures
 #define SSW_CATALOGUE_BUFS(X) X(top8) X(frames) X(sigs)

@@ -1,0 +1,307 @@
+"""The angle search's reference and its surfaces, without a GPU.  `angle_table_ref`, `angle_cost_ref` and `find_angle_ref` are the
+numpy restatement of the definition include/ssw.h states for ssw_find_angle_rgb8 -- integers only, so the device results must
+EQUAL them (tests/test_angle_gpu.py imports them).  Checked here: the cases the constants of the ladder were chosen on (the cat
+turned by Pillow), the tie rules, the smallest ranges, the host's table of C(n), S(n) against Python's for every angle, and the
+Python, CLI and C++ surfaces."""
+import functools
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+from PIL import Image
+
+from conftest import GOLDEN, ROOT
+from spread_spectrum_watermarking_amd import _lib as L
+from spread_spectrum_watermarking_amd import api, cli
+from test_jpeg_cpu import cat_image
+from test_rotate_cpu import rotation_matrix_ref
+
+STEP, KEEP, NEAR, PER_DEGREE = 8, 4, 7, 32
+
+
+# ---- the restatement ---------------------------------------------------------------------------------------------------------
+def angle_table_ref(n):
+    """(C, S) of the angle n / 32 degrees: Pillow's matrix entries m0, m1 in 16.16 fixed point, rounded half up in doubles"""
+    m = rotation_matrix_ref(n / 32.0, 0, 0)
+    return math.floor(m[0] * 65536 + 0.5), math.floor(m[1] * 65536 + 0.5)
+
+
+def luma_ref(frame):
+    f = frame.astype(np.int64)
+    return (77 * f[:, :, 0] + 150 * f[:, :, 1] + 29 * f[:, :, 2] + 128) >> 8
+
+
+def plane_ref(frame, f):
+    """The plane of factor f of a frame u8 [H, W, 3], int64: the luma (f = 1), its decimated 4 x 4 box means (f = 4)"""
+    lum = luma_ref(frame)
+    if f == 1:
+        return lum
+    hr, wr = lum.shape[0] >> 2, lum.shape[1] >> 2
+    return (lum[:4 * hr, :4 * wr].reshape(hr, 4, wr, 4).sum(axis=(1, 3)) + 8) >> 4
+
+
+def angle_cost_ref(Po, Ps, W, H, f, n):
+    """(D, c) of the angle n at factor f: the planes Po, Ps [hr, wr] int64 of a W x H frame"""
+    C, S = angle_table_ref(n)
+    sh = 17 + {1: 0, 4: 2}[f]
+    hr, wr = Ps.shape
+    X, Y = np.arange(wr, dtype=np.int64)[None, :], np.arange(hr, dtype=np.int64)[:, None]
+    p, q = 2 * f * X + f - W, 2 * f * Y + f - H
+    Rx, Ry = (W - f) * 65536 + C * p + S * q, (H - f) * 65536 - S * p + C * q
+    X0, Y0, fx, fy = Rx >> sh, Ry >> sh, (Rx >> (sh - 8)) & 255, (Ry >> (sh - 8)) & 255
+    valid = (X0 >= 1) & (X0 <= wr - 3) & (Y0 >= 1) & (Y0 <= hr - 3)
+    x, y, fx, fy = X0[valid], Y0[valid], fx[valid], fy[valid]
+    v = ((256 - fx) * (256 - fy) * Po[y, x] + fx * (256 - fy) * Po[y, x + 1] + (256 - fx) * fy * Po[y + 1, x] + fx * fy * Po[y + 1, x + 1] + 32768) >> 16
+    return int(np.abs(Ps[valid] - v).sum()), int(valid.sum())
+
+
+def rungs_ref(amin, amax):
+    return max(-180, math.floor(4 * amin)), min(180, math.ceil(4 * amax))
+
+
+def _before(a, b):
+    """(D, c, index) a before b: the smaller mean, cross-multiplied, ties to the smaller index"""
+    l, r = a[0] * b[1], b[0] * a[1]
+    return -1 if l < r or (l == r and a[2] < b[2]) else 1
+
+
+class FoundRef:
+    def __init__(self, n, D, c, j0, j1, rungs, kept, refined):
+        self.n, self.D, self.c, self.j0, self.j1, self.rungs, self.kept, self.refined = n, D, c, j0, j1, rungs, kept, refined
+        self.angle = n / PER_DEGREE
+
+
+def find_angle_ref(base, suspect, amin, amax):
+    """The answer (n, D, c), every rung's (D, c), the kept rungs (indices j - j0, best first) and every refined (n, D, c)"""
+    H, W = base.shape[:2]
+    j0, j1 = rungs_ref(amin, amax)
+    Po4, Ps4 = plane_ref(base, 4), plane_ref(suspect, 4)
+    rungs = [angle_cost_ref(Po4, Ps4, W, H, 4, STEP * j) for j in range(j0, j1 + 1)]
+    order = sorted(((D, c, i) for i, (D, c) in enumerate(rungs)), key=functools.cmp_to_key(_before))
+    kept = [i for _, _, i in order[:KEEP]]
+    ns = []
+    for i in kept:
+        ns += [n for n in range(STEP * (j0 + i) - NEAR, STEP * (j0 + i) + NEAR + 1) if STEP * j0 <= n <= STEP * j1 and n not in ns]
+    Po1, Ps1 = plane_ref(base, 1), plane_ref(suspect, 1)
+    refined = [(n,) + angle_cost_ref(Po1, Ps1, W, H, 1, n) for n in sorted(ns)]
+    D, c, n = sorted(((D, c, n) for n, D, c in refined), key=functools.cmp_to_key(_before))[0]
+    return FoundRef(n, D, c, j0, j1, rungs, kept, refined)
+
+
+# ---- cases -------------------------------------------------------------------------------------------------------------------
+FILL = (200, 30, 120)
+FILTERS = {"BICUBIC": Image.BICUBIC, "BILINEAR": Image.BILINEAR}
+# (true angle, Pillow's filter, range): the truth is on the 1/32 degree grid
+ON_GRID = [(-2.5, "BICUBIC", (-10, 10)), (5.0, "BILINEAR", (-10, 10)), (0.03125, "BICUBIC", (-1, 1)), (-7.96875, "BICUBIC", (-8, 8)),
+           (30.0, "BICUBIC", (-45, 45)), (-45.0, "BILINEAR", (-45, 45)), (3.4375, "BICUBIC", (3, 4))]
+# (true angle, the grid angle that answers it): the cat plus +-3 noise, range +-10
+OFF_GRID = [(0.7, 0.6875), (-3.3, -3.3125), (7.9, 7.90625), (0.1, 0.125), (-9.6, -9.59375)]
+FURTHER = [1.0, -0.15625, 0.0]
+
+
+@functools.lru_cache(maxsize=1)
+def cat():
+    return cat_image()
+
+
+@functools.lru_cache(maxsize=1)
+def marked_cat():
+    return np.asarray(Image.open(os.path.join(GOLDEN, "watermarked_with_1.png")).convert("RGB"))
+
+
+@functools.lru_cache(maxsize=1)
+def noisy_cat():
+    d = np.random.default_rng(7).integers(-3, 4, cat().shape)
+    return np.clip(cat().astype(np.int64) + d, 0, 255).astype(np.uint8)
+
+
+def turned(frame, angle, filt="BICUBIC", fill=FILL):
+    return np.asarray(Image.fromarray(frame).rotate(angle, resample=FILTERS[filt], fillcolor=fill))
+
+
+def smooth(w, h, seed=0):
+    """A smooth random field: a random quarter-size frame resized up with Pillow's bicubic"""
+    small = np.random.default_rng(1000 * w + h + seed).integers(0, 256, (max(2, h // 4), max(2, w // 4), 3), dtype=np.uint8)
+    return np.asarray(Image.fromarray(small).resize((w, h), Image.BICUBIC))
+
+
+# ---- 1. the cases the constants were chosen on ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("angle,filt,search", ON_GRID, ids=lambda v: str(v))
+def test_an_angle_on_the_grid_is_found_exactly(angle, filt, search):
+    assert marked_cat().shape == cat().shape
+    f = find_angle_ref(cat(), turned(marked_cat(), angle, filt), *search)
+    print(angle, filt, search, "->", f.angle, f.D / f.c, "kept", [(f.j0 + i) / 4 for i in f.kept], "rungs", len(f.rungs))
+    assert f.n == round(32 * angle) and f.angle == angle
+    assert 2.0 < f.D / f.c < 4.5                                       # a marked copy's own distance, not a wrong angle's
+    assert all(abs((f.j0 + i) / 4 - angle) <= 0.5 for i in f.kept[:3])  # the best three rungs are the truth's neighbours
+    assert len(f.rungs) == {(-45, 45): 361, (3, 4): 5}.get(search, len(f.rungs))
+
+
+@pytest.mark.parametrize("angle,answer", OFF_GRID, ids=lambda v: str(v))
+def test_an_angle_off_the_grid_lands_on_the_grid_angle_stated(angle, answer):
+    f = find_angle_ref(cat(), turned(noisy_cat(), angle), -10, 10)
+    near = {n: round(D / c, 4) for n, D, c in f.refined if abs(n - 32 * angle) < 3}
+    print(angle, "->", f.angle, f.D / f.c, near)
+    assert f.angle == answer
+
+
+@pytest.mark.parametrize("angle", FURTHER)
+def test_further_angles_are_found_exactly(angle):
+    f = find_angle_ref(cat(), turned(marked_cat(), angle), -10, 10)
+    assert f.angle == angle
+
+
+# ---- 2. ties and the smallest ranges --------------------------------------------------------------------------------------------
+def test_a_flat_frame_ties_everywhere():
+    flat = np.full((40, 52, 3), 93, np.uint8)
+    f = find_angle_ref(flat, flat, -3, 3)
+    assert all(D == 0 and c > 0 for D, c in f.rungs) and len(f.rungs) == 25
+    assert f.kept == [0, 1, 2, 3]                                       # ties to the smaller j
+    assert (f.n, f.D) == (-96, 0) and f.n == STEP * f.j0                # ... and to the smaller n
+    assert [n for n, _, _ in f.refined] == list(range(-96, -96 + 3 * STEP + NEAR + 1))      # each n once
+
+
+def test_a_range_of_one_angle():
+    base = smooth(96, 64)
+    f = find_angle_ref(base, turned(base, 1.0), 1.0, 1.0)
+    assert (f.j0, f.j1, len(f.rungs), f.kept) == (4, 4, 1, [0]) and [n for n, _, _ in f.refined] == [32] and f.n == 32
+
+
+def test_a_range_with_two_rungs():
+    base = smooth(96, 64)
+    f = find_angle_ref(base, turned(base, 0.34375), 0.3, 0.4)
+    assert (f.j0, f.j1, len(f.rungs)) == (1, 2, 2) and sorted(f.kept) == [0, 1]
+    assert [n for n, _, _ in f.refined] == list(range(8, 17))           # inside 8 j0 .. 8 j1 only
+    assert 8 <= f.n <= 16
+
+
+def test_every_pixel_counts_once_and_a_frame_matches_itself():
+    base = smooth(65, 41)
+    D, c = angle_cost_ref(plane_ref(base, 1), plane_ref(base, 1), 65, 41, 1, 0)
+    assert (D, c) == (0, (65 - 3) * (41 - 3))                           # angle 0: X0 = X, fx = 0; valid 1 .. wr - 3
+    D4, c4 = angle_cost_ref(plane_ref(base, 4), plane_ref(base, 4), 65, 41, 4, 0)
+    assert plane_ref(base, 4).shape == (10, 16) and c4 == (16 - 3) * (10 - 3)
+    assert angle_table_ref(0) == (65536, 0) and angle_table_ref(32 * 45) == (46341, -46341) and angle_table_ref(-960) == (56756, 32768)
+
+
+# ---- 3. the host's table -----------------------------------------------------------------------------------------------------
+def build_exe(tmp, name, sources, sanitize, extra=()):
+    exe = str(tmp / (name + ("_san" if sanitize else "")))
+    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
+    done = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", *flags, "-I", os.path.join(ROOT, "spread_spectrum_watermarking_amd", "csrc"),
+                           "-I", os.path.join(ROOT, "include"), *extra, *[os.path.join(ROOT, "tests", "cpp", s) for s in sources], "-o", exe],
+                          check=True, capture_output=True, text=True)
+    assert done.stderr == "", done.stderr
+    return exe
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_host_table_is_pythons_for_every_angle(tmp_path, sanitize):
+    exe = build_exe(tmp_path, "angle_tables_test", ["angle_tables_test.cpp"], sanitize)
+    out = subprocess.run([exe, "table"], check=True, capture_output=True, text=True)
+    assert out.stderr == ""
+    lines = out.stdout.splitlines()
+    assert len(lines) == 2881
+    for n, line in zip(range(-1440, 1441), lines):
+        assert tuple(int(v) for v in line.split()) == (n,) + angle_table_ref(n), n
+    ranges = [(-10, 10), (-45, 45), (3, 4), (1.0, 1.0), (0.3, 0.4), (-0.5, 0.5), (-45, -44.9), (0.26, 0.49)]
+    out = subprocess.run([exe, "rungs"] + [float(v).hex() for r in ranges for v in r], check=True, capture_output=True, text=True).stdout
+    assert [tuple(int(v) for v in line.split()) for line in out.splitlines()] == [(1,) + rungs_ref(*r) for r in ranges]
+    bad = [(1.0, 0.5), (-45.25, 0), (0, 45.5), (float("nan"), 1), (0, float("inf"))]
+    out = subprocess.run([exe, "rungs"] + [float(v).hex() for r in bad for v in r], check=True, capture_output=True, text=True).stdout
+    assert [line.split()[0] for line in out.splitlines()] == ["0"] * len(bad)
+
+
+def test_the_library_exports_the_table():
+    import ctypes as C
+    lib = L.load()
+    c, s = C.c_int32(), C.c_int32()
+    for n in (-1440, -253, -1, 0, 1, 22, 960, 1440):
+        assert lib.ssw_angle_table(n, C.byref(c), C.byref(s)) == L.SSW_OK and (c.value, s.value) == angle_table_ref(n)
+    assert lib.ssw_angle_table(0, None, C.byref(s)) == L.SSW_ERR_BAD_ARG and lib.ssw_angle_table(0, C.byref(c), None) == L.SSW_ERR_BAD_ARG
+
+
+# ---- 4. the surfaces ---------------------------------------------------------------------------------------------------------
+def test_header_declares_what_the_loader_binds():
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ssw.h")).read(), flags=re.S)
+    assert re.search(r"int ssw_find_angle_rgb8\(ssw_ctx\* ctx, const uint8_t\* dev_base, const uint8_t\* dev_suspects, size_t n, size_t w, size_t h,\s*"
+                     r"double amin, double amax, ssw_angle_found\* host_found, uint64_t\* host_rungs\);", text)
+    assert "int ssw_angle_table(int32_t n, int32_t* c, int32_t* s);" in text
+    assert "typedef struct ssw_angle_found { int32_t n; uint32_t n_rungs; uint64_t sad, count; } ssw_angle_found;" in text
+    assert re.search(r"SSW_STAGE_COUNT = 15\b", text) and len(L.STAGES) == 15
+    import ctypes as C
+    assert len(L.SIGNATURES["ssw_find_angle_rgb8"][1]) == 10 and L.SIGNATURES["ssw_find_angle_rgb8"][1][6:8] == [C.c_double, C.c_double]
+    assert [f[0] for f in L.AngleFound._fields_] == ["n", "n_rungs", "sad", "count"] and C.sizeof(L.AngleFound) == 24
+
+
+def test_python_surface_without_a_gpu():
+    z = np.zeros((40, 40, 3), np.uint8)
+    assert api.Rotated(1.5).angle == 1.5 and api.Rotated(1.5).search == (-10.0, 10.0)
+    assert api.Rotated().angle is None and api.Rotated().search == (-10.0, 10.0) and api.Rotated(search=(-2, 3)).search == (-2.0, 3.0)
+    assert api.find_angle(z, []) == []
+    for bad in (lambda: api.Rotated(search=(2, 1)), lambda: api.Rotated(search=(-46, 0)), lambda: api.Rotated(search=(0, 45.5)),
+                lambda: api.Rotated(search=(float("nan"), 1)), lambda: api.Rotated(search=(1,)), lambda: api.Rotated(search=("0", 1)),
+                lambda: api.Rotated(search=None), lambda: api.Rotated("1"),
+                lambda: api.find_angle(z, [z], search=(3, 2)), lambda: api.find_angle(z, [z], search=(0, 50)),
+                lambda: api.find_angle(z, [np.zeros((40, 41, 3), np.uint8)]), lambda: api.find_angle(z, [np.zeros((40, 40, 4), np.uint8)]),
+                lambda: api.find_angle(np.zeros((31, 40, 3), np.uint8), [np.zeros((31, 40, 3), np.uint8)]),
+                lambda: api.find_angle(z.astype(np.float32), [z]),
+                lambda: api._undo_rotated(None, [z], [api.Rotated()], None),
+                lambda: api._undo_rotated(z, [np.zeros((40, 40, 4), np.uint8)], [api.Rotated()], None)):
+        with pytest.raises(ValueError):
+            bad()
+
+
+def test_undoing_makes_one_search_per_range_and_one_unrotate():
+    """A call's searched entries are resolved together, and a call without them makes no search at all"""
+    z = np.zeros((40, 40, 3), np.uint8)
+    calls = []
+
+    def find(base, suspects, search, ctx):
+        calls.append(("find", len(suspects), search))
+        return [api.FoundAngle(0.25 * (i + 1), 8 * (i + 1), 10, 5, 2.0) for i in range(len(suspects))]
+
+    def unrotate(base, suspects, angles, ctx):
+        calls.append(("unrotate", list(angles)))
+        return [s + 1 for s in suspects]
+
+    pl = [api.Rotated(), None, api.Rotated(3.0), api.Rotated(), api.Placement(0, 0)]
+    sus, out, found = api._undo_rotated(z, [z] * 5, pl, None, find, unrotate)
+    assert calls == [("find", 2, (-10.0, 10.0)), ("unrotate", [0.25, 3.0, 0.5])]
+    assert out == [None, None, None, None, api.Placement(0, 0)] and sorted(found) == [0, 3] and found[3].n == 16
+    assert [int(s[0, 0, 0]) for s in sus] == [1, 0, 1, 1, 0]
+    calls.clear()
+    api._undo_rotated(z, [z] * 2, [api.Rotated(1.0), api.Rotated(-2.0)], None, find, unrotate)
+    assert calls == [("unrotate", [1.0, -2.0])]                        # what it did before there was a search
+    calls.clear()
+    api._undo_rotated(z, [z] * 3, [api.Rotated(), api.Rotated(search=(0, 5)), api.Rotated()], None, find, unrotate)
+    assert [c[:3] for c in calls[:2]] == [("find", 2, (-10.0, 10.0)), ("find", 1, (0.0, 5.0))] and len(calls) == 3
+
+
+def test_cli_parsing():
+    assert cli.parse_place("a.png=rotate:1.5") == ("a.png", api.Rotated(1.5))
+    assert cli.parse_place("a.png=rotate:?") == ("a.png", api.Rotated())
+    assert cli.parse_place("a.png=rotate:-3..4.5") == ("a.png", api.Rotated(search=(-3.0, 4.5)))
+    assert cli.parse_place("a=b.png=rotate:-1..-0.5") == ("a=b.png", api.Rotated(search=(-1.0, -0.5)))
+    assert cli.parse_place("a.png=3,4") == ("a.png", api.Placement(3, 4))
+    for bad in ("a.png=rotate:", "a.png=rotate:??", "a.png=rotate:5..1", "a.png=rotate:0..90", "a.png=rotate:x..1", "a.png=rotate:1..", "=rotate:?"):
+        with pytest.raises(ValueError):
+            cli.parse_place(bad)
+    assert cli.trace_placements(["a.png", "b.png"], ["b.png=rotate:?"]) == {"b.png": api.Rotated()}
+    assert cli.turned_text(api.FoundAngle(0.6875, 22, 270, 200, 1.35)) == "0.6875 (mean luma difference 1.35)"
+    assert cli.turned_text(api.FoundAngle(30.03125, 961, 300, 100, 3.0)) == "30.03125 (mean luma difference 3.00)"
+    assert cli.turned_text(api.FoundAngle(-1.0, -32, 0, 10, 0.0)) == "-1 (mean luma difference 0.00)"
+
+
+# ---- 5. the C++ wrapper --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_cpp_wrapper_against_a_stub(tmp_path, sanitize):
+    """wm::find_angle (include/ssw_angle.hpp) over a stub of the two C functions: argument order, vector sizes, a thrown status
+    with nothing left alive -- a stand-alone program, plain and under ASan/UBSan"""
+    exe = build_exe(tmp_path, "angle_wrappers_test", ["angle_wrappers_test.cpp", "angle_stub.cpp", "ssw_stub.cpp"], sanitize)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stderr == "", out.stdout + out.stderr
+    assert out.stdout.splitlines()[-1] == "angle wrappers: ok"
