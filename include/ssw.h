@@ -979,12 +979,84 @@ int ssw_rotation_matrix(double angle, size_t w, size_t h, double* m);
    SSW_STAGE_LOCATE_COARSE (work: byte differences), as ssw_locate_rgb8 bills its own.
    n == 0 is checked first: SSW_OK.  SSW_ERR_BAD_ARG: a null pointer, a range that is not finite, reversed or beyond +-45;
    SSW_ERR_BAD_DIMS: a side below 32 (with this limit c > 0 at every angle of the range); SSW_ERR_UNSUPPORTED: w h > 2^27
-   (the cross-multiplied products stay below 2^63).  Not searched: a copy that was turned AND cropped or scaled, a rotation
-   about another centre.  The answer's resolution is 1/32 degree. */
+   (the cross-multiplied products stay below 2^63).  Not searched: a copy that was turned AND scaled; a copy that was turned and
+   cropped, or turned about another centre, is ssw_locate_turned_rgb8's.  The answer's resolution is 1/32 degree. */
 typedef struct ssw_angle_found { int32_t n; uint32_t n_rungs; uint64_t sad, count; } ssw_angle_found;
 int ssw_find_angle_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const uint8_t* dev_suspects, size_t n, size_t w, size_t h,
                         double amin, double amax, ssw_angle_found* host_found, uint64_t* host_rungs);
 int ssw_angle_table(int32_t n, int32_t* c, int32_t* s);
+
+/* ---- locating cut-outs of a turned copy: angle and position together (csrc/locate_turned.hip) --------------------------------
+   "Straighten by a degree" turns a picture and crops the wedges away: what reaches the tracer is a cut-out of a turned frame,
+   its angle and its position both unknown.  Everything is an integer and no sum depends on its order: the answer equals the
+   numpy restatement of tests/test_locate_turned_cpu.py exactly.  The reference has no counterpart.
+   Inputs.  The original O = dev_base [h][w][3] u8, here W x H; per suspect S = dev_suspects[i] [sh][sw][3] u8, shapes[i] =
+   (sw, sh, channels).  A range amin <= amax in degrees, counter-clockwise as PIL.Image.rotate, within +-45.  The suspect is
+   taken to be an axis-aligned crop of the original's frame turned about any centre, at the original's scale and without any of
+   the attacker's fill.
+   Angles and planes.  An angle is n / 32 degrees; C(n), S(n) are those of ssw_angle_table.  Lo, Ls: the luma
+   (77 R + 150 G + 29 B + 128) >> 8 of O and S.
+   Template of angle n at size tw x th: the suspect's luma turned back about its own centre.  For 0 <= X < tw, 0 <= Y < th
+   (64-bit integers, arithmetic shifts):
+       p  = 2 X + 1 - tw                           q  = 2 Y + 1 - th
+       Rx = (sw - 1) * 65536 + C p - S q           Ry = (sh - 1) * 65536 + S p + C q
+       X0 = Rx >> 17, fx = (Rx >> 9) & 255; Y0, fy likewise of Ry
+       T(X, Y) = ((256-fx)(256-fy) Ls[Y0][X0] + fx (256-fy) Ls[Y0][X0+1] + (256-fx) fy Ls[Y0+1][X0] + fx fy Ls[Y0+1][X0+1] + 32768) >> 16
+   A pixel is valid when 0 <= X0 <= sw - 2 and 0 <= Y0 <= sh - 2.
+   Template size of angle n: the largest i in 1 .. sw / 8 for which the four corner pixels of the template tw = 8 i,
+   th = 8 max(1, (2 i sh + sw) / (2 sw)) are valid.  Rx and Ry are monotone in X and in Y, so the corners bound every tap: every
+   pixel of a template is valid.  The angle is dropped when there is no such i, when min(tw, th) < 32, when tw > W or th > H.
+   Ladder.  j0 = floor(4 amin), j1 = ceil(4 amax); one rung per j, at the angle n = 8 j.  T_j: the 8 x 8 box means (sum + 32) >> 6
+   of the rung's template at multiples of 8.  B8: the box means of Lo of ssw_locate_scaled_rgb8, at every multiple of 4.
+   D_j(x, y) = sum |T_j(i, k) - B8(x + 8 i, y + 8 k)| at the candidate positions x <= W - tw, y <= H - th that are multiples of 4.
+   The rung's entry is its smallest (D, y, x); n_j = (tw / 8)(th / 8).
+   Kept: the 4 rungs of smallest D_j / n_j (all, when fewer are left), compared cross-multiplied in 64 bits, ties to the smaller j;
+   dropped rungs are never kept.
+   Refinement.  Every n within 7 of a kept rung's 8 j and inside 8 j0 .. 8 j1, each once: an angle within 7 of two kept rungs
+   belongs to the one of better rank.  A dropped angle is passed over.  For n, its own template tw_n x th_n at full resolution
+   takes steps 2-7 of ssw_locate_rgb8 (as the luma of R), the positions restricted to those within +-8 of
+   ((2 x_j + tw_j - tw_n) >> 1, (2 y_j + th_j - th_n) >> 1), clipped to the frame; an angle whose window is empty after the
+   clipping is passed over (the rung's own angle never is).
+   Answer.  The smallest SAD / (tw th), compared cross-multiplied; ties to the smaller n, then y, then x.  host_found[i] (a HOST
+   array of n): n, x, y, tw, th, sad and n_rungs = j1 - j0 + 1.  The suspect's centre lies at (2 x + tw, 2 y + th) half pixels of
+   the original, its angle is n / 32 degrees.  host_rungs (a HOST array, may be null): [n][n_rungs][4] = D, n_j, x, y of every
+   rung's entry, a dropped rung all zero.
+   The suspects go in groups of at most 256 MiB of luma planes (one suspect's, if larger); a launch holds at most 32 rungs and
+   256 MiB of boxes and differences; the refinement's templates go 256 MiB at a time.  The kept rungs are chosen on the host:
+   a group waits for the context's stream twice -- for the ladder's minima and for the answer -- and once more for every
+   further 256 MiB of templates.  Templates are timed under SSW_STAGE_RESIZE, the searches under SSW_STAGE_LOCATE and
+   SSW_STAGE_LOCATE_COARSE as ssw_locate_scaled_rgb8 bills its own.
+   n == 0 is checked first: SSW_OK.  SSW_ERR_BAD_ARG: a null pointer, channels other than 3 or 4, a range that is not finite,
+   reversed or beyond +-45; SSW_ERR_BAD_DIMS: a side of 0 or above 65535, every rung of a suspect dropped;
+   SSW_ERR_UNSUPPORTED: 4 channels, 2^32 or more candidate positions.  Not searched: a cut-out that was scaled as well, one
+   that holds the attacker's fill.  The answer's position grid is one pixel (the centre half a pixel): a half-pixel refinement
+   of the centre is the step after.
+   ssw_locate_turned_rung_boxes: *tw, *th = the template size of angle n (-1440 .. 1440) for a suspect sw x sh, and, unless
+   host_boxes is null, host_boxes [th / 8][tw / 8] = its T_j as the device makes it (for tests; waits for the stream).
+   SSW_ERR_BAD_ARG: a null pointer, n out of range; SSW_ERR_BAD_DIMS: a side of 0 or above 65535, no valid size. */
+typedef struct ssw_turned_shape { uint32_t w, h, channels; } ssw_turned_shape;
+typedef struct ssw_turned_found { int32_t n; uint32_t x, y, tw, th, n_rungs; uint64_t sad; } ssw_turned_found;
+int ssw_locate_turned_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
+                           const ssw_turned_shape* shapes, size_t n, double amin, double amax, ssw_turned_found* host_found,
+                           uint64_t* host_rungs);
+int ssw_locate_turned_rung_boxes(ssw_ctx* ctx, const void* dev_suspect, size_t sw, size_t sh, int32_t n, uint32_t* tw, uint32_t* th,
+                                 uint8_t* host_boxes);
+/* Restoring a cut-out of a turned copy whose angle and centre are known (found by ssw_locate_turned_rgb8, or given): what a
+   tracer does with it before ssw_fingerprint_trace.  jobs[i] = (angle, cx, cy) in doubles for suspect i: turned by `angle`
+   degrees, its centre at (cx, cy) pixels of the original; the found ones are n / 32, x + tw / 2.0 and y + th / 2.0.  b is the
+   matrix of ssw_rotation_matrix(-angle, ...), of which only the entries 0, 1, 3 and 4 are used, and
+       m = [b0, b1, (b0 * -cx + b1 * -cy + 0.0) + sw / 2.0, b3, b4, (b3 * -cx + b4 * -cy + 0.0) + sh / 2.0],
+   every operation rounded on its own.  dev_out[i] [h][w][3]: a pixel is what PIL.Image.transform((w, h), AFFINE, m, BICUBIC)
+   makes of the suspect -- the arithmetic of ssw_affine_rgb8, steps 1-3 and 5 -- where the sample point is inside the suspect and
+   the footprint needs no clamping (x-1 >= 0, x+2 <= sw-1, y-1 >= 0, y+2 <= sh-1); elsewhere the original's pixel stands, the
+   reference's recipe for lost pixels as in ssw_unrotate_rgb8.  The restored frames equal `restore_turned_ref` of
+   tests/test_locate_turned_cpu.py byte for byte.  One launch per suspect, no frame in between; only enqueues on the context's
+   stream; timed under SSW_STAGE_RESIZE (work 3 sw sh + 3 w h bytes per suspect).
+   n == 0 is checked first: SSW_OK.  SSW_ERR_BAD_ARG: a null pointer, channels other than 3 or 4, a job that is not finite, an
+   output that overlaps an input; SSW_ERR_BAD_DIMS: a side of 0 or above 65535; SSW_ERR_UNSUPPORTED: 4 channels. */
+typedef struct ssw_turned_job { double angle, cx, cy; } ssw_turned_job;
+int ssw_restore_turned_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
+                            const ssw_turned_shape* shapes, const ssw_turned_job* jobs, size_t n, uint8_t* dev_out);
 
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,

@@ -112,6 +112,24 @@ class AngleFound(C.Structure):
     _fields_ = [("n", C.c_int32), ("n_rungs", C.c_uint32), ("sad", C.c_uint64), ("count", C.c_uint64)]
 
 
+class TurnedShape(C.Structure):
+    """ssw_turned_shape (include/ssw.h): a suspect of ssw_locate_turned_rgb8 -- its width, height and channels."""
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("channels", C.c_uint32)]
+
+
+class TurnedFound(C.Structure):
+    """ssw_turned_found (include/ssw.h): one answer of ssw_locate_turned_rgb8 -- the angle is n / 32 degrees, the template tw x th
+    lies at (x, y) of the original with the sum of absolute luma differences sad."""
+    _fields_ = [("n", C.c_int32), ("x", C.c_uint32), ("y", C.c_uint32), ("tw", C.c_uint32), ("th", C.c_uint32), ("n_rungs", C.c_uint32),
+                ("sad", C.c_uint64)]
+
+
+class TurnedJob(C.Structure):
+    """ssw_turned_job (include/ssw.h): one suspect of ssw_restore_turned_rgb8 -- turned by `angle` degrees, its centre at (cx, cy)
+    pixels of the original."""
+    _fields_ = [("angle", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
 ANGLE_PER_DEGREE = 32        # ssw_find_angle_rgb8: the answer's resolution
 ANGLE_MIN_SIDE = 32          # ... refuses smaller frames
 ANGLE_MAX_PIXELS = 1 << 27   # ... and larger ones
@@ -231,6 +249,10 @@ SIGNATURES = {
     "ssw_affine_plan": (C.c_int, [_sz, _sz, C.POINTER(C.c_double), C.POINTER(C.c_int), _u32p, _u32p]),
     "ssw_rotation_matrix": (C.c_int, [C.c_double, _sz, _sz, C.POINTER(C.c_double)]),
     "ssw_find_angle_rgb8": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, C.c_double, C.c_double, C.POINTER(AngleFound), _u64p]),
+    "ssw_locate_turned_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(C.c_void_p), C.POINTER(TurnedShape), _sz, C.c_double, C.c_double,
+                                         C.POINTER(TurnedFound), _u64p]),
+    "ssw_restore_turned_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(C.c_void_p), C.POINTER(TurnedShape), C.POINTER(TurnedJob), _sz, _vp]),
+    "ssw_locate_turned_rung_boxes": (C.c_int, [_vp, _vp, _sz, _sz, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _vp]),
     "ssw_angle_table": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ssw_ssim_rgb8": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64p, _vp]),
     "ssw_fingerprint_trace_restored_host_rgb8": (C.c_int, [_vp, _cfgp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, _sz, _f32p, _sz, C.c_float,

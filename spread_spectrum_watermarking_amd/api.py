@@ -21,7 +21,7 @@ import ctypes as C
 import math
 from contextlib import contextmanager
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Any, Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -529,12 +529,15 @@ class Reader:
             turned = {}
             if any(isinstance(p, Rotated) for p in placements):          # turned copies: one angle search, one unrotate call
                 suspects, placements, turned = _undo_rotated(base, suspects, placements, self._ctx)
+            located_turned = {}
+            if any(isinstance(p, Locate) and p.turned_range() for p in placements):      # cut-outs of a turned copy: found and laid back
+                suspects, placements, located_turned = _undo_turned_cuts(base, suspects, placements, self._ctx)
             if any(isinstance(p, Locate) for p in placements):           # cut-outs at an unknown position: one locate call
                 placements, _ = _resolve_locates(base, suspects, placements, self._ctx)
             arrs, ptrs, pl = _placed_suspects(suspects, placements, self.width, self.height)
             m, k = _trace_marks(marks, k)
             res = TraceResult.empty(len(arrs), m.shape[0], k)
-            res.turned = turned
+            res.turned, res.located_turned = turned, located_turned
             b = None if base is None else _base_rgb8(base, self.width, self.height)
             check(self._lib.ssw_reader_trace_restored_host_rgb8(self._h, b.ctypes.data if b is not None else None, ptrs, pl, len(arrs), k,
                                                                 *res._args(m, threshold)), "Reader::trace")
@@ -658,6 +661,7 @@ class TraceResult:
     n_exceed: np.ndarray
     threshold: float = 6.0
     turned: dict = field(default_factory=dict)      # {suspect: FoundAngle} of the `Rotated` entries whose angle was searched for
+    located_turned: dict = field(default_factory=dict)      # {suspect: LocatedTurned} of the `Locate(turned=...)` entries
     NONE = L.TRACE_NONE
 
     @staticmethod
@@ -734,14 +738,27 @@ class Locate:
     """A placement entry that says "find me": the suspect is a cut-out of the original at an unknown position; w x h is the
     size it had in the original's frame (None: its own size).  When that size is not known either: `widths=(lo, hi)`, the
     widths it may have had in the original, or `scale=(lo, hi)`, the same as factors of the suspect's own width (0.5: it was
-    enlarged to twice its size after it was cut out) -- found by the scale ladder of ssw_locate_scaled_rgb8."""
+    enlarged to twice its size after it was cut out) -- found by the scale ladder of ssw_locate_scaled_rgb8.  `turned=(lo, hi)`,
+    or `turned=True` for +-10 degrees: the suspect is a cut-out of the frame TURNED by an unknown angle in that range -- what a
+    photo editor's "straighten" leaves --, at the original's scale: angle and centre are found together (`locate_turned`) and the
+    suspect is laid back into the frame (`restore_turned`).  `turned=` goes with none of the others."""
     w: Optional[int] = None
     h: Optional[int] = None
     widths: Optional[Tuple[int, int]] = None
     scale: Optional[Tuple[float, float]] = None
+    turned: Any = None
+
+    def turned_range(self) -> Optional[Tuple[float, float]]:
+        """(lo, hi) in degrees of a `turned=` entry, None for any other."""
+        if self.turned is None or self.turned is False:
+            return None
+        if self.w is not None or self.h is not None or self.widths is not None or self.scale is not None:
+            raise ValueError("Locate: turned= goes with none of (w, h), widths= and scale=")
+        return _search((-10.0, 10.0) if self.turned is True else self.turned, "Locate(turned=)")
 
     def width_range(self, suspect_width: int) -> Optional[Tuple[int, int]]:
         """(wmin, wmax) of a ranged entry -- scale factors rounded outwards --, None for an entry of known size."""
+        self.turned_range()                                      # (refuses turned= beside the others)
         if self.widths is None and self.scale is None:
             return None
         if (self.widths is not None and self.scale is not None) or self.w is not None or self.h is not None:
@@ -794,7 +811,7 @@ def locate(base, suspects, sizes=None, ctx: Optional[Context] = None) -> list:
     cut-out is not supported).  sizes: None, or per suspect a `Locate(w, h)` / (w, h) pair / None -- the size the cut-out
     had in the original when it was scaled afterwards --, or a `Locate(widths=(lo, hi))` / `Locate(scale=(lo, hi))` when that
     size is unknown: those entries go through the scale ladder (ssw_locate_scaled_rgb8; aspect ratio kept, the smaller side at
-    least 32) and `Located.size` says what was found.  Returns one `Located` per suspect.  A turned cut-out is not found, and a
+    least 32) and `Located.size` says what was found.  Returns one `Located` per suspect.  A turned cut-out is `locate_turned`'s; a
     cut-out of a featureless region (the cat's grey background) is ambiguous."""
     ctx = ctx or default_context()
     b = _base_rgb8(base)
@@ -808,6 +825,8 @@ def locate(base, suspects, sizes=None, ctx: Optional[Context] = None) -> list:
     sizes = list(sizes) if sizes is not None else [None] * len(arrs)
     if len(sizes) != len(arrs):
         raise ValueError("sizes: one entry (a Locate, a (w, h) pair or None) per suspect")
+    if any(isinstance(z, Locate) and z.turned_range() for z in sizes):
+        raise ValueError("locate: a Locate(turned=...) entry is searched for with locate_turned")
     ranges = [z.width_range(a.shape[1]) if isinstance(z, Locate) else None for a, z in zip(arrs, sizes)]
     if any(r is not None for r in ranges):
         return _locate_mixed(ctx, b, arrs, sizes, ranges)
@@ -885,11 +904,14 @@ def restore(base, suspects, placements=None, ctx: Optional[Context] = None) -> l
     without w / h at (0, 0), means "whole frame" when the suspect's size differs from the original's (a scaled copy), and
     "own size at (x, y)" otherwise (a cut-out, or an RGBA image of full size).  An alpha channel is filtered like a colour
     channel and blended over the original: alpha 0 keeps the original's pixel.  A `Locate(w, h)` entry is a cut-out whose
-    position is not known: all such entries are found with one `locate` call first and then treated as that Placement."""
+    position is not known: all such entries are found with one `locate` call first and then treated as that Placement; a
+    `Locate(turned=...)` entry is found with `locate_turned` and comes back as `restore_turned` makes it."""
     ctx = ctx or default_context()
     b = _base_rgb8(base)
     H, W = b.shape[:2]
     suspects = list(suspects)
+    if placements is not None and any(isinstance(p, Locate) and p.turned_range() for p in placements):
+        suspects, placements, _ = _undo_turned_cuts(b, suspects, placements, ctx)
     if placements is not None and any(isinstance(p, Locate) for p in placements):
         placements, _ = _resolve_locates(b, suspects, placements, ctx)
     arrs, _, pl = _placed_suspects(suspects, placements if placements is not None else [None] * len(suspects), W, H)
@@ -915,7 +937,8 @@ def trace_many(base, suspects, marks, k: Optional[int] = None, threshold: float 
     unknown position -- are found with one `locate` call first.  `Rotated(angle)` entries -- copies of the original's size that
     were turned by a known angle -- are turned back with one `unrotate` call first and traced as whole frames; `Rotated()`
     entries, whose angle is not known, are searched for with one `find_angle` call before that (`TraceResult.turned` says what
-    was found)."""
+    was found).  `Locate(turned=...)` entries -- cut-outs of a copy turned by an unknown angle -- are found with one `locate_turned`
+    call per distinct range and laid back into the frame with one `restore_turned` call (`TraceResult.located_turned`)."""
     ctx = ctx or default_context()
     config = config or ReadConfig.default()
     if placements is not None:
@@ -923,12 +946,15 @@ def trace_many(base, suspects, marks, k: Optional[int] = None, threshold: float 
         turned = {}
         if any(isinstance(p, Rotated) for p in placements):
             suspects, placements, turned = _undo_rotated(b, suspects, placements, ctx)
+        located_turned = {}
+        if any(isinstance(p, Locate) and p.turned_range() for p in placements):
+            suspects, placements, located_turned = _undo_turned_cuts(b, suspects, placements, ctx)
         if any(isinstance(p, Locate) for p in placements):
             placements, _ = _resolve_locates(b, suspects, placements, ctx)
         arrs, ptrs, pl = _placed_suspects(suspects, placements, b.shape[1], b.shape[0])
         m, k = _trace_marks(marks, k)
         res = TraceResult.empty(len(arrs), m.shape[0], k)
-        res.turned = turned
+        res.turned, res.located_turned = turned, located_turned
         cfg = config._c()
         check(ctx._lib.ssw_fingerprint_trace_restored_host_rgb8(ctx.handle, C.byref(cfg), b.ctypes.data, b.shape[1], b.shape[0], ptrs, pl,
                                                                 len(arrs), k, *res._args(m, threshold)),
@@ -1713,7 +1739,8 @@ def find_angle(base, suspects, search=DEFAULT_ANGLE_SEARCH, ctx: Optional[Contex
     degrees apart on 4 x 4 box means, the 4 best rungs refined in steps of 1/32 degree at full resolution -- exactly reproducible,
     see include/ssw.h for the definition.  base: the original, 8-bit [H, W, 3], both sides at least 32; suspects: 8-bit [H, W, 3]
     of that size; search: (lo, hi) in degrees, within +-45.  Returns one `FoundAngle` per suspect; with rungs=True also the
-    ladder's sums, uint64 [n][rungs][2] = D, c.  A copy that was turned and cropped or scaled is not found."""
+    ladder's sums, uint64 [n][rungs][2] = D, c.  A copy that was turned and cropped is `locate_turned`'s; one that was turned and
+    scaled is not found."""
     lo, hi = _search(search, "find_angle")
     b = _frames_u8([base], "find_angle")[0]
     frames = _frames_u8(suspects, "find_angle")
@@ -1740,6 +1767,109 @@ def find_angle(base, suspects, search=DEFAULT_ANGLE_SEARCH, ctx: Optional[Contex
             sums[g0:g0 + len(g)] = part
             found += [FoundAngle(int(f.n) / L.ANGLE_PER_DEGREE, int(f.n), int(f.sad), int(f.count), int(f.sad) / max(1, int(f.count))) for f in got]
     return (found, sums) if rungs else found
+
+
+@dataclass
+class LocatedTurned:
+    """Where a cut-out of a turned copy lies and by which angle it was turned (ssw_locate_turned_rgb8): `angle` = n / 32 degrees,
+    counter-clockwise as PIL.Image.rotate's; `centre`, the (x, y) of the suspect's centre in pixels of the original (a multiple
+    of one half); `template`, the (w, h) of the turned-back part of the suspect that was compared; `sad`, the sum of absolute luma
+    differences there; `mean_abs_diff` = sad / (w h of the template) -- a few units for a true match of a marked copy."""
+    angle: float
+    n: int
+    centre: Tuple[float, float]
+    template: Tuple[int, int]
+    sad: int
+    mean_abs_diff: float
+
+
+def locate_turned(base, suspects, search=DEFAULT_ANGLE_SEARCH, ctx: Optional[Context] = None, rungs: bool = False):
+    """Where does each suspect lie, and by which angle was it turned?  For cut-outs of a turned copy -- what "straighten" in a
+    photo editor leaves: the frame turned, the wedges cropped away --, a search over angle and position together on the device
+    (ssw_locate_turned_rgb8): per angle of a ladder 0.25 degrees apart the suspect is turned back about its own centre and its
+    8 x 8 box means searched for in the original's, the 4 best rungs are refined in steps of 1/32 degree at full resolution --
+    exactly reproducible, see include/ssw.h for the definition.  base: the original, 8-bit [H, W, 3]; suspects: 8-bit [h, w, 3]
+    of any sizes, at the original's scale and without the attacker's fill; search: (lo, hi) in degrees, within +-45.  Returns
+    one `LocatedTurned` per suspect; with rungs=True also the ladder's entries, uint64 [n][rungs][4] = D, n_j, x, y (a dropped
+    rung: zeros).  A cut-out that was scaled as well is not found."""
+    lo, hi = _search(search, "locate_turned")
+    b = _base_rgb8(base)
+    H, W = b.shape[:2]
+    arrs = [np.ascontiguousarray(np.asarray(im)) for im in suspects]
+    for a in arrs:
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or 0 in a.shape:
+            raise ValueError("locate_turned: suspects are 8-bit [h, w, 3] arrays (RGBA is not supported)")
+    n = len(arrs)
+    n_rungs = min(180, math.ceil(4.0 * hi)) - max(-180, math.floor(4.0 * lo)) + 1
+    entries = np.zeros((n, n_rungs, 4), np.uint64)
+    if not arrs:
+        return ([], entries) if rungs else []
+    ctx = ctx or default_context()
+    with _owned(ctx) as alloc:
+        dev_b = _upload_frames(ctx, alloc(b.nbytes), [b])
+        dev = [_upload_frames(ctx, alloc(a.nbytes), [a]) for a in arrs]
+        ptrs = (C.c_void_p * n)(*[d.ptr.value for d in dev])
+        shapes = (L.TurnedShape * n)(*[L.TurnedShape(a.shape[1], a.shape[0], 3) for a in arrs])
+        got = (L.TurnedFound * n)()
+        check(ctx._lib.ssw_locate_turned_rgb8(ctx.handle, dev_b.ptr, W, H, ptrs, shapes, n, lo, hi, got, entries.ctypes.data), "ssw_locate_turned_rgb8")
+    found = [LocatedTurned(int(f.n) / L.ANGLE_PER_DEGREE, int(f.n), (int(f.x) + int(f.tw) / 2.0, int(f.y) + int(f.th) / 2.0), (int(f.tw), int(f.th)),
+                           int(f.sad), int(f.sad) / (int(f.tw) * int(f.th))) for f in got]
+    return (found, entries) if rungs else found
+
+
+def restore_turned(base, suspects, found, ctx: Optional[Context] = None) -> list:
+    """Cut-outs of a turned copy laid back into the original's frame (ssw_restore_turned_rgb8): what tracing a
+    `Locate(turned=...)` entry extracts from.  found: per suspect a `LocatedTurned`, or an (angle, cx, cy) triple -- turned by
+    `angle` degrees counter-clockwise, its centre at (cx, cy) pixels of the original.  The suspect is turned back and moved with
+    Pillow's BICUBIC affine transform, exactly; where its footprint would need clamping, and outside it, the original's pixel
+    stands.  Returns one u8 [H, W, 3] frame per suspect."""
+    b = _base_rgb8(base)
+    H, W = b.shape[:2]
+    arrs = [np.ascontiguousarray(np.asarray(im)) for im in suspects]
+    for a in arrs:
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or 0 in a.shape:
+            raise ValueError("restore_turned: suspects are 8-bit [h, w, 3] arrays (RGBA is not supported)")
+    found = list(found)
+    if len(found) != len(arrs):
+        raise ValueError("restore_turned: one LocatedTurned or (angle, cx, cy) per suspect")
+    triples = [(f.angle, f.centre[0], f.centre[1]) if isinstance(f, LocatedTurned) else tuple(float(v) for v in f) for f in found]
+    if any(len(t) != 3 or not all(math.isfinite(v) for v in t) for t in triples):
+        raise ValueError("restore_turned: (angle, cx, cy), three finite numbers")
+    if not arrs:
+        return []
+    ctx = ctx or default_context()
+    n, fb = len(arrs), W * H * 3
+    with _owned(ctx) as alloc:
+        dev_b, dev_o = _upload_frames(ctx, alloc(fb), [b]), alloc(n * fb)
+        dev = [_upload_frames(ctx, alloc(a.nbytes), [a]) for a in arrs]
+        ptrs = (C.c_void_p * n)(*[d.ptr.value for d in dev])
+        shapes = (L.TurnedShape * n)(*[L.TurnedShape(a.shape[1], a.shape[0], 3) for a in arrs])
+        jobs = (L.TurnedJob * n)(*[L.TurnedJob(*t) for t in triples])
+        check(ctx._lib.ssw_restore_turned_rgb8(ctx.handle, dev_b.ptr, W, H, ptrs, shapes, jobs, n, dev_o.ptr), "ssw_restore_turned_rgb8")
+        return list(dev_o.to_host(np.uint8, (n, H, W, 3)))
+
+
+def _undo_turned_cuts(base, suspects, placements, ctx, locate_fn=None, restore_fn=None):
+    """placements with `Locate(turned=...)` entries -> (suspects, placements, {index: LocatedTurned}) with every such suspect laid
+    back into the frame and its entry None: a whole frame of the original's size.  One `locate_turned` call per distinct range,
+    one `restore_turned` call.  The other entries pass through untouched."""
+    placements, suspects = list(placements), list(suspects)
+    if len(placements) != len(suspects):
+        raise ValueError("placements: one entry (a Placement, a Locate, a Rotated or None) per suspect")
+    ranges = {i: p.turned_range() for i, p in enumerate(placements) if isinstance(p, Locate)}
+    todo = [i for i, r in ranges.items() if r is not None]
+    if not todo:
+        return suspects, placements, {}
+    if base is None:
+        raise ValueError("Locate(turned=) entries need the original's pixels (base=)")
+    b = _base_rgb8(base)
+    found = {}
+    for search in sorted({ranges[i] for i in todo}):
+        idx = [i for i in todo if ranges[i] == search]
+        found.update(zip(idx, (locate_fn or locate_turned)(b, [suspects[i] for i in idx], search, ctx)))
+    for i, f in zip(todo, (restore_fn or restore_turned)(b, [suspects[i] for i in todo], [found[i] for i in todo], ctx)):
+        suspects[i], placements[i] = f, None
+    return suspects, placements, found
 
 
 def _rotations(rotations, what: str) -> list:

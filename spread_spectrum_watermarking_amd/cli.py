@@ -10,7 +10,7 @@
         -> <stem>_fp<i>.png (i zero-padded) and one <stem>_fp.json holding the N marks, described "<desc> #i";
            `test <file> <stem>_fp<i>.png <stem>_fp.json` then names the copy that leaked
     python -m spread_spectrum_watermarking_amd.cli trace <base> --suspects A.png B.png ... --marks X_fp.json [Y.json ...]
-            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] | FILE=rotate:DEGREES | FILE=rotate:? | FILE=rotate:LO..HI ...] [--locate FILE[=WxH|=W0..W1] ...]
+            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] | FILE=rotate:DEGREES | FILE=rotate:? | FILE=rotate:LO..HI ...] [--locate FILE[=WxH|=W0..W1|=rotate:?|=rotate:LO..HI] ...]
         -> one record per suspect: the stored mark it carries (or none) and every further mark above the threshold;
            one GPU call per group of stored marks with equal (config, length), whatever the number of suspects.
            Attacked copies are restored on the GPU first (tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70): a
@@ -21,7 +21,9 @@
            one search on the GPU, and the record says "Turned:".
            --locate finds where a cut-out belongs (the size WxH it had in the base when it was scaled afterwards) by a
            search over every translation on the GPU; its record says "Located:" too.  FILE=W0..W1: the size is not known
-           either, only that the cut-out was between W0 and W1 wide in the base -- a search over scale as well
+           either, only that the cut-out was between W0 and W1 wide in the base -- a search over scale as well.
+           FILE=rotate:? (or FILE=rotate:LO..HI): the cut-out was taken from a copy TURNED by an unknown angle -- a search over
+           angle and position together; the record says "Located: centre X,Y turned DEGREES"
     python -m spread_spectrum_watermarking_amd.cli index FILES... -o catalogue.npz [--marks FILE_fp.json ...]
         -> creates catalogue.npz or appends to it: one signature (1024 bytes) per original, with its size and the marks file
            that goes with it (given in the order of FILES, else <stem>_fp.json beside the image where that exists)
@@ -57,7 +59,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from ._lib import COLLUDE_METHODS
-from .api import (IDENTIFY_MAX_DISTANCE, Catalogue, Filter, Locate, MarkBuf, Placement, Reader, Rotate, Rotated, Scale, Tester, TraceResult, Writer, identify, locate,
+from .api import (IDENTIFY_MAX_DISTANCE, Catalogue, Filter, Locate, MarkBuf, Placement, Reader, Rotate, Rotated, Scale, Tester, TraceResult, Writer, identify, locate, locate_turned, restore_turned,
                   strength_report)
 from .storage import Configuration, DescribedWatermark, Version1Storage
 
@@ -189,6 +191,16 @@ def parse_locate(text: str, suspects: List[str]) -> Tuple[str, Locate]:
     if text in suspects:
         return text, Locate()
     name, sep, spec = text.rpartition("=")
+    if spec.startswith("rotate:"):                       # a cut-out of a turned copy: angle and position are both unknown
+        try:
+            if not sep or not name:
+                raise ValueError
+            lo, dots, hi = spec[len("rotate:"):].partition("..")
+            z = Locate(turned=True) if (lo, dots, hi) == ("?", "", "") else Locate(turned=(float(lo), float(hi)))
+            z.turned_range()
+        except ValueError:
+            raise ValueError(f"--locate {text!r}: expected FILE=rotate:? or FILE=rotate:LO..HI, degrees within +-45") from None
+        return name, z
     if ".." in spec:                                     # a range of widths: the scale is unknown
         lo, _, hi = spec.partition("..")
         if not sep or not name or not (lo.isascii() and lo.isdigit() and hi.isascii() and hi.isdigit()):
@@ -208,6 +220,12 @@ def located_text(f, ranged: bool) -> str:
     """The record's "Located:" value; an entry whose size was searched for says what was found."""
     size = f" as {f.placement.w}x{f.placement.h}" if ranged else ""
     return f"{f.placement.x},{f.placement.y}{size} (mean luma difference {f.mean_abs_diff:.2f})"
+
+
+def located_turned_text(f) -> str:
+    """The record's "Located:" value of a cut-out of a turned copy (f: a LocatedTurned)."""
+    degrees = f"{f.angle:.5f}".rstrip("0").rstrip(".")          # n / 32: five decimals are all there are
+    return f"centre {f.centre[0]:.1f},{f.centre[1]:.1f} turned {degrees} (mean luma difference {f.mean_abs_diff:.2f})"
 
 
 def trace_locates(suspects: List[str], locates: Optional[List[str]], placed: Dict[str, Placement]) -> Dict[str, Locate]:
@@ -285,9 +303,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Where the cut-out FILE (one of --suspects) lies in the base, and the size it had there; "
                         "FILE=rotate:DEGREES: a copy turned by a known angle; FILE=rotate:? or FILE=rotate:LO..HI: the angle is "
                         "searched for. Repeatable.")
-    r.add_argument("--locate", action="append", metavar="FILE[=WxH|=W0..W1]",
+    r.add_argument("--locate", action="append", metavar="FILE[=WxH|=W0..W1|=rotate:?|=rotate:LO..HI]",
                    help="Find where the cut-out FILE (one of --suspects) lies in the base; WxH: the size it had there; "
-                        "W0..W1: the widths it may have had there (the scale is searched too). Repeatable.")
+                        "W0..W1: the widths it may have had there (the scale is searched too); rotate:? or rotate:LO..HI: it was "
+                        "cut out of a turned copy (angle and position are searched together). Repeatable.")
     x = sub.add_parser("index", help="Add originals to an image catalogue (created when it does not exist).")
     x.add_argument("files", nargs="+", help="The originals.")
     x.add_argument("-o", "--output", required=True, metavar="CATALOGUE.npz", help="The catalogue file.")
@@ -575,6 +594,20 @@ def cmd_trace(args, out=sys.stdout) -> int:
     placed: Dict[str, Placement] = dict(getattr(args, "placements", {}))
     located: Dict[str, str] = {}
     wanted = [(path, img, z) for path, img in zip(args.suspects, suspects) for z in [getattr(args, "locates", {}).get(path)] if z is not None]
+    # ... and every cut-out of a turned copy with one call per range; laid back into the frame, it is a whole frame from here on
+    laid_back: Dict[str, str] = {}
+    cuts = [(path, img, z) for path, img, z in wanted if z.turned_range() is not None]
+    wanted = [(path, img, z) for path, img, z in wanted if z.turned_range() is None]
+    for path, img, _ in cuts:
+        if img.shape[2] != 3:
+            raise SystemExit(f"{path}: a cut-out of a turned copy has no alpha channel")
+    for search in sorted({z.turned_range() for _, _, z in cuts}):
+        group = [(path, img) for path, img, z in cuts if z.turned_range() == search]
+        found = locate_turned(base, [img for _, img in group], search)
+        for (path, _), f, frame in zip(group, found, restore_turned(base, [img for _, img in group], found)):
+            suspects[args.suspects.index(path)] = frame
+            located[path] = located_turned_text(f)
+            laid_back[path] = f"turned back by {f.angle:g} degrees about {f.centre[0]:.1f},{f.centre[1]:.1f}, completed with the base"
     for path, img, z in wanted:
         if z.widths is not None:
             continue                                     # the ladder drops the widths that do not fit
@@ -588,6 +621,10 @@ def cmd_trace(args, out=sys.stdout) -> int:
     for path, img in zip(args.suspects, suspects):
         sh, sw, c = img.shape
         p = placed.get(path)
+        if path in laid_back:
+            placements.append(None)
+            restored.append(laid_back[path])
+            continue
         if isinstance(p, Rotated):
             if (sw, sh, c) != (W, H, 3):
                 raise SystemExit(f"{path}: a turned copy has the base's size ({W}x{H}) and no alpha channel")

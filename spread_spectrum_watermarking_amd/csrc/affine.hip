@@ -14,12 +14,15 @@
 //   any conversion to an integer; a tap index is clamped to the frame, and in the LDS form to the box as well.
 //   UNDO: the transform by `m` (BICUBIC), then the mask of include/ssw.h -- the footprint needs no clamping and `fwd` puts its
 //   four corners inside --, and where the mask fails the original's byte: one launch, no frame in between.
+// affine_cutout_kernel: the undoing of a cut-out of a turned copy (ssw_restore_turned_rgb8) -- a source of another size than the
+//   output, the mask the footprint alone; a kernel of its own, so that the family above compiles to what it compiled to before.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "affine_tables.hpp"
 #include "ssw_host.hpp"
+#include "turned_tables.hpp"
 
 #pragma clang fp contract(off)
 
@@ -170,6 +173,36 @@ __global__ __launch_bounds__(AFFINE_THREADS) void affine_kept_kernel(AffineArgs 
     const bool keep = X < a.w && Y < a.h && af_undo_keeps(a, X, Y);
     const unsigned long long votes = __ballot(keep);
     if ((threadIdx.x & 63) == 0 && votes) atomicAdd(count, (unsigned long long)__popcll(votes));
+}
+
+// The undoing of a cut-out of a turned copy (ssw_restore_turned_rgb8): the suspect [h][w][3] laid back into the original's frame
+// [oh][ow][3] by a.m (BICUBIC) where the sample point is inside and the footprint needs no clamping, the original's byte elsewhere
+// -- one launch, no frame in between.  Under the mask no tap is clamped, so the taps come from global memory as they are.
+// grid: (tiles across, tiles down); block: AFFINE_THREADS
+__global__ __launch_bounds__(AFFINE_THREADS) void affine_cutout_kernel(AffineArgs a, const uint8_t* __restrict__ in, const uint8_t* __restrict__ base,
+                                                                       uint8_t* __restrict__ out) {
+    const uint32_t X = blockIdx.x * AFFINE_TILE_W + threadIdx.x % AFFINE_TILE_W, Y = blockIdx.y * AFFINE_TILE_H + threadIdx.x / AFFINE_TILE_W;
+    if (X >= a.ow || Y >= a.oh) return;
+    const size_t o = ((size_t)Y * a.ow + X) * 3;
+    double xin, yin;
+    affine_point(a.m, X, Y, xin, yin);
+    bool keep = affine_inside(xin, yin, a.w, a.h);          // on the doubles, before any conversion
+    int x = 0, y = 0;
+    double dx = 0.0, dy = 0.0;
+    if (keep) {
+        xin -= 0.5; yin -= 0.5;
+        const double fx = floor(xin), fy = floor(yin);
+        x = (int)fx; y = (int)fy;
+        dx = xin - fx; dy = yin - fy;
+        keep = x - 1 >= 0 && x + 2 <= (int)a.w - 1 && y - 1 >= 0 && y + 2 <= (int)a.h - 1;
+    }
+    if (!keep) {
+        out[o] = base[o]; out[o + 1] = base[o + 1]; out[o + 2] = base[o + 2];
+        return;
+    }
+    const AffineSource<false> s{in, a.w};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[o + c] = af_sample<AFFINE_BICUBIC>(s, x, y, dx, dy, (int)a.w, (int)a.h, c);
 }
 
 namespace host {
@@ -360,6 +393,40 @@ extern "C" int ssw_unrotate_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const ui
                                    dev_out + j0 * fb));
         }
         j0 = j1;
+    }
+    return SSW_OK;
+}
+
+extern "C" int ssw_restore_turned_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
+                                       const ssw_turned_shape* shapes, const ssw_turned_job* jobs, size_t n, uint8_t* dev_out) {
+    using namespace ssw::host;
+    if (!ctx) return SSW_ERR_BAD_ARG;
+    if (n == 0) return SSW_OK;
+    if (!dev_base || !dev_suspects || !shapes || !jobs || !dev_out) return SSW_ERR_BAD_ARG;
+    for (size_t i = 0; i < n; ++i)
+        if (!dev_suspects[i] || (shapes[i].channels != 3 && shapes[i].channels != 4) || !std::isfinite(jobs[i].angle) || !std::isfinite(jobs[i].cx) ||
+            !std::isfinite(jobs[i].cy)) return SSW_ERR_BAD_ARG;
+    if (!af_side_ok(w) || !af_side_ok(h)) return SSW_ERR_BAD_DIMS;
+    for (size_t i = 0; i < n; ++i)
+        if (!af_side_ok(shapes[i].w) || !af_side_ok(shapes[i].h)) return SSW_ERR_BAD_DIMS;
+    const size_t fb = w * h * 3;
+    for (size_t i = 0; i < n; ++i) {
+        if (shapes[i].channels == 4) return SSW_ERR_UNSUPPORTED;
+        if (af_overlaps((const uint8_t*)dev_suspects[i], (size_t)shapes[i].w * shapes[i].h * 3, dev_out, n * fb)) return SSW_ERR_BAD_ARG;
+    }
+    if (af_overlaps(dev_base, fb, dev_out, n * fb)) return SSW_ERR_BAD_ARG;
+    CtxGuard g(ctx);
+    double bytes = 0.0;
+    for (size_t i = 0; i < n; ++i) bytes += 3.0 * (double)shapes[i].w * shapes[i].h + (double)fb;
+    StageTimer t(ctx, SSW_STAGE_RESIZE, ctx->stream, bytes);
+    const dim3 grid((unsigned)((w + ssw::AFFINE_TILE_W - 1) / ssw::AFFINE_TILE_W), (unsigned)((h + ssw::AFFINE_TILE_H - 1) / ssw::AFFINE_TILE_H));
+    for (size_t i = 0; i < n; ++i) {
+        ssw::AffineArgs a{};
+        ssw::turned_restore_matrix(jobs[i].angle, jobs[i].cx, jobs[i].cy, shapes[i].w, shapes[i].h, a.m);
+        if (!af_finite(a.m, 6)) return SSW_ERR_BAD_ARG;
+        a.w = shapes[i].w; a.h = shapes[i].h; a.ow = (uint32_t)w; a.oh = (uint32_t)h;
+        ssw::affine_cutout_kernel<<<grid, ssw::AFFINE_THREADS, 0, ctx->stream>>>(a, (const uint8_t*)dev_suspects[i], dev_base, dev_out + i * fb);
+        SSW_HIP_CHECK(hipGetLastError());
     }
     return SSW_OK;
 }

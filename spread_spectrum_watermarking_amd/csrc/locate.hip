@@ -425,7 +425,7 @@ int restore_prepare_rgb(ssw_ctx* ctx, std::vector<ssw_placement> pl) {
 }
 
 // placements (and the windows of a refinement) -> what each search needs; SSW_ERR_UNSUPPORTED: a position is 32 bits of the key
-int plan_items(const std::vector<ssw_placement>& pl, const std::vector<LocWindow>* win, size_t w, size_t h, std::vector<Item>* items) {
+int plan_items(const std::vector<ssw_placement>& pl, const std::vector<LocWindow>* win, size_t w, size_t h, bool luma_planes, std::vector<Item>* items) {
     items->resize(pl.size());
     for (size_t i = 0; i < pl.size(); ++i) {
         Item& it = (*items)[i];
@@ -451,7 +451,7 @@ int plan_items(const std::vector<ssw_placement>& pl, const std::vector<LocWindow
         size_t o = 0;
         it.off_rgb = o;   o += rs ? up((size_t)it.p.pw * it.p.ph * 3, 256) : 0;
         it.off_strip = o; o += rs && it.p.channels == 4 ? up((size_t)it.p.w * it.p.h * 3, 256) : 0;
-        it.off_lr = o;    o += up((size_t)it.rpitch * it.p.ph, 256);
+        it.off_lr = o;    o += luma_planes ? 0 : up((size_t)it.rpitch * it.p.ph, 256);      // (a luma plane is read where it lies)
         it.off_sf = o;    o += it.f == 4 ? up((size_t)it.tpitch * it.th, 256) : 0;
         it.bytes_d = up((size_t)it.nx * it.ny * 4, 256);
         it.off_d = o;     o += it.bytes_d;
@@ -484,7 +484,7 @@ struct Original { const uint8_t* lo; unsigned opitch, h; const uint8_t* phases; 
 // The searches of the suspects [b0, b0 + m) of a group, m <= LOC_BATCH, whose R (where resized) is in the workspace ws: luma,
 // S_f, coarse search, the 8 best of it, their full-resolution SADs and the answer into res
 int enqueue_batch(ssw_ctx* ctx, const std::vector<Item>& items, const Group& g, size_t b0, unsigned m, const void* const* dev_suspects,
-                  uint8_t* ws, const Original& og, uint64_t* keys, uint64_t* sums, uint64_t* res) {
+                  uint8_t* ws, const Original& og, uint64_t* keys, uint64_t* sums, uint64_t* res, bool luma_planes) {
     hipStream_t st = ctx->stream;
     LumaBatch lb{};
     BoxBatch bb{};
@@ -498,21 +498,22 @@ int enqueue_batch(ssw_ctx* ctx, const std::vector<Item>& items, const Group& g, 
         const Item& it = items[b0 + s];
         uint8_t* wsi = ws + g.base_off[b0 + s - g.g0];
         const bool rs = resized(it.p), own = !g.shared[b0 + s - g.g0], f4 = it.f == 4;
-        if (own) lb.it[nl++] = LumaDev{rs ? wsi + it.off_rgb : (const uint8_t*)dev_suspects[b0 + s], wsi + it.off_lr, it.p.pw, it.p.ph,
+        const uint8_t* lr = luma_planes ? (const uint8_t*)dev_suspects[b0 + s] : wsi + it.off_lr;
+        if (own && !luma_planes) lb.it[nl++] = LumaDev{rs ? wsi + it.off_rgb : (const uint8_t*)dev_suspects[b0 + s], wsi + it.off_lr, it.p.pw, it.p.ph,
                                        rs ? 3u : it.p.channels, it.rpitch};
         max_words = std::max(max_words, it.rpitch / 4);
         max_rows = std::max(max_rows, it.p.ph);
         if (f4 && own) {
-            bb.it[nbox++] = BoxDev{wsi + it.off_lr, wsi + it.off_sf, it.rpitch, it.p.pw, it.p.ph, it.tpitch, it.tw, it.th, 1u, 0u};
+            bb.it[nbox++] = BoxDev{lr, wsi + it.off_sf, it.rpitch, it.p.pw, it.p.ph, it.tpitch, it.tw, it.th, 1u, 0u};
             max_q = std::max(max_q, it.tpitch);
             max_qrows = std::max(max_qrows, it.th);
         }
         cb.it[s] = coarse_desc(f4 ? og.phases : og.lo, f4 ? og.qpitch : og.opitch, f4 ? og.hq : og.h, f4 ? og.plane_stride : 0,
-                               wsi + (f4 ? it.off_sf : it.off_lr), it.tpitch, it.tw, it.th, (uint32_t*)(ws + g.d_off[b0 + s - g.g0]), it.nx, it.ny,
+                               f4 ? wsi + it.off_sf : lr, it.tpitch, it.tw, it.th, (uint32_t*)(ws + g.d_off[b0 + s - g.g0]), it.nx, it.ny,
                                it.f, it.bx, it.by, &tiles);
         tb.it[s] = TopDev{cb.it[s].D, it.nx * it.ny, it.nx, it.skipx, it.skipy};
         max_n = std::max(max_n, it.nx * it.ny);
-        fb.it[s] = FineDev{wsi + it.off_lr, it.rpitch, it.p.pw, it.p.ph, it.nx, it.bx, it.by};
+        fb.it[s] = FineDev{lr, it.rpitch, it.p.pw, it.p.ph, it.nx, it.bx, it.by};
         max_ph = std::max(max_ph, it.p.ph);
         bd += (double)it.nx * it.ny * ((double)it.tw * it.th);
     }
@@ -571,11 +572,11 @@ int locate_box4_planes(ssw_ctx* ctx, const uint8_t* luma, size_t luma_stride, un
 }
 
 int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
-                const std::vector<ssw_placement>& pl, uint64_t* host_res, const std::vector<LocWindow>* win) {
+                const std::vector<ssw_placement>& pl, uint64_t* host_res, const std::vector<LocWindow>* win, bool luma_planes) {
     const size_t n = pl.size();
     hipStream_t st = ctx->stream;
     std::vector<Item> items;
-    SSW_TRY(plan_items(pl, win, w, h, &items));
+    SSW_TRY(plan_items(pl, win, w, h, luma_planes, &items));
     const bool any_f4 = std::any_of(items.begin(), items.end(), [](const Item& it) { return it.f == 4; });
     // the original: luma plane once per call, and its 16 phase planes when a suspect takes the coarse factor 4
     const unsigned wq = (unsigned)(w / 4), hq = (unsigned)(h / 4), qpitch = (unsigned)up(std::max(wq, 1u), 4);
@@ -629,7 +630,7 @@ int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const
         }
         StageTimer t(ctx, SSW_STAGE_LOCATE, st, px_bytes);
         for (size_t b0 = g0; b0 < g.g1; b0 += LOC_BATCH)
-            SSW_TRY(enqueue_batch(ctx, items, g, b0, (unsigned)std::min<size_t>(LOC_BATCH, g.g1 - b0), dev_suspects, ws, og, keys, sums, res));
+            SSW_TRY(enqueue_batch(ctx, items, g, b0, (unsigned)std::min<size_t>(LOC_BATCH, g.g1 - b0), dev_suspects, ws, og, keys, sums, res, luma_planes));
         g0 = g.g1;
     }
     SSW_HIP_CHECK(hipMemcpyAsync(host_res, res, n * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -903,6 +904,55 @@ int rung_boxes_impl(ssw_ctx* ctx, const void* dev_suspect, const ssw_placement& 
     untimed_work(ctx);
     SSW_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (uint32_t k = 0; k < r.th; ++k) std::memcpy(host_t + (size_t)k * r.tw, t.data() + (size_t)k * r.dev.tpitch, r.tw);
+    return SSW_OK;
+}
+
+// ---- for the ladder of another file (locate_turned.hip) ------------------------------------------------------------------------
+static_assert(LOCATE_KEY_STRIDE == LOC_TOP && LOCATE_BATCH == LOC_BATCH, "ssw_host.hpp states both");
+
+int locate_box8_planes(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const uint8_t** planes, unsigned* qpitch, unsigned* qrows,
+                       size_t* plane_stride) {
+    const unsigned nbx = (unsigned)((w - 8) / 4 + 1), nby = (unsigned)((h - 8) / 4 + 1);
+    *qpitch = (unsigned)up((nbx + 1) / 2, 4); *qrows = (nby + 1) / 2;
+    *plane_stride = (size_t)*qpitch * *qrows;
+    if (4 * *plane_stride > 0xFFFFFFFFull) return SSW_ERR_UNSUPPORTED;
+    uint8_t* out = nullptr;
+    SSW_TRY(grow_as(ctx->locate.box_planes, 4 * *plane_stride + 16, out));
+    StageTimer t(ctx, SSW_STAGE_LOCATE, ctx->stream, (double)w * h * 4.5);
+    uint8_t* lo = nullptr;
+    unsigned opitch = 0;
+    SSW_TRY(original_luma(ctx, dev_base, w, h, &lo, &opitch));
+    locate_box8_kernel<<<dim3((*qpitch + 255) / 256, grid_rows(*qrows)), 256, 0, ctx->stream>>>(lo, opitch, (unsigned)w, (unsigned)h, out, *qpitch, *qrows,
+                                                                                                   (unsigned)*plane_stride);
+    SSW_HIP_CHECK(hipGetLastError());
+    *planes = out;
+    return SSW_OK;
+}
+
+int locate_box_searches(ssw_ctx* ctx, const uint8_t* planes, unsigned qpitch, unsigned qrows, size_t plane_stride, const BoxSearch* it, unsigned m,
+                        uint64_t* keys) {
+    CoarseBatch cb{};
+    TopBatch tb{};
+    unsigned tiles = 0;
+    uint32_t max_n = 1;
+    double bd = 0.0, px_bytes = 0.0;
+    for (unsigned s = 0; s < m; ++s) {
+        const BoxSearch& b = it[s];
+        cb.it[s] = coarse_desc(planes, qpitch, qrows, plane_stride, b.T, b.tpitch, b.tw, b.th, b.D, b.nx, b.ny, 2u, 0u, 0u, &tiles);
+        tb.it[s] = TopDev{b.D, b.nx * b.ny, 0u, 0u, 0u};
+        max_n = std::max(max_n, b.nx * b.ny);
+        bd += (double)b.nx * b.ny * ((double)b.tw * b.th);
+        px_bytes += 8.0 * b.nx * b.ny + (double)b.tw * b.th;
+    }
+    StageTimer t(ctx, SSW_STAGE_LOCATE, ctx->stream, px_bytes);
+    {
+        StageTimer tc(ctx, SSW_STAGE_LOCATE_COARSE, ctx->stream);
+        if (ctx->timing) ctx->stage_work[SSW_STAGE_LOCATE_COARSE] += bd;              // byte differences, not bytes
+        locate_coarse_kernel<<<tiles, 256, 0, ctx->stream>>>(cb, m);
+        SSW_HIP_CHECK(hipGetLastError());
+    }
+    locate_topk_kernel<<<dim3(topk_blocks(max_n), m), 256, 0, ctx->stream>>>(tb, keys, 0);
+    SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
 

@@ -203,8 +203,22 @@ int restore_enqueue(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, c
 // win (the refinement of ssw_locate_scaled_rgb8; null: every position): per entry the candidate positions x0..x1, y0..y1
 // (inclusive, valid ones) it searches, and whether it is the same suspect at the same size as the entry before it
 struct LocWindow { uint32_t x0, x1, y0, y1; bool share; };
+// luma_planes (the refinement of ssw_locate_turned_rgb8): dev_suspects[i] is not a frame but its luma plane already,
+// [ph][pw rounded up to 4] with zeros behind pw, read where it lies; pl[i] then has pw == w, ph == h.
 int locate_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
-                const std::vector<ssw_placement>& pl, uint64_t* host_res, const std::vector<LocWindow>* win = nullptr);
+                const std::vector<ssw_placement>& pl, uint64_t* host_res, const std::vector<LocWindow>* win = nullptr, bool luma_planes = false);
+// locate.hip's planes of the original for the ladders (ssw_locate_scaled_rgb8, ssw_locate_turned_rgb8), enqueued on the context's
+// stream: its luma plane (locate.luma) and the 2 x 2 phase planes of its 8 x 8 box means at every fourth position
+// (locate.box_planes), rows of *qpitch bytes, *qrows of them, *plane_stride bytes apart.  w, h >= 8.
+int locate_box8_planes(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const uint8_t** planes, unsigned* qpitch, unsigned* qrows,
+                       size_t* plane_stride);
+// ... and one launch of box searches over them, m <= LOCATE_BATCH: search s is the template T [th][tpitch] of tw x th box means
+// (tpitch % 4 == 0) at the nx x ny candidate positions (4 x, 4 y) into D [ny][nx]; keys[LOCATE_KEY_STRIDE s] (all ones before)
+// receives (D << 32) | (y nx + x) of its smallest (D, y, x).  Timed as ssw_locate_scaled_rgb8 times its ladder.
+constexpr unsigned LOCATE_BATCH = 32, LOCATE_KEY_STRIDE = 8;
+struct BoxSearch { const uint8_t* T; uint32_t* D; uint32_t tpitch, tw, th, nx, ny; };
+int locate_box_searches(ssw_ctx* ctx, const uint8_t* planes, unsigned qpitch, unsigned qrows, size_t plane_stride, const BoxSearch* it, unsigned m,
+                        uint64_t* keys);
 // locate.hip's plane kernels for the angle search (angle.hip), enqueued on the context's stream: the luma planes of n frames
 // [h][w][3] (rows of `pitch` bytes, pitch % 4 == 0), and of such planes the decimated 4 x 4 box means (h / 4 rows of `opitch` bytes)
 int locate_luma_planes(ssw_ctx* ctx, const uint8_t* rgb, size_t n, size_t w, size_t h, uint8_t* out, size_t out_stride, unsigned pitch);

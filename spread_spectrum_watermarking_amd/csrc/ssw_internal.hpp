@@ -401,7 +401,9 @@ SSW_BUF_GROUP(TraceBufs, SSW_TRACE_BUFS);
 // boxes; the refinement's resized cut-outs) | keys, sums, results | (scale ladder) the original's 8 x 8 box planes | its tap tables
 // angle.hip shares luma, phases (the original's one decimated plane) and group (the suspects' planes) and adds: C, S of every
 // angle of a call's range | answers, rung and refinement sums, the refinement's slot lists
-#define SSW_LOCATE_BUFS(X) X(luma) X(phases) X(group) X(keys) X(box_planes) X(taps) X(angle_tab) X(angle_sums)
+// locate_turned.hip shares luma, group (the ladder's boxes and D), keys, box_planes and angle_tab and adds: the suspects' luma
+// planes | the full-resolution template planes of one group of the refinement's searches
+#define SSW_LOCATE_BUFS(X) X(luma) X(phases) X(group) X(keys) X(box_planes) X(taps) X(angle_tab) X(angle_sums) X(turned_luma) X(turned_templates)
 SSW_BUF_GROUP(LocateBufs, SSW_LOCATE_BUFS);
 // catalogue.hip: the blocks' top-8 lists of a match | host form: one group of frames | its signatures
 #define SSW_CATALOGUE_BUFS(X) X(top8) X(frames) X(sigs)
