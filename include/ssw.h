@@ -986,6 +986,36 @@ int ssw_find_angle_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const uint8_t* de
                         double amin, double amax, ssw_angle_found* host_found, uint64_t* host_rungs);
 int ssw_angle_table(int32_t n, int32_t* c, int32_t* s);
 
+/* ---- the rotation attack undone by the angle FOUND: the strength report's unknown-angle row (csrc/angle.hip) -----------------
+   What does a turn leave of the mark when the tracer is NOT told the angle?  Job i is defined entirely by calls above:
+     T_i       = what ssw_affine_rgb8 makes of frame jobs[i].frame of dev_frames [n_frames][h][w][3] with jobs[i].forward, filter
+                 and fill at the frame's own size -- the first half of ssw_rotate_attack_rgb8.  jobs[i].back is NOT read.
+     found_i   = what ssw_find_angle_rgb8(dev_base, T_i, amin, amax) answers: host_found[i] (n, n_rungs, sad, count) and, when
+                 host_rungs (a HOST array, may be null) is given, [n_jobs][n_rungs][2] = D, c of every rung.  Ladder, the 4 kept
+                 rungs, tie rules and refinement are that call's; no constant differs.
+     dev_out[i] [h][w][3] = what ssw_unrotate_rgb8 makes of T_i over dev_base for the job whose forward is
+                 ssw_rotation_matrix(n_i / 32, w, h) and whose back is ssw_rotation_matrix(-n_i / 32, w, h): turned back by the
+                 angle found and completed with the original (n_i = 0: a copy of T_i).
+     host_kept[i] (a HOST array of n_jobs) = what ssw_unrotate_kept counts for that job.
+     dev_turned (may be null): [n_jobs][h][w][3] receives T_i.
+   What runs.  All suspects of the call have one original, and the cost of an angle turns the ORIGINAL forward: the turned values
+   depend on (original, angle) only.  Jobs whose forward matrices are equal form share-groups of at most 16; angle_cost_shared_kernel
+   makes the turned values of a (tile, candidate angle) once and compares them with every member that wants the candidate -- in the
+   ladder every member wants every rung, in the refinement the candidates of a group are the union of its members' lists and a
+   member's sums go to its own slots only, so a neighbour never changes an answer.  The sums are integers: host_found and the
+   rungs EQUAL ssw_find_angle_rgb8's.  Jobs go in groups whose turned frames and planes are at most 256 MiB (one job's, if they
+   are larger); the call waits for the context's stream TWICE per group -- for the slot lists, of which the host forms the unions,
+   and for the answers, which shape the undoing -- and once more at its end (rung sums, kept counts), whatever the number of
+   suspects or angles.  Timed under SSW_STAGE_LOCATE / SSW_STAGE_LOCATE_COARSE (planes, ladder, refinement) and SSW_STAGE_RESIZE
+   (the turn and its undoing).
+   n_jobs == 0 is checked first: SSW_OK.  SSW_ERR_BAD_ARG: a null pointer (dev_turned and host_rungs excepted), a range that is
+   not finite, reversed or beyond +-45, frame >= n_frames, a filter that is not an ssw_affine_filter, a forward entry that is not
+   finite, an output that overlaps an input or the other output; SSW_ERR_BAD_DIMS: a side below 32 or above 65535;
+   SSW_ERR_UNSUPPORTED: w h > 2^27. */
+int ssw_rotate_search_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h,
+                                  const ssw_rotate_job* jobs, size_t n_jobs, double amin, double amax, uint8_t* dev_out,
+                                  uint8_t* dev_turned, ssw_angle_found* host_found, uint64_t* host_rungs, uint64_t* host_kept);
+
 /* ---- locating cut-outs of a turned copy: angle and position together (csrc/locate_turned.hip) --------------------------------
    "Straighten by a degree" turns a picture and crops the wedges away: what reaches the tracer is a cut-out of a turned frame,
    its angle and its position both unknown.  Everything is an integer and no sum depends on its order: the answer equals the

@@ -249,6 +249,8 @@ SIGNATURES = {
     "ssw_affine_plan": (C.c_int, [_sz, _sz, C.POINTER(C.c_double), C.POINTER(C.c_int), _u32p, _u32p]),
     "ssw_rotation_matrix": (C.c_int, [C.c_double, _sz, _sz, C.POINTER(C.c_double)]),
     "ssw_find_angle_rgb8": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, C.c_double, C.c_double, C.POINTER(AngleFound), _u64p]),
+    "ssw_rotate_search_attack_rgb8": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, C.POINTER(RotateJob), _sz, C.c_double, C.c_double, _vp, _vp,
+                                                C.POINTER(AngleFound), _u64p, _u64p]),
     "ssw_locate_turned_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(C.c_void_p), C.POINTER(TurnedShape), _sz, C.c_double, C.c_double,
                                          C.POINTER(TurnedFound), _u64p]),
     "ssw_restore_turned_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(C.c_void_p), C.POINTER(TurnedShape), C.POINTER(TurnedJob), _sz, _vp]),

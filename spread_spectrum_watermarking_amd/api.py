@@ -1648,18 +1648,25 @@ def rotate(images, angle, filter="bicubic", fill=(0, 0, 0), ctx: Optional[Contex
 class Rotate:
     """One attack of ssw_rotate_attack_rgb8: the copy as PIL.Image.rotate(angle, filter) makes it, turned back by the known
     angle and completed with the original as `trace` does it for a `Rotated(angle)` suspect.  angle: degrees counter-clockwise,
-    as Pillow's; filter: "bilinear" or "bicubic" (the default).  `label` names it in reports: "rotate 0.5 bicubic"."""
+    as Pillow's; filter: "bilinear" or "bicubic" (the default).  `label` names it in reports: "rotate 0.5 bicubic".
+    search: None (the default), or the range (lo, hi) of degrees within +-45 in which the tracer, who is NOT told the angle,
+    searches for it (True: -10 .. 10) -- the copy is then turned back by the angle found (ssw_rotate_search_attack_rgb8;
+    `strength_report` and `rotate_search_attack` read it, `job` does not); the label gains ", angle searched in -10..10"."""
     angle: float
     filter: str = "bicubic"
+    search: Optional[Tuple[float, float]] = None
 
     def __post_init__(self):
         _affine_filter(self.filter)
         object.__setattr__(self, "filter", self.filter.lower())
         object.__setattr__(self, "angle", _angle(self.angle, "Rotate"))
+        if self.search is not None:
+            object.__setattr__(self, "search", _search(DEFAULT_ANGLE_SEARCH if self.search is True else self.search, "Rotate"))
 
     @property
     def label(self) -> str:
-        return f"rotate {self.angle:g} {self.filter}"
+        searched = "" if self.search is None else f", angle searched in {self.search[0]:g}..{self.search[1]:g}"
+        return f"rotate {self.angle:g} {self.filter}{searched}"
 
     def job(self, frame: int, w: int, h: int, fill=(0, 0, 0)) -> L.RotateJob:
         return L.RotateJob(frame, L.AFFINE_FILTERS[self.filter], (C.c_uint8 * 4)(*fill, 0), (C.c_double * 6)(*rotation_matrix(self.angle, w, h)),
@@ -1908,6 +1915,56 @@ def rotate_attack(base, images, rotations, ctx: Optional[Context] = None) -> lis
     return _attack_every(ctx, frames, ro, _rotate_attack(w, h), b)
 
 
+def _found_angle(f) -> "FoundAngle":
+    return FoundAngle(int(f.n) / L.ANGLE_PER_DEGREE, int(f.n), int(f.sad), int(f.count), int(f.sad) / max(1, int(f.count)))
+
+
+def _search_ranges(rotations) -> list:
+    """[(range, positions in `rotations`)] of the entries that carry a search, ranges in the order of their first entry"""
+    ranges = {}
+    for i, r in enumerate(rotations):
+        if r.search is not None:
+            ranges.setdefault(r.search, []).append(i)
+    return list(ranges.items())
+
+
+def rotate_search_attack(base, images, rotations, ctx: Optional[Context] = None) -> tuple:
+    """Every image after every rotation attack when the tracer is NOT told the angle (ssw_rotate_search_attack_rgb8): turned as
+    Pillow does it, the angle searched for on the device as `find_angle` does (all copies of a call at once: they share the
+    original, so the original is turned once per candidate angle and compared with every copy), then turned back by the angle
+    FOUND and completed with `base`.  rotations: `Rotate` objects; the range is each one's `search` (None: -10 .. 10), one library
+    call per distinct range.  Returns (frames [len(images)][len(rotations)] u8 [H, W, 3], found [len(images)][len(rotations)]
+    of `FoundAngle`).  Both sides at least 32."""
+    frames, ro = _frames_u8(images, "rotate_search_attack"), _rotations(rotations, "rotate_search_attack")
+    ro = [r if r.search is not None else Rotate(r.angle, r.filter, True) for r in ro]
+    if not frames or not ro:
+        return [[] for _ in frames], [[] for _ in frames]
+    b = _frames_u8([base], "rotate_search_attack")[0]
+    if b.shape != frames[0].shape:
+        raise ValueError("rotate_search_attack: the original has the images' size")
+    h, w = b.shape[:2]
+    if min(w, h) < L.ANGLE_MIN_SIDE or w * h > L.ANGLE_MAX_PIXELS:
+        raise ValueError(f"rotate_search_attack: frames of at least {L.ANGLE_MIN_SIDE} x {L.ANGLE_MIN_SIDE} and at most 2^27 pixels")
+    ctx = ctx or default_context()
+    fb = w * h * 3
+    out, found = [[None] * len(ro) for _ in frames], [[None] * len(ro) for _ in frames]
+    for (lo, hi), which in _search_ranges(ro):
+        jobs = [(i, p) for i in range(len(frames)) for p in which]
+        for used, g0, g1 in _job_groups([(i,) for i, _ in jobs], fb):
+            where, n = {i: j for j, i in enumerate(used)}, g1 - g0
+            arr = (L.RotateJob * n)(*[ro[p].job(where[i], w, h) for i, p in jobs[g0:g1]])
+            got, kept = (L.AngleFound * n)(), np.zeros(n, np.uint64)
+            with _owned(ctx) as alloc:
+                dev_f, dev_o = alloc(len(used) * fb), alloc(n * fb)
+                _upload_frames(ctx, dev_f, [frames[i] for i in used])
+                dev_b = _upload_frames(ctx, alloc(fb), [b])
+                check(ctx._lib.ssw_rotate_search_attack_rgb8(ctx.handle, dev_b.ptr, dev_f.ptr, len(used), w, h, arr, n, lo, hi, dev_o.ptr, None, got,
+                                                             None, kept.ctypes.data), "ssw_rotate_search_attack_rgb8")
+                for (i, p), frame, f in zip(jobs[g0:g1], dev_o.to_host(np.uint8, (n, h, w, 3)), got):
+                    out[i][p], found[i][p] = frame, _found_angle(f)
+    return out, found
+
+
 def unrotate(base, suspects, angles, ctx: Optional[Context] = None) -> list:
     """Every suspect turned back by its angle and completed with the original where the turn lost pixels (ssw_unrotate_rgb8;
     include/ssw.h states the mask): what tracing a `Rotated(angle)` entry extracts from.  base: the original, 8-bit [H, W, 3];
@@ -2027,7 +2084,9 @@ class ScaleResult:
 class RotateResult:
     """What tracing made of the marked copies after the rotation attack `rotation` (a `Rotate.label`), turned back by the known
     angle; kept: the share of the frame's pixels the undoing took from the rotated copy (the rest is the original's); the other
-    fields as in `JpegResult`."""
+    fields as in `JpegResult`.  For a rotation with a `search` the copies were turned back by the angle FOUND in that range:
+    search = (lo, hi); found_min / found_max: the smallest and the largest angle found over the copies; worst_angle_error: the
+    largest |found - angle|; kept: the smallest share over the copies."""
     rotation: str
     kept: float
     survived: int
@@ -2038,6 +2097,10 @@ class RotateResult:
     psnr_max: float
     ssim_min: float = math.nan
     ssim_max: float = math.nan
+    search: Optional[Tuple[float, float]] = None
+    found_min: float = math.nan
+    found_max: float = math.nan
+    worst_angle_error: float = math.nan
 
 
 @dataclass
@@ -2115,12 +2178,18 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     scale in `StrengthRow.scales` -- whether `trace` still names the recipient of a thumbnail that Pillow made.
     rotations: `Rotate` objects; the same after the scales with one ssw_rotate_attack_rgb8 call, rotation-major: one
     `RotateResult` per rotation in `StrengthRow.rotations` -- what `trace` finds in a copy that Pillow turned when it is told the angle.
+    Rotations with a `search` (`Rotate(1.3, search=True)`) answer the publisher's question instead -- what is left when the
+    tracer is NOT told the angle: after the call above, one ssw_rotate_search_attack_rgb8 call per distinct range turns the
+    copies, searches for every copy's angle and turns it back by the angle found; then the same trace, quality and SSIM calls.
+    Their rows stand in `StrengthRow.rotations` where they were given, with `found_min`, `found_max` and `worst_angle_error`.
     Returns one `StrengthRow` per alpha."""
     jq, fl, sc = _jpeg_qualities(jpeg, "strength_report"), _filters(filters, "strength_report"), _scales(scales, "strength_report")
     ro = _rotations(rotations, "strength_report")
     img = _frames_of_side([image], "strength_report", "a JPEG attack", L.JPEG_MIN_SIDE if jq else 0)[0]
     if ssim:
         _frames_of_side([img], "strength_report", "SSIM", L.SSIM_MIN_SIDE)
+    if any(r.search is not None for r in ro) and (min(img.shape[:2]) < L.ANGLE_MIN_SIDE or img.shape[0] * img.shape[1] > L.ANGLE_MAX_PIXELS):
+        raise ValueError(f"strength_report: a searched rotation needs frames of at least {L.ANGLE_MIN_SIDE} x {L.ANGLE_MIN_SIDE} and at most 2^27 pixels")
     sizes, methods = [int(c) for c in sizes], [str(m).lower() for m in methods]
     if any(c > copies for c in sizes):
         raise ValueError("strength_report: a coalition cannot be larger than the number of copies")
@@ -2152,10 +2221,13 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
             return (name if len(attack) == 3 else (name, True), (struct * n)(*[job(c, p) for p in params for c in range(copies)]), n,
                     [alloc(n * b) for b in (fb, k * 4, copies * 4, 8 * L.QUALITY_STATS)] if n else None)
 
-        def attacked(cfg, made, labels, result):       # attack, trace, quality, the downloads, SSIM: one `result` per label
+        def attacked(cfg, made, labels, result, call=None):       # attack, trace, quality, the downloads, SSIM: one `result` per label
             name, jobs, n, (dev_frames, dev_e, dev_s, dev_st) = made
             name, lead = (name, ()) if isinstance(name, str) else (name[0], (dev_img.ptr,))       # the original in front
-            check(getattr(lib, name)(ctx.handle, *lead, dev_copies.ptr, copies, w, h, jobs, n, dev_frames.ptr), name)
+            if call is None:
+                check(getattr(lib, name)(ctx.handle, *lead, dev_copies.ptr, copies, w, h, jobs, n, dev_frames.ptr), name)
+            else:                                        # (the searched rotations: a call with answers of its own)
+                call(jobs, n, dev_frames)
             trace(cfg, dev_frames, n, dev_e, dev_s)
             measure(dev_frames, n, dev_st)
             sims = dev_s.to_host(np.float32, (len(labels), copies, copies))
@@ -2168,9 +2240,26 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
         dev_copies, dev_stats = alloc(copies * fb), alloc(copies * 8 * L.QUALITY_STATS)
         dev_forged, dev_ext, dev_sims = alloc(max(nf, 1) * fb), alloc(max(nf * k, 1) * 4), alloc(max(nf * copies, 1) * 4)
         jpeg_stage, filter_stage, scale_stage = stage(_JPEG_ATTACK, jq), stage(_FILTER_ATTACK, fl), stage(_scale_attack(w, h), sc)
-        rotate_stage = stage(_rotate_attack(w, h), ro)
-        dev_ssim = alloc(max(copies, jpeg_stage[2], filter_stage[2], scale_stage[2], rotate_stage[2]) * 8 * L.SSIM_STATS) if ssim else None
-        kept = list(zip([r.label for r in ro], _kept_shares(ctx, ro, w, h)))
+        known = [i for i, r in enumerate(ro) if r.search is None]
+        rotate_stage = stage(_rotate_attack(w, h), [ro[i] for i in known])
+        # the searched rotations: per distinct range the positions in `ro`, the stage, the answers of its call
+        search_stages = [(rng, which, stage(_rotate_attack(w, h), [ro[i] for i in which]), (L.AngleFound * (len(which) * copies))(),
+                          np.zeros(len(which) * copies, np.uint64)) for rng, which in _search_ranges(ro)]
+        dev_ssim = alloc(max([copies, jpeg_stage[2], filter_stage[2], scale_stage[2], rotate_stage[2]] + [s[2][2] for s in search_stages])
+                         * 8 * L.SSIM_STATS) if ssim else None
+        kept = list(zip([ro[i].label for i in known], _kept_shares(ctx, [ro[i] for i in known], w, h)))
+
+        def searched(cfg, rng, which, made, found, counts):      # one RotateResult per rotation of the range `rng`
+            def call(jobs, n, dev_frames):
+                check(lib.ssw_rotate_search_attack_rgb8(ctx.handle, dev_img.ptr, dev_copies.ptr, copies, w, h, jobs, n, rng[0], rng[1], dev_frames.ptr,
+                                                        None, found, None, counts.ctypes.data), "ssw_rotate_search_attack_rgb8")
+
+            def result(i, sims, q, threshold, s):
+                angles = [int(f.n) / L.ANGLE_PER_DEGREE for f in found[i * copies:(i + 1) * copies]]
+                return RotateResult(ro[which[i]].label, int(counts[i * copies:(i + 1) * copies].min()) / (w * h),
+                                    *_attack_fold(sims, q, threshold, s), search=rng, found_min=min(angles), found_max=max(angles),
+                                    worst_angle_error=max(abs(a - ro[which[i]].angle) for a in angles))
+            return attacked(cfg, made, list(range(len(which))), result, call)
         for alpha in alphas:
             cfg = L.Config(config.ordering.tag, config.insertion.tag, float(alpha), config.precision)
             check(lib.ssw_fingerprint_embed_rgb8(ctx.handle, C.byref(cfg), dev_img.ptr, w, h, dev_marks.ptr, copies, k, dev_copies.ptr, None),
@@ -2192,7 +2281,10 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
             if sc:
                 rows[-1].scales = attacked(cfg, scale_stage, [(s.label, s.size(w, h)) for s in sc], _scale_result)
             if ro:
-                rows[-1].rotations = attacked(cfg, rotate_stage, kept, _rotate_result)
+                by_place = dict(zip(known, attacked(cfg, rotate_stage, kept, _rotate_result))) if known else {}
+                for rng, which, made, found, counts in search_stages:
+                    by_place.update(zip(which, searched(cfg, rng, which, made, found, counts)))
+                rows[-1].rotations = [by_place[i] for i in range(len(ro))]
     return rows
 
 

@@ -34,7 +34,7 @@
         -> `identify` for every suspect in one call, then the trace above once per original that was named, with the marks
            file the catalogue holds for it; every record gains an "Original:" line
     python -m spread_spectrum_watermarking_amd.cli strength <file> --alpha 0.02 0.05 0.1 [-n 1000] [--copies 8] [--collude 2 4]
-            [--method average median min max minmax mosaic] [--jpeg 90 75 50] [--filter blur:1.5 median unsharp:2,150,3] [--scale 0.5 0.25:lanczos 640x360:bilinear] [--rotate 0.5 2:bilinear -1] [--ssim]
+            [--method average median min max minmax mosaic] [--jpeg 90 75 50] [--filter blur:1.5 median unsharp:2,150,3] [--scale 0.5 0.25:lanczos 640x360:bilinear] [--rotate 0.5 2:bilinear -1 1.3:? 1.3:?-5..5] [--ssim]
             [--similarity-exceed 6.0] [--json]
         -> before a copy ships: per alpha the PSNR range of the marked copies (with --ssim also their mean SSIM and the worst
            8 x 8 window), and per collusion method and coalition size
@@ -44,7 +44,9 @@
            or a 3 x 3 median (median), as Pillow's filters of those names do them; with --scale the same after the copy was
            scaled as Pillow's Image.resize does it (FACTOR[:FILTER] or WIDTHxHEIGHT[:FILTER]) and brought back to size; with --rotate
            the same after the copy was turned as Pillow's Image.rotate does it (DEGREES[:FILTER]) and turned back by the known
-           angle, with the share of the frame that survives the two turns; everything stays on the GPU between the original going up and the numbers coming down
+           angle, with the share of the frame that survives the two turns (DEGREES[:FILTER]:? -- the tracer is NOT told the
+           angle: every copy's angle is searched for in -10 .. 10 degrees, or in LO..HI with :?LO..HI, and the copy turned back by
+           the angle found; the line says which angles were found); everything stays on the GPU between the original going up and the numbers coming down
 
 Host plumbing only (argument parsing, PIL image I/O, JSON); all arithmetic goes through the GPU
 library via the crate-surface mirror in api.py.
@@ -98,14 +100,24 @@ def _scale_arg(text: str) -> Scale:
 
 
 def _rotate_arg(text: str) -> Rotate:
-    """DEGREES[:FILTER]"""
-    what, colon, name = text.partition(":")
+    """DEGREES[:FILTER][:?[LO..HI]] -- a last part that begins with `?`: the tracer is not told the angle and searches for it, in
+    -10 .. 10 degrees or in LO..HI"""
+    what, *rest = text.split(":")
     try:
-        if colon and not name:
+        search = None
+        if rest and rest[-1].startswith("?"):
+            spec = rest.pop()[1:]
+            search = True
+            if spec:
+                lo, dots, hi = spec.partition("..")
+                if not dots:
+                    raise ValueError("?LO..HI names both ends of the range")
+                search = (float(lo), float(hi))
+        if len(rest) > 1 or (rest and not rest[0]):
             raise ValueError("a filter's name after the colon")
-        return Rotate(float(what), name or "bicubic")
+        return Rotate(float(what), rest[0] if rest else "bicubic", search)
     except ValueError as e:
-        raise argparse.ArgumentTypeError(f"{text!r}: DEGREES[:FILTER] ({e})") from e
+        raise argparse.ArgumentTypeError(f"{text!r}: DEGREES[:FILTER][:?[LO..HI]] ({e})") from e
 
 
 def _rust_f32(x: float) -> str:
@@ -337,7 +349,8 @@ def build_parser() -> argparse.ArgumentParser:
                         "FACTOR[:FILTER] (0 < FACTOR <= 4) or WIDTHxHEIGHT[:FILTER]; FILTER box, bilinear, bicubic (default) or lanczos.")
     g.add_argument("--rotate", type=_rotate_arg, nargs="+", default=[], metavar="ROTATION", dest="rotations",
                    help="Also turn every copy as Pillow's Image.rotate does, turn it back by the known angle and trace what is left: "
-                        "DEGREES[:FILTER]; FILTER bilinear or bicubic (default).")
+                        "DEGREES[:FILTER]; FILTER bilinear or bicubic (default).  With :? at the end (1.3:?, 2:bilinear:?, 1.3:?-5..5) the "
+                        "angle is not told: it is searched for in -10 .. 10 degrees (or LO..HI) and the copy turned back by the angle found.")
     g.add_argument("--ssim", action="store_true", help="Also report the structural similarity (SSIM) of every copy and its worst window.")
     g.add_argument("--json", action="store_true", help="Print the report as one JSON document.")
     return p
@@ -507,6 +520,9 @@ def cmd_strength(args, out=None) -> int:
                 d["scales"] = [dict(attack("scale", a), size=list(a.size)) for a in r.scales]
             if rotations:                                    # ... when --rotate was given
                 d["rotations"] = [dict(attack("rotation", a), kept=a.kept) for a in r.rotations]
+                for row, a in zip(d["rotations"], r.rotations):
+                    if a.search is not None:             # the angle was searched for: what was found
+                        row.update(search=list(a.search), found_min=a.found_min, found_max=a.found_max, worst_angle_error=a.worst_angle_error)
         print(json.dumps(doc), file=out)
         return 0
     for r in rows:
@@ -531,7 +547,8 @@ def cmd_strength(args, out=None) -> int:
             accused = f", {a.accused} innocent accused" if a.accused else ""
             ssim = f", ssim {a.ssim_min:.2f} .. {a.ssim_max:.2f}" if r.ssim else ""
             kept = f", {100 * a.kept:.1f} % kept" if hasattr(a, "kept") else ""
-            print(f"  {label}: own mark found {a.survived}/{len(r.quality)}, weakest {a.weakest_own:.1f}, "
+            found = f"found {a.found_min:g} .. {a.found_max:g}, " if getattr(a, "search", None) is not None else ""
+            print(f"  {label}: {found}own mark found {a.survived}/{len(r.quality)}, weakest {a.weakest_own:.1f}, "
                   f"strongest innocent {innocent}{accused}, {a.psnr_min:.1f} .. {a.psnr_max:.1f} dB{ssim}{kept}", file=out)
     return 0
 

@@ -258,6 +258,25 @@ int affine_enqueue(ssw_ctx* ctx, const uint8_t* in, size_t in_fb, const uint32_t
 bool af_job_is_copy(const ssw_rotate_job& j) { return affine_is_identity(j.forward) && affine_is_identity(j.back); }
 
 }  // namespace
+
+// For the rotation search of angle.hip (ssw_rotate_search_attack_rgb8; ssw_host.hpp declares them): the launches of one
+// transform at the frame's own size, and the count of one undoing's mask
+int affine_frames(ssw_ctx* ctx, const uint8_t* in, size_t in_fb, const uint32_t* frames, size_t n, size_t w, size_t h, const double* m,
+                  const double* fwd, int filter, const uint8_t* fill, const uint8_t* base, uint8_t* out) {
+    return affine_enqueue(ctx, in, in_fb, frames, n, w, h, w, h, m, fwd, filter, fill, base, out);
+}
+
+int affine_kept_enqueue(ssw_ctx* ctx, size_t w, size_t h, const double* back, const double* forward, unsigned long long* dev_count) {
+    const dim3 grid((unsigned)((w + AFFINE_TILE_W - 1) / AFFINE_TILE_W), (unsigned)((h + AFFINE_TILE_H - 1) / AFFINE_TILE_H));
+    AffineArgs a{};
+    std::copy(back, back + 6, a.m);
+    std::copy(forward, forward + 6, a.fwd);
+    a.w = a.ow = (uint32_t)w; a.h = a.oh = (uint32_t)h;
+    affine_kept_kernel<<<grid, AFFINE_THREADS, 0, ctx->stream>>>(a, dev_count);
+    SSW_HIP_CHECK(hipGetLastError());
+    return SSW_OK;
+}
+
 }  // namespace host
 }  // namespace ssw
 

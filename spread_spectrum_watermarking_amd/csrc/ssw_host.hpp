@@ -224,6 +224,12 @@ int locate_box_searches(ssw_ctx* ctx, const uint8_t* planes, unsigned qpitch, un
 int locate_luma_planes(ssw_ctx* ctx, const uint8_t* rgb, size_t n, size_t w, size_t h, uint8_t* out, size_t out_stride, unsigned pitch);
 int locate_box4_planes(ssw_ctx* ctx, const uint8_t* luma, size_t luma_stride, unsigned lpitch, size_t n, size_t w, size_t h, uint8_t* out,
                        size_t out_stride, unsigned opitch);
+// affine.hip's launches for the rotation search (angle.hip: ssw_rotate_search_attack_rgb8), enqueued on the context's stream: result i
+// [h][w][3] at out + i * w * h * 3 is frame frames[i] of `in` (in_fb bytes apart) under m; fwd != null: the fused undo over `base`
+// (BICUBIC).  affine_kept_enqueue: the pixels under the mask of the undoing (back, forward), added to *dev_count.
+int affine_frames(ssw_ctx* ctx, const uint8_t* in, size_t in_fb, const uint32_t* frames, size_t n, size_t w, size_t h, const double* m,
+                  const double* fwd, int filter, const uint8_t* fill, const uint8_t* base, uint8_t* out);
+int affine_kept_enqueue(ssw_ctx* ctx, size_t w, size_t h, const double* back, const double* forward, unsigned long long* dev_count);
 // ssw_lib.hip: the cached CatmullRom tap table (in_len -> out_len) of the context
 int get_taps(ssw_ctx* ctx, size_t in_len, size_t out_len, DeviceTaps* out);
 

@@ -400,7 +400,8 @@ SSW_BUF_GROUP(TraceBufs, SSW_TRACE_BUFS);
 // locate.hip: the original's luma plane | its 16 phase planes | one group's workspace (suspects R, luma, S_f, D; the ladder's
 // boxes; the refinement's resized cut-outs) | keys, sums, results | (scale ladder) the original's 8 x 8 box planes | its tap tables
 // angle.hip shares luma, phases (the original's one decimated plane) and group (the suspects' planes) and adds: C, S of every
-// angle of a call's range | answers, rung and refinement sums, the refinement's slot lists
+// angle of a call's range | answers, rung and refinement sums, the refinement's slot lists (ssw_rotate_search_attack_rgb8: behind
+// them the kept counts, the share-groups and their candidates; its turned frames lie in shared.affine)
 // locate_turned.hip shares luma, group (the ladder's boxes and D), keys, box_planes and angle_tab and adds: the suspects' luma
 // planes | the full-resolution template planes of one group of the refinement's searches
 #define SSW_LOCATE_BUFS(X) X(luma) X(phases) X(group) X(keys) X(box_planes) X(taps) X(angle_tab) X(angle_sums) X(turned_luma) X(turned_templates)
