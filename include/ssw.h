@@ -1088,6 +1088,54 @@ typedef struct ssw_turned_job { double angle, cx, cy; } ssw_turned_job;
 int ssw_restore_turned_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
                             const ssw_turned_shape* shapes, const ssw_turned_job* jobs, size_t n, uint8_t* dev_out);
 
+/* ---- the crop attack: a part of the picture, placed or searched, also scaled (csrc/crop.hip) ----------------------------------
+   The reference's second robustness test cuts a rectangle out of the marked copy and lays it over the original again
+   (tests/attack_crop.rs:56-70); the most common leaked copy is such a part that was also scaled for the web.  Both calls make the
+   frames a trace of such a copy sees, and both are defined entirely by calls above.  Job j, with F = frame jobs[j].frame of
+   dev_frames [n_frames][h][w][3]:
+     C_j   = the rectangle (x, y, cw, ch) of F as a dense frame [ch][cw][3].
+     T_j   = C_j when tw = th = 0, else what ssw_resample_rgb8(C_j, cw, ch, tw, th, filter) makes of it: Pillow's
+             crop((x, y, x + cw, y + ch)).resize((tw, th), filter), byte for byte.
+     ssw_crop_attack_rgb8 (placed: the tracer is told the rectangle)
+       dev_out[j] [h][w][3] = what ssw_restore_rgb8(dev_base, T_j, {w, h of T_j, 3, x, y, cw, ch}) makes: T_j brought back to
+             cw x ch by the CatmullRom of csrc/resize_common.hpp when it was scaled, and the original everywhere else.
+     ssw_crop_search_attack_rgb8 (searched: the tracer's own search says where the piece came from)
+       host_found[j], host_sad[j] = for searches[j] = (0, 0) what ssw_locate_rgb8(dev_base, T_j) answers for the piece at its own
+             size (pw, ph are filled in with T_j's w, h); otherwise what ssw_locate_scaled_rgb8(dev_base, T_j, {wmin, wmax})
+             answers.  Definition, tie rules and every constant are those calls'; none differs.
+       dev_out[j] = what ssw_restore_rgb8(dev_base, T_j, host_found[j]) makes.
+     dev_thumbs (may be null) receives the T_j packed one behind the other, in job order, 3 tw th (or 3 cw ch) bytes each.
+   What runs.  The resizes, the searches and the restore of a scaled or searched piece ARE the calls named, made inside the
+   library on the pieces where they lie; consecutive jobs of one (cw, ch, tw, th, filter) are one ssw_resample_rgb8 call, the
+   searches of a group one ssw_locate_rgb8 and one ssw_locate_scaled_rgb8 call.  Two kernels are new.  crop_cut_kernel makes the
+   C_j that a resize or a search reads (and the T_j of an unscaled job when dev_thumbs asks for it).  crop_complement_kernel makes
+   dev_out[j] of a placed, unscaled job in one pass -- every output row is the original's bytes, the copy's, the original's -- so
+   no piece is written and read back: it equals cut + ssw_restore_rgb8 byte for byte.  Neither assumes an alignment of any
+   pointer, of 3 x or of 3 w.
+   Jobs run in groups, in the order of the call, whose pieces and thumbnails in the context's workspace are at most 256 MiB (one
+   job's, if they are more); with dev_thumbs the thumbnails lie there and only the pieces of scaled jobs count.
+   ssw_crop_attack_rgb8 only enqueues on the context's stream, apart from the wait ssw_restore_rgb8 has for a tap table
+   (cw <- tw, ch <- th) the context has not cached; those tables go up before anything is enqueued.
+   ssw_crop_search_attack_rgb8 waits as the locate calls do, PER GROUP: once for the group's (0, 0) searches if it has any
+   (ssw_locate_rgb8), twice for its ranged searches if it has any (ssw_locate_scaled_rgb8: after the ladder and for the answer),
+   and once more per tap table that is new to the context (the refinement's and the restore's).
+   Timed under the stages of the parts: the cuts as SSW_STAGE_CONVERT (6 bytes per pixel of a piece), the resamples as
+   SSW_STAGE_CONVERT, the complement and the restores as SSW_STAGE_RESIZE (the complement: 6 w h bytes per job), the searches as
+   SSW_STAGE_LOCATE / SSW_STAGE_LOCATE_COARSE.  A call of placed, unscaled jobs without dev_thumbs bills SSW_STAGE_RESIZE alone.
+   n_jobs == 0 is checked first: SSW_OK.  SSW_ERR_BAD_ARG: a null pointer (dev_thumbs excepted), frame >= n_frames, cw or ch of 0,
+   a rectangle that leaves the frame, one of tw, th zero and the other not, an unknown filter of a scaled job, an output that
+   overlaps an input or the other output; SSW_ERR_BAD_DIMS: w or h of 0, a side above 65535.  Nothing is enqueued then.  The
+   status codes of the parts come through as they are (ssw_locate_scaled_rgb8: SSW_ERR_BAD_ARG for a range that leaves no rung
+   or has min(wmin, ph(wmin)) < 32; SSW_ERR_UNSUPPORTED for a resize that has no LDS tile); the groups before the failing one
+   have run. */
+typedef struct ssw_crop_job { uint32_t frame, x, y, cw, ch, tw, th, filter; } ssw_crop_job;      /* tw = th = 0: not scaled */
+int ssw_crop_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h,
+                         const ssw_crop_job* jobs, size_t n_jobs, uint8_t* dev_out, uint8_t* dev_thumbs);
+typedef struct ssw_crop_search { uint32_t wmin, wmax; } ssw_crop_search;                         /* 0, 0: the piece's own size */
+int ssw_crop_search_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h,
+                                const ssw_crop_job* jobs, const ssw_crop_search* searches, size_t n_jobs, uint8_t* dev_out,
+                                uint8_t* dev_thumbs, ssw_placement* host_found, uint64_t* host_sad);
+
 /* ---- 16-bit frames (device-resident, batched) ----------------------------------- */
 /* `DynamicImage::into_rgb32f()` for 16-bit input (ImageRgb16; call sites src/algorithm.rs:308, :476): v / 65535,
    and `into_rgb16()` from Rgb32F: round(clamp(v,0,1) * 65535) (`image 0.24.3`, like the 8-bit forms). */

@@ -107,6 +107,18 @@ class RotateJob(C.Structure):
     _fields_ = [("frame", C.c_uint32), ("filter", C.c_uint32), ("fill", C.c_uint8 * 4), ("forward", C.c_double * 6), ("back", C.c_double * 6)]
 
 
+class CropJob(C.Structure):
+    """ssw_crop_job (include/ssw.h): one result of ssw_crop_attack_rgb8 / ssw_crop_search_attack_rgb8 -- a frame of the call, the
+    rectangle cut out of it, and the thumbnail's size and ssw_resample_filter (tw = th = 0: the piece is not scaled)."""
+    _fields_ = [("frame", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("cw", C.c_uint32), ("ch", C.c_uint32),
+                ("tw", C.c_uint32), ("th", C.c_uint32), ("filter", C.c_uint32)]
+
+
+class CropSearch(C.Structure):
+    """ssw_crop_search (include/ssw.h): the widths the piece may have had in the original; 0, 0: its own size."""
+    _fields_ = [("wmin", C.c_uint32), ("wmax", C.c_uint32)]
+
+
 class AngleFound(C.Structure):
     """ssw_angle_found (include/ssw.h): one answer of ssw_find_angle_rgb8 -- the angle is n / 32 degrees, sad and count its D and c."""
     _fields_ = [("n", C.c_int32), ("n_rungs", C.c_uint32), ("sad", C.c_uint64), ("count", C.c_uint64)]
@@ -132,6 +144,7 @@ class TurnedJob(C.Structure):
 
 ANGLE_PER_DEGREE = 32        # ssw_find_angle_rgb8: the answer's resolution
 ANGLE_MIN_SIDE = 32          # ... refuses smaller frames
+LOCATE_SCALED_MIN_SIDE = 32  # ssw_locate_scaled_rgb8 refuses a range whose smallest rung has a side below this
 ANGLE_MAX_PIXELS = 1 << 27   # ... and larger ones
 
 # ssw_affine_filter, by the names the Python surface and the CLI accept (Pillow's)
@@ -251,6 +264,9 @@ SIGNATURES = {
     "ssw_find_angle_rgb8": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, C.c_double, C.c_double, C.POINTER(AngleFound), _u64p]),
     "ssw_rotate_search_attack_rgb8": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, C.POINTER(RotateJob), _sz, C.c_double, C.c_double, _vp, _vp,
                                                 C.POINTER(AngleFound), _u64p, _u64p]),
+    "ssw_crop_attack_rgb8": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, C.POINTER(CropJob), _sz, _vp, _vp]),
+    "ssw_crop_search_attack_rgb8": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, C.POINTER(CropJob), C.POINTER(CropSearch), _sz, _vp, _vp, _plp,
+                                              _u64p]),
     "ssw_locate_turned_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(C.c_void_p), C.POINTER(TurnedShape), _sz, C.c_double, C.c_double,
                                          C.POINTER(TurnedFound), _u64p]),
     "ssw_restore_turned_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(C.c_void_p), C.POINTER(TurnedShape), C.POINTER(TurnedJob), _sz, _vp]),

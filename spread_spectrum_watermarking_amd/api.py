@@ -18,6 +18,7 @@ GPU through libssw_hip.so; there is no CPU path in this package.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 from contextlib import contextmanager
 from dataclasses import dataclass, field
@@ -1965,6 +1966,216 @@ def rotate_search_attack(base, images, rotations, ctx: Optional[Context] = None)
     return out, found
 
 
+# ---- the crop attack, placed or searched, also scaled (include/ssw.h: ssw_crop_attack_rgb8, ssw_crop_search_attack_rgb8) ------
+def _ladder_height(pw: int, sw: int, sh: int) -> int:
+    """ph(pw) of ssw_locate_scaled_rgb8: the height the ladder gives a piece of sw x sh at width pw"""
+    return max(1, (2 * sh * pw + sw) // (2 * sw))
+
+
+@dataclass(frozen=True)
+class Crop:
+    """One attack of ssw_crop_attack_rgb8 / ssw_crop_search_attack_rgb8: a rectangle cut out of the copy -- perhaps made a
+    thumbnail as PIL.Image.resize makes it -- and laid over the original again, as the reference's crop test does it.
+    `Crop(0.5)`: that fraction of both sides, cw = max(1, floor(W f + 0.5)) and ch likewise, centred: x = (W - cw) // 2,
+    y = (H - ch) // 2; `anchor=(ax, ay)` in 0 .. 1 puts it elsewhere, x = floor((W - cw) ax): (0, 0) the top left corner, (0, 1)
+    the bottom left.  `Crop.rect(x, y, cw, ch)`: that rectangle whatever the frame's size.  `scale=0.5` (a factor of the piece's
+    sides, rounded as `Scale` rounds) or `to=(tw, th)` makes the piece a thumbnail with `filter` ("box", "bilinear", "bicubic",
+    "lanczos").  search: None -- the tracer is told the rectangle; True -- it searches for it: the position of an unscaled piece
+    (ssw_locate_rgb8), position and size of a thumbnail over the widths from its own up to the frame's
+    (ssw_locate_scaled_rgb8); (wmin, wmax) -- over those widths.  `label` names it in reports: "crop 0.5", "crop 340,160,225x225",
+    "crop 0.75 @ 0.5 lanczos"."""
+    fraction: float = 0.0
+    anchor: Tuple[float, float] = (0.5, 0.5)
+    scale: float = 0.0
+    to: Optional[Tuple[int, int]] = None
+    filter: str = "bicubic"
+    search: Any = None
+    rectangle: Optional[Tuple[int, int, int, int]] = None
+
+    def __post_init__(self):
+        number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(v)
+        whole = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        _resample_filter(self.filter)
+        object.__setattr__(self, "filter", self.filter.lower())
+        if self.rectangle is not None:
+            r = tuple(self.rectangle)
+            if self.fraction or len(r) != 4 or not all(whole(v) for v in r) or min(r[:2]) < 0 or min(r[2:]) < 1:
+                raise ValueError("Crop.rect: x, y >= 0 and cw, ch >= 1, integers (and no fraction beside them)")
+            object.__setattr__(self, "rectangle", tuple(int(v) for v in r))
+        else:
+            if not number(self.fraction) or not 0.0 < self.fraction <= 1.0:
+                raise ValueError("Crop: a fraction above 0 and at most 1")
+            object.__setattr__(self, "fraction", float(self.fraction))
+        a = tuple(self.anchor) if isinstance(self.anchor, (tuple, list)) else ()
+        if len(a) != 2 or not all(number(v) and 0.0 <= v <= 1.0 for v in a):
+            raise ValueError("Crop: anchor=(ax, ay), both 0 .. 1")
+        object.__setattr__(self, "anchor", (float(a[0]), float(a[1])))
+        if self.to is not None:
+            if self.scale:
+                raise ValueError("Crop: scale= or to=, not both")
+            if not isinstance(self.to, (tuple, list)) or len(self.to) != 2:
+                raise ValueError("Crop: to=(tw, th)")
+            object.__setattr__(self, "to", (_side(self.to[0], "Crop"), _side(self.to[1], "Crop")))
+        elif self.scale:
+            if not number(self.scale) or not 0.0 < self.scale <= L.SCALE_FACTOR_MAX:
+                raise ValueError(f"Crop: scale= above 0 and at most {L.SCALE_FACTOR_MAX:g}")
+            object.__setattr__(self, "scale", float(self.scale))
+        s = self.search
+        if s is False:
+            object.__setattr__(self, "search", None)
+        elif s is not None and s is not True:
+            if not isinstance(s, (tuple, list)) or len(s) != 2 or not all(whole(v) for v in s) or not 0 < s[0] <= s[1]:
+                raise ValueError("Crop: search=True or search=(wmin, wmax), integers with 0 < wmin <= wmax")
+            object.__setattr__(self, "search", (int(s[0]), int(s[1])))
+
+    @classmethod
+    def rect(cls, x, y, cw, ch, **kwargs) -> "Crop":
+        return cls(rectangle=(x, y, cw, ch), **kwargs)
+
+    @property
+    def scaled(self) -> bool:
+        return bool(self.scale) or self.to is not None
+
+    def rect_in(self, w: int, h: int) -> Tuple[int, int, int, int]:
+        """(x, y, cw, ch) in a w x h frame; ValueError when an explicit rectangle leaves it"""
+        if self.rectangle is not None:
+            x, y, cw, ch = self.rectangle
+            if x + cw > w or y + ch > h:
+                raise ValueError(f"Crop: the rectangle {x},{y},{cw}x{ch} leaves the {w}x{h} frame")
+            return self.rectangle
+        cw, ch = max(1, int(w * self.fraction + 0.5)), max(1, int(h * self.fraction + 0.5))
+        return int((w - cw) * self.anchor[0]), int((h - ch) * self.anchor[1]), cw, ch
+
+    def thumb(self, w: int, h: int) -> Optional[Tuple[int, int]]:
+        """(tw, th) of the thumbnail made of the piece in a w x h frame; None when it is not scaled"""
+        if self.to is not None:
+            return self.to
+        if not self.scale:
+            return None
+        _, _, cw, ch = self.rect_in(w, h)
+        return max(1, int(cw * self.scale + 0.5)), max(1, int(ch * self.scale + 0.5))
+
+    def search_range(self, w: int, h: int) -> Optional[Tuple[int, int]]:
+        """None: placed; (0, 0): the position of the piece at its own size is searched; (wmin, wmax): the scale ladder's widths.
+        ValueError for a range the ladder refuses (a side below 32 at wmin, nothing that fits the frame)."""
+        if self.search is None:
+            return None
+        t = self.thumb(w, h)
+        if self.search is True and t is None:
+            return 0, 0
+        sw, sh = t or self.rect_in(w, h)[2:]
+        lo, hi = (sw, w) if self.search is True else self.search
+        if lo > hi or min(lo, _ladder_height(lo, sw, sh)) < L.LOCATE_SCALED_MIN_SIDE or lo > w or _ladder_height(lo, sw, sh) > h:
+            raise ValueError(f"Crop: the widths {lo}..{hi} searched for a {sw}x{sh} piece need both sides at least "
+                             f"{L.LOCATE_SCALED_MIN_SIDE} at the smallest and a smallest that fits the frame")
+        return lo, hi
+
+    @property
+    def label(self) -> str:
+        what = "{},{},{}x{}".format(*self.rectangle) if self.rectangle is not None else f"{self.fraction:g}"
+        if self.anchor != (0.5, 0.5) and self.rectangle is None:
+            what += f" anchor {self.anchor[0]:g},{self.anchor[1]:g}"
+        if self.to is not None:
+            what += f" @ {self.to[0]}x{self.to[1]} {self.filter}"
+        elif self.scale:
+            what += f" @ {self.scale:g} {self.filter}"
+        return "crop " + what
+
+    def job(self, frame: int, w: int, h: int) -> L.CropJob:
+        tw, th = self.thumb(w, h) or (0, 0)
+        return L.CropJob(frame, *self.rect_in(w, h), tw, th, L.RESAMPLE_FILTERS[self.filter] if tw else 0)
+
+
+def _crops(crops, what: str, w: Optional[int] = None, h: Optional[int] = None) -> list:
+    """The `Crop` objects of a call, each checked against the w x h frame when that is given: every ValueError comes from here"""
+    cr = list(crops)
+    if any(not isinstance(c, Crop) for c in cr):
+        raise ValueError(f"{what}: crops are made with Crop(fraction) or Crop.rect(x, y, cw, ch)")
+    if w is not None:
+        for c in cr:
+            c.rect_in(w, h)
+            if max(c.thumb(w, h) or (0, 0)) > L.RESAMPLE_SIDE_MAX:
+                raise ValueError(f"{what}: a thumbnail's side is at most {L.RESAMPLE_SIDE_MAX}")
+            c.search_range(w, h)
+    return cr
+
+
+def _crop_attack(w: int, h: int) -> tuple:
+    """The attack of the report's stage for frames of w x h: a crop's rectangle needs the frame's size; the original goes in front"""
+    return ("ssw_crop_attack_rgb8", L.CropJob, lambda frame, c: c.job(frame, w, h), True)
+
+
+def _crop_sizes(jobs) -> list:
+    """(tw, th) of the T of every job: the thumbnail's size, or the piece's"""
+    return [(int(j.tw), int(j.th)) if j.tw else (int(j.cw), int(j.ch)) for j in jobs]
+
+
+def _crop_run(ctx: Optional[Context], what: str, base, images, crops, search: bool, thumbs: bool) -> tuple:
+    """The runner of `crop_attack` and `crop_search_attack`: jobs in frame order over the groups of `_job_groups`.  Returns
+    (frames, thumbs or None, found or None), each [len(images)][len(crops)]."""
+    frames = _frames_u8(images, what)
+    b = _frames_u8([base], what)[0] if frames else None
+    if frames and b.shape != frames[0].shape:
+        raise ValueError(f"{what}: the original has the images' size")
+    cr = _crops(crops, what, *((b.shape[1], b.shape[0]) if frames else ()))
+    out = [[None] * len(cr) for _ in frames]
+    th, found = ([[None] * len(cr) for _ in frames] if thumbs else None), ([[None] * len(cr) for _ in frames] if search else None)
+    if not frames or not cr:
+        return [[] for _ in frames] if not cr else out, th, found
+    ctx = ctx or default_context()
+    h, w = b.shape[:2]
+    fb = w * h * 3
+    jobs = [(i, p) for i in range(len(frames)) for p in range(len(cr))]
+    for used, g0, g1 in _job_groups([(i,) for i, _ in jobs], fb):
+        where, n = {i: j for j, i in enumerate(used)}, g1 - g0
+        arr = (L.CropJob * n)(*[cr[p].job(where[i], w, h) for i, p in jobs[g0:g1]])
+        sizes = _crop_sizes(arr)
+        with _owned(ctx) as alloc:
+            dev_f, dev_o = alloc(len(used) * fb), alloc(n * fb)
+            dev_t = alloc(sum(3 * a * c for a, c in sizes)) if thumbs else None
+            _upload_frames(ctx, dev_f, [frames[i] for i in used])
+            dev_b = _upload_frames(ctx, alloc(fb), [b])
+            if search:
+                rng = (L.CropSearch * n)(*[L.CropSearch(*cr[p].search_range(w, h)) for _, p in jobs[g0:g1]])
+                got, sad = (L.Placement * n)(), np.zeros(n, np.uint64)
+                check(ctx._lib.ssw_crop_search_attack_rgb8(ctx.handle, dev_b.ptr, dev_f.ptr, len(used), w, h, arr, rng, n, dev_o.ptr,
+                                                           dev_t.ptr if thumbs else None, got, sad.ctypes.data),
+                      "ssw_crop_search_attack_rgb8")
+                for (i, p), f, s in zip(jobs[g0:g1], got, sad):
+                    found[i][p] = Located(Placement(int(f.x), int(f.y), int(f.pw), int(f.ph)), int(s), int(s) / max(1, int(f.pw) * int(f.ph)))
+            else:
+                check(ctx._lib.ssw_crop_attack_rgb8(ctx.handle, dev_b.ptr, dev_f.ptr, len(used), w, h, arr, n, dev_o.ptr,
+                                                    dev_t.ptr if thumbs else None), "ssw_crop_attack_rgb8")
+            for (i, p), frame in zip(jobs[g0:g1], dev_o.to_host(np.uint8, (n, h, w, 3))):
+                out[i][p] = frame
+            if thumbs:
+                flat, at = dev_t.to_host(np.uint8, (sum(3 * a * c for a, c in sizes),)), 0
+                for (i, p), (a, c) in zip(jobs[g0:g1], sizes):
+                    th[i][p], at = flat[at:at + 3 * a * c].reshape(c, a, 3), at + 3 * a * c
+    return out, th, found
+
+
+def crop_attack(base, images, crops, thumbs: bool = False, ctx: Optional[Context] = None):
+    """Every image after every crop attack when the tracer is told the rectangle (ssw_crop_attack_rgb8): the rectangle cut out,
+    made a thumbnail as Pillow does it when the `Crop` says so, brought back to its size and laid over `base`, the original, as
+    `trace` with a `Placement` would.  base: 8-bit [H, W, 3]; images: 8-bit [H, W, 3] of that size; crops: `Crop` objects (a
+    `search` of theirs is not read).  Returns [len(images)][len(crops)] u8 [H, W, 3] frames; with thumbs=True (frames, thumbs),
+    thumbs the pieces as they would leak, u8 [th, tw, 3]: PIL's crop((x, y, x + cw, y + ch)).resize((tw, th), filter), byte for byte."""
+    cr = [dataclasses.replace(c, search=None) if isinstance(c, Crop) else c for c in crops]
+    out, th, _ = _crop_run(ctx, "crop_attack", base, images, cr, False, thumbs)
+    return (out, th) if thumbs else out
+
+
+def crop_search_attack(base, images, crops, ctx: Optional[Context] = None) -> tuple:
+    """Every image after every crop attack when the tracer is NOT told where the piece came from (ssw_crop_search_attack_rgb8):
+    cut, perhaps scaled, then placed where `locate` finds it -- the position of an unscaled piece, position and size of a
+    thumbnail over each `Crop`'s widths (search=None is taken as True).  Returns (frames [len(images)][len(crops)] u8 [H, W, 3],
+    found [len(images)][len(crops)] of `Located`)."""
+    cr = [dataclasses.replace(c, search=True) if isinstance(c, Crop) and c.search is None else c for c in crops]
+    out, _, found = _crop_run(ctx, "crop_search_attack", base, images, cr, True, False)
+    return out, found
+
+
 def unrotate(base, suspects, angles, ctx: Optional[Context] = None) -> list:
     """Every suspect turned back by its angle and completed with the original where the turn lost pixels (ssw_unrotate_rgb8;
     include/ssw.h states the mask): what tracing a `Rotated(angle)` entry extracts from.  base: the original, 8-bit [H, W, 3];
@@ -2104,11 +2315,38 @@ class RotateResult:
 
 
 @dataclass
+class CropResult:
+    """What tracing made of the marked copies after the crop attack `crop` (a `Crop.label`): size (cw, ch), rect (x, y, cw, ch),
+    thumb (tw, th) when the piece was made a thumbnail, kept = cw ch / (W H); the other fields as in `JpegResult`.  For a crop
+    with a `search` the piece was laid where the tracer's own search found it: search = (wmin, wmax) as the call got it, (0, 0)
+    for the piece's own size; found: per copy (x, y, pw, ph); found_exact: how many copies got the true rectangle;
+    worst_offset: the largest |x - true x|, |y - true y| over the copies; worst_size_error: the largest |pw - cw|, |ph - ch|."""
+    crop: str
+    size: Tuple[int, int]
+    survived: int
+    weakest_own: float
+    strongest_innocent: float
+    accused: int
+    psnr_min: float
+    psnr_max: float
+    ssim_min: float = math.nan
+    ssim_max: float = math.nan
+    rect: Tuple[int, int, int, int] = (0, 0, 0, 0)
+    thumb: Optional[Tuple[int, int]] = None
+    kept: float = math.nan
+    search: Optional[Tuple[int, int]] = None
+    found: list = field(default_factory=list)
+    found_exact: int = 0
+    worst_offset: Tuple[int, int] = (0, 0)
+    worst_size_error: Tuple[int, int] = (0, 0)
+
+
+@dataclass
 class StrengthRow:
     """`strength_report` for one alpha: the `Quality` of every copy, one `Collusion` per (method, size), methods outermost, and
     one `JpegResult` per JPEG quality asked for; ssim: the `Ssim` of every copy when the report was asked for it; filters: one
     `FilterResult` per filter asked for; scales: one `ScaleResult` per scale asked for; rotations: one `RotateResult` per rotation
-    asked for."""
+    asked for; crops: one `CropResult` per crop asked for."""
     alpha: float
     quality: list
     collusions: list
@@ -2117,6 +2355,7 @@ class StrengthRow:
     filters: list = field(default_factory=list)
     scales: list = field(default_factory=list)
     rotations: list = field(default_factory=list)
+    crops: list = field(default_factory=list)
 
     def collusion(self, method: str, size: int) -> Collusion:
         return next(c for c in self.collusions if (c.method, c.size) == (method, size))
@@ -2159,7 +2398,7 @@ def _rotate_result(label_kept: tuple, sims: np.ndarray, qualities: list, thresho
 def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                     methods=("average", "median", "min", "max", "minmax", "mosaic"), threshold: float = 6.0,
                     config: Optional[WriteConfig] = None, seed=None, ctx: Optional[Context] = None, jpeg=(), ssim: bool = False,
-                    filters=(), scales=(), rotations=()) -> list:
+                    filters=(), scales=(), rotations=(), crops=()) -> list:
     """The two questions to answer before a copy ships, per insertion strength: how visible is the mark, and how many
     recipients must pool their copies before tracing fails?  For each alpha (`config` with its alpha replaced; the default
     Option2 + Energy): `copies` marked copies of the 8-bit `image` (ssw_fingerprint_embed_rgb8), their distance from it
@@ -2182,10 +2421,15 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
     tracer is NOT told the angle: after the call above, one ssw_rotate_search_attack_rgb8 call per distinct range turns the
     copies, searches for every copy's angle and turns it back by the angle found; then the same trace, quality and SSIM calls.
     Their rows stand in `StrengthRow.rotations` where they were given, with `found_min`, `found_max` and `worst_angle_error`.
+    crops: `Crop` objects; the same after the rotations -- how much of the picture must a leak keep?  The crops without a
+    `search` go in one ssw_crop_attack_rgb8 call, crop-major; those with one -- what is left when nobody tells the tracer where
+    the piece came from -- in one ssw_crop_search_attack_rgb8 call; each followed by the same trace, quality and SSIM calls: one
+    `CropResult` per crop in `StrengthRow.crops`, in the order given.
     Returns one `StrengthRow` per alpha."""
     jq, fl, sc = _jpeg_qualities(jpeg, "strength_report"), _filters(filters, "strength_report"), _scales(scales, "strength_report")
     ro = _rotations(rotations, "strength_report")
     img = _frames_of_side([image], "strength_report", "a JPEG attack", L.JPEG_MIN_SIDE if jq else 0)[0]
+    cr = _crops(crops, "strength_report", img.shape[1], img.shape[0])
     if ssim:
         _frames_of_side([img], "strength_report", "SSIM", L.SSIM_MIN_SIDE)
     if any(r.search is not None for r in ro) and (min(img.shape[:2]) < L.ANGLE_MIN_SIDE or img.shape[0] * img.shape[1] > L.ANGLE_MAX_PIXELS):
@@ -2245,8 +2489,13 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
         # the searched rotations: per distinct range the positions in `ro`, the stage, the answers of its call
         search_stages = [(rng, which, stage(_rotate_attack(w, h), [ro[i] for i in which]), (L.AngleFound * (len(which) * copies))(),
                           np.zeros(len(which) * copies, np.uint64)) for rng, which in _search_ranges(ro)]
-        dev_ssim = alloc(max([copies, jpeg_stage[2], filter_stage[2], scale_stage[2], rotate_stage[2]] + [s[2][2] for s in search_stages])
-                         * 8 * L.SSIM_STATS) if ssim else None
+        # the crops: the placed ones and the searched ones, each kind one stage and one call; positions in `cr`
+        placed, sought = [i for i, c in enumerate(cr) if c.search is None], [i for i, c in enumerate(cr) if c.search is not None]
+        crop_stage, crop_search_stage = stage(_crop_attack(w, h), [cr[i] for i in placed]), stage(_crop_attack(w, h), [cr[i] for i in sought])
+        crop_ranges = (L.CropSearch * max(1, len(sought) * copies))(*[L.CropSearch(*cr[i].search_range(w, h)) for i in sought for _ in range(copies)])
+        crop_found, crop_sad = (L.Placement * max(1, len(sought) * copies))(), np.zeros(max(1, len(sought) * copies), np.uint64)
+        dev_ssim = alloc(max([copies, jpeg_stage[2], filter_stage[2], scale_stage[2], rotate_stage[2], crop_stage[2], crop_search_stage[2]]
+                             + [s[2][2] for s in search_stages]) * 8 * L.SSIM_STATS) if ssim else None
         kept = list(zip([ro[i].label for i in known], _kept_shares(ctx, [ro[i] for i in known], w, h)))
 
         def searched(cfg, rng, which, made, found, counts):      # one RotateResult per rotation of the range `rng`
@@ -2259,6 +2508,28 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                 return RotateResult(ro[which[i]].label, int(counts[i * copies:(i + 1) * copies].min()) / (w * h),
                                     *_attack_fold(sims, q, threshold, s), search=rng, found_min=min(angles), found_max=max(angles),
                                     worst_angle_error=max(abs(a - ro[which[i]].angle) for a in angles))
+            return attacked(cfg, made, list(range(len(which))), result, call)
+
+        def cropped(cfg, which, made, search):                   # one CropResult per crop of `which`, placed or searched
+            def call(jobs, n, dev_frames):
+                if search:
+                    check(lib.ssw_crop_search_attack_rgb8(ctx.handle, dev_img.ptr, dev_copies.ptr, copies, w, h, jobs, crop_ranges, n, dev_frames.ptr,
+                                                          None, crop_found, crop_sad.ctypes.data), "ssw_crop_search_attack_rgb8")
+                else:
+                    check(lib.ssw_crop_attack_rgb8(ctx.handle, dev_img.ptr, dev_copies.ptr, copies, w, h, jobs, n, dev_frames.ptr, None),
+                          "ssw_crop_attack_rgb8")
+
+            def result(i, sims, q, threshold, s):
+                c = cr[which[i]]
+                x, y, cw, ch = rect = c.rect_in(w, h)
+                more = {}
+                if search:
+                    got = [(int(f.x), int(f.y), int(f.pw), int(f.ph)) for f in crop_found[i * copies:(i + 1) * copies]]
+                    more = dict(search=c.search_range(w, h), found=got, found_exact=sum(g == rect for g in got),
+                                worst_offset=(max(abs(g[0] - x) for g in got), max(abs(g[1] - y) for g in got)),
+                                worst_size_error=(max(abs(g[2] - cw) for g in got), max(abs(g[3] - ch) for g in got)))
+                return CropResult(c.label, (cw, ch), *_attack_fold(sims, q, threshold, s), rect=rect, thumb=c.thumb(w, h),
+                                  kept=cw * ch / (w * h), **more)
             return attacked(cfg, made, list(range(len(which))), result, call)
         for alpha in alphas:
             cfg = L.Config(config.ordering.tag, config.insertion.tag, float(alpha), config.precision)
@@ -2285,6 +2556,11 @@ def strength_report(image, alphas, k: int = 1000, copies: int = 8, sizes=(2, 4),
                 for rng, which, made, found, counts in search_stages:
                     by_place.update(zip(which, searched(cfg, rng, which, made, found, counts)))
                 rows[-1].rotations = [by_place[i] for i in range(len(ro))]
+            if cr:
+                by_place = dict(zip(placed, cropped(cfg, placed, crop_stage, False))) if placed else {}
+                if sought:
+                    by_place.update(zip(sought, cropped(cfg, sought, crop_search_stage, True)))
+                rows[-1].crops = [by_place[i] for i in range(len(cr))]
     return rows
 
 

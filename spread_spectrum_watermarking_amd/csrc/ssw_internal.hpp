@@ -417,8 +417,8 @@ SSW_BUF_GROUP(FingerprintBufs, SSW_FINGERPRINT_BUFS);
 // intermediate of the resize's vertical pass | the original's pixels while a restoring trace runs | jpeg.hip: the decoded Y,
 // Cb and Cr planes of one group of jobs | filter.hip: the row-blurred planes of one group of jobs | resample.hip: a call's tap
 // tables, the row-resampled planes of one group of frames and (scale attack) the thumbnails of one group of jobs | affine.hip:
-// the rotated frames of one group of jobs of a rotation attack
-#define SSW_SHARED_BUFS(X) X(overflow) X(base_prune_stats) X(small) X(sort_scratch) X(resize_tmp) X(restore_base) X(jpeg) X(filter) X(resample) X(affine)
+// the rotated frames of one group of jobs of a rotation attack | crop.hip: the pieces and thumbnails of one group of jobs
+#define SSW_SHARED_BUFS(X) X(overflow) X(base_prune_stats) X(small) X(sort_scratch) X(resize_tmp) X(restore_base) X(jpeg) X(filter) X(resample) X(affine) X(crop)
 SSW_BUF_GROUP(SharedBufs, SSW_SHARED_BUFS);
 }  // namespace ssw
 
