@@ -6,12 +6,10 @@
 // counterpart.
 //
 // Kernels (the planes come from locate.hip's locate_luma_kernel and locate_box_kernel):
-//   angle_cost_kernel    THE HOT PATH, both factors: a block takes a tile of 32 x 32 pixels of a suspect's plane for one candidate
-//                        angle (grid y: the candidate slot, grid z: the suspect).  The map is monotone in X and in Y, so the
-//                        sample points of the tile's four corners bound the box of the original's plane it can touch: the box
-//                        is staged in LDS and all four taps come from there.  The tile's origin is formed in 64 bits, the box's
-//                        origin subtracted, and a lane adds its own offset in 32 bits -- integer adds, exact.  A lane sums
-//                        |Ps - v| and its valid bit; wave, then block reduction; one 64-bit atomic add of D and one of c per block.
+//   angle_cost_kernel    THE HOT PATH, both factors: a block takes a tile of a suspect's plane for one candidate angle (grid y:
+//                        the candidate slot, grid z: the suspect) and the staged box of the original's plane: turned_tile.hpp.
+//                        A lane sums |Ps - v| and its valid bit, a pixel per row step; wave, then block reduction; one 64-bit
+//                        atomic add of D and one of c per block.
 //   angle_keep_kernel    one block per suspect: the 4 rungs of smallest mean cost (cross-multiplied in 64 bits, ties to the
 //                        smaller j) and the refinement's slot list of 60 angles, duplicates and angles outside the range marked
 //                        as skipped -- on the device, so the call waits for the stream once
@@ -31,80 +29,91 @@
 #include "angle_share.hpp"
 #include "angle_tables.hpp"
 #include "ssw_host.hpp"
+#include "turned_tile.hpp"
 
 namespace ssw {
 
-constexpr unsigned ANG_TW = 32, ANG_TH = 32, ANG_THREADS = 256, ANG_ROWS = ANG_THREADS / ANG_TW;      // a lane: ANG_TH / ANG_ROWS pixels of a column
-// The staged box.  The sample points of a tile spread over (C 31 + |S| 31) / 65536 <= 31 sqrt(2) = 43.9 plane pixels across and
-// down (at 45 degrees): their floors take at most 45 values, the second tap adds one.
-constexpr unsigned ANG_BOX_W = 48, ANG_BOX_H = 46;
+constexpr unsigned ANG_ROWS = TURN_THREADS / TURN_TILE_W;         // angle_cost_kernel's lane: TURN_TILE_H / ANG_ROWS pixels of a column
 constexpr unsigned ANG_RUNGS_MAX = 2 * ANGLE_RUNG_MAX + 1;
 constexpr int32_t ANG_SKIP = INT32_MIN;
 static_assert(ANG_SKIP == ANGLE_SLOT_SKIP, "angle_share.hpp reads the slot lists angle_keep_kernel writes");
 
-struct AngleCost {
+// A level of the search, the part of a descriptor both cost kernels read: the ladder's (f = 4, sh = 19, the 4 x 4 box planes) or
+// the refinement's (f = 1, sh = 17, the luma planes)
+struct AngleLevel {
     const uint8_t* po;              // the original's plane [hr][po_pitch]
     const uint8_t* ps;              // the suspects' planes [hr][ps_pitch], ps_stride bytes apart
     size_t ps_stride;
     const int32_t* tab;             // C, S of angle a at tab[2 (a - a_lo)]
-    const int32_t* slots;           // the refinement: the angle of slot y of suspect z at [z][ANGLE_SLOTS], or ANG_SKIP; null: the ladder
-    unsigned long long* sums;       // [suspect][slot][2]: D, c
+    unsigned long long* sums;       // [suspect][n_slots][2]: D, c
     uint32_t po_pitch, ps_pitch, wr, hr, w, h, f, sh, tiles_x, n_slots;
     int32_t a_lo, a_first;          // the ladder: slot y is the angle a_first + 8 y
 };
+struct AngleCost {
+    AngleLevel lv;
+    const int32_t* slots;           // the refinement: the angle of slot y of suspect z at [z][ANGLE_SLOTS], or ANG_SKIP; null: the ladder
+};
+struct AngleShared {                // ps_pitch % 4 == 0, ps_stride % 256 == 0
+    AngleLevel lv;                  // sums: at the rung (ladder), at the member's own slot (refinement)
+    const ShareGroup* groups;       // grid z: the share-group sg0 + z
+    const ShareCand* cands;         // the refinement: candidate y of the group at [first_cand + y]; null: the ladder, every member wants rung y
+    uint32_t sg0;
+};
 
-__device__ inline int64_t ang_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
+// A block of either cost kernel: the tile blockIdx.x of the candidate angle, and the valid window 1 <= X0 <= wr - 3 as the box
+// sees it -- X0 = bx0 + (local X0), the local one 0 .. bw - 2
+struct AngleBlock {
+    Turn m;
+    TurnedTile tl;
+    uint32_t Xt, Yt;
+    int nx, ny;
+    int32_t lox, hix, loy, hiy;
+};
 
-// grid: (tiles of the plane, slots, suspects); block: ANG_THREADS
-__global__ __launch_bounds__(ANG_THREADS) void angle_cost_kernel(AngleCost d) {
-    __shared__ uint8_t s_box[ANG_BOX_H][ANG_BOX_W];
-    __shared__ uint32_t s_red[2][ANG_THREADS / 64];
+// stages the box; false, and nothing staged: no pixel of the tile is valid (uniform)
+__device__ __forceinline__ bool angle_block(const AngleLevel& d, int32_t a, TurnedBox& s_box, AngleBlock& b) {
+    b.m = Turn{d.tab[2 * (a - d.a_lo)], d.tab[2 * (a - d.a_lo) + 1], d.f, d.sh, d.w, d.h, d.w, d.h};
+    b.Xt = (blockIdx.x % d.tiles_x) * TURN_TILE_W; b.Yt = (blockIdx.x / d.tiles_x) * TURN_TILE_H;
+    b.nx = (int)min(TURN_TILE_W, d.wr - b.Xt); b.ny = (int)min(TURN_TILE_H, d.hr - b.Yt);
+    b.tl = turned_tile(b.m, b.Xt, b.Yt, b.nx, b.ny);
+    const TurnedTile& tl = b.tl;
+    if (tl.bx1 - 1 < 1 || tl.bx0 > (int64_t)d.wr - 3 || tl.by1 - 1 < 1 || tl.by0 > (int64_t)d.hr - 3) return false;      // X0 is one of bx0 .. bx1 - 1
+    turned_stage(s_box, d.po, d.po_pitch, d.wr, d.hr, tl);
+    const auto local = [](int64_t v) { return (int32_t)turn_clamp(v, -4096, 4096); };
+    b.lox = max(local(1 - tl.bx0), 0); b.hix = min(local((int64_t)d.wr - 3 - tl.bx0), tl.bw - 2);
+    b.loy = max(local(1 - tl.by0), 0); b.hiy = min(local((int64_t)d.hr - 3 - tl.by0), tl.bh - 2);
+    return true;
+}
+
+// pixel (dx, dy) of the tile: whether it is valid, and then its turned value
+__device__ __forceinline__ bool angle_value(const AngleBlock& b, const TurnedBox& s_box, int dx, int dy, uint32_t& v) {
+    int32_t lrx, lry;
+    turned_pixel(b.m, b.tl, dx, dy, &lrx, &lry);
+    const int32_t X0 = lrx >> b.m.shift, Y0 = lry >> b.m.shift;
+    const bool valid = dx < b.nx && dy < b.ny && X0 >= b.lox && X0 <= b.hix && Y0 >= b.loy && Y0 <= b.hiy;
+    if (valid) v = turned_value(s_box, b.m, X0, Y0, lrx, lry);
+    return valid;
+}
+
+// grid: (tiles of the plane, slots, suspects); block: TURN_THREADS
+__global__ __launch_bounds__(TURN_THREADS) void angle_cost_kernel(AngleCost d) {
+    __shared__ TurnedBox s_box;
+    __shared__ uint32_t s_red[2][TURN_THREADS / 64];
+    const AngleLevel& lv = d.lv;
     const unsigned t = threadIdx.x, slot = blockIdx.y, sus = blockIdx.z;
-    const int32_t a = d.slots ? d.slots[(size_t)sus * ANGLE_SLOTS + slot] : d.a_first + ANGLE_RUNG_STEP * (int32_t)slot;
+    const int32_t a = d.slots ? d.slots[(size_t)sus * ANGLE_SLOTS + slot] : lv.a_first + ANGLE_RUNG_STEP * (int32_t)slot;
     if (a == ANG_SKIP) return;                                          // (uniform)
-    const int32_t C = d.tab[2 * (a - d.a_lo)], S = d.tab[2 * (a - d.a_lo) + 1];
-    const uint32_t Xt = (blockIdx.x % d.tiles_x) * ANG_TW, Yt = (blockIdx.x / d.tiles_x) * ANG_TH;
-    const int nx = (int)min(ANG_TW, d.wr - Xt), ny = (int)min(ANG_TH, d.hr - Yt);
-    // the tile's origin, 64 bits
-    const int64_t f = d.f;
-    const int64_t p0 = 2 * f * Xt + f - (int64_t)d.w, q0 = 2 * f * Yt + f - (int64_t)d.h;
-    const int64_t Rx0 = ((int64_t)d.w - f) * 65536 + C * p0 + S * q0;
-    const int64_t Ry0 = ((int64_t)d.h - f) * 65536 - S * p0 + C * q0;
-    // the four corners' offsets from it bound every pixel's: 2 f (C dx + S dy) and 2 f (-S dx + C dy)
-    const int32_t f2 = 2 * (int32_t)d.f, ex = f2 * (nx - 1), ey = f2 * (ny - 1);
-    const int32_t cxx = C * ex, sxy = S * ey, syx = -S * ex, cyy = C * ey;
-    const int32_t oxmin = min(0, cxx) + min(0, sxy), oxmax = max(0, cxx) + max(0, sxy);
-    const int32_t oymin = min(0, syx) + min(0, cyy), oymax = max(0, syx) + max(0, cyy);
-    const int64_t bx0 = (Rx0 + oxmin) >> d.sh, bx1 = ((Rx0 + oxmax) >> d.sh) + 1;       // the box: plane columns bx0 .. bx1
-    const int64_t by0 = (Ry0 + oymin) >> d.sh, by1 = ((Ry0 + oymax) >> d.sh) + 1;
-    // no pixel of the tile is valid: X0 is one of bx0 .. bx1 - 1
-    if (bx1 - 1 < 1 || bx0 > (int64_t)d.wr - 3 || by1 - 1 < 1 || by0 > (int64_t)d.hr - 3) return;      // (uniform)
-    const int bw = (int)ang_clamp(bx1 - bx0 + 1, 2, ANG_BOX_W), bh = (int)ang_clamp(by1 - by0 + 1, 2, ANG_BOX_H);      // (the bound holds)
-    for (int i = (int)t; i < bw * bh; i += (int)ANG_THREADS) {
-        const int r = i / bw, c = i - r * bw;
-        const int64_t gx = bx0 + c, gy = by0 + r;
-        const bool in = gx >= 0 && gx < (int64_t)d.wr && gy >= 0 && gy < (int64_t)d.hr;
-        s_box[r][c] = in ? d.po[(size_t)gy * d.po_pitch + (size_t)gx] : (uint8_t)0;
-    }
-    __syncthreads();
-    // valid as the box sees it: 1 <= X0 <= wr - 3 with X0 = bx0 + (local X0), the local one 0 .. bw - 2
-    const auto local = [](int64_t v) { return (int32_t)ang_clamp(v, -4096, 4096); };
-    const int32_t lox = max(local(1 - bx0), 0), hix = min(local((int64_t)d.wr - 3 - bx0), bw - 2);
-    const int32_t loy = max(local(1 - by0), 0), hiy = min(local((int64_t)d.hr - 3 - by0), bh - 2);
-    const int32_t lrx0 = (int32_t)(Rx0 - bx0 * ((int64_t)1 << d.sh)), lry0 = (int32_t)(Ry0 - by0 * ((int64_t)1 << d.sh));
-    const int dx = (int)(t % ANG_TW);
-    const uint8_t* __restrict__ ps = d.ps + (size_t)sus * d.ps_stride + (size_t)Yt * d.ps_pitch + Xt + dx;
+    AngleBlock b;
+    if (!angle_block(lv, a, s_box, b)) return;
+    const int dx = (int)(t % TURN_TILE_W);
+    const uint8_t* __restrict__ ps = lv.ps + (size_t)sus * lv.ps_stride + (size_t)b.Yt * lv.ps_pitch + b.Xt + dx;
     uint32_t diff = 0, votes = 0;
 #pragma unroll
-    for (int dy = (int)(t / ANG_TW); dy < (int)ANG_TH; dy += (int)ANG_ROWS) {
-        const int32_t lrx = lrx0 + f2 * (C * dx + S * dy), lry = lry0 + f2 * (C * dy - S * dx);
-        const int32_t X0 = lrx >> d.sh, Y0 = lry >> d.sh;
-        const bool valid = dx < nx && dy < ny && X0 >= lox && X0 <= hix && Y0 >= loy && Y0 <= hiy;
+    for (int dy = (int)(t / TURN_TILE_W); dy < (int)TURN_TILE_H; dy += (int)ANG_ROWS) {
+        uint32_t v = 0;
+        const bool valid = angle_value(b, s_box, dx, dy, v);
         if (valid) {
-            const uint32_t fx = (uint32_t)(lrx >> (d.sh - 8)) & 255u, fy = (uint32_t)(lry >> (d.sh - 8)) & 255u;
-            const uint32_t v00 = s_box[Y0][X0], v01 = s_box[Y0][X0 + 1], v10 = s_box[Y0 + 1][X0], v11 = s_box[Y0 + 1][X0 + 1];
-            const uint32_t v = ((256u - fx) * (256u - fy) * v00 + fx * (256u - fy) * v01 + (256u - fx) * fy * v10 + fx * fy * v11 + 32768u) >> 16;
-            const uint32_t s = ps[(size_t)dy * d.ps_pitch];
+            const uint32_t s = ps[(size_t)dy * lv.ps_pitch];
             diff += s > v ? s - v : v - s;
         }
         votes += (uint32_t)__popcll(__ballot(valid));
@@ -116,79 +125,37 @@ __global__ __launch_bounds__(ANG_THREADS) void angle_cost_kernel(AngleCost d) {
     if (t == 0) {
         uint32_t D = 0, c = 0;
 #pragma unroll
-        for (unsigned wv = 0; wv < ANG_THREADS / 64; ++wv) { D += s_red[0][wv]; c += s_red[1][wv]; }
-        unsigned long long* out = d.sums + ((size_t)sus * d.n_slots + slot) * 2;
+        for (unsigned wv = 0; wv < TURN_THREADS / 64; ++wv) { D += s_red[0][wv]; c += s_red[1][wv]; }
+        unsigned long long* out = lv.sums + ((size_t)sus * lv.n_slots + slot) * 2;
         if (c) { atomicAdd(out, (unsigned long long)D); atomicAdd(out + 1, (unsigned long long)c); }
     }
 }
 
 // The cost of one candidate angle for every member of a share-group (angle_share.hpp) at once -- the search inside
 // ssw_rotate_search_attack_rgb8, where all suspects have one original and the copies of one rotation nearly one list of angles.
-// The turned values v depend on (original, angle) only: a block stages the box and evaluates them once per (tile, candidate),
-// then compares them with the plane of every member that wants the candidate.  The box bound, the 64-bit origin, the staging
-// and the valid test are angle_cost_kernel's, number for number; all sums are integers, so a member's (D, c) EQUAL that kernel's.
-struct AngleShared {
-    const uint8_t* po;              // the original's plane [hr][po_pitch]
-    const uint8_t* ps;              // the suspects' planes [hr][ps_pitch], ps_stride bytes apart; ps_pitch % 4 == 0, ps_stride % 256 == 0
-    size_t ps_stride;
-    const int32_t* tab;             // C, S of angle a at tab[2 (a - a_lo)]
-    const ShareGroup* groups;       // grid z: the share-group sg0 + z
-    const ShareCand* cands;         // the refinement: candidate y of the group at [first_cand + y]; null: the ladder, every member wants rung y
-    unsigned long long* sums;       // [suspect][n_slots][2]: D, c -- at the rung (ladder), at the member's own slot (refinement)
-    uint32_t po_pitch, ps_pitch, wr, hr, w, h, f, sh, tiles_x, n_slots, sg0;
-    int32_t a_lo, a_first;          // the ladder: candidate y is the angle a_first + 8 y
-};
-
-// grid: (tiles of the plane, candidates, share-groups); block: ANG_THREADS.  A lane owns four consecutive pixels of one row of the
+// The turned values v depend on (original, angle) only: a block stages the box and evaluates them once per (tile, candidate)
+// -- angle_block and angle_value, as angle_cost_kernel --, then compares them with the plane of every member that wants the
+// candidate.  All sums are integers, so a member's (D, c) EQUAL that kernel's.
+// grid: (tiles of the plane, candidates, share-groups); block: TURN_THREADS.  A lane owns four consecutive pixels of one row of the
 // tile, one aligned word of a member's plane (pitches are multiples of 4, tile origins of 32, plane strides of 256).
-__global__ __launch_bounds__(ANG_THREADS) void angle_cost_shared_kernel(AngleShared d) {
-    __shared__ uint8_t s_box[ANG_BOX_H][ANG_BOX_W];
-    __shared__ uint32_t s_red[ANG_THREADS / 64][ANGLE_SHARE_MAX + 1];
+__global__ __launch_bounds__(TURN_THREADS) void angle_cost_shared_kernel(AngleShared d) {
+    __shared__ TurnedBox s_box;
+    __shared__ uint32_t s_red[TURN_THREADS / 64][ANGLE_SHARE_MAX + 1];
+    const AngleLevel& lv = d.lv;
     const unsigned t = threadIdx.x, cand = blockIdx.y;
     const ShareGroup& g = d.groups[d.sg0 + blockIdx.z];
     const ShareCand* sc = d.cands ? d.cands + g.first_cand + cand : nullptr;
-    const int32_t a = sc ? sc->a : d.a_first + ANGLE_RUNG_STEP * (int32_t)cand;
+    const int32_t a = sc ? sc->a : lv.a_first + ANGLE_RUNG_STEP * (int32_t)cand;
     const uint32_t want = sc ? sc->mask : (1u << g.n_members) - 1u;     // (uniform, as everything up to the staging)
-    const int32_t C = d.tab[2 * (a - d.a_lo)], S = d.tab[2 * (a - d.a_lo) + 1];
-    const uint32_t Xt = (blockIdx.x % d.tiles_x) * ANG_TW, Yt = (blockIdx.x / d.tiles_x) * ANG_TH;
-    const int nx = (int)min(ANG_TW, d.wr - Xt), ny = (int)min(ANG_TH, d.hr - Yt);
-    // the tile's origin, 64 bits
-    const int64_t f = d.f;
-    const int64_t p0 = 2 * f * Xt + f - (int64_t)d.w, q0 = 2 * f * Yt + f - (int64_t)d.h;
-    const int64_t Rx0 = ((int64_t)d.w - f) * 65536 + C * p0 + S * q0;
-    const int64_t Ry0 = ((int64_t)d.h - f) * 65536 - S * p0 + C * q0;
-    const int32_t f2 = 2 * (int32_t)d.f, ex = f2 * (nx - 1), ey = f2 * (ny - 1);
-    const int32_t cxx = C * ex, sxy = S * ey, syx = -S * ex, cyy = C * ey;
-    const int32_t oxmin = min(0, cxx) + min(0, sxy), oxmax = max(0, cxx) + max(0, sxy);
-    const int32_t oymin = min(0, syx) + min(0, cyy), oymax = max(0, syx) + max(0, cyy);
-    const int64_t bx0 = (Rx0 + oxmin) >> d.sh, bx1 = ((Rx0 + oxmax) >> d.sh) + 1;
-    const int64_t by0 = (Ry0 + oymin) >> d.sh, by1 = ((Ry0 + oymax) >> d.sh) + 1;
-    if (bx1 - 1 < 1 || bx0 > (int64_t)d.wr - 3 || by1 - 1 < 1 || by0 > (int64_t)d.hr - 3) return;      // (uniform) no pixel of the tile is valid
-    const int bw = (int)ang_clamp(bx1 - bx0 + 1, 2, ANG_BOX_W), bh = (int)ang_clamp(by1 - by0 + 1, 2, ANG_BOX_H);
-    for (int i = (int)t; i < bw * bh; i += (int)ANG_THREADS) {
-        const int r = i / bw, c = i - r * bw;
-        const int64_t gx = bx0 + c, gy = by0 + r;
-        const bool in = gx >= 0 && gx < (int64_t)d.wr && gy >= 0 && gy < (int64_t)d.hr;
-        s_box[r][c] = in ? d.po[(size_t)gy * d.po_pitch + (size_t)gx] : (uint8_t)0;
-    }
-    __syncthreads();
-    const auto local = [](int64_t v) { return (int32_t)ang_clamp(v, -4096, 4096); };
-    const int32_t lox = max(local(1 - bx0), 0), hix = min(local((int64_t)d.wr - 3 - bx0), bw - 2);
-    const int32_t loy = max(local(1 - by0), 0), hiy = min(local((int64_t)d.hr - 3 - by0), bh - 2);
-    const int32_t lrx0 = (int32_t)(Rx0 - bx0 * ((int64_t)1 << d.sh)), lry0 = (int32_t)(Ry0 - by0 * ((int64_t)1 << d.sh));
+    AngleBlock b;
+    if (!angle_block(lv, a, s_box, b)) return;
     // the lane's four turned values as one word, and the bytes of it that are valid
-    const int dx0 = 4 * (int)(t % (ANG_TW / 4)), dy = (int)(t / (ANG_TW / 4));
+    const int dx0 = 4 * (int)(t % (TURN_TILE_W / 4)), dy = (int)(t / (TURN_TILE_W / 4));
     uint32_t V = 0, M = 0, votes = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int dx = dx0 + i;
-        const int32_t lrx = lrx0 + f2 * (C * dx + S * dy), lry = lry0 + f2 * (C * dy - S * dx);
-        const int32_t X0 = lrx >> d.sh, Y0 = lry >> d.sh;
-        const bool valid = dx < nx && dy < ny && X0 >= lox && X0 <= hix && Y0 >= loy && Y0 <= hiy;
-        if (valid) {
-            const uint32_t fx = (uint32_t)(lrx >> (d.sh - 8)) & 255u, fy = (uint32_t)(lry >> (d.sh - 8)) & 255u;
-            const uint32_t v00 = s_box[Y0][X0], v01 = s_box[Y0][X0 + 1], v10 = s_box[Y0 + 1][X0], v11 = s_box[Y0 + 1][X0 + 1];
-            const uint32_t v = ((256u - fx) * (256u - fy) * v00 + fx * (256u - fy) * v01 + (256u - fx) * fy * v10 + fx * fy * v11 + 32768u) >> 16;
+        uint32_t v = 0;
+        if (angle_value(b, s_box, dx0 + i, dy, v)) {
             V |= v << (8 * i);
             M |= 255u << (8 * i);
             ++votes;
@@ -197,7 +164,7 @@ __global__ __launch_bounds__(ANG_THREADS) void angle_cost_shared_kernel(AngleSha
     // per member: one aligned word of its plane (a valid byte lies inside the plane, so the word lies inside its row), the
     // invalid bytes replaced by v's -- they add nothing -- and four absolute differences in one instruction
     // (a lane without a valid byte reads the plane's first word and adds nothing: no divergent branch; a plane has fewer than 2^32 bytes)
-    const uint32_t at = M ? (Yt + (uint32_t)dy) * d.ps_pitch + Xt + (uint32_t)dx0 : 0u;
+    const uint32_t at = M ? (b.Yt + (uint32_t)dy) * lv.ps_pitch + b.Xt + (uint32_t)dx0 : 0u;
     // Four members at a time, so that four loads are in flight and nothing but the staged values lives across a branch; a member
     // of the four that does not want the candidate reads member 0's word again and its sum is never looked at.  A lane's sum is
     // at most 4 * 255 and a wave's at most 65280: two members share a register through the wave's reduction.
@@ -209,7 +176,7 @@ __global__ __launch_bounds__(ANG_THREADS) void angle_cost_shared_kernel(AngleSha
 #pragma unroll
             for (unsigned k = 0; k < 4; ++k) {
                 const uint32_t member = ((wq >> k) & 1u) ? g.member[4 * q + k] : g.member[0];
-                P[k] = *reinterpret_cast<const uint32_t*>(d.ps + (size_t)member * d.ps_stride + at);
+                P[k] = *reinterpret_cast<const uint32_t*>(lv.ps + (size_t)member * lv.ps_stride + at);
             }
 #pragma unroll
             for (unsigned k = 0; k < 4; ++k) P[k] = __builtin_amdgcn_sad_u8((P[k] & M) | (V & ~M), V, 0u);
@@ -229,9 +196,9 @@ __global__ __launch_bounds__(ANG_THREADS) void angle_cost_shared_kernel(AngleSha
     if (t < ANGLE_SHARE_MAX && ((want >> t) & 1u)) {                    // c is counted once and added for every member
         uint32_t D = 0, c = 0;
 #pragma unroll
-        for (unsigned wv = 0; wv < ANG_THREADS / 64; ++wv) { D += s_red[wv][t]; c += s_red[wv][ANGLE_SHARE_MAX]; }
+        for (unsigned wv = 0; wv < TURN_THREADS / 64; ++wv) { D += s_red[wv][t]; c += s_red[wv][ANGLE_SHARE_MAX]; }
         const unsigned slot = sc ? sc->slot[t] : cand;
-        unsigned long long* out = d.sums + ((size_t)g.member[t] * d.n_slots + slot) * 2;
+        unsigned long long* out = lv.sums + ((size_t)g.member[t] * lv.n_slots + slot) * 2;
         if (c) { atomicAdd(out, (unsigned long long)D); atomicAdd(out + 1, (unsigned long long)c); }
     }
 }
@@ -298,17 +265,132 @@ __global__ __launch_bounds__(64) void angle_final_kernel(const int32_t* __restri
 namespace host {
 namespace {
 
-constexpr size_t ANG_GROUP_BYTES = (size_t)256 << 20;        // the planes of one group of suspects (one suspect's, if larger)
+constexpr size_t ANG_GROUP_BYTES = (size_t)256 << 20;        // the workspace of one group of suspects (one suspect's, if larger)
 constexpr size_t ANG_GROUP_MAX = 65535;                      // grid z
 
-size_t ang_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+bool rs_finite(const double* m, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(m[i])) return false;
+    return true;
+}
+bool rs_overlaps(const uint8_t* a, size_t na, const uint8_t* b, size_t nb) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa < pb + nb && pb < pa + na;
+}
+
+dim3 angle_grid(const AngleLevel& lv, unsigned y, unsigned z) { return dim3(lv.tiles_x * ((lv.hr + TURN_TILE_H - 1) / TURN_TILE_H), y, z); }
 
 int angle_launch(ssw_ctx* ctx, const AngleCost& d, size_t suspects) {
-    const unsigned tiles_y = (d.hr + ANG_TH - 1) / ANG_TH;
-    angle_cost_kernel<<<dim3(d.tiles_x * tiles_y, d.n_slots, (unsigned)suspects), ANG_THREADS, 0, ctx->stream>>>(d);
+    angle_cost_kernel<<<angle_grid(d.lv, d.lv.n_slots, (unsigned)suspects), TURN_THREADS, 0, ctx->stream>>>(d);
     SSW_HIP_CHECK(hipGetLastError());
     return SSW_OK;
 }
+
+int angle_shared_launch(ssw_ctx* ctx, const AngleShared& d, unsigned cands, unsigned share_groups) {
+    angle_cost_shared_kernel<<<angle_grid(d.lv, cands, share_groups), TURN_THREADS, 0, ctx->stream>>>(d);
+    SSW_HIP_CHECK(hipGetLastError());
+    return SSW_OK;
+}
+
+// What the two searches set up alike, once per call: the table, the layout of locate.angle_sums, the planes' geometry and the
+// workspace of a group of `per` suspects.  Nothing here is timed; the callers own every StageTimer.
+struct AngleSearch {
+    ssw_ctx* ctx;
+    size_t n, w, h, wq, hq;
+    int j0, j1;
+    unsigned n_rungs;
+    int32_t a_lo;
+    int32_t* dev_tab = nullptr;          // C, S of every angle of the range
+    // locate.angle_sums: answers [n][3] | rung sums [n][n_rungs][2] | refinement sums [n][ANGLE_SLOTS][2] | kept counts [n] -- all
+    // 64-bit, `zeroed` bytes of them -- | slot lists [n][ANGLE_SLOTS] i32 | share-groups [n] | their candidates [n ANGLE_SLOTS];
+    // the counts, groups and candidates for the strength report only
+    unsigned long long *res = nullptr, *rungs = nullptr, *fine = nullptr, *kept = nullptr;
+    int32_t* slots = nullptr;
+    ShareGroup* groups = nullptr;
+    ShareCand* cands = nullptr;
+    size_t zeroed = 0;
+    // planes: luma rows of lp bytes, box rows of qp bytes, a suspect's planes sl and sq bytes apart
+    unsigned lp, qp;
+    size_t sl, sq, per;
+    double px, pq;                       // a plane's pixels
+    uint8_t *lo = nullptr, *lo4 = nullptr, *sus_l = nullptr, *sus_q = nullptr;
+
+    AngleSearch(ssw_ctx* c, size_t n_, size_t w_, size_t h_, int j0_, int j1_)
+        : ctx(c), n(n_), w(w_), h(h_), wq(w_ / 4), hq(h_ / 4), j0(j0_), j1(j1_), n_rungs((unsigned)(j1_ - j0_ + 1)), a_lo(ANGLE_RUNG_STEP * j0_),
+          lp((unsigned)round_up(w_, 4)), qp((unsigned)round_up(w_ / 4, 4)), sl(round_up((size_t)lp * h_, 256)), sq(round_up((size_t)qp * (h_ / 4), 256)),
+          px((double)w_ * h_), pq((double)(w_ / 4) * (h_ / 4)) {}
+
+    // `extra`: what a suspect takes of a group's bytes beside its two planes; `report`: the strength report's call
+    int init(size_t extra, bool report) {
+        hipStream_t st = ctx->stream;
+        std::vector<int32_t> tab(2 * ((size_t)ANGLE_RUNG_STEP * (n_rungs - 1) + 1));
+        for (size_t i = 0; 2 * i < tab.size(); ++i) angle_table(a_lo + (int32_t)i, &tab[2 * i], &tab[2 * i + 1]);
+        SSW_TRY(grow_as(ctx->locate.angle_tab, tab.size() * sizeof(int32_t), dev_tab));
+        SSW_TRY(upload(ctx, dev_tab, tab.data(), tab.size() * sizeof(int32_t), st));
+        untimed_work(ctx);
+        size_t bytes = 0;
+        const auto take = [&bytes](size_t b) { const size_t at = bytes; bytes += b; return at; };
+        const size_t word = sizeof(unsigned long long);
+        const size_t o_res = take(n * 3 * word), o_rungs = take(n * 2 * n_rungs * word), o_fine = take(n * 2 * ANGLE_SLOTS * word);
+        const size_t o_kept = take(report ? n * word : 0);
+        zeroed = bytes;
+        const size_t o_slots = take(n * ANGLE_SLOTS * sizeof(int32_t)), o_groups = take(report ? n * sizeof(ShareGroup) : 0);
+        const size_t o_cands = take(report ? n * ANGLE_SLOTS * sizeof(ShareCand) : 0);
+        uint8_t* base = nullptr;
+        SSW_TRY(grow_as(ctx->locate.angle_sums, bytes, base));
+        using Sums = unsigned long long*;
+        res = reinterpret_cast<Sums>(base + o_res); rungs = reinterpret_cast<Sums>(base + o_rungs); fine = reinterpret_cast<Sums>(base + o_fine);
+        kept = reinterpret_cast<Sums>(base + o_kept); slots = reinterpret_cast<int32_t*>(base + o_slots);
+        groups = reinterpret_cast<ShareGroup*>(base + o_groups); cands = reinterpret_cast<ShareCand*>(base + o_cands);
+        per = std::min(n, std::min(ANG_GROUP_MAX, std::max<size_t>(1, ANG_GROUP_BYTES / (extra + sl + sq))));
+        SSW_TRY(grow_as(ctx->locate.luma, (size_t)lp * h + 16, lo));
+        SSW_TRY(grow_as(ctx->locate.phases, (size_t)qp * hq + 16, lo4));
+        SSW_TRY(grow_as(ctx->locate.group, per * (sl + sq) + 16, sus_l));
+        sus_q = sus_l + per * sl;
+        return SSW_OK;
+    }
+    // the sums zeroed and the original's luma and 4 x 4 box planes
+    int original_planes(const uint8_t* dev_base) {
+        SSW_HIP_CHECK(hipMemsetAsync(res, 0, zeroed, ctx->stream));
+        SSW_TRY(locate_luma_planes(ctx, dev_base, 1, w, h, lo, 0, lp));
+        return locate_box4_planes(ctx, lo, 0, lp, 1, w, h, lo4, 0, qp);
+    }
+    // ... and those of the m suspects of a group
+    int suspect_planes(const uint8_t* frames, size_t m) {
+        SSW_TRY(locate_luma_planes(ctx, frames, m, w, h, sus_l, sl, lp));
+        return locate_box4_planes(ctx, sus_l, sl, lp, m, w, h, sus_q, sq, qp);
+    }
+    // a level for the group that begins at suspect g0: the ladder, every rung at f = 4 on the box planes, or the refinement, the
+    // slot lists at f = 1 on the luma planes
+    AngleLevel level(bool refine, size_t g0) const {
+        AngleLevel lv{};
+        lv.tab = dev_tab; lv.a_lo = a_lo; lv.a_first = a_lo; lv.w = (uint32_t)w; lv.h = (uint32_t)h; lv.ps_stride = refine ? sl : sq;
+        lv.po = refine ? lo : lo4; lv.ps = refine ? sus_l : sus_q; lv.po_pitch = lv.ps_pitch = refine ? lp : qp;
+        lv.wr = (uint32_t)(refine ? w : wq); lv.hr = (uint32_t)(refine ? h : hq); lv.f = refine ? 1 : 4; lv.sh = refine ? 17 : 19;
+        lv.tiles_x = (lv.wr + TURN_TILE_W - 1) / TURN_TILE_W; lv.n_slots = refine ? ANGLE_SLOTS : n_rungs;
+        lv.sums = refine ? fine + g0 * 2 * ANGLE_SLOTS : rungs + g0 * 2 * n_rungs;
+        return lv;
+    }
+    // the ladder's launch of m suspects, nested as the coarse pass, as ssw_locate_rgb8 bills its own; then their kept rungs' slot lists
+    template <class Launch> int ladder(size_t g0, size_t m, Launch launch) {
+        {
+            StageTimer tc(ctx, SSW_STAGE_LOCATE_COARSE, ctx->stream);
+            if (ctx->timing) ctx->stage_work[SSW_STAGE_LOCATE_COARSE] += (double)m * n_rungs * pq;       // byte differences, not bytes
+            SSW_TRY(launch());
+        }
+        angle_keep_kernel<<<(unsigned)m, 256, 0, ctx->stream>>>(rungs + g0 * 2 * n_rungs, n_rungs, j0, j1, slots + g0 * ANGLE_SLOTS);
+        SSW_HIP_CHECK(hipGetLastError());
+        return SSW_OK;
+    }
+    // the answers of m suspects from their refinement sums
+    int answers(size_t g0, size_t m) {
+        angle_final_kernel<<<(unsigned)((m + 63) / 64), 64, 0, ctx->stream>>>(slots + g0 * ANGLE_SLOTS, fine + g0 * 2 * ANGLE_SLOTS, (unsigned)m, res + 3 * g0);
+        SSW_HIP_CHECK(hipGetLastError());
+        return SSW_OK;
+    }
+    ssw_angle_found found(const uint64_t* got) const { return ssw_angle_found{(int32_t)(int64_t)got[0], n_rungs, got[1], got[2]}; }
+};
+static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the sums come down as they are");
 
 }  // namespace
 }  // namespace host
@@ -332,102 +414,33 @@ extern "C" int ssw_find_angle_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const 
     if (w > ANGLE_PIXELS_MAX || h > ANGLE_PIXELS_MAX || w * h > ANGLE_PIXELS_MAX) return SSW_ERR_UNSUPPORTED;
     CtxGuard g(ctx);
     hipStream_t st = ctx->stream;
-    const unsigned n_rungs = (unsigned)(j1 - j0 + 1);
-    const int32_t a_lo = ANGLE_RUNG_STEP * j0;
-    // C, S of every angle of the range: one copy
-    std::vector<int32_t> tab(2 * ((size_t)ANGLE_RUNG_STEP * (n_rungs - 1) + 1));
-    for (size_t i = 0; 2 * i < tab.size(); ++i) angle_table(a_lo + (int32_t)i, &tab[2 * i], &tab[2 * i + 1]);
-    int32_t* dev_tab = nullptr;
-    SSW_TRY(grow_as(ctx->locate.angle_tab, tab.size() * sizeof(int32_t), dev_tab));
-    SSW_TRY(upload(ctx, dev_tab, tab.data(), tab.size() * sizeof(int32_t), st));
-    untimed_work(ctx);
-    // answers [n][3] | rung sums [n][n_rungs][2] | refinement sums [n][ANGLE_SLOTS][2] | slot lists [n][ANGLE_SLOTS] i32
-    const size_t head = n * (3 + 2 * (size_t)n_rungs), words = head + n * 2 * ANGLE_SLOTS;
-    unsigned long long* res = nullptr;
-    SSW_TRY(grow_as(ctx->locate.angle_sums, words * sizeof(unsigned long long) + n * ANGLE_SLOTS * sizeof(int32_t), res));
-    unsigned long long *rungs = res + 3 * n, *fine = res + head;
-    int32_t* slots = reinterpret_cast<int32_t*>(res + words);
-    // planes: luma rows of lp bytes, box rows of qp bytes
-    const size_t wq = w / 4, hq = h / 4;
-    const unsigned lp = (unsigned)ang_up(w, 4), qp = (unsigned)ang_up(wq, 4);
-    const size_t sl = ang_up((size_t)lp * h, 256), sq = ang_up((size_t)qp * hq, 256);
-    const size_t per = std::min(n, std::min(ANG_GROUP_MAX, std::max<size_t>(1, ANG_GROUP_BYTES / (sl + sq))));
-    uint8_t *lo = nullptr, *lo4 = nullptr, *ws = nullptr;
-    SSW_TRY(grow_as(ctx->locate.luma, (size_t)lp * h + 16, lo));
-    SSW_TRY(grow_as(ctx->locate.phases, (size_t)qp * hq + 16, lo4));
-    SSW_TRY(grow_as(ctx->locate.group, per * (sl + sq) + 16, ws));
+    AngleSearch s(ctx, n, w, h, j0, j1);
+    SSW_TRY(s.init(0, false));
+    const unsigned n_rungs = s.n_rungs;
     {
         // plane bytes: made once, read once per candidate
-        const double px = (double)w * h, pq = (double)wq * hq;
-        StageTimer t(ctx, SSW_STAGE_LOCATE, st, (double)(n + 1) * (4.0 * px + 2.0 * pq) + (double)n * 2.0 * (n_rungs * pq + ANGLE_SLOTS * px));
-        SSW_HIP_CHECK(hipMemsetAsync(res, 0, words * sizeof(unsigned long long), st));
-        SSW_TRY(locate_luma_planes(ctx, dev_base, 1, w, h, lo, 0, lp));
-        SSW_TRY(locate_box4_planes(ctx, lo, 0, lp, 1, w, h, lo4, 0, qp));
-        for (size_t g0 = 0; g0 < n; g0 += per) {
-            const size_t m = std::min(per, n - g0);
-            uint8_t *sus_l = ws, *sus_q = ws + per * sl;
-            SSW_TRY(locate_luma_planes(ctx, dev_suspects + g0 * w * h * 3, m, w, h, sus_l, sl, lp));
-            SSW_TRY(locate_box4_planes(ctx, sus_l, sl, lp, m, w, h, sus_q, sq, qp));
-            AngleCost d{};
-            d.tab = dev_tab; d.a_lo = a_lo; d.a_first = a_lo; d.w = (uint32_t)w; d.h = (uint32_t)h;
-            // the ladder: every rung at f = 4
-            d.po = lo4; d.po_pitch = qp; d.ps = sus_q; d.ps_stride = sq; d.ps_pitch = qp; d.wr = (uint32_t)wq; d.hr = (uint32_t)hq;
-            d.f = 4; d.sh = 19; d.tiles_x = (uint32_t)((wq + ANG_TW - 1) / ANG_TW); d.n_slots = n_rungs;
-            d.slots = nullptr; d.sums = rungs + g0 * 2 * n_rungs;
-            {
-                StageTimer tc(ctx, SSW_STAGE_LOCATE_COARSE, st);          // the coarse pass, as ssw_locate_rgb8 bills its own
-                if (ctx->timing) ctx->stage_work[SSW_STAGE_LOCATE_COARSE] += (double)m * n_rungs * pq;       // byte differences, not bytes
-                SSW_TRY(angle_launch(ctx, d, m));
-            }
-            angle_keep_kernel<<<(unsigned)m, 256, 0, st>>>(rungs + g0 * 2 * n_rungs, n_rungs, j0, j1, slots + g0 * ANGLE_SLOTS);
-            SSW_HIP_CHECK(hipGetLastError());
+        StageTimer t(ctx, SSW_STAGE_LOCATE, st, (double)(n + 1) * (4.0 * s.px + 2.0 * s.pq) + (double)n * 2.0 * (n_rungs * s.pq + ANGLE_SLOTS * s.px));
+        SSW_TRY(s.original_planes(dev_base));
+        for (size_t g0 = 0; g0 < n; g0 += s.per) {
+            const size_t m = std::min(s.per, n - g0);
+            SSW_TRY(s.suspect_planes(dev_suspects + g0 * w * h * 3, m));
+            const AngleCost rung{s.level(false, g0), nullptr};
+            SSW_TRY(s.ladder(g0, m, [&] { return angle_launch(ctx, rung, m); }));
             untimed_work(ctx);                                          // (the call's own timer ends behind everything, not with the ladder's)
-            // the refinement: the slot lists at f = 1
-            d.po = lo; d.po_pitch = lp; d.ps = sus_l; d.ps_stride = sl; d.ps_pitch = lp; d.wr = (uint32_t)w; d.hr = (uint32_t)h;
-            d.f = 1; d.sh = 17; d.tiles_x = (uint32_t)((w + ANG_TW - 1) / ANG_TW); d.n_slots = ANGLE_SLOTS;
-            d.slots = slots + g0 * ANGLE_SLOTS; d.sums = fine + g0 * 2 * ANGLE_SLOTS;
-            SSW_TRY(angle_launch(ctx, d, m));
-            angle_final_kernel<<<(unsigned)((m + 63) / 64), 64, 0, st>>>(slots + g0 * ANGLE_SLOTS, fine + g0 * 2 * ANGLE_SLOTS, (unsigned)m, res + 3 * g0);
-            SSW_HIP_CHECK(hipGetLastError());
+            SSW_TRY(angle_launch(ctx, AngleCost{s.level(true, g0), s.slots + g0 * ANGLE_SLOTS}, m));
+            SSW_TRY(s.answers(g0, m));
         }
     }
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the sums come down as they are");
-    std::vector<uint64_t> got(head);
-    SSW_HIP_CHECK(hipMemcpyAsync(got.data(), res, head * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    std::vector<uint64_t> got(n * (3 + 2 * (size_t)n_rungs));           // the answers and the rung sums lie together
+    SSW_HIP_CHECK(hipMemcpyAsync(got.data(), s.res, got.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     untimed_work(ctx);
     SSW_HIP_CHECK(hipStreamSynchronize(st));
-    for (size_t i = 0; i < n; ++i)
-        host_found[i] = ssw_angle_found{(int32_t)(int64_t)got[3 * i], n_rungs, got[3 * i + 1], got[3 * i + 2]};
+    for (size_t i = 0; i < n; ++i) host_found[i] = s.found(&got[3 * i]);
     if (host_rungs) std::copy(got.begin() + 3 * n, got.end(), host_rungs);
     return SSW_OK;
 }
 
 // ---- the unknown-angle row of the strength report ----------------------------------------------------------------------------
-namespace ssw {
-namespace host {
-namespace {
-
-bool rs_finite(const double* m, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(m[i])) return false;
-    return true;
-}
-bool rs_overlaps(const uint8_t* a, size_t na, const uint8_t* b, size_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + nb && pb < pa + na;
-}
-
-int angle_shared_launch(ssw_ctx* ctx, const AngleShared& d, unsigned cands, unsigned share_groups) {
-    const unsigned tiles_y = (d.hr + ANG_TH - 1) / ANG_TH;
-    angle_cost_shared_kernel<<<dim3(d.tiles_x * tiles_y, cands, share_groups), ANG_THREADS, 0, ctx->stream>>>(d);
-    SSW_HIP_CHECK(hipGetLastError());
-    return SSW_OK;
-}
-
-}  // namespace
-}  // namespace host
-}  // namespace ssw
-
 extern "C" int ssw_rotate_search_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_base, const uint8_t* dev_frames, size_t n_frames, size_t w, size_t h,
                                              const ssw_rotate_job* jobs, size_t n_jobs, double amin, double amax, uint8_t* dev_out,
                                              uint8_t* dev_turned, ssw_angle_found* host_found, uint64_t* host_rungs, uint64_t* host_kept) {
@@ -447,40 +460,17 @@ extern "C" int ssw_rotate_search_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_ba
                        rs_overlaps(dev_out, N * fb, dev_turned, N * fb))) return SSW_ERR_BAD_ARG;
     CtxGuard g(ctx);
     hipStream_t st = ctx->stream;
-    const unsigned n_rungs = (unsigned)(j1 - j0 + 1);
-    const int32_t a_lo = ANGLE_RUNG_STEP * j0;
-    std::vector<int32_t> tab(2 * ((size_t)ANGLE_RUNG_STEP * (n_rungs - 1) + 1));
-    for (size_t i = 0; 2 * i < tab.size(); ++i) angle_table(a_lo + (int32_t)i, &tab[2 * i], &tab[2 * i + 1]);
-    int32_t* dev_tab = nullptr;
-    SSW_TRY(grow_as(ctx->locate.angle_tab, tab.size() * sizeof(int32_t), dev_tab));
-    SSW_TRY(upload(ctx, dev_tab, tab.data(), tab.size() * sizeof(int32_t), st));
-    untimed_work(ctx);
-    // answers [N][3] | rung sums [N][n_rungs][2] | refinement sums [N][ANGLE_SLOTS][2] | kept counts [N] | slot lists [N][ANGLE_SLOTS] i32
-    // | share-groups [N] | their candidates [N ANGLE_SLOTS]
-    const size_t head = N * (3 + 2 * (size_t)n_rungs), words = head + N * 2 * ANGLE_SLOTS + N;
-    unsigned long long* res = nullptr;
-    SSW_TRY(grow_as(ctx->locate.angle_sums, words * sizeof(unsigned long long) + N * ANGLE_SLOTS * sizeof(int32_t) + N * sizeof(ShareGroup) +
-                                                N * ANGLE_SLOTS * sizeof(ShareCand), res));
-    unsigned long long *rungs = res + 3 * N, *fine = res + head, *kept = fine + N * 2 * ANGLE_SLOTS;
-    int32_t* slots = reinterpret_cast<int32_t*>(res + words);
-    ShareGroup* dev_groups = reinterpret_cast<ShareGroup*>(slots + N * ANGLE_SLOTS);
-    ShareCand* dev_cands = reinterpret_cast<ShareCand*>(dev_groups + N);
-    // planes: luma rows of lp bytes, box rows of qp bytes; a group: the turned frames and their planes, ANG_GROUP_BYTES at most
-    const size_t wq = w / 4, hq = h / 4;
-    const unsigned lp = (unsigned)ang_up(w, 4), qp = (unsigned)ang_up(wq, 4);
-    const size_t sl = ang_up((size_t)lp * h, 256), sq = ang_up((size_t)qp * hq, 256);
-    const size_t per = std::min(N, std::min(ANG_GROUP_MAX, std::max<size_t>(1, ANG_GROUP_BYTES / (fb + sl + sq))));
-    uint8_t *lo = nullptr, *lo4 = nullptr, *ws = nullptr, *turned_ws = nullptr;
-    SSW_TRY(grow_as(ctx->locate.luma, (size_t)lp * h + 16, lo));
-    SSW_TRY(grow_as(ctx->locate.phases, (size_t)qp * hq + 16, lo4));
-    SSW_TRY(grow_as(ctx->locate.group, per * (sl + sq) + 16, ws));
+    // a group: the turned frames and their planes, ANG_GROUP_BYTES at most
+    AngleSearch s(ctx, N, w, h, j0, j1);
+    SSW_TRY(s.init(fb, true));
+    const unsigned n_rungs = s.n_rungs;
+    const size_t per = s.per;
+    const double px = s.px, pq = s.pq;
+    uint8_t* turned_ws = nullptr;
     if (!dev_turned) SSW_TRY(grow_as(ctx->shared.affine, per * fb, turned_ws));
-    const double px = (double)w * h, pq = (double)wq * hq;
     {
         StageTimer t(ctx, SSW_STAGE_LOCATE, st, 4.0 * px + 2.0 * pq);
-        SSW_HIP_CHECK(hipMemsetAsync(res, 0, words * sizeof(unsigned long long), st));
-        SSW_TRY(locate_luma_planes(ctx, dev_base, 1, w, h, lo, 0, lp));
-        SSW_TRY(locate_box4_planes(ctx, lo, 0, lp, 1, w, h, lo4, 0, qp));
+        SSW_TRY(s.original_planes(dev_base));
     }
     std::map<int32_t, size_t> kept_at;                       // the angle found -> where its mask is counted
     std::vector<int32_t> found_n(N);
@@ -490,7 +480,6 @@ extern "C" int ssw_rotate_search_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_ba
     for (size_t g0 = 0; g0 < N; g0 += per) {
         const size_t m = std::min(per, N - g0);
         uint8_t* T = dev_turned ? dev_turned + g0 * fb : turned_ws;
-        uint8_t *sus_l = ws, *sus_q = ws + per * sl;
         {
             // the turn: consecutive jobs of one filter, fill and matrix in one set of launches
             StageTimer t(ctx, SSW_STAGE_RESIZE, st, (double)m * 2.0 * (double)fb);
@@ -508,54 +497,39 @@ extern "C" int ssw_rotate_search_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_ba
         std::vector<const double*> keys(m);
         for (size_t i = 0; i < m; ++i) keys[i] = jobs[g0 + i].forward;
         std::vector<ShareGroup> groups = angle_share_groups(keys);
-        SSW_TRY(upload(ctx, dev_groups, groups.data(), groups.size() * sizeof(ShareGroup), st));
+        SSW_TRY(upload(ctx, s.groups, groups.data(), groups.size() * sizeof(ShareGroup), st));
         untimed_work(ctx);
-        AngleShared d{};
-        d.tab = dev_tab; d.a_lo = a_lo; d.a_first = a_lo; d.w = (uint32_t)w; d.h = (uint32_t)h; d.groups = dev_groups;
         {
+            // the ladder: every member of a share-group
             StageTimer t(ctx, SSW_STAGE_LOCATE, st, (double)m * (4.0 * px + 2.0 * pq + 2.0 * n_rungs * pq));
-            SSW_TRY(locate_luma_planes(ctx, T, m, w, h, sus_l, sl, lp));
-            SSW_TRY(locate_box4_planes(ctx, sus_l, sl, lp, m, w, h, sus_q, sq, qp));
-            // the ladder: every rung at f = 4, every member of a share-group
-            d.po = lo4; d.po_pitch = qp; d.ps = sus_q; d.ps_stride = sq; d.ps_pitch = qp; d.wr = (uint32_t)wq; d.hr = (uint32_t)hq;
-            d.f = 4; d.sh = 19; d.tiles_x = (uint32_t)((wq + ANG_TW - 1) / ANG_TW); d.n_slots = n_rungs;
-            d.cands = nullptr; d.sums = rungs + g0 * 2 * n_rungs; d.sg0 = 0;
-            {
-                StageTimer tc(ctx, SSW_STAGE_LOCATE_COARSE, st);
-                if (ctx->timing) ctx->stage_work[SSW_STAGE_LOCATE_COARSE] += (double)m * n_rungs * pq;
-                SSW_TRY(angle_shared_launch(ctx, d, n_rungs, (unsigned)groups.size()));
-            }
-            angle_keep_kernel<<<(unsigned)m, 256, 0, st>>>(rungs + g0 * 2 * n_rungs, n_rungs, j0, j1, slots + g0 * ANGLE_SLOTS);
-            SSW_HIP_CHECK(hipGetLastError());
+            SSW_TRY(s.suspect_planes(T, m));
+            const AngleShared rung{s.level(false, g0), s.groups, nullptr, 0};
+            SSW_TRY(s.ladder(g0, m, [&] { return angle_shared_launch(ctx, rung, n_rungs, (unsigned)groups.size()); }));
         }
         // the first wait of the group: the slot lists come down, the host forms the unions and who wants what
         host_slots.resize(m * ANGLE_SLOTS);
-        SSW_TRY(download(ctx, host_slots.data(), slots + g0 * ANGLE_SLOTS, m * ANGLE_SLOTS * sizeof(int32_t), st));
+        SSW_TRY(download(ctx, host_slots.data(), s.slots + g0 * ANGLE_SLOTS, m * ANGLE_SLOTS * sizeof(int32_t), st));
         angle_share_cands(host_slots.data(), groups, cands);
-        SSW_TRY(upload(ctx, dev_groups, groups.data(), groups.size() * sizeof(ShareGroup), st));
-        SSW_TRY(upload(ctx, dev_cands, cands.data(), cands.size() * sizeof(ShareCand), st));
+        SSW_TRY(upload(ctx, s.groups, groups.data(), groups.size() * sizeof(ShareGroup), st));
+        SSW_TRY(upload(ctx, s.cands, cands.data(), cands.size() * sizeof(ShareCand), st));
         untimed_work(ctx);
         {
-            // the refinement at f = 1: one launch per share-group, its grid exactly the group's candidates
+            // the refinement: one launch per share-group, its grid exactly the group's candidates
             StageTimer t(ctx, SSW_STAGE_LOCATE, st, (double)cands.size() * px + (double)m * ANGLE_SLOTS * px);
-            d.po = lo; d.po_pitch = lp; d.ps = sus_l; d.ps_stride = sl; d.ps_pitch = lp; d.wr = (uint32_t)w; d.hr = (uint32_t)h;
-            d.f = 1; d.sh = 17; d.tiles_x = (uint32_t)((w + ANG_TW - 1) / ANG_TW); d.n_slots = ANGLE_SLOTS;
-            d.cands = dev_cands; d.sums = fine + g0 * 2 * ANGLE_SLOTS;
-            for (size_t s = 0; s < groups.size(); ++s) {
-                if (!groups[s].n_cands) continue;
-                d.sg0 = (uint32_t)s;
-                SSW_TRY(angle_shared_launch(ctx, d, groups[s].n_cands, 1));
+            AngleShared d{s.level(true, g0), s.groups, s.cands, 0};
+            for (size_t sg = 0; sg < groups.size(); ++sg) {
+                if (!groups[sg].n_cands) continue;
+                d.sg0 = (uint32_t)sg;
+                SSW_TRY(angle_shared_launch(ctx, d, groups[sg].n_cands, 1));
             }
-            angle_final_kernel<<<(unsigned)((m + 63) / 64), 64, 0, st>>>(slots + g0 * ANGLE_SLOTS, fine + g0 * 2 * ANGLE_SLOTS, (unsigned)m, res + 3 * g0);
-            SSW_HIP_CHECK(hipGetLastError());
+            SSW_TRY(s.answers(g0, m));
         }
         // the second wait: the answers, which shape the undoing
-        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the sums come down as they are");
         got.resize(3 * m);
-        SSW_TRY(download(ctx, got.data(), res + 3 * g0, 3 * m * sizeof(uint64_t), st));
+        SSW_TRY(download(ctx, got.data(), s.res + 3 * g0, 3 * m * sizeof(uint64_t), st));
         untimed_work(ctx);
         for (size_t i = 0; i < m; ++i) {
-            host_found[g0 + i] = ssw_angle_found{(int32_t)(int64_t)got[3 * i], n_rungs, got[3 * i + 1], got[3 * i + 2]};
+            host_found[g0 + i] = s.found(&got[3 * i]);
             found_n[g0 + i] = host_found[g0 + i].n;
         }
         {
@@ -576,7 +550,7 @@ extern "C" int ssw_rotate_search_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_ba
                     if (!kept_at.count(found_n[i0])) {
                         const size_t at = kept_at.size();
                         kept_at[found_n[i0]] = at;
-                        SSW_TRY(affine_kept_enqueue(ctx, w, h, B, F, kept + at));
+                        SSW_TRY(affine_kept_enqueue(ctx, w, h, B, F, s.kept + at));
                     }
                 }
                 i0 = i1;
@@ -585,8 +559,8 @@ extern "C" int ssw_rotate_search_attack_rgb8(ssw_ctx* ctx, const uint8_t* dev_ba
     }
     // the call's last wait: the rung sums and the masks' counts
     std::vector<uint64_t> counts(kept_at.size());
-    if (!counts.empty()) SSW_HIP_CHECK(hipMemcpyAsync(counts.data(), kept, counts.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (host_rungs) SSW_HIP_CHECK(hipMemcpyAsync(host_rungs, rungs, N * 2 * (size_t)n_rungs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (!counts.empty()) SSW_HIP_CHECK(hipMemcpyAsync(counts.data(), s.kept, counts.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (host_rungs) SSW_HIP_CHECK(hipMemcpyAsync(host_rungs, s.rungs, N * 2 * (size_t)n_rungs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     untimed_work(ctx);
     SSW_HIP_CHECK(hipStreamSynchronize(st));
     for (size_t i = 0; i < N; ++i) {

@@ -8,13 +8,11 @@
 //
 // Kernel (the planes and the searches are locate.hip's):
 //   turned_template_kernel   THE HOT PATH THAT IS NEW, both epilogues: a block takes a tile of 32 x 32 template pixels of one
-//                            (suspect, angle).  The map is monotone in X and in Y, so the sample points of the tile's four corners
-//                            bound the box of the suspect's luma plane it touches: the box is staged in LDS and all four taps come
-//                            from there.  The tile's origin is formed in 64 bits, the box's origin subtracted, and a lane adds its
-//                            own offset in 32 bits -- integer adds, exact.  A lane makes 4 pixels of a row, one word.  The ladder's
-//                            epilogue puts the words into LDS and stores only the tile's 8 x 8 box means T_j (tiles are multiples
-//                            of 8 pixels: no box straddles two blocks), so a rung's template never reaches HBM at full resolution;
-//                            the refinement's epilogue stores the word.
+//                            (suspect, angle) and the staged box of the suspect's luma plane: turned_tile.hpp, with f = 1 and
+//                            -S.  A lane makes 4 pixels of a row, one word.  The ladder's epilogue puts the words into LDS and
+//                            stores only the tile's 8 x 8 box means T_j (tiles are multiples of 8 pixels: no box straddles two
+//                            blocks), so a rung's template never reaches HBM at full resolution; the refinement's epilogue
+//                            stores the word.
 // Launch descriptors travel as kernel arguments, 32 (suspect, angle) items per launch, like locate.hip's.
 #include <algorithm>
 #include <cstring>
@@ -22,13 +20,9 @@
 
 #include "ssw_host.hpp"
 #include "turned_tables.hpp"
+#include "turned_tile.hpp"
 
 namespace ssw {
-
-constexpr unsigned TRN_TW = 32, TRN_TH = 32, TRN_THREADS = 256;     // a lane: 4 pixels of one row of the tile
-// The staged box.  The sample points of a tile spread over (C 31 + |S| 31) / 65536 <= 31 sqrt(2) = 43.9 suspect pixels across and
-// down (at 45 degrees): their floors take at most 45 values, the second tap adds one.
-constexpr unsigned TRN_BOX_W = 48, TRN_BOX_H = 46;
 
 struct TurnedDev {
     const uint8_t* ls;           // the suspect's luma plane [sh][lpitch]
@@ -38,52 +32,29 @@ struct TurnedDev {
 };
 struct TurnedBatch { TurnedDev it[host::LOCATE_BATCH]; };
 
-__device__ inline int64_t trn_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-// grid: (tiles of all items of the launch); block: TRN_THREADS
-__global__ __launch_bounds__(TRN_THREADS) void turned_template_kernel(TurnedBatch b, unsigned n) {
-    __shared__ uint8_t s_box[TRN_BOX_H][TRN_BOX_W];
-    __shared__ uint32_t s_t[TRN_TH][TRN_TW / 4];
+// grid: (tiles of all items of the launch); block: TURN_THREADS.  A lane: 4 pixels of one row of the tile
+__global__ __launch_bounds__(TURN_THREADS) void turned_template_kernel(TurnedBatch b, unsigned n) {
+    __shared__ TurnedBox s_box;
+    __shared__ uint32_t s_t[TURN_TILE_H][TURN_TILE_W / 4];
     unsigned s = 0;
     while (s + 1 < n && blockIdx.x >= b.it[s + 1].tile_begin) ++s;
     const TurnedDev& d = b.it[s];
     const unsigned t = threadIdx.x, tile = blockIdx.x - d.tile_begin;
-    const int32_t C = d.C, S = d.S;
-    const uint32_t Xt = (tile % d.tiles_x) * TRN_TW, Yt = (tile / d.tiles_x) * TRN_TH;
-    const int nx = (int)min(TRN_TW, d.tw - Xt), ny = (int)min(TRN_TH, d.th - Yt);          // multiples of 8
-    // the tile's origin, 64 bits
-    const int64_t p0 = 2 * (int64_t)Xt + 1 - (int64_t)d.tw, q0 = 2 * (int64_t)Yt + 1 - (int64_t)d.th;
-    const int64_t Rx0 = ((int64_t)d.sw - 1) * 65536 + C * p0 - S * q0;
-    const int64_t Ry0 = ((int64_t)d.sh - 1) * 65536 + S * p0 + C * q0;
-    // the four corners' offsets from it bound every pixel's: 2 (C dx - S dy) and 2 (S dx + C dy)
-    const int32_t ex = 2 * (nx - 1), ey = 2 * (ny - 1);
-    const int32_t cxx = C * ex, sxy = -S * ey, syx = S * ex, cyy = C * ey;
-    const int32_t oxmin = min(0, cxx) + min(0, sxy), oxmax = max(0, cxx) + max(0, sxy);
-    const int32_t oymin = min(0, syx) + min(0, cyy), oymax = max(0, syx) + max(0, cyy);
-    const int64_t bx0 = (Rx0 + oxmin) >> 17, bx1 = ((Rx0 + oxmax) >> 17) + 1;         // the box: plane columns bx0 .. bx1
-    const int64_t by0 = (Ry0 + oymin) >> 17, by1 = ((Ry0 + oymax) >> 17) + 1;
-    const int bw = (int)trn_clamp(bx1 - bx0 + 1, 2, TRN_BOX_W), bh = (int)trn_clamp(by1 - by0 + 1, 2, TRN_BOX_H);      // (the bound holds)
-    for (int i = (int)t; i < bw * bh; i += (int)TRN_THREADS) {
-        const int r = i / bw, c = i - r * bw;
-        const int64_t gx = bx0 + c, gy = by0 + r;
-        const bool in = gx >= 0 && gx < (int64_t)d.sw && gy >= 0 && gy < (int64_t)d.sh;       // (every tap of a template is inside)
-        s_box[r][c] = in ? d.ls[(size_t)gy * d.lpitch + (size_t)gx] : (uint8_t)0;
-    }
-    __syncthreads();
-    const int32_t lrx0 = (int32_t)(Rx0 - bx0 * 131072), lry0 = (int32_t)(Ry0 - by0 * 131072);
-    const int dx0 = 4 * (int)(t % (TRN_TW / 4)), dy = (int)(t / (TRN_TW / 4));
+    const Turn m{d.C, -d.S, 1, 17, d.sw, d.sh, d.tw, d.th};            // the suspect's plane turned BACK into the template
+    const uint32_t Xt = (tile % d.tiles_x) * TURN_TILE_W, Yt = (tile / d.tiles_x) * TURN_TILE_H;
+    const int nx = (int)min(TURN_TILE_W, d.tw - Xt), ny = (int)min(TURN_TILE_H, d.th - Yt);          // multiples of 8
+    const TurnedTile tl = turned_tile(m, Xt, Yt, nx, ny);
+    turned_stage(s_box, d.ls, d.lpitch, d.sw, d.sh, tl);               // (every tap of a template is inside the plane)
+    const int dx0 = 4 * (int)(t % (TURN_TILE_W / 4)), dy = (int)(t / (TURN_TILE_W / 4));
     const bool mine = dx0 < nx && dy < ny;
     uint32_t word = 0;
     if (mine) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int dx = dx0 + k;
-            const int32_t lrx = lrx0 + 2 * (C * dx - S * dy), lry = lry0 + 2 * (S * dx + C * dy);
-            const int32_t X0 = min(max(lrx >> 17, 0), bw - 2), Y0 = min(max(lry >> 17, 0), bh - 2);       // (inside the box as it is)
-            const uint32_t fx = (uint32_t)(lrx >> 9) & 255u, fy = (uint32_t)(lry >> 9) & 255u;
-            const uint32_t v00 = s_box[Y0][X0], v01 = s_box[Y0][X0 + 1], v10 = s_box[Y0 + 1][X0], v11 = s_box[Y0 + 1][X0 + 1];
-            const uint32_t v = ((256u - fx) * (256u - fy) * v00 + fx * (256u - fy) * v01 + (256u - fx) * fy * v10 + fx * fy * v11 + 32768u) >> 16;
-            word |= v << (8 * k);
+            int32_t lrx, lry;
+            turned_pixel(m, tl, dx0 + k, dy, &lrx, &lry);
+            const int32_t X0 = min(max(lrx >> m.shift, 0), tl.bw - 2), Y0 = min(max(lry >> m.shift, 0), tl.bh - 2);       // (inside the box as it is)
+            word |= turned_value(s_box, m, X0, Y0, lrx, lry) << (8 * k);
         }
     }
     if (!d.boxes) {                                                              // (uniform)
@@ -111,16 +82,14 @@ namespace {
 
 constexpr size_t TRN_GROUP_BYTES = (size_t)256 << 20;        // workspace of one group: suspects' planes, a launch's boxes and D, templates
 
-size_t trn_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 struct TurnedSuspect { const uint8_t* ls; uint32_t sw, sh, lpitch; };
 // one (suspect, angle): the template and where it goes
 struct TurnedItem { uint32_t sus; int32_t n; uint32_t tw, th, opitch; size_t bytes; uint8_t* out; };
 
 TurnedItem turned_item(uint32_t sus, int32_t n, uint32_t tw, uint32_t th, bool boxes) {
     TurnedItem it{sus, n, tw, th, 0, 0, nullptr};
-    it.opitch = (uint32_t)trn_up(boxes ? tw / 8 : tw, 4);
-    it.bytes = trn_up((size_t)it.opitch * (boxes ? th / 8 : th), 256);
+    it.opitch = (uint32_t)round_up(boxes ? tw / 8 : tw, 4);
+    it.bytes = round_up((size_t)it.opitch * (boxes ? th / 8 : th), 256);
     return it;
 }
 
@@ -138,11 +107,11 @@ int enqueue_templates(ssw_ctx* ctx, const std::vector<TurnedSuspect>& sus, const
             const TurnedSuspect& su = sus[it.sus];
             TurnedDev& d = tb.it[s];
             d.ls = su.ls; d.out = it.out; d.lpitch = su.lpitch; d.sw = su.sw; d.sh = su.sh; d.tw = it.tw; d.th = it.th; d.opitch = it.opitch;
-            d.tiles_x = (it.tw + TRN_TW - 1) / TRN_TW; d.tile_begin = tiles; d.boxes = boxes ? 1u : 0u;
+            d.tiles_x = (it.tw + TURN_TILE_W - 1) / TURN_TILE_W; d.tile_begin = tiles; d.boxes = boxes ? 1u : 0u;
             angle_table(it.n, &d.C, &d.S);
-            tiles += d.tiles_x * ((it.th + TRN_TH - 1) / TRN_TH);
+            tiles += d.tiles_x * ((it.th + TURN_TILE_H - 1) / TURN_TILE_H);
         }
-        turned_template_kernel<<<tiles, TRN_THREADS, 0, ctx->stream>>>(tb, m);
+        turned_template_kernel<<<tiles, TURN_THREADS, 0, ctx->stream>>>(tb, m);
         SSW_HIP_CHECK(hipGetLastError());
     }
     return SSW_OK;
@@ -154,14 +123,14 @@ int suspect_planes(ssw_ctx* ctx, const void* const* dev_suspects, const ssw_turn
     std::vector<size_t> off;
     for (size_t i = i0; i < i1; ++i) {
         off.push_back(total);
-        total += trn_up(trn_up(shapes[i].w, 4) * (size_t)shapes[i].h, 256);
+        total += round_up(round_up(shapes[i].w, 4) * (size_t)shapes[i].h, 256);
     }
     uint8_t* planes = nullptr;
     SSW_TRY(grow_as(ctx->locate.turned_luma, total + 16, planes));
     StageTimer t(ctx, SSW_STAGE_LOCATE, ctx->stream, 4.0 * (double)total);
     sus->clear();
     for (size_t i = i0; i < i1; ++i) {
-        const TurnedSuspect s{planes + off[i - i0], shapes[i].w, shapes[i].h, (uint32_t)trn_up(shapes[i].w, 4)};
+        const TurnedSuspect s{planes + off[i - i0], shapes[i].w, shapes[i].h, (uint32_t)round_up(shapes[i].w, 4)};
         SSW_TRY(locate_luma_planes(ctx, (const uint8_t*)dev_suspects[i], 1, s.sw, s.sh, planes + off[i - i0], 0, s.lpitch));
         sus->push_back(s);
     }
@@ -207,7 +176,7 @@ int turned_group(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, cons
     SSW_HIP_CHECK(hipMemsetAsync(keys, 0xFF, nr * LOCATE_KEY_STRIDE * sizeof(uint64_t), st));
     untimed_work(ctx);
     // launches of at most LOCATE_BATCH rungs and a group's bytes of workspace (T and D of each)
-    auto d_bytes = [&](const TurnedItem& it) { return trn_up((size_t)((w - it.tw) / TURNED_STRIDE + 1) * ((h - it.th) / TURNED_STRIDE + 1) * 4, 256); };
+    auto d_bytes = [&](const TurnedItem& it) { return round_up((size_t)((w - it.tw) / TURNED_STRIDE + 1) * ((h - it.th) / TURNED_STRIDE + 1) * 4, 256); };
     for (size_t b0 = 0; b0 < nr;) {
         size_t b1 = b0, bytes = 0;
         while (b1 < nr && b1 - b0 < LOCATE_BATCH && (b1 == b0 || bytes + items[b1].bytes + d_bytes(items[b1]) <= TRN_GROUP_BYTES)) {

@@ -10,6 +10,9 @@
 namespace ssw {
 namespace host {
 
+// v rounded up to a multiple of a
+inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
 // Makes the context's GPU current for the duration of one ABI call and restores the caller's device
 // afterwards (a host thread may drive several contexts, or torch on another GPU).
 struct DeviceGuard {

@@ -215,6 +215,17 @@ def test_host_table_is_pythons_for_every_angle(tmp_path, sanitize):
     assert [line.split()[0] for line in out.splitlines()] == ["0"] * len(bad)
 
 
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_the_staged_box_holds_every_tile(tmp_path, sanitize):
+    """csrc/turned_tile.hpp, the tile the two cost kernels and turned_template_kernel share: the 48 x 46 box is never clamped, the
+    32-bit taps are the definition's and lie inside it, nothing overflows -- every angle, both levels, both signs of S (the cases:
+    tests/cpp/turned_tile_test.cpp).  A stand-alone program, plain and under ASan/UBSan"""
+    exe = build_exe(tmp_path, "turned_tile_test", ["turned_tile_test.cpp"], sanitize)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stderr == "", out.stdout + out.stderr
+    assert out.stdout.startswith("turned tile: ok (")
+
+
 def test_the_library_exports_the_table():
     import ctypes as C
     lib = L.load()

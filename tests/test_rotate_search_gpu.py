@@ -171,6 +171,17 @@ def test_find_angle_answers_the_same_on_the_same_turned_frames():
     assert alone == found and np.array_equal(alone_rungs, rungs)
 
 
+def test_every_rung_sum_is_find_angles_on_the_turned_frames():
+    """angle_cost_shared_kernel against angle_cost_kernel at every rung, not only the winner: one 65 x 41 frame, 3 copies, +-2
+    degrees -- the rung sums [n][n_rungs][2] of the call are, word for word, those ssw_find_angle_rgb8 returns for dev_turned"""
+    base = smooth(65, 41)
+    jobs = [(i, 1.25, BICUBIC, FILL) for i in range(3)]
+    found, rungs, tur, _, _ = dev_search(base, variants(base, 3), jobs, -2, 2)
+    alone, alone_rungs = dev_find(base, list(tur), -2, 2)
+    assert rungs.shape == alone_rungs.shape == (3, 17, 2) and rungs.dtype == alone_rungs.dtype == np.uint64
+    assert np.array_equal(alone_rungs, rungs) and alone == found
+
+
 def test_a_report_without_a_searched_entry_leaves_locate_untimed():
     base = smooth(64, 48)
     c = ctx()
