@@ -614,6 +614,41 @@ int ssw_locate_scaled_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, 
 int ssw_locate_rung_boxes(ssw_ctx* ctx, const void* dev_suspect, size_t sw, size_t sh, size_t channels, size_t pw, size_t ph,
                           uint8_t* host_boxes);
 
+/* ---- locating a scaled cut-out whose aspect ratio was not kept exactly: a free height (csrc/locate_free.hip) ---- */
+/* The scale ladder tries one height per width.  A thumbnail made for the web has both sides rounded on their own (480 x 333
+   halves to 240 x 166, and ph(480) = 332), so the ladder's answer sits a row or a column off and the trace loses most of its
+   similarity.  This call is the ladder followed by a full-resolution rescoring of the sizes near its answer, in both dimensions.
+   pw, ph, x, y of each placement are OUTPUTS; w, h, channels are inputs; slack[s] = a, 1 <= a <= 4 (anything else:
+   SSW_ERR_BAD_ARG).  Definition, per suspect S [sh][sw][c] against the original O [H][W][3]; everything is an integer, no sum
+   depends on its order, and the result equals the numpy restatement in tests/test_locate_free_cpu.py exactly in pw, ph, x, y
+   and SAD:
+     1. A0 = (pw0, ph0, x0, y0) is exactly what ssw_locate_scaled_rgb8 answers for that suspect and range: every step and every
+        constant of it stays as it is, and its status codes pass through.
+     2. Sizes: every (pw, ph) with |pw - pw0| <= a, |ph - ph0| <= a, wmin <= pw <= wmax, min(pw, ph) >= 32, pw <= W, ph <= H.
+        The height is free of the aspect rule.
+     3. Positions, per size: x in [x0 - 4, x0 + 4] and [0, W - pw], y in [y0 - 4, y0 + 4] and [0, H - ph]; a window that is
+        empty after clipping contributes nothing.
+     4. SAD(pw, ph, x, y) = sum |L_R(i, j) - L_O(x + i, y + j)| over all pw ph pixels, with R and the luma of steps 1-2 of
+        ssw_locate_rgb8: R = S when the size is the suspect's own, else the CatmullRom resize with the taps, clamping and
+        rounding of csrc/resize_common.hpp.  An alpha channel is ignored.  No coarse pass and no top-8: every position of
+        the window is scored in full.
+     5. Answer: the smallest SAD / (pw ph), compared by cross-multiplication in 64 bits; ties: smaller pw, then smaller ph,
+        then y, then x.  A0 is one of the candidates, so the answer's SAD per pixel is never above A0's.
+   +-4 positions and the cap of 4 on a are fixed parts of the definition: at most 81 sizes x 81 positions per suspect.
+   Known limits: aspect deviations beyond +-4 pixels are not searched; a deliberately squeezed picture is not this call's
+   business; smooth regions stay ambiguous (as for ssw_locate_rgb8); there is no rotation.
+   What runs: the ladder, then per (suspect, size) one fused resize tile (the front end of the ladder's rung kernel) whose
+   epilogue sums the tile against the staged window of the original's luma plane: R is never stored.  Every tap table of the
+   stage goes up in one copy; 32 (suspect, size) items per launch.  The final comparison runs on the HOST: the call waits for
+   the stream three times, the ladder's two and once for the sums (81 x 8 bytes per size come back).  Workspace beyond the
+   ladder's: the sums and the tap tables, a few hundred KiB.  SSW_ERR_UNSUPPORTED: a size whose resize has no LDS tile
+   at all (the tile is chosen with the window counted, so no scale factor is refused for the window's sake).  Other status
+   codes as ssw_locate_scaled_rgb8; n == 0: SSW_OK.  Timed as the ladder is, the stage itself as SSW_STAGE_LOCATE and
+   SSW_STAGE_RESIZE (one kernel is both). */
+int ssw_locate_free_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, size_t h, const void* const* dev_suspects,
+                         ssw_placement* placements, const ssw_scale_range* ranges, const uint32_t* slack, size_t n,
+                         uint64_t* host_sad);
+
 /* ---- identifying a suspect's original: an image catalogue searched on the device ---- */
 /* Every stage above starts from "here is the original"; the finder of a leaked picture who owns a few thousand originals does
    not know which one it is.  These calls answer that, and so precede everything the reference's `test` command does with an

@@ -145,6 +145,7 @@ class TurnedJob(C.Structure):
 ANGLE_PER_DEGREE = 32        # ssw_find_angle_rgb8: the answer's resolution
 ANGLE_MIN_SIDE = 32          # ... refuses smaller frames
 LOCATE_SCALED_MIN_SIDE = 32  # ssw_locate_scaled_rgb8 refuses a range whose smallest rung has a side below this
+LOCATE_FREE_MAX_SLACK = 4    # ssw_locate_free_rgb8: sizes within 1 .. 4 pixels of the ladder's answer
 ANGLE_MAX_PIXELS = 1 << 27   # ... and larger ones
 
 # ssw_affine_filter, by the names the Python surface and the CLI accept (Pillow's)
@@ -246,6 +247,8 @@ SIGNATURES = {
     "ssw_locate_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, _sz, C.POINTER(C.c_uint64)]),
     "ssw_locate_scaled_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, C.POINTER(ScaleRange), _sz, C.POINTER(C.c_uint64)]),
     "ssw_locate_rung_boxes": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp]),
+    "ssw_locate_free_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, C.POINTER(ScaleRange), C.POINTER(C.c_uint32), _sz,
+                                       C.POINTER(C.c_uint64)]),
     "ssw_signature_rgb8": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(ImageShape), _sz, _vp]),
     "ssw_signature_host_rgb8": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(ImageShape), _sz, _vp]),
     "ssw_signature_match": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _u32p, _u32p, _u32p]),

@@ -742,24 +742,39 @@ class Locate:
     enlarged to twice its size after it was cut out) -- found by the scale ladder of ssw_locate_scaled_rgb8.  `turned=(lo, hi)`,
     or `turned=True` for +-10 degrees: the suspect is a cut-out of the frame TURNED by an unknown angle in that range -- what a
     photo editor's "straighten" leaves --, at the original's scale: angle and centre are found together (`locate_turned`) and the
-    suspect is laid back into the frame (`restore_turned`).  `turned=` goes with none of the others."""
+    suspect is laid back into the frame (`restore_turned`).  `turned=` goes with none of the others.  `aspect=a`, 1 .. 4, beside
+    `widths=` or `scale=`: the cut-out's sides were rounded on their own when it was scaled (480 x 333 halved is 240 x 166, not
+    the 332 rows the kept aspect ratio gives back), so the sizes within a pixels of the ladder's answer are rescored in both
+    dimensions (ssw_locate_free_rgb8).  0 or None: the ladder's answer as it is."""
     w: Optional[int] = None
     h: Optional[int] = None
     widths: Optional[Tuple[int, int]] = None
     scale: Optional[Tuple[float, float]] = None
     turned: Any = None
+    aspect: Optional[int] = None
+
+    def aspect_slack(self) -> int:
+        """a of an `aspect=` entry, 0 for any other; ValueError for an a outside 0 .. 4 or an entry that has no range of widths."""
+        if self.aspect is None:
+            return 0
+        if isinstance(self.aspect, bool) or int(self.aspect) != self.aspect or not 0 <= self.aspect <= L.LOCATE_FREE_MAX_SLACK:
+            raise ValueError(f"Locate: aspect= is an integer from 0 to {L.LOCATE_FREE_MAX_SLACK}")
+        if self.widths is None and self.scale is None:
+            raise ValueError("Locate: aspect= goes with widths= or scale=, not with (w, h) or turned=")
+        return int(self.aspect)
 
     def turned_range(self) -> Optional[Tuple[float, float]]:
         """(lo, hi) in degrees of a `turned=` entry, None for any other."""
         if self.turned is None or self.turned is False:
             return None
-        if self.w is not None or self.h is not None or self.widths is not None or self.scale is not None:
-            raise ValueError("Locate: turned= goes with none of (w, h), widths= and scale=")
+        if self.w is not None or self.h is not None or self.widths is not None or self.scale is not None or self.aspect is not None:
+            raise ValueError("Locate: turned= goes with none of (w, h), widths=, scale= and aspect=")
         return _search((-10.0, 10.0) if self.turned is True else self.turned, "Locate(turned=)")
 
     def width_range(self, suspect_width: int) -> Optional[Tuple[int, int]]:
         """(wmin, wmax) of a ranged entry -- scale factors rounded outwards --, None for an entry of known size."""
         self.turned_range()                                      # (refuses turned= beside the others)
+        self.aspect_slack()                                      # (refuses aspect= without a range)
         if self.widths is None and self.scale is None:
             return None
         if (self.widths is not None and self.scale is not None) or self.w is not None or self.h is not None:
@@ -812,7 +827,8 @@ def locate(base, suspects, sizes=None, ctx: Optional[Context] = None) -> list:
     cut-out is not supported).  sizes: None, or per suspect a `Locate(w, h)` / (w, h) pair / None -- the size the cut-out
     had in the original when it was scaled afterwards --, or a `Locate(widths=(lo, hi))` / `Locate(scale=(lo, hi))` when that
     size is unknown: those entries go through the scale ladder (ssw_locate_scaled_rgb8; aspect ratio kept, the smaller side at
-    least 32) and `Located.size` says what was found.  Returns one `Located` per suspect.  A turned cut-out is `locate_turned`'s; a
+    least 32) and `Located.size` says what was found; with `aspect=a` the sizes within a pixels of that answer are rescored in
+    both dimensions (ssw_locate_free_rgb8), for thumbnails whose sides were rounded on their own.  Returns one `Located` per suspect.  A turned cut-out is `locate_turned`'s; a
     cut-out of a featureless region (the cat's grey background) is ambiguous."""
     ctx = ctx or default_context()
     b = _base_rgb8(base)
@@ -846,15 +862,18 @@ def locate(base, suspects, sizes=None, ctx: Optional[Context] = None) -> list:
 
 
 def _locate_mixed(ctx, b, arrs, sizes, ranges) -> list:
-    """`locate` with ranged entries: one ssw_locate_scaled_rgb8 call for those, one ssw_locate_rgb8 call for the others."""
+    """`locate` with ranged entries: one ssw_locate_scaled_rgb8 call for those, one ssw_locate_rgb8 call for the others, and
+    one ssw_locate_free_rgb8 call for the ranged entries with `aspect` > 0."""
     H, W = b.shape[:2]
-    ranged = [i for i, r in enumerate(ranges) if r is not None]
+    slack = [z.aspect_slack() if isinstance(z, Locate) else 0 for z in sizes]
+    ranged = [i for i, r in enumerate(ranges) if r is not None and not slack[i]]
+    free = [i for i, r in enumerate(ranges) if r is not None and slack[i]]
     fixed = [i for i, r in enumerate(ranges) if r is None]
     out = [None] * len(arrs)
     dev_base = ctx.to_device(b)
     dev = [ctx.to_device(a) for a in arrs]
     try:
-        for idx, scaled in ((fixed, False), (ranged, True)):
+        for idx, scaled in ((fixed, False), (ranged, True), (free, True)):
             if not idx:
                 continue
             n = len(idx)
@@ -863,7 +882,11 @@ def _locate_mixed(ctx, b, arrs, sizes, ranges) -> list:
             if scaled:
                 pl = (L.Placement * n)(*[L.Placement(arrs[i].shape[1], arrs[i].shape[0], arrs[i].shape[2], 0, 0, 0, 0) for i in idx])
                 rg = (L.ScaleRange * n)(*[L.ScaleRange(*ranges[i]) for i in idx])
-                check(ctx._lib.ssw_locate_scaled_rgb8(ctx.handle, dev_base.ptr, W, H, ptrs, pl, rg, n, sad), "ssw_locate_scaled_rgb8")
+                if idx is free:
+                    sl = (C.c_uint32 * n)(*[slack[i] for i in idx])
+                    check(ctx._lib.ssw_locate_free_rgb8(ctx.handle, dev_base.ptr, W, H, ptrs, pl, rg, sl, n, sad), "ssw_locate_free_rgb8")
+                else:
+                    check(ctx._lib.ssw_locate_scaled_rgb8(ctx.handle, dev_base.ptr, W, H, ptrs, pl, rg, n, sad), "ssw_locate_scaled_rgb8")
             else:
                 pl = _locate_sizes([arrs[i] for i in idx], [sizes[i] for i in idx], W, H)
                 check(ctx._lib.ssw_locate_rgb8(ctx.handle, dev_base.ptr, W, H, ptrs, pl, n, sad), "ssw_locate_rgb8")

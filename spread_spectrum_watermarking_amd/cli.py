@@ -10,7 +10,7 @@
         -> <stem>_fp<i>.png (i zero-padded) and one <stem>_fp.json holding the N marks, described "<desc> #i";
            `test <file> <stem>_fp<i>.png <stem>_fp.json` then names the copy that leaked
     python -m spread_spectrum_watermarking_amd.cli trace <base> --suspects A.png B.png ... --marks X_fp.json [Y.json ...]
-            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] | FILE=rotate:DEGREES | FILE=rotate:? | FILE=rotate:LO..HI ...] [--locate FILE[=WxH|=W0..W1|=rotate:?|=rotate:LO..HI] ...]
+            [--similarity-exceed 6.0] [--place FILE=X,Y[,WxH] | FILE=rotate:DEGREES | FILE=rotate:? | FILE=rotate:LO..HI ...] [--locate FILE[=WxH|=W0..W1[~A]|=rotate:?|=rotate:LO..HI] ...]
         -> one record per suspect: the stored mark it carries (or none) and every further mark above the threshold;
            one GPU call per group of stored marks with equal (config, length), whatever the number of suspects.
            Attacked copies are restored on the GPU first (tests/attack_resize.rs:31-36, tests/attack_crop.rs:56-70): a
@@ -22,6 +22,8 @@
            --locate finds where a cut-out belongs (the size WxH it had in the base when it was scaled afterwards) by a
            search over every translation on the GPU; its record says "Located:" too.  FILE=W0..W1: the size is not known
            either, only that the cut-out was between W0 and W1 wide in the base -- a search over scale as well.
+           FILE=W0..W1~A (A from 1 to 4): its sides were rounded on their own, as a thumbnail's are -- the sizes within A
+           pixels of the scale search's answer are rescored in both dimensions.
            FILE=rotate:? (or FILE=rotate:LO..HI): the cut-out was taken from a copy TURNED by an unknown angle -- a search over
            angle and position together; the record says "Located: centre X,Y turned DEGREES"
     python -m spread_spectrum_watermarking_amd.cli index FILES... -o catalogue.npz [--marks FILE_fp.json ...]
@@ -240,7 +242,7 @@ def trace_placements(suspects: List[str], place: Optional[List[str]]) -> Dict[st
 
 
 def parse_locate(text: str, suspects: List[str]) -> Tuple[str, Locate]:
-    """FILE[=WxH] or FILE=W0..W1 -> (FILE, Locate); a text that is one of the suspects as it stands is a FILE without a size.
+    """FILE[=WxH] or FILE=W0..W1[~A] -> (FILE, Locate); a text that is one of the suspects as it stands is a FILE without a size.
     ValueError on anything else."""
     if text in suspects:
         return text, Locate()
@@ -256,12 +258,15 @@ def parse_locate(text: str, suspects: List[str]) -> Tuple[str, Locate]:
             raise ValueError(f"--locate {text!r}: expected FILE=rotate:? or FILE=rotate:LO..HI, degrees within +-45") from None
         return name, z
     if ".." in spec:                                     # a range of widths: the scale is unknown
+        spec, tilde, slack = spec.partition("~")         # ~A: the height may differ from the kept-aspect one by up to A pixels
         lo, _, hi = spec.partition("..")
         if not sep or not name or not (lo.isascii() and lo.isdigit() and hi.isascii() and hi.isdigit()):
-            raise ValueError(f"--locate {text!r}: expected FILE=W0..W1")
+            raise ValueError(f"--locate {text!r}: expected FILE=W0..W1[~A]")
+        if tilde and not (slack.isascii() and slack.isdigit() and len(slack) == 1 and 0 <= int(slack) <= 4):
+            raise ValueError(f"--locate {text!r}: expected FILE=W0..W1~A with A from 0 to 4")
         if not 0 < int(lo) <= int(hi):
             raise ValueError(f"--locate {text!r}: an empty range of widths")
-        return name, Locate(widths=(int(lo), int(hi)))
+        return name, (Locate(widths=(int(lo), int(hi)), aspect=int(slack)) if tilde else Locate(widths=(int(lo), int(hi))))
     ws, xs, hs = spec.partition("x")
     if not sep or not name or not xs or not (ws.isascii() and ws.isdigit() and hs.isascii() and hs.isdigit()):
         raise ValueError(f"--locate {text!r}: expected FILE[=WxH]")
@@ -357,9 +362,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Where the cut-out FILE (one of --suspects) lies in the base, and the size it had there; "
                         "FILE=rotate:DEGREES: a copy turned by a known angle; FILE=rotate:? or FILE=rotate:LO..HI: the angle is "
                         "searched for. Repeatable.")
-    r.add_argument("--locate", action="append", metavar="FILE[=WxH|=W0..W1|=rotate:?|=rotate:LO..HI]",
+    r.add_argument("--locate", action="append", metavar="FILE[=WxH|=W0..W1[~A]|=rotate:?|=rotate:LO..HI]",
                    help="Find where the cut-out FILE (one of --suspects) lies in the base; WxH: the size it had there; "
-                        "W0..W1: the widths it may have had there (the scale is searched too); rotate:? or rotate:LO..HI: it was "
+                        "W0..W1: the widths it may have had there (the scale is searched too; ~A, 1 to 4: width and height may each be "
+                        "up to A pixels off the size that search answers, as a thumbnail's rounded sides are); rotate:? or rotate:LO..HI: it was "
                         "cut out of a turned copy (angle and position are searched together). Repeatable.")
     x = sub.add_parser("index", help="Add originals to an image catalogue (created when it does not exist).")
     x.add_argument("files", nargs="+", help="The originals.")

@@ -646,28 +646,6 @@ constexpr unsigned LAD_STEP = 8, LAD_KEEP = 8, LAD_NEAR_W = 7, LAD_NEAR_XY = 8, 
 
 uint32_t ladder_height(uint64_t pw, uint64_t sw, uint64_t sh) { return (uint32_t)std::max<uint64_t>(1, (2 * sh * pw + sw) / (2 * sw)); }
 
-// every tap table of a call's ladder in one host buffer: one upload, one wait
-struct LadderTaps {
-    std::vector<uint32_t> words;
-    std::map<std::pair<size_t, size_t>, TapRef> refs;
-    const TapRef& get(size_t in_len, size_t out_len) {
-        const auto key = std::make_pair(in_len, out_len);
-        const auto it = refs.find(key);
-        if (it != refs.end()) return it->second;
-        ResizeTaps t;
-        build_resize_taps(in_len, out_len, t);
-        TapRef r;
-        r.left = (uint32_t)words.size();   words.insert(words.end(), t.left.begin(), t.left.end());
-        r.count = (uint32_t)words.size();  words.insert(words.end(), t.count.begin(), t.count.end());
-        r.weights = (uint32_t)words.size();
-        words.resize(words.size() + t.weights.size());
-        std::memcpy(words.data() + r.weights, t.weights.data(), t.weights.size() * sizeof(float));
-        r.shape.max_taps = t.max_taps;
-        resize_spans(t, out_len, r.shape.span);
-        return refs[key] = r;
-    }
-};
-
 struct Rung {
     uint32_t sus, pw, ph, tw, th, nx, ny;      // nx, ny: candidate positions (multiples of 4)
     RungDev dev;                               // src, T, taps and tile_begin are filled in per launch
@@ -690,14 +668,6 @@ int make_rung(LadderTaps& taps, const ssw_placement& p, uint32_t sus, uint32_t p
     r.bytes_t = up((size_t)d.tpitch * r.th, 256);
     r.bytes_d = up((size_t)r.nx * r.ny * 4, 256);
     *out = r;
-    return SSW_OK;
-}
-
-int upload_taps(ssw_ctx* ctx, const LadderTaps& taps, const uint32_t** dev) {
-    SSW_TRY(grow(ctx->locate.taps, taps.words.size() * sizeof(uint32_t)));
-    SSW_HIP_CHECK(hipMemcpyAsync(ctx->locate.taps.p, taps.words.data(), taps.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    untimed_work(ctx);
-    *dev = ctx->locate.taps.as<const uint32_t>();
     return SSW_OK;
 }
 
@@ -734,8 +704,14 @@ int enqueue_rungs(ssw_ctx* ctx, const std::vector<Rung>& rungs, size_t b0, size_
 
 }  // namespace
 
-// One suspect's answer of the scaled search
-struct ScaledAnswer { uint32_t pw, ph, x, y; uint64_t sad; };
+// (the host buffer `taps` must stay alive until the stream was waited for)
+int upload_taps(ssw_ctx* ctx, const LadderTaps& taps, const uint32_t** dev) {
+    SSW_TRY(grow(ctx->locate.taps, taps.words.size() * sizeof(uint32_t)));
+    SSW_HIP_CHECK(hipMemcpyAsync(ctx->locate.taps.p, taps.words.data(), taps.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    untimed_work(ctx);
+    *dev = ctx->locate.taps.as<const uint32_t>();
+    return SSW_OK;
+}
 
 // pl: w, h, channels of each suspect (checked); ranges [n][2].  Waits for the stream twice: for the ladder's per-rung minima
 // (the 8 kept rungs decide which widths are resized next, and restore_enqueue's launches are shaped on the host), and for the answer.

@@ -10,7 +10,11 @@
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <initializer_list>
+#include <map>
+#include <utility>
+#include <vector>
 
 #include "ssw_internal.hpp"
 
@@ -212,6 +216,28 @@ inline void resize_spans(const ResizeTaps& t, size_t out_len, uint32_t (&span)[8
     }
 }
 
+// every tap table of a call (the scale ladder of locate.hip, the sizes of locate_free.hip) in one host buffer: one upload, one wait
+struct LadderTaps {
+    std::vector<uint32_t> words;
+    std::map<std::pair<size_t, size_t>, TapRef> refs;
+    const TapRef& get(size_t in_len, size_t out_len) {
+        const auto key = std::make_pair(in_len, out_len);
+        const auto it = refs.find(key);
+        if (it != refs.end()) return it->second;
+        ResizeTaps t;
+        build_resize_taps(in_len, out_len, t);
+        TapRef r;
+        r.left = (uint32_t)words.size();   words.insert(words.end(), t.left.begin(), t.left.end());
+        r.count = (uint32_t)words.size();  words.insert(words.end(), t.count.begin(), t.count.end());
+        r.weights = (uint32_t)words.size();
+        words.resize(words.size() + t.weights.size());
+        std::memcpy(words.data() + r.weights, t.weights.data(), t.weights.size() * sizeof(float));
+        r.shape.max_taps = t.max_taps;
+        resize_spans(t, out_len, r.shape.span);
+        return refs[key] = r;
+    }
+};
+
 // The dynamic LDS a fused kernel may ask for: above the 64 KB a kernel gets by default, so every kernel that takes a tile of
 // pick_resize_tile needs the per-device function attribute -- set once per device (`done`: the caller's static flags; two
 // host threads, two contexts: no plain bools)
@@ -229,9 +255,10 @@ inline int resize_raise_lds_limit(std::initializer_list<const void*> kernels, st
 // tile shape: the cheapest one (input bytes loaded + vertical taps per output pixel) whose LDS footprint lets two
 // blocks share a CU; spans = reach (in input samples) of 1, 2, 4, ... 128 consecutive outputs (DeviceTaps::span);
 // ch interleaved input channels, 3 output bytes per pixel.  ey_min / ex_min: the smallest tile (log2) the caller can use --
-// locate_rung_kernel wants whole 8 x 8 boxes in a tile
+// locate_rung_kernel wants whole 8 x 8 boxes in a tile.  extra(oyb, oxb): bytes of LDS the caller puts behind the tile
+// (locate_free_kernel's window of the original), counted against the same budget; *lds_bytes stays the tile's own
 inline bool pick_resize_tile(const DeviceTaps& vt, const DeviceTaps& ht, size_t nw, size_t nh, unsigned ch, ResizeTile* out,
-                             size_t* lds_bytes, int ey_min = 0, int ex_min = 2) {
+                             size_t* lds_bytes, int ey_min = 0, int ex_min = 2, size_t (*extra)(unsigned, unsigned) = nullptr) {
     double best = 1e300;
     bool found = false;
     const double vtaps = (double)(vt.span[0] ? vt.span[0] : 1);
@@ -247,7 +274,7 @@ inline bool pick_resize_tile(const DeviceTaps& vt, const DeviceTaps& ht, size_t 
             const ResizeTile tl{oyb, oxb, pitch, rows, (unsigned)((nw + oxb - 1) / oxb), (unsigned)((nh + oyb - 1) / oyb), (unsigned)ex};
             const size_t lds = resize_lds_in_offset(tl, ht.max_taps, vt.max_taps) + (in_tile > out_tile ? in_tile : out_tile);
             if ((size_t)oxb * ht.max_taps > 1024 || (size_t)oyb * vt.max_taps > 1024) continue;   // tap tables: <= 4 values per thread
-            if (lds > RESIZE_LDS_LIMIT - 2 * 1024) continue;             // two blocks per CU (160 KB of LDS)
+            if (lds + (extra ? extra(oyb, oxb) : 0) > RESIZE_LDS_LIMIT - 2 * 1024) continue;   // two blocks per CU (160 KB of LDS)
             const double cost = ((double)rows * pitch + (double)oyb * pitch * vtaps) / ((double)oyb * oxb);
             if (cost < best) {
                 best = cost;

@@ -8,6 +8,7 @@
 #include "ssw_internal.hpp"
 
 namespace ssw {
+struct LadderTaps;               // resize_common.hpp
 namespace host {
 
 // v rounded up to a multiple of a
@@ -222,6 +223,14 @@ constexpr unsigned LOCATE_BATCH = 32, LOCATE_KEY_STRIDE = 8;
 struct BoxSearch { const uint8_t* T; uint32_t* D; uint32_t tpitch, tw, th, nx, ny; };
 int locate_box_searches(ssw_ctx* ctx, const uint8_t* planes, unsigned qpitch, unsigned qrows, size_t plane_stride, const BoxSearch* it, unsigned m,
                         uint64_t* keys);
+// locate.hip's scale ladder for locate_free.hip (ssw_locate_free_rgb8 starts from its answer): pl = w, h, channels of each suspect
+// (checked), ranges [n][2] = wmin, wmax; one answer per suspect.  Waits for the stream twice.  upload_taps: every tap table of a
+// call (resize_common.hpp: LadderTaps) into locate.taps with one copy on the context's stream; `taps` stays alive until the
+// stream was waited for.
+struct ScaledAnswer { uint32_t pw, ph, x, y; uint64_t sad; };
+int locate_scaled_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
+                       const std::vector<ssw_placement>& pl, const uint32_t* ranges, ScaledAnswer* out);
+int upload_taps(ssw_ctx* ctx, const LadderTaps& taps, const uint32_t** dev);
 // locate.hip's plane kernels for the angle search (angle.hip), enqueued on the context's stream: the luma planes of n frames
 // [h][w][3] (rows of `pitch` bytes, pitch % 4 == 0), and of such planes the decimated 4 x 4 box means (h / 4 rows of `opitch` bytes)
 int locate_luma_planes(ssw_ctx* ctx, const uint8_t* rgb, size_t n, size_t w, size_t h, uint8_t* out, size_t out_stride, unsigned pitch);

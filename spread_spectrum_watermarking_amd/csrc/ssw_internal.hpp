@@ -404,7 +404,8 @@ SSW_BUF_GROUP(TraceBufs, SSW_TRACE_BUFS);
 // them the kept counts, the share-groups and their candidates; its turned frames lie in shared.affine)
 // locate_turned.hip shares luma, group (the ladder's boxes and D), keys, box_planes and angle_tab and adds: the suspects' luma
 // planes | the full-resolution template planes of one group of the refinement's searches
-#define SSW_LOCATE_BUFS(X) X(luma) X(phases) X(group) X(keys) X(box_planes) X(taps) X(angle_tab) X(angle_sums) X(turned_luma) X(turned_templates)
+// locate_free.hip shares luma and taps and adds: the sums of every (suspect, size, position) of a call
+#define SSW_LOCATE_BUFS(X) X(luma) X(phases) X(group) X(keys) X(box_planes) X(taps) X(angle_tab) X(angle_sums) X(turned_luma) X(turned_templates) X(free_sums)
 SSW_BUF_GROUP(LocateBufs, SSW_LOCATE_BUFS);
 // catalogue.hip: the blocks' top-8 lists of a match | host form: one group of frames | its signatures
 #define SSW_CATALOGUE_BUFS(X) X(top8) X(frames) X(sigs)
