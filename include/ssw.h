@@ -648,6 +648,19 @@ int ssw_locate_rung_boxes(ssw_ctx* ctx, const void* dev_suspect, size_t sw, size
 int ssw_locate_free_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, size_t h, const void* const* dev_suspects,
                          ssw_placement* placements, const ssw_scale_range* ranges, const uint32_t* slack, size_t n,
                          uint64_t* host_sad);
+/* Diagnostic: steps 2-5 of ssw_locate_free_rgb8 for ONE suspect [sh][sw][channels] from a start A0 = (pw0, ph0, x0, y0) the
+   caller gives in place of the ladder's answer, every sum returned.  The same stage as the public call runs (the same items,
+   launches and host comparison); a = slack.  host_sums [(2a + 1)^2][81], 64 bits each: SAD(pw, ph, x, y) lies at size slot
+   (pw - pw0 + a) (2a + 1) + (ph - ph0 + a), position slot 9 (y - y0 + 4) + (x - x0 + 4) -- relative to the unclipped start, so
+   the layout does not depend on the clipping.  Every slot that the definition does not score holds UINT64_MAX: a size dropped
+   by wmin, wmax, 32, W or H, a position outside the clipped window, a window that is empty.  *answer (w, h, channels as given)
+   and *host_sad are step 5; when no size is scored at all they are A0 and 0.  SSW_ERR_BAD_ARG: a null pointer, slack outside
+   1 .. 4, channels not 3 or 4, a zero size, wmin > wmax (wmin below 32 is allowed: sizes stop at 32), a start the ladder never
+   answers: pw0 == 0, ph0 == 0, pw0 > w, ph0 > h, x0 > w - pw0 or y0 > h - ph0.  SSW_ERR_UNSUPPORTED as for the public call.
+   Waits for the stream once. */
+int ssw_locate_free_sums_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, size_t h, const void* dev_suspect, size_t sw,
+                              size_t sh, size_t channels, const uint32_t start[4] /* pw0, ph0, x0, y0 */, uint32_t wmin,
+                              uint32_t wmax, uint32_t slack, uint64_t* host_sums, ssw_placement* answer, uint64_t* host_sad);
 
 /* ---- identifying a suspect's original: an image catalogue searched on the device ---- */
 /* Every stage above starts from "here is the original"; the finder of a leaked picture who owns a few thousand originals does

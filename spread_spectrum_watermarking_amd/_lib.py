@@ -249,6 +249,8 @@ SIGNATURES = {
     "ssw_locate_rung_boxes": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp]),
     "ssw_locate_free_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(_vp), _plp, C.POINTER(ScaleRange), C.POINTER(C.c_uint32), _sz,
                                        C.POINTER(C.c_uint64)]),
+    "ssw_locate_free_sums_rgb8": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.POINTER(C.c_uint64), _plp, C.POINTER(C.c_uint64)]),
     "ssw_signature_rgb8": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(ImageShape), _sz, _vp]),
     "ssw_signature_host_rgb8": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(ImageShape), _sz, _vp]),
     "ssw_signature_match": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _u32p, _u32p, _u32p]),

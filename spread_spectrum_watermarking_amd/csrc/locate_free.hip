@@ -217,16 +217,14 @@ int enqueue_items(ssw_ctx* ctx, const std::vector<FreeItem>& items, size_t b0, s
     return SSW_OK;
 }
 
-}  // namespace
-
-// pl: w, h, channels of each suspect (checked); ranges [n][2]; slack [n], each 1 .. FREE_SLACK_MAX (checked).  Waits for the stream
-// three times: the ladder's two (locate_scaled_impl), and once for the sums of this stage.
-int locate_free_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
-                     const std::vector<ssw_placement>& pl, const uint32_t* ranges, const uint32_t* slack, ScaledAnswer* out) {
+// Steps 2-5 of the definition for n suspects from their starts a0 (the ladder's answers, or the start a caller of the diagnostic
+// gives): the items and the luma plane, the launches, the sums back, the comparison.  Waits for the stream once.
+// all_sums (ssw_locate_free_sums_rgb8; n == 1): [(2 a + 1)^2][FREE_POS], every sum of suspect 0 at its slot relative to the
+// unclipped start, all ones where nothing was scored.
+int free_stage(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects, const std::vector<ssw_placement>& pl,
+               const uint32_t* ranges, const uint32_t* slack, const ScaledAnswer* a0, ScaledAnswer* out, uint64_t* all_sums) {
     const size_t n = pl.size();
     hipStream_t st = ctx->stream;
-    std::vector<ScaledAnswer> a0(n);
-    SSW_TRY(locate_scaled_impl(ctx, dev_base, w, h, dev_suspects, pl, ranges, a0.data()));
     // sizes and windows, per suspect in the order (pw, ph): the order of the answer's ties
     LadderTaps taps;
     std::vector<FreeItem> items;
@@ -284,7 +282,29 @@ int locate_free_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, 
         }
         out[i] = best;
     }
+    if (all_sums) {
+        const int64_t a = slack[0], side = 2 * a + 1;
+        std::fill(all_sums, all_sums + side * side * FREE_POS, ~0ull);
+        for (size_t q = first[0]; q < first[1]; ++q) {
+            const FreeDev& d = items[q].dev;
+            uint64_t* slot = all_sums + (((int64_t)d.pw - a0[0].pw + a) * side + ((int64_t)d.ph - a0[0].ph + a)) * FREE_POS;
+            for (uint32_t dy = 0; dy < d.nwy; ++dy)
+                for (uint32_t dx = 0; dx < d.nwx; ++dx)
+                    slot[(d.ya + dy + FREE_NEAR - a0[0].y) * FREE_SIDE + (d.xa + dx + FREE_NEAR - a0[0].x)] = hs[q * FREE_POS + dy * FREE_SIDE + dx];
+        }
+    }
     return SSW_OK;
+}
+
+}  // namespace
+
+// pl: w, h, channels of each suspect (checked); ranges [n][2]; slack [n], each 1 .. FREE_SLACK_MAX (checked).  Waits for the stream
+// three times: the ladder's two (locate_scaled_impl), and once for the sums of the stage.
+int locate_free_impl(ssw_ctx* ctx, const uint8_t* dev_base, size_t w, size_t h, const void* const* dev_suspects,
+                     const std::vector<ssw_placement>& pl, const uint32_t* ranges, const uint32_t* slack, ScaledAnswer* out) {
+    std::vector<ScaledAnswer> a0(pl.size());
+    SSW_TRY(locate_scaled_impl(ctx, dev_base, w, h, dev_suspects, pl, ranges, a0.data()));
+    return free_stage(ctx, dev_base, w, h, dev_suspects, pl, ranges, slack, a0.data(), out, nullptr);
 }
 
 }  // namespace host
@@ -314,5 +334,28 @@ extern "C" int ssw_locate_free_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, s
         placements[i].x = ans[i].x; placements[i].y = ans[i].y;
         host_sad[i] = ans[i].sad;
     }
+    return SSW_OK;
+}
+
+extern "C" int ssw_locate_free_sums_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, size_t h, const void* dev_suspect, size_t sw, size_t sh,
+                                         size_t channels, const uint32_t start[4], uint32_t wmin, uint32_t wmax, uint32_t slack, uint64_t* host_sums,
+                                         ssw_placement* answer, uint64_t* host_sad) {
+    using namespace ssw::host;
+    if (!ctx || !dev_base_rgb || !dev_suspect || !start || !host_sums || !answer || !host_sad) return SSW_ERR_BAD_ARG;
+    if (w == 0 || h == 0 || w > 0xFFFFFFFFull || h > 0xFFFFFFFFull) return SSW_ERR_BAD_ARG;
+    if ((channels != 3 && channels != 4) || sw == 0 || sh == 0 || sh > 0xFFFFFFFFull || (uint64_t)sw * channels > 0xFFFFFFFFull) return SSW_ERR_BAD_ARG;
+    if (slack < 1 || slack > ssw::FREE_SLACK_MAX || wmin > wmax) return SSW_ERR_BAD_ARG;
+    if (start[0] == 0 || start[1] == 0 || start[0] > w || start[1] > h || start[2] > w - start[0] || start[3] > h - start[1]) return SSW_ERR_BAD_ARG;
+    CtxGuard g(ctx);
+    ssw_placement p{};
+    p.w = (uint32_t)sw; p.h = (uint32_t)sh; p.channels = (uint32_t)channels;
+    const std::vector<ssw_placement> pl(1, p);
+    const uint32_t range[2] = {wmin, wmax};
+    const ScaledAnswer a0{start[0], start[1], start[2], start[3], 0};
+    ScaledAnswer ans{};
+    SSW_TRY(free_stage(ctx, dev_base_rgb, w, h, &dev_suspect, pl, range, &slack, &a0, &ans, host_sums));
+    p.pw = ans.pw; p.ph = ans.ph; p.x = ans.x; p.y = ans.y;
+    *answer = p;
+    *host_sad = ans.sad;
     return SSW_OK;
 }

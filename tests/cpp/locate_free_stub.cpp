@@ -45,4 +45,22 @@ int ssw_locate_free_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, si
     }
     return SSW_OK;
 }
+
+// the diagnostic beside it: the argument checks of include/ssw.h; reads the original, the suspect and the start; nothing is
+// scored, so every slot holds all ones and the answer is the start with SAD 0
+int ssw_locate_free_sums_rgb8(ssw_ctx* ctx, const uint8_t* dev_base_rgb, size_t w, size_t h, const void* dev_suspect, size_t sw, size_t sh,
+                              size_t channels, const uint32_t start[4], uint32_t wmin, uint32_t wmax, uint32_t slack, uint64_t* host_sums,
+                              ssw_placement* answer, uint64_t* host_sad) {
+    if (g_fail != SSW_OK) { const int s = g_fail; g_fail = SSW_OK; return s; }
+    if (!ctx || !dev_base_rgb || !dev_suspect || !start || !host_sums || !answer || !host_sad || w == 0 || h == 0) return SSW_ERR_BAD_ARG;
+    if ((channels != 3 && channels != 4) || sw == 0 || sh == 0 || slack < 1 || slack > 4 || wmin > wmax) return SSW_ERR_BAD_ARG;
+    if (start[0] == 0 || start[1] == 0 || start[0] > w || start[1] > h || start[2] > w - start[0] || start[3] > h - start[1]) return SSW_ERR_BAD_ARG;
+    for (size_t b = 0; b < w * h * 3; ++b) g_sum = g_sum * 31 + dev_base_rgb[b];
+    for (size_t b = 0; b < sw * sh * channels; ++b) g_sum = g_sum * 31 + static_cast<const uint8_t*>(dev_suspect)[b];
+    const size_t side = 2 * (size_t)slack + 1;
+    for (size_t i = 0; i < side * side * 81; ++i) host_sums[i] = UINT64_MAX;
+    *answer = ssw_placement{(uint32_t)sw, (uint32_t)sh, (uint32_t)channels, start[2], start[3], start[0], start[1]};
+    *host_sad = 0;
+    return SSW_OK;
+}
 }
